@@ -4,8 +4,13 @@ BASELINE.json configuration "512^3 density, 1024x1024, 1024 spp progressive" (co
 driver's N>1 runs are configs[3]: the same job sharded by 8x8-pixel tile over N GPUs with an RCCL
 reduce of the accumulated radiance buffer).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times K steps and prints the line (value, ms_per_step, the roofline from the timed launches'
+own counters); --dump-outputs DIR writes the frame of the last timed step as .npy files.  --full adds everything else:
+the rocprofv3 --pmc child runs, measured ceilings and working set of the roofline, the progressive and DELTA legs, the CPU
+baseline, the input's density statistics and the frame's SHA-256.
 
 A "step" = the 1024-spp job of BASELINE.json configs[2]/[3]: --spp-per-step (default 1024) subframes of the whole
 frame, whatever N is ("scaling": "strong" -- rank r renders its 1/N of the 8x8-pixel tiles for all 1024 subframes):
@@ -78,6 +83,14 @@ def parse_args():
                          "frame_sha256 as the torchrun path's, so the two merged frames can be compared")
     ap.add_argument("--sync-steps", action="store_true",
                     help="wait for every step before the next one is enqueued (no path continuation across launches)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the rocprofv3 --pmc child runs, the measured ceilings and the working set "
+                         "of the roofline, the progressive and DELTA legs, the CPU baseline, the input's density statistics and the "
+                         "frame's SHA-256 (the --no-* options above still drop single legs).  Without it a run sets up, warms up, "
+                         "times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame of the last timed step ([mean | M2], what ct_download hands a caller) to DIR/<name>.npy "
+                         "as float32, a fixed seeded sample of its pixels when the whole frame exceeds 64 MB")
     return ap.parse_args()
 
 
@@ -458,6 +471,27 @@ def frame_sha256(mean, m2):
     return hashlib.sha256(np.ascontiguousarray(mean).tobytes() + np.ascontiguousarray(m2).tobytes()).hexdigest()
 
 
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def write_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: each [H, W, 4] frame buffer of `arrays` as out_dir/<name>.npy (float32).  When they exceed `budget`
+    together, the same fixed seeded sample of pixels is taken from every buffer ([k, 4] each, pixels in raster order) and
+    the sampled flat pixel indices go beside them as sample_pixel_index.npy (float64, exact)."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    if sum(a.nbytes for a in arrays.values()) > budget:
+        h, w, c = next(iter(arrays.values())).shape
+        per_pixel = 4 * c * len(arrays) + 8
+        n = min(h * w, (budget - 4096) // per_pixel)   # (4096: room for the .npy headers)
+        idx = np.sort(np.random.default_rng(0).choice(h * w, size=n, replace=False))
+        arrays = {k: v.reshape(h * w, c)[idx] for k, v in arrays.items()}
+        arrays["sample_pixel_index"] = idx.astype(np.float64)
+    for k, v in arrays.items():
+        np.save(out / f"{k}.npy", v)
+
+
 def group_main(args):
     """bench.py --gpus N --group: the fixed 1024-spp job on N devices driven by ONE process through ct_group_* (csrc/ct_group.hip:
     one handle per device, RCCL by ncclCommInitAll, ct_group_merge = one ncclReduce of [mean | M2] per device inside a group call).
@@ -485,7 +519,9 @@ def group_main(args):
         merge_s += time.perf_counter() - t1
         nxt += S
     elapsed = time.perf_counter() - t0
-    mean, m2 = g.mean(), g.m2()
+    mean, m2 = (g.mean(), g.m2()) if (args.full or args.dump_outputs) else (None, None)
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, {"mean": mean, "m2": m2})
     c = g.counters()
     out = {
         "metric": "Msamples/s (rays x spp) at 512^3 vol, 1024^2 frame; HBM GB/s vs roofline",
@@ -499,9 +535,11 @@ def group_main(args):
                    "pipelined_steps": False},
         "multi_gpu": {"implementation": "ct_group (csrc/ct_group.hip)", "devices": devices, "merge_ms_per_step": merge_s / args.steps * 1e3},
         "roofline": None, "cpu_baseline": None, "setup_s": setup_s,
-        "frame_sha256": frame_sha256(mean, m2), "subframes_in_the_frame": nxt - 1,
+        "subframes_in_the_frame": nxt - 1,
         "counters": c,
     }
+    if args.full:
+        out["frame_sha256"] = frame_sha256(mean, m2)
     g.close()
     print(json.dumps(out), flush=True)
 
@@ -517,6 +555,9 @@ def main():
         if world == 1 and args.gpus > 1:
             raise SystemExit("launch N>1 with: python -m torch.distributed.run --nproc-per-node N bench.py --gpus N")
         args.gpus = world
+    if not args.full:
+        # a plain run times the headline and nothing else: no PMC child runs, no cadence, DELTA or CPU legs
+        args.no_pmc_traffic = args.no_cpu_baseline = args.no_delta_leg = args.no_progressive_leg = True
 
     if "rocprof" in os.environ.get("LD_PRELOAD", "") and not os.environ.get("CT_BENCH_ALL_LEGS"):
         # under a profiler (tools/gpu_pmc_*.sh, gpu_timeline.sh run this command behind rocprofv3) only the headline's launches
@@ -678,7 +719,7 @@ def main():
             except Exception:
                 traffic = None
     here = {}
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         try:
             here = measured_ceilings(torch, local_rank)
         except Exception:
@@ -707,7 +748,7 @@ def main():
         "frac_of_line_fill_rate_of_a_1_GiB_set": lines_per_s / by_set[1024] if (lines_per_s and by_set.get(1024)) else None,
         "resident_lanes": resident_lanes, "lane_occupancy": lane_occ,
         "lane_occupancy_source": "SQ_THREAD_CYCLES_VALU / (64 SQ_ACTIVE_INST_VALU) of the timed launch, rocprofv3 --pmc child run of this command" if lane_occ else
-                                 "not measured in this run (no profiler, N > 1 or --no-pmc-traffic)",
+                                 "not measured in this run (no --full, no profiler, N > 1 or --no-pmc-traffic)",
         "miss_latency_ns_idle_chip": {"infinity_cache_hit": mall_hit_ns, "hbm": hbm_miss_ns},
         "littles_law_ceiling_lines_per_s": resident_lanes * lane_occ / (hbm_miss_ns * 1e-9) if (resident_lanes and lane_occ) else None,
         "frac_of_littles_law_ceiling": lines_per_s / (resident_lanes * lane_occ / (hbm_miss_ns * 1e-9)) if (lines_per_s and resident_lanes and lane_occ) else None,
@@ -725,7 +766,7 @@ def main():
         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
         "achieved_is": "max(issued bytes, PMC traffic) per launch / average launch duration; the traffic is bytes across the L2's memory side, "
                        "so Infinity-Cache hits are inside it: an upper bound on HBM bytes.  frac = traffic_frac; useful_frac is what the kernel asked for" if traffic else
-                       "issued bytes only: no PMC traffic was measured in this run (N > 1, --no-pmc-traffic or no profiler); the "
+                       "issued bytes only: no PMC traffic was measured in this run (no --full, N > 1, --no-pmc-traffic or no profiler); the "
                        "traffic-based fraction is on the N = 1 line",
         "traffic": traffic, "traffic_source": traffic_source,
         "useful_frac": useful_GBps / HBM_PEAK_GBS,        # 8 B per footprint the kernel loaded + 16 B per sample written
@@ -795,9 +836,10 @@ def main():
                         "(Mie multi-scatter + NEE), estimator "
                         f"{('MARCH (reference-faithful)', 'DELTA (Woodcock, LDS-resident majorant cells)')[args.estimator]}, max_depth 2000",
             "volume": args.volume, "width": W, "height": H, "spp_per_step": S,
-            # the synthetic input's value distribution
-            "density_stats": {"nonzero_fraction": float((tex > 0).mean()), "mean": float(tex.mean()), "max": int(tex.max()),
-                              "histogram_16_bins": [int(v) for v in np.bincount(tex.reshape(-1) >> 4, minlength=16)]},
+            # the synthetic input's value distribution (--full: a pass over the whole volume)
+            **({"density_stats": {"nonzero_fraction": float((tex > 0).mean()), "mean": float(tex.mean()), "max": int(tex.max()),
+                                  "histogram_16_bins": [int(v) for v in np.bincount(tex.reshape(-1) >> 4, minlength=16)]}}
+               if args.full else {}),
             # bytes of the volume's representations on the device (ct_debug_memory; "sparse": 0 dense march bricks, 1 row extents,
             # 2 dense addressing with sparse backing -- march_bricks_stored is then the memory behind the addresses)
             "volume_memory": tr.debug_memory(),
@@ -814,11 +856,16 @@ def main():
     if rank == 0:
         # the merged frame the timed steps produced ([mean | M2] after `subframes_in_the_frame` subframes): equal, bit for bit, to
         # the frame of `bench.py --gpus N --group` with the same --steps / --warmup, and to the N = 1 frame
-        if world > 1:
-            fm = st.merged.cpu().numpy()
-            out["frame_sha256"] = frame_sha256(fm[0], fm[1])
-        else:
-            out["frame_sha256"] = frame_sha256(tr.mean(), tr.m2())
+        if args.full or args.dump_outputs:
+            if world > 1:
+                fm = st.merged.cpu().numpy()
+                mean, m2 = fm[0], fm[1]
+            else:
+                mean, m2 = tr.mean(), tr.m2()
+            if args.dump_outputs:
+                write_outputs(args.dump_outputs, {"mean": mean, "m2": m2})
+            if args.full:
+                out["frame_sha256"] = frame_sha256(mean, m2)
         out["subframes_in_the_frame"] = nxt - 1
     if rank == 0 and world == 1 and not args.simple_kernel and not args.no_progressive_leg and not args.sync_steps:
         prog, nxt = progressive_leg(tr, W, H, nxt)

@@ -153,8 +153,8 @@ def test_bench_group_mode_and_torchrun_mode_produce_the_same_frame():
     hashes must equal each other and the N = 1 frame's -- the comparison the driver's 8-GPU node can repeat on RCCL."""
     import json
     import subprocess
-    common = ["--steps", "2", "--warmup", "1", "--volume", "64", "--width", "128", "--height", "96", "--spp-per-step", "24", "--no-cpu-baseline",
-              "--no-pmc-traffic", "--no-delta-leg", "--no-progressive-leg"]
+    common = ["--steps", "2", "--warmup", "1", "--volume", "64", "--width", "128", "--height", "96", "--spp-per-step", "24", "--full",
+              "--no-cpu-baseline", "--no-pmc-traffic", "--no-delta-leg", "--no-progressive-leg"]
     port = 29800 + (os.getpid() % 90)
     cmds = {
         "single": [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", *common],

@@ -3,8 +3,8 @@
 #   gpurun -- 'bash tools/gpu_configs_bench.sh <tag>'
 cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/${1:-configs}; mkdir -p "$OUT"
-python bench.py --volume 256 --width 512 --height 512 --steps 8 --no-cpu-baseline > "$OUT/bench_c1.json" 2> "$OUT/bench_c1.err" || { tail -3 "$OUT/bench_c1.err"; exit 1; }
-CT_SCRATCH_GIB=32 python bench.py --volume 1024 --width 2048 --height 2048 --spp-per-step 512 --steps 2 --no-cpu-baseline > "$OUT/bench_c4.json" 2> "$OUT/bench_c4.err" || { tail -3 "$OUT/bench_c4.err"; exit 1; }
+python bench.py --full --volume 256 --width 512 --height 512 --steps 8 --no-cpu-baseline > "$OUT/bench_c1.json" 2> "$OUT/bench_c1.err" || { tail -3 "$OUT/bench_c1.err"; exit 1; }
+CT_SCRATCH_GIB=32 python bench.py --full --volume 1024 --width 2048 --height 2048 --spp-per-step 512 --steps 2 --no-cpu-baseline > "$OUT/bench_c4.json" 2> "$OUT/bench_c4.err" || { tail -3 "$OUT/bench_c4.err"; exit 1; }
 python - "$OUT" <<'PY'
 import json, sys
 for f in ("bench_c1", "bench_c4"):

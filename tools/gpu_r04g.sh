@@ -13,7 +13,7 @@ print("1024^3 MARCH CT_SPARSE", sys.argv[2], round(d["value"], 1), "Msamples/s",
       round(m["march_bricks_stored"] / 1e9, 3), "GB stored of", round(m["march_bricks_dense"] / 1e9, 3), "GB; setup", round(d["setup_s"], 1), "s")
 PY
 done
-timeout -k 10 400 python bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"; echo "default bench rc=$?" | tee -a "$OUT/summary.log"
+timeout -k 10 400 python bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"; echo "default bench rc=$?" | tee -a "$OUT/summary.log"
 python - "$OUT/bench_default.json" <<'PY' | tee -a "$OUT/summary.log"
 import json, sys
 d = json.load(open(sys.argv[1])); r = d["roofline"]

@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
 OUT=gpurun_out/r04z; mkdir -p "$OUT"
 timeout -k 10 600 python -m pytest tests/test_gpu_parity.py -q -m gpu -x -k "delta or knobs or differential" > "$OUT/tests_delta.log" 2>&1; echo "delta tests rc=$?"; tail -2 "$OUT/tests_delta.log"
 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1; echo "smoke rc=$?"; tail -1 "$OUT/smoke.log"
-( time python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" ) 2>&1 | grep real; echo "bench rc=$?"
+( time python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" ) 2>&1 | grep real; echo "bench rc=$?"
 python - "$OUT/bench.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); r = d["roofline"]

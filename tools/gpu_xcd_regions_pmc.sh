@@ -6,7 +6,7 @@ cd "$GRAFT_REPO_ROOT" 2>/dev/null || true
 OUT=gpurun_out/${1:-r03s}
 mkdir -p "$OUT"
 for R in ${REGIONS:-8 16 64}; do
-  CT_XCD_QUEUES=1 CT_XCD_REGIONS=$R timeout -k 10 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-delta-leg --no-progressive-leg > "$OUT/bench_xcd_regions_$R.json" 2> /dev/null || { echo "regions $R FAILED"; continue; }
+  CT_XCD_QUEUES=1 CT_XCD_REGIONS=$R timeout -k 10 400 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-delta-leg --no-progressive-leg > "$OUT/bench_xcd_regions_$R.json" 2> /dev/null || { echo "regions $R FAILED"; continue; }
   python3 - "$OUT/bench_xcd_regions_$R.json" $R <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1]); r = d["roofline"]

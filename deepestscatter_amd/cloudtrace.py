@@ -435,6 +435,20 @@ class CloudTracer:
         return {"cell": int(out[0]), "stored": tuple(int(v) for v in out[1:4]), "origin": tuple(int(v) for v in out[4:7]),
                 "nee": int(out[7] & 0xff), "interior": bool(out[7] & 0x100)}
 
+    def march_meta(self) -> dict:
+        """The march bricks' row meta bytes (ct_debug_march_meta): "meta"[z, y, bx] is the byte of the row of base texels
+        x = 3 bx - bias_x .. +2, y - bias, z - bias (dense bricks; None when sparse)."""
+        geom = np.zeros(8, np.uint32)
+        check(self.L.ct_debug_march_meta(self.h, _p(geom), C.c_void_p(), 0), self.h)
+        d = {"radius": int(geom[0]), "bias_x": int(geom[1]), "bias": int(geom[2]),
+             "bricks": tuple(int(v) for v in geom[3:6]), "sparse": bool(geom[6]), "meta": None}
+        if not d["sparse"]:
+            gx, gy, gz = d["bricks"]
+            meta = np.zeros((gz * 4, gy * 4, gx), np.uint8)
+            check(self.L.ct_debug_march_meta(self.h, _p(geom), _p(meta), meta.size), self.h)
+            d["meta"] = meta
+        return d
+
     def kernel_time(self):
         """-> (estimator kernel ms, accumulate kernel ms, estimator launches) since create/reset."""
         a, b, n = C.c_double(0), C.c_double(0), C.c_uint64(0)
@@ -457,12 +471,15 @@ class CloudTracer:
         # running after they had found the job queue empty (0.5 ms bins)
         d["wave_end_hist_5ms"] = [int(v) for v in out[16:40]]
         d["wave_end_minus_drained_hist_0p5ms"] = [int(v) for v in out[40:64]]
-        ex = np.zeros(72, np.uint64)
-        check(self.L.ct_debug_stats_ex(self.h, _p(ex), 72), self.h)
+        ex = np.zeros(73, np.uint64)
+        check(self.L.ct_debug_stats_ex(self.h, _p(ex), 73), self.h)
         # of the march fetches: the lane's previous fetch was in the same 128-B brick line / a lower lane of the wave
         # fetches the same line in the same instruction (what a brick cache in LDS could find: DESIGN.md 4.3)
         d["march_fetch_same_line_as_lanes_previous"] = int(ex[68])
         d["march_fetch_line_shared_with_a_lower_lane"] = int(ex[69])
+        # of the NEE lookups (MARCH): those whose footprint was known to be zero (shadow-zero row) and not loaded; they are
+        # counted in nee_footprints_reused too
+        d["nee_lookups_skipped_shadow_zero"] = int(ex[72])
         d["raw"] = [int(v) for v in out]
         d["watchdog"] = int(out[63])     # exchange kernels: waves that gave up on a bounded wait (must be 0)
         return d

@@ -70,6 +70,7 @@ struct CtHandle_ {
     uint2 *d_mrows = nullptr;          // sparse march bricks: extent of every brick row (DevScene::m_rows)
     uint8_t *d_mcoarse = nullptr;      // ... and the clearance of the coarse cells outside the extents
     size_t mbricks_dense_bytes = 0, mbricks_bytes = 0;
+    int nee_skip_r = 0;   // radius of the march bricks' shadow-zero flags (0: none set)
     // CT_FLAG_VMM_BRICKS: d_mbricks is a reserved virtual range (not a hipMalloc), backed chunk by chunk
     struct VmmBricks {
         void *va = nullptr;
@@ -354,6 +355,45 @@ static void build_guide(const std::vector<float> &cdf, std::vector<uint16_t> &gu
         guide[b] = (uint16_t)t;
     }
     guide[kGuideN + 1] = guide[kGuideN];
+}
+
+// ---- shadow-zero rows (DevScene::mbricks bit 6, DevScene::nee_reach; launch_nee_skip_flags) ---------------------------------
+// render_persistent_kernel skips the NEE of a collision whose march-brick row has bit 6 set and whose back-off
+// t = fl(lg * inv) is <= nee_reach.  Its scatter position is pos_s = fl(pos - fl(fl(dir * lg) * inv)), |dir_a| <= 1 + 2^-22, so
+// per axis |pos - pos_s| <= lg * inv * (1 + 2^-20) <= nee_reach * (1 + 2^-20) plus the rounding of the subtraction, and in texel
+// coordinates f = fl(fma(p, s_a, -0.5)) the two positions differ by at most
+//     D_a = nee_reach * s_a * (1 + 2^-20) + 2^-22 * (s_a + 1)
+// (three roundings of magnitude <= 2^-24 * (1.1 s_a + 0.5): |p| <= 1.1 wherever a collision happens, the box being at most
+// [-0.01, 1.01]).  Integers floor(f_c) - floor(f_s) < D_a + 1, so the NEE's base texel is within ceil(D_a) of the collision's
+// on every axis: the radius r of the flag.  The back-off lg / density is at most one step up to rounding, but that rounding is
+// unbounded relative to a tiny density * step (T's last bits); nee_reach is a little under one step, so that at one texel per
+// step -- the benchmark's setting -- r is 1, and the few back-offs beyond it (about 0.4 % of the collisions, and the rare
+// long ones) evaluate their NEE.
+constexpr int kNeeSkipMaxR = 8;   // beyond this the flags are left clear (the distance transform's cost grows with r)
+
+static float nee_skip_reach(const DevScene &d)
+{
+    return d.sample_step * (1.0f - 1.0f / 256.0f);
+}
+
+// The flags' radius in texels, or 0: no skip.  The skip needs in_scattering_finish of a zero footprint to be +-0 (finite light,
+// sun ratio and phase tables) -- rad + (+-0) is rad then, rad never being -0.
+static int nee_skip_radius(const DevScene &d, bool mie_finite)
+{
+    if (!mie_finite || !std::isfinite(d.lr) || !std::isfinite(d.lg) || !std::isfinite(d.lb) || !std::isfinite(d.sun_ratio) ||
+        !(d.sample_step > 0.0f) || !std::isfinite(d.sample_step)) {
+        return 0;
+    }
+    const double reach = (double)nee_skip_reach(d);
+    int r = 0;
+    for (const float s : { d.sx, d.sy, d.sz }) {
+        const double D = reach * s * (1.0 + std::ldexp(1.0, -20)) + std::ldexp(1.0, -22) * (s + 1.0);
+        if (!(D < kNeeSkipMaxR)) {
+            return 0;
+        }
+        r = std::max(r, (int)std::ceil(D));
+    }
+    return std::max(r, 1);
 }
 
 static uint32_t morton2(uint32_t x, uint32_t y)
@@ -826,6 +866,10 @@ static int create_impl(const CtScene *s, CtHandle h)
     HIPCHK(h, hipMemcpyAsync(h->d_guide, guide.data(), (kGuideN + 2) * sizeof(uint16_t), hipMemcpyHostToDevice,
                              h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream)); // the vectors die at scope exit
+    bool mie_finite = true;   // (nee_skip_radius)
+    for (int i = 0; i < kMieN; i++) {
+        mie_finite = mie_finite && std::isfinite(mie_tex[i]) && std::isfinite(chopped_tex[i]);
+    }
     d.mie = h->d_mie;
     d.chopped = h->d_chopped;
     d.cdf = h->d_cdf;
@@ -1031,6 +1075,19 @@ static int create_impl(const CtScene *s, CtHandle h)
         if (e == hipSuccess) {
             e = launch_build_bricks(h->d_inscatter, nx, ny, nz, bbias, (int)bgx, (int)bgy, (int)bgz, h->d_ibricks, h->stream);
         }
+        uint8_t *tmp_c = nullptr;
+        const int nee_r = s->estimator == CT_EST_MARCH ? nee_skip_radius(d, mie_finite) : 0;
+        if (e == hipSuccess && nee_r > 0) {
+            // shadow-zero rows (bit 6 of the march bricks' meta bytes): written after the shadow volume, whose march reads the
+            // bricks, and before the sparse compaction below, which copies them.  tmp_b keeps the distance volume for it.
+            e = hipMalloc(&tmp_c, texels);
+            if (e == hipSuccess) {
+                e = launch_nee_skip_flags(h->d_inscatter, nx, ny, nz, nee_r, mbias, bbias, (int)mgx, (int)bgy, (int)bgz, tmp_a, tmp_c,
+                                          h->d_mbricks, h->stream);
+                d.nee_reach = nee_skip_reach(d);
+                h->nee_skip_r = nee_r;
+            }
+        }
         if (e == hipSuccess && s->estimator == CT_EST_DELTA && d.delta_nee == 2u) {
             // twin bricks (DevScene::tbricks): density and shadow volume of 3^3 base texels in one line, over the texel range
             // of the apron bricks (which is that of the majorant cells: every position a flight can reach)
@@ -1141,6 +1198,9 @@ static int create_impl(const CtScene *s, CtHandle h)
         }
         hipFree(tmp_a);
         hipFree(tmp_b);
+        if (tmp_c) {
+            hipFree(tmp_c);
+        }
         HIPCHK(h, e);
         HIPCHK(h, e2);
         if (src != CT_OK) {
@@ -3313,6 +3373,47 @@ extern "C" int ct_debug_delta_grid(CtHandle h, uint32_t out[8])
     out[5] = delta ? (uint32_t)d.mc_y0 : 0u;
     out[6] = delta ? (uint32_t)d.mc_z0 : 0u;
     out[7] = delta ? (d.delta_nee | (d.delta_interior ? 0x100u : 0u)) : 0u;
+    return CT_OK;
+}
+
+extern "C" int ct_debug_march_meta(CtHandle h, uint32_t geom_out[8], uint8_t *meta_out, size_t capacity)
+{
+    NEED(h);
+    if (!geom_out) {
+        return fail(h, CT_E_INVAL, "geom_out is NULL");
+    }
+    const DevScene &d = h->dev;
+    const size_t rows = (size_t)d.m_gx * d.brick_gy * d.brick_gz * 16;
+    geom_out[0] = (uint32_t)h->nee_skip_r;
+    geom_out[1] = (uint32_t)d.m_bias_x;
+    geom_out[2] = (uint32_t)d.brick_bias;
+    geom_out[3] = (uint32_t)d.m_gx;
+    geom_out[4] = (uint32_t)d.brick_gy;
+    geom_out[5] = (uint32_t)d.brick_gz;
+    geom_out[6] = d.m_rows ? 1u : 0u;
+    geom_out[7] = 0u;
+    if (!meta_out) {
+        return CT_OK;
+    }
+    if (d.m_rows || h->mbricks_bytes != rows * 8 || capacity < rows) {
+        return fail(h, CT_E_INVAL, "ct_debug_march_meta: dense march bricks in ordinary memory only, capacity >= %zu", rows);
+    }
+    std::vector<uint8_t> bricks(h->mbricks_bytes);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(bricks.data(), h->d_mbricks, bricks.size(), hipMemcpyDeviceToHost));
+    const size_t gx = (size_t)d.m_gx, gy = (size_t)d.brick_gy, gz = (size_t)d.brick_gz;
+    for (size_t bz = 0; bz < gz; bz++) {
+        for (size_t by = 0; by < gy; by++) {
+            for (size_t bx = 0; bx < gx; bx++) {
+                const uint8_t *b = bricks.data() + (((bz * gy + by) * gx + bx) << 7);
+                for (size_t lz = 0; lz < 4; lz++) {
+                    for (size_t ly = 0; ly < 4; ly++) {
+                        meta_out[((bz * 4 + lz) * gy * 4 + by * 4 + ly) * gx + bx] = b[lz * 25 + ly * 5 + 4];
+                    }
+                }
+            }
+        }
+    }
     return CT_OK;
 }
 

@@ -113,7 +113,9 @@ struct DevScene {
     // (every footprint based within Chebyshev distance c of any of them is all zero and every such
     // position passes isInBox; texel-granular, so rows inside partly filled bricks get one too),
     // bit 7 = "interior" for the row's bases (1 <= base <= N-3 on every axis: isInBox holds for
-    // every position based there and for a scatter position backed off from it).
+    // every position based there and for a scatter position backed off from it).  The clearance is bits 0-5 (capped at 63);
+    // bit 6 = "shadow-zero": every shadow-volume footprint based within nee_skip_r texels of the row's bases is all zero
+    // (set in rows of clearance 0 only, after the shadow volume is built: launch_nee_skip_flags).
     const uint8_t *mbricks;
     // Sparse march bricks (CT_FLAG_SPARSE_BRICKS / CT_SPARSE=1): of every brick row (by, bz) only the bricks
     // between its first and its last one that holds a non-zero texel are stored, one row after the other.
@@ -176,6 +178,8 @@ struct DevScene {
     uint32_t burst_idle;   // ... this many lanes are idle)
     uint32_t tail_burst;   // march steps per visit once the job queue is empty
     uint32_t nee_cache;    // 1 = fetch_cell_cached may reuse a lane's last shadow-volume footprint (fewer than 2^25 bricks)
+    float nee_reach;       // a collision in a shadow-zero row whose back-off lg / density is <= this skips its NEE (0: never;
+                           // ct_api.cpp derives the flags' radius from it)
     uint32_t hint_period;  // scheduler visits between two looks at the job counter (power of two, 0 = never)
     uint32_t burst_march_min; // a burst also ends when fewer lanes than this still march (>= 1)
     uint32_t scatter_num, scatter_den; // run the scatter phase when nb * den > nm * num ...
@@ -463,7 +467,9 @@ CT_DEV uint2 combine_twin(const RawCell &r)
 // free path apart, which at the reference's settings is about a texel, so the shadow-volume footprint of the next
 // event is often the one just read.  `key` = the footprint's byte offset in the brick array (0xffffffff = empty);
 // the volumes are immutable, so an entry never goes stale and may outlive the path that loaded it.
-CT_DEV uint2 fetch_cell_cached(const DevScene &sc, const uint8_t *bricks, f3 p, uint32_t &key, uint2 &cached, bool &reused)
+// zero = true: the footprint is known to be all zero (a shadow-zero row): nothing is loaded, the entry stays as it was.
+CT_DEV uint2 fetch_cell_cached(const DevScene &sc, const uint8_t *bricks, f3 p, uint32_t &key, uint2 &cached, bool &reused,
+                               bool zero = false)
 {
     const float fx = fmaf(p.x, sc.sx, -0.5f), fy = fmaf(p.y, sc.sy, -0.5f), fz = fmaf(p.z, sc.sz, -0.5f);
     const uint32_t x = (uint32_t)(floor_to_int(fx) + sc.brick_bias), y = (uint32_t)(floor_to_int(fy) + sc.brick_bias),
@@ -472,7 +478,7 @@ CT_DEV uint2 fetch_cell_cached(const DevScene &sc, const uint8_t *bricks, f3 p, 
     const uint32_t local = __umul24(z & 3u, 25u) + __umul24(y & 3u, 5u) + (x & 3u);
     const uint32_t off = (brick << 7) | local;   // unique while there are fewer than 2^25 bricks: DevScene::nee_cache
     reused = sc.nee_cache != 0u && off == key;
-    if (!reused) {
+    if (!reused && !zero) {
         const uint8_t *q = bricks + (((size_t)brick << 7) | local);
         uint2 a, c;
         __builtin_memcpy(&a, q, 8);
@@ -481,7 +487,7 @@ CT_DEV uint2 fetch_cell_cached(const DevScene &sc, const uint8_t *bricks, f3 p, 
         cached.y = __builtin_amdgcn_perm(c.y, c.x, 0x06050100u);
         key = off;
     }
-    return cached;
+    return zero ? make_uint2(0u, 0u) : cached;
 }
 
 template <bool SPARSE>

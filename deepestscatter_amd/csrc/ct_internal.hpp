@@ -12,7 +12,7 @@ constexpr int kTile = 8;            // pixel tile edge: 8x8 = one wave of primar
 constexpr int kCounterCount = 9;    // paths, box_hits, density, inscatter, scatter, capped (the algorithm's, = the oracle's);
                                     // then what the kernels ISSUED: density fetches, shadow-volume fetches (ct_fetch_counters),
                                     // and the samples the accumulate kernels found without alpha == 1 (ct_debug_invariants)
-constexpr int kStatCount = 72;      // scheduler diagnostics (ct_debug_stats): [0,64) as before, [64,68) path conservation
+constexpr int kStatCount = 73;      // scheduler diagnostics (ct_debug_stats): [0,64) as before, [64,68) path conservation
                                     // (samples dealt, paths resumed, results written, paths suspended; STATS kernels only)
 constexpr int kContWords = 16;      // words of a suspended path (render_persistent_kernel)
 constexpr int kContWordsDelta = 32; // the same for render_delta_kernel (its DDA state rides along)
@@ -142,6 +142,8 @@ hipError_t launch_mbrick_chunk_quantize(uint8_t *chunk, int64_t chunk_bytes, hip
 #endif
 hipError_t launch_mbrick_extent(const uint8_t *bricks, int gx, int gy, int gz, uint32_t *row_x0, uint32_t *row_x1, hipStream_t stream);
 hipError_t launch_mbrick_compact(const uint8_t *dense, int gx, int gy, int gz, const uint2 *rows, uint8_t *compact, hipStream_t stream);
+hipError_t launch_nee_skip_flags(const uint8_t *shadow, int nx, int ny, int nz, int r, int bias_x, int bias, int gx, int gy,
+                                 int gz, uint8_t *tmp_a, uint8_t *tmp_c, uint8_t *bricks, hipStream_t stream);
 hipError_t launch_coarse_clearance(const uint8_t *dist, int nx, int ny, int nz, int bias, int cshift, int cgx, int cgy, int cgz,
                                    uint8_t *out, hipStream_t stream);
 hipError_t launch_render_delta(const DevScene &sc, const BatchArgs &ba, LaunchShape shape, hipStream_t stream);

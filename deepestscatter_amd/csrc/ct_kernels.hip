@@ -105,7 +105,8 @@ hipError_t launch_build_bricks(const uint8_t *texels, int nx, int ny, int nz, in
 // =============================================================================================
 // march bricks (DevScene::mbricks): texel-granular clearance + 3x4x4 bricks with a meta byte per row
 // =============================================================================================
-constexpr int kClearMax = 127;
+// A row's meta byte: bit 7 "interior", bit 6 "shadow-zero" (set afterwards by launch_nee_skip_flags), bits 0-5 the clearance.
+constexpr int kClearMax = 63;
 
 // blocked[b] = 1 when a march step may not be skipped at base texel b: the footprint based there
 // has a non-zero texel, or b is not "interior" (1 <= b <= N-3 on every axis).
@@ -133,8 +134,9 @@ __global__ void blocked_mask_kernel(const uint8_t *__restrict__ t, int nx, int n
 //   pass 1, 2: out = min over k of max(k, in[.. -+ k ..]).
 // Everything outside the grid counts as blocked.  The scan walks outwards and stops at the first k
 // that cannot improve the result, so its cost is proportional to the distance found.
+// Distances are capped at cap + 1.
 template <int AXIS>
-__global__ void cheb_pass_kernel(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, int nx, int ny, int nz)
+__global__ void cheb_pass_kernel(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, int nx, int ny, int nz, int cap)
 {
     const int64_t total = (int64_t)nx * ny * nz;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -142,9 +144,9 @@ __global__ void cheb_pass_kernel(const uint8_t *__restrict__ in, uint8_t *__rest
         const int c = AXIS == 0 ? x : (AXIS == 1 ? y : z);
         const int n = AXIS == 0 ? nx : (AXIS == 1 ? ny : nz);
         const int64_t stride = AXIS == 0 ? 1 : (AXIS == 1 ? (int64_t)nx : (int64_t)nx * ny);
-        int best = kClearMax + 1;
+        int best = cap + 1;
         for (int k = 0; k < best; k++) {
-            int v = AXIS == 0 ? (kClearMax + 1) : 0; // value at an out-of-grid neighbour: blocked
+            int v = AXIS == 0 ? (cap + 1) : 0; // value at an out-of-grid neighbour: blocked
             bool hit = false;
             if (c - k >= 0) {
                 const int a = in[i - k * stride];
@@ -157,7 +159,7 @@ __global__ void cheb_pass_kernel(const uint8_t *__restrict__ in, uint8_t *__rest
                 hit = true;
                 v = 0;
             }
-            int w = AXIS == 0 ? (kClearMax + 1) : 0;
+            int w = AXIS == 0 ? (cap + 1) : 0;
             if (c + k < n) {
                 const int a = in[i + k * stride];
                 if (AXIS == 0) {
@@ -177,7 +179,7 @@ __global__ void cheb_pass_kernel(const uint8_t *__restrict__ in, uint8_t *__rest
                 best = min(best, max(k, min(v, w)));
             }
         }
-        out[i] = (uint8_t)min(best, kClearMax + 1);
+        out[i] = (uint8_t)min(best, cap + 1);
     }
 }
 
@@ -226,9 +228,9 @@ hipError_t launch_build_mbricks(const uint8_t *texels, int nx, int ny, int nz, i
     const int threads = 256;
     const int tb = (int)std::min<int64_t>((texels_n + threads - 1) / threads, 65536 * 4);
     hipLaunchKernelGGL(blocked_mask_kernel, dim3(tb), dim3(threads), 0, stream, texels, nx, ny, nz, tmp_a);
-    hipLaunchKernelGGL(cheb_pass_kernel<0>, dim3(tb), dim3(threads), 0, stream, tmp_a, tmp_b, nx, ny, nz);
-    hipLaunchKernelGGL(cheb_pass_kernel<1>, dim3(tb), dim3(threads), 0, stream, tmp_b, tmp_a, nx, ny, nz);
-    hipLaunchKernelGGL(cheb_pass_kernel<2>, dim3(tb), dim3(threads), 0, stream, tmp_a, tmp_b, nx, ny, nz);
+    hipLaunchKernelGGL(cheb_pass_kernel<0>, dim3(tb), dim3(threads), 0, stream, tmp_a, tmp_b, nx, ny, nz, kClearMax);
+    hipLaunchKernelGGL(cheb_pass_kernel<1>, dim3(tb), dim3(threads), 0, stream, tmp_b, tmp_a, nx, ny, nz, kClearMax);
+    hipLaunchKernelGGL(cheb_pass_kernel<2>, dim3(tb), dim3(threads), 0, stream, tmp_a, tmp_b, nx, ny, nz, kClearMax);
     const int64_t total = (int64_t)gx * gy * gz * 128;
     const int bb = (int)std::min<int64_t>((total + threads - 1) / threads, 65536 * 4);
     hipLaunchKernelGGL(build_mbricks_kernel, dim3(bb), dim3(threads), 0, stream, texels, tmp_b, nx, ny, nz, bias_x, bias,
@@ -236,17 +238,83 @@ hipError_t launch_build_mbricks(const uint8_t *texels, int nx, int ny, int nz, i
     return hipGetLastError();
 }
 
+// ---- shadow-zero rows (bit 6 of a row's meta byte; render_persistent_kernel skips the NEE of a collision in such a row) ----
+// blocked[b] = 1 when the shadow volume's footprint based at texel b -- read as the NEE reads it, clamp-to-edge -- holds a
+// non-zero texel.
+__global__ void shadow_blocked_kernel(const uint8_t *__restrict__ t, int nx, int ny, int nz, uint8_t *__restrict__ blocked)
+{
+    const int64_t total = (int64_t)nx * ny * nz;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int x = (int)(i % nx), y = (int)((i / nx) % ny), z = (int)(i / ((int64_t)nx * ny));
+        const int x1 = min(x + 1, nx - 1), y1 = min(y + 1, ny - 1), z1 = min(z + 1, nz - 1);
+        const size_t r00 = ((size_t)z * ny + y) * nx, r10 = ((size_t)z * ny + y1) * nx, r01 = ((size_t)z1 * ny + y) * nx,
+                     r11 = ((size_t)z1 * ny + y1) * nx;
+        const uint32_t m = t[r00 + x] | t[r00 + x1] | t[r10 + x] | t[r10 + x1] | t[r01 + x] | t[r01 + x1] | t[r11 + x] | t[r11 + x1];
+        blocked[i] = m != 0u ? 1 : 0;
+    }
+}
+
+// One thread per row of the (dense) march-brick array: dist = Chebyshev distance of a base texel to the nearest blocked one,
+// capped at r + 1, out-of-grid bases blocked (cheb_pass_kernel).  The row gets bit 6 when each of its three bases is more than
+// r from every blocked base: every footprint based within r of the row is then all zero and inside the volume.  Only rows of
+// clearance 0 are marked, which are the only ones a collision can happen in (a row whose clearance is 1 or more has no
+// non-zero footprint), so the bytes of free space are unchanged.
+__global__ void nee_skip_flags_kernel(const uint8_t *__restrict__ dist, int nx, int ny, int nz, int r, int bias_x, int bias,
+                                      uint8_t *__restrict__ bricks, int gx, int gy, int gz)
+{
+    const int64_t total = (int64_t)gx * gy * gz * 16;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t b = i >> 4;
+        const int ly = (int)(i & 3), lz = (int)((i >> 2) & 3);
+        const int x0 = (int)(b % gx) * 3 - bias_x;
+        const int y = (int)((b / gx) % gy) * 4 + ly - bias;
+        const int z = (int)(b / ((int64_t)gx * gy)) * 4 + lz - bias;
+        uint8_t *m = bricks + ((size_t)b << 7) + lz * 25 + ly * 5 + 4;
+        const uint32_t meta = *m;
+        if ((meta & 0x3fu) != 0u) {
+            continue;
+        }
+        bool zero = true;
+        for (int k = 0; k < 3; k++) {
+            const int x = x0 + k;
+            const bool in_grid = x >= 0 && y >= 0 && z >= 0 && x < nx && y < ny && z < nz;
+            zero = zero && in_grid && (int)dist[((size_t)z * ny + y) * nx + x] > r;
+        }
+        if (zero) {
+            *m = (uint8_t)(meta | 0x40u);
+        }
+    }
+}
+
+// (after launch_build_mbricks and the shadow volume: tmp_a and tmp_c are scratch volumes of nx*ny*nz bytes)
+hipError_t launch_nee_skip_flags(const uint8_t *shadow, int nx, int ny, int nz, int r, int bias_x, int bias, int gx, int gy,
+                                 int gz, uint8_t *tmp_a, uint8_t *tmp_c, uint8_t *bricks, hipStream_t stream)
+{
+    const int64_t texels_n = (int64_t)nx * ny * nz;
+    const int threads = 256;
+    const int tb = (int)std::min<int64_t>((texels_n + threads - 1) / threads, 65536 * 4);
+    hipLaunchKernelGGL(shadow_blocked_kernel, dim3(tb), dim3(threads), 0, stream, shadow, nx, ny, nz, tmp_a);
+    hipLaunchKernelGGL(cheb_pass_kernel<0>, dim3(tb), dim3(threads), 0, stream, tmp_a, tmp_c, nx, ny, nz, r);
+    hipLaunchKernelGGL(cheb_pass_kernel<1>, dim3(tb), dim3(threads), 0, stream, tmp_c, tmp_a, nx, ny, nz, r);
+    hipLaunchKernelGGL(cheb_pass_kernel<2>, dim3(tb), dim3(threads), 0, stream, tmp_a, tmp_c, nx, ny, nz, r);
+    const int64_t rows = (int64_t)gx * gy * gz * 16;
+    const int rb = (int)std::min<int64_t>((rows + threads - 1) / threads, 65536 * 4);
+    hipLaunchKernelGGL(nee_skip_flags_kernel, dim3(rb), dim3(threads), 0, stream, tmp_c, nx, ny, nz, r, bias_x, bias, bricks, gx, gy,
+                       gz);
+    return hipGetLastError();
+}
+
 #ifdef CT_EXPERIMENTS
 // ---- march bricks with dense ADDRESSING and sparse BACKING (CT_FLAG_VMM_BRICKS; ct_api.cpp maps the chunks) ---------------
 // Texel bytes: lx < 4; meta bytes: lx == 4 of the base rows ly, lz < 4 (build_mbricks_kernel).  A chunk without a non-zero
 // texel byte is described by its meta bytes alone, and its clearances may be rounded DOWN without changing a result (a
-// smaller clearance only shortens the exact free-space skip): quantised to {0, 4, 8, 16, 32, 64, 127} texels, two such chunks
-// with the same bytes can share one piece of memory.
+// smaller clearance only shortens the exact free-space skip): quantised to {0, 4, 8, 16, 32, 63} texels, two such chunks
+// with the same bytes can share one piece of memory.  The interior and shadow-zero flags (bits 7, 6) are kept.
 CT_DEV uint32_t quantize_meta(uint32_t v)
 {
-    const uint32_t c = v & 0x7fu;
-    const uint32_t q = c >= 127u ? 127u : (c >= 64u ? 64u : (c >= 32u ? 32u : (c >= 16u ? 16u : (c >= 8u ? 8u : (c >= 4u ? 4u : 0u)))));
-    return (v & 0x80u) | q;
+    const uint32_t c = v & 0x3fu;
+    const uint32_t q = c >= 63u ? 63u : (c >= 32u ? 32u : (c >= 16u ? 16u : (c >= 8u ? 8u : (c >= 4u ? 4u : 0u))));
+    return (v & 0xc0u) | q;
 }
 
 // One block per chunk: out[chunk] = (any texel byte non-zero, 0, hash of the quantised meta bytes: low, high word).
@@ -818,8 +886,9 @@ CT_DEV NeeLoads in_scattering_issue_phase(const DevScene &sc, f3 dir, bool chopp
 // The same with the chopped table in LDS and the lane's one-entry footprint cache (MARCH kernel; in the DELTA kernel,
 // which is bound by instruction issue at its register limit, the cache cost 2 %); the un-chopped table (first bounce)
 // stays global.
+// zero = true: the footprint is known to be all zero (CT_MARCH_NEE_SKIP == 2): its load is not issued, the cell is zero.
 CT_DEV NeeLoads in_scattering_issue_lds(const DevScene &sc, const float *lds_chopped, f3 pos, f3 dir, bool chopped,
-                                        uint32_t &nee_key, uint2 &nee_cell, bool &reused)
+                                        uint32_t &nee_key, uint2 &nee_cell, bool &reused, bool zero = false)
 {
     NeeLoads n;
     const float cos_light = dot3(mk3(sc.nlx, sc.nly, sc.nlz), dir);
@@ -836,7 +905,7 @@ CT_DEV NeeLoads in_scattering_issue_lds(const DevScene &sc, const float *lds_cho
     n.a = (i > kMieN - 2) ? pair.y : pair.x;
     n.b = (i < 0) ? pair.x : pair.y;
     n.w = fract_(x);
-    n.cell = fetch_cell_cached(sc, sc.ibricks, pos, nee_key, nee_cell, reused);
+    n.cell = fetch_cell_cached(sc, sc.ibricks, pos, nee_key, nee_cell, reused, zero);
     return n;
 }
 
@@ -866,6 +935,12 @@ enum : int { ST_IDLE = 0, ST_MARCH = 1, ST_BOUNCE = 2 };
 #define CT_MARCH_FUSE 1
 #endif
 constexpr bool MARCH_FUSE = CT_MARCH_FUSE != 0;
+// NEE of a collision in a shadow-zero row (DevScene::mbricks, bit 6): its footprint is all zero, so in_scattering_finish is +0
+// and rad + (+0) is rad bit for bit (rad is never -0).  1: the lane branches around the NEE's loads and arithmetic; 2: only the
+// footprint load is predicated off, the arithmetic runs on a zero cell; 0 (build --variant noneeskip): every NEE is evaluated.
+#ifndef CT_MARCH_NEE_SKIP
+#define CT_MARCH_NEE_SKIP 1
+#endif
 
 // 1 / max per-axis advance of one march step, in texels (approximate reciprocal is fine: it only
 // sizes a conservative skip, see the free-space skip in the march phase).
@@ -952,7 +1027,7 @@ __global__ __launch_bounds__(256) void inscatter_kernel(DevScene sc, uint8_t *__
             }
             p = add3(p, step_to_light);
             s += 1;
-            const uint32_t clear = meta & 0x7fu;
+            const uint32_t clear = meta & 0x3fu;
             if (clear != 0u) {
                 const int n = min(skip_steps(clear, inv_maxd), step_count - s);
                 replay_steps(p, step_to_light, n);
@@ -1137,7 +1212,7 @@ __global__ __launch_bounds__(256) void primary_advance_kernel(DevScene sc, const
             steps += 1u;
             uint32_t meta;
             const uint2 cell = fetch_cell_m<SPARSE>(sc, pos, meta);
-            dfree = meta & 0x7fu;
+            dfree = meta & 0x3fu;
             if ((cell.x | cell.y) != 0u || ((meta & 0x80u) == 0u && !in_box(sc, pos))) {
                 break;
             }
@@ -1208,6 +1283,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void r
     uint32_t st_fetch = 0, st_zero = 0, st_skip = 0, st_zero_d0 = 0, st_zero_d1 = 0, st_skip_iters = 0, st_stolen = 0, st_iters = 0, st_first = 0;
     uint32_t st_hit2 = 0, st_hit3 = 0, st_h2 = 0xffffffffu, st_h3 = 0xffffffffu;   // (diagnostics: a deeper footprint cache)
     uint32_t st_same_line = 0, st_dup_line = 0, st_prev_line = 0xffffffffu;   // brick-line reuse of the march fetches (STATS)
+    uint32_t st_nee_zero = 0;   // NEE lookups skipped in shadow-zero rows (STATS)
 
     // ---------------- resume the paths the previous launch suspended ----------------
     // How often this lane's path has been suspended so far (0 = started by this launch).  A path may be handed on while its
@@ -1405,20 +1481,35 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void r
                 // The collision's back-off (cloud.cuh:99) was left for this phase: in the march phase
                 // one lane in fifteen collides per step, so its log and two divisions would run for
                 // nearly every wave at 7 % lane occupancy.  `inv_maxd` carries the density sampled at
-                // the collision, `dfree` the brick's "interior" flag (both are reset below).
+                // the collision, `dfree` the row's "interior" and "shadow-zero" flags (both are reset below).
+                bool nee_zero = false;
                 {
                     const float lg = logf_above_one(div_(xi, T));
                     // (the density of a collision is of moderate magnitude: T fell at this step, so exp(-density * step) < 1,
                     // i.e. density * step >= 2^-25; and density <= densityMultiplier < 80 / step)
                     const float inv = rcp_moderate(inv_maxd);
                     pos = sub3(pos, scale3(scale3(dir, lg), inv)); // scatterPos, :99
+                    // The back-off is about a step at most, but not always (T's rounding at a tiny density * step): the flag's
+                    // radius covers back-offs up to nee_reach (ct_api.cpp), a longer one is evaluated
+                    nee_zero = CT_MARCH_NEE_SKIP != 0 && (dfree & 0x40u) != 0u && lg * inv <= sc.nee_reach;
                 }
                 // isInBox(scatterPos), cloudRadianceMaterials.cu:49-52
-                if (dfree != 0u || in_box(sc, pos)) {
+                if ((dfree & 0x80u) != 0u || in_box(sc, pos)) {
                     const bool chopped = (MODE == 1) ? true : (MODE == 0 ? (depth != 1) : false);
-                    bool nee_reused;
+                    bool nee_reused = false;
                     const uint32_t st_key_before = nee_key;
-                    const NeeLoads nee = in_scattering_issue_lds(sc, lds.chopped, pos, dir, chopped, nee_key, nee_cell, nee_reused);
+                    NeeLoads nee;
+                    if (CT_MARCH_NEE_SKIP == 1) {
+                        if (!nee_zero) {
+                            nee = in_scattering_issue_lds(sc, lds.chopped, pos, dir, chopped, nee_key, nee_cell, nee_reused);
+                        }
+                    } else {
+                        nee = in_scattering_issue_lds(sc, lds.chopped, pos, dir, chopped, nee_key, nee_cell, nee_reused, nee_zero);
+                    }
+                    if (STATS) {
+                        st_nee_zero += nee_zero ? 1u : 0u;
+                        nee_reused = nee_reused || nee_zero;   // (a skipped lookup counts as a reused footprint: no load)
+                    }
                     if (STATS && !nee_reused) {
                         // (would a second / third entry -- the footprints before the one just replaced -- have held this one?)
                         st_hit2 += (nee_key == st_h2) ? 1u : 0u;
@@ -1426,7 +1517,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void r
                         st_h3 = st_h2;
                         st_h2 = st_key_before;
                     }
-                    nee_fetched = !nee_reused;
+                    nee_fetched = !nee_reused && !nee_zero;
                     if (STATS) {
                         st_first += nee_reused ? 1u : 0u;
                         if (ba.touched_shadow && !nee_reused) {
@@ -1447,7 +1538,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void r
                             go = false;
                         }
                     }
-                    rad = add3(rad, in_scattering_finish(sc, nee, pos));
+                    if (CT_MARCH_NEE_SKIP != 1 || !nee_zero) {
+                        rad = add3(rad, in_scattering_finish(sc, nee, pos));
+                    }
                     // (setting the next flight up for every lane and selecting the state -- no region for the rare path at its
                     // depth cap -- measured: MARCH -0.7 %, the DELTA kernel's counterpart -1.6 %, profiles/r04aa)
                     if (go) {
@@ -1512,7 +1605,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void r
                 pos = add3(pos, stepv);
                 uint32_t meta;
                 const uint2 cell = fetch_cell_m<SPARSE>(sc, pos, meta);
-                dfree = meta & 0x7fu;
+                dfree = meta & 0x3fu;
                 c_dl += 1;
                 if (COST) {
                     work += 1u;
@@ -1559,12 +1652,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void r
                 // known to hold (see DevScene), so the six comparisons are skipped.
 #if CT_MARCH_FLAT_EXIT
                 state = collided ? ST_BOUNCE : state;
-                dfree = collided ? (meta & 0x80u) : dfree;
+                dfree = collided ? (meta & 0xc0u) : dfree;
                 if (!collided & ((meta & 0x80u) == 0u) & !in_box_flat(sc, pos)) {
 #else
                 if (collided) {
                     state = ST_BOUNCE;
-                    dfree = meta & 0x80u;
+                    dfree = meta & 0xc0u;
                 } else if ((meta & 0x80u) == 0u && !in_box(sc, pos)) {
 #endif
                     ba.frames[out_idx] = make_float4(rad.x, rad.y, rad.z, 1.f);
@@ -1661,10 +1754,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void r
         vals[i] = v;
     }
     if (STATS) {
-        uint32_t sv[15] = { st_fetch, st_zero, st_skip, st_zero_d0, st_zero_d1, st_skip_iters, st_first,
-                            iv_dealt, iv_resumed, iv_written, iv_suspended, st_same_line, st_dup_line, st_hit2, st_hit3 };
+        uint32_t sv[16] = { st_fetch, st_zero, st_skip, st_zero_d0, st_zero_d1, st_skip_iters, st_first,
+                            iv_dealt, iv_resumed, iv_written, iv_suspended, st_same_line, st_dup_line, st_hit2, st_hit3, st_nee_zero };
 #pragma unroll
-        for (int i = 0; i < 15; i++) {
+        for (int i = 0; i < 16; i++) {
             uint32_t v = sv[i];
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) {
@@ -1705,6 +1798,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void r
             atomicAdd(&ba.stats[69], (unsigned long long)sv[12]);
             atomicAdd(&ba.stats[70], (unsigned long long)sv[13]);
             atomicAdd(&ba.stats[71], (unsigned long long)sv[14]);
+            atomicAdd(&ba.stats[72], (unsigned long long)sv[15]);
         }
     }
     if (lane == 0) {

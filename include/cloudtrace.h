@@ -412,6 +412,12 @@ CT_API int ct_debug_memory(CtHandle h, uint64_t out[8]);
  * without that test and that clamp runs; CT_DELTA_INTERIOR=0 keeps both). */
 CT_API int ct_debug_delta_grid(CtHandle h, uint32_t out[8]);
 
+/* The MARCH estimator's march-brick row meta bytes (bit 7 interior, bit 6 shadow-zero, bits 0-5 clearance in texels).
+ * geom_out: [0] radius r of the shadow-zero flags (0: none set), [1] x bias, [2] y/z bias, [3..5] bricks per axis (3x4x4
+ * texels each), [6] 1 when the bricks are sparse.  meta_out (NULL: geometry only; dense bricks only) receives one byte per
+ * row, [z][y][brick x] with z, y in [0, 4 * bricks): the row of base texels x = 3 bx - x bias .. +2, y - bias, z - bias. */
+CT_API int ct_debug_march_meta(CtHandle h, uint32_t geom_out[8], uint8_t *meta_out, size_t capacity);
+
 /* PMC calibration probe (no handle): allocates 2^log2_lines 128-byte lines on `device`, and has one
  * thread per line issue the estimator's access pattern (two unaligned 8-byte loads at byte 13 and
  * byte 38 of a pseudo-randomly chosen, never repeated line).  Under rocprofv3 --pmc FETCH_SIZE this

@@ -660,6 +660,10 @@ static int create_impl(const CtScene *s, CtHandle h)
         h->exchange = s->estimator == CT_EST_DELTA ? std::min(2, std::max(0, atoi(e))) : 0;
     }
 #ifdef CT_EXPERIMENTS
+    if (h->exchange && (s->flags & CT_FLAG_TEX_FIXED8)) {
+        // (the path-exchange kernels are measured-and-rejected experiments: they filter with the exact weights only)
+        return fail(h, CT_E_INVAL, "CT_EXCHANGE has no CT_FLAG_TEX_FIXED8 kernels");
+    }
     if (h->exchange) {
         h->xshape = h->exchange == 2 ? wave_exchange_shape(s->device) : exchange_shape(s->device);
         h->xshape.stats = h->shape.stats;
@@ -714,6 +718,7 @@ static int create_impl(const CtScene *s, CtHandle h)
     d.height = s->height;
     d.max_depth = s->max_depth;
     d.mode = s->mode;
+    d.tex_fixed8 = (s->flags & CT_FLAG_TEX_FIXED8) ? 1u : 0u;   // every launcher picks its kernel by it (the shadow volume's too)
     d.tiles_x = (s->width + kTile - 1) / kTile;
     d.tiles_y = (s->height + kTile - 1) / kTile;
     // (re-swept on the final kernel: 8 instead of 16 is worth +1.4 % at 512^3 and +5 % at 256^3; 16 stays best at 1024^3)

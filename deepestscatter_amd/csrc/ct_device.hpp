@@ -98,6 +98,10 @@ struct DevScene {
     int32_t brick_gx;        // bricks per row
     int32_t brick_gxy;       // bricks per slice
     int32_t brick_gy, brick_gz;
+    // CT_FLAG_TEX_FIXED8 (tex_weight<true>).  Read on the host only, where the launchers pick the kernel instantiation that
+    // samples with 1.8 fixed-point weights; no kernel reads it.  (It sits in the padding before the next pointer: the kernel
+    // argument block keeps its size.)
+    uint32_t tex_fixed8;
     // Bytes 125 and 126 of every DENSITY brick are its meta bytes.  Byte 126 = majorant M: the
     // max of the texels [lo-1, lo+5]^3, i.e. of everything a trilinear footprint based in the brick
     // (or on its boundary) can read.  Byte 125: bits 0-6 = free-space distance D (Chebyshev
@@ -223,6 +227,24 @@ CT_DEV bool in_box_flat(const DevScene &sc, f3 p)
 // which is exactly the oracle's fracf().
 CT_DEV float fract_(float x) { return __builtin_amdgcn_fractf(x); }
 
+// The weight of every linear / trilinear filter.  FIXED8 = false (the default): the exact fraction, the oracle's default
+// build.  FIXED8 = true (CT_FLAG_TEX_FIXED8): the fraction rounded to 1.8 fixed point like the reference's texture unit,
+// rint(frac * 256) / 256 with round-to-nearest-even (v_rndne_f32), bit for bit the oracle's -DORC_TEX_FIXED8 build
+// (libct_oracle_fixed8.so).  A fraction above 255.5 / 256 becomes exactly 1.0 and stays so.  Both scalings are by powers of
+// two and exact.  Every shortcut the kernels take around the filter still holds with rounded weights: the filter is a convex
+// combination of its texels, so a footprint of eight zeros filters to +0 (free-space skips and replays, the pre-walked
+// primary prefix, the shadow-volume walk, the NEE shadow-zero skip) and a value never leaves its texels' range (the DELTA
+// majorants and the sigma_low early accept).
+template <bool FIXED8>
+CT_DEV float tex_weight(float x)
+{
+    if constexpr (FIXED8) {
+        return __builtin_rintf(fract_(x) * 256.0f) * (1.0f / 256.0f);
+    } else {
+        return fract_(x);
+    }
+}
+
 // Trilinear filter of one corner cell: x, then y, then z; lerp(a,b,t)=fma(t,b-a,a); /255 last.
 CT_DEV float filter_cell(uint2 c, float wx, float wy, float wz)
 {
@@ -334,12 +356,13 @@ CT_DEV int32_t floor_to_int(float x)
 
 // tex3D for positions the tracer can reach (inside the slack box +- one step): no clamp, the
 // apron supplies clamp-to-edge.
+template <bool FIXED8>
 CT_DEV float tex3_apron(const DevScene &sc, const uint8_t *bricks, f3 p)
 {
     const float x = fmaf(p.x, sc.sx, -0.5f), y = fmaf(p.y, sc.sy, -0.5f), z = fmaf(p.z, sc.sz, -0.5f);
     const int32_t ix = floor_to_int(x), iy = floor_to_int(y), iz = floor_to_int(z);
     const uint2 c = load_footprint(sc, bricks, ix, iy, iz);
-    return filter_cell(c, fract_(x), fract_(y), fract_(z));
+    return filter_cell(c, tex_weight<FIXED8>(x), tex_weight<FIXED8>(y), tex_weight<FIXED8>(z));
 }
 
 // The march splits the texture fetch in three so that several loads can be in flight and all-zero
@@ -497,14 +520,16 @@ CT_DEV uint2 fetch_cell_m(const DevScene &sc, f3 p, uint32_t &meta)
     return load_footprint_m<SPARSE>(sc, floor_to_int(x), floor_to_int(y), floor_to_int(z), meta);
 }
 
+template <bool FIXED8>
 CT_DEV float filter_at(const DevScene &sc, uint2 cell, f3 p)
 {
     const float x = fmaf(p.x, sc.sx, -0.5f), y = fmaf(p.y, sc.sy, -0.5f), z = fmaf(p.z, sc.sz, -0.5f);
-    return filter_cell(cell, fract_(x), fract_(y), fract_(z));
+    return filter_cell(cell, tex_weight<FIXED8>(x), tex_weight<FIXED8>(y), tex_weight<FIXED8>(z));
 }
 
 // tex3D with explicit clamp-to-edge, for the shadow-volume precompute which marches up to
 // one box length away from the box (inScatter.cu:55-59 has no box test).
+template <bool FIXED8>
 CT_DEV float tex3_clamped(const DevScene &sc, const uint8_t *bricks, f3 p)
 {
     const float x = fmaf(p.x, sc.sx, -0.5f), y = fmaf(p.y, sc.sy, -0.5f), z = fmaf(p.z, sc.sz, -0.5f);
@@ -514,11 +539,11 @@ CT_DEV float tex3_clamped(const DevScene &sc, const uint8_t *bricks, f3 p)
     const int32_t iy = (int32_t)fminf(fmaxf(fly, -1.0f), (float)(sc.ny - 1));
     const int32_t iz = (int32_t)fminf(fmaxf(flz, -1.0f), (float)(sc.nz - 1));
     const uint2 c = load_footprint(sc, bricks, ix, iy, iz);
-    return filter_cell(c, fract_(x), fract_(y), fract_(z));
+    return filter_cell(c, tex_weight<FIXED8>(x), tex_weight<FIXED8>(y), tex_weight<FIXED8>(z));
 }
 
 // ---- 1-D texture unit on a float table (Mie.cpp:8229-8240): linear, clamp, normalised -----
-template <typename Ptr>
+template <bool FIXED8, typename Ptr>
 CT_DEV float tex1(Ptr t, float u)
 {
     const float x = fmaf(u, (float)kMieN, -0.5f);
@@ -527,7 +552,7 @@ CT_DEV float tex1(Ptr t, float u)
     const int32_t i0 = min(max(i, 0), kMieN - 1);
     const int32_t i1 = min(max(i + 1, 0), kMieN - 1);
     const float a = t[i0], b = t[i1];
-    return fmaf(fract_(x), b - a, a);
+    return fmaf(tex_weight<FIXED8>(x), b - a, a);
 }
 
 // ---- CDF inversion ------------------------------------------------------------------------

@@ -26,6 +26,8 @@
 // cannot block).  A ring cannot overflow: it has at least as many entries as the pool has slots, and a slot's id is in at
 // most one place.
 //
+// These kernels filter with the exact weights only (tex_weight<false>): ct_create refuses CT_FLAG_TEX_FIXED8 with CT_EXCHANGE.
+//
 // Nothing here changes a value: a path's arithmetic is the same sequence of operations on the same numbers wherever it
 // runs, samples are written to the same place, and the counters are sums.  Parity with the oracle twin is bit for bit, as
 // for render_delta_kernel (tests: every DELTA test runs both kernels).
@@ -232,7 +234,7 @@ __global__ __launch_bounds__(kXThreads) void render_delta_x_kernel(DevScene sc, 
             f3 rad = mk3(__uint_as_float(c.x), __uint_as_float(c.y), __uint_as_float(c.z));
             uint32_t s = a.w, depth = b.w;
             const bool chopped = (MODE == 1) ? true : (MODE == 0 ? (depth != 1u) : false);
-            const NeeLoads nee = in_scattering_issue(sc, pos, d, chopped);
+            const NeeLoads nee = in_scattering_issue<false>(sc, pos, d, chopped);
             c_il += 1;
             bool go = (MODE != 2);
             if (go) {
@@ -243,7 +245,7 @@ __global__ __launch_bounds__(kXThreads) void render_delta_x_kernel(DevScene sc, 
                     go = false;
                 }
             }
-            rad = add3(rad, in_scattering_finish(sc, nee, pos));
+            rad = add3(rad, in_scattering_finish<false>(sc, nee, pos));
             if (go) {
                 slotA[id].w = s;
                 slotB[id] = make_uint4(__float_as_uint(d.x), __float_as_uint(d.y), __float_as_uint(d.z), depth);
@@ -506,7 +508,7 @@ __global__ __launch_bounds__(kXThreads) void render_delta_x_kernel(DevScene sc, 
                             uint32_t meta_unused;
                             const uint2 cell = fetch_cell_in_grid(sc, sc.dbricks, p, meta_unused);
                             c_dl += 1;
-                            real = z * sigma_bar < filter_at(sc, cell, p) * sc.density_multiplier;
+                            real = z * sigma_bar < filter_at<false>(sc, cell, p) * sc.density_multiplier;
                         }
                         if (real) {
                             if (in_box(sc, p)) {
@@ -777,7 +779,7 @@ __global__ __launch_bounds__(kXThreads) void render_delta_w_kernel(DevScene sc, 
                 uint32_t s = a.w, depth = b.w;
                 // ---- the scatter phase of render_delta_kernel (cloudRadianceMaterials.cu:53-61) ----
                 const bool chopped = (MODE == 1) ? true : (MODE == 0 ? (depth != 1u) : false);
-                const NeeLoads nee = in_scattering_issue(sc, pos, d, chopped);
+                const NeeLoads nee = in_scattering_issue<false>(sc, pos, d, chopped);
                 c_il += 1;
                 bool go = (MODE != 2);
                 if (go) {
@@ -788,7 +790,7 @@ __global__ __launch_bounds__(kXThreads) void render_delta_w_kernel(DevScene sc, 
                         go = false;
                     }
                 }
-                rad = add3(rad, in_scattering_finish(sc, nee, pos));
+                rad = add3(rad, in_scattering_finish<false>(sc, nee, pos));
                 if (go) {
                     slotA[id].w = s;
                     slotB[id] = make_uint4(__float_as_uint(d.x), __float_as_uint(d.y), __float_as_uint(d.z), depth);
@@ -983,7 +985,7 @@ __global__ __launch_bounds__(kXThreads) void render_delta_w_kernel(DevScene sc, 
                             uint32_t meta_unused;
                             const uint2 cell = fetch_cell_in_grid(sc, sc.dbricks, p, meta_unused);
                             c_dl += 1;
-                            real = z * sigma_bar < filter_at(sc, cell, p) * sc.density_multiplier;
+                            real = z * sigma_bar < filter_at<false>(sc, cell, p) * sc.density_multiplier;
                         }
                         if (real) {
                             if (in_box(sc, p)) {

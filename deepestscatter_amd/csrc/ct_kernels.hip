@@ -826,14 +826,16 @@ hipError_t launch_fill_frame(float4 *frame, uint32_t width, uint32_t height, uin
     return hipGetLastError();
 }
 
-// NEE: getInScattering, cloud.cuh:146-158.
+// NEE: getInScattering, cloud.cuh:146-158.  FIXED8 here and below: the filter weights of tex_weight<FIXED8>
+// (CT_FLAG_TEX_FIXED8).
+template <bool FIXED8>
 CT_DEV f3 in_scattering(const DevScene &sc, f3 pos, f3 dir, bool chopped)
 {
     const float cos_light = dot3(mk3(sc.nlx, sc.nly, sc.nlz), dir);
     const float u = (cos_light + 1) / 2;
     const float *table = chopped ? sc.chopped : sc.mie;
-    const float phase = tex1(table, u);
-    const float ins = tex3_apron(sc, sc.ibricks, pos);
+    const float phase = tex1<FIXED8>(table, u);
+    const float ins = tex3_apron<FIXED8>(sc, sc.ibricks, pos);
     f3 l = scale3(mk3(sc.lr, sc.lg, sc.lb), ins);
     l = scale3(l, phase);
     return scale3(l, sc.sun_ratio);
@@ -846,6 +848,7 @@ struct NeeLoads {
     uint2 cell;        // shadow-volume footprint
 };
 
+template <bool FIXED8>
 CT_DEV NeeLoads in_scattering_issue(const DevScene &sc, f3 pos, f3 dir, bool chopped)
 {
     NeeLoads n;
@@ -859,13 +862,14 @@ CT_DEV NeeLoads in_scattering_issue(const DevScene &sc, f3 pos, f3 dir, bool cho
     __builtin_memcpy(&pair, table + min(max(i, 0), kMieN - 2), sizeof pair);
     n.a = (i > kMieN - 2) ? pair.y : pair.x;
     n.b = (i < 0) ? pair.x : pair.y;
-    n.w = fract_(x);
+    n.w = tex_weight<FIXED8>(x);
     uint32_t meta_unused;
     n.cell = fetch_cell(sc, sc.ibricks, pos, meta_unused);
     return n;
 }
 
 // Only the phase-table half of in_scattering_issue (the caller has the shadow-volume footprint already).
+template <bool FIXED8>
 CT_DEV NeeLoads in_scattering_issue_phase(const DevScene &sc, f3 dir, bool chopped)
 {
     NeeLoads n;
@@ -878,7 +882,7 @@ CT_DEV NeeLoads in_scattering_issue_phase(const DevScene &sc, f3 dir, bool chopp
     __builtin_memcpy(&pair, table + min(max(i, 0), kMieN - 2), sizeof pair);
     n.a = (i > kMieN - 2) ? pair.y : pair.x;
     n.b = (i < 0) ? pair.x : pair.y;
-    n.w = fract_(x);
+    n.w = tex_weight<FIXED8>(x);
     n.cell = make_uint2(0u, 0u);
     return n;
 }
@@ -887,6 +891,7 @@ CT_DEV NeeLoads in_scattering_issue_phase(const DevScene &sc, f3 dir, bool chopp
 // which is bound by instruction issue at its register limit, the cache cost 2 %); the un-chopped table (first bounce)
 // stays global.
 // zero = true: the footprint is known to be all zero (CT_MARCH_NEE_SKIP == 2): its load is not issued, the cell is zero.
+template <bool FIXED8>
 CT_DEV NeeLoads in_scattering_issue_lds(const DevScene &sc, const float *lds_chopped, f3 pos, f3 dir, bool chopped,
                                         uint32_t &nee_key, uint2 &nee_cell, bool &reused, bool zero = false)
 {
@@ -904,15 +909,16 @@ CT_DEV NeeLoads in_scattering_issue_lds(const DevScene &sc, const float *lds_cho
     }
     n.a = (i > kMieN - 2) ? pair.y : pair.x;
     n.b = (i < 0) ? pair.x : pair.y;
-    n.w = fract_(x);
+    n.w = tex_weight<FIXED8>(x);
     n.cell = fetch_cell_cached(sc, sc.ibricks, pos, nee_key, nee_cell, reused, zero);
     return n;
 }
 
+template <bool FIXED8>
 CT_DEV f3 in_scattering_finish(const DevScene &sc, const NeeLoads &n, f3 pos)
 {
     const float phase = fmaf(n.w, n.b - n.a, n.a);
-    const float ins = filter_at(sc, n.cell, pos);
+    const float ins = filter_at<FIXED8>(sc, n.cell, pos);
     f3 l = scale3(mk3(sc.lr, sc.lg, sc.lb), ins);
     l = scale3(l, phase);
     return scale3(l, sc.sun_ratio);
@@ -988,6 +994,9 @@ CT_DEV void replay_steps(f3 &pos, f3 stepv, int n)
 // from the clamped sampler.  167 -> 24 ms at 512^3, 21 -> 4.7 ms at 256^3 (tools/gpu_create_profile.sh, profiles/r02r).
 // zero_faces: bit 0/1 = the texel layers x = 0 / x = nx-1 are all zero, bits 2/3 the same for y, 4/5 for z.
 // =============================================================================================
+// FIXED8 (CT_FLAG_TEX_FIXED8): both samplers filter with tex_weight<true>; the skips above only pass over footprints of eight
+// zeros and layers of zeros, whose filter is +0 whatever the weights.
+template <bool FIXED8>
 __global__ __launch_bounds__(256) void inscatter_kernel(DevScene sc, uint8_t *__restrict__ out, uint32_t zero_faces)
 {
     const int64_t total = (int64_t)sc.nx * sc.ny * sc.nz;
@@ -1017,7 +1026,7 @@ __global__ __launch_bounds__(256) void inscatter_kernel(DevScene sc, uint8_t *__
             uint32_t meta;
             const uint2 cell = fetch_cell_m<false>(sc, p, meta);
             if ((cell.x | cell.y) != 0u) {
-                const float density = filter_at(sc, cell, p) * sc.density_multiplier;
+                const float density = filter_at<FIXED8>(sc, cell, p) * sc.density_multiplier;
                 const float extinction = density * sc.sample_step;
                 transmittance *= ct_expf(-extinction);
                 if (transmittance * 255.f < 1.f) {
@@ -1047,7 +1056,7 @@ __global__ __launch_bounds__(256) void inscatter_kernel(DevScene sc, uint8_t *__
         if (gone) {
             break;
         }
-        const float density = tex3_clamped(sc, sc.dbricks, p) * sc.density_multiplier;
+        const float density = tex3_clamped<FIXED8>(sc, sc.dbricks, p) * sc.density_multiplier;
         const float extinction = density * sc.sample_step;
         transmittance *= ct_expf(-extinction);
         p = add3(p, step_to_light);
@@ -1063,7 +1072,11 @@ hipError_t launch_inscatter(const DevScene &sc, uint8_t *out, uint32_t zero_face
     const int64_t total = (int64_t)sc.nx * sc.ny * sc.nz;
     const int threads = 256;
     const int64_t blocks = (total + threads - 1) / threads;
-    hipLaunchKernelGGL(inscatter_kernel, dim3((unsigned)blocks), dim3(threads), 0, stream, sc, out, zero_faces);
+    if (sc.tex_fixed8) {
+        hipLaunchKernelGGL(inscatter_kernel<true>, dim3((unsigned)blocks), dim3(threads), 0, stream, sc, out, zero_faces);
+    } else {
+        hipLaunchKernelGGL(inscatter_kernel<false>, dim3((unsigned)blocks), dim3(threads), 0, stream, sc, out, zero_faces);
+    }
     return hipGetLastError();
 }
 
@@ -1244,7 +1257,10 @@ hipError_t launch_primary_advance(const DevScene &sc, const float4 *primary, flo
 // uses 75 today; an edit of take_job once moved it to 85 and cost a third of the occupancy, hence the bound.)
 // COST = false: a launch that does not record the paths' costs (BatchArgs::cost is null: every launch but the one that measures
 // them) runs the kernel compiled without the per-path work counter.  Instantiated for the dense, non-diagnostic kernel.
-template <int MODE, bool STATS, bool SPARSE, bool COST = true>
+// FIXED8 = true (CT_FLAG_TEX_FIXED8): every filter weight is tex_weight<true>; a template parameter, not a run-time test, so
+// that the default kernel's instructions stay as they are.  The free-space skip and the NEE shadow-zero skip hold as they
+// are (see tex_weight).
+template <int MODE, bool STATS, bool SPARSE, bool COST = true, bool FIXED8 = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void render_persistent_kernel(DevScene sc, BatchArgs ba)
 {
     __shared__ MieLdsFull lds;
@@ -1501,10 +1517,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void r
                     NeeLoads nee;
                     if (CT_MARCH_NEE_SKIP == 1) {
                         if (!nee_zero) {
-                            nee = in_scattering_issue_lds(sc, lds.chopped, pos, dir, chopped, nee_key, nee_cell, nee_reused);
+                            nee = in_scattering_issue_lds<FIXED8>(sc, lds.chopped, pos, dir, chopped, nee_key, nee_cell, nee_reused);
                         }
                     } else {
-                        nee = in_scattering_issue_lds(sc, lds.chopped, pos, dir, chopped, nee_key, nee_cell, nee_reused, nee_zero);
+                        nee = in_scattering_issue_lds<FIXED8>(sc, lds.chopped, pos, dir, chopped, nee_key, nee_cell, nee_reused, nee_zero);
                     }
                     if (STATS) {
                         st_nee_zero += nee_zero ? 1u : 0u;
@@ -1539,7 +1555,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void r
                         }
                     }
                     if (CT_MARCH_NEE_SKIP != 1 || !nee_zero) {
-                        rad = add3(rad, in_scattering_finish(sc, nee, pos));
+                        rad = add3(rad, in_scattering_finish<FIXED8>(sc, nee, pos));
                     }
                     // (setting the next flight up for every lane and selecting the state -- no region for the rare path at its
                     // depth cap -- measured: MARCH -0.7 %, the DELTA kernel's counterpart -1.6 %, profiles/r04aa)
@@ -1639,7 +1655,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void r
                 bool collided = false;
                 if (CT_MARCH_FLAT_ZERO || (cell.x | cell.y) != 0u) {
                     // all-zero footprints give density 0, exp(-0) = 1, T unchanged: nothing to evaluate
-                    const float density = filter_at(sc, cell, pos) * sc.density_multiplier;
+                    const float density = filter_at<FIXED8>(sc, cell, pos) * sc.density_multiplier;
                     const float extinction = density * sc.sample_step;
                     T *= expf_inrange(-extinction);
                     if (xi > T) {
@@ -1843,14 +1859,16 @@ hipError_t launch_mip_level(const uint8_t *prev, int px, int py, int pz, uint8_t
     return hipGetLastError();
 }
 
-// One level of rtTex3DLod: trilinear, clamp-to-edge, x = fma(pos, textureScale * dim, -0.5).
+// One level of rtTex3DLod: trilinear, clamp-to-edge, x = fma(pos, textureScale * dim, -0.5).  FIXED8: the texel weights of
+// CT_FLAG_TEX_FIXED8; the blend of the two mip levels (descriptor_kernel) stays exact, as in the oracle's tex3_lod.
+template <bool FIXED8>
 CT_DEV float tex3_level(const DevScene &sc, const MipPyramid &mp, uint32_t l, f3 p)
 {
     const int32_t nx = mp.nx[l], ny = mp.ny[l], nz = mp.nz[l];
     const float x = fmaf(p.x, sc.tsx * (float)nx, -0.5f), y = fmaf(p.y, sc.tsy * (float)ny, -0.5f),
                 z = fmaf(p.z, sc.tsz * (float)nz, -0.5f);
     const float flx = floorf(x), fly = floorf(y), flz = floorf(z);
-    const float wx = fract_(x), wy = fract_(y), wz = fract_(z);
+    const float wx = tex_weight<FIXED8>(x), wy = tex_weight<FIXED8>(y), wz = tex_weight<FIXED8>(z);
     const int32_t ix = (int32_t)flx, iy = (int32_t)fly, iz = (int32_t)flz;
     const int32_t x0 = min(max(ix, 0), nx - 1), x1 = min(max(ix + 1, 0), nx - 1);
     const int32_t y0 = min(max(iy, 0), ny - 1), y1 = min(max(iy + 1, 0), ny - 1);
@@ -1867,6 +1885,7 @@ CT_DEV float tex3_level(const DevScene &sc, const MipPyramid &mp, uint32_t l, f3
 
 // setupHierarchicalDescriptor, DisneyDescriptor.cuh:71-112.  One block per (sample, layer), one thread
 // per grid point: the 225 points of a layer touch neighbouring texels of one or two pyramid levels.
+template <bool FIXED8>
 __global__ __launch_bounds__(256) void descriptor_kernel(DevScene sc, MipPyramid mp, const float *__restrict__ positions,
                                                          const float *__restrict__ directions, uint32_t count,
                                                          float level0, float voxel_m, float cloud_size_m,
@@ -1898,9 +1917,9 @@ __global__ __launch_bounds__(256) void descriptor_kernel(DevScene sc, MipPyramid
     const float fl = floorf(lc);
     const uint32_t l0 = (uint32_t)fl;
     const float w = lc - fl;
-    float density = tex3_level(sc, mp, l0, pos);
+    float density = tex3_level<FIXED8>(sc, mp, l0, pos);
     if (w > 0.0f) {
-        const float s1 = tex3_level(sc, mp, min(l0 + 1u, mp.levels - 1u), pos);
+        const float s1 = tex3_level<FIXED8>(sc, mp, min(l0 + 1u, mp.levels - 1u), pos);
         density = fmaf(w, s1 - density, density);
     }
     // distanceToBox, :47-55
@@ -1920,8 +1939,13 @@ hipError_t launch_descriptors(const DevScene &sc, const MipPyramid &mp, const fl
                               uint32_t count, float level0, float voxel_m, float cloud_size_m, uint8_t *out,
                               hipStream_t stream)
 {
-    hipLaunchKernelGGL(descriptor_kernel, dim3(count * 10u), dim3(256), 0, stream, sc, mp, positions, directions, count,
-                       level0, voxel_m, cloud_size_m, out);
+    if (sc.tex_fixed8) {
+        hipLaunchKernelGGL(descriptor_kernel<true>, dim3(count * 10u), dim3(256), 0, stream, sc, mp, positions, directions, count,
+                           level0, voxel_m, cloud_size_m, out);
+    } else {
+        hipLaunchKernelGGL(descriptor_kernel<false>, dim3(count * 10u), dim3(256), 0, stream, sc, mp, positions, directions, count,
+                           level0, voxel_m, cloud_size_m, out);
+    }
     return hipGetLastError();
 }
 
@@ -2175,7 +2199,7 @@ hipError_t launch_primary_advance_delta(const DevScene &sc, const float4 *primar
 //      unnecessary.
 // INTERIOR: DevScene::delta_interior as a compile-time fact (the box test of a real collision and its three scene constants are
 // not in the kernel at all; as a run-time test it cost 3.4 %: the kernel spills scalar registers).  Instantiated for NEE = 1 and 2.
-template <int MODE, bool STATS, int NEE, bool INTERIOR = false>
+template <int MODE, bool STATS, int NEE, bool INTERIOR = false, bool FIXED8 = false>
 __global__ __launch_bounds__(kDeltaThreads) __attribute__((amdgpu_waves_per_eu(CT_DELTA_WAVES))) void render_delta_kernel(DevScene sc, BatchArgs ba)
 {
     // 24 KiB of Mie tables + 40 KiB of majorants + 10 KiB of lower-bound codes + 2 KiB per block of 768 threads:
@@ -2414,9 +2438,9 @@ __global__ __launch_bounds__(kDeltaThreads) __attribute__((amdgpu_waves_per_eu(C
                 const bool chopped = (MODE == 1) ? true : (MODE == 0 ? (depth != 1) : false);
                 NeeLoads nee;
                 if (NEE == 0) {
-                    nee = in_scattering_issue(sc, pos, dir, chopped);
+                    nee = in_scattering_issue<FIXED8>(sc, pos, dir, chopped);
                 } else {
-                    nee = in_scattering_issue_phase(sc, dir, chopped);
+                    nee = in_scattering_issue_phase<FIXED8>(sc, dir, chopped);
                 }
                 c_il += 1;
                 bool go = (MODE != 2);
@@ -2431,7 +2455,7 @@ __global__ __launch_bounds__(kDeltaThreads) __attribute__((amdgpu_waves_per_eu(C
                 if (NEE != 0) {
                     nee.cell = (NEE == 1) ? combine_apron(nee_raw) : combine_twin(nee_raw);
                 }
-                rad = add3(rad, in_scattering_finish(sc, nee, pos));
+                rad = add3(rad, in_scattering_finish<FIXED8>(sc, nee, pos));
                 if (go) {
                     dda_begin(sc, dda, pos, dir);
                     if (DELTA_END_MERGE && !dda_enter_box(sc, dda)) {
@@ -2552,7 +2576,7 @@ __global__ __launch_bounds__(kDeltaThreads) __attribute__((amdgpu_waves_per_eu(C
                                 atomicOr(&ba.touched_density[line >> 5], 1u << (line & 31u));
                             }
                         }
-                        real = z * sigma_bar < filter_at(sc, cell, p) * sc.density_multiplier;
+                        real = z * sigma_bar < filter_at<FIXED8>(sc, cell, p) * sc.density_multiplier;
                     }
                     // (one divergent region instead of two nested ones: the box test runs under the collision's mask -- the same
                     // wave instructions as under the real collisions' -- and the position is a select)
@@ -2719,40 +2743,41 @@ __global__ __launch_bounds__(kDeltaThreads) __attribute__((amdgpu_waves_per_eu(C
     }
 }
 
-template <bool STATS, int NEE>
+template <bool STATS, int NEE, bool FIXED8>
 static void launch_render_delta_mode(const DevScene &sc, const BatchArgs &ba, dim3 grid, dim3 block, hipStream_t stream)
 {
     if (NEE != 0 && !STATS && sc.delta_interior != 0u && ba.cost == nullptr) {   // (the launch that measures path costs: the general kernel)
         constexpr int N = NEE != 0 ? NEE : 1;   // (NEE = 0, the round-3 layout kept for A/Bs, has no interior kernel)
         switch (sc.mode) {
-        case 0: hipLaunchKernelGGL((render_delta_kernel<0, false, N, true>), grid, block, 0, stream, sc, ba); break;
-        case 1: hipLaunchKernelGGL((render_delta_kernel<1, false, N, true>), grid, block, 0, stream, sc, ba); break;
-        default: hipLaunchKernelGGL((render_delta_kernel<2, false, N, true>), grid, block, 0, stream, sc, ba); break;
+        case 0: hipLaunchKernelGGL((render_delta_kernel<0, false, N, true, FIXED8>), grid, block, 0, stream, sc, ba); break;
+        case 1: hipLaunchKernelGGL((render_delta_kernel<1, false, N, true, FIXED8>), grid, block, 0, stream, sc, ba); break;
+        default: hipLaunchKernelGGL((render_delta_kernel<2, false, N, true, FIXED8>), grid, block, 0, stream, sc, ba); break;
         }
         return;
     }
     switch (sc.mode) {
-    case 0: hipLaunchKernelGGL((render_delta_kernel<0, STATS, NEE>), grid, block, 0, stream, sc, ba); break;
-    case 1: hipLaunchKernelGGL((render_delta_kernel<1, STATS, NEE>), grid, block, 0, stream, sc, ba); break;
-    default: hipLaunchKernelGGL((render_delta_kernel<2, STATS, NEE>), grid, block, 0, stream, sc, ba); break;
+    case 0: hipLaunchKernelGGL((render_delta_kernel<0, STATS, NEE, false, FIXED8>), grid, block, 0, stream, sc, ba); break;
+    case 1: hipLaunchKernelGGL((render_delta_kernel<1, STATS, NEE, false, FIXED8>), grid, block, 0, stream, sc, ba); break;
+    default: hipLaunchKernelGGL((render_delta_kernel<2, STATS, NEE, false, FIXED8>), grid, block, 0, stream, sc, ba); break;
     }
 }
 
+template <bool FIXED8>
 static void launch_render_delta_nee(const DevScene &sc, const BatchArgs &ba, dim3 grid, dim3 block, hipStream_t stream, bool stats)
 {
     // (DevScene::delta_nee: 2 needs the twin bricks, which ct_create builds only when it chose that layout)
     const int nee = sc.delta_nee == 2u && sc.tbricks ? 2 : (sc.delta_nee == 1u ? 1 : 0);
     if (stats) {
         switch (nee) {
-        case 0: launch_render_delta_mode<true, 0>(sc, ba, grid, block, stream); break;
-        case 1: launch_render_delta_mode<true, 1>(sc, ba, grid, block, stream); break;
-        default: launch_render_delta_mode<true, 2>(sc, ba, grid, block, stream); break;
+        case 0: launch_render_delta_mode<true, 0, FIXED8>(sc, ba, grid, block, stream); break;
+        case 1: launch_render_delta_mode<true, 1, FIXED8>(sc, ba, grid, block, stream); break;
+        default: launch_render_delta_mode<true, 2, FIXED8>(sc, ba, grid, block, stream); break;
         }
     } else {
         switch (nee) {
-        case 0: launch_render_delta_mode<false, 0>(sc, ba, grid, block, stream); break;
-        case 1: launch_render_delta_mode<false, 1>(sc, ba, grid, block, stream); break;
-        default: launch_render_delta_mode<false, 2>(sc, ba, grid, block, stream); break;
+        case 0: launch_render_delta_mode<false, 0, FIXED8>(sc, ba, grid, block, stream); break;
+        case 1: launch_render_delta_mode<false, 1, FIXED8>(sc, ba, grid, block, stream); break;
+        default: launch_render_delta_mode<false, 2, FIXED8>(sc, ba, grid, block, stream); break;
         }
     }
 }
@@ -2760,7 +2785,11 @@ static void launch_render_delta_nee(const DevScene &sc, const BatchArgs &ba, dim
 hipError_t launch_render_delta(const DevScene &sc, const BatchArgs &ba, LaunchShape shape, hipStream_t stream)
 {
     const dim3 grid(shape.blocks), block(shape.threads);
-    launch_render_delta_nee(sc, ba, grid, block, stream, shape.stats);
+    if (sc.tex_fixed8) {   // (CT_FLAG_TEX_FIXED8: the same table over the kernels that filter with 1.8 fixed-point weights)
+        launch_render_delta_nee<true>(sc, ba, grid, block, stream, shape.stats);
+    } else {
+        launch_render_delta_nee<false>(sc, ba, grid, block, stream, shape.stats);
+    }
     return hipGetLastError();
 }
 
@@ -2791,38 +2820,49 @@ LaunchShape persistent_shape(int device, bool delta, int blocks_per_cu)
     return s;
 }
 
-template <bool STATS, bool SPARSE>
+template <bool STATS, bool SPARSE, bool FIXED8>
 static void launch_render_persistent_mode(const DevScene &sc, const BatchArgs &ba, dim3 grid, dim3 block, hipStream_t stream)
 {
     if (!STATS && !SPARSE && ba.cost == nullptr) {
         switch (sc.mode) {
-        case 0: hipLaunchKernelGGL((render_persistent_kernel<0, false, false, false>), grid, block, 0, stream, sc, ba); break;
-        case 1: hipLaunchKernelGGL((render_persistent_kernel<1, false, false, false>), grid, block, 0, stream, sc, ba); break;
-        default: hipLaunchKernelGGL((render_persistent_kernel<2, false, false, false>), grid, block, 0, stream, sc, ba); break;
+        case 0: hipLaunchKernelGGL((render_persistent_kernel<0, false, false, false, FIXED8>), grid, block, 0, stream, sc, ba); break;
+        case 1: hipLaunchKernelGGL((render_persistent_kernel<1, false, false, false, FIXED8>), grid, block, 0, stream, sc, ba); break;
+        default: hipLaunchKernelGGL((render_persistent_kernel<2, false, false, false, FIXED8>), grid, block, 0, stream, sc, ba); break;
         }
         return;
     }
     switch (sc.mode) {
-    case 0: hipLaunchKernelGGL((render_persistent_kernel<0, STATS, SPARSE>), grid, block, 0, stream, sc, ba); break;
-    case 1: hipLaunchKernelGGL((render_persistent_kernel<1, STATS, SPARSE>), grid, block, 0, stream, sc, ba); break;
-    default: hipLaunchKernelGGL((render_persistent_kernel<2, STATS, SPARSE>), grid, block, 0, stream, sc, ba); break;
+    case 0: hipLaunchKernelGGL((render_persistent_kernel<0, STATS, SPARSE, true, FIXED8>), grid, block, 0, stream, sc, ba); break;
+    case 1: hipLaunchKernelGGL((render_persistent_kernel<1, STATS, SPARSE, true, FIXED8>), grid, block, 0, stream, sc, ba); break;
+    default: hipLaunchKernelGGL((render_persistent_kernel<2, STATS, SPARSE, true, FIXED8>), grid, block, 0, stream, sc, ba); break;
+    }
+}
+
+template <bool FIXED8>
+static void launch_render_persistent_stats(const DevScene &sc, const BatchArgs &ba, dim3 grid, dim3 block, hipStream_t stream,
+                                            bool stats)
+{
+    const bool sparse = sc.m_rows != nullptr;
+    if (stats) { // diagnostics build of the same kernel
+        if (sparse) {
+            launch_render_persistent_mode<true, true, FIXED8>(sc, ba, grid, block, stream);
+        } else {
+            launch_render_persistent_mode<true, false, FIXED8>(sc, ba, grid, block, stream);
+        }
+    } else if (sparse) {
+        launch_render_persistent_mode<false, true, FIXED8>(sc, ba, grid, block, stream);
+    } else {
+        launch_render_persistent_mode<false, false, FIXED8>(sc, ba, grid, block, stream);
     }
 }
 
 hipError_t launch_render_persistent(const DevScene &sc, const BatchArgs &ba, LaunchShape shape, hipStream_t stream)
 {
     const dim3 grid(shape.blocks), block(shape.threads);
-    const bool sparse = sc.m_rows != nullptr;
-    if (shape.stats) { // diagnostics build of the same kernel
-        if (sparse) {
-            launch_render_persistent_mode<true, true>(sc, ba, grid, block, stream);
-        } else {
-            launch_render_persistent_mode<true, false>(sc, ba, grid, block, stream);
-        }
-    } else if (sparse) {
-        launch_render_persistent_mode<false, true>(sc, ba, grid, block, stream);
+    if (sc.tex_fixed8) {   // (CT_FLAG_TEX_FIXED8: the same table over the kernels that filter with 1.8 fixed-point weights)
+        launch_render_persistent_stats<true>(sc, ba, grid, block, stream, shape.stats);
     } else {
-        launch_render_persistent_mode<false, false>(sc, ba, grid, block, stream);
+        launch_render_persistent_stats<false>(sc, ba, grid, block, stream, shape.stats);
     }
     return hipGetLastError();
 }
@@ -2830,6 +2870,7 @@ hipError_t launch_render_persistent(const DevScene &sc, const BatchArgs &ba, Lau
 // One thread per pixel of one subframe, the reference's control flow verbatim (nested loops).
 // Kept as an independent second implementation on the GPU (tests cross-check it against the
 // persistent kernel and the oracle) and as the divergence baseline in bench_kernels.
+template <bool FIXED8>
 __global__ __launch_bounds__(256) void render_simple_kernel(DevScene sc, BatchArgs ba, uint32_t shard_index,
                                                             uint32_t shard_count)
 {
@@ -2880,7 +2921,7 @@ __global__ __launch_bounds__(256) void render_simple_kernel(DevScene sc, BatchAr
             bool scattered = false;
             while (in_box(sc, pos)) {
                 pos = add3(pos, stepv);
-                const float density = tex3_apron(sc, sc.dbricks, pos) * sc.density_multiplier;
+                const float density = tex3_apron<FIXED8>(sc, sc.dbricks, pos) * sc.density_multiplier;
                 c_dl++;
                 const float extinction = density * sc.sample_step;
                 T *= ct_expf(-extinction);
@@ -2896,7 +2937,7 @@ __global__ __launch_bounds__(256) void render_simple_kernel(DevScene sc, BatchAr
                 break;
             }
             const bool chopped = (sc.mode == 1) ? true : (sc.mode == 0 ? (depth != 1) : false);
-            rad = add3(rad, in_scattering(sc, pos, dir, chopped));
+            rad = add3(rad, in_scattering<FIXED8>(sc, pos, dir, chopped));
             c_il++;
             if (sc.mode == 2) {
                 break;
@@ -2919,8 +2960,13 @@ hipError_t launch_render_simple(const DevScene &sc, const BatchArgs &ba, uint32_
                                 uint32_t shard_count, hipStream_t stream)
 {
     const uint32_t tiles = sc.tiles_x * sc.tiles_y;
-    hipLaunchKernelGGL(render_simple_kernel, dim3((tiles + 3) / 4), dim3(256), 0, stream, sc, ba, shard_index,
-                       shard_count);
+    if (sc.tex_fixed8) {
+        hipLaunchKernelGGL(render_simple_kernel<true>, dim3((tiles + 3) / 4), dim3(256), 0, stream, sc, ba, shard_index,
+                           shard_count);
+    } else {
+        hipLaunchKernelGGL(render_simple_kernel<false>, dim3((tiles + 3) / 4), dim3(256), 0, stream, sc, ba, shard_index,
+                           shard_count);
+    }
     return hipGetLastError();
 }
 
@@ -2929,13 +2975,14 @@ hipError_t launch_render_simple(const DevScene &sc, const BatchArgs &ba, uint32_
 // =============================================================================================
 // getNextScatteringEvent (cloud.cuh:77-114) as a plain loop; returns true when the flight collided
 // and leaves the scatter position (or the exit position) in `pos`.
+template <bool FIXED8>
 CT_DEV bool plain_flight(const DevScene &sc, float xi, f3 &pos, f3 dir)
 {
     const f3 stepv = scale3(dir, sc.sample_step);
     float T = 1;
     while (in_box(sc, pos)) {
         pos = add3(pos, stepv);
-        const float density = tex3_apron(sc, sc.dbricks, pos) * sc.density_multiplier;
+        const float density = tex3_apron<FIXED8>(sc, sc.dbricks, pos) * sc.density_multiplier;
         const float extinction = density * sc.sample_step;
         T *= ct_expf(-extinction);
         if (xi > T) {
@@ -2948,6 +2995,7 @@ CT_DEV bool plain_flight(const DevScene &sc, float xi, f3 &pos, f3 dir)
     return false;
 }
 
+template <bool FIXED8>
 __global__ __launch_bounds__(64) void scatter_samples_kernel(DevScene sc, uint32_t count, uint32_t batch_seed,
                                                             float *__restrict__ positions,
                                                             float *__restrict__ directions)
@@ -2998,7 +3046,7 @@ __global__ __launch_bounds__(64) void scatter_samples_kernel(DevScene sc, uint32
         const f3 direction = normalize3(rdir);
         uint32_t seed2 = tea4(i * 4096u, batch_seed + attempt);
         const float xi = u24_to_float(lcg24(seed2));
-        const bool scattered = plain_flight(sc, xi, pos, direction);
+        const bool scattered = plain_flight<FIXED8>(sc, xi, pos, direction);
         if (scattered && in_box(sc, pos)) {
             out_p = sub3(pos, scale3(mk3(sc.bx, sc.by, sc.bz), 0.5f));
             out_d = rdir;
@@ -3012,8 +3060,13 @@ __global__ __launch_bounds__(64) void scatter_samples_kernel(DevScene sc, uint32
 hipError_t launch_scatter_samples(const DevScene &sc, uint32_t count, uint32_t batch_seed, float *positions,
                                   float *directions, hipStream_t stream)
 {
-    hipLaunchKernelGGL(scatter_samples_kernel, dim3((count + 63) / 64), dim3(64), 0, stream, sc, count, batch_seed,
-                       positions, directions);
+    if (sc.tex_fixed8) {
+        hipLaunchKernelGGL(scatter_samples_kernel<true>, dim3((count + 63) / 64), dim3(64), 0, stream, sc, count, batch_seed,
+                           positions, directions);
+    } else {
+        hipLaunchKernelGGL(scatter_samples_kernel<false>, dim3((count + 63) / 64), dim3(64), 0, stream, sc, count, batch_seed,
+                           positions, directions);
+    }
     return hipGetLastError();
 }
 

@@ -5,10 +5,11 @@
 //
 //   cloudtrace <cloud> [--size WxH] [--spp N] [--mode total|multi|single] [--light Side|Back|Front]
 //              [--size-m 7000] [--out DIR] [--data DIR] [--unfused] [--display] [--estimator march|delta] [--format exr|pfm]
+//              [--tex-fixed8]   filter weights in 1.8 fixed point like the reference's texture unit (CT_FLAG_TEX_FIXED8)
 //              [--gpus N | --gpus a,b,c]   one process, one shard of 8x8-pixel tiles per GPU, RCCL reduce of [mean | M2] (ct_group_*)
 //   <cloud> = file.vdb | procedural:<N>[:<seed>] | file.f32grid
 //
-//   cloudtrace collect <cloud>|@list.txt [--scene-id I] [--scenes N] [--jobs K] [--gpus ..] [--batch 2048] [--light L] [--size-m M] [--out DIR] [--data DIR] [--estimator ..]
+//   cloudtrace collect <cloud>|@list.txt [--scene-id I] [--scenes N] [--jobs K] [--gpus ..] [--batch 2048] [--light L] [--size-m M] [--out DIR] [--data DIR] [--estimator ..] [--tex-fixed8]
 //              = Tasks::collect (Tasks.cpp:114-155) for one SceneSetup: the ScatterSample, Result and DisneyDescriptor
 //              collectors one after the other over records [I * batch, (I + 1) * batch), written as flat tables
 #include <atomic>
@@ -58,6 +59,7 @@ namespace
         bool fused = true;
         bool display = false;                                                     // --display: tonemap + convergence test after every update, like the GUI
         int estimator = CT_EST_MARCH;                                             // --estimator delta: Woodcock tracking (not the reference's sampler)
+        bool texFixed8 = false;                                                   // --tex-fixed8: CT_FLAG_TEX_FIXED8, the reference's texture-unit weights
         std::vector<int32_t> devices;                                             // --gpus N | --gpus a,b,c: pixel-tile shards, RCCL frame reduce (ct_group_*)
         bool collect = false;                                                     // `cloudtrace collect ...`
         int32_t sceneId = 0;
@@ -91,6 +93,7 @@ namespace
         auto t0 = Clock::now();
         auto context = std::make_shared<Context>();
         context->devices = { device };
+        if (opt.texFixed8) context->scene.flags |= CT_FLAG_TEX_FIXED8;
         auto resources = std::make_shared<Resources>(context);
         SceneDescription scene{
             Cloud{ Cloud::Rendering{ 1.0f / 512.f, Cloud::Rendering::Mode::SunMultipleScatter },
@@ -240,6 +243,7 @@ namespace
         {
             auto context = std::make_shared<Context>();
             context->devices = opt.devices;
+            if (opt.texFixed8) context->scene.flags |= CT_FLAG_TEX_FIXED8;
             auto resources = std::make_shared<Resources>(context);
             // installSceneSetup (installers.cpp:65-105)
             const float3 direction = normalize(getLightDirection(lightDirection));
@@ -272,7 +276,7 @@ int main(int argc, char* argv[])
     try
     {
         Options opt;
-        if (argc < 2) { std::cerr << "usage: cloudtrace <cloud> [--size WxH] [--spp N] [--mode total|multi|single] [--light L] [--size-m M] [--out DIR] [--data DIR] [--unfused] [--display] [--estimator march|delta] [--format exr|pfm] [--gpus N|a,b,c]\n"; return 2; }
+        if (argc < 2) { std::cerr << "usage: cloudtrace <cloud> [--size WxH] [--spp N] [--mode total|multi|single] [--light L] [--size-m M] [--out DIR] [--data DIR] [--unfused] [--display] [--estimator march|delta] [--format exr|pfm] [--gpus N|a,b,c] [--tex-fixed8]\n"; return 2; }
         int first = 2;
         opt.cloud = argv[1];
         if (opt.cloud == "collect")
@@ -308,6 +312,7 @@ int main(int argc, char* argv[])
                 if (opt.devices.empty()) throw std::invalid_argument("--gpus N | --gpus a,b,c");
             }
             else if (a == "--display") opt.display = true;
+            else if (a == "--tex-fixed8") opt.texFixed8 = true;
             else if (a == "--estimator")
             {
                 const std::string e = next();

@@ -138,6 +138,17 @@ typedef struct CtScene {
                                        onto one of a few shared chunks (all-zero texels, a clearance rounded down to 4, 8, 16,
                                        32, 64 or 127 texels).  The kernel and its address arithmetic are the dense ones;
                                        identical results (a smaller clearance only makes the exact free-space skip shorter) */
+#define CT_FLAG_TEX_FIXED8 16u      /* filter with the reference's texture arithmetic: every linear / trilinear filter weight becomes
+                                       rint(frac * 256) / 256, round to nearest even -- the 9-bit fixed point with 8 fractional bits
+                                       in which the CUDA texture unit stores it -- exactly as the oracle's ORC_TEX_FIXED8 build does.
+                                       A weight can round up to exactly 1.0, and that value is kept.
+                                       Covers every filtered fetch: the density and the shadow volume (both estimators, the simple
+                                       kernel, the shadow-volume precompute, ct_point_radiance_launch, ct_generate_scatter_samples),
+                                       the phase tables of the NEE, and each pyramid level that ct_collect_descriptors reads.  Not
+                                       covered: the blend between two mip levels of the descriptor sampler stays exact, as in the
+                                       oracle; the CDF bisection of the scatter direction is unchanged (its weights are multiples of
+                                       1/16, which the rounding keeps).  Off (the default): the exact fraction.  The experiments
+                                       build's path-exchange kernels (CT_EXCHANGE) answer CT_E_INVAL. */
 
 /* Deterministic work counters of everything rendered since create/ct_reset
  * (the algorithmic-bytes figure is built from these). */

@@ -9,6 +9,7 @@
 #include <array>
 #include <atomic>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -16,6 +17,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <utility>
 #include <map>
 #include <vector>
 
@@ -52,6 +54,18 @@ struct CtTuning {
         return t;
     }
 };
+
+// One way to read an integer knob: atoi's reading (text that is not a number reads as 0), clamped to [lo, hi]; dflt when unset.
+static int knob_int(const Knob &k, int lo, int hi, int dflt)
+{
+    return k ? std::min(hi, std::max(lo, atoi(k.get()))) : dflt;
+}
+
+// ... and an on/off knob: on for any non-zero number.
+static bool knob_flag(const Knob &k, bool dflt)
+{
+    return k ? atoi(k.get()) != 0 : dflt;
+}
 
 struct CtHandle_ {
     CtTuning tune;         // the environment's knobs as they were at ct_create
@@ -437,6 +451,29 @@ static hipError_t dmalloc(T **p, size_t count)
     return hipMalloc((void **)p, count * sizeof(T));
 }
 
+// A device temporary (move-only): allocated by dmalloc, freed when it goes out of scope -- which its user places after the
+// stream synchronise that follows the temporary's last use.
+template <typename T>
+struct DevTemp {
+    T *p = nullptr;
+    DevTemp() = default;
+    DevTemp(DevTemp &&o) noexcept : p(std::exchange(o.p, nullptr)) {}
+    ~DevTemp()
+    {
+        if (p) {
+            hipFree(p);
+        }
+    }
+    operator T *() const { return p; }
+    T *release() { return std::exchange(p, nullptr); }
+};
+
+template <typename T>
+static hipError_t dmalloc(DevTemp<T> *t, size_t count)
+{
+    return dmalloc(&t->p, count);
+}
+
 static void release(CtHandle h)
 {
     if (!h) {
@@ -512,7 +549,7 @@ static void release(CtHandle h)
 // without one is described by its meta bytes alone, and a clearance may be rounded down without changing a result (the exact
 // free-space skip gets shorter, nothing else): the clearances are quantised to {0, 4, 8, 16, 32, 64, 127} texels, and all
 // chunks whose quantised bytes are equal are mapped onto ONE piece of memory.  For that to happen chunk boundaries must fall
-// on brick-row boundaries, so this layout pads a brick row to a power of two bricks (create_impl).  The estimator's kernel is
+// on brick-row boundaries, so this layout pads a brick row to a power of two bricks (build_march_layouts).  The estimator's kernel is
 // the dense one, unchanged -- same address arithmetic, one more level of sharing in the page tables -- and its results are
 // identical (tests/test_gpu_parity.py: test_vmm_backed_march_bricks..., the knob test with CT_SPARSE=2; tests/test_configs.py).
 static int vmm_back_mbricks(CtHandle h)
@@ -530,7 +567,7 @@ static int vmm_back_mbricks(CtHandle h)
     }
     const size_t n_chunks = (dense_bytes + chunk - 1) / chunk;
     const size_t va_size = n_chunks * chunk;
-    uint4 *d_class = nullptr;
+    DevTemp<uint4> d_class;
     HIPCHK(h, dmalloc(&d_class, n_chunks));
     std::vector<uint4> cls(n_chunks);
     uint8_t *dense = h->d_mbricks;
@@ -544,7 +581,6 @@ static int vmm_back_mbricks(CtHandle h)
             }
             hipMemAddressFree(va, va_size);
         }
-        hipFree(d_class);
     };
 #define VMMCHK(expr)                                                                                       \
     do {                                                                                                   \
@@ -608,9 +644,9 @@ static int vmm_back_mbricks(CtHandle h)
     }
     VMMCHK(hipStreamSynchronize(h->stream));
 #undef VMMCHK
-    hipFree(d_class);
     HIPCHK(h, hipFree(dense));
     h->d_mbricks = (uint8_t *)va;
+    h->dev.mbricks = h->d_mbricks;
     h->vmm.va = va;
     h->vmm.size = va_size;
     h->vmm.chunk = chunk;
@@ -628,15 +664,184 @@ static int vmm_back_mbricks(CtHandle h)
 }
 #endif
 
-static int create_impl(const CtScene *s, CtHandle h)
-{
-    const uint32_t nx = s->dims[0], ny = s->dims[1], nz = s->dims[2];
-    const size_t texels = (size_t)nx * ny * nz;
-    h->scene = *s;
-    h->device = s->device;
-    h->volume_bytes = texels;
-    h->tune = CtTuning::from_env();
+// ---- ct_create's layout stages: each builds one layout into the handle or returns a CT_* code (create_impl calls them in order)
 
+#define CT_TRY(expr)            \
+    do {                        \
+        const int rc_ = (expr); \
+        if (rc_ != CT_OK) {     \
+            return rc_;         \
+        }                       \
+    } while (0)
+
+// A brick grid is addressed with 32-bit brick indices whose xy plane has 24 bits (apron, march and twin bricks alike).
+static bool brick_indices_fit(int64_t gx, int64_t gy, int64_t gz)
+{
+    return gx * gy * gz < (1ll << 31) && gx * gy < (1ll << 24);
+}
+
+// Volumes far larger than the caches -- at 1024^3 nine fetches in ten miss L2 -- get schedules of their own.
+static bool beyond_caches(const CtScene *s)
+{
+    return (uint64_t)s->dims[0] * s->dims[1] * s->dims[2] >= 768ull * 768ull * 768ull;
+}
+
+// Bounding box [lo, hi] of the non-zero texels; an empty volume leaves lo = n, hi = -1.
+static void density_bbox(const uint8_t *t, const int32_t n[3], int32_t lo[3], int32_t hi[3])
+{
+    for (int a = 0; a < 3; a++) {
+        lo[a] = n[a];
+        hi[a] = -1;
+    }
+    for (int32_t z = 0; z < n[2]; z++) {
+        for (int32_t y = 0; y < n[1]; y++) {
+            const uint8_t *row = t + ((size_t)z * n[1] + y) * n[0];
+            int32_t x0 = 0, x1 = n[0] - 1;
+            while (x0 <= x1 && row[x0] == 0) {
+                x0++;
+            }
+            if (x0 > x1) {
+                continue;
+            }
+            while (row[x1] == 0) {
+                x1--;
+            }
+            lo[0] = std::min(lo[0], x0);
+            hi[0] = std::max(hi[0], x1);
+            lo[1] = std::min(lo[1], y);
+            hi[1] = std::max(hi[1], y);
+            lo[2] = std::min(lo[2], z);
+            hi[2] = std::max(hi[2], z);
+        }
+    }
+}
+
+// Majorant cells of the DELTA grid (orc_majorant_grid / orc_build_majorants in the oracle, same rule).  A VIRTUAL grid of cubic
+// cells of C texels covers [-bias, n + bias); stored -- and copied to LDS by every block -- is only the box of cells that can have a
+// non-zero majorant: per axis the cells whose clamped read interval [clamp(lo - 1), clamp(lo + C + 1)] meets the bounding interval
+// of the non-zero texels.  C = the smallest value >= 4 whose box fits the kernel's LDS array: the benchmark cloud at 512^3 gets
+// 10-texel cells where a grid over the whole volume allowed 16 (round 4).
+struct MajorantCells {
+    int32_t C = 4, div = 0, origin[3] = { 0, 0, 0 }, stored[3] = { 1, 1, 1 }, virt[3] = { 1, 1, 1 };
+};
+
+static MajorantCells majorant_cells(const int32_t n[3], int32_t bbias, const int32_t lo[3], const int32_t hi[3])
+{
+    MajorantCells m;
+    for (;; m.C++) {
+        const int32_t C = m.C;
+        int64_t cells = 1;
+        for (int a = 0; a < 3; a++) {
+            const int32_t v = (n[a] + 2 * bbias + C - 1) / C;
+            int32_t c0 = v, c1 = -1;
+            for (int32_t c = 0; c < v; c++) {
+                const int32_t r0 = std::min(std::max(C * c - bbias - 1, 0), n[a] - 1), r1 = std::min(std::max(C * c - bbias + C + 1, 0), n[a] - 1);
+                if (r0 <= hi[a] && r1 >= lo[a]) {
+                    c0 = std::min(c0, c);
+                    c1 = c;
+                }
+            }
+            if (c1 < c0) {   // an empty volume: one stored cell, whose majorant will be 0
+                c0 = c1 = 0;
+            }
+            m.origin[a] = c0;
+            m.stored[a] = c1 - c0 + 1;
+            m.virt[a] = v;
+            cells *= (int64_t)m.stored[a];
+        }
+        if (cells <= kMajCellsMax) {
+            break;
+        }
+    }
+    m.div = (int32_t)(((1u << 20) + (uint32_t)m.C - 1u) / (uint32_t)m.C);
+    return m;
+}
+
+// x / C as (x * div) >> 20 for every texel index of the grid (dda_begin): checked, not argued
+static bool majorant_div_exact(const MajorantCells &m)
+{
+    for (int32_t x = 0; x < (std::max({ m.virt[0], m.virt[1], m.virt[2] }) + 1) * m.C; x++) {
+        if ((int32_t)(((uint32_t)x * (uint32_t)m.div) >> 20) != x / m.C || (uint64_t)x * (uint64_t)m.div >= (1ull << 32)) {
+            return false;
+        }
+    }
+    return true;
+}
+
+// DevScene::delta_interior (render_delta_kernel drops the texel clamp), first half:
+// (a real collision has a non-zero texel in its footprint, i.e. its texel coordinate is within one texel of the non-zero
+// texels' bounding box: two texels of margin put it inside the box whatever the rounding; CT_DELTA_INTERIOR=0: always test)
+// (and a tentative collision lies in a stored cell -- to a hundredth of a texel: the error of the crossings' sums -- so
+// when the stored box, grown by one texel, is inside the brick grid its texel index needs no clamp)
+static bool cells_inside_apron(const int32_t lo[3], const int32_t hi[3], const int32_t n[3], const MajorantCells &m, const int32_t bg[3])
+{
+    for (int a = 0; a < 3; a++) {
+        if (lo[a] < 2 || hi[a] > n[a] - 3 || m.C * m.origin[a] < 1 || m.C * (m.origin[a] + m.stored[a]) > 4 * bg[a] - 1) {
+            return false;
+        }
+    }
+    return true;
+}
+
+// (delta_interior's second half for the twin layout: the stored cells, grown by a texel, inside the TWIN grid)
+static bool cells_inside_twin(const DevScene &d)
+{
+    const int32_t tg[3] = { d.t_gx, d.t_gy, d.t_gz }, o[3] = { d.mc_x0, d.mc_y0, d.mc_z0 }, st[3] = { d.mc_gx, d.mc_gy, d.mc_gz };
+    for (int a = 0; a < 3; a++) {
+        if (d.mc_cell * o[a] - d.brick_bias - 1 < -d.t_bias || d.mc_cell * (o[a] + st[a]) - d.brick_bias > 3 * tg[a] - 1 - d.t_bias) {
+            return false;
+        }
+    }
+    return true;
+}
+
+// Which of the volume's six boundary layers are empty (launch_inscatter: a march that leaves through one of those is over):
+// bit 2 * axis for the layer at 0, bit 2 * axis + 1 for the last one.
+static uint32_t zero_faces(const uint8_t *t, uint32_t nx, uint32_t ny, uint32_t nz)
+{
+    const uint32_t n[3] = { nx, ny, nz };
+    uint32_t faces = 0;
+    for (uint32_t f = 0; f < 6; f++) {
+        const uint32_t axis = f / 2, u_axis = (axis + 1) % 3, v_axis = (axis + 2) % 3;
+        uint32_t c[3];
+        c[axis] = (f & 1) ? n[axis] - 1 : 0;
+        bool zero = true;
+        for (c[v_axis] = 0; zero && c[v_axis] < n[v_axis]; c[v_axis]++) {
+            for (c[u_axis] = 0; zero && c[u_axis] < n[u_axis]; c[u_axis]++) {
+                zero = t[((size_t)c[2] * ny + c[1]) * nx + c[0]] == 0;
+            }
+        }
+        faces |= (zero ? 1u : 0u) << f;
+    }
+    return faces;
+}
+
+// How the march bricks are stored.  CT_FLAG_SPARSE_BRICKS / CT_FLAG_VMM_BRICKS choose; CT_SPARSE, set to anything, overrides both
+// (0 dense, 1 row extents, 2 virtual memory, 3 its padded rows alone, 4 virtual memory without them).
+struct MarchStorage {
+    bool sparse;         // compacted to the extents of the brick rows (compact_march_bricks; MARCH only)
+    bool vmm;            // dense addressing with sparse backing (vmm_back_mbricks; MARCH only, experiments build)
+    bool pad_rows;       // brick rows padded to a power of two bricks (for the virtual-memory chunks)
+    bool experimental;   // one of the virtual-memory layouts: the product build refuses them
+};
+
+static MarchStorage march_storage(const CtScene *s, const Knob &sparse_knob)
+{
+    bool sparse = (s->flags & CT_FLAG_SPARSE_BRICKS) != 0, vmm = (s->flags & CT_FLAG_VMM_BRICKS) != 0, pad_only = false, no_pad = false;
+    if (const char *env = sparse_knob.get()) {
+        const int v = atoi(env);
+        sparse = v == 1;
+        vmm = v == 2 || v == 4;
+        pad_only = v == 3;   // (A/B: the padded rows of the virtual-memory layout in ordinary memory)
+        no_pad = v == 4;     // (A/B: the mapping without the padded rows)
+    }
+    const bool march = s->estimator == CT_EST_MARCH;
+    vmm = vmm && march;
+    return { sparse && march, vmm && !sparse, (vmm && !no_pad) || pad_only, vmm || pad_only };
+}
+
+static int open_device(const CtScene *s, CtHandle h)
+{
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
         return fail(h, CT_E_NODEVICE, "no HIP device visible (libcloudtrace has no CPU fallback)");
@@ -651,14 +856,20 @@ static int create_impl(const CtScene *s, CtHandle h)
     for (auto &e : h->ev) {
         HIPCHK(h, hipEventCreate(&e));
     }
-    h->shape = persistent_shape(s->device, s->estimator == CT_EST_DELTA, h->tune.BLOCKS_PER_CU ? atoi(h->tune.BLOCKS_PER_CU.get()) : 0);
-    if (const char *e = h->tune.DEBUG_INVARIANTS.get()) {
-        h->debug_invariants = atoi(e) != 0;
-    }
-    h->shape.stats = h->tune.STATS.get() != nullptr || h->debug_invariants;
-    if (const char *e = h->tune.EXCHANGE.get()) {
-        h->exchange = s->estimator == CT_EST_DELTA ? std::min(2, std::max(0, atoi(e))) : 0;
-    }
+    return CT_OK;
+}
+
+// The schedule (launch shapes, scheduler constants, job queues, pipeline): defaults by estimator and volume size, then the knobs.
+static int choose_schedule(const CtScene *s, CtHandle h)
+{
+    const CtTuning &t = h->tune;
+    DevScene &d = h->dev;
+    const bool delta = s->estimator == CT_EST_DELTA, big = beyond_caches(s);
+    // (persistent_shape takes CT_BLOCKS_PER_CU from 1 to 8 and ignores other values)
+    h->shape = persistent_shape(s->device, delta, knob_int(t.BLOCKS_PER_CU, INT_MIN, INT_MAX, 0));
+    h->debug_invariants = knob_flag(t.DEBUG_INVARIANTS, h->debug_invariants);
+    h->shape.stats = t.STATS.get() != nullptr || h->debug_invariants;
+    h->exchange = delta ? knob_int(t.EXCHANGE, 0, 2, 0) : 0;
 #ifdef CT_EXPERIMENTS
     if (h->exchange && (s->flags & CT_FLAG_TEX_FIXED8)) {
         // (the path-exchange kernels are measured-and-rejected experiments: they filter with the exact weights only)
@@ -675,9 +886,82 @@ static int create_impl(const CtScene *s, CtHandle h)
                                    "CT_LIBRARY=libcloudtrace_exp.so)");
     }
 #endif
+    // measured (profiles/README.md, burst sweep): 1207 Msamples/s without bursts, 1453 with 8/32/32
+    // (re-swept on the final kernel, 512 spp per launch: burst_scatter 48 -> 40 is worth +3 %, 2871 -> 2963)
+    // DELTA: a tracking visit ends in a real collision 6 times out of 10: short bursts and an early refill
+    // (sweep at 512^3/1024^2: 8/16 -> 2300 Msamples/s, 1/16 -> 2700, 1/4 -> 2870, 3/4 -> 3460)
+    // (round 2, on the final kernel: 3/4 with scatter phases as soon as one lane waits 4200; the scatter phase held back
+    // until 16 lanes wait 4241; that with bursts of 2: 4295 -- profiles/r02e/delta_scatter_min_sweep.log)
+    // Beyond the caches every fetch is an L2 miss and longer bursts pay: 1914 vs 1855 Msamples/s at 1024^3.
+    d.march_burst = (uint32_t)knob_int(t.MARCH_BURST, 1, 1024, delta ? 2 : 8);
+    d.burst_scatter = (uint32_t)knob_int(t.BURST_SCATTER, 1, 65, delta || big ? 48 : 40);
+    d.burst_idle = (uint32_t)knob_int(t.BURST_IDLE, 1, 65, 32);
+    d.burst_march_min = (uint32_t)knob_int(t.BURST_MARCH_MIN, 1, 64, 1);
+    d.tail_burst = (uint32_t)knob_int(t.TAIL_BURST, 1, 1024, 8);
+    // (re-swept on the final kernel: 8 instead of 16 is worth +1.4 % at 512^3 and +5 % at 256^3; 16 stays best at 1024^3)
+    d.regen_min = (uint32_t)knob_int(t.REGEN_MIN, 1, 64, delta ? 4 : big ? 16 : 8);
+    // measured: running the scatter phase as soon as any lane needs it beats waiting for a fuller
+    // phase (927 vs 877 Msamples/s); a waiting lane is latency added to a serial path
+    // (DELTA: 16 until the tracking burst followed the scatter phase in one iteration; 8 / 12 / 16 / 24 / 32: 5284 / 5290 / 5273
+    // / 5168 / 5104, profiles/r04h, r04i)
+    d.scatter_min = (uint32_t)knob_int(t.SCATTER_MIN, 1, 64, delta ? 12 : 1);
+    d.scatter_num = 0;
+    d.scatter_den = 1;
+    if (const char *e = t.SCATTER_RATIO.get()) { // "num/den"
+        unsigned a = 1, b = 1;
+        if (sscanf(e, "%u/%u", &a, &b) == 2 && b > 0 && a < 1000 && b < 1000) {
+            d.scatter_num = a;
+            d.scatter_den = b;
+        }
+    }
+    d.hint_period = 64;
+    if (const char *e = t.HINT_PERIOD.get()) {
+        const int v = atoi(e);
+        d.hint_period = (v > 0 && (v & (v - 1)) == 0) ? (uint32_t)v : 0u;
+    }
+    if (delta) {
+        // measured at 512^3 / 1024^2 (profiles/r04b, r04c): 0 -> 5020 Msamples/s, 1 -> 5125 (+2.1 %: 2.8 % fewer vector
+        // instructions, the NEE miss off the bounce's critical path), 2 -> 5100 (+1.6 % although the launch moves 32 % fewer
+        // bytes: the kernel is bound by instruction issue, not by line fills -- DESIGN.md 4.2 "Round 4")
+        // ... and at 1024^3 / 2048^2, where nine fetches in ten miss L2 and the volume is four times the Infinity Cache, the
+        // twin bricks win: 0 -> 3841, 1 -> 3914, 2 -> 4562 Msamples/s (+19 %; profiles/r04d)
+        // (CT_DELTA_NEE, render_delta_kernel<.., NEE>: where a collision's two lookups come from)
+        d.delta_nee = (uint32_t)knob_int(t.DELTA_NEE, 0, 2, big ? 2 : 1);
+        h->job_work = 48.f;     // (its cost unit is a bounce; 16 measured 0.4 % slower there)
+    }
+    // measured (profiles/README.md): regional queues raise the L2 hit rate from 67 % to 77 % but not
+    // the speed (the kernel is bound by the L1 gather rate and by instruction issue, not by L2
+    // misses), and any imbalance between regions costs more than that: off unless asked for
+    // ... unless the volume is far larger than the caches: at 1024^3 (2.7 GB of march bricks) the regional
+    // queues are worth +4.5 % (1824 -> 1906 Msamples/s at 2048^2); at 512^3 they cost 0.5-2 %
+    h->queues_enabled = knob_flag(t.XCD_QUEUES, big);
+    h->regions = (uint32_t)knob_int(t.XCD_REGIONS, 1, 65536, (int)h->regions);
+    if (const char *e = t.SHARED_DEPTH.get()) {
+        h->shared_depth = (float)atof(e);
+    }
+    h->job_max = (uint32_t)knob_int(t.JOB_MAX, 1, 4096, (int)h->job_max);
+    if (const char *e = t.JOB_WORK.get()) {
+        h->job_work = (float)std::max(1.0, atof(e));
+    }
+    h->no_advance = knob_flag(t.NO_ADVANCE, h->no_advance);
+    h->point_order = knob_flag(t.POINT_ORDER, h->point_order);
+    h->continuation = knob_flag(t.CONTINUATION, h->continuation) && !h->exchange;   // (the exchange kernels run every path to its end)
+    h->chunk_interleave = knob_flag(t.CHUNK_INTERLEAVE, h->chunk_interleave);
+    if (const char *e = t.TILE_ORDER.get()) {
+        h->tile_hilbert = strcmp(e, "hilbert") == 0;
+    }
+    h->chunk_morton = knob_flag(t.CHUNK_MORTON, h->chunk_morton);
+    h->serpentine = knob_flag(t.SERPENTINE, h->serpentine);
+    h->hand_on_jobs = knob_flag(t.HAND_ON_JOBS, h->hand_on_jobs);
+    h->max_age_override = knob_int(t.MAX_AGE, 0, CtHandle_::kMaxRegions - 1, h->max_age_override);
+    h->ahead = (uint32_t)knob_int(t.RENDER_AHEAD, 0, 65535, (int)h->ahead);
+    return CT_OK;
+}
 
-    // ---- uniforms: VDBCloud::setupVolumeVariables (VDBCloud.cpp:98-111), Sun::init (Sun.cpp:13-18)
-    DevScene &d = h->dev;
+// ---- uniforms: VDBCloud::setupVolumeVariables (VDBCloud.cpp:98-111), Sun::init (Sun.cpp:13-18)
+static void scene_uniforms(const CtScene *s, DevScene &d)
+{
+    const uint32_t nx = s->dims[0], ny = s->dims[1], nz = s->dims[2];
     const float fx = (float)nx, fy = (float)ny, fz = (float)nz;
     const float maxs = fmaxf(fmaxf(fx, fy), fz);
     d.nx = (int32_t)nx;
@@ -721,140 +1005,38 @@ static int create_impl(const CtScene *s, CtHandle h)
     d.tex_fixed8 = (s->flags & CT_FLAG_TEX_FIXED8) ? 1u : 0u;   // every launcher picks its kernel by it (the shadow volume's too)
     d.tiles_x = (s->width + kTile - 1) / kTile;
     d.tiles_y = (s->height + kTile - 1) / kTile;
-    // (re-swept on the final kernel: 8 instead of 16 is worth +1.4 % at 512^3 and +5 % at 256^3; 16 stays best at 1024^3)
-    d.regen_min = 8;
-    // measured: running the scatter phase as soon as any lane needs it beats waiting for a fuller
-    // phase (927 vs 877 Msamples/s); a waiting lane is latency added to a serial path
-    d.scatter_num = 0;
-    d.scatter_den = 1;
-    d.scatter_min = 1;
-    // measured (profiles/README.md, burst sweep): 1207 Msamples/s without bursts, 1453 with 8/32/32
-    // (re-swept on the final kernel, 512 spp per launch: burst_scatter 48 -> 40 is worth +3 %, 2871 -> 2963)
-    d.march_burst = 8;
-    d.burst_scatter = 40;
-    d.burst_idle = 32;
-    if (s->estimator == CT_EST_DELTA) {
-        // a tracking visit ends in a real collision 6 times out of 10: short bursts and an early refill
-        // (sweep at 512^3/1024^2: 8/16 -> 2300 Msamples/s, 1/16 -> 2700, 1/4 -> 2870, 3/4 -> 3460)
-        // (round 2, on the final kernel: 3/4 with scatter phases as soon as one lane waits 4200; the scatter phase held back
-        // until 16 lanes wait 4241; that with bursts of 2: 4295 -- profiles/r02e/delta_scatter_min_sweep.log)
-        d.march_burst = 2;
-        d.burst_scatter = 48;
-        d.regen_min = 4;
-        d.scatter_min = 12;   // (16 until the tracking burst followed the scatter phase in one iteration; 8 / 12 / 16 / 24 / 32: 5284 / 5290 / 5273 / 5168 / 5104, profiles/r04h, r04i)
-    }
-    // measured (profiles/README.md): regional queues raise the L2 hit rate from 67 % to 77 % but not
-    // the speed (the kernel is bound by the L1 gather rate and by instruction issue, not by L2
-    // misses), and any imbalance between regions costs more than that: off unless asked for
-    h->queues_enabled = false;
-    // ... unless the volume is far larger than the caches: at 1024^3 (2.7 GB of march bricks) the regional
-    // queues are worth +4.5 % (1824 -> 1906 Msamples/s at 2048^2); at 512^3 they cost 0.5-2 %
-    if ((uint64_t)nx * ny * nz >= 768ull * 768ull * 768ull) {
-        h->queues_enabled = true;
-        d.burst_scatter = 48; // there every fetch is an L2 miss and longer bursts pay: 1914 vs 1855 Msamples/s at 1024^3
-        if (s->estimator == CT_EST_MARCH) {
-            d.regen_min = 16;
-        }
-    }
-    if (const char *e = h->tune.JOB_MAX.get()) {
-        h->job_max = (uint32_t)std::min(4096, std::max(1, atoi(e)));
-    }
-    if (s->estimator == CT_EST_DELTA) {
-        h->job_work = 48.f;     // (its cost unit is a bounce; 16 measured 0.4 % slower there)
-        // measured at 512^3 / 1024^2 (profiles/r04b, r04c): 0 -> 5020 Msamples/s, 1 -> 5125 (+2.1 %: 2.8 % fewer vector
-        // instructions, the NEE miss off the bounce's critical path), 2 -> 5100 (+1.6 % although the launch moves 32 % fewer
-        // bytes: the kernel is bound by instruction issue, not by line fills -- DESIGN.md 4.2 "Round 4")
-        d.delta_nee = 1u;
-        // ... and at 1024^3 / 2048^2, where nine fetches in ten miss L2 and the volume is four times the Infinity Cache, the
-        // twin bricks win: 0 -> 3841, 1 -> 3914, 2 -> 4562 Msamples/s (+19 %; profiles/r04d)
-        if ((uint64_t)nx * ny * nz >= 768ull * 768ull * 768ull) {
-            d.delta_nee = 2u;
-        }
-        if (const char *e = h->tune.DELTA_NEE.get()) {   // render_delta_kernel<.., NEE>: where a collision's two lookups come from
-            d.delta_nee = (uint32_t)std::min(2, std::max(0, atoi(e)));
-        }
-    }
-    if (const char *e = h->tune.JOB_WORK.get()) {
-        h->job_work = (float)std::max(1.0, atof(e));
-    }
-    if (const char *e = h->tune.NO_ADVANCE.get()) {
-        h->no_advance = atoi(e) != 0;
-    }
-    if (const char *e = h->tune.XCD_QUEUES.get()) {
-        h->queues_enabled = atoi(e) != 0;
-    }
-    d.burst_march_min = 1;
-    if (const char *e = h->tune.BURST_MARCH_MIN.get()) {
-        d.burst_march_min = (uint32_t)std::min(64, std::max(1, atoi(e)));
-    }
-    d.hint_period = 64;
-    if (const char *e = h->tune.HINT_PERIOD.get()) {
-        const int v = atoi(e);
-        d.hint_period = (v > 0 && (v & (v - 1)) == 0) ? (uint32_t)v : 0u;
-    }
-    d.tail_burst = 8;
-    if (const char *e = h->tune.TAIL_BURST.get()) {
-        d.tail_burst = (uint32_t)std::min(1024, std::max(1, atoi(e)));
-    }
-    if (const char *e = h->tune.XCD_REGIONS.get()) {
-        h->regions = (uint32_t)std::min(65536, std::max(1, atoi(e)));
-    }
-    if (const char *e = h->tune.SHARED_DEPTH.get()) {
-        h->shared_depth = (float)atof(e);
-    }
-    if (const char *e = h->tune.MARCH_BURST.get()) {
-        d.march_burst = (uint32_t)std::min(1024, std::max(1, atoi(e)));
-    }
-    if (const char *e = h->tune.BURST_SCATTER.get()) {
-        d.burst_scatter = (uint32_t)std::min(65, std::max(1, atoi(e)));
-    }
-    if (const char *e = h->tune.BURST_IDLE.get()) {
-        d.burst_idle = (uint32_t)std::min(65, std::max(1, atoi(e)));
-    }
-    if (const char *e = h->tune.SCATTER_MIN.get()) {
-        d.scatter_min = (uint32_t)std::min(64, std::max(1, atoi(e)));
-    }
-    // tuning knobs for experiments (schedule only; results never change)
-    if (const char *e = h->tune.REGEN_MIN.get()) {
-        d.regen_min = (uint32_t)std::min(64, std::max(1, atoi(e)));
-    }
-    if (const char *e = h->tune.SCATTER_RATIO.get()) { // "num/den"
-        unsigned a = 1, b = 1;
-        if (sscanf(e, "%u/%u", &a, &b) == 2 && b > 0 && a < 1000 && b < 1000) {
-            d.scatter_num = a;
-            d.scatter_den = b;
-        }
-    }
+}
 
-    // apron: farthest texel a marching path can address: slack box + the steps it fetches
-    // speculatively in one scheduler visit (kSpec in ct_kernels.hip, 8 allowed for here)
-    const int apron = (int)ceilf((0.01f + 8.0f * s->sample_step) * fmaxf(fmaxf(d.sx, d.sy), d.sz) + 0.5f) + 1;
+// The apron bricks' grid (4^3 texels each).  apron: the farthest texel a marching path can address -- slack box + the steps it
+// fetches speculatively in one scheduler visit (kSpec in ct_kernels.hip, 8 allowed for here).
+static int apron_grid(const CtScene *s, CtHandle h, int &apron)
+{
+    DevScene &d = h->dev;
+    const uint32_t nx = s->dims[0], ny = s->dims[1], nz = s->dims[2];
+    apron = (int)ceilf((0.01f + 8.0f * s->sample_step) * fmaxf(fmaxf(d.sx, d.sy), d.sz) + 0.5f) + 1;
     if (apron > 160) {
         return fail(h, CT_E_INVAL, "sample_step %g too coarse for a %u^3 volume", (double)s->sample_step,
-                    (unsigned)maxs);
+                    (unsigned)std::max({ nx, ny, nz }));
     }
     // brick coordinates = (texel index + bias) / 4, bias a multiple of 4 covering the apron
     const int bbias = ((apron + 3) / 4) * 4;
     const int64_t bgx = ((int64_t)nx + 2 * bbias + 3) / 4 + 1, bgy = ((int64_t)ny + 2 * bbias + 3) / 4 + 1,
                   bgz = ((int64_t)nz + 2 * bbias + 3) / 4 + 1;
-    if (bgx * bgy * bgz >= (1ll << 31) || bgx * bgy >= (1ll << 24)) {
+    if (!brick_indices_fit(bgx, bgy, bgz)) {
         return fail(h, CT_E_INVAL, "volume too large for 32-bit brick indices");
     }
     d.brick_bias = bbias;
-    d.nee_cache = (bgx * bgy * bgz < (1ll << 25)) ? 1u : 0u;
-    if (const char *e = h->tune.NEE_CACHE.get()) {
-        d.nee_cache = (atoi(e) != 0 && d.nee_cache) ? 1u : 0u;
-    }
-    if (const char *e = h->tune.POINT_ORDER.get()) {
-        h->point_order = atoi(e) != 0;
-    }
+    d.nee_cache = (bgx * bgy * bgz < (1ll << 25) && knob_flag(h->tune.NEE_CACHE, true)) ? 1u : 0u;
     d.brick_gx = (int32_t)bgx;
     d.brick_gxy = (int32_t)(bgx * bgy);
     d.brick_gy = (int32_t)bgy;
     d.brick_gz = (int32_t)bgz;
-    const size_t brick_bytes = (size_t)(bgx * bgy * bgz) * 128;
+    return CT_OK;
+}
 
-    // ---- Mie textures (Mie.cpp:8206-8297) + guide table
+// ---- Mie textures (Mie.cpp:8206-8297) + guide table.  mie_finite: both phase tables are finite (nee_skip_radius).
+static int upload_mie(const CtScene *s, CtHandle h, bool &mie_finite)
+{
     std::vector<float> mie_tex, chopped_tex, cdf_tex;
     std::vector<uint16_t> guide;
     mie_phase_texture(s->mie_host, s->mie_count, mie_tex);
@@ -871,16 +1053,27 @@ static int create_impl(const CtScene *s, CtHandle h)
     HIPCHK(h, hipMemcpyAsync(h->d_guide, guide.data(), (kGuideN + 2) * sizeof(uint16_t), hipMemcpyHostToDevice,
                              h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream)); // the vectors die at scope exit
-    bool mie_finite = true;   // (nee_skip_radius)
+    mie_finite = true;
     for (int i = 0; i < kMieN; i++) {
         mie_finite = mie_finite && std::isfinite(mie_tex[i]) && std::isfinite(chopped_tex[i]);
     }
-    d.mie = h->d_mie;
-    d.chopped = h->d_chopped;
-    d.cdf = h->d_cdf;
-    d.guide = h->d_guide;
+    h->dev.mie = h->d_mie;
+    h->dev.chopped = h->d_chopped;
+    h->dev.cdf = h->d_cdf;
+    h->dev.guide = h->d_guide;
+    return CT_OK;
+}
 
-    // ---- density -> corner cells; shadow volume (VDBCloud::InitInScatter) -> corner cells
+// ---- density -> corner cells, with the free-space distance field on the brick grid itself embedded as the bricks' meta byte;
+// shadow volume (VDBCloud::InitInScatter) -> corner cells: allocated here, built once it is marched (build_march_layouts)
+static int build_apron_bricks(const CtScene *s, CtHandle h)
+{
+    DevScene &d = h->dev;
+    const uint32_t nx = s->dims[0], ny = s->dims[1], nz = s->dims[2];
+    const size_t texels = h->volume_bytes;
+    const int bbias = d.brick_bias;
+    const int64_t bgx = d.brick_gx, bgy = d.brick_gy, bgz = d.brick_gz;
+    const size_t brick_bytes = (size_t)(bgx * bgy * bgz) * 128;
     HIPCHK(h, dmalloc(&h->d_density, texels));
     HIPCHK(h, dmalloc(&h->d_inscatter, texels));
     HIPCHK(h, dmalloc(&h->d_dbricks, brick_bytes));
@@ -889,343 +1082,222 @@ static int create_impl(const CtScene *s, CtHandle h)
     HIPCHK(h, launch_build_bricks(h->d_density, nx, ny, nz, bbias, (int)bgx, (int)bgy, (int)bgz, h->d_dbricks, h->stream));
     d.dbricks = h->d_dbricks;
     d.ibricks = h->d_ibricks;
-    {
-        // free-space distance field on the brick grid itself, embedded as the bricks' meta byte
-        const size_t nb = (size_t)(bgx * bgy * bgz);
-        HIPCHK(h, dmalloc(&h->d_dist, nb));
-        HIPCHK(h, dmalloc(&h->d_dist_tmp, nb));
-        HIPCHK(h, dmalloc(&h->d_majorant, nb));
-        HIPCHK(h, launch_build_dist(h->d_density, nx, ny, nz, bbias, (int)bgx, (int)bgy, (int)bgz, h->d_dist,
-                                    h->d_dist_tmp, h->d_majorant, h->stream));
-        HIPCHK(h, launch_brick_meta(h->d_dist, h->d_majorant, nx, ny, nz, bbias, (int)bgx, (int)bgy, (int)bgz,
-                                    h->d_dbricks, h->stream));
+    const size_t nb = (size_t)(bgx * bgy * bgz);
+    HIPCHK(h, dmalloc(&h->d_dist, nb));
+    HIPCHK(h, dmalloc(&h->d_dist_tmp, nb));
+    HIPCHK(h, dmalloc(&h->d_majorant, nb));
+    HIPCHK(h, launch_build_dist(h->d_density, nx, ny, nz, bbias, (int)bgx, (int)bgy, (int)bgz, h->d_dist,
+                                h->d_dist_tmp, h->d_majorant, h->stream));
+    HIPCHK(h, launch_brick_meta(h->d_dist, h->d_majorant, nx, ny, nz, bbias, (int)bgx, (int)bgy, (int)bgz,
+                                h->d_dbricks, h->stream));
+    return CT_OK;
+}
+
+// The DELTA estimator's majorant grid (majorant_cells) and the first half of delta_interior.
+static int build_majorant_grid(const CtScene *s, CtHandle h)
+{
+    DevScene &d = h->dev;
+    const uint32_t nx = s->dims[0], ny = s->dims[1], nz = s->dims[2];
+    const int32_t n[3] = { (int32_t)nx, (int32_t)ny, (int32_t)nz };
+    const int bbias = d.brick_bias;
+    int32_t lo[3], hi[3];
+    density_bbox(s->density_host, n, lo, hi);
+    const MajorantCells m = majorant_cells(n, bbias, lo, hi);
+    if (!majorant_div_exact(m)) {
+        return fail(h, CT_E_INVAL, "volume too large for the majorant grid's index arithmetic");
     }
-    if (s->estimator == CT_EST_DELTA) {
-        // Majorant cells of the DELTA grid (orc_majorant_grid / orc_build_majorants in the oracle, same rule).  A VIRTUAL grid of
-        // cubic cells of C texels covers [-bias, n + bias); stored -- and copied to LDS by every block -- is only the box of cells
-        // that can have a non-zero majorant: per axis the cells whose clamped read interval [clamp(lo - 1), clamp(lo + C + 1)] meets
-        // the bounding interval of the non-zero texels.  C = the smallest value >= 4 whose box fits the kernel's LDS array: the
-        // benchmark cloud at 512^3 gets 10-texel cells where a grid over the whole volume allowed 16 (round 4).
-        const int32_t n[3] = { (int32_t)nx, (int32_t)ny, (int32_t)nz };
-        int32_t lo[3] = { n[0], n[1], n[2] }, hi[3] = { -1, -1, -1 };
-        {
-            const uint8_t *t = s->density_host;
-            for (int32_t z = 0; z < n[2]; z++) {
-                for (int32_t y = 0; y < n[1]; y++) {
-                    const uint8_t *row = t + ((size_t)z * n[1] + y) * n[0];
-                    int32_t x0 = 0, x1 = n[0] - 1;
-                    while (x0 <= x1 && row[x0] == 0) {
-                        x0++;
-                    }
-                    if (x0 > x1) {
-                        continue;
-                    }
-                    while (row[x1] == 0) {
-                        x1--;
-                    }
-                    lo[0] = std::min(lo[0], x0);
-                    hi[0] = std::max(hi[0], x1);
-                    lo[1] = std::min(lo[1], y);
-                    hi[1] = std::max(hi[1], y);
-                    lo[2] = std::min(lo[2], z);
-                    hi[2] = std::max(hi[2], z);
-                }
-            }
-        }
-        int32_t C = 4, origin[3] = { 0, 0, 0 }, stored[3] = { 1, 1, 1 }, virt[3] = { 1, 1, 1 };
-        for (;; C++) {
-            int64_t cells = 1;
-            for (int a = 0; a < 3; a++) {
-                const int32_t v = (n[a] + 2 * bbias + C - 1) / C;
-                int32_t c0 = v, c1 = -1;
-                for (int32_t c = 0; c < v; c++) {
-                    const int32_t r0 = std::min(std::max(C * c - bbias - 1, 0), n[a] - 1), r1 = std::min(std::max(C * c - bbias + C + 1, 0), n[a] - 1);
-                    if (r0 <= hi[a] && r1 >= lo[a]) {
-                        c0 = std::min(c0, c);
-                        c1 = c;
-                    }
-                }
-                if (c1 < c0) {   // an empty volume: one stored cell, whose majorant will be 0
-                    c0 = c1 = 0;
-                }
-                origin[a] = c0;
-                stored[a] = c1 - c0 + 1;
-                virt[a] = v;
-                cells *= (int64_t)stored[a];
-            }
-            if (cells <= kMajCellsMax) {
-                break;
-            }
-        }
-        // x / C as (x * div) >> 20 for every texel index of the grid (dda_begin): checked, not argued
-        const int32_t div = (int32_t)(((1u << 20) + (uint32_t)C - 1u) / (uint32_t)C);
-        for (int32_t x = 0; x < (std::max({ virt[0], virt[1], virt[2] }) + 1) * C; x++) {
-            if ((int32_t)(((uint32_t)x * (uint32_t)div) >> 20) != x / C || (uint64_t)x * (uint64_t)div >= (1ull << 32)) {
-                return fail(h, CT_E_INVAL, "volume too large for the majorant grid's index arithmetic");
-            }
-        }
-        const size_t cells = (size_t)stored[0] * stored[1] * stored[2];
-        HIPCHK(h, dmalloc(&h->d_maj_cells, (cells + 3) & ~(size_t)3)); // the kernel copies whole words
-        HIPCHK(h, hipMemsetAsync(h->d_maj_cells, 0, (cells + 3) & ~(size_t)3, h->stream));
-        HIPCHK(h, dmalloc(&h->d_maj_codes, (cells + 3) & ~(size_t)3));
-        HIPCHK(h, hipMemsetAsync(h->d_maj_codes, 0, (cells + 3) & ~(size_t)3, h->stream));
-        HIPCHK(h, launch_majorant_cells(h->d_density, nx, ny, nz, bbias, C, origin, stored[0], stored[1], stored[2], h->d_maj_cells,
-                                        h->d_maj_codes, h->stream));
-        d.maj_cells = h->d_maj_cells;
-        d.maj_codes = h->d_maj_codes;
-        d.mc_cell = C;
-        d.mc_div = div;
-        d.mc_gx = stored[0];
-        d.mc_gy = stored[1];
-        d.mc_gz = stored[2];
-        d.mc_x0 = origin[0];
-        d.mc_y0 = origin[1];
-        d.mc_z0 = origin[2];
-        d.mc_vx = virt[0];
-        d.mc_vy = virt[1];
-        d.mc_vz = virt[2];
-        // (a real collision has a non-zero texel in its footprint, i.e. its texel coordinate is within one texel of the non-zero
-        // texels' bounding box: two texels of margin put it inside the box whatever the rounding; CT_DELTA_INTERIOR=0: always test)
-        d.delta_interior = 1u;
-        // (and a tentative collision lies in a stored cell -- to a hundredth of a texel: the error of the crossings' sums -- so
-        // when the stored box, grown by one texel, is inside the brick grid its texel index needs no clamp)
-        const int32_t bg[3] = { d.brick_gx, d.brick_gy, d.brick_gz };
-        for (int a = 0; a < 3; a++) {
-            if (lo[a] < 2 || hi[a] > n[a] - 3 || C * origin[a] < 1 || C * (origin[a] + stored[a]) > 4 * bg[a] - 1) {
-                d.delta_interior = 0u;
-            }
-        }
-        if (const char *e = h->tune.DELTA_INTERIOR.get()) {
-            d.delta_interior = (atoi(e) != 0 && d.delta_interior) ? 1u : 0u;
-        }
+    const auto &[C, div, origin, stored, virt] = m;
+    const size_t cells = (size_t)stored[0] * stored[1] * stored[2];
+    HIPCHK(h, dmalloc(&h->d_maj_cells, (cells + 3) & ~(size_t)3)); // the kernel copies whole words
+    HIPCHK(h, hipMemsetAsync(h->d_maj_cells, 0, (cells + 3) & ~(size_t)3, h->stream));
+    HIPCHK(h, dmalloc(&h->d_maj_codes, (cells + 3) & ~(size_t)3));
+    HIPCHK(h, hipMemsetAsync(h->d_maj_codes, 0, (cells + 3) & ~(size_t)3, h->stream));
+    HIPCHK(h, launch_majorant_cells(h->d_density, nx, ny, nz, bbias, C, origin, stored[0], stored[1], stored[2], h->d_maj_cells,
+                                    h->d_maj_codes, h->stream));
+    d.maj_cells = h->d_maj_cells;
+    d.maj_codes = h->d_maj_codes;
+    d.mc_cell = C;
+    d.mc_div = div;
+    d.mc_gx = stored[0];
+    d.mc_gy = stored[1];
+    d.mc_gz = stored[2];
+    d.mc_x0 = origin[0];
+    d.mc_y0 = origin[1];
+    d.mc_z0 = origin[2];
+    d.mc_vx = virt[0];
+    d.mc_vy = virt[1];
+    d.mc_vz = virt[2];
+    const int32_t bg[3] = { d.brick_gx, d.brick_gy, d.brick_gz };
+    d.delta_interior = (cells_inside_apron(lo, hi, n, m, bg) && knob_flag(h->tune.DELTA_INTERIOR, true)) ? 1u : 0u;
+    return CT_OK;
+}
+
+// Twin bricks (DevScene::tbricks): density and shadow volume of 3^3 base texels in one line, over the texel range of the apron
+// bricks (which is that of the majorant cells: every position a flight can reach).  The grid; build_march_layouts fills it.
+static int twin_grid(CtHandle h)
+{
+    DevScene &d = h->dev;
+    const int bbias = d.brick_bias, tbias = ((bbias + 2) / 3) * 3;
+    const int64_t tgx = ((int64_t)d.nx + bbias + tbias + 2) / 3 + 1, tgy = ((int64_t)d.ny + bbias + tbias + 2) / 3 + 1,
+                  tgz = ((int64_t)d.nz + bbias + tbias + 2) / 3 + 1;
+    if (!brick_indices_fit(tgx, tgy, tgz) || (int64_t)std::max({ d.nx, d.ny, d.nz }) + 2 * tbias >= (1 << 15)) {
+        return fail(h, CT_E_INVAL, "volume too large for 32-bit brick indices");
     }
-    // which of the volume's six boundary layers are empty (launch_inscatter: a march that leaves through one of those is over)
-    uint32_t zero_faces = 0;
-    {
-        const uint8_t *t = s->density_host;
-        const auto layer_is_zero = [&](int axis, uint32_t at) {
-            const uint32_t n[3] = { nx, ny, nz };
-            const uint32_t u_axis = (axis + 1) % 3, v_axis = (axis + 2) % 3;
-            for (uint32_t v = 0; v < n[v_axis]; v++) {
-                for (uint32_t u = 0; u < n[u_axis]; u++) {
-                    uint32_t c[3];
-                    c[axis] = at;
-                    c[u_axis] = u;
-                    c[v_axis] = v;
-                    if (t[((size_t)c[2] * ny + c[1]) * nx + c[0]] != 0) {
-                        return false;
-                    }
-                }
-            }
-            return true;
-        };
-        const uint32_t last[3] = { nx - 1, ny - 1, nz - 1 };
-        for (int axis = 0; axis < 3; axis++) {
-            zero_faces |= (layer_is_zero(axis, 0) ? 1u : 0u) << (2 * axis);
-            zero_faces |= (layer_is_zero(axis, last[axis]) ? 1u : 0u) << (2 * axis + 1);
-        }
+    if (hipMalloc(&h->d_tbricks, (size_t)(tgx * tgy * tgz) * 128) != hipSuccess) {
+        return fail(h, CT_E_NOMEM, "out of device memory (twin bricks)");
     }
-    {
-        // march bricks (3x4x4 texels, one meta byte per row; DevScene::mbricks).  The two scratch
-        // volumes of the distance transform are borrowed from the shadow-volume brick array's
-        // neighbourhood: plain temporaries, freed when the build has run.
-        const int mbias = ((apron + 2) / 3) * 3;
-        int64_t mgx = ((int64_t)nx + 2 * mbias + 2) / 3 + 1;
-        bool vmm = (s->flags & CT_FLAG_VMM_BRICKS) != 0;
-        bool pad_only = false;   // CT_SPARSE=3 (A/B): the padded rows of the virtual-memory layout in ordinary memory
-        if (const char *env = h->tune.SPARSE.get()) {
-            vmm = atoi(env) == 2 || atoi(env) == 4;
-            pad_only = atoi(env) == 3;
+    d.tbricks = h->d_tbricks;
+    d.t_bias = tbias;
+    d.t_gx = (int32_t)tgx;
+    d.t_gy = (int32_t)tgy;
+    d.t_gz = (int32_t)tgz;
+    if (!cells_inside_twin(d)) {
+        d.delta_interior = 0u;
+    }
+    return CT_OK;
+}
+
+// Sparse storage (BASELINE.json configs[4]: "1024^3 sparse brick-compressed density"): CT_FLAG_SPARSE_BRICKS, or
+// CT_SPARSE=0/1 in the environment.  Not the default at any size: measured at 1024^3 / 2048^2 the stored bricks
+// shrink from 3.41 GB to 0.36 GB, but the march runs 20 % slower (1670 vs 2083 Msamples/s,
+// profiles/r02c/ab_sparse_1024.log) -- the row-extent lookup is one more dependent load in a gather that is bound
+// by latency and by the L1's address rate, and only 5 % of the fetches land outside the stored extents, so there
+// are few line fills to save.  With 288 GB of HBM the dense array is the faster choice; this is the option for
+// when capacity matters.
+// Each brick row keeps its bricks from the first to the last one with a texel; the cells outside those extents get a coarse
+// clearance from the distance volume tmp_b.
+static int compact_march_bricks(CtHandle h, const uint8_t *tmp_b)
+{
+    DevScene &d = h->dev;
+    const uint32_t nx = (uint32_t)d.nx, ny = (uint32_t)d.ny, nz = (uint32_t)d.nz;
+    const int bbias = d.brick_bias;
+    const int64_t bgx = d.brick_gx, bgy = d.brick_gy, bgz = d.brick_gz, mgx = d.m_gx;
+    const size_t rows = (size_t)(bgy * bgz);
+    DevTemp<uint32_t> d_x0, d_x1;
+    DevTemp<uint8_t> compact;
+    auto run = [&]() -> int {
+        HIPCHK(h, dmalloc(&d_x0, rows));
+        HIPCHK(h, dmalloc(&d_x1, rows));
+        HIPCHK(h, hipMemsetAsync(d_x0, 0xff, rows * sizeof(uint32_t), h->stream));
+        HIPCHK(h, hipMemsetAsync(d_x1, 0, rows * sizeof(uint32_t), h->stream));
+        HIPCHK(h, launch_mbrick_extent(h->d_mbricks, (int)mgx, (int)bgy, (int)bgz, d_x0, d_x1, h->stream));
+        std::vector<uint32_t> x0(rows), x1(rows);
+        HIPCHK(h, hipMemcpyAsync(x0.data(), d_x0, rows * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(x1.data(), d_x1, rows * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        std::vector<uint2> ri(rows);
+        uint64_t lines = 0;
+        for (size_t r = 0; r < rows; r++) {
+            const uint32_t cnt = x1[r] > x0[r] ? x1[r] - x0[r] : 0u;
+            ri[r] = make_uint2((uint32_t)lines, cnt ? (x0[r] | (cnt << 16)) : 0u);
+            lines += cnt;
         }
-        vmm = vmm && s->estimator == CT_EST_MARCH;
-#ifndef CT_EXPERIMENTS
-        if (vmm || pad_only) {
-            return fail(h, CT_E_INVAL, "march bricks behind virtual memory (CT_FLAG_VMM_BRICKS, CT_SPARSE=2..4) were measured and rejected "
-                                       "(DESIGN.md 4.3 item 7b): they exist in the experiments build only (build --variant exp; CT_LIBRARY=libcloudtrace_exp.so)");
-        }
-#endif
-        const bool no_pad = h->tune.SPARSE.get() && atoi(h->tune.SPARSE.get()) == 4;   // (A/B: the mapping without the padded rows)
-        if ((vmm && !no_pad) || pad_only) {
-            // dense addressing with sparse backing (vmm_back_mbricks): chunks of 2 MiB = 2^14 bricks must hold whole brick rows for
-            // empty chunks to have equal bytes, so a row is padded to a power of two bricks (addresses cost nothing)
-            int64_t p2 = 1;
-            while (p2 < mgx) {
-                p2 <<= 1;
-            }
-            mgx = p2;
-        }
-        if (mgx * bgy * bgz >= (1ll << 31) || mgx * bgy >= (1ll << 24) || (int64_t)nx + 2 * mbias >= (1 << 17)) {
+        if (lines >= (1ull << 32)) {
             return fail(h, CT_E_INVAL, "volume too large for 32-bit brick indices");
         }
-        uint8_t *tmp_a = nullptr, *tmp_b = nullptr;
-        const size_t dense_bytes = (size_t)(mgx * bgy * bgz) * 128;
-        h->mbricks_dense_bytes = h->mbricks_bytes = dense_bytes;
-        HIPCHK(h, dmalloc(&h->d_mbricks, dense_bytes));
-        HIPCHK(h, dmalloc(&tmp_a, texels));
-        if (hipMalloc(&tmp_b, texels) != hipSuccess) {
-            hipFree(tmp_a);
-            return fail(h, CT_E_NOMEM, "out of device memory (distance transform scratch)");
-        }
-        hipError_t e = launch_build_mbricks(h->d_density, nx, ny, nz, mbias, bbias, (int)mgx, (int)bgy, (int)bgz,
-                                            tmp_a, tmp_b, h->d_mbricks, h->stream);
-        if (e == hipSuccess) {
-            // the shadow volume (VDBCloud::InitInScatter): its march towards the sun walks the (dense) march bricks
-            DevScene walk = d;
-            walk.mbricks = h->d_mbricks;
-            walk.m_bias_x = mbias;
-            walk.m_gx = (int32_t)mgx;
-            walk.m_gxy = (int32_t)(mgx * bgy);
-            e = launch_inscatter(walk, h->d_inscatter, zero_faces, h->stream);
-        }
-        if (e == hipSuccess) {
-            e = launch_build_bricks(h->d_inscatter, nx, ny, nz, bbias, (int)bgx, (int)bgy, (int)bgz, h->d_ibricks, h->stream);
-        }
-        uint8_t *tmp_c = nullptr;
-        const int nee_r = s->estimator == CT_EST_MARCH ? nee_skip_radius(d, mie_finite) : 0;
-        if (e == hipSuccess && nee_r > 0) {
-            // shadow-zero rows (bit 6 of the march bricks' meta bytes): written after the shadow volume, whose march reads the
-            // bricks, and before the sparse compaction below, which copies them.  tmp_b keeps the distance volume for it.
-            e = hipMalloc(&tmp_c, texels);
-            if (e == hipSuccess) {
-                e = launch_nee_skip_flags(h->d_inscatter, nx, ny, nz, nee_r, mbias, bbias, (int)mgx, (int)bgy, (int)bgz, tmp_a, tmp_c,
-                                          h->d_mbricks, h->stream);
-                d.nee_reach = nee_skip_reach(d);
-                h->nee_skip_r = nee_r;
-            }
-        }
-        if (e == hipSuccess && s->estimator == CT_EST_DELTA && d.delta_nee == 2u) {
-            // twin bricks (DevScene::tbricks): density and shadow volume of 3^3 base texels in one line, over the texel range
-            // of the apron bricks (which is that of the majorant cells: every position a flight can reach)
-            const int tbias = ((bbias + 2) / 3) * 3;
-            const int64_t tgx = ((int64_t)nx + bbias + tbias + 2) / 3 + 1, tgy = ((int64_t)ny + bbias + tbias + 2) / 3 + 1,
-                          tgz = ((int64_t)nz + bbias + tbias + 2) / 3 + 1;
-            if (tgx * tgy * tgz >= (1ll << 31) || tgx * tgy >= (1ll << 24) || (int64_t)std::max({ nx, ny, nz }) + 2 * tbias >= (1 << 15)) {
-                hipFree(tmp_a);
-                hipFree(tmp_b);
-                return fail(h, CT_E_INVAL, "volume too large for 32-bit brick indices");
-            }
-            if (hipMalloc(&h->d_tbricks, (size_t)(tgx * tgy * tgz) * 128) != hipSuccess) {
-                hipFree(tmp_a);
-                hipFree(tmp_b);
-                return fail(h, CT_E_NOMEM, "out of device memory (twin bricks)");
-            }
-            e = launch_build_twin_bricks(h->d_density, h->d_inscatter, nx, ny, nz, tbias, (int)tgx, (int)tgy, (int)tgz, h->d_tbricks, h->stream);
-            d.tbricks = h->d_tbricks;
-            d.t_bias = tbias;
-            d.t_gx = (int32_t)tgx;
-            d.t_gy = (int32_t)tgy;
-            d.t_gz = (int32_t)tgz;
-            // (delta_interior's second half for this layout: the stored cells, grown by a texel, inside the TWIN grid)
-            const int32_t tg[3] = { d.t_gx, d.t_gy, d.t_gz }, o[3] = { d.mc_x0, d.mc_y0, d.mc_z0 }, st[3] = { d.mc_gx, d.mc_gy, d.mc_gz };
-            for (int a = 0; a < 3; a++) {
-                if (d.mc_cell * o[a] - bbias - 1 < -tbias || d.mc_cell * (o[a] + st[a]) - bbias > 3 * tg[a] - 1 - tbias) {
-                    d.delta_interior = 0u;
-                }
-            }
-        }
-        const hipError_t e2 = hipStreamSynchronize(h->stream);
-        // Sparse storage (BASELINE.json configs[4]: "1024^3 sparse brick-compressed density"): CT_FLAG_SPARSE_BRICKS, or
-        // CT_SPARSE=0/1 in the environment.  Not the default at any size: measured at 1024^3 / 2048^2 the stored bricks
-        // shrink from 3.41 GB to 0.36 GB, but the march runs 20 % slower (1670 vs 2083 Msamples/s,
-        // profiles/r02c/ab_sparse_1024.log) -- the row-extent lookup is one more dependent load in a gather that is bound
-        // by latency and by the L1's address rate, and only 5 % of the fetches land outside the stored extents, so there
-        // are few line fills to save.  With 288 GB of HBM the dense array is the faster choice; this is the option for
-        // when capacity matters.
-        bool sparse = (s->flags & CT_FLAG_SPARSE_BRICKS) != 0;
-        if (const char *env = h->tune.SPARSE.get()) {
-            sparse = atoi(env) == 1;   // (2 = dense addressing with sparse backing, below)
-        }
-        int src = CT_OK;
-        if (e == hipSuccess && e2 == hipSuccess && sparse && s->estimator == CT_EST_MARCH) {
-            src = [&]() -> int {
-                const size_t rows = (size_t)(bgy * bgz);
-                uint32_t *d_x0 = nullptr, *d_x1 = nullptr;
-                uint8_t *compact = nullptr;
-                auto cleanup = [&]() {
-                    for (void *q : { (void *)d_x0, (void *)d_x1 }) {
-                        if (q) {
-                            hipFree(q);
-                        }
-                    }
-                };
-                auto body = [&]() -> int {
-                    HIPCHK(h, dmalloc(&d_x0, rows));
-                    HIPCHK(h, dmalloc(&d_x1, rows));
-                    HIPCHK(h, hipMemsetAsync(d_x0, 0xff, rows * sizeof(uint32_t), h->stream));
-                    HIPCHK(h, hipMemsetAsync(d_x1, 0, rows * sizeof(uint32_t), h->stream));
-                    HIPCHK(h, launch_mbrick_extent(h->d_mbricks, (int)mgx, (int)bgy, (int)bgz, d_x0, d_x1, h->stream));
-                    std::vector<uint32_t> x0(rows), x1(rows);
-                    HIPCHK(h, hipMemcpyAsync(x0.data(), d_x0, rows * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-                    HIPCHK(h, hipMemcpyAsync(x1.data(), d_x1, rows * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-                    HIPCHK(h, hipStreamSynchronize(h->stream));
-                    std::vector<uint2> ri(rows);
-                    uint64_t lines = 0;
-                    for (size_t r = 0; r < rows; r++) {
-                        const uint32_t cnt = x1[r] > x0[r] ? x1[r] - x0[r] : 0u;
-                        ri[r] = make_uint2((uint32_t)lines, cnt ? (x0[r] | (cnt << 16)) : 0u);
-                        lines += cnt;
-                    }
-                    if (lines >= (1ull << 32)) {
-                        return fail(h, CT_E_INVAL, "volume too large for 32-bit brick indices");
-                    }
-                    HIPCHK(h, dmalloc(&h->d_mrows, rows));
-                    HIPCHK(h, hipMemcpyAsync(h->d_mrows, ri.data(), rows * sizeof(uint2), hipMemcpyHostToDevice, h->stream));
-                    HIPCHK(h, dmalloc(&compact, std::max<size_t>((size_t)lines, 1) * 128));
-                    HIPCHK(h, launch_mbrick_compact(h->d_mbricks, (int)mgx, (int)bgy, (int)bgz, h->d_mrows, compact, h->stream));
-                    // clearance of the cells outside the extents: cubic cells of 8 texels over the brick grid's texel range
-                    const int cshift = 3;
-                    const int64_t cgx = (4 * bgx + 7) >> cshift, cgy = (4 * bgy + 7) >> cshift, cgz = (4 * bgz + 7) >> cshift;
-                    HIPCHK(h, dmalloc(&h->d_mcoarse, (size_t)(cgx * cgy * cgz)));
-                    HIPCHK(h, launch_coarse_clearance(tmp_b, nx, ny, nz, bbias, cshift, (int)cgx, (int)cgy, (int)cgz, h->d_mcoarse,
-                                                      h->stream));
-                    HIPCHK(h, hipStreamSynchronize(h->stream)); // `ri` dies at scope exit; the dense array is freed below
-                    HIPCHK(h, hipFree(h->d_mbricks));
-                    h->d_mbricks = compact;
-                    compact = nullptr;
-                    h->mbricks_bytes = (size_t)lines * 128;
-                    d.m_rows = h->d_mrows;
-                    d.m_coarse = h->d_mcoarse;
-                    d.m_cshift = cshift;
-                    d.m_cgx = (int32_t)cgx;
-                    d.m_cgxy = (int32_t)(cgx * cgy);
-                    return CT_OK;
-                };
-                const int rc = body();
-                if (rc != CT_OK) {
-                    hipStreamSynchronize(h->stream);
-                    if (compact) {
-                        hipFree(compact);
-                    }
-                }
-                cleanup();
-                return rc;
-            }();
-        }
-        hipFree(tmp_a);
-        hipFree(tmp_b);
-        if (tmp_c) {
-            hipFree(tmp_c);
-        }
-        HIPCHK(h, e);
-        HIPCHK(h, e2);
-        if (src != CT_OK) {
-            return src;
-        }
-#ifdef CT_EXPERIMENTS
-        if (vmm && !sparse) {
-            const int rc = vmm_back_mbricks(h);
-            if (rc != CT_OK) {
-                return rc;
-            }
-        }
-#endif
+        HIPCHK(h, dmalloc(&h->d_mrows, rows));
+        HIPCHK(h, hipMemcpyAsync(h->d_mrows, ri.data(), rows * sizeof(uint2), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, dmalloc(&compact, std::max<size_t>((size_t)lines, 1) * 128));
+        HIPCHK(h, launch_mbrick_compact(h->d_mbricks, (int)mgx, (int)bgy, (int)bgz, h->d_mrows, compact, h->stream));
+        // clearance of the cells outside the extents: cubic cells of 8 texels over the brick grid's texel range
+        const int cshift = 3;
+        const int64_t cgx = (4 * bgx + 7) >> cshift, cgy = (4 * bgy + 7) >> cshift, cgz = (4 * bgz + 7) >> cshift;
+        HIPCHK(h, dmalloc(&h->d_mcoarse, (size_t)(cgx * cgy * cgz)));
+        HIPCHK(h, launch_coarse_clearance(tmp_b, nx, ny, nz, bbias, cshift, (int)cgx, (int)cgy, (int)cgz, h->d_mcoarse,
+                                          h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream)); // `ri` dies at scope exit; the dense array is freed below
+        HIPCHK(h, hipFree(h->d_mbricks));
+        h->d_mbricks = compact.release();
         d.mbricks = h->d_mbricks;
-        d.m_bias_x = mbias;
-        d.m_gx = (int32_t)mgx;
-        d.m_gxy = (int32_t)(mgx * bgy);
+        h->mbricks_bytes = (size_t)lines * 128;
+        d.m_rows = h->d_mrows;
+        d.m_coarse = h->d_mcoarse;
+        d.m_cshift = cshift;
+        d.m_cgx = (int32_t)cgx;
+        d.m_cgxy = (int32_t)(cgx * cgy);
+        return CT_OK;
+    };
+    const int rc = run();
+    if (rc != CT_OK) {
+        hipStreamSynchronize(h->stream);   // (before the temporaries go)
     }
+    return rc;
+}
 
-    // ---- Camera::init buffers (Camera.cpp:45-48) + reset (:77-86)
+// March bricks (3x4x4 texels, one meta byte per row; DevScene::mbricks) and what is built over them up to the compaction (in the
+// order create_impl states).  A launch error skips the launches that follow and is reported after the stream synchronise.
+static int build_march_layouts(const CtScene *s, CtHandle h, int apron, const MarchStorage &ms, uint32_t zero_faces, bool mie_finite)
+{
+    DevScene &d = h->dev;
+    const uint32_t nx = s->dims[0], ny = s->dims[1], nz = s->dims[2];
+    const size_t texels = h->volume_bytes;
+    const int bbias = d.brick_bias;
+    const int64_t bgx = d.brick_gx, bgy = d.brick_gy, bgz = d.brick_gz;
+#ifndef CT_EXPERIMENTS
+    if (ms.experimental) {
+        return fail(h, CT_E_INVAL, "march bricks behind virtual memory (CT_FLAG_VMM_BRICKS, CT_SPARSE=2..4) were measured and rejected "
+                                   "(DESIGN.md 4.3 item 7b): they exist in the experiments build only (build --variant exp; CT_LIBRARY=libcloudtrace_exp.so)");
+    }
+#endif
+    const int mbias = ((apron + 2) / 3) * 3;
+    int64_t mgx = ((int64_t)nx + 2 * mbias + 2) / 3 + 1;
+    if (ms.pad_rows) {
+        // dense addressing with sparse backing (vmm_back_mbricks): chunks of 2 MiB = 2^14 bricks must hold whole brick rows for
+        // empty chunks to have equal bytes, so a row is padded to a power of two bricks (addresses cost nothing)
+        int64_t p2 = 1;
+        while (p2 < mgx) {
+            p2 <<= 1;
+        }
+        mgx = p2;
+    }
+    if (!brick_indices_fit(mgx, bgy, bgz) || (int64_t)nx + 2 * mbias >= (1 << 17)) {
+        return fail(h, CT_E_INVAL, "volume too large for 32-bit brick indices");
+    }
+    const size_t dense_bytes = (size_t)(mgx * bgy * bgz) * 128;
+    h->mbricks_dense_bytes = h->mbricks_bytes = dense_bytes;
+    HIPCHK(h, dmalloc(&h->d_mbricks, dense_bytes));
+    d.mbricks = h->d_mbricks;
+    d.m_bias_x = mbias;
+    d.m_gx = (int32_t)mgx;
+    d.m_gxy = (int32_t)(mgx * bgy);
+    DevTemp<uint8_t> tmp_a, tmp_b, tmp_c;
+    HIPCHK(h, dmalloc(&tmp_a, texels));
+    if (dmalloc(&tmp_b, texels) != hipSuccess) {
+        return fail(h, CT_E_NOMEM, "out of device memory (distance transform scratch)");
+    }
+    hipError_t e = launch_build_mbricks(h->d_density, nx, ny, nz, mbias, bbias, (int)mgx, (int)bgy, (int)bgz,
+                                        tmp_a, tmp_b, h->d_mbricks, h->stream);
+    if (e == hipSuccess) {
+        // the shadow volume (VDBCloud::InitInScatter): its march towards the sun walks the (dense) march bricks
+        e = launch_inscatter(d, h->d_inscatter, zero_faces, h->stream);
+    }
+    if (e == hipSuccess) {
+        e = launch_build_bricks(h->d_inscatter, nx, ny, nz, bbias, (int)bgx, (int)bgy, (int)bgz, h->d_ibricks, h->stream);
+    }
+    const int nee_r = s->estimator == CT_EST_MARCH ? nee_skip_radius(d, mie_finite) : 0;
+    if (e == hipSuccess && nee_r > 0) {
+        // shadow-zero rows (bit 6 of the march bricks' meta bytes)
+        e = dmalloc(&tmp_c, texels);
+        if (e == hipSuccess) {
+            e = launch_nee_skip_flags(h->d_inscatter, nx, ny, nz, nee_r, mbias, bbias, (int)mgx, (int)bgy, (int)bgz, tmp_a, tmp_c,
+                                      h->d_mbricks, h->stream);
+            d.nee_reach = nee_skip_reach(d);
+            h->nee_skip_r = nee_r;
+        }
+    }
+    if (e == hipSuccess && s->estimator == CT_EST_DELTA && d.delta_nee == 2u) {
+        CT_TRY(twin_grid(h));
+        e = launch_build_twin_bricks(h->d_density, h->d_inscatter, nx, ny, nz, d.t_bias, d.t_gx, d.t_gy, d.t_gz, h->d_tbricks, h->stream);
+    }
+    const hipError_t e2 = hipStreamSynchronize(h->stream);
+    HIPCHK(h, e);
+    HIPCHK(h, e2);
+    return ms.sparse ? compact_march_bricks(h, tmp_b) : CT_OK;
+}
+
+// ---- Camera::init buffers (Camera.cpp:45-48) + reset (:77-86), and the pipeline of enqueued batches
+static int frame_buffers(const CtScene *s, CtHandle h)
+{
     const size_t pixels = (size_t)s->width * s->height;
     HIPCHK(h, dmalloc(&h->d_frame, pixels));
     HIPCHK(h, dmalloc(&h->d_mean, pixels));
@@ -1240,37 +1312,10 @@ static int create_impl(const CtScene *s, CtHandle h)
     h->cont_capacity = (size_t)h->shape.blocks * h->shape.threads;
     HIPCHK(h, hipEventCreate(&h->ev_flush0));
     HIPCHK(h, hipEventCreate(&h->ev_flush1));
-    if (const char *e = h->tune.CONTINUATION.get()) {
-        h->continuation = atoi(e) != 0;
-    }
-    if (h->exchange) {
-        h->continuation = false;   // (the exchange kernels run every path to its end)
-    }
-    if (const char *e = h->tune.CHUNK_INTERLEAVE.get()) {
-        h->chunk_interleave = atoi(e) != 0;
-    }
-    if (const char *e = h->tune.TILE_ORDER.get()) {
-        h->tile_hilbert = strcmp(e, "hilbert") == 0;
-    }
-    if (const char *e = h->tune.CHUNK_MORTON.get()) {
-        h->chunk_morton = atoi(e) != 0;
-    }
-    if (const char *e = h->tune.SERPENTINE.get()) {
-        h->serpentine = atoi(e) != 0;
-    }
-    if (const char *e = h->tune.HAND_ON_JOBS.get()) {
-        h->hand_on_jobs = atoi(e) != 0;
-    }
-    if (const char *e = h->tune.MAX_AGE.get()) {
-        h->max_age_override = std::min(CtHandle_::kMaxRegions - 1, std::max(0, atoi(e)));
-    }
     if (h->tune.TIMELINE.get()) {
         const size_t waves = (size_t)h->shape.blocks * h->shape.threads / 64u;
         HIPCHK(h, dmalloc(&h->d_timeline, 4 * waves));
         HIPCHK(h, hipMemsetAsync(h->d_timeline, 0, 4 * waves * sizeof(unsigned long long), h->stream));
-    }
-    if (const char *e = h->tune.RENDER_AHEAD.get()) {
-        h->ahead = (uint32_t)std::min(65535, std::max(0, atoi(e)));
     }
     HIPCHK(h, dmalloc(&h->d_cont_total, 1));
     HIPCHK(h, hipMemsetAsync(h->d_cont_total, 0, sizeof(unsigned long long), h->stream));
@@ -1301,6 +1346,40 @@ static int create_impl(const CtScene *s, CtHandle h)
     HIPCHK(h, dmalloc(&h->d_primary, 2 * pixels));
     HIPCHK(h, dmalloc(&h->d_advance, (s->estimator == CT_EST_DELTA ? 4 : 1) * pixels));
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    return CT_OK;
+}
+
+// The stages in order.  The order is the dependencies between them:
+//  - the shadow volume marches over the DENSE march bricks: after them, before the sparse compaction;
+//  - the shadow-zero (NEE-skip) flags follow the shadow volume and precede the compaction, which copies the meta bytes;
+//  - the twin bricks hold the shadow volume, so they follow it;
+//  - delta_interior's second half needs the twin grid (twin_grid re-evaluates it);
+//  - the compaction's coarse clearance reads the distance volume in tmp_b, which lives until the compaction is done.
+static int create_impl(const CtScene *s, CtHandle h)
+{
+    h->scene = *s;
+    h->device = s->device;
+    h->volume_bytes = (size_t)s->dims[0] * s->dims[1] * s->dims[2];
+    h->tune = CtTuning::from_env();
+    CT_TRY(open_device(s, h));
+    CT_TRY(choose_schedule(s, h));
+    scene_uniforms(s, h->dev);
+    int apron = 0;
+    CT_TRY(apron_grid(s, h, apron));
+    bool mie_finite = true;
+    CT_TRY(upload_mie(s, h, mie_finite));
+    CT_TRY(build_apron_bricks(s, h));
+    if (s->estimator == CT_EST_DELTA) {
+        CT_TRY(build_majorant_grid(s, h));
+    }
+    const MarchStorage ms = march_storage(s, h->tune.SPARSE);
+    CT_TRY(build_march_layouts(s, h, apron, ms, zero_faces(s->density_host, s->dims[0], s->dims[1], s->dims[2]), mie_finite));
+#ifdef CT_EXPERIMENTS
+    if (ms.vmm) {
+        CT_TRY(vmm_back_mbricks(h));
+    }
+#endif
+    CT_TRY(frame_buffers(s, h));
 
     // ---- default pose: Camera.cpp:37-39 through sutil::calculateCameraVariables
     const float eye[3] = { 2.5f, -0.4f, 0.f }, lookat[3] = { 0, 0, 0 }, up[3] = { 0, 1, 0 };
@@ -1816,14 +1895,10 @@ static uint64_t scratch_slot_bytes(CtHandle h)
     // CT_SCRATCH_GIB sets the size of one of the two regions a long batch uses.  Default 16: the 1024-spp job of a 1024^2
     // frame is then ONE launch, 14 GB, instead of two of 512 -- a launch costs a few ms besides its samples -- and 28 GB of
     // scratch are a tenth of this GPU's memory.  Allocated as needed; a device that cannot give that much gets less (below).
-    uint64_t slot_bytes = 16ull << 30;
-    if (const char *e = h->tune.SCRATCH_GIB.get()) {
-        slot_bytes = (uint64_t)std::min(64, std::max(1, atoi(e))) << 30;
+    if (h->tune.SCRATCH_MIB) {   // (tests: chunks of a few pixel groups on small frames)
+        return (uint64_t)knob_int(h->tune.SCRATCH_MIB, 1, 65536, 0) << 20;
     }
-    if (const char *e = h->tune.SCRATCH_MIB.get()) {   // (tests: chunks of a few pixel groups on small frames)
-        slot_bytes = (uint64_t)std::min(65536, std::max(1, atoi(e))) << 20;
-    }
-    return slot_bytes;
+    return (uint64_t)knob_int(h->tune.SCRATCH_GIB, 1, 64, 16) << 30;
 }
 
 // How many pixel groups a launch of S subframes renders at once: what one scratch region holds (all of them when it can).
@@ -2426,8 +2501,7 @@ constexpr uint32_t kTuneSubframes = 16;
 // a pose needs its longest path either way.  Removed.)
 static uint32_t tune_subframes(CtHandle h)
 {
-    const char *e = h->tune.TUNE_SUBFRAMES.get();   // (A/B: how short may the cost-measuring launch be?)
-    return e ? (uint32_t)std::min(1024, std::max(1, atoi(e))) : kTuneSubframes;
+    return (uint32_t)knob_int(h->tune.TUNE_SUBFRAMES, 1, 1024, (int)kTuneSubframes);   // (A/B: how short may the cost-measuring launch be?)
 }
 
 static int render_accumulate_impl(CtHandle h, uint32_t first_subframe_id, uint32_t count, bool wait)
@@ -2713,11 +2787,8 @@ extern "C" int ct_point_radiance_launch(CtHandle h, CtPointRadianceTask *tasks_h
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) == hipSuccess && cus > 0) {
             const int per_cu = std::max(1, shape.blocks / cus);
-            int share = std::max(1, per_cu / std::max(1, in_flight.mine));
-            if (const char *e = h->tune.POINT_BLOCKS_PER_CU.get()) {   // (A/B)
-                share = std::min(per_cu, std::max(1, atoi(e)));
-            }
-            shape.blocks = share * cus;
+            const int share = std::max(1, per_cu / std::max(1, in_flight.mine));
+            shape.blocks = knob_int(h->tune.POINT_BLOCKS_PER_CU, 1, per_cu, share) * cus;   // (CT_POINT_BLOCKS_PER_CU: A/B)
         }
     }
     const uint32_t waves = (uint32_t)shape.blocks * (uint32_t)shape.threads / 64u;
@@ -2837,7 +2908,7 @@ extern "C" int ct_generate_scatter_samples(CtHandle h, uint32_t count, uint32_t 
     if (!positions_host_out || !directions_host_out || count == 0 || count > (1u << 20)) {
         return fail(h, CT_E_INVAL, "ct_generate_scatter_samples: need 1..2^20 samples and two output arrays");
     }
-    float *d_pos = nullptr, *d_dir = nullptr;
+    DevTemp<float> d_pos, d_dir;
     auto run = [&]() -> int {
         HIPCHK(h, dmalloc(&d_pos, 3 * (size_t)count));
         HIPCHK(h, dmalloc(&d_dir, 3 * (size_t)count));
@@ -2850,11 +2921,6 @@ extern "C" int ct_generate_scatter_samples(CtHandle h, uint32_t count, uint32_t 
     const int rc = run();
     if (rc != CT_OK) {
         hipStreamSynchronize(h->stream);
-    }
-    for (void *p : { (void *)d_pos, (void *)d_dir }) {
-        if (p) {
-            hipFree(p);
-        }
     }
     return rc;
 }
@@ -2913,8 +2979,8 @@ extern "C" int ct_collect_descriptors(CtHandle h, const float *positions_host, c
     const float voxel_m = h->scene.cloud_size_m / maxs;
     const float voxel_fp = voxel_m / h->scene.mean_free_path_m;
     const float level0 = -ct_log2f(voxel_fp) - 1;
-    float *d_pos = nullptr, *d_dir = nullptr;
-    uint8_t *d_out = nullptr;
+    DevTemp<float> d_pos, d_dir;
+    DevTemp<uint8_t> d_out;
     auto run = [&]() -> int {
         HIPCHK(h, dmalloc(&d_pos, 3 * (size_t)count));
         HIPCHK(h, dmalloc(&d_dir, 3 * (size_t)count));
@@ -2931,11 +2997,6 @@ extern "C" int ct_collect_descriptors(CtHandle h, const float *positions_host, c
     const int rc = run();
     if (rc != CT_OK) {
         hipStreamSynchronize(h->stream);
-    }
-    for (void *p : { (void *)d_pos, (void *)d_dir, (void *)d_out }) {
-        if (p) {
-            hipFree(p);
-        }
     }
     return rc;
 }
@@ -3450,13 +3511,10 @@ extern "C" int ct_debug_fetch_probe(int32_t device, uint32_t log2_lines, uint32_
     if (log2_lines < 10 || log2_lines > 28 || hipSetDevice(device) != hipSuccess) {
         return fail(nullptr, CT_E_INVAL, "ct_debug_fetch_probe: bad device or size");
     }
-    uint8_t *buf = nullptr;
-    unsigned long long *sum = nullptr;
+    DevTemp<uint8_t> buf;
+    DevTemp<unsigned long long> sum;
     const size_t bytes = (size_t)128 << log2_lines;
-    if (hipMalloc((void **)&buf, bytes) != hipSuccess || hipMalloc((void **)&sum, 8) != hipSuccess) {
-        if (buf) {
-            hipFree(buf);
-        }
+    if (dmalloc(&buf, bytes) != hipSuccess || dmalloc(&sum, 1) != hipSuccess) {
         return fail(nullptr, CT_E_NOMEM, "ct_debug_fetch_probe: out of device memory");
     }
     hipMemset(buf, 0, bytes);
@@ -3470,8 +3528,6 @@ extern "C" int ct_debug_fetch_probe(int32_t device, uint32_t log2_lines, uint32_
     }
     unsigned long long v = 0;
     hipMemcpy(&v, sum, 8, hipMemcpyDeviceToHost);
-    hipFree(buf);
-    hipFree(sum);
     if (sum_out) {
         *sum_out = v;
     }
@@ -3487,13 +3543,10 @@ extern "C" int ct_debug_fetch_probe_ws(int32_t device, uint32_t log2_threads, ui
     if (log2_threads < 10 || log2_threads > 28 || ws_lines < 1024 || ws_lines > (1ull << 28) || hipSetDevice(device) != hipSuccess) {
         return fail(nullptr, CT_E_INVAL, "ct_debug_fetch_probe_ws: bad device or size");
     }
-    uint8_t *buf = nullptr;
-    unsigned long long *sum = nullptr;
+    DevTemp<uint8_t> buf;
+    DevTemp<unsigned long long> sum;
     const size_t bytes = (size_t)128 * ws_lines;
-    if (hipMalloc((void **)&buf, bytes) != hipSuccess || hipMalloc((void **)&sum, 8) != hipSuccess) {
-        if (buf) {
-            hipFree(buf);
-        }
+    if (dmalloc(&buf, bytes) != hipSuccess || dmalloc(&sum, 1) != hipSuccess) {
         return fail(nullptr, CT_E_NOMEM, "ct_debug_fetch_probe_ws: out of device memory");
     }
     hipMemset(buf, 0, bytes);
@@ -3507,8 +3560,6 @@ extern "C" int ct_debug_fetch_probe_ws(int32_t device, uint32_t log2_threads, ui
     }
     unsigned long long v = 0;
     hipMemcpy(&v, sum, 8, hipMemcpyDeviceToHost);
-    hipFree(buf);
-    hipFree(sum);
     if (sum_out) {
         *sum_out = v;
     }

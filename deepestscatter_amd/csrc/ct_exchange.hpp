@@ -428,15 +428,7 @@ __global__ __launch_bounds__(kXThreads) void render_delta_x_kernel(DevScene sc, 
                             }
                             if (go) {
                                 if (MODE != 1 && ba.advance) {
-                                    const float4 a0 = ba.advance[4 * (size_t)pixel], a1 = ba.advance[4 * (size_t)pixel + 1];
-                                    const float4 a2 = ba.advance[4 * (size_t)pixel + 2], a3 = ba.advance[4 * (size_t)pixel + 3];
-                                    dda.org = mk3(a0.x, a0.y, a0.z);
-                                    dda.t = a0.w;
-                                    dda.tmax = mk3(a1.x, a1.y, a1.z);
-                                    dda.bx = __float_as_int(a1.w);
-                                    dda.tdelta = mk3(a2.x, a2.y, a2.z);
-                                    dda.by = __float_as_int(a2.w);
-                                    dda.bz = __float_as_int(a3.x);
+                                    load_dda_prefix(ba, pixel, dda);
                                 } else {
                                     dda_begin(sc, dda, pos, dir);
                                 }
@@ -568,26 +560,12 @@ __global__ __launch_bounds__(kXThreads) void render_delta_x_kernel(DevScene sc, 
     if (__builtin_amdgcn_ballot_w64(bad) != 0ull && lane == 0) {
         atomicAdd(&ba.stats[63], 1ull);
     }
-    uint32_t vals[3] = { c_dl, c_il, c_cap };
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-        uint32_t v = vals[i];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            v += __shfl_xor(v, off);
-        }
-        vals[i] = v;
-    }
+    const uint32_t vals[3] = { wave_sum(c_dl), wave_sum(c_il), wave_sum(c_cap) };
     if (STATS) {
         uint32_t sv[2] = { iv_dealt, iv_written };
 #pragma unroll
         for (int i = 0; i < 2; i++) {
-            uint32_t v = sv[i];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                v += __shfl_xor(v, off);
-            }
-            sv[i] = v;
+            sv[i] = wave_sum(sv[i]);
         }
         if (lane == 0) {
             atomicAdd(&ba.stats[0], (unsigned long long)st_regen);
@@ -603,14 +581,7 @@ __global__ __launch_bounds__(kXThreads) void render_delta_x_kernel(DevScene sc, 
             atomicAdd(&ba.stats[66], (unsigned long long)sv[1]);
         }
     }
-    if (lane == 0) {
-        atomicAdd(&ba.counters[2], (unsigned long long)vals[0]);
-        atomicAdd(&ba.counters[3], (unsigned long long)vals[1]);
-        atomicAdd(&ba.counters[4], (unsigned long long)vals[1]);
-        atomicAdd(&ba.counters[5], (unsigned long long)vals[2]);
-        atomicAdd(&ba.counters[6], (unsigned long long)vals[0]);
-        atomicAdd(&ba.counters[7], (unsigned long long)vals[1]);
-    }
+    flush_counters(ba, lane, vals[0], vals[1], vals[2], vals[0], vals[1]);
 }
 
 // Bytes of dynamic LDS for a pool of n_slots slots + the two rings.
@@ -912,15 +883,7 @@ __global__ __launch_bounds__(kXThreads) void render_delta_w_kernel(DevScene sc, 
                             }
                             if (go) {
                                 if (MODE != 1 && ba.advance) {
-                                    const float4 a0 = ba.advance[4 * (size_t)pixel], a1 = ba.advance[4 * (size_t)pixel + 1];
-                                    const float4 a2 = ba.advance[4 * (size_t)pixel + 2], a3 = ba.advance[4 * (size_t)pixel + 3];
-                                    dda.org = mk3(a0.x, a0.y, a0.z);
-                                    dda.t = a0.w;
-                                    dda.tmax = mk3(a1.x, a1.y, a1.z);
-                                    dda.bx = __float_as_int(a1.w);
-                                    dda.tdelta = mk3(a2.x, a2.y, a2.z);
-                                    dda.by = __float_as_int(a2.w);
-                                    dda.bz = __float_as_int(a3.x);
+                                    load_dda_prefix(ba, pixel, dda);
                                 } else {
                                     dda_begin(sc, dda, pos, dir);
                                 }
@@ -1027,26 +990,12 @@ __global__ __launch_bounds__(kXThreads) void render_delta_w_kernel(DevScene sc, 
         }
     }
 
-    uint32_t vals[3] = { c_dl, c_il, c_cap };
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-        uint32_t v = vals[i];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            v += __shfl_xor(v, off);
-        }
-        vals[i] = v;
-    }
+    const uint32_t vals[3] = { wave_sum(c_dl), wave_sum(c_il), wave_sum(c_cap) };
     if (STATS) {
         uint32_t sv[2] = { iv_dealt, iv_written };
 #pragma unroll
         for (int i = 0; i < 2; i++) {
-            uint32_t v = sv[i];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                v += __shfl_xor(v, off);
-            }
-            sv[i] = v;
+            sv[i] = wave_sum(sv[i]);
         }
         if (lane == 0) {
             atomicAdd(&ba.stats[0], (unsigned long long)st_regen);
@@ -1061,14 +1010,7 @@ __global__ __launch_bounds__(kXThreads) void render_delta_w_kernel(DevScene sc, 
             atomicAdd(&ba.stats[66], (unsigned long long)sv[1]);
         }
     }
-    if (lane == 0) {
-        atomicAdd(&ba.counters[2], (unsigned long long)vals[0]);
-        atomicAdd(&ba.counters[3], (unsigned long long)vals[1]);
-        atomicAdd(&ba.counters[4], (unsigned long long)vals[1]);
-        atomicAdd(&ba.counters[5], (unsigned long long)vals[2]);
-        atomicAdd(&ba.counters[6], (unsigned long long)vals[0]);
-        atomicAdd(&ba.counters[7], (unsigned long long)vals[1]);
-    }
+    flush_counters(ba, lane, vals[0], vals[1], vals[2], vals[0], vals[1]);
 }
 
 inline size_t delta_w_pool_bytes(uint32_t slots_per_wave)

@@ -1080,113 +1080,8 @@ hipError_t launch_inscatter(const DevScene &sc, uint8_t *out, uint32_t zero_face
     return hipGetLastError();
 }
 
-// The XCD this wave runs on (XCC_ID, hardware register 20, bits 3:0).
-CT_DEV uint32_t xcd_id()
-{
-    return (uint32_t)__builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11)) & (uint32_t)(kQueues - 1);
-}
-
-// A job the previous launch handed on (BatchArgs::left_in).  Wave-uniform.
-struct JobState {
-    uint32_t g, next, end;       // pixel group; samples [next, end) still to start: sample q is lane q & 63 of the job's subframe q >> 6
-    uint32_t base;               // scratch index of the job's first subframe, lane 0 (absolute: region, row and the group's column)
-    uint32_t first;              // subframe id of the job's first subframe
-    uint32_t age;                // the age its samples start with
-};   // (six SGPRs that live through the whole scheduler loop; the scratch's row stride is the same for every job in flight)
-
-// Where group g's 64 results of a subframe go within a subframe's row of the scratch (BatchArgs::group_rank).
-CT_DEV uint32_t group_column(const BatchArgs &ba, uint32_t g)
-{
-    return (ba.group_rank ? __builtin_amdgcn_readfirstlane(ba.group_rank[g]) - ba.rank_base : g) * 64u;
-}
-
-CT_DEV bool take_leftover(const BatchArgs &ba, uint32_t lane, bool &left_done, JobState &job)
-{
-    if (!ba.left_in || left_done) {
-        return false;
-    }
-    uint32_t i = 0;
-    if (lane == 0) {
-        i = atomicAdd(ba.left_cursor, 1u);
-    }
-    i = __builtin_amdgcn_readfirstlane(i);
-    if (i >= __builtin_amdgcn_readfirstlane(*ba.left_in_count)) {
-        left_done = true;
-        return false;
-    }
-    const uint32_t *r = ba.left_in + (size_t)i * kLeftWords;
-    job.g = __builtin_amdgcn_readfirstlane(r[0]);
-    job.next = __builtin_amdgcn_readfirstlane(r[1]);
-    job.end = __builtin_amdgcn_readfirstlane(r[2]);
-    job.base = __builtin_amdgcn_readfirstlane(r[3]);
-    job.first = __builtin_amdgcn_readfirstlane(r[4]);
-    job.age = __builtin_amdgcn_readfirstlane(r[5]);
-    return true;
-}
-
-// The rest of this wave's job goes to the next launch (see BatchArgs::left_out).  Returns false if there is no room.
-CT_DEV bool hand_on_job(const BatchArgs &ba, uint32_t lane, const JobState &job)
-{
-    uint32_t i = 0;
-    if (lane == 0) {
-        i = atomicAdd(ba.left_out_count, 1u);
-        if (i >= ba.left_capacity) {
-            atomicSub(ba.left_out_count, 1u);
-            i = 0xffffffffu;
-        } else {
-            uint4 *r = (uint4 *)(ba.left_out + (size_t)i * kLeftWords);
-            r[0] = make_uint4(job.g, job.next, job.end, job.base);
-            r[1] = make_uint4(job.first, job.age + 1u, 0u, 0u);
-        }
-    }
-    return __builtin_amdgcn_readfirstlane(i) != 0xffffffffu;
-}
-
-// Next job for this wave: from the queue it is working on (first the shared one), else from its
-// XCD's, else from the following ones.  Wave-uniform.  Returns false when every queue is empty.
-CT_DEV bool take_job(const BatchArgs &ba, uint32_t lane, uint32_t &q_cur, uint32_t &q_tried, uint32_t &job)
-{
-    while (q_tried < (uint32_t)kQueues) {
-        const uint32_t begin = ba.q_begin[q_cur], end = ba.q_begin[q_cur + 1];
-        if (begin != end) {
-            uint32_t j = 0;
-            if (lane == 0) {
-                j = atomicAdd(&ba.queue[q_cur], 1u);
-            }
-            j = __builtin_amdgcn_readfirstlane(j);
-            if (j < end - begin) {
-                job = ba.reverse ? end - 1u - j : begin + j;
-                if (j + 1u == end - begin && lane == 0) {
-                    // The last job of THIS queue.  The list is empty when that has happened to every queue that had jobs; whoever
-                    // finds it so raises the flag that the other waves look at now and then (see the suspend logic).  (Until round
-                    // 3 the flag went up with the job of the highest index, which is "the list is empty" for one queue only: with
-                    // per-XCD queues the waves did not look at it, and a busy wave learnt that nothing was left only when 16 of
-                    // its lanes had run out of work -- a launch of 10 subframes drained for 0.9 of its 4.3 ms.)
-                    uint32_t with_jobs = 0;
-                    for (uint32_t x = 0; x <= (uint32_t)kQueues; x++) {
-                        with_jobs += (ba.q_begin[x] != ba.q_begin[x + 1u]) ? 1u : 0u;
-                    }
-                    if (atomicAdd(&ba.queue[kQueueDone], 1u) + 1u == with_jobs) {
-                        __atomic_store_n(ba.queue + kQueueFlag, 1u, __ATOMIC_RELAXED);
-                    }
-                }
-                return true;
-            }
-        }
-        if (q_cur == (uint32_t)kQueues) {
-            q_cur = xcd_id();
-        } else {
-            q_tried += 1;
-            q_cur = (q_cur + 1u) & (uint32_t)(kQueues - 1);
-        }
-    }
-    return false;
-}
-
-CT_DEV uint32_t lane_rank(uint64_t mask)
-{
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
+// The wave scheduler of the two estimator kernels (render_persistent_kernel, render_delta_kernel) and their path records.
+#include "ct_sched.hpp"
 
 // No jitter also means that every sample of a pixel marches the same way until its primary ray
 // meets the first non-zero footprint: T stays 1 and xi < 1 cannot collide.  That prefix -- mostly the
@@ -1759,27 +1654,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void r
     }
 #endif
     // flush counters: per-lane tallies -> one atomic per counter per wave
-    uint32_t vals[3] = { c_dl, c_il, c_cap };
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-        uint32_t v = vals[i];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            v += __shfl_xor(v, off);
-        }
-        vals[i] = v;
-    }
+    const uint32_t vals[3] = { wave_sum(c_dl), wave_sum(c_il), wave_sum(c_cap) };
     if (STATS) {
         uint32_t sv[16] = { st_fetch, st_zero, st_skip, st_zero_d0, st_zero_d1, st_skip_iters, st_first,
                             iv_dealt, iv_resumed, iv_written, iv_suspended, st_same_line, st_dup_line, st_hit2, st_hit3, st_nee_zero };
 #pragma unroll
         for (int i = 0; i < 16; i++) {
-            uint32_t v = sv[i];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                v += __shfl_xor(v, off);
-            }
-            sv[i] = v;
+            sv[i] = wave_sum(sv[i]);
         }
         if (lane == 0) {
             atomicAdd(&ba.stats[0], (unsigned long long)st_regen);
@@ -1817,14 +1698,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void r
             atomicAdd(&ba.stats[72], (unsigned long long)sv[15]);
         }
     }
-    if (lane == 0) {
-        atomicAdd(&ba.counters[2], (unsigned long long)vals[0]);
-        atomicAdd(&ba.counters[3], (unsigned long long)vals[1]);
-        atomicAdd(&ba.counters[4], (unsigned long long)vals[1]); // scatter events == NEE lookups
-        atomicAdd(&ba.counters[5], (unsigned long long)vals[2]);
-        atomicAdd(&ba.counters[6], (unsigned long long)w_fetch);
-        atomicAdd(&ba.counters[7], (unsigned long long)w_nee);
-    }
+    flush_counters(ba, lane, vals[0], vals[1], vals[2], w_fetch, w_nee);
 }
 
 // =============================================================================================
@@ -1983,13 +1857,6 @@ constexpr uint32_t DELTA_CHECK_EVERY = CT_DELTA_CHECK_EVERY;
 #endif
 constexpr bool DELTA_END_MERGE = CT_DELTA_END_MERGE != 0;
 constexpr int kDeltaThreads = CT_DELTA_THREADS;
-
-struct Dda {
-    f3 org;            // origin of the flight (box coordinates), positions are fma(dir, t, org)
-    float t;
-    f3 tmax, tdelta;   // ray parameter at the next cell boundary per axis / between boundaries
-    int32_t bx, by, bz;
-};
 
 // Is the flight's cell one of the STORED cells (the box around the cloud)?  A flight that leaves the box is over: a straight
 // line does not come back into a box, and outside it every cell is empty (no random number is drawn there).
@@ -2374,16 +2241,7 @@ __global__ __launch_bounds__(kDeltaThreads) __attribute__((amdgpu_waves_per_eu(C
                         }
                         if (go) {
                             if (MODE != 1 && ba.advance) {
-                                // the pixel's pre-walked DDA prefix (primary_advance_delta_kernel)
-                                const float4 a0 = ba.advance[4 * (size_t)pixel], a1 = ba.advance[4 * (size_t)pixel + 1];
-                                const float4 a2 = ba.advance[4 * (size_t)pixel + 2], a3 = ba.advance[4 * (size_t)pixel + 3];
-                                dda.org = mk3(a0.x, a0.y, a0.z);
-                                dda.t = a0.w;
-                                dda.tmax = mk3(a1.x, a1.y, a1.z);
-                                dda.bx = __float_as_int(a1.w);
-                                dda.tdelta = mk3(a2.x, a2.y, a2.z);
-                                dda.by = __float_as_int(a2.w);
-                                dda.bz = __float_as_int(a3.x);
+                                load_dda_prefix(ba, pixel, dda);
                             } else {
                                 dda_begin(sc, dda, pos, dir);
                             }
@@ -2689,26 +2547,12 @@ __global__ __launch_bounds__(kDeltaThreads) __attribute__((amdgpu_waves_per_eu(C
         }
     }
 
-    uint32_t vals[3] = { c_dl, c_il, c_cap };
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-        uint32_t v = vals[i];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            v += __shfl_xor(v, off);
-        }
-        vals[i] = v;
-    }
+    const uint32_t vals[3] = { wave_sum(c_dl), wave_sum(c_il), wave_sum(c_cap) };
     if (STATS) {
         uint32_t sv[8] = { st_fetch, st_zero, st_skip, iv_dealt, iv_resumed, iv_written, iv_suspended, st_empty };
 #pragma unroll
         for (int i = 0; i < 8; i++) {
-            uint32_t v = sv[i];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                v += __shfl_xor(v, off);
-            }
-            sv[i] = v;
+            sv[i] = wave_sum(sv[i]);
         }
         if (lane == 0) {
             atomicAdd(&ba.stats[0], (unsigned long long)st_regen);
@@ -2732,15 +2576,8 @@ __global__ __launch_bounds__(kDeltaThreads) __attribute__((amdgpu_waves_per_eu(C
             atomicAdd(&ba.stats[67], (unsigned long long)sv[6]);
         }
     }
-    if (lane == 0) {
-        atomicAdd(&ba.counters[2], (unsigned long long)vals[0]);
-        atomicAdd(&ba.counters[3], (unsigned long long)vals[1]);
-        atomicAdd(&ba.counters[4], (unsigned long long)vals[1]);
-        atomicAdd(&ba.counters[5], (unsigned long long)vals[2]);
-        // this kernel issues one fetch per counted lookup: cells below their lower bound are neither counted nor fetched
-        atomicAdd(&ba.counters[6], (unsigned long long)vals[0]);
-        atomicAdd(&ba.counters[7], (unsigned long long)vals[1]);
-    }
+    // this kernel issues one fetch per counted lookup: cells below their lower bound are neither counted nor fetched
+    flush_counters(ba, lane, vals[0], vals[1], vals[2], vals[0], vals[1]);
 }
 
 template <bool STATS, int NEE, bool FIXED8>

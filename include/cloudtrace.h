@@ -106,6 +106,8 @@ typedef struct CtScene {
     float light_intensity;    /* 1e6 */
 
     /* --- Camera::Settings, src/Scene/Cameras/Camera.h:20-28 --- */
+    /* The largest frame ct_create accepts is 12288 x 4096 (width: the tonemap kernel keeps a row of column sums in LDS;
+     * height: the seed packs x * 4096 + y); anything larger, or 0, is CT_E_INVAL. */
     uint32_t width, height;
 
     /* --- Mie tables: Scene::init binds them (Scene.cpp:38-40); data of Mie.cpp:8-8203 --- */

@@ -18,6 +18,8 @@ CT_MODE_SUN_AND_SKY_ALL_SCATTER, CT_MODE_SUN_MULTIPLE_SCATTER, CT_MODE_SUN_SINGL
 CT_EST_MARCH, CT_EST_DELTA = 0, 1
 CT_BUF_MEAN, CT_BUF_M2, CT_BUF_FRAME, CT_BUF_SCREEN, CT_BUF_INSCATTER, CT_BUF_DENSITY = range(6)
 CT_FLAG_NONE, CT_FLAG_SIMPLE_KERNEL, CT_FLAG_LIGHT_NORMALIZED, CT_FLAG_SPARSE_BRICKS, CT_FLAG_VMM_BRICKS = 0, 1, 2, 4, 8
+(CT_LAYOUT_DENSITY_BRICKS, CT_LAYOUT_SHADOW_BRICKS, CT_LAYOUT_MARCH_BRICKS, CT_LAYOUT_MARCH_ROWS, CT_LAYOUT_MARCH_COARSE,
+ CT_LAYOUT_TWIN_BRICKS, CT_LAYOUT_MAJORANT_CELLS, CT_LAYOUT_MAJORANT_CODES) = range(8)   # ct_debug_layout
 CT_FLAG_TEX_FIXED8 = 16   # filter weights in 1.8 fixed point, like the reference's texture unit (include/cloudtrace.h)
 
 # every symbol include/cloudtrace.h declares (tests check the library exports all of them)
@@ -25,7 +27,7 @@ EXPORTS = [
     "ct_create", "ct_destroy", "ct_last_error", "ct_set_stream", "ct_set_camera", "ct_render_subframe",
     "ct_accumulate", "ct_render_accumulate", "ct_render_accumulate_async", "ct_synchronize", "ct_copy_to_device_async", "ct_point_radiance_launch", "ct_generate_scatter_samples", "ct_collect_descriptors", "ct_reset", "ct_tonemap", "ct_tonemap_async", "ct_set_render_ahead", "ct_rendered_subframes", "ct_set_stop_when_converged", "ct_converged_at", "ct_is_converged", "ct_tonemap_buffer", "ct_is_converged_buffers", "ct_download", "ct_upload",
     "ct_buffer_bytes", "ct_copy_to_device", "ct_device_ptr", "ct_subframes", "ct_set_subframes", "ct_counters", "ct_kernel_time",
-    "ct_debug_cdf_inversion", "ct_debug_math_selftest", "ct_debug_fetch_probe", "ct_debug_fetch_probe_ws", "ct_debug_track_lines", "ct_debug_touched_lines", "ct_debug_stats", "ct_debug_stats_ex", "ct_debug_suspended", "ct_debug_timeline", "ct_debug_invariants", "ct_debug_memory", "ct_debug_delta_grid", "ct_debug_march_meta", "ct_fetch_counters", "ct_calculate_camera_variables", "ct_quantize_volume", "ct_load_vdb", "ct_generate_mipmaps",
+    "ct_debug_cdf_inversion", "ct_debug_math_selftest", "ct_debug_fetch_probe", "ct_debug_fetch_probe_ws", "ct_debug_track_lines", "ct_debug_touched_lines", "ct_debug_stats", "ct_debug_stats_ex", "ct_debug_suspended", "ct_debug_timeline", "ct_debug_invariants", "ct_debug_memory", "ct_debug_delta_grid", "ct_debug_march_meta", "ct_debug_layout", "ct_fetch_counters", "ct_calculate_camera_variables", "ct_quantize_volume", "ct_load_vdb", "ct_generate_mipmaps",
     "ct_tile_owner", "ct_make_procedural_cloud",
     "ct_group_create", "ct_group_destroy", "ct_group_last_error", "ct_group_size", "ct_group_handle", "ct_group_set_camera",
     "ct_group_render_accumulate", "ct_group_reset", "ct_group_merge", "ct_group_download", "ct_group_tonemap",
@@ -145,6 +147,7 @@ def load():
         "ct_debug_memory": (i32, [vp, vp]),
         "ct_debug_delta_grid": (i32, [vp, vp]),
         "ct_debug_march_meta": (i32, [vp, vp, vp, C.c_size_t]),
+        "ct_debug_layout": (i32, [vp, i32, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
         "ct_fetch_counters": (i32, [vp, C.POINTER(CtFetchCounters)]),
         "ct_debug_fetch_probe": (i32, [i32, u32, u32, C.POINTER(C.c_uint64)]),
         "ct_debug_fetch_probe_ws": (i32, [i32, u32, C.c_uint64, u32, C.POINTER(C.c_uint64)]),

@@ -449,6 +449,33 @@ class CloudTracer:
             d["meta"] = meta
         return d
 
+    LAYOUTS = ("density_bricks", "shadow_bricks", "march_bricks", "march_rows", "march_coarse", "twin_bricks", "majorant_cells",
+               "majorant_codes")
+
+    def layout(self, which) -> tuple[np.ndarray, dict]:
+        """The device bytes of one volume layout as stored, and the geometry that indexes it (ct_debug_layout): `which` is a
+        name of LAYOUTS or a CT_LAYOUT_* value.  Bricks come as uint8 [bz, by, bx, 128] (sparse march bricks: [stored brick,
+        128]), the row table as uint32 [bz, by, 2], the coarse grid and the majorant cells / codes as uint8 [z, y, x].  A
+        layout the handle does not have raises CloudTraceError(CT_E_INVAL)."""
+        which = self.LAYOUTS.index(which) if isinstance(which, str) else int(which)
+        geom, n = np.zeros(16, np.uint32), C.c_size_t(0)
+        check(self.L.ct_debug_layout(self.h, which, _p(geom), C.c_void_p(), 0, C.byref(n)), self.h)
+        g = [int(v) for v in geom]
+        raw = np.zeros(n.value, np.uint8)
+        check(self.L.ct_debug_layout(self.h, which, _p(geom), _p(raw), raw.size, C.byref(n)), self.h)
+        if which in (_lib.CT_LAYOUT_DENSITY_BRICKS, _lib.CT_LAYOUT_SHADOW_BRICKS, _lib.CT_LAYOUT_TWIN_BRICKS):
+            d = {"bias": g[0], "bricks": tuple(g[1:4])}
+            return raw.reshape(g[3], g[2], g[1], 128), d
+        if which == _lib.CT_LAYOUT_MARCH_BRICKS:
+            d = {"bias_x": g[0], "bias": g[1], "bricks": tuple(g[2:5]), "sparse": bool(g[5])}
+            return (raw.reshape(-1, 128) if d["sparse"] else raw.reshape(g[4], g[3], g[2], 128)), d
+        if which == _lib.CT_LAYOUT_MARCH_ROWS:
+            return raw.view(np.uint32).reshape(g[1], g[0], 2), {"rows": (g[0], g[1])}
+        if which == _lib.CT_LAYOUT_MARCH_COARSE:
+            return raw.reshape(g[3], g[2], g[1]), {"shift": g[0], "cells": tuple(g[1:4]), "bias": g[4]}
+        d = {"cell": g[0], "div": g[1], "stored": tuple(g[2:5]), "origin": tuple(g[5:8]), "virtual": tuple(g[8:11]), "bias": g[11]}
+        return raw.reshape(g[4], g[3], g[2]), d
+
     def kernel_time(self):
         """-> (estimator kernel ms, accumulate kernel ms, estimator launches) since create/reset."""
         a, b, n = C.c_double(0), C.c_double(0), C.c_uint64(0)

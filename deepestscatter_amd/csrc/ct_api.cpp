@@ -3483,6 +3483,103 @@ extern "C" int ct_debug_march_meta(CtHandle h, uint32_t geom_out[8], uint8_t *me
     return CT_OK;
 }
 
+// The device bytes of one volume layout as stored, and the geometry that indexes it (include/cloudtrace.h).  No kernel: a
+// stream synchronise and one copy.
+extern "C" int ct_debug_layout(CtHandle h, int32_t which, uint32_t geom_out[16], void *dst_host, size_t capacity, size_t *bytes_out)
+{
+    NEED(h);
+    if (!geom_out || !bytes_out) {
+        return fail(h, CT_E_INVAL, "geom_out or bytes_out is NULL");
+    }
+    const DevScene &d = h->dev;
+    uint32_t g[16] = { 0 };
+    const void *src = nullptr;
+    size_t bytes = 0;
+    const size_t apron_bytes = (size_t)d.brick_gxy * (size_t)d.brick_gz * 128;
+    switch (which) {
+    case CT_LAYOUT_DENSITY_BRICKS:
+    case CT_LAYOUT_SHADOW_BRICKS:
+        src = which == CT_LAYOUT_DENSITY_BRICKS ? h->d_dbricks : h->d_ibricks;
+        bytes = apron_bytes;
+        g[0] = (uint32_t)d.brick_bias;
+        g[1] = (uint32_t)d.brick_gx;
+        g[2] = (uint32_t)d.brick_gy;
+        g[3] = (uint32_t)d.brick_gz;
+        break;
+    case CT_LAYOUT_MARCH_BRICKS:
+        src = h->vmm.va ? nullptr : h->d_mbricks;   // (a virtual range with holes cannot be copied)
+        bytes = h->mbricks_bytes;
+        g[0] = (uint32_t)d.m_bias_x;
+        g[1] = (uint32_t)d.brick_bias;
+        g[2] = (uint32_t)d.m_gx;
+        g[3] = (uint32_t)d.brick_gy;
+        g[4] = (uint32_t)d.brick_gz;
+        g[5] = d.m_rows ? 1u : 0u;
+        break;
+    case CT_LAYOUT_MARCH_ROWS:
+        src = h->d_mrows;
+        bytes = (size_t)d.brick_gy * (size_t)d.brick_gz * sizeof(uint2);
+        g[0] = (uint32_t)d.brick_gy;
+        g[1] = (uint32_t)d.brick_gz;
+        break;
+    case CT_LAYOUT_MARCH_COARSE:
+        src = h->d_mcoarse;
+        if (src) {
+            const int32_t cgy = d.m_cgxy / d.m_cgx, cgz = (4 * d.brick_gz + 7) >> d.m_cshift;   // (compact_march_bricks)
+            bytes = (size_t)d.m_cgxy * (size_t)cgz;
+            g[0] = (uint32_t)d.m_cshift;
+            g[1] = (uint32_t)d.m_cgx;
+            g[2] = (uint32_t)cgy;
+            g[3] = (uint32_t)cgz;
+            g[4] = (uint32_t)d.brick_bias;
+        }
+        break;
+    case CT_LAYOUT_TWIN_BRICKS:
+        src = h->d_tbricks;
+        bytes = (size_t)d.t_gx * (size_t)d.t_gy * (size_t)d.t_gz * 128;
+        g[0] = (uint32_t)d.t_bias;
+        g[1] = (uint32_t)d.t_gx;
+        g[2] = (uint32_t)d.t_gy;
+        g[3] = (uint32_t)d.t_gz;
+        break;
+    case CT_LAYOUT_MAJORANT_CELLS:
+    case CT_LAYOUT_MAJORANT_CODES:
+        src = which == CT_LAYOUT_MAJORANT_CELLS ? h->d_maj_cells : h->d_maj_codes;
+        bytes = (size_t)d.mc_gx * (size_t)d.mc_gy * (size_t)d.mc_gz;
+        g[0] = (uint32_t)d.mc_cell;
+        g[1] = (uint32_t)d.mc_div;
+        g[2] = (uint32_t)d.mc_gx;
+        g[3] = (uint32_t)d.mc_gy;
+        g[4] = (uint32_t)d.mc_gz;
+        g[5] = (uint32_t)d.mc_x0;
+        g[6] = (uint32_t)d.mc_y0;
+        g[7] = (uint32_t)d.mc_z0;
+        g[8] = (uint32_t)d.mc_vx;
+        g[9] = (uint32_t)d.mc_vy;
+        g[10] = (uint32_t)d.mc_vz;
+        g[11] = (uint32_t)d.brick_bias;
+        break;
+    default:
+        return fail(h, CT_E_INVAL, "ct_debug_layout: unknown layout %d", which);
+    }
+    if (!src) {
+        return fail(h, CT_E_INVAL, "ct_debug_layout: this handle has no layout %d", which);
+    }
+    memcpy(geom_out, g, sizeof g);
+    *bytes_out = bytes;
+    if (!dst_host) {
+        return CT_OK;
+    }
+    if (capacity < bytes) {
+        return fail(h, CT_E_INVAL, "ct_debug_layout: layout %d has %zu bytes, capacity %zu", which, bytes, capacity);
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (bytes) {
+        HIPCHK(h, hipMemcpy(dst_host, src, bytes, hipMemcpyDeviceToHost));
+    }
+    return CT_OK;
+}
+
 extern "C" int ct_debug_timeline(CtHandle h, uint64_t *out, uint32_t waves)
 {
     NEED(h);

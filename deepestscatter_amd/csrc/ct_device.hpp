@@ -84,6 +84,10 @@ constexpr int kMajCellsMax = 43008;   // cells of the DELTA majorant grid (one b
                                       // which left a 256^3 volume (35^3 = 42875 cells of 8 texels) with 16-texel cells
 
 // All uniforms of the path: the OptiX variable scopes of SURVEY section 8b, flattened.
+// The comments on the volume layouts below (apron, march, sparse and twin bricks, the majorant grid) are their definition:
+// tests/test_layouts.py reads every one of them back (ct_debug_layout) and holds it, byte for byte, to a numpy reference
+// written from these comments alone -- a stored clearance, distance or majorant may be neither more generous NOR more
+// conservative than what they say.  Change a layout and its comment together, and that test with them.
 struct DevScene {
     // Volumes live in HBM as "apron bricks": one 128-byte cache line per 4x4x4 texels holding the
     // 5x5x5 texels [4b, 4b+4]^3 (clamp-to-edge applied) at byte lz*25 + ly*5 + lx.  The 2x2x2

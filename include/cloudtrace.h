@@ -431,6 +431,34 @@ CT_API int ct_debug_delta_grid(CtHandle h, uint32_t out[8]);
  * row, [z][y][brick x] with z, y in [0, 4 * bricks): the row of base texels x = 3 bx - x bias .. +2, y - bias, z - bias. */
 CT_API int ct_debug_march_meta(CtHandle h, uint32_t geom_out[8], uint8_t *meta_out, size_t capacity);
 
+/* The raw bytes of one of the volume layouts that ct_create builds on the device, as stored (diagnostic; tests/test_layouts.py
+ * holds every one of them to a brute-force reference).  Waits for the handle's stream, fills geom_out with what is needed to
+ * index the structure (unused words 0), stores its size in *bytes_out and, when dst_host is not NULL, copies it there.
+ * A structure the handle does not have (twin bricks without the twin layout, the row table of dense march bricks, the
+ * majorant grid of a MARCH handle), an unknown `which` and a capacity below the size answer CT_E_INVAL.
+ *   CT_LAYOUT_DENSITY_BRICKS, CT_LAYOUT_SHADOW_BRICKS   128 bytes per apron brick, x fastest;
+ *                             geom: [0] bias, [1..3] bricks x, y, z
+ *   CT_LAYOUT_MARCH_BRICKS    128 bytes per march brick: dense x fastest, or (sparse) the stored bricks row after row;
+ *                             geom: [0] x bias, [1] y/z bias, [2..4] bricks x, y, z of the dense grid, [5] 1 when sparse
+ *   CT_LAYOUT_MARCH_ROWS      (sparse) two uint32 per brick row (by, bz), y fastest: index of the row's first stored brick,
+ *                             first brick x | count << 16;  geom: [0] rows in y, [1] rows in z
+ *   CT_LAYOUT_MARCH_COARSE    (sparse) one byte per coarse cell, x fastest;  geom: [0] log2 of the cell edge, [1..3] cells x, y, z,
+ *                             [4] bias
+ *   CT_LAYOUT_TWIN_BRICKS     128 bytes per twin brick, x fastest;  geom: [0] bias, [1..3] bricks x, y, z
+ *   CT_LAYOUT_MAJORANT_CELLS, CT_LAYOUT_MAJORANT_CODES   one byte per stored cell, x fastest;  geom: [0] cell edge, [1] mc_div,
+ *                             [2..4] stored cells x, y, z, [5..7] first stored cell, [8..10] virtual cells, [11] bias */
+enum {
+    CT_LAYOUT_DENSITY_BRICKS = 0,
+    CT_LAYOUT_SHADOW_BRICKS = 1,
+    CT_LAYOUT_MARCH_BRICKS = 2,
+    CT_LAYOUT_MARCH_ROWS = 3,
+    CT_LAYOUT_MARCH_COARSE = 4,
+    CT_LAYOUT_TWIN_BRICKS = 5,
+    CT_LAYOUT_MAJORANT_CELLS = 6,
+    CT_LAYOUT_MAJORANT_CODES = 7
+};
+CT_API int ct_debug_layout(CtHandle h, int32_t which, uint32_t geom_out[16], void *dst_host, size_t capacity, size_t *bytes_out);
+
 /* PMC calibration probe (no handle): allocates 2^log2_lines 128-byte lines on `device`, and has one
  * thread per line issue the estimator's access pattern (two unaligned 8-byte loads at byte 13 and
  * byte 38 of a pseudo-randomly chosen, never repeated line).  Under rocprofv3 --pmc FETCH_SIZE this

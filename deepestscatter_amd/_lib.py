@@ -24,12 +24,12 @@ CT_FLAG_TEX_FIXED8 = 16   # filter weights in 1.8 fixed point, like the referenc
 
 # every symbol include/cloudtrace.h declares (tests check the library exports all of them)
 EXPORTS = [
-    "ct_create", "ct_destroy", "ct_last_error", "ct_set_stream", "ct_set_camera", "ct_render_subframe",
+    "ct_create", "ct_destroy", "ct_last_error", "ct_set_stream", "ct_set_camera", "ct_set_light", "ct_render_subframe",
     "ct_accumulate", "ct_render_accumulate", "ct_render_accumulate_async", "ct_synchronize", "ct_copy_to_device_async", "ct_point_radiance_launch", "ct_generate_scatter_samples", "ct_collect_descriptors", "ct_reset", "ct_tonemap", "ct_tonemap_async", "ct_set_render_ahead", "ct_rendered_subframes", "ct_set_stop_when_converged", "ct_converged_at", "ct_is_converged", "ct_tonemap_buffer", "ct_is_converged_buffers", "ct_download", "ct_upload",
     "ct_buffer_bytes", "ct_copy_to_device", "ct_device_ptr", "ct_subframes", "ct_set_subframes", "ct_counters", "ct_kernel_time",
     "ct_debug_cdf_inversion", "ct_debug_math_selftest", "ct_debug_fetch_probe", "ct_debug_fetch_probe_ws", "ct_debug_track_lines", "ct_debug_touched_lines", "ct_debug_stats", "ct_debug_stats_ex", "ct_debug_suspended", "ct_debug_timeline", "ct_debug_invariants", "ct_debug_memory", "ct_debug_delta_grid", "ct_debug_march_meta", "ct_debug_layout", "ct_fetch_counters", "ct_calculate_camera_variables", "ct_quantize_volume", "ct_load_vdb", "ct_generate_mipmaps",
     "ct_tile_owner", "ct_make_procedural_cloud",
-    "ct_group_create", "ct_group_destroy", "ct_group_last_error", "ct_group_size", "ct_group_handle", "ct_group_set_camera",
+    "ct_group_create", "ct_group_destroy", "ct_group_last_error", "ct_group_size", "ct_group_handle", "ct_group_set_camera", "ct_group_set_light",
     "ct_group_render_accumulate", "ct_group_reset", "ct_group_merge", "ct_group_download", "ct_group_tonemap",
     "ct_group_is_converged", "ct_group_counters",
 ]
@@ -109,6 +109,7 @@ def load():
         "ct_last_error": (C.c_char_p, [vp]),
         "ct_set_stream": (i32, [vp, vp]),
         "ct_set_camera": (i32, [vp, vp, vp, vp, vp]),
+        "ct_set_light": (i32, [vp, vp, vp, f32]),
         "ct_render_subframe": (i32, [vp, u32, vp]),
         "ct_accumulate": (i32, [vp, u32, vp]),
         "ct_render_accumulate": (i32, [vp, u32, u32]),
@@ -164,6 +165,7 @@ def load():
         "ct_group_size": (i32, [vp, C.POINTER(u32)]),
         "ct_group_handle": (i32, [vp, u32, C.POINTER(vp)]),
         "ct_group_set_camera": (i32, [vp, vp, vp, vp, vp]),
+        "ct_group_set_light": (i32, [vp, vp, vp, f32]),
         "ct_group_render_accumulate": (i32, [vp, u32, u32]),
         "ct_group_reset": (i32, [vp]),
         "ct_group_merge": (i32, [vp]),

@@ -176,6 +176,13 @@ def make_scene(density: np.ndarray, p: SceneParams):
     return s, (density, mie, chopped)
 
 
+def _light_args(direction, color):
+    """float32[3] arrays for ct_set_light; None stays None (the library answers a NULL direction itself)."""
+    d = None if direction is None else np.ascontiguousarray(direction, np.float32).reshape(3)
+    c = None if color is None else np.ascontiguousarray(color, np.float32).reshape(3)
+    return d, c
+
+
 class CloudTracer:
     """Owns one CtHandle.  `density` is the uint8 [Z,Y,X] texture incl. its zero border."""
 
@@ -213,6 +220,12 @@ class CloudTracer:
     def set_camera(self, eye, U, V, W):
         a = [np.asarray(v, np.float32) for v in (eye, U, V, W)]
         check(self.L.ct_set_camera(self.h, *[_p(v) for v in a]), self.h)
+
+    def set_light(self, direction, color=None, intensity: float = 1e6):
+        """ct_set_light: a new light on the live handle -- the shadow volume and what is built from it are redone, the
+        density layouts, tables and buffers stay.  `color=None` keeps the colour.  The image is not cleared: reset() next."""
+        d, c = _light_args(direction, color)
+        check(self.L.ct_set_light(self.h, _p(d) if d is not None else None, _p(c) if c is not None else None, intensity), self.h)
 
     def render_subframe(self, subframe_id: int, out_dev_ptr: int | None = None):
         check(self.L.ct_render_subframe(self.h, subframe_id, C.c_void_p(out_dev_ptr) if out_dev_ptr else None), self.h)
@@ -566,6 +579,11 @@ class TracerGroup:
     def set_camera(self, eye, U, V, W):
         a = [np.asarray(v, np.float32) for v in (eye, U, V, W)]
         self._check(self.L.ct_group_set_camera(self.g, *[_p(v) for v in a]))
+
+    def set_light(self, direction, color=None, intensity: float = 1e6):
+        """ct_group_set_light: CloudTracer.set_light on every shard; reset() next."""
+        d, c = _light_args(direction, color)
+        self._check(self.L.ct_group_set_light(self.g, _p(d) if d is not None else None, _p(c) if c is not None else None, intensity))
 
     def render_accumulate(self, first_subframe_id: int, count: int):
         self._check(self.L.ct_group_render_accumulate(self.g, first_subframe_id, count))

@@ -85,6 +85,9 @@ struct CtHandle_ {
     uint8_t *d_mcoarse = nullptr;      // ... and the clearance of the coarse cells outside the extents
     size_t mbricks_dense_bytes = 0, mbricks_bytes = 0;
     int nee_skip_r = 0;   // radius of the march bricks' shadow-zero flags (0: none set)
+    // kept from ct_create for ct_set_light, which has neither the density nor the Mie tables on the host any more
+    uint32_t zero_faces = 0;   // empty boundary layers of the density (zero_faces(); launch_inscatter)
+    bool mie_finite = true;    // both phase tables are finite (nee_skip_radius)
     // CT_FLAG_VMM_BRICKS: d_mbricks is a reserved virtual range (not a hipMalloc), backed chunk by chunk
     struct VmmBricks {
         void *va = nullptr;
@@ -959,6 +962,21 @@ static int choose_schedule(const CtScene *s, CtHandle h)
 }
 
 // ---- uniforms: VDBCloud::setupVolumeVariables (VDBCloud.cpp:98-111), Sun::init (Sun.cpp:13-18)
+// The light's share of them (ct_create and ct_set_light): nlx/nly/nlz and lr/lg/lb.
+static void light_uniforms(const CtScene *s, DevScene &d)
+{
+    float l[3] = { s->light_direction[0], s->light_direction[1], s->light_direction[2] };
+    if (!(s->flags & CT_FLAG_LIGHT_NORMALIZED)) {
+        v3_normalize_twice(s->light_direction, l);
+    }
+    d.nlx = -l[0];
+    d.nly = -l[1];
+    d.nlz = -l[2];
+    d.lr = s->light_color[0] * s->light_intensity;
+    d.lg = s->light_color[1] * s->light_intensity;
+    d.lb = s->light_color[2] * s->light_intensity;
+}
+
 static void scene_uniforms(const CtScene *s, DevScene &d)
 {
     const uint32_t nx = s->dims[0], ny = s->dims[1], nz = s->dims[2];
@@ -981,16 +999,7 @@ static void scene_uniforms(const CtScene *s, DevScene &d)
     d.sz = (maxs / fz) * fz;
     d.density_multiplier = s->cloud_size_m / s->mean_free_path_m;
     d.sample_step = s->sample_step;
-    float l[3] = { s->light_direction[0], s->light_direction[1], s->light_direction[2] };
-    if (!(s->flags & CT_FLAG_LIGHT_NORMALIZED)) {
-        v3_normalize_twice(s->light_direction, l);
-    }
-    d.nlx = -l[0];
-    d.nly = -l[1];
-    d.nlz = -l[2];
-    d.lr = s->light_color[0] * s->light_intensity;
-    d.lg = s->light_color[1] * s->light_intensity;
-    d.lb = s->light_color[2] * s->light_intensity;
+    light_uniforms(s, d);
     {
         // cloud.cuh:148-151 evaluated once on the host, in float like the device code.
         const float sunAngularRadiusDeg = 0.53f / 2;
@@ -1366,14 +1375,14 @@ static int create_impl(const CtScene *s, CtHandle h)
     scene_uniforms(s, h->dev);
     int apron = 0;
     CT_TRY(apron_grid(s, h, apron));
-    bool mie_finite = true;
-    CT_TRY(upload_mie(s, h, mie_finite));
+    CT_TRY(upload_mie(s, h, h->mie_finite));
     CT_TRY(build_apron_bricks(s, h));
     if (s->estimator == CT_EST_DELTA) {
         CT_TRY(build_majorant_grid(s, h));
     }
     const MarchStorage ms = march_storage(s, h->tune.SPARSE);
-    CT_TRY(build_march_layouts(s, h, apron, ms, zero_faces(s->density_host, s->dims[0], s->dims[1], s->dims[2]), mie_finite));
+    h->zero_faces = zero_faces(s->density_host, s->dims[0], s->dims[1], s->dims[2]);
+    CT_TRY(build_march_layouts(s, h, apron, ms, h->zero_faces, h->mie_finite));
 #ifdef CT_EXPERIMENTS
     if (ms.vmm) {
         CT_TRY(vmm_back_mbricks(h));
@@ -1489,6 +1498,83 @@ extern "C" int ct_set_camera(CtHandle h, const float eye[3], const float U[3], c
     h->queue_dirty = true; // primary rays and the work queue depend on the pose
     discard_ahead(h);      // (and so does every sample rendered ahead of the calls)
     return CT_OK;
+}
+
+// What depends on the light, rebuilt in place in the order create_impl documents: the uniforms, the shadow volume (marched over
+// the march bricks as they are stored: dense, or sparse through the row table), its apron bricks, bit 6 of the march bricks'
+// clearance-0 rows (MARCH), the shadow half of the twin bricks (DELTA, delta_nee == 2).  Every temporary is allocated before
+// anything of the handle changes, so an allocation failure leaves the old light in place.  Nothing is in flight (the caller
+// has flushed); the stream is idle on return.
+static int relight(CtHandle h, const CtScene &s)
+{
+    DevScene d = h->dev;
+    light_uniforms(&s, d);
+    const bool march = s.estimator == CT_EST_MARCH;
+    const int nee_r = march ? nee_skip_radius(d, h->mie_finite) : 0;
+    DevTemp<uint8_t> tmp_a, tmp_c;   // the Chebyshev passes' two scratch volumes
+    if (nee_r > 0 && (dmalloc(&tmp_a, h->volume_bytes) != hipSuccess || dmalloc(&tmp_c, h->volume_bytes) != hipSuccess)) {
+        (void)hipGetLastError();
+        return fail(h, CT_E_NOMEM, "out of device memory (shadow-zero flags scratch); the light is unchanged");
+    }
+    d.nee_reach = nee_r > 0 ? nee_skip_reach(d) : 0.0f;
+    h->scene = s;
+    h->dev = d;
+    h->nee_skip_r = nee_r;
+    discard_ahead(h);   // (samples rendered ahead of the calls saw the old light)
+    // A new light is a new scene setup: the next render call starts as a fresh handle's first one does, with the pose's primary
+    // rays, pixel list and job order rebuilt and its costs measured again.  The job list decides which samples a lane runs one
+    // after the other, and with them what its one-entry footprint cache serves: ct_fetch_counters would otherwise depend on what
+    // the handle rendered under the old light.
+    h->queue_dirty = true;
+    h->tile_deepest.clear();
+    const int nx = d.nx, ny = d.ny, nz = d.nz, bbias = d.brick_bias;
+    hipError_t e = launch_inscatter(d, h->d_inscatter, h->zero_faces, h->stream);
+    if (e == hipSuccess) {
+        e = launch_build_bricks(h->d_inscatter, nx, ny, nz, bbias, d.brick_gx, d.brick_gy, d.brick_gz, h->d_ibricks, h->stream);
+    }
+    if (e == hipSuccess && march) {
+        e = launch_shadow_zero_rows(h->d_inscatter, nx, ny, nz, nee_r, d.m_bias_x, bbias, d.m_gx, d.brick_gy, d.brick_gz, tmp_a, tmp_c,
+                                    h->d_mbricks, h->d_mrows, h->stream);
+    }
+    if (e == hipSuccess && h->d_tbricks) {
+        e = launch_twin_shadow_half(h->d_inscatter, nx, ny, nz, d.t_bias, d.t_gx, d.t_gy, d.t_gz, h->d_tbricks, h->stream);
+    }
+    const hipError_t e2 = hipStreamSynchronize(h->stream);   // (before the temporaries go)
+    HIPCHK(h, e);
+    HIPCHK(h, e2);
+    return CT_OK;
+}
+
+extern "C" int ct_set_light(CtHandle h, const float direction[3], const float color[3], float intensity)
+{
+    NEED_NOFLUSH(h);
+    // (arguments first: a rejected call leaves the handle exactly as it was, batches in flight included)
+    if (!direction) {
+        return fail(h, CT_E_INVAL, "light direction must not be NULL");
+    }
+    if (!std::isfinite(direction[0]) || !std::isfinite(direction[1]) || !std::isfinite(direction[2])) {
+        return fail(h, CT_E_INVAL, "light direction is not finite");
+    }
+    if (!(direction[0] * direction[0] + direction[1] * direction[1] + direction[2] * direction[2] > 0.f)) {
+        return fail(h, CT_E_INVAL, "light_direction is zero");
+    }
+    if (h->vmm.va) {
+        // (experiments build: chunks of the virtual range share memory by their meta bytes, bit 6 included)
+        return fail(h, CT_E_INVAL, "ct_set_light: march bricks behind virtual memory cannot be re-lit");
+    }
+    const int rc = flush(h);
+    if (rc != CT_OK) {
+        return rc;
+    }
+    CtScene s = h->scene;
+    for (int a = 0; a < 3; a++) {
+        s.light_direction[a] = direction[a];
+        if (color) {
+            s.light_color[a] = color[a];
+        }
+    }
+    s.light_intensity = intensity;
+    return relight(h, s);
 }
 
 // Primary rays of the current pose + the list of this shard's pixels that hit the box, in

@@ -286,6 +286,23 @@ extern "C" int ct_group_set_camera(CtGroup g, const float eye[3], const float U[
     return CT_OK;
 }
 
+// ct_set_light on every shard.  The arguments are checked by the first shard before anything changes; a shard that runs out of
+// memory keeps its old light while the shards before it have the new one, so the group is re-lit again or destroyed then.
+extern "C" int ct_group_set_light(CtGroup g, const float direction[3], const float color[3], float intensity)
+{
+    if (!g) {
+        return gfail(nullptr, CT_E_INVAL, "null group");
+    }
+    for (uint32_t i = 0; i < g->handles.size(); i++) {
+        const int rc = ct_set_light(g->handles[i], direction, color, intensity);
+        if (rc != CT_OK) {
+            return shard_fail(g, i, rc);
+        }
+    }
+    g->merged = false;
+    return CT_OK;
+}
+
 // Every shard enqueues its batch (the devices work at the same time), then every shard is waited for.
 extern "C" int ct_group_render_accumulate(CtGroup g, uint32_t first_subframe_id, uint32_t count)
 {

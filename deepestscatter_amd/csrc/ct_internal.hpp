@@ -144,6 +144,10 @@ hipError_t launch_mbrick_extent(const uint8_t *bricks, int gx, int gy, int gz, u
 hipError_t launch_mbrick_compact(const uint8_t *dense, int gx, int gy, int gz, const uint2 *rows, uint8_t *compact, hipStream_t stream);
 hipError_t launch_nee_skip_flags(const uint8_t *shadow, int nx, int ny, int nz, int r, int bias_x, int bias, int gx, int gy,
                                  int gz, uint8_t *tmp_a, uint8_t *tmp_c, uint8_t *bricks, hipStream_t stream);
+hipError_t launch_shadow_zero_rows(const uint8_t *shadow, int nx, int ny, int nz, int r, int bias_x, int bias, int gx, int gy, int gz,
+                                   uint8_t *tmp_a, uint8_t *tmp_c, uint8_t *bricks, const uint2 *rows, hipStream_t stream);
+hipError_t launch_twin_shadow_half(const uint8_t *shadow, int nx, int ny, int nz, int bias, int gx, int gy, int gz, uint8_t *bricks,
+                                   hipStream_t stream);
 hipError_t launch_coarse_clearance(const uint8_t *dist, int nx, int ny, int nz, int bias, int cshift, int cgx, int cgy, int cgz,
                                    uint8_t *out, hipStream_t stream);
 hipError_t launch_render_delta(const DevScene &sc, const BatchArgs &ba, LaunchShape shape, hipStream_t stream);

@@ -14,6 +14,8 @@
 //   accumulate_batch_kernel, accumulate_list_kernel
 //                              updateFrameResult (progressive.cu:17-27) over S subframes in order
 //   inscatter_kernel           inScatter.cu:40-66
+//   shadow_zero_rows_kernel, twin_shadow_half_kernel
+//                              ct_set_light: what depends on the light in the march and twin bricks, rewritten in place
 //   build_bricks_kernel, brick_free_kernel, brick_dist_relax_kernel, brick_meta_kernel
 //                              uint8 volume -> 128-byte apron bricks of 4^3 texels + meta bytes
 //   blocked_mask_kernel, cheb_pass_kernel, build_mbricks_kernel
@@ -88,6 +90,39 @@ hipError_t launch_build_twin_bricks(const uint8_t *density, const uint8_t *shado
     const int threads = 256;
     const int blocks = (int)((total + threads - 1) / threads < 65536 ? (total + threads - 1) / threads : 65536);
     hipLaunchKernelGGL(build_twin_bricks_kernel, dim3(blocks), dim3(threads), 0, stream, density, shadow, nx, ny, nz, bias, bricks, gx, gy, gz);
+    return hipGetLastError();
+}
+
+// ct_set_light: only the shadow half (bytes 64..127) of every twin brick, from a new shadow volume; the density half stays.
+// One thread per row of four texels (lx = 0..3 at byte 64 + lz*16 + ly*4, a word of its own).
+__global__ __launch_bounds__(256) void twin_shadow_half_kernel(const uint8_t *__restrict__ shadow, int nx, int ny, int nz, int bias,
+                                                               uint8_t *__restrict__ bricks, int gx, int gy, int gz)
+{
+    const int64_t total = (int64_t)gx * gy * gz * 16;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t b = i >> 4;
+        const int ly = (int)(i & 3), lz = (int)((i >> 2) & 3);
+        const int x0 = (int)(b % gx) * 3 - bias;
+        const int y = (int)((b / gx) % gy) * 3 + ly - bias;
+        const int z = (int)(b / ((int64_t)gx * gy)) * 3 + lz - bias;
+        const int yc = min(max(y, 0), ny - 1), zc = min(max(z, 0), nz - 1);
+        const uint8_t *row = shadow + ((size_t)zc * ny + yc) * nx;
+        uint32_t w = 0;
+#pragma unroll
+        for (int lx = 0; lx < 4; lx++) {
+            w |= (uint32_t)row[min(max(x0 + lx, 0), nx - 1)] << (8 * lx);
+        }
+        *(uint32_t *)(bricks + ((size_t)b << 7) + 64 + lz * 16 + ly * 4) = w;
+    }
+}
+
+hipError_t launch_twin_shadow_half(const uint8_t *shadow, int nx, int ny, int nz, int bias, int gx, int gy, int gz, uint8_t *bricks,
+                                   hipStream_t stream)
+{
+    const int64_t total = (int64_t)gx * gy * gz * 16;
+    const int threads = 256;
+    const int blocks = (int)std::min<int64_t>((total + threads - 1) / threads, 65536);
+    hipLaunchKernelGGL(twin_shadow_half_kernel, dim3(blocks), dim3(threads), 0, stream, shadow, nx, ny, nz, bias, bricks, gx, gy, gz);
     return hipGetLastError();
 }
 
@@ -301,6 +336,71 @@ hipError_t launch_nee_skip_flags(const uint8_t *shadow, int nx, int ny, int nz, 
     const int rb = (int)std::min<int64_t>((rows + threads - 1) / threads, 65536 * 4);
     hipLaunchKernelGGL(nee_skip_flags_kernel, dim3(rb), dim3(threads), 0, stream, tmp_c, nx, ny, nz, r, bias_x, bias, bricks, gx, gy,
                        gz);
+    return hipGetLastError();
+}
+
+// ct_set_light: bit 6 of every row of clearance 0 REWRITTEN for a new shadow volume -- set where nee_skip_flags_kernel would set
+// it, cleared elsewhere -- and no other bit or byte of a brick touched.  One thread per row of the dense index space; rows !=
+// NULL (sparse march bricks, DevScene::m_rows): bricks outside their row's stored extent have no bytes and are passed over, the
+// others are found through the table.  dist == NULL (radius 0: no skip): every flag cleared.
+__global__ __launch_bounds__(256) void shadow_zero_rows_kernel(const uint8_t *__restrict__ dist, int nx, int ny, int nz, int r, int bias_x,
+                                                               int bias, uint8_t *__restrict__ bricks, const uint2 *__restrict__ rows,
+                                                               int gx, int gy, int gz)
+{
+    const int64_t total = (int64_t)gx * gy * gz * 16;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t b = i >> 4;
+        const int ly = (int)(i & 3), lz = (int)((i >> 2) & 3);
+        const int bx = (int)(b % gx);
+        size_t line = (size_t)b;
+        if (rows != nullptr) {
+            const uint2 ri = rows[b / gx];
+            const uint32_t rel = (uint32_t)bx - (ri.y & 0xffffu);
+            if (rel >= (ri.y >> 16)) {
+                continue;
+            }
+            line = (size_t)ri.x + rel;
+        }
+        uint8_t *m = bricks + (line << 7) + lz * 25 + ly * 5 + 4;
+        const uint32_t meta = *m;
+        if ((meta & 0x3fu) != 0u) {
+            continue;
+        }
+        bool zero = dist != nullptr;
+        if (zero) {
+            const int x0 = bx * 3 - bias_x;
+            const int y = (int)((b / gx) % gy) * 4 + ly - bias;
+            const int z = (int)(b / ((int64_t)gx * gy)) * 4 + lz - bias;
+            for (int k = 0; k < 3; k++) {
+                const int x = x0 + k;
+                const bool in_grid = x >= 0 && y >= 0 && z >= 0 && x < nx && y < ny && z < nz;
+                zero = zero && in_grid && (int)dist[((size_t)z * ny + y) * nx + x] > r;
+            }
+        }
+        const uint32_t want = (meta & ~0x40u) | (zero ? 0x40u : 0u);
+        if (want != meta) {
+            *m = (uint8_t)want;
+        }
+    }
+}
+
+// (tmp_a and tmp_c: scratch volumes of nx*ny*nz bytes, unused when r == 0; rows: DevScene::m_rows or NULL for dense bricks)
+hipError_t launch_shadow_zero_rows(const uint8_t *shadow, int nx, int ny, int nz, int r, int bias_x, int bias, int gx, int gy, int gz,
+                                   uint8_t *tmp_a, uint8_t *tmp_c, uint8_t *bricks, const uint2 *rows, hipStream_t stream)
+{
+    const int threads = 256;
+    if (r > 0) {
+        const int64_t texels_n = (int64_t)nx * ny * nz;
+        const int tb = (int)std::min<int64_t>((texels_n + threads - 1) / threads, 65536 * 4);
+        hipLaunchKernelGGL(shadow_blocked_kernel, dim3(tb), dim3(threads), 0, stream, shadow, nx, ny, nz, tmp_a);
+        hipLaunchKernelGGL(cheb_pass_kernel<0>, dim3(tb), dim3(threads), 0, stream, tmp_a, tmp_c, nx, ny, nz, r);
+        hipLaunchKernelGGL(cheb_pass_kernel<1>, dim3(tb), dim3(threads), 0, stream, tmp_c, tmp_a, nx, ny, nz, r);
+        hipLaunchKernelGGL(cheb_pass_kernel<2>, dim3(tb), dim3(threads), 0, stream, tmp_a, tmp_c, nx, ny, nz, r);
+    }
+    const int64_t total = (int64_t)gx * gy * gz * 16;
+    const int rb = (int)std::min<int64_t>((total + threads - 1) / threads, 65536 * 4);
+    hipLaunchKernelGGL(shadow_zero_rows_kernel, dim3(rb), dim3(threads), 0, stream, r > 0 ? tmp_c : nullptr, nx, ny, nz, r, bias_x, bias,
+                       bricks, rows, gx, gy, gz);
     return hipGetLastError();
 }
 
@@ -996,7 +1096,11 @@ CT_DEV void replay_steps(f3 &pos, f3 stepv, int n)
 // =============================================================================================
 // FIXED8 (CT_FLAG_TEX_FIXED8): both samplers filter with tex_weight<true>; the skips above only pass over footprints of eight
 // zeros and layers of zeros, whose filter is +0 whatever the weights.
-template <bool FIXED8>
+// SPARSE (ct_set_light on a handle with sparse march bricks, whose dense array is gone): the same walk over the stored bricks,
+// with the coarse clearance outside the row extents (fetch_cell_m<true>, as primary_advance_kernel<true>).  A coarse
+// clearance is never larger than the rows' it stands for, so the walk fetches at more of the same positions: every skipped
+// sample is still a no-op inside the box, the position adds are the same, and so are the bytes written.
+template <bool FIXED8, bool SPARSE = false>
 __global__ __launch_bounds__(256) void inscatter_kernel(DevScene sc, uint8_t *__restrict__ out, uint32_t zero_faces)
 {
     const int64_t total = (int64_t)sc.nx * sc.ny * sc.nz;
@@ -1020,11 +1124,11 @@ __global__ __launch_bounds__(256) void inscatter_kernel(DevScene sc, uint8_t *__
     float transmittance = 1;
     int s = 0;
     bool done = false;
-    if (sc.mbricks != nullptr && sc.m_rows == nullptr) {
+    if (sc.mbricks != nullptr && (SPARSE || sc.m_rows == nullptr)) {
         const float inv_maxd = inv_max_advance(sc, step_to_light);
         while (s < step_count && in_box(sc, p)) {
             uint32_t meta;
-            const uint2 cell = fetch_cell_m<false>(sc, p, meta);
+            const uint2 cell = fetch_cell_m<SPARSE>(sc, p, meta);
             if ((cell.x | cell.y) != 0u) {
                 const float density = filter_at<FIXED8>(sc, cell, p) * sc.density_multiplier;
                 const float extinction = density * sc.sample_step;
@@ -1072,10 +1176,17 @@ hipError_t launch_inscatter(const DevScene &sc, uint8_t *out, uint32_t zero_face
     const int64_t total = (int64_t)sc.nx * sc.ny * sc.nz;
     const int threads = 256;
     const int64_t blocks = (total + threads - 1) / threads;
-    if (sc.tex_fixed8) {
-        hipLaunchKernelGGL(inscatter_kernel<true>, dim3((unsigned)blocks), dim3(threads), 0, stream, sc, out, zero_faces);
+    const dim3 grid((unsigned)blocks), block(threads);
+    if (sc.mbricks != nullptr && sc.m_rows != nullptr) {
+        if (sc.tex_fixed8) {
+            hipLaunchKernelGGL((inscatter_kernel<true, true>), grid, block, 0, stream, sc, out, zero_faces);
+        } else {
+            hipLaunchKernelGGL((inscatter_kernel<false, true>), grid, block, 0, stream, sc, out, zero_faces);
+        }
+    } else if (sc.tex_fixed8) {
+        hipLaunchKernelGGL(inscatter_kernel<true>, grid, block, 0, stream, sc, out, zero_faces);
     } else {
-        hipLaunchKernelGGL(inscatter_kernel<false>, dim3((unsigned)blocks), dim3(threads), 0, stream, sc, out, zero_faces);
+        hipLaunchKernelGGL(inscatter_kernel<false>, grid, block, 0, stream, sc, out, zero_faces);
     }
     return hipGetLastError();
 }

@@ -40,6 +40,7 @@ namespace DeepestScatter
         void init() override                                                     // PathTracingRenderer.cpp:14-19
         {
             // all scene items have published their variables by now (installApp order, installers.cpp:32-35)
+            if (context->created()) return;   // the context of an earlier task of the same cloud: Sun::init has re-lit it
             CtScene& s = context->scene;
             s.density_host = context->density.data();
             s.mie_host = context->mie.data();

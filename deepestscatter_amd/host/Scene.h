@@ -65,6 +65,14 @@ namespace DeepestScatter
             if (group) checkGroup(ct_group_set_camera(group, eye, U, V, W), group, "ct_group_set_camera");
             else check(ct_set_camera(handle, eye, U, V, W), handle, "ct_set_camera");
         }
+        // A new sun on the live renderer (ct_set_light): the shadow volume and what is built from it are redone, the cloud's
+        // own layouts stay.  The image is not cleared: Camera::reset follows, as after a camera move.
+        bool created() const { return group != nullptr || handle != nullptr; }
+        void setLight(const float* direction, const float* color, float intensity)
+        {
+            if (group) checkGroup(ct_group_set_light(group, direction, color, intensity), group, "ct_group_set_light");
+            else check(ct_set_light(handle, direction, color, intensity), handle, "ct_set_light");
+        }
         void renderAccumulate(uint32_t first, uint32_t count, bool enqueue)
         {
             if (group) checkGroup(ct_group_render_accumulate(group, first, count), group, "ct_group_render_accumulate");
@@ -205,6 +213,8 @@ namespace DeepestScatter
             context->scene.light_intensity = intensity;
             // `direction` has been normalised by installSceneSetup and by DirectionalLight's constructor
             context->scene.flags |= CT_FLAG_LIGHT_NORMALIZED;
+            // a context that already renders (the next light of the same cloud, main.cpp) is re-lit in place
+            if (context->created()) context->setLight(context->scene.light_direction, context->scene.light_color, intensity);
         }
 
     private:

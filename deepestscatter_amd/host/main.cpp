@@ -3,7 +3,8 @@
 // "Side" then "Back", 512x256, 7000 m, output <cloud>.<Light>.PT.exr (Tasks.cpp:88-90; --format pfm for PFM).  The GLUT loop
 // (GuiExecutionLoop.cpp:85-128) becomes a plain while(!scene->isCompleted()) scene->update().
 //
-//   cloudtrace <cloud> [--size WxH] [--spp N] [--mode total|multi|single] [--light Side|Back|Front]
+//   cloudtrace <cloud> [--size WxH] [--spp N] [--mode total|multi|single] [--light Side|Back|Front]...
+//              (several --light: one task each; the tasks after the first re-light the first one's renderer, ct_set_light)
 //              [--size-m 7000] [--out DIR] [--data DIR] [--unfused] [--display] [--estimator march|delta] [--format exr|pfm]
 //              [--tex-fixed8]   filter weights in 1.8 fixed point like the reference's texture unit (CT_FLAG_TEX_FIXED8)
 //              [--gpus N | --gpus a,b,c]   one process, one shard of 8x8-pixel tiles per GPU, RCCL reduce of [mean | M2] (ct_group_*)
@@ -237,11 +238,14 @@ namespace
 
     using LazyTask = std::function<std::shared_ptr<Scene>()>;
 
-    LazyTask renderCloudSingleTask(const Options& opt, LightDirection lightDirection)   // Tasks.cpp:67-102
+    // `context`: one per cloud.  The reference builds a whole context per task; here the tasks of one cloud differ in the sun
+    // alone, so the second and later ones keep the first one's renderer and re-light it (Sun::init -> ct_set_light, then
+    // Camera::reset) instead of uploading the density and rebuilding its layouts again.  Same images.
+    LazyTask renderCloudSingleTask(const Options& opt, LightDirection lightDirection, std::shared_ptr<Context> context)   // Tasks.cpp:67-102
     {
         return [=]()
         {
-            auto context = std::make_shared<Context>();
+            const bool relight = context->created();
             context->devices = opt.devices;
             if (opt.texFixed8) context->scene.flags |= CT_FLAG_TEX_FIXED8;
             auto resources = std::make_shared<Resources>(context);
@@ -266,6 +270,7 @@ namespace
             camera->fused = opt.fused;
             camera->headless = opt.fused && !opt.display;
             std::vector<std::shared_ptr<SceneItem>> items{ sun, cloud, material, camera };
+            if (relight) items = { sun, material, camera };                       // the volume is on the device already
             return std::make_shared<Scene>(items, context, opt.dataDir);
         };
     }
@@ -278,6 +283,7 @@ int main(int argc, char* argv[])
         Options opt;
         if (argc < 2) { std::cerr << "usage: cloudtrace <cloud> [--size WxH] [--spp N] [--mode total|multi|single] [--light L] [--size-m M] [--out DIR] [--data DIR] [--unfused] [--display] [--estimator march|delta] [--format exr|pfm] [--gpus N|a,b,c] [--tex-fixed8]\n"; return 2; }
         int first = 2;
+        bool lightsGiven = false;
         opt.cloud = argv[1];
         if (opt.cloud == "collect")
         {
@@ -331,8 +337,11 @@ int main(int argc, char* argv[])
             }
             else if (a == "--light")
             {
+                // the first --light replaces the default pair, every further one adds a task for the same cloud
                 const std::string l = next();
-                opt.lights = { l == "Front" ? LightDirection::Front : l == "Back" ? LightDirection::Back : LightDirection::Side };
+                if (!lightsGiven) opt.lights.clear();
+                lightsGiven = true;
+                opt.lights.push_back(l == "Front" ? LightDirection::Front : l == "Back" ? LightDirection::Back : LightDirection::Side);
             }
             else throw std::invalid_argument("unknown option " + a);
         }
@@ -340,7 +349,8 @@ int main(int argc, char* argv[])
         if (opt.collect) return collectScenes(opt);
 
         std::queue<LazyTask> tasks;                                               // Tasks::renderCloud, Tasks.cpp:104-112
-        for (auto l : opt.lights) tasks.push(renderCloudSingleTask(opt, l));
+        auto context = std::make_shared<Context>();
+        for (auto l : opt.lights) tasks.push(renderCloudSingleTask(opt, l, context));
 
         while (!tasks.empty())                                                    // GuiExecutionLoop::getNextTask
         {

@@ -201,6 +201,25 @@ CT_API int ct_set_stream(CtHandle h, void *hip_stream);
 /* ARenderer::getCamera()["eye"|"U"|"V"|"W"]->setFloat(...)   Camera.cpp:126-133 */
 CT_API int ct_set_camera(CtHandle h, const float eye[3], const float U[3], const float V[3], const float W[3]);
 
+/* Sun::init again (Sun.cpp:13-18) on a live handle: a new light without a new ct_create.  In the reference the light belongs to
+ * the scene setup, not to the cloud -- Tasks::renderCloud renders every cloud under two suns (Tasks.cpp:52-65) -- and only the
+ * shadow volume (VDBCloud::InitInScatter), its bricks, the shadow-zero flags of the march bricks, the shadow half of the twin
+ * bricks and the uniforms lightDirection / lightColor * lightIntensity depend on it: those are rebuilt, everything else of the
+ * handle (density layouts, Mie tables, frame buffers, scratch) stays.  Afterwards the handle's device state is that of a handle
+ * created with the new light, and the next render call starts as that handle's first one would: the pose's pixel list and job
+ * order are rebuilt and its path costs measured again, as after ct_set_camera.
+ * `direction` is the direction the light travels, as CtScene::light_direction, and goes through the same two normalisations
+ * unless the handle was created with CT_FLAG_LIGHT_NORMALIZED.  color == NULL keeps the handle's colour; intensity is always
+ * set.  A NULL handle, a NULL, zero or non-finite direction: CT_E_INVAL, and the handle is exactly as it was (colour and
+ * intensity are not checked: as at ct_create, non-finite ones only turn the shadow-zero NEE skip off).
+ * Waits for the batches in flight, drops the samples rendered ahead (ct_set_render_ahead) -- no path of the old light survives
+ * -- and returns when the stream is idle.  Its temporaries are allocated before anything changes: CT_E_NOMEM leaves the old
+ * light in place and the handle usable.
+ * Does NOT touch mean, M2, the subframe count or the counters: follow it with ct_reset, as after a camera move in the reference
+ * (Camera.cpp:93-98).  What ct_set_stop_when_converged has set, a frozen image included, is likewise kept until ct_reset
+ * clears it. */
+CT_API int ct_set_light(CtHandle h, const float direction[3], const float color[3], float intensity);
+
 /* ARenderer::render(frameResultBuffer) after context["subframeId"]=id  (Camera.cpp:191-195,
  * PathTracingRenderer.cpp:21-31): one path per pixel, result float4(r,g,b,1) per pixel into
  * the handle's frame buffer; if frame_rgba_dev != NULL the frame is also copied there
@@ -511,6 +530,7 @@ CT_API const char *ct_group_last_error(CtGroup g);      /* g == NULL: last failu
 CT_API int ct_group_size(CtGroup g, uint32_t *count_out);
 CT_API int ct_group_handle(CtGroup g, uint32_t index, CtHandle *out);   /* shard `index` (owned by the group) */
 CT_API int ct_group_set_camera(CtGroup g, const float eye[3], const float U[3], const float V[3], const float W[3]);
+CT_API int ct_group_set_light(CtGroup g, const float direction[3], const float color[3], float intensity);   /* ct_set_light on every shard; follow with ct_group_reset */
 CT_API int ct_group_render_accumulate(CtGroup g, uint32_t first_subframe_id, uint32_t count);
 CT_API int ct_group_reset(CtGroup g);
 CT_API int ct_group_merge(CtGroup g);

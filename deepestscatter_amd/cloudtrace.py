@@ -269,6 +269,50 @@ class CloudTracer:
         check(self.L.ct_collect_descriptors(self.h, _p(pos), _p(d), len(pos), _p(out)), self.h)
         return out
 
+    def descriptor_frame(self, subframe_id: int, rect=None, capacity: int | None = None):
+        """ct_descriptor_frame: the network's input for the pixels of `rect` = (x0, y0, x1, y1) (half-open; None = the whole
+        frame) -- per pixel whose primary ray scatters in the cloud, the first scatter position and the descriptor there, in
+        the rect's row-major order, without leaving the device.
+        -> (descriptors uint8 [n,10,9,5,5], positions float32 [n,3], directions float32 [n,3], pixels int32 [n] = y * width + x),
+        torch tensors on the handle's device, cut to the number of records.  `capacity` (default: the rect's area) is what the
+        tensors are allocated for; fewer than the rect's valid pixels raises CloudTraceError(CT_E_INVAL) whose `needed` is
+        their number."""
+        import torch
+        x0, y0, x1, y1 = (int(v) for v in (rect if rect is not None else (0, 0, self.width, self.height)))
+        r = np.array([x0, y0, x1, y1], np.int64)
+        if (r < 0).any() or (r >= 2 ** 32).any():
+            raise _lib.CloudTraceError(_lib.CT_E_INVAL, "descriptor_frame: rect out of range")
+        r = r.astype(np.uint32)
+        area = max(x1 - x0, 0) * max(y1 - y0, 0)
+        # (a rect never yields more records than it has pixels, and the library refuses one of more than 2^20)
+        capacity = min(area if capacity is None else int(capacity), area, 1 << 20)
+        if capacity < 0:
+            raise ValueError("capacity must not be negative")
+        dev = torch.device("cuda", self.params.device)
+        n_alloc = max(capacity, 1)
+        desc = torch.empty((n_alloc, 10, 9, 5, 5), dtype=torch.uint8, device=dev)
+        pos = torch.empty((n_alloc, 3), dtype=torch.float32, device=dev)
+        d = torch.empty((n_alloc, 3), dtype=torch.float32, device=dev)
+        pix = torch.empty((n_alloc,), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)      # the library writes them on the handle's stream, not on torch's
+        n = C.c_uint32(0)
+        rc = self.L.ct_descriptor_frame(self.h, subframe_id & 0xFFFFFFFF, _p(r) if rect is not None else None,
+                                        min(capacity, 0xFFFFFFFF), C.c_void_p(desc.data_ptr()), C.c_void_p(pos.data_ptr()),
+                                        C.c_void_p(d.data_ptr()), C.c_void_p(pix.data_ptr()), C.byref(n))
+        if rc != _lib.CT_OK:
+            msg = self.L.ct_last_error(self.h)
+            e = _lib.CloudTraceError(rc, msg.decode("utf-8", "replace") if msg else "")
+            e.needed = int(n.value)
+            raise e
+        k = int(n.value)
+        return desc[:k], pos[:k], d[:k], pix[:k]
+
+    def descriptor_frame_time(self):
+        """-> (first flights + compaction ms, descriptor gather ms) of the last descriptor_frame (ct_debug_descriptor_frame_time)."""
+        a, b = C.c_double(0), C.c_double(0)
+        check(self.L.ct_debug_descriptor_frame_time(self.h, C.byref(a), C.byref(b)), self.h)
+        return float(a.value), float(b.value)
+
     def reset(self):
         check(self.L.ct_reset(self.h), self.h)
 

@@ -243,6 +243,7 @@ struct CtHandle_ {
     LaunchShape xshape{ 256, 1024, false };
     uint32_t subframes = 0;
     double render_ms = 0, accum_ms = 0;
+    double dframe_scatter_ms = 0, dframe_gather_ms = 0;   // the last ct_descriptor_frame (ct_debug_descriptor_frame_time)
     uint64_t launches = 0;
     std::string error;
 };
@@ -3085,6 +3086,94 @@ extern "C" int ct_collect_descriptors(CtHandle h, const float *positions_host, c
         hipStreamSynchronize(h->stream);
     }
     return rc;
+}
+
+extern "C" int ct_descriptor_frame(CtHandle h, uint32_t subframe_id, const uint32_t rect[4], uint32_t capacity,
+                                   uint8_t *descriptors_dev, float *positions_dev, float *directions_dev, uint32_t *pixels_dev,
+                                   uint32_t *count_out)
+{
+    NEED(h);
+    if (!descriptors_dev || !count_out) {
+        return fail(h, CT_E_INVAL, "ct_descriptor_frame: need a descriptor array and count_out");
+    }
+    *count_out = 0;
+    if (!h->camera_set) {
+        return fail(h, CT_E_STATE, "ct_set_camera has not been called");
+    }
+    const uint32_t W = h->scene.width, H = h->scene.height;
+    const uint32_t x0 = rect ? rect[0] : 0u, y0 = rect ? rect[1] : 0u, x1 = rect ? rect[2] : W, y1 = rect ? rect[3] : H;
+    if (x0 >= x1 || y0 >= y1 || x1 > W || y1 > H || (uint64_t)(x1 - x0) * (y1 - y0) > (1ull << 20)) {
+        return fail(h, CT_E_INVAL, "ct_descriptor_frame: the rect must be non-empty, inside the %u x %u frame and of at most 2^20 pixels", W, H);
+    }
+    const uint32_t rw = x1 - x0, n = rw * (y1 - y0), n_pad = (n + 255u) / 256u * 256u;
+    // VDBCloud::getVoxelSizeInMeters / getVoxelSizeInTermsOfFreePath, as in ct_collect_descriptors
+    const float maxs = (float)std::max(h->scene.dims[0], std::max(h->scene.dims[1], h->scene.dims[2]));
+    const float voxel_m = h->scene.cloud_size_m / maxs;
+    const float voxel_fp = voxel_m / h->scene.mean_free_path_m;
+    const float level0 = -ct_log2f(voxel_fp) - 1;
+    DevTemp<float4> d_found;
+    DevTemp<uint32_t> d_waves;
+    DevTemp<float> d_pos, d_dir;
+    h->dframe_scatter_ms = h->dframe_gather_ms = 0;
+    auto run = [&]() -> int {
+        // every temporary before any kernel
+        const size_t held = std::max<size_t>(1, std::min<size_t>(capacity, n));   // records the compacting write can produce
+        HIPCHK(h, dmalloc(&d_found, n_pad));
+        HIPCHK(h, dmalloc(&d_waves, n_pad / 64u + 1u));
+        if (!positions_dev) {
+            HIPCHK(h, dmalloc(&d_pos, 3 * held));
+        }
+        if (!directions_dev) {
+            HIPCHK(h, dmalloc(&d_dir, 3 * held));
+        }
+        const int prc = ensure_pyramid(h);
+        if (prc != CT_OK) {
+            return prc;
+        }
+        float *pos = positions_dev ? positions_dev : d_pos.p, *dir = directions_dev ? directions_dev : d_dir.p;
+        HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
+        HIPCHK(h, launch_first_scatter_frame(h->dev, x0, y0, rw, n, subframe_id, d_found, d_waves, capacity, pos, dir, pixels_dev,
+                                             h->stream));
+        HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
+        uint32_t count = 0;
+        HIPCHK(h, hipMemcpyAsync(&count, d_waves + n_pad / 64u, sizeof count, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        *count_out = count;
+        float ms = 0;
+        HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+        h->dframe_scatter_ms = ms;
+        if (count > capacity) {
+            return fail(h, CT_E_INVAL, "ct_descriptor_frame: %u valid pixels do not fit a capacity of %u", count, capacity);
+        }
+        if (count == 0) {
+            return CT_OK;
+        }
+        HIPCHK(h, hipEventRecord(h->ev[0], h->stream));   // (not ev[1] again: the host's look at the count is no part of the gather)
+        HIPCHK(h, launch_descriptors(h->dev, h->pyramid, pos, dir, count, level0, voxel_m, h->scene.cloud_size_m, descriptors_dev,
+                                     h->stream));
+        HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+        h->dframe_gather_ms = ms;
+        return CT_OK;
+    };
+    const int rc = run();
+    if (rc != CT_OK) {
+        hipStreamSynchronize(h->stream);
+    }
+    return rc;
+}
+
+extern "C" int ct_debug_descriptor_frame_time(CtHandle h, double *first_scatter_ms_out, double *gather_ms_out)
+{
+    NEED_NOFLUSH(h);
+    if (first_scatter_ms_out) {
+        *first_scatter_ms_out = h->dframe_scatter_ms;
+    }
+    if (gather_ms_out) {
+        *gather_ms_out = h->dframe_gather_ms;
+    }
+    return CT_OK;
 }
 
 extern "C" int ct_reset(CtHandle h)

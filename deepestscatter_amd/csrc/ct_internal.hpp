@@ -202,6 +202,13 @@ hipError_t launch_point_accumulate(const float4 *frames, uint32_t stride, void *
                                    hipStream_t stream);
 hipError_t launch_scatter_samples(const DevScene &sc, uint32_t count, uint32_t batch_seed, float *positions,
                                   float *directions, hipStream_t stream);
+// ct_descriptor_frame: first flight of the n pixels of the rect (x0, y0, row length w), a scan of the per-wave counts and the
+// compacting write, three dispatches.  found: (n rounded up to 256) float4; wave_counts: (n rounded up to 256) / 64 + 1 words,
+// afterwards the waves' offsets and, in the last word, the number of records; positions / directions hold `capacity` records,
+// pixels may be NULL.
+hipError_t launch_first_scatter_frame(const DevScene &sc, uint32_t x0, uint32_t y0, uint32_t w, uint32_t n, uint32_t subframe_id,
+                                      float4 *found, uint32_t *wave_counts, uint32_t capacity, float *positions, float *directions,
+                                      uint32_t *pixels, hipStream_t stream);
 // Density pyramid (Resources::generateMipmaps) and the descriptor gather.
 constexpr int kMaxMipLevels = 16;
 struct MipPyramid {

@@ -3019,6 +3019,146 @@ hipError_t launch_scatter_samples(const DevScene &sc, uint32_t count, uint32_t b
 }
 
 // =============================================================================================
+// first-scatter frame (ct_descriptor_frame): the device side of the reference's neural renderer, disneyCamera.cu -- per
+// pixel of a rect the first scatter position of the primary ray, compacted in the rect's row-major order.
+// =============================================================================================
+// Three dispatches.  (1) first_scatter_frame_kernel: lane i of the grid is pixel i of the rect in row-major order; it makes the
+// pixel's first flight with the device functions of primary_rays_kernel and scatter_samples_kernel, keeps the result in a
+// temporary -- (world position, valid ? 1 : 0), 16 bytes per rect pixel: the flight is hundreds of fetches and is not made
+// twice -- and every wave writes the number of its valid lanes.  (2) first_scatter_scan_kernel: exclusive scan of the wave
+// counts in one block (a rect has at most 2^20 pixels = 16384 waves), the total behind them.  (3) first_scatter_compact_kernel
+// reads the temporary, ranks the wave's valid lanes again (ballot + mbcnt: cheap) and stores position, direction and pixel index at
+// wave offset + rank.  No atomics: record k is the k-th valid pixel of the rect, whatever the order the waves ran in.
+struct FrameRect {
+    uint32_t x0, y0, w, n;   // origin, row length and pixel count of the rect
+};
+
+// pixel i of the rect, row-major
+CT_DEV void rect_pixel(const FrameRect &r, uint32_t i, uint32_t &x, uint32_t &y)
+{
+    x = r.x0 + i % r.w;
+    y = r.y0 + i / r.w;
+}
+
+template <bool FIXED8>
+__global__ __launch_bounds__(256) void first_scatter_frame_kernel(DevScene sc, FrameRect r, uint32_t subframe_id,
+                                                                 float4 *__restrict__ found, uint32_t *__restrict__ wave_counts)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;   // (every lane reaches the ballot: no early return)
+    bool valid = false;
+    f3 world = mk3(0, 0, 0);
+    if (i < r.n) {
+        uint32_t x, y;
+        rect_pixel(r, i, x, y);
+        const f3 eye = mk3(sc.ex, sc.ey, sc.ez);
+        const f3 d = primary_direction(sc, x, y);
+        float t_hit = 0;
+        if (intersect_box(sc, eye, d, t_hit)) {
+            f3 pos = add3(eye, scale3(d, t_hit));                       // cloudRadianceMaterials.cu:11
+            pos = add3(pos, scale3(mk3(sc.bx, sc.by, sc.bz), 0.5f));    // :12
+            const f3 dir = normalize3(d);                               // :17
+            uint32_t seed = tea4(x * 4096u + y, subframe_id);           // :21
+            const float xi = u24_to_float(lcg24(seed));
+            const bool scattered = plain_flight<FIXED8>(sc, xi, pos, dir);
+            if (scattered && in_box(sc, pos)) {
+                valid = true;
+                world = sub3(pos, scale3(mk3(sc.bx, sc.by, sc.bz), 0.5f));
+            }
+        }
+        found[i] = make_float4(world.x, world.y, world.z, valid ? 1.f : 0.f);
+    }
+    const uint64_t mask = __builtin_amdgcn_ballot_w64(valid);
+    if ((threadIdx.x & 63u) == 0u) {
+        wave_counts[i >> 6] = (uint32_t)__popcll(mask);
+    }
+}
+
+// In place: counts[w] becomes the number of valid pixels in the waves before w, counts[n_waves] the total.  One block.
+__global__ __launch_bounds__(1024) void first_scatter_scan_kernel(uint32_t *__restrict__ counts, uint32_t n_waves)
+{
+    __shared__ uint32_t sums[2][1024];
+    const uint32_t t = threadIdx.x;
+    const uint32_t per = (n_waves + 1023u) / 1024u;
+    const uint32_t begin = min(t * per, n_waves), end = min(begin + per, n_waves);
+    uint32_t own = 0;
+    for (uint32_t w = begin; w < end; w++) {
+        own += counts[w];
+    }
+    sums[0][t] = own;
+    __syncthreads();
+    int cur = 0;
+    for (uint32_t d = 1; d < 1024u; d *= 2u) {   // Hillis-Steele, inclusive
+        sums[cur ^ 1][t] = sums[cur][t] + (t >= d ? sums[cur][t - d] : 0u);
+        cur ^= 1;
+        __syncthreads();
+    }
+    uint32_t run = sums[cur][t] - own;
+    for (uint32_t w = begin; w < end; w++) {
+        const uint32_t c = counts[w];
+        counts[w] = run;
+        run += c;
+    }
+    if (t == 1023u) {
+        counts[n_waves] = sums[cur][t];
+    }
+}
+
+__global__ __launch_bounds__(256) void first_scatter_compact_kernel(DevScene sc, FrameRect r, const float4 *__restrict__ found,
+                                                                   const uint32_t *__restrict__ wave_offsets, uint32_t capacity,
+                                                                   float *__restrict__ positions, float *__restrict__ directions,
+                                                                   uint32_t *__restrict__ pixels)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    float4 f = make_float4(0, 0, 0, 0);
+    if (i < r.n) {
+        f = found[i];
+    }
+    const bool valid = f.w != 0.f;
+    const uint64_t mask = __builtin_amdgcn_ballot_w64(valid);
+    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+    if (!valid) {
+        return;
+    }
+    const size_t slot = (size_t)wave_offsets[i >> 6] + rank;
+    if (slot >= capacity) {   // (the host answers CT_E_INVAL for this call; nothing is written past the caller's arrays)
+        return;
+    }
+    uint32_t x, y;
+    rect_pixel(r, i, x, y);
+    const f3 dir = normalize3(primary_direction(sc, x, y));   // d2, as first_scatter_frame_kernel made it
+    positions[3 * slot + 0] = f.x; positions[3 * slot + 1] = f.y; positions[3 * slot + 2] = f.z;
+    directions[3 * slot + 0] = dir.x; directions[3 * slot + 1] = dir.y; directions[3 * slot + 2] = dir.z;
+    if (pixels) {
+        pixels[slot] = y * sc.width + x;
+    }
+}
+
+hipError_t launch_first_scatter_frame(const DevScene &sc, uint32_t x0, uint32_t y0, uint32_t w, uint32_t n, uint32_t subframe_id,
+                                      float4 *found, uint32_t *wave_counts, uint32_t capacity, float *positions, float *directions,
+                                      uint32_t *pixels, hipStream_t stream)
+{
+    const FrameRect r{ x0, y0, w, n };
+    const uint32_t blocks = (n + 255u) / 256u;
+    if (sc.tex_fixed8) {
+        hipLaunchKernelGGL(first_scatter_frame_kernel<true>, dim3(blocks), dim3(256), 0, stream, sc, r, subframe_id, found, wave_counts);
+    } else {
+        hipLaunchKernelGGL(first_scatter_frame_kernel<false>, dim3(blocks), dim3(256), 0, stream, sc, r, subframe_id, found, wave_counts);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        return e;
+    }
+    hipLaunchKernelGGL(first_scatter_scan_kernel, dim3(1), dim3(1024), 0, stream, wave_counts, blocks * 4u);
+    e = hipGetLastError();
+    if (e != hipSuccess) {
+        return e;
+    }
+    hipLaunchKernelGGL(first_scatter_compact_kernel, dim3(blocks), dim3(256), 0, stream, sc, r, found, wave_counts, capacity, positions,
+                       directions, pixels);
+    return hipGetLastError();
+}
+
+// =============================================================================================
 // progressive accumulation (progressive.cu:17-27) of S consecutive subframes, in order.
 // Only this shard's pixels are touched; everything else stays exactly 0 so that a sum over
 // shards (RCCL) reproduces the single-GPU image bit for bit.

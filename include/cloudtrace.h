@@ -362,6 +362,44 @@ CT_API int ct_generate_scatter_samples(CtHandle h, uint32_t count, uint32_t batc
 CT_API int ct_collect_descriptors(CtHandle h, const float *positions_host, const float *directions_host,
                                   uint32_t count, uint8_t *descriptors_host_out);
 
+/* The device side of the reference's neural renderer (src/CUDA/disneyCamera.cu + sampleDisneyDescriptor over rects of the
+ * frame): for every pixel of a rect, the first scatter position of the primary ray and the hierarchical descriptor at that
+ * point, as a device-resident batch a model can consume -- the two entry points above without the host in between.
+ * rect = {x0, y0, x1, y1}, half-open, inside the frame; NULL = the whole frame.  Pixel (x, y) follows the first lines of
+ * pinholeCamera / singleScatterSunRadiance (pathTracingCamera.cu:12-21, cloudRadianceMaterials.cu:11-21,120-134) exactly:
+ * d1 = normalize(U*dx + V*dy + W), dx = x / width * 2 - 1; a ray that misses the box gives no record; the flight starts at
+ * eye + d1 * t_hit + bbox / 2 in the direction d2 = normalize(d1) with xi = the first number of the seed
+ * tea<4>(x*4096+y, subframe_id) and is ONE march flight (getNextScatteringEvent, cloud.cuh:77-114) -- the first event
+ * CT_MODE_SUN_SINGLE_SCATTER draws for that pixel and subframe, whatever the handle's mode; the handle's estimator does not
+ * matter either (a DELTA handle makes the same march flight, as in ct_generate_scatter_samples).  A pixel whose flight
+ * scattered at a position inside the box (isInBox) is VALID and yields one record: position = the scatter position in world
+ * coordinates (box centred at 0, as ct_generate_scatter_samples), direction = d2, pixel = y * width + x, descriptor = exactly
+ * the bytes ct_collect_descriptors returns for that (position, direction).  CT_FLAG_TEX_FIXED8 applies to the flight and the
+ * gather as it does there.
+ * Records are compacted in ascending row-major order INSIDE THE RECT (wave counts, a scan, a ranked write: no atomics), so the
+ * same call always gives the same bytes.  *count_out = valid pixels of the rect.  The three record arrays hold `capacity`
+ * records each (descriptors_dev capacity * CT_DESCRIPTOR_BYTES bytes, positions_dev / directions_dev 3 * capacity floats,
+ * pixels_dev capacity words; those three may be NULL); *count_out > capacity: CT_E_INVAL with *count_out set, the arrays'
+ * contents unspecified (nothing is written past them), the handle usable.  No valid pixel: CT_OK, count 0.
+ * CT_E_INVAL: a NULL handle, descriptors_dev or count_out; a rect that is empty, exceeds the frame or has more than 2^20
+ * pixels.  The scene's shard_index / shard_count are IGNORED: the rect is the caller's way to split a frame over GPUs.
+ * Waits for the batches in flight, runs on the handle's stream and returns when it is idle.  Does not touch mean, M2, the
+ * frame, the subframe count, CtCounters or CtFetchCounters, drops no samples rendered ahead and leaves the pose's pixel
+ * list alone.  Temporaries are allocated before any kernel runs: CT_E_NOMEM leaves the handle usable.  The mip pyramid is
+ * built on first use, as in ct_collect_descriptors. */
+CT_API int ct_descriptor_frame(CtHandle h, uint32_t subframe_id, const uint32_t rect[4],
+                               uint32_t capacity,          /* records the three arrays can hold */
+                               uint8_t  *descriptors_dev,  /* capacity * CT_DESCRIPTOR_BYTES    */
+                               float    *positions_dev,    /* capacity * 3, may be NULL         */
+                               float    *directions_dev,   /* capacity * 3, may be NULL         */
+                               uint32_t *pixels_dev,       /* capacity, y * width + x, may be NULL */
+                               uint32_t *count_out);
+
+/* Diagnostic: milliseconds the GPU spent in the last ct_descriptor_frame of this handle, measured with HIP events on its
+ * stream: the first flights with their compaction, and the descriptor gather (0 when the call did not get that far).
+ * Either pointer may be NULL. */
+CT_API int ct_debug_descriptor_frame_time(CtHandle h, double *first_scatter_ms_out, double *gather_ms_out);
+
 /* ---- data access -------------------------------------------------------------------- */
 
 /* BufferBind<T>(buffer) map/copy, src/Util/BufferBind.h:11-74 (e.g. Camera.cpp:161,239-240).

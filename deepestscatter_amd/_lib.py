@@ -19,7 +19,7 @@ CT_EST_MARCH, CT_EST_DELTA = 0, 1
 CT_BUF_MEAN, CT_BUF_M2, CT_BUF_FRAME, CT_BUF_SCREEN, CT_BUF_INSCATTER, CT_BUF_DENSITY = range(6)
 CT_FLAG_NONE, CT_FLAG_SIMPLE_KERNEL, CT_FLAG_LIGHT_NORMALIZED, CT_FLAG_SPARSE_BRICKS, CT_FLAG_VMM_BRICKS = 0, 1, 2, 4, 8
 (CT_LAYOUT_DENSITY_BRICKS, CT_LAYOUT_SHADOW_BRICKS, CT_LAYOUT_MARCH_BRICKS, CT_LAYOUT_MARCH_ROWS, CT_LAYOUT_MARCH_COARSE,
- CT_LAYOUT_TWIN_BRICKS, CT_LAYOUT_MAJORANT_CELLS, CT_LAYOUT_MAJORANT_CODES) = range(8)   # ct_debug_layout
+ CT_LAYOUT_TWIN_BRICKS, CT_LAYOUT_MAJORANT_CELLS, CT_LAYOUT_MAJORANT_CODES, CT_LAYOUT_MIP_PYRAMID) = range(9)   # ct_debug_layout
 CT_FLAG_TEX_FIXED8 = 16   # filter weights in 1.8 fixed point, like the reference's texture unit (include/cloudtrace.h)
 
 # every symbol include/cloudtrace.h declares (tests check the library exports all of them)

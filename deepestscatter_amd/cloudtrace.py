@@ -507,13 +507,14 @@ class CloudTracer:
         return d
 
     LAYOUTS = ("density_bricks", "shadow_bricks", "march_bricks", "march_rows", "march_coarse", "twin_bricks", "majorant_cells",
-               "majorant_codes")
+               "majorant_codes", "mip_pyramid")
 
     def layout(self, which) -> tuple[np.ndarray, dict]:
         """The device bytes of one volume layout as stored, and the geometry that indexes it (ct_debug_layout): `which` is a
         name of LAYOUTS or a CT_LAYOUT_* value.  Bricks come as uint8 [bz, by, bx, 128] (sparse march bricks: [stored brick,
-        128]), the row table as uint32 [bz, by, 2], the coarse grid and the majorant cells / codes as uint8 [z, y, x].  A
-        layout the handle does not have raises CloudTraceError(CT_E_INVAL)."""
+        128]), the row table as uint32 [bz, by, 2], the coarse grid and the majorant cells / codes as uint8 [z, y, x], the mip
+        pyramid as its raw bytes, level after level (geometry: "levels" and the level-0 "dims" x, y, z).  A layout the handle
+        does not have raises CloudTraceError(CT_E_INVAL)."""
         which = self.LAYOUTS.index(which) if isinstance(which, str) else int(which)
         geom, n = np.zeros(16, np.uint32), C.c_size_t(0)
         check(self.L.ct_debug_layout(self.h, which, _p(geom), C.c_void_p(), 0, C.byref(n)), self.h)
@@ -530,6 +531,8 @@ class CloudTracer:
             return raw.view(np.uint32).reshape(g[1], g[0], 2), {"rows": (g[0], g[1])}
         if which == _lib.CT_LAYOUT_MARCH_COARSE:
             return raw.reshape(g[3], g[2], g[1]), {"shift": g[0], "cells": tuple(g[1:4]), "bias": g[4]}
+        if which == _lib.CT_LAYOUT_MIP_PYRAMID:
+            return raw, {"levels": g[0], "dims": tuple(g[1:4])}
         d = {"cell": g[0], "div": g[1], "stored": tuple(g[2:5]), "origin": tuple(g[5:8]), "virtual": tuple(g[8:11]), "bias": g[11]}
         return raw.reshape(g[4], g[3], g[2]), d
 

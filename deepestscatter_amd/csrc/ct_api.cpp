@@ -2847,6 +2847,18 @@ extern "C" int ct_point_radiance_launch(CtHandle h, CtPointRadianceTask *tasks_h
     if (h->scene.flags & CT_FLAG_SIMPLE_KERNEL) {
         return fail(h, CT_E_INVAL, "point radiance tasks need the persistent kernel");
     }
+    // A zero direction, or a direction or origin with a component that is not finite, has no ray, but can still "hit" the box
+    // (fmaxf drops the NaN slabs; 0 / 0 needs only an origin inside): the path would then march with NaN coordinates, which
+    // neither the estimators' brick addressing nor the DELTA estimator's cell walk is written for.  No ray of the reference is such.
+    for (uint32_t i = 0; i < count; i++) {
+        const float *d = tasks_host[i].direction, *o = tasks_host[i].position;
+        if (!(std::isfinite(d[0]) && std::isfinite(d[1]) && std::isfinite(d[2])) || (d[0] == 0.f && d[1] == 0.f && d[2] == 0.f)) {
+            return fail(h, CT_E_INVAL, "ct_point_radiance_launch: task %u has a zero or non-finite direction", i);
+        }
+        if (!(std::isfinite(o[0]) && std::isfinite(o[1]) && std::isfinite(o[2]))) {
+            return fail(h, CT_E_INVAL, "ct_point_radiance_launch: task %u has a non-finite position", i);
+        }
+    }
     const uint32_t n_pad = (count + 63u) & ~63u, n_groups = n_pad / 64u;
     if ((uint64_t)n_pad * launches > 0xffffffffull) {
         return fail(h, CT_E_INVAL, "too many task-launches for one call");
@@ -3659,7 +3671,7 @@ extern "C" int ct_debug_march_meta(CtHandle h, uint32_t geom_out[8], uint8_t *me
 }
 
 // The device bytes of one volume layout as stored, and the geometry that indexes it (include/cloudtrace.h).  No kernel: a
-// stream synchronise and one copy.
+// stream synchronise and one copy (CT_LAYOUT_MIP_PYRAMID builds the pyramid first if no descriptor call has yet).
 extern "C" int ct_debug_layout(CtHandle h, int32_t which, uint32_t geom_out[16], void *dst_host, size_t capacity, size_t *bytes_out)
 {
     NEED(h);
@@ -3734,6 +3746,20 @@ extern "C" int ct_debug_layout(CtHandle h, int32_t which, uint32_t geom_out[16],
         g[10] = (uint32_t)d.mc_vz;
         g[11] = (uint32_t)d.brick_bias;
         break;
+    case CT_LAYOUT_MIP_PYRAMID: {
+        const int prc = ensure_pyramid(h);   // (built on first use, as in ct_collect_descriptors; the copy below waits for it)
+        if (prc != CT_OK) {
+            return prc;
+        }
+        const MipPyramid &mp = h->pyramid;
+        src = h->d_pyramid;
+        bytes = (size_t)mp.offset[mp.levels - 1u] + (size_t)mp.nx[mp.levels - 1u] * mp.ny[mp.levels - 1u] * mp.nz[mp.levels - 1u];
+        g[0] = mp.levels;
+        g[1] = (uint32_t)mp.nx[0];
+        g[2] = (uint32_t)mp.ny[0];
+        g[3] = (uint32_t)mp.nz[0];
+        break;
+    }
     default:
         return fail(h, CT_E_INVAL, "ct_debug_layout: unknown layout %d", which);
     }

@@ -1897,6 +1897,14 @@ __global__ __launch_bounds__(256) void descriptor_kernel(DevScene sc, MipPyramid
     const int x = (int)(sample % 5u) - 2, y = (int)((sample / 5u) % 5u) - 2, z = (int)(sample / 25u) - 2;
     const f3 dir = add3(add3(scale3(ex, (float)x), scale3(ey, (float)y)), scale3(ez, (float)z));
     const f3 pos = add3(origin, scale3(dir, scale));
+    uint8_t *const dst = out + ((size_t)i * 10u + layer) * 225u + sample;
+    // A view (anti)parallel to the light has eX = normalize(0) = NaN, so every grid point of the sample is NaN, as it is
+    // for a sample whose position or view is not finite.  Such a point has no density to store: its byte is 0, by
+    // definition (include/cloudtrace.h), decided here before any float becomes an integer.
+    if (!(isfinite(pos.x) && isfinite(pos.y) && isfinite(pos.z))) {
+        *dst = 0;
+        return;
+    }
     // rtTex3DLod, mip-linear
     float lc = fminf(fmaxf(0.0f, lod), (float)(mp.levels - 1u));
     const float fl = floorf(lc);
@@ -1917,7 +1925,7 @@ __global__ __launch_bounds__(256) void descriptor_kernel(DevScene sc, MipPyramid
     const float distance = sqrtf(dot3(dist, dist));
     const float t = fminf(fmaxf(distance / mip_voxel, 0.0f), 1.0f);
     density = density + t * (0.0f - density);
-    out[((size_t)i * 10u + layer) * 225u + sample] = (uint8_t)(density * 255.0f);
+    *dst = isfinite(density) ? (uint8_t)(density * 255.0f) : (uint8_t)0;
 }
 
 hipError_t launch_descriptors(const DevScene &sc, const MipPyramid &mp, const float *positions, const float *directions,

@@ -331,7 +331,9 @@ typedef struct CtPointRadianceTask {
  * Tasks.cpp:135), seed tea<4>(i*4096, frame), and folds prd.result.x into task i with
  * PointRadianceTask::addExperimentResult (:40-51), in frame order.  tasks_host is updated in place.
  * This is the device part of RadianceCollector::update (RadianceCollector.cpp:88-96); replication,
- * merging, convergence and rescheduling stay with the caller. */
+ * merging, convergence and rescheduling stay with the caller.
+ * A task whose direction is zero, or whose direction or position has a component that is not finite, has no ray (a NaN sample
+ * of ct_generate_scatter_samples is one): CT_E_INVAL before anything is launched, tasks_host untouched. */
 CT_API int ct_point_radiance_launch(CtHandle h, CtPointRadianceTask *tasks_host, uint32_t count,
                                     uint32_t first_frame_id, uint32_t launches);
 
@@ -355,7 +357,11 @@ CT_API int ct_generate_scatter_samples(CtHandle h, uint32_t count, uint32_t batc
  * (f * 255, truncating).  positions are the ScatterSample records' `point` (world coordinates, box centred
  * at 0); both inputs are host arrays of 3*count floats; descriptors_host_out receives
  * count * CT_DESCRIPTOR_BYTES bytes, layer-major, then z, y, x -- the `grid` field of
- * Persistance::DisneyDescriptor (DeepestScatter_Train/Protocols/DisneyDescriptor.proto:7-10). */
+ * Persistance::DisneyDescriptor (DeepestScatter_Train/Protocols/DisneyDescriptor.proto:7-10).
+ * A view exactly parallel or antiparallel to the light has no frame: eX = normalize(0) is NaN and with it every grid point.
+ * The reference converts that NaN to a byte, which C leaves undefined; here a grid point whose position is not finite (this
+ * case, or a sample whose position or view is not finite) stores 0 -- what a saturating conversion gives -- so such a sample's
+ * descriptor is 2250 zero bytes.  The test is made on the floats, before any conversion to an integer. */
 #define CT_DESCRIPTOR_LAYERS 10
 #define CT_DESCRIPTOR_LAYER_SIZE 225
 #define CT_DESCRIPTOR_BYTES (CT_DESCRIPTOR_LAYERS * CT_DESCRIPTOR_LAYER_SIZE)
@@ -503,7 +509,10 @@ CT_API int ct_debug_march_meta(CtHandle h, uint32_t geom_out[8], uint8_t *meta_o
  *                             [4] bias
  *   CT_LAYOUT_TWIN_BRICKS     128 bytes per twin brick, x fastest;  geom: [0] bias, [1..3] bricks x, y, z
  *   CT_LAYOUT_MAJORANT_CELLS, CT_LAYOUT_MAJORANT_CODES   one byte per stored cell, x fastest;  geom: [0] cell edge, [1] mc_div,
- *                             [2..4] stored cells x, y, z, [5..7] first stored cell, [8..10] virtual cells, [11] bias */
+ *                             [2..4] stored cells x, y, z, [5..7] first stored cell, [8..10] virtual cells, [11] bias
+ *   CT_LAYOUT_MIP_PYRAMID     the density pyramid that ct_collect_descriptors and ct_descriptor_frame sample (built here if neither
+ *                             has run yet): one byte per texel, x fastest, level after level from level 0, level l having
+ *                             max(1, n >> l) texels per axis;  geom: [0] levels, [1..3] texels x, y, z of level 0 */
 enum {
     CT_LAYOUT_DENSITY_BRICKS = 0,
     CT_LAYOUT_SHADOW_BRICKS = 1,
@@ -512,7 +521,8 @@ enum {
     CT_LAYOUT_MARCH_COARSE = 4,
     CT_LAYOUT_TWIN_BRICKS = 5,
     CT_LAYOUT_MAJORANT_CELLS = 6,
-    CT_LAYOUT_MAJORANT_CODES = 7
+    CT_LAYOUT_MAJORANT_CODES = 7,
+    CT_LAYOUT_MIP_PYRAMID = 8
 };
 CT_API int ct_debug_layout(CtHandle h, int32_t which, uint32_t geom_out[16], void *dst_host, size_t capacity, size_t *bytes_out);
 

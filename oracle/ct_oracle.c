@@ -1014,11 +1014,19 @@ ORC_API void orc_collect_descriptors(const OrcScene *s, const float *positions, 
                     for (int x = -2; x <= 2; x++) {
                         const v3 dir = v3_add(v3_add(v3_scale(ex, (float)x), v3_scale(ey, (float)y)), v3_scale(ez, (float)z));
                         const v3 pos = v3_add(origin, v3_scale(dir, scale));
+                        /* a view (anti)parallel to the light (eX = normalize(0) = NaN), a position or a view that is
+                         * not finite: no density to store, the byte is 0 by definition -- tested before any float
+                         * becomes an integer (converting NaN is undefined in C) */
+                        if (!(isfinite(pos.x) && isfinite(pos.y) && isfinite(pos.z))) {
+                            o[layer * ORC_DESC_LAYER_SIZE + sample] = 0;
+                            sample++;
+                            continue;
+                        }
                         float density = tex3_lod(&c, pyramid, offsets, s->dims, levels, pos, lod);
                         const float distance = distance_to_box(&c, pos, mip_voxel);
                         const float t = fminf(fmaxf(distance / mip_voxel, 0.0f), 1.0f); /* saturate */
                         density = density + t * (0.0f - density);                      /* optix lerp */
-                        o[layer * ORC_DESC_LAYER_SIZE + sample] = (uint8_t)(density * 255.0f);
+                        o[layer * ORC_DESC_LAYER_SIZE + sample] = isfinite(density) ? (uint8_t)(density * 255.0f) : (uint8_t)0;
                         sample++;
                     }
                 }

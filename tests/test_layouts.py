@@ -460,7 +460,7 @@ def test_layouts_a_handle_does_not_have(monkeypatch):
     """Twin bricks and the majorant grid on a MARCH handle, twin bricks on a DELTA handle with another fetch layout, an unknown
     layout and a capacity that is too small answer CT_E_INVAL; a NULL destination returns size and geometry only."""
     tr = tracer("blobs")
-    for which in ("twin_bricks", "majorant_cells", "majorant_codes", 8, -1):
+    for which in ("twin_bricks", "majorant_cells", "majorant_codes", 9, -1):
         with pytest.raises(_lib.CloudTraceError) as e:
             tr.layout(which)
         assert e.value.code == _lib.CT_E_INVAL

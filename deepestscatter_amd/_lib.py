@@ -25,7 +25,7 @@ CT_FLAG_TEX_FIXED8 = 16   # filter weights in 1.8 fixed point, like the referenc
 # every symbol include/cloudtrace.h declares (tests check the library exports all of them)
 EXPORTS = [
     "ct_create", "ct_destroy", "ct_last_error", "ct_set_stream", "ct_set_camera", "ct_set_light", "ct_render_subframe",
-    "ct_accumulate", "ct_render_accumulate", "ct_render_accumulate_async", "ct_synchronize", "ct_copy_to_device_async", "ct_point_radiance_launch", "ct_generate_scatter_samples", "ct_collect_descriptors", "ct_descriptor_frame", "ct_debug_descriptor_frame_time", "ct_reset", "ct_tonemap", "ct_tonemap_async", "ct_set_render_ahead", "ct_rendered_subframes", "ct_set_stop_when_converged", "ct_converged_at", "ct_is_converged", "ct_tonemap_buffer", "ct_is_converged_buffers", "ct_download", "ct_upload",
+    "ct_accumulate", "ct_render_accumulate", "ct_render_accumulate_async", "ct_synchronize", "ct_copy_to_device_async", "ct_point_radiance_launch", "ct_generate_scatter_samples", "ct_collect_descriptors", "ct_descriptor_frame", "ct_debug_descriptor_frame_time", "ct_network_create", "ct_network_destroy", "ct_network_eval", "ct_debug_network_time", "ct_reset", "ct_tonemap", "ct_tonemap_async", "ct_set_render_ahead", "ct_rendered_subframes", "ct_set_stop_when_converged", "ct_converged_at", "ct_is_converged", "ct_tonemap_buffer", "ct_is_converged_buffers", "ct_download", "ct_upload",
     "ct_buffer_bytes", "ct_copy_to_device", "ct_device_ptr", "ct_subframes", "ct_set_subframes", "ct_counters", "ct_kernel_time",
     "ct_debug_cdf_inversion", "ct_debug_math_selftest", "ct_debug_fetch_probe", "ct_debug_fetch_probe_ws", "ct_debug_track_lines", "ct_debug_touched_lines", "ct_debug_stats", "ct_debug_stats_ex", "ct_debug_suspended", "ct_debug_timeline", "ct_debug_invariants", "ct_debug_memory", "ct_debug_delta_grid", "ct_debug_march_meta", "ct_debug_layout", "ct_fetch_counters", "ct_calculate_camera_variables", "ct_quantize_volume", "ct_load_vdb", "ct_generate_mipmaps",
     "ct_tile_owner", "ct_make_procedural_cloud",
@@ -33,6 +33,8 @@ EXPORTS = [
     "ct_group_render_accumulate", "ct_group_reset", "ct_group_merge", "ct_group_download", "ct_group_tonemap",
     "ct_group_is_converged", "ct_group_counters",
 ]
+# ... and ct_debug_bf16_round, the one declared symbol whose name has digits (the list above is matched by name pattern)
+DEBUG_EXPORTS = ["ct_debug_bf16_round"]
 
 
 class CtScene(C.Structure):
@@ -73,6 +75,18 @@ class CtCounters(C.Structure):
 
     def as_dict(self) -> dict:
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class CtNetworkDesc(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_uint32),
+        ("blocks", C.c_uint32),
+        ("width", C.c_uint32),
+        ("aux", C.c_uint32),
+        ("head_layers", C.c_uint32),
+        ("weights_host", C.c_void_p),
+        ("weight_count", C.c_size_t),
+    ]
 
 
 class CtFetchCounters(C.Structure):
@@ -120,6 +134,11 @@ def load():
         "ct_collect_descriptors": (i32, [vp, vp, vp, u32, vp]),
         "ct_descriptor_frame": (i32, [vp, u32, vp, u32, vp, vp, vp, vp, C.POINTER(u32)]),
         "ct_debug_descriptor_frame_time": (i32, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "ct_network_create": (i32, [vp, C.POINTER(CtNetworkDesc), C.POINTER(vp)]),
+        "ct_network_destroy": (i32, [vp]),
+        "ct_network_eval": (i32, [vp, vp, vp, vp, u32, vp]),
+        "ct_debug_network_time": (i32, [vp, C.POINTER(C.c_double)]),
+        "ct_debug_bf16_round": (f32, [f32]),
         "ct_reset": (i32, [vp]),
         "ct_tonemap": (i32, [vp, f32, vp, C.POINTER(f32)]),
         "ct_tonemap_async": (i32, [vp, f32]),

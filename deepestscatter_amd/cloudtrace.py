@@ -197,6 +197,7 @@ class CloudTracer:
         del keep
         check(rc, None)
         self.h = h
+        self._light = tuple(float(v) for v in self.params.light_direction)   # as given; light_direction() normalises it
 
     # -- lifetime -----------------------------------------------------------------------------
     def close(self):
@@ -226,6 +227,7 @@ class CloudTracer:
         density layouts, tables and buffers stay.  `color=None` keeps the colour.  The image is not cleared: reset() next."""
         d, c = _light_args(direction, color)
         check(self.L.ct_set_light(self.h, _p(d) if d is not None else None, _p(c) if c is not None else None, intensity), self.h)
+        self._light = tuple(float(v) for v in d)
 
     def render_subframe(self, subframe_id: int, out_dev_ptr: int | None = None):
         check(self.L.ct_render_subframe(self.h, subframe_id, C.c_void_p(out_dev_ptr) if out_dev_ptr else None), self.h)
@@ -312,6 +314,35 @@ class CloudTracer:
         a, b = C.c_double(0), C.c_double(0)
         check(self.L.ct_debug_descriptor_frame_time(self.h, C.byref(a), C.byref(b)), self.h)
         return float(a.value), float(b.value)
+
+    def network_frame(self, net, subframe_id: int, rect=None):
+        """The network's picture of `rect` (None = the whole frame): descriptor_frame, aux = dot(view direction, the direction
+        the light travels), net.eval, and the results scattered by the pixel list.
+        -> (float32 torch tensor [rect height, rect width] on the handle's device, 0 at the pixels without a record; records).
+        `net` is a deepestscatter_amd.network.Network of this tracer with one aux input."""
+        import torch
+        if net.shape.aux != 1:
+            raise ValueError(f"network_frame feeds one aux input (the light angle); this network has {net.shape.aux}")
+        x0, y0, x1, y1 = (int(v) for v in (rect if rect is not None else (0, 0, self.width, self.height)))
+        desc, _, view, pix = self.descriptor_frame(subframe_id, rect=rect)
+        count = int(pix.shape[0])
+        image = torch.zeros(((y1 - y0) * (x1 - x0),), dtype=torch.float32, device=desc.device)
+        if count:
+            light = torch.tensor(self.light_direction(), dtype=torch.float32, device=desc.device)
+            aux = (view * light).sum(dim=1).contiguous()
+            out = torch.empty((count,), dtype=torch.float32, device=desc.device)
+            torch.cuda.synchronize(desc.device)      # the library reads and writes them on the handle's stream, not on torch's
+            net.eval(desc.data_ptr(), aux.data_ptr(), count, out.data_ptr())
+            p = pix.to(torch.int64)
+            image[(p // self.width - y0) * (x1 - x0) + (p % self.width - x0)] = out
+        return image.reshape(y1 - y0, x1 - x0), count
+
+    def light_direction(self) -> np.ndarray:
+        """The direction the light travels, as the library normalises it (twice, like the reference: ct_set_light)."""
+        v = np.asarray(self._light, np.float32)
+        for _ in range(2):
+            v = v * (np.float32(1) / np.sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2], dtype=np.float32))
+        return v
 
     def reset(self):
         check(self.L.ct_reset(self.h), self.h)

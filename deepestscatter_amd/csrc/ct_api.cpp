@@ -23,6 +23,7 @@
 
 #include "../../include/cloudtrace.h"
 #include "ct_internal.hpp"
+#include "ct_network.hpp"
 
 using namespace ct;
 
@@ -3186,6 +3187,38 @@ extern "C" int ct_debug_descriptor_frame_time(CtHandle h, double *first_scatter_
         *gather_ms_out = h->dframe_gather_ms;
     }
     return CT_OK;
+}
+
+// The scattering network (ct_network.hip): the handle's part is the device, the stream and the wait for batches in flight.
+extern "C" int ct_network_create(CtHandle h, const CtNetworkDesc *d, CtNetwork *out)
+{
+    if (!h) {
+        return fail(nullptr, CT_E_INVAL, "null handle");
+    }
+    char err[256] = "";
+    int rc = ct::network_validate(d, out, err, sizeof err);   // (before the handle's device is touched)
+    if (rc != CT_OK) {
+        return fail(h, rc, "%s", err);
+    }
+    NEED(h);
+    rc = ct::network_create(h->device, d, out, err, sizeof err);
+    return rc == CT_OK ? CT_OK : fail(h, rc, "%s", err);
+}
+
+extern "C" int ct_network_eval(CtHandle h, CtNetwork n, const uint8_t *descriptors_dev, const float *aux_dev, uint32_t count,
+                               float *out_dev)
+{
+    NEED(h);
+    if (!n) {
+        return fail(h, CT_E_INVAL, "ct_network_eval: null network");
+    }
+    if (ct::network_device(n) != h->device) {
+        return fail(h, CT_E_INVAL, "ct_network_eval: the network lives on device %d, the handle on device %d", ct::network_device(n),
+                    h->device);
+    }
+    char err[256] = "";
+    const int rc = ct::network_eval(n, h->stream, descriptors_dev, aux_dev, count, out_dev, err, sizeof err);
+    return rc == CT_OK ? CT_OK : fail(h, rc, "%s", err);
 }
 
 extern "C" int ct_reset(CtHandle h)

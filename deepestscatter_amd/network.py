@@ -1,0 +1,225 @@
+"""The scattering network that ct_network_eval runs on descriptor records (include/cloudtrace.h, "the scattering network").
+
+The network is THIS PROJECT'S DEFINITION: the reference's DisneyModel.py was not available, so this is the progressive-feed
+residual MLP of the paper the reference implements (Kallweit et al. 2017), parameterised by its shapes.
+
+    ScatterNet          the torch.nn.Module a user trains or loads a state dict into (float32, no rounding)
+    pack_weights        its parameters as the flat float32 array of CtNetworkDesc.weights_host
+    reference_forward   numpy, with the rounding points of the definition: what the device is held to
+    Network             a CtNetwork on a CloudTracer's device
+
+State-dict names (the mapping an exported model needs): blocks.k.fc1 = W1_k, c1_k; blocks.k.fc2 = W2_k, c2_k (k = 0 .. 9);
+head.i = V_i, d_i (i = 0 .. H - 2); out = v, d.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _lib
+from ._lib import check
+
+BLOCKS = 10          # CT_DESCRIPTOR_LAYERS
+LAYER_BYTES = 225    # CT_DESCRIPTOR_LAYER_SIZE
+RECORD_BYTES = BLOCKS * LAYER_BYTES
+
+
+@dataclass(frozen=True)
+class NetworkShape:
+    width: int = 200
+    aux: int = 1
+    head_layers: int = 3
+
+    def fan_in(self, block: int) -> int:
+        return (self.width if block else 0) + LAYER_BYTES + self.aux
+
+    def weight_count(self) -> int:
+        w = self.width
+        blocks = sum(w * self.fan_in(k) + w + w * w + w for k in range(BLOCKS))
+        return blocks + (self.head_layers - 1) * (w * w + w) + w + 1
+
+    def macs(self) -> int:
+        """Multiply-adds per record (the biases are not counted)."""
+        w = self.width
+        return sum(w * self.fan_in(k) + w * w for k in range(BLOCKS)) + (self.head_layers - 1) * w * w + w
+
+
+def bf16_round(x) -> np.ndarray:
+    """float32 -> bf16 -> float32, round to nearest, ties to even; a NaN stays a NaN (as ct_debug_bf16_round)."""
+    a = np.ascontiguousarray(x, np.float32)
+    u = a.view(np.uint32).astype(np.uint64)
+    r = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000
+    nan = (u & 0x7FFFFFFF) > 0x7F800000
+    r = np.where(nan, (u | 0x400000) & 0xFFFF0000, r)
+    return r.astype(np.uint32).view(np.float32).reshape(a.shape)
+
+
+def _torch_module():
+    import torch
+
+    class _Block(torch.nn.Module):
+        def __init__(self, fan_in, width):
+            super().__init__()
+            self.fc1 = torch.nn.Linear(fan_in, width)
+            self.fc2 = torch.nn.Linear(width, width)
+
+    class ScatterNet(torch.nn.Module):
+        """forward(descriptors uint8 [n, 10, ...] or [n, 2250], aux float [n, A] or None) -> [n]."""
+
+        def __init__(self, width: int = 200, aux: int = 1, head_layers: int = 3):
+            super().__init__()
+            self.shape = NetworkShape(width, aux, head_layers)
+            self.blocks = torch.nn.ModuleList(_Block(self.shape.fan_in(k), width) for k in range(BLOCKS))
+            self.head = torch.nn.ModuleList(torch.nn.Linear(width, width) for _ in range(head_layers - 1))
+            self.out = torch.nn.Linear(width, 1)
+
+        def forward(self, descriptors, aux=None):
+            dtype = self.out.weight.dtype
+            n = descriptors.shape[0]
+            b = descriptors.reshape(n, BLOCKS, LAYER_BYTES).to(dtype) / 255.0
+            a = aux.reshape(n, self.shape.aux).to(dtype) if self.shape.aux else b.new_zeros((n, 0))
+            relu = torch.nn.functional.relu
+            z = None
+            for k, blk in enumerate(self.blocks):
+                x = torch.cat([b[:, k], a] if z is None else [z, b[:, k], a], dim=1)
+                h = relu(blk.fc1(x))
+                z = relu(blk.fc2(h)) if z is None else relu(z + blk.fc2(h))
+            for layer in self.head:
+                z = relu(layer(z))
+            return self.out(z)[:, 0]
+
+    return ScatterNet
+
+
+def __getattr__(name):
+    # ScatterNet needs torch, which the rest of this module (and the CPU-only users of the package) does not
+    if name == "ScatterNet":
+        cls = _torch_module()
+        globals()["ScatterNet"] = cls
+        return cls
+    raise AttributeError(name)
+
+
+def pack_weights(module) -> np.ndarray:
+    """The flat float32 array of CtNetworkDesc.weights_host: block after block W1, c1, W2, c2, then the head, each matrix before
+    its bias."""
+    layers = []
+    for blk in module.blocks:
+        layers += [blk.fc1, blk.fc2]
+    layers += list(module.head) + [module.out]
+    parts = []
+    for layer in layers:
+        parts.append(layer.weight.detach().cpu().numpy().astype(np.float32).reshape(-1))
+        parts.append(layer.bias.detach().cpu().numpy().astype(np.float32).reshape(-1))
+    flat = np.concatenate(parts)
+    assert flat.size == module.shape.weight_count()
+    return flat
+
+
+def unpack_weights(weights, shape: NetworkShape):
+    """-> [(W [out, in], bias [out])] in the array's order: W1_0, W2_0, W1_1, ... , V_i ..., v."""
+    w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+    if w.size != shape.weight_count():
+        raise ValueError(f"{w.size} weights, the shapes imply {shape.weight_count()}")
+    dims = []
+    for k in range(BLOCKS):
+        dims += [(shape.width, shape.fan_in(k)), (shape.width, shape.width)]
+    dims += [(shape.width, shape.width)] * (shape.head_layers - 1) + [(1, shape.width)]
+    out, at = [], 0
+    for rows, cols in dims:
+        W = w[at:at + rows * cols].reshape(rows, cols)
+        at += rows * cols
+        out.append((W, w[at:at + rows]))
+        at += rows
+    return out
+
+
+def reference_forward(weights, desc: NetworkShape, descriptors_u8, aux, accumulate=np.float64, rounding: bool = True) -> np.ndarray:
+    """The rounded model on the CPU: bf16 weights (byte columns as bf16(w / 255)), bytes as integers, aux / h / z rounded to
+    bf16 when produced, a layer's products and float32 bias summed in `accumulate`, out in float32's range as `accumulate`.
+    accumulate=np.float64 is the definition the device is held to, np.float32 the restatement whose distance from it sets the
+    tolerance.  rounding=False (tests only) is the plain network in `accumulate`: ScatterNet.forward."""
+    acc = np.dtype(accumulate)
+    rnd = (lambda v: bf16_round(np.asarray(v, np.float32)).astype(acc)) if rounding else (lambda v: np.asarray(v, acc))
+    layers = unpack_weights(weights, desc)
+    n = len(descriptors_u8)
+    b = np.asarray(descriptors_u8, np.uint8).reshape(n, BLOCKS, LAYER_BYTES).astype(acc)
+    a = rnd(np.asarray(aux, np.float32).reshape(n, desc.aux)) if desc.aux else np.zeros((n, 0), acc)
+
+    def matrix(W, byte_first=None):
+        W = np.array(W, np.float32)
+        if byte_first is not None:
+            cols = slice(byte_first, byte_first + LAYER_BYTES)
+            if rounding:
+                W[:, cols] = W[:, cols] / np.float32(255.0)
+            else:
+                W = W.astype(acc)
+                W[:, cols] = W[:, cols] / acc.type(255.0)
+        return rnd(W)
+
+    def linear(x, W, c):
+        return x @ W.T + c.astype(acc)
+
+    z = None
+    for k in range(BLOCKS):
+        (W1, c1), (W2, c2) = layers[2 * k], layers[2 * k + 1]
+        x = np.concatenate([b[:, k], a] if z is None else [z, b[:, k], a], axis=1)
+        h = rnd(np.maximum(linear(x, matrix(W1, desc.width if k else 0), c1), 0))
+        y = linear(h, matrix(W2), c2)
+        z = rnd(np.maximum(y if z is None else z + y, 0))
+    for W, c in layers[2 * BLOCKS:-1]:
+        z = rnd(np.maximum(linear(z, matrix(W), c), 0))
+    W, c = layers[-1]
+    return linear(z, matrix(W), c)[:, 0]
+
+
+class Network:
+    """A CtNetwork on `tracer`'s device (ct_network_create).  `module_or_weights`: a ScatterNet, or the flat array with
+    width / aux / head_layers given.  Close it before the tracer."""
+
+    def __init__(self, tracer, module_or_weights, width: int | None = None, aux: int | None = None, head_layers: int | None = None):
+        self.L = _lib.load()
+        self.tracer = tracer
+        if hasattr(module_or_weights, "blocks"):
+            self.shape = module_or_weights.shape
+            weights = pack_weights(module_or_weights)
+        else:
+            self.shape = NetworkShape(*(d if v is None else int(v) for v, d in zip((width, aux, head_layers), (200, 1, 3))))
+            weights = np.ascontiguousarray(module_or_weights, np.float32).reshape(-1)
+        d = _lib.CtNetworkDesc(_lib.CT_ABI_VERSION, BLOCKS, self.shape.width, self.shape.aux, self.shape.head_layers,
+                               weights.ctypes.data_as(C.c_void_p), weights.size)
+        n = C.c_void_p()
+        check(self.L.ct_network_create(tracer.h, C.byref(d), C.byref(n)), tracer.h)
+        self.n = n
+
+    def close(self):
+        if getattr(self, "n", None):
+            self.L.ct_network_destroy(self.n)
+            self.n = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def eval(self, descriptors_dev_ptr: int, aux_dev_ptr: int | None, count: int, out_dev_ptr: int):
+        """ct_network_eval on raw device pointers: count records of 2250 bytes, count * A floats (None when A == 0), count floats out."""
+        check(self.L.ct_network_eval(self.tracer.h, self.n, C.c_void_p(descriptors_dev_ptr), C.c_void_p(aux_dev_ptr) if aux_dev_ptr else None,
+                                     count, C.c_void_p(out_dev_ptr)), self.tracer.h)
+
+    def time_ms(self) -> float:
+        """GPU milliseconds of the last eval (ct_debug_network_time)."""
+        ms = C.c_double(0)
+        rc = self.L.ct_debug_network_time(self.n, C.byref(ms))
+        if rc != _lib.CT_OK:
+            raise _lib.CloudTraceError(rc, "ct_debug_network_time")
+        return float(ms.value)

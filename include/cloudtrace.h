@@ -406,6 +406,75 @@ CT_API int ct_descriptor_frame(CtHandle h, uint32_t subframe_id, const uint32_t 
  * Either pointer may be NULL. */
 CT_API int ct_debug_descriptor_frame_time(CtHandle h, double *first_scatter_ms_out, double *gather_ms_out);
 
+/* ---- the scattering network ------------------------------------------------------------
+ *
+ * ct_network_eval runs a network on the records that ct_descriptor_frame (or ct_collect_descriptors, uploaded) leaves on the
+ * device: one fused bf16 MFMA kernel that reads each record's 2250 bytes once and writes one float per record.
+ *
+ * THE NETWORK IS THIS PROJECT'S DEFINITION.  The reference's DisneyModel.py was not available when this was written; what
+ * follows is the progressive-feed residual MLP of the paper the reference implements (Kallweit et al. 2017, "Deep Scattering"),
+ * parameterised by its shapes.  A model trained elsewhere is exported into it by name (deepestscatter_amd/network.py, ScatterNet):
+ *     blocks.k.fc1.weight / .bias = W1_k, c1_k     blocks.k.fc2.weight / .bias = W2_k, c2_k      (k = 0 .. 9)
+ *     head.i.weight / .bias       = V_i, d_i       (i = 0 .. H - 2)                out.weight / .bias = v, d
+ *
+ * Parameters: K = CT_DESCRIPTOR_LAYERS (10) blocks; width Wd, a multiple of 8 with 16 <= Wd <= 256 (the reference-sized case is
+ * 200); A aux inputs per record, 0 <= A <= 8; H head layers, 1 <= H <= 4.
+ * Per record: b_k = the 225 bytes of descriptor layer k in the order ct_collect_descriptors stores them (z, y, x); a = the
+ * record's A aux floats.
+ * Forward pass (there is no state z_0):
+ *     block 0:      h = relu(W1_0 [b_0/255 | a] + c1_0)            z_1     = relu(W2_0 h + c2_0)
+ *     block k >= 1: h = relu(W1_k [z_k | b_k/255 | a] + c1_k)      z_{k+1} = relu(z_k + W2_k h + c2_k)
+ *     head:         H - 1 layers z <- relu(V_i z + d_i) of width Wd, then out = v z + d, one float, no output transform.
+ * Matrices are [out][in] row-major (the torch.nn.Linear layout), biases float32.
+ * Rounding (the "rounded model" the device implements; reference_forward of deepestscatter_amd/network.py restates it):
+ *   - every matrix entry is rounded to bf16, round-to-nearest-even, once, at create; the byte columns of W1_k are stored as
+ *     bf16(float32(w) / 255.0f) and the bytes enter as the integers 0 .. 255, which bf16 holds exactly;
+ *   - a, every h and every z_k are bf16 values, each rounded when it is produced; the residual adds the rounded z_k;
+ *   - inside a layer the products are summed in float32, and the float32 bias and the ReLU are applied there; out is float32.
+ *   The kernel pads to its tile sizes with zeros, which is exact and no part of the definition.  The order of a layer's float32
+ *   sum is the matrix unit's, so results agree with a CPU evaluation of the rounded model to float32 summation error, which
+ *   can flip a bf16 rounding that later layers carry on (tests/test_network.py states the bound).
+ *
+ * weights_host is one flat float32 array: block after block W1_k, c1_k, W2_k, c2_k (W1_0 has 225 + A columns, every other W1_k
+ * Wd + 225 + A in the order [z | b | a]), then the head V_0, d_0, ..., then v (Wd floats) and d (1) -- each matrix before its
+ * bias.  weight_count must be the number the shapes imply:
+ *     Wd (225 + A) + 9 Wd (Wd + 225 + A) + 10 (Wd Wd + 2 Wd) + (H - 1)(Wd Wd + Wd) + Wd + 1.
+ * The array is packed (padded, permuted to the kernel's fragments, rounded) at create and not retained. */
+typedef struct CtNetworkDesc {
+    uint32_t abi_version;      /* must be CT_ABI_VERSION */
+    uint32_t blocks;           /* must be CT_DESCRIPTOR_LAYERS */
+    uint32_t width;            /* Wd */
+    uint32_t aux;              /* A */
+    uint32_t head_layers;      /* H */
+    const float *weights_host;
+    size_t weight_count;
+} CtNetworkDesc;
+typedef struct CtNetwork_ *CtNetwork;
+
+/* A network on h's device, owned by the caller: destroy it before h.  CT_E_INVAL, before anything is allocated: a NULL
+ * argument, a wrong abi_version, blocks, width, aux or head_layers, a wrong weight_count, a weight that is not finite.
+ * ct_last_error(h) has the message. */
+CT_API int ct_network_create(CtHandle h, const CtNetworkDesc *d, CtNetwork *out);
+CT_API int ct_network_destroy(CtNetwork n);   /* NULL is a no-op */
+
+/* out_dev[i] = the network's output for record i, i < count.  descriptors_dev holds count * CT_DESCRIPTOR_BYTES bytes, aux_dev
+ * count * A floats, record after record (NULL if and only if A == 0); the arrays are 4-byte aligned.  Waits for the batches
+ * in flight like every synchronous entry point, runs on the handle's stream and returns when it is idle.  Allocates nothing
+ * (the packed weights belong to the CtNetwork) and uses no atomics: the same call gives the same bits.  Reads nothing past
+ * the count records, writes nothing but out_dev[0 .. count), and touches nothing of the progressive render -- mean, M2,
+ * frame, subframe count, counters, samples rendered ahead -- exactly as ct_descriptor_frame.  count == 0: CT_OK, nothing
+ * written.  CT_E_INVAL: a NULL handle, network, descriptors_dev or out_dev, aux_dev not matching A, an unaligned array,
+ * count > 2^20, a network that lives on another device than h. */
+CT_API int ct_network_eval(CtHandle h, CtNetwork n, const uint8_t *descriptors_dev, const float *aux_dev, uint32_t count,
+                           float *out_dev);
+
+/* Diagnostic: milliseconds the GPU spent in the kernel of the last ct_network_eval of this network (HIP events on its stream). */
+CT_API int ct_debug_network_time(CtNetwork n, double *ms_out);
+
+/* Diagnostic: x rounded to bf16 (round to nearest, ties to even; a NaN stays a NaN) and widened again -- the one rounding
+ * routine ct_network_create packs with. */
+CT_API float ct_debug_bf16_round(float x);
+
 /* ---- data access -------------------------------------------------------------------- */
 
 /* BufferBind<T>(buffer) map/copy, src/Util/BufferBind.h:11-74 (e.g. Camera.cpp:161,239-240).

@@ -21,11 +21,12 @@ CT_FLAG_NONE, CT_FLAG_SIMPLE_KERNEL, CT_FLAG_LIGHT_NORMALIZED, CT_FLAG_SPARSE_BR
 (CT_LAYOUT_DENSITY_BRICKS, CT_LAYOUT_SHADOW_BRICKS, CT_LAYOUT_MARCH_BRICKS, CT_LAYOUT_MARCH_ROWS, CT_LAYOUT_MARCH_COARSE,
  CT_LAYOUT_TWIN_BRICKS, CT_LAYOUT_MAJORANT_CELLS, CT_LAYOUT_MAJORANT_CODES, CT_LAYOUT_MIP_PYRAMID) = range(9)   # ct_debug_layout
 CT_FLAG_TEX_FIXED8 = 16   # filter weights in 1.8 fixed point, like the reference's texture unit (include/cloudtrace.h)
+CT_NET_OUT_LINEAR, CT_NET_OUT_EXPM1 = 0, 1   # CtNetworkRender.transform
 
 # every symbol include/cloudtrace.h declares (tests check the library exports all of them)
 EXPORTS = [
     "ct_create", "ct_destroy", "ct_last_error", "ct_set_stream", "ct_set_camera", "ct_set_light", "ct_render_subframe",
-    "ct_accumulate", "ct_render_accumulate", "ct_render_accumulate_async", "ct_synchronize", "ct_copy_to_device_async", "ct_point_radiance_launch", "ct_generate_scatter_samples", "ct_collect_descriptors", "ct_descriptor_frame", "ct_debug_descriptor_frame_time", "ct_network_create", "ct_network_destroy", "ct_network_eval", "ct_debug_network_time", "ct_reset", "ct_tonemap", "ct_tonemap_async", "ct_set_render_ahead", "ct_rendered_subframes", "ct_set_stop_when_converged", "ct_converged_at", "ct_is_converged", "ct_tonemap_buffer", "ct_is_converged_buffers", "ct_download", "ct_upload",
+    "ct_accumulate", "ct_render_accumulate", "ct_render_accumulate_async", "ct_synchronize", "ct_copy_to_device_async", "ct_point_radiance_launch", "ct_generate_scatter_samples", "ct_collect_descriptors", "ct_descriptor_frame", "ct_debug_descriptor_frame_time", "ct_network_create", "ct_network_destroy", "ct_network_eval", "ct_debug_network_time", "ct_network_render_subframe", "ct_network_render_accumulate", "ct_debug_network_aux", "ct_debug_network_render_time", "ct_reset", "ct_tonemap", "ct_tonemap_async", "ct_set_render_ahead", "ct_rendered_subframes", "ct_set_stop_when_converged", "ct_converged_at", "ct_is_converged", "ct_tonemap_buffer", "ct_is_converged_buffers", "ct_download", "ct_upload",
     "ct_buffer_bytes", "ct_copy_to_device", "ct_device_ptr", "ct_subframes", "ct_set_subframes", "ct_counters", "ct_kernel_time",
     "ct_debug_cdf_inversion", "ct_debug_math_selftest", "ct_debug_fetch_probe", "ct_debug_fetch_probe_ws", "ct_debug_track_lines", "ct_debug_touched_lines", "ct_debug_stats", "ct_debug_stats_ex", "ct_debug_suspended", "ct_debug_timeline", "ct_debug_invariants", "ct_debug_memory", "ct_debug_delta_grid", "ct_debug_march_meta", "ct_debug_layout", "ct_fetch_counters", "ct_calculate_camera_variables", "ct_quantize_volume", "ct_load_vdb", "ct_generate_mipmaps",
     "ct_tile_owner", "ct_make_procedural_cloud",
@@ -89,6 +90,15 @@ class CtNetworkDesc(C.Structure):
     ]
 
 
+class CtNetworkRender(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_uint32),
+        ("transform", C.c_int32),
+        ("rgb_scale", C.c_float * 3),
+        ("band_pixels", C.c_uint32),
+    ]
+
+
 class CtFetchCounters(C.Structure):
     _fields_ = [("density_fetches", C.c_uint64), ("inscatter_fetches", C.c_uint64)]
 
@@ -139,6 +149,10 @@ def load():
         "ct_network_eval": (i32, [vp, vp, vp, vp, u32, vp]),
         "ct_debug_network_time": (i32, [vp, C.POINTER(C.c_double)]),
         "ct_debug_bf16_round": (f32, [f32]),
+        "ct_network_render_subframe": (i32, [vp, vp, C.POINTER(CtNetworkRender), u32, vp]),
+        "ct_network_render_accumulate": (i32, [vp, vp, C.POINTER(CtNetworkRender), u32, u32]),
+        "ct_debug_network_aux": (i32, [vp, vp, u32, vp]),
+        "ct_debug_network_render_time": (i32, [vp, C.POINTER(C.c_double)]),
         "ct_reset": (i32, [vp]),
         "ct_tonemap": (i32, [vp, f32, vp, C.POINTER(f32)]),
         "ct_tonemap_async": (i32, [vp, f32]),

@@ -337,6 +337,67 @@ class CloudTracer:
             image[(p // self.width - y0) * (x1 - x0) + (p % self.width - x0)] = out
         return image.reshape(y1 - y0, x1 - x0), count
 
+    @staticmethod
+    def _network_render_params(transform, rgb_scale, band_pixels) -> "_lib.CtNetworkRender":
+        names = {"linear": _lib.CT_NET_OUT_LINEAR, "expm1": _lib.CT_NET_OUT_EXPM1}
+        t = names.get(transform, transform) if isinstance(transform, str) else transform
+        if isinstance(t, str):
+            raise _lib.CloudTraceError(_lib.CT_E_INVAL, f"network render: unknown transform {transform!r} (linear | expm1)")
+        p = _lib.CtNetworkRender()
+        p.abi_version = _lib.CT_ABI_VERSION
+        p.transform = int(t)
+        p.rgb_scale[:] = [float(v) for v in rgb_scale]
+        p.band_pixels = int(band_pixels)
+        return p
+
+    def network_render_subframe(self, net, subframe_id: int, transform="linear", rgb_scale=(1.0, 1.0, 1.0), band_pixels: int = 0,
+                                out=None):
+        """ct_network_render_subframe: the network's frame of one subframe -- per pixel with a first-scatter record
+        rgb_scale * max(L, 0) with L = out ("linear") or expf(out) - 1 ("expm1"), alpha 1; (0, 0, 0, 1) elsewhere -- into the
+        handle's CT_BUF_FRAME and into a float32 torch tensor [H, W, 4] on the handle's device, which is returned (`out`: a
+        tensor of that shape to write into; False: CT_BUF_FRAME only, returns None).  `net`: a deepestscatter_amd.network.Network
+        of this tracer with one aux input.  band_pixels: pixels handled at once (0 = 2^20); the image does not depend on it."""
+        p = self._network_render_params(transform, rgb_scale, band_pixels)
+        ptr = None
+        if out is not False:
+            import torch
+            dev = torch.device("cuda", self.params.device)
+            if out is None:
+                out = torch.empty((self.height, self.width, 4), dtype=torch.float32, device=dev)
+            if tuple(out.shape) != (self.height, self.width, 4) or out.dtype != torch.float32 or not out.is_contiguous():
+                raise ValueError("out must be a contiguous float32 tensor [H, W, 4]")
+            torch.cuda.synchronize(dev)      # the library writes it on the handle's stream, not on torch's
+            ptr = C.c_void_p(out.data_ptr())
+        check(self.L.ct_network_render_subframe(self.h, net.n, C.byref(p), subframe_id & 0xFFFFFFFF, ptr), self.h)
+        return None if out is False else out
+
+    def network_render_accumulate(self, net, first_subframe_id: int, count: int, transform="linear", rgb_scale=(1.0, 1.0, 1.0),
+                                  band_pixels: int = 0):
+        """ct_network_render_accumulate: network_render_subframe(id) + accumulate(id) for id = first .. first + count - 1, fused
+        (no frame is materialised); mean, M2 and the subframe count end exactly as that loop leaves them."""
+        p = self._network_render_params(transform, rgb_scale, band_pixels)
+        check(self.L.ct_network_render_accumulate(self.h, net.n, C.byref(p), first_subframe_id & 0xFFFFFFFF, count), self.h)
+
+    def network_aux(self, directions):
+        """ct_debug_network_aux: the renderer's aux input dot(direction, the direction the light travels) for a float32 torch
+        tensor [n, 3] on the handle's device -> float32 tensor [n]."""
+        import torch
+        d = directions.contiguous()
+        if d.dtype != torch.float32 or d.dim() != 2 or d.shape[1] != 3:
+            raise ValueError("directions must be a float32 tensor [n, 3]")
+        aux = torch.empty((d.shape[0],), dtype=torch.float32, device=d.device)
+        torch.cuda.synchronize(d.device)
+        check(self.L.ct_debug_network_aux(self.h, C.c_void_p(d.data_ptr()) if d.shape[0] else None, int(d.shape[0]),
+                                          C.c_void_p(aux.data_ptr()) if d.shape[0] else None), self.h)
+        return aux
+
+    def network_render_time(self):
+        """-> (first flights + compaction, descriptor gather, network, aux + compose / accumulate) GPU milliseconds of the last
+        network_render_subframe / network_render_accumulate, summed over its bands and subframes (ct_debug_network_render_time)."""
+        ms = (C.c_double * 4)()
+        check(self.L.ct_debug_network_render_time(self.h, ms), self.h)
+        return tuple(float(v) for v in ms)
+
     def light_direction(self) -> np.ndarray:
         """The direction the light travels, as the library normalises it (twice, like the reference: ct_set_light)."""
         v = np.asarray(self._light, np.float32)

@@ -37,7 +37,7 @@ struct Knob {
     const char *get() const { return is_set ? text.c_str() : nullptr; }
     explicit operator bool() const { return is_set; }
 };
-#define CT_KNOBS(X) X(BURST_IDLE) X(BURST_MARCH_MIN) X(BURST_SCATTER) X(CHUNK_INTERLEAVE) X(CHUNK_MORTON) X(CONTINUATION) X(DEBUG_INVARIANTS) X(DELTA_INTERIOR) X(DELTA_NEE) X(EXCHANGE) X(HAND_ON_JOBS) X(HINT_PERIOD) X(JOB_MAX) X(JOB_WORK) X(MARCH_BURST) X(MAX_AGE) X(NEE_CACHE) X(NO_ADVANCE) X(POINT_BLOCKS_PER_CU) X(POINT_ORDER) X(REGEN_MIN) X(RENDER_AHEAD) X(SCATTER_MIN) X(SCATTER_RATIO) X(SCRATCH_GIB) X(SCRATCH_MIB) X(SERPENTINE) X(SHARED_DEPTH) X(SPARSE) X(STATS) X(TAIL_BURST) X(TILE_ORDER) X(TIMELINE) X(TRACE) X(TUNE_SUBFRAMES) X(XCD_QUEUES) X(XCD_QUEUES_UNTUNED) X(XCD_REGIONS) X(BLOCKS_PER_CU)
+#define CT_KNOBS(X) X(BURST_IDLE) X(BURST_MARCH_MIN) X(BURST_SCATTER) X(CHUNK_INTERLEAVE) X(CHUNK_MORTON) X(CONTINUATION) X(DEBUG_INVARIANTS) X(DELTA_INTERIOR) X(DELTA_NEE) X(EXCHANGE) X(HAND_ON_JOBS) X(HINT_PERIOD) X(JOB_MAX) X(JOB_WORK) X(MARCH_BURST) X(MAX_AGE) X(NEE_CACHE) X(NET_DESC_RECORDS) X(NO_ADVANCE) X(POINT_BLOCKS_PER_CU) X(POINT_ORDER) X(REGEN_MIN) X(RENDER_AHEAD) X(SCATTER_MIN) X(SCATTER_RATIO) X(SCRATCH_GIB) X(SCRATCH_MIB) X(SERPENTINE) X(SHARED_DEPTH) X(SPARSE) X(STATS) X(TAIL_BURST) X(TILE_ORDER) X(TIMELINE) X(TRACE) X(TUNE_SUBFRAMES) X(XCD_QUEUES) X(XCD_QUEUES_UNTUNED) X(XCD_REGIONS) X(BLOCKS_PER_CU)
 struct CtTuning {
 #define X(name) Knob name;
     CT_KNOBS(X)
@@ -245,6 +245,17 @@ struct CtHandle_ {
     uint32_t subframes = 0;
     double render_ms = 0, accum_ms = 0;
     double dframe_scatter_ms = 0, dframe_gather_ms = 0;   // the last ct_descriptor_frame (ct_debug_descriptor_frame_time)
+    // ct_network_render_*: the temporaries of a band stay with the handle (a frame is many bands, a render many frames).
+    // found / waves / pos / dir / aux / out hold a band of band_cap pixels; desc holds desc_cap records, the largest count
+    // seen so far (or what the device gave: a band with more records goes through gather and network in pieces).
+    struct NetScratch {
+        float4 *found = nullptr;
+        uint32_t *waves = nullptr;
+        float *pos = nullptr, *dir = nullptr, *aux = nullptr, *out = nullptr;
+        uint8_t *desc = nullptr;
+        size_t band_cap = 0, desc_cap = 0;
+        double ms[4] = { 0, 0, 0, 0 };   // the last call (ct_debug_network_render_time)
+    } net;
     uint64_t launches = 0;
     std::string error;
 };
@@ -502,7 +513,8 @@ static void release(CtHandle h)
 #endif
     void *ptrs[] = { h->d_density, h->d_inscatter, h->d_dbricks, h->d_ibricks, h->d_mbricks, h->d_tbricks, h->d_touched[0], h->d_touched[1], h->d_mrows, h->d_mcoarse, h->d_pyramid, h->d_mie, h->d_chopped, h->d_cdf,
                      h->d_guide, h->d_dist, h->d_dist_tmp, h->d_majorant, h->d_maj_cells, h->d_maj_codes, h->d_frame, h->d_mean, h->d_m2, h->d_screen, h->d_frames_all, h->cont[0], h->cont[1], h->left[0], h->left[1], h->d_cont_count, h->d_cont_total, h->d_primary, h->d_advance, h->d_pixels, h->d_cost, h->d_group_rank, h->d_group_order, h->d_job_group, h->d_job_sub, h->d_queue,
-                     h->d_counters, h->d_colsum, h->d_avg, h->d_freeze, h->d_hit, h->d_cost_plane, h->d_timeline, h->pt.tasks, h->pt.primary, h->pt.frames, h->pt.pixels, h->pt.jg, h->pt.js };
+                     h->d_counters, h->d_colsum, h->d_avg, h->d_freeze, h->d_hit, h->d_cost_plane, h->d_timeline, h->pt.tasks, h->pt.primary, h->pt.frames, h->pt.pixels, h->pt.jg, h->pt.js,
+                     h->net.found, h->net.waves, h->net.pos, h->net.dir, h->net.aux, h->net.out, h->net.desc };
     for (void *p : ptrs) {
         if (p) {
             hipFree(p);
@@ -3219,6 +3231,302 @@ extern "C" int ct_network_eval(CtHandle h, CtNetwork n, const uint8_t *descripto
     char err[256] = "";
     const int rc = ct::network_eval(n, h->stream, descriptors_dev, aux_dev, count, out_dev, err, sizeof err);
     return rc == CT_OK ? CT_OK : fail(h, rc, "%s", err);
+}
+
+// ---- the network as a renderer (ct_network_render_*) ------------------------------------------------------------------
+// Every CT_E_INVAL of the two entry points except the NULL handle and the ids; nothing of the handle is touched.
+static int net_validate(CtHandle h, CtNetwork n, const CtNetworkRender *p, const char *who)
+{
+    if (!n || !p) {
+        return fail(h, CT_E_INVAL, "%s: need a network and its parameters", who);
+    }
+    if (p->abi_version != CT_ABI_VERSION) {
+        return fail(h, CT_E_INVAL, "%s: abi_version %u, this library is %u", who, p->abi_version, CT_ABI_VERSION);
+    }
+    if (p->transform != CT_NET_OUT_LINEAR && p->transform != CT_NET_OUT_EXPM1) {
+        return fail(h, CT_E_INVAL, "%s: unknown output transform %d", who, p->transform);
+    }
+    if (!std::isfinite(p->rgb_scale[0]) || !std::isfinite(p->rgb_scale[1]) || !std::isfinite(p->rgb_scale[2])) {
+        return fail(h, CT_E_INVAL, "%s: rgb_scale is not finite", who);
+    }
+    if (ct::network_aux_inputs(n) != 1u) {
+        return fail(h, CT_E_INVAL, "%s: the renderer feeds one aux input (the light angle); this network has %u", who,
+                    ct::network_aux_inputs(n));
+    }
+    if (ct::network_device(n) != h->device) {
+        return fail(h, CT_E_INVAL, "%s: the network lives on device %d, the handle on device %d", who, ct::network_device(n), h->device);
+    }
+    if (h->scene.shard_count > 1u) {
+        return fail(h, CT_E_INVAL, "%s: this handle renders shard %u of %u; a sharded network frame is out of scope (ct_descriptor_frame "
+                                   "ignores shards: split the frame by rects over the GPUs)", who, h->scene.shard_index, h->scene.shard_count);
+    }
+    return CT_OK;
+}
+
+// Rows of a band: whole rows of at most band_pixels pixels, at least one (a row has at most 12288 pixels), at most 2^20 pixels.
+static uint32_t net_band_rows(CtHandle h, uint32_t band_pixels)
+{
+    const uint32_t cap = (band_pixels == 0u || band_pixels > (1u << 20)) ? (1u << 20) : band_pixels;
+    return std::min(h->scene.height, std::max(1u, cap / h->scene.width));
+}
+
+// Records the descriptor array may hold at most: 2^20 (a band has no more), or CT_NET_DESC_RECORDS.
+static size_t net_descriptor_limit(CtHandle h)
+{
+    return (size_t)knob_int(h->tune.NET_DESC_RECORDS, 1, 1 << 20, 1 << 20);
+}
+
+// Everything a call needs before its first kernel: the band-sized temporaries and a first piece of the descriptor array.  The
+// stream is idle.  A failed growth leaves what the handle had.
+static int net_reserve(CtHandle h, size_t band_pixels)
+{
+    CtHandle_::NetScratch &s = h->net;
+    const size_t n_pad = (band_pixels + 255u) / 256u * 256u;
+    if (n_pad > s.band_cap) {
+        DevTemp<float4> found;
+        DevTemp<uint32_t> waves;
+        DevTemp<float> pos, dir, aux, out;
+        HIPCHK(h, dmalloc(&found, n_pad));
+        HIPCHK(h, dmalloc(&waves, n_pad / 64u + 1u));
+        HIPCHK(h, dmalloc(&pos, 3 * n_pad));
+        HIPCHK(h, dmalloc(&dir, 3 * n_pad));
+        HIPCHK(h, dmalloc(&aux, n_pad));
+        HIPCHK(h, dmalloc(&out, n_pad));
+        for (void *old : { (void *)s.found, (void *)s.waves, (void *)s.pos, (void *)s.dir, (void *)s.aux, (void *)s.out }) {
+            if (old) {
+                hipFree(old);
+            }
+        }
+        s.found = found.release();
+        s.waves = waves.release();
+        s.pos = pos.release();
+        s.dir = dir.release();
+        s.aux = aux.release();
+        s.out = out.release();
+        s.band_cap = n_pad;
+    }
+    if (s.desc_cap == 0) {
+        // (CT_NET_DESC_RECORDS: the array never holds more records than this -- what a device without room for the growth leaves
+        // a handle with, for the test that runs a band in pieces)
+        const size_t first = std::min<size_t>(std::min<size_t>(n_pad, 4096), net_descriptor_limit(h));
+        HIPCHK(h, dmalloc(&s.desc, first * CT_DESCRIPTOR_BYTES));
+        s.desc_cap = first;
+    }
+    return CT_OK;
+}
+
+// The descriptor array follows the largest record count seen.  Between bands, the stream idle.  When the device has no room
+// for it the array stays as it is and the band's records are gathered and evaluated in pieces of its size.
+static void net_grow_descriptors(CtHandle h, size_t count)
+{
+    CtHandle_::NetScratch &s = h->net;
+    count = std::min(count, net_descriptor_limit(h));
+    if (count <= s.desc_cap) {
+        return;
+    }
+    uint8_t *bigger = nullptr;
+    if (dmalloc(&bigger, count * CT_DESCRIPTOR_BYTES) != hipSuccess) {
+        (void)hipGetLastError();
+        return;
+    }
+    hipFree(s.desc);
+    s.desc = bigger;
+    s.desc_cap = count;
+}
+
+// One band: rows [y0, y0 + rows) of subframe `sid` into the frame (frame != NULL) or into mean / M2.
+static int net_band(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t sid, uint32_t y0, uint32_t rows, float level0,
+                    float voxel_m, bool accumulate)
+{
+    CtHandle_::NetScratch &s = h->net;
+    const uint32_t W = h->scene.width, npx = W * rows, n_pad = (npx + 255u) / 256u * 256u;
+    float ms = 0;
+    HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
+    HIPCHK(h, launch_first_scatter_frame(h->dev, 0u, y0, W, npx, sid, s.found, s.waves, npx, s.pos, s.dir, nullptr, h->stream));
+    HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
+    uint32_t count = 0;
+    HIPCHK(h, hipMemcpyAsync(&count, s.waves + n_pad / 64u, sizeof count, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+    s.ms[0] += ms;
+    if (count > npx) {
+        return fail(h, CT_E_HIP, "internal: a band of %u pixels counted %u records", npx, count);
+    }
+    if (count != 0u) {
+        net_grow_descriptors(h, count);
+        for (uint32_t at = 0; at < count;) {
+            const uint32_t piece = (uint32_t)std::min<size_t>(count - at, s.desc_cap);
+            HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
+            HIPCHK(h, launch_descriptors(h->dev, h->pyramid, s.pos + 3 * (size_t)at, s.dir + 3 * (size_t)at, piece, level0, voxel_m,
+                                         h->scene.cloud_size_m, s.desc, h->stream));
+            HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
+            // l = the direction the light travels: the uniforms hold -l (Sun.cpp:13-18)
+            HIPCHK(h, launch_network_aux(s.dir + 3 * (size_t)at, piece, -h->dev.nlx, -h->dev.nly, -h->dev.nlz, s.aux + at, h->stream));
+            HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
+            char err[256] = "";
+            const int rc = ct::network_eval(n, h->stream, s.desc, s.aux + at, piece, s.out + at, err, sizeof err);   // (waits)
+            if (rc != CT_OK) {
+                return fail(h, rc, "%s", err);
+            }
+            HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+            s.ms[1] += ms;
+            HIPCHK(h, hipEventElapsedTime(&ms, h->ev[1], h->ev[2]));
+            s.ms[3] += ms;
+            double net_ms = 0;
+            ct_debug_network_time(n, &net_ms);
+            s.ms[2] += net_ms;
+            at += piece;
+        }
+    }
+    const NetCompose c{ p->transform, p->rgb_scale[0], p->rgb_scale[1], p->rgb_scale[2] };
+    const size_t first_pixel = (size_t)y0 * W;
+    HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
+    HIPCHK(h, launch_network_compose(s.found, s.waves, s.out, npx, c, accumulate ? nullptr : h->d_frame + first_pixel,
+                                     h->d_mean + first_pixel, h->d_m2 + first_pixel, sid, h->stop_cadence ? h->d_freeze : nullptr,
+                                     h->stream));
+    HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
+    HIPCHK(h, hipEventSynchronize(h->ev[1]));
+    HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+    s.ms[3] += ms;
+    if (accumulate) {
+        h->accum_ms += ms;
+    }
+    return CT_OK;
+}
+
+// Subframes [first, first + count) band by band.  The caller has validated and flushed.
+static int net_run(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t first, uint32_t count, bool accumulate)
+{
+    const uint32_t H = h->scene.height, rows = net_band_rows(h, p->band_pixels);
+    // VDBCloud::getVoxelSizeInMeters / getVoxelSizeInTermsOfFreePath, as in ct_collect_descriptors
+    const float maxs = (float)std::max(h->scene.dims[0], std::max(h->scene.dims[1], h->scene.dims[2]));
+    const float voxel_m = h->scene.cloud_size_m / maxs;
+    const float voxel_fp = voxel_m / h->scene.mean_free_path_m;
+    const float level0 = -ct_log2f(voxel_fp) - 1;
+    for (double &ms : h->net.ms) {
+        ms = 0;
+    }
+    auto run = [&]() -> int {
+        int rc = net_reserve(h, (size_t)h->scene.width * rows);
+        if (rc == CT_OK) {
+            rc = ensure_pyramid(h);
+        }
+        if (rc != CT_OK) {
+            return rc;
+        }
+        if (accumulate) {
+            discard_ahead(h);   // like ct_accumulate: the running mean leaves the order the samples rendered ahead were made for
+        }
+        for (uint32_t k = 0; k < count; k++) {
+            const uint32_t sid = first + k;
+            for (uint32_t y0 = 0; y0 < H; y0 += rows) {
+                rc = net_band(h, n, p, sid, y0, std::min(rows, H - y0), level0, voxel_m, accumulate);
+                if (rc != CT_OK) {
+                    return rc;
+                }
+            }
+            if (accumulate) {
+                if (h->stop_cadence && sid % h->stop_cadence == 0u && sid >= h->stop_min) {   // as ct_accumulate
+                    rc = enqueue_convergence_test(h, sid);
+                    if (rc != CT_OK) {
+                        return rc;
+                    }
+                    HIPCHK(h, hipStreamSynchronize(h->stream));
+                }
+                h->subframes = sid;
+                discard_ahead(h);
+            }
+        }
+        return CT_OK;
+    };
+    const int rc = run();
+    if (rc != CT_OK) {
+        hipStreamSynchronize(h->stream);
+    }
+    return rc;
+}
+
+extern "C" int ct_network_render_subframe(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t subframe_id, float *frame_rgba_dev)
+{
+    NEED_NOFLUSH(h);
+    // (arguments first: a rejected call leaves the handle exactly as it was, batches in flight included)
+    int rc = net_validate(h, n, p, "ct_network_render_subframe");
+    if (rc != CT_OK) {
+        return rc;
+    }
+    if (subframe_id == 0) {
+        return fail(h, CT_E_INVAL, "subframe ids are 1-based (Camera.cpp:191)");
+    }
+    if (!h->camera_set) {
+        return fail(h, CT_E_STATE, "ct_set_camera has not been called");
+    }
+    rc = flush(h);
+    if (rc != CT_OK) {
+        return rc;
+    }
+    rc = net_run(h, n, p, subframe_id, 1, false);
+    if (rc != CT_OK) {
+        return rc;
+    }
+    if (frame_rgba_dev) {
+        HIPCHK(h, hipMemcpyAsync(frame_rgba_dev, h->d_frame, (size_t)h->scene.width * h->scene.height * sizeof(float4),
+                                 hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return CT_OK;
+}
+
+extern "C" int ct_network_render_accumulate(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t first_subframe_id, uint32_t count)
+{
+    NEED_NOFLUSH(h);
+    int rc = net_validate(h, n, p, "ct_network_render_accumulate");
+    if (rc != CT_OK) {
+        return rc;
+    }
+    if (first_subframe_id == 0 || count == 0) {
+        return fail(h, CT_E_INVAL, "ct_network_render_accumulate: subframe ids are 1-based and count must not be 0");
+    }
+    if (!h->camera_set) {
+        return fail(h, CT_E_STATE, "ct_set_camera has not been called");
+    }
+    rc = flush(h);
+    if (rc != CT_OK) {
+        return rc;
+    }
+    if (first_subframe_id != h->subframes + 1) {
+        return fail(h, CT_E_STATE, "first_subframe_id %u but %u subframes are accumulated", first_subframe_id, h->subframes);
+    }
+    if (count > 0xffffffffu - first_subframe_id + 1u) {
+        return fail(h, CT_E_INVAL, "ct_network_render_accumulate: %u subframes from %u on exceed the 32-bit subframe id", count,
+                    first_subframe_id);
+    }
+    return net_run(h, n, p, first_subframe_id, count, true);
+}
+
+extern "C" int ct_debug_network_aux(CtHandle h, const float *directions_dev, uint32_t count, float *aux_dev_out)
+{
+    NEED(h);
+    if (count == 0) {
+        return CT_OK;
+    }
+    if (!directions_dev || !aux_dev_out) {
+        return fail(h, CT_E_INVAL, "ct_debug_network_aux: need directions and an output array");
+    }
+    HIPCHK(h, launch_network_aux(directions_dev, count, -h->dev.nlx, -h->dev.nly, -h->dev.nlz, aux_dev_out, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return CT_OK;
+}
+
+extern "C" int ct_debug_network_render_time(CtHandle h, double ms_out[4])
+{
+    NEED_NOFLUSH(h);
+    if (!ms_out) {
+        return fail(h, CT_E_INVAL, "ct_debug_network_render_time: ms_out is NULL");
+    }
+    for (int i = 0; i < 4; i++) {
+        ms_out[i] = h->net.ms[i];
+    }
+    return CT_OK;
 }
 
 extern "C" int ct_reset(CtHandle h)

@@ -209,6 +209,18 @@ hipError_t launch_scatter_samples(const DevScene &sc, uint32_t count, uint32_t b
 hipError_t launch_first_scatter_frame(const DevScene &sc, uint32_t x0, uint32_t y0, uint32_t w, uint32_t n, uint32_t subframe_id,
                                       float4 *found, uint32_t *wave_counts, uint32_t capacity, float *positions, float *directions,
                                       uint32_t *pixels, hipStream_t stream);
+// ct_network_render_*: aux[i] = dot(directions[i], l), left to right; and the pixels of a band of n pixels (whole rows) from the
+// flight's temporary, the scanned wave counts and the network's outputs of the band's records.  frame != NULL: the pixels are
+// stored there (the band's first pixel); frame == NULL: they go into the Welford update of mean / m2 (the band's first pixel)
+// with n = subframe_id, unless *frozen.
+struct NetCompose {
+    int32_t transform;   // CT_NET_OUT_*
+    float sr, sg, sb;    // rgb_scale
+};
+hipError_t launch_network_aux(const float *directions, uint32_t count, float lx, float ly, float lz, float *aux, hipStream_t stream);
+hipError_t launch_network_compose(const float4 *found, const uint32_t *wave_offsets, const float *out, uint32_t n, const NetCompose &c,
+                                  float4 *frame, float4 *mean, float4 *m2, uint32_t subframe_id, const uint32_t *frozen,
+                                  hipStream_t stream);
 // Density pyramid (Resources::generateMipmaps) and the descriptor gather.
 constexpr int kMaxMipLevels = 16;
 struct MipPyramid {

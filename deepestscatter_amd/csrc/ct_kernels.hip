@@ -3166,6 +3166,91 @@ hipError_t launch_first_scatter_frame(const DevScene &sc, uint32_t x0, uint32_t 
     return hipGetLastError();
 }
 
+// Declared here for network_compose_kernel; defined with the progressive accumulation below.
+CT_DEV void welford(float4 &mu, float4 &var, float4 nr, uint32_t subframe_id);
+
+// =============================================================================================
+// the network as a renderer (ct_network_render_*): the aux input of a band's records, and the band's pixels from the
+// network's outputs.
+// =============================================================================================
+// aux = dot(d2, light travel direction), left to right (the build has no contraction): what ct_debug_network_aux exposes.
+__global__ __launch_bounds__(256) void network_aux_kernel(const float *__restrict__ directions, uint32_t count, float lx, float ly,
+                                                          float lz, float *__restrict__ aux)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= count) {
+        return;
+    }
+    const size_t at = 3 * (size_t)i;
+    aux[i] = directions[at + 0] * lx + directions[at + 1] * ly + directions[at + 2] * lz;
+}
+
+hipError_t launch_network_aux(const float *directions, uint32_t count, float lx, float ly, float lz, float *aux, hipStream_t stream)
+{
+    if (count == 0u) {
+        return hipSuccess;
+    }
+    hipLaunchKernelGGL(network_aux_kernel, dim3((count + 255u) / 256u), dim3(256), 0, stream, directions, count, lx, ly, lz, aux);
+    return hipGetLastError();
+}
+
+// Lane i is pixel i of the band (whole rows, so also pixel i behind the band's first pixel in the frame).  Its record, if it has
+// one, is where first_scatter_compact_kernel put it: the wave's offset + the lane's rank among the wave's valid lanes, both
+// made again from the flight's temporary -- a gather, so neither a scatter by the pixel list nor an atomic.
+// ACCUMULATE: the pixel goes straight into the Welford update of mean and M2 (accumulate_batch_kernel's arithmetic, its frozen
+// test included); otherwise into the frame.
+template <bool ACCUMULATE>
+__global__ __launch_bounds__(256) void network_compose_kernel(const float4 *__restrict__ found, const uint32_t *__restrict__ wave_offsets,
+                                                              const float *__restrict__ out, uint32_t n, NetCompose c,
+                                                              float4 *__restrict__ frame, float4 *__restrict__ mean,
+                                                              float4 *__restrict__ m2, uint32_t subframe_id,
+                                                              const uint32_t *__restrict__ frozen)
+{
+    if (ACCUMULATE && frozen && *frozen != 0u) {
+        return;   // the image has converged (converged_freeze_kernel): the running mean stays as it is
+    }
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;   // (every lane reaches the ballot)
+    bool valid = false;
+    if (i < n) {
+        valid = found[i].w != 0.f;
+    }
+    const uint64_t mask = __builtin_amdgcn_ballot_w64(valid);
+    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+    if (i >= n) {
+        return;
+    }
+    float4 v = make_float4(0.f, 0.f, 0.f, 1.f);   // the miss value of ct_render_subframe
+    if (valid) {
+        const float o = out[(size_t)wave_offsets[i >> 6] + rank];
+        const float L = c.transform == 1 /* CT_NET_OUT_EXPM1 */ ? ct_expf(o) - 1.0f : o;
+        const float g = L > 0.f ? L : 0.f;   // (a NaN becomes 0)
+        v = make_float4(c.sr * g, c.sg * g, c.sb * g, 1.f);
+    }
+    if (ACCUMULATE) {
+        float4 mu = mean[i], var = m2[i];
+        welford(mu, var, v, subframe_id);
+        mean[i] = mu;
+        m2[i] = var;
+    } else {
+        frame[i] = v;
+    }
+}
+
+hipError_t launch_network_compose(const float4 *found, const uint32_t *wave_offsets, const float *out, uint32_t n, const NetCompose &c,
+                                  float4 *frame, float4 *mean, float4 *m2, uint32_t subframe_id, const uint32_t *frozen,
+                                  hipStream_t stream)
+{
+    const uint32_t blocks = (n + 255u) / 256u;
+    if (frame) {
+        hipLaunchKernelGGL(network_compose_kernel<false>, dim3(blocks), dim3(256), 0, stream, found, wave_offsets, out, n, c, frame,
+                           (float4 *)nullptr, (float4 *)nullptr, subframe_id, (const uint32_t *)nullptr);
+    } else {
+        hipLaunchKernelGGL(network_compose_kernel<true>, dim3(blocks), dim3(256), 0, stream, found, wave_offsets, out, n, c,
+                           (float4 *)nullptr, mean, m2, subframe_id, frozen);
+    }
+    return hipGetLastError();
+}
+
 // =============================================================================================
 // progressive accumulation (progressive.cu:17-27) of S consecutive subframes, in order.
 // Only this shard's pixels are touched; everything else stays exactly 0 so that a sum over

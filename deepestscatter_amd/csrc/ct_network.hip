@@ -539,6 +539,11 @@ int network_device(CtNetwork n)
     return n->device;
 }
 
+uint32_t network_aux_inputs(CtNetwork n)
+{
+    return n->geo.aux;
+}
+
 int network_eval(CtNetwork n, hipStream_t stream, const uint8_t *descriptors_dev, const float *aux_dev, uint32_t count,
                  float *out_dev, char *err, size_t err_len)
 {

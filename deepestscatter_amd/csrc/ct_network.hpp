@@ -15,6 +15,7 @@ int network_validate(const CtNetworkDesc *d, CtNetwork *out, char *err, size_t e
 // Packs the weights on the host (padded, permuted, bf16) and uploads them to `device`, which is the current one.
 int network_create(int device, const CtNetworkDesc *d, CtNetwork *out, char *err, size_t err_len);
 int network_device(CtNetwork n);
+uint32_t network_aux_inputs(CtNetwork n);   // A
 // One launch on `stream`, HIP events of the network around it, and a wait for the stream.
 int network_eval(CtNetwork n, hipStream_t stream, const uint8_t *descriptors_dev, const float *aux_dev, uint32_t count,
                  float *out_dev, char *err, size_t err_len);

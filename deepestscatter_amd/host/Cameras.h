@@ -7,6 +7,7 @@
 #include <cfloat>
 #include <filesystem>
 
+#include "NetworkFile.h"
 #include "Scene.h"
 
 namespace DeepestScatter
@@ -55,21 +56,71 @@ namespace DeepestScatter
         void render(float* frameResultBuffer) override                           // PathTracingRenderer.cpp:21-31
         {
             if (context->group) throw std::runtime_error("the two-launch loop (--unfused) renders on one GPU only");
-            if (camera.valid)
-            {
-                context->setCamera(camera.eye.data(), camera.U.data(), camera.V.data(), camera.W.data());
-                camera.valid = false;
-            }
+            applyCamera();
             Context::check(ct_render_subframe(context->handle, subframeId, frameResultBuffer), context->handle, "ct_render_subframe");
+        }
+
+        // The fused form of Camera::render's loop (Camera.cpp:189-200) for subframes first .. first + count - 1; `enqueue`: the
+        // batch need not be waited for.  A renderer with another source of frames overrides it.
+        virtual void renderAccumulate(uint32_t first, uint32_t count, bool enqueue)
+        {
+            applyCamera();
+            context->renderAccumulate(first, count, enqueue);
         }
 
         uint32_t subframeId = 0;        // context["subframeId"], set by Camera::render (Camera.cpp:191-192)
         int estimator = CT_EST_MARCH;   // CT_EST_DELTA: Woodcock tracking instead of the reference's fixed-step march
         inline static const std::string NAME = "PT";
 
-    private:
+    protected:
+        void applyCamera()              // the pose Camera::updatePosition left, published once
+        {
+            if (!camera.valid) return;
+            context->setCamera(camera.eye.data(), camera.U.data(), camera.V.data(), camera.W.data());
+            camera.valid = false;
+        }
+
         std::shared_ptr<Context> context;
         CameraProgram camera;
+    };
+
+    // The reference's neural renderers are ARenderers too: the same Camera loop, the frame made by the scattering network
+    // (ct_network_render_subframe / ct_network_render_accumulate) instead of the estimator.  It keeps the path tracer's scene
+    // set-up (init) and output name; the network lives on the context's handle and goes before it.
+    class NetworkRenderer : public PathTracingRenderer
+    {
+    public:
+        NetworkRenderer(std::shared_ptr<Context> context, std::shared_ptr<const NetworkFile> file, const CtNetworkRender& params)
+            : PathTracingRenderer(std::move(context)), file(std::move(file)), params(params) {}
+        ~NetworkRenderer() override { if (network) ct_network_destroy(network); }
+
+        void init() override
+        {
+            if (context->devices.size() > 1) throw std::runtime_error("--network renders on one GPU only (a sharded network frame is not implemented)");
+            PathTracingRenderer::init();
+            if (network) return;
+            CtNetworkDesc d{ CT_ABI_VERSION, file->blocks, file->width, file->aux, file->headLayers, file->weights.data(), file->weights.size() };
+            Context::check(ct_network_create(context->handle, &d, &network), context->handle, "ct_network_create");
+        }
+
+        void render(float* frameResultBuffer) override
+        {
+            applyCamera();
+            Context::check(ct_network_render_subframe(context->handle, network, &params, subframeId, frameResultBuffer), context->handle,
+                           "ct_network_render_subframe");
+        }
+
+        void renderAccumulate(uint32_t first, uint32_t count, bool /*enqueue: every band waits for its record count*/) override
+        {
+            applyCamera();
+            Context::check(ct_network_render_accumulate(context->handle, network, &params, first, count), context->handle,
+                           "ct_network_render_accumulate");
+        }
+
+    private:
+        std::shared_ptr<const NetworkFile> file;
+        CtNetworkRender params;
+        CtNetwork network = nullptr;
     };
 
     class Camera : public SceneItem                                              // Camera.h:16-103
@@ -199,13 +250,7 @@ namespace DeepestScatter
                 auto* pt = dynamic_cast<PathTracingRenderer*>(renderer.get());
                 if (fused && pt != nullptr)
                 {
-                    CameraProgram* camera = renderer->getCamera();
-                    if (camera->valid)
-                    {
-                        context->setCamera(camera->eye.data(), camera->U.data(), camera->V.data(), camera->W.data());
-                        camera->valid = false;
-                    }
-                    context->renderAccumulate(subframeId + 1, count, headless);
+                    pt->renderAccumulate(subframeId + 1, count, headless);        // (the estimator's fused batch, or the network's)
                     subframeId += count;
                     std::cout << "rendering subframe " << subframeId << std::endl;
                 }

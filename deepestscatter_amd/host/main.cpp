@@ -8,6 +8,8 @@
 //              [--size-m 7000] [--out DIR] [--data DIR] [--unfused] [--display] [--estimator march|delta] [--format exr|pfm]
 //              [--tex-fixed8]   filter weights in 1.8 fixed point like the reference's texture unit (CT_FLAG_TEX_FIXED8)
 //              [--gpus N | --gpus a,b,c]   one process, one shard of 8x8-pixel tiles per GPU, RCCL reduce of [mean | M2] (ct_group_*)
+//              [--network FILE [--net-transform linear|expm1] [--net-scale r,g,b]]   the job's subframes come from the scattering
+//                               network in FILE (NetworkFile.h; ct_network_render_accumulate) instead of the estimator
 //   <cloud> = file.vdb | procedural:<N>[:<seed>] | file.f32grid
 //
 //   cloudtrace collect <cloud>|@list.txt [--scene-id I] [--scenes N] [--jobs K] [--gpus ..] [--batch 2048] [--light L] [--size-m M] [--out DIR] [--data DIR] [--estimator ..] [--tex-fixed8]
@@ -62,6 +64,9 @@ namespace
         int estimator = CT_EST_MARCH;                                             // --estimator delta: Woodcock tracking (not the reference's sampler)
         bool texFixed8 = false;                                                   // --tex-fixed8: CT_FLAG_TEX_FIXED8, the reference's texture-unit weights
         std::vector<int32_t> devices;                                             // --gpus N | --gpus a,b,c: pixel-tile shards, RCCL frame reduce (ct_group_*)
+        std::string networkPath;                                                  // --network FILE: the scattering network renders instead of the estimator
+        std::shared_ptr<const NetworkFile> network;                               // ... read and checked before anything is created
+        CtNetworkRender networkRender{ CT_ABI_VERSION, CT_NET_OUT_LINEAR, { 1.f, 1.f, 1.f }, 0 };   // --net-transform, --net-scale
         bool collect = false;                                                     // `cloudtrace collect ...`
         int32_t sceneId = 0;
         uint32_t batch = 2048;                                                    // Tasks.cpp:137
@@ -259,7 +264,8 @@ namespace
             std::replace(stem.begin(), stem.end(), ':', '_');
             auto outputPath = std::filesystem::path(opt.outDir) / (stem + "." + toString(lightDirection) + "." + PathTracingRenderer::NAME + "." + opt.format);
             // installFramework + installApp: Sun, VDBCloud, CloudMaterial, Camera in this order (installers.cpp:28-38)
-            auto renderer = std::make_shared<PathTracingRenderer>(context);
+            std::shared_ptr<PathTracingRenderer> renderer = opt.network ? std::make_shared<NetworkRenderer>(context, opt.network, opt.networkRender)
+                                                                        : std::make_shared<PathTracingRenderer>(context);
             renderer->estimator = opt.estimator;
             auto sun = std::make_shared<Sun>(std::make_shared<DirectionalLight>(scene.light), context);
             auto cloud = std::make_shared<VDBCloud>(std::make_shared<Cloud::Model>(scene.cloud.model), context, resources);
@@ -281,7 +287,7 @@ int main(int argc, char* argv[])
     try
     {
         Options opt;
-        if (argc < 2) { std::cerr << "usage: cloudtrace <cloud> [--size WxH] [--spp N] [--mode total|multi|single] [--light L] [--size-m M] [--out DIR] [--data DIR] [--unfused] [--display] [--estimator march|delta] [--format exr|pfm] [--gpus N|a,b,c] [--tex-fixed8]\n"; return 2; }
+        if (argc < 2) { std::cerr << "usage: cloudtrace <cloud> [--size WxH] [--spp N] [--mode total|multi|single] [--light L] [--size-m M] [--out DIR] [--data DIR] [--unfused] [--display] [--estimator march|delta] [--format exr|pfm] [--gpus N|a,b,c] [--tex-fixed8] [--network FILE [--net-transform linear|expm1] [--net-scale r,g,b]]\n"; return 2; }
         int first = 2;
         bool lightsGiven = false;
         opt.cloud = argv[1];
@@ -318,6 +324,19 @@ int main(int argc, char* argv[])
                 if (opt.devices.empty()) throw std::invalid_argument("--gpus N | --gpus a,b,c");
             }
             else if (a == "--display") opt.display = true;
+            else if (a == "--network") opt.networkPath = next();
+            else if (a == "--net-transform")
+            {
+                const std::string t = next();
+                if (t == "linear") opt.networkRender.transform = CT_NET_OUT_LINEAR;
+                else if (t == "expm1") opt.networkRender.transform = CT_NET_OUT_EXPM1;
+                else throw std::invalid_argument("--net-transform linear|expm1");
+            }
+            else if (a == "--net-scale")
+            {
+                float* s = opt.networkRender.rgb_scale;
+                if (std::sscanf(next().c_str(), "%f,%f,%f", &s[0], &s[1], &s[2]) != 3) throw std::invalid_argument("--net-scale r,g,b");
+            }
             else if (a == "--tex-fixed8") opt.texFixed8 = true;
             else if (a == "--estimator")
             {
@@ -347,6 +366,14 @@ int main(int argc, char* argv[])
         }
 
         if (opt.collect) return collectScenes(opt);
+
+        if (!opt.networkPath.empty())
+        {
+            // read and checked against the header's formula here, before a renderer exists: a malformed file costs no device
+            if (opt.devices.size() > 1) throw std::invalid_argument("--network renders on one GPU only");
+            opt.network = std::make_shared<const NetworkFile>(NetworkFile::load(opt.networkPath));
+            if (opt.network->aux != 1) throw std::invalid_argument("--network: the renderer feeds one aux input (the light angle); this network has " + std::to_string(opt.network->aux));
+        }
 
         std::queue<LazyTask> tasks;                                               // Tasks::renderCloud, Tasks.cpp:104-112
         auto context = std::make_shared<Context>();

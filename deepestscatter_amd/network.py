@@ -7,6 +7,8 @@ residual MLP of the paper the reference implements (Kallweit et al. 2017), param
     pack_weights        its parameters as the flat float32 array of CtNetworkDesc.weights_host
     reference_forward   numpy, with the rounding points of the definition: what the device is held to
     Network             a CtNetwork on a CloudTracer's device
+    render_values       numpy restatement of what ct_network_render_* makes of the outputs (transform, clamp, rgb scale)
+    save_weights / load_weights   the weight file `cloudtrace --network` reads
 
 State-dict names (the mapping an exported model needs): blocks.k.fc1 = W1_k, c1_k; blocks.k.fc2 = W2_k, c2_k (k = 0 .. 9);
 head.i = V_i, d_i (i = 0 .. H - 2); out = v, d.
@@ -173,6 +175,78 @@ def reference_forward(weights, desc: NetworkShape, descriptors_u8, aux, accumula
         z = rnd(np.maximum(linear(z, matrix(W), c), 0))
     W, c = layers[-1]
     return linear(z, matrix(W), c)[:, 0]
+
+
+def render_values(out, transform="linear", rgb_scale=(1.0, 1.0, 1.0), expf=None) -> np.ndarray:
+    """The pixel values ct_network_render_* makes of network outputs, restated in numpy float32: L = out ("linear") or
+    expf(out) - 1 ("expm1"), g = L if L > 0 else 0 (so a NaN gives 0), pixel = (rgb_scale * g, 1) -> float32 [n, 4].
+    `expf`: a float -> float function standing for the library's ct_expf (include/ct_fmath.h); "expm1" needs one (np.exp is
+    not bit-identical to it)."""
+    o = np.ascontiguousarray(out, np.float32).reshape(-1)
+    if transform in ("linear", 0):
+        L = o
+    elif transform in ("expm1", 1):
+        if expf is None:
+            raise ValueError("render_values: the expm1 transform needs an expf function")
+        L = np.array([np.float32(expf(float(v))) for v in o], np.float32) - np.float32(1.0)
+    else:
+        raise ValueError(f"render_values: unknown transform {transform!r} (linear | expm1)")
+    with np.errstate(invalid="ignore"):
+        g = np.where(L > 0, L, np.float32(0)).astype(np.float32)
+    s = np.asarray(rgb_scale, np.float32).reshape(3)
+    px = np.empty((o.size, 4), np.float32)
+    px[:, :3] = s[None, :] * g[:, None]
+    px[:, 3] = 1.0
+    return px
+
+
+# The weight file: a 32-byte little-endian header -- magic "CTNW", u32 version, blocks, width, aux, head_layers, u64 weight
+# count -- and then weight_count float32 values in the order of CtNetworkDesc.weights_host.
+WEIGHT_MAGIC = b"CTNW"
+WEIGHT_VERSION = 1
+_WEIGHT_HEADER = "<4sIIIIIQ"
+
+
+def save_weights(path, module_or_weights, shape: NetworkShape | None = None):
+    """Writes a ScatterNet, or a flat weight array with its `shape`, as a weight file (read by load_weights and by
+    `cloudtrace --network`)."""
+    import struct
+    if hasattr(module_or_weights, "blocks"):
+        shape = module_or_weights.shape
+        weights = pack_weights(module_or_weights)
+    else:
+        if shape is None:
+            raise ValueError("save_weights: a flat weight array needs its NetworkShape")
+        weights = np.ascontiguousarray(module_or_weights, np.float32).reshape(-1)
+    if weights.size != shape.weight_count():
+        raise ValueError(f"{weights.size} weights, the shapes imply {shape.weight_count()}")
+    with open(path, "wb") as f:
+        f.write(struct.pack(_WEIGHT_HEADER, WEIGHT_MAGIC, WEIGHT_VERSION, BLOCKS, shape.width, shape.aux, shape.head_layers, weights.size))
+        f.write(weights.astype("<f4").tobytes())
+
+
+def load_weights(path):
+    """-> (flat float32 weights, NetworkShape).  ValueError for a file that is malformed: a wrong magic or version, a count
+    that is not what the shapes imply, or fewer bytes than the header announces."""
+    import struct
+    with open(path, "rb") as f:
+        data = f.read()
+    n_head = struct.calcsize(_WEIGHT_HEADER)
+    if len(data) < n_head:
+        raise ValueError(f"{path}: shorter than the {n_head}-byte header of a weight file")
+    magic, version, blocks, width, aux, head, count = struct.unpack(_WEIGHT_HEADER, data[:n_head])
+    if magic != WEIGHT_MAGIC:
+        raise ValueError(f"{path}: not a weight file (magic {magic!r})")
+    if version != WEIGHT_VERSION:
+        raise ValueError(f"{path}: weight file version {version}, this reader knows {WEIGHT_VERSION}")
+    if blocks != BLOCKS or width < 16 or width > 256 or width % 8 or aux > 8 or not 1 <= head <= 4:
+        raise ValueError(f"{path}: shapes out of range (blocks {blocks}, width {width}, aux {aux}, head layers {head})")
+    shape = NetworkShape(width, aux, head)
+    if count != shape.weight_count():
+        raise ValueError(f"{path}: {count} weights, the shapes imply {shape.weight_count()}")
+    if len(data) - n_head != 4 * count:
+        raise ValueError(f"{path}: {len(data) - n_head} bytes of weights, {count} weights need {4 * count}")
+    return np.frombuffer(data, "<f4", count, n_head).astype(np.float32), shape
 
 
 class Network:

@@ -475,6 +475,80 @@ CT_API int ct_debug_network_time(CtNetwork n, double *ms_out);
  * routine ct_network_create packs with. */
 CT_API float ct_debug_bf16_round(float x);
 
+/* ---- the scattering network as a renderer ---------------------------------------------------
+ *
+ * The reference's neural renderers are ARenderers: render(frameResultBuffer) fills the frame and Camera::render runs the same
+ * Welford accumulation, tonemap and convergence test as for the path tracer (Camera.cpp:189-214).  These two entry points are
+ * that for a CtNetwork with ONE aux input: ct_descriptor_frame, the aux input, ct_network_eval and the frame, for whole frames
+ * of any size ct_create accepts, without leaving the device.
+ *
+ * Definition, per pixel (x, y) of the whole frame and subframe s:
+ *   - the record is ct_descriptor_frame's for that pixel and subframe: the same flight, position, direction d2 and descriptor
+ *     bytes; CT_FLAG_TEX_FIXED8 applies as it does there, the handle's estimator and mode do not matter;
+ *   - aux = d2.x * l.x + d2.y * l.y + d2.z * l.z with l = the handle's twice-normalised light travel direction (ct_set_light),
+ *     evaluated left to right in float32 without contraction;
+ *   - out = ct_network_eval's value for that record;
+ *   - L = out (CT_NET_OUT_LINEAR) or ct_expf(out) - 1.0f (CT_NET_OUT_EXPM1, include/ct_fmath.h); g = L > 0 ? L : 0, so a NaN
+ *     becomes 0;
+ *   - the pixel is (rgb_scale[0] * g, rgb_scale[1] * g, rgb_scale[2] * g, 1);
+ *   - a pixel without a record is (0, 0, 0, 1), the miss value of ct_render_subframe.
+ *
+ * Bands.  The frame is cut into bands of whole rows of at most band_pixels pixels (at least one row, at most 2^20 pixels; 0 =
+ * 2^20), taken bottom to top; each band is one pass through the first flights and their compaction, the 4-byte read of the
+ * record count, the descriptor gather, the aux kernel, the network and one kernel that forms the pixels.  That kernel ranks a
+ * pixel among its wave's valid lanes from the flight's per-pixel temporary and the scanned wave counts and reads its record's
+ * output there: no scatter, no atomics, the same call gives the same bits.  Records are per pixel and a record's output does
+ * not depend on its place in a batch, so the image does not depend on band_pixels.  A band without a record skips the gather,
+ * the aux kernel and the network.
+ *
+ * Scratch.  The temporaries belong to the handle: allocated on first use, grown when a call needs more, never freed between
+ * calls, freed by ct_destroy; a warm call allocates nothing.  The per-pixel temporary, positions, directions, aux and out are
+ * sized for the band and allocated, with a first piece of the descriptor array, before the call's first kernel: CT_E_NOMEM can
+ * only be answered there, and then frame, mean, M2 and the subframe count are exactly as they were and the handle is usable.
+ * The descriptor array (2250 bytes per record: 2^20 records would be 2.4 GB, which is why the count is read first and why
+ * band_pixels exists) is sized for the largest record count seen so far and grown between bands, with the stream idle; if
+ * the device refuses that growth the band's records go through the gather and the network in pieces of the size it has -- the
+ * same bits, since records are independent -- and the call succeeds.
+ *
+ * CT_E_INVAL: a NULL handle (answered without a device), network or params; a wrong abi_version; an unknown transform; an
+ * rgb_scale that is not finite; a network with aux != 1; a network on another device than h; a handle created with
+ * shard_count > 1 (a sharded frame is out of scope here: ct_descriptor_frame ignores shards, and splitting a frame by rects
+ * over a CtGroup is a later change); subframe_id == 0; count == 0.  CT_E_STATE: no camera pose (ct_create sets the default
+ * one, so a live handle always has one); ct_network_render_accumulate with first_subframe_id != subframes + 1, as
+ * ct_render_accumulate.  Arguments are checked before anything of the handle changes.
+ * Both wait for the batches in flight, run on the handle's stream and return when it is idle. */
+enum { CT_NET_OUT_LINEAR = 0, CT_NET_OUT_EXPM1 = 1 };
+typedef struct CtNetworkRender {
+    uint32_t abi_version;   /* must be CT_ABI_VERSION */
+    int32_t  transform;     /* CT_NET_OUT_LINEAR: L = out; CT_NET_OUT_EXPM1: L = ct_expf(out) - 1.0f */
+    float    rgb_scale[3];  /* finite */
+    uint32_t band_pixels;   /* largest number of pixels handled at once; 0 = 2^20.  Bands are whole rows, at least one row,
+                               at most 2^20 pixels */
+} CtNetworkRender;
+
+/* ARenderer::render(frameResultBuffer) of the network: the frame defined above into the handle's CT_BUF_FRAME and, when
+ * frame_rgba_dev != NULL, into that device buffer too (W*H*4 floats, caller-owned), exactly as ct_render_subframe.  Touches
+ * nothing else: not the mean, M2, the subframe count, CtCounters, CtFetchCounters, the samples rendered ahead or the pose's
+ * pixel list. */
+CT_API int ct_network_render_subframe(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t subframe_id, float *frame_rgba_dev);
+
+/* for id = first .. first + count - 1 { ct_network_render_subframe(id); ct_accumulate(id, NULL) } fused: mean, M2, the subframe
+ * count, the frozen state and ct_converged_at are left bit for bit as that loop leaves them (ct_set_stop_when_converged is
+ * honoured the way ct_accumulate honours it: the test follows every cadence-th subframe from min_subframes on), but the
+ * float4 frame is not materialised -- the kernel that forms a band's pixels applies the Welford update to mean and M2
+ * directly -- and CT_BUF_FRAME is left alone.  Like ct_accumulate it drops the samples rendered ahead. */
+CT_API int ct_network_render_accumulate(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t first_subframe_id, uint32_t count);
+
+/* Diagnostic: the aux kernel of the two entry points above on caller-supplied directions: aux_dev_out[i] = d.x * l.x + d.y * l.y +
+ * d.z * l.z for d = directions_dev[3 i .. 3 i + 2] and the handle's light.  count == 0: CT_OK, nothing read or written.
+ * CT_E_INVAL: a NULL handle, or a NULL array with count > 0. */
+CT_API int ct_debug_network_aux(CtHandle h, const float *directions_dev, uint32_t count, float *aux_dev_out);
+
+/* Diagnostic: milliseconds the GPU spent in the last ct_network_render_subframe / ct_network_render_accumulate of this handle
+ * (HIP events on its stream), summed over its bands and subframes: ms_out[0] first flights with their compaction, [1] the
+ * descriptor gather, [2] the network, [3] the aux kernel and the kernel that forms the pixels (and accumulates them). */
+CT_API int ct_debug_network_render_time(CtHandle h, double ms_out[4]);
+
 /* ---- data access -------------------------------------------------------------------- */
 
 /* BufferBind<T>(buffer) map/copy, src/Util/BufferBind.h:11-74 (e.g. Camera.cpp:161,239-240).

@@ -1,0 +1,82 @@
+#!/usr/bin/env python3
+"""What rendering with the scattering network costs and where the time goes: the flagship scene (the 512^3 procedural cloud,
+1024 x 1024, default pose) and a seeded random ScatterNet(200, 1, 3), warm calls, medians.
+  line 1  the four stage times of one ct_network_render_subframe (ct_debug_network_render_time: HIP events, summed over the
+          bands) and its wall time;
+  line 2  the wall time of ct_network_render_accumulate over 16 subframes against the unfused loop
+          ct_network_render_subframe + ct_accumulate;
+  line 3  the Python route of the same tree, CloudTracer.network_frame (descriptor_frame with its allocations, aux and the
+          scatter as torch ops), per subframe.
+Needs a GPU.  Prints three JSON lines.
+    python tools/network_render_time.py [--repeats 5] [--volume 512] [--size 1024] [--subframes 16] [--band 0]"""
+import argparse, json, statistics, sys, time
+from pathlib import Path
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+
+
+def wall_ms(fn):
+    t = time.perf_counter()
+    fn()
+    return (time.perf_counter() - t) * 1e3
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--volume", type=int, default=512)
+    ap.add_argument("--size", type=int, default=1024)
+    ap.add_argument("--subframes", type=int, default=16)
+    ap.add_argument("--band", type=int, default=0)
+    a = ap.parse_args()
+    import torch
+    import deepestscatter_amd as ds
+    from deepestscatter_amd import network as N
+    tr = ds.CloudTracer(ds.make_procedural_cloud(a.volume), width=a.size, height=a.size)
+    torch.manual_seed(1)
+    net = N.Network(tr, N.ScatterNet(200, 1, 3))
+    common = {"network": [200, 1, 3], "volume": a.volume, "frame": [a.size, a.size], "band_pixels": a.band, "repeats": a.repeats}
+    med = statistics.median
+
+    # one subframe: stages and wall time (the first call allocates the scratch and builds the pyramid: warm-up)
+    stages, wall = [], []
+    for i in range(a.repeats + 1):
+        wall.append(wall_ms(lambda: tr.network_render_subframe(net, 1, band_pixels=a.band, out=False)))
+        stages.append(tr.network_render_time())
+    records = int(tr.descriptor_frame(1)[3].shape[0])
+    names = ["flights_and_compaction_ms", "gather_ms", "network_ms", "aux_and_compose_ms"]
+    line = {"route": "ct_network_render_subframe", **common, "records": records, "wall_ms": med(wall[1:])}
+    line.update({n: med([s[k] for s in stages[1:]]) for k, n in enumerate(names)})
+    print(json.dumps(line), flush=True)
+
+    # S subframes: fused against the unfused loop
+    S = a.subframes
+
+    def unfused():
+        for sid in range(1, S + 1):
+            tr.network_render_subframe(net, sid, band_pixels=a.band, out=False)
+            tr.accumulate(sid)
+
+    fused_ms, loop_ms = [], []
+    for i in range(a.repeats + 1):
+        tr.reset()
+        fused_ms.append(wall_ms(lambda: tr.network_render_accumulate(net, 1, S, band_pixels=a.band)))
+        tr.reset()
+        loop_ms.append(wall_ms(unfused))
+    print(json.dumps({"route": "ct_network_render_accumulate", **common, "subframes": S, "fused_wall_ms": med(fused_ms[1:]),
+                      "unfused_loop_wall_ms": med(loop_ms[1:]), "fused_ms_per_subframe": med(fused_ms[1:]) / S,
+                      "unfused_ms_per_subframe": med(loop_ms[1:]) / S}), flush=True)
+
+    # the Python route: one float per pixel of one rect of at most 2^20 pixels
+    py_ms = []
+    if a.size * a.size <= 1 << 20:
+        for i in range(a.repeats + 1):
+            def route():
+                tr.network_frame(net, 1)
+                torch.cuda.synchronize()
+            py_ms.append(wall_ms(route))
+    print(json.dumps({"route": "CloudTracer.network_frame", **common, "records": records,
+                      "wall_ms": med(py_ms[1:]) if py_ms else None,
+                      "note": None if py_ms else "the frame exceeds the 2^20 pixels of one descriptor_frame rect"}), flush=True)
+    net.close()
+    tr.close()

@@ -21,7 +21,8 @@ CT_FLAG_NONE, CT_FLAG_SIMPLE_KERNEL, CT_FLAG_LIGHT_NORMALIZED, CT_FLAG_SPARSE_BR
 (CT_LAYOUT_DENSITY_BRICKS, CT_LAYOUT_SHADOW_BRICKS, CT_LAYOUT_MARCH_BRICKS, CT_LAYOUT_MARCH_ROWS, CT_LAYOUT_MARCH_COARSE,
  CT_LAYOUT_TWIN_BRICKS, CT_LAYOUT_MAJORANT_CELLS, CT_LAYOUT_MAJORANT_CODES, CT_LAYOUT_MIP_PYRAMID) = range(9)   # ct_debug_layout
 CT_FLAG_TEX_FIXED8 = 16   # filter weights in 1.8 fixed point, like the reference's texture unit (include/cloudtrace.h)
-CT_NET_OUT_LINEAR, CT_NET_OUT_EXPM1 = 0, 1   # CtNetworkRender.transform
+CT_NET_OUT_LINEAR, CT_NET_OUT_EXPM1 = 0, 1   # CtNetworkRender.transform, low byte
+CT_NET_ADD_SINGLE_SCATTER = 0x100            # CtNetworkRender.transform, bit 8: add the sun's single-scatter term
 
 # every symbol include/cloudtrace.h declares (tests check the library exports all of them)
 EXPORTS = [

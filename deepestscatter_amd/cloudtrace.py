@@ -338,26 +338,29 @@ class CloudTracer:
         return image.reshape(y1 - y0, x1 - x0), count
 
     @staticmethod
-    def _network_render_params(transform, rgb_scale, band_pixels) -> "_lib.CtNetworkRender":
+    def _network_render_params(transform, rgb_scale, band_pixels, direct: bool = False) -> "_lib.CtNetworkRender":
         names = {"linear": _lib.CT_NET_OUT_LINEAR, "expm1": _lib.CT_NET_OUT_EXPM1}
         t = names.get(transform, transform) if isinstance(transform, str) else transform
         if isinstance(t, str):
             raise _lib.CloudTraceError(_lib.CT_E_INVAL, f"network render: unknown transform {transform!r} (linear | expm1)")
         p = _lib.CtNetworkRender()
         p.abi_version = _lib.CT_ABI_VERSION
-        p.transform = int(t)
+        p.transform = int(t) | (_lib.CT_NET_ADD_SINGLE_SCATTER if direct else 0)   # (an integer passes through as it is)
         p.rgb_scale[:] = [float(v) for v in rgb_scale]
         p.band_pixels = int(band_pixels)
         return p
 
     def network_render_subframe(self, net, subframe_id: int, transform="linear", rgb_scale=(1.0, 1.0, 1.0), band_pixels: int = 0,
-                                out=None):
+                                out=None, direct: bool = False):
         """ct_network_render_subframe: the network's frame of one subframe -- per pixel with a first-scatter record
         rgb_scale * max(L, 0) with L = out ("linear") or expf(out) - 1 ("expm1"), alpha 1; (0, 0, 0, 1) elsewhere -- into the
         handle's CT_BUF_FRAME and into a float32 torch tensor [H, W, 4] on the handle's device, which is returned (`out`: a
         tensor of that shape to write into; False: CT_BUF_FRAME only, returns None).  `net`: a deepestscatter_amd.network.Network
-        of this tracer with one aux input.  band_pixels: pixels handled at once (0 = 2^20); the image does not depend on it."""
-        p = self._network_render_params(transform, rgb_scale, band_pixels)
+        of this tracer with one aux input.  band_pixels: pixels handled at once (0 = 2^20); the image does not depend on it.
+        direct=True (CT_NET_ADD_SINGLE_SCATTER): a pixel with a record also gets the sun's single-scatter term of that pixel and
+        subframe -- what a CT_MODE_SUN_SINGLE_SCATTER tracer renders there -- added behind the scaled network output, so that a
+        network trained on the multiple-scatter labels gives the path tracer's picture."""
+        p = self._network_render_params(transform, rgb_scale, band_pixels, direct)
         ptr = None
         if out is not False:
             import torch
@@ -372,10 +375,10 @@ class CloudTracer:
         return None if out is False else out
 
     def network_render_accumulate(self, net, first_subframe_id: int, count: int, transform="linear", rgb_scale=(1.0, 1.0, 1.0),
-                                  band_pixels: int = 0):
+                                  band_pixels: int = 0, direct: bool = False):
         """ct_network_render_accumulate: network_render_subframe(id) + accumulate(id) for id = first .. first + count - 1, fused
-        (no frame is materialised); mean, M2 and the subframe count end exactly as that loop leaves them."""
-        p = self._network_render_params(transform, rgb_scale, band_pixels)
+        (no frame is materialised); mean, M2 and the subframe count end exactly as that loop leaves them.  direct: as there."""
+        p = self._network_render_params(transform, rgb_scale, band_pixels, direct)
         check(self.L.ct_network_render_accumulate(self.h, net.n, C.byref(p), first_subframe_id & 0xFFFFFFFF, count), self.h)
 
     def network_aux(self, directions):

@@ -247,13 +247,14 @@ struct CtHandle_ {
     double dframe_scatter_ms = 0, dframe_gather_ms = 0;   // the last ct_descriptor_frame (ct_debug_descriptor_frame_time)
     // ct_network_render_*: the temporaries of a band stay with the handle (a frame is many bands, a render many frames).
     // found / waves / pos / dir / aux / out hold a band of band_cap pixels; desc holds desc_cap records, the largest count
-    // seen so far (or what the device gave: a band with more records goes through gather and network in pieces).
+    // seen so far (or what the device gave: a band with more records goes through gather and network in pieces).  direct holds
+    // a band of direct_cap pixels and exists from the first call with CT_NET_ADD_SINGLE_SCATTER on.
     struct NetScratch {
-        float4 *found = nullptr;
+        float4 *found = nullptr, *direct = nullptr;
         uint32_t *waves = nullptr;
         float *pos = nullptr, *dir = nullptr, *aux = nullptr, *out = nullptr;
         uint8_t *desc = nullptr;
-        size_t band_cap = 0, desc_cap = 0;
+        size_t band_cap = 0, desc_cap = 0, direct_cap = 0;
         double ms[4] = { 0, 0, 0, 0 };   // the last call (ct_debug_network_render_time)
     } net;
     uint64_t launches = 0;
@@ -514,7 +515,7 @@ static void release(CtHandle h)
     void *ptrs[] = { h->d_density, h->d_inscatter, h->d_dbricks, h->d_ibricks, h->d_mbricks, h->d_tbricks, h->d_touched[0], h->d_touched[1], h->d_mrows, h->d_mcoarse, h->d_pyramid, h->d_mie, h->d_chopped, h->d_cdf,
                      h->d_guide, h->d_dist, h->d_dist_tmp, h->d_majorant, h->d_maj_cells, h->d_maj_codes, h->d_frame, h->d_mean, h->d_m2, h->d_screen, h->d_frames_all, h->cont[0], h->cont[1], h->left[0], h->left[1], h->d_cont_count, h->d_cont_total, h->d_primary, h->d_advance, h->d_pixels, h->d_cost, h->d_group_rank, h->d_group_order, h->d_job_group, h->d_job_sub, h->d_queue,
                      h->d_counters, h->d_colsum, h->d_avg, h->d_freeze, h->d_hit, h->d_cost_plane, h->d_timeline, h->pt.tasks, h->pt.primary, h->pt.frames, h->pt.pixels, h->pt.jg, h->pt.js,
-                     h->net.found, h->net.waves, h->net.pos, h->net.dir, h->net.aux, h->net.out, h->net.desc };
+                     h->net.found, h->net.waves, h->net.pos, h->net.dir, h->net.aux, h->net.out, h->net.desc, h->net.direct };
     for (void *p : ptrs) {
         if (p) {
             hipFree(p);
@@ -3157,7 +3158,7 @@ extern "C" int ct_descriptor_frame(CtHandle h, uint32_t subframe_id, const uint3
         }
         float *pos = positions_dev ? positions_dev : d_pos.p, *dir = directions_dev ? directions_dev : d_dir.p;
         HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-        HIPCHK(h, launch_first_scatter_frame(h->dev, x0, y0, rw, n, subframe_id, d_found, d_waves, capacity, pos, dir, pixels_dev,
+        HIPCHK(h, launch_first_scatter_frame(h->dev, x0, y0, rw, n, subframe_id, d_found, d_waves, capacity, pos, dir, pixels_dev, nullptr,
                                              h->stream));
         HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
         uint32_t count = 0;
@@ -3243,8 +3244,10 @@ static int net_validate(CtHandle h, CtNetwork n, const CtNetworkRender *p, const
     if (p->abi_version != CT_ABI_VERSION) {
         return fail(h, CT_E_INVAL, "%s: abi_version %u, this library is %u", who, p->abi_version, CT_ABI_VERSION);
     }
-    if (p->transform != CT_NET_OUT_LINEAR && p->transform != CT_NET_OUT_EXPM1) {
-        return fail(h, CT_E_INVAL, "%s: unknown output transform %d", who, p->transform);
+    const int32_t out_transform = p->transform & ~CT_NET_ADD_SINGLE_SCATTER;
+    if (out_transform != CT_NET_OUT_LINEAR && out_transform != CT_NET_OUT_EXPM1) {
+        return fail(h, CT_E_INVAL, "%s: unknown output transform %d (CT_NET_OUT_LINEAR or CT_NET_OUT_EXPM1, with or without "
+                                   "CT_NET_ADD_SINGLE_SCATTER)", who, p->transform);
     }
     if (!std::isfinite(p->rgb_scale[0]) || !std::isfinite(p->rgb_scale[1]) || !std::isfinite(p->rgb_scale[2])) {
         return fail(h, CT_E_INVAL, "%s: rgb_scale is not finite", who);
@@ -3277,11 +3280,20 @@ static size_t net_descriptor_limit(CtHandle h)
 }
 
 // Everything a call needs before its first kernel: the band-sized temporaries and a first piece of the descriptor array.  The
-// stream is idle.  A failed growth leaves what the handle had.
-static int net_reserve(CtHandle h, size_t band_pixels)
+// stream is idle.  A failed growth leaves what the handle had.  direct: the call carries CT_NET_ADD_SINGLE_SCATTER.
+static int net_reserve(CtHandle h, size_t band_pixels, bool direct)
 {
     CtHandle_::NetScratch &s = h->net;
     const size_t n_pad = (band_pixels + 255u) / 256u * 256u;
+    if (direct && n_pad > s.direct_cap) {
+        DevTemp<float4> sun;
+        HIPCHK(h, dmalloc(&sun, n_pad));
+        if (s.direct) {
+            hipFree(s.direct);
+        }
+        s.direct = sun.release();
+        s.direct_cap = n_pad;
+    }
     if (n_pad > s.band_cap) {
         DevTemp<float4> found;
         DevTemp<uint32_t> waves;
@@ -3340,9 +3352,11 @@ static int net_band(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t 
 {
     CtHandle_::NetScratch &s = h->net;
     const uint32_t W = h->scene.width, npx = W * rows, n_pad = (npx + 255u) / 256u * 256u;
+    float4 *const direct = (p->transform & CT_NET_ADD_SINGLE_SCATTER) ? s.direct : nullptr;
     float ms = 0;
     HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-    HIPCHK(h, launch_first_scatter_frame(h->dev, 0u, y0, W, npx, sid, s.found, s.waves, npx, s.pos, s.dir, nullptr, h->stream));
+    HIPCHK(h, launch_first_scatter_frame(h->dev, 0u, y0, W, npx, sid, s.found, s.waves, npx, s.pos, s.dir, nullptr, direct,
+                                         h->stream));
     HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
     uint32_t count = 0;
     HIPCHK(h, hipMemcpyAsync(&count, s.waves + n_pad / 64u, sizeof count, hipMemcpyDeviceToHost, h->stream));
@@ -3378,12 +3392,12 @@ static int net_band(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t 
             at += piece;
         }
     }
-    const NetCompose c{ p->transform, p->rgb_scale[0], p->rgb_scale[1], p->rgb_scale[2] };
+    const NetCompose c{ p->transform & 0xff, p->rgb_scale[0], p->rgb_scale[1], p->rgb_scale[2] };
     const size_t first_pixel = (size_t)y0 * W;
     HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
     HIPCHK(h, launch_network_compose(s.found, s.waves, s.out, npx, c, accumulate ? nullptr : h->d_frame + first_pixel,
                                      h->d_mean + first_pixel, h->d_m2 + first_pixel, sid, h->stop_cadence ? h->d_freeze : nullptr,
-                                     h->stream));
+                                     direct, h->stream));
     HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
     HIPCHK(h, hipEventSynchronize(h->ev[1]));
     HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
@@ -3407,7 +3421,7 @@ static int net_run(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t f
         ms = 0;
     }
     auto run = [&]() -> int {
-        int rc = net_reserve(h, (size_t)h->scene.width * rows);
+        int rc = net_reserve(h, (size_t)h->scene.width * rows, (p->transform & CT_NET_ADD_SINGLE_SCATTER) != 0);
         if (rc == CT_OK) {
             rc = ensure_pyramid(h);
         }

@@ -205,22 +205,23 @@ hipError_t launch_scatter_samples(const DevScene &sc, uint32_t count, uint32_t b
 // ct_descriptor_frame: first flight of the n pixels of the rect (x0, y0, row length w), a scan of the per-wave counts and the
 // compacting write, three dispatches.  found: (n rounded up to 256) float4; wave_counts: (n rounded up to 256) / 64 + 1 words,
 // afterwards the waves' offsets and, in the last word, the number of records; positions / directions hold `capacity` records,
-// pixels may be NULL.
+// pixels may be NULL.  direct != NULL ((n rounded up to 256) float4): the flight also stores, by rect pixel, the single-scatter
+// term of its collision (CT_NET_ADD_SINGLE_SCATTER), zeros where the pixel has no record.
 hipError_t launch_first_scatter_frame(const DevScene &sc, uint32_t x0, uint32_t y0, uint32_t w, uint32_t n, uint32_t subframe_id,
                                       float4 *found, uint32_t *wave_counts, uint32_t capacity, float *positions, float *directions,
-                                      uint32_t *pixels, hipStream_t stream);
+                                      uint32_t *pixels, float4 *direct, hipStream_t stream);
 // ct_network_render_*: aux[i] = dot(directions[i], l), left to right; and the pixels of a band of n pixels (whole rows) from the
 // flight's temporary, the scanned wave counts and the network's outputs of the band's records.  frame != NULL: the pixels are
 // stored there (the band's first pixel); frame == NULL: they go into the Welford update of mean / m2 (the band's first pixel)
-// with n = subframe_id, unless *frozen.
+// with n = subframe_id, unless *frozen.  direct != NULL: the flight's single-scatter temporary, added to the pixels with a record.
 struct NetCompose {
-    int32_t transform;   // CT_NET_OUT_*
+    int32_t transform;   // CT_NET_OUT_* (the low byte of CtNetworkRender::transform)
     float sr, sg, sb;    // rgb_scale
 };
 hipError_t launch_network_aux(const float *directions, uint32_t count, float lx, float ly, float lz, float *aux, hipStream_t stream);
 hipError_t launch_network_compose(const float4 *found, const uint32_t *wave_offsets, const float *out, uint32_t n, const NetCompose &c,
                                   float4 *frame, float4 *mean, float4 *m2, uint32_t subframe_id, const uint32_t *frozen,
-                                  hipStream_t stream);
+                                  const float4 *direct, hipStream_t stream);
 // Density pyramid (Resources::generateMipmaps) and the descriptor gather.
 constexpr int kMaxMipLevels = 16;
 struct MipPyramid {

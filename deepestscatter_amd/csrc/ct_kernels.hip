@@ -3037,6 +3037,10 @@ hipError_t launch_scatter_samples(const DevScene &sc, uint32_t count, uint32_t b
 // counts in one block (a rect has at most 2^20 pixels = 16384 waves), the total behind them.  (3) first_scatter_compact_kernel
 // reads the temporary, ranks the wave's valid lanes again (ballot + mbcnt: cheap) and stores position, direction and pixel index at
 // wave offset + rank.  No atomics: record k is the k-th valid pixel of the rect, whatever the order the waves ran in.
+// DIRECT (ct_network_render_* with CT_NET_ADD_SINGLE_SCATTER): a valid lane also evaluates the NEE of its collision with the
+// un-chopped Mie table -- singleScatterSunRadiance's value for this pixel and subframe, render_simple_kernel's mode 2 -- at the
+// flight's own end position (texture space: the world position of the record plus the half box does not round back to it) and
+// keeps it in a second temporary, 16 bytes per rect pixel, (0, 0, 0) where there is no record.
 struct FrameRect {
     uint32_t x0, y0, w, n;   // origin, row length and pixel count of the rect
 };
@@ -3048,13 +3052,15 @@ CT_DEV void rect_pixel(const FrameRect &r, uint32_t i, uint32_t &x, uint32_t &y)
     y = r.y0 + i / r.w;
 }
 
-template <bool FIXED8>
+template <bool FIXED8, bool DIRECT>
 __global__ __launch_bounds__(256) void first_scatter_frame_kernel(DevScene sc, FrameRect r, uint32_t subframe_id,
-                                                                 float4 *__restrict__ found, uint32_t *__restrict__ wave_counts)
+                                                                 float4 *__restrict__ found, uint32_t *__restrict__ wave_counts,
+                                                                 float4 *__restrict__ direct)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;   // (every lane reaches the ballot: no early return)
     bool valid = false;
     f3 world = mk3(0, 0, 0);
+    f3 sun = mk3(0, 0, 0);
     if (i < r.n) {
         uint32_t x, y;
         rect_pixel(r, i, x, y);
@@ -3071,9 +3077,15 @@ __global__ __launch_bounds__(256) void first_scatter_frame_kernel(DevScene sc, F
             if (scattered && in_box(sc, pos)) {
                 valid = true;
                 world = sub3(pos, scale3(mk3(sc.bx, sc.by, sc.bz), 0.5f));
+                if constexpr (DIRECT) {
+                    sun = in_scattering<FIXED8>(sc, pos, dir, false);
+                }
             }
         }
         found[i] = make_float4(world.x, world.y, world.z, valid ? 1.f : 0.f);
+        if constexpr (DIRECT) {
+            direct[i] = make_float4(sun.x, sun.y, sun.z, 0.f);
+        }
     }
     const uint64_t mask = __builtin_amdgcn_ballot_w64(valid);
     if ((threadIdx.x & 63u) == 0u) {
@@ -3143,15 +3155,17 @@ __global__ __launch_bounds__(256) void first_scatter_compact_kernel(DevScene sc,
 
 hipError_t launch_first_scatter_frame(const DevScene &sc, uint32_t x0, uint32_t y0, uint32_t w, uint32_t n, uint32_t subframe_id,
                                       float4 *found, uint32_t *wave_counts, uint32_t capacity, float *positions, float *directions,
-                                      uint32_t *pixels, hipStream_t stream)
+                                      uint32_t *pixels, float4 *direct, hipStream_t stream)
 {
     const FrameRect r{ x0, y0, w, n };
     const uint32_t blocks = (n + 255u) / 256u;
-    if (sc.tex_fixed8) {
-        hipLaunchKernelGGL(first_scatter_frame_kernel<true>, dim3(blocks), dim3(256), 0, stream, sc, r, subframe_id, found, wave_counts);
-    } else {
-        hipLaunchKernelGGL(first_scatter_frame_kernel<false>, dim3(blocks), dim3(256), 0, stream, sc, r, subframe_id, found, wave_counts);
+    auto flight = first_scatter_frame_kernel<false, false>;
+    if (direct) {
+        flight = sc.tex_fixed8 ? first_scatter_frame_kernel<true, true> : first_scatter_frame_kernel<false, true>;
+    } else if (sc.tex_fixed8) {
+        flight = first_scatter_frame_kernel<true, false>;
     }
+    hipLaunchKernelGGL(flight, dim3(blocks), dim3(256), 0, stream, sc, r, subframe_id, found, wave_counts, direct);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         return e;
@@ -3199,12 +3213,15 @@ hipError_t launch_network_aux(const float *directions, uint32_t count, float lx,
 // made again from the flight's temporary -- a gather, so neither a scatter by the pixel list nor an atomic.
 // ACCUMULATE: the pixel goes straight into the Welford update of mean and M2 (accumulate_batch_kernel's arithmetic, its frozen
 // test included); otherwise into the frame.
-template <bool ACCUMULATE>
+// DIRECT (CT_NET_ADD_SINGLE_SCATTER): a pixel with a record gets the flight's single-scatter term, read by pixel index, added
+// behind the scaled network output (the product is rounded first: the build has no contraction).
+template <bool ACCUMULATE, bool DIRECT>
 __global__ __launch_bounds__(256) void network_compose_kernel(const float4 *__restrict__ found, const uint32_t *__restrict__ wave_offsets,
                                                               const float *__restrict__ out, uint32_t n, NetCompose c,
                                                               float4 *__restrict__ frame, float4 *__restrict__ mean,
                                                               float4 *__restrict__ m2, uint32_t subframe_id,
-                                                              const uint32_t *__restrict__ frozen)
+                                                              const uint32_t *__restrict__ frozen,
+                                                              const float4 *__restrict__ direct)
 {
     if (ACCUMULATE && frozen && *frozen != 0u) {
         return;   // the image has converged (converged_freeze_kernel): the running mean stays as it is
@@ -3225,6 +3242,12 @@ __global__ __launch_bounds__(256) void network_compose_kernel(const float4 *__re
         const float L = c.transform == 1 /* CT_NET_OUT_EXPM1 */ ? ct_expf(o) - 1.0f : o;
         const float g = L > 0.f ? L : 0.f;   // (a NaN becomes 0)
         v = make_float4(c.sr * g, c.sg * g, c.sb * g, 1.f);
+        if constexpr (DIRECT) {
+            const float4 d = direct[i];
+            v.x += d.x;
+            v.y += d.y;
+            v.z += d.z;
+        }
     }
     if (ACCUMULATE) {
         float4 mu = mean[i], var = m2[i];
@@ -3238,15 +3261,17 @@ __global__ __launch_bounds__(256) void network_compose_kernel(const float4 *__re
 
 hipError_t launch_network_compose(const float4 *found, const uint32_t *wave_offsets, const float *out, uint32_t n, const NetCompose &c,
                                   float4 *frame, float4 *mean, float4 *m2, uint32_t subframe_id, const uint32_t *frozen,
-                                  hipStream_t stream)
+                                  const float4 *direct, hipStream_t stream)
 {
     const uint32_t blocks = (n + 255u) / 256u;
     if (frame) {
-        hipLaunchKernelGGL(network_compose_kernel<false>, dim3(blocks), dim3(256), 0, stream, found, wave_offsets, out, n, c, frame,
-                           (float4 *)nullptr, (float4 *)nullptr, subframe_id, (const uint32_t *)nullptr);
+        auto compose = direct ? network_compose_kernel<false, true> : network_compose_kernel<false, false>;
+        hipLaunchKernelGGL(compose, dim3(blocks), dim3(256), 0, stream, found, wave_offsets, out, n, c, frame, (float4 *)nullptr,
+                           (float4 *)nullptr, subframe_id, (const uint32_t *)nullptr, direct);
     } else {
-        hipLaunchKernelGGL(network_compose_kernel<true>, dim3(blocks), dim3(256), 0, stream, found, wave_offsets, out, n, c,
-                           (float4 *)nullptr, mean, m2, subframe_id, frozen);
+        auto compose = direct ? network_compose_kernel<true, true> : network_compose_kernel<true, false>;
+        hipLaunchKernelGGL(compose, dim3(blocks), dim3(256), 0, stream, found, wave_offsets, out, n, c, (float4 *)nullptr, mean, m2,
+                           subframe_id, frozen, direct);
     }
     return hipGetLastError();
 }

@@ -86,7 +86,8 @@ namespace DeepestScatter
 
     // The reference's neural renderers are ARenderers too: the same Camera loop, the frame made by the scattering network
     // (ct_network_render_subframe / ct_network_render_accumulate) instead of the estimator.  It keeps the path tracer's scene
-    // set-up (init) and output name; the network lives on the context's handle and goes before it.
+    // set-up (init) and output name; the network lives on the context's handle and goes before it.  params.transform may
+    // carry CT_NET_ADD_SINGLE_SCATTER (--net-direct): both entry points then add the sun's single-scatter term to the frame.
     class NetworkRenderer : public PathTracingRenderer
     {
     public:

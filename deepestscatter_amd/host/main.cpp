@@ -8,8 +8,10 @@
 //              [--size-m 7000] [--out DIR] [--data DIR] [--unfused] [--display] [--estimator march|delta] [--format exr|pfm]
 //              [--tex-fixed8]   filter weights in 1.8 fixed point like the reference's texture unit (CT_FLAG_TEX_FIXED8)
 //              [--gpus N | --gpus a,b,c]   one process, one shard of 8x8-pixel tiles per GPU, RCCL reduce of [mean | M2] (ct_group_*)
-//              [--network FILE [--net-transform linear|expm1] [--net-scale r,g,b]]   the job's subframes come from the scattering
-//                               network in FILE (NetworkFile.h; ct_network_render_accumulate) instead of the estimator
+//              [--network FILE [--net-transform linear|expm1] [--net-scale r,g,b] [--net-direct]]   the job's subframes come from
+//                               the scattering network in FILE (NetworkFile.h; ct_network_render_accumulate) instead of the
+//                               estimator; --net-direct adds the sun's single-scatter term (CT_NET_ADD_SINGLE_SCATTER), so that a
+//                               network trained on the multiple-scatter labels gives the picture --mode total gives
 //   <cloud> = file.vdb | procedural:<N>[:<seed>] | file.f32grid
 //
 //   cloudtrace collect <cloud>|@list.txt [--scene-id I] [--scenes N] [--jobs K] [--gpus ..] [--batch 2048] [--light L] [--size-m M] [--out DIR] [--data DIR] [--estimator ..] [--tex-fixed8]
@@ -67,6 +69,7 @@ namespace
         std::string networkPath;                                                  // --network FILE: the scattering network renders instead of the estimator
         std::shared_ptr<const NetworkFile> network;                               // ... read and checked before anything is created
         CtNetworkRender networkRender{ CT_ABI_VERSION, CT_NET_OUT_LINEAR, { 1.f, 1.f, 1.f }, 0 };   // --net-transform, --net-scale
+        bool netDirect = false;                                                   // --net-direct: CT_NET_ADD_SINGLE_SCATTER joins networkRender.transform
         bool collect = false;                                                     // `cloudtrace collect ...`
         int32_t sceneId = 0;
         uint32_t batch = 2048;                                                    // Tasks.cpp:137
@@ -287,7 +290,7 @@ int main(int argc, char* argv[])
     try
     {
         Options opt;
-        if (argc < 2) { std::cerr << "usage: cloudtrace <cloud> [--size WxH] [--spp N] [--mode total|multi|single] [--light L] [--size-m M] [--out DIR] [--data DIR] [--unfused] [--display] [--estimator march|delta] [--format exr|pfm] [--gpus N|a,b,c] [--tex-fixed8] [--network FILE [--net-transform linear|expm1] [--net-scale r,g,b]]\n"; return 2; }
+        if (argc < 2) { std::cerr << "usage: cloudtrace <cloud> [--size WxH] [--spp N] [--mode total|multi|single] [--light L] [--size-m M] [--out DIR] [--data DIR] [--unfused] [--display] [--estimator march|delta] [--format exr|pfm] [--gpus N|a,b,c] [--tex-fixed8] [--network FILE [--net-transform linear|expm1] [--net-scale r,g,b] [--net-direct]]\n"; return 2; }
         int first = 2;
         bool lightsGiven = false;
         opt.cloud = argv[1];
@@ -337,6 +340,7 @@ int main(int argc, char* argv[])
                 float* s = opt.networkRender.rgb_scale;
                 if (std::sscanf(next().c_str(), "%f,%f,%f", &s[0], &s[1], &s[2]) != 3) throw std::invalid_argument("--net-scale r,g,b");
             }
+            else if (a == "--net-direct") opt.netDirect = true;
             else if (a == "--tex-fixed8") opt.texFixed8 = true;
             else if (a == "--estimator")
             {
@@ -367,6 +371,7 @@ int main(int argc, char* argv[])
 
         if (opt.collect) return collectScenes(opt);
 
+        if (opt.netDirect) opt.networkRender.transform |= CT_NET_ADD_SINGLE_SCATTER;   // (after the loop: --net-transform may follow it)
         if (!opt.networkPath.empty())
         {
             // read and checked against the header's formula here, before a renderer exists: a malformed file costs no device

@@ -177,11 +177,12 @@ def reference_forward(weights, desc: NetworkShape, descriptors_u8, aux, accumula
     return linear(z, matrix(W), c)[:, 0]
 
 
-def render_values(out, transform="linear", rgb_scale=(1.0, 1.0, 1.0), expf=None) -> np.ndarray:
+def render_values(out, transform="linear", rgb_scale=(1.0, 1.0, 1.0), expf=None, direct=None) -> np.ndarray:
     """The pixel values ct_network_render_* makes of network outputs, restated in numpy float32: L = out ("linear") or
     expf(out) - 1 ("expm1"), g = L if L > 0 else 0 (so a NaN gives 0), pixel = (rgb_scale * g, 1) -> float32 [n, 4].
     `expf`: a float -> float function standing for the library's ct_expf (include/ct_fmath.h); "expm1" needs one (np.exp is
-    not bit-identical to it)."""
+    not bit-identical to it).  `direct`: float32 [n, 3], the single-scatter term of CT_NET_ADD_SINGLE_SCATTER per record, added
+    to the rgb after the scale, in float32."""
     o = np.ascontiguousarray(out, np.float32).reshape(-1)
     if transform in ("linear", 0):
         L = o
@@ -197,6 +198,8 @@ def render_values(out, transform="linear", rgb_scale=(1.0, 1.0, 1.0), expf=None)
     px = np.empty((o.size, 4), np.float32)
     px[:, :3] = s[None, :] * g[:, None]
     px[:, 3] = 1.0
+    if direct is not None:
+        px[:, :3] += np.ascontiguousarray(direct, np.float32).reshape(o.size, 3)
     return px
 
 

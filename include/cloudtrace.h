@@ -493,6 +493,20 @@ CT_API float ct_debug_bf16_round(float x);
  *   - the pixel is (rgb_scale[0] * g, rgb_scale[1] * g, rgb_scale[2] * g, 1);
  *   - a pixel without a record is (0, 0, 0, 1), the miss value of ct_render_subframe.
  *
+ * The sun's single-scatter term (CT_NET_ADD_SINGLE_SCATTER).  A network trained on ct_point_radiance_launch's
+ * CT_MODE_SUN_MULTIPLE_SCATTER labels predicts the multiply scattered light only; per pixel and subframe
+ *     CT_MODE_TOTAL  =  CT_MODE_SUN_SINGLE_SCATTER  +  (multiple scatter from the first-scatter point),
+ * the first summand being the un-chopped-Mie NEE at the first collision, with the same seed and the same first flight.  With
+ * the flag in `transform` a pixel that has a record is
+ *     (rgb_scale[0] * g + D.x, rgb_scale[1] * g + D.y, rgb_scale[2] * g + D.z, 1),
+ * each product rounded to float32 before its sum (no contraction).  D is what singleScatterSunRadiance returns for that pixel
+ * and subframe, i.e. what ct_render_subframe of a CT_MODE_SUN_SINGLE_SCATTER handle writes there: getInScattering at the
+ * flight's end position and d2 with the un-chopped Mie table, the handle's shadow volume (it follows ct_set_light), light
+ * colour x intensity and sun_ratio.  rgb_scale does not apply to D, which is in the estimator's own units.  D is evaluated in
+ * the first-flight pass, at the flight's own texture-space end position (the record's world position plus the half box does
+ * not round back to it).  Like the flight, D ignores the handle's mode and estimator; CT_FLAG_TEX_FIXED8 applies to it as to
+ * every other NEE.  A pixel without a record stays (0, 0, 0, 1).  A call without the flag is bit for bit what it was.
+ *
  * Bands.  The frame is cut into bands of whole rows of at most band_pixels pixels (at least one row, at most 2^20 pixels; 0 =
  * 2^20), taken bottom to top; each band is one pass through the first flights and their compaction, the 4-byte read of the
  * record count, the descriptor gather, the aux kernel, the network and one kernel that forms the pixels.  That kernel ranks a
@@ -502,25 +516,30 @@ CT_API float ct_debug_bf16_round(float x);
  * the aux kernel and the network.
  *
  * Scratch.  The temporaries belong to the handle: allocated on first use, grown when a call needs more, never freed between
- * calls, freed by ct_destroy; a warm call allocates nothing.  The per-pixel temporary, positions, directions, aux and out are
- * sized for the band and allocated, with a first piece of the descriptor array, before the call's first kernel: CT_E_NOMEM can
- * only be answered there, and then frame, mean, M2 and the subframe count are exactly as they were and the handle is usable.
+ * calls, freed by ct_destroy; a warm call allocates nothing.  The per-pixel temporary, positions, directions, aux and out --
+ * and, from the first call that carries CT_NET_ADD_SINGLE_SCATTER on, the single-scatter temporary, 16 more bytes per band
+ * pixel -- are sized for the band and allocated, with a first piece of the descriptor array, before the call's first kernel:
+ * CT_E_NOMEM can only be answered there, and then frame, mean, M2 and the subframe count are exactly as they were and the
+ * handle is usable.
  * The descriptor array (2250 bytes per record: 2^20 records would be 2.4 GB, which is why the count is read first and why
  * band_pixels exists) is sized for the largest record count seen so far and grown between bands, with the stream idle; if
  * the device refuses that growth the band's records go through the gather and the network in pieces of the size it has -- the
  * same bits, since records are independent -- and the call succeeds.
  *
- * CT_E_INVAL: a NULL handle (answered without a device), network or params; a wrong abi_version; an unknown transform; an
- * rgb_scale that is not finite; a network with aux != 1; a network on another device than h; a handle created with
+ * CT_E_INVAL: a NULL handle (answered without a device), network or params; a wrong abi_version; an unknown transform (a low
+ * byte that is no CT_NET_OUT_* value, or any bit set above it other than CT_NET_ADD_SINGLE_SCATTER); an rgb_scale that is not
+ * finite; a network with aux != 1; a network on another device than h; a handle created with
  * shard_count > 1 (a sharded frame is out of scope here: ct_descriptor_frame ignores shards, and splitting a frame by rects
  * over a CtGroup is a later change); subframe_id == 0; count == 0.  CT_E_STATE: no camera pose (ct_create sets the default
  * one, so a live handle always has one); ct_network_render_accumulate with first_subframe_id != subframes + 1, as
  * ct_render_accumulate.  Arguments are checked before anything of the handle changes.
  * Both wait for the batches in flight, run on the handle's stream and return when it is idle. */
 enum { CT_NET_OUT_LINEAR = 0, CT_NET_OUT_EXPM1 = 1 };
+#define CT_NET_ADD_SINGLE_SCATTER 0x100   /* bit 8 of CtNetworkRender::transform: add the sun's single-scatter term D */
 typedef struct CtNetworkRender {
     uint32_t abi_version;   /* must be CT_ABI_VERSION */
-    int32_t  transform;     /* CT_NET_OUT_LINEAR: L = out; CT_NET_OUT_EXPM1: L = ct_expf(out) - 1.0f */
+    int32_t  transform;     /* low byte: CT_NET_OUT_LINEAR: L = out; CT_NET_OUT_EXPM1: L = ct_expf(out) - 1.0f.  Bit 8:
+                               CT_NET_ADD_SINGLE_SCATTER.  Any other bit set: CT_E_INVAL */
     float    rgb_scale[3];  /* finite */
     uint32_t band_pixels;   /* largest number of pixels handled at once; 0 = 2^20.  Bands are whole rows, at least one row,
                                at most 2^20 pixels */
@@ -545,7 +564,8 @@ CT_API int ct_network_render_accumulate(CtHandle h, CtNetwork n, const CtNetwork
 CT_API int ct_debug_network_aux(CtHandle h, const float *directions_dev, uint32_t count, float *aux_dev_out);
 
 /* Diagnostic: milliseconds the GPU spent in the last ct_network_render_subframe / ct_network_render_accumulate of this handle
- * (HIP events on its stream), summed over its bands and subframes: ms_out[0] first flights with their compaction, [1] the
+ * (HIP events on its stream), summed over its bands and subframes: ms_out[0] first flights with their compaction (and the NEE of
+ * CT_NET_ADD_SINGLE_SCATTER, which runs in the flight's kernel), [1] the
  * descriptor gather, [2] the network, [3] the aux kernel and the kernel that forms the pixels (and accumulates them). */
 CT_API int ct_debug_network_render_time(CtHandle h, double ms_out[4]);
 

@@ -7,8 +7,11 @@
           ct_network_render_subframe + ct_accumulate;
   line 3  the Python route of the same tree, CloudTracer.network_frame (descriptor_frame with its allocations, aux and the
           scatter as torch ops), per subframe.
-Needs a GPU.  Prints three JSON lines.
-    python tools/network_render_time.py [--repeats 5] [--volume 512] [--size 1024] [--subframes 16] [--band 0]"""
+--direct: what CT_NET_ADD_SINGLE_SCATTER costs.  Lines 1 and 2 are measured twice in the same run, the calls without and with
+the flag taking turns, and printed twice ("direct": false, then true); line 1 also carries the smallest and largest
+first-flight time of its repeats, the spread the difference has to be read against.
+Needs a GPU.  Prints three JSON lines (five with --direct).
+    python tools/network_render_time.py [--repeats 5] [--volume 512] [--size 1024] [--subframes 16] [--band 0] [--direct]"""
 import argparse, json, statistics, sys, time
 from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
@@ -28,6 +31,7 @@ if __name__ == "__main__":
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--subframes", type=int, default=16)
     ap.add_argument("--band", type=int, default=0)
+    ap.add_argument("--direct", action="store_true")
     a = ap.parse_args()
     import torch
     import deepestscatter_amd as ds
@@ -39,33 +43,44 @@ if __name__ == "__main__":
     med = statistics.median
 
     # one subframe: stages and wall time (the first call allocates the scratch and builds the pyramid: warm-up)
-    stages, wall = [], []
+    flags = [False, True] if a.direct else [False]
+    stages, wall = {f: [] for f in flags}, {f: [] for f in flags}
     for i in range(a.repeats + 1):
-        wall.append(wall_ms(lambda: tr.network_render_subframe(net, 1, band_pixels=a.band, out=False)))
-        stages.append(tr.network_render_time())
+        for f in flags:
+            wall[f].append(wall_ms(lambda: tr.network_render_subframe(net, 1, band_pixels=a.band, out=False, direct=f)))
+            stages[f].append(tr.network_render_time())
     records = int(tr.descriptor_frame(1)[3].shape[0])
     names = ["flights_and_compaction_ms", "gather_ms", "network_ms", "aux_and_compose_ms"]
-    line = {"route": "ct_network_render_subframe", **common, "records": records, "wall_ms": med(wall[1:])}
-    line.update({n: med([s[k] for s in stages[1:]]) for k, n in enumerate(names)})
-    print(json.dumps(line), flush=True)
+    for f in flags:
+        line = {"route": "ct_network_render_subframe", **common, "records": records, "wall_ms": med(wall[f][1:])}
+        line.update({n: med([s[k] for s in stages[f][1:]]) for k, n in enumerate(names)})
+        if a.direct:
+            flights = [s[0] for s in stages[f][1:]]
+            line.update({"direct": f, "flights_and_compaction_ms_min": min(flights), "flights_and_compaction_ms_max": max(flights)})
+        print(json.dumps(line), flush=True)
 
     # S subframes: fused against the unfused loop
     S = a.subframes
 
-    def unfused():
+    def unfused(f):
         for sid in range(1, S + 1):
-            tr.network_render_subframe(net, sid, band_pixels=a.band, out=False)
+            tr.network_render_subframe(net, sid, band_pixels=a.band, out=False, direct=f)
             tr.accumulate(sid)
 
-    fused_ms, loop_ms = [], []
+    fused_ms, loop_ms = {f: [] for f in flags}, {f: [] for f in flags}
     for i in range(a.repeats + 1):
-        tr.reset()
-        fused_ms.append(wall_ms(lambda: tr.network_render_accumulate(net, 1, S, band_pixels=a.band)))
-        tr.reset()
-        loop_ms.append(wall_ms(unfused))
-    print(json.dumps({"route": "ct_network_render_accumulate", **common, "subframes": S, "fused_wall_ms": med(fused_ms[1:]),
-                      "unfused_loop_wall_ms": med(loop_ms[1:]), "fused_ms_per_subframe": med(fused_ms[1:]) / S,
-                      "unfused_ms_per_subframe": med(loop_ms[1:]) / S}), flush=True)
+        for f in flags:
+            tr.reset()
+            fused_ms[f].append(wall_ms(lambda: tr.network_render_accumulate(net, 1, S, band_pixels=a.band, direct=f)))
+            tr.reset()
+            loop_ms[f].append(wall_ms(lambda: unfused(f)))
+    for f in flags:
+        line = {"route": "ct_network_render_accumulate", **common, "subframes": S, "fused_wall_ms": med(fused_ms[f][1:]),
+                "unfused_loop_wall_ms": med(loop_ms[f][1:]), "fused_ms_per_subframe": med(fused_ms[f][1:]) / S,
+                "unfused_ms_per_subframe": med(loop_ms[f][1:]) / S}
+        if a.direct:
+            line["direct"] = f
+        print(json.dumps(line), flush=True)
 
     # the Python route: one float per pixel of one rect of at most 2^20 pixels
     py_ms = []

@@ -27,13 +27,14 @@ CT_NET_ADD_SINGLE_SCATTER = 0x100            # CtNetworkRender.transform, bit 8:
 # every symbol include/cloudtrace.h declares (tests check the library exports all of them)
 EXPORTS = [
     "ct_create", "ct_destroy", "ct_last_error", "ct_set_stream", "ct_set_camera", "ct_set_light", "ct_render_subframe",
-    "ct_accumulate", "ct_render_accumulate", "ct_render_accumulate_async", "ct_synchronize", "ct_copy_to_device_async", "ct_point_radiance_launch", "ct_generate_scatter_samples", "ct_collect_descriptors", "ct_descriptor_frame", "ct_debug_descriptor_frame_time", "ct_network_create", "ct_network_destroy", "ct_network_eval", "ct_debug_network_time", "ct_network_render_subframe", "ct_network_render_accumulate", "ct_debug_network_aux", "ct_debug_network_render_time", "ct_reset", "ct_tonemap", "ct_tonemap_async", "ct_set_render_ahead", "ct_rendered_subframes", "ct_set_stop_when_converged", "ct_converged_at", "ct_is_converged", "ct_tonemap_buffer", "ct_is_converged_buffers", "ct_download", "ct_upload",
+    "ct_accumulate", "ct_render_accumulate", "ct_render_accumulate_async", "ct_synchronize", "ct_copy_to_device_async", "ct_point_radiance_launch", "ct_generate_scatter_samples", "ct_collect_descriptors", "ct_descriptor_frame", "ct_debug_descriptor_frame_time", "ct_network_create", "ct_network_destroy", "ct_network_eval", "ct_debug_network_time", "ct_network_render_subframe", "ct_network_render_accumulate", "ct_network_render_shard_subframe", "ct_network_render_shard_accumulate", "ct_debug_network_scratch", "ct_debug_network_aux", "ct_debug_network_render_time", "ct_reset", "ct_tonemap", "ct_tonemap_async", "ct_set_render_ahead", "ct_rendered_subframes", "ct_set_stop_when_converged", "ct_converged_at", "ct_is_converged", "ct_tonemap_buffer", "ct_is_converged_buffers", "ct_download", "ct_upload",
     "ct_buffer_bytes", "ct_copy_to_device", "ct_device_ptr", "ct_subframes", "ct_set_subframes", "ct_counters", "ct_kernel_time",
     "ct_debug_cdf_inversion", "ct_debug_math_selftest", "ct_debug_fetch_probe", "ct_debug_fetch_probe_ws", "ct_debug_track_lines", "ct_debug_touched_lines", "ct_debug_stats", "ct_debug_stats_ex", "ct_debug_suspended", "ct_debug_timeline", "ct_debug_invariants", "ct_debug_memory", "ct_debug_delta_grid", "ct_debug_march_meta", "ct_debug_layout", "ct_fetch_counters", "ct_calculate_camera_variables", "ct_quantize_volume", "ct_load_vdb", "ct_generate_mipmaps",
-    "ct_tile_owner", "ct_make_procedural_cloud",
+    "ct_tile_owner", "ct_shard_tiles", "ct_make_procedural_cloud",
     "ct_group_create", "ct_group_destroy", "ct_group_last_error", "ct_group_size", "ct_group_handle", "ct_group_set_camera", "ct_group_set_light",
     "ct_group_render_accumulate", "ct_group_reset", "ct_group_merge", "ct_group_download", "ct_group_tonemap",
     "ct_group_is_converged", "ct_group_counters",
+    "ct_group_network_create", "ct_group_network_destroy", "ct_group_network_render_accumulate",
 ]
 # ... and ct_debug_bf16_round, the one declared symbol whose name has digits (the list above is matched by name pattern)
 DEBUG_EXPORTS = ["ct_debug_bf16_round"]
@@ -152,6 +153,9 @@ def load():
         "ct_debug_bf16_round": (f32, [f32]),
         "ct_network_render_subframe": (i32, [vp, vp, C.POINTER(CtNetworkRender), u32, vp]),
         "ct_network_render_accumulate": (i32, [vp, vp, C.POINTER(CtNetworkRender), u32, u32]),
+        "ct_network_render_shard_subframe": (i32, [vp, vp, C.POINTER(CtNetworkRender), u32, vp]),
+        "ct_network_render_shard_accumulate": (i32, [vp, vp, C.POINTER(CtNetworkRender), u32, u32]),
+        "ct_debug_network_scratch": (i32, [vp, C.POINTER(C.c_uint64)]),
         "ct_debug_network_aux": (i32, [vp, vp, u32, vp]),
         "ct_debug_network_render_time": (i32, [vp, C.POINTER(C.c_double)]),
         "ct_reset": (i32, [vp]),
@@ -195,6 +199,7 @@ def load():
         "ct_load_vdb": (i32, [C.c_char_p, vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_char_p, C.c_size_t]),
         "ct_generate_mipmaps": (i32, [vp, vp, vp, C.c_size_t, C.POINTER(u32), C.POINTER(C.c_size_t), vp]),
         "ct_tile_owner": (u32, [u32, u32, u32]),
+        "ct_shard_tiles": (i32, [u32, u32, u32, u32, vp, u32, C.POINTER(u32)]),
         "ct_group_create": (i32, [C.POINTER(CtScene), vp, u32, C.POINTER(vp)]),
         "ct_group_destroy": (i32, [vp]),
         "ct_group_last_error": (C.c_char_p, [vp]),
@@ -209,6 +214,9 @@ def load():
         "ct_group_tonemap": (i32, [vp, f32, vp, C.POINTER(f32)]),
         "ct_group_is_converged": (i32, [vp, C.POINTER(i32), C.POINTER(C.c_uint64)]),
         "ct_group_counters": (i32, [vp, C.POINTER(CtCounters)]),
+        "ct_group_network_create": (i32, [vp, C.POINTER(CtNetworkDesc), C.POINTER(vp)]),
+        "ct_group_network_destroy": (i32, [vp]),
+        "ct_group_network_render_accumulate": (i32, [vp, vp, C.POINTER(CtNetworkRender), u32, u32]),
         "ct_make_procedural_cloud": (i32, [u32, u32, vp]),
     }
     for name, (res, args) in sig.items():

@@ -84,7 +84,7 @@ def build_variant(name: str, force: bool = False, verbose: bool = False) -> Path
     out = PKG / f"libcloudtrace_{name}.so"
     deps = [CSRC / s for s in SOURCES] + HEADERS
     if force or not out.exists() or any(d.stat().st_mtime > out.stat().st_mtime for d in deps):
-        cmd = [hipcc(), *FLAGS, *VARIANTS[name], "-o", str(out), *[str(CSRC / s) for s in SOURCES], "-lz", "-ldl"]
+        cmd = [hipcc(), *FLAGS, *VARIANTS[name], "-o", str(out), *[str(CSRC / s) for s in SOURCES], "-lz", "-ldl", "-pthread"]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.run(cmd, check=True, cwd=str(CSRC))
@@ -94,7 +94,7 @@ def build_variant(name: str, force: bool = False, verbose: bool = False) -> Path
 def build(force: bool = False, verbose: bool = False) -> Path:
     if force or needs_build():
         # CT_EXTRA_FLAGS: e.g. -DCT_DEBUG_BOUNDS (device-side index checks that report instead of faulting)
-        cmd = [hipcc(), *FLAGS, *os.environ.get("CT_EXTRA_FLAGS", "").split(), "-o", str(LIB), *[str(CSRC / s) for s in SOURCES], "-lz", "-ldl"]
+        cmd = [hipcc(), *FLAGS, *os.environ.get("CT_EXTRA_FLAGS", "").split(), "-o", str(LIB), *[str(CSRC / s) for s in SOURCES], "-lz", "-ldl", "-pthread"]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.run(cmd, check=True, cwd=str(CSRC))

@@ -126,6 +126,21 @@ def shard_mask(width: int, height: int, shard_index: int, shard_count: int) -> n
     return ((tx + 3 * ty) % shard_count) == shard_index
 
 
+def shard_tiles(width: int, height: int, shard_index: int, shard_count: int) -> np.ndarray:
+    """ct_shard_tiles: the shard's 8x8 tiles as ty * tiles_x + tx, ascending (uint32): the order the sharded network renderer
+    takes them in."""
+    L = _lib.load()
+    n = C.c_uint32(0)
+    rc = L.ct_shard_tiles(width, height, shard_index, shard_count, None, 0, C.byref(n))
+    if rc != _lib.CT_OK:
+        raise _lib.CloudTraceError(rc, "ct_shard_tiles: an empty frame, or a shard index that is not below the shard count")
+    out = np.empty(n.value, np.uint32)
+    rc = L.ct_shard_tiles(width, height, shard_index, shard_count, _p(out) if n.value else None, n.value, C.byref(n))
+    if rc != _lib.CT_OK:
+        raise _lib.CloudTraceError(rc, "ct_shard_tiles")
+    return out
+
+
 @dataclass
 class SceneParams:
     """Defaults = the reference's hard-coded configuration (SURVEY.md section 5 'config')."""
@@ -360,6 +375,10 @@ class CloudTracer:
         direct=True (CT_NET_ADD_SINGLE_SCATTER): a pixel with a record also gets the sun's single-scatter term of that pixel and
         subframe -- what a CT_MODE_SUN_SINGLE_SCATTER tracer renders there -- added behind the scaled network output, so that a
         network trained on the multiple-scatter labels gives the path tracer's picture."""
+        return self._network_render_subframe(self.L.ct_network_render_subframe, net, subframe_id, transform, rgb_scale, band_pixels,
+                                             out, direct)
+
+    def _network_render_subframe(self, entry, net, subframe_id, transform, rgb_scale, band_pixels, out, direct):
         p = self._network_render_params(transform, rgb_scale, band_pixels, direct)
         ptr = None
         if out is not False:
@@ -371,7 +390,7 @@ class CloudTracer:
                 raise ValueError("out must be a contiguous float32 tensor [H, W, 4]")
             torch.cuda.synchronize(dev)      # the library writes it on the handle's stream, not on torch's
             ptr = C.c_void_p(out.data_ptr())
-        check(self.L.ct_network_render_subframe(self.h, net.n, C.byref(p), subframe_id & 0xFFFFFFFF, ptr), self.h)
+        check(entry(self.h, net.n, C.byref(p), subframe_id & 0xFFFFFFFF, ptr), self.h)
         return None if out is False else out
 
     def network_render_accumulate(self, net, first_subframe_id: int, count: int, transform="linear", rgb_scale=(1.0, 1.0, 1.0),
@@ -380,6 +399,29 @@ class CloudTracer:
         (no frame is materialised); mean, M2 and the subframe count end exactly as that loop leaves them.  direct: as there."""
         p = self._network_render_params(transform, rgb_scale, band_pixels, direct)
         check(self.L.ct_network_render_accumulate(self.h, net.n, C.byref(p), first_subframe_id & 0xFFFFFFFF, count), self.h)
+
+    def network_render_shard_subframe(self, net, subframe_id: int, transform="linear", rgb_scale=(1.0, 1.0, 1.0), band_pixels: int = 0,
+                                      out=None, direct: bool = False):
+        """ct_network_render_shard_subframe: network_render_subframe on a tracer of any shard_count -- the pixels of the shard's
+        own tiles are the unsharded frame's, foreign pixels (0, 0, 0, 0) -- rendered tile band by tile band (band_pixels / 64
+        tiles at once).  With shard_count == 1 the bits are network_render_subframe's."""
+        return self._network_render_subframe(self.L.ct_network_render_shard_subframe, net, subframe_id, transform, rgb_scale,
+                                             band_pixels, out, direct)
+
+    def network_render_shard_accumulate(self, net, first_subframe_id: int, count: int, transform="linear", rgb_scale=(1.0, 1.0, 1.0),
+                                        band_pixels: int = 0, direct: bool = False):
+        """ct_network_render_shard_accumulate: network_render_accumulate on a tracer of any shard_count; foreign pixels of mean
+        and M2 stay exactly 0, so the sum over the shards is the unsharded image."""
+        p = self._network_render_params(transform, rgb_scale, band_pixels, direct)
+        check(self.L.ct_network_render_shard_accumulate(self.h, net.n, C.byref(p), first_subframe_id & 0xFFFFFFFF, count), self.h)
+
+    def network_scratch(self) -> dict:
+        """ct_debug_network_scratch: the device addresses and capacities of the network renderer's scratch (a warm call leaves
+        them as they are)."""
+        v = (C.c_uint64 * 12)()
+        check(self.L.ct_debug_network_scratch(self.h, v), self.h)
+        names = ("found", "waves", "pos", "dir", "aux", "out", "desc", "direct", "tiles", "band_cap", "desc_cap", "direct_cap")
+        return {k: int(x) for k, x in zip(names, v)}
 
     def network_aux(self, directions):
         """ct_debug_network_aux: the renderer's aux input dot(direction, the direction the light travels) for a float32 torch
@@ -709,8 +751,16 @@ class TracerGroup:
 
     def close(self):
         if getattr(self, "g", None):
+            for net in list(getattr(self, "_networks", ())):
+                net.close()       # (a group's networks go before the group)
             self.L.ct_group_destroy(self.g)
             self.g = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
     def __del__(self):
         try:
@@ -729,6 +779,18 @@ class TracerGroup:
 
     def render_accumulate(self, first_subframe_id: int, count: int):
         self._check(self.L.ct_group_render_accumulate(self.g, first_subframe_id, count))
+
+    def network(self, module_or_weights, width: int | None = None, aux: int | None = None, head_layers: int | None = None):
+        """ct_group_network_create: the network on every shard's device -> GroupNetwork (arguments as network.Network's)."""
+        return GroupNetwork(self, module_or_weights, width, aux, head_layers)
+
+    def network_render_accumulate(self, net, first_subframe_id: int, count: int, transform="linear", rgb_scale=(1.0, 1.0, 1.0),
+                                  band_pixels: int = 0, direct: bool = False):
+        """ct_group_network_render_accumulate: CloudTracer.network_render_shard_accumulate on every shard, each shard on a host
+        thread of its own; mean(), m2(), tonemap() and is_converged() then give what one unsharded tracer gives."""
+        p = CloudTracer._network_render_params(transform, rgb_scale, band_pixels, direct)
+        self._check(self.L.ct_group_network_render_accumulate(self.g, net.gn if net is not None else None, C.byref(p),
+                                                              first_subframe_id & 0xFFFFFFFF, count))
 
     def reset(self):
         self._check(self.L.ct_group_reset(self.g))
@@ -762,6 +824,45 @@ class TracerGroup:
         c = CtCounters()
         self._check(self.L.ct_group_counters(self.g, C.byref(c)))
         return c.as_dict()
+
+
+class GroupNetwork:
+    """A CtGroupNetwork: one CtNetwork per shard of a TracerGroup (TracerGroup.network).  Closed with, or before, its group."""
+
+    def __init__(self, group: TracerGroup, module_or_weights, width=None, aux=None, head_layers=None):
+        from . import network as N
+        self.L, self.group = group.L, group
+        if hasattr(module_or_weights, "blocks"):
+            self.shape = module_or_weights.shape
+            weights = N.pack_weights(module_or_weights)
+        else:
+            self.shape = N.NetworkShape(*(d if v is None else int(v) for v, d in zip((width, aux, head_layers), (200, 1, 3))))
+            weights = np.ascontiguousarray(module_or_weights, np.float32).reshape(-1)
+        d = _lib.CtNetworkDesc(_lib.CT_ABI_VERSION, N.BLOCKS, self.shape.width, self.shape.aux, self.shape.head_layers,
+                               weights.ctypes.data_as(C.c_void_p), weights.size)
+        gn = C.c_void_p()
+        group._check(self.L.ct_group_network_create(group.g, C.byref(d), C.byref(gn)))
+        self.gn = gn
+        group.__dict__.setdefault("_networks", []).append(self)
+
+    def close(self):
+        if getattr(self, "gn", None):
+            self.L.ct_group_network_destroy(self.gn)
+            self.gn = None
+            if self in getattr(self.group, "_networks", []):
+                self.group._networks.remove(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def algorithmic_bytes(counters: dict, pixels_times_spp: int) -> int:

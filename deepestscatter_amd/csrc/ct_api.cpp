@@ -256,6 +256,10 @@ struct CtHandle_ {
         uint8_t *desc = nullptr;
         size_t band_cap = 0, desc_cap = 0, direct_cap = 0;
         double ms[4] = { 0, 0, 0, 0 };   // the last call (ct_debug_network_render_time)
+        // ct_network_render_shard_*: this shard's 8x8 tiles in ascending ty * tiles_x + tx (ct_shard_tiles), built on first use
+        uint32_t *tiles = nullptr;
+        uint32_t n_tiles = 0;
+        bool tiles_built = false;
     } net;
     uint64_t launches = 0;
     std::string error;
@@ -515,7 +519,7 @@ static void release(CtHandle h)
     void *ptrs[] = { h->d_density, h->d_inscatter, h->d_dbricks, h->d_ibricks, h->d_mbricks, h->d_tbricks, h->d_touched[0], h->d_touched[1], h->d_mrows, h->d_mcoarse, h->d_pyramid, h->d_mie, h->d_chopped, h->d_cdf,
                      h->d_guide, h->d_dist, h->d_dist_tmp, h->d_majorant, h->d_maj_cells, h->d_maj_codes, h->d_frame, h->d_mean, h->d_m2, h->d_screen, h->d_frames_all, h->cont[0], h->cont[1], h->left[0], h->left[1], h->d_cont_count, h->d_cont_total, h->d_primary, h->d_advance, h->d_pixels, h->d_cost, h->d_group_rank, h->d_group_order, h->d_job_group, h->d_job_sub, h->d_queue,
                      h->d_counters, h->d_colsum, h->d_avg, h->d_freeze, h->d_hit, h->d_cost_plane, h->d_timeline, h->pt.tasks, h->pt.primary, h->pt.frames, h->pt.pixels, h->pt.jg, h->pt.js,
-                     h->net.found, h->net.waves, h->net.pos, h->net.dir, h->net.aux, h->net.out, h->net.desc, h->net.direct };
+                     h->net.found, h->net.waves, h->net.pos, h->net.dir, h->net.aux, h->net.out, h->net.desc, h->net.direct, h->net.tiles };
     for (void *p : ptrs) {
         if (p) {
             hipFree(p);
@@ -3159,7 +3163,7 @@ extern "C" int ct_descriptor_frame(CtHandle h, uint32_t subframe_id, const uint3
         float *pos = positions_dev ? positions_dev : d_pos.p, *dir = directions_dev ? directions_dev : d_dir.p;
         HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
         HIPCHK(h, launch_first_scatter_frame(h->dev, x0, y0, rw, n, subframe_id, d_found, d_waves, capacity, pos, dir, pixels_dev, nullptr,
-                                             h->stream));
+                                             nullptr, h->stream));
         HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
         uint32_t count = 0;
         HIPCHK(h, hipMemcpyAsync(&count, d_waves + n_pad / 64u, sizeof count, hipMemcpyDeviceToHost, h->stream));
@@ -3236,7 +3240,7 @@ extern "C" int ct_network_eval(CtHandle h, CtNetwork n, const uint8_t *descripto
 
 // ---- the network as a renderer (ct_network_render_*) ------------------------------------------------------------------
 // Every CT_E_INVAL of the two entry points except the NULL handle and the ids; nothing of the handle is touched.
-static int net_validate(CtHandle h, CtNetwork n, const CtNetworkRender *p, const char *who)
+static int net_validate(CtHandle h, CtNetwork n, const CtNetworkRender *p, const char *who, bool shards)
 {
     if (!n || !p) {
         return fail(h, CT_E_INVAL, "%s: need a network and its parameters", who);
@@ -3259,9 +3263,9 @@ static int net_validate(CtHandle h, CtNetwork n, const CtNetworkRender *p, const
     if (ct::network_device(n) != h->device) {
         return fail(h, CT_E_INVAL, "%s: the network lives on device %d, the handle on device %d", who, ct::network_device(n), h->device);
     }
-    if (h->scene.shard_count > 1u) {
-        return fail(h, CT_E_INVAL, "%s: this handle renders shard %u of %u; a sharded network frame is out of scope (ct_descriptor_frame "
-                                   "ignores shards: split the frame by rects over the GPUs)", who, h->scene.shard_index, h->scene.shard_count);
+    if (!shards && h->scene.shard_count > 1u) {
+        return fail(h, CT_E_INVAL, "%s: this handle renders shard %u of %u; a shard's network frame is ct_network_render_shard_subframe / "
+                                   "ct_network_render_shard_accumulate", who, h->scene.shard_index, h->scene.shard_count);
     }
     return CT_OK;
 }
@@ -3346,17 +3350,50 @@ static void net_grow_descriptors(CtHandle h, size_t count)
     s.desc_cap = count;
 }
 
-// One band: rows [y0, y0 + rows) of subframe `sid` into the frame (frame != NULL) or into mean / M2.
-static int net_band(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t sid, uint32_t y0, uint32_t rows, float level0,
-                    float voxel_m, bool accumulate)
+// The tiles of a band of the tile path: at most band_pixels / 64, at least one, at most 2^14 (2^20 lanes).
+static uint32_t net_band_tiles(uint32_t band_pixels)
+{
+    const uint32_t cap = (band_pixels == 0u || band_pixels > (1u << 20)) ? (1u << 20) : band_pixels;
+    return std::max(1u, cap / 64u);
+}
+
+// The shard's tile list on the device, from ct_shard_tiles, once per handle.  The stream is idle.
+static int net_ensure_tiles(CtHandle h)
 {
     CtHandle_::NetScratch &s = h->net;
-    const uint32_t W = h->scene.width, npx = W * rows, n_pad = (npx + 255u) / 256u * 256u;
+    if (s.tiles_built) {
+        return CT_OK;
+    }
+    uint32_t count = 0;
+    if (ct_shard_tiles(h->scene.width, h->scene.height, h->scene.shard_index, h->scene.shard_count, nullptr, 0, &count) != CT_OK) {
+        return fail(h, CT_E_INVAL, "internal: ct_shard_tiles refused the handle's own frame");
+    }
+    std::vector<uint32_t> list(std::max(count, 1u), 0u);
+    if (ct_shard_tiles(h->scene.width, h->scene.height, h->scene.shard_index, h->scene.shard_count, list.data(), count, &count) != CT_OK) {
+        return fail(h, CT_E_INVAL, "internal: ct_shard_tiles refused the handle's own frame");
+    }
+    DevTemp<uint32_t> dev;
+    HIPCHK(h, dmalloc(&dev, list.size()));
+    HIPCHK(h, hipMemcpy(dev.p, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    s.tiles = dev.release();
+    s.n_tiles = count;
+    s.tiles_built = true;
+    return CT_OK;
+}
+
+// One band of subframe `sid` into the frame (frame != NULL) or into mean / M2.  Row path: rows [y0, y0 + rows); tile path
+// (tiles): the `rows` tiles of the shard's list from tile y0 on.
+static int net_band(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t sid, uint32_t y0, uint32_t rows, float level0,
+                    float voxel_m, bool accumulate, bool tiles)
+{
+    CtHandle_::NetScratch &s = h->net;
+    const uint32_t W = h->scene.width, npx = tiles ? 64u * rows : W * rows, n_pad = (npx + 255u) / 256u * 256u;
+    const uint32_t *const band_tiles = tiles ? s.tiles + y0 : nullptr;
     float4 *const direct = (p->transform & CT_NET_ADD_SINGLE_SCATTER) ? s.direct : nullptr;
     float ms = 0;
     HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-    HIPCHK(h, launch_first_scatter_frame(h->dev, 0u, y0, W, npx, sid, s.found, s.waves, npx, s.pos, s.dir, nullptr, direct,
-                                         h->stream));
+    HIPCHK(h, launch_first_scatter_frame(h->dev, 0u, tiles ? 0u : y0, W, npx, sid, s.found, s.waves, npx, s.pos, s.dir, nullptr, direct,
+                                         band_tiles, h->stream));
     HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
     uint32_t count = 0;
     HIPCHK(h, hipMemcpyAsync(&count, s.waves + n_pad / 64u, sizeof count, hipMemcpyDeviceToHost, h->stream));
@@ -3393,11 +3430,11 @@ static int net_band(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t 
         }
     }
     const NetCompose c{ p->transform & 0xff, p->rgb_scale[0], p->rgb_scale[1], p->rgb_scale[2] };
-    const size_t first_pixel = (size_t)y0 * W;
+    const size_t first_pixel = tiles ? 0 : (size_t)y0 * W;   // (the tile path writes at y * W + x of the whole frame)
     HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
     HIPCHK(h, launch_network_compose(s.found, s.waves, s.out, npx, c, accumulate ? nullptr : h->d_frame + first_pixel,
                                      h->d_mean + first_pixel, h->d_m2 + first_pixel, sid, h->stop_cadence ? h->d_freeze : nullptr,
-                                     direct, h->stream));
+                                     direct, band_tiles, h->dev.tiles_x, W, h->scene.height, h->stream));
     HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
     HIPCHK(h, hipEventSynchronize(h->ev[1]));
     HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
@@ -3408,10 +3445,11 @@ static int net_band(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t 
     return CT_OK;
 }
 
-// Subframes [first, first + count) band by band.  The caller has validated and flushed.
-static int net_run(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t first, uint32_t count, bool accumulate)
+// Subframes [first, first + count) band by band.  The caller has validated and flushed.  tiles: the bands are runs of the
+// shard's tile list (ct_network_render_shard_*) instead of rows; a frame is first filled with the shard's background.
+static int net_run(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t first, uint32_t count, bool accumulate, bool tiles)
 {
-    const uint32_t H = h->scene.height, rows = net_band_rows(h, p->band_pixels);
+    const uint32_t H = h->scene.height, rows = tiles ? net_band_tiles(p->band_pixels) : net_band_rows(h, p->band_pixels);
     // VDBCloud::getVoxelSizeInMeters / getVoxelSizeInTermsOfFreePath, as in ct_collect_descriptors
     const float maxs = (float)std::max(h->scene.dims[0], std::max(h->scene.dims[1], h->scene.dims[2]));
     const float voxel_m = h->scene.cloud_size_m / maxs;
@@ -3421,7 +3459,14 @@ static int net_run(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t f
         ms = 0;
     }
     auto run = [&]() -> int {
-        int rc = net_reserve(h, (size_t)h->scene.width * rows, (p->transform & CT_NET_ADD_SINGLE_SCATTER) != 0);
+        int rc = tiles ? net_ensure_tiles(h) : CT_OK;
+        if (rc != CT_OK) {
+            return rc;
+        }
+        // (bands of the row path run bottom to top over H rows; those of the tile path over the list's n_tiles tiles)
+        const uint32_t units = tiles ? h->net.n_tiles : H;
+        const size_t band = tiles ? (size_t)64 * std::min(rows, std::max(units, 1u)) : (size_t)h->scene.width * rows;
+        rc = net_reserve(h, band, (p->transform & CT_NET_ADD_SINGLE_SCATTER) != 0);
         if (rc == CT_OK) {
             rc = ensure_pyramid(h);
         }
@@ -3433,8 +3478,18 @@ static int net_run(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t f
         }
         for (uint32_t k = 0; k < count; k++) {
             const uint32_t sid = first + k;
-            for (uint32_t y0 = 0; y0 < H; y0 += rows) {
-                rc = net_band(h, n, p, sid, y0, std::min(rows, H - y0), level0, voxel_m, accumulate);
+            if (tiles && !accumulate) {
+                // the shard's background, as ct_render_subframe starts from it: the bands write the own pixels only
+                float ms = 0;
+                HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
+                HIPCHK(h, launch_fill_frame(h->d_frame, h->scene.width, H, h->scene.shard_index, h->scene.shard_count, h->stream));
+                HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
+                HIPCHK(h, hipEventSynchronize(h->ev[1]));
+                HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+                h->net.ms[3] += ms;
+            }
+            for (uint32_t y0 = 0; y0 < units; y0 += rows) {
+                rc = net_band(h, n, p, sid, y0, std::min(rows, units - y0), level0, voxel_m, accumulate, tiles);
                 if (rc != CT_OK) {
                     return rc;
                 }
@@ -3460,11 +3515,11 @@ static int net_run(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t f
     return rc;
 }
 
-extern "C" int ct_network_render_subframe(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t subframe_id, float *frame_rgba_dev)
+static int net_subframe(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t subframe_id, float *frame_rgba_dev, bool tiles)
 {
     NEED_NOFLUSH(h);
     // (arguments first: a rejected call leaves the handle exactly as it was, batches in flight included)
-    int rc = net_validate(h, n, p, "ct_network_render_subframe");
+    int rc = net_validate(h, n, p, tiles ? "ct_network_render_shard_subframe" : "ct_network_render_subframe", tiles);
     if (rc != CT_OK) {
         return rc;
     }
@@ -3478,7 +3533,7 @@ extern "C" int ct_network_render_subframe(CtHandle h, CtNetwork n, const CtNetwo
     if (rc != CT_OK) {
         return rc;
     }
-    rc = net_run(h, n, p, subframe_id, 1, false);
+    rc = net_run(h, n, p, subframe_id, 1, false, tiles);
     if (rc != CT_OK) {
         return rc;
     }
@@ -3490,15 +3545,27 @@ extern "C" int ct_network_render_subframe(CtHandle h, CtNetwork n, const CtNetwo
     return CT_OK;
 }
 
-extern "C" int ct_network_render_accumulate(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t first_subframe_id, uint32_t count)
+extern "C" int ct_network_render_subframe(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t subframe_id, float *frame_rgba_dev)
+{
+    return net_subframe(h, n, p, subframe_id, frame_rgba_dev, false);
+}
+
+extern "C" int ct_network_render_shard_subframe(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t subframe_id,
+                                                float *frame_rgba_dev)
+{
+    return net_subframe(h, n, p, subframe_id, frame_rgba_dev, true);
+}
+
+static int net_accumulate(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t first_subframe_id, uint32_t count, bool tiles)
 {
     NEED_NOFLUSH(h);
-    int rc = net_validate(h, n, p, "ct_network_render_accumulate");
+    const char *const who = tiles ? "ct_network_render_shard_accumulate" : "ct_network_render_accumulate";
+    int rc = net_validate(h, n, p, who, tiles);
     if (rc != CT_OK) {
         return rc;
     }
     if (first_subframe_id == 0 || count == 0) {
-        return fail(h, CT_E_INVAL, "ct_network_render_accumulate: subframe ids are 1-based and count must not be 0");
+        return fail(h, CT_E_INVAL, "%s: subframe ids are 1-based and count must not be 0", who);
     }
     if (!h->camera_set) {
         return fail(h, CT_E_STATE, "ct_set_camera has not been called");
@@ -3511,10 +3578,20 @@ extern "C" int ct_network_render_accumulate(CtHandle h, CtNetwork n, const CtNet
         return fail(h, CT_E_STATE, "first_subframe_id %u but %u subframes are accumulated", first_subframe_id, h->subframes);
     }
     if (count > 0xffffffffu - first_subframe_id + 1u) {
-        return fail(h, CT_E_INVAL, "ct_network_render_accumulate: %u subframes from %u on exceed the 32-bit subframe id", count,
-                    first_subframe_id);
+        return fail(h, CT_E_INVAL, "%s: %u subframes from %u on exceed the 32-bit subframe id", who, count, first_subframe_id);
     }
-    return net_run(h, n, p, first_subframe_id, count, true);
+    return net_run(h, n, p, first_subframe_id, count, true, tiles);
+}
+
+extern "C" int ct_network_render_accumulate(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t first_subframe_id, uint32_t count)
+{
+    return net_accumulate(h, n, p, first_subframe_id, count, false);
+}
+
+extern "C" int ct_network_render_shard_accumulate(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t first_subframe_id,
+                                                  uint32_t count)
+{
+    return net_accumulate(h, n, p, first_subframe_id, count, true);
 }
 
 extern "C" int ct_debug_network_aux(CtHandle h, const float *directions_dev, uint32_t count, float *aux_dev_out)
@@ -3540,6 +3617,23 @@ extern "C" int ct_debug_network_render_time(CtHandle h, double ms_out[4])
     for (int i = 0; i < 4; i++) {
         ms_out[i] = h->net.ms[i];
     }
+    return CT_OK;
+}
+
+extern "C" int ct_debug_network_scratch(CtHandle h, uint64_t out[12])
+{
+    NEED_NOFLUSH(h);
+    if (!out) {
+        return fail(h, CT_E_INVAL, "ct_debug_network_scratch: out is NULL");
+    }
+    const CtHandle_::NetScratch &s = h->net;
+    const void *ptrs[9] = { s.found, s.waves, s.pos, s.dir, s.aux, s.out, s.desc, s.direct, s.tiles };
+    for (int i = 0; i < 9; i++) {
+        out[i] = (uint64_t)(uintptr_t)ptrs[i];
+    }
+    out[9] = s.band_cap;
+    out[10] = s.desc_cap;
+    out[11] = s.direct_cap;
     return CT_OK;
 }
 
@@ -4276,4 +4370,27 @@ extern "C" int ct_debug_cdf_inversion(CtHandle h, uint32_t first_u24, uint32_t c
 extern "C" uint32_t ct_tile_owner(uint32_t tile_x, uint32_t tile_y, uint32_t shard_count)
 {
     return tile_owner(tile_x, tile_y, shard_count);
+}
+
+extern "C" int ct_shard_tiles(uint32_t width, uint32_t height, uint32_t shard_index, uint32_t shard_count, uint32_t *tiles_out,
+                              uint32_t capacity, uint32_t *count_out)
+{
+    if (width == 0 || height == 0 || shard_count == 0 || shard_index >= shard_count || !count_out) {
+        return CT_E_INVAL;
+    }
+    const uint32_t tiles_x = (width + kTile - 1) / kTile, tiles_y = (height + kTile - 1) / kTile;
+    uint32_t count = 0;
+    for (uint32_t ty = 0; ty < tiles_y; ty++) {
+        for (uint32_t tx = 0; tx < tiles_x; tx++) {
+            if (tile_owner(tx, ty, shard_count) != shard_index) {
+                continue;
+            }
+            if (tiles_out && count < capacity) {
+                tiles_out[count] = ty * tiles_x + tx;
+            }
+            count++;
+        }
+    }
+    *count_out = count;
+    return tiles_out && count > capacity ? CT_E_INVAL : CT_OK;
 }

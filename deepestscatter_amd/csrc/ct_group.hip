@@ -25,6 +25,7 @@
 #include <set>
 #include <mutex>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../include/cloudtrace.h"
@@ -323,6 +324,87 @@ extern "C" int ct_group_render_accumulate(CtGroup g, uint32_t first_subframe_id,
     }
     g->subframes = first_subframe_id + count - 1;
     g->merged = false;
+    return CT_OK;
+}
+
+// ---- the scattering network on a group ---------------------------------------------------------------------------------
+struct CtGroupNetwork_ {
+    CtGroup group = nullptr;
+    std::vector<CtNetwork> nets;   // per shard, on its device
+};
+
+extern "C" int ct_group_network_destroy(CtGroupNetwork gn)
+{
+    if (!gn) {
+        return CT_OK;
+    }
+    for (CtNetwork n : gn->nets) {
+        ct_network_destroy(n);
+    }
+    delete gn;
+    return CT_OK;
+}
+
+extern "C" int ct_group_network_create(CtGroup g, const CtNetworkDesc *d, CtGroupNetwork *out)
+{
+    if (!g) {
+        return gfail(nullptr, CT_E_INVAL, "null group");
+    }
+    if (!out) {
+        return gfail(g, CT_E_INVAL, "ct_group_network_create: out is NULL");
+    }
+    *out = nullptr;
+    CtGroupNetwork gn = new (std::nothrow) CtGroupNetwork_();
+    if (!gn) {
+        return gfail(g, CT_E_NOMEM, "out of host memory");
+    }
+    gn->group = g;
+    for (uint32_t i = 0; i < g->handles.size(); i++) {
+        CtNetwork n = nullptr;
+        const int rc = ct_network_create(g->handles[i], d, &n);
+        if (rc != CT_OK) {
+            ct_group_network_destroy(gn);
+            return shard_fail(g, i, rc);
+        }
+        gn->nets.push_back(n);
+    }
+    *out = gn;
+    return CT_OK;
+}
+
+// ct_network_render_shard_accumulate waits for every band's record count, so the devices only work at the same time when every
+// shard has a host thread: shards 1 .. N-1 on threads of this call, shard 0 on the caller.  Handles are independent, every
+// entry point selects its device on the thread it is called on, and a handle's error message is its own.
+extern "C" int ct_group_network_render_accumulate(CtGroup g, CtGroupNetwork gn, const CtNetworkRender *p, uint32_t first_subframe_id,
+                                                  uint32_t count)
+{
+    if (!g) {
+        return gfail(nullptr, CT_E_INVAL, "null group");
+    }
+    if (!gn || gn->group != g || gn->nets.size() != g->handles.size()) {
+        return gfail(g, CT_E_INVAL, "ct_group_network_render_accumulate: need a CtGroupNetwork of this group");
+    }
+    const uint32_t shards = (uint32_t)g->handles.size();
+    std::vector<int> codes(shards, CT_OK);
+    auto shard = [&](uint32_t i) {
+        codes[i] = ct_network_render_shard_accumulate(g->handles[i], gn->nets[i], p, first_subframe_id, count);
+    };
+    std::vector<std::thread> threads;
+    threads.reserve(shards);
+    for (uint32_t i = 1; i < shards; i++) {
+        threads.emplace_back(shard, i);
+    }
+    shard(0);
+    for (std::thread &t : threads) {
+        t.join();
+    }
+    g->merged = false;
+    for (uint32_t i = 0; i < shards; i++) {
+        if (codes[i] != CT_OK) {
+            return shard_fail(g, i, codes[i]);
+        }
+    }
+    g->subframes = first_subframe_id + count - 1;
     return CT_OK;
 }
 

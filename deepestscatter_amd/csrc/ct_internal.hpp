@@ -207,13 +207,18 @@ hipError_t launch_scatter_samples(const DevScene &sc, uint32_t count, uint32_t b
 // afterwards the waves' offsets and, in the last word, the number of records; positions / directions hold `capacity` records,
 // pixels may be NULL.  direct != NULL ((n rounded up to 256) float4): the flight also stores, by rect pixel, the single-scatter
 // term of its collision (CT_NET_ADD_SINGLE_SCATTER), zeros where the pixel has no record.
+// tiles != NULL (device, n / 64 entries, ty * tiles_x + tx each): the n lanes are those 8x8 tiles, one wave per tile, lane l of
+// a tile its pixel (l & 7, l >> 3); x0, y0 and w are unused, lanes that the frame clips are never valid, and found, direct and
+// the counts are indexed by lane.
 hipError_t launch_first_scatter_frame(const DevScene &sc, uint32_t x0, uint32_t y0, uint32_t w, uint32_t n, uint32_t subframe_id,
                                       float4 *found, uint32_t *wave_counts, uint32_t capacity, float *positions, float *directions,
-                                      uint32_t *pixels, float4 *direct, hipStream_t stream);
+                                      uint32_t *pixels, float4 *direct, const uint32_t *tiles, hipStream_t stream);
 // ct_network_render_*: aux[i] = dot(directions[i], l), left to right; and the pixels of a band of n pixels (whole rows) from the
 // flight's temporary, the scanned wave counts and the network's outputs of the band's records.  frame != NULL: the pixels are
 // stored there (the band's first pixel); frame == NULL: they go into the Welford update of mean / m2 (the band's first pixel)
 // with n = subframe_id, unless *frozen.  direct != NULL: the flight's single-scatter temporary, added to the pixels with a record.
+// tiles != NULL: the n lanes are the tiles of launch_first_scatter_frame's tile form; frame / mean / m2 are then the whole
+// frame's (width x height, tiles_x tiles per row) and only the pixels of those tiles are written.
 struct NetCompose {
     int32_t transform;   // CT_NET_OUT_* (the low byte of CtNetworkRender::transform)
     float sr, sg, sb;    // rgb_scale
@@ -221,7 +226,8 @@ struct NetCompose {
 hipError_t launch_network_aux(const float *directions, uint32_t count, float lx, float ly, float lz, float *aux, hipStream_t stream);
 hipError_t launch_network_compose(const float4 *found, const uint32_t *wave_offsets, const float *out, uint32_t n, const NetCompose &c,
                                   float4 *frame, float4 *mean, float4 *m2, uint32_t subframe_id, const uint32_t *frozen,
-                                  const float4 *direct, hipStream_t stream);
+                                  const float4 *direct, const uint32_t *tiles, uint32_t tiles_x, uint32_t width, uint32_t height,
+                                  hipStream_t stream);
 // Density pyramid (Resources::generateMipmaps) and the descriptor gather.
 constexpr int kMaxMipLevels = 16;
 struct MipPyramid {

@@ -3041,8 +3041,12 @@ hipError_t launch_scatter_samples(const DevScene &sc, uint32_t count, uint32_t b
 // un-chopped Mie table -- singleScatterSunRadiance's value for this pixel and subframe, render_simple_kernel's mode 2 -- at the
 // flight's own end position (texture space: the world position of the record plus the half box does not round back to it) and
 // keeps it in a second temporary, 16 bytes per rect pixel, (0, 0, 0) where there is no record.
+// TILES (ct_network_render_shard_*): the lanes are not a rect but a run of 8x8 tiles of the shard's tile list, one wave per
+// tile -- render_simple_kernel's map -- so a wave's 64 flights are one tile's and a shard pays for no foreign pixel.  A lane
+// of a tile that the frame clips has no pixel: it is never valid, its `found` says so, and nothing else is stored for it.
 struct FrameRect {
-    uint32_t x0, y0, w, n;   // origin, row length and pixel count of the rect
+    uint32_t x0, y0, w, n;   // origin, row length and pixel count of the rect; TILES: n = 64 * tiles, the rest unused
+    const uint32_t *tiles;   // TILES: the band's tiles, ty * tiles_x + tx each
 };
 
 // pixel i of the rect, row-major
@@ -3052,7 +3056,29 @@ CT_DEV void rect_pixel(const FrameRect &r, uint32_t i, uint32_t &x, uint32_t &y)
     y = r.y0 + i / r.w;
 }
 
-template <bool FIXED8, bool DIRECT>
+// lane i (< 64 * tiles) of a run of tiles: false where the frame clips the tile
+CT_DEV bool tile_pixel(const uint32_t *__restrict__ tiles, uint32_t tiles_x, uint32_t width, uint32_t height, uint32_t i, uint32_t &x,
+                       uint32_t &y)
+{
+    const uint32_t tile = tiles[i >> 6], l = i & 63u;
+    const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    x = tx * kTile + (l & 7u);
+    y = ty * kTile + (l >> 3);
+    return x < width && y < height;
+}
+
+template <bool TILES>
+CT_DEV bool band_pixel(const DevScene &sc, const FrameRect &r, uint32_t i, uint32_t &x, uint32_t &y)
+{
+    if constexpr (TILES) {
+        return tile_pixel(r.tiles, sc.tiles_x, sc.width, sc.height, i, x, y);
+    } else {
+        rect_pixel(r, i, x, y);
+        return true;
+    }
+}
+
+template <bool FIXED8, bool DIRECT, bool TILES>
 __global__ __launch_bounds__(256) void first_scatter_frame_kernel(DevScene sc, FrameRect r, uint32_t subframe_id,
                                                                  float4 *__restrict__ found, uint32_t *__restrict__ wave_counts,
                                                                  float4 *__restrict__ direct)
@@ -3063,11 +3089,11 @@ __global__ __launch_bounds__(256) void first_scatter_frame_kernel(DevScene sc, F
     f3 sun = mk3(0, 0, 0);
     if (i < r.n) {
         uint32_t x, y;
-        rect_pixel(r, i, x, y);
+        const bool pixel = band_pixel<TILES>(sc, r, i, x, y);
         const f3 eye = mk3(sc.ex, sc.ey, sc.ez);
         const f3 d = primary_direction(sc, x, y);
         float t_hit = 0;
-        if (intersect_box(sc, eye, d, t_hit)) {
+        if (pixel && intersect_box(sc, eye, d, t_hit)) {
             f3 pos = add3(eye, scale3(d, t_hit));                       // cloudRadianceMaterials.cu:11
             pos = add3(pos, scale3(mk3(sc.bx, sc.by, sc.bz), 0.5f));    // :12
             const f3 dir = normalize3(d);                               // :17
@@ -3123,6 +3149,7 @@ __global__ __launch_bounds__(1024) void first_scatter_scan_kernel(uint32_t *__re
     }
 }
 
+template <bool TILES>
 __global__ __launch_bounds__(256) void first_scatter_compact_kernel(DevScene sc, FrameRect r, const float4 *__restrict__ found,
                                                                    const uint32_t *__restrict__ wave_offsets, uint32_t capacity,
                                                                    float *__restrict__ positions, float *__restrict__ directions,
@@ -3144,7 +3171,7 @@ __global__ __launch_bounds__(256) void first_scatter_compact_kernel(DevScene sc,
         return;
     }
     uint32_t x, y;
-    rect_pixel(r, i, x, y);
+    (void)band_pixel<TILES>(sc, r, i, x, y);                  // (a valid lane has a pixel)
     const f3 dir = normalize3(primary_direction(sc, x, y));   // d2, as first_scatter_frame_kernel made it
     positions[3 * slot + 0] = f.x; positions[3 * slot + 1] = f.y; positions[3 * slot + 2] = f.z;
     directions[3 * slot + 0] = dir.x; directions[3 * slot + 1] = dir.y; directions[3 * slot + 2] = dir.z;
@@ -3155,15 +3182,21 @@ __global__ __launch_bounds__(256) void first_scatter_compact_kernel(DevScene sc,
 
 hipError_t launch_first_scatter_frame(const DevScene &sc, uint32_t x0, uint32_t y0, uint32_t w, uint32_t n, uint32_t subframe_id,
                                       float4 *found, uint32_t *wave_counts, uint32_t capacity, float *positions, float *directions,
-                                      uint32_t *pixels, float4 *direct, hipStream_t stream)
+                                      uint32_t *pixels, float4 *direct, const uint32_t *tiles, hipStream_t stream)
 {
-    const FrameRect r{ x0, y0, w, n };
+    const FrameRect r{ x0, y0, w, n, tiles };
     const uint32_t blocks = (n + 255u) / 256u;
-    auto flight = first_scatter_frame_kernel<false, false>;
-    if (direct) {
-        flight = sc.tex_fixed8 ? first_scatter_frame_kernel<true, true> : first_scatter_frame_kernel<false, true>;
+    auto flight = first_scatter_frame_kernel<false, false, false>;
+    if (tiles) {
+        if (direct) {
+            flight = sc.tex_fixed8 ? first_scatter_frame_kernel<true, true, true> : first_scatter_frame_kernel<false, true, true>;
+        } else {
+            flight = sc.tex_fixed8 ? first_scatter_frame_kernel<true, false, true> : first_scatter_frame_kernel<false, false, true>;
+        }
+    } else if (direct) {
+        flight = sc.tex_fixed8 ? first_scatter_frame_kernel<true, true, false> : first_scatter_frame_kernel<false, true, false>;
     } else if (sc.tex_fixed8) {
-        flight = first_scatter_frame_kernel<true, false>;
+        flight = first_scatter_frame_kernel<true, false, false>;
     }
     hipLaunchKernelGGL(flight, dim3(blocks), dim3(256), 0, stream, sc, r, subframe_id, found, wave_counts, direct);
     hipError_t e = hipGetLastError();
@@ -3175,8 +3208,8 @@ hipError_t launch_first_scatter_frame(const DevScene &sc, uint32_t x0, uint32_t 
     if (e != hipSuccess) {
         return e;
     }
-    hipLaunchKernelGGL(first_scatter_compact_kernel, dim3(blocks), dim3(256), 0, stream, sc, r, found, wave_counts, capacity, positions,
-                       directions, pixels);
+    auto compact = tiles ? first_scatter_compact_kernel<true> : first_scatter_compact_kernel<false>;
+    hipLaunchKernelGGL(compact, dim3(blocks), dim3(256), 0, stream, sc, r, found, wave_counts, capacity, positions, directions, pixels);
     return hipGetLastError();
 }
 
@@ -3215,13 +3248,21 @@ hipError_t launch_network_aux(const float *directions, uint32_t count, float lx,
 // test included); otherwise into the frame.
 // DIRECT (CT_NET_ADD_SINGLE_SCATTER): a pixel with a record gets the flight's single-scatter term, read by pixel index, added
 // behind the scaled network output (the product is rounded first: the build has no contraction).
-template <bool ACCUMULATE, bool DIRECT>
+// TILES (ct_network_render_shard_*): lane i is a lane of the band's run of tiles (tile_pixel), found / direct / the wave offsets
+// are indexed by lane as before, and frame / mean / m2 are the whole frame's, written at y * width + x.  A clipped lane writes
+// nothing, and no lane belongs to a foreign tile, so foreign pixels keep what they hold.
+struct TileBand {
+    const uint32_t *tiles;   // the band's tiles, ty * tiles_x + tx each
+    uint32_t tiles_x, width, height;
+};
+
+template <bool ACCUMULATE, bool DIRECT, bool TILES>
 __global__ __launch_bounds__(256) void network_compose_kernel(const float4 *__restrict__ found, const uint32_t *__restrict__ wave_offsets,
                                                               const float *__restrict__ out, uint32_t n, NetCompose c,
                                                               float4 *__restrict__ frame, float4 *__restrict__ mean,
                                                               float4 *__restrict__ m2, uint32_t subframe_id,
                                                               const uint32_t *__restrict__ frozen,
-                                                              const float4 *__restrict__ direct)
+                                                              const float4 *__restrict__ direct, TileBand tb)
 {
     if (ACCUMULATE && frozen && *frozen != 0u) {
         return;   // the image has converged (converged_freeze_kernel): the running mean stays as it is
@@ -3235,6 +3276,14 @@ __global__ __launch_bounds__(256) void network_compose_kernel(const float4 *__re
     const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
     if (i >= n) {
         return;
+    }
+    size_t at = i;
+    if constexpr (TILES) {
+        uint32_t x, y;
+        if (!tile_pixel(tb.tiles, tb.tiles_x, tb.width, tb.height, i, x, y)) {
+            return;
+        }
+        at = (size_t)y * tb.width + x;
     }
     float4 v = make_float4(0.f, 0.f, 0.f, 1.f);   // the miss value of ct_render_subframe
     if (valid) {
@@ -3250,28 +3299,36 @@ __global__ __launch_bounds__(256) void network_compose_kernel(const float4 *__re
         }
     }
     if (ACCUMULATE) {
-        float4 mu = mean[i], var = m2[i];
+        float4 mu = mean[at], var = m2[at];
         welford(mu, var, v, subframe_id);
-        mean[i] = mu;
-        m2[i] = var;
+        mean[at] = mu;
+        m2[at] = var;
     } else {
-        frame[i] = v;
+        frame[at] = v;
     }
 }
 
 hipError_t launch_network_compose(const float4 *found, const uint32_t *wave_offsets, const float *out, uint32_t n, const NetCompose &c,
                                   float4 *frame, float4 *mean, float4 *m2, uint32_t subframe_id, const uint32_t *frozen,
-                                  const float4 *direct, hipStream_t stream)
+                                  const float4 *direct, const uint32_t *tiles, uint32_t tiles_x, uint32_t width, uint32_t height,
+                                  hipStream_t stream)
 {
     const uint32_t blocks = (n + 255u) / 256u;
+    const TileBand tb{ tiles, tiles_x, width, height };
     if (frame) {
-        auto compose = direct ? network_compose_kernel<false, true> : network_compose_kernel<false, false>;
+        auto compose = direct ? network_compose_kernel<false, true, false> : network_compose_kernel<false, false, false>;
+        if (tiles) {
+            compose = direct ? network_compose_kernel<false, true, true> : network_compose_kernel<false, false, true>;
+        }
         hipLaunchKernelGGL(compose, dim3(blocks), dim3(256), 0, stream, found, wave_offsets, out, n, c, frame, (float4 *)nullptr,
-                           (float4 *)nullptr, subframe_id, (const uint32_t *)nullptr, direct);
+                           (float4 *)nullptr, subframe_id, (const uint32_t *)nullptr, direct, tb);
     } else {
-        auto compose = direct ? network_compose_kernel<true, true> : network_compose_kernel<true, false>;
+        auto compose = direct ? network_compose_kernel<true, true, false> : network_compose_kernel<true, false, false>;
+        if (tiles) {
+            compose = direct ? network_compose_kernel<true, true, true> : network_compose_kernel<true, false, true>;
+        }
         hipLaunchKernelGGL(compose, dim3(blocks), dim3(256), 0, stream, found, wave_offsets, out, n, c, (float4 *)nullptr, mean, m2,
-                           subframe_id, frozen, direct);
+                           subframe_id, frozen, direct, tb);
     }
     return hipGetLastError();
 }

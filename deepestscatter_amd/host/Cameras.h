@@ -88,24 +88,31 @@ namespace DeepestScatter
     // (ct_network_render_subframe / ct_network_render_accumulate) instead of the estimator.  It keeps the path tracer's scene
     // set-up (init) and output name; the network lives on the context's handle and goes before it.  params.transform may
     // carry CT_NET_ADD_SINGLE_SCATTER (--net-direct): both entry points then add the sun's single-scatter term to the frame.
+    // With --gpus the context is a group: one network per shard (ct_group_network_create), every shard renders its own tiles
+    // (ct_group_network_render_accumulate), and the group's merge, tonemap and convergence test apply as for the estimator.
     class NetworkRenderer : public PathTracingRenderer
     {
     public:
         NetworkRenderer(std::shared_ptr<Context> context, std::shared_ptr<const NetworkFile> file, const CtNetworkRender& params)
             : PathTracingRenderer(std::move(context)), file(std::move(file)), params(params) {}
-        ~NetworkRenderer() override { if (network) ct_network_destroy(network); }
+        ~NetworkRenderer() override
+        {
+            if (network) ct_network_destroy(network);
+            if (groupNetwork) ct_group_network_destroy(groupNetwork);
+        }
 
         void init() override
         {
-            if (context->devices.size() > 1) throw std::runtime_error("--network renders on one GPU only (a sharded network frame is not implemented)");
             PathTracingRenderer::init();
-            if (network) return;
+            if (network || groupNetwork) return;
             CtNetworkDesc d{ CT_ABI_VERSION, file->blocks, file->width, file->aux, file->headLayers, file->weights.data(), file->weights.size() };
-            Context::check(ct_network_create(context->handle, &d, &network), context->handle, "ct_network_create");
+            if (context->group) Context::checkGroup(ct_group_network_create(context->group, &d, &groupNetwork), context->group, "ct_group_network_create");
+            else Context::check(ct_network_create(context->handle, &d, &network), context->handle, "ct_network_create");
         }
 
         void render(float* frameResultBuffer) override
         {
+            if (context->group) throw std::runtime_error("the two-launch loop (--unfused) renders on one GPU only");
             applyCamera();
             Context::check(ct_network_render_subframe(context->handle, network, &params, subframeId, frameResultBuffer), context->handle,
                            "ct_network_render_subframe");
@@ -114,6 +121,12 @@ namespace DeepestScatter
         void renderAccumulate(uint32_t first, uint32_t count, bool /*enqueue: every band waits for its record count*/) override
         {
             applyCamera();
+            if (context->group)
+            {
+                Context::checkGroup(ct_group_network_render_accumulate(context->group, groupNetwork, &params, first, count), context->group,
+                                    "ct_group_network_render_accumulate");
+                return;
+            }
             Context::check(ct_network_render_accumulate(context->handle, network, &params, first, count), context->handle,
                            "ct_network_render_accumulate");
         }
@@ -122,6 +135,7 @@ namespace DeepestScatter
         std::shared_ptr<const NetworkFile> file;
         CtNetworkRender params;
         CtNetwork network = nullptr;
+        CtGroupNetwork groupNetwork = nullptr;   // with --gpus: one network per shard, destroyed before the group
     };
 
     class Camera : public SceneItem                                              // Camera.h:16-103

@@ -9,7 +9,8 @@
 //              [--tex-fixed8]   filter weights in 1.8 fixed point like the reference's texture unit (CT_FLAG_TEX_FIXED8)
 //              [--gpus N | --gpus a,b,c]   one process, one shard of 8x8-pixel tiles per GPU, RCCL reduce of [mean | M2] (ct_group_*)
 //              [--network FILE [--net-transform linear|expm1] [--net-scale r,g,b] [--net-direct]]   the job's subframes come from
-//                               the scattering network in FILE (NetworkFile.h; ct_network_render_accumulate) instead of the
+//                               the scattering network in FILE (NetworkFile.h; ct_network_render_accumulate, with --gpus
+//                               ct_group_network_render_accumulate: every GPU renders its own tiles) instead of the
 //                               estimator; --net-direct adds the sun's single-scatter term (CT_NET_ADD_SINGLE_SCATTER), so that a
 //                               network trained on the multiple-scatter labels gives the picture --mode total gives
 //   <cloud> = file.vdb | procedural:<N>[:<seed>] | file.f32grid
@@ -290,7 +291,7 @@ int main(int argc, char* argv[])
     try
     {
         Options opt;
-        if (argc < 2) { std::cerr << "usage: cloudtrace <cloud> [--size WxH] [--spp N] [--mode total|multi|single] [--light L] [--size-m M] [--out DIR] [--data DIR] [--unfused] [--display] [--estimator march|delta] [--format exr|pfm] [--gpus N|a,b,c] [--tex-fixed8] [--network FILE [--net-transform linear|expm1] [--net-scale r,g,b] [--net-direct]]\n"; return 2; }
+        if (argc < 2) { std::cerr << "usage: cloudtrace <cloud> [--size WxH] [--spp N] [--mode total|multi|single] [--light L] [--size-m M] [--out DIR] [--data DIR] [--unfused] [--display] [--estimator march|delta] [--format exr|pfm] [--gpus N|a,b,c] [--tex-fixed8] [--network FILE [--net-transform linear|expm1] [--net-scale r,g,b] [--net-direct]] (--network with --gpus: every GPU renders its own tiles)\n"; return 2; }
         int first = 2;
         bool lightsGiven = false;
         opt.cloud = argv[1];
@@ -375,7 +376,6 @@ int main(int argc, char* argv[])
         if (!opt.networkPath.empty())
         {
             // read and checked against the header's formula here, before a renderer exists: a malformed file costs no device
-            if (opt.devices.size() > 1) throw std::invalid_argument("--network renders on one GPU only");
             opt.network = std::make_shared<const NetworkFile>(NetworkFile::load(opt.networkPath));
             if (opt.network->aux != 1) throw std::invalid_argument("--network: the renderer feeds one aux input (the light angle); this network has " + std::to_string(opt.network->aux));
         }

@@ -529,8 +529,8 @@ CT_API float ct_debug_bf16_round(float x);
  * CT_E_INVAL: a NULL handle (answered without a device), network or params; a wrong abi_version; an unknown transform (a low
  * byte that is no CT_NET_OUT_* value, or any bit set above it other than CT_NET_ADD_SINGLE_SCATTER); an rgb_scale that is not
  * finite; a network with aux != 1; a network on another device than h; a handle created with
- * shard_count > 1 (a sharded frame is out of scope here: ct_descriptor_frame ignores shards, and splitting a frame by rects
- * over a CtGroup is a later change); subframe_id == 0; count == 0.  CT_E_STATE: no camera pose (ct_create sets the default
+ * shard_count > 1 (a shard renders its tiles with ct_network_render_shard_* below, a CtGroup with
+ * ct_group_network_render_accumulate); subframe_id == 0; count == 0.  CT_E_STATE: no camera pose (ct_create sets the default
  * one, so a live handle always has one); ct_network_render_accumulate with first_subframe_id != subframes + 1, as
  * ct_render_accumulate.  Arguments are checked before anything of the handle changes.
  * Both wait for the batches in flight, run on the handle's stream and return when it is idle. */
@@ -557,6 +557,38 @@ CT_API int ct_network_render_subframe(CtHandle h, CtNetwork n, const CtNetworkRe
  * float4 frame is not materialised -- the kernel that forms a band's pixels applies the Welford update to mean and M2
  * directly -- and CT_BUF_FRAME is left alone.  Like ct_accumulate it drops the samples rendered ahead. */
 CT_API int ct_network_render_accumulate(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t first_subframe_id, uint32_t count);
+
+/* The same renderer on a handle of any shard_count >= 1: the frame of THIS SHARD, as ct_render_subframe leaves a shard's frame.
+ *
+ * Definition.  A pixel of a tile the shard owns (ct_tile_owner) is exactly the pixel defined above -- same flight, seed, record,
+ * aux, output, transform, single-scatter term -- so on a shard_count == 1 handle the two entry points give the bits of
+ * ct_network_render_subframe / ct_network_render_accumulate.  A foreign pixel of the frame is (0, 0, 0, 0); foreign pixels of
+ * mean and M2 are never touched and stay exactly 0, so a SUM over the shards is the unsharded image bit for bit and
+ * ct_group_merge, ct_group_tonemap and ct_group_is_converged apply unchanged.
+ *
+ * Bands.  The shard's tiles are taken in ascending ty * tiles_x + tx (ct_shard_tiles; the list is built on the device on first
+ * use and freed by ct_destroy).  A band is a run of at most max(1, band_pixels / 64) consecutive tiles of that list, at most
+ * 2^14 (band_pixels == 0 or > 2^20: 2^14), one wave per tile: lane l of a tile is its pixel (l & 7, l >> 3), and a lane
+ * the frame clips has no pixel.  A wave's 64 flights are therefore one tile's, and a shard spends nothing on foreign pixels.
+ * The passes of a band, the ranking by ballot (one count per tile), "no scatter, no atomics" and "the image does not depend on
+ * band_pixels" are as above; records reach gather and network in tile order.  ct_network_render_shard_subframe first fills the
+ * frame with the shard's background -- (0, 0, 0, 1) on own pixels, (0, 0, 0, 0) on foreign ones -- and the bands then write
+ * the own pixels.
+ *
+ * Scratch is the same scratch, shared with the two entry points above and sized in lanes (64 per tile of a band); the
+ * tile list is allocated with it, before the call's first kernel.  Errors, their order, "arguments checked before anything
+ * changes", the samples rendered ahead, ct_set_stop_when_converged (which refuses shards itself) and the stages of
+ * ct_debug_network_render_time (the background fill counts to [3]) are those of the two entry points above, except that
+ * shard_count > 1 is accepted.  Both are synchronous: every band waits for its record count, so the shards of a job only work
+ * at the same time when each is driven by its own host thread (ct_group_network_render_accumulate does that). */
+CT_API int ct_network_render_shard_subframe(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t subframe_id, float *frame_rgba_dev);
+CT_API int ct_network_render_shard_accumulate(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t first_subframe_id, uint32_t count);
+
+/* Diagnostic: the scratch of the network renderer as the handle holds it now: out[0 .. 8] = the device addresses of the
+ * per-lane temporary, the wave counts, positions, directions, aux, out, the descriptor array, the single-scatter temporary and
+ * the shard's tile list (0 = not allocated), out[9 .. 11] = the capacities in lanes of the band arrays, in records of the
+ * descriptor array, in lanes of the single-scatter temporary.  A warm call leaves all twelve as they were. */
+CT_API int ct_debug_network_scratch(CtHandle h, uint64_t out[12]);
 
 /* Diagnostic: the aux kernel of the two entry points above on caller-supplied directions: aux_dev_out[i] = d.x * l.x + d.y * l.y +
  * d.z * l.z for d = directions_dev[3 i .. 3 i + 2] and the handle's light.  count == 0: CT_OK, nothing read or written.
@@ -750,6 +782,19 @@ CT_API int ct_group_tonemap(CtGroup g, float exposure, uint8_t *rgba_host, float
 CT_API int ct_group_is_converged(CtGroup g, int32_t *converged_out, uint64_t *unconverged_pixels_out);
 CT_API int ct_group_counters(CtGroup g, CtCounters *out);              /* sums over the shards */
 
+/* The scattering network on a group: one CtNetwork per shard handle, on that shard's device, from one description
+ * (ct_network_create's rules and errors; the first failing shard's code and message are the group's).  Destroy it BEFORE the
+ * group.  ct_group_network_render_accumulate is ct_network_render_shard_accumulate(first_subframe_id, count) on every shard --
+ * shards 1 .. N-1 each on a host thread of their own, shard 0 on the caller, because the entry point is synchronous -- and
+ * returns when all have finished; the first failing shard's code and message are reported then.  Like
+ * ct_group_render_accumulate it sets the group's subframe count and invalidates the merge.  CT_E_INVAL: a NULL argument, a gn
+ * that belongs to another group. */
+typedef struct CtGroupNetwork_ *CtGroupNetwork;
+CT_API int ct_group_network_create(CtGroup g, const CtNetworkDesc *d, CtGroupNetwork *out);
+CT_API int ct_group_network_destroy(CtGroupNetwork gn);   /* NULL is a no-op */
+CT_API int ct_group_network_render_accumulate(CtGroup g, CtGroupNetwork gn, const CtNetworkRender *p, uint32_t first_subframe_id,
+                                              uint32_t count);
+
 /* ---- host-side helpers of the same path (pure CPU, no handle, no GPU) ------------------- */
 
 /* sutil::calculateCameraVariables(..., fov_is_vertical=false), src/Util/sutil.cpp:501-524, as
@@ -784,6 +829,13 @@ CT_API int ct_generate_mipmaps(const uint8_t *level0_host, const uint32_t dims[3
  * into 8x8-pixel tiles; tile (tx,ty) belongs to shard (tx + 3*ty) mod shard_count, a skewed
  * interleave that gives every GPU the same mix of cloud and background. */
 CT_API uint32_t ct_tile_owner(uint32_t tile_x, uint32_t tile_y, uint32_t shard_count);
+
+/* The tiles of shard `shard_index` of `shard_count` of a width x height frame, as ty * tiles_x + tx (tiles_x = ceil(width / 8)),
+ * ascending: the order ct_network_render_shard_* takes them in.  *count_out = their number; tiles_out == NULL queries it.
+ * CT_E_INVAL: an empty frame, shard_count == 0, shard_index >= shard_count, count_out == NULL, or capacity < the count (the
+ * first `capacity` tiles are written and *count_out is set all the same). */
+CT_API int ct_shard_tiles(uint32_t width, uint32_t height, uint32_t shard_index, uint32_t shard_count, uint32_t *tiles_out,
+                          uint32_t capacity, uint32_t *count_out);
 
 /* Synthetic cloud of SURVEY section 8(d): 5-octave gradient-noise fBm x ellipsoidal falloff,
  * thresholded, quantised by ct_quantize_volume's rule into an n^3 texture (payload n-2). */

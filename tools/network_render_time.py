@@ -10,8 +10,13 @@
 --direct: what CT_NET_ADD_SINGLE_SCATTER costs.  Lines 1 and 2 are measured twice in the same run, the calls without and with
 the flag taking turns, and printed twice ("direct": false, then true); line 1 also carries the smallest and largest
 first-flight time of its repeats, the spread the difference has to be read against.
-Needs a GPU.  Prints three JSON lines (five with --direct).
-    python tools/network_render_time.py [--repeats 5] [--volume 512] [--size 1024] [--subframes 16] [--band 0] [--direct]"""
+--shards N [N ...]: what N GPUs could reach, measured on one (as profiles/r03l measured strong scaling): instead of lines 2 and
+3, the tile path (ct_network_render_shard_subframe) of the unsharded handle against the row path of line 1 -- an 8 x 8 wave
+against a 64 x 1 one -- and then, for every N, each of the N shards rendered in turn on a handle of its own (records, the four
+stage times, wall time) and the slowest shard against the row-path call of the same run: the speedup N GPUs could reach.
+Needs a GPU.  Prints three JSON lines (five with --direct; with --shards 2 + sum(N) + len(N)).
+    python tools/network_render_time.py [--repeats 5] [--volume 512] [--size 1024] [--subframes 16] [--band 0] [--direct]
+                                        [--shards 2 4 8]"""
 import argparse, json, statistics, sys, time
 from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
@@ -32,6 +37,7 @@ if __name__ == "__main__":
     ap.add_argument("--subframes", type=int, default=16)
     ap.add_argument("--band", type=int, default=0)
     ap.add_argument("--direct", action="store_true")
+    ap.add_argument("--shards", type=int, nargs="+", default=[])
     a = ap.parse_args()
     import torch
     import deepestscatter_amd as ds
@@ -58,6 +64,44 @@ if __name__ == "__main__":
             flights = [s[0] for s in stages[f][1:]]
             line.update({"direct": f, "flights_and_compaction_ms_min": min(flights), "flights_and_compaction_ms_max": max(flights)})
         print(json.dumps(line), flush=True)
+
+    if a.shards:
+        direct = a.direct
+        row = {n: med([s[k] for s in stages[direct][1:]]) for k, n in enumerate(names)}
+        row_wall = med(wall[direct][1:])
+        pixels = tr.descriptor_frame(1)[3].cpu().numpy()
+
+        def shard_call(t, n):
+            """-> (median wall ms, median stage times) of warm ct_network_render_shard_subframe calls on tracer t"""
+            w, st = [], []
+            for i in range(a.repeats + 1):
+                w.append(wall_ms(lambda: t.network_render_shard_subframe(n, 1, band_pixels=a.band, out=False, direct=direct)))
+                st.append(t.network_render_time())
+            return med(w[1:]), {name: med([x[k] for x in st[1:]]) for k, name in enumerate(names)}
+
+        tile_wall, tile = shard_call(tr, net)
+        print(json.dumps({"route": "ct_network_render_shard_subframe", **common, "direct": direct, "shard": [0, 1], "records": records,
+                          "wall_ms": tile_wall, **tile, "row_path_wall_ms": row_wall,
+                          "row_path_flights_and_compaction_ms": row["flights_and_compaction_ms"], "row_path_gather_ms": row["gather_ms"],
+                          "flights_tile_over_row": tile["flights_and_compaction_ms"] / row["flights_and_compaction_ms"],
+                          "gather_tile_over_row": tile["gather_ms"] / row["gather_ms"]}), flush=True)
+        net.close()
+        tr.close()
+        tex = ds.make_procedural_cloud(a.volume)
+        for count in a.shards:
+            slowest = 0.0
+            for index in range(count):
+                mask = ds.shard_mask(a.size, a.size, index, count).reshape(-1)
+                with ds.CloudTracer(tex, width=a.size, height=a.size, shard_index=index, shard_count=count) as t:
+                    torch.manual_seed(1)
+                    with N.Network(t, N.ScatterNet(200, 1, 3)) as n:
+                        w, st = shard_call(t, n)
+                slowest = max(slowest, w)
+                print(json.dumps({"route": "ct_network_render_shard_subframe", **common, "direct": direct, "shard": [index, count],
+                                  "records": int(mask[pixels].sum()), "wall_ms": w, **st}), flush=True)
+            print(json.dumps({"route": "shards", **common, "direct": direct, "shards": count, "slowest_shard_wall_ms": slowest,
+                              "row_path_wall_ms": row_wall, "speedup_n_gpus_could_reach": row_wall / slowest}), flush=True)
+        sys.exit(0)
 
     # S subframes: fused against the unfused loop
     S = a.subframes

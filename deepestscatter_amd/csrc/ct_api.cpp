@@ -22,252 +22,11 @@
 #include <vector>
 
 #include "../../include/cloudtrace.h"
-#include "ct_internal.hpp"
-#include "ct_network.hpp"
-
-using namespace ct;
-
-// ---- tuning knobs ----------------------------------------------------------------------------------------------------------
-// Every environment variable the library reads, copied ONCE per ct_create into the handle (DESIGN.md 4.4 lists them with
-// what they do and what was measured).  Knobs choose schedules, scratch sizes, layouts and diagnostics; none changes a
-// result (tests/test_gpu_parity.py: the knob test).  get() returns the variable's text as it was at ct_create, or NULL.
-struct Knob {
-    bool is_set = false;
-    std::string text;
-    const char *get() const { return is_set ? text.c_str() : nullptr; }
-    explicit operator bool() const { return is_set; }
-};
-#define CT_KNOBS(X) X(BURST_IDLE) X(BURST_MARCH_MIN) X(BURST_SCATTER) X(CHUNK_INTERLEAVE) X(CHUNK_MORTON) X(CONTINUATION) X(DEBUG_INVARIANTS) X(DELTA_INTERIOR) X(DELTA_NEE) X(EXCHANGE) X(HAND_ON_JOBS) X(HINT_PERIOD) X(JOB_MAX) X(JOB_WORK) X(MARCH_BURST) X(MAX_AGE) X(NEE_CACHE) X(NET_DESC_RECORDS) X(NO_ADVANCE) X(POINT_BLOCKS_PER_CU) X(POINT_ORDER) X(REGEN_MIN) X(RENDER_AHEAD) X(SCATTER_MIN) X(SCATTER_RATIO) X(SCRATCH_GIB) X(SCRATCH_MIB) X(SERPENTINE) X(SHARED_DEPTH) X(SPARSE) X(STATS) X(TAIL_BURST) X(TILE_ORDER) X(TIMELINE) X(TRACE) X(TUNE_SUBFRAMES) X(XCD_QUEUES) X(XCD_QUEUES_UNTUNED) X(XCD_REGIONS) X(BLOCKS_PER_CU)
-struct CtTuning {
-#define X(name) Knob name;
-    CT_KNOBS(X)
-#undef X
-    static CtTuning from_env()
-    {
-        CtTuning t;
-#define X(name)                                  \
-    if (const char *e = getenv("CT_" #name)) {   \
-        t.name.is_set = true;                    \
-        t.name.text = e;                         \
-    }
-        CT_KNOBS(X)
-#undef X
-        return t;
-    }
-};
-
-// One way to read an integer knob: atoi's reading (text that is not a number reads as 0), clamped to [lo, hi]; dflt when unset.
-static int knob_int(const Knob &k, int lo, int hi, int dflt)
-{
-    return k ? std::min(hi, std::max(lo, atoi(k.get()))) : dflt;
-}
-
-// ... and an on/off knob: on for any non-zero number.
-static bool knob_flag(const Knob &k, bool dflt)
-{
-    return k ? atoi(k.get()) != 0 : dflt;
-}
-
-struct CtHandle_ {
-    CtTuning tune;         // the environment's knobs as they were at ct_create
-    CtScene scene{};       // as given (host pointers are NOT retained)
-    int device = 0;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[3] = { nullptr, nullptr, nullptr };
-
-    DevScene dev{};
-    bool camera_set = false;
-
-    // device memory
-    uint8_t *d_density = nullptr, *d_inscatter = nullptr, *d_dist = nullptr, *d_dist_tmp = nullptr, *d_majorant = nullptr, *d_maj_cells = nullptr, *d_maj_codes = nullptr;
-    uint8_t *d_dbricks = nullptr, *d_ibricks = nullptr, *d_mbricks = nullptr, *d_tbricks = nullptr;
-    uint2 *d_mrows = nullptr;          // sparse march bricks: extent of every brick row (DevScene::m_rows)
-    uint8_t *d_mcoarse = nullptr;      // ... and the clearance of the coarse cells outside the extents
-    size_t mbricks_dense_bytes = 0, mbricks_bytes = 0;
-    int nee_skip_r = 0;   // radius of the march bricks' shadow-zero flags (0: none set)
-    // kept from ct_create for ct_set_light, which has neither the density nor the Mie tables on the host any more
-    uint32_t zero_faces = 0;   // empty boundary layers of the density (zero_faces(); launch_inscatter)
-    bool mie_finite = true;    // both phase tables are finite (nee_skip_radius)
-    // CT_FLAG_VMM_BRICKS: d_mbricks is a reserved virtual range (not a hipMalloc), backed chunk by chunk
-    struct VmmBricks {
-        void *va = nullptr;
-        size_t size = 0, chunk = 0;
-        std::vector<hipMemGenericAllocationHandle_t> handles;   // one per chunk with memory of its own + the shared ones
-        size_t real_chunks = 0, shared_chunks = 0, mapped_chunks = 0;
-    } vmm;
-    uint8_t *d_pyramid = nullptr;     // density mip pyramid, built on first use (ct_collect_descriptors)
-    MipPyramid pyramid{};
-    float *d_mie = nullptr, *d_chopped = nullptr, *d_cdf = nullptr;
-    uint16_t *d_guide = nullptr;
-    float4 *d_frame = nullptr, *d_mean = nullptr, *d_m2 = nullptr;
-    uchar4 *d_screen = nullptr;
-    // Batches enqueued with ct_render_accumulate_async form a pipeline on the handle's stream (M = max_age):
-    //     R1  R2 .. R(1+M) A1  R(2+M) A2  ...  (flush:) Rf A(n-M+1) .. An
-    // The estimator launch R(k) does not run its surviving paths to their end when its job list is empty: it suspends
-    // them (BatchArgs::cont_out) and R(k+1) resumes them first, so no launch ends with a tail of waves that carry a few
-    // long paths each.  A path may be suspended M times, so batch k is complete once R(k+M) has run, and A(k), its
-    // accumulate kernel, follows that launch (or the flush launch Rf, which only resumes and runs everything to its end).
-    // The per-sample scratch is a ring of n_regions = M + 1 regions ([S][stride] compact, or [S][H][W] for the simple
-    // kernel): batch k writes region k mod n_regions, which A(k - n_regions) has long left.  M = 1 (two regions) is
-    // round 2's scheme and what long batches use -- a launch of 20 ms outlasts the longest path (2000 bounces, ~10 ms);
-    // short batches (the reference renders 10 subframes per display update, Camera.cpp:189) get more regions, so that a
-    // launch never has to wait for a path that an earlier one handed to it.
-    // A slot owns a region, its queue counters and its events; the suspended paths alternate between two buffers.
-    static constexpr int kMaxRegions = 64;
-    struct Slot {
-        uint32_t *queue = nullptr;
-        hipEvent_t ev_in = nullptr, ev_start = nullptr, ev_done = nullptr, ev_acc0 = nullptr, ev_acc1 = nullptr;
-        bool pending = false;              // launched, kernel times not booked yet
-        bool accumulated = false;          // its accumulate kernel has been enqueued (ev_acc0/1 valid)
-        bool awaits_accumulate = false;    // in `waiting`: some of its subframes are still to be accumulated
-        bool complete = false;             // no path of the batch is in flight any more (max_age launches have followed, or a flush)
-        uint32_t acc_done = 0;             // subframes of the batch whose accumulate kernels are enqueued
-        uint32_t first = 0, S = 0;
-        uint32_t rank_base = 0, groups = 0;   // the chunk of pixel groups this launch renders (places in the job order)
-        bool with_misses = false;          // its accumulate kernel also accounts for the pixels that miss the box (once per batch)
-        bool last_chunk = true;            // ... and is the last of its batch: the running mean is a whole image again after it
-    };
-    Slot slots[kMaxRegions];
-    int n_regions = 2;                     // regions of the scratch in use
-    int next_slot = 0;
-    std::vector<int> waiting;              // slots with subframes still to be accumulated, oldest first
-    // Render-ahead (ct_set_render_ahead, CT_RENDER_AHEAD): enqueued calls of fewer subframes than `ahead` -- the reference's
-    // display loop asks for 10 at a time, Camera.cpp:189 -- are served by estimator launches of `ahead` subframes, of which
-    // every call accumulates its own share: R(k) a(k-M,0) a(k-M,1) .. R(k+1) a(k-M+1,0) ..  A launch of 10 subframes is
-    // mostly beginning and end -- every lane resumes a path and suspends one -- which a launch of `ahead` amortises (DESIGN.md
-    // 4.3 item 13).  `rendered` >= `subframes`: the subframes the estimator has been launched for / the caller has asked
-    // for; the running mean follows the calls by M * ahead subframes until something waits (flush: exactly `subframes`).
-    uint32_t ahead = 0;
-    uint32_t rendered = 0;
-    // Stop-when-converged (ct_set_stop_when_converged): behind the accumulate kernel of every `stop_cadence`-th subframe (from
-    // `stop_min` on) the convergence test runs on the device, and once it holds the accumulate kernels leave the running
-    // mean alone -- Camera::render's `if (!isConverged())` (Camera.cpp:179) without a host round trip per update.
-    // d_freeze: converged_freeze_kernel's state words; freeze_host: their first four, copied back after every test (pinned).
-    uint32_t stop_cadence = 0, stop_min = 100;
-    uint32_t *d_freeze = nullptr, *freeze_host = nullptr;
-    uint32_t *cont[2] = { nullptr, nullptr }; // suspended paths: launch k writes cont[k & 1], launch k+1 reads it
-    uint64_t launch_no = 0;                // estimator launches enqueued so far
-    bool cont_live = false;                // the last launch may have suspended paths: the next one resumes them
-    float4 *d_frames_all = nullptr;        // the whole per-sample scratch
-    size_t frames_total = 0;               // float4 allocated
-    size_t slot_capacity = 0;              // float4 per region
-    uint64_t scratch_cap_bytes = 0;        // 0 = CT_SCRATCH_GIB / the default; else what an out-of-memory allocation left us with
-    uint32_t layout_S = 0;                 // batch size the regions were laid out for
-    uint32_t *left[2] = { nullptr, nullptr }; // job remainders handed on the same way (BatchArgs::left_out)
-    size_t left_capacity = 0;              // entries per buffer: one per wave
-    uint32_t *d_cont_count = nullptr;      // [0,1] entries in cont[i], [2] resume cursor, [3,4] entries in left[i], [5] its cursor
-    unsigned long long *d_cont_total = nullptr; // paths handed from one launch to the next so far (ct_debug_suspended)
-    size_t cont_capacity = 0;              // entries per buffer
-    hipEvent_t ev_flush0 = nullptr, ev_flush1 = nullptr;
-    bool continuation = true;              // CT_CONTINUATION=0: async batches run every path to its end
-    int max_age_override = 0;              // CT_MAX_AGE=n: n + 1 regions whatever the batch size (0 = by batch duration)
-    bool hand_on_jobs = true;              // CT_HAND_ON_JOBS=0: a wave finishes its own job before it suspends (A/B)
-    bool serpentine = false;               // CT_SERPENTINE=1: short launches walk their job queues alternately forwards and backwards
-    // work queue of the persistent kernel (rebuilt when the camera moves)
-    float4 *d_primary = nullptr;      // cached primary rays, 2 float4 per pixel
-    float4 *d_advance = nullptr;      // per pixel: pre-walked prefix of the primary march (MARCH estimator)
-    uint32_t *d_pixels = nullptr;     // this shard's box-hitting pixels, padded to groups of 64
-    uint8_t *d_hit = nullptr, *hit_host = nullptr;   // per pixel: the primary ray hits the box (device; pinned host copy)
-    uint32_t *d_cost = nullptr;       // measured per group: [0,n) sum of path costs, [n,2n) deepest path
-    uint32_t *d_touched[2] = { nullptr, nullptr };   // ct_debug_track_lines: one bit per line of the density / shadow arrays
-    size_t touched_lines[2] = { 0, 0 };
-    unsigned long long *d_timeline = nullptr;   // CT_TIMELINE=1: [start, end] of every wave of the last enqueued estimator launch (MARCH)
-    uint2 *d_cost_plane = nullptr;    // ... as the cost-measuring launch leaves them, per sample (BatchArgs::cost)
-    size_t cost_plane_capacity = 0;
-    uint32_t *d_job_group = nullptr, *d_job_sub = nullptr; // job list of the current batch size
-    uint32_t n_groups = 0, groups_capacity = 0;
-    uint32_t n_jobs = 0, jobs_capacity = 0, jobs_S = 0;
-    uint32_t *jobs_host_g = nullptr, *jobs_host_s = nullptr;   // the list as built on the host (pinned)
-    size_t jobs_host_capacity = 0;
-    bool jobs_brief = false;          // the list was laid out for short launches (short_batch)
-    // The job list is built chunk by chunk: a chunk is a contiguous piece of `chunk_groups` groups of the cost-sorted
-    // group order, and a launch renders all S subframes of ONE chunk into a scratch region of chunk_groups * 64 columns --
-    // so the per-sample scratch does not have to hold the whole frame, while a launch still works through a few pixel groups at
-    // a time for all their subframes (what keeps its paths close together in the volume; cutting a batch by SUBFRAMES
-    // instead makes every launch sweep the whole image and costs 9-14 %).
-    uint32_t chunk_groups = 0, n_chunks = 0;
-    std::vector<std::array<uint32_t, kQueues + 2>> chunk_q_begin;   // per chunk: job ranges of the queues (absolute indices)
-    uint32_t *d_group_rank = nullptr, *d_group_order = nullptr;     // place of a group in the job order / the group at a place
-    uint32_t jobs_hint = 0;           // batch size the caller asked for last (job lists are built for it)
-    // subframes per job at most (cheap groups), and the bounces (x cost unit) a job's lane is expected to run.
-    // Re-swept on the final kernels (8 / 256 before): +4.3 % at 512^3, +5.6 % at 1024^3, +2.6 % at 256^3, +1.3 % DELTA
-    // (16 / 48 until the end of round 2; 16 / 16 since: the whole-frame launch does not care, 3288 either way, a rank's
-    // launch of an eighth of the tiles is 1.6 % shorter, 43.6 instead of 44.3 ms)
-    uint32_t job_max = 16;
-    float job_work = 16.f;
-    uint32_t q_begin[kQueues + 2] = {}; // job ranges of the per-XCD queues + the shared one
-    uint64_t own_pixels = 0, hit_pixels = 0;
-    bool queue_dirty = true, order_tuned = false;
-    bool no_advance = false;             // CT_NO_ADVANCE=1: samples start at the box face (A/B)
-    bool queues_enabled = false;         // per-XCD regions (CT_XCD_QUEUES=1; default: one global list)
-    float shared_depth = 1e30f;          // groups at least this deep (bounces) use the shared queue
-    uint32_t regions = 128;              // image regions dealt to the per-XCD queues
-    std::vector<uint32_t> group_order;   // groups, most expensive first (until tuned: by what the last pose measured for their tiles)
-    std::vector<uint32_t> group_tile;    // the 8x8 tile of a group's first pixel
-    std::vector<uint32_t> tile_deepest;  // per tile of the image: the deepest path the last measured pose produced there (0 = never measured)
-    std::vector<uint32_t> job_order;     // the order the job list is built in: group_order, or its chunks interleaved (build_jobs)
-    bool chunk_interleave = false;       // CT_CHUNK_INTERLEAVE=1: every chunk is every C-th group of group_order (A/B: worse, the neighbours are gone)
-    bool chunk_morton = false;           // CT_CHUNK_MORTON=1: chunks are compact image regions (A/B)
-    bool tile_hilbert = false;           // CT_TILE_ORDER=hilbert: pixel groups along a Hilbert curve instead of Morton order (A/B)
-    std::vector<float> group_depth;      // measured mean path cost per group (0 until tuned), in the
-                                         // units of BatchArgs::cost
-    unsigned long long host_paths = 0, host_hits = 0; // paths / box hits of the persistent path
-    uint32_t *d_queue = nullptr;
-    unsigned long long *d_counters = nullptr; // kCounterCount + 1 (unconverged) + kStatCount
-    float *d_colsum = nullptr, *d_avg = nullptr;
-    uint32_t reinhard_generation = 0;   // launches on d_avg's barrier counter (launch_reinhard)
-
-    // CT_DEBUG_INVARIANTS=1: the diagnostics build of the estimator counts samples dealt / paths resumed / results
-    // written / paths suspended, the scratch is filled with NaNs before every launch, and every point at which
-    // nothing is in flight checks: dealt + resumed == written + suspended, resumed == suspended, dealt == what the
-    // host handed out, no sample without alpha 1 reached an accumulate kernel.  A violation fails the call.
-    bool debug_invariants = false;
-    uint64_t iv_expected_dealt = 0, iv_checks = 0, iv_violations = 0;
-
-    // ct_point_radiance_launch: a collector calls it about a thousand times per scene setup, each call a launch of a few
-    // milliseconds, so its device buffers stay (grown on demand; freeing one would wait for the whole device, i.e. for
-    // the launches of the other scene setups in flight)
-    struct PointBuffers {
-        CtPointRadianceTask *tasks = nullptr;
-        float4 *primary = nullptr, *frames = nullptr;
-        uint32_t *pixels = nullptr, *jg = nullptr, *js = nullptr;
-        size_t cap_tasks = 0, cap_primary = 0, cap_pixels = 0, cap_frames = 0, cap_jg = 0, cap_js = 0;
-    } pt;
-    bool point_order = true;             // CT_POINT_ORDER=0: jobs of 8 frames in task order over 8 queues, as until round 2 (A/B)
-
-    size_t volume_bytes = 0;
-    LaunchShape shape{ 1024, 256, false };
-    // CT_EXCHANGE=1: the estimator kernels with a block-wide exchange of paths between waves (ct_exchange.hpp) render the
-    // batches whose job order is tuned; the cost-measuring launch of a pose keeps the per-lane kernels
-    int exchange = 0;                  // 0 per-lane kernels, 1 block-wide exchange, 2 exchange within a wave
-    LaunchShape xshape{ 256, 1024, false };
-    uint32_t subframes = 0;
-    double render_ms = 0, accum_ms = 0;
-    double dframe_scatter_ms = 0, dframe_gather_ms = 0;   // the last ct_descriptor_frame (ct_debug_descriptor_frame_time)
-    // ct_network_render_*: the temporaries of a band stay with the handle (a frame is many bands, a render many frames).
-    // found / waves / pos / dir / aux / out hold a band of band_cap pixels; desc holds desc_cap records, the largest count
-    // seen so far (or what the device gave: a band with more records goes through gather and network in pieces).  direct holds
-    // a band of direct_cap pixels and exists from the first call with CT_NET_ADD_SINGLE_SCATTER on.
-    struct NetScratch {
-        float4 *found = nullptr, *direct = nullptr;
-        uint32_t *waves = nullptr;
-        float *pos = nullptr, *dir = nullptr, *aux = nullptr, *out = nullptr;
-        uint8_t *desc = nullptr;
-        size_t band_cap = 0, desc_cap = 0, direct_cap = 0;
-        double ms[4] = { 0, 0, 0, 0 };   // the last call (ct_debug_network_render_time)
-        // ct_network_render_shard_*: this shard's 8x8 tiles in ascending ty * tiles_x + tx (ct_shard_tiles), built on first use
-        uint32_t *tiles = nullptr;
-        uint32_t n_tiles = 0;
-        bool tiles_built = false;
-    } net;
-    uint64_t launches = 0;
-    std::string error;
-};
+#include "ct_handle.hpp"
 
 static thread_local std::string g_create_error;
 
-static int fail(CtHandle h, int code, const char *fmt, ...)
+int ct::fail(CtHandle h, int code, const char *fmt, ...)
 {
     char buf[512];
     va_list ap;
@@ -281,15 +40,6 @@ static int fail(CtHandle h, int code, const char *fmt, ...)
     }
     return code;
 }
-
-#define HIPCHK(h, expr)                                                                              \
-    do {                                                                                             \
-        hipError_t e_ = (expr);                                                                      \
-        if (e_ != hipSuccess) {                                                                      \
-            return fail((h), e_ == hipErrorOutOfMemory ? CT_E_NOMEM : CT_E_HIP, "%s failed: %s", #expr, \
-                        hipGetErrorString(e_));                                                      \
-        }                                                                                            \
-    } while (0)
 
 // CT_TRACE=1: host-side phases of a new pose (rebuild_queue, tune_order, build_jobs) with their durations on stderr.
 struct TracePhase {
@@ -308,30 +58,7 @@ struct TracePhase {
 
 inline TracePhase::TracePhase(CtHandle h, const char *n) : name(n), t0(std::chrono::steady_clock::now()), on(h && h->tune.TRACE) {}
 
-static int flush(CtHandle h);
 static int check_invariants(CtHandle h);
-static void discard_ahead(CtHandle h);
-
-#define NEED_NOFLUSH(h)                                \
-    do {                                               \
-        if (!(h)) {                                    \
-            return fail(nullptr, CT_E_INVAL, "null handle"); \
-        }                                              \
-        if (hipSetDevice((h)->device) != hipSuccess) { \
-            return fail((h), CT_E_HIP, "hipSetDevice(%d) failed", (h)->device); \
-        }                                              \
-        (void)hipGetLastError(); /* a stale error of another library in this thread (RCCL leaves them) is not ours */ \
-    } while (0)
-
-// Every entry point except the *_async ones first waits for the batches in flight.
-#define NEED(h)                                        \
-    do {                                               \
-        NEED_NOFLUSH(h);                               \
-        const int rc_flush_ = flush(h);                \
-        if (rc_flush_ != CT_OK) {                      \
-            return rc_flush_;                          \
-        }                                              \
-    } while (0)
 
 static void v3_normalize_twice(const float in[3], float out[3])
 {
@@ -464,35 +191,6 @@ static uint32_t hilbert2(uint32_t x, uint32_t y)
         }
     }
     return d;
-}
-
-template <typename T>
-static hipError_t dmalloc(T **p, size_t count)
-{
-    return hipMalloc((void **)p, count * sizeof(T));
-}
-
-// A device temporary (move-only): allocated by dmalloc, freed when it goes out of scope -- which its user places after the
-// stream synchronise that follows the temporary's last use.
-template <typename T>
-struct DevTemp {
-    T *p = nullptr;
-    DevTemp() = default;
-    DevTemp(DevTemp &&o) noexcept : p(std::exchange(o.p, nullptr)) {}
-    ~DevTemp()
-    {
-        if (p) {
-            hipFree(p);
-        }
-    }
-    operator T *() const { return p; }
-    T *release() { return std::exchange(p, nullptr); }
-};
-
-template <typename T>
-static hipError_t dmalloc(DevTemp<T> *t, size_t count)
-{
-    return dmalloc(&t->p, count);
 }
 
 static void release(CtHandle h)
@@ -2110,7 +1808,7 @@ static int collect(CtHandle h, CtHandle_::Slot &sl)
 
 // The convergence test on the running mean after `subframes` subframes, and its outcome copied to where the host can
 // read it without waiting (ct_converged_at).
-static int enqueue_convergence_test(CtHandle h, uint32_t subframes)
+int ct::enqueue_convergence_test(CtHandle h, uint32_t subframes)
 {
     HIPCHK(h, launch_converged_freeze(h->d_mean, h->d_m2, subframes, (uint64_t)h->scene.width * h->scene.height, 500u /* Camera.cpp:267 */,
                                       h->d_freeze, h->stream));
@@ -2200,7 +1898,7 @@ static int advance_accumulate(CtHandle h, uint32_t target)
 
 // Forgets the subframes that were rendered ahead of the calls (the pose, the layout of the scratch or the count of
 // subframes changes).  Nothing may be in flight: the caller has flushed, so what is left in `waiting` is exactly that.
-static void discard_ahead(CtHandle h)
+void ct::discard_ahead(CtHandle h)
 {
     for (int w : h->waiting) {
         h->slots[w].awaits_accumulate = false;
@@ -2425,7 +2123,7 @@ static int check_invariants(CtHandle h)
 
 // Every batch in flight has finished when this returns.  Batches that still wait for suspended paths get ONE launch that
 // only resumes them (no jobs, no suspension: everything runs to its end), then their accumulate kernels in order.
-static int flush(CtHandle h)
+int ct::flush(CtHandle h)
 {
     if (h->cont_live) {
         BatchArgs ba{};
@@ -3040,601 +2738,6 @@ extern "C" int ct_generate_scatter_samples(CtHandle h, uint32_t count, uint32_t 
         hipStreamSynchronize(h->stream);
     }
     return rc;
-}
-
-// Resources::generateMipmaps (Resources.cpp:169-209) on the device: levels = floor(log2(maxDim)) + 1.
-static int ensure_pyramid(CtHandle h)
-{
-    if (h->d_pyramid) {
-        return CT_OK;
-    }
-    const uint32_t nx = h->scene.dims[0], ny = h->scene.dims[1], nz = h->scene.dims[2];
-    uint32_t m = std::max(nx, std::max(ny, nz)), levels = 1;
-    while (m /= 2) {
-        levels++;
-    }
-    if (levels > (uint32_t)kMaxMipLevels) {
-        return fail(h, CT_E_INVAL, "volume too large for the mip pyramid");
-    }
-    MipPyramid mp{};
-    mp.levels = levels;
-    size_t total = 0;
-    for (uint32_t l = 0; l < levels; l++) {
-        mp.nx[l] = (int32_t)std::max(1u, nx >> l);
-        mp.ny[l] = (int32_t)std::max(1u, ny >> l);
-        mp.nz[l] = (int32_t)std::max(1u, nz >> l);
-        mp.offset[l] = (uint32_t)total;
-        total += (size_t)mp.nx[l] * mp.ny[l] * mp.nz[l];
-    }
-    if (total >= (1ull << 32)) {
-        return fail(h, CT_E_INVAL, "volume too large for the mip pyramid");
-    }
-    HIPCHK(h, dmalloc(&h->d_pyramid, total));
-    HIPCHK(h, hipMemcpyAsync(h->d_pyramid, h->d_density, (size_t)nx * ny * nz, hipMemcpyDeviceToDevice, h->stream));
-    for (uint32_t l = 1; l < levels; l++) {
-        HIPCHK(h, launch_mip_level(h->d_pyramid + mp.offset[l - 1], mp.nx[l - 1], mp.ny[l - 1], mp.nz[l - 1],
-                                   h->d_pyramid + mp.offset[l], mp.nx[l], mp.ny[l], mp.nz[l], h->stream));
-    }
-    mp.base = h->d_pyramid;
-    h->pyramid = mp;
-    return CT_OK;
-}
-
-extern "C" int ct_collect_descriptors(CtHandle h, const float *positions_host, const float *directions_host,
-                                      uint32_t count, uint8_t *descriptors_host_out)
-{
-    NEED(h);
-    if (!positions_host || !directions_host || !descriptors_host_out || count == 0 || count > (1u << 20)) {
-        return fail(h, CT_E_INVAL, "ct_collect_descriptors: need 1..2^20 samples, two input arrays and an output array");
-    }
-    const int prc = ensure_pyramid(h);
-    if (prc != CT_OK) {
-        return prc;
-    }
-    // VDBCloud::getVoxelSizeInMeters / getVoxelSizeInTermsOfFreePath (VDBCloud.cpp:35-46), DisneyDescriptor.cuh:83
-    const float maxs = (float)std::max(h->scene.dims[0], std::max(h->scene.dims[1], h->scene.dims[2]));
-    const float voxel_m = h->scene.cloud_size_m / maxs;
-    const float voxel_fp = voxel_m / h->scene.mean_free_path_m;
-    const float level0 = -ct_log2f(voxel_fp) - 1;
-    DevTemp<float> d_pos, d_dir;
-    DevTemp<uint8_t> d_out;
-    auto run = [&]() -> int {
-        HIPCHK(h, dmalloc(&d_pos, 3 * (size_t)count));
-        HIPCHK(h, dmalloc(&d_dir, 3 * (size_t)count));
-        HIPCHK(h, dmalloc(&d_out, (size_t)count * CT_DESCRIPTOR_BYTES));
-        HIPCHK(h, hipMemcpyAsync(d_pos, positions_host, 3 * (size_t)count * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(d_dir, directions_host, 3 * (size_t)count * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, launch_descriptors(h->dev, h->pyramid, d_pos, d_dir, count, level0, voxel_m, h->scene.cloud_size_m,
-                                     d_out, h->stream));
-        HIPCHK(h, hipMemcpyAsync(descriptors_host_out, d_out, (size_t)count * CT_DESCRIPTOR_BYTES, hipMemcpyDeviceToHost,
-                                 h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        return CT_OK;
-    };
-    const int rc = run();
-    if (rc != CT_OK) {
-        hipStreamSynchronize(h->stream);
-    }
-    return rc;
-}
-
-extern "C" int ct_descriptor_frame(CtHandle h, uint32_t subframe_id, const uint32_t rect[4], uint32_t capacity,
-                                   uint8_t *descriptors_dev, float *positions_dev, float *directions_dev, uint32_t *pixels_dev,
-                                   uint32_t *count_out)
-{
-    NEED(h);
-    if (!descriptors_dev || !count_out) {
-        return fail(h, CT_E_INVAL, "ct_descriptor_frame: need a descriptor array and count_out");
-    }
-    *count_out = 0;
-    if (!h->camera_set) {
-        return fail(h, CT_E_STATE, "ct_set_camera has not been called");
-    }
-    const uint32_t W = h->scene.width, H = h->scene.height;
-    const uint32_t x0 = rect ? rect[0] : 0u, y0 = rect ? rect[1] : 0u, x1 = rect ? rect[2] : W, y1 = rect ? rect[3] : H;
-    if (x0 >= x1 || y0 >= y1 || x1 > W || y1 > H || (uint64_t)(x1 - x0) * (y1 - y0) > (1ull << 20)) {
-        return fail(h, CT_E_INVAL, "ct_descriptor_frame: the rect must be non-empty, inside the %u x %u frame and of at most 2^20 pixels", W, H);
-    }
-    const uint32_t rw = x1 - x0, n = rw * (y1 - y0), n_pad = (n + 255u) / 256u * 256u;
-    // VDBCloud::getVoxelSizeInMeters / getVoxelSizeInTermsOfFreePath, as in ct_collect_descriptors
-    const float maxs = (float)std::max(h->scene.dims[0], std::max(h->scene.dims[1], h->scene.dims[2]));
-    const float voxel_m = h->scene.cloud_size_m / maxs;
-    const float voxel_fp = voxel_m / h->scene.mean_free_path_m;
-    const float level0 = -ct_log2f(voxel_fp) - 1;
-    DevTemp<float4> d_found;
-    DevTemp<uint32_t> d_waves;
-    DevTemp<float> d_pos, d_dir;
-    h->dframe_scatter_ms = h->dframe_gather_ms = 0;
-    auto run = [&]() -> int {
-        // every temporary before any kernel
-        const size_t held = std::max<size_t>(1, std::min<size_t>(capacity, n));   // records the compacting write can produce
-        HIPCHK(h, dmalloc(&d_found, n_pad));
-        HIPCHK(h, dmalloc(&d_waves, n_pad / 64u + 1u));
-        if (!positions_dev) {
-            HIPCHK(h, dmalloc(&d_pos, 3 * held));
-        }
-        if (!directions_dev) {
-            HIPCHK(h, dmalloc(&d_dir, 3 * held));
-        }
-        const int prc = ensure_pyramid(h);
-        if (prc != CT_OK) {
-            return prc;
-        }
-        float *pos = positions_dev ? positions_dev : d_pos.p, *dir = directions_dev ? directions_dev : d_dir.p;
-        HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-        HIPCHK(h, launch_first_scatter_frame(h->dev, x0, y0, rw, n, subframe_id, d_found, d_waves, capacity, pos, dir, pixels_dev, nullptr,
-                                             nullptr, h->stream));
-        HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
-        uint32_t count = 0;
-        HIPCHK(h, hipMemcpyAsync(&count, d_waves + n_pad / 64u, sizeof count, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        *count_out = count;
-        float ms = 0;
-        HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-        h->dframe_scatter_ms = ms;
-        if (count > capacity) {
-            return fail(h, CT_E_INVAL, "ct_descriptor_frame: %u valid pixels do not fit a capacity of %u", count, capacity);
-        }
-        if (count == 0) {
-            return CT_OK;
-        }
-        HIPCHK(h, hipEventRecord(h->ev[0], h->stream));   // (not ev[1] again: the host's look at the count is no part of the gather)
-        HIPCHK(h, launch_descriptors(h->dev, h->pyramid, pos, dir, count, level0, voxel_m, h->scene.cloud_size_m, descriptors_dev,
-                                     h->stream));
-        HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-        h->dframe_gather_ms = ms;
-        return CT_OK;
-    };
-    const int rc = run();
-    if (rc != CT_OK) {
-        hipStreamSynchronize(h->stream);
-    }
-    return rc;
-}
-
-extern "C" int ct_debug_descriptor_frame_time(CtHandle h, double *first_scatter_ms_out, double *gather_ms_out)
-{
-    NEED_NOFLUSH(h);
-    if (first_scatter_ms_out) {
-        *first_scatter_ms_out = h->dframe_scatter_ms;
-    }
-    if (gather_ms_out) {
-        *gather_ms_out = h->dframe_gather_ms;
-    }
-    return CT_OK;
-}
-
-// The scattering network (ct_network.hip): the handle's part is the device, the stream and the wait for batches in flight.
-extern "C" int ct_network_create(CtHandle h, const CtNetworkDesc *d, CtNetwork *out)
-{
-    if (!h) {
-        return fail(nullptr, CT_E_INVAL, "null handle");
-    }
-    char err[256] = "";
-    int rc = ct::network_validate(d, out, err, sizeof err);   // (before the handle's device is touched)
-    if (rc != CT_OK) {
-        return fail(h, rc, "%s", err);
-    }
-    NEED(h);
-    rc = ct::network_create(h->device, d, out, err, sizeof err);
-    return rc == CT_OK ? CT_OK : fail(h, rc, "%s", err);
-}
-
-extern "C" int ct_network_eval(CtHandle h, CtNetwork n, const uint8_t *descriptors_dev, const float *aux_dev, uint32_t count,
-                               float *out_dev)
-{
-    NEED(h);
-    if (!n) {
-        return fail(h, CT_E_INVAL, "ct_network_eval: null network");
-    }
-    if (ct::network_device(n) != h->device) {
-        return fail(h, CT_E_INVAL, "ct_network_eval: the network lives on device %d, the handle on device %d", ct::network_device(n),
-                    h->device);
-    }
-    char err[256] = "";
-    const int rc = ct::network_eval(n, h->stream, descriptors_dev, aux_dev, count, out_dev, err, sizeof err);
-    return rc == CT_OK ? CT_OK : fail(h, rc, "%s", err);
-}
-
-// ---- the network as a renderer (ct_network_render_*) ------------------------------------------------------------------
-// Every CT_E_INVAL of the two entry points except the NULL handle and the ids; nothing of the handle is touched.
-static int net_validate(CtHandle h, CtNetwork n, const CtNetworkRender *p, const char *who, bool shards)
-{
-    if (!n || !p) {
-        return fail(h, CT_E_INVAL, "%s: need a network and its parameters", who);
-    }
-    if (p->abi_version != CT_ABI_VERSION) {
-        return fail(h, CT_E_INVAL, "%s: abi_version %u, this library is %u", who, p->abi_version, CT_ABI_VERSION);
-    }
-    const int32_t out_transform = p->transform & ~CT_NET_ADD_SINGLE_SCATTER;
-    if (out_transform != CT_NET_OUT_LINEAR && out_transform != CT_NET_OUT_EXPM1) {
-        return fail(h, CT_E_INVAL, "%s: unknown output transform %d (CT_NET_OUT_LINEAR or CT_NET_OUT_EXPM1, with or without "
-                                   "CT_NET_ADD_SINGLE_SCATTER)", who, p->transform);
-    }
-    if (!std::isfinite(p->rgb_scale[0]) || !std::isfinite(p->rgb_scale[1]) || !std::isfinite(p->rgb_scale[2])) {
-        return fail(h, CT_E_INVAL, "%s: rgb_scale is not finite", who);
-    }
-    if (ct::network_aux_inputs(n) != 1u) {
-        return fail(h, CT_E_INVAL, "%s: the renderer feeds one aux input (the light angle); this network has %u", who,
-                    ct::network_aux_inputs(n));
-    }
-    if (ct::network_device(n) != h->device) {
-        return fail(h, CT_E_INVAL, "%s: the network lives on device %d, the handle on device %d", who, ct::network_device(n), h->device);
-    }
-    if (!shards && h->scene.shard_count > 1u) {
-        return fail(h, CT_E_INVAL, "%s: this handle renders shard %u of %u; a shard's network frame is ct_network_render_shard_subframe / "
-                                   "ct_network_render_shard_accumulate", who, h->scene.shard_index, h->scene.shard_count);
-    }
-    return CT_OK;
-}
-
-// Rows of a band: whole rows of at most band_pixels pixels, at least one (a row has at most 12288 pixels), at most 2^20 pixels.
-static uint32_t net_band_rows(CtHandle h, uint32_t band_pixels)
-{
-    const uint32_t cap = (band_pixels == 0u || band_pixels > (1u << 20)) ? (1u << 20) : band_pixels;
-    return std::min(h->scene.height, std::max(1u, cap / h->scene.width));
-}
-
-// Records the descriptor array may hold at most: 2^20 (a band has no more), or CT_NET_DESC_RECORDS.
-static size_t net_descriptor_limit(CtHandle h)
-{
-    return (size_t)knob_int(h->tune.NET_DESC_RECORDS, 1, 1 << 20, 1 << 20);
-}
-
-// Everything a call needs before its first kernel: the band-sized temporaries and a first piece of the descriptor array.  The
-// stream is idle.  A failed growth leaves what the handle had.  direct: the call carries CT_NET_ADD_SINGLE_SCATTER.
-static int net_reserve(CtHandle h, size_t band_pixels, bool direct)
-{
-    CtHandle_::NetScratch &s = h->net;
-    const size_t n_pad = (band_pixels + 255u) / 256u * 256u;
-    if (direct && n_pad > s.direct_cap) {
-        DevTemp<float4> sun;
-        HIPCHK(h, dmalloc(&sun, n_pad));
-        if (s.direct) {
-            hipFree(s.direct);
-        }
-        s.direct = sun.release();
-        s.direct_cap = n_pad;
-    }
-    if (n_pad > s.band_cap) {
-        DevTemp<float4> found;
-        DevTemp<uint32_t> waves;
-        DevTemp<float> pos, dir, aux, out;
-        HIPCHK(h, dmalloc(&found, n_pad));
-        HIPCHK(h, dmalloc(&waves, n_pad / 64u + 1u));
-        HIPCHK(h, dmalloc(&pos, 3 * n_pad));
-        HIPCHK(h, dmalloc(&dir, 3 * n_pad));
-        HIPCHK(h, dmalloc(&aux, n_pad));
-        HIPCHK(h, dmalloc(&out, n_pad));
-        for (void *old : { (void *)s.found, (void *)s.waves, (void *)s.pos, (void *)s.dir, (void *)s.aux, (void *)s.out }) {
-            if (old) {
-                hipFree(old);
-            }
-        }
-        s.found = found.release();
-        s.waves = waves.release();
-        s.pos = pos.release();
-        s.dir = dir.release();
-        s.aux = aux.release();
-        s.out = out.release();
-        s.band_cap = n_pad;
-    }
-    if (s.desc_cap == 0) {
-        // (CT_NET_DESC_RECORDS: the array never holds more records than this -- what a device without room for the growth leaves
-        // a handle with, for the test that runs a band in pieces)
-        const size_t first = std::min<size_t>(std::min<size_t>(n_pad, 4096), net_descriptor_limit(h));
-        HIPCHK(h, dmalloc(&s.desc, first * CT_DESCRIPTOR_BYTES));
-        s.desc_cap = first;
-    }
-    return CT_OK;
-}
-
-// The descriptor array follows the largest record count seen.  Between bands, the stream idle.  When the device has no room
-// for it the array stays as it is and the band's records are gathered and evaluated in pieces of its size.
-static void net_grow_descriptors(CtHandle h, size_t count)
-{
-    CtHandle_::NetScratch &s = h->net;
-    count = std::min(count, net_descriptor_limit(h));
-    if (count <= s.desc_cap) {
-        return;
-    }
-    uint8_t *bigger = nullptr;
-    if (dmalloc(&bigger, count * CT_DESCRIPTOR_BYTES) != hipSuccess) {
-        (void)hipGetLastError();
-        return;
-    }
-    hipFree(s.desc);
-    s.desc = bigger;
-    s.desc_cap = count;
-}
-
-// The tiles of a band of the tile path: at most band_pixels / 64, at least one, at most 2^14 (2^20 lanes).
-static uint32_t net_band_tiles(uint32_t band_pixels)
-{
-    const uint32_t cap = (band_pixels == 0u || band_pixels > (1u << 20)) ? (1u << 20) : band_pixels;
-    return std::max(1u, cap / 64u);
-}
-
-// The shard's tile list on the device, from ct_shard_tiles, once per handle.  The stream is idle.
-static int net_ensure_tiles(CtHandle h)
-{
-    CtHandle_::NetScratch &s = h->net;
-    if (s.tiles_built) {
-        return CT_OK;
-    }
-    uint32_t count = 0;
-    if (ct_shard_tiles(h->scene.width, h->scene.height, h->scene.shard_index, h->scene.shard_count, nullptr, 0, &count) != CT_OK) {
-        return fail(h, CT_E_INVAL, "internal: ct_shard_tiles refused the handle's own frame");
-    }
-    std::vector<uint32_t> list(std::max(count, 1u), 0u);
-    if (ct_shard_tiles(h->scene.width, h->scene.height, h->scene.shard_index, h->scene.shard_count, list.data(), count, &count) != CT_OK) {
-        return fail(h, CT_E_INVAL, "internal: ct_shard_tiles refused the handle's own frame");
-    }
-    DevTemp<uint32_t> dev;
-    HIPCHK(h, dmalloc(&dev, list.size()));
-    HIPCHK(h, hipMemcpy(dev.p, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    s.tiles = dev.release();
-    s.n_tiles = count;
-    s.tiles_built = true;
-    return CT_OK;
-}
-
-// One band of subframe `sid` into the frame (frame != NULL) or into mean / M2.  Row path: rows [y0, y0 + rows); tile path
-// (tiles): the `rows` tiles of the shard's list from tile y0 on.
-static int net_band(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t sid, uint32_t y0, uint32_t rows, float level0,
-                    float voxel_m, bool accumulate, bool tiles)
-{
-    CtHandle_::NetScratch &s = h->net;
-    const uint32_t W = h->scene.width, npx = tiles ? 64u * rows : W * rows, n_pad = (npx + 255u) / 256u * 256u;
-    const uint32_t *const band_tiles = tiles ? s.tiles + y0 : nullptr;
-    float4 *const direct = (p->transform & CT_NET_ADD_SINGLE_SCATTER) ? s.direct : nullptr;
-    float ms = 0;
-    HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-    HIPCHK(h, launch_first_scatter_frame(h->dev, 0u, tiles ? 0u : y0, W, npx, sid, s.found, s.waves, npx, s.pos, s.dir, nullptr, direct,
-                                         band_tiles, h->stream));
-    HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
-    uint32_t count = 0;
-    HIPCHK(h, hipMemcpyAsync(&count, s.waves + n_pad / 64u, sizeof count, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-    s.ms[0] += ms;
-    if (count > npx) {
-        return fail(h, CT_E_HIP, "internal: a band of %u pixels counted %u records", npx, count);
-    }
-    if (count != 0u) {
-        net_grow_descriptors(h, count);
-        for (uint32_t at = 0; at < count;) {
-            const uint32_t piece = (uint32_t)std::min<size_t>(count - at, s.desc_cap);
-            HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-            HIPCHK(h, launch_descriptors(h->dev, h->pyramid, s.pos + 3 * (size_t)at, s.dir + 3 * (size_t)at, piece, level0, voxel_m,
-                                         h->scene.cloud_size_m, s.desc, h->stream));
-            HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
-            // l = the direction the light travels: the uniforms hold -l (Sun.cpp:13-18)
-            HIPCHK(h, launch_network_aux(s.dir + 3 * (size_t)at, piece, -h->dev.nlx, -h->dev.nly, -h->dev.nlz, s.aux + at, h->stream));
-            HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
-            char err[256] = "";
-            const int rc = ct::network_eval(n, h->stream, s.desc, s.aux + at, piece, s.out + at, err, sizeof err);   // (waits)
-            if (rc != CT_OK) {
-                return fail(h, rc, "%s", err);
-            }
-            HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-            s.ms[1] += ms;
-            HIPCHK(h, hipEventElapsedTime(&ms, h->ev[1], h->ev[2]));
-            s.ms[3] += ms;
-            double net_ms = 0;
-            ct_debug_network_time(n, &net_ms);
-            s.ms[2] += net_ms;
-            at += piece;
-        }
-    }
-    const NetCompose c{ p->transform & 0xff, p->rgb_scale[0], p->rgb_scale[1], p->rgb_scale[2] };
-    const size_t first_pixel = tiles ? 0 : (size_t)y0 * W;   // (the tile path writes at y * W + x of the whole frame)
-    HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-    HIPCHK(h, launch_network_compose(s.found, s.waves, s.out, npx, c, accumulate ? nullptr : h->d_frame + first_pixel,
-                                     h->d_mean + first_pixel, h->d_m2 + first_pixel, sid, h->stop_cadence ? h->d_freeze : nullptr,
-                                     direct, band_tiles, h->dev.tiles_x, W, h->scene.height, h->stream));
-    HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
-    HIPCHK(h, hipEventSynchronize(h->ev[1]));
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-    s.ms[3] += ms;
-    if (accumulate) {
-        h->accum_ms += ms;
-    }
-    return CT_OK;
-}
-
-// Subframes [first, first + count) band by band.  The caller has validated and flushed.  tiles: the bands are runs of the
-// shard's tile list (ct_network_render_shard_*) instead of rows; a frame is first filled with the shard's background.
-static int net_run(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t first, uint32_t count, bool accumulate, bool tiles)
-{
-    const uint32_t H = h->scene.height, rows = tiles ? net_band_tiles(p->band_pixels) : net_band_rows(h, p->band_pixels);
-    // VDBCloud::getVoxelSizeInMeters / getVoxelSizeInTermsOfFreePath, as in ct_collect_descriptors
-    const float maxs = (float)std::max(h->scene.dims[0], std::max(h->scene.dims[1], h->scene.dims[2]));
-    const float voxel_m = h->scene.cloud_size_m / maxs;
-    const float voxel_fp = voxel_m / h->scene.mean_free_path_m;
-    const float level0 = -ct_log2f(voxel_fp) - 1;
-    for (double &ms : h->net.ms) {
-        ms = 0;
-    }
-    auto run = [&]() -> int {
-        int rc = tiles ? net_ensure_tiles(h) : CT_OK;
-        if (rc != CT_OK) {
-            return rc;
-        }
-        // (bands of the row path run bottom to top over H rows; those of the tile path over the list's n_tiles tiles)
-        const uint32_t units = tiles ? h->net.n_tiles : H;
-        const size_t band = tiles ? (size_t)64 * std::min(rows, std::max(units, 1u)) : (size_t)h->scene.width * rows;
-        rc = net_reserve(h, band, (p->transform & CT_NET_ADD_SINGLE_SCATTER) != 0);
-        if (rc == CT_OK) {
-            rc = ensure_pyramid(h);
-        }
-        if (rc != CT_OK) {
-            return rc;
-        }
-        if (accumulate) {
-            discard_ahead(h);   // like ct_accumulate: the running mean leaves the order the samples rendered ahead were made for
-        }
-        for (uint32_t k = 0; k < count; k++) {
-            const uint32_t sid = first + k;
-            if (tiles && !accumulate) {
-                // the shard's background, as ct_render_subframe starts from it: the bands write the own pixels only
-                float ms = 0;
-                HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-                HIPCHK(h, launch_fill_frame(h->d_frame, h->scene.width, H, h->scene.shard_index, h->scene.shard_count, h->stream));
-                HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
-                HIPCHK(h, hipEventSynchronize(h->ev[1]));
-                HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-                h->net.ms[3] += ms;
-            }
-            for (uint32_t y0 = 0; y0 < units; y0 += rows) {
-                rc = net_band(h, n, p, sid, y0, std::min(rows, units - y0), level0, voxel_m, accumulate, tiles);
-                if (rc != CT_OK) {
-                    return rc;
-                }
-            }
-            if (accumulate) {
-                if (h->stop_cadence && sid % h->stop_cadence == 0u && sid >= h->stop_min) {   // as ct_accumulate
-                    rc = enqueue_convergence_test(h, sid);
-                    if (rc != CT_OK) {
-                        return rc;
-                    }
-                    HIPCHK(h, hipStreamSynchronize(h->stream));
-                }
-                h->subframes = sid;
-                discard_ahead(h);
-            }
-        }
-        return CT_OK;
-    };
-    const int rc = run();
-    if (rc != CT_OK) {
-        hipStreamSynchronize(h->stream);
-    }
-    return rc;
-}
-
-static int net_subframe(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t subframe_id, float *frame_rgba_dev, bool tiles)
-{
-    NEED_NOFLUSH(h);
-    // (arguments first: a rejected call leaves the handle exactly as it was, batches in flight included)
-    int rc = net_validate(h, n, p, tiles ? "ct_network_render_shard_subframe" : "ct_network_render_subframe", tiles);
-    if (rc != CT_OK) {
-        return rc;
-    }
-    if (subframe_id == 0) {
-        return fail(h, CT_E_INVAL, "subframe ids are 1-based (Camera.cpp:191)");
-    }
-    if (!h->camera_set) {
-        return fail(h, CT_E_STATE, "ct_set_camera has not been called");
-    }
-    rc = flush(h);
-    if (rc != CT_OK) {
-        return rc;
-    }
-    rc = net_run(h, n, p, subframe_id, 1, false, tiles);
-    if (rc != CT_OK) {
-        return rc;
-    }
-    if (frame_rgba_dev) {
-        HIPCHK(h, hipMemcpyAsync(frame_rgba_dev, h->d_frame, (size_t)h->scene.width * h->scene.height * sizeof(float4),
-                                 hipMemcpyDeviceToDevice, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    return CT_OK;
-}
-
-extern "C" int ct_network_render_subframe(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t subframe_id, float *frame_rgba_dev)
-{
-    return net_subframe(h, n, p, subframe_id, frame_rgba_dev, false);
-}
-
-extern "C" int ct_network_render_shard_subframe(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t subframe_id,
-                                                float *frame_rgba_dev)
-{
-    return net_subframe(h, n, p, subframe_id, frame_rgba_dev, true);
-}
-
-static int net_accumulate(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t first_subframe_id, uint32_t count, bool tiles)
-{
-    NEED_NOFLUSH(h);
-    const char *const who = tiles ? "ct_network_render_shard_accumulate" : "ct_network_render_accumulate";
-    int rc = net_validate(h, n, p, who, tiles);
-    if (rc != CT_OK) {
-        return rc;
-    }
-    if (first_subframe_id == 0 || count == 0) {
-        return fail(h, CT_E_INVAL, "%s: subframe ids are 1-based and count must not be 0", who);
-    }
-    if (!h->camera_set) {
-        return fail(h, CT_E_STATE, "ct_set_camera has not been called");
-    }
-    rc = flush(h);
-    if (rc != CT_OK) {
-        return rc;
-    }
-    if (first_subframe_id != h->subframes + 1) {
-        return fail(h, CT_E_STATE, "first_subframe_id %u but %u subframes are accumulated", first_subframe_id, h->subframes);
-    }
-    if (count > 0xffffffffu - first_subframe_id + 1u) {
-        return fail(h, CT_E_INVAL, "%s: %u subframes from %u on exceed the 32-bit subframe id", who, count, first_subframe_id);
-    }
-    return net_run(h, n, p, first_subframe_id, count, true, tiles);
-}
-
-extern "C" int ct_network_render_accumulate(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t first_subframe_id, uint32_t count)
-{
-    return net_accumulate(h, n, p, first_subframe_id, count, false);
-}
-
-extern "C" int ct_network_render_shard_accumulate(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t first_subframe_id,
-                                                  uint32_t count)
-{
-    return net_accumulate(h, n, p, first_subframe_id, count, true);
-}
-
-extern "C" int ct_debug_network_aux(CtHandle h, const float *directions_dev, uint32_t count, float *aux_dev_out)
-{
-    NEED(h);
-    if (count == 0) {
-        return CT_OK;
-    }
-    if (!directions_dev || !aux_dev_out) {
-        return fail(h, CT_E_INVAL, "ct_debug_network_aux: need directions and an output array");
-    }
-    HIPCHK(h, launch_network_aux(directions_dev, count, -h->dev.nlx, -h->dev.nly, -h->dev.nlz, aux_dev_out, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return CT_OK;
-}
-
-extern "C" int ct_debug_network_render_time(CtHandle h, double ms_out[4])
-{
-    NEED_NOFLUSH(h);
-    if (!ms_out) {
-        return fail(h, CT_E_INVAL, "ct_debug_network_render_time: ms_out is NULL");
-    }
-    for (int i = 0; i < 4; i++) {
-        ms_out[i] = h->net.ms[i];
-    }
-    return CT_OK;
-}
-
-extern "C" int ct_debug_network_scratch(CtHandle h, uint64_t out[12])
-{
-    NEED_NOFLUSH(h);
-    if (!out) {
-        return fail(h, CT_E_INVAL, "ct_debug_network_scratch: out is NULL");
-    }
-    const CtHandle_::NetScratch &s = h->net;
-    const void *ptrs[9] = { s.found, s.waves, s.pos, s.dir, s.aux, s.out, s.desc, s.direct, s.tiles };
-    for (int i = 0; i < 9; i++) {
-        out[i] = (uint64_t)(uintptr_t)ptrs[i];
-    }
-    out[9] = s.band_cap;
-    out[10] = s.desc_cap;
-    out[11] = s.direct_cap;
-    return CT_OK;
 }
 
 extern "C" int ct_reset(CtHandle h)

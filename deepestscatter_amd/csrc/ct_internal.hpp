@@ -1,4 +1,4 @@
-// ct_internal.hpp -- launcher declarations shared by ct_kernels.hip and ct_api.cpp.
+// ct_internal.hpp -- launcher declarations shared by ct_kernels.hip and the host files (ct_api.cpp, ct_neural.cpp).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -202,32 +202,48 @@ hipError_t launch_point_accumulate(const float4 *frames, uint32_t stride, void *
                                    hipStream_t stream);
 hipError_t launch_scatter_samples(const DevScene &sc, uint32_t count, uint32_t batch_seed, float *positions,
                                   float *directions, hipStream_t stream);
-// ct_descriptor_frame: first flight of the n pixels of the rect (x0, y0, row length w), a scan of the per-wave counts and the
-// compacting write, three dispatches.  found: (n rounded up to 256) float4; wave_counts: (n rounded up to 256) / 64 + 1 words,
-// afterwards the waves' offsets and, in the last word, the number of records; positions / directions hold `capacity` records,
-// pixels may be NULL.  direct != NULL ((n rounded up to 256) float4): the flight also stores, by rect pixel, the single-scatter
-// term of its collision (CT_NET_ADD_SINGLE_SCATTER), zeros where the pixel has no record.
-// tiles != NULL (device, n / 64 entries, ty * tiles_x + tx each): the n lanes are those 8x8 tiles, one wave per tile, lane l of
-// a tile its pixel (l & 7, l >> 3); x0, y0 and w are unused, lanes that the frame clips are never valid, and found, direct and
-// the counts are indexed by lane.
-hipError_t launch_first_scatter_frame(const DevScene &sc, uint32_t x0, uint32_t y0, uint32_t w, uint32_t n, uint32_t subframe_id,
-                                      float4 *found, uint32_t *wave_counts, uint32_t capacity, float *positions, float *directions,
-                                      uint32_t *pixels, float4 *direct, const uint32_t *tiles, hipStream_t stream);
-// ct_network_render_*: aux[i] = dot(directions[i], l), left to right; and the pixels of a band of n pixels (whole rows) from the
-// flight's temporary, the scanned wave counts and the network's outputs of the band's records.  frame != NULL: the pixels are
-// stored there (the band's first pixel); frame == NULL: they go into the Welford update of mean / m2 (the band's first pixel)
-// with n = subframe_id, unless *frozen.  direct != NULL: the flight's single-scatter temporary, added to the pixels with a record.
-// tiles != NULL: the n lanes are the tiles of launch_first_scatter_frame's tile form; frame / mean / m2 are then the whole
-// frame's (width x height, tiles_x tiles per row) and only the pixels of those tiles are written.
+// The pixels a pass of the first-scatter / network path works on, one per lane: a rect of the frame in row-major order, or a run
+// of 8x8 tiles of a shard's tile list, one wave per tile, lane l of a tile its pixel (l & 7, l >> 3).  A lane of a tile that the
+// frame clips has no pixel.
+struct PixelBand {
+    uint32_t x0, y0, w;      // rect: origin and row length
+    uint32_t n;              // lanes: the rect's pixels, or 64 per tile
+    const uint32_t *tiles;   // tile run (device, n / 64 entries, ty * tiles_x + tx each); NULL: a rect
+    uint32_t tiles_x, width, height;   // tile run: the frame's
+};
+inline PixelBand rect_band(uint32_t x0, uint32_t y0, uint32_t w, uint32_t rows)
+{
+    return { x0, y0, w, w * rows, nullptr, 0u, 0u, 0u };
+}
+inline PixelBand tile_band(const DevScene &sc, const uint32_t *tiles, uint32_t count)
+{
+    return { 0u, 0u, 0u, 64u * count, tiles, sc.tiles_x, sc.width, sc.height };
+}
+// The flight's temporaries, indexed by lane: found and direct hold (n rounded up to 256) float4, waves (n rounded up to 256) / 64 + 1
+// words -- the waves' record counts, after the scan their offsets and, in the last word, the number of records.
+struct FlightTemps {
+    float4 *found;
+    uint32_t *waves;
+    float4 *direct;   // the single-scatter term of a lane's collision (CT_NET_ADD_SINGLE_SCATTER), zeros without a record; NULL: not made
+};
+// ct_descriptor_frame: the band's first flights, a scan of the per-wave counts and the compacting write, three dispatches.
+// positions / directions hold `capacity` records, pixels may be NULL.
+hipError_t launch_first_scatter_frame(const DevScene &sc, const PixelBand &band, const FlightTemps &t, uint32_t subframe_id,
+                                      uint32_t capacity, float *positions, float *directions, uint32_t *pixels, hipStream_t stream);
+// ct_network_render_*: aux[i] = dot(directions[i], l), left to right; and the band's pixels from the flight's temporaries and the
+// network's outputs of the band's records.
 struct NetCompose {
     int32_t transform;   // CT_NET_OUT_* (the low byte of CtNetworkRender::transform)
     float sr, sg, sb;    // rgb_scale
 };
+struct ComposeTarget {       // a rect: at the band's first pixel; a tile run: the whole frame's
+    float4 *frame;           // the pixels are stored here; NULL: they go into the Welford update of
+    float4 *mean, *m2;       // ... these, with n = subframe_id, unless *frozen
+    uint32_t subframe_id;
+};
 hipError_t launch_network_aux(const float *directions, uint32_t count, float lx, float ly, float lz, float *aux, hipStream_t stream);
-hipError_t launch_network_compose(const float4 *found, const uint32_t *wave_offsets, const float *out, uint32_t n, const NetCompose &c,
-                                  float4 *frame, float4 *mean, float4 *m2, uint32_t subframe_id, const uint32_t *frozen,
-                                  const float4 *direct, const uint32_t *tiles, uint32_t tiles_x, uint32_t width, uint32_t height,
-                                  hipStream_t stream);
+hipError_t launch_network_compose(const PixelBand &band, const FlightTemps &t, const NetCompose &c, const float *out,
+                                  const ComposeTarget &dst, const uint32_t *frozen, hipStream_t stream);
 // Density pyramid (Resources::generateMipmaps) and the descriptor gather.
 constexpr int kMaxMipLevels = 16;
 struct MipPyramid {

@@ -3044,42 +3044,25 @@ hipError_t launch_scatter_samples(const DevScene &sc, uint32_t count, uint32_t b
 // TILES (ct_network_render_shard_*): the lanes are not a rect but a run of 8x8 tiles of the shard's tile list, one wave per
 // tile -- render_simple_kernel's map -- so a wave's 64 flights are one tile's and a shard pays for no foreign pixel.  A lane
 // of a tile that the frame clips has no pixel: it is never valid, its `found` says so, and nothing else is stored for it.
-struct FrameRect {
-    uint32_t x0, y0, w, n;   // origin, row length and pixel count of the rect; TILES: n = 64 * tiles, the rest unused
-    const uint32_t *tiles;   // TILES: the band's tiles, ty * tiles_x + tx each
-};
-
-// pixel i of the rect, row-major
-CT_DEV void rect_pixel(const FrameRect &r, uint32_t i, uint32_t &x, uint32_t &y)
-{
-    x = r.x0 + i % r.w;
-    y = r.y0 + i / r.w;
-}
-
-// lane i (< 64 * tiles) of a run of tiles: false where the frame clips the tile
-CT_DEV bool tile_pixel(const uint32_t *__restrict__ tiles, uint32_t tiles_x, uint32_t width, uint32_t height, uint32_t i, uint32_t &x,
-                       uint32_t &y)
-{
-    const uint32_t tile = tiles[i >> 6], l = i & 63u;
-    const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    x = tx * kTile + (l & 7u);
-    y = ty * kTile + (l >> 3);
-    return x < width && y < height;
-}
-
+// The pixel of lane i (< b.n) of a band (PixelBand, ct_internal.hpp): false where the frame clips the lane's tile.
 template <bool TILES>
-CT_DEV bool band_pixel(const DevScene &sc, const FrameRect &r, uint32_t i, uint32_t &x, uint32_t &y)
+CT_DEV bool band_pixel(const PixelBand &b, uint32_t i, uint32_t &x, uint32_t &y)
 {
     if constexpr (TILES) {
-        return tile_pixel(r.tiles, sc.tiles_x, sc.width, sc.height, i, x, y);
+        const uint32_t tile = b.tiles[i >> 6], l = i & 63u;
+        const uint32_t ty = tile / b.tiles_x, tx = tile - ty * b.tiles_x;
+        x = tx * kTile + (l & 7u);
+        y = ty * kTile + (l >> 3);
+        return x < b.width && y < b.height;
     } else {
-        rect_pixel(r, i, x, y);
+        x = b.x0 + i % b.w;   // row-major
+        y = b.y0 + i / b.w;
         return true;
     }
 }
 
 template <bool FIXED8, bool DIRECT, bool TILES>
-__global__ __launch_bounds__(256) void first_scatter_frame_kernel(DevScene sc, FrameRect r, uint32_t subframe_id,
+__global__ __launch_bounds__(256) void first_scatter_frame_kernel(DevScene sc, PixelBand r, uint32_t subframe_id,
                                                                  float4 *__restrict__ found, uint32_t *__restrict__ wave_counts,
                                                                  float4 *__restrict__ direct)
 {
@@ -3089,7 +3072,7 @@ __global__ __launch_bounds__(256) void first_scatter_frame_kernel(DevScene sc, F
     f3 sun = mk3(0, 0, 0);
     if (i < r.n) {
         uint32_t x, y;
-        const bool pixel = band_pixel<TILES>(sc, r, i, x, y);
+        const bool pixel = band_pixel<TILES>(r, i, x, y);
         const f3 eye = mk3(sc.ex, sc.ey, sc.ez);
         const f3 d = primary_direction(sc, x, y);
         float t_hit = 0;
@@ -3150,7 +3133,7 @@ __global__ __launch_bounds__(1024) void first_scatter_scan_kernel(uint32_t *__re
 }
 
 template <bool TILES>
-__global__ __launch_bounds__(256) void first_scatter_compact_kernel(DevScene sc, FrameRect r, const float4 *__restrict__ found,
+__global__ __launch_bounds__(256) void first_scatter_compact_kernel(DevScene sc, PixelBand r, const float4 *__restrict__ found,
                                                                    const uint32_t *__restrict__ wave_offsets, uint32_t capacity,
                                                                    float *__restrict__ positions, float *__restrict__ directions,
                                                                    uint32_t *__restrict__ pixels)
@@ -3171,7 +3154,7 @@ __global__ __launch_bounds__(256) void first_scatter_compact_kernel(DevScene sc,
         return;
     }
     uint32_t x, y;
-    (void)band_pixel<TILES>(sc, r, i, x, y);                  // (a valid lane has a pixel)
+    (void)band_pixel<TILES>(r, i, x, y);                  // (a valid lane has a pixel)
     const f3 dir = normalize3(primary_direction(sc, x, y));   // d2, as first_scatter_frame_kernel made it
     positions[3 * slot + 0] = f.x; positions[3 * slot + 1] = f.y; positions[3 * slot + 2] = f.z;
     directions[3 * slot + 0] = dir.x; directions[3 * slot + 1] = dir.y; directions[3 * slot + 2] = dir.z;
@@ -3180,36 +3163,29 @@ __global__ __launch_bounds__(256) void first_scatter_compact_kernel(DevScene sc,
     }
 }
 
-hipError_t launch_first_scatter_frame(const DevScene &sc, uint32_t x0, uint32_t y0, uint32_t w, uint32_t n, uint32_t subframe_id,
-                                      float4 *found, uint32_t *wave_counts, uint32_t capacity, float *positions, float *directions,
-                                      uint32_t *pixels, float4 *direct, const uint32_t *tiles, hipStream_t stream)
+hipError_t launch_first_scatter_frame(const DevScene &sc, const PixelBand &band, const FlightTemps &t, uint32_t subframe_id,
+                                      uint32_t capacity, float *positions, float *directions, uint32_t *pixels, hipStream_t stream)
 {
-    const FrameRect r{ x0, y0, w, n, tiles };
-    const uint32_t blocks = (n + 255u) / 256u;
-    auto flight = first_scatter_frame_kernel<false, false, false>;
-    if (tiles) {
-        if (direct) {
-            flight = sc.tex_fixed8 ? first_scatter_frame_kernel<true, true, true> : first_scatter_frame_kernel<false, true, true>;
-        } else {
-            flight = sc.tex_fixed8 ? first_scatter_frame_kernel<true, false, true> : first_scatter_frame_kernel<false, false, true>;
-        }
-    } else if (direct) {
-        flight = sc.tex_fixed8 ? first_scatter_frame_kernel<true, true, false> : first_scatter_frame_kernel<false, true, false>;
-    } else if (sc.tex_fixed8) {
-        flight = first_scatter_frame_kernel<true, false, false>;
-    }
-    hipLaunchKernelGGL(flight, dim3(blocks), dim3(256), 0, stream, sc, r, subframe_id, found, wave_counts, direct);
+#define K(TILES, DIRECT) first_scatter_frame_kernel<false, DIRECT, TILES>, first_scatter_frame_kernel<true, DIRECT, TILES>
+    static constexpr decltype(&first_scatter_frame_kernel<false, false, false>) flights[8] = { K(false, false), K(false, true),
+                                                                                              K(true, false), K(true, true) };
+#undef K
+    const bool tiles = band.tiles != nullptr, direct = t.direct != nullptr;
+    const uint32_t blocks = (band.n + 255u) / 256u;
+    hipLaunchKernelGGL(flights[4 * tiles + 2 * direct + (sc.tex_fixed8 ? 1 : 0)], dim3(blocks), dim3(256), 0, stream, sc, band, subframe_id,
+                       t.found, t.waves, t.direct);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         return e;
     }
-    hipLaunchKernelGGL(first_scatter_scan_kernel, dim3(1), dim3(1024), 0, stream, wave_counts, blocks * 4u);
+    hipLaunchKernelGGL(first_scatter_scan_kernel, dim3(1), dim3(1024), 0, stream, t.waves, blocks * 4u);
     e = hipGetLastError();
     if (e != hipSuccess) {
         return e;
     }
     auto compact = tiles ? first_scatter_compact_kernel<true> : first_scatter_compact_kernel<false>;
-    hipLaunchKernelGGL(compact, dim3(blocks), dim3(256), 0, stream, sc, r, found, wave_counts, capacity, positions, directions, pixels);
+    hipLaunchKernelGGL(compact, dim3(blocks), dim3(256), 0, stream, sc, band, (const float4 *)t.found, (const uint32_t *)t.waves, capacity,
+                       positions, directions, pixels);
     return hipGetLastError();
 }
 
@@ -3248,42 +3224,39 @@ hipError_t launch_network_aux(const float *directions, uint32_t count, float lx,
 // test included); otherwise into the frame.
 // DIRECT (CT_NET_ADD_SINGLE_SCATTER): a pixel with a record gets the flight's single-scatter term, read by pixel index, added
 // behind the scaled network output (the product is rounded first: the build has no contraction).
-// TILES (ct_network_render_shard_*): lane i is a lane of the band's run of tiles (tile_pixel), found / direct / the wave offsets
+// TILES (ct_network_render_shard_*): lane i is a lane of the band's run of tiles (band_pixel), found / direct / the wave offsets
 // are indexed by lane as before, and frame / mean / m2 are the whole frame's, written at y * width + x.  A clipped lane writes
 // nothing, and no lane belongs to a foreign tile, so foreign pixels keep what they hold.
-struct TileBand {
-    const uint32_t *tiles;   // the band's tiles, ty * tiles_x + tx each
-    uint32_t tiles_x, width, height;
-};
 
 template <bool ACCUMULATE, bool DIRECT, bool TILES>
-__global__ __launch_bounds__(256) void network_compose_kernel(const float4 *__restrict__ found, const uint32_t *__restrict__ wave_offsets,
-                                                              const float *__restrict__ out, uint32_t n, NetCompose c,
+__global__ __launch_bounds__(256) void network_compose_kernel(PixelBand b, const float4 *__restrict__ found,
+                                                              const uint32_t *__restrict__ wave_offsets,
+                                                              const float *__restrict__ out, NetCompose c,
                                                               float4 *__restrict__ frame, float4 *__restrict__ mean,
                                                               float4 *__restrict__ m2, uint32_t subframe_id,
                                                               const uint32_t *__restrict__ frozen,
-                                                              const float4 *__restrict__ direct, TileBand tb)
+                                                              const float4 *__restrict__ direct)
 {
     if (ACCUMULATE && frozen && *frozen != 0u) {
         return;   // the image has converged (converged_freeze_kernel): the running mean stays as it is
     }
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;   // (every lane reaches the ballot)
     bool valid = false;
-    if (i < n) {
+    if (i < b.n) {
         valid = found[i].w != 0.f;
     }
     const uint64_t mask = __builtin_amdgcn_ballot_w64(valid);
     const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-    if (i >= n) {
+    if (i >= b.n) {
         return;
     }
     size_t at = i;
     if constexpr (TILES) {
         uint32_t x, y;
-        if (!tile_pixel(tb.tiles, tb.tiles_x, tb.width, tb.height, i, x, y)) {
+        if (!band_pixel<true>(b, i, x, y)) {
             return;
         }
-        at = (size_t)y * tb.width + x;
+        at = (size_t)y * b.width + x;
     }
     float4 v = make_float4(0.f, 0.f, 0.f, 1.f);   // the miss value of ct_render_subframe
     if (valid) {
@@ -3308,28 +3281,17 @@ __global__ __launch_bounds__(256) void network_compose_kernel(const float4 *__re
     }
 }
 
-hipError_t launch_network_compose(const float4 *found, const uint32_t *wave_offsets, const float *out, uint32_t n, const NetCompose &c,
-                                  float4 *frame, float4 *mean, float4 *m2, uint32_t subframe_id, const uint32_t *frozen,
-                                  const float4 *direct, const uint32_t *tiles, uint32_t tiles_x, uint32_t width, uint32_t height,
-                                  hipStream_t stream)
+hipError_t launch_network_compose(const PixelBand &band, const FlightTemps &t, const NetCompose &c, const float *out,
+                                  const ComposeTarget &dst, const uint32_t *frozen, hipStream_t stream)
 {
-    const uint32_t blocks = (n + 255u) / 256u;
-    const TileBand tb{ tiles, tiles_x, width, height };
-    if (frame) {
-        auto compose = direct ? network_compose_kernel<false, true, false> : network_compose_kernel<false, false, false>;
-        if (tiles) {
-            compose = direct ? network_compose_kernel<false, true, true> : network_compose_kernel<false, false, true>;
-        }
-        hipLaunchKernelGGL(compose, dim3(blocks), dim3(256), 0, stream, found, wave_offsets, out, n, c, frame, (float4 *)nullptr,
-                           (float4 *)nullptr, subframe_id, (const uint32_t *)nullptr, direct, tb);
-    } else {
-        auto compose = direct ? network_compose_kernel<true, true, false> : network_compose_kernel<true, false, false>;
-        if (tiles) {
-            compose = direct ? network_compose_kernel<true, true, true> : network_compose_kernel<true, false, true>;
-        }
-        hipLaunchKernelGGL(compose, dim3(blocks), dim3(256), 0, stream, found, wave_offsets, out, n, c, (float4 *)nullptr, mean, m2,
-                           subframe_id, frozen, direct, tb);
-    }
+#define K(ACCUMULATE, TILES) network_compose_kernel<ACCUMULATE, false, TILES>, network_compose_kernel<ACCUMULATE, true, TILES>
+    static constexpr decltype(&network_compose_kernel<false, false, false>) composes[8] = { K(false, false), K(false, true),
+                                                                                           K(true, false), K(true, true) };
+#undef K
+    const bool accumulate = dst.frame == nullptr, tiles = band.tiles != nullptr, direct = t.direct != nullptr;
+    hipLaunchKernelGGL(composes[4 * accumulate + 2 * tiles + direct], dim3((band.n + 255u) / 256u), dim3(256), 0, stream, band,
+                       (const float4 *)t.found, (const uint32_t *)t.waves, out, c, dst.frame, dst.mean, dst.m2, dst.subframe_id, frozen,
+                       (const float4 *)t.direct);
     return hipGetLastError();
 }
 

@@ -1,0 +1,607 @@
+// ct_neural.cpp -- the first-scatter and network path of the C ABI: the density pyramid and the descriptor gather
+// (ct_collect_descriptors, ct_descriptor_frame), the scattering network (ct_network_create, ct_network_eval) and the network as a
+// renderer (ct_network_render_*), on the handle of ct_handle.hpp.  The network itself is ct_network.hip.
+#include <cmath>
+
+#include "ct_handle.hpp"
+#include "ct_network.hpp"
+
+// VDBCloud::getVoxelSizeInMeters / getVoxelSizeInTermsOfFreePath (VDBCloud.cpp:35-46), DisneyDescriptor.cuh:83
+struct DescriptorScale {
+    float level0, voxel_m;
+};
+static DescriptorScale descriptor_scale(CtHandle h)
+{
+    const float maxs = (float)std::max(h->scene.dims[0], std::max(h->scene.dims[1], h->scene.dims[2]));
+    const float voxel_m = h->scene.cloud_size_m / maxs;
+    const float voxel_fp = voxel_m / h->scene.mean_free_path_m;
+    const float level0 = -ct_log2f(voxel_fp) - 1;
+    return { level0, voxel_m };
+}
+
+// Resources::generateMipmaps (Resources.cpp:169-209) on the device: levels = floor(log2(maxDim)) + 1.
+int ct::ensure_pyramid(CtHandle h)
+{
+    if (h->d_pyramid) {
+        return CT_OK;
+    }
+    const uint32_t nx = h->scene.dims[0], ny = h->scene.dims[1], nz = h->scene.dims[2];
+    uint32_t m = std::max(nx, std::max(ny, nz)), levels = 1;
+    while (m /= 2) {
+        levels++;
+    }
+    if (levels > (uint32_t)kMaxMipLevels) {
+        return fail(h, CT_E_INVAL, "volume too large for the mip pyramid");
+    }
+    MipPyramid mp{};
+    mp.levels = levels;
+    size_t total = 0;
+    for (uint32_t l = 0; l < levels; l++) {
+        mp.nx[l] = (int32_t)std::max(1u, nx >> l);
+        mp.ny[l] = (int32_t)std::max(1u, ny >> l);
+        mp.nz[l] = (int32_t)std::max(1u, nz >> l);
+        mp.offset[l] = (uint32_t)total;
+        total += (size_t)mp.nx[l] * mp.ny[l] * mp.nz[l];
+    }
+    if (total >= (1ull << 32)) {
+        return fail(h, CT_E_INVAL, "volume too large for the mip pyramid");
+    }
+    HIPCHK(h, dmalloc(&h->d_pyramid, total));
+    HIPCHK(h, hipMemcpyAsync(h->d_pyramid, h->d_density, (size_t)nx * ny * nz, hipMemcpyDeviceToDevice, h->stream));
+    for (uint32_t l = 1; l < levels; l++) {
+        HIPCHK(h, launch_mip_level(h->d_pyramid + mp.offset[l - 1], mp.nx[l - 1], mp.ny[l - 1], mp.nz[l - 1],
+                                   h->d_pyramid + mp.offset[l], mp.nx[l], mp.ny[l], mp.nz[l], h->stream));
+    }
+    mp.base = h->d_pyramid;
+    h->pyramid = mp;
+    return CT_OK;
+}
+
+extern "C" int ct_collect_descriptors(CtHandle h, const float *positions_host, const float *directions_host,
+                                      uint32_t count, uint8_t *descriptors_host_out)
+{
+    NEED(h);
+    if (!positions_host || !directions_host || !descriptors_host_out || count == 0 || count > (1u << 20)) {
+        return fail(h, CT_E_INVAL, "ct_collect_descriptors: need 1..2^20 samples, two input arrays and an output array");
+    }
+    const int prc = ensure_pyramid(h);
+    if (prc != CT_OK) {
+        return prc;
+    }
+    const DescriptorScale ds = descriptor_scale(h);
+    DevTemp<float> d_pos, d_dir;
+    DevTemp<uint8_t> d_out;
+    auto run = [&]() -> int {
+        HIPCHK(h, dmalloc(&d_pos, 3 * (size_t)count));
+        HIPCHK(h, dmalloc(&d_dir, 3 * (size_t)count));
+        HIPCHK(h, dmalloc(&d_out, (size_t)count * CT_DESCRIPTOR_BYTES));
+        HIPCHK(h, hipMemcpyAsync(d_pos, positions_host, 3 * (size_t)count * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(d_dir, directions_host, 3 * (size_t)count * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, launch_descriptors(h->dev, h->pyramid, d_pos, d_dir, count, ds.level0, ds.voxel_m, h->scene.cloud_size_m,
+                                     d_out, h->stream));
+        HIPCHK(h, hipMemcpyAsync(descriptors_host_out, d_out, (size_t)count * CT_DESCRIPTOR_BYTES, hipMemcpyDeviceToHost,
+                                 h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return CT_OK;
+    };
+    const int rc = run();
+    if (rc != CT_OK) {
+        hipStreamSynchronize(h->stream);
+    }
+    return rc;
+}
+
+extern "C" int ct_descriptor_frame(CtHandle h, uint32_t subframe_id, const uint32_t rect[4], uint32_t capacity,
+                                   uint8_t *descriptors_dev, float *positions_dev, float *directions_dev, uint32_t *pixels_dev,
+                                   uint32_t *count_out)
+{
+    NEED(h);
+    if (!descriptors_dev || !count_out) {
+        return fail(h, CT_E_INVAL, "ct_descriptor_frame: need a descriptor array and count_out");
+    }
+    *count_out = 0;
+    if (!h->camera_set) {
+        return fail(h, CT_E_STATE, "ct_set_camera has not been called");
+    }
+    const uint32_t W = h->scene.width, H = h->scene.height;
+    const uint32_t x0 = rect ? rect[0] : 0u, y0 = rect ? rect[1] : 0u, x1 = rect ? rect[2] : W, y1 = rect ? rect[3] : H;
+    if (x0 >= x1 || y0 >= y1 || x1 > W || y1 > H || (uint64_t)(x1 - x0) * (y1 - y0) > (1ull << 20)) {
+        return fail(h, CT_E_INVAL, "ct_descriptor_frame: the rect must be non-empty, inside the %u x %u frame and of at most 2^20 pixels", W, H);
+    }
+    const uint32_t rw = x1 - x0, n = rw * (y1 - y0), n_pad = (n + 255u) / 256u * 256u;
+    const DescriptorScale ds = descriptor_scale(h);
+    DevTemp<float4> d_found;
+    DevTemp<uint32_t> d_waves;
+    DevTemp<float> d_pos, d_dir;
+    h->dframe_scatter_ms = h->dframe_gather_ms = 0;
+    auto run = [&]() -> int {
+        // every temporary before any kernel
+        const size_t held = std::max<size_t>(1, std::min<size_t>(capacity, n));   // records the compacting write can produce
+        HIPCHK(h, dmalloc(&d_found, n_pad));
+        HIPCHK(h, dmalloc(&d_waves, n_pad / 64u + 1u));
+        if (!positions_dev) {
+            HIPCHK(h, dmalloc(&d_pos, 3 * held));
+        }
+        if (!directions_dev) {
+            HIPCHK(h, dmalloc(&d_dir, 3 * held));
+        }
+        const int prc = ensure_pyramid(h);
+        if (prc != CT_OK) {
+            return prc;
+        }
+        float *pos = positions_dev ? positions_dev : d_pos.p, *dir = directions_dev ? directions_dev : d_dir.p;
+        HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
+        HIPCHK(h, launch_first_scatter_frame(h->dev, rect_band(x0, y0, rw, y1 - y0), { d_found, d_waves, nullptr }, subframe_id, capacity,
+                                             pos, dir, pixels_dev, h->stream));
+        HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
+        uint32_t count = 0;
+        HIPCHK(h, hipMemcpyAsync(&count, d_waves + n_pad / 64u, sizeof count, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        *count_out = count;
+        float ms = 0;
+        HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+        h->dframe_scatter_ms = ms;
+        if (count > capacity) {
+            return fail(h, CT_E_INVAL, "ct_descriptor_frame: %u valid pixels do not fit a capacity of %u", count, capacity);
+        }
+        if (count == 0) {
+            return CT_OK;
+        }
+        HIPCHK(h, hipEventRecord(h->ev[0], h->stream));   // (not ev[1] again: the host's look at the count is no part of the gather)
+        HIPCHK(h, launch_descriptors(h->dev, h->pyramid, pos, dir, count, ds.level0, ds.voxel_m, h->scene.cloud_size_m, descriptors_dev,
+                                     h->stream));
+        HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+        h->dframe_gather_ms = ms;
+        return CT_OK;
+    };
+    const int rc = run();
+    if (rc != CT_OK) {
+        hipStreamSynchronize(h->stream);
+    }
+    return rc;
+}
+
+extern "C" int ct_debug_descriptor_frame_time(CtHandle h, double *first_scatter_ms_out, double *gather_ms_out)
+{
+    NEED_NOFLUSH(h);
+    if (first_scatter_ms_out) {
+        *first_scatter_ms_out = h->dframe_scatter_ms;
+    }
+    if (gather_ms_out) {
+        *gather_ms_out = h->dframe_gather_ms;
+    }
+    return CT_OK;
+}
+
+// The scattering network (ct_network.hip): the handle's part is the device, the stream and the wait for batches in flight.
+extern "C" int ct_network_create(CtHandle h, const CtNetworkDesc *d, CtNetwork *out)
+{
+    if (!h) {
+        return fail(nullptr, CT_E_INVAL, "null handle");
+    }
+    char err[256] = "";
+    int rc = ct::network_validate(d, out, err, sizeof err);   // (before the handle's device is touched)
+    if (rc != CT_OK) {
+        return fail(h, rc, "%s", err);
+    }
+    NEED(h);
+    rc = ct::network_create(h->device, d, out, err, sizeof err);
+    return rc == CT_OK ? CT_OK : fail(h, rc, "%s", err);
+}
+
+extern "C" int ct_network_eval(CtHandle h, CtNetwork n, const uint8_t *descriptors_dev, const float *aux_dev, uint32_t count,
+                               float *out_dev)
+{
+    NEED(h);
+    if (!n) {
+        return fail(h, CT_E_INVAL, "ct_network_eval: null network");
+    }
+    if (ct::network_device(n) != h->device) {
+        return fail(h, CT_E_INVAL, "ct_network_eval: the network lives on device %d, the handle on device %d", ct::network_device(n),
+                    h->device);
+    }
+    char err[256] = "";
+    const int rc = ct::network_eval(n, h->stream, descriptors_dev, aux_dev, count, out_dev, err, sizeof err);
+    return rc == CT_OK ? CT_OK : fail(h, rc, "%s", err);
+}
+
+// ---- the network as a renderer (ct_network_render_*) ------------------------------------------------------------------
+// Every CT_E_INVAL of the two entry points except the NULL handle and the ids; nothing of the handle is touched.
+static int net_validate(CtHandle h, CtNetwork n, const CtNetworkRender *p, const char *who, bool shards)
+{
+    if (!n || !p) {
+        return fail(h, CT_E_INVAL, "%s: need a network and its parameters", who);
+    }
+    if (p->abi_version != CT_ABI_VERSION) {
+        return fail(h, CT_E_INVAL, "%s: abi_version %u, this library is %u", who, p->abi_version, CT_ABI_VERSION);
+    }
+    const int32_t out_transform = p->transform & ~CT_NET_ADD_SINGLE_SCATTER;
+    if (out_transform != CT_NET_OUT_LINEAR && out_transform != CT_NET_OUT_EXPM1) {
+        return fail(h, CT_E_INVAL, "%s: unknown output transform %d (CT_NET_OUT_LINEAR or CT_NET_OUT_EXPM1, with or without "
+                                   "CT_NET_ADD_SINGLE_SCATTER)", who, p->transform);
+    }
+    if (!std::isfinite(p->rgb_scale[0]) || !std::isfinite(p->rgb_scale[1]) || !std::isfinite(p->rgb_scale[2])) {
+        return fail(h, CT_E_INVAL, "%s: rgb_scale is not finite", who);
+    }
+    if (ct::network_aux_inputs(n) != 1u) {
+        return fail(h, CT_E_INVAL, "%s: the renderer feeds one aux input (the light angle); this network has %u", who,
+                    ct::network_aux_inputs(n));
+    }
+    if (ct::network_device(n) != h->device) {
+        return fail(h, CT_E_INVAL, "%s: the network lives on device %d, the handle on device %d", who, ct::network_device(n), h->device);
+    }
+    if (!shards && h->scene.shard_count > 1u) {
+        return fail(h, CT_E_INVAL, "%s: this handle renders shard %u of %u; a shard's network frame is ct_network_render_shard_subframe / "
+                                   "ct_network_render_shard_accumulate", who, h->scene.shard_index, h->scene.shard_count);
+    }
+    return CT_OK;
+}
+
+// A validated call.  Its bands are made of units: rows of the frame, or (tiles: ct_network_render_shard_*) tiles of the shard's
+// tile list.
+struct NetCall {
+    CtNetwork n;
+    const CtNetworkRender *p;
+    bool accumulate;   // into mean / M2 instead of the frame
+    bool tiles;
+    bool direct;       // the call carries CT_NET_ADD_SINGLE_SCATTER
+    DescriptorScale ds;
+};
+
+// What the entry points do before they run: the handle, every argument (first: a rejected call leaves the handle exactly as it
+// was, batches in flight included), the camera, then the wait for the batches in flight.  bad_ids: NULL, or the message
+// (a format of `who`) that refuses the call's subframe ids.
+static int net_begin(CtHandle h, CtNetwork n, const CtNetworkRender *p, const char *who, bool accumulate, bool tiles, const char *bad_ids,
+                     NetCall &c)
+{
+    NEED_NOFLUSH(h);
+    const int rc = net_validate(h, n, p, who, tiles);
+    if (rc != CT_OK) {
+        return rc;
+    }
+    if (bad_ids) {
+        return fail(h, CT_E_INVAL, bad_ids, who);
+    }
+    if (!h->camera_set) {
+        return fail(h, CT_E_STATE, "ct_set_camera has not been called");
+    }
+    c = { n, p, accumulate, tiles, (p->transform & CT_NET_ADD_SINGLE_SCATTER) != 0, descriptor_scale(h) };
+    return flush(h);
+}
+
+// Units of a band.  Rows: whole rows of at most band_pixels pixels, at least one (a row has at most 12288 pixels), at most 2^20
+// pixels.  Tiles: at most band_pixels / 64, at least one, at most 2^14 (2^20 lanes).
+static uint32_t net_band_units(CtHandle h, const NetCall &c)
+{
+    const uint32_t band_pixels = c.p->band_pixels;
+    const uint32_t cap = (band_pixels == 0u || band_pixels > (1u << 20)) ? (1u << 20) : band_pixels;
+    return c.tiles ? std::max(1u, cap / 64u) : std::min(h->scene.height, std::max(1u, cap / h->scene.width));
+}
+
+// Records the descriptor array may hold at most: 2^20 (a band has no more), or CT_NET_DESC_RECORDS.
+static size_t net_descriptor_limit(CtHandle h)
+{
+    return (size_t)knob_int(h->tune.NET_DESC_RECORDS, 1, 1 << 20, 1 << 20);
+}
+
+// Everything a call needs before its first kernel: the band-sized temporaries and a first piece of the descriptor array.  The
+// stream is idle.  A failed growth leaves what the handle had.  direct: the call carries CT_NET_ADD_SINGLE_SCATTER.
+static int net_reserve(CtHandle h, size_t band_pixels, bool direct)
+{
+    CtHandle_::NetScratch &s = h->net;
+    const size_t n_pad = (band_pixels + 255u) / 256u * 256u;
+    if (direct && n_pad > s.direct_cap) {
+        DevTemp<float4> sun;
+        HIPCHK(h, dmalloc(&sun, n_pad));
+        if (s.direct) {
+            hipFree(s.direct);
+        }
+        s.direct = sun.release();
+        s.direct_cap = n_pad;
+    }
+    if (n_pad > s.band_cap) {
+        DevTemp<float4> found;
+        DevTemp<uint32_t> waves;
+        DevTemp<float> pos, dir, aux, out;
+        HIPCHK(h, dmalloc(&found, n_pad));
+        HIPCHK(h, dmalloc(&waves, n_pad / 64u + 1u));
+        HIPCHK(h, dmalloc(&pos, 3 * n_pad));
+        HIPCHK(h, dmalloc(&dir, 3 * n_pad));
+        HIPCHK(h, dmalloc(&aux, n_pad));
+        HIPCHK(h, dmalloc(&out, n_pad));
+        for (void *old : { (void *)s.found, (void *)s.waves, (void *)s.pos, (void *)s.dir, (void *)s.aux, (void *)s.out }) {
+            if (old) {
+                hipFree(old);
+            }
+        }
+        s.found = found.release();
+        s.waves = waves.release();
+        s.pos = pos.release();
+        s.dir = dir.release();
+        s.aux = aux.release();
+        s.out = out.release();
+        s.band_cap = n_pad;
+    }
+    if (s.desc_cap == 0) {
+        // (CT_NET_DESC_RECORDS: the array never holds more records than this -- what a device without room for the growth leaves
+        // a handle with, for the test that runs a band in pieces)
+        const size_t first = std::min<size_t>(std::min<size_t>(n_pad, 4096), net_descriptor_limit(h));
+        HIPCHK(h, dmalloc(&s.desc, first * CT_DESCRIPTOR_BYTES));
+        s.desc_cap = first;
+    }
+    return CT_OK;
+}
+
+// The descriptor array follows the largest record count seen.  Between bands, the stream idle.  When the device has no room
+// for it the array stays as it is and the band's records are gathered and evaluated in pieces of its size.
+static void net_grow_descriptors(CtHandle h, size_t count)
+{
+    CtHandle_::NetScratch &s = h->net;
+    count = std::min(count, net_descriptor_limit(h));
+    if (count <= s.desc_cap) {
+        return;
+    }
+    uint8_t *bigger = nullptr;
+    if (dmalloc(&bigger, count * CT_DESCRIPTOR_BYTES) != hipSuccess) {
+        (void)hipGetLastError();
+        return;
+    }
+    hipFree(s.desc);
+    s.desc = bigger;
+    s.desc_cap = count;
+}
+
+// The shard's tile list on the device, from ct_shard_tiles, once per handle.  The stream is idle.
+static int net_ensure_tiles(CtHandle h)
+{
+    CtHandle_::NetScratch &s = h->net;
+    if (s.tiles_built) {
+        return CT_OK;
+    }
+    uint32_t count = 0;
+    if (ct_shard_tiles(h->scene.width, h->scene.height, h->scene.shard_index, h->scene.shard_count, nullptr, 0, &count) != CT_OK) {
+        return fail(h, CT_E_INVAL, "internal: ct_shard_tiles refused the handle's own frame");
+    }
+    std::vector<uint32_t> list(std::max(count, 1u), 0u);
+    if (ct_shard_tiles(h->scene.width, h->scene.height, h->scene.shard_index, h->scene.shard_count, list.data(), count, &count) != CT_OK) {
+        return fail(h, CT_E_INVAL, "internal: ct_shard_tiles refused the handle's own frame");
+    }
+    DevTemp<uint32_t> dev;
+    HIPCHK(h, dmalloc(&dev, list.size()));
+    HIPCHK(h, hipMemcpy(dev.p, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    s.tiles = dev.release();
+    s.n_tiles = count;
+    s.tiles_built = true;
+    return CT_OK;
+}
+
+// One band of subframe `sid`, units [unit0, unit0 + units) of the call, into the frame or into mean / M2.
+static int net_band(CtHandle h, const NetCall &c, uint32_t sid, uint32_t unit0, uint32_t units)
+{
+    CtHandle_::NetScratch &s = h->net;
+    const uint32_t W = h->scene.width;
+    const PixelBand band = c.tiles ? tile_band(h->dev, s.tiles + unit0, units) : rect_band(0u, unit0, W, units);
+    const uint32_t npx = band.n, n_pad = (npx + 255u) / 256u * 256u;
+    const FlightTemps temps{ s.found, s.waves, c.direct ? s.direct : nullptr };
+    float ms = 0;
+    HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
+    HIPCHK(h, launch_first_scatter_frame(h->dev, band, temps, sid, npx, s.pos, s.dir, nullptr, h->stream));
+    HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
+    uint32_t count = 0;
+    HIPCHK(h, hipMemcpyAsync(&count, s.waves + n_pad / 64u, sizeof count, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+    s.ms[0] += ms;
+    if (count > npx) {
+        return fail(h, CT_E_HIP, "internal: a band of %u pixels counted %u records", npx, count);
+    }
+    if (count != 0u) {
+        net_grow_descriptors(h, count);
+        for (uint32_t at = 0; at < count;) {
+            const uint32_t piece = (uint32_t)std::min<size_t>(count - at, s.desc_cap);
+            HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
+            HIPCHK(h, launch_descriptors(h->dev, h->pyramid, s.pos + 3 * (size_t)at, s.dir + 3 * (size_t)at, piece, c.ds.level0, c.ds.voxel_m,
+                                         h->scene.cloud_size_m, s.desc, h->stream));
+            HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
+            // l = the direction the light travels: the uniforms hold -l (Sun.cpp:13-18)
+            HIPCHK(h, launch_network_aux(s.dir + 3 * (size_t)at, piece, -h->dev.nlx, -h->dev.nly, -h->dev.nlz, s.aux + at, h->stream));
+            HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
+            char err[256] = "";
+            const int rc = ct::network_eval(c.n, h->stream, s.desc, s.aux + at, piece, s.out + at, err, sizeof err);   // (waits)
+            if (rc != CT_OK) {
+                return fail(h, rc, "%s", err);
+            }
+            HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+            s.ms[1] += ms;
+            HIPCHK(h, hipEventElapsedTime(&ms, h->ev[1], h->ev[2]));
+            s.ms[3] += ms;
+            double net_ms = 0;
+            ct_debug_network_time(c.n, &net_ms);
+            s.ms[2] += net_ms;
+            at += piece;
+        }
+    }
+    const NetCompose compose{ c.p->transform & 0xff, c.p->rgb_scale[0], c.p->rgb_scale[1], c.p->rgb_scale[2] };
+    const size_t first_pixel = c.tiles ? 0 : (size_t)unit0 * W;   // (the tile path writes at y * W + x of the whole frame)
+    const ComposeTarget dst{ c.accumulate ? nullptr : h->d_frame + first_pixel, h->d_mean + first_pixel, h->d_m2 + first_pixel, sid };
+    HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
+    HIPCHK(h, launch_network_compose(band, temps, compose, s.out, dst, h->stop_cadence ? h->d_freeze : nullptr, h->stream));
+    HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
+    HIPCHK(h, hipEventSynchronize(h->ev[1]));
+    HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+    s.ms[3] += ms;
+    if (c.accumulate) {
+        h->accum_ms += ms;
+    }
+    return CT_OK;
+}
+
+// Subframes [first, first + count) band by band.  The caller has validated and flushed.  A frame of the tile path is first
+// filled with the shard's background.
+static int net_run(CtHandle h, const NetCall &c, uint32_t first, uint32_t count)
+{
+    const uint32_t H = h->scene.height, per_band = net_band_units(h, c);
+    for (double &ms : h->net.ms) {
+        ms = 0;
+    }
+    auto run = [&]() -> int {
+        int rc = c.tiles ? net_ensure_tiles(h) : CT_OK;
+        if (rc != CT_OK) {
+            return rc;
+        }
+        // (bands of the row path run bottom to top over H rows; those of the tile path over the list's n_tiles tiles)
+        const uint32_t units = c.tiles ? h->net.n_tiles : H;
+        const size_t band = c.tiles ? (size_t)64 * std::min(per_band, std::max(units, 1u)) : (size_t)h->scene.width * per_band;
+        rc = net_reserve(h, band, c.direct);
+        if (rc == CT_OK) {
+            rc = ensure_pyramid(h);
+        }
+        if (rc != CT_OK) {
+            return rc;
+        }
+        if (c.accumulate) {
+            discard_ahead(h);   // like ct_accumulate: the running mean leaves the order the samples rendered ahead were made for
+        }
+        for (uint32_t k = 0; k < count; k++) {
+            const uint32_t sid = first + k;
+            if (c.tiles && !c.accumulate) {
+                // the shard's background, as ct_render_subframe starts from it: the bands write the own pixels only
+                float ms = 0;
+                HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
+                HIPCHK(h, launch_fill_frame(h->d_frame, h->scene.width, H, h->scene.shard_index, h->scene.shard_count, h->stream));
+                HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
+                HIPCHK(h, hipEventSynchronize(h->ev[1]));
+                HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+                h->net.ms[3] += ms;
+            }
+            for (uint32_t unit0 = 0; unit0 < units; unit0 += per_band) {
+                rc = net_band(h, c, sid, unit0, std::min(per_band, units - unit0));
+                if (rc != CT_OK) {
+                    return rc;
+                }
+            }
+            if (c.accumulate) {
+                if (h->stop_cadence && sid % h->stop_cadence == 0u && sid >= h->stop_min) {   // as ct_accumulate
+                    rc = enqueue_convergence_test(h, sid);
+                    if (rc != CT_OK) {
+                        return rc;
+                    }
+                    HIPCHK(h, hipStreamSynchronize(h->stream));
+                }
+                h->subframes = sid;
+                discard_ahead(h);
+            }
+        }
+        return CT_OK;
+    };
+    const int rc = run();
+    if (rc != CT_OK) {
+        hipStreamSynchronize(h->stream);
+    }
+    return rc;
+}
+
+static int net_subframe(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t subframe_id, float *frame_rgba_dev, bool tiles)
+{
+    NetCall c;
+    int rc = net_begin(h, n, p, tiles ? "ct_network_render_shard_subframe" : "ct_network_render_subframe", false, tiles,
+                       subframe_id == 0 ? "subframe ids are 1-based (Camera.cpp:191)" : nullptr, c);
+    if (rc != CT_OK) {
+        return rc;
+    }
+    rc = net_run(h, c, subframe_id, 1);
+    if (rc != CT_OK) {
+        return rc;
+    }
+    if (frame_rgba_dev) {
+        HIPCHK(h, hipMemcpyAsync(frame_rgba_dev, h->d_frame, (size_t)h->scene.width * h->scene.height * sizeof(float4),
+                                 hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return CT_OK;
+}
+
+extern "C" int ct_network_render_subframe(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t subframe_id, float *frame_rgba_dev)
+{
+    return net_subframe(h, n, p, subframe_id, frame_rgba_dev, false);
+}
+
+extern "C" int ct_network_render_shard_subframe(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t subframe_id,
+                                                float *frame_rgba_dev)
+{
+    return net_subframe(h, n, p, subframe_id, frame_rgba_dev, true);
+}
+
+static int net_accumulate(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t first_subframe_id, uint32_t count, bool tiles)
+{
+    const char *const who = tiles ? "ct_network_render_shard_accumulate" : "ct_network_render_accumulate";
+    NetCall c;
+    const int rc = net_begin(h, n, p, who, true, tiles,
+                             first_subframe_id == 0 || count == 0 ? "%s: subframe ids are 1-based and count must not be 0" : nullptr, c);
+    if (rc != CT_OK) {
+        return rc;
+    }
+    if (first_subframe_id != h->subframes + 1) {
+        return fail(h, CT_E_STATE, "first_subframe_id %u but %u subframes are accumulated", first_subframe_id, h->subframes);
+    }
+    if (count > 0xffffffffu - first_subframe_id + 1u) {
+        return fail(h, CT_E_INVAL, "%s: %u subframes from %u on exceed the 32-bit subframe id", who, count, first_subframe_id);
+    }
+    return net_run(h, c, first_subframe_id, count);
+}
+
+extern "C" int ct_network_render_accumulate(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t first_subframe_id, uint32_t count)
+{
+    return net_accumulate(h, n, p, first_subframe_id, count, false);
+}
+
+extern "C" int ct_network_render_shard_accumulate(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t first_subframe_id,
+                                                  uint32_t count)
+{
+    return net_accumulate(h, n, p, first_subframe_id, count, true);
+}
+
+extern "C" int ct_debug_network_aux(CtHandle h, const float *directions_dev, uint32_t count, float *aux_dev_out)
+{
+    NEED(h);
+    if (count == 0) {
+        return CT_OK;
+    }
+    if (!directions_dev || !aux_dev_out) {
+        return fail(h, CT_E_INVAL, "ct_debug_network_aux: need directions and an output array");
+    }
+    HIPCHK(h, launch_network_aux(directions_dev, count, -h->dev.nlx, -h->dev.nly, -h->dev.nlz, aux_dev_out, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return CT_OK;
+}
+
+extern "C" int ct_debug_network_render_time(CtHandle h, double ms_out[4])
+{
+    NEED_NOFLUSH(h);
+    if (!ms_out) {
+        return fail(h, CT_E_INVAL, "ct_debug_network_render_time: ms_out is NULL");
+    }
+    for (int i = 0; i < 4; i++) {
+        ms_out[i] = h->net.ms[i];
+    }
+    return CT_OK;
+}
+
+extern "C" int ct_debug_network_scratch(CtHandle h, uint64_t out[12])
+{
+    NEED_NOFLUSH(h);
+    if (!out) {
+        return fail(h, CT_E_INVAL, "ct_debug_network_scratch: out is NULL");
+    }
+    const CtHandle_::NetScratch &s = h->net;
+    const void *ptrs[9] = { s.found, s.waves, s.pos, s.dir, s.aux, s.out, s.desc, s.direct, s.tiles };
+    for (int i = 0; i < 9; i++) {
+        out[i] = (uint64_t)(uintptr_t)ptrs[i];
+    }
+    out[9] = s.band_cap;
+    out[10] = s.desc_cap;
+    out[11] = s.direct_cap;
+    return CT_OK;
+}

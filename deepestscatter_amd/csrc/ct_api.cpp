@@ -215,7 +215,7 @@ static void release(CtHandle h)
     }
 #endif
     void *ptrs[] = { h->d_density, h->d_inscatter, h->d_dbricks, h->d_ibricks, h->d_mbricks, h->d_tbricks, h->d_touched[0], h->d_touched[1], h->d_mrows, h->d_mcoarse, h->d_pyramid, h->d_mie, h->d_chopped, h->d_cdf,
-                     h->d_guide, h->d_dist, h->d_dist_tmp, h->d_majorant, h->d_maj_cells, h->d_maj_codes, h->d_frame, h->d_mean, h->d_m2, h->d_screen, h->d_frames_all, h->cont[0], h->cont[1], h->left[0], h->left[1], h->d_cont_count, h->d_cont_total, h->d_primary, h->d_advance, h->d_pixels, h->d_cost, h->d_group_rank, h->d_group_order, h->d_job_group, h->d_job_sub, h->d_queue,
+                     h->d_guide, h->d_dist, h->d_dist_tmp, h->d_majorant, h->d_maj_cells, h->d_maj_codes, h->d_frame, h->d_mean, h->d_m2, h->d_screen, h->d_frames_all, h->cont[0], h->cont[1], h->left[0], h->left[1], h->d_cont_count, h->d_cont_total, h->d_primary, h->d_advance, h->d_pixels, h->d_start, h->d_cost, h->d_group_rank, h->d_group_order, h->d_job_group, h->d_job_sub, h->d_queue,
                      h->d_counters, h->d_colsum, h->d_avg, h->d_freeze, h->d_hit, h->d_cost_plane, h->d_timeline, h->pt.tasks, h->pt.primary, h->pt.frames, h->pt.pixels, h->pt.jg, h->pt.js,
                      h->net.found, h->net.waves, h->net.pos, h->net.dir, h->net.aux, h->net.out, h->net.desc, h->net.direct, h->net.tiles };
     for (void *p : ptrs) {
@@ -981,6 +981,10 @@ static int build_march_layouts(const CtScene *s, CtHandle h, int apron, const Ma
     }
     const size_t dense_bytes = (size_t)(mgx * bgy * bgz) * 128;
     h->mbricks_dense_bytes = h->mbricks_bytes = dense_bytes;
+    // The MARCH kernel addresses footprints with 32-bit byte offsets while the march bricks and the shadow volume's bricks are
+    // each at most 4 GiB (1024^3: 3.4 GB and 2.2 GB), else with 64-bit ones.  CT_WIDE_OFFSETS=1 forces those (tests).
+    const size_t ibricks_bytes = (size_t)(bgx * bgy * bgz) * 128;
+    h->shape.wide = std::max(dense_bytes, ibricks_bytes) > (1ull << 32) || knob_flag(h->tune.WIDE_OFFSETS, false);
     HIPCHK(h, dmalloc(&h->d_mbricks, dense_bytes));
     d.mbricks = h->d_mbricks;
     d.m_bias_x = mbias;
@@ -1294,8 +1298,15 @@ extern "C" int ct_set_light(CtHandle h, const float direction[3], const float co
     return relight(h, s);
 }
 
+// Does the handle keep start records (BatchArgs::start)?  The MARCH kernel's image launches read them; CT_START_RECORDS=0: none (A/B).
+static bool start_records(CtHandle h)
+{
+    return h->scene.estimator == CT_EST_MARCH && !(h->scene.flags & CT_FLAG_SIMPLE_KERNEL) && knob_flag(h->tune.START_RECORDS, true);
+}
+
 // Primary rays of the current pose + the list of this shard's pixels that hit the box, in
 // tile-Morton order, cut into groups of 64 (one wave's worth).
+// ... and, from those, the start record of every slot of the list.
 static int rebuild_queue(CtHandle h)
 {
     TracePhase trace(h, "rebuild_queue");
@@ -1348,12 +1359,13 @@ static int rebuild_queue(CtHandle h)
     }
     h->n_groups = (uint32_t)(list.size() / 64);
     if (h->n_groups > h->groups_capacity) {
-        for (void *p : { (void *)h->d_pixels, (void *)h->d_cost }) {
+        for (void *p : { (void *)h->d_pixels, (void *)h->d_cost, (void *)h->d_start }) {
             if (p) {
                 HIPCHK(h, hipFree(p));
             }
         }
         h->d_pixels = h->d_cost = nullptr;
+        h->d_start = nullptr;
         for (void *p : { (void *)h->d_group_rank, (void *)h->d_group_order }) {
             if (p) {
                 HIPCHK(h, hipFree(p));
@@ -1364,6 +1376,9 @@ static int rebuild_queue(CtHandle h)
         HIPCHK(h, dmalloc(&h->d_cost, 2 * (size_t)h->n_groups));
         HIPCHK(h, dmalloc(&h->d_group_rank, (size_t)h->n_groups));
         HIPCHK(h, dmalloc(&h->d_group_order, (size_t)h->n_groups));
+        if (start_records(h)) {
+            HIPCHK(h, dmalloc(&h->d_start, 2 * (size_t)h->n_groups * 64));
+        }
         h->groups_capacity = h->n_groups;
     }
     h->group_order.resize(h->n_groups);
@@ -1394,6 +1409,12 @@ static int rebuild_queue(CtHandle h)
         HIPCHK(h, hipMemcpyAsync(h->d_pixels, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
                                  h->stream));
         HIPCHK(h, hipMemsetAsync(h->d_cost, 0, 2 * (size_t)h->n_groups * sizeof(uint32_t), h->stream));
+        if (h->d_start) {
+            // (this function alone writes d_primary, d_advance and d_pixels, so the records are as fresh as those)
+            const bool prefix = h->scene.mode != 1 && !h->no_advance;
+            HIPCHK(h, launch_start_records(h->dev, h->d_pixels, h->n_groups * 64u, h->d_primary, prefix ? h->d_advance : nullptr, h->d_start,
+                                           h->stream));
+        }
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
     h->queue_dirty = false;
@@ -1955,6 +1976,7 @@ static int submit_batch(CtHandle h, int slot, float4 *dense_frames, uint32_t fir
     ba.primary = h->d_primary;
     ba.advance = h->no_advance ? nullptr : h->d_advance;
     ba.pixels = h->d_pixels;
+    ba.start = dense ? nullptr : h->d_start;   // (a dense frame is indexed by pixel, which a start record does not hold)
     ba.group_rank = (simple || dense || h->n_chunks <= 1) ? nullptr : h->d_group_rank;   // (one chunk: column g * 64, as ever)
     ba.rank_base = rank_base;
     ba.job_group = h->d_job_group;
@@ -2132,6 +2154,7 @@ int ct::flush(CtHandle h)
         ba.primary = h->d_primary;
         ba.advance = h->no_advance ? nullptr : h->d_advance;
         ba.pixels = h->d_pixels;
+        ba.start = h->d_start;
         ba.job_group = h->d_job_group;
         ba.job_sub = h->d_job_sub;
         ba.n_jobs = 0;                  // q_begin stays all zero: every queue is empty

@@ -311,14 +311,26 @@ CT_DEV uint2 load_footprint_meta(const DevScene &sc, const uint8_t *bricks, int3
     return r;
 }
 
+// The two 8-byte loads of a footprint in a brick array: bytes [0, 8) and [25, 33) from byte (brick << 7 | local).  WIDE = false,
+// for an array of at most 4 GiB: that offset is a 32-bit number and the loads take the array's base from SGPRs -- no 64-bit shift and
+// add between a position and the issue of its loads.  (A template parameter: as a wave-uniform branch in the march step the
+// choice cost 1.4 %, DESIGN.md 4.1 "Round 5".)  The kernels that run once per pose or per light use the wide form.
+template <bool WIDE>
+CT_DEV void load_footprint_pair(const uint8_t *bricks, uint32_t brick, uint32_t local, uint2 &a, uint2 &c)
+{
+    const uint8_t *p = WIDE ? bricks + (((size_t)brick << 7) | local) : bricks + (uint32_t)((brick << 7) | local);
+    __builtin_memcpy(&a, p, 8);
+    __builtin_memcpy(&c, p + 25, 8);
+}
+
 // Footprint + row meta byte from the 3x4x4 march bricks (see DevScene::mbricks): two loads.
-template <bool SPARSE>
+template <bool SPARSE, bool WIDE = true>
 CT_DEV uint2 load_footprint_m(const DevScene &sc, int32_t ix, int32_t iy, int32_t iz, uint32_t &meta)
 {
     const uint32_t x = (uint32_t)(ix + sc.m_bias_x), y = (uint32_t)(iy + sc.brick_bias), z = (uint32_t)(iz + sc.brick_bias);
     const uint32_t bx = __umul24(x, 43691u) >> 17; // x / 3, exact for x < 2^17
-    const uint32_t lx = x - __umul24(bx, 3u);
-    const uint32_t brick = __umul24(z >> 2, (uint32_t)sc.m_gxy) + __umul24(y >> 2, (uint32_t)sc.m_gx) + bx;
+    const uint32_t lx = x - ((bx << 1) + bx);
+    uint32_t brick = __umul24(z >> 2, (uint32_t)sc.m_gxy) + __umul24(y >> 2, (uint32_t)sc.m_gx) + bx;
     const uint32_t local = __umul24(z & 3u, 25u) + __umul24(y & 3u, 5u) + lx;
 #ifdef CT_DEBUG_BOUNDS
     if (bx >= (uint32_t)sc.m_gx || (y >> 2) >= (uint32_t)sc.brick_gy || (z >> 2) >= (uint32_t)sc.brick_gz) {
@@ -327,7 +339,6 @@ CT_DEV uint2 load_footprint_m(const DevScene &sc, int32_t ix, int32_t iy, int32_
         return make_uint2(0u, 0u);
     }
 #endif
-    const uint8_t *p = sc.mbricks + (((size_t)brick << 7) | local);
     if (SPARSE) {
         const uint32_t row = __umul24(z >> 2, (uint32_t)sc.brick_gy) + (y >> 2);
         const uint2 ri = sc.m_rows[row];
@@ -338,11 +349,10 @@ CT_DEV uint2 load_footprint_m(const DevScene &sc, int32_t ix, int32_t iy, int32_
             meta = sc.m_coarse[__umul24(z >> sc.m_cshift, (uint32_t)sc.m_cgxy) + __umul24(y >> sc.m_cshift, (uint32_t)sc.m_cgx) + cx];
             return make_uint2(0u, 0u);
         }
-        p = sc.mbricks + (((size_t)(ri.x + rel) << 7) | local);
+        brick = ri.x + rel;
     }
-    uint2 a, c;
-    __builtin_memcpy(&a, p, 8);       // t_lx, t_lx+1 of row ly at bytes 0,1; of row ly+1 at 5,6; M at 4-lx
-    __builtin_memcpy(&c, p + 25, 8);  // the same one z-slice up
+    uint2 a, c;   // t_lx, t_lx+1 of row ly at bytes 0,1; of row ly+1 at 5,6; M at 4-lx; c: the same one z-slice up
+    load_footprint_pair<WIDE>(sc.mbricks, brick, local, a, c);
     meta = __builtin_amdgcn_perm(a.y, a.x, 0x0c0c0c04u - lx);
     uint2 r;
     r.x = __builtin_amdgcn_perm(a.y, a.x, 0x06050100u);
@@ -495,6 +505,7 @@ CT_DEV uint2 combine_twin(const RawCell &r)
 // event is often the one just read.  `key` = the footprint's byte offset in the brick array (0xffffffff = empty);
 // the volumes are immutable, so an entry never goes stale and may outlive the path that loaded it.
 // zero = true: the footprint is known to be all zero (a shadow-zero row): nothing is loaded, the entry stays as it was.
+template <bool WIDE>
 CT_DEV uint2 fetch_cell_cached(const DevScene &sc, const uint8_t *bricks, f3 p, uint32_t &key, uint2 &cached, bool &reused,
                                bool zero = false)
 {
@@ -506,10 +517,8 @@ CT_DEV uint2 fetch_cell_cached(const DevScene &sc, const uint8_t *bricks, f3 p, 
     const uint32_t off = (brick << 7) | local;   // unique while there are fewer than 2^25 bricks: DevScene::nee_cache
     reused = sc.nee_cache != 0u && off == key;
     if (!reused && !zero) {
-        const uint8_t *q = bricks + (((size_t)brick << 7) | local);
         uint2 a, c;
-        __builtin_memcpy(&a, q, 8);
-        __builtin_memcpy(&c, q + 25, 8);
+        load_footprint_pair<WIDE>(bricks, brick, local, a, c);
         cached.x = __builtin_amdgcn_perm(a.y, a.x, 0x06050100u);
         cached.y = __builtin_amdgcn_perm(c.y, c.x, 0x06050100u);
         key = off;
@@ -517,11 +526,11 @@ CT_DEV uint2 fetch_cell_cached(const DevScene &sc, const uint8_t *bricks, f3 p, 
     return zero ? make_uint2(0u, 0u) : cached;
 }
 
-template <bool SPARSE>
+template <bool SPARSE, bool WIDE = true>
 CT_DEV uint2 fetch_cell_m(const DevScene &sc, f3 p, uint32_t &meta)
 {
     const float x = fmaf(p.x, sc.sx, -0.5f), y = fmaf(p.y, sc.sy, -0.5f), z = fmaf(p.z, sc.sz, -0.5f);
-    return load_footprint_m<SPARSE>(sc, floor_to_int(x), floor_to_int(y), floor_to_int(z), meta);
+    return load_footprint_m<SPARSE, WIDE>(sc, floor_to_int(x), floor_to_int(y), floor_to_int(z), meta);
 }
 
 template <bool FIXED8>

@@ -34,6 +34,9 @@ struct BatchArgs {
                                // (MARCH, primary_advance_kernel) or 4 (DELTA, primary_advance_delta_kernel);
                                // NULL = start at the entry point
     const uint32_t *pixels;    // this shard's box-hitting pixels, 64 per group, 0xffffffff padded
+    const float4 *start;       // image launches of the MARCH kernel: per slot of `pixels` what its samples start from, 2 float4
+                               // (start_records_kernel): the regenerate phase then reads neither pixels, primary nor advance.
+                               // NULL (point tasks, dense frames, the other kernels): it reads those three
     // A launch may cover only a CHUNK of the pixel groups (all S subframes of each): the scratch then has a column of 64
     // entries per group of the chunk, group g's at (group_rank[g] - rank_base) * 64 -- group_rank = the group's place in the
     // cost-sorted order the job list is built in, of which a chunk is a contiguous piece.  NULL: column g * 64 (every group).
@@ -104,6 +107,8 @@ struct LaunchShape {
     bool stats;   // launch the diagnostics build of the kernel (CT_STATS / CT_DEBUG_INVARIANTS at ct_create)
     uint32_t pool_slots = 0;   // exchange kernels (ct_exchange.hpp): slots of the block's path pool in LDS
     uint32_t scatter_waves = 0; // ... and how many of a block's 16 waves only run scatter batches
+    bool wide = false;          // MARCH: a brick array of more than 4 GiB (or CT_WIDE_OFFSETS=1): launch the kernels that address
+                                // footprints with 64-bit offsets
 };
 
 // Evenly split job list (no locality information): point tasks, first launches.
@@ -158,6 +163,8 @@ hipError_t launch_cost_reduce(const uint2 *cost_plane, uint32_t frame_stride, ui
                               hipStream_t stream);
 hipError_t launch_hit_flags(const float4 *primary, uint8_t *flags, uint32_t pixels, hipStream_t stream);
 hipError_t launch_primary_advance(const DevScene &sc, const float4 *primary, float4 *advance, hipStream_t stream);
+hipError_t launch_start_records(const DevScene &sc, const uint32_t *pixels, uint32_t slots, const float4 *primary,
+                                const float4 *advance, float4 *start, hipStream_t stream);
 hipError_t launch_primary_advance_delta(const DevScene &sc, const float4 *primary, float4 *advance, hipStream_t stream);
 // Zeroes up to six short word arrays in ONE dispatch (the counters a launch of the estimator starts from: five memsets
 // of a few words each were five dispatches of 5 us in front of every 10-subframe launch).

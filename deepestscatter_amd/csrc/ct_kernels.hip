@@ -692,12 +692,25 @@ struct MieLds {
     uint16_t guide[kGuideN + 2];
 };
 
-// The MARCH kernel also keeps the chopped phase table there (NEE reads two neighbouring entries of it at
-// every bounce but the first): 40 KiB per block, which 512-thread blocks make affordable (3 per CU, the
-// same 6 waves per SIMD) -- one divergent gather per scatter less on an L1 that is busy 77 % of all cycles.
+// The MARCH kernel keeps both phase tables there too (NEE reads two neighbouring entries: of the un-chopped table at the
+// first bounce, of the chopped one at every later bounce), so a scatter visit issues no vector-memory instruction for the
+// phase function: 56 KiB per block, run as 2 blocks of 768 threads per CU (the same 6 waves per SIMD, the DELTA kernel's
+// block shape) on an L1 whose addresser is busy 0.8 of all cycles.
+// CT_MARCH_PHASE_LDS (A/B, DESIGN.md 4.1 "Round 5"): 2 = as above; 1 = only the chopped table in LDS (40 KiB, 3 blocks of 512
+// threads), read through an LDS pointer, the un-chopped one through a global pointer under the lanes at depth 1; 0 = as 1 but
+// through generic pointers, which the compiler merges into one flat load per scatter visit (until round 4).
+#ifndef CT_MARCH_PHASE_LDS
+#define CT_MARCH_PHASE_LDS 2
+#endif
+constexpr int kMarchThreads = CT_MARCH_PHASE_LDS == 2 ? 768 : 512;
+constexpr int kMarchBlocksPerCu = CT_MARCH_PHASE_LDS == 2 ? 2 : 3;
+
 struct MieLdsFull {
     float cdf[kMieN];
     float chopped[kMieN];
+#if CT_MARCH_PHASE_LDS == 2
+    float mie[kMieN];
+#endif
     uint16_t guide[kGuideN + 2];
 };
 
@@ -706,6 +719,9 @@ CT_DEV void load_tables(const DevScene &sc, MieLdsFull &lds)
     for (int i = threadIdx.x; i < kMieN; i += blockDim.x) {
         lds.cdf[i] = sc.cdf[i];
         lds.chopped[i] = sc.chopped[i];
+#if CT_MARCH_PHASE_LDS == 2
+        lds.mie[i] = sc.mie[i];
+#endif
     }
     for (int i = threadIdx.x; i < kGuideN + 2; i += blockDim.x) {
         lds.guide[i] = sc.guide[i];
@@ -987,12 +1003,16 @@ CT_DEV NeeLoads in_scattering_issue_phase(const DevScene &sc, f3 dir, bool chopp
     return n;
 }
 
-// The same with the chopped table in LDS and the lane's one-entry footprint cache (MARCH kernel; in the DELTA kernel,
-// which is bound by instruction issue at its register limit, the cache cost 2 %); the un-chopped table (first bounce)
-// stays global.
+// The same with the phase tables in LDS and the lane's one-entry footprint cache (MARCH kernel; in the DELTA kernel,
+// which is bound by instruction issue at its register limit, the cache cost 2 %).  The address spaces are explicit: through
+// generic pointers the compiler merges an LDS read and a global read into one flat load, which goes through the texture
+// addresser like a global one.
 // zero = true: the footprint is known to be all zero (CT_MARCH_NEE_SKIP == 2): its load is not issued, the cell is zero.
-template <bool FIXED8>
-CT_DEV NeeLoads in_scattering_issue_lds(const DevScene &sc, const float *lds_chopped, f3 pos, f3 dir, bool chopped,
+typedef const float __attribute__((address_space(3))) LdsFloat;
+typedef const float __attribute__((address_space(1))) GlobalFloat;
+
+template <bool FIXED8, bool WIDE>
+CT_DEV NeeLoads in_scattering_issue_lds(const DevScene &sc, const MieLdsFull &lds, f3 pos, f3 dir, bool chopped,
                                         uint32_t &nee_key, uint2 &nee_cell, bool &reused, bool zero = false)
 {
     NeeLoads n;
@@ -1002,15 +1022,27 @@ CT_DEV NeeLoads in_scattering_issue_lds(const DevScene &sc, const float *lds_cho
     const int32_t i = (int32_t)floorf(x);
     const int32_t j = min(max(i, 0), kMieN - 2);
     float2 pair;
+#if CT_MARCH_PHASE_LDS == 2
+    LdsFloat *table = chopped ? (LdsFloat *)lds.chopped : (LdsFloat *)lds.mie;
+    pair = make_float2(table[j], table[j + 1]);
+#elif CT_MARCH_PHASE_LDS == 1
+    LdsFloat *table = (LdsFloat *)lds.chopped;
+    pair = make_float2(table[j], table[j + 1]);
+    if (!chopped) {
+        GlobalFloat *first = (GlobalFloat *)(sc.mie + j);
+        pair = make_float2(first[0], first[1]);
+    }
+#else
     if (chopped) {
-        pair = make_float2(lds_chopped[j], lds_chopped[j + 1]);
+        pair = make_float2(lds.chopped[j], lds.chopped[j + 1]);
     } else {
         __builtin_memcpy(&pair, sc.mie + j, sizeof pair);
     }
+#endif
     n.a = (i > kMieN - 2) ? pair.y : pair.x;
     n.b = (i < 0) ? pair.x : pair.y;
     n.w = tex_weight<FIXED8>(x);
-    n.cell = fetch_cell_cached(sc, sc.ibricks, pos, nee_key, nee_cell, reused, zero);
+    n.cell = fetch_cell_cached<WIDE>(sc, sc.ibricks, pos, nee_key, nee_cell, reused, zero);
     return n;
 }
 
@@ -1251,6 +1283,47 @@ hipError_t launch_primary_advance(const DevScene &sc, const float4 *primary, flo
     return hipGetLastError();
 }
 
+// What a new sample of an image launch starts from depends on the pose and the pixel list only, so it is gathered once per
+// pose into one 32-byte record per slot of the pixel groups (BatchArgs::start): the regenerate phase then reads two float4
+// side by side at (group, lane) instead of the pixel, then its primary ray, then its prefix, each behind the one before.
+//   start[2 i]     = (where the sample starts: the end of the pre-walked prefix where there is one, else the entry point;
+//                     bits: 0-23 the prefix's steps, 24-29 its clearance (both 0 without a prefix), 30 = padding slot,
+//                     31 = the sample does not start: the ray misses the box or enters outside it)
+//   start[2 i + 1] = (direction, bits of the seed base)
+__global__ __launch_bounds__(256) void start_records_kernel(DevScene sc, const uint32_t *__restrict__ pixels, uint32_t slots,
+                                                            const float4 *__restrict__ primary, const float4 *__restrict__ advance,
+                                                            float4 *__restrict__ start)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= slots) {
+        return;
+    }
+    const uint32_t pixel = pixels[i];
+    float4 r0 = make_float4(0.f, 0.f, 0.f, __uint_as_float(0xc0000000u)), r1 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (pixel != 0xffffffffu) {
+        const float4 p0 = primary[2 * (size_t)pixel];
+        r1 = primary[2 * (size_t)pixel + 1];
+        const bool go = p0.w != 0.f && in_box(sc, mk3(p0.x, p0.y, p0.z));
+        uint32_t bits = go ? 0u : 0x80000000u;
+        r0 = p0;
+        if (go && advance) {
+            r0 = advance[pixel];
+            bits |= __float_as_uint(r0.w) & 0x3fffffffu;
+        }
+        r0.w = __uint_as_float(bits);
+    }
+    start[2 * (size_t)i] = r0;
+    start[2 * (size_t)i + 1] = r1;
+}
+
+// advance: the pixels' prefixes (launch_primary_advance), or NULL where samples take none (mode 1, CT_NO_ADVANCE).
+hipError_t launch_start_records(const DevScene &sc, const uint32_t *pixels, uint32_t slots, const float4 *primary,
+                                const float4 *advance, float4 *start, hipStream_t stream)
+{
+    hipLaunchKernelGGL(start_records_kernel, dim3((slots + 255u) / 256u), dim3(256), 0, stream, sc, pixels, slots, primary, advance, start);
+    return hipGetLastError();
+}
+
 // Persistent wave-scheduled estimator.  Every lane owns one path at a time; a wave repeatedly
 // picks the phase (regenerate / march one step / scatter) that the most lanes are waiting
 // for, so lanes marching through empty space do not hold back lanes that collide every step
@@ -1259,15 +1332,16 @@ hipError_t launch_primary_advance(const DevScene &sc, const float4 *primary, flo
 //
 // The queue hands out jobs = (pixel group, subframe range); a group is 64 consecutive entries of
 // the list of this shard's box-hitting pixels (tile-Morton order).  See BatchArgs for the order.
-// (6 waves per SIMD = 3 blocks of 512 threads per CU: the register allocator must stay within 80 VGPRs.  It
-// uses 75 today; an edit of take_job once moved it to 85 and cost a third of the occupancy, hence the bound.)
+// (6 waves per SIMD = 2 blocks of 768 threads per CU, see MieLdsFull: the register allocator must stay within 80 VGPRs;
+// an edit of take_job once moved it to 85 and cost a third of the occupancy, hence the bound.)
 // COST = false: a launch that does not record the paths' costs (BatchArgs::cost is null: every launch but the one that measures
 // them) runs the kernel compiled without the per-path work counter.  Instantiated for the dense, non-diagnostic kernel.
 // FIXED8 = true (CT_FLAG_TEX_FIXED8): every filter weight is tex_weight<true>; a template parameter, not a run-time test, so
 // that the default kernel's instructions stay as they are.  The free-space skip and the NEE shadow-zero skip hold as they
 // are (see tex_weight).
-template <int MODE, bool STATS, bool SPARSE, bool COST = true, bool FIXED8 = false>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void render_persistent_kernel(DevScene sc, BatchArgs ba)
+// WIDE = true (LaunchShape::wide): a brick array of more than 4 GiB, addressed with 64-bit offsets (load_footprint_pair).
+template <int MODE, bool STATS, bool SPARSE, bool COST = true, bool FIXED8 = false, bool WIDE = false>
+__global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu(6))) void render_persistent_kernel(DevScene sc, BatchArgs ba)
 {
     __shared__ MieLdsFull lds;
     load_tables(sc, lds);
@@ -1427,18 +1501,47 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void r
                 if (take) {
                     const uint32_t s = q >> 6, l = q & 63u;   // (subframe within the job, lane)
                     const uint32_t g = job.g;
-                    const uint32_t pixel = ba.pixels[g * 64u + l];
-                    if (pixel != 0xffffffffu) {
+                    // where the sample starts, which way, its seed base; bits: the prefix's steps | clearance << 24
+                    f3 p_start = mk3(0, 0, 0), p_dir = mk3(0, 0, 1);
+                    uint32_t seed_base = 0, bits = 0;
+                    bool valid, starts = false;
+                    const float4 *prefix = nullptr;   // (still to be loaded)
+                    if (ba.start) {
+                        // image launches: the slot's start record (start_records_kernel), two loads side by side
+                        const float4 *rec = ba.start + 2 * (size_t)(g * 64u + l);
+                        const float4 r0 = rec[0], r1 = rec[1];
+                        const uint32_t w = __float_as_uint(r0.w);
+                        valid = (w & 0x40000000u) == 0u;
+                        starts = (w & 0x80000000u) == 0u;
+                        bits = w & 0x3fffffffu;
+                        p_start = mk3(r0.x, r0.y, r0.z);
+                        p_dir = mk3(r1.x, r1.y, r1.z);
+                        seed_base = __float_as_uint(r1.w);
+                        out_idx = job.base + s * ba.frame_stride + l;
+                    } else {
+                        const uint32_t pixel = ba.pixels[g * 64u + l];
+                        valid = pixel != 0xffffffffu;
+                        if (valid) {
+                            const float4 p0 = ba.primary[2 * (size_t)pixel];
+                            const float4 p1 = ba.primary[2 * (size_t)pixel + 1];
+                            out_idx = ba.frame_stride ? job.base + s * ba.frame_stride + l : pixel;
+                            p_start = mk3(p0.x, p0.y, p0.z);
+                            // image jobs list hitting pixels only; point tasks may miss
+                            starts = p0.w != 0.f && in_box(sc, p_start);
+                            p_dir = mk3(p1.x, p1.y, p1.z);
+                            seed_base = __float_as_uint(p1.w);
+                            if (MODE != 1 && ba.advance) {
+                                prefix = ba.advance + pixel;   // the pixel's pre-walked prefix (primary_advance_kernel)
+                            }
+                        }
+                    }
+                    if (valid) {
                         if (STATS) {
                             iv_dealt += 1;
                         }
-                        const float4 p0 = ba.primary[2 * (size_t)pixel];
-                        const float4 p1 = ba.primary[2 * (size_t)pixel + 1];
-                        out_idx = ba.frame_stride ? job.base + s * ba.frame_stride + l : pixel;
-                        pos = mk3(p0.x, p0.y, p0.z);
-                        const bool hit = p0.w != 0.f; // image jobs list hitting pixels only; point tasks may miss
-                        dir = mk3(p1.x, p1.y, p1.z);
-                        seed = tea4(__float_as_uint(p1.w), job.first + s); // :21
+                        pos = p_start;
+                        dir = p_dir;
+                        seed = tea4(seed_base, job.first + s); // :21
                         rad = mk3(0, 0, 0);
                         depth = 0;
                         work = 0;
@@ -1447,7 +1550,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void r
                             dir = new_direction(lds.cdf, lds.guide, seed, dir);  // :86
                         }
                         // first loop test + depth bump (:28-34); mode 2 has no loop (:134)
-                        bool go = hit && in_box(sc, pos);
+                        bool go = starts;
                         if (MODE != 2 && go) {
                             depth = 1;
                             if (depth == sc.max_depth) {
@@ -1460,15 +1563,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void r
                             T = 1;
                             stepv = scale3(dir, sc.sample_step);
                             inv_maxd = inv_max_advance(sc, stepv);
-                            dfree = 0;
-                            if (MODE != 1 && ba.advance) {
-                                // the pixel's pre-walked prefix (primary_advance_kernel)
-                                const float4 a = ba.advance[pixel];
-                                const uint32_t bits = __float_as_uint(a.w);
+                            if (prefix) {
+                                const float4 a = *prefix;
                                 pos = mk3(a.x, a.y, a.z);
-                                dfree = bits >> 24;
-                                c_dl += bits & 0x00ffffffu;
+                                bits = __float_as_uint(a.w);
                             }
+                            dfree = bits >> 24;
+                            c_dl += bits & 0x00ffffffu;
                             state = ST_MARCH;
                         } else {
                             ba.frames[out_idx] = make_float4(0.f, 0.f, 0.f, 1.f);
@@ -1523,10 +1624,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void r
                     NeeLoads nee;
                     if (CT_MARCH_NEE_SKIP == 1) {
                         if (!nee_zero) {
-                            nee = in_scattering_issue_lds<FIXED8>(sc, lds.chopped, pos, dir, chopped, nee_key, nee_cell, nee_reused);
+                            nee = in_scattering_issue_lds<FIXED8, WIDE>(sc, lds, pos, dir, chopped, nee_key, nee_cell, nee_reused);
                         }
                     } else {
-                        nee = in_scattering_issue_lds<FIXED8>(sc, lds.chopped, pos, dir, chopped, nee_key, nee_cell, nee_reused, nee_zero);
+                        nee = in_scattering_issue_lds<FIXED8, WIDE>(sc, lds, pos, dir, chopped, nee_key, nee_cell, nee_reused, nee_zero);
                     }
                     if (STATS) {
                         st_nee_zero += nee_zero ? 1u : 0u;
@@ -1626,7 +1727,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void r
                 }
                 pos = add3(pos, stepv);
                 uint32_t meta;
-                const uint2 cell = fetch_cell_m<SPARSE>(sc, pos, meta);
+                const uint2 cell = fetch_cell_m<SPARSE, WIDE>(sc, pos, meta);
                 dfree = meta & 0x3fu;
                 c_dl += 1;
                 if (COST) {
@@ -2758,15 +2859,15 @@ hipError_t launch_render_delta(const DevScene &sc, const BatchArgs &ba, LaunchSh
 LaunchShape persistent_shape(int device, bool delta, int blocks_per_cu)
 {
     hipDeviceProp_t prop;
-    LaunchShape s{ 1024, delta ? kDeltaThreads : 512, false };
+    LaunchShape s{ 1024, delta ? kDeltaThreads : kMarchThreads, false };
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) {
-        // as many blocks per CU as the kernel's registers and LDS admit: MARCH 512 threads / 40 KiB,
+        // as many blocks per CU as the kernel's registers and LDS admit: MARCH 768 threads / 56 KiB,
         // DELTA 768 threads / 64 KiB
         int per_cu = 0;
         const hipError_t e = delta ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, render_delta_kernel<0, false, 0>, kDeltaThreads, 0)
-                                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, render_persistent_kernel<0, false, false>, 512, 0);
+                                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, render_persistent_kernel<0, false, false>, kMarchThreads, 0);
         if (e != hipSuccess || per_cu < 1) {
-            per_cu = delta ? 2 : 3;
+            per_cu = delta ? 2 : kMarchBlocksPerCu;
         }
         s.blocks = prop.multiProcessorCount * std::min(per_cu, 8);
         if (blocks_per_cu >= 1 && blocks_per_cu <= 8) {   // (CT_BLOCKS_PER_CU: tuning knob for experiments)
@@ -2776,10 +2877,10 @@ LaunchShape persistent_shape(int device, bool delta, int blocks_per_cu)
     return s;
 }
 
-template <bool STATS, bool SPARSE, bool FIXED8>
+template <bool STATS, bool SPARSE, bool FIXED8, bool WIDE>
 static void launch_render_persistent_mode(const DevScene &sc, const BatchArgs &ba, dim3 grid, dim3 block, hipStream_t stream)
 {
-    if (!STATS && !SPARSE && ba.cost == nullptr) {
+    if (!STATS && !SPARSE && !WIDE && ba.cost == nullptr) {
         switch (sc.mode) {
         case 0: hipLaunchKernelGGL((render_persistent_kernel<0, false, false, false, FIXED8>), grid, block, 0, stream, sc, ba); break;
         case 1: hipLaunchKernelGGL((render_persistent_kernel<1, false, false, false, FIXED8>), grid, block, 0, stream, sc, ba); break;
@@ -2788,37 +2889,47 @@ static void launch_render_persistent_mode(const DevScene &sc, const BatchArgs &b
         return;
     }
     switch (sc.mode) {
-    case 0: hipLaunchKernelGGL((render_persistent_kernel<0, STATS, SPARSE, true, FIXED8>), grid, block, 0, stream, sc, ba); break;
-    case 1: hipLaunchKernelGGL((render_persistent_kernel<1, STATS, SPARSE, true, FIXED8>), grid, block, 0, stream, sc, ba); break;
-    default: hipLaunchKernelGGL((render_persistent_kernel<2, STATS, SPARSE, true, FIXED8>), grid, block, 0, stream, sc, ba); break;
+    case 0: hipLaunchKernelGGL((render_persistent_kernel<0, STATS, SPARSE, true, FIXED8, WIDE>), grid, block, 0, stream, sc, ba); break;
+    case 1: hipLaunchKernelGGL((render_persistent_kernel<1, STATS, SPARSE, true, FIXED8, WIDE>), grid, block, 0, stream, sc, ba); break;
+    default: hipLaunchKernelGGL((render_persistent_kernel<2, STATS, SPARSE, true, FIXED8, WIDE>), grid, block, 0, stream, sc, ba); break;
     }
 }
 
-template <bool FIXED8>
+template <bool FIXED8, bool WIDE>
 static void launch_render_persistent_stats(const DevScene &sc, const BatchArgs &ba, dim3 grid, dim3 block, hipStream_t stream,
                                             bool stats)
 {
     const bool sparse = sc.m_rows != nullptr;
     if (stats) { // diagnostics build of the same kernel
         if (sparse) {
-            launch_render_persistent_mode<true, true, FIXED8>(sc, ba, grid, block, stream);
+            launch_render_persistent_mode<true, true, FIXED8, WIDE>(sc, ba, grid, block, stream);
         } else {
-            launch_render_persistent_mode<true, false, FIXED8>(sc, ba, grid, block, stream);
+            launch_render_persistent_mode<true, false, FIXED8, WIDE>(sc, ba, grid, block, stream);
         }
     } else if (sparse) {
-        launch_render_persistent_mode<false, true, FIXED8>(sc, ba, grid, block, stream);
+        launch_render_persistent_mode<false, true, FIXED8, WIDE>(sc, ba, grid, block, stream);
     } else {
-        launch_render_persistent_mode<false, false, FIXED8>(sc, ba, grid, block, stream);
+        launch_render_persistent_mode<false, false, FIXED8, WIDE>(sc, ba, grid, block, stream);
+    }
+}
+
+template <bool WIDE>
+static void launch_render_persistent_wide(const DevScene &sc, const BatchArgs &ba, dim3 grid, dim3 block, hipStream_t stream, bool stats)
+{
+    if (sc.tex_fixed8) {   // (CT_FLAG_TEX_FIXED8: the same table over the kernels that filter with 1.8 fixed-point weights)
+        launch_render_persistent_stats<true, WIDE>(sc, ba, grid, block, stream, stats);
+    } else {
+        launch_render_persistent_stats<false, WIDE>(sc, ba, grid, block, stream, stats);
     }
 }
 
 hipError_t launch_render_persistent(const DevScene &sc, const BatchArgs &ba, LaunchShape shape, hipStream_t stream)
 {
     const dim3 grid(shape.blocks), block(shape.threads);
-    if (sc.tex_fixed8) {   // (CT_FLAG_TEX_FIXED8: the same table over the kernels that filter with 1.8 fixed-point weights)
-        launch_render_persistent_stats<true>(sc, ba, grid, block, stream, shape.stats);
+    if (shape.wide) {   // (a brick array of more than 4 GiB, or CT_WIDE_OFFSETS=1: the kernels with 64-bit footprint offsets)
+        launch_render_persistent_wide<true>(sc, ba, grid, block, stream, shape.stats);
     } else {
-        launch_render_persistent_stats<false>(sc, ba, grid, block, stream, shape.stats);
+        launch_render_persistent_wide<false>(sc, ba, grid, block, stream, shape.stats);
     }
     return hipGetLastError();
 }

@@ -375,7 +375,7 @@ class CloudTracer:
         direct=True (CT_NET_ADD_SINGLE_SCATTER): a pixel with a record also gets the sun's single-scatter term of that pixel and
         subframe -- what a CT_MODE_SUN_SINGLE_SCATTER tracer renders there -- added behind the scaled network output, so that a
         network trained on the multiple-scatter labels gives the path tracer's picture."""
-        return self._network_render_subframe(self.L.ct_network_render_subframe, net, subframe_id, transform, rgb_scale, band_pixels,
+        return self._network_render_subframe(self.L.ct_network_render_subframe, net.n, subframe_id, transform, rgb_scale, band_pixels,
                                              out, direct)
 
     def _network_render_subframe(self, entry, net, subframe_id, transform, rgb_scale, band_pixels, out, direct):
@@ -390,7 +390,7 @@ class CloudTracer:
                 raise ValueError("out must be a contiguous float32 tensor [H, W, 4]")
             torch.cuda.synchronize(dev)      # the library writes it on the handle's stream, not on torch's
             ptr = C.c_void_p(out.data_ptr())
-        check(entry(self.h, net.n, C.byref(p), subframe_id & 0xFFFFFFFF, ptr), self.h)
+        check(entry(self.h, net, C.byref(p), subframe_id & 0xFFFFFFFF, ptr), self.h)
         return None if out is False else out
 
     def network_render_accumulate(self, net, first_subframe_id: int, count: int, transform="linear", rgb_scale=(1.0, 1.0, 1.0),
@@ -405,7 +405,7 @@ class CloudTracer:
         """ct_network_render_shard_subframe: network_render_subframe on a tracer of any shard_count -- the pixels of the shard's
         own tiles are the unsharded frame's, foreign pixels (0, 0, 0, 0) -- rendered tile band by tile band (band_pixels / 64
         tiles at once).  With shard_count == 1 the bits are network_render_subframe's."""
-        return self._network_render_subframe(self.L.ct_network_render_shard_subframe, net, subframe_id, transform, rgb_scale,
+        return self._network_render_subframe(self.L.ct_network_render_shard_subframe, net.n, subframe_id, transform, rgb_scale,
                                              band_pixels, out, direct)
 
     def network_render_shard_accumulate(self, net, first_subframe_id: int, count: int, transform="linear", rgb_scale=(1.0, 1.0, 1.0),
@@ -414,6 +414,57 @@ class CloudTracer:
         and M2 stay exactly 0, so the sum over the shards is the unsharded image."""
         p = self._network_render_params(transform, rgb_scale, band_pixels, direct)
         check(self.L.ct_network_render_shard_accumulate(self.h, net.n, C.byref(p), first_subframe_id & 0xFFFFFFFF, count), self.h)
+
+    # -- the network baked into a probe table (ct_network_bake, ct_baked_render_*) ------------------------------------
+    def network_bake(self, net, grid, azimuths: int, cosines: int):
+        """ct_network_bake -> deepestscatter_amd.network.Bake: `net` evaluated on grid[0] x grid[1] x grid[2] position nodes x
+        `azimuths` (a multiple of 4) x `cosines` polar nodes, for the light as it is now."""
+        from .network import Bake
+        return Bake(self, net, grid, azimuths, cosines)
+
+    def bake_lookup(self, bake, positions, directions):
+        """ct_debug_bake_lookup: the table lookup for float32 torch tensors [n, 3] on the handle's device -> float32 tensor [n]."""
+        import torch
+        w, d = positions.contiguous(), directions.contiguous()
+        for t in (w, d):
+            if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 3 or t.shape[0] != w.shape[0]:
+                raise ValueError("positions and directions must be float32 tensors [n, 3]")
+        out = torch.empty((w.shape[0],), dtype=torch.float32, device=w.device)
+        torch.cuda.synchronize(w.device)
+        n = int(w.shape[0])
+        check(self.L.ct_debug_bake_lookup(self.h, bake.b, C.c_void_p(w.data_ptr()) if n else None, C.c_void_p(d.data_ptr()) if n else None, n,
+                                          C.c_void_p(out.data_ptr()) if n else None), self.h)
+        return out
+
+    def baked_render_subframe(self, bake, subframe_id: int, transform="linear", rgb_scale=(1.0, 1.0, 1.0), band_pixels: int = 0,
+                              out=None, direct: bool = False):
+        """ct_baked_render_subframe: network_render_subframe with a record's output interpolated from `bake`."""
+        return self._network_render_subframe(self.L.ct_baked_render_subframe, bake.b, subframe_id, transform, rgb_scale, band_pixels,
+                                             out, direct)
+
+    def baked_render_accumulate(self, bake, first_subframe_id: int, count: int, transform="linear", rgb_scale=(1.0, 1.0, 1.0),
+                                band_pixels: int = 0, direct: bool = False):
+        """ct_baked_render_accumulate: network_render_accumulate with the table; all subframes are enqueued and waited for once."""
+        p = self._network_render_params(transform, rgb_scale, band_pixels, direct)
+        check(self.L.ct_baked_render_accumulate(self.h, bake.b, C.byref(p), first_subframe_id & 0xFFFFFFFF, count), self.h)
+
+    def baked_render_shard_subframe(self, bake, subframe_id: int, transform="linear", rgb_scale=(1.0, 1.0, 1.0), band_pixels: int = 0,
+                                    out=None, direct: bool = False):
+        """ct_baked_render_shard_subframe: baked_render_subframe on a tracer of any shard_count (foreign pixels (0, 0, 0, 0))."""
+        return self._network_render_subframe(self.L.ct_baked_render_shard_subframe, bake.b, subframe_id, transform, rgb_scale,
+                                             band_pixels, out, direct)
+
+    def baked_render_shard_accumulate(self, bake, first_subframe_id: int, count: int, transform="linear", rgb_scale=(1.0, 1.0, 1.0),
+                                      band_pixels: int = 0, direct: bool = False):
+        """ct_baked_render_shard_accumulate: baked_render_accumulate on a tracer of any shard_count."""
+        p = self._network_render_params(transform, rgb_scale, band_pixels, direct)
+        check(self.L.ct_baked_render_shard_accumulate(self.h, bake.b, C.byref(p), first_subframe_id & 0xFFFFFFFF, count), self.h)
+
+    def baked_render_time(self) -> float:
+        """GPU milliseconds of the last baked_render_* call (ct_debug_baked_render_time)."""
+        ms = C.c_double(0)
+        check(self.L.ct_debug_baked_render_time(self.h, C.byref(ms)), self.h)
+        return float(ms.value)
 
     def network_scratch(self) -> dict:
         """ct_debug_network_scratch: the device addresses and capacities of the network renderer's scratch (a warm call leaves

@@ -1295,6 +1295,7 @@ extern "C" int ct_set_light(CtHandle h, const float direction[3], const float co
         }
     }
     s.light_intensity = intensity;
+    h->light_epoch++;   // (a CtBake made under the old light is stale from here on, whatever relight answers)
     return relight(h, s);
 }
 

@@ -250,6 +250,8 @@ struct CtHandle_ {
         uint32_t n_tiles = 0;
         bool tiles_built = false;
     } net;
+    uint64_t light_epoch = 0;   // bumped by ct_set_light: a CtBake remembers the one it was baked under
+    double baked_ms = 0;        // the last ct_baked_render_* (ct_debug_baked_render_time)
     uint64_t launches = 0;
     std::string error;
 };

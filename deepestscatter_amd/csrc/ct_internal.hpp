@@ -237,6 +237,8 @@ struct FlightTemps {
 // positions / directions hold `capacity` records, pixels may be NULL.
 hipError_t launch_first_scatter_frame(const DevScene &sc, const PixelBand &band, const FlightTemps &t, uint32_t subframe_id,
                                       uint32_t capacity, float *positions, float *directions, uint32_t *pixels, hipStream_t stream);
+// ... and its first dispatch alone (ct_baked_render_*): found, direct and the waves' counts, neither scanned nor compacted.
+hipError_t launch_first_flights(const DevScene &sc, const PixelBand &band, const FlightTemps &t, uint32_t subframe_id, hipStream_t stream);
 // ct_network_render_*: aux[i] = dot(directions[i], l), left to right; and the band's pixels from the flight's temporaries and the
 // network's outputs of the band's records.
 struct NetCompose {
@@ -251,6 +253,21 @@ struct ComposeTarget {       // a rect: at the band's first pixel; a tile run: t
 hipError_t launch_network_aux(const float *directions, uint32_t count, float lx, float ly, float lz, float *aux, hipStream_t stream);
 hipError_t launch_network_compose(const PixelBand &band, const FlightTemps &t, const NetCompose &c, const float *out,
                                   const ComposeTarget &dst, const uint32_t *frozen, hipStream_t stream);
+// ct_network_bake: the probe table as the lookup sees it (include/cloudtrace.h, "the network baked into a probe table").
+struct BakeTable {
+    const float *table;              // [z][y][x][azimuth][cosine]
+    uint32_t nx, ny, nz, nphi, nc;
+    float lx, ly, lz;                // the light travel direction the table was baked for
+    float ax, ay, az, bx, by, bz;    // the azimuth frame
+};
+// The bake's own kernels: aux[i] = value; table[i * stride + k] = out[i]; and (ct_debug_bake_lookup) the lookup of caller-supplied
+// records.  launch_baked_compose is launch_network_compose with a record's output looked up in the table.
+hipError_t launch_bake_fill(float *aux, uint32_t count, float value, hipStream_t stream);
+hipError_t launch_bake_store(const float *out, uint32_t count, float *table, uint32_t stride, uint32_t k, hipStream_t stream);
+hipError_t launch_bake_lookup(const DevScene &sc, const BakeTable &t, const float *positions, const float *directions, uint32_t count,
+                              float *out, hipStream_t stream);
+hipError_t launch_baked_compose(const DevScene &sc, const PixelBand &band, const FlightTemps &t, const BakeTable &table, const NetCompose &c,
+                                const ComposeTarget &dst, const uint32_t *frozen, hipStream_t stream);
 // Density pyramid (Resources::generateMipmaps) and the descriptor gather.
 constexpr int kMaxMipLevels = 16;
 struct MipPyramid {

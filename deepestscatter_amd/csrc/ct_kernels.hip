@@ -3274,8 +3274,7 @@ __global__ __launch_bounds__(256) void first_scatter_compact_kernel(DevScene sc,
     }
 }
 
-hipError_t launch_first_scatter_frame(const DevScene &sc, const PixelBand &band, const FlightTemps &t, uint32_t subframe_id,
-                                      uint32_t capacity, float *positions, float *directions, uint32_t *pixels, hipStream_t stream)
+hipError_t launch_first_flights(const DevScene &sc, const PixelBand &band, const FlightTemps &t, uint32_t subframe_id, hipStream_t stream)
 {
 #define K(TILES, DIRECT) first_scatter_frame_kernel<false, DIRECT, TILES>, first_scatter_frame_kernel<true, DIRECT, TILES>
     static constexpr decltype(&first_scatter_frame_kernel<false, false, false>) flights[8] = { K(false, false), K(false, true),
@@ -3285,7 +3284,15 @@ hipError_t launch_first_scatter_frame(const DevScene &sc, const PixelBand &band,
     const uint32_t blocks = (band.n + 255u) / 256u;
     hipLaunchKernelGGL(flights[4 * tiles + 2 * direct + (sc.tex_fixed8 ? 1 : 0)], dim3(blocks), dim3(256), 0, stream, sc, band, subframe_id,
                        t.found, t.waves, t.direct);
-    hipError_t e = hipGetLastError();
+    return hipGetLastError();
+}
+
+hipError_t launch_first_scatter_frame(const DevScene &sc, const PixelBand &band, const FlightTemps &t, uint32_t subframe_id,
+                                      uint32_t capacity, float *positions, float *directions, uint32_t *pixels, hipStream_t stream)
+{
+    const bool tiles = band.tiles != nullptr;
+    const uint32_t blocks = (band.n + 255u) / 256u;
+    hipError_t e = launch_first_flights(sc, band, t, subframe_id, stream);
     if (e != hipSuccess) {
         return e;
     }
@@ -3403,6 +3410,172 @@ hipError_t launch_network_compose(const PixelBand &band, const FlightTemps &t, c
     hipLaunchKernelGGL(composes[4 * accumulate + 2 * tiles + direct], dim3((band.n + 255u) / 256u), dim3(256), 0, stream, band,
                        (const float4 *)t.found, (const uint32_t *)t.waves, out, c, dst.frame, dst.mean, dst.m2, dst.subframe_id, frozen,
                        (const float4 *)t.direct);
+    return hipGetLastError();
+}
+
+// =============================================================================================
+// the network baked into a probe table (ct_network_bake, ct_baked_render_*): the bake's two small kernels, the lookup, and the
+// band's pixels from the flight's temporaries and the table.
+// =============================================================================================
+__global__ __launch_bounds__(256) void bake_fill_kernel(float *__restrict__ aux, uint32_t count, float value)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < count) {
+        aux[i] = value;
+    }
+}
+
+// table = the chunk's first probe: polar node k of probe i is table[i * stride + k].
+__global__ __launch_bounds__(256) void bake_store_kernel(const float *__restrict__ out, uint32_t count, float *__restrict__ table,
+                                                         uint32_t stride, uint32_t k)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < count) {
+        table[(size_t)i * stride + k] = out[i];
+    }
+}
+
+hipError_t launch_bake_fill(float *aux, uint32_t count, float value, hipStream_t stream)
+{
+    hipLaunchKernelGGL(bake_fill_kernel, dim3((count + 255u) / 256u), dim3(256), 0, stream, aux, count, value);
+    return hipGetLastError();
+}
+
+hipError_t launch_bake_store(const float *out, uint32_t count, float *table, uint32_t stride, uint32_t k, hipStream_t stream)
+{
+    hipLaunchKernelGGL(bake_store_kernel, dim3((count + 255u) / 256u), dim3(256), 0, stream, out, count, table, stride, k);
+    return hipGetLastError();
+}
+
+// A coordinate in [0, n - 1] split into its cell and the weight in it (a NaN goes to cell 0, weight 0: nothing is read out of
+// bounds whatever the record holds).
+CT_DEV void bake_cell(float f, uint32_t n, uint32_t &i0, float &w)
+{
+    f = fminf(fmaxf(f, 0.f), (float)(n - 1u));
+    i0 = min((uint32_t)(int32_t)f, n - 2u);
+    w = f - (float)i0;
+}
+
+CT_DEV float lerp_(float u, float v, float w) { return u + (v - u) * w; }
+
+// The azimuth of d around the light axis in the table's frame, a number in [0, 4] made without a trigonometric function.
+CT_DEV float bake_azimuth(const BakeTable &t, f3 d)
+{
+    const float px = d.x * t.ax + d.y * t.ay + d.z * t.az, py = d.x * t.bx + d.y * t.by + d.z * t.bz;
+    const float s = fabsf(px) + fabsf(py);
+    if (!(s > 0.f) || !(s < __builtin_inff())) {
+        return 0.f;
+    }
+    const float p = px / s;
+    return py >= 0.f ? 1.0f - p : 3.0f + p;
+}
+
+// The table at (world position w, view d2): 32 taps, the pair of polar nodes of a (corner, azimuth) being 8 adjacent bytes --
+// 16 loads of 8 bytes (4-byte aligned: the compiler is told so) from a table that lives in L2 and the Infinity Cache.  The lerps
+// run over the polar node, then the azimuth, then x, y, z.
+CT_DEV float bake_lookup(const DevScene &sc, const BakeTable &t, f3 w, f3 d)
+{
+    uint32_t x0, y0, z0, k0;
+    float wx, wy, wz, wc;
+    bake_cell((w.x + 0.5f * sc.bx) * ((float)(t.nx - 1u) / sc.bx), t.nx, x0, wx);
+    bake_cell((w.y + 0.5f * sc.by) * ((float)(t.ny - 1u) / sc.by), t.ny, y0, wy);
+    bake_cell((w.z + 0.5f * sc.bz) * ((float)(t.nz - 1u) / sc.bz), t.nz, z0, wz);
+    const float c = d.x * t.lx + d.y * t.ly + d.z * t.lz;
+    bake_cell((c + 1.0f) * (0.5f * (float)(t.nc - 1u)), t.nc, k0, wc);
+    const float ft = bake_azimuth(t, d) * ((float)t.nphi * 0.25f);
+    const float fl = floorf(ft);
+    const float wphi = ft - fl;
+    const uint32_t j0 = (uint32_t)(int32_t)fl % t.nphi, j1 = (j0 + 1u) % t.nphi;
+    float corner[8];
+#pragma unroll
+    for (uint32_t q = 0; q < 8u; q++) {
+        const uint32_t x = x0 + (q & 1u), y = y0 + ((q >> 1) & 1u), z = z0 + (q >> 2);
+        const uint32_t probe = ((z * t.ny + y) * t.nx + x) * t.nphi;   // (entries <= 2^26)
+        float2 a, b;
+        __builtin_memcpy(&a, t.table + (size_t)(probe + j0) * t.nc + k0, sizeof a);
+        __builtin_memcpy(&b, t.table + (size_t)(probe + j1) * t.nc + k0, sizeof b);
+        corner[q] = lerp_(lerp_(a.x, a.y, wc), lerp_(b.x, b.y, wc), wphi);
+    }
+    const float c00 = lerp_(corner[0], corner[1], wx), c10 = lerp_(corner[2], corner[3], wx);
+    const float c01 = lerp_(corner[4], corner[5], wx), c11 = lerp_(corner[6], corner[7], wx);
+    return lerp_(lerp_(c00, c10, wy), lerp_(c01, c11, wy), wz);
+}
+
+__global__ __launch_bounds__(256) void bake_lookup_kernel(DevScene sc, BakeTable t, const float *__restrict__ positions,
+                                                          const float *__restrict__ directions, uint32_t count, float *__restrict__ out)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= count) {
+        return;
+    }
+    const size_t at = 3 * (size_t)i;
+    out[i] = bake_lookup(sc, t, mk3(positions[at], positions[at + 1], positions[at + 2]),
+                         mk3(directions[at], directions[at + 1], directions[at + 2]));
+}
+
+hipError_t launch_bake_lookup(const DevScene &sc, const BakeTable &t, const float *positions, const float *directions, uint32_t count,
+                              float *out, hipStream_t stream)
+{
+    hipLaunchKernelGGL(bake_lookup_kernel, dim3((count + 255u) / 256u), dim3(256), 0, stream, sc, t, positions, directions, count, out);
+    return hipGetLastError();
+}
+
+// network_compose_kernel with a record's output looked up in the table at the record's world position (the flight's temporary)
+// and d2, made again from the pixel as first_scatter_compact_kernel makes it: no ballot, no rank, no wave offsets.  ACCUMULATE,
+// DIRECT, TILES, the frozen test and what a lane without a pixel or a record does are network_compose_kernel's.
+template <bool ACCUMULATE, bool DIRECT, bool TILES>
+__global__ __launch_bounds__(256) void baked_compose_kernel(DevScene sc, PixelBand b, const float4 *__restrict__ found, BakeTable t,
+                                                            NetCompose c, float4 *__restrict__ frame, float4 *__restrict__ mean,
+                                                            float4 *__restrict__ m2, uint32_t subframe_id,
+                                                            const uint32_t *__restrict__ frozen, const float4 *__restrict__ direct)
+{
+    if (ACCUMULATE && frozen && *frozen != 0u) {
+        return;
+    }
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= b.n) {
+        return;
+    }
+    uint32_t x, y;
+    if (!band_pixel<TILES>(b, i, x, y)) {
+        return;
+    }
+    const size_t at = TILES ? (size_t)y * b.width + x : (size_t)i;
+    const float4 f = found[i];
+    float4 v = make_float4(0.f, 0.f, 0.f, 1.f);
+    if (f.w != 0.f) {
+        const f3 dir = normalize3(primary_direction(sc, x, y));
+        const float o = bake_lookup(sc, t, mk3(f.x, f.y, f.z), dir);
+        const float L = c.transform == 1 /* CT_NET_OUT_EXPM1 */ ? ct_expf(o) - 1.0f : o;
+        const float g = L > 0.f ? L : 0.f;
+        v = make_float4(c.sr * g, c.sg * g, c.sb * g, 1.f);
+        if constexpr (DIRECT) {
+            const float4 d = direct[i];
+            v.x += d.x;
+            v.y += d.y;
+            v.z += d.z;
+        }
+    }
+    if (ACCUMULATE) {
+        float4 mu = mean[at], var = m2[at];
+        welford(mu, var, v, subframe_id);
+        mean[at] = mu;
+        m2[at] = var;
+    } else {
+        frame[at] = v;
+    }
+}
+
+hipError_t launch_baked_compose(const DevScene &sc, const PixelBand &band, const FlightTemps &t, const BakeTable &table, const NetCompose &c,
+                                const ComposeTarget &dst, const uint32_t *frozen, hipStream_t stream)
+{
+#define K(ACCUMULATE, TILES) baked_compose_kernel<ACCUMULATE, false, TILES>, baked_compose_kernel<ACCUMULATE, true, TILES>
+    static constexpr decltype(&baked_compose_kernel<false, false, false>) composes[8] = { K(false, false), K(false, true),
+                                                                                         K(true, false), K(true, true) };
+#undef K
+    const bool accumulate = dst.frame == nullptr, tiles = band.tiles != nullptr, direct = t.direct != nullptr;
+    hipLaunchKernelGGL(composes[4 * accumulate + 2 * tiles + direct], dim3((band.n + 255u) / 256u), dim3(256), 0, stream, sc, band,
+                       (const float4 *)t.found, table, c, dst.frame, dst.mean, dst.m2, dst.subframe_id, frozen, (const float4 *)t.direct);
     return hipGetLastError();
 }
 

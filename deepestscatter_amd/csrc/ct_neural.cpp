@@ -1,6 +1,7 @@
 // ct_neural.cpp -- the first-scatter and network path of the C ABI: the density pyramid and the descriptor gather
 // (ct_collect_descriptors, ct_descriptor_frame), the scattering network (ct_network_create, ct_network_eval) and the network as a
-// renderer (ct_network_render_*), on the handle of ct_handle.hpp.  The network itself is ct_network.hip.
+// renderer (ct_network_render_*) and baked into a probe table (ct_network_bake, ct_baked_render_*), on the handle of ct_handle.hpp.
+// The network itself is ct_network.hip.
 #include <cmath>
 
 #include "ct_handle.hpp"
@@ -209,11 +210,9 @@ extern "C" int ct_network_eval(CtHandle h, CtNetwork n, const uint8_t *descripto
 
 // ---- the network as a renderer (ct_network_render_*) ------------------------------------------------------------------
 // Every CT_E_INVAL of the two entry points except the NULL handle and the ids; nothing of the handle is touched.
-static int net_validate(CtHandle h, CtNetwork n, const CtNetworkRender *p, const char *who, bool shards)
+// (in three parts, which the baked entry points below share in the same order: the parameters, the network, the shards)
+static int net_validate_params(CtHandle h, const CtNetworkRender *p, const char *who)
 {
-    if (!n || !p) {
-        return fail(h, CT_E_INVAL, "%s: need a network and its parameters", who);
-    }
     if (p->abi_version != CT_ABI_VERSION) {
         return fail(h, CT_E_INVAL, "%s: abi_version %u, this library is %u", who, p->abi_version, CT_ABI_VERSION);
     }
@@ -225,6 +224,11 @@ static int net_validate(CtHandle h, CtNetwork n, const CtNetworkRender *p, const
     if (!std::isfinite(p->rgb_scale[0]) || !std::isfinite(p->rgb_scale[1]) || !std::isfinite(p->rgb_scale[2])) {
         return fail(h, CT_E_INVAL, "%s: rgb_scale is not finite", who);
     }
+    return CT_OK;
+}
+
+static int net_validate_network(CtHandle h, CtNetwork n, const char *who)
+{
     if (ct::network_aux_inputs(n) != 1u) {
         return fail(h, CT_E_INVAL, "%s: the renderer feeds one aux input (the light angle); this network has %u", who,
                     ct::network_aux_inputs(n));
@@ -232,11 +236,31 @@ static int net_validate(CtHandle h, CtNetwork n, const CtNetworkRender *p, const
     if (ct::network_device(n) != h->device) {
         return fail(h, CT_E_INVAL, "%s: the network lives on device %d, the handle on device %d", who, ct::network_device(n), h->device);
     }
+    return CT_OK;
+}
+
+static int net_validate_shards(CtHandle h, const char *who, bool shards, const char *family)
+{
     if (!shards && h->scene.shard_count > 1u) {
-        return fail(h, CT_E_INVAL, "%s: this handle renders shard %u of %u; a shard's network frame is ct_network_render_shard_subframe / "
-                                   "ct_network_render_shard_accumulate", who, h->scene.shard_index, h->scene.shard_count);
+        return fail(h, CT_E_INVAL, "%s: this handle renders shard %u of %u; a shard's network frame is %s_shard_subframe / "
+                                   "%s_shard_accumulate", who, h->scene.shard_index, h->scene.shard_count, family, family);
     }
     return CT_OK;
+}
+
+static int net_validate(CtHandle h, CtNetwork n, const CtNetworkRender *p, const char *who, bool shards)
+{
+    if (!n || !p) {
+        return fail(h, CT_E_INVAL, "%s: need a network and its parameters", who);
+    }
+    int rc = net_validate_params(h, p, who);
+    if (rc == CT_OK) {
+        rc = net_validate_network(h, n, who);
+    }
+    if (rc == CT_OK) {
+        rc = net_validate_shards(h, who, shards, "ct_network_render");
+    }
+    return rc;
 }
 
 // A validated call.  Its bands are made of units: rows of the frame, or (tiles: ct_network_render_shard_*) tiles of the shard's
@@ -561,6 +585,526 @@ extern "C" int ct_network_render_shard_accumulate(CtHandle h, CtNetwork n, const
                                                   uint32_t count)
 {
     return net_accumulate(h, n, p, first_subframe_id, count, true);
+}
+
+// ---- the network baked into a probe table (ct_network_bake, ct_baked_render_*) -----------------------------------------
+struct CtBake_ {
+    CtHandle h = nullptr;
+    int device = 0;
+    uint32_t grid[3] = { 0, 0, 0 }, azimuths = 0, cosines = 0;
+    uint64_t entries = 0;
+    float *d_table = nullptr;
+    float l[3] = {}, a[3] = {}, b[3] = {};   // the light the table holds and the azimuth frame
+    float cosine[64] = {};
+    uint64_t epoch = 0;                      // the handle's light epoch at the bake
+    double gather_ms = 0, network_ms = 0;
+};
+
+static uint64_t bake_probes_total(const CtBake_ *b)
+{
+    return b->entries / b->cosines;
+}
+
+// The record of probe `index` = ((z Ny + y) Nx + x) Nphi + j: its position node and u_j, made in double and rounded once.
+static void bake_probe(const CtBake_ *b, uint64_t index, float pos[3], float dir[3])
+{
+    const uint32_t j = (uint32_t)(index % b->azimuths);
+    uint64_t cell = index / b->azimuths;
+    const float box[3] = { b->h->dev.bx, b->h->dev.by, b->h->dev.bz };
+    for (int axis = 0; axis < 3; axis++) {
+        const uint32_t i = (uint32_t)(cell % b->grid[axis]);
+        cell /= b->grid[axis];
+        pos[axis] = (float)(-0.5 * (double)box[axis] + (double)box[axis] * (double)i / (double)(b->grid[axis] - 1u));
+    }
+    const double t = (double)j / (double)(b->azimuths / 4u);
+    const double p = t <= 2.0 ? 1.0 - t : t - 3.0, q = t <= 2.0 ? 1.0 - std::fabs(p) : -(1.0 - std::fabs(p));
+    double u[3], len = 0;
+    for (int axis = 0; axis < 3; axis++) {
+        u[axis] = p * (double)b->a[axis] + q * (double)b->b[axis];
+        len += u[axis] * u[axis];
+    }
+    len = std::sqrt(len);
+    for (int axis = 0; axis < 3; axis++) {
+        dir[axis] = (float)(u[axis] / len);
+    }
+}
+
+// The light of the handle as it is now, and a frame (a, b) perpendicular to it: a = normalize(l x e) for the coordinate axis e
+// on which l is shortest, b = l x a.
+static void bake_frame(CtHandle h, CtBake_ *b)
+{
+    const double l[3] = { -(double)h->dev.nlx, -(double)h->dev.nly, -(double)h->dev.nlz };
+    int e = 0;
+    for (int axis = 1; axis < 3; axis++) {
+        if (std::fabs(l[axis]) < std::fabs(l[e])) {
+            e = axis;
+        }
+    }
+    double ev[3] = { 0, 0, 0 };
+    ev[e] = 1;
+    double ll = std::sqrt(l[0] * l[0] + l[1] * l[1] + l[2] * l[2]);
+    const double n[3] = { l[0] / ll, l[1] / ll, l[2] / ll };
+    double a[3] = { n[1] * ev[2] - n[2] * ev[1], n[2] * ev[0] - n[0] * ev[2], n[0] * ev[1] - n[1] * ev[0] };
+    const double al = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+    for (double &v : a) {
+        v /= al;
+    }
+    const double bb[3] = { n[1] * a[2] - n[2] * a[1], n[2] * a[0] - n[0] * a[2], n[0] * a[1] - n[1] * a[0] };
+    for (int axis = 0; axis < 3; axis++) {
+        b->l[axis] = (float)l[axis];
+        b->a[axis] = (float)a[axis];
+        b->b[axis] = (float)bb[axis];
+    }
+    b->epoch = h->light_epoch;
+}
+
+static BakeTable bake_table(const CtBake_ *b)
+{
+    return { b->d_table, b->grid[0], b->grid[1], b->grid[2], b->azimuths, b->cosines, b->l[0], b->l[1], b->l[2],
+             b->a[0], b->a[1], b->a[2], b->b[0], b->b[1], b->b[2] };
+}
+
+// Fills `table` (b->entries floats, allocated) for the handle's light and network n: the probes in chunks through the handle's
+// scratch, one gather per piece and one evaluation per polar node.  b's frame is the new light's already.
+static int bake_run(CtHandle h, CtNetwork n, CtBake_ *b, float *table)
+{
+    CtHandle_::NetScratch &s = h->net;
+    const uint64_t probes = bake_probes_total(b);
+    const size_t chunk = (size_t)std::min<uint64_t>(probes, std::min<size_t>(net_descriptor_limit(h), (size_t)1 << 20));
+    const DescriptorScale ds = descriptor_scale(h);
+    std::vector<float> pos(3 * chunk), dir(3 * chunk);
+    double gather_ms = 0, network_ms = 0;
+    auto run = [&]() -> int {
+        int rc = net_reserve(h, chunk, false);
+        if (rc == CT_OK) {
+            rc = ensure_pyramid(h);
+        }
+        if (rc != CT_OK) {
+            return rc;
+        }
+        net_grow_descriptors(h, chunk);
+        for (uint64_t first = 0; first < probes; first += chunk) {
+            const uint32_t count = (uint32_t)std::min<uint64_t>(chunk, probes - first);
+            for (uint32_t i = 0; i < count; i++) {
+                bake_probe(b, first + i, &pos[3 * (size_t)i], &dir[3 * (size_t)i]);
+            }
+            HIPCHK(h, hipMemcpyAsync(s.pos, pos.data(), 3 * (size_t)count * sizeof(float), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipMemcpyAsync(s.dir, dir.data(), 3 * (size_t)count * sizeof(float), hipMemcpyHostToDevice, h->stream));
+            for (uint32_t at = 0; at < count;) {
+                const uint32_t piece = (uint32_t)std::min<size_t>(count - at, s.desc_cap);
+                float ms = 0;
+                HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
+                HIPCHK(h, launch_descriptors(h->dev, h->pyramid, s.pos + 3 * (size_t)at, s.dir + 3 * (size_t)at, piece, ds.level0, ds.voxel_m,
+                                             h->scene.cloud_size_m, s.desc, h->stream));
+                HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
+                for (uint32_t k = 0; k < b->cosines; k++) {
+                    HIPCHK(h, launch_bake_fill(s.aux, piece, b->cosine[k], h->stream));
+                    char err[256] = "";
+                    rc = ct::network_eval(n, h->stream, s.desc, s.aux, piece, s.out, err, sizeof err);   // (waits)
+                    if (rc != CT_OK) {
+                        return fail(h, rc, "%s", err);
+                    }
+                    double net_ms = 0;
+                    ct_debug_network_time(n, &net_ms);
+                    network_ms += net_ms;
+                    HIPCHK(h, launch_bake_store(s.out, piece, table + (first + at) * b->cosines, b->cosines, k, h->stream));
+                }
+                HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+                gather_ms += ms;
+                at += piece;
+            }
+            HIPCHK(h, hipStreamSynchronize(h->stream));   // (before the host arrays are filled again)
+        }
+        return CT_OK;
+    };
+    const int rc = run();
+    if (rc != CT_OK) {
+        hipStreamSynchronize(h->stream);
+        return rc;
+    }
+    b->gather_ms = gather_ms;
+    b->network_ms = network_ms;
+    return CT_OK;
+}
+
+extern "C" int ct_network_bake(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtBake *out)
+{
+    const char *const who = "ct_network_bake";
+    if (!h) {
+        return fail(nullptr, CT_E_INVAL, "null handle");
+    }
+    if (!n || !d || !out) {
+        return fail(h, CT_E_INVAL, "%s: need a network, a description and out", who);
+    }
+    *out = nullptr;
+    if (d->abi_version != CT_ABI_VERSION) {
+        return fail(h, CT_E_INVAL, "%s: abi_version %u, this library is %u", who, d->abi_version, CT_ABI_VERSION);
+    }
+    uint64_t entries = 1;
+    for (int axis = 0; axis < 3; axis++) {
+        if (d->grid[axis] < 2u || d->grid[axis] > 256u) {
+            return fail(h, CT_E_INVAL, "%s: grid[%d] = %u, a grid has 2 .. 256 nodes per axis", who, axis, d->grid[axis]);
+        }
+        entries *= d->grid[axis];
+    }
+    if (d->azimuths < 4u || d->azimuths > 64u || d->azimuths % 4u != 0u) {
+        return fail(h, CT_E_INVAL, "%s: %u azimuths; a multiple of 4 in 4 .. 64", who, d->azimuths);
+    }
+    if (d->cosines < 2u || d->cosines > 64u) {
+        return fail(h, CT_E_INVAL, "%s: %u cosines; 2 .. 64", who, d->cosines);
+    }
+    entries *= (uint64_t)d->azimuths * d->cosines;
+    if (entries > (1ull << 26)) {
+        return fail(h, CT_E_INVAL, "%s: %llu entries, a table holds at most 2^26", who, (unsigned long long)entries);
+    }
+    NEED_NOFLUSH(h);
+    int rc = net_validate_network(h, n, who);
+    if (rc != CT_OK) {
+        return rc;
+    }
+    rc = flush(h);
+    if (rc != CT_OK) {
+        return rc;
+    }
+    CtBake_ *b = new CtBake_();
+    b->h = h;
+    b->device = h->device;
+    for (int axis = 0; axis < 3; axis++) {
+        b->grid[axis] = d->grid[axis];
+    }
+    b->azimuths = d->azimuths;
+    b->cosines = d->cosines;
+    b->entries = entries;
+    for (uint32_t k = 0; k < b->cosines; k++) {
+        b->cosine[k] = (float)(-1.0 + 2.0 * (double)k / (double)(b->cosines - 1u));
+    }
+    if (dmalloc(&b->d_table, (size_t)entries) != hipSuccess) {   // (before the first kernel)
+        (void)hipGetLastError();
+        delete b;
+        return fail(h, CT_E_NOMEM, "%s: no device memory for a table of %llu entries", who, (unsigned long long)entries);
+    }
+    bake_frame(h, b);
+    rc = bake_run(h, n, b, b->d_table);
+    if (rc != CT_OK) {
+        hipFree(b->d_table);
+        delete b;
+        return rc;
+    }
+    *out = b;
+    return CT_OK;
+}
+
+extern "C" int ct_bake_update(CtHandle h, CtNetwork n, CtBake b)
+{
+    const char *const who = "ct_bake_update";
+    if (!h) {
+        return fail(nullptr, CT_E_INVAL, "null handle");
+    }
+    if (!n || !b) {
+        return fail(h, CT_E_INVAL, "%s: need a network and a bake", who);
+    }
+    NEED_NOFLUSH(h);
+    int rc = net_validate_network(h, n, who);
+    if (rc != CT_OK) {
+        return rc;
+    }
+    if (b->h != h) {
+        return fail(h, CT_E_INVAL, "%s: the bake was made on another handle", who);
+    }
+    rc = flush(h);
+    if (rc != CT_OK) {
+        return rc;
+    }
+    // into a second table: a failure leaves the old table, its light and its frame as they were
+    DevTemp<float> fresh;
+    if (dmalloc(&fresh, (size_t)b->entries) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(h, CT_E_NOMEM, "%s: no device memory for a table of %llu entries", who, (unsigned long long)b->entries);
+    }
+    const CtBake_ before = *b;
+    bake_frame(h, b);
+    rc = bake_run(h, n, b, fresh);
+    if (rc != CT_OK) {
+        *b = before;
+        return rc;
+    }
+    hipFree(b->d_table);
+    b->d_table = fresh.release();
+    return CT_OK;
+}
+
+extern "C" int ct_bake_destroy(CtBake b)
+{
+    if (!b) {
+        return CT_OK;
+    }
+    hipSetDevice(b->device);
+    hipFree(b->d_table);
+    delete b;
+    return CT_OK;
+}
+
+extern "C" int ct_bake_info(CtBake b, CtBakeInfo *out)
+{
+    if (!b || !out) {
+        return fail(b ? b->h : nullptr, CT_E_INVAL, "ct_bake_info: need a bake and out");
+    }
+    *out = CtBakeInfo{};
+    for (int axis = 0; axis < 3; axis++) {
+        out->grid[axis] = b->grid[axis];
+        out->light[axis] = b->l[axis];
+        out->axis_a[axis] = b->a[axis];
+        out->axis_b[axis] = b->b[axis];
+    }
+    out->azimuths = b->azimuths;
+    out->cosines = b->cosines;
+    out->entries = b->entries;
+    for (uint32_t k = 0; k < b->cosines; k++) {
+        out->cosine[k] = b->cosine[k];
+    }
+    out->current = b->epoch == b->h->light_epoch ? 1u : 0u;
+    out->gather_ms = b->gather_ms;
+    out->network_ms = b->network_ms;
+    return CT_OK;
+}
+
+extern "C" int ct_bake_probes(CtBake b, uint64_t first, uint32_t count, float *positions_host_out, float *directions_host_out)
+{
+    if (!b) {
+        return fail(nullptr, CT_E_INVAL, "ct_bake_probes: null bake");
+    }
+    if (!positions_host_out || !directions_host_out) {
+        return fail(b->h, CT_E_INVAL, "ct_bake_probes: need two output arrays");
+    }
+    const uint64_t probes = bake_probes_total(b);
+    if (first > probes || count > probes - first) {
+        return fail(b->h, CT_E_INVAL, "ct_bake_probes: probes %llu .. +%u of %llu", (unsigned long long)first, count,
+                    (unsigned long long)probes);
+    }
+    for (uint32_t i = 0; i < count; i++) {
+        bake_probe(b, first + i, positions_host_out + 3 * (size_t)i, directions_host_out + 3 * (size_t)i);
+    }
+    return CT_OK;
+}
+
+extern "C" int ct_bake_download(CtBake b, float *table_host_out, size_t count)
+{
+    if (!b) {
+        return fail(nullptr, CT_E_INVAL, "ct_bake_download: null bake");
+    }
+    CtHandle h = b->h;
+    if (!table_host_out || count != b->entries) {
+        return fail(h, CT_E_INVAL, "ct_bake_download: need an array of exactly %llu floats", (unsigned long long)b->entries);
+    }
+    NEED(h);
+    HIPCHK(h, hipMemcpy(table_host_out, b->d_table, count * sizeof(float), hipMemcpyDeviceToHost));
+    return CT_OK;
+}
+
+// A bake that belongs to h and holds h's light: CT_E_INVAL / CT_E_STATE otherwise.
+static int bake_foreign(CtHandle h, CtBake b, const char *who)
+{
+    return b->h == h ? CT_OK : fail(h, CT_E_INVAL, "%s: the bake was made on another handle", who);
+}
+static int bake_stale(CtHandle h, CtBake b, const char *who)
+{
+    if (b->epoch != h->light_epoch) {
+        return fail(h, CT_E_STATE, "%s: the handle's light has changed since the bake; ct_bake_update bakes it again", who);
+    }
+    return CT_OK;
+}
+
+extern "C" int ct_debug_bake_lookup(CtHandle h, CtBake b, const float *positions_dev, const float *directions_dev, uint32_t count,
+                                    float *out_dev)
+{
+    const char *const who = "ct_debug_bake_lookup";
+    if (!h) {
+        return fail(nullptr, CT_E_INVAL, "null handle");
+    }
+    if (!b || (count != 0u && (!positions_dev || !directions_dev || !out_dev))) {
+        return fail(h, CT_E_INVAL, "%s: need a bake, positions, directions and an output array", who);
+    }
+    NEED_NOFLUSH(h);
+    int rc = bake_foreign(h, b, who);
+    if (rc == CT_OK) {
+        rc = bake_stale(h, b, who);
+    }
+    if (rc == CT_OK) {
+        rc = flush(h);
+    }
+    if (rc != CT_OK || count == 0u) {
+        return rc;
+    }
+    HIPCHK(h, launch_bake_lookup(h->dev, bake_table(b), positions_dev, directions_dev, count, out_dev, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return CT_OK;
+}
+
+// net_begin for a bake: the same order -- arguments, ids, camera -- then the bake's light, then the wait.
+static int baked_begin(CtHandle h, CtBake b, const CtNetworkRender *p, const char *who, bool accumulate, bool tiles, const char *bad_ids,
+                       NetCall &c)
+{
+    if (!h) {
+        return fail(nullptr, CT_E_INVAL, "null handle");
+    }
+    if (!b || !p) {
+        return fail(h, CT_E_INVAL, "%s: need a bake and its parameters", who);
+    }
+    NEED_NOFLUSH(h);
+    int rc = net_validate_params(h, p, who);
+    if (rc == CT_OK) {
+        rc = bake_foreign(h, b, who);
+    }
+    if (rc == CT_OK) {
+        rc = net_validate_shards(h, who, tiles, "ct_baked_render");
+    }
+    if (rc != CT_OK) {
+        return rc;
+    }
+    if (bad_ids) {
+        return fail(h, CT_E_INVAL, bad_ids, who);
+    }
+    if (!h->camera_set) {
+        return fail(h, CT_E_STATE, "ct_set_camera has not been called");
+    }
+    rc = bake_stale(h, b, who);
+    if (rc != CT_OK) {
+        return rc;
+    }
+    c = { nullptr, p, accumulate, tiles, (p->transform & CT_NET_ADD_SINGLE_SCATTER) != 0, descriptor_scale(h) };
+    return flush(h);
+}
+
+// net_run without gather and network: per band the flights and one kernel that looks the table up and forms the pixels.
+// Everything is enqueued and waited for once (the convergence test keeps its own wait); one event pair times the call.
+static int baked_run(CtHandle h, CtBake b, const NetCall &c, uint32_t first, uint32_t count)
+{
+    const uint32_t W = h->scene.width, H = h->scene.height, per_band = net_band_units(h, c);
+    h->baked_ms = 0;
+    auto run = [&]() -> int {
+        int rc = c.tiles ? net_ensure_tiles(h) : CT_OK;
+        if (rc != CT_OK) {
+            return rc;
+        }
+        CtHandle_::NetScratch &s = h->net;
+        const uint32_t units = c.tiles ? s.n_tiles : H;
+        const size_t band_lanes = c.tiles ? (size_t)64 * std::min(per_band, std::max(units, 1u)) : (size_t)W * per_band;
+        rc = net_reserve(h, band_lanes, c.direct);
+        if (rc != CT_OK) {
+            return rc;
+        }
+        if (c.accumulate) {
+            discard_ahead(h);
+        }
+        const BakeTable table = bake_table(b);
+        const NetCompose compose{ c.p->transform & 0xff, c.p->rgb_scale[0], c.p->rgb_scale[1], c.p->rgb_scale[2] };
+        const FlightTemps temps{ s.found, s.waves, c.direct ? s.direct : nullptr };
+        HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
+        for (uint32_t k = 0; k < count; k++) {
+            const uint32_t sid = first + k;
+            if (c.tiles && !c.accumulate) {
+                HIPCHK(h, launch_fill_frame(h->d_frame, W, H, h->scene.shard_index, h->scene.shard_count, h->stream));
+            }
+            for (uint32_t unit0 = 0; unit0 < units; unit0 += per_band) {
+                const uint32_t n_units = std::min(per_band, units - unit0);
+                const PixelBand band = c.tiles ? tile_band(h->dev, s.tiles + unit0, n_units) : rect_band(0u, unit0, W, n_units);
+                const size_t first_pixel = c.tiles ? 0 : (size_t)unit0 * W;
+                const ComposeTarget dst{ c.accumulate ? nullptr : h->d_frame + first_pixel, h->d_mean + first_pixel, h->d_m2 + first_pixel, sid };
+                HIPCHK(h, launch_first_flights(h->dev, band, temps, sid, h->stream));
+                HIPCHK(h, launch_baked_compose(h->dev, band, temps, table, compose, dst, h->stop_cadence ? h->d_freeze : nullptr, h->stream));
+            }
+            if (c.accumulate) {
+                if (h->stop_cadence && sid % h->stop_cadence == 0u && sid >= h->stop_min) {   // as ct_accumulate
+                    rc = enqueue_convergence_test(h, sid);
+                    if (rc != CT_OK) {
+                        return rc;
+                    }
+                    HIPCHK(h, hipStreamSynchronize(h->stream));
+                }
+                h->subframes = sid;
+                discard_ahead(h);
+            }
+        }
+        HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        float ms = 0;
+        HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[2]));
+        h->baked_ms = ms;
+        return CT_OK;
+    };
+    const int rc = run();
+    if (rc != CT_OK) {
+        hipStreamSynchronize(h->stream);
+    }
+    return rc;
+}
+
+static int baked_subframe(CtHandle h, CtBake b, const CtNetworkRender *p, uint32_t subframe_id, float *frame_rgba_dev, bool tiles)
+{
+    NetCall c;
+    int rc = baked_begin(h, b, p, tiles ? "ct_baked_render_shard_subframe" : "ct_baked_render_subframe", false, tiles,
+                         subframe_id == 0 ? "%s: subframe ids are 1-based (Camera.cpp:191)" : nullptr, c);
+    if (rc != CT_OK) {
+        return rc;
+    }
+    rc = baked_run(h, b, c, subframe_id, 1);
+    if (rc != CT_OK) {
+        return rc;
+    }
+    if (frame_rgba_dev) {
+        HIPCHK(h, hipMemcpyAsync(frame_rgba_dev, h->d_frame, (size_t)h->scene.width * h->scene.height * sizeof(float4),
+                                 hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return CT_OK;
+}
+
+static int baked_accumulate(CtHandle h, CtBake b, const CtNetworkRender *p, uint32_t first_subframe_id, uint32_t count, bool tiles)
+{
+    const char *const who = tiles ? "ct_baked_render_shard_accumulate" : "ct_baked_render_accumulate";
+    NetCall c;
+    const int rc = baked_begin(h, b, p, who, true, tiles,
+                               first_subframe_id == 0 || count == 0 ? "%s: subframe ids are 1-based and count must not be 0" : nullptr, c);
+    if (rc != CT_OK) {
+        return rc;
+    }
+    if (first_subframe_id != h->subframes + 1) {
+        return fail(h, CT_E_STATE, "first_subframe_id %u but %u subframes are accumulated", first_subframe_id, h->subframes);
+    }
+    if (count > 0xffffffffu - first_subframe_id + 1u) {
+        return fail(h, CT_E_INVAL, "%s: %u subframes from %u on exceed the 32-bit subframe id", who, count, first_subframe_id);
+    }
+    return baked_run(h, b, c, first_subframe_id, count);
+}
+
+extern "C" int ct_baked_render_subframe(CtHandle h, CtBake b, const CtNetworkRender *p, uint32_t subframe_id, float *frame_rgba_dev)
+{
+    return baked_subframe(h, b, p, subframe_id, frame_rgba_dev, false);
+}
+
+extern "C" int ct_baked_render_shard_subframe(CtHandle h, CtBake b, const CtNetworkRender *p, uint32_t subframe_id, float *frame_rgba_dev)
+{
+    return baked_subframe(h, b, p, subframe_id, frame_rgba_dev, true);
+}
+
+extern "C" int ct_baked_render_accumulate(CtHandle h, CtBake b, const CtNetworkRender *p, uint32_t first_subframe_id, uint32_t count)
+{
+    return baked_accumulate(h, b, p, first_subframe_id, count, false);
+}
+
+extern "C" int ct_baked_render_shard_accumulate(CtHandle h, CtBake b, const CtNetworkRender *p, uint32_t first_subframe_id, uint32_t count)
+{
+    return baked_accumulate(h, b, p, first_subframe_id, count, true);
+}
+
+extern "C" int ct_debug_baked_render_time(CtHandle h, double *gpu_ms_out)
+{
+    NEED_NOFLUSH(h);
+    if (!gpu_ms_out) {
+        return fail(h, CT_E_INVAL, "ct_debug_baked_render_time: gpu_ms_out is NULL");
+    }
+    *gpu_ms_out = h->baked_ms;
+    return CT_OK;
 }
 
 extern "C" int ct_debug_network_aux(CtHandle h, const float *directions_dev, uint32_t count, float *aux_dev_out)

@@ -131,11 +131,60 @@ namespace DeepestScatter
                            "ct_network_render_accumulate");
         }
 
-    private:
+    protected:
         std::shared_ptr<const NetworkFile> file;
         CtNetworkRender params;
         CtNetwork network = nullptr;
         CtGroupNetwork groupNetwork = nullptr;   // with --gpus: one network per shard, destroyed before the group
+    };
+
+    // The reference's default renderer (BakedRenderer): the network evaluated once per light on a probe grid (ct_network_bake,
+    // --net-baked NX,NY,NZ,NPHI,NC) and every subframe interpolated from that table (ct_baked_render_*): no gather and no
+    // network per subframe.  The table is baked in init, which follows Sun::init and so every ct_set_light, and baked again
+    // should the light have changed since.  One GPU only: main refuses --net-baked with --gpus.
+    class BakedRenderer : public NetworkRenderer
+    {
+    public:
+        BakedRenderer(std::shared_ptr<Context> context, std::shared_ptr<const NetworkFile> file, const CtNetworkRender& params, const CtBakeDesc& desc)
+            : NetworkRenderer(std::move(context), std::move(file), params), desc(desc) {}
+        ~BakedRenderer() override
+        {
+            if (bake) ct_bake_destroy(bake);   // (before the network and the handle)
+        }
+
+        void init() override
+        {
+            NetworkRenderer::init();
+            if (context->group) throw std::runtime_error("--net-baked renders on one GPU only");
+            if (!bake) Context::check(ct_network_bake(context->handle, network, &desc, &bake), context->handle, "ct_network_bake");
+        }
+
+        void render(float* frameResultBuffer) override
+        {
+            applyCamera();
+            refresh();
+            Context::check(ct_baked_render_subframe(context->handle, bake, &params, subframeId, frameResultBuffer), context->handle,
+                           "ct_baked_render_subframe");
+        }
+
+        void renderAccumulate(uint32_t first, uint32_t count, bool /*enqueue: the call waits once, at its end*/) override
+        {
+            applyCamera();
+            refresh();
+            Context::check(ct_baked_render_accumulate(context->handle, bake, &params, first, count), context->handle,
+                           "ct_baked_render_accumulate");
+        }
+
+    private:
+        void refresh()   // a light set since the bake: bake again
+        {
+            CtBakeInfo info;
+            Context::check(ct_bake_info(bake, &info), context->handle, "ct_bake_info");
+            if (!info.current) Context::check(ct_bake_update(context->handle, network, bake), context->handle, "ct_bake_update");
+        }
+
+        CtBakeDesc desc;
+        CtBake bake = nullptr;
     };
 
     class Camera : public SceneItem                                              // Camera.h:16-103

@@ -13,6 +13,8 @@
 //                               ct_group_network_render_accumulate: every GPU renders its own tiles) instead of the
 //                               estimator; --net-direct adds the sun's single-scatter term (CT_NET_ADD_SINGLE_SCATTER), so that a
 //                               network trained on the multiple-scatter labels gives the picture --mode total gives
+//              [--net-baked NX,NY,NZ,NPHI,NC]   with --network: bake the network once per light on that probe grid (ct_network_bake)
+//                               and interpolate every subframe from the table (ct_baked_render_accumulate); one GPU, not with --gpus
 //   <cloud> = file.vdb | procedural:<N>[:<seed>] | file.f32grid
 //
 //   cloudtrace collect <cloud>|@list.txt [--scene-id I] [--scenes N] [--jobs K] [--gpus ..] [--batch 2048] [--light L] [--size-m M] [--out DIR] [--data DIR] [--estimator ..] [--tex-fixed8]
@@ -70,6 +72,8 @@ namespace
         std::string networkPath;                                                  // --network FILE: the scattering network renders instead of the estimator
         std::shared_ptr<const NetworkFile> network;                               // ... read and checked before anything is created
         CtNetworkRender networkRender{ CT_ABI_VERSION, CT_NET_OUT_LINEAR, { 1.f, 1.f, 1.f }, 0 };   // --net-transform, --net-scale
+        bool netBaked = false;                                                    // --net-baked NX,NY,NZ,NPHI,NC: render from a baked probe table (BakedRenderer)
+        CtBakeDesc bake{ CT_ABI_VERSION, { 0, 0, 0 }, 0, 0 };
         bool netDirect = false;                                                   // --net-direct: CT_NET_ADD_SINGLE_SCATTER joins networkRender.transform
         bool collect = false;                                                     // `cloudtrace collect ...`
         int32_t sceneId = 0;
@@ -268,8 +272,9 @@ namespace
             std::replace(stem.begin(), stem.end(), ':', '_');
             auto outputPath = std::filesystem::path(opt.outDir) / (stem + "." + toString(lightDirection) + "." + PathTracingRenderer::NAME + "." + opt.format);
             // installFramework + installApp: Sun, VDBCloud, CloudMaterial, Camera in this order (installers.cpp:28-38)
-            std::shared_ptr<PathTracingRenderer> renderer = opt.network ? std::make_shared<NetworkRenderer>(context, opt.network, opt.networkRender)
-                                                                        : std::make_shared<PathTracingRenderer>(context);
+            std::shared_ptr<PathTracingRenderer> renderer = !opt.network ? std::make_shared<PathTracingRenderer>(context)
+                : opt.netBaked ? std::make_shared<BakedRenderer>(context, opt.network, opt.networkRender, opt.bake)
+                               : std::make_shared<NetworkRenderer>(context, opt.network, opt.networkRender);
             renderer->estimator = opt.estimator;
             auto sun = std::make_shared<Sun>(std::make_shared<DirectionalLight>(scene.light), context);
             auto cloud = std::make_shared<VDBCloud>(std::make_shared<Cloud::Model>(scene.cloud.model), context, resources);
@@ -291,7 +296,7 @@ int main(int argc, char* argv[])
     try
     {
         Options opt;
-        if (argc < 2) { std::cerr << "usage: cloudtrace <cloud> [--size WxH] [--spp N] [--mode total|multi|single] [--light L] [--size-m M] [--out DIR] [--data DIR] [--unfused] [--display] [--estimator march|delta] [--format exr|pfm] [--gpus N|a,b,c] [--tex-fixed8] [--network FILE [--net-transform linear|expm1] [--net-scale r,g,b] [--net-direct]] (--network with --gpus: every GPU renders its own tiles)\n"; return 2; }
+        if (argc < 2) { std::cerr << "usage: cloudtrace <cloud> [--size WxH] [--spp N] [--mode total|multi|single] [--light L] [--size-m M] [--out DIR] [--data DIR] [--unfused] [--display] [--estimator march|delta] [--format exr|pfm] [--gpus N|a,b,c] [--tex-fixed8] [--network FILE [--net-transform linear|expm1] [--net-scale r,g,b] [--net-direct] [--net-baked NX,NY,NZ,NPHI,NC]] (--network with --gpus: every GPU renders its own tiles; --net-baked: one GPU)\n"; return 2; }
         int first = 2;
         bool lightsGiven = false;
         opt.cloud = argv[1];
@@ -342,6 +347,12 @@ int main(int argc, char* argv[])
                 if (std::sscanf(next().c_str(), "%f,%f,%f", &s[0], &s[1], &s[2]) != 3) throw std::invalid_argument("--net-scale r,g,b");
             }
             else if (a == "--net-direct") opt.netDirect = true;
+            else if (a == "--net-baked")
+            {
+                CtBakeDesc& b = opt.bake;
+                if (std::sscanf(next().c_str(), "%u,%u,%u,%u,%u", &b.grid[0], &b.grid[1], &b.grid[2], &b.azimuths, &b.cosines) != 5) throw std::invalid_argument("--net-baked NX,NY,NZ,NPHI,NC");
+                opt.netBaked = true;
+            }
             else if (a == "--tex-fixed8") opt.texFixed8 = true;
             else if (a == "--estimator")
             {
@@ -373,6 +384,8 @@ int main(int argc, char* argv[])
         if (opt.collect) return collectScenes(opt);
 
         if (opt.netDirect) opt.networkRender.transform |= CT_NET_ADD_SINGLE_SCATTER;   // (after the loop: --net-transform may follow it)
+        if (opt.netBaked && opt.networkPath.empty()) throw std::invalid_argument("--net-baked bakes the network of --network FILE");
+        if (opt.netBaked && !opt.devices.empty()) throw std::invalid_argument("--net-baked renders on one GPU: it cannot be combined with --gpus");
         if (!opt.networkPath.empty())
         {
             // read and checked against the header's formula here, before a renderer exists: a malformed file costs no device

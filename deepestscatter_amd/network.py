@@ -8,6 +8,8 @@ residual MLP of the paper the reference implements (Kallweit et al. 2017), param
     reference_forward   numpy, with the rounding points of the definition: what the device is held to
     Network             a CtNetwork on a CloudTracer's device
     render_values       numpy restatement of what ct_network_render_* makes of the outputs (transform, clamp, rgb scale)
+    Bake                a CtBake: the network evaluated on a probe grid (ct_network_bake), which ct_baked_render_* interpolate
+    bake_azimuth / bake_lookup_reference   numpy float32 restatement of the table lookup: what the device is held to
     save_weights / load_weights   the weight file `cloudtrace --network` reads
 
 State-dict names (the mapping an exported model needs): blocks.k.fc1 = W1_k, c1_k; blocks.k.fc2 = W2_k, c2_k (k = 0 .. 9);
@@ -203,6 +205,67 @@ def render_values(out, transform="linear", rgb_scale=(1.0, 1.0, 1.0), expf=None,
     return px
 
 
+def bake_azimuth(directions, axis_a, axis_b) -> np.ndarray:
+    """The azimuth t in [0, 4] of float32 directions [n, 3] around the light axis, in the frame (axis_a, axis_b) of a CtBakeInfo:
+    px = d . a, py = d . b (left to right), s = |px| + |py|, t = 0 when s is 0 or not finite, else p = px / s and
+    t = 1 - p (py >= 0) or 3 + p.  No trigonometric function: float32 numpy gives the device's bits."""
+    d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+    a, b = np.asarray(axis_a, np.float32).reshape(3), np.asarray(axis_b, np.float32).reshape(3)
+    with np.errstate(all="ignore"):
+        px = (d[:, 0] * a[0] + d[:, 1] * a[1]) + d[:, 2] * a[2]
+        py = (d[:, 0] * b[0] + d[:, 1] * b[1]) + d[:, 2] * b[2]
+        s = np.abs(px) + np.abs(py)
+        ok = np.isfinite(s) & (s > 0)
+        p = px / np.where(ok, s, np.float32(1))
+        t = np.where(py >= 0, np.float32(1) - p, np.float32(3) + p)
+    return np.where(ok, t, np.float32(0)).astype(np.float32)
+
+
+def bake_lookup_reference(table, info, box, positions, directions) -> np.ndarray:
+    """ct_debug_bake_lookup in numpy float32, the definition the device is held to (include/cloudtrace.h, "the network baked
+    into a probe table").  table: float32 of info["entries"] values in the table's order; info: Bake.info (grid, azimuths, cosines,
+    light, axis_a, axis_b); box: the box size (bx, by, bz) as float32; positions, directions: float32 [n, 3] -> float32 [n]."""
+    f32 = np.float32
+    nx, ny, nz = (int(v) for v in info["grid"])
+    nphi, nc = int(info["azimuths"]), int(info["cosines"])
+    T = np.ascontiguousarray(table, f32).reshape(nz, ny, nx, nphi, nc)
+    w = np.ascontiguousarray(positions, f32).reshape(-1, 3)
+    d = np.ascontiguousarray(directions, f32).reshape(-1, 3)
+    box = np.asarray(box, f32).reshape(3)
+    l = np.asarray(info["light"], f32).reshape(3)
+
+    def cell(f, n):
+        f = np.minimum(np.maximum(f, f32(0)), f32(n - 1)).astype(f32)
+        i0 = np.minimum(f.astype(np.int64), n - 2)
+        return i0, (f - i0.astype(f32)).astype(f32)
+
+    def lerp(u, v, wt):
+        return (u + ((v - u).astype(f32) * wt).astype(f32)).astype(f32)
+
+    cells = []
+    for axis, n in enumerate((nx, ny, nz)):
+        scale = f32(f32(n - 1) / box[axis])
+        cells.append(cell(((w[:, axis] + f32(0.5) * box[axis]).astype(f32) * scale).astype(f32), n))
+    (x0, wx), (y0, wy), (z0, wz) = cells
+    c = ((d[:, 0] * l[0] + d[:, 1] * l[1]).astype(f32) + d[:, 2] * l[2]).astype(f32)
+    k0, wc = cell(((c + f32(1.0)).astype(f32) * f32(f32(0.5) * f32(nc - 1))).astype(f32), nc)
+    ft = (bake_azimuth(d, info["axis_a"], info["axis_b"]) * f32(f32(nphi) * f32(0.25))).astype(f32)
+    fl = np.floor(ft).astype(f32)
+    wphi = (ft - fl).astype(f32)
+    j0 = fl.astype(np.int64) % nphi
+    j1 = (j0 + 1) % nphi
+
+    def corner(z, y, x):
+        at = [lerp(T[z, y, x, j, k0], T[z, y, x, j, k0 + 1], wc) for j in (j0, j1)]
+        return lerp(at[0], at[1], wphi)
+
+    c00 = lerp(corner(z0, y0, x0), corner(z0, y0, x0 + 1), wx)
+    c10 = lerp(corner(z0, y0 + 1, x0), corner(z0, y0 + 1, x0 + 1), wx)
+    c01 = lerp(corner(z0 + 1, y0, x0), corner(z0 + 1, y0, x0 + 1), wx)
+    c11 = lerp(corner(z0 + 1, y0 + 1, x0), corner(z0 + 1, y0 + 1, x0 + 1), wx)
+    return lerp(lerp(c00, c10, wy), lerp(c01, c11, wy), wz)
+
+
 # The weight file: a 32-byte little-endian header -- magic "CTNW", u32 version, blocks, width, aux, head_layers, u64 weight
 # count -- and then weight_count float32 values in the order of CtNetworkDesc.weights_host.
 WEIGHT_MAGIC = b"CTNW"
@@ -300,3 +363,66 @@ class Network:
         if rc != _lib.CT_OK:
             raise _lib.CloudTraceError(rc, "ct_debug_network_time")
         return float(ms.value)
+
+
+class Bake:
+    """A CtBake of `net` on its tracer (ct_network_bake): the network evaluated on a grid of grid[0] x grid[1] x grid[2] position
+    nodes x `azimuths` view azimuths around the light x `cosines` polar nodes, which CloudTracer.baked_render_* interpolate in
+    place of gather and network.  Close it before the tracer; after tracer.set_light call update()."""
+
+    def __init__(self, tracer, net, grid, azimuths: int, cosines: int):
+        self.L = _lib.load()
+        self.tracer = tracer
+        d = _lib.CtBakeDesc(_lib.CT_ABI_VERSION, (C.c_uint32 * 3)(*[int(v) for v in grid]), int(azimuths), int(cosines))
+        b = C.c_void_p()
+        check(self.L.ct_network_bake(tracer.h, net.n, C.byref(d), C.byref(b)), tracer.h)
+        self.b = b
+
+    def close(self):
+        if getattr(self, "b", None):
+            self.L.ct_bake_destroy(self.b)
+            self.b = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def update(self, net):
+        """ct_bake_update: bake again in place, for the tracer's light as it is now and for `net`."""
+        check(self.L.ct_bake_update(self.tracer.h, net.n, self.b), self.tracer.h)
+
+    @property
+    def info(self) -> dict:
+        """ct_bake_info: grid, azimuths, cosines, entries, light, axis_a, axis_b (float32 [3]), cosine (float32 [cosines]),
+        current, gather_ms, network_ms."""
+        i = _lib.CtBakeInfo()
+        check(self.L.ct_bake_info(self.b, C.byref(i)), self.tracer.h)
+        return {"grid": tuple(int(v) for v in i.grid), "azimuths": int(i.azimuths), "cosines": int(i.cosines), "entries": int(i.entries),
+                "light": np.array(i.light[:], np.float32), "axis_a": np.array(i.axis_a[:], np.float32),
+                "axis_b": np.array(i.axis_b[:], np.float32), "cosine": np.array(i.cosine[:int(i.cosines)], np.float32),
+                "current": bool(i.current), "gather_ms": float(i.gather_ms), "network_ms": float(i.network_ms)}
+
+    def probes(self, first: int = 0, count: int | None = None):
+        """ct_bake_probes -> (positions, directions) float32 [count, 3], the records the bake used, in index order."""
+        if count is None:
+            i = self.info
+            count = i["entries"] // i["cosines"] - first
+        pos, d = np.empty((count, 3), np.float32), np.empty((count, 3), np.float32)
+        check(self.L.ct_bake_probes(self.b, first, count, pos.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p)), self.tracer.h)
+        return pos, d
+
+    def table(self) -> np.ndarray:
+        """ct_bake_download -> float32 [Nz, Ny, Nx, azimuths, cosines], the raw network outputs."""
+        i = self.info
+        t = np.empty(i["entries"], np.float32)
+        check(self.L.ct_bake_download(self.b, t.ctypes.data_as(C.c_void_p), t.size), self.tracer.h)
+        nx, ny, nz = i["grid"]
+        return t.reshape(nz, ny, nx, i["azimuths"], i["cosines"])

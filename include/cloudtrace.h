@@ -601,6 +601,90 @@ CT_API int ct_debug_network_aux(CtHandle h, const float *directions_dev, uint32_
  * descriptor gather, [2] the network, [3] the aux kernel and the kernel that forms the pixels (and accumulates them). */
 CT_API int ct_debug_network_render_time(CtHandle h, double ms_out[4]);
 
+/* ---- the network baked into a probe table ---------------------------------------------------
+ *
+ * The reference's default renderer is its second neural one: BakedRenderer keeps light probes on a grid and interpolates them
+ * (bakedCamera.cu, lightProbeMaterial.cu, LightProbe.cuh; not available, like DisneyModel.py, so THE DEFINITION BELOW IS THIS
+ * PROJECT'S).  It rests on a symmetry of the renderer above: for a fixed cloud, light and network a record's output is a
+ * function of five numbers -- the position, the azimuth of the view around the light axis (all the descriptor sees of the view:
+ * eX = normalize(eZ x view)) and aux = d2 . l (which the descriptor does not depend on).  ct_network_bake evaluates the network
+ * once on a regular grid over those five; a subframe is then the first flight and a 32-tap interpolation: no gather, no network,
+ * no record count, no compaction, no host wait between bands or subframes.  A new light is a re-bake (ct_bake_update), as
+ * ct_set_light is a rebuild of the shadow volume.  What the table costs in accuracy is its resolution: the caller's trade.
+ *
+ * The grid.  b = the box size (dims / max dim, the box centred at 0 like every position of this ABI).  Nx, Ny, Nz = grid, each
+ * 2 .. 256; Nphi = azimuths, a multiple of 4 in 4 .. 64; Nc = cosines, 2 .. 64; entries = Nx Ny Nz Nphi Nc <= 2^26.
+ *   - position node i of an axis: -b/2 + b * i / (N - 1);
+ *   - azimuth: the library picks an orthonormal pair a, b perpendicular to l when it bakes (CtBakeInfo).  For a direction d:
+ *     px = d.a, py = d.b (each left to right in float32), s = |px| + |py|; t = 0 when s is 0 or not finite, otherwise p = px / s
+ *     and t = py >= 0 ? 1 - p : 3 + p, a number in [0, 4] made without a trigonometric function.  Azimuth node j sits at
+ *     t_j = j / (Nphi / 4); its probe direction is u_j = normalize(p a + q b) with p = 1 - t_j, q = 1 - |p| for t_j <= 2 and
+ *     p = t_j - 3, q = -(1 - |p|) beyond: a unit vector perpendicular to the light;
+ *   - polar node k: cosine[k] = -1 + 2 k / (Nc - 1);
+ *   - probe (z, y, x, j) has index ((z Ny + y) Nx + x) Nphi + j and the record (position node, u_j); ct_bake_probes returns
+ *     exactly the floats the bake used;
+ *   - table[index * Nc + k] = ct_network_eval's value for the descriptor ct_collect_descriptors gives that record, with
+ *     aux = cosine[k]: raw outputs, the transform is applied at lookup.  CT_FLAG_TEX_FIXED8 applies to the gather as everywhere.
+ *
+ * The lookup for (world position w, direction d2), which ct_debug_bake_lookup exposes.  Per spatial axis
+ * fx = (w.x + 0.5f * bx) * ((float)(Nx - 1) / bx) clamped to [0, Nx - 1], x0 = min((int)fx, Nx - 2), wx = fx - x0; polar
+ * c = d2 . l left to right, fc = (c + 1.0f) * (0.5f * (Nc - 1)) clamped and split into k0, wc the same way; azimuth
+ * ft = t(d2) * (Nphi * 0.25f), j0 = (int)floor(ft), wphi = ft - j0, j0 %= Nphi, j1 = (j0 + 1) % Nphi.  Every lerp is
+ * u + (v - u) * w with the product rounded before the sum, over k, then j, then x, y, z.
+ *
+ * The pixel is exactly ct_network_render_*'s pixel with `out` replaced by the lookup at the record's world position and d2:
+ * flight, seed, validity, transform, g, rgb_scale, the CT_NET_ADD_SINGLE_SCATTER term, the miss value and a shard's foreign
+ * pixels are the same; "fused = the loop subframe + ct_accumulate, bit for bit" holds; the frozen test and
+ * ct_set_stop_when_converged behave as there.  band_pixels sizes only the flight's temporaries (the handle's scratch of the
+ * renderer above, which the bake's chunks use too) and the image does not depend on it.  A render call enqueues all its bands and
+ * subframes and waits once (the convergence test keeps its own wait); a warm call allocates nothing.
+ *
+ * The bake sends the probes through gather and network in chunks of at most min(CT_NET_DESC_RECORDS, 2^20) records, one gather
+ * per chunk serving all Nc evaluations; the result does not depend on the chunk size.  The table is allocated before the first
+ * kernel: CT_E_NOMEM leaves the handle -- and in ct_bake_update the old table -- as they were.
+ *
+ * Errors, checked before anything changes, in the order of the renderer above.  CT_E_INVAL: a NULL argument (a NULL handle is
+ * answered without a device); a wrong abi_version; a size outside the ranges above, or too many entries; a network with
+ * aux != 1 or on another device; a bake made on another handle; a sharded handle on the unsharded entry points;
+ * subframe_id == 0 or count == 0; an unknown transform or a non-finite scale; ct_bake_probes / ct_bake_download out of range.
+ * CT_E_STATE: rendering, or ct_debug_bake_lookup, with a bake whose light is no longer the handle's (ct_bake_update bakes it
+ * again); first_subframe_id != subframes + 1. */
+typedef struct CtBakeDesc {
+    uint32_t abi_version;   /* must be CT_ABI_VERSION */
+    uint32_t grid[3];       /* Nx, Ny, Nz */
+    uint32_t azimuths;      /* Nphi */
+    uint32_t cosines;       /* Nc */
+} CtBakeDesc;
+typedef struct CtBake_ *CtBake;
+typedef struct CtBakeInfo {
+    uint32_t grid[3], azimuths, cosines;
+    uint64_t entries;
+    float light[3];                /* l: the twice-normalised travel direction the table was baked for */
+    float axis_a[3], axis_b[3];    /* orthonormal, perpendicular to l; chosen by the library */
+    float cosine[64];              /* the aux value of polar node k, k < cosines */
+    uint32_t current;              /* 1 while the handle's light is the one the table was baked for */
+    double gather_ms, network_ms;  /* GPU time of the last bake / update */
+} CtBakeInfo;
+
+CT_API int ct_network_bake(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtBake *out);
+CT_API int ct_bake_update(CtHandle h, CtNetwork n, CtBake b);   /* bake again, in place: after ct_set_light, or for another network */
+CT_API int ct_bake_destroy(CtBake b);                           /* NULL is a no-op; destroy before h */
+CT_API int ct_bake_info(CtBake b, CtBakeInfo *out);
+/* Probes first .. first + count - 1 (index order) as the bake made them: 3 floats each.  first + count <= entries / cosines. */
+CT_API int ct_bake_probes(CtBake b, uint64_t first, uint32_t count, float *positions_host_out, float *directions_host_out);
+CT_API int ct_bake_download(CtBake b, float *table_host_out, size_t count);   /* count must equal entries */
+/* Diagnostic: the lookup on caller-supplied records (3 floats each, device memory) -> count floats.  count == 0: CT_OK. */
+CT_API int ct_debug_bake_lookup(CtHandle h, CtBake b, const float *positions_dev, const float *directions_dev, uint32_t count,
+                                float *out_dev);
+
+/* ct_network_render_subframe / _accumulate / _shard_subframe / _shard_accumulate with the table in the network's place. */
+CT_API int ct_baked_render_subframe(CtHandle h, CtBake b, const CtNetworkRender *p, uint32_t subframe_id, float *frame_rgba_dev);
+CT_API int ct_baked_render_accumulate(CtHandle h, CtBake b, const CtNetworkRender *p, uint32_t first_subframe_id, uint32_t count);
+CT_API int ct_baked_render_shard_subframe(CtHandle h, CtBake b, const CtNetworkRender *p, uint32_t subframe_id, float *frame_rgba_dev);
+CT_API int ct_baked_render_shard_accumulate(CtHandle h, CtBake b, const CtNetworkRender *p, uint32_t first_subframe_id, uint32_t count);
+/* Diagnostic: GPU milliseconds of the last ct_baked_render_* of this handle, one event pair around the call's kernels. */
+CT_API int ct_debug_baked_render_time(CtHandle h, double *gpu_ms_out);
+
 /* ---- data access -------------------------------------------------------------------- */
 
 /* BufferBind<T>(buffer) map/copy, src/Util/BufferBind.h:11-74 (e.g. Camera.cpp:161,239-240).

@@ -1,0 +1,88 @@
+#!/usr/bin/env python3
+"""What rendering from a baked probe table (ct_network_bake, ct_baked_render_*) costs beside the network renderer, and what the
+table's resolution costs in accuracy: f-7's scene (the 512^3 procedural cloud, 1024 x 1024, default pose) and a seeded random
+ScatterNet(200, 1, 3), warm calls, medians.  Per grid (16^3, 32^3, 64^3, each x 16 azimuths x 8 polar nodes) one JSON line:
+  the bake's gather and network GPU ms (CtBakeInfo) and its wall time, the table's size in bytes;
+  the baked subframe's GPU ms (ct_debug_baked_render_time) and wall ms beside ct_network_render_subframe's stage sum and wall
+  ms -- the two routes take turns in the same run;
+  the relative L2 distance between the two routes' means after --subframes subframes, and the same distance relative to the
+  network route's variation about its mean level over the lit pixels (--bias raises the output bias so that the seeded
+  network's outputs, small and negative as they come, are positive: negative outputs render black on both routes).
+Needs a GPU.  No threshold: the table's resolution is the user's trade.
+    python tools/baked_render_time.py [--repeats 5] [--volume 512] [--size 1024] [--subframes 16] [--grids 16 32 64]
+                                      [--azimuths 16] [--cosines 8] [--direct] [--bias 1.0]"""
+import argparse, json, statistics, sys, time
+from pathlib import Path
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+
+
+def wall_ms(fn):
+    t = time.perf_counter()
+    fn()
+    return (time.perf_counter() - t) * 1e3
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--volume", type=int, default=512)
+    ap.add_argument("--size", type=int, default=1024)
+    ap.add_argument("--subframes", type=int, default=16)
+    ap.add_argument("--grids", type=int, nargs="+", default=[16, 32, 64])
+    ap.add_argument("--azimuths", type=int, default=16)
+    ap.add_argument("--cosines", type=int, default=8)
+    ap.add_argument("--direct", action="store_true")
+    ap.add_argument("--bias", type=float, default=1.0)
+    a = ap.parse_args()
+    import numpy as np
+    import torch
+    import deepestscatter_amd as ds
+    from deepestscatter_amd import network as N
+    tr = ds.CloudTracer(ds.make_procedural_cloud(a.volume), width=a.size, height=a.size)
+    torch.manual_seed(1)
+    module = N.ScatterNet(200, 1, 3)
+    with torch.no_grad():
+        module.out.bias += a.bias      # a random network's outputs are small and of one sign: negative ones render black
+    net = N.Network(tr, module)
+    med = statistics.median
+    common = {"network": [200, 1, 3], "output_bias_raised_by": a.bias, "volume": a.volume, "frame": [a.size, a.size], "repeats": a.repeats,
+              "direct": a.direct}
+
+    # the network route's image, once
+    tr.reset()
+    tr.network_render_accumulate(net, 1, a.subframes, direct=a.direct)
+    want = tr.mean()[..., :3].astype(np.float64)
+    lit = want[..., 0] > 0
+    level = want[lit].mean() if lit.any() else 0.0      # the image is nearly one level (a random network): the variation is what a table can get wrong
+    common.update({"lit_pixels": int(lit.sum()), "network_route_mean_level": float(level),
+                   "network_route_min_max": [float(want[lit].min()), float(want[lit].max())] if lit.any() else None})
+
+    for g in a.grids:
+        t0 = time.perf_counter()
+        bake = tr.network_bake(net, (g, g, g), a.azimuths, a.cosines)
+        bake_wall = (time.perf_counter() - t0) * 1e3
+        info = bake.info
+        baked_gpu, baked_wall, net_gpu, net_wall = [], [], [], []
+        for i in range(a.repeats + 1):          # (the first pair is the warm-up)
+            baked_wall.append(wall_ms(lambda: tr.baked_render_subframe(bake, 1, out=False, direct=a.direct)))
+            baked_gpu.append(tr.baked_render_time())
+            net_wall.append(wall_ms(lambda: tr.network_render_subframe(net, 1, out=False, direct=a.direct)))
+            net_gpu.append(sum(tr.network_render_time()))
+        tr.reset()
+        acc_wall = wall_ms(lambda: tr.baked_render_accumulate(bake, 1, a.subframes, direct=a.direct))
+        got = tr.mean()[..., :3].astype(np.float64)
+        rel = float(np.sqrt(((got - want) ** 2).sum() / (want ** 2).sum())) if lit.any() else None
+        var = ((want - level)[lit] ** 2).sum()
+        rel_var = float(np.sqrt(((got - want)[lit] ** 2).sum() / var)) if lit.any() and var > 0 else None
+        print(json.dumps({"route": "ct_baked_render_subframe", **common, "grid": [g, g, g, a.azimuths, a.cosines],
+                          "entries": info["entries"], "table_bytes": 4 * info["entries"], "bake_gather_ms": info["gather_ms"],
+                          "bake_network_ms": info["network_ms"], "bake_wall_ms": bake_wall,
+                          "baked_gpu_ms": med(baked_gpu[1:]), "baked_wall_ms": med(baked_wall[1:]),
+                          "network_route_gpu_ms": med(net_gpu[1:]), "network_route_wall_ms": med(net_wall[1:]),
+                          "subframes": a.subframes, "baked_accumulate_wall_ms_per_subframe": acc_wall / a.subframes,
+                          "relative_l2_of_the_means": rel,
+                          "relative_l2_against_the_variation_about_the_mean_level": rel_var}), flush=True)
+        bake.close()
+    net.close()
+    tr.close()

@@ -416,11 +416,28 @@ class CloudTracer:
         check(self.L.ct_network_render_shard_accumulate(self.h, net.n, C.byref(p), first_subframe_id & 0xFFFFFFFF, count), self.h)
 
     # -- the network baked into a probe table (ct_network_bake, ct_baked_render_*) ------------------------------------
-    def network_bake(self, net, grid, azimuths: int, cosines: int):
+    def network_bake(self, net, grid, azimuths: int, cosines: int, sparse: bool = False):
         """ct_network_bake -> deepestscatter_amd.network.Bake: `net` evaluated on grid[0] x grid[1] x grid[2] position nodes x
-        `azimuths` (a multiple of 4) x `cosines` polar nodes, for the light as it is now."""
+        `azimuths` (a multiple of 4) x `cosines` polar nodes, for the light as it is now.  sparse: ct_network_bake_sparse, which
+        bakes only the probes a first flight can reach; every frame is the same."""
         from .network import Bake
-        return Bake(self, net, grid, azimuths, cosines)
+        return Bake(self, net, grid, azimuths, cosines, sparse)
+
+    def bake_mask(self, grid):
+        """ct_debug_bake_mask: the sparse bake's mask of a grid (Nx, Ny, Nz) on this handle, no network needed
+        -> (cells uint8 [Nz-1, Ny-1, Nx-1], nodes uint8 [Nz, Ny, Nx], the active node indices uint32, ascending)."""
+        nx, ny, nz = (int(v) for v in grid)
+        g = np.array([nx, ny, nz], np.int64)
+        if (g < 0).any() or (g >= 2 ** 32).any():
+            raise _lib.CloudTraceError(_lib.CT_E_INVAL, "bake_mask: grid out of range")
+        g = g.astype(np.uint32)
+        n = C.c_uint32(0)
+        ok = bool((g >= 2).all() and (g <= 256).all())                      # (the library refuses the others before it reads the arrays)
+        cells = np.empty((nz - 1, ny - 1, nx - 1) if ok else (0, 0, 0), np.uint8)
+        nodes = np.empty((nz, ny, nx) if ok else (0, 0, 0), np.uint8)
+        active = np.empty(max(nodes.size, 1), np.uint32)
+        check(self.L.ct_debug_bake_mask(self.h, _p(g), _p(cells), _p(nodes), _p(active), nodes.size, C.byref(n)), self.h)
+        return cells, nodes, active[:n.value].copy()
 
     def bake_lookup(self, bake, positions, directions):
         """ct_debug_bake_lookup: the table lookup for float32 torch tensors [n, 3] on the handle's device -> float32 tensor [n]."""

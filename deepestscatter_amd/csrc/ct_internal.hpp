@@ -266,6 +266,26 @@ hipError_t launch_bake_fill(float *aux, uint32_t count, float value, hipStream_t
 hipError_t launch_bake_store(const float *out, uint32_t count, float *table, uint32_t stride, uint32_t k, hipStream_t stream);
 hipError_t launch_bake_lookup(const DevScene &sc, const BakeTable &t, const float *positions, const float *directions, uint32_t count,
                               float *out, hipStream_t stream);
+// ct_network_bake_sparse: the mask of a probe grid (include/cloudtrace.h, "the sparse bake").  Everything is the caller's,
+// allocated: ranges = the texel range lo | hi << 16 of every cell of x, then y, then z; tmp_x = slab * dims[1] * (grid[0] - 1)
+// bytes and tmp_xy = slab * (grid[1] - 1) * (grid[0] - 1), the z planes the reduction takes at a time; cells, x fastest; nodes;
+// waves = (nodes rounded up to 256) / 64 + 1 counts, the last of which becomes the number of active nodes; list = room for every
+// node, filled with the active ones in ascending order.
+struct BakeMaskArgs {
+    const uint8_t *density;
+    uint32_t dims[3], grid[3], slab;
+    const uint32_t *ranges;
+    uint8_t *tmp_x, *tmp_xy, *cells, *nodes;
+    uint32_t *waves, *list;
+};
+hipError_t launch_bake_mask(const BakeMaskArgs &a, hipStream_t stream);
+// The bake's chunk from the list: records [first, first + count) of the compacted probes (node list[p / nphi], azimuth p % nphi)
+// from the host's tables (axes: the position nodes of x, y, z; directions: nphi x 3), and launch_bake_store through the list
+// into the whole table.
+hipError_t launch_bake_records(const uint32_t *list, uint64_t first, uint32_t count, uint32_t nx, uint32_t ny, uint32_t nphi,
+                               const float *axes, const float *directions, float *pos, float *dir, hipStream_t stream);
+hipError_t launch_bake_store_list(const float *out, const uint32_t *list, uint64_t first, uint32_t count, uint32_t nphi, float *table,
+                                  uint32_t stride, uint32_t k, hipStream_t stream);
 hipError_t launch_baked_compose(const DevScene &sc, const PixelBand &band, const FlightTemps &t, const BakeTable &table, const NetCompose &c,
                                 const ComposeTarget &dst, const uint32_t *frozen, hipStream_t stream);
 // Density pyramid (Resources::generateMipmaps) and the descriptor gather.

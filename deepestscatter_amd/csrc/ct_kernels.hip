@@ -3447,6 +3447,224 @@ hipError_t launch_bake_store(const float *out, uint32_t count, float *table, uin
     return hipGetLastError();
 }
 
+// ---- the sparse bake (ct_network_bake_sparse): the mask of the probes a flight can reach, the list of its nodes, and the
+// bake's records and stores through that list (include/cloudtrace.h, "the sparse bake").
+// The mask is "any non-zero texel in a box of texels", per grid cell; the box is a product of three per-axis ranges (lo | hi << 16,
+// made on the host), so the "any" is reduced along x, then y, then z and the volume is read once.
+//
+// Along x.  One wave per texel row of a slab of z planes, rows [row0, row0 + rows) of the volume.  The wave reads its row -- dx
+// bytes at an arbitrary byte offset -- in 16-byte pieces aligned in memory: a piece that lies inside the volume is one load, the
+// bytes of a piece before or behind the row are masked out, and a piece that reaches over either end of the volume is read byte
+// by byte, the bytes beyond the volume not at all.  The row's non-zero texels become a bit mask in LDS (dx <= 2048: 64 words);
+// lane c, c + 64, ... then answers cell c of the axis from the words its range touches.  out[row][c], one byte.
+__global__ __launch_bounds__(256) void bake_mask_x_kernel(const uint8_t *__restrict__ density, uint64_t volume_bytes, uint32_t dx,
+                                                          uint64_t row0, uint32_t rows, const uint32_t *__restrict__ ranges,
+                                                          uint32_t cells, uint8_t *__restrict__ out)
+{
+    __shared__ uint32_t bits[4][65];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t row = blockIdx.x * 4u + wave;
+    const bool live = row < rows;   // (every wave reaches the barriers)
+    bits[wave][lane] = 0u;
+    if (lane == 0u) {
+        bits[wave][64] = 0u;
+    }
+    __syncthreads();
+    if (live) {
+        const uint64_t begin = (row0 + row) * dx, end = begin + dx;                    // the row's bytes in the volume
+        const uint64_t base = (uint64_t)(uintptr_t)density;
+        const uint64_t first = (base + begin) & ~15ull, last = (base + end - 1u) & ~15ull;   // the aligned pieces, as addresses
+        for (uint64_t piece = first + 16ull * lane; piece <= last; piece += 16ull * 64ull) {
+            uint32_t w[4] = { 0u, 0u, 0u, 0u };
+            if (piece >= base && piece + 16u <= base + volume_bytes) {
+                const uint4 v = *(const uint4 *)(uintptr_t)piece;
+                w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+            } else {
+                for (uint32_t b = 0; b < 16u; b++) {
+                    const uint64_t at = piece + b;
+                    if (at >= base && at < base + volume_bytes) {
+                        w[b >> 2] |= (uint32_t)density[at - base] << (8u * (b & 3u));
+                    }
+                }
+            }
+            uint32_t m = 0u;   // bit b: byte b of the piece is a non-zero texel of this row
+#pragma unroll
+            for (uint32_t b = 0; b < 16u; b++) {
+                const uint64_t at = piece + b - base;   // (wraps below the volume: then it is not in [begin, end))
+                if (((w[b >> 2] >> (8u * (b & 3u))) & 0xFFu) != 0u && at >= begin && at < end) {
+                    m |= 1u << b;
+                }
+            }
+            if (m != 0u) {
+                int64_t x0 = (int64_t)(piece - base) - (int64_t)begin;   // the texel of byte 0: -15 .. dx - 1
+                if (x0 < 0) {
+                    m >>= (uint32_t)(-x0);
+                    x0 = 0;
+                }
+                const uint32_t word = (uint32_t)x0 >> 5, shift = (uint32_t)x0 & 31u;
+                atomicOr(&bits[wave][word], m << shift);
+                if (shift > 16u && (m >> (32u - shift)) != 0u) {
+                    atomicOr(&bits[wave][word + 1u], m >> (32u - shift));
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (live) {
+        for (uint32_t c = lane; c < cells; c += 64u) {
+            const uint32_t lo = ranges[c] & 0xFFFFu, hi = ranges[c] >> 16;
+            uint32_t any = 0u;
+            for (uint32_t word = lo >> 5; word <= hi >> 5; word++) {
+                uint32_t keep = 0xFFFFFFFFu;
+                if (word == lo >> 5) {
+                    keep &= 0xFFFFFFFFu << (lo & 31u);
+                }
+                if (word == hi >> 5) {
+                    keep &= 0xFFFFFFFFu >> (31u - (hi & 31u));
+                }
+                any |= bits[wave][word] & keep;
+            }
+            out[(size_t)row * cells + c] = any != 0u ? 1u : 0u;
+        }
+    }
+}
+
+// Along an outer axis: in is [planes][n][width], out [planes][cells][width]; out[p][c][i] = any of in[p][lo .. hi][i] with the
+// range of cell c clipped to [first, first + n) -- the rows of that axis that `in` holds.  ACCUMULATE: out keeps what it has
+// (the z reduction, one call per slab: every thread owns its byte, and the slabs follow each other on the stream).
+template <bool ACCUMULATE>
+__global__ __launch_bounds__(256) void bake_mask_reduce_kernel(const uint8_t *__restrict__ in, uint32_t planes, uint32_t first, uint32_t n,
+                                                               uint32_t width, const uint32_t *__restrict__ ranges, uint32_t cells,
+                                                               uint8_t *__restrict__ out)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= (uint64_t)planes * cells * width) {
+        return;
+    }
+    const uint32_t x = (uint32_t)(i % width), c = (uint32_t)(i / width % cells), p = (uint32_t)(i / width / cells);
+    const uint32_t lo = max(ranges[c] & 0xFFFFu, first), hi = min(ranges[c] >> 16, first + n - 1u);
+    uint32_t any = ACCUMULATE ? out[i] : 0u;
+    for (uint32_t r = lo; r <= hi && any == 0u; r++) {   // (lo > hi: the range misses these rows)
+        any = in[((size_t)p * n + (r - first)) * width + x];
+    }
+    out[i] = any != 0u ? 1u : 0u;
+}
+
+// Node (x, y, z) is active when one of the up to eight cells it is a corner of is occupied; every wave writes the number of its
+// active nodes (first_scatter_frame_kernel's pattern, and first_scatter_scan_kernel scans them).
+__global__ __launch_bounds__(256) void bake_mask_nodes_kernel(const uint8_t *__restrict__ cells, uint32_t nx, uint32_t ny, uint32_t nz,
+                                                              uint8_t *__restrict__ nodes, uint32_t *__restrict__ wave_counts)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;   // (every lane reaches the ballot; nodes <= 2^24)
+    bool active = false;
+    if (i < nx * ny * nz) {
+        const uint32_t x = i % nx, y = i / nx % ny, z = i / nx / ny;
+        for (uint32_t q = 0; q < 8u; q++) {
+            const uint32_t cx = x + (q & 1u), cy = y + ((q >> 1) & 1u), cz = z + (q >> 2);   // the cell's index + 1
+            if (cx >= 1u && cx < nx && cy >= 1u && cy < ny && cz >= 1u && cz < nz) {
+                active = active || cells[((size_t)(cz - 1u) * (ny - 1u) + (cy - 1u)) * (nx - 1u) + (cx - 1u)] != 0u;
+            }
+        }
+        nodes[i] = active ? 1u : 0u;
+    }
+    const uint64_t mask = __builtin_amdgcn_ballot_w64(active);
+    if ((threadIdx.x & 63u) == 0u) {
+        wave_counts[i >> 6] = (uint32_t)__popcll(mask);
+    }
+}
+
+// list[wave offset + rank] = the node's index: ascending, and the same list for the same mask (no atomics).
+__global__ __launch_bounds__(256) void bake_mask_list_kernel(const uint8_t *__restrict__ nodes, uint32_t count,
+                                                             const uint32_t *__restrict__ wave_offsets, uint32_t *__restrict__ list)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const bool active = i < count && nodes[i] != 0u;
+    const uint64_t mask = __builtin_amdgcn_ballot_w64(active);
+    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+    if (active) {
+        list[wave_offsets[i >> 6] + rank] = i;   // (< the total, which is <= count: the list holds `count` entries)
+    }
+}
+
+hipError_t launch_bake_mask(const BakeMaskArgs &a, hipStream_t stream)
+{
+    const uint32_t cx = a.grid[0] - 1u, cy = a.grid[1] - 1u, cz = a.grid[2] - 1u;
+    const uint32_t *rx = a.ranges, *ry = a.ranges + cx, *rz = a.ranges + cx + cy;
+    hipError_t e = hipMemsetAsync(a.cells, 0, (size_t)cx * cy * cz, stream);
+    if (e != hipSuccess) {
+        return e;
+    }
+    for (uint32_t z0 = 0; z0 < a.dims[2]; z0 += a.slab) {
+        const uint32_t planes = std::min(a.slab, a.dims[2] - z0), rows = planes * a.dims[1];
+        hipLaunchKernelGGL(bake_mask_x_kernel, dim3((rows + 3u) / 4u), dim3(256), 0, stream, a.density,
+                           (uint64_t)a.dims[0] * a.dims[1] * a.dims[2], a.dims[0], (uint64_t)z0 * a.dims[1], rows, rx, cx, a.tmp_x);
+        const uint64_t n_y = (uint64_t)planes * cy * cx, n_z = (uint64_t)cz * cy * cx;
+        hipLaunchKernelGGL(bake_mask_reduce_kernel<false>, dim3((uint32_t)((n_y + 255u) / 256u)), dim3(256), 0, stream,
+                           (const uint8_t *)a.tmp_x, planes, 0u, a.dims[1], cx, ry, cy, a.tmp_xy);
+        hipLaunchKernelGGL(bake_mask_reduce_kernel<true>, dim3((uint32_t)((n_z + 255u) / 256u)), dim3(256), 0, stream,
+                           (const uint8_t *)a.tmp_xy, 1u, z0, planes, cy * cx, rz, cz, a.cells);
+        e = hipGetLastError();
+        if (e != hipSuccess) {
+            return e;
+        }
+    }
+    const uint32_t nodes = a.grid[0] * a.grid[1] * a.grid[2], blocks = (nodes + 255u) / 256u;
+    hipLaunchKernelGGL(bake_mask_nodes_kernel, dim3(blocks), dim3(256), 0, stream, (const uint8_t *)a.cells, a.grid[0], a.grid[1], a.grid[2],
+                       a.nodes, a.waves);
+    hipLaunchKernelGGL(first_scatter_scan_kernel, dim3(1), dim3(1024), 0, stream, a.waves, blocks * 4u);
+    hipLaunchKernelGGL(bake_mask_list_kernel, dim3(blocks), dim3(256), 0, stream, (const uint8_t *)a.nodes, nodes, (const uint32_t *)a.waves,
+                       a.list);
+    return hipGetLastError();
+}
+
+// Compacted probe p = first + i is azimuth p % nphi of node list[p / nphi].  Its record is read from the host's tables -- axes:
+// the position nodes of x, then y, then z; directions: u_j, 3 floats each -- so the floats are ct_bake_probes' own.
+__global__ __launch_bounds__(256) void bake_records_kernel(const uint32_t *__restrict__ list, uint64_t first, uint32_t count, uint32_t nx,
+                                                           uint32_t ny, uint32_t nphi, const float *__restrict__ axes,
+                                                           const float *__restrict__ directions, float *__restrict__ pos,
+                                                           float *__restrict__ dir)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= count) {
+        return;
+    }
+    const uint64_t p = first + i;
+    const uint32_t node = list[p / nphi], j = (uint32_t)(p % nphi);
+    const uint32_t x = node % nx, y = node / nx % ny, z = node / nx / ny;
+    const size_t at = 3 * (size_t)i;
+    pos[at + 0] = axes[x]; pos[at + 1] = axes[nx + y]; pos[at + 2] = axes[nx + ny + z];
+    dir[at + 0] = directions[3u * j + 0u]; dir[at + 1] = directions[3u * j + 1u]; dir[at + 2] = directions[3u * j + 2u];
+}
+
+// bake_store_kernel through the list: table is the whole table.
+__global__ __launch_bounds__(256) void bake_store_list_kernel(const float *__restrict__ out, const uint32_t *__restrict__ list,
+                                                              uint64_t first, uint32_t count, uint32_t nphi, float *__restrict__ table,
+                                                              uint32_t stride, uint32_t k)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= count) {
+        return;
+    }
+    const uint64_t p = first + i;
+    table[((size_t)list[p / nphi] * nphi + (uint32_t)(p % nphi)) * stride + k] = out[i];
+}
+
+hipError_t launch_bake_records(const uint32_t *list, uint64_t first, uint32_t count, uint32_t nx, uint32_t ny, uint32_t nphi,
+                               const float *axes, const float *directions, float *pos, float *dir, hipStream_t stream)
+{
+    hipLaunchKernelGGL(bake_records_kernel, dim3((count + 255u) / 256u), dim3(256), 0, stream, list, first, count, nx, ny, nphi, axes,
+                       directions, pos, dir);
+    return hipGetLastError();
+}
+
+hipError_t launch_bake_store_list(const float *out, const uint32_t *list, uint64_t first, uint32_t count, uint32_t nphi, float *table,
+                                  uint32_t stride, uint32_t k, hipStream_t stream)
+{
+    hipLaunchKernelGGL(bake_store_list_kernel, dim3((count + 255u) / 256u), dim3(256), 0, stream, out, list, first, count, nphi, table,
+                       stride, k);
+    return hipGetLastError();
+}
+
 // A coordinate in [0, n - 1] split into its cell and the weight in it (a NaN goes to cell 0, weight 0: nothing is read out of
 // bounds whatever the record holds).
 CT_DEV void bake_cell(float f, uint32_t n, uint32_t &i0, float &w)

@@ -598,6 +598,15 @@ struct CtBake_ {
     float cosine[64] = {};
     uint64_t epoch = 0;                      // the handle's light epoch at the bake
     double gather_ms = 0, network_ms = 0;
+    // ct_network_bake_sparse: only the probes of the active position nodes are baked.  The density of a live handle
+    // never changes, so the mask and the list are made once and ct_bake_update reuses them.
+    bool sparse = false;
+    uint32_t margin = 0;                     // M
+    uint64_t active = 0;                     // active nodes
+    uint8_t *d_nodes = nullptr;              // one byte per node
+    uint32_t *d_list = nullptr;              // the active nodes, ascending
+    float *d_probe = nullptr;                // the position nodes of x, y, z and the Nphi probe directions (bake_probe's floats)
+    double mask_ms = 0;
 };
 
 static uint64_t bake_probes_total(const CtBake_ *b)
@@ -664,17 +673,111 @@ static BakeTable bake_table(const CtBake_ *b)
              b->a[0], b->a[1], b->a[2], b->b[0], b->b[1], b->b[2] };
 }
 
+// The mask of a probe grid on h (include/cloudtrace.h, "the sparse bake"): its device memory, allocated by bake_mask_reserve
+// before anything runs, and filled by bake_mask_run.
+struct BakeMask {
+    std::vector<uint32_t> host_ranges;   // lo | hi << 16 per cell of x, then y, then z
+    uint32_t margin = 0, slab = 0;
+    DevTemp<uint32_t> ranges, waves, list;
+    DevTemp<uint8_t> tmp_x, tmp_xy, cells, nodes;
+};
+
+static size_t bake_mask_waves(uint64_t nodes)
+{
+    return (size_t)((nodes + 255u) / 256u * 4u + 1u);
+}
+
+static int bake_mask_reserve(CtHandle h, const uint32_t grid[3], BakeMask &m)
+{
+    const uint32_t *dims = h->scene.dims;
+    const uint32_t maxdim = std::max(dims[0], std::max(dims[1], dims[2]));
+    const double S = (double)h->scene.sample_step * (double)maxdim;
+    m.margin = (uint32_t)std::ceil(S) + 3u;
+    m.host_ranges.clear();
+    for (int axis = 0; axis < 3; axis++) {
+        const double D = (double)dims[axis], last = (double)(grid[axis] - 1u), M = (double)m.margin;
+        for (uint32_t c = 0; c + 1u < grid[axis]; c++) {
+            const double lo = std::max(0.0, std::floor((double)c * D / last) - M);
+            const double hi = std::min(D - 1.0, std::ceil((double)(c + 1u) * D / last) + M);
+            m.host_ranges.push_back((uint32_t)lo | (uint32_t)hi << 16);   // (dims <= 2048)
+        }
+    }
+    const size_t cx = grid[0] - 1u, cy = grid[1] - 1u, cz = grid[2] - 1u, nodes = (size_t)grid[0] * grid[1] * grid[2];
+    // (CT_BAKE_MASK_BYTES: the most the first temporary may take; a volume whose planes need more goes through in slabs of z)
+    const size_t cap = (size_t)knob_int(h->tune.BAKE_MASK_BYTES, 1, 1 << 30, 64 << 20), plane = (size_t)dims[1] * cx;
+    m.slab = (uint32_t)std::min<size_t>(dims[2], std::max<size_t>(1, cap / plane));
+    HIPCHK(h, dmalloc(&m.ranges, m.host_ranges.size()));
+    HIPCHK(h, dmalloc(&m.tmp_x, m.slab * plane));
+    HIPCHK(h, dmalloc(&m.tmp_xy, m.slab * cy * cx));
+    HIPCHK(h, dmalloc(&m.cells, cz * cy * cx));
+    HIPCHK(h, dmalloc(&m.nodes, nodes));
+    HIPCHK(h, dmalloc(&m.waves, bake_mask_waves(nodes)));
+    HIPCHK(h, dmalloc(&m.list, nodes));
+    return CT_OK;
+}
+
+// The stream is idle.  *active_out = the number of active nodes (the one 4-byte read), *ms_out = the kernels' GPU time.
+static int bake_mask_run(CtHandle h, const uint32_t grid[3], BakeMask &m, uint32_t *active_out, double *ms_out)
+{
+    const uint64_t nodes = (uint64_t)grid[0] * grid[1] * grid[2];
+    auto run = [&]() -> int {
+        HIPCHK(h, hipMemcpyAsync(m.ranges, m.host_ranges.data(), m.host_ranges.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+        BakeMaskArgs a{};
+        a.density = h->d_density;
+        for (int axis = 0; axis < 3; axis++) {
+            a.dims[axis] = h->scene.dims[axis];
+            a.grid[axis] = grid[axis];
+        }
+        a.slab = m.slab;
+        a.ranges = m.ranges;
+        a.tmp_x = m.tmp_x;
+        a.tmp_xy = m.tmp_xy;
+        a.cells = m.cells;
+        a.nodes = m.nodes;
+        a.waves = m.waves;
+        a.list = m.list;
+        HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
+        HIPCHK(h, launch_bake_mask(a, h->stream));
+        HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
+        uint32_t count = 0;
+        HIPCHK(h, hipMemcpyAsync(&count, m.waves + (bake_mask_waves(nodes) - 1u), sizeof count, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        float ms = 0;
+        HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+        if (count > nodes) {
+            return fail(h, CT_E_HIP, "internal: a grid of %llu nodes counted %u active ones", (unsigned long long)nodes, count);
+        }
+        *active_out = count;
+        *ms_out = ms;
+        return CT_OK;
+    };
+    const int rc = run();
+    if (rc != CT_OK) {
+        hipStreamSynchronize(h->stream);
+    }
+    return rc;
+}
+
 // Fills `table` (b->entries floats, allocated) for the handle's light and network n: the probes in chunks through the handle's
 // scratch, one gather per piece and one evaluation per polar node.  b's frame is the new light's already.
+// A sparse bake runs the compacted probes -- azimuth p % Nphi of node list[p / Nphi] -- the same way: the table is zeroed first,
+// the chunk's records come from a kernel and the stores go through the list.
 static int bake_run(CtHandle h, CtNetwork n, CtBake_ *b, float *table)
 {
     CtHandle_::NetScratch &s = h->net;
-    const uint64_t probes = bake_probes_total(b);
+    const uint64_t probes = b->sparse ? b->active * b->azimuths : bake_probes_total(b);
     const size_t chunk = (size_t)std::min<uint64_t>(probes, std::min<size_t>(net_descriptor_limit(h), (size_t)1 << 20));
     const DescriptorScale ds = descriptor_scale(h);
-    std::vector<float> pos(3 * chunk), dir(3 * chunk);
-    double gather_ms = 0, network_ms = 0;
+    std::vector<float> pos(b->sparse ? 0 : 3 * chunk), dir(b->sparse ? 0 : 3 * chunk);
+    double gather_ms = 0, network_ms = 0, records_ms = 0;
     auto run = [&]() -> int {
+        if (b->sparse) {
+            HIPCHK(h, hipMemsetAsync(table, 0, (size_t)b->entries * sizeof(float), h->stream));
+            if (probes == 0u) {
+                HIPCHK(h, hipStreamSynchronize(h->stream));
+                return CT_OK;
+            }
+        }
         int rc = net_reserve(h, chunk, false);
         if (rc == CT_OK) {
             rc = ensure_pyramid(h);
@@ -683,13 +786,46 @@ static int bake_run(CtHandle h, CtNetwork n, CtBake_ *b, float *table)
             return rc;
         }
         net_grow_descriptors(h, chunk);
+        const float *axes = b->d_probe, *directions = b->sparse ? b->d_probe + (b->grid[0] + b->grid[1] + b->grid[2]) : nullptr;
+        if (b->sparse) {   // the tables of the record kernel, by bake_probe: ct_bake_probes' floats
+            const uint32_t nx = b->grid[0], ny = b->grid[1], nz = b->grid[2];
+            std::vector<float> host(nx + ny + nz + 3 * (size_t)b->azimuths);
+            float p[3], d[3];
+            for (uint32_t i = 0; i < nx; i++) {
+                bake_probe(b, (uint64_t)i * b->azimuths, p, d);
+                host[i] = p[0];
+            }
+            for (uint32_t i = 0; i < ny; i++) {
+                bake_probe(b, (uint64_t)i * nx * b->azimuths, p, d);
+                host[nx + i] = p[1];
+            }
+            for (uint32_t i = 0; i < nz; i++) {
+                bake_probe(b, (uint64_t)i * nx * ny * b->azimuths, p, d);
+                host[nx + ny + i] = p[2];
+            }
+            for (uint32_t j = 0; j < b->azimuths; j++) {
+                bake_probe(b, j, p, &host[nx + ny + nz + 3 * (size_t)j]);
+            }
+            HIPCHK(h, hipMemcpy(b->d_probe, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
+        }
         for (uint64_t first = 0; first < probes; first += chunk) {
             const uint32_t count = (uint32_t)std::min<uint64_t>(chunk, probes - first);
-            for (uint32_t i = 0; i < count; i++) {
-                bake_probe(b, first + i, &pos[3 * (size_t)i], &dir[3 * (size_t)i]);
+            if (b->sparse) {
+                float ms = 0;
+                HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
+                HIPCHK(h, launch_bake_records(b->d_list, first, count, b->grid[0], b->grid[1], b->azimuths, axes, directions, s.pos, s.dir,
+                                              h->stream));
+                HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
+                HIPCHK(h, hipEventSynchronize(h->ev[1]));
+                HIPCHK(h, hipEventElapsedTime(&ms, h->ev[2], h->ev[1]));
+                records_ms += ms;
+            } else {
+                for (uint32_t i = 0; i < count; i++) {
+                    bake_probe(b, first + i, &pos[3 * (size_t)i], &dir[3 * (size_t)i]);
+                }
+                HIPCHK(h, hipMemcpyAsync(s.pos, pos.data(), 3 * (size_t)count * sizeof(float), hipMemcpyHostToDevice, h->stream));
+                HIPCHK(h, hipMemcpyAsync(s.dir, dir.data(), 3 * (size_t)count * sizeof(float), hipMemcpyHostToDevice, h->stream));
             }
-            HIPCHK(h, hipMemcpyAsync(s.pos, pos.data(), 3 * (size_t)count * sizeof(float), hipMemcpyHostToDevice, h->stream));
-            HIPCHK(h, hipMemcpyAsync(s.dir, dir.data(), 3 * (size_t)count * sizeof(float), hipMemcpyHostToDevice, h->stream));
             for (uint32_t at = 0; at < count;) {
                 const uint32_t piece = (uint32_t)std::min<size_t>(count - at, s.desc_cap);
                 float ms = 0;
@@ -707,7 +843,11 @@ static int bake_run(CtHandle h, CtNetwork n, CtBake_ *b, float *table)
                     double net_ms = 0;
                     ct_debug_network_time(n, &net_ms);
                     network_ms += net_ms;
-                    HIPCHK(h, launch_bake_store(s.out, piece, table + (first + at) * b->cosines, b->cosines, k, h->stream));
+                    if (b->sparse) {
+                        HIPCHK(h, launch_bake_store_list(s.out, b->d_list, first + at, piece, b->azimuths, table, b->cosines, k, h->stream));
+                    } else {
+                        HIPCHK(h, launch_bake_store(s.out, piece, table + (first + at) * b->cosines, b->cosines, k, h->stream));
+                    }
                 }
                 HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
                 gather_ms += ms;
@@ -724,12 +864,24 @@ static int bake_run(CtHandle h, CtNetwork n, CtBake_ *b, float *table)
     }
     b->gather_ms = gather_ms;
     b->network_ms = network_ms;
+    b->mask_ms = records_ms;
     return CT_OK;
 }
 
-extern "C" int ct_network_bake(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtBake *out)
+static void bake_free(CtBake_ *b)
 {
-    const char *const who = "ct_network_bake";
+    for (void *p : { (void *)b->d_table, (void *)b->d_nodes, (void *)b->d_list, (void *)b->d_probe }) {
+        if (p) {
+            hipFree(p);
+        }
+    }
+    delete b;
+}
+
+// ct_network_bake and ct_network_bake_sparse: one validation, one order of errors.
+static int bake_create(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtBake *out, bool sparse)
+{
+    const char *const who = sparse ? "ct_network_bake_sparse" : "ct_network_bake";
     if (!h) {
         return fail(nullptr, CT_E_INVAL, "null handle");
     }
@@ -783,14 +935,127 @@ extern "C" int ct_network_bake(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtB
         delete b;
         return fail(h, CT_E_NOMEM, "%s: no device memory for a table of %llu entries", who, (unsigned long long)entries);
     }
-    bake_frame(h, b);
-    rc = bake_run(h, n, b, b->d_table);
+    if (sparse) {   // the mask's temporaries, the node bytes, the list and the record tables: all before the first kernel, too
+        BakeMask m;
+        rc = bake_mask_reserve(h, b->grid, m);
+        if (rc == CT_OK && dmalloc(&b->d_probe, b->grid[0] + b->grid[1] + b->grid[2] + 3 * (size_t)b->azimuths) != hipSuccess) {
+            (void)hipGetLastError();
+            rc = fail(h, CT_E_NOMEM, "%s: no device memory for the probe tables", who);
+        }
+        uint32_t active = 0;
+        double mask_ms = 0;
+        if (rc == CT_OK) {
+            rc = bake_mask_run(h, b->grid, m, &active, &mask_ms);
+        }
+        if (rc != CT_OK) {
+            bake_free(b);
+            return rc;
+        }
+        b->sparse = true;
+        b->margin = m.margin;
+        b->active = active;
+        b->d_nodes = m.nodes.release();
+        b->d_list = m.list.release();
+        bake_frame(h, b);
+        rc = bake_run(h, n, b, b->d_table);
+        b->mask_ms += mask_ms;
+    } else {
+        bake_frame(h, b);
+        rc = bake_run(h, n, b, b->d_table);
+    }
     if (rc != CT_OK) {
-        hipFree(b->d_table);
-        delete b;
+        bake_free(b);
         return rc;
     }
     *out = b;
+    return CT_OK;
+}
+
+extern "C" int ct_network_bake(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtBake *out)
+{
+    return bake_create(h, n, d, out, false);
+}
+
+extern "C" int ct_network_bake_sparse(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtBake *out)
+{
+    return bake_create(h, n, d, out, true);
+}
+
+extern "C" int ct_bake_sparse_info(CtBake b, CtBakeSparseInfo *out)
+{
+    if (!b || !out) {
+        return fail(b ? b->h : nullptr, CT_E_INVAL, "ct_bake_sparse_info: need a bake and out");
+    }
+    *out = CtBakeSparseInfo{};
+    out->sparse = b->sparse ? 1u : 0u;
+    out->margin_texels = b->margin;
+    out->nodes = (uint64_t)b->grid[0] * b->grid[1] * b->grid[2];
+    out->active_nodes = b->sparse ? b->active : out->nodes;
+    out->probes_baked = out->active_nodes * b->azimuths;
+    out->mask_ms = b->mask_ms;
+    return CT_OK;
+}
+
+extern "C" int ct_bake_mask(CtBake b, uint8_t *nodes_host_out, size_t count)
+{
+    if (!b) {
+        return fail(nullptr, CT_E_INVAL, "ct_bake_mask: null bake");
+    }
+    CtHandle h = b->h;
+    const size_t nodes = (size_t)b->grid[0] * b->grid[1] * b->grid[2];
+    if (!nodes_host_out || count != nodes) {
+        return fail(h, CT_E_INVAL, "ct_bake_mask: need an array of exactly %llu bytes", (unsigned long long)nodes);
+    }
+    if (!b->sparse) {
+        std::fill(nodes_host_out, nodes_host_out + nodes, (uint8_t)1);
+        return CT_OK;
+    }
+    NEED(h);
+    HIPCHK(h, hipMemcpy(nodes_host_out, b->d_nodes, nodes, hipMemcpyDeviceToHost));
+    return CT_OK;
+}
+
+extern "C" int ct_debug_bake_mask(CtHandle h, const uint32_t grid[3], uint8_t *cells_host_out, uint8_t *nodes_host_out,
+                                  uint32_t *active_host_out, uint32_t capacity, uint32_t *count_out)
+{
+    const char *const who = "ct_debug_bake_mask";
+    if (!h) {
+        return fail(nullptr, CT_E_INVAL, "null handle");
+    }
+    if (!grid || !count_out) {
+        return fail(h, CT_E_INVAL, "%s: need a grid and count_out", who);
+    }
+    *count_out = 0;
+    for (int axis = 0; axis < 3; axis++) {
+        if (grid[axis] < 2u || grid[axis] > 256u) {
+            return fail(h, CT_E_INVAL, "%s: grid[%d] = %u, a grid has 2 .. 256 nodes per axis", who, axis, grid[axis]);
+        }
+    }
+    NEED(h);
+    BakeMask m;
+    int rc = bake_mask_reserve(h, grid, m);
+    uint32_t active = 0;
+    double ms = 0;
+    if (rc == CT_OK) {
+        rc = bake_mask_run(h, grid, m, &active, &ms);
+    }
+    if (rc != CT_OK) {
+        return rc;
+    }
+    *count_out = active;
+    if (active_host_out && capacity < active) {
+        return fail(h, CT_E_INVAL, "%s: %u active nodes do not fit a capacity of %u", who, active, capacity);
+    }
+    const size_t cells = (size_t)(grid[0] - 1u) * (grid[1] - 1u) * (grid[2] - 1u), nodes = (size_t)grid[0] * grid[1] * grid[2];
+    if (cells_host_out) {
+        HIPCHK(h, hipMemcpy(cells_host_out, m.cells, cells, hipMemcpyDeviceToHost));
+    }
+    if (nodes_host_out) {
+        HIPCHK(h, hipMemcpy(nodes_host_out, m.nodes, nodes, hipMemcpyDeviceToHost));
+    }
+    if (active_host_out && active != 0u) {
+        HIPCHK(h, hipMemcpy(active_host_out, m.list, (size_t)active * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
     return CT_OK;
 }
 
@@ -839,8 +1104,7 @@ extern "C" int ct_bake_destroy(CtBake b)
         return CT_OK;
     }
     hipSetDevice(b->device);
-    hipFree(b->d_table);
-    delete b;
+    bake_free(b);
     return CT_OK;
 }
 

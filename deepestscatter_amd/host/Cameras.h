@@ -141,12 +141,14 @@ namespace DeepestScatter
     // The reference's default renderer (BakedRenderer): the network evaluated once per light on a probe grid (ct_network_bake,
     // --net-baked NX,NY,NZ,NPHI,NC) and every subframe interpolated from that table (ct_baked_render_*): no gather and no
     // network per subframe.  The table is baked in init, which follows Sun::init and so every ct_set_light, and baked again
-    // should the light have changed since.  One GPU only: main refuses --net-baked with --gpus.
+    // should the light have changed since.  One GPU only: main refuses --net-baked with --gpus.  sparse (--net-bake-sparse): the
+    // table is baked by ct_network_bake_sparse, only where a first flight can look it up; the images are the same.
     class BakedRenderer : public NetworkRenderer
     {
     public:
-        BakedRenderer(std::shared_ptr<Context> context, std::shared_ptr<const NetworkFile> file, const CtNetworkRender& params, const CtBakeDesc& desc)
-            : NetworkRenderer(std::move(context), std::move(file), params), desc(desc) {}
+        BakedRenderer(std::shared_ptr<Context> context, std::shared_ptr<const NetworkFile> file, const CtNetworkRender& params, const CtBakeDesc& desc,
+                      bool sparse = false)
+            : NetworkRenderer(std::move(context), std::move(file), params), desc(desc), sparse(sparse) {}
         ~BakedRenderer() override
         {
             if (bake) ct_bake_destroy(bake);   // (before the network and the handle)
@@ -156,6 +158,7 @@ namespace DeepestScatter
         {
             NetworkRenderer::init();
             if (context->group) throw std::runtime_error("--net-baked renders on one GPU only");
+            if (!bake && sparse) Context::check(ct_network_bake_sparse(context->handle, network, &desc, &bake), context->handle, "ct_network_bake_sparse");
             if (!bake) Context::check(ct_network_bake(context->handle, network, &desc, &bake), context->handle, "ct_network_bake");
         }
 
@@ -184,6 +187,7 @@ namespace DeepestScatter
         }
 
         CtBakeDesc desc;
+        bool sparse;
         CtBake bake = nullptr;
     };
 

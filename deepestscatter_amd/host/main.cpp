@@ -15,6 +15,7 @@
 //                               network trained on the multiple-scatter labels gives the picture --mode total gives
 //              [--net-baked NX,NY,NZ,NPHI,NC]   with --network: bake the network once per light on that probe grid (ct_network_bake)
 //                               and interpolate every subframe from the table (ct_baked_render_accumulate); one GPU, not with --gpus
+//              [--net-bake-sparse]              with --net-baked: bake only the probes a first flight can reach (ct_network_bake_sparse); the same images
 //   <cloud> = file.vdb | procedural:<N>[:<seed>] | file.f32grid
 //
 //   cloudtrace collect <cloud>|@list.txt [--scene-id I] [--scenes N] [--jobs K] [--gpus ..] [--batch 2048] [--light L] [--size-m M] [--out DIR] [--data DIR] [--estimator ..] [--tex-fixed8]
@@ -74,6 +75,7 @@ namespace
         CtNetworkRender networkRender{ CT_ABI_VERSION, CT_NET_OUT_LINEAR, { 1.f, 1.f, 1.f }, 0 };   // --net-transform, --net-scale
         bool netBaked = false;                                                    // --net-baked NX,NY,NZ,NPHI,NC: render from a baked probe table (BakedRenderer)
         CtBakeDesc bake{ CT_ABI_VERSION, { 0, 0, 0 }, 0, 0 };
+        bool netBakeSparse = false;                                               // --net-bake-sparse: ct_network_bake_sparse in place of ct_network_bake
         bool netDirect = false;                                                   // --net-direct: CT_NET_ADD_SINGLE_SCATTER joins networkRender.transform
         bool collect = false;                                                     // `cloudtrace collect ...`
         int32_t sceneId = 0;
@@ -273,7 +275,7 @@ namespace
             auto outputPath = std::filesystem::path(opt.outDir) / (stem + "." + toString(lightDirection) + "." + PathTracingRenderer::NAME + "." + opt.format);
             // installFramework + installApp: Sun, VDBCloud, CloudMaterial, Camera in this order (installers.cpp:28-38)
             std::shared_ptr<PathTracingRenderer> renderer = !opt.network ? std::make_shared<PathTracingRenderer>(context)
-                : opt.netBaked ? std::make_shared<BakedRenderer>(context, opt.network, opt.networkRender, opt.bake)
+                : opt.netBaked ? std::make_shared<BakedRenderer>(context, opt.network, opt.networkRender, opt.bake, opt.netBakeSparse)
                                : std::make_shared<NetworkRenderer>(context, opt.network, opt.networkRender);
             renderer->estimator = opt.estimator;
             auto sun = std::make_shared<Sun>(std::make_shared<DirectionalLight>(scene.light), context);
@@ -296,7 +298,7 @@ int main(int argc, char* argv[])
     try
     {
         Options opt;
-        if (argc < 2) { std::cerr << "usage: cloudtrace <cloud> [--size WxH] [--spp N] [--mode total|multi|single] [--light L] [--size-m M] [--out DIR] [--data DIR] [--unfused] [--display] [--estimator march|delta] [--format exr|pfm] [--gpus N|a,b,c] [--tex-fixed8] [--network FILE [--net-transform linear|expm1] [--net-scale r,g,b] [--net-direct] [--net-baked NX,NY,NZ,NPHI,NC]] (--network with --gpus: every GPU renders its own tiles; --net-baked: one GPU)\n"; return 2; }
+        if (argc < 2) { std::cerr << "usage: cloudtrace <cloud> [--size WxH] [--spp N] [--mode total|multi|single] [--light L] [--size-m M] [--out DIR] [--data DIR] [--unfused] [--display] [--estimator march|delta] [--format exr|pfm] [--gpus N|a,b,c] [--tex-fixed8] [--network FILE [--net-transform linear|expm1] [--net-scale r,g,b] [--net-direct] [--net-baked NX,NY,NZ,NPHI,NC [--net-bake-sparse]]] (--network with --gpus: every GPU renders its own tiles; --net-baked: one GPU)\n"; return 2; }
         int first = 2;
         bool lightsGiven = false;
         opt.cloud = argv[1];
@@ -353,6 +355,10 @@ int main(int argc, char* argv[])
                 if (std::sscanf(next().c_str(), "%u,%u,%u,%u,%u", &b.grid[0], &b.grid[1], &b.grid[2], &b.azimuths, &b.cosines) != 5) throw std::invalid_argument("--net-baked NX,NY,NZ,NPHI,NC");
                 opt.netBaked = true;
             }
+            else if (a == "--net-bake-sparse")
+            {
+                opt.netBakeSparse = true;
+            }
             else if (a == "--tex-fixed8") opt.texFixed8 = true;
             else if (a == "--estimator")
             {
@@ -384,6 +390,7 @@ int main(int argc, char* argv[])
         if (opt.collect) return collectScenes(opt);
 
         if (opt.netDirect) opt.networkRender.transform |= CT_NET_ADD_SINGLE_SCATTER;   // (after the loop: --net-transform may follow it)
+        if (opt.netBakeSparse && !opt.netBaked) throw std::invalid_argument("--net-bake-sparse chooses how --net-baked NX,NY,NZ,NPHI,NC bakes its table");
         if (opt.netBaked && opt.networkPath.empty()) throw std::invalid_argument("--net-baked bakes the network of --network FILE");
         if (opt.netBaked && !opt.devices.empty()) throw std::invalid_argument("--net-baked renders on one GPU: it cannot be combined with --gpus");
         if (!opt.networkPath.empty())

@@ -10,6 +10,7 @@ residual MLP of the paper the reference implements (Kallweit et al. 2017), param
     render_values       numpy restatement of what ct_network_render_* makes of the outputs (transform, clamp, rgb scale)
     Bake                a CtBake: the network evaluated on a probe grid (ct_network_bake), which ct_baked_render_* interpolate
     bake_azimuth / bake_lookup_reference   numpy float32 restatement of the table lookup: what the device is held to
+    bake_mask_reference numpy restatement of the sparse bake's mask (ct_network_bake_sparse): cells, nodes and the margin M
     save_weights / load_weights   the weight file `cloudtrace --network` reads
 
 State-dict names (the mapping an exported model needs): blocks.k.fc1 = W1_k, c1_k; blocks.k.fc2 = W2_k, c2_k (k = 0 .. 9);
@@ -266,6 +267,32 @@ def bake_lookup_reference(table, info, box, positions, directions) -> np.ndarray
     return lerp(lerp(c00, c10, wy), lerp(c01, c11, wy), wz)
 
 
+def bake_mask_reference(density, grid, sample_step):
+    """The mask of ct_network_bake_sparse in numpy, the definition the device is held to (include/cloudtrace.h, "the sparse
+    bake").  density: uint8 [Dz, Dy, Dx]; grid: (Nx, Ny, Nz); sample_step: the handle's (read as float32, like CtScene's).
+    -> (cells uint8 [Nz-1, Ny-1, Nx-1], nodes uint8 [Nz, Ny, Nx], M): a cell is occupied when any texel in the box of its three
+    per-axis ranges t_lo .. t_hi is non-zero, a node active when a cell it is a corner of is occupied."""
+    occupied = np.ascontiguousarray(density) != 0
+    if occupied.ndim != 3:
+        raise ValueError("density must be [Dz, Dy, Dx]")
+    dz, dy, dx = occupied.shape
+    nx, ny, nz = (int(v) for v in grid)
+    M = int(np.ceil(np.float64(np.float32(sample_step)) * np.float64(max(dx, dy, dz)))) + 3
+    for axis, (n, d) in enumerate(((nz, dz), (ny, dy), (nx, dx))):          # the array's axes: z, y, x
+        c = np.arange(n - 1, dtype=np.float64)
+        lo = np.maximum(0.0, np.floor(c * np.float64(d) / np.float64(n - 1)) - M).astype(np.int64)
+        hi = np.minimum(np.float64(d - 1), np.ceil((c + 1.0) * np.float64(d) / np.float64(n - 1)) + M).astype(np.int64)
+        count = np.concatenate([np.zeros_like(np.take(occupied, [0], axis), np.int64), np.cumsum(occupied, axis, dtype=np.int64)], axis)
+        occupied = (np.take(count, hi + 1, axis) - np.take(count, lo, axis)) > 0
+    cells = occupied.astype(np.uint8)
+    nodes = np.zeros((nz, ny, nx), np.uint8)
+    for oz in (0, 1):
+        for oy in (0, 1):
+            for ox in (0, 1):
+                nodes[oz:oz + nz - 1, oy:oy + ny - 1, ox:ox + nx - 1] |= cells
+    return cells, nodes, M
+
+
 # The weight file: a 32-byte little-endian header -- magic "CTNW", u32 version, blocks, width, aux, head_layers, u64 weight
 # count -- and then weight_count float32 values in the order of CtNetworkDesc.weights_host.
 WEIGHT_MAGIC = b"CTNW"
@@ -368,14 +395,16 @@ class Network:
 class Bake:
     """A CtBake of `net` on its tracer (ct_network_bake): the network evaluated on a grid of grid[0] x grid[1] x grid[2] position
     nodes x `azimuths` view azimuths around the light x `cosines` polar nodes, which CloudTracer.baked_render_* interpolate in
-    place of gather and network.  Close it before the tracer; after tracer.set_light call update()."""
+    place of gather and network.  sparse: ct_network_bake_sparse, which bakes only the probes a flight can reach and leaves the
+    rest of the table 0.  Close it before the tracer; after tracer.set_light call update()."""
 
-    def __init__(self, tracer, net, grid, azimuths: int, cosines: int):
+    def __init__(self, tracer, net, grid, azimuths: int, cosines: int, sparse: bool = False):
         self.L = _lib.load()
         self.tracer = tracer
         d = _lib.CtBakeDesc(_lib.CT_ABI_VERSION, (C.c_uint32 * 3)(*[int(v) for v in grid]), int(azimuths), int(cosines))
         b = C.c_void_p()
-        check(self.L.ct_network_bake(tracer.h, net.n, C.byref(d), C.byref(b)), tracer.h)
+        entry = self.L.ct_network_bake_sparse if sparse else self.L.ct_network_bake
+        check(entry(tracer.h, net.n, C.byref(d), C.byref(b)), tracer.h)
         self.b = b
 
     def close(self):
@@ -409,6 +438,21 @@ class Bake:
                 "light": np.array(i.light[:], np.float32), "axis_a": np.array(i.axis_a[:], np.float32),
                 "axis_b": np.array(i.axis_b[:], np.float32), "cosine": np.array(i.cosine[:int(i.cosines)], np.float32),
                 "current": bool(i.current), "gather_ms": float(i.gather_ms), "network_ms": float(i.network_ms)}
+
+    @property
+    def sparse_info(self) -> dict:
+        """ct_bake_sparse_info: sparse, margin_texels (M), nodes, active_nodes, probes_baked, mask_ms."""
+        i = _lib.CtBakeSparseInfo()
+        check(self.L.ct_bake_sparse_info(self.b, C.byref(i)), self.tracer.h)
+        return {"sparse": bool(i.sparse), "margin_texels": int(i.margin_texels), "nodes": int(i.nodes),
+                "active_nodes": int(i.active_nodes), "probes_baked": int(i.probes_baked), "mask_ms": float(i.mask_ms)}
+
+    def mask(self) -> np.ndarray:
+        """ct_bake_mask -> uint8 [Nz, Ny, Nx]: 1 where the node's probes were baked (a dense bake: everywhere)."""
+        nx, ny, nz = self.info["grid"]
+        m = np.empty((nz, ny, nx), np.uint8)
+        check(self.L.ct_bake_mask(self.b, m.ctypes.data_as(C.c_void_p), m.size), self.tracer.h)
+        return m
 
     def probes(self, first: int = 0, count: int | None = None):
         """ct_bake_probes -> (positions, directions) float32 [count, 3], the records the bake used, in index order."""

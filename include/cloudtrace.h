@@ -677,6 +677,51 @@ CT_API int ct_bake_download(CtBake b, float *table_host_out, size_t count);   /*
 CT_API int ct_debug_bake_lookup(CtHandle h, CtBake b, const float *positions_dev, const float *directions_dev, uint32_t count,
                                 float *out_dev);
 
+/* ---- the sparse bake: only the probes a flight can reach ---------------------------------------
+ *
+ * A lookup only ever happens at a first-scatter position, and a first-scatter position is next to non-zero density: the flight
+ * ends at most one march step (S = sample_step * max dim texels) behind a sample whose eight-texel footprint holds a non-zero
+ * texel.  ct_network_bake_sparse bakes the probes of the position nodes such a position can touch and leaves every other entry
+ * of the table 0.0f.  The table stays dense in memory: the lookup, the render entry points and every function above take the
+ * CtBake as they take ct_network_bake's, and every frame is the dense bake's frame bit for bit.
+ *
+ * The mask, in integers.  dims = (Dx, Dy, Dz), M = ceil((double)sample_step * max dim) + 3.  Per axis with N nodes and D texels,
+ * cell c (between nodes c and c + 1) has the texel range, computed in double,
+ *     t_lo(c) = max(0, floor(c * D / (N - 1)) - M),   t_hi(c) = min(D - 1, ceil((c + 1) * D / (N - 1)) + M);
+ * cell (cx, cy, cz) is occupied when any texel of the level-0 density in the box of its three ranges is non-zero; node (x, y, z)
+ * is active when one of the up to eight cells it is a corner of is occupied.  The sparse table is the dense table, bit for bit,
+ * on every entry (all Nphi azimuths, all Nc polar nodes) of an active node and 0.0f elsewhere.  The probes baked are the active
+ * nodes in ascending node index, each with j = 0 .. Nphi - 1, in chunks as above; the result does not depend on the chunk size.
+ * ct_bake_probes keeps answering every probe of the grid, baked or not.
+ *
+ * THE ONE OBSERVABLE DIFFERENCE from a dense bake: ct_debug_bake_lookup at a position that no flight can produce (far from
+ * every non-zero texel) interpolates the zeros of inactive nodes.
+ *
+ * ct_network_bake_sparse has ct_network_bake's validation, error order and limits (the storage is dense: 2^26 entries).  The
+ * table, the mask's temporaries, the node bytes and the list are allocated before the first kernel: CT_E_NOMEM leaves the handle
+ * as it was.  A grid without an active node is CT_OK: an all-zero table, no gather and no network call.  ct_bake_update of a
+ * sparse bake stays sparse and reuses the list (the density of a live handle never changes); it bakes into a zeroed second table
+ * and swaps, as for a dense bake.  CtBakeInfo's gather_ms and network_ms are those of the probes actually baked. */
+typedef struct CtBakeSparseInfo {
+    uint32_t sparse;          /* 1: made by ct_network_bake_sparse */
+    uint32_t margin_texels;   /* M (0 for a dense bake) */
+    uint64_t nodes;           /* Nx Ny Nz */
+    uint64_t active_nodes;    /* = nodes for a dense bake */
+    uint64_t probes_baked;    /* active_nodes * Nphi */
+    double   mask_ms;         /* GPU time of the mask, list and record kernels of the last bake / update (an update: the record kernel) */
+} CtBakeSparseInfo;
+
+CT_API int ct_network_bake_sparse(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtBake *out);
+CT_API int ct_bake_sparse_info(CtBake b, CtBakeSparseInfo *out);
+/* One byte per node, index (z Ny + y) Nx + x; a dense bake answers all 1.  count must equal Nx Ny Nz. */
+CT_API int ct_bake_mask(CtBake b, uint8_t *nodes_host_out, size_t count);
+/* Diagnostic, no network needed: the mask of a grid (2 .. 256 nodes per axis) on this handle.
+ * cells_host_out: (Nx-1)(Ny-1)(Nz-1) bytes, x fastest.  nodes_host_out: Nx Ny Nz bytes.
+ * active_host_out: up to `capacity` ascending node indices.  Any of the three may be NULL.
+ * *count_out = active nodes (set even when capacity is too small, which is CT_E_INVAL). */
+CT_API int ct_debug_bake_mask(CtHandle h, const uint32_t grid[3], uint8_t *cells_host_out, uint8_t *nodes_host_out,
+                              uint32_t *active_host_out, uint32_t capacity, uint32_t *count_out);
+
 /* ct_network_render_subframe / _accumulate / _shard_subframe / _shard_accumulate with the table in the network's place. */
 CT_API int ct_baked_render_subframe(CtHandle h, CtBake b, const CtNetworkRender *p, uint32_t subframe_id, float *frame_rgba_dev);
 CT_API int ct_baked_render_accumulate(CtHandle h, CtBake b, const CtNetworkRender *p, uint32_t first_subframe_id, uint32_t count);

@@ -8,9 +8,13 @@ ScatterNet(200, 1, 3), warm calls, medians.  Per grid (16^3, 32^3, 64^3, each x 
   the relative L2 distance between the two routes' means after --subframes subframes, and the same distance relative to the
   network route's variation about its mean level over the lit pixels (--bias raises the output bias so that the seeded
   network's outputs, small and negative as they come, are positive: negative outputs render black on both routes).
+--sparse: instead, what ct_network_bake_sparse saves.  Per grid the dense and the sparse bake take turns,
+--repeats times each after one warm-up pair, and one JSON line carries the active-node share, and for both routes the medians of
+mask_ms, the gather ms, the network ms and the bake's wall ms (with the dense repeats' spread), the baked subframe's GPU ms, and
+whether the two routes' means after --subframes subframes are bit-identical (the tool exits with 1 if they are not).
 Needs a GPU.  No threshold: the table's resolution is the user's trade.
     python tools/baked_render_time.py [--repeats 5] [--volume 512] [--size 1024] [--subframes 16] [--grids 16 32 64]
-                                      [--azimuths 16] [--cosines 8] [--direct] [--bias 1.0]"""
+                                      [--azimuths 16] [--cosines 8] [--direct] [--bias 1.0] [--sparse]"""
 import argparse, json, statistics, sys, time
 from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
@@ -21,6 +25,48 @@ def wall_ms(fn):
     t = time.perf_counter()
     fn()
     return (time.perf_counter() - t) * 1e3
+
+
+def sparse_against_dense(a, tr, net, common):
+    """The --sparse protocol -> True when every grid's two means were bit-identical."""
+    import numpy as np
+    med = statistics.median
+    same = True
+    for g in a.grids:
+        runs = {False: [], True: []}
+        means = {}
+        for i in range(a.repeats + 1):          # (the first pair is the warm-up)
+            for sparse in (False, True):
+                t0 = time.perf_counter()
+                bake = tr.network_bake(net, (g, g, g), a.azimuths, a.cosines, sparse=sparse)
+                wall = (time.perf_counter() - t0) * 1e3
+                info, sp = bake.info, bake.sparse_info
+                gpu = []
+                for _ in range(3):
+                    tr.baked_render_subframe(bake, 1, out=False, direct=a.direct)
+                    gpu.append(tr.baked_render_time())
+                if i == a.repeats:
+                    tr.reset()
+                    tr.baked_render_accumulate(bake, 1, a.subframes, direct=a.direct)
+                    means[sparse] = tr.mean()
+                bake.close()
+                if i:
+                    runs[sparse].append({"wall": wall, "gather": info["gather_ms"], "network": info["network_ms"], "mask": sp["mask_ms"],
+                                         "subframe": med(gpu), "active": sp["active_nodes"], "nodes": sp["nodes"]})
+        identical = bool(np.array_equal(means[False], means[True]))
+        same = same and identical
+        line = {"route": "ct_network_bake_sparse against ct_network_bake", **common, "grid": [g, g, g, a.azimuths, a.cosines],
+                "nodes": runs[True][0]["nodes"], "active_nodes": runs[True][0]["active"],
+                "active_share": runs[True][0]["active"] / runs[True][0]["nodes"], "subframes": a.subframes,
+                "means_bit_identical": identical, "lit_pixels_of_the_mean": int((means[False][..., 0] > 0).sum())}
+        for sparse, name in ((False, "dense"), (True, "sparse")):
+            r = runs[sparse]
+            line.update({f"{name}_mask_ms": med(v["mask"] for v in r), f"{name}_gather_ms": med(v["gather"] for v in r),
+                         f"{name}_network_ms": med(v["network"] for v in r), f"{name}_bake_wall_ms": med(v["wall"] for v in r),
+                         f"{name}_bake_wall_ms_min_max": [min(v["wall"] for v in r), max(v["wall"] for v in r)],
+                         f"{name}_baked_subframe_gpu_ms": med(v["subframe"] for v in r)})
+        print(json.dumps(line), flush=True)
+    return same
 
 
 if __name__ == "__main__":
@@ -34,6 +80,7 @@ if __name__ == "__main__":
     ap.add_argument("--cosines", type=int, default=8)
     ap.add_argument("--direct", action="store_true")
     ap.add_argument("--bias", type=float, default=1.0)
+    ap.add_argument("--sparse", action="store_true")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -48,6 +95,12 @@ if __name__ == "__main__":
     med = statistics.median
     common = {"network": [200, 1, 3], "output_bias_raised_by": a.bias, "volume": a.volume, "frame": [a.size, a.size], "repeats": a.repeats,
               "direct": a.direct}
+
+    if a.sparse:
+        ok = sparse_against_dense(a, tr, net, common)
+        net.close()
+        tr.close()
+        sys.exit(0 if ok else 1)
 
     # the network route's image, once
     tr.reset()

@@ -234,7 +234,8 @@ struct CtHandle_ {
     uint32_t subframes = 0;
     double render_ms = 0, accum_ms = 0;
     double dframe_scatter_ms = 0, dframe_gather_ms = 0;   // the last ct_descriptor_frame (ct_debug_descriptor_frame_time)
-    // ct_network_render_*: the temporaries of a band stay with the handle (a frame is many bands, a render many frames).
+    // ct_network_render_*, ct_baked_render_* and the bake's chunks: the temporaries of a band stay with the handle (a frame is
+    // many bands, a render many frames).  The baked renderer uses found / waves / direct only, reserved at the same sizes.
     // found / waves / pos / dir / aux / out hold a band of band_cap pixels; desc holds desc_cap records, the largest count
     // seen so far (or what the device gave: a band with more records goes through gather and network in pieces).  direct holds
     // a band of direct_cap pixels and exists from the first call with CT_NET_ADD_SINGLE_SCATTER on.
@@ -244,7 +245,7 @@ struct CtHandle_ {
         float *pos = nullptr, *dir = nullptr, *aux = nullptr, *out = nullptr;
         uint8_t *desc = nullptr;
         size_t band_cap = 0, desc_cap = 0, direct_cap = 0;
-        double ms[4] = { 0, 0, 0, 0 };   // the last call (ct_debug_network_render_time)
+        double ms[4] = { 0, 0, 0, 0 };   // the last ct_network_render_* call (ct_debug_network_render_time); a baked call leaves it
         // ct_network_render_shard_*: this shard's 8x8 tiles in ascending ty * tiles_x + tx (ct_shard_tiles), built on first use
         uint32_t *tiles = nullptr;
         uint32_t n_tiles = 0;

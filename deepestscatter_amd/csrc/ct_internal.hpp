@@ -261,7 +261,8 @@ struct BakeTable {
     float ax, ay, az, bx, by, bz;    // the azimuth frame
 };
 // The bake's own kernels: aux[i] = value; table[i * stride + k] = out[i]; and (ct_debug_bake_lookup) the lookup of caller-supplied
-// records.  launch_baked_compose is launch_network_compose with a record's output looked up in the table.
+// records.  launch_baked_compose forms a band's pixels as launch_network_compose does (the kernels share everything behind a
+// record's output), with the output looked up in the table.
 hipError_t launch_bake_fill(float *aux, uint32_t count, float value, hipStream_t stream);
 hipError_t launch_bake_store(const float *out, uint32_t count, float *table, uint32_t stride, uint32_t k, hipStream_t stream);
 hipError_t launch_bake_lookup(const DevScene &sc, const BakeTable &t, const float *positions, const float *directions, uint32_t count,

@@ -3335,6 +3335,43 @@ hipError_t launch_network_aux(const float *directions, uint32_t count, float lx,
     return hipGetLastError();
 }
 
+// What network_compose_kernel and baked_compose_kernel share behind a record's network output o, which each obtains its own way.
+
+// A pixel without a record: the miss value of ct_render_subframe.
+CT_DEV float4 compose_miss()
+{
+    return make_float4(0.f, 0.f, 0.f, 1.f);
+}
+
+// A pixel with a record, lane i of the band.  DIRECT: its single-scatter term is added behind the rounded product.
+template <bool DIRECT>
+CT_DEV float4 compose_value(const NetCompose &c, float o, const float4 *direct, uint32_t i)
+{
+    const float L = c.transform == 1 /* CT_NET_OUT_EXPM1 */ ? ct_expf(o) - 1.0f : o;
+    const float g = L > 0.f ? L : 0.f;   // (a NaN becomes 0)
+    float4 v = make_float4(c.sr * g, c.sg * g, c.sb * g, 1.f);
+    if constexpr (DIRECT) {
+        const float4 d = direct[i];
+        v.x += d.x;
+        v.y += d.y;
+        v.z += d.z;
+    }
+    return v;
+}
+
+template <bool ACCUMULATE>
+CT_DEV void compose_store(float4 v, size_t at, float4 *frame, float4 *mean, float4 *m2, uint32_t subframe_id)
+{
+    if constexpr (ACCUMULATE) {
+        float4 mu = mean[at], var = m2[at];
+        welford(mu, var, v, subframe_id);
+        mean[at] = mu;
+        m2[at] = var;
+    } else {
+        frame[at] = v;
+    }
+}
+
 // Lane i is pixel i of the band (whole rows, so also pixel i behind the band's first pixel in the frame).  Its record, if it has
 // one, is where first_scatter_compact_kernel put it: the wave's offset + the lane's rank among the wave's valid lanes, both
 // made again from the flight's temporary -- a gather, so neither a scatter by the pixel list nor an atomic.
@@ -3376,27 +3413,11 @@ __global__ __launch_bounds__(256) void network_compose_kernel(PixelBand b, const
         }
         at = (size_t)y * b.width + x;
     }
-    float4 v = make_float4(0.f, 0.f, 0.f, 1.f);   // the miss value of ct_render_subframe
+    float4 v = compose_miss();
     if (valid) {
-        const float o = out[(size_t)wave_offsets[i >> 6] + rank];
-        const float L = c.transform == 1 /* CT_NET_OUT_EXPM1 */ ? ct_expf(o) - 1.0f : o;
-        const float g = L > 0.f ? L : 0.f;   // (a NaN becomes 0)
-        v = make_float4(c.sr * g, c.sg * g, c.sb * g, 1.f);
-        if constexpr (DIRECT) {
-            const float4 d = direct[i];
-            v.x += d.x;
-            v.y += d.y;
-            v.z += d.z;
-        }
+        v = compose_value<DIRECT>(c, out[(size_t)wave_offsets[i >> 6] + rank], direct, i);
     }
-    if (ACCUMULATE) {
-        float4 mu = mean[at], var = m2[at];
-        welford(mu, var, v, subframe_id);
-        mean[at] = mu;
-        m2[at] = var;
-    } else {
-        frame[at] = v;
-    }
+    compose_store<ACCUMULATE>(v, at, frame, mean, m2, subframe_id);
 }
 
 hipError_t launch_network_compose(const PixelBand &band, const FlightTemps &t, const NetCompose &c, const float *out,
@@ -3738,9 +3759,9 @@ hipError_t launch_bake_lookup(const DevScene &sc, const BakeTable &t, const floa
     return hipGetLastError();
 }
 
-// network_compose_kernel with a record's output looked up in the table at the record's world position (the flight's temporary)
-// and d2, made again from the pixel as first_scatter_compact_kernel makes it: no ballot, no rank, no wave offsets.  ACCUMULATE,
-// DIRECT, TILES, the frozen test and what a lane without a pixel or a record does are network_compose_kernel's.
+// The band's pixels with a record's output looked up in the table at the record's world position (the flight's temporary) and
+// d2, made again from the pixel as first_scatter_compact_kernel makes it: no ballot, no rank, no wave offsets.  ACCUMULATE,
+// DIRECT and TILES mean what they mean for network_compose_kernel, and everything behind the output is the shared compose_* code.
 template <bool ACCUMULATE, bool DIRECT, bool TILES>
 __global__ __launch_bounds__(256) void baked_compose_kernel(DevScene sc, PixelBand b, const float4 *__restrict__ found, BakeTable t,
                                                             NetCompose c, float4 *__restrict__ frame, float4 *__restrict__ mean,
@@ -3748,7 +3769,7 @@ __global__ __launch_bounds__(256) void baked_compose_kernel(DevScene sc, PixelBa
                                                             const uint32_t *__restrict__ frozen, const float4 *__restrict__ direct)
 {
     if (ACCUMULATE && frozen && *frozen != 0u) {
-        return;
+        return;   // the image has converged (converged_freeze_kernel): the running mean stays as it is
     }
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= b.n) {
@@ -3760,28 +3781,12 @@ __global__ __launch_bounds__(256) void baked_compose_kernel(DevScene sc, PixelBa
     }
     const size_t at = TILES ? (size_t)y * b.width + x : (size_t)i;
     const float4 f = found[i];
-    float4 v = make_float4(0.f, 0.f, 0.f, 1.f);
+    float4 v = compose_miss();
     if (f.w != 0.f) {
         const f3 dir = normalize3(primary_direction(sc, x, y));
-        const float o = bake_lookup(sc, t, mk3(f.x, f.y, f.z), dir);
-        const float L = c.transform == 1 /* CT_NET_OUT_EXPM1 */ ? ct_expf(o) - 1.0f : o;
-        const float g = L > 0.f ? L : 0.f;
-        v = make_float4(c.sr * g, c.sg * g, c.sb * g, 1.f);
-        if constexpr (DIRECT) {
-            const float4 d = direct[i];
-            v.x += d.x;
-            v.y += d.y;
-            v.z += d.z;
-        }
+        v = compose_value<DIRECT>(c, bake_lookup(sc, t, mk3(f.x, f.y, f.z), dir), direct, i);
     }
-    if (ACCUMULATE) {
-        float4 mu = mean[at], var = m2[at];
-        welford(mu, var, v, subframe_id);
-        mean[at] = mu;
-        m2[at] = var;
-    } else {
-        frame[at] = v;
-    }
+    compose_store<ACCUMULATE>(v, at, frame, mean, m2, subframe_id);
 }
 
 hipError_t launch_baked_compose(const DevScene &sc, const PixelBand &band, const FlightTemps &t, const BakeTable &table, const NetCompose &c,

@@ -7,6 +7,40 @@
 #include "ct_handle.hpp"
 #include "ct_network.hpp"
 
+// Runs `body`; when it fails, what it has enqueued is waited for before the call returns.
+template <typename F>
+static int drained(CtHandle h, F &&body)
+{
+    const int rc = body();
+    if (rc != CT_OK) {
+        hipStreamSynchronize(h->stream);
+    }
+    return rc;
+}
+
+// `launches` between the handle's first two events, waited for; *ms_sum grows by their GPU time.  count_dev: a count the
+// launches leave on the device, read into *count_out behind them (the one 4-byte read of a band, a frame or a mask).
+template <typename F>
+static int timed(CtHandle h, double *ms_sum, F &&launches, const uint32_t *count_dev = nullptr, uint32_t *count_out = nullptr)
+{
+    HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
+    const int rc = launches();
+    if (rc != CT_OK) {
+        return rc;
+    }
+    HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
+    if (count_dev) {
+        HIPCHK(h, hipMemcpyAsync(count_out, count_dev, sizeof *count_out, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    } else {
+        HIPCHK(h, hipEventSynchronize(h->ev[1]));
+    }
+    float ms = 0;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+    *ms_sum += ms;
+    return CT_OK;
+}
+
 // VDBCloud::getVoxelSizeInMeters / getVoxelSizeInTermsOfFreePath (VDBCloud.cpp:35-46), DisneyDescriptor.cuh:83
 struct DescriptorScale {
     float level0, voxel_m;
@@ -72,7 +106,7 @@ extern "C" int ct_collect_descriptors(CtHandle h, const float *positions_host, c
     const DescriptorScale ds = descriptor_scale(h);
     DevTemp<float> d_pos, d_dir;
     DevTemp<uint8_t> d_out;
-    auto run = [&]() -> int {
+    return drained(h, [&]() -> int {
         HIPCHK(h, dmalloc(&d_pos, 3 * (size_t)count));
         HIPCHK(h, dmalloc(&d_dir, 3 * (size_t)count));
         HIPCHK(h, dmalloc(&d_out, (size_t)count * CT_DESCRIPTOR_BYTES));
@@ -84,10 +118,21 @@ extern "C" int ct_collect_descriptors(CtHandle h, const float *positions_host, c
                                  h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         return CT_OK;
-    };
-    const int rc = run();
-    if (rc != CT_OK) {
-        hipStreamSynchronize(h->stream);
+    });
+}
+
+// A band's first flights, the scan of their counts and the compacting write (at most `capacity` records), timed into *ms_sum,
+// then the band's record count: one 4-byte read and the wait for it.  No band counts more records than it has pixels.
+static int flights_counted(CtHandle h, const PixelBand &band, const FlightTemps &t, uint32_t subframe_id, uint32_t capacity, float *pos,
+                           float *dir, uint32_t *pixels, double *ms_sum, uint32_t *count_out)
+{
+    const uint32_t n_pad = (band.n + 255u) / 256u * 256u;
+    const int rc = timed(h, ms_sum, [&]() -> int {
+        HIPCHK(h, launch_first_scatter_frame(h->dev, band, t, subframe_id, capacity, pos, dir, pixels, h->stream));
+        return CT_OK;
+    }, t.waves + n_pad / 64u, count_out);
+    if (rc == CT_OK && *count_out > band.n) {
+        return fail(h, CT_E_HIP, "internal: a band of %u pixels counted %u records", band.n, *count_out);
     }
     return rc;
 }
@@ -115,7 +160,7 @@ extern "C" int ct_descriptor_frame(CtHandle h, uint32_t subframe_id, const uint3
     DevTemp<uint32_t> d_waves;
     DevTemp<float> d_pos, d_dir;
     h->dframe_scatter_ms = h->dframe_gather_ms = 0;
-    auto run = [&]() -> int {
+    return drained(h, [&]() -> int {
         // every temporary before any kernel
         const size_t held = std::max<size_t>(1, std::min<size_t>(capacity, n));   // records the compacting write can produce
         HIPCHK(h, dmalloc(&d_found, n_pad));
@@ -131,37 +176,25 @@ extern "C" int ct_descriptor_frame(CtHandle h, uint32_t subframe_id, const uint3
             return prc;
         }
         float *pos = positions_dev ? positions_dev : d_pos.p, *dir = directions_dev ? directions_dev : d_dir.p;
-        HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-        HIPCHK(h, launch_first_scatter_frame(h->dev, rect_band(x0, y0, rw, y1 - y0), { d_found, d_waves, nullptr }, subframe_id, capacity,
-                                             pos, dir, pixels_dev, h->stream));
-        HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
         uint32_t count = 0;
-        HIPCHK(h, hipMemcpyAsync(&count, d_waves + n_pad / 64u, sizeof count, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
+        const int rc = flights_counted(h, rect_band(x0, y0, rw, y1 - y0), { d_found, d_waves, nullptr }, subframe_id, capacity, pos, dir,
+                                       pixels_dev, &h->dframe_scatter_ms, &count);
+        if (rc != CT_OK) {
+            return rc;
+        }
         *count_out = count;
-        float ms = 0;
-        HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-        h->dframe_scatter_ms = ms;
         if (count > capacity) {
             return fail(h, CT_E_INVAL, "ct_descriptor_frame: %u valid pixels do not fit a capacity of %u", count, capacity);
         }
         if (count == 0) {
             return CT_OK;
         }
-        HIPCHK(h, hipEventRecord(h->ev[0], h->stream));   // (not ev[1] again: the host's look at the count is no part of the gather)
-        HIPCHK(h, launch_descriptors(h->dev, h->pyramid, pos, dir, count, ds.level0, ds.voxel_m, h->scene.cloud_size_m, descriptors_dev,
-                                     h->stream));
-        HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-        h->dframe_gather_ms = ms;
-        return CT_OK;
-    };
-    const int rc = run();
-    if (rc != CT_OK) {
-        hipStreamSynchronize(h->stream);
-    }
-    return rc;
+        return timed(h, &h->dframe_gather_ms, [&]() -> int {   // (the host's look at the count is no part of the gather)
+            HIPCHK(h, launch_descriptors(h->dev, h->pyramid, pos, dir, count, ds.level0, ds.voxel_m, h->scene.cloud_size_m,
+                                         descriptors_dev, h->stream));
+            return CT_OK;
+        });
+    });
 }
 
 extern "C" int ct_debug_descriptor_frame_time(CtHandle h, double *first_scatter_ms_out, double *gather_ms_out)
@@ -208,9 +241,8 @@ extern "C" int ct_network_eval(CtHandle h, CtNetwork n, const uint8_t *descripto
     return rc == CT_OK ? CT_OK : fail(h, rc, "%s", err);
 }
 
-// ---- the network as a renderer (ct_network_render_*) ------------------------------------------------------------------
-// Every CT_E_INVAL of the two entry points except the NULL handle and the ids; nothing of the handle is touched.
-// (in three parts, which the baked entry points below share in the same order: the parameters, the network, the shards)
+// ---- what the renderer (ct_network_render_*, ct_baked_render_*) and the bake share: checks and the handle's scratch ----------
+// The checks touch nothing of the handle.
 static int net_validate_params(CtHandle h, const CtNetworkRender *p, const char *who)
 {
     if (p->abi_version != CT_ABI_VERSION) {
@@ -246,62 +278,6 @@ static int net_validate_shards(CtHandle h, const char *who, bool shards, const c
                                    "%s_shard_accumulate", who, h->scene.shard_index, h->scene.shard_count, family, family);
     }
     return CT_OK;
-}
-
-static int net_validate(CtHandle h, CtNetwork n, const CtNetworkRender *p, const char *who, bool shards)
-{
-    if (!n || !p) {
-        return fail(h, CT_E_INVAL, "%s: need a network and its parameters", who);
-    }
-    int rc = net_validate_params(h, p, who);
-    if (rc == CT_OK) {
-        rc = net_validate_network(h, n, who);
-    }
-    if (rc == CT_OK) {
-        rc = net_validate_shards(h, who, shards, "ct_network_render");
-    }
-    return rc;
-}
-
-// A validated call.  Its bands are made of units: rows of the frame, or (tiles: ct_network_render_shard_*) tiles of the shard's
-// tile list.
-struct NetCall {
-    CtNetwork n;
-    const CtNetworkRender *p;
-    bool accumulate;   // into mean / M2 instead of the frame
-    bool tiles;
-    bool direct;       // the call carries CT_NET_ADD_SINGLE_SCATTER
-    DescriptorScale ds;
-};
-
-// What the entry points do before they run: the handle, every argument (first: a rejected call leaves the handle exactly as it
-// was, batches in flight included), the camera, then the wait for the batches in flight.  bad_ids: NULL, or the message
-// (a format of `who`) that refuses the call's subframe ids.
-static int net_begin(CtHandle h, CtNetwork n, const CtNetworkRender *p, const char *who, bool accumulate, bool tiles, const char *bad_ids,
-                     NetCall &c)
-{
-    NEED_NOFLUSH(h);
-    const int rc = net_validate(h, n, p, who, tiles);
-    if (rc != CT_OK) {
-        return rc;
-    }
-    if (bad_ids) {
-        return fail(h, CT_E_INVAL, bad_ids, who);
-    }
-    if (!h->camera_set) {
-        return fail(h, CT_E_STATE, "ct_set_camera has not been called");
-    }
-    c = { n, p, accumulate, tiles, (p->transform & CT_NET_ADD_SINGLE_SCATTER) != 0, descriptor_scale(h) };
-    return flush(h);
-}
-
-// Units of a band.  Rows: whole rows of at most band_pixels pixels, at least one (a row has at most 12288 pixels), at most 2^20
-// pixels.  Tiles: at most band_pixels / 64, at least one, at most 2^14 (2^20 lanes).
-static uint32_t net_band_units(CtHandle h, const NetCall &c)
-{
-    const uint32_t band_pixels = c.p->band_pixels;
-    const uint32_t cap = (band_pixels == 0u || band_pixels > (1u << 20)) ? (1u << 20) : band_pixels;
-    return c.tiles ? std::max(1u, cap / 64u) : std::min(h->scene.height, std::max(1u, cap / h->scene.width));
 }
 
 // Records the descriptor array may hold at most: 2^20 (a band has no more), or CT_NET_DESC_RECORDS.
@@ -399,192 +375,6 @@ static int net_ensure_tiles(CtHandle h)
     s.n_tiles = count;
     s.tiles_built = true;
     return CT_OK;
-}
-
-// One band of subframe `sid`, units [unit0, unit0 + units) of the call, into the frame or into mean / M2.
-static int net_band(CtHandle h, const NetCall &c, uint32_t sid, uint32_t unit0, uint32_t units)
-{
-    CtHandle_::NetScratch &s = h->net;
-    const uint32_t W = h->scene.width;
-    const PixelBand band = c.tiles ? tile_band(h->dev, s.tiles + unit0, units) : rect_band(0u, unit0, W, units);
-    const uint32_t npx = band.n, n_pad = (npx + 255u) / 256u * 256u;
-    const FlightTemps temps{ s.found, s.waves, c.direct ? s.direct : nullptr };
-    float ms = 0;
-    HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-    HIPCHK(h, launch_first_scatter_frame(h->dev, band, temps, sid, npx, s.pos, s.dir, nullptr, h->stream));
-    HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
-    uint32_t count = 0;
-    HIPCHK(h, hipMemcpyAsync(&count, s.waves + n_pad / 64u, sizeof count, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-    s.ms[0] += ms;
-    if (count > npx) {
-        return fail(h, CT_E_HIP, "internal: a band of %u pixels counted %u records", npx, count);
-    }
-    if (count != 0u) {
-        net_grow_descriptors(h, count);
-        for (uint32_t at = 0; at < count;) {
-            const uint32_t piece = (uint32_t)std::min<size_t>(count - at, s.desc_cap);
-            HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-            HIPCHK(h, launch_descriptors(h->dev, h->pyramid, s.pos + 3 * (size_t)at, s.dir + 3 * (size_t)at, piece, c.ds.level0, c.ds.voxel_m,
-                                         h->scene.cloud_size_m, s.desc, h->stream));
-            HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
-            // l = the direction the light travels: the uniforms hold -l (Sun.cpp:13-18)
-            HIPCHK(h, launch_network_aux(s.dir + 3 * (size_t)at, piece, -h->dev.nlx, -h->dev.nly, -h->dev.nlz, s.aux + at, h->stream));
-            HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
-            char err[256] = "";
-            const int rc = ct::network_eval(c.n, h->stream, s.desc, s.aux + at, piece, s.out + at, err, sizeof err);   // (waits)
-            if (rc != CT_OK) {
-                return fail(h, rc, "%s", err);
-            }
-            HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-            s.ms[1] += ms;
-            HIPCHK(h, hipEventElapsedTime(&ms, h->ev[1], h->ev[2]));
-            s.ms[3] += ms;
-            double net_ms = 0;
-            ct_debug_network_time(c.n, &net_ms);
-            s.ms[2] += net_ms;
-            at += piece;
-        }
-    }
-    const NetCompose compose{ c.p->transform & 0xff, c.p->rgb_scale[0], c.p->rgb_scale[1], c.p->rgb_scale[2] };
-    const size_t first_pixel = c.tiles ? 0 : (size_t)unit0 * W;   // (the tile path writes at y * W + x of the whole frame)
-    const ComposeTarget dst{ c.accumulate ? nullptr : h->d_frame + first_pixel, h->d_mean + first_pixel, h->d_m2 + first_pixel, sid };
-    HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-    HIPCHK(h, launch_network_compose(band, temps, compose, s.out, dst, h->stop_cadence ? h->d_freeze : nullptr, h->stream));
-    HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
-    HIPCHK(h, hipEventSynchronize(h->ev[1]));
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-    s.ms[3] += ms;
-    if (c.accumulate) {
-        h->accum_ms += ms;
-    }
-    return CT_OK;
-}
-
-// Subframes [first, first + count) band by band.  The caller has validated and flushed.  A frame of the tile path is first
-// filled with the shard's background.
-static int net_run(CtHandle h, const NetCall &c, uint32_t first, uint32_t count)
-{
-    const uint32_t H = h->scene.height, per_band = net_band_units(h, c);
-    for (double &ms : h->net.ms) {
-        ms = 0;
-    }
-    auto run = [&]() -> int {
-        int rc = c.tiles ? net_ensure_tiles(h) : CT_OK;
-        if (rc != CT_OK) {
-            return rc;
-        }
-        // (bands of the row path run bottom to top over H rows; those of the tile path over the list's n_tiles tiles)
-        const uint32_t units = c.tiles ? h->net.n_tiles : H;
-        const size_t band = c.tiles ? (size_t)64 * std::min(per_band, std::max(units, 1u)) : (size_t)h->scene.width * per_band;
-        rc = net_reserve(h, band, c.direct);
-        if (rc == CT_OK) {
-            rc = ensure_pyramid(h);
-        }
-        if (rc != CT_OK) {
-            return rc;
-        }
-        if (c.accumulate) {
-            discard_ahead(h);   // like ct_accumulate: the running mean leaves the order the samples rendered ahead were made for
-        }
-        for (uint32_t k = 0; k < count; k++) {
-            const uint32_t sid = first + k;
-            if (c.tiles && !c.accumulate) {
-                // the shard's background, as ct_render_subframe starts from it: the bands write the own pixels only
-                float ms = 0;
-                HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-                HIPCHK(h, launch_fill_frame(h->d_frame, h->scene.width, H, h->scene.shard_index, h->scene.shard_count, h->stream));
-                HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
-                HIPCHK(h, hipEventSynchronize(h->ev[1]));
-                HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-                h->net.ms[3] += ms;
-            }
-            for (uint32_t unit0 = 0; unit0 < units; unit0 += per_band) {
-                rc = net_band(h, c, sid, unit0, std::min(per_band, units - unit0));
-                if (rc != CT_OK) {
-                    return rc;
-                }
-            }
-            if (c.accumulate) {
-                if (h->stop_cadence && sid % h->stop_cadence == 0u && sid >= h->stop_min) {   // as ct_accumulate
-                    rc = enqueue_convergence_test(h, sid);
-                    if (rc != CT_OK) {
-                        return rc;
-                    }
-                    HIPCHK(h, hipStreamSynchronize(h->stream));
-                }
-                h->subframes = sid;
-                discard_ahead(h);
-            }
-        }
-        return CT_OK;
-    };
-    const int rc = run();
-    if (rc != CT_OK) {
-        hipStreamSynchronize(h->stream);
-    }
-    return rc;
-}
-
-static int net_subframe(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t subframe_id, float *frame_rgba_dev, bool tiles)
-{
-    NetCall c;
-    int rc = net_begin(h, n, p, tiles ? "ct_network_render_shard_subframe" : "ct_network_render_subframe", false, tiles,
-                       subframe_id == 0 ? "subframe ids are 1-based (Camera.cpp:191)" : nullptr, c);
-    if (rc != CT_OK) {
-        return rc;
-    }
-    rc = net_run(h, c, subframe_id, 1);
-    if (rc != CT_OK) {
-        return rc;
-    }
-    if (frame_rgba_dev) {
-        HIPCHK(h, hipMemcpyAsync(frame_rgba_dev, h->d_frame, (size_t)h->scene.width * h->scene.height * sizeof(float4),
-                                 hipMemcpyDeviceToDevice, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    return CT_OK;
-}
-
-extern "C" int ct_network_render_subframe(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t subframe_id, float *frame_rgba_dev)
-{
-    return net_subframe(h, n, p, subframe_id, frame_rgba_dev, false);
-}
-
-extern "C" int ct_network_render_shard_subframe(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t subframe_id,
-                                                float *frame_rgba_dev)
-{
-    return net_subframe(h, n, p, subframe_id, frame_rgba_dev, true);
-}
-
-static int net_accumulate(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t first_subframe_id, uint32_t count, bool tiles)
-{
-    const char *const who = tiles ? "ct_network_render_shard_accumulate" : "ct_network_render_accumulate";
-    NetCall c;
-    const int rc = net_begin(h, n, p, who, true, tiles,
-                             first_subframe_id == 0 || count == 0 ? "%s: subframe ids are 1-based and count must not be 0" : nullptr, c);
-    if (rc != CT_OK) {
-        return rc;
-    }
-    if (first_subframe_id != h->subframes + 1) {
-        return fail(h, CT_E_STATE, "first_subframe_id %u but %u subframes are accumulated", first_subframe_id, h->subframes);
-    }
-    if (count > 0xffffffffu - first_subframe_id + 1u) {
-        return fail(h, CT_E_INVAL, "%s: %u subframes from %u on exceed the 32-bit subframe id", who, count, first_subframe_id);
-    }
-    return net_run(h, c, first_subframe_id, count);
-}
-
-extern "C" int ct_network_render_accumulate(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t first_subframe_id, uint32_t count)
-{
-    return net_accumulate(h, n, p, first_subframe_id, count, false);
-}
-
-extern "C" int ct_network_render_shard_accumulate(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t first_subframe_id,
-                                                  uint32_t count)
-{
-    return net_accumulate(h, n, p, first_subframe_id, count, true);
 }
 
 // ---- the network baked into a probe table (ct_network_bake, ct_baked_render_*) -----------------------------------------
@@ -720,7 +510,7 @@ static int bake_mask_reserve(CtHandle h, const uint32_t grid[3], BakeMask &m)
 static int bake_mask_run(CtHandle h, const uint32_t grid[3], BakeMask &m, uint32_t *active_out, double *ms_out)
 {
     const uint64_t nodes = (uint64_t)grid[0] * grid[1] * grid[2];
-    auto run = [&]() -> int {
+    return drained(h, [&]() -> int {
         HIPCHK(h, hipMemcpyAsync(m.ranges, m.host_ranges.data(), m.host_ranges.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
         BakeMaskArgs a{};
         a.density = h->d_density;
@@ -736,32 +526,86 @@ static int bake_mask_run(CtHandle h, const uint32_t grid[3], BakeMask &m, uint32
         a.nodes = m.nodes;
         a.waves = m.waves;
         a.list = m.list;
-        HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-        HIPCHK(h, launch_bake_mask(a, h->stream));
-        HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
         uint32_t count = 0;
-        HIPCHK(h, hipMemcpyAsync(&count, m.waves + (bake_mask_waves(nodes) - 1u), sizeof count, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        float ms = 0;
-        HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+        double ms = 0;
+        const int rc = timed(h, &ms, [&]() -> int {
+            HIPCHK(h, launch_bake_mask(a, h->stream));
+            return CT_OK;
+        }, m.waves + (bake_mask_waves(nodes) - 1u), &count);
+        if (rc != CT_OK) {
+            return rc;
+        }
         if (count > nodes) {
             return fail(h, CT_E_HIP, "internal: a grid of %llu nodes counted %u active ones", (unsigned long long)nodes, count);
         }
         *active_out = count;
         *ms_out = ms;
         return CT_OK;
-    };
-    const int rc = run();
-    if (rc != CT_OK) {
-        hipStreamSynchronize(h->stream);
+    });
+}
+
+// The tables of the sparse bake's record kernel in b->d_probe, by bake_probe (ct_bake_probes' floats): the position nodes of x,
+// y and z, then the Nphi probe directions.
+static int bake_upload_probe_tables(CtHandle h, const CtBake_ *b)
+{
+    const uint32_t nx = b->grid[0], ny = b->grid[1], nz = b->grid[2];
+    std::vector<float> host(nx + ny + nz + 3 * (size_t)b->azimuths);
+    float p[3], d[3];
+    for (uint32_t i = 0; i < nx; i++) {
+        bake_probe(b, (uint64_t)i * b->azimuths, p, d);
+        host[i] = p[0];
     }
-    return rc;
+    for (uint32_t i = 0; i < ny; i++) {
+        bake_probe(b, (uint64_t)i * nx * b->azimuths, p, d);
+        host[nx + i] = p[1];
+    }
+    for (uint32_t i = 0; i < nz; i++) {
+        bake_probe(b, (uint64_t)i * nx * ny * b->azimuths, p, d);
+        host[nx + ny + i] = p[2];
+    }
+    for (uint32_t j = 0; j < b->azimuths; j++) {
+        bake_probe(b, j, p, &host[nx + ny + nz + 3 * (size_t)j]);
+    }
+    HIPCHK(h, hipMemcpy(b->d_probe, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
+    return CT_OK;
+}
+
+// The records of probes [first, first + count) in the handle's scratch.  Dense: made on the host (pos / dir, which the stream
+// has left) and copied.  Sparse: the compacted probes -- azimuth p % Nphi of node list[p / Nphi] -- from the record kernel,
+// timed into *records_ms.
+static int bake_chunk_records(CtHandle h, const CtBake_ *b, uint64_t first, uint32_t count, std::vector<float> &pos, std::vector<float> &dir,
+                              double *records_ms)
+{
+    CtHandle_::NetScratch &s = h->net;
+    if (b->sparse) {
+        return timed(h, records_ms, [&]() -> int {
+            HIPCHK(h, launch_bake_records(b->d_list, first, count, b->grid[0], b->grid[1], b->azimuths, b->d_probe,
+                                          b->d_probe + (b->grid[0] + b->grid[1] + b->grid[2]), s.pos, s.dir, h->stream));
+            return CT_OK;
+        });
+    }
+    for (uint32_t i = 0; i < count; i++) {
+        bake_probe(b, first + i, &pos[3 * (size_t)i], &dir[3 * (size_t)i]);
+    }
+    HIPCHK(h, hipMemcpyAsync(s.pos, pos.data(), 3 * (size_t)count * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(s.dir, dir.data(), 3 * (size_t)count * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    return CT_OK;
+}
+
+// The network's outputs for polar node k of probes [first, first + piece) into the table: in place, or through the list.
+static int bake_store_piece(CtHandle h, const CtBake_ *b, float *table, uint64_t first, uint32_t piece, uint32_t k)
+{
+    if (b->sparse) {
+        HIPCHK(h, launch_bake_store_list(h->net.out, b->d_list, first, piece, b->azimuths, table, b->cosines, k, h->stream));
+    } else {
+        HIPCHK(h, launch_bake_store(h->net.out, piece, table + first * b->cosines, b->cosines, k, h->stream));
+    }
+    return CT_OK;
 }
 
 // Fills `table` (b->entries floats, allocated) for the handle's light and network n: the probes in chunks through the handle's
 // scratch, one gather per piece and one evaluation per polar node.  b's frame is the new light's already.
-// A sparse bake runs the compacted probes -- azimuth p % Nphi of node list[p / Nphi] -- the same way: the table is zeroed first,
-// the chunk's records come from a kernel and the stores go through the list.
+// A sparse bake zeroes the table first and runs only the probes of its list.
 static int bake_run(CtHandle h, CtNetwork n, CtBake_ *b, float *table)
 {
     CtHandle_::NetScratch &s = h->net;
@@ -770,7 +614,7 @@ static int bake_run(CtHandle h, CtNetwork n, CtBake_ *b, float *table)
     const DescriptorScale ds = descriptor_scale(h);
     std::vector<float> pos(b->sparse ? 0 : 3 * chunk), dir(b->sparse ? 0 : 3 * chunk);
     double gather_ms = 0, network_ms = 0, records_ms = 0;
-    auto run = [&]() -> int {
+    const int rc = drained(h, [&]() -> int {
         if (b->sparse) {
             HIPCHK(h, hipMemsetAsync(table, 0, (size_t)b->entries * sizeof(float), h->stream));
             if (probes == 0u) {
@@ -786,45 +630,17 @@ static int bake_run(CtHandle h, CtNetwork n, CtBake_ *b, float *table)
             return rc;
         }
         net_grow_descriptors(h, chunk);
-        const float *axes = b->d_probe, *directions = b->sparse ? b->d_probe + (b->grid[0] + b->grid[1] + b->grid[2]) : nullptr;
-        if (b->sparse) {   // the tables of the record kernel, by bake_probe: ct_bake_probes' floats
-            const uint32_t nx = b->grid[0], ny = b->grid[1], nz = b->grid[2];
-            std::vector<float> host(nx + ny + nz + 3 * (size_t)b->azimuths);
-            float p[3], d[3];
-            for (uint32_t i = 0; i < nx; i++) {
-                bake_probe(b, (uint64_t)i * b->azimuths, p, d);
-                host[i] = p[0];
+        if (b->sparse) {
+            rc = bake_upload_probe_tables(h, b);
+            if (rc != CT_OK) {
+                return rc;
             }
-            for (uint32_t i = 0; i < ny; i++) {
-                bake_probe(b, (uint64_t)i * nx * b->azimuths, p, d);
-                host[nx + i] = p[1];
-            }
-            for (uint32_t i = 0; i < nz; i++) {
-                bake_probe(b, (uint64_t)i * nx * ny * b->azimuths, p, d);
-                host[nx + ny + i] = p[2];
-            }
-            for (uint32_t j = 0; j < b->azimuths; j++) {
-                bake_probe(b, j, p, &host[nx + ny + nz + 3 * (size_t)j]);
-            }
-            HIPCHK(h, hipMemcpy(b->d_probe, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
         }
         for (uint64_t first = 0; first < probes; first += chunk) {
             const uint32_t count = (uint32_t)std::min<uint64_t>(chunk, probes - first);
-            if (b->sparse) {
-                float ms = 0;
-                HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
-                HIPCHK(h, launch_bake_records(b->d_list, first, count, b->grid[0], b->grid[1], b->azimuths, axes, directions, s.pos, s.dir,
-                                              h->stream));
-                HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
-                HIPCHK(h, hipEventSynchronize(h->ev[1]));
-                HIPCHK(h, hipEventElapsedTime(&ms, h->ev[2], h->ev[1]));
-                records_ms += ms;
-            } else {
-                for (uint32_t i = 0; i < count; i++) {
-                    bake_probe(b, first + i, &pos[3 * (size_t)i], &dir[3 * (size_t)i]);
-                }
-                HIPCHK(h, hipMemcpyAsync(s.pos, pos.data(), 3 * (size_t)count * sizeof(float), hipMemcpyHostToDevice, h->stream));
-                HIPCHK(h, hipMemcpyAsync(s.dir, dir.data(), 3 * (size_t)count * sizeof(float), hipMemcpyHostToDevice, h->stream));
+            rc = bake_chunk_records(h, b, first, count, pos, dir, &records_ms);
+            if (rc != CT_OK) {
+                return rc;
             }
             for (uint32_t at = 0; at < count;) {
                 const uint32_t piece = (uint32_t)std::min<size_t>(count - at, s.desc_cap);
@@ -843,10 +659,9 @@ static int bake_run(CtHandle h, CtNetwork n, CtBake_ *b, float *table)
                     double net_ms = 0;
                     ct_debug_network_time(n, &net_ms);
                     network_ms += net_ms;
-                    if (b->sparse) {
-                        HIPCHK(h, launch_bake_store_list(s.out, b->d_list, first + at, piece, b->azimuths, table, b->cosines, k, h->stream));
-                    } else {
-                        HIPCHK(h, launch_bake_store(s.out, piece, table + (first + at) * b->cosines, b->cosines, k, h->stream));
+                    rc = bake_store_piece(h, b, table, first + at, piece, k);
+                    if (rc != CT_OK) {
+                        return rc;
                     }
                 }
                 HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
@@ -856,10 +671,8 @@ static int bake_run(CtHandle h, CtNetwork n, CtBake_ *b, float *table)
             HIPCHK(h, hipStreamSynchronize(h->stream));   // (before the host arrays are filled again)
         }
         return CT_OK;
-    };
-    const int rc = run();
+    });
     if (rc != CT_OK) {
-        hipStreamSynchronize(h->stream);
         return rc;
     }
     b->gather_ms = gather_ms;
@@ -935,6 +748,7 @@ static int bake_create(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtBake *out
         delete b;
         return fail(h, CT_E_NOMEM, "%s: no device memory for a table of %llu entries", who, (unsigned long long)entries);
     }
+    double mask_ms = 0;
     if (sparse) {   // the mask's temporaries, the node bytes, the list and the record tables: all before the first kernel, too
         BakeMask m;
         rc = bake_mask_reserve(h, b->grid, m);
@@ -943,7 +757,6 @@ static int bake_create(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtBake *out
             rc = fail(h, CT_E_NOMEM, "%s: no device memory for the probe tables", who);
         }
         uint32_t active = 0;
-        double mask_ms = 0;
         if (rc == CT_OK) {
             rc = bake_mask_run(h, b->grid, m, &active, &mask_ms);
         }
@@ -956,13 +769,10 @@ static int bake_create(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtBake *out
         b->active = active;
         b->d_nodes = m.nodes.release();
         b->d_list = m.list.release();
-        bake_frame(h, b);
-        rc = bake_run(h, n, b, b->d_table);
-        b->mask_ms += mask_ms;
-    } else {
-        bake_frame(h, b);
-        rc = bake_run(h, n, b, b->d_table);
     }
+    bake_frame(h, b);
+    rc = bake_run(h, n, b, b->d_table);
+    b->mask_ms += mask_ms;   // (bake_run has set it to its record kernel's time)
     if (rc != CT_OK) {
         bake_free(b);
         return rc;
@@ -1204,78 +1014,182 @@ extern "C" int ct_debug_bake_lookup(CtHandle h, CtBake b, const float *positions
     return CT_OK;
 }
 
-// net_begin for a bake: the same order -- arguments, ids, camera -- then the bake's light, then the wait.
-static int baked_begin(CtHandle h, CtBake b, const CtNetworkRender *p, const char *who, bool accumulate, bool tiles, const char *bad_ids,
-                       NetCall &c)
+// ---- the renderer: the network evaluated band by band (ct_network_render_*) or looked up in its bake (ct_baked_render_*) -------
+// A call of one of the eight entry points.  Its bands are made of units: rows of the frame, or (tiles: the *_shard_* entry
+// points) tiles of the shard's tile list.  The entry point fills the first part, net_begin the second.
+struct NetCall {
+    const char *who;
+    CtNetwork n;       // the source of a record's output: the network ...
+    CtBake b;          // ... or (baked) its bake; the other one is NULL
+    const CtNetworkRender *p;
+    bool baked, tiles;
+    bool accumulate;   // into mean / M2 instead of the frame
+    bool direct;       // the call carries CT_NET_ADD_SINGLE_SCATTER
+    DescriptorScale ds;
+};
+
+// What the entry points do before they run: the handle, every argument (first: a rejected call leaves the handle exactly as it
+// was, batches in flight included), the camera, a bake's light, then the wait for the batches in flight.  bad_ids: NULL, or the
+// message (a format of c.who) that refuses the call's subframe ids.
+static int net_begin(CtHandle h, NetCall &c, bool accumulate, const char *bad_ids)
 {
     if (!h) {
         return fail(nullptr, CT_E_INVAL, "null handle");
     }
-    if (!b || !p) {
-        return fail(h, CT_E_INVAL, "%s: need a bake and its parameters", who);
+    if (!c.p || (c.baked ? !c.b : !c.n)) {
+        return fail(h, CT_E_INVAL, "%s: need a %s and its parameters", c.who, c.baked ? "bake" : "network");
     }
     NEED_NOFLUSH(h);
-    int rc = net_validate_params(h, p, who);
+    int rc = net_validate_params(h, c.p, c.who);
     if (rc == CT_OK) {
-        rc = bake_foreign(h, b, who);
+        rc = c.baked ? bake_foreign(h, c.b, c.who) : net_validate_network(h, c.n, c.who);
     }
     if (rc == CT_OK) {
-        rc = net_validate_shards(h, who, tiles, "ct_baked_render");
+        rc = net_validate_shards(h, c.who, c.tiles, c.baked ? "ct_baked_render" : "ct_network_render");
     }
     if (rc != CT_OK) {
         return rc;
     }
     if (bad_ids) {
-        return fail(h, CT_E_INVAL, bad_ids, who);
+        return fail(h, CT_E_INVAL, bad_ids, c.who);
     }
     if (!h->camera_set) {
         return fail(h, CT_E_STATE, "ct_set_camera has not been called");
     }
-    rc = bake_stale(h, b, who);
-    if (rc != CT_OK) {
-        return rc;
+    if (c.baked) {
+        rc = bake_stale(h, c.b, c.who);
+        if (rc != CT_OK) {
+            return rc;
+        }
     }
-    c = { nullptr, p, accumulate, tiles, (p->transform & CT_NET_ADD_SINGLE_SCATTER) != 0, descriptor_scale(h) };
+    c.accumulate = accumulate;
+    c.direct = (c.p->transform & CT_NET_ADD_SINGLE_SCATTER) != 0;
+    c.ds = descriptor_scale(h);
     return flush(h);
 }
 
-// net_run without gather and network: per band the flights and one kernel that looks the table up and forms the pixels.
-// Everything is enqueued and waited for once (the convergence test keeps its own wait); one event pair times the call.
-static int baked_run(CtHandle h, CtBake b, const NetCall &c, uint32_t first, uint32_t count)
+// Units of a band.  Rows: whole rows of at most band_pixels pixels, at least one (a row has at most 12288 pixels), at most 2^20
+// pixels.  Tiles: at most band_pixels / 64, at least one, at most 2^14 (2^20 lanes).
+static uint32_t net_band_units(CtHandle h, const NetCall &c)
+{
+    const uint32_t band_pixels = c.p->band_pixels;
+    const uint32_t cap = (band_pixels == 0u || band_pixels > (1u << 20)) ? (1u << 20) : band_pixels;
+    return c.tiles ? std::max(1u, cap / 64u) : std::min(h->scene.height, std::max(1u, cap / h->scene.width));
+}
+
+// One band of subframe `sid`, units [unit0, unit0 + units) of the call, into the frame or into mean / M2.
+// Baked: the flights and one kernel that looks the table up and forms the pixels, enqueued only.  Otherwise the flights with
+// scan and compaction, the wait for the record count, gather and network in pieces of the descriptor array, and the compose
+// kernel; every stage is waited for and booked into h->net.ms.
+static int net_band(CtHandle h, const NetCall &c, uint32_t sid, uint32_t unit0, uint32_t units)
+{
+    CtHandle_::NetScratch &s = h->net;
+    const uint32_t W = h->scene.width;
+    const PixelBand band = c.tiles ? tile_band(h->dev, s.tiles + unit0, units) : rect_band(0u, unit0, W, units);
+    const FlightTemps temps{ s.found, s.waves, c.direct ? s.direct : nullptr };
+    const NetCompose compose{ c.p->transform & 0xff, c.p->rgb_scale[0], c.p->rgb_scale[1], c.p->rgb_scale[2] };
+    const size_t first_pixel = c.tiles ? 0 : (size_t)unit0 * W;   // (the tile path writes at y * W + x of the whole frame)
+    const ComposeTarget dst{ c.accumulate ? nullptr : h->d_frame + first_pixel, h->d_mean + first_pixel, h->d_m2 + first_pixel, sid };
+    const uint32_t *const frozen = h->stop_cadence ? h->d_freeze : nullptr;
+    if (c.baked) {
+        HIPCHK(h, launch_first_flights(h->dev, band, temps, sid, h->stream));
+        HIPCHK(h, launch_baked_compose(h->dev, band, temps, bake_table(c.b), compose, dst, frozen, h->stream));
+        return CT_OK;
+    }
+    uint32_t count = 0;
+    int rc = flights_counted(h, band, temps, sid, band.n, s.pos, s.dir, nullptr, &s.ms[0], &count);
+    if (rc != CT_OK) {
+        return rc;
+    }
+    net_grow_descriptors(h, count);
+    for (uint32_t at = 0; at < count;) {
+        const uint32_t piece = (uint32_t)std::min<size_t>(count - at, s.desc_cap);
+        float ms = 0;
+        HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
+        HIPCHK(h, launch_descriptors(h->dev, h->pyramid, s.pos + 3 * (size_t)at, s.dir + 3 * (size_t)at, piece, c.ds.level0, c.ds.voxel_m,
+                                     h->scene.cloud_size_m, s.desc, h->stream));
+        HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
+        // l = the direction the light travels: the uniforms hold -l (Sun.cpp:13-18)
+        HIPCHK(h, launch_network_aux(s.dir + 3 * (size_t)at, piece, -h->dev.nlx, -h->dev.nly, -h->dev.nlz, s.aux + at, h->stream));
+        HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
+        char err[256] = "";
+        rc = ct::network_eval(c.n, h->stream, s.desc, s.aux + at, piece, s.out + at, err, sizeof err);   // (waits)
+        if (rc != CT_OK) {
+            return fail(h, rc, "%s", err);
+        }
+        HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+        s.ms[1] += ms;
+        HIPCHK(h, hipEventElapsedTime(&ms, h->ev[1], h->ev[2]));
+        s.ms[3] += ms;
+        double net_ms = 0;
+        ct_debug_network_time(c.n, &net_ms);
+        s.ms[2] += net_ms;
+        at += piece;
+    }
+    double compose_ms = 0;
+    rc = timed(h, &compose_ms, [&]() -> int {
+        HIPCHK(h, launch_network_compose(band, temps, compose, s.out, dst, frozen, h->stream));
+        return CT_OK;
+    });
+    s.ms[3] += compose_ms;
+    if (c.accumulate) {
+        h->accum_ms += compose_ms;
+    }
+    return rc;
+}
+
+// Subframes [first, first + count) band by band.  The caller has validated and flushed.  A frame of the tile path is first
+// filled with the shard's background.  A baked call only enqueues -- the convergence test keeps its own wait -- and is waited
+// for once at its end: one event pair times it into h->baked_ms, and h->net.ms stays the last network call's.
+static int net_run(CtHandle h, const NetCall &c, uint32_t first, uint32_t count)
 {
     const uint32_t W = h->scene.width, H = h->scene.height, per_band = net_band_units(h, c);
-    h->baked_ms = 0;
-    auto run = [&]() -> int {
+    if (c.baked) {
+        h->baked_ms = 0;
+    } else {
+        for (double &ms : h->net.ms) {
+            ms = 0;
+        }
+    }
+    return drained(h, [&]() -> int {
         int rc = c.tiles ? net_ensure_tiles(h) : CT_OK;
         if (rc != CT_OK) {
             return rc;
         }
-        CtHandle_::NetScratch &s = h->net;
-        const uint32_t units = c.tiles ? s.n_tiles : H;
-        const size_t band_lanes = c.tiles ? (size_t)64 * std::min(per_band, std::max(units, 1u)) : (size_t)W * per_band;
-        rc = net_reserve(h, band_lanes, c.direct);
+        // (bands of the row path run bottom to top over H rows; those of the tile path over the list's n_tiles tiles)
+        const uint32_t units = c.tiles ? h->net.n_tiles : H;
+        const size_t band = c.tiles ? (size_t)64 * std::min(per_band, std::max(units, 1u)) : (size_t)W * per_band;
+        rc = net_reserve(h, band, c.direct);
+        if (rc == CT_OK && !c.baked) {
+            rc = ensure_pyramid(h);
+        }
         if (rc != CT_OK) {
             return rc;
         }
         if (c.accumulate) {
-            discard_ahead(h);
+            discard_ahead(h);   // like ct_accumulate: the running mean leaves the order the samples rendered ahead were made for
         }
-        const BakeTable table = bake_table(b);
-        const NetCompose compose{ c.p->transform & 0xff, c.p->rgb_scale[0], c.p->rgb_scale[1], c.p->rgb_scale[2] };
-        const FlightTemps temps{ s.found, s.waves, c.direct ? s.direct : nullptr };
-        HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
+        // the shard's background, as ct_render_subframe starts from it: the bands write the own pixels only
+        const auto fill = [&]() -> int {
+            HIPCHK(h, launch_fill_frame(h->d_frame, W, H, h->scene.shard_index, h->scene.shard_count, h->stream));
+            return CT_OK;
+        };
+        if (c.baked) {
+            HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
+        }
         for (uint32_t k = 0; k < count; k++) {
             const uint32_t sid = first + k;
             if (c.tiles && !c.accumulate) {
-                HIPCHK(h, launch_fill_frame(h->d_frame, W, H, h->scene.shard_index, h->scene.shard_count, h->stream));
+                rc = c.baked ? fill() : timed(h, &h->net.ms[3], fill);
+                if (rc != CT_OK) {
+                    return rc;
+                }
             }
             for (uint32_t unit0 = 0; unit0 < units; unit0 += per_band) {
-                const uint32_t n_units = std::min(per_band, units - unit0);
-                const PixelBand band = c.tiles ? tile_band(h->dev, s.tiles + unit0, n_units) : rect_band(0u, unit0, W, n_units);
-                const size_t first_pixel = c.tiles ? 0 : (size_t)unit0 * W;
-                const ComposeTarget dst{ c.accumulate ? nullptr : h->d_frame + first_pixel, h->d_mean + first_pixel, h->d_m2 + first_pixel, sid };
-                HIPCHK(h, launch_first_flights(h->dev, band, temps, sid, h->stream));
-                HIPCHK(h, launch_baked_compose(h->dev, band, temps, table, compose, dst, h->stop_cadence ? h->d_freeze : nullptr, h->stream));
+                rc = net_band(h, c, sid, unit0, std::min(per_band, units - unit0));
+                if (rc != CT_OK) {
+                    return rc;
+                }
             }
             if (c.accumulate) {
                 if (h->stop_cadence && sid % h->stop_cadence == 0u && sid >= h->stop_min) {   // as ct_accumulate
@@ -1289,29 +1203,24 @@ static int baked_run(CtHandle h, CtBake b, const NetCall &c, uint32_t first, uin
                 discard_ahead(h);
             }
         }
-        HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        float ms = 0;
-        HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[2]));
-        h->baked_ms = ms;
+        if (c.baked) {
+            HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            float ms = 0;
+            HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[2]));
+            h->baked_ms = ms;
+        }
         return CT_OK;
-    };
-    const int rc = run();
-    if (rc != CT_OK) {
-        hipStreamSynchronize(h->stream);
-    }
-    return rc;
+    });
 }
 
-static int baked_subframe(CtHandle h, CtBake b, const CtNetworkRender *p, uint32_t subframe_id, float *frame_rgba_dev, bool tiles)
+static int net_subframe(CtHandle h, NetCall c, uint32_t subframe_id, float *frame_rgba_dev)
 {
-    NetCall c;
-    int rc = baked_begin(h, b, p, tiles ? "ct_baked_render_shard_subframe" : "ct_baked_render_subframe", false, tiles,
-                         subframe_id == 0 ? "%s: subframe ids are 1-based (Camera.cpp:191)" : nullptr, c);
+    int rc = net_begin(h, c, false, subframe_id == 0 ? "%s: subframe ids are 1-based (Camera.cpp:191)" : nullptr);
     if (rc != CT_OK) {
         return rc;
     }
-    rc = baked_run(h, b, c, subframe_id, 1);
+    rc = net_run(h, c, subframe_id, 1);
     if (rc != CT_OK) {
         return rc;
     }
@@ -1323,12 +1232,10 @@ static int baked_subframe(CtHandle h, CtBake b, const CtNetworkRender *p, uint32
     return CT_OK;
 }
 
-static int baked_accumulate(CtHandle h, CtBake b, const CtNetworkRender *p, uint32_t first_subframe_id, uint32_t count, bool tiles)
+static int net_accumulate(CtHandle h, NetCall c, uint32_t first_subframe_id, uint32_t count)
 {
-    const char *const who = tiles ? "ct_baked_render_shard_accumulate" : "ct_baked_render_accumulate";
-    NetCall c;
-    const int rc = baked_begin(h, b, p, who, true, tiles,
-                               first_subframe_id == 0 || count == 0 ? "%s: subframe ids are 1-based and count must not be 0" : nullptr, c);
+    const int rc = net_begin(h, c, true,
+                             first_subframe_id == 0 || count == 0 ? "%s: subframe ids are 1-based and count must not be 0" : nullptr);
     if (rc != CT_OK) {
         return rc;
     }
@@ -1336,30 +1243,53 @@ static int baked_accumulate(CtHandle h, CtBake b, const CtNetworkRender *p, uint
         return fail(h, CT_E_STATE, "first_subframe_id %u but %u subframes are accumulated", first_subframe_id, h->subframes);
     }
     if (count > 0xffffffffu - first_subframe_id + 1u) {
-        return fail(h, CT_E_INVAL, "%s: %u subframes from %u on exceed the 32-bit subframe id", who, count, first_subframe_id);
+        return fail(h, CT_E_INVAL, "%s: %u subframes from %u on exceed the 32-bit subframe id", c.who, count, first_subframe_id);
     }
-    return baked_run(h, b, c, first_subframe_id, count);
+    return net_run(h, c, first_subframe_id, count);
+}
+
+extern "C" int ct_network_render_subframe(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t subframe_id, float *frame_rgba_dev)
+{
+    return net_subframe(h, { "ct_network_render_subframe", n, nullptr, p, false, false }, subframe_id, frame_rgba_dev);
+}
+
+extern "C" int ct_network_render_shard_subframe(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t subframe_id,
+                                                float *frame_rgba_dev)
+{
+    return net_subframe(h, { "ct_network_render_shard_subframe", n, nullptr, p, false, true }, subframe_id, frame_rgba_dev);
+}
+
+extern "C" int ct_network_render_accumulate(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t first_subframe_id, uint32_t count)
+{
+    return net_accumulate(h, { "ct_network_render_accumulate", n, nullptr, p, false, false }, first_subframe_id, count);
+}
+
+extern "C" int ct_network_render_shard_accumulate(CtHandle h, CtNetwork n, const CtNetworkRender *p, uint32_t first_subframe_id,
+                                                  uint32_t count)
+{
+    return net_accumulate(h, { "ct_network_render_shard_accumulate", n, nullptr, p, false, true }, first_subframe_id, count);
 }
 
 extern "C" int ct_baked_render_subframe(CtHandle h, CtBake b, const CtNetworkRender *p, uint32_t subframe_id, float *frame_rgba_dev)
 {
-    return baked_subframe(h, b, p, subframe_id, frame_rgba_dev, false);
+    return net_subframe(h, { "ct_baked_render_subframe", nullptr, b, p, true, false }, subframe_id, frame_rgba_dev);
 }
 
 extern "C" int ct_baked_render_shard_subframe(CtHandle h, CtBake b, const CtNetworkRender *p, uint32_t subframe_id, float *frame_rgba_dev)
 {
-    return baked_subframe(h, b, p, subframe_id, frame_rgba_dev, true);
+    return net_subframe(h, { "ct_baked_render_shard_subframe", nullptr, b, p, true, true }, subframe_id, frame_rgba_dev);
 }
 
 extern "C" int ct_baked_render_accumulate(CtHandle h, CtBake b, const CtNetworkRender *p, uint32_t first_subframe_id, uint32_t count)
 {
-    return baked_accumulate(h, b, p, first_subframe_id, count, false);
+    return net_accumulate(h, { "ct_baked_render_accumulate", nullptr, b, p, true, false }, first_subframe_id, count);
 }
 
 extern "C" int ct_baked_render_shard_accumulate(CtHandle h, CtBake b, const CtNetworkRender *p, uint32_t first_subframe_id, uint32_t count)
 {
-    return baked_accumulate(h, b, p, first_subframe_id, count, true);
+    return net_accumulate(h, { "ct_baked_render_shard_accumulate", nullptr, b, p, true, true }, first_subframe_id, count);
 }
+
 
 extern "C" int ct_debug_baked_render_time(CtHandle h, double *gpu_ms_out)
 {

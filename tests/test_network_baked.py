@@ -436,6 +436,19 @@ def test_the_image_does_not_depend_on_the_bands(scene):
 
 
 @pytest.mark.gpu
+def test_a_baked_call_leaves_the_network_renderers_times(scene):
+    """The two routes share one driver but not their clocks: the four stage times are the last network call's, and a baked call
+    sets its own time only."""
+    tr, net, bake = scene["tr"], scene["net"], scene["bake_net"]
+    tr.network_render_subframe(net, SID, rgb_scale=SCALE)
+    want = tr.network_render_time()
+    assert len(want) == 4 and all(ms > 0 for ms in want)
+    tr.baked_render_subframe(bake, SID, rgb_scale=SCALE)
+    assert tr.network_render_time() == want
+    assert tr.baked_render_time() > 0
+
+
+@pytest.mark.gpu
 def test_render_subframe_touches_nothing_but_the_frame():
     tex = cloud()
     states = []

@@ -416,12 +416,15 @@ class CloudTracer:
         check(self.L.ct_network_render_shard_accumulate(self.h, net.n, C.byref(p), first_subframe_id & 0xFFFFFFFF, count), self.h)
 
     # -- the network baked into a probe table (ct_network_bake, ct_baked_render_*) ------------------------------------
-    def network_bake(self, net, grid, azimuths: int, cosines: int, sparse: bool = False):
+    def network_bake(self, net, grid, azimuths: int, cosines: int, sparse: bool = False, compact: bool = False):
         """ct_network_bake -> deepestscatter_amd.network.Bake: `net` evaluated on grid[0] x grid[1] x grid[2] position nodes x
         `azimuths` (a multiple of 4) x `cosines` polar nodes, for the light as it is now.  sparse: ct_network_bake_sparse, which
-        bakes only the probes a first flight can reach; every frame is the same."""
+        bakes only the probes a first flight can reach; every frame is the same.  compact: ct_network_bake_compact, which also
+        stores only those probes (the 2^26 limit then bounds what is stored); `sparse` and `compact` together: ValueError."""
         from .network import Bake
-        return Bake(self, net, grid, azimuths, cosines, sparse)
+        if sparse and compact:
+            raise ValueError("network_bake: sparse or compact, not both")
+        return Bake(self, net, grid, azimuths, cosines, sparse, compact)
 
     def bake_mask(self, grid):
         """ct_debug_bake_mask: the sparse bake's mask of a grid (Nx, Ny, Nz) on this handle, no network needed

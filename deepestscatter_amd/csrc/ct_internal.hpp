@@ -259,6 +259,7 @@ struct BakeTable {
     uint32_t nx, ny, nz, nphi, nc;
     float lx, ly, lz;                // the light travel direction the table was baked for
     float ax, ay, az, bx, by, bz;    // the azimuth frame
+    const uint32_t *slots;           // ct_network_bake_compact: the block of node (z Ny + y) Nx + x in the table; nullptr: dense addressing
 };
 // The bake's own kernels: aux[i] = value; table[i * stride + k] = out[i]; and (ct_debug_bake_lookup) the lookup of caller-supplied
 // records.  launch_baked_compose forms a band's pixels as launch_network_compose does (the kernels share everything behind a
@@ -271,13 +272,14 @@ hipError_t launch_bake_lookup(const DevScene &sc, const BakeTable &t, const floa
 // allocated: ranges = the texel range lo | hi << 16 of every cell of x, then y, then z; tmp_x = slab * dims[1] * (grid[0] - 1)
 // bytes and tmp_xy = slab * (grid[1] - 1) * (grid[0] - 1), the z planes the reduction takes at a time; cells, x fastest; nodes;
 // waves = (nodes rounded up to 256) / 64 + 1 counts, the last of which becomes the number of active nodes; list = room for every
-// node, filled with the active ones in ascending order.
+// node, filled with the active ones in ascending order; slots (ct_network_bake_compact) = nullptr, or one word per node: 1 + the
+// node's place in the list, 0 for an inactive node.
 struct BakeMaskArgs {
     const uint8_t *density;
     uint32_t dims[3], grid[3], slab;
     const uint32_t *ranges;
     uint8_t *tmp_x, *tmp_xy, *cells, *nodes;
-    uint32_t *waves, *list;
+    uint32_t *waves, *list, *slots;
 };
 hipError_t launch_bake_mask(const BakeMaskArgs &a, hipStream_t stream);
 // The bake's chunk from the list: records [first, first + count) of the compacted probes (node list[p / nphi], azimuth p % nphi)

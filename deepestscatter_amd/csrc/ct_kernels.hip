@@ -3607,6 +3607,20 @@ __global__ __launch_bounds__(256) void bake_mask_list_kernel(const uint8_t *__re
     }
 }
 
+// ct_network_bake_compact: slots[i] = 1 + the place of node i in the list, 0 for an inactive node -- the list kernel's ballot,
+// rank and scanned wave offsets, so the same index for the same mask (no atomics).
+__global__ __launch_bounds__(256) void bake_slots_kernel(const uint8_t *__restrict__ nodes, uint32_t count,
+                                                         const uint32_t *__restrict__ wave_offsets, uint32_t *__restrict__ slots)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const bool active = i < count && nodes[i] != 0u;
+    const uint64_t mask = __builtin_amdgcn_ballot_w64(active);
+    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+    if (i < count) {
+        slots[i] = active ? 1u + wave_offsets[i >> 6] + rank : 0u;
+    }
+}
+
 hipError_t launch_bake_mask(const BakeMaskArgs &a, hipStream_t stream)
 {
     const uint32_t cx = a.grid[0] - 1u, cy = a.grid[1] - 1u, cz = a.grid[2] - 1u;
@@ -3635,6 +3649,10 @@ hipError_t launch_bake_mask(const BakeMaskArgs &a, hipStream_t stream)
     hipLaunchKernelGGL(first_scatter_scan_kernel, dim3(1), dim3(1024), 0, stream, a.waves, blocks * 4u);
     hipLaunchKernelGGL(bake_mask_list_kernel, dim3(blocks), dim3(256), 0, stream, (const uint8_t *)a.nodes, nodes, (const uint32_t *)a.waves,
                        a.list);
+    if (a.slots) {
+        hipLaunchKernelGGL(bake_slots_kernel, dim3(blocks), dim3(256), 0, stream, (const uint8_t *)a.nodes, nodes, (const uint32_t *)a.waves,
+                           a.slots);
+    }
     return hipGetLastError();
 }
 
@@ -3712,6 +3730,11 @@ CT_DEV float bake_azimuth(const BakeTable &t, f3 d)
 // The table at (world position w, view d2): 32 taps, the pair of polar nodes of a (corner, azimuth) being 8 adjacent bytes --
 // 16 loads of 8 bytes (4-byte aligned: the compiler is told so) from a table that lives in L2 and the Infinity Cache.  The lerps
 // run over the polar node, then the azimuth, then x, y, z.
+// COMPACT (ct_network_bake_compact): the table holds the blocks of the active nodes behind a zero block, and the block of a corner
+// is slots[node].  The two x-neighbours of a corner pair are adjacent words, so the eight slots are four loads of 8 bytes
+// (4-byte aligned), all issued before the first table load: the index costs one memory round trip per lookup, not eight.  An
+// inactive corner reads the zero block, so there is no branch on activity.
+template <bool COMPACT>
 CT_DEV float bake_lookup(const DevScene &sc, const BakeTable &t, f3 w, f3 d)
 {
     uint32_t x0, y0, z0, k0;
@@ -3725,11 +3748,23 @@ CT_DEV float bake_lookup(const DevScene &sc, const BakeTable &t, f3 w, f3 d)
     const float fl = floorf(ft);
     const float wphi = ft - fl;
     const uint32_t j0 = (uint32_t)(int32_t)fl % t.nphi, j1 = (j0 + 1u) % t.nphi;
+    uint32_t slot[8] = {};
+    if constexpr (COMPACT) {
+#pragma unroll
+        for (uint32_t r = 0; r < 4u; r++) {
+            const uint32_t y = y0 + (r & 1u), z = z0 + (r >> 1);
+            uint2 pair;   // nodes (x0, y, z) and (x0 + 1, y, z): x0 <= Nx - 2
+            __builtin_memcpy(&pair, t.slots + ((size_t)(z * t.ny + y) * t.nx + x0), sizeof pair);
+            slot[2u * r] = pair.x;
+            slot[2u * r + 1u] = pair.y;
+        }
+    }
     float corner[8];
 #pragma unroll
     for (uint32_t q = 0; q < 8u; q++) {
         const uint32_t x = x0 + (q & 1u), y = y0 + ((q >> 1) & 1u), z = z0 + (q >> 2);
-        const uint32_t probe = ((z * t.ny + y) * t.nx + x) * t.nphi;   // (entries <= 2^26)
+        // (dense: entries <= 2^26; compact: stored entries <= 2^26)
+        const uint32_t probe = (COMPACT ? slot[q] : (z * t.ny + y) * t.nx + x) * t.nphi;
         float2 a, b;
         __builtin_memcpy(&a, t.table + (size_t)(probe + j0) * t.nc + k0, sizeof a);
         __builtin_memcpy(&b, t.table + (size_t)(probe + j1) * t.nc + k0, sizeof b);
@@ -3740,6 +3775,7 @@ CT_DEV float bake_lookup(const DevScene &sc, const BakeTable &t, f3 w, f3 d)
     return lerp_(lerp_(c00, c10, wy), lerp_(c01, c11, wy), wz);
 }
 
+template <bool COMPACT>
 __global__ __launch_bounds__(256) void bake_lookup_kernel(DevScene sc, BakeTable t, const float *__restrict__ positions,
                                                           const float *__restrict__ directions, uint32_t count, float *__restrict__ out)
 {
@@ -3748,21 +3784,23 @@ __global__ __launch_bounds__(256) void bake_lookup_kernel(DevScene sc, BakeTable
         return;
     }
     const size_t at = 3 * (size_t)i;
-    out[i] = bake_lookup(sc, t, mk3(positions[at], positions[at + 1], positions[at + 2]),
-                         mk3(directions[at], directions[at + 1], directions[at + 2]));
+    out[i] = bake_lookup<COMPACT>(sc, t, mk3(positions[at], positions[at + 1], positions[at + 2]),
+                                  mk3(directions[at], directions[at + 1], directions[at + 2]));
 }
 
 hipError_t launch_bake_lookup(const DevScene &sc, const BakeTable &t, const float *positions, const float *directions, uint32_t count,
                               float *out, hipStream_t stream)
 {
-    hipLaunchKernelGGL(bake_lookup_kernel, dim3((count + 255u) / 256u), dim3(256), 0, stream, sc, t, positions, directions, count, out);
+    hipLaunchKernelGGL(t.slots ? bake_lookup_kernel<true> : bake_lookup_kernel<false>, dim3((count + 255u) / 256u), dim3(256), 0, stream, sc,
+                       t, positions, directions, count, out);
     return hipGetLastError();
 }
 
 // The band's pixels with a record's output looked up in the table at the record's world position (the flight's temporary) and
 // d2, made again from the pixel as first_scatter_compact_kernel makes it: no ballot, no rank, no wave offsets.  ACCUMULATE,
 // DIRECT and TILES mean what they mean for network_compose_kernel, and everything behind the output is the shared compose_* code.
-template <bool ACCUMULATE, bool DIRECT, bool TILES>
+// COMPACT: the table of a compact bake (bake_lookup).
+template <bool ACCUMULATE, bool DIRECT, bool TILES, bool COMPACT>
 __global__ __launch_bounds__(256) void baked_compose_kernel(DevScene sc, PixelBand b, const float4 *__restrict__ found, BakeTable t,
                                                             NetCompose c, float4 *__restrict__ frame, float4 *__restrict__ mean,
                                                             float4 *__restrict__ m2, uint32_t subframe_id,
@@ -3784,7 +3822,7 @@ __global__ __launch_bounds__(256) void baked_compose_kernel(DevScene sc, PixelBa
     float4 v = compose_miss();
     if (f.w != 0.f) {
         const f3 dir = normalize3(primary_direction(sc, x, y));
-        v = compose_value<DIRECT>(c, bake_lookup(sc, t, mk3(f.x, f.y, f.z), dir), direct, i);
+        v = compose_value<DIRECT>(c, bake_lookup<COMPACT>(sc, t, mk3(f.x, f.y, f.z), dir), direct, i);
     }
     compose_store<ACCUMULATE>(v, at, frame, mean, m2, subframe_id);
 }
@@ -3792,12 +3830,15 @@ __global__ __launch_bounds__(256) void baked_compose_kernel(DevScene sc, PixelBa
 hipError_t launch_baked_compose(const DevScene &sc, const PixelBand &band, const FlightTemps &t, const BakeTable &table, const NetCompose &c,
                                 const ComposeTarget &dst, const uint32_t *frozen, hipStream_t stream)
 {
-#define K(ACCUMULATE, TILES) baked_compose_kernel<ACCUMULATE, false, TILES>, baked_compose_kernel<ACCUMULATE, true, TILES>
-    static constexpr decltype(&baked_compose_kernel<false, false, false>) composes[8] = { K(false, false), K(false, true),
-                                                                                         K(true, false), K(true, true) };
+#define K(ACCUMULATE, TILES, COMPACT) \
+    baked_compose_kernel<ACCUMULATE, false, TILES, COMPACT>, baked_compose_kernel<ACCUMULATE, true, TILES, COMPACT>
+#define K4(COMPACT) K(false, false, COMPACT), K(false, true, COMPACT), K(true, false, COMPACT), K(true, true, COMPACT)
+    static constexpr decltype(&baked_compose_kernel<false, false, false, false>) composes[16] = { K4(false), K4(true) };
+#undef K4
 #undef K
     const bool accumulate = dst.frame == nullptr, tiles = band.tiles != nullptr, direct = t.direct != nullptr;
-    hipLaunchKernelGGL(composes[4 * accumulate + 2 * tiles + direct], dim3((band.n + 255u) / 256u), dim3(256), 0, stream, sc, band,
+    const bool compact = table.slots != nullptr;
+    hipLaunchKernelGGL(composes[8 * compact + 4 * accumulate + 2 * tiles + direct], dim3((band.n + 255u) / 256u), dim3(256), 0, stream, sc, band,
                        (const float4 *)t.found, table, c, dst.frame, dst.mean, dst.m2, dst.subframe_id, frozen, (const float4 *)t.direct);
     return hipGetLastError();
 }

@@ -397,6 +397,11 @@ struct CtBake_ {
     uint32_t *d_list = nullptr;              // the active nodes, ascending
     float *d_probe = nullptr;                // the position nodes of x, y, z and the Nphi probe directions (bake_probe's floats)
     double mask_ms = 0;
+    // ct_network_bake_compact: a sparse bake whose table holds a zero block and then the blocks of the active nodes
+    // in the list's order; d_slots finds a node's block.  `stored` is the floats d_table holds (every other bake: entries).
+    bool compact = false;
+    uint64_t stored = 0;
+    uint32_t *d_slots = nullptr;             // one word per node: 1 + its place in the list, 0 for an inactive node
 };
 
 static uint64_t bake_probes_total(const CtBake_ *b)
@@ -460,7 +465,7 @@ static void bake_frame(CtHandle h, CtBake_ *b)
 static BakeTable bake_table(const CtBake_ *b)
 {
     return { b->d_table, b->grid[0], b->grid[1], b->grid[2], b->azimuths, b->cosines, b->l[0], b->l[1], b->l[2],
-             b->a[0], b->a[1], b->a[2], b->b[0], b->b[1], b->b[2] };
+             b->a[0], b->a[1], b->a[2], b->b[0], b->b[1], b->b[2], b->d_slots };
 }
 
 // The mask of a probe grid on h (include/cloudtrace.h, "the sparse bake"): its device memory, allocated by bake_mask_reserve
@@ -468,7 +473,7 @@ static BakeTable bake_table(const CtBake_ *b)
 struct BakeMask {
     std::vector<uint32_t> host_ranges;   // lo | hi << 16 per cell of x, then y, then z
     uint32_t margin = 0, slab = 0;
-    DevTemp<uint32_t> ranges, waves, list;
+    DevTemp<uint32_t> ranges, waves, list, slots;   // slots: only with bake_mask_reserve's `slots`
     DevTemp<uint8_t> tmp_x, tmp_xy, cells, nodes;
 };
 
@@ -477,7 +482,7 @@ static size_t bake_mask_waves(uint64_t nodes)
     return (size_t)((nodes + 255u) / 256u * 4u + 1u);
 }
 
-static int bake_mask_reserve(CtHandle h, const uint32_t grid[3], BakeMask &m)
+static int bake_mask_reserve(CtHandle h, const uint32_t grid[3], BakeMask &m, bool slots = false)
 {
     const uint32_t *dims = h->scene.dims;
     const uint32_t maxdim = std::max(dims[0], std::max(dims[1], dims[2]));
@@ -503,6 +508,9 @@ static int bake_mask_reserve(CtHandle h, const uint32_t grid[3], BakeMask &m)
     HIPCHK(h, dmalloc(&m.nodes, nodes));
     HIPCHK(h, dmalloc(&m.waves, bake_mask_waves(nodes)));
     HIPCHK(h, dmalloc(&m.list, nodes));
+    if (slots) {
+        HIPCHK(h, dmalloc(&m.slots, nodes));
+    }
     return CT_OK;
 }
 
@@ -526,6 +534,7 @@ static int bake_mask_run(CtHandle h, const uint32_t grid[3], BakeMask &m, uint32
         a.nodes = m.nodes;
         a.waves = m.waves;
         a.list = m.list;
+        a.slots = m.slots;
         uint32_t count = 0;
         double ms = 0;
         const int rc = timed(h, &ms, [&]() -> int {
@@ -593,9 +602,12 @@ static int bake_chunk_records(CtHandle h, const CtBake_ *b, uint64_t first, uint
 }
 
 // The network's outputs for polar node k of probes [first, first + piece) into the table: in place, or through the list.
+// Compact: the table is contiguous in compacted-probe order behind its zero block, so in place again.
 static int bake_store_piece(CtHandle h, const CtBake_ *b, float *table, uint64_t first, uint32_t piece, uint32_t k)
 {
-    if (b->sparse) {
+    if (b->compact) {
+        HIPCHK(h, launch_bake_store(h->net.out, piece, table + (b->azimuths + first) * b->cosines, b->cosines, k, h->stream));
+    } else if (b->sparse) {
         HIPCHK(h, launch_bake_store_list(h->net.out, b->d_list, first, piece, b->azimuths, table, b->cosines, k, h->stream));
     } else {
         HIPCHK(h, launch_bake_store(h->net.out, piece, table + first * b->cosines, b->cosines, k, h->stream));
@@ -603,9 +615,9 @@ static int bake_store_piece(CtHandle h, const CtBake_ *b, float *table, uint64_t
     return CT_OK;
 }
 
-// Fills `table` (b->entries floats, allocated) for the handle's light and network n: the probes in chunks through the handle's
+// Fills `table` (b->stored floats, allocated) for the handle's light and network n: the probes in chunks through the handle's
 // scratch, one gather per piece and one evaluation per polar node.  b's frame is the new light's already.
-// A sparse bake zeroes the table first and runs only the probes of its list.
+// A sparse bake zeroes the table first and runs only the probes of its list; a compact one zeroes only the zero block.
 static int bake_run(CtHandle h, CtNetwork n, CtBake_ *b, float *table)
 {
     CtHandle_::NetScratch &s = h->net;
@@ -616,7 +628,8 @@ static int bake_run(CtHandle h, CtNetwork n, CtBake_ *b, float *table)
     double gather_ms = 0, network_ms = 0, records_ms = 0;
     const int rc = drained(h, [&]() -> int {
         if (b->sparse) {
-            HIPCHK(h, hipMemsetAsync(table, 0, (size_t)b->entries * sizeof(float), h->stream));
+            const uint64_t zeroed = b->compact ? (uint64_t)b->azimuths * b->cosines : b->entries;
+            HIPCHK(h, hipMemsetAsync(table, 0, (size_t)zeroed * sizeof(float), h->stream));
             if (probes == 0u) {
                 HIPCHK(h, hipStreamSynchronize(h->stream));
                 return CT_OK;
@@ -683,7 +696,7 @@ static int bake_run(CtHandle h, CtNetwork n, CtBake_ *b, float *table)
 
 static void bake_free(CtBake_ *b)
 {
-    for (void *p : { (void *)b->d_table, (void *)b->d_nodes, (void *)b->d_list, (void *)b->d_probe }) {
+    for (void *p : { (void *)b->d_table, (void *)b->d_nodes, (void *)b->d_list, (void *)b->d_probe, (void *)b->d_slots }) {
         if (p) {
             hipFree(p);
         }
@@ -691,10 +704,13 @@ static void bake_free(CtBake_ *b)
     delete b;
 }
 
-// ct_network_bake and ct_network_bake_sparse: one validation, one order of errors.
-static int bake_create(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtBake *out, bool sparse)
+// ct_network_bake, ct_network_bake_sparse and ct_network_bake_compact: one validation, one order of errors.
+enum class BakeKind { Dense, Sparse, Compact };
+
+static int bake_create(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtBake *out, BakeKind kind)
 {
-    const char *const who = sparse ? "ct_network_bake_sparse" : "ct_network_bake";
+    const bool sparse = kind != BakeKind::Dense, compact = kind == BakeKind::Compact;
+    const char *const who = compact ? "ct_network_bake_compact" : sparse ? "ct_network_bake_sparse" : "ct_network_bake";
     if (!h) {
         return fail(nullptr, CT_E_INVAL, "null handle");
     }
@@ -718,8 +734,8 @@ static int bake_create(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtBake *out
     if (d->cosines < 2u || d->cosines > 64u) {
         return fail(h, CT_E_INVAL, "%s: %u cosines; 2 .. 64", who, d->cosines);
     }
-    entries *= (uint64_t)d->azimuths * d->cosines;
-    if (entries > (1ull << 26)) {
+    entries *= (uint64_t)d->azimuths * d->cosines;   // (<= 2^36)
+    if (!compact && entries > (1ull << 26)) {        // (a compact bake bounds what it stores, once the mask has been counted)
         return fail(h, CT_E_INVAL, "%s: %llu entries, a table holds at most 2^26", who, (unsigned long long)entries);
     }
     NEED_NOFLUSH(h);
@@ -740,18 +756,19 @@ static int bake_create(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtBake *out
     b->azimuths = d->azimuths;
     b->cosines = d->cosines;
     b->entries = entries;
+    b->stored = entries;
     for (uint32_t k = 0; k < b->cosines; k++) {
         b->cosine[k] = (float)(-1.0 + 2.0 * (double)k / (double)(b->cosines - 1u));
     }
-    if (dmalloc(&b->d_table, (size_t)entries) != hipSuccess) {   // (before the first kernel)
+    if (!compact && dmalloc(&b->d_table, (size_t)entries) != hipSuccess) {   // (before the first kernel)
         (void)hipGetLastError();
         delete b;
         return fail(h, CT_E_NOMEM, "%s: no device memory for a table of %llu entries", who, (unsigned long long)entries);
     }
     double mask_ms = 0;
-    if (sparse) {   // the mask's temporaries, the node bytes, the list and the record tables: all before the first kernel, too
+    if (sparse) {   // the mask's temporaries, the node bytes, the list, the slots and the record tables: all before the first kernel, too
         BakeMask m;
-        rc = bake_mask_reserve(h, b->grid, m);
+        rc = bake_mask_reserve(h, b->grid, m, compact);
         if (rc == CT_OK && dmalloc(&b->d_probe, b->grid[0] + b->grid[1] + b->grid[2] + 3 * (size_t)b->azimuths) != hipSuccess) {
             (void)hipGetLastError();
             rc = fail(h, CT_E_NOMEM, "%s: no device memory for the probe tables", who);
@@ -760,15 +777,29 @@ static int bake_create(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtBake *out
         if (rc == CT_OK) {
             rc = bake_mask_run(h, b->grid, m, &active, &mask_ms);
         }
+        if (rc == CT_OK && compact) {
+            // The one allocation behind a kernel: the stored table has the size the mask has counted.  Still before any gather or
+            // network kernel, and nothing of the handle has changed.
+            b->stored = ((uint64_t)active + 1u) * b->azimuths * b->cosines;
+            if (b->stored > (1ull << 26)) {
+                rc = fail(h, CT_E_INVAL, "%s: %u active nodes of %llu store %llu entries, a table holds at most 2^26 (%llu)", who, active,
+                          (unsigned long long)(entries / b->azimuths / b->cosines), (unsigned long long)b->stored, 1ull << 26);
+            } else if (dmalloc(&b->d_table, (size_t)b->stored) != hipSuccess) {
+                (void)hipGetLastError();
+                rc = fail(h, CT_E_NOMEM, "%s: no device memory for a table of %llu stored entries", who, (unsigned long long)b->stored);
+            }
+        }
         if (rc != CT_OK) {
             bake_free(b);
             return rc;
         }
         b->sparse = true;
+        b->compact = compact;
         b->margin = m.margin;
         b->active = active;
         b->d_nodes = m.nodes.release();
         b->d_list = m.list.release();
+        b->d_slots = m.slots.release();   // (nullptr unless compact)
     }
     bake_frame(h, b);
     rc = bake_run(h, n, b, b->d_table);
@@ -783,12 +814,67 @@ static int bake_create(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtBake *out
 
 extern "C" int ct_network_bake(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtBake *out)
 {
-    return bake_create(h, n, d, out, false);
+    return bake_create(h, n, d, out, BakeKind::Dense);
 }
 
 extern "C" int ct_network_bake_sparse(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtBake *out)
 {
-    return bake_create(h, n, d, out, true);
+    return bake_create(h, n, d, out, BakeKind::Sparse);
+}
+
+extern "C" int ct_network_bake_compact(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtBake *out)
+{
+    return bake_create(h, n, d, out, BakeKind::Compact);
+}
+
+extern "C" int ct_bake_storage_info(CtBake b, CtBakeStorageInfo *out)
+{
+    if (!b || !out) {
+        return fail(b ? b->h : nullptr, CT_E_INVAL, "ct_bake_storage_info: need a bake and out");
+    }
+    *out = CtBakeStorageInfo{};
+    const uint64_t nodes = (uint64_t)b->grid[0] * b->grid[1] * b->grid[2];
+    out->compact = b->compact ? 1u : 0u;
+    out->slots = b->compact ? b->active + 1u : nodes;
+    out->stored_entries = b->stored;
+    out->table_bytes = 4u * b->stored;
+    out->index_bytes = b->compact ? 4u * nodes : 0u;
+    return CT_OK;
+}
+
+extern "C" int ct_bake_slots(CtBake b, uint32_t *slots_host_out, size_t count)
+{
+    if (!b) {
+        return fail(nullptr, CT_E_INVAL, "ct_bake_slots: null bake");
+    }
+    CtHandle h = b->h;
+    if (!b->compact) {
+        return fail(h, CT_E_INVAL, "ct_bake_slots: only a bake of ct_network_bake_compact has slots");
+    }
+    const size_t nodes = (size_t)b->grid[0] * b->grid[1] * b->grid[2];
+    if (!slots_host_out || count != nodes) {
+        return fail(h, CT_E_INVAL, "ct_bake_slots: need an array of exactly %llu words", (unsigned long long)nodes);
+    }
+    NEED(h);
+    HIPCHK(h, hipMemcpy(slots_host_out, b->d_slots, nodes * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return CT_OK;
+}
+
+extern "C" int ct_bake_download_stored(CtBake b, float *table_host_out, size_t count)
+{
+    if (!b) {
+        return fail(nullptr, CT_E_INVAL, "ct_bake_download_stored: null bake");
+    }
+    CtHandle h = b->h;
+    if (!b->compact) {
+        return fail(h, CT_E_INVAL, "ct_bake_download_stored: only a bake of ct_network_bake_compact has a stored table; ct_bake_download");
+    }
+    if (!table_host_out || count != b->stored) {
+        return fail(h, CT_E_INVAL, "ct_bake_download_stored: need an array of exactly %llu floats", (unsigned long long)b->stored);
+    }
+    NEED(h);
+    HIPCHK(h, hipMemcpy(table_host_out, b->d_table, count * sizeof(float), hipMemcpyDeviceToHost));
+    return CT_OK;
 }
 
 extern "C" int ct_bake_sparse_info(CtBake b, CtBakeSparseInfo *out)
@@ -892,9 +978,9 @@ extern "C" int ct_bake_update(CtHandle h, CtNetwork n, CtBake b)
     }
     // into a second table: a failure leaves the old table, its light and its frame as they were
     DevTemp<float> fresh;
-    if (dmalloc(&fresh, (size_t)b->entries) != hipSuccess) {
+    if (dmalloc(&fresh, (size_t)b->stored) != hipSuccess) {   // (a compact bake: its stored table; list and slots are reused)
         (void)hipGetLastError();
-        return fail(h, CT_E_NOMEM, "%s: no device memory for a table of %llu entries", who, (unsigned long long)b->entries);
+        return fail(h, CT_E_NOMEM, "%s: no device memory for a table of %llu entries", who, (unsigned long long)b->stored);
     }
     const CtBake_ before = *b;
     bake_frame(h, b);
@@ -971,6 +1057,21 @@ extern "C" int ct_bake_download(CtBake b, float *table_host_out, size_t count)
         return fail(h, CT_E_INVAL, "ct_bake_download: need an array of exactly %llu floats", (unsigned long long)b->entries);
     }
     NEED(h);
+    if (b->compact) {   // expanded on the host: zeros off the mask, the stored blocks on it -- the sparse bake's table
+        const size_t block = (size_t)b->azimuths * b->cosines, nodes = (size_t)b->grid[0] * b->grid[1] * b->grid[2];
+        std::vector<float> stored((size_t)b->stored);
+        std::vector<uint32_t> slots(nodes);
+        HIPCHK(h, hipMemcpy(stored.data(), b->d_table, stored.size() * sizeof(float), hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(slots.data(), b->d_slots, nodes * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (size_t node = 0; node < nodes; node++) {
+            if (slots[node] > b->active) {
+                return fail(h, CT_E_HIP, "internal: node %llu has slot %u of %llu", (unsigned long long)node, slots[node],
+                            (unsigned long long)b->active + 1u);
+            }
+            std::copy_n(stored.data() + slots[node] * block, block, table_host_out + node * block);
+        }
+        return CT_OK;
+    }
     HIPCHK(h, hipMemcpy(table_host_out, b->d_table, count * sizeof(float), hipMemcpyDeviceToHost));
     return CT_OK;
 }

@@ -142,13 +142,14 @@ namespace DeepestScatter
     // --net-baked NX,NY,NZ,NPHI,NC) and every subframe interpolated from that table (ct_baked_render_*): no gather and no
     // network per subframe.  The table is baked in init, which follows Sun::init and so every ct_set_light, and baked again
     // should the light have changed since.  One GPU only: main refuses --net-baked with --gpus.  sparse (--net-bake-sparse): the
-    // table is baked by ct_network_bake_sparse, only where a first flight can look it up; the images are the same.
+    // table is baked by ct_network_bake_sparse, only where a first flight can look it up; the images are the same.  compact
+    // (--net-bake-compact): ct_network_bake_compact, which also stores only those probes; the images are the same again.
     class BakedRenderer : public NetworkRenderer
     {
     public:
         BakedRenderer(std::shared_ptr<Context> context, std::shared_ptr<const NetworkFile> file, const CtNetworkRender& params, const CtBakeDesc& desc,
-                      bool sparse = false)
-            : NetworkRenderer(std::move(context), std::move(file), params), desc(desc), sparse(sparse) {}
+                      bool sparse = false, bool compact = false)
+            : NetworkRenderer(std::move(context), std::move(file), params), desc(desc), sparse(sparse), compact(compact) {}
         ~BakedRenderer() override
         {
             if (bake) ct_bake_destroy(bake);   // (before the network and the handle)
@@ -158,6 +159,7 @@ namespace DeepestScatter
         {
             NetworkRenderer::init();
             if (context->group) throw std::runtime_error("--net-baked renders on one GPU only");
+            if (!bake && compact) Context::check(ct_network_bake_compact(context->handle, network, &desc, &bake), context->handle, "ct_network_bake_compact");
             if (!bake && sparse) Context::check(ct_network_bake_sparse(context->handle, network, &desc, &bake), context->handle, "ct_network_bake_sparse");
             if (!bake) Context::check(ct_network_bake(context->handle, network, &desc, &bake), context->handle, "ct_network_bake");
         }
@@ -187,7 +189,7 @@ namespace DeepestScatter
         }
 
         CtBakeDesc desc;
-        bool sparse;
+        bool sparse, compact;
         CtBake bake = nullptr;
     };
 

@@ -16,6 +16,7 @@
 //              [--net-baked NX,NY,NZ,NPHI,NC]   with --network: bake the network once per light on that probe grid (ct_network_bake)
 //                               and interpolate every subframe from the table (ct_baked_render_accumulate); one GPU, not with --gpus
 //              [--net-bake-sparse]              with --net-baked: bake only the probes a first flight can reach (ct_network_bake_sparse); the same images
+//              [--net-bake-compact]             with --net-baked: bake and store only those probes (ct_network_bake_compact); the same images; not with --net-bake-sparse
 //   <cloud> = file.vdb | procedural:<N>[:<seed>] | file.f32grid
 //
 //   cloudtrace collect <cloud>|@list.txt [--scene-id I] [--scenes N] [--jobs K] [--gpus ..] [--batch 2048] [--light L] [--size-m M] [--out DIR] [--data DIR] [--estimator ..] [--tex-fixed8]
@@ -76,6 +77,7 @@ namespace
         bool netBaked = false;                                                    // --net-baked NX,NY,NZ,NPHI,NC: render from a baked probe table (BakedRenderer)
         CtBakeDesc bake{ CT_ABI_VERSION, { 0, 0, 0 }, 0, 0 };
         bool netBakeSparse = false;                                               // --net-bake-sparse: ct_network_bake_sparse in place of ct_network_bake
+        bool netBakeCompact = false;                                              // --net-bake-compact: ct_network_bake_compact in place of ct_network_bake
         bool netDirect = false;                                                   // --net-direct: CT_NET_ADD_SINGLE_SCATTER joins networkRender.transform
         bool collect = false;                                                     // `cloudtrace collect ...`
         int32_t sceneId = 0;
@@ -275,7 +277,7 @@ namespace
             auto outputPath = std::filesystem::path(opt.outDir) / (stem + "." + toString(lightDirection) + "." + PathTracingRenderer::NAME + "." + opt.format);
             // installFramework + installApp: Sun, VDBCloud, CloudMaterial, Camera in this order (installers.cpp:28-38)
             std::shared_ptr<PathTracingRenderer> renderer = !opt.network ? std::make_shared<PathTracingRenderer>(context)
-                : opt.netBaked ? std::make_shared<BakedRenderer>(context, opt.network, opt.networkRender, opt.bake, opt.netBakeSparse)
+                : opt.netBaked ? std::make_shared<BakedRenderer>(context, opt.network, opt.networkRender, opt.bake, opt.netBakeSparse, opt.netBakeCompact)
                                : std::make_shared<NetworkRenderer>(context, opt.network, opt.networkRender);
             renderer->estimator = opt.estimator;
             auto sun = std::make_shared<Sun>(std::make_shared<DirectionalLight>(scene.light), context);
@@ -298,7 +300,7 @@ int main(int argc, char* argv[])
     try
     {
         Options opt;
-        if (argc < 2) { std::cerr << "usage: cloudtrace <cloud> [--size WxH] [--spp N] [--mode total|multi|single] [--light L] [--size-m M] [--out DIR] [--data DIR] [--unfused] [--display] [--estimator march|delta] [--format exr|pfm] [--gpus N|a,b,c] [--tex-fixed8] [--network FILE [--net-transform linear|expm1] [--net-scale r,g,b] [--net-direct] [--net-baked NX,NY,NZ,NPHI,NC [--net-bake-sparse]]] (--network with --gpus: every GPU renders its own tiles; --net-baked: one GPU)\n"; return 2; }
+        if (argc < 2) { std::cerr << "usage: cloudtrace <cloud> [--size WxH] [--spp N] [--mode total|multi|single] [--light L] [--size-m M] [--out DIR] [--data DIR] [--unfused] [--display] [--estimator march|delta] [--format exr|pfm] [--gpus N|a,b,c] [--tex-fixed8] [--network FILE [--net-transform linear|expm1] [--net-scale r,g,b] [--net-direct] [--net-baked NX,NY,NZ,NPHI,NC [--net-bake-sparse | --net-bake-compact]]] (--network with --gpus: every GPU renders its own tiles; --net-baked: one GPU)\n"; return 2; }
         int first = 2;
         bool lightsGiven = false;
         opt.cloud = argv[1];
@@ -359,6 +361,10 @@ int main(int argc, char* argv[])
             {
                 opt.netBakeSparse = true;
             }
+            else if (a == "--net-bake-compact")
+            {
+                opt.netBakeCompact = true;
+            }
             else if (a == "--tex-fixed8") opt.texFixed8 = true;
             else if (a == "--estimator")
             {
@@ -390,6 +396,8 @@ int main(int argc, char* argv[])
         if (opt.collect) return collectScenes(opt);
 
         if (opt.netDirect) opt.networkRender.transform |= CT_NET_ADD_SINGLE_SCATTER;   // (after the loop: --net-transform may follow it)
+        if (opt.netBakeCompact && !opt.netBaked) throw std::invalid_argument("--net-bake-compact chooses how --net-baked NX,NY,NZ,NPHI,NC bakes and stores its table");
+        if (opt.netBakeCompact && opt.netBakeSparse) throw std::invalid_argument("--net-bake-compact and --net-bake-sparse are two ways to bake one table: give one of them");
         if (opt.netBakeSparse && !opt.netBaked) throw std::invalid_argument("--net-bake-sparse chooses how --net-baked NX,NY,NZ,NPHI,NC bakes its table");
         if (opt.netBaked && opt.networkPath.empty()) throw std::invalid_argument("--net-baked bakes the network of --network FILE");
         if (opt.netBaked && !opt.devices.empty()) throw std::invalid_argument("--net-baked renders on one GPU: it cannot be combined with --gpus");

@@ -11,6 +11,7 @@ residual MLP of the paper the reference implements (Kallweit et al. 2017), param
     Bake                a CtBake: the network evaluated on a probe grid (ct_network_bake), which ct_baked_render_* interpolate
     bake_azimuth / bake_lookup_reference   numpy float32 restatement of the table lookup: what the device is held to
     bake_mask_reference numpy restatement of the sparse bake's mask (ct_network_bake_sparse): cells, nodes and the margin M
+    bake_slots_reference numpy restatement of the compact bake's slot index (ct_network_bake_compact)
     save_weights / load_weights   the weight file `cloudtrace --network` reads
 
 State-dict names (the mapping an exported model needs): blocks.k.fc1 = W1_k, c1_k; blocks.k.fc2 = W2_k, c2_k (k = 0 .. 9);
@@ -293,6 +294,15 @@ def bake_mask_reference(density, grid, sample_step):
     return cells, nodes, M
 
 
+def bake_slots_reference(nodes) -> np.ndarray:
+    """The slot index of ct_network_bake_compact in numpy (include/cloudtrace.h, "the compact bake").  nodes: the mask's node
+    bytes [Nz, Ny, Nx] -> uint32 of the same shape: 0 for an inactive node, 1 + r for the r-th active node in ascending node
+    index (z Ny + y) Nx + x."""
+    active = np.ascontiguousarray(nodes).reshape(-1) != 0
+    slots = np.where(active, np.cumsum(active, dtype=np.uint64), 0).astype(np.uint32)
+    return slots.reshape(np.shape(nodes))
+
+
 # The weight file: a 32-byte little-endian header -- magic "CTNW", u32 version, blocks, width, aux, head_layers, u64 weight
 # count -- and then weight_count float32 values in the order of CtNetworkDesc.weights_host.
 WEIGHT_MAGIC = b"CTNW"
@@ -396,14 +406,17 @@ class Bake:
     """A CtBake of `net` on its tracer (ct_network_bake): the network evaluated on a grid of grid[0] x grid[1] x grid[2] position
     nodes x `azimuths` view azimuths around the light x `cosines` polar nodes, which CloudTracer.baked_render_* interpolate in
     place of gather and network.  sparse: ct_network_bake_sparse, which bakes only the probes a flight can reach and leaves the
-    rest of the table 0.  Close it before the tracer; after tracer.set_light call update()."""
+    rest of the table 0.  compact: ct_network_bake_compact, the sparse bake with only the active nodes stored, behind a slot index.
+    Close it before the tracer; after tracer.set_light call update()."""
 
-    def __init__(self, tracer, net, grid, azimuths: int, cosines: int, sparse: bool = False):
+    def __init__(self, tracer, net, grid, azimuths: int, cosines: int, sparse: bool = False, compact: bool = False):
+        if sparse and compact:
+            raise ValueError("a bake is sparse or compact, not both")
         self.L = _lib.load()
         self.tracer = tracer
         d = _lib.CtBakeDesc(_lib.CT_ABI_VERSION, (C.c_uint32 * 3)(*[int(v) for v in grid]), int(azimuths), int(cosines))
         b = C.c_void_p()
-        entry = self.L.ct_network_bake_sparse if sparse else self.L.ct_network_bake
+        entry = self.L.ct_network_bake_compact if compact else self.L.ct_network_bake_sparse if sparse else self.L.ct_network_bake
         check(entry(tracer.h, net.n, C.byref(d), C.byref(b)), tracer.h)
         self.b = b
 
@@ -453,6 +466,29 @@ class Bake:
         m = np.empty((nz, ny, nx), np.uint8)
         check(self.L.ct_bake_mask(self.b, m.ctypes.data_as(C.c_void_p), m.size), self.tracer.h)
         return m
+
+    @property
+    def storage_info(self) -> dict:
+        """ct_bake_storage_info: compact, slots, stored_entries, table_bytes, index_bytes."""
+        i = _lib.CtBakeStorageInfo()
+        check(self.L.ct_bake_storage_info(self.b, C.byref(i)), self.tracer.h)
+        return {"compact": bool(i.compact), "slots": int(i.slots), "stored_entries": int(i.stored_entries),
+                "table_bytes": int(i.table_bytes), "index_bytes": int(i.index_bytes)}
+
+    def slots(self) -> np.ndarray:
+        """ct_bake_slots -> uint32 [Nz, Ny, Nx]: the node's block in stored_table(), 0 for an inactive node (compact bakes only)."""
+        nx, ny, nz = self.info["grid"]
+        s = np.empty((nz, ny, nx), np.uint32)
+        check(self.L.ct_bake_slots(self.b, s.ctypes.data_as(C.c_void_p), s.size), self.tracer.h)
+        return s
+
+    def stored_table(self) -> np.ndarray:
+        """ct_bake_download_stored -> float32 [slots, azimuths, cosines]: the zero block, then the blocks of the active nodes in
+        ascending node index (compact bakes only)."""
+        i, st = self.info, self.storage_info
+        t = np.empty(st["stored_entries"], np.float32)
+        check(self.L.ct_bake_download_stored(self.b, t.ctypes.data_as(C.c_void_p), t.size), self.tracer.h)
+        return t.reshape(-1, i["azimuths"], i["cosines"])
 
     def probes(self, first: int = 0, count: int | None = None):
         """ct_bake_probes -> (positions, directions) float32 [count, 3], the records the bake used, in index order."""

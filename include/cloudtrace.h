@@ -722,6 +722,52 @@ CT_API int ct_bake_mask(CtBake b, uint8_t *nodes_host_out, size_t count);
 CT_API int ct_debug_bake_mask(CtHandle h, const uint32_t grid[3], uint8_t *cells_host_out, uint8_t *nodes_host_out,
                               uint32_t *active_host_out, uint32_t capacity, uint32_t *count_out);
 
+/* ---- the compact bake: only the active nodes are stored -----------------------------------------
+ *
+ * ct_network_bake_compact is the sparse bake with a table that holds nothing for an inactive node.  Mask, margin M, occupied
+ * cells, active nodes and their ascending list are the sparse bake's, byte for byte.
+ *   - slots: slot[node] = 0 for an inactive node; the r-th active node in ascending node index (r from 0) has slot[node] = 1 + r.
+ *     One uint32 per node, Nx Ny Nz of them, in node index order (z Ny + y) Nx + x (ct_bake_slots).
+ *   - the stored table holds (active + 1) Nphi Nc floats (ct_bake_download_stored): slot 0 is Nphi Nc times 0.0f, slot s >= 1 the
+ *     [Nphi][Nc] block of node list[s - 1], bit for bit the dense bake's values for that node.
+ *   - the lookup is exactly the lookup defined above -- same cell split, same weights, same lerp order k, j, x, y, z -- with the tap
+ *     of (node, j, k) read at ((size_t)slot[node] Nphi + j) Nc + k.  An inactive corner reads the zero slot; there is no branch on
+ *     activity.  It is therefore the SPARSE bake's lookup bit for bit for every input, positions no flight can produce included,
+ *     and "the one observable difference from a dense bake" stays the sparse bake's.
+ * Every ct_baked_render_* entry point, the shard ones included, and ct_debug_bake_lookup take a compact CtBake as they take any
+ * other; every frame, mean and M2 is the dense bake's bit for bit wherever a dense bake of that grid exists.
+ *
+ * Limits.  Grid, azimuth and cosine ranges are unchanged.  The 2^26 bound applies to the STORED entries (active + 1) Nphi Nc, not
+ * to the virtual Nx Ny Nz Nphi Nc: CtBakeInfo::entries stays the virtual count (at most 2^36).  Dense and sparse bakes keep their
+ * limit.
+ *
+ * The existing entry points on a compact bake: ct_bake_download takes count == entries (the virtual count) and writes the table
+ * expanded on the host -- zeros off the mask, the stored blocks on it: the sparse bake's table bit for bit; ct_bake_sparse_info
+ * and ct_bake_mask answer as for a sparse bake (sparse = 1); ct_bake_probes answers every probe of the grid; ct_bake_update
+ * stays compact, reuses the list and the slots, bakes into a second STORED table and swaps (a failure leaves everything as it was).
+ *
+ * Errors and allocation: ct_network_bake's validation and order, without the bound on the virtual entries.  The mask's
+ * temporaries, the node bytes, the list, the slots and the probe tables are allocated before the first kernel.  THE ONE PLACE
+ * WHERE THE ORDER DIFFERS FROM THE SPARSE BAKE: the stored table can only be sized once the 4-byte count of active nodes is back,
+ * so it is allocated behind the mask kernels.  More than 2^26 stored entries is CT_E_INVAL (the message names both numbers), a
+ * refused allocation CT_E_NOMEM; both come before any gather or network kernel, with *out = NULL and the handle exactly as it
+ * was.  No active node is CT_OK: one zero slot, no gather and no network call. */
+typedef struct CtBakeStorageInfo {
+    uint32_t compact;        /* 1: made by ct_network_bake_compact */
+    uint32_t reserved;       /* 0 */
+    uint64_t slots;          /* active + 1; dense / sparse bake: Nx Ny Nz */
+    uint64_t stored_entries; /* floats the table holds on the device */
+    uint64_t table_bytes;    /* 4 * stored_entries */
+    uint64_t index_bytes;    /* 4 * Nx Ny Nz; 0 for a dense / sparse bake */
+} CtBakeStorageInfo;
+
+CT_API int ct_network_bake_compact(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtBake *out);
+CT_API int ct_bake_storage_info(CtBake b, CtBakeStorageInfo *out);                    /* every kind of bake */
+/* One uint32 per node, index (z Ny + y) Nx + x.  count must equal Nx Ny Nz; a bake that is not compact: CT_E_INVAL. */
+CT_API int ct_bake_slots(CtBake b, uint32_t *slots_host_out, size_t count);
+/* The table as stored: [slot][Nphi][Nc].  count must equal stored_entries; a bake that is not compact: CT_E_INVAL. */
+CT_API int ct_bake_download_stored(CtBake b, float *table_host_out, size_t count);
+
 /* ct_network_render_subframe / _accumulate / _shard_subframe / _shard_accumulate with the table in the network's place. */
 CT_API int ct_baked_render_subframe(CtHandle h, CtBake b, const CtNetworkRender *p, uint32_t subframe_id, float *frame_rgba_dev);
 CT_API int ct_baked_render_accumulate(CtHandle h, CtBake b, const CtNetworkRender *p, uint32_t first_subframe_id, uint32_t count);

@@ -12,9 +12,15 @@ ScatterNet(200, 1, 3), warm calls, medians.  Per grid (16^3, 32^3, 64^3, each x 
 --repeats times each after one warm-up pair, and one JSON line carries the active-node share, and for both routes the medians of
 mask_ms, the gather ms, the network ms and the bake's wall ms (with the dense repeats' spread), the baked subframe's GPU ms, and
 whether the two routes' means after --subframes subframes are bit-identical (the tool exits with 1 if they are not).
+--compact: instead, what ct_network_bake_compact stores and costs.  Per grid the dense, the sparse and the
+compact bake take turns, --repeats times each after one warm-up round, and one JSON line carries the active-node share, and per
+route the table's and the index's bytes, the medians of the bake's wall ms and of the baked subframe's GPU ms with their spread
+over the repeats, and whether the three routes' means after --subframes subframes are bit-identical (exit 1 if not).  Then one
+grid beyond the dense limit, --beyond^3 (128), compact only: the active share and the sizes, or -- should (active + 1) x azimuths x
+cosines exceed 2^26 -- the library's CT_E_INVAL message.
 Needs a GPU.  No threshold: the table's resolution is the user's trade.
     python tools/baked_render_time.py [--repeats 5] [--volume 512] [--size 1024] [--subframes 16] [--grids 16 32 64]
-                                      [--azimuths 16] [--cosines 8] [--direct] [--bias 1.0] [--sparse]"""
+                                      [--azimuths 16] [--cosines 8] [--direct] [--bias 1.0] [--sparse | --compact [--beyond 128]]"""
 import argparse, json, statistics, sys, time
 from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
@@ -69,6 +75,77 @@ def sparse_against_dense(a, tr, net, common):
     return same
 
 
+ROUTES = (("dense", {}), ("sparse", {"sparse": True}), ("compact", {"compact": True}))
+
+
+def compact_against_the_others(a, tr, net, common):
+    """The --compact protocol -> True when every grid's three means were bit-identical."""
+    import numpy as np
+    from deepestscatter_amd import _lib
+    med = statistics.median
+    same = True
+    for g in a.grids:
+        runs = {name: [] for name, _ in ROUTES}
+        means = {}
+        for i in range(a.repeats + 1):          # (the first round is the warm-up)
+            for name, kw in ROUTES:
+                t0 = time.perf_counter()
+                bake = tr.network_bake(net, (g, g, g), a.azimuths, a.cosines, **kw)
+                wall = (time.perf_counter() - t0) * 1e3
+                sp, st = bake.sparse_info, bake.storage_info
+                gpu = []
+                for _ in range(6):              # (the first subframe of a fresh table reads it cold)
+                    tr.baked_render_subframe(bake, 1, out=False, direct=a.direct)
+                    gpu.append(tr.baked_render_time())
+                if i == a.repeats:
+                    tr.reset()
+                    tr.baked_render_accumulate(bake, 1, a.subframes, direct=a.direct)
+                    means[name] = tr.mean()
+                bake.close()
+                if i:
+                    runs[name].append({"wall": wall, "subframe": med(gpu[1:]), "first_subframe": gpu[0], "active": sp["active_nodes"],
+                                       "nodes": sp["nodes"], "table_bytes": st["table_bytes"], "index_bytes": st["index_bytes"]})
+        identical = all(bool(np.array_equal(means["dense"].view(np.uint32), means[name].view(np.uint32))) for name in ("sparse", "compact"))
+        same = same and identical
+        line = {"route": "ct_network_bake_compact against ct_network_bake_sparse and ct_network_bake", **common,
+                "grid": [g, g, g, a.azimuths, a.cosines], "nodes": runs["compact"][0]["nodes"], "active_nodes": runs["compact"][0]["active"],
+                "active_share": runs["compact"][0]["active"] / runs["compact"][0]["nodes"], "subframes": a.subframes,
+                "means_bit_identical": identical, "lit_pixels_of_the_mean": int((means["dense"][..., 0] > 0).sum())}
+        for name, _ in ROUTES:
+            r = runs[name]
+            line.update({f"{name}_table_bytes": r[0]["table_bytes"], f"{name}_index_bytes": r[0]["index_bytes"],
+                         f"{name}_bake_wall_ms": med(v["wall"] for v in r),
+                         f"{name}_bake_wall_ms_min_max": [min(v["wall"] for v in r), max(v["wall"] for v in r)],
+                         f"{name}_baked_subframe_gpu_ms": med(v["subframe"] for v in r),
+                         f"{name}_baked_subframe_gpu_ms_min_max": [min(v["subframe"] for v in r), max(v["subframe"] for v in r)],
+                         f"{name}_first_subframe_gpu_ms": med(v["first_subframe"] for v in r)})
+        print(json.dumps(line), flush=True)
+    # one grid beyond the dense limit, compact only
+    g = a.beyond
+    line = {"route": "ct_network_bake_compact beyond the dense limit", **common, "grid": [g, g, g, a.azimuths, a.cosines],
+            "virtual_entries": g ** 3 * a.azimuths * a.cosines, "stored_limit": 2 ** 26}
+    _, nodes, active = tr.bake_mask((g, g, g))
+    line.update({"nodes": int(nodes.size), "active_nodes": int(len(active)), "active_share": len(active) / nodes.size,
+                 "stored_entries_needed": (len(active) + 1) * a.azimuths * a.cosines})
+    try:
+        t0 = time.perf_counter()
+        bake = tr.network_bake(net, (g, g, g), a.azimuths, a.cosines, compact=True)
+        line["bake_wall_ms"] = (time.perf_counter() - t0) * 1e3
+        info, st = bake.info, bake.storage_info
+        gpu = []
+        for _ in range(6):
+            tr.baked_render_subframe(bake, 1, out=False, direct=a.direct)
+            gpu.append(tr.baked_render_time())
+        line.update({"table_bytes": st["table_bytes"], "index_bytes": st["index_bytes"], "stored_entries": st["stored_entries"],
+                     "bake_gather_ms": info["gather_ms"], "bake_network_ms": info["network_ms"],
+                     "baked_subframe_gpu_ms": med(gpu[1:]), "first_subframe_gpu_ms": gpu[0]})
+        bake.close()
+    except _lib.CloudTraceError as e:
+        line.update({"error_code": e.code, "error": e.message})
+    print(json.dumps(line), flush=True)
+    return same
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
@@ -81,6 +158,8 @@ if __name__ == "__main__":
     ap.add_argument("--direct", action="store_true")
     ap.add_argument("--bias", type=float, default=1.0)
     ap.add_argument("--sparse", action="store_true")
+    ap.add_argument("--compact", action="store_true")
+    ap.add_argument("--beyond", type=int, default=128)
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -96,8 +175,8 @@ if __name__ == "__main__":
     common = {"network": [200, 1, 3], "output_bias_raised_by": a.bias, "volume": a.volume, "frame": [a.size, a.size], "repeats": a.repeats,
               "direct": a.direct}
 
-    if a.sparse:
-        ok = sparse_against_dense(a, tr, net, common)
+    if a.sparse or a.compact:
+        ok = compact_against_the_others(a, tr, net, common) if a.compact else sparse_against_dense(a, tr, net, common)
         net.close()
         tr.close()
         sys.exit(0 if ok else 1)

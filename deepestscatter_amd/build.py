@@ -68,6 +68,8 @@ def build_cli(force: bool = False, verbose: bool = False) -> Path:
 #   w8    the DELTA kernel as two 1024-thread blocks per CU, 8 waves per SIMD, 64 VGPRs (round-4 A/B)
 #   nofuse  both estimator kernels with a scatter phase and a march / tracking burst as separate scheduler iterations (round-4 A/B)
 #   noneeskip  the MARCH kernel without the shadow-zero NEE skip (CT_MARCH_NEE_SKIP=0)
+#   ab1..ab3   CT_ABn_FLAGS, e.g. -DCT_MARCH_REPLAY_MAX=0 / 8: the MARCH kernel's free-space replay as the former loop / with
+#         another bound per lane and burst step (default 4)
 VARIANTS = {
     "exp": ["-DCT_EXPERIMENTS"],
     "w8": ["-DCT_DELTA_THREADS=1024", "-DCT_DELTA_WAVES=8"],

@@ -766,8 +766,8 @@ class CloudTracer:
         # running after they had found the job queue empty (0.5 ms bins)
         d["wave_end_hist_5ms"] = [int(v) for v in out[16:40]]
         d["wave_end_minus_drained_hist_0p5ms"] = [int(v) for v in out[40:64]]
-        ex = np.zeros(73, np.uint64)
-        check(self.L.ct_debug_stats_ex(self.h, _p(ex), 73), self.h)
+        ex = np.zeros(75, np.uint64)
+        check(self.L.ct_debug_stats_ex(self.h, _p(ex), 75), self.h)
         # of the march fetches: the lane's previous fetch was in the same 128-B brick line / a lower lane of the wave
         # fetches the same line in the same instruction (what a brick cache in LDS could find: DESIGN.md 4.3)
         d["march_fetch_same_line_as_lanes_previous"] = int(ex[68])
@@ -775,6 +775,11 @@ class CloudTracer:
         # of the NEE lookups (MARCH): those whose footprint was known to be zero (shadow-zero row) and not loaded; they are
         # counted in nee_footprints_reused too
         d["nee_lookups_skipped_shadow_zero"] = int(ex[72])
+        # MARCH free-space skips of at least one step, and the burst steps in which a lane replayed some of a skip's adds
+        # (more of these than skips: skips longer than CT_MARCH_REPLAY_MAX were spread over several burst steps);
+        # skip_loop_wave_iterations counts the replay blocks the waves executed
+        d["free_space_skips"] = int(ex[73])
+        d["replay_lane_steps"] = int(ex[74])
         d["raw"] = [int(v) for v in out]
         d["watchdog"] = int(out[63])     # exchange kernels: waves that gave up on a bounded wait (must be 0)
         return d

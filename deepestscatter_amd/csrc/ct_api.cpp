@@ -614,7 +614,9 @@ static int choose_schedule(const CtScene *s, CtHandle h)
     // until 16 lanes wait 4241; that with bursts of 2: 4295 -- profiles/r02e/delta_scatter_min_sweep.log)
     // Beyond the caches every fetch is an L2 miss and longer bursts pay: 1914 vs 1855 Msamples/s at 1024^3.
     d.march_burst = (uint32_t)knob_int(t.MARCH_BURST, 1, 1024, delta ? 2 : 8);
-    d.burst_scatter = (uint32_t)knob_int(t.BURST_SCATTER, 1, 65, delta || big ? 48 : 40);
+    // (round 6, with the bounded free-space replay, CT_MARCH_REPLAY_MAX = 4: burst_scatter 24 / 28 / 32 / 36 / 40 / 48 ->
+    // 3825 / 3880 / 3895 / 3862 / 3766 / 3481 Msamples/s; the parent's loop: 3725 / 3790 / 3827 / 3823 / 3763 / 3532; profiles/r06a)
+    d.burst_scatter = (uint32_t)knob_int(t.BURST_SCATTER, 1, 65, delta || big ? 48 : 32);
     d.burst_idle = (uint32_t)knob_int(t.BURST_IDLE, 1, 65, 32);
     d.burst_march_min = (uint32_t)knob_int(t.BURST_MARCH_MIN, 1, 64, 1);
     d.tail_burst = (uint32_t)knob_int(t.TAIL_BURST, 1, 1024, 8);

@@ -1112,6 +1112,29 @@ CT_DEV void replay_steps(f3 &pos, f3 stepv, int n)
     }
 }
 
+// render_persistent_kernel replays at most CT_MARCH_REPLAY_MAX skipped steps per lane and burst step, in one straight-line
+// block, and carries the rest of a longer skip to its next burst steps (see its march phase); 0 = replay_steps, the whole
+// skip at once at the pace of the wave's longest (A/B builds).  Measured with the scatter-burst threshold it goes with
+// (ct_api.cpp, burst_scatter 32): 4 / 6 / 8 give 3895 / 3890 / 3877 Msamples/s against 3827 with the loop; 16 is slower than
+// the loop (profiles/r06a).
+#ifndef CT_MARCH_REPLAY_MAX
+#define CT_MARCH_REPLAY_MAX 4
+#endif
+
+// The first min(owed, CT_MARCH_REPLAY_MAX) position adds of a skip: the same adds in the same order as replay_steps', each
+// under `k < owed`, so the lanes drop out one after the other and none comes back.  Returns what is still owed.
+CT_DEV uint32_t replay_bounded(f3 &pos, f3 stepv, uint32_t owed)
+{
+#pragma unroll
+    for (uint32_t k = 0; k < (uint32_t)CT_MARCH_REPLAY_MAX; k++) {
+        if (k >= owed) {
+            break;
+        }
+        pos = add3(pos, stepv);
+    }
+    return owed - min(owed, (uint32_t)CT_MARCH_REPLAY_MAX);
+}
+
 // =============================================================================================
 // shadow volume  (inScatter.cu:40-66): sample, THEN step; <= 1/sampleStep steps; early out
 // when T*255 < 1; uchar(T*255) truncating.  One thread per texel.
@@ -1380,6 +1403,7 @@ __global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu(6
     uint32_t st_hit2 = 0, st_hit3 = 0, st_h2 = 0xffffffffu, st_h3 = 0xffffffffu;   // (diagnostics: a deeper footprint cache)
     uint32_t st_same_line = 0, st_dup_line = 0, st_prev_line = 0xffffffffu;   // brick-line reuse of the march fetches (STATS)
     uint32_t st_nee_zero = 0;   // NEE lookups skipped in shadow-zero rows (STATS)
+    uint32_t st_skips = 0, st_replay_l = 0;   // free-space skips of at least one step; burst steps in which a lane replayed adds (STATS)
 
     // ---------------- resume the paths the previous launch suspended ----------------
     // How often this lane's path has been suspended so far (0 = started by this launch).  A path may be handed on while its
@@ -1693,9 +1717,11 @@ __global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu(6
             // ---------------- march (getNextScatteringEvent, cloud.cuh:87-105) ----------------
             if (STATS) {
                 st_march += 1;
-                st_march_l += nm_track;
+                st_march_l += CT_MARCH_REPLAY_MAX == 0 ? nm_track : 0u;   // (else: the lanes that step, counted in the burst)
             }
+#if CT_MARCH_REPLAY_MAX == 0
             w_fetch += nm_track; // every marching lane issues one footprint fetch per burst iteration
+#endif
             // A burst of up to sc.march_burst steps per scheduler visit: the scheduler's own
             // instructions are paid once per burst, and the lanes that collide meanwhile wait for a
             // fuller scatter phase.  The burst ends early when enough lanes wait for the scatter
@@ -1704,12 +1730,44 @@ __global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu(6
             // latency of its longest paths, so a collided lane no longer waits for a burst to end
             uint32_t burst = drained ? sc.tail_burst : sc.march_burst;
             for (;;) {
+            // Free-space skip: every brick within Chebyshev distance dfree-1 of the one `pos` is
+            // in is free, so the next n steps can neither collide (all 8 texels are 0, T *= 1)
+            // nor leave the box; only the position updates have to be replayed (same float adds
+            // in the same order -> bit-identical path).  They still count as density lookups:
+            // the counter is the algorithm's lookup count, not the loads this kernel issued.
+#if CT_MARCH_REPLAY_MAX != 0
+            // Bounded replay: a loop over the adds runs until the longest skip among the wave's lanes is done, with the other
+            // lanes' loads not yet issued.  So a lane replays at most CT_MARCH_REPLAY_MAX adds per burst step; the clearance
+            // (dfree bits 0-7) turns into the count of adds it owes once (bits 8 and up), and a lane that still owes some takes
+            // no step: it stays ST_MARCH and goes on in the next burst step or burst.  Only the schedule of a path's adds
+            // changes.  A suspended path finishes them first (below): its record has eight bits for dfree.
+            if (state == ST_MARCH && dfree != 0u) {
+                uint32_t owed = dfree >> 8;
+                if ((dfree & 0xffu) != 0u) {
+                    owed = (uint32_t)skip_steps(dfree & 0xffu, inv_maxd);
+                    c_dl += owed;
+                    if (STATS) {
+                        st_skip += owed;
+                        st_skips += owed != 0u ? 1u : 0u;
+                    }
+                }
+                if (STATS) {
+                    st_replay_l += owed != 0u ? 1u : 0u;
+                    st_skip_iters += (lane_rank(__builtin_amdgcn_ballot_w64(true)) == 0u) ? 1u : 0u;   // replay blocks executed
+                }
+                dfree = replay_bounded(pos, stepv, owed) << 8;
+            }
+            const bool steps = state == ST_MARCH && dfree == 0u;
+            {
+                const uint32_t n_steps = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(steps));
+                w_fetch += n_steps; // every lane that steps issues one footprint fetch
+                if (STATS) {
+                    st_march_l += n_steps;
+                }
+            }
+            if (steps) {
+#else
             if (state == ST_MARCH) {
-                // Free-space skip: every brick within Chebyshev distance dfree-1 of the one `pos` is
-                // in is free, so the next n steps can neither collide (all 8 texels are 0, T *= 1)
-                // nor leave the box; only the position updates have to be replayed (same float adds
-                // in the same order -> bit-identical path).  They still count as density lookups:
-                // the counter is the algorithm's lookup count, not the loads this kernel issued.
                 if (dfree != 0u) {
                     const int n = skip_steps(dfree, inv_maxd);
                     replay_steps(pos, stepv, n);
@@ -1723,8 +1781,11 @@ __global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu(6
                             wmax = max(wmax, __shfl_xor(wmax, off));
                         }
                         st_skip_iters += (lane_rank(__builtin_amdgcn_ballot_w64(true)) == 0u) ? (uint32_t)wmax : 0u;
+                        st_skips += n > 0 ? 1u : 0u;
+                        st_replay_l += n > 0 ? 1u : 0u;
                     }
                 }
+#endif
                 pos = add3(pos, stepv);
                 uint32_t meta;
                 const uint2 cell = fetch_cell_m<SPARSE, WIDE>(sc, pos, meta);
@@ -1809,10 +1870,12 @@ __global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu(6
             } else if (m_now < sc.burst_march_min || b_now >= sc.burst_scatter || 64u - m_now - b_now >= sc.burst_idle) {
                 break;
             }
+#if CT_MARCH_REPLAY_MAX == 0
             w_fetch += m_now;
+#endif
             if (STATS) {
                 st_march += 1;
-                st_march_l += m_now;
+                st_march_l += CT_MARCH_REPLAY_MAX == 0 ? m_now : 0u;
             }
             }
         }
@@ -1847,6 +1910,13 @@ __global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu(6
                 base = __builtin_amdgcn_readlane(base, __builtin_ctzll(live));
                 if (mine && base != 0xffffffffu) {
                     uint4 *e = (uint4 *)(ba.cont_out + (size_t)(base + lane_rank(live)) * kContWords);
+#if CT_MARCH_REPLAY_MAX != 0
+                    // (a path in mid-skip: the adds it still owes, so that the record's dfree keeps its eight bits)
+                    for (uint32_t owed = dfree >> 8; owed != 0u; owed--) {
+                        pos = add3(pos, stepv);
+                    }
+                    dfree &= 0xffu;
+#endif
                     e[0] = make_uint4(__float_as_uint(pos.x), __float_as_uint(pos.y), __float_as_uint(pos.z), __float_as_uint(dir.x));
                     e[1] = make_uint4(__float_as_uint(dir.y), __float_as_uint(dir.z), __float_as_uint(rad.x), __float_as_uint(rad.y));
                     e[2] = make_uint4(__float_as_uint(rad.z), seed, out_idx, __float_as_uint(xi));
@@ -1868,10 +1938,11 @@ __global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu(6
     // flush counters: per-lane tallies -> one atomic per counter per wave
     const uint32_t vals[3] = { wave_sum(c_dl), wave_sum(c_il), wave_sum(c_cap) };
     if (STATS) {
-        uint32_t sv[16] = { st_fetch, st_zero, st_skip, st_zero_d0, st_zero_d1, st_skip_iters, st_first,
-                            iv_dealt, iv_resumed, iv_written, iv_suspended, st_same_line, st_dup_line, st_hit2, st_hit3, st_nee_zero };
+        uint32_t sv[18] = { st_fetch, st_zero, st_skip, st_zero_d0, st_zero_d1, st_skip_iters, st_first,
+                            iv_dealt, iv_resumed, iv_written, iv_suspended, st_same_line, st_dup_line, st_hit2, st_hit3, st_nee_zero,
+                            st_skips, st_replay_l };
 #pragma unroll
-        for (int i = 0; i < 16; i++) {
+        for (int i = 0; i < 18; i++) {
             sv[i] = wave_sum(sv[i]);
         }
         if (lane == 0) {
@@ -1908,6 +1979,8 @@ __global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu(6
             atomicAdd(&ba.stats[70], (unsigned long long)sv[13]);
             atomicAdd(&ba.stats[71], (unsigned long long)sv[14]);
             atomicAdd(&ba.stats[72], (unsigned long long)sv[15]);
+            atomicAdd(&ba.stats[73], (unsigned long long)sv[16]);
+            atomicAdd(&ba.stats[74], (unsigned long long)sv[17]);
         }
     }
     flush_counters(ba, lane, vals[0], vals[1], vals[2], w_fetch, w_nee);

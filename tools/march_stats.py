@@ -22,7 +22,14 @@ out = {"volume": n, "size": size, "spp": spp, "memory": t.debug_memory(),
                       "zero_footprints_with_clearance_0": d(s0, s1, "zero_cells_nonfree_brick") / paths,
                       "zero_footprints_with_clearance_1": d(s0, s1, "zero_cells_free_brick_d1") / paths,
                       "skipped_steps": d(s0, s1, "skipped_steps") / paths,
+                      # the free-space replay: skips of at least one step, the burst steps in which a lane replayed adds, and
+                      # what the waves paid (iterations of the replay loop with CT_MARCH_REPLAY_MAX=0, else replay blocks)
+                      "free_space_skips": d(s0, s1, "free_space_skips") / paths,
+                      "replay_lane_steps": d(s0, s1, "replay_lane_steps") / paths,
+                      "skip_loop_wave_iterations": d(s0, s1, "skip_loop_wave_iterations") / paths,
                       "inscatter_lookups": d(k0, k1, "inscatter_lookups") / paths, "inscatter_fetches": d(f0, f1, "inscatter_fetches") / paths,
                       "march_phase_lanes": d(s0, s1, "march_lanes") / max(d(s0, s1, "march_phases"), 1),
-                      "scatter_phase_lanes": d(s0, s1, "scatter_lanes") / max(d(s0, s1, "scatter_phases"), 1)}}
+                      "scatter_phase_lanes": d(s0, s1, "scatter_lanes") / max(d(s0, s1, "scatter_phases"), 1)},
+       "per_march_burst_step": {"skip_loop_wave_iterations": d(s0, s1, "skip_loop_wave_iterations") / max(d(s0, s1, "march_phases"), 1)},
+       "march_burst_steps_per_sample": d(s0, s1, "march_phases") / paths}
 print(json.dumps(out, indent=1))

@@ -526,6 +526,33 @@ CT_DEV uint2 fetch_cell_cached(const DevScene &sc, const uint8_t *bricks, f3 p, 
     return zero ? make_uint2(0u, 0u) : cached;
 }
 
+// The same cache holding the two RAW 8-byte words of the footprint (x, y = bytes [0, 8); z, w = bytes [25, 33)), so that a
+// fetch is nothing but the issue of its two loads: no instruction here reads their destination, hence no wait here.  The
+// caller combines the entry (combine_raw_footprint) where it needs the footprint -- a reused entry too, again each time: two
+// instructions the wave executes anyway.  (CT_MARCH_NEE_ASYNC, DESIGN.md 4.1 "Round 7")
+template <bool WIDE>
+CT_DEV void fetch_cell_cached_raw(const DevScene &sc, const uint8_t *bricks, f3 p, uint32_t &key, uint4 &raw, bool &reused,
+                                  bool zero = false)
+{
+    const float fx = fmaf(p.x, sc.sx, -0.5f), fy = fmaf(p.y, sc.sy, -0.5f), fz = fmaf(p.z, sc.sz, -0.5f);
+    const uint32_t x = (uint32_t)(floor_to_int(fx) + sc.brick_bias), y = (uint32_t)(floor_to_int(fy) + sc.brick_bias),
+                   z = (uint32_t)(floor_to_int(fz) + sc.brick_bias);
+    const uint32_t brick = __umul24(z >> 2, (uint32_t)sc.brick_gxy) + __umul24(y >> 2, (uint32_t)sc.brick_gx) + (x >> 2);
+    const uint32_t local = __umul24(z & 3u, 25u) + __umul24(y & 3u, 5u) + (x & 3u);
+    const uint32_t off = (brick << 7) | local;   // (see fetch_cell_cached)
+    reused = sc.nee_cache != 0u && off == key;
+    if (!reused && !zero) {
+        uint2 a, c;
+        load_footprint_pair<WIDE>(bricks, brick, local, a, c);
+        raw = make_uint4(a.x, a.y, c.x, c.y);
+        key = off;
+    }
+}
+CT_DEV uint2 combine_raw_footprint(const uint4 &raw)
+{
+    return make_uint2(__builtin_amdgcn_perm(raw.y, raw.x, 0x06050100u), __builtin_amdgcn_perm(raw.w, raw.z, 0x06050100u));
+}
+
 template <bool SPARSE, bool WIDE = true>
 CT_DEV uint2 fetch_cell_m(const DevScene &sc, f3 p, uint32_t &meta)
 {

@@ -957,8 +957,12 @@ CT_DEV f3 in_scattering(const DevScene &sc, f3 pos, f3 dir, bool chopped)
     return scale3(l, sc.sun_ratio);
 }
 
-// The same NEE in two halves, so that its three loads (two phase-table entries, the shadow
-// volume's footprint) are in flight while the direction sampling runs: identical arithmetic.
+// The same NEE in two halves, issue and finish, with the direction sampling between them: identical arithmetic.  What is in
+// flight meanwhile depends on the issuing half.  in_scattering_issue and in_scattering_issue_phase hand back the combined
+// footprint, and the two v_perm_b32 that combine it wait for its loads on the spot: only the arithmetic is deferred.
+// in_scattering_issue_lds with CT_MARCH_NEE_ASYNC (render_persistent_kernel) leaves `cell` unset and the footprint's two raw
+// words in the lane's cache; the caller combines them just ahead of in_scattering_finish, so the loads are in flight while
+// the direction is sampled (DESIGN.md 4.1 "Round 7").
 struct NeeLoads {
     float a, b, w;     // phase table entries and filter weight
     uint2 cell;        // shadow-volume footprint
@@ -1011,9 +1015,22 @@ CT_DEV NeeLoads in_scattering_issue_phase(const DevScene &sc, f3 dir, bool chopp
 typedef const float __attribute__((address_space(3))) LdsFloat;
 typedef const float __attribute__((address_space(1))) GlobalFloat;
 
+// CT_MARCH_NEE_ASYNC (A/B, DESIGN.md 4.1 "Round 7"): 1 = the cache holds the footprint's two raw words (NeeCache = uint4,
+// fetch_cell_cached_raw) and NeeLoads::cell is left for the caller to combine just ahead of in_scattering_finish; 0 = the
+// cache holds the combined footprint, whose two v_perm_b32 -- and with them the wait for the loads -- sit right behind the
+// loads' issue, as until round 6.
+#ifndef CT_MARCH_NEE_ASYNC
+#define CT_MARCH_NEE_ASYNC 1
+#endif
+#if CT_MARCH_NEE_ASYNC
+typedef uint4 NeeCache;
+#else
+typedef uint2 NeeCache;
+#endif
+
 template <bool FIXED8, bool WIDE>
 CT_DEV NeeLoads in_scattering_issue_lds(const DevScene &sc, const MieLdsFull &lds, f3 pos, f3 dir, bool chopped,
-                                        uint32_t &nee_key, uint2 &nee_cell, bool &reused, bool zero = false)
+                                        uint32_t &nee_key, NeeCache &nee_cell, bool &reused, bool zero = false)
 {
     NeeLoads n;
     const float cos_light = dot3(mk3(sc.nlx, sc.nly, sc.nlz), dir);
@@ -1042,7 +1059,11 @@ CT_DEV NeeLoads in_scattering_issue_lds(const DevScene &sc, const MieLdsFull &ld
     n.a = (i > kMieN - 2) ? pair.y : pair.x;
     n.b = (i < 0) ? pair.x : pair.y;
     n.w = tex_weight<FIXED8>(x);
+#if CT_MARCH_NEE_ASYNC
+    fetch_cell_cached_raw<WIDE>(sc, sc.ibricks, pos, nee_key, nee_cell, reused, zero);
+#else
     n.cell = fetch_cell_cached<WIDE>(sc, sc.ibricks, pos, nee_key, nee_cell, reused, zero);
+#endif
     return n;
 }
 
@@ -1396,7 +1417,11 @@ __global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu(6
     // path conservation (STATS kernels only, CT_DEBUG_INVARIANTS): samples dealt, results written
     uint32_t iv_dealt = 0, iv_written = 0, iv_resumed = 0, iv_suspended = 0;
     uint32_t nee_key = 0xffffffffu;         // fetch_cell_cached: this lane's last shadow-volume footprint
-    uint2 nee_cell = make_uint2(0u, 0u);
+#if CT_MARCH_NEE_ASYNC
+    NeeCache nee_cell = make_uint4(0u, 0u, 0u, 0u);   // (the footprint's raw words)
+#else
+    NeeCache nee_cell = make_uint2(0u, 0u);
+#endif
     // scheduler diagnostics (STATS builds only), see ct_debug_stats
     uint32_t st_regen = 0, st_regen_l = 0, st_march = 0, st_march_l = 0, st_scat = 0, st_scat_l = 0;
     uint32_t st_fetch = 0, st_zero = 0, st_skip = 0, st_zero_d0 = 0, st_zero_d1 = 0, st_skip_iters = 0, st_stolen = 0, st_iters = 0, st_first = 0;
@@ -1624,6 +1649,13 @@ __global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu(6
                 st_scat_l += nb;
             }
             bool nee_fetched = false;
+#if CT_MARCH_NEE_ASYNC
+            // vmcnt(0), the other counters untouched.  Not a new wait: the NEE's address computation below waits for vector
+            // memory anyway (only a result store of the previous burst step can be outstanding here).  Stated at the phase's
+            // entry, it keeps the compiler, which joins several paths here, from putting its own into the first pass of the CDF
+            // search, behind the NEE loads.
+            __builtin_amdgcn_s_waitcnt(0x0f70);
+#endif
             if (state == ST_BOUNCE) {
                 // The collision's back-off (cloud.cuh:99) was left for this phase: in the march phase
                 // one lane in fifteen collides per step, so its log and two divisions would run for
@@ -1685,6 +1717,12 @@ __global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu(6
                             go = false;
                         }
                     }
+#if CT_MARCH_NEE_ASYNC
+                    // (the pin keeps the footprint's combination and in_scattering_finish behind the direction sampling: left to
+                    // itself the scheduler moves them, and the wait for the loads, up between the CDF inversion and the sincos)
+                    asm volatile("" : "+v"(nee_cell.x), "+v"(nee_cell.y), "+v"(nee_cell.z), "+v"(nee_cell.w), "+v"(dir.x), "+v"(dir.y), "+v"(dir.z));
+                    nee.cell = (CT_MARCH_NEE_SKIP == 2 && nee_zero) ? make_uint2(0u, 0u) : combine_raw_footprint(nee_cell);
+#endif
                     if (CT_MARCH_NEE_SKIP != 1 || !nee_zero) {
                         rad = add3(rad, in_scattering_finish<FIXED8>(sc, nee, pos));
                     }

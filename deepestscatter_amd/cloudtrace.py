@@ -426,6 +426,16 @@ class CloudTracer:
             raise ValueError("network_bake: sparse or compact, not both")
         return Bake(self, net, grid, azimuths, cosines, sparse, compact)
 
+    def traced_bake(self, grid, azimuths: int, cosines: int, samples: int, sparse: bool = False, compact: bool = False):
+        """ct_bake_traced -> deepestscatter_amd.network.Bake: the probe table of network_bake's grid filled with the means of
+        `samples` experiments of the path tracer's point estimator (multiply scattered sun radiance) per entry, no network.
+        baked_render_*(direct=True) on it renders the path tracer's total up to the table's resolution; Bake.trace_more refines
+        it, Bake.retrace follows set_light.  `sparse` and `compact` as in network_bake."""
+        from .network import Bake
+        if sparse and compact:
+            raise ValueError("traced_bake: sparse or compact, not both")
+        return Bake(self, None, grid, azimuths, cosines, sparse, compact, samples=int(samples))
+
     def bake_mask(self, grid):
         """ct_debug_bake_mask: the sparse bake's mask of a grid (Nx, Ny, Nz) on this handle, no network needed
         -> (cells uint8 [Nz-1, Ny-1, Nx-1], nodes uint8 [Nz, Ny, Nx], the active node indices uint32, ascending)."""

@@ -2579,32 +2579,36 @@ extern "C" int ct_synchronize(CtHandle h)
 
 static_assert(sizeof(CtPointRadianceTask) == 40, "Gpu::PointRadianceTask is 40 bytes (PointRadianceTask.h:70-77)");
 
-extern "C" int ct_point_radiance_launch(CtHandle h, CtPointRadianceTask *tasks_host, uint32_t count,
-                                        uint32_t first_frame_id, uint32_t launches)
+// (re)allocation waits for the device, so it happens only when a call is larger than every call before it
+template <typename T>
+static hipError_t point_grow(T **p, size_t &cap, size_t need)
 {
-    NEED(h);
-    if (!tasks_host || count == 0 || launches == 0 || launches > 0xffffu || count > (1u << 24)) {
-        return fail(h, CT_E_INVAL, "ct_point_radiance_launch: need 1..2^24 tasks and 1..65535 launches");
+    if (need <= cap) {
+        return hipSuccess;
     }
-    if (h->scene.flags & CT_FLAG_SIMPLE_KERNEL) {
-        return fail(h, CT_E_INVAL, "point radiance tasks need the persistent kernel");
-    }
-    // A zero direction, or a direction or origin with a component that is not finite, has no ray, but can still "hit" the box
-    // (fmaxf drops the NaN slabs; 0 / 0 needs only an origin inside): the path would then march with NaN coordinates, which
-    // neither the estimators' brick addressing nor the DELTA estimator's cell walk is written for.  No ray of the reference is such.
-    for (uint32_t i = 0; i < count; i++) {
-        const float *d = tasks_host[i].direction, *o = tasks_host[i].position;
-        if (!(std::isfinite(d[0]) && std::isfinite(d[1]) && std::isfinite(d[2])) || (d[0] == 0.f && d[1] == 0.f && d[2] == 0.f)) {
-            return fail(h, CT_E_INVAL, "ct_point_radiance_launch: task %u has a zero or non-finite direction", i);
-        }
-        if (!(std::isfinite(o[0]) && std::isfinite(o[1]) && std::isfinite(o[2]))) {
-            return fail(h, CT_E_INVAL, "ct_point_radiance_launch: task %u has a non-finite position", i);
+    if (*p) {
+        hipError_t e = hipFree(*p);
+        *p = nullptr;
+        cap = 0;
+        if (e != hipSuccess) {
+            return e;
         }
     }
+    hipError_t e = hipMalloc((void **)p, need * sizeof(**p));
+    if (e == hipSuccess) {
+        cap = need;
+    }
+    return e;
+}
+
+// The launch half of ct_point_radiance_launch, which the traced bake (ct_neural.cpp) shares: `launches` experiments, frames
+// first_frame_id .., of the `count` point tasks whose rays `rays` enqueues into h->pt.primary / h->pt.pixels (grown to
+// pad64(count) entries by then).  The results are h->pt.frames[f * pad64(count) + i]; `fold` enqueues what consumes them.
+// Waits for the stream, books the estimator's time and the paths.  sc: the scene the estimator runs with.
+int ct::point_launch(CtHandle h, const DevScene &sc, uint32_t count, uint32_t first_frame_id, uint32_t launches,
+                     const std::function<int()> &rays, const std::function<int()> &fold)
+{
     const uint32_t n_pad = (count + 63u) & ~63u, n_groups = n_pad / 64u;
-    if ((uint64_t)n_pad * launches > 0xffffffffull) {
-        return fail(h, CT_E_INVAL, "too many task-launches for one call");
-    }
     // ---- job list.  A job = (group of 64 tasks, range of frames).  A collector's call is small -- 20480 tasks x 100
     // frames are 32000 wave-jobs of 64 experiments for the chip's 6144 resident waves -- and most of its work is in the few
     // tasks deep inside the cloud, whose every experiment runs to the depth cap (2000 bounces): jobs are single frames
@@ -2656,37 +2660,18 @@ extern "C" int ct_point_radiance_launch(CtHandle h, CtPointRadianceTask *tasks_h
     }
     CtHandle_::PointBuffers &pt = h->pt;
     auto run = [&]() -> int {
-        // (re)allocation waits for the device, so it happens only when a call is larger than every call before it
-        const auto grow = [&](auto **p, size_t &cap, size_t need) -> hipError_t {
-            if (need <= cap) {
-                return hipSuccess;
-            }
-            if (*p) {
-                hipError_t e = hipFree(*p);
-                *p = nullptr;
-                cap = 0;
-                if (e != hipSuccess) {
-                    return e;
-                }
-            }
-            hipError_t e = hipMalloc((void **)p, need * sizeof(**p));
-            if (e == hipSuccess) {
-                cap = need;
-            }
-            return e;
-        };
-        HIPCHK(h, grow(&pt.tasks, pt.cap_tasks, count));
-        HIPCHK(h, grow(&pt.primary, pt.cap_primary, 2 * (size_t)n_pad));
-        HIPCHK(h, grow(&pt.pixels, pt.cap_pixels, n_pad));
-        HIPCHK(h, grow(&pt.frames, pt.cap_frames, (size_t)n_pad * launches));
-        HIPCHK(h, grow(&pt.jg, pt.cap_jg, jg.size()));
-        HIPCHK(h, grow(&pt.js, pt.cap_js, js.size()));
-        HIPCHK(h, hipMemcpyAsync(pt.tasks, tasks_host, (size_t)count * sizeof(CtPointRadianceTask),
-                                 hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, point_grow(&pt.primary, pt.cap_primary, 2 * (size_t)n_pad));
+        HIPCHK(h, point_grow(&pt.pixels, pt.cap_pixels, n_pad));
+        HIPCHK(h, point_grow(&pt.frames, pt.cap_frames, (size_t)n_pad * launches));
+        HIPCHK(h, point_grow(&pt.jg, pt.cap_jg, jg.size()));
+        HIPCHK(h, point_grow(&pt.js, pt.cap_js, js.size()));
         HIPCHK(h, hipMemcpyAsync(pt.jg, jg.data(), jg.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipMemcpyAsync(pt.js, js.data(), js.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipMemsetAsync(h->d_queue, 0, kQueueWords * sizeof(uint32_t), h->stream));
-        HIPCHK(h, launch_point_rays(h->dev, pt.tasks, count, n_pad, pt.primary, pt.pixels, h->stream));
+        int rc = rays();
+        if (rc != CT_OK) {
+            return rc;
+        }
         BatchArgs ba{};
         ba.frames = pt.frames;
         ba.frame_stride = n_pad;
@@ -2712,14 +2697,15 @@ extern "C" int ct_point_radiance_launch(CtHandle h, CtPointRadianceTask *tasks_h
         ba.stats = h->d_counters + kCounterCount + 1;
         HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
         if (h->scene.estimator == CT_EST_DELTA) {
-            HIPCHK(h, launch_render_delta(h->dev, ba, shape, h->stream));
+            HIPCHK(h, launch_render_delta(sc, ba, shape, h->stream));
         } else {
-            HIPCHK(h, launch_render_persistent(h->dev, ba, shape, h->stream));
+            HIPCHK(h, launch_render_persistent(sc, ba, shape, h->stream));
         }
         HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
-        HIPCHK(h, launch_point_accumulate(pt.frames, n_pad, pt.tasks, count, launches, h->stream));
-        HIPCHK(h, hipMemcpyAsync(tasks_host, pt.tasks, (size_t)count * sizeof(CtPointRadianceTask),
-                                 hipMemcpyDeviceToHost, h->stream));
+        rc = fold();
+        if (rc != CT_OK) {
+            return rc;
+        }
         HIPCHK(h, hipStreamSynchronize(h->stream));
         float ms = 0;
         HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
@@ -2740,6 +2726,48 @@ extern "C" int ct_point_radiance_launch(CtHandle h, CtPointRadianceTask *tasks_h
         hipStreamSynchronize(h->stream);
     }
     return rc;
+}
+
+extern "C" int ct_point_radiance_launch(CtHandle h, CtPointRadianceTask *tasks_host, uint32_t count,
+                                        uint32_t first_frame_id, uint32_t launches)
+{
+    NEED(h);
+    if (!tasks_host || count == 0 || launches == 0 || launches > 0xffffu || count > (1u << 24)) {
+        return fail(h, CT_E_INVAL, "ct_point_radiance_launch: need 1..2^24 tasks and 1..65535 launches");
+    }
+    if (h->scene.flags & CT_FLAG_SIMPLE_KERNEL) {
+        return fail(h, CT_E_INVAL, "point radiance tasks need the persistent kernel");
+    }
+    // A zero direction, or a direction or origin with a component that is not finite, has no ray, but can still "hit" the box
+    // (fmaxf drops the NaN slabs; 0 / 0 needs only an origin inside): the path would then march with NaN coordinates, which
+    // neither the estimators' brick addressing nor the DELTA estimator's cell walk is written for.  No ray of the reference is such.
+    for (uint32_t i = 0; i < count; i++) {
+        const float *d = tasks_host[i].direction, *o = tasks_host[i].position;
+        if (!(std::isfinite(d[0]) && std::isfinite(d[1]) && std::isfinite(d[2])) || (d[0] == 0.f && d[1] == 0.f && d[2] == 0.f)) {
+            return fail(h, CT_E_INVAL, "ct_point_radiance_launch: task %u has a zero or non-finite direction", i);
+        }
+        if (!(std::isfinite(o[0]) && std::isfinite(o[1]) && std::isfinite(o[2]))) {
+            return fail(h, CT_E_INVAL, "ct_point_radiance_launch: task %u has a non-finite position", i);
+        }
+    }
+    const uint32_t n_pad = (count + 63u) & ~63u;
+    if ((uint64_t)n_pad * launches > 0xffffffffull) {
+        return fail(h, CT_E_INVAL, "too many task-launches for one call");
+    }
+    CtHandle_::PointBuffers &pt = h->pt;
+    return point_launch(
+        h, h->dev, count, first_frame_id, launches,
+        [&]() -> int {
+            HIPCHK(h, point_grow(&pt.tasks, pt.cap_tasks, count));
+            HIPCHK(h, hipMemcpyAsync(pt.tasks, tasks_host, (size_t)count * sizeof(CtPointRadianceTask), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, launch_point_rays(h->dev, pt.tasks, count, n_pad, pt.primary, pt.pixels, h->stream));
+            return CT_OK;
+        },
+        [&]() -> int {
+            HIPCHK(h, launch_point_accumulate(pt.frames, n_pad, pt.tasks, count, launches, h->stream));
+            HIPCHK(h, hipMemcpyAsync(tasks_host, pt.tasks, (size_t)count * sizeof(CtPointRadianceTask), hipMemcpyDeviceToHost, h->stream));
+            return CT_OK;
+        });
 }
 
 extern "C" int ct_generate_scatter_samples(CtHandle h, uint32_t count, uint32_t batch_seed,

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <array>
 #include <cstdlib>
+#include <functional>
 #include <string>
 #include <utility>
 #include <vector>
@@ -25,7 +26,7 @@ struct Knob {
     const char *get() const { return is_set ? text.c_str() : nullptr; }
     explicit operator bool() const { return is_set; }
 };
-#define CT_KNOBS(X) X(BAKE_MASK_BYTES) X(BURST_IDLE) X(BURST_MARCH_MIN) X(BURST_SCATTER) X(CHUNK_INTERLEAVE) X(CHUNK_MORTON) X(CONTINUATION) X(DEBUG_INVARIANTS) X(DELTA_INTERIOR) X(DELTA_NEE) X(EXCHANGE) X(HAND_ON_JOBS) X(HINT_PERIOD) X(JOB_MAX) X(JOB_WORK) X(MARCH_BURST) X(MAX_AGE) X(NEE_CACHE) X(NET_DESC_RECORDS) X(NO_ADVANCE) X(POINT_BLOCKS_PER_CU) X(POINT_ORDER) X(REGEN_MIN) X(RENDER_AHEAD) X(SCATTER_MIN) X(SCATTER_RATIO) X(SCRATCH_GIB) X(SCRATCH_MIB) X(SERPENTINE) X(SHARED_DEPTH) X(SPARSE) X(STATS) X(TAIL_BURST) X(TILE_ORDER) X(TIMELINE) X(TRACE) X(TUNE_SUBFRAMES) X(XCD_QUEUES) X(XCD_QUEUES_UNTUNED) X(XCD_REGIONS) X(BLOCKS_PER_CU) X(WIDE_OFFSETS) X(START_RECORDS)
+#define CT_KNOBS(X) X(BAKE_MASK_BYTES) X(BAKE_TRACE_RESULTS) X(BURST_IDLE) X(BURST_MARCH_MIN) X(BURST_SCATTER) X(CHUNK_INTERLEAVE) X(CHUNK_MORTON) X(CONTINUATION) X(DEBUG_INVARIANTS) X(DELTA_INTERIOR) X(DELTA_NEE) X(EXCHANGE) X(HAND_ON_JOBS) X(HINT_PERIOD) X(JOB_MAX) X(JOB_WORK) X(MARCH_BURST) X(MAX_AGE) X(NEE_CACHE) X(NET_DESC_RECORDS) X(NO_ADVANCE) X(POINT_BLOCKS_PER_CU) X(POINT_ORDER) X(REGEN_MIN) X(RENDER_AHEAD) X(SCATTER_MIN) X(SCATTER_RATIO) X(SCRATCH_GIB) X(SCRATCH_MIB) X(SERPENTINE) X(SHARED_DEPTH) X(SPARSE) X(STATS) X(TAIL_BURST) X(TILE_ORDER) X(TIMELINE) X(TRACE) X(TUNE_SUBFRAMES) X(XCD_QUEUES) X(XCD_QUEUES_UNTUNED) X(XCD_REGIONS) X(BLOCKS_PER_CU) X(WIDE_OFFSETS) X(START_RECORDS)
 struct CtTuning {
 #define X(name) Knob name;
     CT_KNOBS(X)
@@ -266,6 +267,11 @@ int fail(CtHandle h, int code, const char *fmt, ...);
 int flush(CtHandle h);            // waits for the batches in flight
 void discard_ahead(CtHandle h);
 int enqueue_convergence_test(CtHandle h, uint32_t subframes);
+// ct_point_radiance_launch's launch half (ct_api.cpp), shared with the traced bake: job list, queue split, grid share, the
+// estimator launch with `sc`, its time and the host counters.  rays / fold enqueue what fills h->pt.primary and h->pt.pixels
+// before the estimator and what reads h->pt.frames[f * pad64(count) + i] behind it; the stream is idle when it returns.
+int point_launch(CtHandle h, const DevScene &sc, uint32_t count, uint32_t first_frame_id, uint32_t launches,
+                 const std::function<int()> &rays, const std::function<int()> &fold);
 
 // ct_neural.cpp: the density mip pyramid, built on first use (ct_debug_layout reads it too).
 int ensure_pyramid(CtHandle h);

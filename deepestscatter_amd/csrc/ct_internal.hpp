@@ -292,6 +292,22 @@ hipError_t launch_bake_store_list(const float *out, const uint32_t *list, uint64
                                   uint32_t stride, uint32_t k, hipStream_t stream);
 hipError_t launch_baked_compose(const DevScene &sc, const PixelBand &band, const FlightTemps &t, const BakeTable &table, const NetCompose &c,
                                 const ComposeTarget &dst, const uint32_t *frozen, hipStream_t stream);
+// ct_bake_traced (ct_bake_trace.hip): the stored entries [first, first + n) of a bake as point tasks and their fold.  list:
+// nullptr for a dense bake (stored entry = virtual entry), otherwise the active nodes, whose blocks the stored entries count
+// through.  axes: the position nodes of x, y, z; directions: nphi x nc x 3.  launch_bake_trace_tasks writes primary[2 i],
+// primary[2 i + 1] and pixels[i] for i < n_pad (a multiple of 64, >= n) as launch_point_rays does, with the seed base of the
+// entry's virtual index; launch_bake_trace_fold folds frames[f * stride + i].x, f < passes, into the entry's float of `table`
+// (the stored table: compact = behind its zero block), which holds the mean of `done` experiments.
+struct BakeTraceArgs {
+    const uint32_t *list;
+    const float *axes, *directions;
+    uint32_t nx, ny, nphi, nc;
+    uint64_t first;
+    uint32_t n, n_pad, compact;
+};
+hipError_t launch_bake_trace_tasks(const DevScene &sc, const BakeTraceArgs &a, float4 *primary, uint32_t *pixels, hipStream_t stream);
+hipError_t launch_bake_trace_fold(const BakeTraceArgs &a, const float4 *frames, uint32_t stride, uint32_t passes, uint32_t done,
+                                  float *table, hipStream_t stream);
 // Density pyramid (Resources::generateMipmaps) and the descriptor gather.
 constexpr int kMaxMipLevels = 16;
 struct MipPyramid {

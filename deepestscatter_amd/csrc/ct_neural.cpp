@@ -1,7 +1,8 @@
 // ct_neural.cpp -- the first-scatter and network path of the C ABI: the density pyramid and the descriptor gather
 // (ct_collect_descriptors, ct_descriptor_frame), the scattering network (ct_network_create, ct_network_eval) and the network as a
 // renderer (ct_network_render_*) and baked into a probe table (ct_network_bake, ct_baked_render_*), on the handle of ct_handle.hpp.
-// The network itself is ct_network.hip.
+// The network itself is ct_network.hip.  The traced bake (ct_bake_traced) fills the same table with the path tracer's point
+// estimator instead: its two kernels are ct_bake_trace.hip, its launches ct_api.cpp's point_launch.
 #include <cmath>
 
 #include "ct_handle.hpp"
@@ -402,6 +403,13 @@ struct CtBake_ {
     bool compact = false;
     uint64_t stored = 0;
     uint32_t *d_slots = nullptr;             // one word per node: 1 + its place in the list, 0 for an inactive node
+    // ct_bake_traced: the entries are means of the path tracer's point estimator, no network.  A traced bake of
+    // any kind has d_probe (its position nodes) and d_dirs, the Nphi x Nc x 3 direction table of its frame.
+    bool traced = false;
+    uint32_t samples = 0;                    // experiments folded into every stored entry of an active node
+    uint64_t paths = 0;
+    double trace_ms = 0, fold_ms = 0;
+    float *d_dirs = nullptr;
 };
 
 static uint64_t bake_probes_total(const CtBake_ *b)
@@ -694,9 +702,122 @@ static int bake_run(CtHandle h, CtNetwork n, CtBake_ *b, float *table)
     return CT_OK;
 }
 
+// ---- the traced bake (ct_bake_traced): the table filled by the path tracer's point estimator ---------------------------------------
+// d(j, k) = c l + sqrt(1 - c^2) u_j, c = cosine[k], in double from the frame's floats and rounded once: [j][k][xyz].
+static void bake_directions(const CtBake_ *b, std::vector<float> &out)
+{
+    out.resize(3 * (size_t)b->azimuths * b->cosines);
+    float p[3], u[3];
+    for (uint32_t j = 0; j < b->azimuths; j++) {
+        bake_probe(b, j, p, u);
+        for (uint32_t k = 0; k < b->cosines; k++) {
+            const double c = (double)b->cosine[k], s = std::sqrt(1.0 - c * c);
+            for (int axis = 0; axis < 3; axis++) {
+                out[3 * ((size_t)j * b->cosines + k) + axis] = (float)(c * (double)b->l[axis] + s * (double)u[axis]);
+            }
+        }
+    }
+}
+
+// The tables the task kernel reads, for b's frame as it is: the position nodes and u_j in d_probe, d(j, k) in d_dirs.
+static int bake_upload_trace_tables(CtHandle h, const CtBake_ *b)
+{
+    std::vector<float> dirs;
+    bake_directions(b, dirs);
+    HIPCHK(h, hipMemcpy(b->d_dirs, dirs.data(), dirs.size() * sizeof(float), hipMemcpyHostToDevice));
+    return bake_upload_probe_tables(h, b);
+}
+
+// Results one pass of the traced bake may keep in the point buffers' `frames`: 2^24 (256 MiB), or CT_BAKE_TRACE_RESULTS.
+static uint32_t bake_trace_budget(CtHandle h)
+{
+    return (uint32_t)knob_int(h->tune.BAKE_TRACE_RESULTS, 64, 1 << 26, 1 << 24);
+}
+
+struct TraceEvents {
+    hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
+    ~TraceEvents()
+    {
+        for (hipEvent_t e : ev) {
+            if (e) {
+                hipEventDestroy(e);
+            }
+        }
+    }
+};
+
+// Experiments b->samples + 1 .. b->samples + samples of every stored entry of an active node, folded into `table` (b->stored
+// floats, which hold the means of b->samples experiments).  The stream is idle and the tables of b's frame are uploaded.  The
+// entries go through in chunks of at most 2^20, a chunk's samples in passes that keep at most the budget of results; the
+// estimator runs on a copy of the handle's scene in CT_MODE_SUN_MULTIPLE_SCATTER.  Books b's counts and times.
+static int bake_trace(CtHandle h, CtBake_ *b, float *table, uint32_t samples)
+{
+    const uint64_t block = (uint64_t)b->azimuths * b->cosines, total = b->sparse ? b->active * block : b->entries;
+    b->trace_ms = b->fold_ms = 0;
+    if (samples == 0u || total == 0u) {
+        b->samples += samples;
+        return CT_OK;
+    }
+    const uint32_t budget = bake_trace_budget(h);
+    const uint32_t chunk = (uint32_t)std::min<uint64_t>(total, std::min<uint32_t>(budget, 1u << 20));
+    DevScene sc = h->dev;
+    sc.mode = CT_MODE_SUN_MULTIPLE_SCATTER;
+    TraceEvents te;
+    for (hipEvent_t &e : te.ev) {
+        HIPCHK(h, hipEventCreate(&e));
+    }
+    CtHandle_::PointBuffers &pt = h->pt;
+    const double render_before = h->render_ms;
+    double fold_ms = 0;
+    for (uint64_t first = 0; first < total; first += chunk) {
+        BakeTraceArgs a{};
+        a.list = b->sparse ? b->d_list : nullptr;
+        a.axes = b->d_probe;
+        a.directions = b->d_dirs;
+        a.nx = b->grid[0];
+        a.ny = b->grid[1];
+        a.nphi = b->azimuths;
+        a.nc = b->cosines;
+        a.first = first;
+        a.n = (uint32_t)std::min<uint64_t>(chunk, total - first);
+        a.n_pad = (a.n + 63u) & ~63u;
+        a.compact = b->compact ? 1u : 0u;
+        const uint32_t per_pass = std::min(0xffffu, std::max(1u, budget / a.n_pad));
+        for (uint32_t at = 0; at < samples; at += per_pass) {
+            const uint32_t passes = std::min(per_pass, samples - at), done = b->samples + at;
+            const int rc = point_launch(
+                h, sc, a.n, done + 1u, passes,
+                [&]() -> int {
+                    HIPCHK(h, hipEventRecord(te.ev[0], h->stream));
+                    HIPCHK(h, launch_bake_trace_tasks(sc, a, pt.primary, pt.pixels, h->stream));
+                    HIPCHK(h, hipEventRecord(te.ev[1], h->stream));
+                    return CT_OK;
+                },
+                [&]() -> int {
+                    HIPCHK(h, hipEventRecord(te.ev[2], h->stream));
+                    HIPCHK(h, launch_bake_trace_fold(a, pt.frames, a.n_pad, passes, done, table, h->stream));
+                    HIPCHK(h, hipEventRecord(te.ev[3], h->stream));
+                    return CT_OK;
+                });
+            if (rc != CT_OK) {
+                return rc;
+            }
+            float ms0 = 0, ms1 = 0;
+            HIPCHK(h, hipEventElapsedTime(&ms0, te.ev[0], te.ev[1]));
+            HIPCHK(h, hipEventElapsedTime(&ms1, te.ev[2], te.ev[3]));
+            fold_ms += (double)ms0 + (double)ms1;
+        }
+    }
+    b->samples += samples;
+    b->paths += total * samples;
+    b->trace_ms = h->render_ms - render_before;
+    b->fold_ms = fold_ms;
+    return CT_OK;
+}
+
 static void bake_free(CtBake_ *b)
 {
-    for (void *p : { (void *)b->d_table, (void *)b->d_nodes, (void *)b->d_list, (void *)b->d_probe, (void *)b->d_slots }) {
+    for (void *p : { (void *)b->d_table, (void *)b->d_nodes, (void *)b->d_list, (void *)b->d_probe, (void *)b->d_slots, (void *)b->d_dirs }) {
         if (p) {
             hipFree(p);
         }
@@ -704,18 +825,19 @@ static void bake_free(CtBake_ *b)
     delete b;
 }
 
-// ct_network_bake, ct_network_bake_sparse and ct_network_bake_compact: one validation, one order of errors.
+// ct_network_bake, ct_network_bake_sparse and ct_network_bake_compact: one validation, one order of errors.  trace_samples:
+// ct_bake_traced, which takes no network (n is NULL) and fills the table with that many experiments per entry.
 enum class BakeKind { Dense, Sparse, Compact };
 
-static int bake_create(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtBake *out, BakeKind kind)
+static int bake_create(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtBake *out, BakeKind kind, const uint32_t *trace_samples = nullptr)
 {
-    const bool sparse = kind != BakeKind::Dense, compact = kind == BakeKind::Compact;
-    const char *const who = compact ? "ct_network_bake_compact" : sparse ? "ct_network_bake_sparse" : "ct_network_bake";
+    const bool sparse = kind != BakeKind::Dense, compact = kind == BakeKind::Compact, traced = trace_samples != nullptr;
+    const char *const who = traced ? "ct_bake_traced" : compact ? "ct_network_bake_compact" : sparse ? "ct_network_bake_sparse" : "ct_network_bake";
     if (!h) {
         return fail(nullptr, CT_E_INVAL, "null handle");
     }
-    if (!n || !d || !out) {
-        return fail(h, CT_E_INVAL, "%s: need a network, a description and out", who);
+    if ((!traced && !n) || !d || !out) {
+        return fail(h, CT_E_INVAL, traced ? "%s: need a description and out" : "%s: need a network, a description and out", who);
     }
     *out = nullptr;
     if (d->abi_version != CT_ABI_VERSION) {
@@ -738,8 +860,14 @@ static int bake_create(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtBake *out
     if (!compact && entries > (1ull << 26)) {        // (a compact bake bounds what it stores, once the mask has been counted)
         return fail(h, CT_E_INVAL, "%s: %llu entries, a table holds at most 2^26", who, (unsigned long long)entries);
     }
+    if (traced && *trace_samples > 0xffffu) {
+        return fail(h, CT_E_INVAL, "%s: %u samples, one call traces at most 65535", who, *trace_samples);
+    }
+    if (traced && (h->scene.flags & CT_FLAG_SIMPLE_KERNEL)) {
+        return fail(h, CT_E_INVAL, "%s: point radiance tasks need the persistent kernel", who);
+    }
     NEED_NOFLUSH(h);
-    int rc = net_validate_network(h, n, who);
+    int rc = traced ? CT_OK : net_validate_network(h, n, who);
     if (rc != CT_OK) {
         return rc;
     }
@@ -749,6 +877,7 @@ static int bake_create(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtBake *out
     }
     CtBake_ *b = new CtBake_();
     b->h = h;
+    b->traced = traced;
     b->device = h->device;
     for (int axis = 0; axis < 3; axis++) {
         b->grid[axis] = d->grid[axis];
@@ -764,6 +893,12 @@ static int bake_create(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtBake *out
         (void)hipGetLastError();
         delete b;
         return fail(h, CT_E_NOMEM, "%s: no device memory for a table of %llu entries", who, (unsigned long long)entries);
+    }
+    if (traced && (dmalloc(&b->d_dirs, 3 * (size_t)b->azimuths * b->cosines) != hipSuccess ||
+                   (!sparse && dmalloc(&b->d_probe, b->grid[0] + b->grid[1] + b->grid[2] + 3 * (size_t)b->azimuths) != hipSuccess))) {
+        (void)hipGetLastError();
+        bake_free(b);
+        return fail(h, CT_E_NOMEM, "%s: no device memory for the direction and probe tables", who);
     }
     double mask_ms = 0;
     if (sparse) {   // the mask's temporaries, the node bytes, the list, the slots and the record tables: all before the first kernel, too
@@ -802,7 +937,16 @@ static int bake_create(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtBake *out
         b->d_slots = m.slots.release();   // (nullptr unless compact)
     }
     bake_frame(h, b);
-    rc = bake_run(h, n, b, b->d_table);
+    if (traced) {
+        rc = drained(h, [&]() -> int {
+            HIPCHK(h, hipMemsetAsync(b->d_table, 0, (size_t)b->stored * sizeof(float), h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            const int up = bake_upload_trace_tables(h, b);
+            return up != CT_OK ? up : bake_trace(h, b, b->d_table, *trace_samples);
+        });
+    } else {
+        rc = bake_run(h, n, b, b->d_table);
+    }
     b->mask_ms += mask_ms;   // (bake_run has set it to its record kernel's time)
     if (rc != CT_OK) {
         bake_free(b);
@@ -825,6 +969,22 @@ extern "C" int ct_network_bake_sparse(CtHandle h, CtNetwork n, const CtBakeDesc 
 extern "C" int ct_network_bake_compact(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtBake *out)
 {
     return bake_create(h, n, d, out, BakeKind::Compact);
+}
+
+extern "C" int ct_bake_traced(CtHandle h, const CtBakeDesc *d, uint32_t kind, uint32_t samples, CtBake *out)
+{
+    if (!h) {
+        return fail(nullptr, CT_E_INVAL, "null handle");
+    }
+    if (!d || !out) {
+        return fail(h, CT_E_INVAL, "ct_bake_traced: need a description and out");
+    }
+    *out = nullptr;
+    if (kind != CT_BAKE_DENSE && kind != CT_BAKE_SPARSE && kind != CT_BAKE_COMPACT) {
+        return fail(h, CT_E_INVAL, "ct_bake_traced: unknown kind %u (CT_BAKE_DENSE, CT_BAKE_SPARSE or CT_BAKE_COMPACT)", kind);
+    }
+    return bake_create(h, nullptr, d, out, kind == CT_BAKE_COMPACT ? BakeKind::Compact : kind == CT_BAKE_SPARSE ? BakeKind::Sparse : BakeKind::Dense,
+                       &samples);
 }
 
 extern "C" int ct_bake_storage_info(CtBake b, CtBakeStorageInfo *out)
@@ -972,6 +1132,9 @@ extern "C" int ct_bake_update(CtHandle h, CtNetwork n, CtBake b)
     if (b->h != h) {
         return fail(h, CT_E_INVAL, "%s: the bake was made on another handle", who);
     }
+    if (b->traced) {
+        return fail(h, CT_E_INVAL, "%s: a traced bake holds no network's outputs; ct_bake_retrace traces it again", who);
+    }
     rc = flush(h);
     if (rc != CT_OK) {
         return rc;
@@ -991,6 +1154,121 @@ extern "C" int ct_bake_update(CtHandle h, CtNetwork n, CtBake b)
     }
     hipFree(b->d_table);
     b->d_table = fresh.release();
+    return CT_OK;
+}
+
+// What ct_bake_trace_more and ct_bake_retrace check alike, in this order; the device is set, nothing is flushed.
+static int bake_trace_checks(CtHandle h, CtBake b, uint32_t samples, const char *who)
+{
+    if (!h) {
+        return fail(nullptr, CT_E_INVAL, "null handle");
+    }
+    if (!b) {
+        return fail(h, CT_E_INVAL, "%s: need a bake", who);
+    }
+    NEED_NOFLUSH(h);
+    if (b->h != h) {
+        return fail(h, CT_E_INVAL, "%s: the bake was made on another handle", who);
+    }
+    if (!b->traced) {
+        return fail(h, CT_E_INVAL, "%s: the bake holds a network's outputs; ct_bake_update bakes it again", who);
+    }
+    if (samples == 0u || samples > 0xffffu) {
+        return fail(h, CT_E_INVAL, "%s: %u samples, a call traces 1 .. 65535", who, samples);
+    }
+    return CT_OK;
+}
+
+extern "C" int ct_bake_trace_more(CtHandle h, CtBake b, uint32_t samples)
+{
+    const char *const who = "ct_bake_trace_more";
+    int rc = bake_trace_checks(h, b, samples, who);
+    if (rc != CT_OK) {
+        return rc;
+    }
+    if ((uint64_t)b->samples + samples > (1ull << 24)) {
+        return fail(h, CT_E_INVAL, "%s: %u samples behind %u, an entry holds at most 2^24 experiments", who, samples, b->samples);
+    }
+    if (b->epoch != h->light_epoch) {
+        return fail(h, CT_E_STATE, "%s: the handle's light has changed since the bake; ct_bake_retrace traces it again", who);
+    }
+    rc = flush(h);
+    if (rc != CT_OK) {
+        return rc;
+    }
+    return drained(h, [&]() -> int {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return bake_trace(h, b, b->d_table, samples);
+    });
+}
+
+extern "C" int ct_bake_retrace(CtHandle h, CtBake b, uint32_t samples)
+{
+    const char *const who = "ct_bake_retrace";
+    int rc = bake_trace_checks(h, b, samples, who);
+    if (rc == CT_OK) {
+        rc = flush(h);
+    }
+    if (rc != CT_OK) {
+        return rc;
+    }
+    // into a second table, as ct_bake_update: a failure leaves the old table, its frame and its sample count as they were
+    DevTemp<float> fresh;
+    if (dmalloc(&fresh, (size_t)b->stored) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(h, CT_E_NOMEM, "%s: no device memory for a table of %llu entries", who, (unsigned long long)b->stored);
+    }
+    const CtBake_ before = *b;
+    bake_frame(h, b);
+    b->samples = 0;
+    b->paths = 0;
+    rc = drained(h, [&]() -> int {
+        HIPCHK(h, hipMemsetAsync(fresh, 0, (size_t)b->stored * sizeof(float), h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        const int up = bake_upload_trace_tables(h, b);
+        return up != CT_OK ? up : bake_trace(h, b, fresh, samples);
+    });
+    if (rc != CT_OK) {
+        const std::string text = h->error;
+        *b = before;
+        if (bake_upload_trace_tables(h, b) == CT_OK) {   // (the old frame's tables again; otherwise that failure is the one to report)
+            h->error = text;
+        }
+        return rc;
+    }
+    hipFree(b->d_table);
+    b->d_table = fresh.release();
+    return CT_OK;
+}
+
+extern "C" int ct_bake_trace_info(CtBake b, CtBakeTraceInfo *out)
+{
+    if (!b || !out) {
+        return fail(b ? b->h : nullptr, CT_E_INVAL, "ct_bake_trace_info: need a bake and out");
+    }
+    *out = CtBakeTraceInfo{};
+    if (b->traced) {
+        out->traced = 1u;
+        out->samples = b->samples;
+        out->paths = b->paths;
+        out->trace_ms = b->trace_ms;
+        out->fold_ms = b->fold_ms;
+    }
+    return CT_OK;
+}
+
+extern "C" int ct_bake_directions(CtBake b, float *directions_host_out, size_t count)
+{
+    if (!b) {
+        return fail(nullptr, CT_E_INVAL, "ct_bake_directions: null bake");
+    }
+    const size_t floats = 3 * (size_t)b->azimuths * b->cosines;
+    if (!directions_host_out || count != floats) {
+        return fail(b->h, CT_E_INVAL, "ct_bake_directions: need an array of exactly %llu floats", (unsigned long long)floats);
+    }
+    std::vector<float> dirs;
+    bake_directions(b, dirs);
+    std::copy(dirs.begin(), dirs.end(), directions_host_out);
     return CT_OK;
 }
 
@@ -1084,7 +1362,8 @@ static int bake_foreign(CtHandle h, CtBake b, const char *who)
 static int bake_stale(CtHandle h, CtBake b, const char *who)
 {
     if (b->epoch != h->light_epoch) {
-        return fail(h, CT_E_STATE, "%s: the handle's light has changed since the bake; ct_bake_update bakes it again", who);
+        return fail(h, CT_E_STATE, "%s: the handle's light has changed since the bake; %s", who,
+                    b->traced ? "ct_bake_retrace traces it again" : "ct_bake_update bakes it again");
     }
     return CT_OK;
 }

@@ -193,6 +193,56 @@ namespace DeepestScatter
         CtBake bake = nullptr;
     };
 
+    // The baked renderer without a network (--traced-bake NX,NY,NZ,NPHI,NC --bake-samples N): the probe table holds the means of
+    // N experiments of the path tracer's point estimator per entry (ct_bake_traced) and every subframe is interpolated from it.
+    // Traced in init, and again (ct_bake_retrace) should the light have changed since.  One GPU only.
+    class TracedBakeRenderer : public PathTracingRenderer
+    {
+    public:
+        TracedBakeRenderer(std::shared_ptr<Context> context, const CtNetworkRender& params, const CtBakeDesc& desc, uint32_t kind, uint32_t samples)
+            : PathTracingRenderer(std::move(context)), params(params), desc(desc), kind(kind), samples(samples) {}
+        ~TracedBakeRenderer() override
+        {
+            if (bake) ct_bake_destroy(bake);   // (before the handle)
+        }
+
+        void init() override
+        {
+            PathTracingRenderer::init();
+            if (context->group) throw std::runtime_error("--traced-bake renders on one GPU only");
+            if (!bake) Context::check(ct_bake_traced(context->handle, &desc, kind, samples, &bake), context->handle, "ct_bake_traced");
+        }
+
+        void render(float* frameResultBuffer) override
+        {
+            applyCamera();
+            refresh();
+            Context::check(ct_baked_render_subframe(context->handle, bake, &params, subframeId, frameResultBuffer), context->handle,
+                           "ct_baked_render_subframe");
+        }
+
+        void renderAccumulate(uint32_t first, uint32_t count, bool /*enqueue: the call waits once, at its end*/) override
+        {
+            applyCamera();
+            refresh();
+            Context::check(ct_baked_render_accumulate(context->handle, bake, &params, first, count), context->handle,
+                           "ct_baked_render_accumulate");
+        }
+
+    private:
+        void refresh()   // a light set since the bake: trace again
+        {
+            CtBakeInfo info;
+            Context::check(ct_bake_info(bake, &info), context->handle, "ct_bake_info");
+            if (!info.current) Context::check(ct_bake_retrace(context->handle, bake, samples), context->handle, "ct_bake_retrace");
+        }
+
+        CtNetworkRender params;
+        CtBakeDesc desc;
+        uint32_t kind, samples;
+        CtBake bake = nullptr;
+    };
+
     class Camera : public SceneItem                                              // Camera.h:16-103
     {
     public:

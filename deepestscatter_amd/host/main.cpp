@@ -17,6 +17,9 @@
 //                               and interpolate every subframe from the table (ct_baked_render_accumulate); one GPU, not with --gpus
 //              [--net-bake-sparse]              with --net-baked: bake only the probes a first flight can reach (ct_network_bake_sparse); the same images
 //              [--net-bake-compact]             with --net-baked: bake and store only those probes (ct_network_bake_compact); the same images; not with --net-bake-sparse
+//              [--traced-bake NX,NY,NZ,NPHI,NC --bake-samples N [--net-bake-sparse | --net-bake-compact] [--net-direct]]   without
+//                               --network: fill that probe grid with N path-traced experiments per entry (ct_bake_traced) and
+//                               interpolate every subframe from the table; --net-scale and --net-transform apply; one GPU
 //   <cloud> = file.vdb | procedural:<N>[:<seed>] | file.f32grid
 //
 //   cloudtrace collect <cloud>|@list.txt [--scene-id I] [--scenes N] [--jobs K] [--gpus ..] [--batch 2048] [--light L] [--size-m M] [--out DIR] [--data DIR] [--estimator ..] [--tex-fixed8]
@@ -78,6 +81,8 @@ namespace
         CtBakeDesc bake{ CT_ABI_VERSION, { 0, 0, 0 }, 0, 0 };
         bool netBakeSparse = false;                                               // --net-bake-sparse: ct_network_bake_sparse in place of ct_network_bake
         bool netBakeCompact = false;                                              // --net-bake-compact: ct_network_bake_compact in place of ct_network_bake
+        bool tracedBake = false;                                                  // --traced-bake NX,NY,NZ,NPHI,NC: the table of `bake` traced, no network (TracedBakeRenderer)
+        uint32_t bakeSamples = 0;                                                 // --bake-samples N: experiments per entry of the traced bake
         bool netDirect = false;                                                   // --net-direct: CT_NET_ADD_SINGLE_SCATTER joins networkRender.transform
         bool collect = false;                                                     // `cloudtrace collect ...`
         int32_t sceneId = 0;
@@ -276,7 +281,9 @@ namespace
             std::replace(stem.begin(), stem.end(), ':', '_');
             auto outputPath = std::filesystem::path(opt.outDir) / (stem + "." + toString(lightDirection) + "." + PathTracingRenderer::NAME + "." + opt.format);
             // installFramework + installApp: Sun, VDBCloud, CloudMaterial, Camera in this order (installers.cpp:28-38)
-            std::shared_ptr<PathTracingRenderer> renderer = !opt.network ? std::make_shared<PathTracingRenderer>(context)
+            std::shared_ptr<PathTracingRenderer> renderer = opt.tracedBake ? std::make_shared<TracedBakeRenderer>(context, opt.networkRender, opt.bake,
+                    opt.netBakeCompact ? CT_BAKE_COMPACT : opt.netBakeSparse ? CT_BAKE_SPARSE : CT_BAKE_DENSE, opt.bakeSamples)
+                : !opt.network ? std::make_shared<PathTracingRenderer>(context)
                 : opt.netBaked ? std::make_shared<BakedRenderer>(context, opt.network, opt.networkRender, opt.bake, opt.netBakeSparse, opt.netBakeCompact)
                                : std::make_shared<NetworkRenderer>(context, opt.network, opt.networkRender);
             renderer->estimator = opt.estimator;
@@ -300,7 +307,7 @@ int main(int argc, char* argv[])
     try
     {
         Options opt;
-        if (argc < 2) { std::cerr << "usage: cloudtrace <cloud> [--size WxH] [--spp N] [--mode total|multi|single] [--light L] [--size-m M] [--out DIR] [--data DIR] [--unfused] [--display] [--estimator march|delta] [--format exr|pfm] [--gpus N|a,b,c] [--tex-fixed8] [--network FILE [--net-transform linear|expm1] [--net-scale r,g,b] [--net-direct] [--net-baked NX,NY,NZ,NPHI,NC [--net-bake-sparse | --net-bake-compact]]] (--network with --gpus: every GPU renders its own tiles; --net-baked: one GPU)\n"; return 2; }
+        if (argc < 2) { std::cerr << "usage: cloudtrace <cloud> [--size WxH] [--spp N] [--mode total|multi|single] [--light L] [--size-m M] [--out DIR] [--data DIR] [--unfused] [--display] [--estimator march|delta] [--format exr|pfm] [--gpus N|a,b,c] [--tex-fixed8] [--network FILE [--net-transform linear|expm1] [--net-scale r,g,b] [--net-direct] [--net-baked NX,NY,NZ,NPHI,NC [--net-bake-sparse | --net-bake-compact]]] [--traced-bake NX,NY,NZ,NPHI,NC --bake-samples N [--net-bake-sparse | --net-bake-compact] [--net-direct]] (--network with --gpus: every GPU renders its own tiles; --net-baked: one GPU)\n"; return 2; }
         int first = 2;
         bool lightsGiven = false;
         opt.cloud = argv[1];
@@ -357,6 +364,18 @@ int main(int argc, char* argv[])
                 if (std::sscanf(next().c_str(), "%u,%u,%u,%u,%u", &b.grid[0], &b.grid[1], &b.grid[2], &b.azimuths, &b.cosines) != 5) throw std::invalid_argument("--net-baked NX,NY,NZ,NPHI,NC");
                 opt.netBaked = true;
             }
+            else if (a == "--traced-bake")
+            {
+                CtBakeDesc& b = opt.bake;
+                if (std::sscanf(next().c_str(), "%u,%u,%u,%u,%u", &b.grid[0], &b.grid[1], &b.grid[2], &b.azimuths, &b.cosines) != 5) throw std::invalid_argument("--traced-bake NX,NY,NZ,NPHI,NC");
+                opt.tracedBake = true;
+            }
+            else if (a == "--bake-samples")
+            {
+                const long n = std::stol(next());
+                if (n < 1 || n > 65535) throw std::invalid_argument("--bake-samples N, 1 .. 65535");
+                opt.bakeSamples = (uint32_t)n;
+            }
             else if (a == "--net-bake-sparse")
             {
                 opt.netBakeSparse = true;
@@ -396,9 +415,14 @@ int main(int argc, char* argv[])
         if (opt.collect) return collectScenes(opt);
 
         if (opt.netDirect) opt.networkRender.transform |= CT_NET_ADD_SINGLE_SCATTER;   // (after the loop: --net-transform may follow it)
-        if (opt.netBakeCompact && !opt.netBaked) throw std::invalid_argument("--net-bake-compact chooses how --net-baked NX,NY,NZ,NPHI,NC bakes and stores its table");
+        if (opt.tracedBake && !opt.networkPath.empty()) throw std::invalid_argument("--traced-bake fills the table with path-traced radiance: it cannot be combined with --network");
+        if (opt.tracedBake && opt.netBaked) throw std::invalid_argument("--traced-bake and --net-baked are two ways to fill one table: give one of them");
+        if (opt.tracedBake && opt.bakeSamples == 0) throw std::invalid_argument("--traced-bake needs --bake-samples N");
+        if (opt.bakeSamples != 0 && !opt.tracedBake) throw std::invalid_argument("--bake-samples counts the experiments of --traced-bake NX,NY,NZ,NPHI,NC");
+        if (opt.tracedBake && !opt.devices.empty()) throw std::invalid_argument("--traced-bake renders on one GPU: it cannot be combined with --gpus");
+        if (opt.netBakeCompact && !opt.netBaked && !opt.tracedBake) throw std::invalid_argument("--net-bake-compact chooses how --net-baked NX,NY,NZ,NPHI,NC bakes and stores its table");
         if (opt.netBakeCompact && opt.netBakeSparse) throw std::invalid_argument("--net-bake-compact and --net-bake-sparse are two ways to bake one table: give one of them");
-        if (opt.netBakeSparse && !opt.netBaked) throw std::invalid_argument("--net-bake-sparse chooses how --net-baked NX,NY,NZ,NPHI,NC bakes its table");
+        if (opt.netBakeSparse && !opt.netBaked && !opt.tracedBake) throw std::invalid_argument("--net-bake-sparse chooses how --net-baked NX,NY,NZ,NPHI,NC bakes its table");
         if (opt.netBaked && opt.networkPath.empty()) throw std::invalid_argument("--net-baked bakes the network of --network FILE");
         if (opt.netBaked && !opt.devices.empty()) throw std::invalid_argument("--net-baked renders on one GPU: it cannot be combined with --gpus");
         if (!opt.networkPath.empty())

@@ -303,6 +303,30 @@ def bake_slots_reference(nodes) -> np.ndarray:
     return slots.reshape(np.shape(nodes))
 
 
+def bake_directions_reference(info, probe_directions) -> np.ndarray:
+    """The directions of a traced bake in numpy (include/cloudtrace.h, "the traced bake"): d(j, k) = c l + sqrt(1 - c^2) u_j with
+    c = info["cosine"][k], in float64 from the float32 light info["light"] and the float32 probe directions u_j (the first
+    `azimuths` rows of Bake.probes()[1]), rounded once to float32 -> [azimuths, cosines, 3]."""
+    l = np.asarray(info["light"], np.float32).reshape(3).astype(np.float64)
+    c = np.asarray(info["cosine"], np.float32).reshape(-1).astype(np.float64)
+    u = np.ascontiguousarray(probe_directions, np.float32).reshape(-1, 3)[:int(info["azimuths"])].astype(np.float64)
+    s = np.sqrt(1.0 - c * c)
+    return (c[None, :, None] * l[None, None, :] + s[None, :, None] * u[:, None, :]).astype(np.float32)
+
+
+def point_fold_reference(values_f32, mean=None, count: int = 0) -> np.ndarray:
+    """The `radiance` of PointRadianceTask::addExperimentResult applied to values_f32[0], values_f32[1], ... (float32 [S, ...]) in
+    order, every operation rounded to float32, newWeight = (float)(1.0 / (double)(float)N): what ct_point_radiance_launch and a
+    traced bake store.  mean / count: the state to continue from (default: zeros, 0 experiments)."""
+    f32 = np.float32
+    v = np.ascontiguousarray(values_f32, f32)
+    rad = np.zeros(v.shape[1:], f32) if mean is None else np.array(mean, f32)
+    for k, x in enumerate(v):
+        weight = f32(1.0 / np.float64(f32(count + k + 1)))
+        rad = (rad + ((x - rad).astype(f32) * weight).astype(f32)).astype(f32)
+    return rad
+
+
 # The weight file: a 32-byte little-endian header -- magic "CTNW", u32 version, blocks, width, aux, head_layers, u64 weight
 # count -- and then weight_count float32 values in the order of CtNetworkDesc.weights_host.
 WEIGHT_MAGIC = b"CTNW"
@@ -407,17 +431,27 @@ class Bake:
     nodes x `azimuths` view azimuths around the light x `cosines` polar nodes, which CloudTracer.baked_render_* interpolate in
     place of gather and network.  sparse: ct_network_bake_sparse, which bakes only the probes a flight can reach and leaves the
     rest of the table 0.  compact: ct_network_bake_compact, the sparse bake with only the active nodes stored, behind a slot index.
-    Close it before the tracer; after tracer.set_light call update()."""
+    Close it before the tracer; after tracer.set_light call update().
+    net=None with samples=S: a traced bake (ct_bake_traced) of the same kind, whose entries are the means of S experiments of
+    the path tracer's point estimator instead of a network's outputs; trace_more() refines it, retrace() follows a new light."""
 
-    def __init__(self, tracer, net, grid, azimuths: int, cosines: int, sparse: bool = False, compact: bool = False):
+    def __init__(self, tracer, net, grid, azimuths: int, cosines: int, sparse: bool = False, compact: bool = False, samples: int | None = None):
         if sparse and compact:
             raise ValueError("a bake is sparse or compact, not both")
+        if net is not None and samples is not None:
+            raise ValueError("a bake holds a network's outputs (net) or traced radiance (net=None, samples=...), not both")
+        if net is None and samples is None:
+            raise ValueError("a bake needs a network, or net=None and samples=... for a traced bake")
         self.L = _lib.load()
         self.tracer = tracer
         d = _lib.CtBakeDesc(_lib.CT_ABI_VERSION, (C.c_uint32 * 3)(*[int(v) for v in grid]), int(azimuths), int(cosines))
         b = C.c_void_p()
-        entry = self.L.ct_network_bake_compact if compact else self.L.ct_network_bake_sparse if sparse else self.L.ct_network_bake
-        check(entry(tracer.h, net.n, C.byref(d), C.byref(b)), tracer.h)
+        if net is None:
+            kind = _lib.CT_BAKE_COMPACT if compact else _lib.CT_BAKE_SPARSE if sparse else _lib.CT_BAKE_DENSE
+            check(self.L.ct_bake_traced(tracer.h, C.byref(d), kind, int(samples), C.byref(b)), tracer.h)
+        else:
+            entry = self.L.ct_network_bake_compact if compact else self.L.ct_network_bake_sparse if sparse else self.L.ct_network_bake
+            check(entry(tracer.h, net.n, C.byref(d), C.byref(b)), tracer.h)
         self.b = b
 
     def close(self):
@@ -440,6 +474,28 @@ class Bake:
     def update(self, net):
         """ct_bake_update: bake again in place, for the tracer's light as it is now and for `net`."""
         check(self.L.ct_bake_update(self.tracer.h, net.n, self.b), self.tracer.h)
+
+    def trace_more(self, samples: int):
+        """ct_bake_trace_more: `samples` more experiments per entry of a traced bake, folded behind those it holds."""
+        check(self.L.ct_bake_trace_more(self.tracer.h, self.b, int(samples)), self.tracer.h)
+
+    def retrace(self, samples: int):
+        """ct_bake_retrace: a traced bake again from experiment 1, for the tracer's light as it is now."""
+        check(self.L.ct_bake_retrace(self.tracer.h, self.b, int(samples)), self.tracer.h)
+
+    def trace_info(self) -> dict:
+        """ct_bake_trace_info: traced, samples, paths, trace_ms, fold_ms (a network's bake: all zero)."""
+        i = _lib.CtBakeTraceInfo()
+        check(self.L.ct_bake_trace_info(self.b, C.byref(i)), self.tracer.h)
+        return {"traced": bool(i.traced), "samples": int(i.samples), "paths": int(i.paths), "trace_ms": float(i.trace_ms),
+                "fold_ms": float(i.fold_ms)}
+
+    def directions(self) -> np.ndarray:
+        """ct_bake_directions -> float32 [azimuths, cosines, 3]: d(j, k), the direction a traced bake's entry (j, k) stands for."""
+        i = self.info
+        d = np.empty((i["azimuths"], i["cosines"], 3), np.float32)
+        check(self.L.ct_bake_directions(self.b, d.ctypes.data_as(C.c_void_p), d.size), self.tracer.h)
+        return d
 
     @property
     def info(self) -> dict:

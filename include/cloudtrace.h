@@ -768,6 +768,67 @@ CT_API int ct_bake_slots(CtBake b, uint32_t *slots_host_out, size_t count);
 /* The table as stored: [slot][Nphi][Nc].  count must equal stored_entries; a bake that is not compact: CT_E_INVAL. */
 CT_API int ct_bake_download_stored(CtBake b, float *table_host_out, size_t count);
 
+/* ---- the traced bake: the probe table filled with path-traced radiance -----------------------------
+ *
+ * A table entry at (position node, azimuth node j, polar node k) stands for the multiply scattered sun radiance that arrives at
+ * the node from direction d(j, k): the label a network of this ABI is trained on, and what ct_point_radiance_launch estimates on a
+ * CT_MODE_SUN_MULTIPLE_SCATTER handle.  ct_bake_traced makes a CtBake whose entries are Monte-Carlo means of that estimator,
+ * traced on the device over the bake's own nodes, with no network: pictures from ct_baked_render_* at the baked subframe's cost
+ * (with CT_NET_ADD_SINGLE_SCATTER the path tracer's total, up to the table's resolution), and the table a network bake of the
+ * same grid should approach.
+ *
+ * Grid, limits, frame (l, a, b), cosine[k], position nodes, u_j, mask, active list and slots are those of ct_network_bake (kind
+ * CT_BAKE_DENSE), ct_network_bake_sparse (CT_BAKE_SPARSE) or ct_network_bake_compact (CT_BAKE_COMPACT), with their validation,
+ * their order of errors and their 2^26 bound (a compact bake: on the stored entries).
+ *   - d(j, k) = c l + sqrt(1 - c^2) u_j with c = cosine[k], computed in double from the floats l and u_j (ct_bake_probes') and
+ *     rounded once to float; at c = -1 and c = 1 it is -l and l for every j.  ct_bake_directions returns exactly the floats
+ *     the tracer used, [j][k][xyz], for any kind of bake.
+ *   - e = probe index * Nc + k is the entry's virtual index, whatever the kind.  Experiment f = 1, 2, ... of the entry is the path
+ *     ct_point_radiance_launch traces for a task at array index (uint32_t)e with the probe's position, direction d(j, k) and
+ *     frame f, on a handle of this cloud, light, flags and estimator in CT_MODE_SUN_MULTIPLE_SCATTER: seed
+ *     tea<4>((uint32_t)(e * 4096), f).  ENTRIES 2^20 APART THEREFORE SHARE THEIR RANDOM NUMBERS, as the tasks of that entry
+ *     point do.  The handle's own mode does not matter; its estimator and CT_FLAG_TEX_FIXED8 apply as everywhere.
+ *   - the stored value after S experiments is the `radiance` of PointRadianceTask::addExperimentResult applied S times from
+ *     (0, count 0) in frame order, in float32 with new_weight = (float)(1.0 / (double)N).
+ *   - only the entries of active nodes are traced: a sparse table is 0.0f off the mask, a compact one keeps its zero block, a
+ *     dense bake traces every node; the three agree bit for bit on every active node's block.
+ * ct_bake_trace_more continues the fold with frames samples + 1 ..: traced(a) and then trace_more(b) are the bits of traced(a + b).
+ * ct_bake_retrace, after ct_set_light, rebuilds the frame and traces from frame 1 into a zeroed second table, then swaps; a
+ * failure leaves table, frame and sample count as they were.  ct_bake_update on a traced bake is CT_E_INVAL (ct_bake_retrace).
+ *
+ * Every ct_baked_render_* entry point, the shard ones included, ct_debug_bake_lookup and every ct_bake_* function above take a
+ * traced bake as they take any other; CtBakeInfo's gather_ms and network_ms are 0.  A handle of any shard_count is accepted:
+ * point tasks are not pixels.
+ *
+ * The calls wait for the batches in flight, run on the handle's stream and return when it is idle.  They touch neither mean, M2,
+ * frame, the subframe count, samples rendered ahead nor the pose's pixel list.  CtCounters, CtFetchCounters, ct_kernel_time and
+ * the armed invariants (CT_DEBUG_INVARIANTS) COUNT THE TRACED PATHS EXACTLY AS ct_point_radiance_launch COUNTS ITS OWN.  The
+ * table, the direction table and everything the mask needs are allocated before the first kernel (a compact table behind the
+ * mask's count, as there).  Scratch is the handle's point-task buffers: the entries go through in chunks of at most 2^20, a
+ * chunk's samples in passes of at most max(1, CT_BAKE_TRACE_RESULTS / padded chunk) (default 2^24 results, 256 MiB; 64 .. 2^26);
+ * the result depends neither on the chunks nor on the passes.
+ *
+ * CT_E_INVAL: a NULL argument (a NULL handle is answered without a device); a wrong abi_version, an unknown kind, a grid error;
+ * more than 65535 samples in one call, or 0 in ct_bake_trace_more / ct_bake_retrace (ct_bake_traced with 0 samples is CT_OK: an
+ * all-zero table, nothing launched); more than 2^24 samples in a table's life; a CT_FLAG_SIMPLE_KERNEL handle; a bake of another
+ * handle; ct_bake_trace_more / ct_bake_retrace on a network's bake; a wrong count in ct_bake_directions.
+ * CT_E_STATE: ct_bake_trace_more on a bake whose light is no longer the handle's. */
+enum { CT_BAKE_DENSE = 0, CT_BAKE_SPARSE = 1, CT_BAKE_COMPACT = 2 };
+typedef struct CtBakeTraceInfo {
+    uint32_t traced;      /* 1: made by ct_bake_traced (a network bake answers all zeros) */
+    uint32_t samples;     /* experiments folded into every stored entry of an active node so far */
+    uint64_t paths;       /* estimator paths traced for this table since it was (re)started */
+    double   trace_ms;    /* GPU time of the estimator launches of the last call */
+    double   fold_ms;     /* GPU time of the task and fold kernels of the last call */
+} CtBakeTraceInfo;       /* 32 bytes; samples at 4, paths at 8, trace_ms at 16 */
+
+CT_API int ct_bake_traced(CtHandle h, const CtBakeDesc *d, uint32_t kind, uint32_t samples, CtBake *out);
+CT_API int ct_bake_trace_more(CtHandle h, CtBake b, uint32_t samples);
+CT_API int ct_bake_retrace(CtHandle h, CtBake b, uint32_t samples);   /* after ct_set_light: from sample 1, into a second table, then swap */
+CT_API int ct_bake_trace_info(CtBake b, CtBakeTraceInfo *out);
+/* 3 * Nphi * Nc floats, [j][k][xyz]; any kind of bake.  count must equal that number. */
+CT_API int ct_bake_directions(CtBake b, float *directions_host_out, size_t count);
+
 /* ct_network_render_subframe / _accumulate / _shard_subframe / _shard_accumulate with the table in the network's place. */
 CT_API int ct_baked_render_subframe(CtHandle h, CtBake b, const CtNetworkRender *p, uint32_t subframe_id, float *frame_rgba_dev);
 CT_API int ct_baked_render_accumulate(CtHandle h, CtBake b, const CtNetworkRender *p, uint32_t first_subframe_id, uint32_t count);

@@ -1,0 +1,77 @@
+#!/usr/bin/env python3
+"""What a traced bake (ct_bake_traced) costs and how close its pictures come to the path tracer's: a procedural
+cloud, the default pose, a compact traced bake per grid (g^3 x --azimuths x --cosines) and sample count.  One JSON line each:
+  the table's size, the active-node share, trace_ms and fold_ms (CtBakeTraceInfo), the bake's wall ms and paths per second
+  (paths / trace_ms);
+  the baked subframe's GPU ms (ct_debug_baked_render_time);
+  the relative L2, over the pixels that have a record in one of the subframes, between the mean of
+  baked_render_accumulate(direct=True) on the traced bake and the mode-0 path-traced mean of the same --subframes subframes;
+  beside it the same distance between two path-traced means over disjoint subframe ranges (1 .. S and S + 1 .. 2 S): the noise
+  floor a picture of S subframes cannot be told from.
+Needs a GPU.  No threshold: resolution and samples are the user's trade.
+    python tools/traced_bake_time.py [--volume 256] [--size 512] [--subframes 16] [--grids 16 32] [--azimuths 8] [--cosines 4]
+                                     [--samples 4 16] [--estimator march|delta] [--kind compact|sparse|dense]"""
+import argparse, json, statistics, sys, time
+from pathlib import Path
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+
+
+def rel_l2(a, b, where):
+    import numpy as np
+    a, b = a[where].astype(np.float64), b[where].astype(np.float64)
+    den = (b ** 2).sum()
+    return float(np.sqrt(((a - b) ** 2).sum() / den)) if den > 0 else None
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--volume", type=int, default=256)
+    ap.add_argument("--size", type=int, default=512)
+    ap.add_argument("--subframes", type=int, default=16)
+    ap.add_argument("--grids", type=int, nargs="+", default=[16, 32])
+    ap.add_argument("--azimuths", type=int, default=8)
+    ap.add_argument("--cosines", type=int, default=4)
+    ap.add_argument("--samples", type=int, nargs="+", default=[4, 16])
+    ap.add_argument("--estimator", choices=["march", "delta"], default="march")
+    ap.add_argument("--kind", choices=["compact", "sparse", "dense"], default="compact")
+    a = ap.parse_args()
+    import numpy as np
+    import torch  # noqa: F401  (before the library: descriptor_frame allocates through it)
+    import deepestscatter_amd as ds
+    S = a.subframes
+    tr = ds.CloudTracer(ds.make_procedural_cloud(a.volume), width=a.size, height=a.size, estimator=0 if a.estimator == "march" else 1)
+    # the path tracer's two means, and the pixels with a record
+    tr.render_accumulate(1, S)
+    first = tr.mean()[..., :3].astype(np.float64)
+    tr.render_accumulate(S + 1, S)
+    second = 2.0 * tr.mean()[..., :3].astype(np.float64) - first          # the mean of subframes S + 1 .. 2 S
+    lit = np.zeros(a.size * a.size, bool)
+    for sid in range(1, S + 1):
+        lit[tr.descriptor_frame(sid)[3].cpu().numpy()] = True
+    lit = lit.reshape(a.size, a.size)
+    common = {"volume": a.volume, "frame": [a.size, a.size], "estimator": a.estimator, "kind": a.kind, "subframes": S,
+              "pixels_with_a_record": int(lit.sum()),
+              "relative_l2_of_two_path_traced_means": rel_l2(second, first, lit)}
+    kw = {"compact": a.kind == "compact", "sparse": a.kind == "sparse"}
+    for g in a.grids:
+        for samples in a.samples:
+            t0 = time.perf_counter()
+            bake = tr.traced_bake((g, g, g), a.azimuths, a.cosines, samples, **kw)
+            wall = (time.perf_counter() - t0) * 1e3
+            ti, sp, st = bake.trace_info(), bake.sparse_info, bake.storage_info
+            gpu = []
+            for _ in range(6):                                            # (the first subframe of a fresh table reads it cold)
+                tr.baked_render_subframe(bake, 1, out=False, direct=True)
+                gpu.append(tr.baked_render_time())
+            tr.reset()
+            tr.baked_render_accumulate(bake, 1, S, direct=True)
+            got = tr.mean()[..., :3].astype(np.float64)
+            print(json.dumps({"route": "ct_bake_traced", **common, "grid": [g, g, g, a.azimuths, a.cosines], "samples": samples,
+                              "nodes": sp["nodes"], "active_nodes": sp["active_nodes"], "active_share": sp["active_nodes"] / sp["nodes"],
+                              "table_bytes": st["table_bytes"], "paths": ti["paths"], "trace_ms": ti["trace_ms"], "fold_ms": ti["fold_ms"],
+                              "bake_wall_ms": wall, "paths_per_second": ti["paths"] / ti["trace_ms"] * 1e3 if ti["trace_ms"] > 0 else None,
+                              "baked_subframe_gpu_ms": statistics.median(gpu[1:]),
+                              "relative_l2_against_the_path_traced_mean": rel_l2(got, first, lit)}), flush=True)
+            bake.close()
+    tr.close()

@@ -695,6 +695,20 @@ class CloudTracer:
         names = ["armed", "checks", "violations", "samples_without_alpha_1", "dealt", "resumed", "written", "suspended"]
         return {n: int(v) for n, v in zip(names, out)}
 
+    def debug_pixel_classes(self) -> dict:
+        """This shard's pixels of the current pose by class, and the lookups of one sample of every through pixel, summed
+        (ct_debug_pixel_classes)."""
+        out = np.zeros(4, np.uint64)
+        check(self.L.ct_debug_pixel_classes(self.h, _p(out)), self.h)
+        return {n: int(v) for n, v in zip(["misses", "listed", "through", "through_steps"], out)}
+
+    def debug_pixel_class_plane(self) -> tuple[np.ndarray, np.ndarray]:
+        """(class uint8 [H, W], steps uint32 [H, W]) of every pixel of the frame (ct_debug_pixel_class_plane)."""
+        out = np.zeros(self.params.width * self.params.height, np.uint32)
+        check(self.L.ct_debug_pixel_class_plane(self.h, _p(out), out.size), self.h)
+        out = out.reshape(self.params.height, self.params.width)
+        return (out >> 30).astype(np.uint8), out & np.uint32(0x3FFFFFFF)
+
     def debug_memory(self) -> dict:
         """Bytes of the volume representations on the device (ct_debug_memory)."""
         out = np.zeros(8, np.uint64)

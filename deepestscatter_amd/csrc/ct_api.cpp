@@ -1307,26 +1307,41 @@ static bool start_records(CtHandle h)
     return h->scene.estimator == CT_EST_MARCH && !(h->scene.flags & CT_FLAG_SIMPLE_KERNEL) && knob_flag(h->tune.START_RECORDS, true);
 }
 
-// Primary rays of the current pose + the list of this shard's pixels that hit the box, in
-// tile-Morton order, cut into groups of 64 (one wave's worth).
+// Are through pixels settled without a path?  Only where every sample of a pixel takes the pre-walked prefix and runs the
+// decisive iteration itself: MARCH's persistent kernel, not mode 1 (the direction is drawn first), not CT_NO_ADVANCE; and not
+// at max_depth == 1 outside mode 2, where a sample is capped before its first flight (no lookups, depth_capped + 1).
+// CT_THROUGH_PIXELS=0: every box-hitting pixel is listed (A/B, tests).
+static bool through_on(CtHandle h)
+{
+    return h->scene.estimator == CT_EST_MARCH && !(h->scene.flags & CT_FLAG_SIMPLE_KERNEL) && h->scene.mode != 1 && !h->no_advance &&
+           (h->scene.max_depth > 1 || h->scene.mode == 2) && knob_flag(h->tune.THROUGH_PIXELS, true);
+}
+
+// Primary rays of the current pose + the list of this shard's pixels whose samples need a path (they hit the box and are
+// no through pixels), in tile-Morton order, cut into groups of 64 (one wave's worth).
 // ... and, from those, the start record of every slot of the list.
 static int rebuild_queue(CtHandle h)
 {
     TracePhase trace(h, "rebuild_queue");
     const uint32_t W = h->scene.width, H = h->scene.height;
     const size_t pixels = (size_t)W * H;
+    const bool through = through_on(h);
     HIPCHK(h, launch_primary_rays(h->dev, h->d_primary, h->stream));
     if (h->scene.estimator == CT_EST_DELTA) {
         HIPCHK(h, launch_primary_advance_delta(h->dev, h->d_primary, h->d_advance, h->stream));
     } else {
-        HIPCHK(h, launch_primary_advance(h->dev, h->d_primary, h->d_advance, h->stream));
+        HIPCHK(h, launch_primary_advance(h->dev, h->d_primary, h->d_advance, through, h->stream));
     }
+    // (the class plane and, behind it, the word of the through pixels' steps: one download)
+    const size_t sum_at = (pixels + 7u) & ~(size_t)7u, plane_bytes = sum_at + sizeof(unsigned long long);
     if (!h->d_hit) {
-        HIPCHK(h, dmalloc(&h->d_hit, pixels));
-        HIPCHK(h, hipHostMalloc((void **)&h->hit_host, pixels, hipHostMallocDefault));
+        HIPCHK(h, dmalloc(&h->d_hit, plane_bytes));
+        HIPCHK(h, hipHostMalloc((void **)&h->hit_host, plane_bytes, hipHostMallocDefault));
     }
-    HIPCHK(h, launch_hit_flags(h->d_primary, h->d_hit, (uint32_t)pixels, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->hit_host, h->d_hit, pixels, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->d_hit + sum_at, 0, sizeof(unsigned long long), h->stream));
+    HIPCHK(h, launch_hit_flags(h->d_primary, through ? h->d_advance : nullptr, h->d_hit, (uint32_t)pixels, W, h->scene.shard_index,
+                               h->scene.shard_count, (unsigned long long *)(h->d_hit + sum_at), h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->hit_host, h->d_hit, plane_bytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     const uint8_t *hit = h->hit_host;
     const uint32_t tiles_x = h->dev.tiles_x, tiles_y = h->dev.tiles_y;
@@ -1341,7 +1356,7 @@ static int rebuild_queue(CtHandle h)
     std::sort(tiles.begin(), tiles.end());
     std::vector<uint32_t> list;
     list.reserve(pixels / std::max(1u, h->scene.shard_count) + 64);
-    uint64_t own = 0;
+    uint64_t own = 0, through_pixels = 0;
     for (const auto &t : tiles) {
         const uint32_t ty = t.second / tiles_x, tx = t.second - ty * tiles_x;
         for (uint32_t l = 0; l < 64; l++) {
@@ -1349,14 +1364,24 @@ static int rebuild_queue(CtHandle h)
             if (x < W && y < H) {
                 own++;
                 const uint32_t p = y * W + x;
-                if (hit[p]) {
+                if (hit[p] == 1u) {
                     list.push_back(p);
+                } else if (hit[p] == 2u) {
+                    through_pixels++;
                 }
             }
         }
     }
     h->own_pixels = own;
-    h->hit_pixels = list.size();
+    h->listed_pixels = list.size();
+    h->through_pixels = through_pixels;
+    h->hit_pixels = h->listed_pixels + through_pixels;
+    h->miss_pixels = own - h->hit_pixels;
+    {
+        unsigned long long steps = 0;
+        memcpy(&steps, h->hit_host + sum_at, sizeof steps);
+        h->through_steps = steps;
+    }
     while (list.size() % 64 != 0) {
         list.push_back(0xffffffffu);
     }
@@ -1863,7 +1888,7 @@ static int enqueue_accumulate(CtHandle h, CtHandle_::Slot &sl, const float4 *fra
         } else {
             HIPCHK(h, launch_accumulate_list(frames + (size_t)off * frame_stride(h), (uint32_t)frame_stride(h), h->d_pixels, sl.groups * 64u,
                                              h->n_chunks <= 1 ? nullptr : h->d_group_order, sl.rank_base,
-                                             sl.with_misses, h->d_primary, h->d_mean, h->d_m2, next, piece, h->scene.width,
+                                             sl.with_misses, h->d_hit, h->d_mean, h->d_m2, next, piece, h->scene.width,
                                              h->scene.height, h->scene.shard_index, h->scene.shard_count, h->d_counters + 8, frozen,
                                              h->stream));
         }
@@ -2077,10 +2102,14 @@ static int submit_batch(CtHandle h, int slot, float4 *dense_frames, uint32_t fir
         // (every group is full but the last one of the pixel list, which padding completes; it sits somewhere in the job order)
         uint64_t chunk_hits = 0;
         for (uint32_t r = rank_base; r < rank_base + chunk_n; r++) {
-            chunk_hits += (h->job_order[r] + 1u == h->n_groups) ? 64u - (uint64_t)((uint64_t)h->n_groups * 64u - h->hit_pixels) : 64u;
+            chunk_hits += (h->job_order[r] + 1u == h->n_groups) ? 64u - (uint64_t)((uint64_t)h->n_groups * 64u - h->listed_pixels) : 64u;
         }
         if (chunk == 0) {
             h->host_paths += h->own_pixels * S;
+            // (the samples of through pixels, which no kernel runs: a box hit and the pixel's lookups each)
+            h->host_hits += h->through_pixels * S;
+            h->host_lookups += h->through_steps * S;
+            h->host_settled += h->through_pixels * S;
         }
         h->host_hits += chunk_hits * S;
         h->iv_expected_dealt += chunk_hits * S;
@@ -2810,6 +2839,7 @@ extern "C" int ct_reset(CtHandle h)
     h->render_ms = h->accum_ms = 0;
     h->launches = 0;
     h->host_paths = h->host_hits = 0;
+    h->host_lookups = h->host_settled = 0;
     h->iv_expected_dealt = 0;
     return CT_OK;
 }
@@ -3045,7 +3075,7 @@ extern "C" int ct_counters(CtHandle h, CtCounters *out)
     HIPCHK(h, hipStreamSynchronize(h->stream));
     out->paths = c[0] + h->host_paths;
     out->box_hits = c[1] + h->host_hits;
-    out->density_lookups = c[2];
+    out->density_lookups = c[2] + h->host_lookups;
     out->inscatter_lookups = c[3];
     out->scatter_events = c[4];
     out->depth_capped = c[5];
@@ -3080,10 +3110,69 @@ extern "C" int ct_debug_invariants(CtHandle h, uint64_t out[8])
     out[1] = h->iv_checks;
     out[2] = h->iv_violations;
     out[3] = bad;
-    out[4] = iv[0];
+    // (dealt and written count every sample of a box-hitting pixel, whoever settles it: those of through pixels are the host's)
+    const uint64_t settled = h->debug_invariants ? h->host_settled : 0;
+    out[4] = iv[0] + settled;
     out[5] = iv[1];
-    out[6] = iv[2];
+    out[6] = iv[2] + settled;
     out[7] = iv[3];
+    return CT_OK;
+}
+
+extern "C" int ct_debug_pixel_classes(CtHandle h, uint64_t out[4])
+{
+    NEED(h);
+    if (!out) {
+        return fail(h, CT_E_INVAL, "out is NULL");
+    }
+    if (!h->camera_set) {
+        return fail(h, CT_E_STATE, "ct_set_camera has not been called");
+    }
+    if (h->scene.flags & CT_FLAG_SIMPLE_KERNEL) {
+        return fail(h, CT_E_INVAL, "ct_debug_pixel_classes: the one-thread-per-pixel kernel keeps no pixel list");
+    }
+    if (h->queue_dirty) {   // (the classes of the current pose, rendered or not)
+        int rc = flush(h);
+        discard_ahead(h);
+        if (rc == CT_OK) {
+            rc = rebuild_queue(h);
+        }
+        if (rc != CT_OK) {
+            return rc;
+        }
+    }
+    out[0] = h->miss_pixels;
+    out[1] = h->listed_pixels;
+    out[2] = h->through_pixels;
+    out[3] = h->through_steps;
+    return CT_OK;
+}
+
+extern "C" int ct_debug_pixel_class_plane(CtHandle h, uint32_t *out, size_t count)
+{
+    NEED(h);
+    const size_t pixels = (size_t)h->scene.width * h->scene.height;
+    if (!out || count != pixels) {
+        return fail(h, CT_E_INVAL, "ct_debug_pixel_class_plane: need room for %zu pixels", pixels);
+    }
+    uint64_t counts[4];
+    const int rc = ct_debug_pixel_classes(h, counts);   // (brings the pose's classes up to date)
+    if (rc != CT_OK) {
+        return rc;
+    }
+    std::vector<float4> advance(through_on(h) ? pixels : 0);   // (class 2 appears on no other handle)
+    if (!advance.empty()) {
+        HIPCHK(h, hipMemcpy(advance.data(), h->d_advance, pixels * sizeof(float4), hipMemcpyDeviceToHost));
+    }
+    for (size_t p = 0; p < pixels; p++) {
+        const uint32_t cls = h->hit_host[p];
+        uint32_t steps = 0;
+        if (cls == 2u) {
+            memcpy(&steps, &advance[p].w, sizeof steps);
+            steps &= 0x3fffffffu;
+        }
+        out[p] = cls << 30 | steps;
+    }
     return CT_OK;
 }
 

@@ -26,7 +26,7 @@ struct Knob {
     const char *get() const { return is_set ? text.c_str() : nullptr; }
     explicit operator bool() const { return is_set; }
 };
-#define CT_KNOBS(X) X(BAKE_MASK_BYTES) X(BAKE_TRACE_RESULTS) X(BURST_IDLE) X(BURST_MARCH_MIN) X(BURST_SCATTER) X(CHUNK_INTERLEAVE) X(CHUNK_MORTON) X(CONTINUATION) X(DEBUG_INVARIANTS) X(DELTA_INTERIOR) X(DELTA_NEE) X(EXCHANGE) X(HAND_ON_JOBS) X(HINT_PERIOD) X(JOB_MAX) X(JOB_WORK) X(MARCH_BURST) X(MAX_AGE) X(NEE_CACHE) X(NET_DESC_RECORDS) X(NO_ADVANCE) X(POINT_BLOCKS_PER_CU) X(POINT_ORDER) X(REGEN_MIN) X(RENDER_AHEAD) X(SCATTER_MIN) X(SCATTER_RATIO) X(SCRATCH_GIB) X(SCRATCH_MIB) X(SERPENTINE) X(SHARED_DEPTH) X(SPARSE) X(STATS) X(TAIL_BURST) X(TILE_ORDER) X(TIMELINE) X(TRACE) X(TUNE_SUBFRAMES) X(XCD_QUEUES) X(XCD_QUEUES_UNTUNED) X(XCD_REGIONS) X(BLOCKS_PER_CU) X(WIDE_OFFSETS) X(START_RECORDS)
+#define CT_KNOBS(X) X(BAKE_MASK_BYTES) X(BAKE_TRACE_RESULTS) X(BURST_IDLE) X(BURST_MARCH_MIN) X(BURST_SCATTER) X(CHUNK_INTERLEAVE) X(CHUNK_MORTON) X(CONTINUATION) X(DEBUG_INVARIANTS) X(DELTA_INTERIOR) X(DELTA_NEE) X(EXCHANGE) X(HAND_ON_JOBS) X(HINT_PERIOD) X(JOB_MAX) X(JOB_WORK) X(MARCH_BURST) X(MAX_AGE) X(NEE_CACHE) X(NET_DESC_RECORDS) X(NO_ADVANCE) X(POINT_BLOCKS_PER_CU) X(POINT_ORDER) X(REGEN_MIN) X(RENDER_AHEAD) X(SCATTER_MIN) X(SCATTER_RATIO) X(SCRATCH_GIB) X(SCRATCH_MIB) X(SERPENTINE) X(SHARED_DEPTH) X(SPARSE) X(STATS) X(TAIL_BURST) X(TILE_ORDER) X(TIMELINE) X(TRACE) X(TUNE_SUBFRAMES) X(XCD_QUEUES) X(XCD_QUEUES_UNTUNED) X(XCD_REGIONS) X(BLOCKS_PER_CU) X(WIDE_OFFSETS) X(START_RECORDS) X(THROUGH_PIXELS)
 struct CtTuning {
 #define X(name) Knob name;
     CT_KNOBS(X)
@@ -158,7 +158,9 @@ struct CtHandle_ {
     float4 *d_advance = nullptr;      // per pixel: pre-walked prefix of the primary march (MARCH estimator)
     uint32_t *d_pixels = nullptr;     // this shard's box-hitting pixels, padded to groups of 64
     float4 *d_start = nullptr;        // ... and what a sample of each of those slots starts from (BatchArgs::start; MARCH, CT_START_RECORDS=0: none)
-    uint8_t *d_hit = nullptr, *hit_host = nullptr;   // per pixel: the primary ray hits the box (device; pinned host copy)
+    // per pixel: its class, 0 = misses the box, 1 = listed, 2 = through (hit_flags_kernel; device, pinned host copy); behind
+    // the plane, at the next multiple of 8 bytes, one 64-bit word: the lookups of one sample of every through pixel, summed
+    uint8_t *d_hit = nullptr, *hit_host = nullptr;
     uint32_t *d_cost = nullptr;       // measured per group: [0,n) sum of path costs, [n,2n) deepest path
     uint32_t *d_touched[2] = { nullptr, nullptr };   // ct_debug_track_lines: one bit per line of the density / shadow arrays
     size_t touched_lines[2] = { 0, 0 };
@@ -187,7 +189,12 @@ struct CtHandle_ {
     uint32_t job_max = 16;
     float job_work = 16.f;
     uint32_t q_begin[kQueues + 2] = {}; // job ranges of the per-XCD queues + the shared one
-    uint64_t own_pixels = 0, hit_pixels = 0;
+    // This shard's pixels; those whose primary ray hits the box (what short_batch and the other heuristics are tuned on) =
+    // listed_pixels (in the pixel list: their samples are rendered) + through_pixels (the ray crosses the box without meeting
+    // a non-zero footprint: every sample is (0,0,0,1) after through_steps / through_pixels lookups on average, settled by the
+    // host's counters and the accumulate kernel's constant blocks; 0 unless through_on())
+    uint64_t own_pixels = 0, hit_pixels = 0, listed_pixels = 0, through_pixels = 0, through_steps = 0;
+    uint64_t miss_pixels = 0;            // own_pixels - hit_pixels (ct_debug_pixel_classes)
     bool queue_dirty = true, order_tuned = false;
     bool no_advance = false;             // CT_NO_ADVANCE=1: samples start at the box face (A/B)
     bool queues_enabled = false;         // per-XCD regions (CT_XCD_QUEUES=1; default: one global list)
@@ -203,6 +210,8 @@ struct CtHandle_ {
     std::vector<float> group_depth;      // measured mean path cost per group (0 until tuned), in the
                                          // units of BatchArgs::cost
     unsigned long long host_paths = 0, host_hits = 0; // paths / box hits of the persistent path
+    unsigned long long host_lookups = 0;  // density lookups of the samples of through pixels, which no kernel marches
+    unsigned long long host_settled = 0;  // ... and their number (ct_debug_invariants: dealt and written include them)
     uint32_t *d_queue = nullptr;
     unsigned long long *d_counters = nullptr; // kCounterCount + 1 (unconverged) + kStatCount
     float *d_colsum = nullptr, *d_avg = nullptr;

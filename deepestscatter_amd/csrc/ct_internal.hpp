@@ -162,8 +162,9 @@ hipError_t launch_primary_rays(const DevScene &sc, float4 *primary, hipStream_t 
 hipError_t launch_cost_reduce(const uint2 *cost_plane, uint32_t frame_stride, uint32_t S, uint32_t n_groups_in_chunk,
                               const uint32_t *group_order, uint32_t rank_base, uint32_t *cost_sum, uint32_t *cost_deepest,
                               hipStream_t stream);
-hipError_t launch_hit_flags(const float4 *primary, uint8_t *flags, uint32_t pixels, hipStream_t stream);
-hipError_t launch_primary_advance(const DevScene &sc, const float4 *primary, float4 *advance, hipStream_t stream);
+hipError_t launch_hit_flags(const float4 *primary, const float4 *advance, uint8_t *flags, uint32_t pixels, uint32_t width,
+                            uint32_t shard_index, uint32_t shard_count, unsigned long long *through_steps, hipStream_t stream);
+hipError_t launch_primary_advance(const DevScene &sc, const float4 *primary, float4 *advance, bool classify, hipStream_t stream);
 hipError_t launch_start_records(const DevScene &sc, const uint32_t *pixels, uint32_t slots, const float4 *primary,
                                 const float4 *advance, float4 *start, hipStream_t stream);
 hipError_t launch_primary_advance_delta(const DevScene &sc, const float4 *primary, float4 *advance, hipStream_t stream);
@@ -187,7 +188,7 @@ hipError_t launch_accumulate_batch(const float4 *frames, float4 *mean, float4 *m
                                    hipStream_t stream);
 hipError_t launch_accumulate_list(const float4 *frames, uint32_t frame_stride, const uint32_t *pixels,
                                   uint32_t n_entries, const uint32_t *group_order, uint32_t rank_base, bool with_misses,
-                                  const float4 *primary, float4 *mean, float4 *m2,
+                                  const uint8_t *pixel_class, float4 *mean, float4 *m2,
                                   uint32_t first_subframe, uint32_t S, uint32_t width, uint32_t height,
                                   uint32_t shard_index, uint32_t shard_count, unsigned long long *bad_samples,
                                   const uint32_t *frozen, hipStream_t stream);

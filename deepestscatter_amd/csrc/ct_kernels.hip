@@ -779,13 +779,42 @@ hipError_t launch_primary_rays(const DevScene &sc, float4 *primary, hipStream_t 
     return hipGetLastError();
 }
 
-// One byte per pixel: does the primary ray hit the box?  (What the host needs of the 32 B per pixel of `primary` to build
-// the pixel list of a new pose; fetching the rays themselves was 32 MB over PCIe into pageable memory, 10 of the 13 ms.)
-__global__ __launch_bounds__(256) void hit_flags_kernel(const float4 *__restrict__ primary, uint8_t *__restrict__ flags, uint32_t pixels)
+// One byte per pixel, the pixel's class: 0 = the primary ray misses the box, 1 = listed (its samples are rendered), 2 = a
+// through pixel (primary_advance_kernel: the ray crosses the box without meeting a non-zero footprint, so every sample of it
+// is (0,0,0,1) after the same number of lookups and none is rendered).  (What the host needs of the 32 B per pixel of
+// `primary` to build the pixel list of a new pose; fetching the rays themselves was 32 MB over PCIe into pageable memory, 10
+// of the 13 ms.)  advance == NULL: no pixel is classified as through (DELTA, the simple kernel, samples without a prefix).
+// through_steps: the lookups of one sample of each of this shard's through pixels, summed -- one 64-bit word, cleared by
+// the caller, so that the host needs no second plane.
+__global__ __launch_bounds__(256) void hit_flags_kernel(const float4 *__restrict__ primary, const float4 *__restrict__ advance,
+                                                        uint8_t *__restrict__ flags, uint32_t pixels, uint32_t width,
+                                                        uint32_t shard_index, uint32_t shard_count,
+                                                        unsigned long long *__restrict__ through_steps)
 {
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t steps = 0;
     if (p < pixels) {
-        flags[p] = primary[2 * (size_t)p].w != 0.f ? 1u : 0u;
+        uint8_t cls = primary[2 * (size_t)p].w != 0.f ? 1u : 0u;
+        if (cls != 0u && advance) {
+            const uint32_t bits = __float_as_uint(advance[p].w);
+            if ((bits & 0x40000000u) != 0u) {
+                cls = 2u;
+                const uint32_t x = p % width, y = p / width;
+                if (tile_owner(x / kTile, y / kTile, shard_count) == shard_index) {
+                    steps = bits & 0x3fffffffu;
+                }
+            }
+        }
+        flags[p] = cls;
+    }
+    if (advance) {   // (uniform; a wave's sum stays below 2^30: 64 lanes of less than 2^24 steps)
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            steps += __shfl_xor(steps, off);
+        }
+        if ((threadIdx.x & 63u) == 0u && steps != 0u) {
+            atomicAdd(through_steps, (unsigned long long)steps);
+        }
     }
 }
 
@@ -825,9 +854,11 @@ hipError_t launch_cost_reduce(const uint2 *cost_plane, uint32_t frame_stride, ui
     return hipGetLastError();
 }
 
-hipError_t launch_hit_flags(const float4 *primary, uint8_t *flags, uint32_t pixels, hipStream_t stream)
+hipError_t launch_hit_flags(const float4 *primary, const float4 *advance, uint8_t *flags, uint32_t pixels, uint32_t width,
+                            uint32_t shard_index, uint32_t shard_count, unsigned long long *through_steps, hipStream_t stream)
 {
-    hipLaunchKernelGGL(hit_flags_kernel, dim3((pixels + 255u) / 256u), dim3(256), 0, stream, primary, flags, pixels);
+    hipLaunchKernelGGL(hit_flags_kernel, dim3((pixels + 255u) / 256u), dim3(256), 0, stream, primary, advance, flags, pixels, width,
+                       shard_index, shard_count, through_steps);
     return hipGetLastError();
 }
 
@@ -1276,9 +1307,15 @@ hipError_t launch_inscatter(const DevScene &sc, uint8_t *out, uint32_t zero_face
 // the march phase's operations, and a sample starts at the state recorded BEFORE the decisive
 // iteration (the one whose fetch is non-zero or leaves the box), which it then executes itself:
 // advance[p] = (position, bits: steps done so far | clearance << 24).
+// classify: the kernel knows why its walk ended.  Where the decisive iteration fetched a zero footprint outside the box, a
+// sample that starts from the record takes that one iteration, leaves the box with T = 1 and nothing gathered and writes
+// (0,0,0,1), whatever its random numbers: a THROUGH pixel.  Its record's bits are then 0x40000000 | the steps at the break --
+// prefix, replayed skips and the last step, i.e. the density lookups of one of its samples -- which hit_flags_kernel turns
+// into the pixel's class and a sum; no sample of such a pixel is ever started, so nobody reads the record as a prefix.  (A
+// walk that one of the loop's guards ends is not classified: its pixel is listed.)
 template <bool SPARSE>
 __global__ __launch_bounds__(256) void primary_advance_kernel(DevScene sc, const float4 *__restrict__ primary,
-                                                              float4 *__restrict__ advance)
+                                                              float4 *__restrict__ advance, bool classify)
 {
     const uint32_t x = blockIdx.x * 32u + (threadIdx.x & 31u);
     const uint32_t y = blockIdx.y * 8u + (threadIdx.x >> 5);
@@ -1309,6 +1346,9 @@ __global__ __launch_bounds__(256) void primary_advance_kernel(DevScene sc, const
             const uint2 cell = fetch_cell_m<SPARSE>(sc, pos, meta);
             dfree = meta & 0x3fu;
             if ((cell.x | cell.y) != 0u || ((meta & 0x80u) == 0u && !in_box(sc, pos))) {
+                if (classify && (cell.x | cell.y) == 0u) {
+                    start_bits = 0x40000000u | steps;
+                }
                 break;
             }
         }
@@ -1316,13 +1356,13 @@ __global__ __launch_bounds__(256) void primary_advance_kernel(DevScene sc, const
     advance[p] = make_float4(start.x, start.y, start.z, __uint_as_float(start_bits));
 }
 
-hipError_t launch_primary_advance(const DevScene &sc, const float4 *primary, float4 *advance, hipStream_t stream)
+hipError_t launch_primary_advance(const DevScene &sc, const float4 *primary, float4 *advance, bool classify, hipStream_t stream)
 {
     const dim3 grid((sc.width + 31) / 32, (sc.height + 7) / 8), block(256);
     if (sc.m_rows) {
-        hipLaunchKernelGGL(primary_advance_kernel<true>, grid, block, 0, stream, sc, primary, advance);
+        hipLaunchKernelGGL(primary_advance_kernel<true>, grid, block, 0, stream, sc, primary, advance, classify);
     } else {
-        hipLaunchKernelGGL(primary_advance_kernel<false>, grid, block, 0, stream, sc, primary, advance);
+        hipLaunchKernelGGL(primary_advance_kernel<false>, grid, block, 0, stream, sc, primary, advance, classify);
     }
     return hipGetLastError();
 }
@@ -4022,8 +4062,9 @@ hipError_t launch_accumulate_batch(const float4 *frames, float4 *mean, float4 *m
 }
 
 // Compact form: one thread per entry of the pixel list (this shard's box-hitting pixels) in the first `list_blocks`
-// blocks; behind them (with_misses) one thread per pixel of the frame for this shard's pixels whose primary ray misses the
-// box: those are never rendered, their sample is (0,0,0,1) every subframe (empty miss program, progressive.cu:44-46).  One
+// blocks; behind them (with_misses) one thread per pixel of the frame for this shard's pixels that are not listed
+// (pixel_class, hit_flags_kernel): their primary ray misses the box (empty miss program, progressive.cu:44-46) or crosses it
+// without meeting the cloud (through pixels), so they are never rendered and their sample is (0,0,0,1) every subframe.  One
 // dispatch for both: a display update of 10 subframes pays every dispatch it makes.
 __global__ __launch_bounds__(256) void accumulate_list_kernel(const float4 *__restrict__ frames, uint32_t frame_stride,
                                                               const uint32_t *__restrict__ pixels, uint32_t n_entries,
@@ -4031,7 +4072,7 @@ __global__ __launch_bounds__(256) void accumulate_list_kernel(const float4 *__re
                                                               float4 *__restrict__ mean, float4 *__restrict__ m2,
                                                               uint32_t first_subframe, uint32_t S,
                                                               unsigned long long *__restrict__ bad_samples,
-                                                              uint32_t list_blocks, const float4 *__restrict__ primary,
+                                                              uint32_t list_blocks, const uint8_t *__restrict__ pixel_class,
                                                               uint32_t width, uint32_t height, uint32_t shard_index,
                                                               uint32_t shard_count, const uint32_t *__restrict__ frozen)
 {
@@ -4049,7 +4090,7 @@ __global__ __launch_bounds__(256) void accumulate_list_kernel(const float4 *__re
             return;
         }
         const size_t pix = (size_t)y * width + x;
-        if (primary[2 * pix].w != 0.f) {
+        if (pixel_class[pix] == 1u) {   // (listed: above.  Misses and through pixels: the same sample every subframe)
             return;
         }
         float4 mu = mean[pix], var = m2[pix];
@@ -4102,7 +4143,7 @@ __global__ __launch_bounds__(256) void accumulate_list_kernel(const float4 *__re
 
 hipError_t launch_accumulate_list(const float4 *frames, uint32_t frame_stride, const uint32_t *pixels,
                                   uint32_t n_entries, const uint32_t *group_order, uint32_t rank_base, bool with_misses,
-                                  const float4 *primary, float4 *mean, float4 *m2,
+                                  const uint8_t *pixel_class, float4 *mean, float4 *m2,
                                   uint32_t first_subframe, uint32_t S, uint32_t width, uint32_t height,
                                   uint32_t shard_index, uint32_t shard_count, unsigned long long *bad_samples,
                                   const uint32_t *frozen, hipStream_t stream)
@@ -4113,7 +4154,7 @@ hipError_t launch_accumulate_list(const float4 *frames, uint32_t frame_stride, c
     if (list_blocks + miss_blocks != 0u) {
         hipLaunchKernelGGL(accumulate_list_kernel, dim3(list_blocks + miss_blocks), dim3(256), 0, stream, frames,
                            frame_stride, pixels, n_entries, group_order, rank_base, mean, m2, first_subframe, S, bad_samples,
-                           list_blocks, primary, width, height, shard_index, shard_count, frozen);
+                           list_blocks, pixel_class, width, height, shard_index, shard_count, frozen);
     }
     return hipGetLastError();
 }

@@ -905,6 +905,20 @@ CT_API int ct_debug_suspended(CtHandle h, uint64_t *paths_out);
  * (0 unless out[0]). */
 CT_API int ct_debug_invariants(CtHandle h, uint64_t out[8]);
 
+/* The pixels of this shard under the current pose, by class (diagnostic): out[0] = the primary ray misses the box,
+ * out[1] = listed (the estimator runs a path for every sample), out[2] = through pixels: the ray crosses the box without
+ * meeting a non-zero density footprint, so every sample is (0,0,0,1) after the same number of lookups and none is
+ * rendered -- the counters and the running mean / M2 are what rendering them would give.  out[3] = those lookups, for one
+ * sample of each through pixel, summed.  Through pixels exist for the MARCH estimator's persistent kernel in modes 0 and
+ * 2 unless CT_THROUGH_PIXELS=0 or CT_NO_ADVANCE=1 is in the environment at ct_create; otherwise out[2] = out[3] = 0 and
+ * every box-hitting pixel is listed.  Needs a camera; not for CT_FLAG_SIMPLE_KERNEL handles. */
+CT_API int ct_debug_pixel_classes(CtHandle h, uint64_t out[4]);
+
+/* The same per pixel of the whole frame (foreign shards' pixels included), out[y * width + x] = class << 30 | steps: class
+ * as above (0, 1, 2), steps = the lookups of one sample of a through pixel (0 for the other classes).  count = width *
+ * height.  Downloads the prefix plane: a diagnostic for tests, not for a render loop. */
+CT_API int ct_debug_pixel_class_plane(CtHandle h, uint32_t *out, size_t count);
+
 /* Device memory of the volume representations (bytes): out[0] raw density texture, out[1] density apron bricks,
  * out[2] shadow-volume apron bricks, out[3] march bricks if stored densely, out[4] march bricks as stored,
  * out[5] = 1 when they are stored sparsely (row extents; CT_FLAG_SPARSE_BRICKS or CT_SPARSE=1), out[6] bytes of the

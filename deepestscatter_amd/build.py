@@ -66,16 +66,11 @@ def build_cli(force: bool = False, verbose: bool = False) -> Path:
 #   exp   -DCT_EXPERIMENTS: the product plus the measured-and-rejected experiments (the two path-exchange kernels of
 #         csrc/ct_exchange.hpp; tests/test_exchange.py and the tools that A/B them)
 #   w8    the DELTA kernel as two 1024-thread blocks per CU, 8 waves per SIMD, 64 VGPRs (round-4 A/B)
-#   nofuse  both estimator kernels with a scatter phase and a march / tracking burst as separate scheduler iterations (round-4 A/B)
-#   noneeskip  the MARCH kernel without the shadow-zero NEE skip (CT_MARCH_NEE_SKIP=0)
-#   ab1..ab3   CT_ABn_FLAGS, e.g. -DCT_MARCH_REPLAY_MAX=0 / 8: the MARCH kernel's free-space replay as the former loop / with
-#         another bound per lane and burst step (default 4)
+#   ab1..ab3   CT_ABn_FLAGS, the numeric switches of the kernels, e.g. -DCT_MARCH_REPLAY_MAX=8: the MARCH kernel's free-space
+#         replay with another bound per lane and burst step (default 4)
 VARIANTS = {
     "exp": ["-DCT_EXPERIMENTS"],
     "w8": ["-DCT_DELTA_THREADS=1024", "-DCT_DELTA_WAVES=8"],
-    "nofuse": ["-DCT_DELTA_FUSE=0", "-DCT_MARCH_FUSE=0", "-DCT_DELTA_CHECK_EVERY=1"],
-    "noendmerge": ["-DCT_DELTA_END_MERGE=0"],
-    "noneeskip": ["-DCT_MARCH_NEE_SKIP=0"],   # MARCH evaluates the NEE of collisions in shadow-zero rows too (A/B)
     "ab1": os.environ.get("CT_AB1_FLAGS", "").split(),   # scratch variants for A/B runs of compile-time switches
     "ab2": os.environ.get("CT_AB2_FLAGS", "").split(),
     "ab3": os.environ.get("CT_AB3_FLAGS", "").split(),

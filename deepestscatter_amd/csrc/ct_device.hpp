@@ -185,7 +185,7 @@ struct DevScene {
     uint32_t burst_scatter; // ... this many lanes wait for the scatter phase, or ...
     uint32_t burst_idle;   // ... this many lanes are idle)
     uint32_t tail_burst;   // march steps per visit once the job queue is empty
-    uint32_t nee_cache;    // 1 = fetch_cell_cached may reuse a lane's last shadow-volume footprint (fewer than 2^25 bricks)
+    uint32_t nee_cache;    // 1 = fetch_cell_cached_raw may reuse a lane's last shadow-volume footprint (fewer than 2^25 bricks)
     float nee_reach;       // a collision in a shadow-zero row whose back-off lg / density is <= this skips its NEE (0: never;
                            // ct_api.cpp derives the flags' radius from it)
     uint32_t hint_period;  // scheduler visits between two looks at the job counter (power of two, 0 = never)
@@ -504,10 +504,12 @@ CT_DEV uint2 combine_twin(const RawCell &r)
 // free path apart, which at the reference's settings is about a texel, so the shadow-volume footprint of the next
 // event is often the one just read.  `key` = the footprint's byte offset in the brick array (0xffffffff = empty);
 // the volumes are immutable, so an entry never goes stale and may outlive the path that loaded it.
-// zero = true: the footprint is known to be all zero (a shadow-zero row): nothing is loaded, the entry stays as it was.
+// The entry holds the two RAW 8-byte words of the footprint (x, y = bytes [0, 8); z, w = bytes [25, 33)), so that a
+// fetch is nothing but the issue of its two loads: no instruction here reads their destination, hence no wait here.  The
+// caller combines the entry (combine_raw_footprint) where it needs the footprint -- a reused entry too, again each time: two
+// instructions the wave executes anyway.  (DESIGN.md 4.1 "Round 7")
 template <bool WIDE>
-CT_DEV uint2 fetch_cell_cached(const DevScene &sc, const uint8_t *bricks, f3 p, uint32_t &key, uint2 &cached, bool &reused,
-                               bool zero = false)
+CT_DEV void fetch_cell_cached_raw(const DevScene &sc, const uint8_t *bricks, f3 p, uint32_t &key, uint4 &raw, bool &reused)
 {
     const float fx = fmaf(p.x, sc.sx, -0.5f), fy = fmaf(p.y, sc.sy, -0.5f), fz = fmaf(p.z, sc.sz, -0.5f);
     const uint32_t x = (uint32_t)(floor_to_int(fx) + sc.brick_bias), y = (uint32_t)(floor_to_int(fy) + sc.brick_bias),
@@ -516,32 +518,7 @@ CT_DEV uint2 fetch_cell_cached(const DevScene &sc, const uint8_t *bricks, f3 p, 
     const uint32_t local = __umul24(z & 3u, 25u) + __umul24(y & 3u, 5u) + (x & 3u);
     const uint32_t off = (brick << 7) | local;   // unique while there are fewer than 2^25 bricks: DevScene::nee_cache
     reused = sc.nee_cache != 0u && off == key;
-    if (!reused && !zero) {
-        uint2 a, c;
-        load_footprint_pair<WIDE>(bricks, brick, local, a, c);
-        cached.x = __builtin_amdgcn_perm(a.y, a.x, 0x06050100u);
-        cached.y = __builtin_amdgcn_perm(c.y, c.x, 0x06050100u);
-        key = off;
-    }
-    return zero ? make_uint2(0u, 0u) : cached;
-}
-
-// The same cache holding the two RAW 8-byte words of the footprint (x, y = bytes [0, 8); z, w = bytes [25, 33)), so that a
-// fetch is nothing but the issue of its two loads: no instruction here reads their destination, hence no wait here.  The
-// caller combines the entry (combine_raw_footprint) where it needs the footprint -- a reused entry too, again each time: two
-// instructions the wave executes anyway.  (CT_MARCH_NEE_ASYNC, DESIGN.md 4.1 "Round 7")
-template <bool WIDE>
-CT_DEV void fetch_cell_cached_raw(const DevScene &sc, const uint8_t *bricks, f3 p, uint32_t &key, uint4 &raw, bool &reused,
-                                  bool zero = false)
-{
-    const float fx = fmaf(p.x, sc.sx, -0.5f), fy = fmaf(p.y, sc.sy, -0.5f), fz = fmaf(p.z, sc.sz, -0.5f);
-    const uint32_t x = (uint32_t)(floor_to_int(fx) + sc.brick_bias), y = (uint32_t)(floor_to_int(fy) + sc.brick_bias),
-                   z = (uint32_t)(floor_to_int(fz) + sc.brick_bias);
-    const uint32_t brick = __umul24(z >> 2, (uint32_t)sc.brick_gxy) + __umul24(y >> 2, (uint32_t)sc.brick_gx) + (x >> 2);
-    const uint32_t local = __umul24(z & 3u, 25u) + __umul24(y & 3u, 5u) + (x & 3u);
-    const uint32_t off = (brick << 7) | local;   // (see fetch_cell_cached)
-    reused = sc.nee_cache != 0u && off == key;
-    if (!reused && !zero) {
+    if (!reused) {
         uint2 a, c;
         load_footprint_pair<WIDE>(bricks, brick, local, a, c);
         raw = make_uint4(a.x, a.y, c.x, c.y);

@@ -695,22 +695,16 @@ struct MieLds {
 // The MARCH kernel keeps both phase tables there too (NEE reads two neighbouring entries: of the un-chopped table at the
 // first bounce, of the chopped one at every later bounce), so a scatter visit issues no vector-memory instruction for the
 // phase function: 56 KiB per block, run as 2 blocks of 768 threads per CU (the same 6 waves per SIMD, the DELTA kernel's
-// block shape) on an L1 whose addresser is busy 0.8 of all cycles.
-// CT_MARCH_PHASE_LDS (A/B, DESIGN.md 4.1 "Round 5"): 2 = as above; 1 = only the chopped table in LDS (40 KiB, 3 blocks of 512
-// threads), read through an LDS pointer, the un-chopped one through a global pointer under the lanes at depth 1; 0 = as 1 but
-// through generic pointers, which the compiler merges into one flat load per scatter visit (until round 4).
-#ifndef CT_MARCH_PHASE_LDS
-#define CT_MARCH_PHASE_LDS 2
-#endif
-constexpr int kMarchThreads = CT_MARCH_PHASE_LDS == 2 ? 768 : 512;
-constexpr int kMarchBlocksPerCu = CT_MARCH_PHASE_LDS == 2 ? 2 : 3;
+// block shape) on an L1 whose addresser is busy 0.8 of all cycles.  With only the chopped table in LDS (40 KiB, 3 blocks of
+// 512 threads) the un-chopped one cost a nearly empty global load per visit under the lanes at depth 1, or, through generic
+// pointers, one flat load per scatter visit: both measured slower (DESIGN.md 4.1 "Round 5").
+constexpr int kMarchThreads = 768;
+constexpr int kMarchBlocksPerCu = 2;
 
 struct MieLdsFull {
     float cdf[kMieN];
     float chopped[kMieN];
-#if CT_MARCH_PHASE_LDS == 2
     float mie[kMieN];
-#endif
     uint16_t guide[kGuideN + 2];
 };
 
@@ -719,9 +713,7 @@ CT_DEV void load_tables(const DevScene &sc, MieLdsFull &lds)
     for (int i = threadIdx.x; i < kMieN; i += blockDim.x) {
         lds.cdf[i] = sc.cdf[i];
         lds.chopped[i] = sc.chopped[i];
-#if CT_MARCH_PHASE_LDS == 2
         lds.mie[i] = sc.mie[i];
-#endif
     }
     for (int i = threadIdx.x; i < kGuideN + 2; i += blockDim.x) {
         lds.guide[i] = sc.guide[i];
@@ -991,8 +983,8 @@ CT_DEV f3 in_scattering(const DevScene &sc, f3 pos, f3 dir, bool chopped)
 // The same NEE in two halves, issue and finish, with the direction sampling between them: identical arithmetic.  What is in
 // flight meanwhile depends on the issuing half.  in_scattering_issue and in_scattering_issue_phase hand back the combined
 // footprint, and the two v_perm_b32 that combine it wait for its loads on the spot: only the arithmetic is deferred.
-// in_scattering_issue_lds with CT_MARCH_NEE_ASYNC (render_persistent_kernel) leaves `cell` unset and the footprint's two raw
-// words in the lane's cache; the caller combines them just ahead of in_scattering_finish, so the loads are in flight while
+// in_scattering_issue_lds (render_persistent_kernel) leaves `cell` unset and the footprint's two raw words in the lane's
+// cache; the caller combines them just ahead of in_scattering_finish, so the loads are in flight while
 // the direction is sampled (DESIGN.md 4.1 "Round 7").
 struct NeeLoads {
     float a, b, w;     // phase table entries and filter weight
@@ -1042,26 +1034,16 @@ CT_DEV NeeLoads in_scattering_issue_phase(const DevScene &sc, f3 dir, bool chopp
 // which is bound by instruction issue at its register limit, the cache cost 2 %).  The address spaces are explicit: through
 // generic pointers the compiler merges an LDS read and a global read into one flat load, which goes through the texture
 // addresser like a global one.
-// zero = true: the footprint is known to be all zero (CT_MARCH_NEE_SKIP == 2): its load is not issued, the cell is zero.
 typedef const float __attribute__((address_space(3))) LdsFloat;
-typedef const float __attribute__((address_space(1))) GlobalFloat;
 
-// CT_MARCH_NEE_ASYNC (A/B, DESIGN.md 4.1 "Round 7"): 1 = the cache holds the footprint's two raw words (NeeCache = uint4,
-// fetch_cell_cached_raw) and NeeLoads::cell is left for the caller to combine just ahead of in_scattering_finish; 0 = the
-// cache holds the combined footprint, whose two v_perm_b32 -- and with them the wait for the loads -- sit right behind the
-// loads' issue, as until round 6.
-#ifndef CT_MARCH_NEE_ASYNC
-#define CT_MARCH_NEE_ASYNC 1
-#endif
-#if CT_MARCH_NEE_ASYNC
+// The cache holds the footprint's two raw words (fetch_cell_cached_raw) and NeeLoads::cell is left for the caller to combine
+// just ahead of in_scattering_finish.  A cache of the combined footprint has its two v_perm_b32 -- and with them the wait
+// for the loads -- right behind the loads' issue; the raw words measured 3942 Msamples/s, +1.5 % (DESIGN.md 4.1 "Round 7").
 typedef uint4 NeeCache;
-#else
-typedef uint2 NeeCache;
-#endif
 
 template <bool FIXED8, bool WIDE>
 CT_DEV NeeLoads in_scattering_issue_lds(const DevScene &sc, const MieLdsFull &lds, f3 pos, f3 dir, bool chopped,
-                                        uint32_t &nee_key, NeeCache &nee_cell, bool &reused, bool zero = false)
+                                        uint32_t &nee_key, NeeCache &nee_cell, bool &reused)
 {
     NeeLoads n;
     const float cos_light = dot3(mk3(sc.nlx, sc.nly, sc.nlz), dir);
@@ -1070,31 +1052,12 @@ CT_DEV NeeLoads in_scattering_issue_lds(const DevScene &sc, const MieLdsFull &ld
     const int32_t i = (int32_t)floorf(x);
     const int32_t j = min(max(i, 0), kMieN - 2);
     float2 pair;
-#if CT_MARCH_PHASE_LDS == 2
     LdsFloat *table = chopped ? (LdsFloat *)lds.chopped : (LdsFloat *)lds.mie;
     pair = make_float2(table[j], table[j + 1]);
-#elif CT_MARCH_PHASE_LDS == 1
-    LdsFloat *table = (LdsFloat *)lds.chopped;
-    pair = make_float2(table[j], table[j + 1]);
-    if (!chopped) {
-        GlobalFloat *first = (GlobalFloat *)(sc.mie + j);
-        pair = make_float2(first[0], first[1]);
-    }
-#else
-    if (chopped) {
-        pair = make_float2(lds.chopped[j], lds.chopped[j + 1]);
-    } else {
-        __builtin_memcpy(&pair, sc.mie + j, sizeof pair);
-    }
-#endif
     n.a = (i > kMieN - 2) ? pair.y : pair.x;
     n.b = (i < 0) ? pair.x : pair.y;
     n.w = tex_weight<FIXED8>(x);
-#if CT_MARCH_NEE_ASYNC
-    fetch_cell_cached_raw<WIDE>(sc, sc.ibricks, pos, nee_key, nee_cell, reused, zero);
-#else
-    n.cell = fetch_cell_cached<WIDE>(sc, sc.ibricks, pos, nee_key, nee_cell, reused, zero);
-#endif
+    fetch_cell_cached_raw<WIDE>(sc, sc.ibricks, pos, nee_key, nee_cell, reused);
     return n;
 }
 
@@ -1109,28 +1072,6 @@ CT_DEV f3 in_scattering_finish(const DevScene &sc, const NeeLoads &n, f3 pos)
 }
 
 enum : int { ST_IDLE = 0, ST_MARCH = 1, ST_BOUNCE = 2 };
-
-// A scatter phase is followed by the march burst in the SAME scheduler iteration -- the lanes it has just redirected march at
-// once -- instead of a pass through the loop's top in between: the scheduler's own instructions (idle / marching / bouncing
-// ballots, the job and drain tests, the queue-empty hint) run once per pair of phases.  Round 4, 512^3 / 1024^2: 3297 -> 3349
-// Msamples/s (+1.6 %; DELTA, where the scheduler is a larger share: 5120 -> 5273, +3.0 %; profiles/r04i).  Schedule only.
-// -DCT_MARCH_FUSE=0 / -DCT_DELTA_FUSE=0 (build --variant nofuse): separate iterations, as until round 3.
-#ifndef CT_MARCH_FLAT_ZERO
-#define CT_MARCH_FLAT_ZERO 1   // (1: an all-zero footprint goes through the density evaluation like the others)
-#endif
-#ifndef CT_MARCH_FLAT_EXIT
-#define CT_MARCH_FLAT_EXIT 1
-#endif
-#ifndef CT_MARCH_FUSE
-#define CT_MARCH_FUSE 1
-#endif
-constexpr bool MARCH_FUSE = CT_MARCH_FUSE != 0;
-// NEE of a collision in a shadow-zero row (DevScene::mbricks, bit 6): its footprint is all zero, so in_scattering_finish is +0
-// and rad + (+0) is rad bit for bit (rad is never -0).  1: the lane branches around the NEE's loads and arithmetic; 2: only the
-// footprint load is predicated off, the arithmetic runs on a zero cell; 0 (build --variant noneeskip): every NEE is evaluated.
-#ifndef CT_MARCH_NEE_SKIP
-#define CT_MARCH_NEE_SKIP 1
-#endif
 
 // 1 / max per-axis advance of one march step, in texels (approximate reciprocal is fine: it only
 // sizes a conservative skip, see the free-space skip in the march phase).
@@ -1165,13 +1106,14 @@ CT_DEV void replay_steps(f3 &pos, f3 stepv, int n)
 }
 
 // render_persistent_kernel replays at most CT_MARCH_REPLAY_MAX skipped steps per lane and burst step, in one straight-line
-// block, and carries the rest of a longer skip to its next burst steps (see its march phase); 0 = replay_steps, the whole
-// skip at once at the pace of the wave's longest (A/B builds).  Measured with the scatter-burst threshold it goes with
-// (ct_api.cpp, burst_scatter 32): 4 / 6 / 8 give 3895 / 3890 / 3877 Msamples/s against 3827 with the loop; 16 is slower than
-// the loop (profiles/r06a).
+// block, and carries the rest of a longer skip to its next burst steps (see its march phase).  Measured with the
+// scatter-burst threshold it goes with (ct_api.cpp, burst_scatter 32): 4 / 6 / 8 give 3895 / 3890 / 3877 Msamples/s against
+// 3827 with replay_steps, the whole skip at once at the pace of the wave's longest; 16 is slower than that loop (DESIGN.md
+// 4.3, profiles/r06a).
 #ifndef CT_MARCH_REPLAY_MAX
 #define CT_MARCH_REPLAY_MAX 4
 #endif
+static_assert(CT_MARCH_REPLAY_MAX >= 1, "CT_MARCH_REPLAY_MAX must be at least 1: a lane in mid-skip replays at least one step per burst step");
 
 // The first min(owed, CT_MARCH_REPLAY_MAX) position adds of a skip: the same adds in the same order as replay_steps', each
 // under `k < owed`, so the lanes drop out one after the other and none comes back.  Returns what is still owed.
@@ -1456,12 +1398,8 @@ __global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu(6
     uint32_t w_fetch = 0, w_nee = 0;
     // path conservation (STATS kernels only, CT_DEBUG_INVARIANTS): samples dealt, results written
     uint32_t iv_dealt = 0, iv_written = 0, iv_resumed = 0, iv_suspended = 0;
-    uint32_t nee_key = 0xffffffffu;         // fetch_cell_cached: this lane's last shadow-volume footprint
-#if CT_MARCH_NEE_ASYNC
+    uint32_t nee_key = 0xffffffffu;         // fetch_cell_cached_raw: this lane's last shadow-volume footprint
     NeeCache nee_cell = make_uint4(0u, 0u, 0u, 0u);   // (the footprint's raw words)
-#else
-    NeeCache nee_cell = make_uint2(0u, 0u);
-#endif
     // scheduler diagnostics (STATS builds only), see ct_debug_stats
     uint32_t st_regen = 0, st_regen_l = 0, st_march = 0, st_march_l = 0, st_scat = 0, st_scat_l = 0;
     uint32_t st_fetch = 0, st_zero = 0, st_skip = 0, st_zero_d0 = 0, st_zero_d1 = 0, st_skip_iters = 0, st_stolen = 0, st_iters = 0, st_first = 0;
@@ -1689,13 +1627,11 @@ __global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu(6
                 st_scat_l += nb;
             }
             bool nee_fetched = false;
-#if CT_MARCH_NEE_ASYNC
             // vmcnt(0), the other counters untouched.  Not a new wait: the NEE's address computation below waits for vector
             // memory anyway (only a result store of the previous burst step can be outstanding here).  Stated at the phase's
             // entry, it keeps the compiler, which joins several paths here, from putting its own into the first pass of the CDF
             // search, behind the NEE loads.
             __builtin_amdgcn_s_waitcnt(0x0f70);
-#endif
             if (state == ST_BOUNCE) {
                 // The collision's back-off (cloud.cuh:99) was left for this phase: in the march phase
                 // one lane in fifteen collides per step, so its log and two divisions would run for
@@ -1710,7 +1646,7 @@ __global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu(6
                     pos = sub3(pos, scale3(scale3(dir, lg), inv)); // scatterPos, :99
                     // The back-off is about a step at most, but not always (T's rounding at a tiny density * step): the flag's
                     // radius covers back-offs up to nee_reach (ct_api.cpp), a longer one is evaluated
-                    nee_zero = CT_MARCH_NEE_SKIP != 0 && (dfree & 0x40u) != 0u && lg * inv <= sc.nee_reach;
+                    nee_zero = (dfree & 0x40u) != 0u && lg * inv <= sc.nee_reach;
                 }
                 // isInBox(scatterPos), cloudRadianceMaterials.cu:49-52
                 if ((dfree & 0x80u) != 0u || in_box(sc, pos)) {
@@ -1718,12 +1654,12 @@ __global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu(6
                     bool nee_reused = false;
                     const uint32_t st_key_before = nee_key;
                     NeeLoads nee;
-                    if (CT_MARCH_NEE_SKIP == 1) {
-                        if (!nee_zero) {
-                            nee = in_scattering_issue_lds<FIXED8, WIDE>(sc, lds, pos, dir, chopped, nee_key, nee_cell, nee_reused);
-                        }
-                    } else {
-                        nee = in_scattering_issue_lds<FIXED8, WIDE>(sc, lds, pos, dir, chopped, nee_key, nee_cell, nee_reused, nee_zero);
+                    // NEE of a collision in a shadow-zero row (DevScene::mbricks, bit 6): its footprint is all zero, so
+                    // in_scattering_finish is +0 and rad + (+0) is rad bit for bit (rad is never -0).  The lane branches around
+                    // the NEE's loads and arithmetic: 3428 -> 3682 Msamples/s, +7.4 %, against 3621 (+5.6 %) with only the footprint
+                    // load predicated off (DESIGN.md 4.3 "Shadow-zero NEE skip").
+                    if (!nee_zero) {
+                        nee = in_scattering_issue_lds<FIXED8, WIDE>(sc, lds, pos, dir, chopped, nee_key, nee_cell, nee_reused);
                     }
                     if (STATS) {
                         st_nee_zero += nee_zero ? 1u : 0u;
@@ -1757,13 +1693,11 @@ __global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu(6
                             go = false;
                         }
                     }
-#if CT_MARCH_NEE_ASYNC
                     // (the pin keeps the footprint's combination and in_scattering_finish behind the direction sampling: left to
                     // itself the scheduler moves them, and the wait for the loads, up between the CDF inversion and the sincos)
                     asm volatile("" : "+v"(nee_cell.x), "+v"(nee_cell.y), "+v"(nee_cell.z), "+v"(nee_cell.w), "+v"(dir.x), "+v"(dir.y), "+v"(dir.z));
-                    nee.cell = (CT_MARCH_NEE_SKIP == 2 && nee_zero) ? make_uint2(0u, 0u) : combine_raw_footprint(nee_cell);
-#endif
-                    if (CT_MARCH_NEE_SKIP != 1 || !nee_zero) {
+                    nee.cell = combine_raw_footprint(nee_cell);
+                    if (!nee_zero) {
                         rad = add3(rad, in_scattering_finish<FIXED8>(sc, nee, pos));
                     }
                     // (setting the next flight up for every lane and selecting the state -- no region for the rare path at its
@@ -1784,22 +1718,22 @@ __global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu(6
             }
             w_nee += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(nee_fetched));
         }
-        // (MARCH_FUSE: the march burst follows a scatter phase in the same scheduler iteration, as in render_delta_kernel)
+        // A scatter phase is followed by the march burst in the SAME scheduler iteration -- the lanes it has just redirected
+        // march at once -- instead of a pass through the loop's top in between: the scheduler's own instructions (idle /
+        // marching / bouncing ballots, the job and drain tests, the queue-empty hint) run once per pair of phases.  Round 4,
+        // 512^3 / 1024^2: 3297 -> 3349 Msamples/s (+1.6 %; DELTA, where the scheduler is a larger share: 5120 -> 5273, +3.0 %;
+        // profiles/r04i).  Schedule only.
         bool track = !do_scatter;
         uint32_t nm_track = nm;
-        if (do_scatter && MARCH_FUSE) {
+        if (do_scatter) {
             nm_track = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(state == ST_MARCH));
             track = nm_track != 0u;
         }
         if (track) {
             // ---------------- march (getNextScatteringEvent, cloud.cuh:87-105) ----------------
             if (STATS) {
-                st_march += 1;
-                st_march_l += CT_MARCH_REPLAY_MAX == 0 ? nm_track : 0u;   // (else: the lanes that step, counted in the burst)
+                st_march += 1;   // (st_march_l: the lanes that step, counted in the burst)
             }
-#if CT_MARCH_REPLAY_MAX == 0
-            w_fetch += nm_track; // every marching lane issues one footprint fetch per burst iteration
-#endif
             // A burst of up to sc.march_burst steps per scheduler visit: the scheduler's own
             // instructions are paid once per burst, and the lanes that collide meanwhile wait for a
             // fuller scatter phase.  The burst ends early when enough lanes wait for the scatter
@@ -1813,7 +1747,6 @@ __global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu(6
             // nor leave the box; only the position updates have to be replayed (same float adds
             // in the same order -> bit-identical path).  They still count as density lookups:
             // the counter is the algorithm's lookup count, not the loads this kernel issued.
-#if CT_MARCH_REPLAY_MAX != 0
             // Bounded replay: a loop over the adds runs until the longest skip among the wave's lanes is done, with the other
             // lanes' loads not yet issued.  So a lane replays at most CT_MARCH_REPLAY_MAX adds per burst step; the clearance
             // (dfree bits 0-7) turns into the count of adds it owes once (bits 8 and up), and a lane that still owes some takes
@@ -1844,26 +1777,6 @@ __global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu(6
                 }
             }
             if (steps) {
-#else
-            if (state == ST_MARCH) {
-                if (dfree != 0u) {
-                    const int n = skip_steps(dfree, inv_maxd);
-                    replay_steps(pos, stepv, n);
-                    c_dl += (uint32_t)n;
-                    if (STATS) {
-                        st_skip += (uint32_t)n;
-                        // wave-level iterations of the replay loop = the largest n of the wave
-                        int wmax = n;
-#pragma unroll
-                        for (int off = 32; off > 0; off >>= 1) {
-                            wmax = max(wmax, __shfl_xor(wmax, off));
-                        }
-                        st_skip_iters += (lane_rank(__builtin_amdgcn_ballot_w64(true)) == 0u) ? (uint32_t)wmax : 0u;
-                        st_skips += n > 0 ? 1u : 0u;
-                        st_replay_l += n > 0 ? 1u : 0u;
-                    }
-                }
-#endif
                 pos = add3(pos, stepv);
                 uint32_t meta;
                 const uint2 cell = fetch_cell_m<SPARSE, WIDE>(sc, pos, meta);
@@ -1899,8 +1812,9 @@ __global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu(6
                     st_zero_d1 += ((cell.x | cell.y) == 0u && dfree == 1u) ? 1u : 0u;
                 }
                 bool collided = false;
-                if (CT_MARCH_FLAT_ZERO || (cell.x | cell.y) != 0u) {
-                    // all-zero footprints give density 0, exp(-0) = 1, T unchanged: nothing to evaluate
+                {
+                    // (an all-zero footprint -- density 0, exp(-0) = 1, T unchanged -- goes through the evaluation like the
+                    // others: no branch around it)
                     const float density = filter_at<FIXED8>(sc, cell, pos) * sc.density_multiplier;
                     const float extinction = density * sc.sample_step;
                     T *= expf_inrange(-extinction);
@@ -1912,16 +1826,9 @@ __global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu(6
                 }
                 // isInBox(pos), the loop condition of cloud.cuh:87.  In an "interior" brick it is
                 // known to hold (see DevScene), so the six comparisons are skipped.
-#if CT_MARCH_FLAT_EXIT
                 state = collided ? ST_BOUNCE : state;
                 dfree = collided ? (meta & 0xc0u) : dfree;
                 if (!collided & ((meta & 0x80u) == 0u) & !in_box_flat(sc, pos)) {
-#else
-                if (collided) {
-                    state = ST_BOUNCE;
-                    dfree = meta & 0xc0u;
-                } else if ((meta & 0x80u) == 0u && !in_box(sc, pos)) {
-#endif
                     ba.frames[out_idx] = make_float4(rad.x, rad.y, rad.z, 1.f);
                     if (STATS) {
                         iv_written += 1;
@@ -1948,12 +1855,8 @@ __global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu(6
             } else if (m_now < sc.burst_march_min || b_now >= sc.burst_scatter || 64u - m_now - b_now >= sc.burst_idle) {
                 break;
             }
-#if CT_MARCH_REPLAY_MAX == 0
-            w_fetch += m_now;
-#endif
             if (STATS) {
                 st_march += 1;
-                st_march_l += CT_MARCH_REPLAY_MAX == 0 ? m_now : 0u;
             }
             }
         }
@@ -1988,13 +1891,11 @@ __global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu(6
                 base = __builtin_amdgcn_readlane(base, __builtin_ctzll(live));
                 if (mine && base != 0xffffffffu) {
                     uint4 *e = (uint4 *)(ba.cont_out + (size_t)(base + lane_rank(live)) * kContWords);
-#if CT_MARCH_REPLAY_MAX != 0
                     // (a path in mid-skip: the adds it still owes, so that the record's dfree keeps its eight bits)
                     for (uint32_t owed = dfree >> 8; owed != 0u; owed--) {
                         pos = add3(pos, stepv);
                     }
                     dfree &= 0xffu;
-#endif
                     e[0] = make_uint4(__float_as_uint(pos.x), __float_as_uint(pos.y), __float_as_uint(pos.z), __float_as_uint(dir.x));
                     e[1] = make_uint4(__float_as_uint(dir.y), __float_as_uint(dir.z), __float_as_uint(rad.x), __float_as_uint(rad.y));
                     e[2] = make_uint4(__float_as_uint(rad.z), seed, out_idx, __float_as_uint(xi));
@@ -2212,21 +2113,10 @@ hipError_t launch_descriptors(const DevScene &sc, const MipPyramid &mp, const fl
 #ifndef CT_DELTA_WAVES
 #define CT_DELTA_WAVES 6
 #endif
-#ifndef CT_DELTA_FUSE
-#define CT_DELTA_FUSE 1        // (see CT_MARCH_FUSE)
-#endif
-constexpr bool DELTA_FUSE = CT_DELTA_FUSE != 0;
 #ifndef CT_DELTA_CHECK_EVERY
 #define CT_DELTA_CHECK_EVERY 2   // (5303 -> 5324 Msamples/s against 1, profiles/r04o; -DCT_DELTA_CHECK_EVERY=1: after every visit, as until round 4)
 #endif
 constexpr uint32_t DELTA_CHECK_EVERY = CT_DELTA_CHECK_EVERY;
-#ifndef CT_DELTA_FLAT_EMPTY
-#define CT_DELTA_FLAT_EMPTY 1
-#endif
-#ifndef CT_DELTA_END_MERGE
-#define CT_DELTA_END_MERGE 1     // (a flight that crosses out of the stored box ends in the visit of that crossing; 0: in its next visit, as until round 4)
-#endif
-constexpr bool DELTA_END_MERGE = CT_DELTA_END_MERGE != 0;
 constexpr int kDeltaThreads = CT_DELTA_THREADS;
 
 // Is the flight's cell one of the STORED cells (the box around the cloud)?  A flight that leaves the box is over: a straight
@@ -2249,8 +2139,8 @@ CT_DEV uint32_t cell_index(const DevScene &sc, const Dda &d)
            (uint32_t)(d.bx - sc.mc_x0);
 }
 
-// The same two for a flight whose cell coordinates are kept RELATIVE to the stored box's first cell (render_delta_kernel with
-// DELTA_END_MERGE: no subtraction per visit).
+// The same two for a flight whose cell coordinates are kept RELATIVE to the stored box's first cell (render_delta_kernel:
+// no subtraction per visit).
 CT_DEV bool cell_in_grid_rel(const DevScene &sc, const Dda &d)
 {
     return ((uint32_t)d.bx < (uint32_t)sc.mc_gx) & ((uint32_t)d.by < (uint32_t)sc.mc_gy) & ((uint32_t)d.bz < (uint32_t)sc.mc_gz);
@@ -2616,7 +2506,7 @@ __global__ __launch_bounds__(kDeltaThreads) __attribute__((amdgpu_waves_per_eu(C
                             } else {
                                 dda_begin(sc, dda, pos, dir);
                             }
-                            if (DELTA_END_MERGE && !dda_enter_box(sc, dda)) {
+                            if (!dda_enter_box(sc, dda)) {
                                 // the flight never meets the stored box: what its first visit would have written
                                 ba.frames[out_idx] = make_float4(rad.x, rad.y, rad.z, 1.f);
                                 if (STATS) {
@@ -2687,7 +2577,7 @@ __global__ __launch_bounds__(kDeltaThreads) __attribute__((amdgpu_waves_per_eu(C
                 rad = add3(rad, in_scattering_finish<FIXED8>(sc, nee, pos));
                 if (go) {
                     dda_begin(sc, dda, pos, dir);
-                    if (DELTA_END_MERGE && !dda_enter_box(sc, dda)) {
+                    if (!dda_enter_box(sc, dda)) {
                         finished = true;   // (the new flight never meets the stored box)
                     } else {
                         state = ST_MARCH;
@@ -2699,11 +2589,11 @@ __global__ __launch_bounds__(kDeltaThreads) __attribute__((amdgpu_waves_per_eu(C
         }
         // A scatter phase is followed by the tracking burst in the SAME scheduler iteration -- the lanes it has just redirected
         // march at once -- instead of a pass through the loop's top in between (round 4: the scheduler's own instructions are a
-        // seventh of the kernel's, and this removes a third of its iterations: 5015 -> 5205 Msamples/s, profiles/r04h; DELTA_FUSE
-        // = 0 restores the separate iterations).  Schedule only: a path's arithmetic does not know when it runs.
+        // seventh of the kernel's, and this removes a third of its iterations: 5015 -> 5205 Msamples/s, profiles/r04h).
+        // Schedule only: a path's arithmetic does not know when it runs.
         bool track = !do_scatter;
         uint32_t nm_track = nm;
-        if (do_scatter && DELTA_FUSE) {
+        if (do_scatter) {
             nm_track = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(state == ST_MARCH));
             track = nm_track != 0u;
         }
@@ -2723,54 +2613,33 @@ __global__ __launch_bounds__(kDeltaThreads) __attribute__((amdgpu_waves_per_eu(C
                 // one step of the flight: cross into the next cell, or draw a tentative collision in this one
                 bool ended = false, collide = false;
                 float sigma_bar = 0.0f, sigma_low = 0.0f;
-                // (DELTA_END_MERGE: a marching lane's cell is always a stored one -- the crossing that leaves the box ends the flight
-                // in its own visit, and a flight that begins outside never starts marching -- so the visit begins with the look-up)
-                if (!DELTA_END_MERGE && !cell_in_grid(sc, dda)) {
-                    ended = true; // left the grid without a collision
-                } else {
-                    const uint32_t ci = DELTA_END_MERGE ? cell_index_rel(sc, dda) : cell_index(sc, dda);
-                    const uint32_t M = lds_maj[ci];
-#if CT_DELTA_FLAT_EMPTY
-                    {
-                        // (an empty cell -- one visit in twelve -- goes through the same instructions with the table's entry 0 and keeps
-                        // its seed and its t: no divergent region around the sampling)
-                        const uint32_t q = ((uint32_t)lds_codes[ci >> 2] >> ((ci & 3u) * 2u)) & 3u;
-                        sigma_low = sigma_table[(q * M) >> 2].x;
-                        const float2 sb = sigma_table[M];
-                        sigma_bar = sb.x;
-                        uint32_t drawn = seed;
-                        const float u = u24_to_float(lcg24(drawn));
-                        const float dt = -logf_above_one(1.0f - u) * sb.y;
-                        const float t_exit = fminf(fminf(dda.tmax.x, dda.tmax.y), dda.tmax.z);
-                        const float t_next = dda.t + dt;
-                        collide = (M != 0u) & (t_next < t_exit);
-                        seed = (M != 0u) ? drawn : seed;
-                        dda.t = collide ? t_next : dda.t;
-                    }
-#else
-                    if (M != 0u) {
-                        // (requesting this byte WITH the majorant, before it is known to be non-zero, measured: no gain, profiles/r04aa)
-                        const uint32_t q = ((uint32_t)lds_codes[ci >> 2] >> ((ci & 3u) * 2u)) & 3u;
-                        sigma_low = sigma_table[(q * M) >> 2].x;
-                        const float2 sb = sigma_table[M];
-                        sigma_bar = sb.x;
-                        const float u = u24_to_float(lcg24(seed));
-                        const float dt = -logf_above_one(1.0f - u) * sb.y;
-                        const float t_exit = fminf(fminf(dda.tmax.x, dda.tmax.y), dda.tmax.z);
-                        const float t_next = dda.t + dt;
-                        collide = t_next < t_exit;
-                        dda.t = collide ? t_next : dda.t;
-                    }
-#endif
-                    if (!collide) {
-                        dda_cross(dda, dir);
-                        if (DELTA_END_MERGE) {
-                            ended = !cell_in_grid_rel(sc, dda);
-                        }
-                        if (STATS) {
-                            st_skip += 1;
-                            st_empty += (M == 0u) ? 1u : 0u;
-                        }
+                // A flight that crosses out of the stored box ends in the visit of that crossing, and one that begins outside never
+                // starts marching: a marching lane's cell is always a stored one, so the visit begins with the look-up (until round 4
+                // the flight ended in its next visit; schedule only, +0.4 %).
+                const uint32_t ci = cell_index_rel(sc, dda);
+                const uint32_t M = lds_maj[ci];
+                {
+                    // (an empty cell -- one visit in twelve -- goes through the same instructions with the table's entry 0 and keeps
+                    // its seed and its t: no divergent region around the sampling)
+                    const uint32_t q = ((uint32_t)lds_codes[ci >> 2] >> ((ci & 3u) * 2u)) & 3u;
+                    sigma_low = sigma_table[(q * M) >> 2].x;
+                    const float2 sb = sigma_table[M];
+                    sigma_bar = sb.x;
+                    uint32_t drawn = seed;
+                    const float u = u24_to_float(lcg24(drawn));
+                    const float dt = -logf_above_one(1.0f - u) * sb.y;
+                    const float t_exit = fminf(fminf(dda.tmax.x, dda.tmax.y), dda.tmax.z);
+                    const float t_next = dda.t + dt;
+                    collide = (M != 0u) & (t_next < t_exit);
+                    seed = (M != 0u) ? drawn : seed;
+                    dda.t = collide ? t_next : dda.t;
+                }
+                if (!collide) {
+                    dda_cross(dda, dir);
+                    ended = !cell_in_grid_rel(sc, dda);
+                    if (STATS) {
+                        st_skip += 1;
+                        st_empty += (M == 0u) ? 1u : 0u;
                     }
                 }
                 if (collide) {

@@ -1,6 +1,6 @@
 """The MARCH kernel's bounded replay of the free-space skip (run with -m gpu on an MI355X).
 
-A lane replays at most R = CT_MARCH_REPLAY_MAX skipped steps per burst step (R = 4; the scene serves R = 8 as well) and
+A lane replays at most R = CT_MARCH_REPLAY_MAX skipped steps per burst step (R = 4, at least 1; the scene serves R = 8 as well) and
 carries the rest of a longer skip to its next burst steps, where it neither steps nor fetches until the skip is done.  A
 path's position adds stay the same adds in the same order, so nothing may change by a bit: every case renders with the
 product kernel and with the diagnostics kernel (CT_STATS=1, CT_DEBUG_INVARIANTS=1) and holds mean, M2 and the counters of

@@ -1,7 +1,8 @@
 """The MARCH kernel's scatter phase with its loads overlapped (run with -m gpu on an MI355X).
 
 The scatter phase keeps the two loads of the NEE's shadow-volume footprint in flight until in_scattering_finish: the lane's
-one-entry cache holds the footprint's raw words, which are combined after the new direction is sampled (CT_MARCH_NEE_ASYNC).
+one-entry cache holds the footprint's raw words, which are combined after the new direction is sampled (the
+cache of the combined footprint, which waited for the loads at once, was removed with its compile-time switch).
 Only the order in which a wave issues and awaits its loads changes, so nothing may change by a bit: every case renders with
 the product kernel and with the diagnostics kernel (CT_STATS=1, CT_DEBUG_INVARIANTS=1) and holds mean, M2 and the counters
 of both against the oracle.

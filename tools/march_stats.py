@@ -23,7 +23,8 @@ out = {"volume": n, "size": size, "spp": spp, "memory": t.debug_memory(),
                       "zero_footprints_with_clearance_1": d(s0, s1, "zero_cells_free_brick_d1") / paths,
                       "skipped_steps": d(s0, s1, "skipped_steps") / paths,
                       # the free-space replay: skips of at least one step, the burst steps in which a lane replayed adds, and
-                      # what the waves paid (iterations of the replay loop with CT_MARCH_REPLAY_MAX=0, else replay blocks)
+                      # what the waves paid (replay blocks of at most CT_MARCH_REPLAY_MAX adds; the key keeps its name from the
+                      # former replay loop, whose iterations it counted)
                       "free_space_skips": d(s0, s1, "free_space_skips") / paths,
                       "replay_lane_steps": d(s0, s1, "replay_lane_steps") / paths,
                       "skip_loop_wave_iterations": d(s0, s1, "skip_loop_wave_iterations") / paths,

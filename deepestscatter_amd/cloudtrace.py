@@ -815,10 +815,23 @@ class CloudTracer:
         return int(n.value)
 
     def debug_math_selftest(self, which: int) -> dict:
-        """ct_debug_math_selftest: 0 = reciprocal, 1 = square root -> {tested, mismatches, first_bad_bits}."""
+        """ct_debug_math_selftest: 0 = reciprocal, 1 = square root, 2 = expf_inrange, 3 = logf_above_one, 4 = floor_to_int,
+        5 = fract_ -> {tested, mismatches, first_bad_bits}."""
         out = np.zeros(3, np.uint64)
         check(self.L.ct_debug_math_selftest(self.h, which, _p(out)), self.h)
         return {"tested": int(out[0]), "mismatches": int(out[1]), "first_bad_bits": int(out[2])}
+
+    def debug_math_eval(self, fn: int, a: np.ndarray, b: np.ndarray | None = None) -> tuple[np.ndarray, np.ndarray]:
+        """ct_debug_math_eval: scalar function `fn` (the table in cloudtrace.h) of the device code on the operand bit
+        patterns a (and b): uint32 arrays in, the two results' bit patterns (r0, r1) as uint32 arrays out."""
+        a = np.ascontiguousarray(a, np.uint32).reshape(-1)
+        inp = np.zeros((a.size, 2), np.uint32)
+        inp[:, 0] = a
+        if b is not None:
+            inp[:, 1] = np.ascontiguousarray(b, np.uint32).reshape(-1)
+        out = np.empty_like(inp)
+        check(self.L.ct_debug_math_eval(self.h, fn, _p(inp), a.size, _p(out)), self.h)
+        return out[:, 0].copy(), out[:, 1].copy()
 
     def debug_cdf_inversion(self, first_u24: int, count: int) -> np.ndarray:
         out = np.empty(count, np.uint32)

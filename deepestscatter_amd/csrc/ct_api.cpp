@@ -3562,21 +3562,36 @@ extern "C" int ct_debug_fetch_probe_ws(int32_t device, uint32_t log2_threads, ui
 extern "C" int ct_debug_math_selftest(CtHandle h, int32_t which, uint64_t out[3])
 {
     NEED(h);
-    if (!out || (which != 0 && which != 1)) {
-        return fail(h, CT_E_INVAL, "ct_debug_math_selftest: which = 0 (reciprocal) or 1 (square root)");
+    if (!out || which < 0 || which > 5) {
+        return fail(h, CT_E_INVAL, "ct_debug_math_selftest: which = 0 (reciprocal), 1 (square root), 2 (expf_inrange), 3 (logf_above_one), "
+                                   "4 (floor_to_int) or 5 (fract_)");
     }
-    // every float with 2^-60 <= x < 2^61 (positive: both functions are odd / undefined for negative arguments in the same way
-    // as the IEEE operations, and the kernels only pass positive values); the reciprocal also for the negative range
+    // Up to two ranges of bit patterns [lo, hi] per test, both ends included.
+    // 0, 1: every float with 2^-60 <= x < 2^61 (positive: both functions are odd / undefined for negative arguments in the same way
+    //       as the IEEE operations, and the kernels only pass positive values); the reciprocal also for the negative range
+    // 2:    every float with -87 < x <= -0.0f, and +0.0f (the march's argument is -sigma * step)
+    // 3:    every positive normal float
+    // 4:    every float with -2^31 <= x < 2^31, both zeros and the subnormals included
+    // 5:    every finite float
+    const uint32_t lo = (127u - 60u) << 23, hi = ((127u + 61u) << 23) - 1u;
+    const uint32_t ranges[6][4] = {
+        { lo, hi, lo | 0x80000000u, hi | 0x80000000u },
+        { lo, hi, 1u, 0u },
+        { 0x80000000u, 0xc2adffffu, 0u, 0u },           // -87.0f = 0xc2ae0000
+        { 0x00800000u, 0x7f7fffffu, 1u, 0u },
+        { 0u, 0x4effffffu, 0x80000000u, 0xcf000000u },  // 2^31 = 0x4f000000
+        { 0u, 0x7f7fffffu, 0x80000000u, 0xff7fffffu },
+    };
+    const uint32_t *rg = ranges[which];
     unsigned long long *d = nullptr;
     HIPCHK(h, hipMalloc((void **)&d, 3 * sizeof(unsigned long long)));
     const unsigned long long init[3] = { 0, 0, 0xffffffffull };
     hipError_t e = hipMemcpyAsync(d, init, sizeof init, hipMemcpyHostToDevice, h->stream);
-    const uint32_t lo = (127u - 60u) << 23, hi = ((127u + 61u) << 23) - 1u;
     if (e == hipSuccess) {
-        e = launch_math_selftest(which, lo, hi, d, h->stream);
+        e = launch_math_selftest(which, rg[0], rg[1], d, h->stream);
     }
-    if (e == hipSuccess && which == 0) {
-        e = launch_math_selftest(which, lo | 0x80000000u, hi | 0x80000000u, d, h->stream);
+    if (e == hipSuccess && rg[2] <= rg[3]) {
+        e = launch_math_selftest(which, rg[2], rg[3], d, h->stream);
     }
     unsigned long long r[3] = { 0, 0, 0 };
     if (e == hipSuccess) {
@@ -3590,6 +3605,29 @@ extern "C" int ct_debug_math_selftest(CtHandle h, int32_t which, uint64_t out[3]
     out[0] = r[0];
     out[1] = r[1];
     out[2] = r[2];
+    return CT_OK;
+}
+
+extern "C" int ct_debug_math_eval(CtHandle h, int32_t fn, const uint32_t *in_bits, uint32_t n, uint32_t *out_bits)
+{
+    NEED(h);
+    if (!in_bits || !out_bits || n == 0 || n > (1u << 24) || fn < 0 || fn >= CT_MATH_FN_COUNT) {
+        return fail(h, CT_E_INVAL, "ct_debug_math_eval: fn in [0, %d), 1 <= n <= 2^24, two words per item in and out", CT_MATH_FN_COUNT);
+    }
+    DevTemp<uint32_t> d_in, d_out;
+    HIPCHK(h, dmalloc(&d_in, 2 * (size_t)n));
+    HIPCHK(h, dmalloc(&d_out, 2 * (size_t)n));
+    const size_t bytes = 2 * (size_t)n * sizeof(uint32_t);
+    hipError_t e = hipMemcpyAsync(d_in, in_bits, bytes, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) {
+        e = launch_math_eval(fn, d_in, n, d_out, h->stream);
+    }
+    if (e == hipSuccess) {
+        e = hipMemcpyAsync(out_bits, d_out, bytes, hipMemcpyDeviceToHost, h->stream);
+    }
+    const hipError_t es = hipStreamSynchronize(h->stream);   // before the temporaries go out of scope, whatever happened
+    HIPCHK(h, e);
+    HIPCHK(h, es);
     return CT_OK;
 }
 

@@ -43,7 +43,10 @@ CT_DEV float sqrt_(float x) { return sqrtf(x); }
 // plus one Newton step (two for the square root) carried out with fused multiply-adds, whose residual is exact.  hipcc's IEEE sequences spend
 // most of their ten instructions on scaling for subnormal and huge arguments, which cannot occur here.  That these
 // return the bits of 1.0f / x and sqrtf(x) for EVERY float in the range is not argued but checked, exhaustively, on the
-// device: ct_debug_math_selftest / test_fast_rcp_and_sqrt_are_correctly_rounded_for_every_float_in_range.
+// device: ct_debug_math_selftest / test_fast_rcp_and_sqrt_are_correctly_rounded_for_every_float_in_range.  The same holds for
+// the other device-only variants below -- expf_inrange, logf_above_one, floor_to_int, fract_ (self-tests 2 to 5,
+// tests/test_device_math.py::test_device_only_variants_exhaustively) -- and every scalar function of the contract is held to the
+// host's bits on sets that cover its breakpoints (ct_debug_math_eval, test_device_function_equals_host_bit_for_bit there).
 CT_DEV float rcp_moderate(float x)
 {
     const float r0 = __builtin_amdgcn_rcpf(x);
@@ -228,7 +231,8 @@ CT_DEV bool in_box_flat(const DevScene &sc, f3 p)
 
 // ---- 3-D texture unit ---------------------------------------------------------------------
 // floor / frac of a texel coordinate; v_fract_f32 returns min(x - floor(x), 0x1.fffffep-1)
-// which is exactly the oracle's fracf().
+// which is exactly the oracle's fracf() for every FINITE float (self-test 5).  For +-inf and NaN, which no texel coordinate
+// can be, the instruction returns a NaN and fracf() the clamp, 0x1.fffffep-1.
 CT_DEV float fract_(float x) { return __builtin_amdgcn_fractf(x); }
 
 // The weight of every linear / trilinear filter.  FIXED8 = false (the default): the exact fraction, the oracle's default
@@ -360,7 +364,8 @@ CT_DEV uint2 load_footprint_m(const DevScene &sc, int32_t ix, int32_t iy, int32_
     return r;
 }
 
-// (int)floorf(x) in one instruction (v_cvt_flr_i32_f32); identical for every in-range x.
+// (int)floorf(x) in one instruction (v_cvt_flr_i32_f32); identical for every float with -2^31 <= x < 2^31, the range in which
+// the C conversion is defined (self-test 4, exhaustive).  Texel coordinates (volumes of at most 2048 texels) lie far inside it.
 CT_DEV int32_t floor_to_int(float x)
 {
     int32_t r;
@@ -580,7 +585,7 @@ CT_DEV float tex1(Ptr t, float u)
 // weight ((j-8)&15)/16, so with t = #{ i : cdf[i] < val } (found from a 4096-bucket guide
 // table + a short binary search) only the 15 interior points of texel t-1 remain:
 //     k = min(16(t-1) + 8 + s, 65535),   s = #{ s' in 1..15 : fma(s'/16, cdf[t]-cdf[t-1], cdf[t-1]) < val }.
-// tests/test_cdf_inversion.py checks all 2^24 values of val against the literal bisection.
+// tests/test_gpu_parity.py::test_cdf_inversion_exhaustive checks all 2^24 values of val against the literal bisection.
 template <typename CdfPtr, typename GuidePtr>
 CT_DEV float sample_cos_theta(CdfPtr cdf, GuidePtr guide, uint32_t u24)
 {
@@ -658,7 +663,8 @@ CT_DEV bool intersect_box(const DevScene &sc, f3 o, f3 d, float &t_hit)
 }
 
 // ---- log of a positive NORMAL float (the march's xi/T > 1, the delta tracker's 1-u >= 2^-24):
-// ct_logf's special cases (<= 0, inf, subnormal) can never fire; same instruction sequence otherwise.
+// ct_logf's special cases (<= 0, inf, subnormal) can never fire; same instruction sequence otherwise (a hand copy: self-test 3
+// holds it to ct_logf for every positive normal float).
 CT_DEV float logf_above_one(float x)
 {
     const uint32_t u = ct_float_to_bits(x);
@@ -688,7 +694,8 @@ CT_DEV float logf_above_one(float x)
 }
 
 // ---- exp for the march: arguments are -sigma*step in (-87, 0], so ct_expf's range checks
-// can never fire; same instruction sequence otherwise (bit-identical for in-range x). ---------
+// can never fire; same instruction sequence otherwise (bit-identical for in-range x, -87 < x <= 88: a hand copy that
+// self-test 2 holds to ct_expf for every float of (-87, 0]). ---------
 CT_DEV float expf_inrange(float x)
 {
     const float n = rintf(x * 1.44269504088896341f);

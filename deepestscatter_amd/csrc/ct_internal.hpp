@@ -201,6 +201,7 @@ hipError_t launch_converged_freeze(const float4 *mean, const float4 *m2, uint32_
 hipError_t launch_cdf_selftest(const float *cdf, const uint16_t *guide, uint32_t first_u24, uint32_t count,
                                uint32_t *k_out, hipStream_t stream);
 hipError_t launch_math_selftest(int which, uint32_t lo_bits, uint32_t hi_bits, unsigned long long *out, hipStream_t stream);
+hipError_t launch_math_eval(int fn, const uint32_t *in, uint32_t n, uint32_t *out, hipStream_t stream);
 hipError_t launch_fetch_probe(const uint8_t *buf, uint32_t log2_lines, uint32_t second_offset,
                               unsigned long long *sum, hipStream_t stream);
 hipError_t launch_fetch_probe_ws(const uint8_t *buf, uint32_t log2_threads, uint32_t ws_lines, uint32_t salt, unsigned long long *sum,

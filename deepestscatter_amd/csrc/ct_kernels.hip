@@ -4314,7 +4314,9 @@ hipError_t launch_cdf_selftest(const float *cdf, const uint16_t *guide, uint32_t
 }
 
 // =============================================================================================
-// self-test hook: rcp_moderate / sqrt_moderate against the IEEE operations for EVERY float of their range
+// self-test hook: the device-only variants of ct_device.hpp against what they stand for, for EVERY float of a range of bit
+// patterns: 0 rcp_moderate / 1.0f / x, 1 sqrt_moderate / sqrtf, 2 expf_inrange / ct_expf, 3 logf_above_one / ct_logf,
+// 4 floor_to_int / (int32_t)floorf, 5 fract_ / fminf(x - floorf(x), kFracMax)   (ranges: ct_debug_math_selftest)
 // =============================================================================================
 // out[0] = inputs tested, out[1] = mismatches, out[2] = smallest mismatching bit pattern (0xffffffff: none)
 __global__ void math_selftest_kernel(int which, uint32_t lo_bits, uint32_t hi_bits, unsigned long long *out)
@@ -4325,16 +4327,35 @@ __global__ void math_selftest_kernel(int which, uint32_t lo_bits, uint32_t hi_bi
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
         const uint32_t bits = lo_bits + (uint32_t)i;
         const float x = __uint_as_float(bits);
-        float got, want;
-        if (which == 0) {
-            got = rcp_moderate(x);
-            want = 1.0f / x;
-        } else {
-            got = sqrt_moderate(x);
-            want = sqrtf(x);
+        uint32_t got, want;
+        switch (which) {
+        case 0:
+            got = __float_as_uint(rcp_moderate(x));
+            want = __float_as_uint(1.0f / x);
+            break;
+        case 1:
+            got = __float_as_uint(sqrt_moderate(x));
+            want = __float_as_uint(sqrtf(x));
+            break;
+        case 2:
+            got = __float_as_uint(expf_inrange(x));
+            want = __float_as_uint(ct_expf(x));
+            break;
+        case 3:
+            got = __float_as_uint(logf_above_one(x));
+            want = __float_as_uint(ct_logf(x));
+            break;
+        case 4:
+            got = (uint32_t)floor_to_int(x);
+            want = (uint32_t)(int32_t)floorf(x);
+            break;
+        default:
+            got = __float_as_uint(fract_(x));
+            want = __float_as_uint(fminf(x - floorf(x), 0x1.fffffep-1f));
+            break;
         }
         tested += 1;
-        if (__float_as_uint(got) != __float_as_uint(want)) {
+        if (got != want) {
             bad += 1;
             first = min(first, bits);
         }
@@ -4349,6 +4370,83 @@ __global__ void math_selftest_kernel(int which, uint32_t lo_bits, uint32_t hi_bi
 hipError_t launch_math_selftest(int which, uint32_t lo_bits, uint32_t hi_bits, unsigned long long *out, hipStream_t stream)
 {
     hipLaunchKernelGGL(math_selftest_kernel, dim3(4096), dim3(256), 0, stream, which, lo_bits, hi_bits, out);
+    return hipGetLastError();
+}
+
+// =============================================================================================
+// self-test hook: ONE scalar function of the numeric contract (include/ct_fmath.h, ct_device.hpp) on given operands.
+// in[2i], in[2i+1] = the bits of item i's two operands, out[2i], out[2i+1] = the bits of its two results (an unused
+// result is 0).  fn: the table at ct_debug_math_eval in include/cloudtrace.h.  The functions called are the ones the
+// estimator kernels call, not copies.
+// =============================================================================================
+__global__ void math_eval_kernel(int fn, const uint2 *__restrict__ in, uint32_t n, uint2 *__restrict__ out)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) {
+        return;
+    }
+    const uint2 a = in[i];
+    const float x = __uint_as_float(a.x), y = __uint_as_float(a.y);
+    uint2 r = make_uint2(0u, 0u);
+    switch (fn) {
+    case 0:
+        r.x = __float_as_uint(ct_expf(x));
+        break;
+    case 1:
+        r.x = __float_as_uint(ct_logf(x));
+        break;
+    case 2:
+        r.x = __float_as_uint(ct_log2f(x));
+        break;
+    case 3:
+        r.x = __float_as_uint(ct_powf(x, y));
+        break;
+    case 4: {
+        float s, c;
+        ct_sincosf(x, &s, &c);
+        r = make_uint2(__float_as_uint(s), __float_as_uint(c));
+        break;
+    }
+    case 5:
+        r.x = __float_as_uint(expf_inrange(x));
+        break;
+    case 6:
+        r.x = __float_as_uint(logf_above_one(x));
+        break;
+    case 7:
+        r.x = __float_as_uint(div_(x, y));
+        break;
+    case 8:
+        r.x = __float_as_uint(u24_to_float(a.x));
+        break;
+    case 9:
+        r.x = tea4(a.x, a.y);
+        break;
+    case 10: {
+        uint32_t state = a.x;
+        r.x = lcg24(state);
+        r.y = state;
+        break;
+    }
+    case 11:
+        r.x = (uint32_t)floor_to_int(x);
+        break;
+    case 12:
+        r.x = __float_as_uint(fract_(x));
+        break;
+    case 13:
+        r.x = __float_as_uint(tex_weight<false>(x));
+        break;
+    default:
+        r.x = __float_as_uint(tex_weight<true>(x));
+        break;
+    }
+    out[i] = r;
+}
+
+hipError_t launch_math_eval(int fn, const uint32_t *in, uint32_t n, uint32_t *out, hipStream_t stream)
+{
+    hipLaunchKernelGGL(math_eval_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, fn, (const uint2 *)in, n, (uint2 *)out);
     return hipGetLastError();
 }
 

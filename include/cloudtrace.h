@@ -995,8 +995,26 @@ CT_API int ct_debug_touched_lines(CtHandle h, uint64_t out[4], int32_t clear);
 
 /* Self-test hook: the kernels' short correctly-rounded reciprocal (which = 0) and square root (which = 1) against the IEEE
  * operations for EVERY float of their range, 2^-60 <= |x| < 2^61 (reciprocal: both signs), on the device:
- * out[0] = floats tested, out[1] = mismatches (must be 0), out[2] = smallest mismatching bit pattern or 0xffffffff. */
+ * out[0] = floats tested, out[1] = mismatches (must be 0), out[2] = smallest mismatching bit pattern or 0xffffffff.
+ * The same for the kernels' other device-only variants, each against what it stands for:
+ *   which = 2  expf_inrange(x)   against ct_expf(x)                     every float with -87 < x <= -0.0f, and +0.0f
+ *   which = 3  logf_above_one(x) against ct_logf(x)                     every positive normal float
+ *   which = 4  floor_to_int(x)   against (int32_t)floorf(x)             every float with -2^31 <= x < 2^31 (zeros, subnormals)
+ *   which = 5  fract_(x)         against fminf(x - floorf(x), 1 - 2^-24) every finite float */
 CT_API int ct_debug_math_selftest(CtHandle h, int32_t which, uint64_t out[3]);
+
+/* Self-test hook: ONE scalar function of the numeric contract, as the kernels compile and call it, on given operands.
+ * in_bits and out_bits are host arrays of 2 * n words: the bit patterns of item i's two operands at in_bits[2i], [2i+1],
+ * of its two results at out_bits[2i], [2i+1].  An unused operand is ignored, an unused result is written as 0.
+ * 1 <= n <= 2^24.  fn (device expression -> results):
+ *    0  ct_expf(x)            1  ct_logf(x)            2  ct_log2f(x)          3  ct_powf(x, y)
+ *    4  ct_sincosf(x) -> (sin, cos)                    5  expf_inrange(x)      6  logf_above_one(x)
+ *    7  div_(x, y) = x / y    8  u24_to_float(u)       9  tea4(v0, v1)        10  lcg24(state) -> (value, new state)
+ *   11  floor_to_int(x)      12  fract_(x)            13  tex_weight<false>(x) 14  tex_weight<true>(x)
+ * x, y are floats, u, v0, v1, state and the results of 9, 10 and 11 are 32-bit integers.  A function is evaluated on
+ * whatever bits it is given, also outside the range its callers keep to. */
+#define CT_MATH_FN_COUNT 15
+CT_API int ct_debug_math_eval(CtHandle h, int32_t fn, const uint32_t *in_bits, uint32_t n, uint32_t *out_bits);
 
 /* Self-test hook: k(val) of the CDF inversion (cloud.cuh:162-180) for `count` consecutive 24-bit
  * random integers starting at first_u24, evaluated by the device code; cos(theta) = (2k+1)/65536-1. */

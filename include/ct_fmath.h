@@ -14,7 +14,8 @@
  *
  * Polynomials are the classic single-precision Cephes minimax sets; measured
  * error vs. double libm is <= 2 ulp over the ranges the tracer uses
- * (tests/test_fmath.py).
+ * (tests/test_oracle_basics.py::test_fmath_accuracy; tests/test_device_math.py on the breakpoints, and there also
+ * the gfx950 build against the host build, bit for bit).
  *
  * Usable from C99, C++ and HIP device code.
  */
@@ -46,7 +47,7 @@ CT_FN uint32_t ct_float_to_bits(float f)
 }
 
 /* e^x.  Cody-Waite reduction by ln2 (two-term), degree-5 polynomial, exact 2^n scale.
- * Results below the normal range flush to 0 (the tracer never needs them). */
+ * x <= -87 gives 0 (the tracer never needs those results); e^-87 = 1.6e-38 is above 2^-126, so no result is subnormal. */
 CT_FN float ct_expf(float x)
 {
     if (!(x > -87.0f)) {

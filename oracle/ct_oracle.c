@@ -1418,6 +1418,66 @@ ORC_API float orc_tex3d(const uint8_t *texels, const uint32_t dims[3], const flo
     ctx_init(&c, &s);
     return tex3_fetch(&c.density, v3_make(pos_box[0], pos_box[1], pos_box[2]));
 }
+/* Host twin of the product's ct_debug_math_eval: scalar function `fn` (same numbers as there) on n items of two operand
+ * words each, two result words each (an unused result is 0; an unknown fn gives zeros).  Written from the definitions the
+ * oracle itself uses: ct_fmath.h, orc_tea4, orc_lcg, fracf and filter_weight -- both filter weights are spelled out so that
+ * one library serves the exact-weight and the ORC_TEX_FIXED8 case.  The twins of the kernels' in-range variants (5, 6) are
+ * ct_expf and ct_logf, that of their one-instruction floor (11) is (int32_t)floorf(x), defined for -2^31 <= x < 2^31. */
+ORC_API void orc_math_eval(int32_t fn, const uint32_t *in, uint32_t n, uint32_t *out)
+{
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t a = in[2 * (size_t)i], b = in[2 * (size_t)i + 1];
+        const float x = ct_bits_to_float(a), y = ct_bits_to_float(b);
+        uint32_t r0 = 0, r1 = 0;
+        switch (fn) {
+        case 0: case 5:
+            r0 = ct_float_to_bits(ct_expf(x));
+            break;
+        case 1: case 6:
+            r0 = ct_float_to_bits(ct_logf(x));
+            break;
+        case 2:
+            r0 = ct_float_to_bits(ct_log2f(x));
+            break;
+        case 3:
+            r0 = ct_float_to_bits(ct_powf(x, y));
+            break;
+        case 4: {
+            float s, c;
+            ct_sincosf(x, &s, &c);
+            r0 = ct_float_to_bits(s);
+            r1 = ct_float_to_bits(c);
+            break;
+        }
+        case 7:
+            r0 = ct_float_to_bits(x / y);
+            break;
+        case 8:
+            r0 = ct_float_to_bits((float)a / (float)0x01000000);
+            break;
+        case 9:
+            r0 = orc_tea4(a, b);
+            break;
+        case 10:
+            r1 = a;
+            r0 = orc_lcg(&r1);
+            break;
+        case 11:
+            r0 = (uint32_t)(int32_t)floorf(x);
+            break;
+        case 12: case 13:
+            r0 = ct_float_to_bits(fracf(x, floorf(x)));
+            break;
+        case 14:
+            r0 = ct_float_to_bits(rintf(fracf(x, floorf(x)) * 256.0f) * (1.0f / 256.0f));
+            break;
+        default:
+            break;
+        }
+        out[2 * (size_t)i] = r0;
+        out[2 * (size_t)i + 1] = r1;
+    }
+}
 ORC_API int32_t orc_max_threads(void)
 {
 #ifdef _OPENMP

@@ -162,8 +162,28 @@ def lib(fast=False):
     L.orc_sincosf.argtypes = [C.c_float, f32p, f32p]
     L.orc_cdf_bisect_k.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int32]
     L.orc_max_threads.restype = C.c_int32
+    bind_math_eval(L)
     _LIB[key] = L
     return L
+
+
+def bind_math_eval(L):
+    L.orc_math_eval.restype = None
+    L.orc_math_eval.argtypes = [C.c_int32, C.c_void_p, C.c_uint32, C.c_void_p]
+    return L
+
+
+def math_eval(fn: int, a: np.ndarray, b: np.ndarray | None = None, L=None) -> tuple[np.ndarray, np.ndarray]:
+    """orc_math_eval, the host twin of CloudTracer.debug_math_eval: scalar function `fn` on the operand bit patterns a (and b),
+    uint32 arrays in and (r0, r1) out.  L: another build of ct_oracle.c that bind_math_eval() prepared (default: the oracle)."""
+    a = np.ascontiguousarray(a, np.uint32).reshape(-1)
+    inp = np.zeros((a.size, 2), np.uint32)
+    inp[:, 0] = a
+    if b is not None:
+        inp[:, 1] = np.ascontiguousarray(b, np.uint32).reshape(-1)
+    out = np.empty_like(inp)
+    (L or lib()).orc_math_eval(fn, _ptr(inp), a.size, _ptr(out))
+    return out[:, 0].copy(), out[:, 1].copy()
 
 
 def _ptr(a: np.ndarray):

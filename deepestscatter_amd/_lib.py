@@ -30,7 +30,7 @@ EXPORTS = [
     "ct_accumulate", "ct_render_accumulate", "ct_render_accumulate_async", "ct_synchronize", "ct_copy_to_device_async", "ct_point_radiance_launch", "ct_generate_scatter_samples", "ct_collect_descriptors", "ct_descriptor_frame", "ct_debug_descriptor_frame_time", "ct_network_create", "ct_network_destroy", "ct_network_eval", "ct_debug_network_time", "ct_network_render_subframe", "ct_network_render_accumulate", "ct_network_render_shard_subframe", "ct_network_render_shard_accumulate", "ct_debug_network_scratch", "ct_debug_network_aux", "ct_debug_network_render_time", "ct_network_bake", "ct_bake_update", "ct_bake_destroy", "ct_bake_info", "ct_bake_probes", "ct_bake_download", "ct_debug_bake_lookup", "ct_network_bake_sparse", "ct_bake_sparse_info", "ct_bake_mask", "ct_network_bake_compact", "ct_bake_storage_info", "ct_bake_slots", "ct_bake_download_stored", "ct_bake_traced", "ct_bake_trace_more", "ct_bake_retrace", "ct_bake_trace_info", "ct_bake_directions", "ct_debug_bake_mask", "ct_baked_render_subframe", "ct_baked_render_accumulate", "ct_baked_render_shard_subframe", "ct_baked_render_shard_accumulate", "ct_debug_baked_render_time", "ct_reset", "ct_tonemap", "ct_tonemap_async", "ct_set_render_ahead", "ct_rendered_subframes", "ct_set_stop_when_converged", "ct_converged_at", "ct_is_converged", "ct_tonemap_buffer", "ct_is_converged_buffers", "ct_download", "ct_upload",
     "ct_buffer_bytes", "ct_copy_to_device", "ct_device_ptr", "ct_subframes", "ct_set_subframes", "ct_counters", "ct_kernel_time",
     "ct_debug_cdf_inversion", "ct_debug_math_selftest", "ct_debug_math_eval", "ct_debug_fetch_probe", "ct_debug_fetch_probe_ws", "ct_debug_track_lines", "ct_debug_touched_lines", "ct_debug_stats", "ct_debug_stats_ex", "ct_debug_suspended", "ct_debug_timeline", "ct_debug_invariants", "ct_debug_pixel_classes", "ct_debug_pixel_class_plane", "ct_debug_memory", "ct_debug_delta_grid", "ct_debug_march_meta", "ct_debug_layout", "ct_fetch_counters", "ct_calculate_camera_variables", "ct_quantize_volume", "ct_load_vdb", "ct_generate_mipmaps",
-    "ct_tile_owner", "ct_shard_tiles", "ct_make_procedural_cloud",
+    "ct_tile_owner", "ct_shard_tiles", "ct_debug_allocations", "ct_make_procedural_cloud",
     "ct_group_create", "ct_group_destroy", "ct_group_last_error", "ct_group_size", "ct_group_handle", "ct_group_set_camera", "ct_group_set_light",
     "ct_group_render_accumulate", "ct_group_reset", "ct_group_merge", "ct_group_download", "ct_group_tonemap",
     "ct_group_is_converged", "ct_group_counters",
@@ -286,6 +286,7 @@ def load():
         "ct_quantize_volume": (i32, [vp, vp, vp]),
         "ct_load_vdb": (i32, [C.c_char_p, vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_char_p, C.c_size_t]),
         "ct_generate_mipmaps": (i32, [vp, vp, vp, C.c_size_t, C.POINTER(u32), C.POINTER(C.c_size_t), vp]),
+        "ct_debug_allocations": (i32, [C.POINTER(C.c_uint64)]),
         "ct_tile_owner": (u32, [u32, u32, u32]),
         "ct_shard_tiles": (i32, [u32, u32, u32, u32, vp, u32, C.POINTER(u32)]),
         "ct_group_create": (i32, [C.POINTER(CtScene), vp, u32, C.POINTER(vp)]),

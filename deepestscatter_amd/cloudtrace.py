@@ -118,6 +118,13 @@ def tile_owner(tx: int, ty: int, shard_count: int) -> int:
     return int(_lib.load().ct_tile_owner(tx, ty, shard_count))
 
 
+def debug_allocations() -> dict:
+    """ct_debug_allocations: the device and pinned host buffers the library holds in this process right now, and their bytes."""
+    v = (C.c_uint64 * 4)()
+    check(_lib.load().ct_debug_allocations(v))
+    return dict(zip(("device_buffers", "device_bytes", "pinned_buffers", "pinned_bytes"), (int(x) for x in v)))
+
+
 def shard_mask(width: int, height: int, shard_index: int, shard_count: int) -> np.ndarray:
     """bool [H, W]: pixels whose 8x8 tile belongs to `shard_index`."""
     ty, tx = np.meshgrid(np.arange(height) // 8, np.arange(width) // 8, indexing="ij")

@@ -211,53 +211,15 @@ static void release(CtHandle h)
         }
         hipMemAddressFree(h->vmm.va, h->vmm.size);
         h->vmm.va = nullptr;
-        h->d_mbricks = nullptr;
+        (void)h->d_mbricks.release();   // (not a hipMalloc pointer: nothing to free)
     }
 #endif
-    void *ptrs[] = { h->d_density, h->d_inscatter, h->d_dbricks, h->d_ibricks, h->d_mbricks, h->d_tbricks, h->d_touched[0], h->d_touched[1], h->d_mrows, h->d_mcoarse, h->d_pyramid, h->d_mie, h->d_chopped, h->d_cdf,
-                     h->d_guide, h->d_dist, h->d_dist_tmp, h->d_majorant, h->d_maj_cells, h->d_maj_codes, h->d_frame, h->d_mean, h->d_m2, h->d_screen, h->d_frames_all, h->cont[0], h->cont[1], h->left[0], h->left[1], h->d_cont_count, h->d_cont_total, h->d_primary, h->d_advance, h->d_pixels, h->d_start, h->d_cost, h->d_group_rank, h->d_group_order, h->d_job_group, h->d_job_sub, h->d_queue,
-                     h->d_counters, h->d_colsum, h->d_avg, h->d_freeze, h->d_hit, h->d_cost_plane, h->d_timeline, h->pt.tasks, h->pt.primary, h->pt.frames, h->pt.pixels, h->pt.jg, h->pt.js,
-                     h->net.found, h->net.waves, h->net.pos, h->net.dir, h->net.aux, h->net.out, h->net.desc, h->net.direct, h->net.tiles };
-    for (void *p : ptrs) {
-        if (p) {
-            hipFree(p);
-        }
-    }
-    for (auto &e : h->ev) {
-        if (e) {
-            hipEventDestroy(e);
-        }
-    }
-    for (auto &sl : h->slots) {
-        if (sl.queue) {
-            hipFree(sl.queue);
-        }
-        for (hipEvent_t e : { sl.ev_in, sl.ev_start, sl.ev_done, sl.ev_acc0, sl.ev_acc1 }) {
-            if (e) {
-                hipEventDestroy(e);
-            }
-        }
-    }
-    for (hipEvent_t e : { h->ev_flush0, h->ev_flush1 }) {
-        if (e) {
-            hipEventDestroy(e);
-        }
-    }
-    if (h->freeze_host) {
-        hipHostFree(h->freeze_host);
-    }
-    if (h->hit_host) {
-        hipHostFree(h->hit_host);
-    }
-    for (uint32_t *p : { h->jobs_host_g, h->jobs_host_s }) {
-        if (p) {
-            hipHostFree(p);
-        }
-    }
-    if (h->own_stream) {
-        hipStreamDestroy(h->own_stream);
-    }
+    // Every buffer and event is a member that frees itself.  The handle's own stream goes after them: after the delete.
+    const hipStream_t own_stream = h->own_stream;
     delete h;
+    if (own_stream) {
+        hipStreamDestroy(own_stream);
+    }
 }
 
 #ifdef CT_EXPERIMENTS
@@ -287,10 +249,10 @@ static int vmm_back_mbricks(CtHandle h)
     }
     const size_t n_chunks = (dense_bytes + chunk - 1) / chunk;
     const size_t va_size = n_chunks * chunk;
-    DevTemp<uint4> d_class;
-    HIPCHK(h, dmalloc(&d_class, n_chunks));
+    DevBuf<uint4> d_class;
+    HIPCHK(h, d_class.alloc(n_chunks));
     std::vector<uint4> cls(n_chunks);
-    uint8_t *dense = h->d_mbricks;
+    const uint8_t *dense = h->d_mbricks;
     void *va = nullptr;
     std::vector<hipMemGenericAllocationHandle_t> handles;
     auto undo = [&]() {
@@ -364,8 +326,8 @@ static int vmm_back_mbricks(CtHandle h)
     }
     VMMCHK(hipStreamSynchronize(h->stream));
 #undef VMMCHK
-    HIPCHK(h, hipFree(dense));
-    h->d_mbricks = (uint8_t *)va;
+    HIPCHK(h, h->d_mbricks.reset());
+    h->d_mbricks.hold((uint8_t *)va, va_size);   // (release() detaches the range again)
     h->dev.mbricks = h->d_mbricks;
     h->vmm.va = va;
     h->vmm.size = va_size;
@@ -574,7 +536,7 @@ static int open_device(const CtScene *s, CtHandle h)
     HIPCHK(h, hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
     h->stream = h->own_stream;
     for (auto &e : h->ev) {
-        HIPCHK(h, hipEventCreate(&e));
+        HIPCHK(h, e.create());
     }
     return CT_OK;
 }
@@ -771,10 +733,10 @@ static int upload_mie(const CtScene *s, CtHandle h, bool &mie_finite)
     mie_phase_texture(s->chopped_mie_host, s->mie_count, chopped_tex);
     mie_integral_texture(s->chopped_mie_host, s->mie_count, cdf_tex);
     build_guide(cdf_tex, guide);
-    HIPCHK(h, dmalloc(&h->d_mie, kMieN));
-    HIPCHK(h, dmalloc(&h->d_chopped, kMieN));
-    HIPCHK(h, dmalloc(&h->d_cdf, kMieN));
-    HIPCHK(h, dmalloc(&h->d_guide, kGuideN + 2));
+    HIPCHK(h, h->d_mie.alloc(kMieN));
+    HIPCHK(h, h->d_chopped.alloc(kMieN));
+    HIPCHK(h, h->d_cdf.alloc(kMieN));
+    HIPCHK(h, h->d_guide.alloc(kGuideN + 2));
     HIPCHK(h, hipMemcpyAsync(h->d_mie, mie_tex.data(), kMieN * sizeof(float), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->d_chopped, chopped_tex.data(), kMieN * sizeof(float), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->d_cdf, cdf_tex.data(), kMieN * sizeof(float), hipMemcpyHostToDevice, h->stream));
@@ -802,18 +764,18 @@ static int build_apron_bricks(const CtScene *s, CtHandle h)
     const int bbias = d.brick_bias;
     const int64_t bgx = d.brick_gx, bgy = d.brick_gy, bgz = d.brick_gz;
     const size_t brick_bytes = (size_t)(bgx * bgy * bgz) * 128;
-    HIPCHK(h, dmalloc(&h->d_density, texels));
-    HIPCHK(h, dmalloc(&h->d_inscatter, texels));
-    HIPCHK(h, dmalloc(&h->d_dbricks, brick_bytes));
-    HIPCHK(h, dmalloc(&h->d_ibricks, brick_bytes));
+    HIPCHK(h, h->d_density.alloc(texels));
+    HIPCHK(h, h->d_inscatter.alloc(texels));
+    HIPCHK(h, h->d_dbricks.alloc(brick_bytes));
+    HIPCHK(h, h->d_ibricks.alloc(brick_bytes));
     HIPCHK(h, hipMemcpyAsync(h->d_density, s->density_host, texels, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, launch_build_bricks(h->d_density, nx, ny, nz, bbias, (int)bgx, (int)bgy, (int)bgz, h->d_dbricks, h->stream));
     d.dbricks = h->d_dbricks;
     d.ibricks = h->d_ibricks;
     const size_t nb = (size_t)(bgx * bgy * bgz);
-    HIPCHK(h, dmalloc(&h->d_dist, nb));
-    HIPCHK(h, dmalloc(&h->d_dist_tmp, nb));
-    HIPCHK(h, dmalloc(&h->d_majorant, nb));
+    HIPCHK(h, h->d_dist.alloc(nb));
+    HIPCHK(h, h->d_dist_tmp.alloc(nb));
+    HIPCHK(h, h->d_majorant.alloc(nb));
     HIPCHK(h, launch_build_dist(h->d_density, nx, ny, nz, bbias, (int)bgx, (int)bgy, (int)bgz, h->d_dist,
                                 h->d_dist_tmp, h->d_majorant, h->stream));
     HIPCHK(h, launch_brick_meta(h->d_dist, h->d_majorant, nx, ny, nz, bbias, (int)bgx, (int)bgy, (int)bgz,
@@ -836,9 +798,9 @@ static int build_majorant_grid(const CtScene *s, CtHandle h)
     }
     const auto &[C, div, origin, stored, virt] = m;
     const size_t cells = (size_t)stored[0] * stored[1] * stored[2];
-    HIPCHK(h, dmalloc(&h->d_maj_cells, (cells + 3) & ~(size_t)3)); // the kernel copies whole words
+    HIPCHK(h, h->d_maj_cells.alloc((cells + 3) & ~(size_t)3)); // the kernel copies whole words
     HIPCHK(h, hipMemsetAsync(h->d_maj_cells, 0, (cells + 3) & ~(size_t)3, h->stream));
-    HIPCHK(h, dmalloc(&h->d_maj_codes, (cells + 3) & ~(size_t)3));
+    HIPCHK(h, h->d_maj_codes.alloc((cells + 3) & ~(size_t)3));
     HIPCHK(h, hipMemsetAsync(h->d_maj_codes, 0, (cells + 3) & ~(size_t)3, h->stream));
     HIPCHK(h, launch_majorant_cells(h->d_density, nx, ny, nz, bbias, C, origin, stored[0], stored[1], stored[2], h->d_maj_cells,
                                     h->d_maj_codes, h->stream));
@@ -871,7 +833,7 @@ static int twin_grid(CtHandle h)
     if (!brick_indices_fit(tgx, tgy, tgz) || (int64_t)std::max({ d.nx, d.ny, d.nz }) + 2 * tbias >= (1 << 15)) {
         return fail(h, CT_E_INVAL, "volume too large for 32-bit brick indices");
     }
-    if (hipMalloc(&h->d_tbricks, (size_t)(tgx * tgy * tgz) * 128) != hipSuccess) {
+    if (h->d_tbricks.alloc((size_t)(tgx * tgy * tgz) * 128) != hipSuccess) {
         return fail(h, CT_E_NOMEM, "out of device memory (twin bricks)");
     }
     d.tbricks = h->d_tbricks;
@@ -901,11 +863,11 @@ static int compact_march_bricks(CtHandle h, const uint8_t *tmp_b)
     const int bbias = d.brick_bias;
     const int64_t bgx = d.brick_gx, bgy = d.brick_gy, bgz = d.brick_gz, mgx = d.m_gx;
     const size_t rows = (size_t)(bgy * bgz);
-    DevTemp<uint32_t> d_x0, d_x1;
-    DevTemp<uint8_t> compact;
+    DevBuf<uint32_t> d_x0, d_x1;
+    DevBuf<uint8_t> compact;
     auto run = [&]() -> int {
-        HIPCHK(h, dmalloc(&d_x0, rows));
-        HIPCHK(h, dmalloc(&d_x1, rows));
+        HIPCHK(h, d_x0.alloc(rows));
+        HIPCHK(h, d_x1.alloc(rows));
         HIPCHK(h, hipMemsetAsync(d_x0, 0xff, rows * sizeof(uint32_t), h->stream));
         HIPCHK(h, hipMemsetAsync(d_x1, 0, rows * sizeof(uint32_t), h->stream));
         HIPCHK(h, launch_mbrick_extent(h->d_mbricks, (int)mgx, (int)bgy, (int)bgz, d_x0, d_x1, h->stream));
@@ -923,19 +885,19 @@ static int compact_march_bricks(CtHandle h, const uint8_t *tmp_b)
         if (lines >= (1ull << 32)) {
             return fail(h, CT_E_INVAL, "volume too large for 32-bit brick indices");
         }
-        HIPCHK(h, dmalloc(&h->d_mrows, rows));
+        HIPCHK(h, h->d_mrows.alloc(rows));
         HIPCHK(h, hipMemcpyAsync(h->d_mrows, ri.data(), rows * sizeof(uint2), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, dmalloc(&compact, std::max<size_t>((size_t)lines, 1) * 128));
+        HIPCHK(h, compact.alloc(std::max<size_t>((size_t)lines, 1) * 128));
         HIPCHK(h, launch_mbrick_compact(h->d_mbricks, (int)mgx, (int)bgy, (int)bgz, h->d_mrows, compact, h->stream));
         // clearance of the cells outside the extents: cubic cells of 8 texels over the brick grid's texel range
         const int cshift = 3;
         const int64_t cgx = (4 * bgx + 7) >> cshift, cgy = (4 * bgy + 7) >> cshift, cgz = (4 * bgz + 7) >> cshift;
-        HIPCHK(h, dmalloc(&h->d_mcoarse, (size_t)(cgx * cgy * cgz)));
+        HIPCHK(h, h->d_mcoarse.alloc((size_t)(cgx * cgy * cgz)));
         HIPCHK(h, launch_coarse_clearance(tmp_b, nx, ny, nz, bbias, cshift, (int)cgx, (int)cgy, (int)cgz, h->d_mcoarse,
                                           h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream)); // `ri` dies at scope exit; the dense array is freed below
-        HIPCHK(h, hipFree(h->d_mbricks));
-        h->d_mbricks = compact.release();
+        HIPCHK(h, h->d_mbricks.reset());
+        h->d_mbricks = std::move(compact);
         d.mbricks = h->d_mbricks;
         h->mbricks_bytes = (size_t)lines * 128;
         d.m_rows = h->d_mrows;
@@ -987,14 +949,14 @@ static int build_march_layouts(const CtScene *s, CtHandle h, int apron, const Ma
     // each at most 4 GiB (1024^3: 3.4 GB and 2.2 GB), else with 64-bit ones.  CT_WIDE_OFFSETS=1 forces those (tests).
     const size_t ibricks_bytes = (size_t)(bgx * bgy * bgz) * 128;
     h->shape.wide = std::max(dense_bytes, ibricks_bytes) > (1ull << 32) || knob_flag(h->tune.WIDE_OFFSETS, false);
-    HIPCHK(h, dmalloc(&h->d_mbricks, dense_bytes));
+    HIPCHK(h, h->d_mbricks.alloc(dense_bytes));
     d.mbricks = h->d_mbricks;
     d.m_bias_x = mbias;
     d.m_gx = (int32_t)mgx;
     d.m_gxy = (int32_t)(mgx * bgy);
-    DevTemp<uint8_t> tmp_a, tmp_b, tmp_c;
-    HIPCHK(h, dmalloc(&tmp_a, texels));
-    if (dmalloc(&tmp_b, texels) != hipSuccess) {
+    DevBuf<uint8_t> tmp_a, tmp_b, tmp_c;
+    HIPCHK(h, tmp_a.alloc(texels));
+    if (tmp_b.alloc(texels) != hipSuccess) {
         return fail(h, CT_E_NOMEM, "out of device memory (distance transform scratch)");
     }
     hipError_t e = launch_build_mbricks(h->d_density, nx, ny, nz, mbias, bbias, (int)mgx, (int)bgy, (int)bgz,
@@ -1009,7 +971,7 @@ static int build_march_layouts(const CtScene *s, CtHandle h, int apron, const Ma
     const int nee_r = s->estimator == CT_EST_MARCH ? nee_skip_radius(d, mie_finite) : 0;
     if (e == hipSuccess && nee_r > 0) {
         // shadow-zero rows (bit 6 of the march bricks' meta bytes)
-        e = dmalloc(&tmp_c, texels);
+        e = tmp_c.alloc(texels);
         if (e == hipSuccess) {
             e = launch_nee_skip_flags(h->d_inscatter, nx, ny, nz, nee_r, mbias, bbias, (int)mgx, (int)bgy, (int)bgz, tmp_a, tmp_c,
                                       h->d_mbricks, h->stream);
@@ -1031,43 +993,43 @@ static int build_march_layouts(const CtScene *s, CtHandle h, int apron, const Ma
 static int frame_buffers(const CtScene *s, CtHandle h)
 {
     const size_t pixels = (size_t)s->width * s->height;
-    HIPCHK(h, dmalloc(&h->d_frame, pixels));
-    HIPCHK(h, dmalloc(&h->d_mean, pixels));
-    HIPCHK(h, dmalloc(&h->d_m2, pixels));
-    HIPCHK(h, dmalloc(&h->d_screen, pixels));
-    HIPCHK(h, dmalloc(&h->d_colsum, s->width));
-    HIPCHK(h, dmalloc(&h->d_avg, 2)); // average luminance + the fused tonemap kernel's grid barrier
-    HIPCHK(h, dmalloc(&h->d_queue, kQueueWords));
-    HIPCHK(h, dmalloc(&h->d_cont_count, 6));
+    HIPCHK(h, h->d_frame.alloc(pixels));
+    HIPCHK(h, h->d_mean.alloc(pixels));
+    HIPCHK(h, h->d_m2.alloc(pixels));
+    HIPCHK(h, h->d_screen.alloc(pixels));
+    HIPCHK(h, h->d_colsum.alloc(s->width));
+    HIPCHK(h, h->d_avg.alloc(2)); // average luminance + the fused tonemap kernel's grid barrier
+    HIPCHK(h, h->d_queue.alloc(kQueueWords));
+    HIPCHK(h, h->d_cont_count.alloc(6));
     HIPCHK(h, hipMemsetAsync(h->d_cont_count, 0, 6 * sizeof(uint32_t), h->stream));
     // a lane suspends at most one path per launch, and a launch resumes up to 64 paths per wave: the same number
     h->cont_capacity = (size_t)h->shape.blocks * h->shape.threads;
-    HIPCHK(h, hipEventCreate(&h->ev_flush0));
-    HIPCHK(h, hipEventCreate(&h->ev_flush1));
+    HIPCHK(h, h->ev_flush0.create());
+    HIPCHK(h, h->ev_flush1.create());
     if (h->tune.TIMELINE.get()) {
         const size_t waves = (size_t)h->shape.blocks * h->shape.threads / 64u;
-        HIPCHK(h, dmalloc(&h->d_timeline, 4 * waves));
+        HIPCHK(h, h->d_timeline.alloc(4 * waves));
         HIPCHK(h, hipMemsetAsync(h->d_timeline, 0, 4 * waves * sizeof(unsigned long long), h->stream));
     }
-    HIPCHK(h, dmalloc(&h->d_cont_total, 1));
+    HIPCHK(h, h->d_cont_total.alloc(1));
     HIPCHK(h, hipMemsetAsync(h->d_cont_total, 0, sizeof(unsigned long long), h->stream));
     for (auto &c : h->cont) {
-        HIPCHK(h, dmalloc(&c, h->cont_capacity * (s->estimator == CT_EST_DELTA ? kContWordsDelta : kContWords)));
+        HIPCHK(h, c.alloc(h->cont_capacity * (s->estimator == CT_EST_DELTA ? kContWordsDelta : kContWords)));
     }
     h->left_capacity = h->cont_capacity / 64;   // a wave hands on at most the one job it is working on
     for (auto &c : h->left) {
-        HIPCHK(h, dmalloc(&c, h->left_capacity * kLeftWords));
+        HIPCHK(h, c.alloc(h->left_capacity * kLeftWords));
     }
     for (auto &sl : h->slots) {
-        HIPCHK(h, dmalloc(&sl.queue, kQueueWords));
-        for (hipEvent_t *e : { &sl.ev_in, &sl.ev_start, &sl.ev_done, &sl.ev_acc0, &sl.ev_acc1 }) {
-            HIPCHK(h, hipEventCreate(e));
+        HIPCHK(h, sl.queue.alloc(kQueueWords));
+        for (Event *e : { &sl.ev_in, &sl.ev_start, &sl.ev_done, &sl.ev_acc0, &sl.ev_acc1 }) {
+            HIPCHK(h, e->create());
         }
     }
-    HIPCHK(h, dmalloc(&h->d_counters, kCounterCount + 1 + kStatCount));
-    HIPCHK(h, dmalloc(&h->d_freeze, 8));
+    HIPCHK(h, h->d_counters.alloc(kCounterCount + 1 + kStatCount));
+    HIPCHK(h, h->d_freeze.alloc(8));
     HIPCHK(h, hipMemsetAsync(h->d_freeze, 0, 8 * sizeof(uint32_t), h->stream));
-    HIPCHK(h, hipHostMalloc((void **)&h->freeze_host, 4 * sizeof(uint32_t), hipHostMallocDefault));
+    HIPCHK(h, h->freeze_host.alloc(4));
     memset(h->freeze_host, 0, 4 * sizeof(uint32_t));
     HIPCHK(h, hipMemsetAsync(h->d_frame, 0, pixels * sizeof(float4), h->stream));
     HIPCHK(h, hipMemsetAsync(h->d_mean, 0, pixels * sizeof(float4), h->stream));
@@ -1075,8 +1037,8 @@ static int frame_buffers(const CtScene *s, CtHandle h)
     HIPCHK(h, hipMemsetAsync(h->d_screen, 0, pixels * sizeof(uchar4), h->stream));
     HIPCHK(h, hipMemsetAsync(h->d_counters, 0, (kCounterCount + 1 + kStatCount) * sizeof(unsigned long long), h->stream));
 
-    HIPCHK(h, dmalloc(&h->d_primary, 2 * pixels));
-    HIPCHK(h, dmalloc(&h->d_advance, (s->estimator == CT_EST_DELTA ? 4 : 1) * pixels));
+    HIPCHK(h, h->d_primary.alloc(2 * pixels));
+    HIPCHK(h, h->d_advance.alloc((s->estimator == CT_EST_DELTA ? 4 : 1) * pixels));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return CT_OK;
 }
@@ -1234,8 +1196,8 @@ static int relight(CtHandle h, const CtScene &s)
     light_uniforms(&s, d);
     const bool march = s.estimator == CT_EST_MARCH;
     const int nee_r = march ? nee_skip_radius(d, h->mie_finite) : 0;
-    DevTemp<uint8_t> tmp_a, tmp_c;   // the Chebyshev passes' two scratch volumes
-    if (nee_r > 0 && (dmalloc(&tmp_a, h->volume_bytes) != hipSuccess || dmalloc(&tmp_c, h->volume_bytes) != hipSuccess)) {
+    DevBuf<uint8_t> tmp_a, tmp_c;   // the Chebyshev passes' two scratch volumes
+    if (nee_r > 0 && (tmp_a.alloc(h->volume_bytes) != hipSuccess || tmp_c.alloc(h->volume_bytes) != hipSuccess)) {
         (void)hipGetLastError();
         return fail(h, CT_E_NOMEM, "out of device memory (shadow-zero flags scratch); the light is unchanged");
     }
@@ -1334,10 +1296,8 @@ static int rebuild_queue(CtHandle h)
     }
     // (the class plane and, behind it, the word of the through pixels' steps: one download)
     const size_t sum_at = (pixels + 7u) & ~(size_t)7u, plane_bytes = sum_at + sizeof(unsigned long long);
-    if (!h->d_hit) {
-        HIPCHK(h, dmalloc(&h->d_hit, plane_bytes));
-        HIPCHK(h, hipHostMalloc((void **)&h->hit_host, plane_bytes, hipHostMallocDefault));
-    }
+    HIPCHK(h, h->d_hit.reserve(plane_bytes));   // (the same size at every call: allocated at the first)
+    HIPCHK(h, h->hit_host.reserve(plane_bytes));
     HIPCHK(h, hipMemsetAsync(h->d_hit + sum_at, 0, sizeof(unsigned long long), h->stream));
     HIPCHK(h, launch_hit_flags(h->d_primary, through ? h->d_advance : nullptr, h->d_hit, (uint32_t)pixels, W, h->scene.shard_index,
                                h->scene.shard_count, (unsigned long long *)(h->d_hit + sum_at), h->stream));
@@ -1386,28 +1346,13 @@ static int rebuild_queue(CtHandle h)
         list.push_back(0xffffffffu);
     }
     h->n_groups = (uint32_t)(list.size() / 64);
-    if (h->n_groups > h->groups_capacity) {
-        for (void *p : { (void *)h->d_pixels, (void *)h->d_cost, (void *)h->d_start }) {
-            if (p) {
-                HIPCHK(h, hipFree(p));
-            }
-        }
-        h->d_pixels = h->d_cost = nullptr;
-        h->d_start = nullptr;
-        for (void *p : { (void *)h->d_group_rank, (void *)h->d_group_order }) {
-            if (p) {
-                HIPCHK(h, hipFree(p));
-            }
-        }
-        h->d_group_rank = h->d_group_order = nullptr;
-        HIPCHK(h, dmalloc(&h->d_pixels, (size_t)h->n_groups * 64));
-        HIPCHK(h, dmalloc(&h->d_cost, 2 * (size_t)h->n_groups));
-        HIPCHK(h, dmalloc(&h->d_group_rank, (size_t)h->n_groups));
-        HIPCHK(h, dmalloc(&h->d_group_order, (size_t)h->n_groups));
-        if (start_records(h)) {
-            HIPCHK(h, dmalloc(&h->d_start, 2 * (size_t)h->n_groups * 64));
-        }
-        h->groups_capacity = h->n_groups;
+    // (the old contents are dead: free, then allocate)
+    HIPCHK(h, h->d_pixels.reserve((size_t)h->n_groups * 64));
+    HIPCHK(h, h->d_cost.reserve(2 * (size_t)h->n_groups));
+    HIPCHK(h, h->d_group_rank.reserve((size_t)h->n_groups));
+    HIPCHK(h, h->d_group_order.reserve((size_t)h->n_groups));
+    if (start_records(h)) {
+        HIPCHK(h, h->d_start.reserve(2 * (size_t)h->n_groups * 64));
     }
     h->group_order.resize(h->n_groups);
     h->group_tile.resize(h->n_groups);
@@ -1536,17 +1481,8 @@ static int build_jobs(CtHandle h, uint32_t S, uint32_t chunk_groups)
         const uint32_t len = job_length(g);
         total_jobs += (S + len - 1) / len;
     }
-    if (total_jobs > h->jobs_host_capacity) {
-        for (uint32_t **pp : { &h->jobs_host_g, &h->jobs_host_s }) {
-            if (*pp) {
-                HIPCHK(h, hipHostFree(*pp));
-                *pp = nullptr;
-            }
-        }
-        h->jobs_host_capacity = total_jobs + total_jobs / 4 + 1024;
-        HIPCHK(h, hipHostMalloc((void **)&h->jobs_host_g, h->jobs_host_capacity * sizeof(uint32_t), hipHostMallocDefault));
-        HIPCHK(h, hipHostMalloc((void **)&h->jobs_host_s, h->jobs_host_capacity * sizeof(uint32_t), hipHostMallocDefault));
-    }
+    HIPCHK(h, h->jobs_host_g.reserve(total_jobs, total_jobs / 4 + 1024));
+    HIPCHK(h, h->jobs_host_s.reserve(total_jobs, total_jobs / 4 + 1024));
     uint32_t *const jg = h->jobs_host_g, *const js = h->jobs_host_s;
     size_t nj = 0;
     std::vector<double> q_weight(kQueues + 1, 0.0);
@@ -1628,17 +1564,8 @@ static int build_jobs(CtHandle h, uint32_t S, uint32_t chunk_groups)
     // (nq == 1: everything sits in queue 0 and the other XCDs' waves steal from it -- one global
     // cost-sorted list, the behaviour before the queues were split)
     h->n_jobs = (uint32_t)nj;
-    if (h->n_jobs > h->jobs_capacity) {
-        for (void *p : { (void *)h->d_job_group, (void *)h->d_job_sub }) {
-            if (p) {
-                HIPCHK(h, hipFree(p));
-            }
-        }
-        h->d_job_group = h->d_job_sub = nullptr;
-        h->jobs_capacity = h->n_jobs + h->n_jobs / 4;
-        HIPCHK(h, dmalloc(&h->d_job_group, h->jobs_capacity));
-        HIPCHK(h, dmalloc(&h->d_job_sub, h->jobs_capacity));
-    }
+    HIPCHK(h, h->d_job_group.reserve(h->n_jobs, h->n_jobs / 4));
+    HIPCHK(h, h->d_job_sub.reserve(h->n_jobs, h->n_jobs / 4));
     if (h->n_jobs) {
         HIPCHK(h, hipMemcpyAsync(h->d_job_group, jg, nj * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipMemcpyAsync(h->d_job_sub, js, nj * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
@@ -1769,19 +1696,15 @@ static uint32_t groups_per_chunk(CtHandle h, uint32_t S)
 // At least `total` float4 of per-sample scratch (nothing may be in flight when it grows: the caller has flushed).
 static int reserve_frames(CtHandle h, size_t total)
 {
-    if (total <= h->frames_total) {
+    if (total <= h->d_frames_all.capacity()) {
         return CT_OK;
     }
-    if (h->d_frames_all) {
-        HIPCHK(h, hipFree(h->d_frames_all));
-        h->d_frames_all = nullptr;
-        h->frames_total = 0;
-        h->slot_capacity = 0;
-    }
-    const hipError_t e = dmalloc(&h->d_frames_all, total);
+    // free, then allocate: the scratch is several GB, and two of them may not fit
+    h->slot_capacity = 0;
+    HIPCHK(h, h->d_frames_all.reset());
+    const hipError_t e = h->d_frames_all.alloc(total);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        h->d_frames_all = nullptr;
         return fail(h, e == hipErrorOutOfMemory ? CT_E_NOMEM : CT_E_HIP, "per-sample scratch of %.1f GB: %s", (double)total * 16e-9,
                     hipGetErrorString(e));
     }
@@ -1789,7 +1712,6 @@ static int reserve_frames(CtHandle h, size_t total)
     // take 30 ms longer (measured on the 3.5 GB scratch of a 256-subframe batch)
     HIPCHK(h, hipMemsetAsync(h->d_frames_all, 0, total * sizeof(float4), h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->frames_total = total;
     return CT_OK;
 }
 
@@ -1819,7 +1741,7 @@ static int ensure_frames(CtHandle h, uint32_t S, bool relayout)
         }
     }
     h->slot_capacity = need;
-    h->n_regions = (int)std::min<size_t>((size_t)regions, h->frames_total / need);
+    h->n_regions = (int)std::min<size_t>((size_t)regions, h->d_frames_all.capacity() / need);
     h->layout_S = S;
     h->next_slot = 0;
     return CT_OK;
@@ -2013,14 +1935,7 @@ static int submit_batch(CtHandle h, int slot, float4 *dense_frames, uint32_t fir
     const bool measure = !h->order_tuned && !simple && !dense && chunk_n != 0u;
     if (measure) {
         const size_t entries = (size_t)S * frame_stride(h);
-        if (entries > h->cost_plane_capacity) {
-            if (h->d_cost_plane) {
-                HIPCHK(h, hipFree(h->d_cost_plane));
-                h->d_cost_plane = nullptr;
-            }
-            h->cost_plane_capacity = entries + entries / 4;
-            HIPCHK(h, dmalloc(&h->d_cost_plane, h->cost_plane_capacity));
-        }
+        HIPCHK(h, h->d_cost_plane.reserve(entries, entries / 4));
         HIPCHK(h, hipMemsetAsync(h->d_cost_plane, 0, entries * sizeof(uint2), h->stream));
         ba.cost = h->d_cost_plane;
     }
@@ -2424,7 +2339,7 @@ static int render_accumulate_impl(CtHandle h, uint32_t first_subframe_id, uint32
             const uint64_t budget = 2 * scratch_slot_bytes(h) / sizeof(float4);
             const size_t total = std::min<size_t>((size_t)(enqueue ? wanted_regions(h, h->jobs_hint, need, std::max<uint64_t>(budget, 2 * need)) : 1) * need,
                                                   (0xffffffffull / std::max<size_t>(need, 1)) * need);
-            if (total <= h->frames_total) {
+            if (total <= h->d_frames_all.capacity()) {
                 break;
             }
             int rc = flush(h);
@@ -2608,28 +2523,6 @@ extern "C" int ct_synchronize(CtHandle h)
 
 static_assert(sizeof(CtPointRadianceTask) == 40, "Gpu::PointRadianceTask is 40 bytes (PointRadianceTask.h:70-77)");
 
-// (re)allocation waits for the device, so it happens only when a call is larger than every call before it
-template <typename T>
-static hipError_t point_grow(T **p, size_t &cap, size_t need)
-{
-    if (need <= cap) {
-        return hipSuccess;
-    }
-    if (*p) {
-        hipError_t e = hipFree(*p);
-        *p = nullptr;
-        cap = 0;
-        if (e != hipSuccess) {
-            return e;
-        }
-    }
-    hipError_t e = hipMalloc((void **)p, need * sizeof(**p));
-    if (e == hipSuccess) {
-        cap = need;
-    }
-    return e;
-}
-
 // The launch half of ct_point_radiance_launch, which the traced bake (ct_neural.cpp) shares: `launches` experiments, frames
 // first_frame_id .., of the `count` point tasks whose rays `rays` enqueues into h->pt.primary / h->pt.pixels (grown to
 // pad64(count) entries by then).  The results are h->pt.frames[f * pad64(count) + i]; `fold` enqueues what consumes them.
@@ -2689,11 +2582,11 @@ int ct::point_launch(CtHandle h, const DevScene &sc, uint32_t count, uint32_t fi
     }
     CtHandle_::PointBuffers &pt = h->pt;
     auto run = [&]() -> int {
-        HIPCHK(h, point_grow(&pt.primary, pt.cap_primary, 2 * (size_t)n_pad));
-        HIPCHK(h, point_grow(&pt.pixels, pt.cap_pixels, n_pad));
-        HIPCHK(h, point_grow(&pt.frames, pt.cap_frames, (size_t)n_pad * launches));
-        HIPCHK(h, point_grow(&pt.jg, pt.cap_jg, jg.size()));
-        HIPCHK(h, point_grow(&pt.js, pt.cap_js, js.size()));
+        HIPCHK(h, pt.primary.reserve(2 * (size_t)n_pad));
+        HIPCHK(h, pt.pixels.reserve(n_pad));
+        HIPCHK(h, pt.frames.reserve((size_t)n_pad * launches));
+        HIPCHK(h, pt.jg.reserve(jg.size()));
+        HIPCHK(h, pt.js.reserve(js.size()));
         HIPCHK(h, hipMemcpyAsync(pt.jg, jg.data(), jg.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipMemcpyAsync(pt.js, js.data(), js.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipMemsetAsync(h->d_queue, 0, kQueueWords * sizeof(uint32_t), h->stream));
@@ -2742,11 +2635,9 @@ int ct::point_launch(CtHandle h, const DevScene &sc, uint32_t count, uint32_t fi
         h->launches += 1;
         h->host_paths += (unsigned long long)count * launches;
         h->iv_expected_dealt += (unsigned long long)count * launches;
-        if (pt.cap_frames > ((size_t)64 << 20)) {
+        if (pt.frames.capacity() > ((size_t)64 << 20)) {
             // an unusually large call (> 1 GiB of per-experiment results): do not keep that much for the handle's life
-            HIPCHK(h, hipFree(pt.frames));
-            pt.frames = nullptr;
-            pt.cap_frames = 0;
+            HIPCHK(h, pt.frames.reset());
         }
         return CT_OK;
     };
@@ -2787,7 +2678,7 @@ extern "C" int ct_point_radiance_launch(CtHandle h, CtPointRadianceTask *tasks_h
     return point_launch(
         h, h->dev, count, first_frame_id, launches,
         [&]() -> int {
-            HIPCHK(h, point_grow(&pt.tasks, pt.cap_tasks, count));
+            HIPCHK(h, pt.tasks.reserve(count));
             HIPCHK(h, hipMemcpyAsync(pt.tasks, tasks_host, (size_t)count * sizeof(CtPointRadianceTask), hipMemcpyHostToDevice, h->stream));
             HIPCHK(h, launch_point_rays(h->dev, pt.tasks, count, n_pad, pt.primary, pt.pixels, h->stream));
             return CT_OK;
@@ -2806,10 +2697,10 @@ extern "C" int ct_generate_scatter_samples(CtHandle h, uint32_t count, uint32_t 
     if (!positions_host_out || !directions_host_out || count == 0 || count > (1u << 20)) {
         return fail(h, CT_E_INVAL, "ct_generate_scatter_samples: need 1..2^20 samples and two output arrays");
     }
-    DevTemp<float> d_pos, d_dir;
+    DevBuf<float> d_pos, d_dir;
     auto run = [&]() -> int {
-        HIPCHK(h, dmalloc(&d_pos, 3 * (size_t)count));
-        HIPCHK(h, dmalloc(&d_dir, 3 * (size_t)count));
+        HIPCHK(h, d_pos.alloc(3 * (size_t)count));
+        HIPCHK(h, d_dir.alloc(3 * (size_t)count));
         HIPCHK(h, launch_scatter_samples(h->dev, count, batch_seed, d_pos, d_dir, h->stream));
         HIPCHK(h, hipMemcpyAsync(positions_host_out, d_pos, 3 * (size_t)count * sizeof(float), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipMemcpyAsync(directions_host_out, d_dir, 3 * (size_t)count * sizeof(float), hipMemcpyDeviceToHost, h->stream));
@@ -3228,11 +3119,8 @@ extern "C" int ct_debug_track_lines(CtHandle h, int32_t enable)
 {
     NEED(h);
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (int k = 0; k < 2; k++) {
-        if (h->d_touched[k]) {
-            HIPCHK(h, hipFree(h->d_touched[k]));
-            h->d_touched[k] = nullptr;
-        }
+    for (auto &t : h->d_touched) {
+        HIPCHK(h, t.reset());
     }
     if (!enable) {
         return CT_OK;
@@ -3254,7 +3142,7 @@ extern "C" int ct_debug_track_lines(CtHandle h, int32_t enable)
     h->touched_lines[1] = apron_lines;
     for (int k = 0; k < 2; k++) {
         const size_t words = (h->touched_lines[k] + 31) / 32;
-        HIPCHK(h, dmalloc(&h->d_touched[k], words));
+        HIPCHK(h, h->d_touched[k].alloc(words));
         HIPCHK(h, hipMemsetAsync(h->d_touched[k], 0, words * sizeof(uint32_t), h->stream));
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -3504,10 +3392,10 @@ extern "C" int ct_debug_fetch_probe(int32_t device, uint32_t log2_lines, uint32_
     if (log2_lines < 10 || log2_lines > 28 || hipSetDevice(device) != hipSuccess) {
         return fail(nullptr, CT_E_INVAL, "ct_debug_fetch_probe: bad device or size");
     }
-    DevTemp<uint8_t> buf;
-    DevTemp<unsigned long long> sum;
+    DevBuf<uint8_t> buf;
+    DevBuf<unsigned long long> sum;
     const size_t bytes = (size_t)128 << log2_lines;
-    if (dmalloc(&buf, bytes) != hipSuccess || dmalloc(&sum, 1) != hipSuccess) {
+    if (buf.alloc(bytes) != hipSuccess || sum.alloc(1) != hipSuccess) {
         return fail(nullptr, CT_E_NOMEM, "ct_debug_fetch_probe: out of device memory");
     }
     hipMemset(buf, 0, bytes);
@@ -3536,10 +3424,10 @@ extern "C" int ct_debug_fetch_probe_ws(int32_t device, uint32_t log2_threads, ui
     if (log2_threads < 10 || log2_threads > 28 || ws_lines < 1024 || ws_lines > (1ull << 28) || hipSetDevice(device) != hipSuccess) {
         return fail(nullptr, CT_E_INVAL, "ct_debug_fetch_probe_ws: bad device or size");
     }
-    DevTemp<uint8_t> buf;
-    DevTemp<unsigned long long> sum;
+    DevBuf<uint8_t> buf;
+    DevBuf<unsigned long long> sum;
     const size_t bytes = (size_t)128 * ws_lines;
-    if (dmalloc(&buf, bytes) != hipSuccess || dmalloc(&sum, 1) != hipSuccess) {
+    if (buf.alloc(bytes) != hipSuccess || sum.alloc(1) != hipSuccess) {
         return fail(nullptr, CT_E_NOMEM, "ct_debug_fetch_probe_ws: out of device memory");
     }
     hipMemset(buf, 0, bytes);
@@ -3583,8 +3471,8 @@ extern "C" int ct_debug_math_selftest(CtHandle h, int32_t which, uint64_t out[3]
         { 0u, 0x7f7fffffu, 0x80000000u, 0xff7fffffu },
     };
     const uint32_t *rg = ranges[which];
-    unsigned long long *d = nullptr;
-    HIPCHK(h, hipMalloc((void **)&d, 3 * sizeof(unsigned long long)));
+    DevBuf<unsigned long long> d;   // (freed on return, which on every path follows a wait for the stream or the device)
+    HIPCHK(h, d.alloc(3));
     const unsigned long long init[3] = { 0, 0, 0xffffffffull };
     hipError_t e = hipMemcpyAsync(d, init, sizeof init, hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) {
@@ -3600,7 +3488,6 @@ extern "C" int ct_debug_math_selftest(CtHandle h, int32_t which, uint64_t out[3]
     if (e == hipSuccess) {
         e = hipStreamSynchronize(h->stream);
     }
-    hipFree(d);
     HIPCHK(h, e);
     out[0] = r[0];
     out[1] = r[1];
@@ -3614,9 +3501,9 @@ extern "C" int ct_debug_math_eval(CtHandle h, int32_t fn, const uint32_t *in_bit
     if (!in_bits || !out_bits || n == 0 || n > (1u << 24) || fn < 0 || fn >= CT_MATH_FN_COUNT) {
         return fail(h, CT_E_INVAL, "ct_debug_math_eval: fn in [0, %d), 1 <= n <= 2^24, two words per item in and out", CT_MATH_FN_COUNT);
     }
-    DevTemp<uint32_t> d_in, d_out;
-    HIPCHK(h, dmalloc(&d_in, 2 * (size_t)n));
-    HIPCHK(h, dmalloc(&d_out, 2 * (size_t)n));
+    DevBuf<uint32_t> d_in, d_out;
+    HIPCHK(h, d_in.alloc(2 * (size_t)n));
+    HIPCHK(h, d_out.alloc(2 * (size_t)n));
     const size_t bytes = 2 * (size_t)n * sizeof(uint32_t);
     hipError_t e = hipMemcpyAsync(d_in, in_bits, bytes, hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) {
@@ -3637,8 +3524,8 @@ extern "C" int ct_debug_cdf_inversion(CtHandle h, uint32_t first_u24, uint32_t c
     if (!k_host_out || count == 0 || (uint64_t)first_u24 + count > (1ull << 24)) {
         return fail(h, CT_E_INVAL, "range must lie inside [0, 2^24)");
     }
-    uint32_t *d_k = nullptr;
-    HIPCHK(h, dmalloc(&d_k, count));
+    DevBuf<uint32_t> d_k;
+    HIPCHK(h, d_k.alloc(count));
     hipError_t e = launch_cdf_selftest(h->d_cdf, h->d_guide, first_u24, count, d_k, h->stream);
     if (e == hipSuccess) {
         e = hipMemcpyAsync(k_host_out, d_k, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream);
@@ -3646,8 +3533,18 @@ extern "C" int ct_debug_cdf_inversion(CtHandle h, uint32_t first_u24, uint32_t c
     if (e == hipSuccess) {
         e = hipStreamSynchronize(h->stream);
     }
-    hipFree(d_k);
     HIPCHK(h, e);
+    return CT_OK;
+}
+
+extern "C" int ct_debug_allocations(uint64_t out[4])
+{
+    if (!out) {
+        return CT_E_INVAL;
+    }
+    for (int i = 0; i < 4; i++) {
+        out[i] = g_live_allocations[i].load();
+    }
     return CT_OK;
 }
 

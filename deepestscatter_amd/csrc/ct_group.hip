@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../../include/cloudtrace.h"
+#include "ct_devmem.hpp"
 
 namespace {
 
@@ -100,10 +101,10 @@ __global__ void add_into_kernel(float4 *__restrict__ dst, const float4 *__restri
 struct CtGroup_ {
     std::vector<CtHandle> handles;
     std::vector<int> devices;
-    std::vector<float *> staging;       // per shard, on its device: [mean | M2], 2 * W*H float4
+    std::vector<ct::DevBuf<float>> staging;     // per shard, on its device: [mean | M2], 2 * W*H float4
     std::vector<hipStream_t> streams;   // per shard: the stream of the merge
     std::vector<ncclComm_t> comms;      // empty in the rehearsal mode (a device appears twice)
-    float *scratch = nullptr;           // rehearsal mode: landing buffer on the first device
+    ct::DevBuf<float> scratch;          // rehearsal mode: landing buffer on the first device
     uint32_t width = 0, height = 0, subframes = 0;
     bool merged = false;
     std::string error;
@@ -166,14 +167,14 @@ extern "C" int ct_group_destroy(CtGroup g)
             hipStreamSynchronize(g->streams[i]);
             hipStreamDestroy(g->streams[i]);
         }
-        if (i < g->staging.size() && g->staging[i]) {
-            hipFree(g->staging[i]);
+        if (i < g->staging.size()) {
+            g->staging[i].reset();   // (on its device, set above)
         }
         ct_destroy(g->handles[i]);
     }
     if (g->scratch) {
         hipSetDevice(g->devices[0]);
-        hipFree(g->scratch);
+        g->scratch.reset();
     }
     delete g;
     return CT_OK;
@@ -214,17 +215,16 @@ extern "C" int ct_group_create(const CtScene *scene, const int32_t *devices, uin
             return bail(rc);
         }
         g->handles.push_back(h);
-        float *st = nullptr;
+        ct::DevBuf<float> st;
         hipStream_t stream = nullptr;
-        if (hipSetDevice(devices[i]) != hipSuccess || hipMalloc((void **)&st, floats * sizeof(float)) != hipSuccess ||
-            hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess) {
-            g->staging.push_back(st);
-            g->streams.push_back(stream);
+        const bool ok = hipSetDevice(devices[i]) == hipSuccess && st.alloc(floats) == hipSuccess &&
+                        hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) == hipSuccess;
+        g->staging.push_back(std::move(st));
+        g->streams.push_back(stream);
+        if (!ok) {
             g->error = "out of device memory (merge staging buffer)";
             return bail(CT_E_NOMEM);
         }
-        g->staging.push_back(st);
-        g->streams.push_back(stream);
     }
     if (distinct) {
         if (!g_rccl.load()) {
@@ -240,7 +240,7 @@ extern "C" int ct_group_create(const CtScene *scene, const int32_t *devices, uin
         }
     } else {
         // rehearsal: several shards on one device (RCCL refuses that); merge with copies and adds on the first device
-        if (hipSetDevice(devices[0]) != hipSuccess || hipMalloc((void **)&g->scratch, floats * sizeof(float)) != hipSuccess) {
+        if (hipSetDevice(devices[0]) != hipSuccess || g->scratch.alloc(floats) != hipSuccess) {
             g->error = "out of device memory (merge scratch)";
             return bail(CT_E_NOMEM);
         }
@@ -435,7 +435,7 @@ extern "C" int ct_group_merge(CtGroup g)
     for (uint32_t i = 0; i < g->handles.size(); i++) {
         int rc = ct_copy_to_device(g->handles[i], CT_BUF_MEAN, g->staging[i], bytes);
         if (rc == CT_OK) {
-            rc = ct_copy_to_device(g->handles[i], CT_BUF_M2, (float4 *)g->staging[i] + n, bytes);
+            rc = ct_copy_to_device(g->handles[i], CT_BUF_M2, (float4 *)g->staging[i].get() + n, bytes);
         }
         if (rc != CT_OK) {
             return shard_fail(g, i, rc);
@@ -457,8 +457,8 @@ extern "C" int ct_group_merge(CtGroup g)
         (void)hipGetLastError();
         for (uint32_t i = 1; i < g->handles.size(); i++) {
             GHIP(g, hipMemcpyPeerAsync(g->scratch, g->devices[0], g->staging[i], g->devices[i], 2 * bytes, g->streams[0]));
-            hipLaunchKernelGGL(add_into_kernel, dim3(1024), dim3(256), 0, g->streams[0], (float4 *)g->staging[0],
-                               (const float4 *)g->scratch, 2 * n);
+            hipLaunchKernelGGL(add_into_kernel, dim3(1024), dim3(256), 0, g->streams[0], (float4 *)g->staging[0].get(),
+                               (const float4 *)g->scratch.get(), 2 * n);
             GHIP(g, hipGetLastError());
         }
         GHIP(g, hipStreamSynchronize(g->streams[0]));
@@ -486,7 +486,7 @@ extern "C" int ct_group_download(CtGroup g, int32_t which, void *dst_host, size_
         return gfail(g, CT_E_INVAL, "ct_group_download: CT_BUF_MEAN or CT_BUF_M2, %zu bytes", bytes);
     }
     GHIP(g, hipSetDevice(g->devices[0]));
-    GHIP(g, hipMemcpy(dst_host, (float4 *)g->staging[0] + (which == CT_BUF_M2 ? n : 0), bytes, hipMemcpyDeviceToHost));
+    GHIP(g, hipMemcpy(dst_host, (float4 *)g->staging[0].get() + (which == CT_BUF_M2 ? n : 0), bytes, hipMemcpyDeviceToHost));
     return CT_OK;
 }
 
@@ -507,7 +507,7 @@ extern "C" int ct_group_is_converged(CtGroup g, int32_t *converged_out, uint64_t
         return rc;
     }
     const size_t n = (size_t)g->width * g->height;
-    rc = ct_is_converged_buffers(g->handles[0], g->staging[0], (float *)((float4 *)g->staging[0] + n), g->subframes, converged_out,
+    rc = ct_is_converged_buffers(g->handles[0], g->staging[0], (float *)((float4 *)g->staging[0].get() + n), g->subframes, converged_out,
                                  unconverged_pixels_out);
     return rc == CT_OK ? CT_OK : shard_fail(g, 0, rc);
 }

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/cloudtrace.h"
+#include "ct_devmem.hpp"
 #include "ct_internal.hpp"
 
 using namespace ct;
@@ -61,36 +62,36 @@ struct CtHandle_ {
     CtTuning tune;         // the environment's knobs as they were at ct_create
     CtScene scene{};       // as given (host pointers are NOT retained)
     int device = 0;
-    hipStream_t own_stream = nullptr;
+    hipStream_t own_stream = nullptr;   // (release() destroys it after the delete: the buffers below are freed first)
     hipStream_t stream = nullptr;
-    hipEvent_t ev[3] = { nullptr, nullptr, nullptr };
+    Event ev[3];
 
     DevScene dev{};
     bool camera_set = false;
 
-    // device memory
-    uint8_t *d_density = nullptr, *d_inscatter = nullptr, *d_dist = nullptr, *d_dist_tmp = nullptr, *d_majorant = nullptr, *d_maj_cells = nullptr, *d_maj_codes = nullptr;
-    uint8_t *d_dbricks = nullptr, *d_ibricks = nullptr, *d_mbricks = nullptr, *d_tbricks = nullptr;
-    uint2 *d_mrows = nullptr;          // sparse march bricks: extent of every brick row (DevScene::m_rows)
-    uint8_t *d_mcoarse = nullptr;      // ... and the clearance of the coarse cells outside the extents
+    // device memory: every buffer is a member that owns it (ct_devmem.hpp), so deleting the handle frees them all
+    DevBuf<uint8_t> d_density, d_inscatter, d_dist, d_dist_tmp, d_majorant, d_maj_cells, d_maj_codes;
+    DevBuf<uint8_t> d_dbricks, d_ibricks, d_mbricks, d_tbricks;
+    DevBuf<uint2> d_mrows;             // sparse march bricks: extent of every brick row (DevScene::m_rows)
+    DevBuf<uint8_t> d_mcoarse;         // ... and the clearance of the coarse cells outside the extents
     size_t mbricks_dense_bytes = 0, mbricks_bytes = 0;
     int nee_skip_r = 0;   // radius of the march bricks' shadow-zero flags (0: none set)
     // kept from ct_create for ct_set_light, which has neither the density nor the Mie tables on the host any more
     uint32_t zero_faces = 0;   // empty boundary layers of the density (zero_faces(); launch_inscatter)
     bool mie_finite = true;    // both phase tables are finite (nee_skip_radius)
-    // CT_FLAG_VMM_BRICKS: d_mbricks is a reserved virtual range (not a hipMalloc), backed chunk by chunk
+    // CT_FLAG_VMM_BRICKS: d_mbricks holds a reserved virtual range (not a hipMalloc: release() detaches it), backed chunk by chunk
     struct VmmBricks {
         void *va = nullptr;
         size_t size = 0, chunk = 0;
         std::vector<hipMemGenericAllocationHandle_t> handles;   // one per chunk with memory of its own + the shared ones
         size_t real_chunks = 0, shared_chunks = 0, mapped_chunks = 0;
     } vmm;
-    uint8_t *d_pyramid = nullptr;     // density mip pyramid, built on first use (ct_collect_descriptors)
+    DevBuf<uint8_t> d_pyramid;        // density mip pyramid, built on first use (ct_collect_descriptors)
     MipPyramid pyramid{};
-    float *d_mie = nullptr, *d_chopped = nullptr, *d_cdf = nullptr;
-    uint16_t *d_guide = nullptr;
-    float4 *d_frame = nullptr, *d_mean = nullptr, *d_m2 = nullptr;
-    uchar4 *d_screen = nullptr;
+    DevBuf<float> d_mie, d_chopped, d_cdf;
+    DevBuf<uint16_t> d_guide;
+    DevBuf<float4> d_frame, d_mean, d_m2;
+    DevBuf<uchar4> d_screen;
     // Batches enqueued with ct_render_accumulate_async form a pipeline on the handle's stream (M = max_age):
     //     R1  R2 .. R(1+M) A1  R(2+M) A2  ...  (flush:) Rf A(n-M+1) .. An
     // The estimator launch R(k) does not run its surviving paths to their end when its job list is empty: it suspends
@@ -105,8 +106,8 @@ struct CtHandle_ {
     // A slot owns a region, its queue counters and its events; the suspended paths alternate between two buffers.
     static constexpr int kMaxRegions = 64;
     struct Slot {
-        uint32_t *queue = nullptr;
-        hipEvent_t ev_in = nullptr, ev_start = nullptr, ev_done = nullptr, ev_acc0 = nullptr, ev_acc1 = nullptr;
+        DevBuf<uint32_t> queue;
+        Event ev_in, ev_start, ev_done, ev_acc0, ev_acc1;
         bool pending = false;              // launched, kernel times not booked yet
         bool accumulated = false;          // its accumulate kernel has been enqueued (ev_acc0/1 valid)
         bool awaits_accumulate = false;    // in `waiting`: some of its subframes are still to be accumulated
@@ -134,44 +135,43 @@ struct CtHandle_ {
     // mean alone -- Camera::render's `if (!isConverged())` (Camera.cpp:179) without a host round trip per update.
     // d_freeze: converged_freeze_kernel's state words; freeze_host: their first four, copied back after every test (pinned).
     uint32_t stop_cadence = 0, stop_min = 100;
-    uint32_t *d_freeze = nullptr, *freeze_host = nullptr;
-    uint32_t *cont[2] = { nullptr, nullptr }; // suspended paths: launch k writes cont[k & 1], launch k+1 reads it
+    DevBuf<uint32_t> d_freeze;
+    HostBuf<uint32_t> freeze_host;
+    DevBuf<uint32_t> cont[2];                 // suspended paths: launch k writes cont[k & 1], launch k+1 reads it
     uint64_t launch_no = 0;                // estimator launches enqueued so far
     bool cont_live = false;                // the last launch may have suspended paths: the next one resumes them
-    float4 *d_frames_all = nullptr;        // the whole per-sample scratch
-    size_t frames_total = 0;               // float4 allocated
+    DevBuf<float4> d_frames_all;           // the whole per-sample scratch
     size_t slot_capacity = 0;              // float4 per region
     uint64_t scratch_cap_bytes = 0;        // 0 = CT_SCRATCH_GIB / the default; else what an out-of-memory allocation left us with
     uint32_t layout_S = 0;                 // batch size the regions were laid out for
-    uint32_t *left[2] = { nullptr, nullptr }; // job remainders handed on the same way (BatchArgs::left_out)
+    DevBuf<uint32_t> left[2];                 // job remainders handed on the same way (BatchArgs::left_out)
     size_t left_capacity = 0;              // entries per buffer: one per wave
-    uint32_t *d_cont_count = nullptr;      // [0,1] entries in cont[i], [2] resume cursor, [3,4] entries in left[i], [5] its cursor
-    unsigned long long *d_cont_total = nullptr; // paths handed from one launch to the next so far (ct_debug_suspended)
+    DevBuf<uint32_t> d_cont_count;         // [0,1] entries in cont[i], [2] resume cursor, [3,4] entries in left[i], [5] its cursor
+    DevBuf<unsigned long long> d_cont_total;    // paths handed from one launch to the next so far (ct_debug_suspended)
     size_t cont_capacity = 0;              // entries per buffer
-    hipEvent_t ev_flush0 = nullptr, ev_flush1 = nullptr;
+    Event ev_flush0, ev_flush1;
     bool continuation = true;              // CT_CONTINUATION=0: async batches run every path to its end
     int max_age_override = 0;              // CT_MAX_AGE=n: n + 1 regions whatever the batch size (0 = by batch duration)
     bool hand_on_jobs = true;              // CT_HAND_ON_JOBS=0: a wave finishes its own job before it suspends (A/B)
     bool serpentine = false;               // CT_SERPENTINE=1: short launches walk their job queues alternately forwards and backwards
     // work queue of the persistent kernel (rebuilt when the camera moves)
-    float4 *d_primary = nullptr;      // cached primary rays, 2 float4 per pixel
-    float4 *d_advance = nullptr;      // per pixel: pre-walked prefix of the primary march (MARCH estimator)
-    uint32_t *d_pixels = nullptr;     // this shard's box-hitting pixels, padded to groups of 64
-    float4 *d_start = nullptr;        // ... and what a sample of each of those slots starts from (BatchArgs::start; MARCH, CT_START_RECORDS=0: none)
+    DevBuf<float4> d_primary;         // cached primary rays, 2 float4 per pixel
+    DevBuf<float4> d_advance;         // per pixel: pre-walked prefix of the primary march (MARCH estimator)
+    DevBuf<uint32_t> d_pixels;        // this shard's box-hitting pixels, padded to groups of 64
+    DevBuf<float4> d_start;           // ... and what a sample of each of those slots starts from (BatchArgs::start; MARCH, CT_START_RECORDS=0: none)
     // per pixel: its class, 0 = misses the box, 1 = listed, 2 = through (hit_flags_kernel; device, pinned host copy); behind
     // the plane, at the next multiple of 8 bytes, one 64-bit word: the lookups of one sample of every through pixel, summed
-    uint8_t *d_hit = nullptr, *hit_host = nullptr;
-    uint32_t *d_cost = nullptr;       // measured per group: [0,n) sum of path costs, [n,2n) deepest path
-    uint32_t *d_touched[2] = { nullptr, nullptr };   // ct_debug_track_lines: one bit per line of the density / shadow arrays
+    DevBuf<uint8_t> d_hit;
+    HostBuf<uint8_t> hit_host;
+    DevBuf<uint32_t> d_cost;          // measured per group: [0,n) sum of path costs, [n,2n) deepest path
+    DevBuf<uint32_t> d_touched[2];    // ct_debug_track_lines: one bit per line of the density / shadow arrays
     size_t touched_lines[2] = { 0, 0 };
-    unsigned long long *d_timeline = nullptr;   // CT_TIMELINE=1: [start, end] of every wave of the last enqueued estimator launch (MARCH)
-    uint2 *d_cost_plane = nullptr;    // ... as the cost-measuring launch leaves them, per sample (BatchArgs::cost)
-    size_t cost_plane_capacity = 0;
-    uint32_t *d_job_group = nullptr, *d_job_sub = nullptr; // job list of the current batch size
-    uint32_t n_groups = 0, groups_capacity = 0;
-    uint32_t n_jobs = 0, jobs_capacity = 0, jobs_S = 0;
-    uint32_t *jobs_host_g = nullptr, *jobs_host_s = nullptr;   // the list as built on the host (pinned)
-    size_t jobs_host_capacity = 0;
+    DevBuf<unsigned long long> d_timeline;      // CT_TIMELINE=1: [start, end] of every wave of the last enqueued estimator launch (MARCH)
+    DevBuf<uint2> d_cost_plane;       // ... as the cost-measuring launch leaves them, per sample (BatchArgs::cost)
+    DevBuf<uint32_t> d_job_group, d_job_sub;               // job list of the current batch size 
+    uint32_t n_groups = 0;
+    uint32_t n_jobs = 0, jobs_S = 0;
+    HostBuf<uint32_t> jobs_host_g, jobs_host_s;                // the list as built on the host (pinned)
     bool jobs_brief = false;          // the list was laid out for short launches (short_batch)
     // The job list is built chunk by chunk: a chunk is a contiguous piece of `chunk_groups` groups of the cost-sorted
     // group order, and a launch renders all S subframes of ONE chunk into a scratch region of chunk_groups * 64 columns --
@@ -180,7 +180,7 @@ struct CtHandle_ {
     // instead makes every launch sweep the whole image and costs 9-14 %).
     uint32_t chunk_groups = 0, n_chunks = 0;
     std::vector<std::array<uint32_t, kQueues + 2>> chunk_q_begin;   // per chunk: job ranges of the queues (absolute indices)
-    uint32_t *d_group_rank = nullptr, *d_group_order = nullptr;     // place of a group in the job order / the group at a place
+    DevBuf<uint32_t> d_group_rank, d_group_order;                   // place of a group in the job order / the group at a place
     uint32_t jobs_hint = 0;           // batch size the caller asked for last (job lists are built for it)
     // subframes per job at most (cheap groups), and the bounces (x cost unit) a job's lane is expected to run.
     // Re-swept on the final kernels (8 / 256 before): +4.3 % at 512^3, +5.6 % at 1024^3, +2.6 % at 256^3, +1.3 % DELTA
@@ -212,9 +212,9 @@ struct CtHandle_ {
     unsigned long long host_paths = 0, host_hits = 0; // paths / box hits of the persistent path
     unsigned long long host_lookups = 0;  // density lookups of the samples of through pixels, which no kernel marches
     unsigned long long host_settled = 0;  // ... and their number (ct_debug_invariants: dealt and written include them)
-    uint32_t *d_queue = nullptr;
-    unsigned long long *d_counters = nullptr; // kCounterCount + 1 (unconverged) + kStatCount
-    float *d_colsum = nullptr, *d_avg = nullptr;
+    DevBuf<uint32_t> d_queue;
+    DevBuf<unsigned long long> d_counters;    // kCounterCount + 1 (unconverged) + kStatCount
+    DevBuf<float> d_colsum, d_avg;
     uint32_t reinhard_generation = 0;   // launches on d_avg's barrier counter (launch_reinhard)
 
     // CT_DEBUG_INVARIANTS=1: the diagnostics build of the estimator counts samples dealt / paths resumed / results
@@ -228,10 +228,9 @@ struct CtHandle_ {
     // milliseconds, so its device buffers stay (grown on demand; freeing one would wait for the whole device, i.e. for
     // the launches of the other scene setups in flight)
     struct PointBuffers {
-        CtPointRadianceTask *tasks = nullptr;
-        float4 *primary = nullptr, *frames = nullptr;
-        uint32_t *pixels = nullptr, *jg = nullptr, *js = nullptr;
-        size_t cap_tasks = 0, cap_primary = 0, cap_pixels = 0, cap_frames = 0, cap_jg = 0, cap_js = 0;
+        DevBuf<CtPointRadianceTask> tasks;
+        DevBuf<float4> primary, frames;
+        DevBuf<uint32_t> pixels, jg, js;
     } pt;
     bool point_order = true;             // CT_POINT_ORDER=0: jobs of 8 frames in task order over 8 queues, as until round 2 (A/B)
 
@@ -246,18 +245,19 @@ struct CtHandle_ {
     double dframe_scatter_ms = 0, dframe_gather_ms = 0;   // the last ct_descriptor_frame (ct_debug_descriptor_frame_time)
     // ct_network_render_*, ct_baked_render_* and the bake's chunks: the temporaries of a band stay with the handle (a frame is
     // many bands, a render many frames).  The baked renderer uses found / waves / direct only, reserved at the same sizes.
-    // found / waves / pos / dir / aux / out hold a band of band_cap pixels; desc holds desc_cap records, the largest count
+    // found / waves / pos / dir / aux / out hold a band of band_cap pixels; desc holds desc_records() records, the largest count
     // seen so far (or what the device gave: a band with more records goes through gather and network in pieces).  direct holds
-    // a band of direct_cap pixels and exists from the first call with CT_NET_ADD_SINGLE_SCATTER on.
+    // a band of direct.capacity() pixels and exists from the first call with CT_NET_ADD_SINGLE_SCATTER on.
     struct NetScratch {
-        float4 *found = nullptr, *direct = nullptr;
-        uint32_t *waves = nullptr;
-        float *pos = nullptr, *dir = nullptr, *aux = nullptr, *out = nullptr;
-        uint8_t *desc = nullptr;
-        size_t band_cap = 0, desc_cap = 0, direct_cap = 0;
+        DevBuf<float4> found, direct;
+        DevBuf<uint32_t> waves;
+        DevBuf<float> pos, dir, aux, out;
+        DevBuf<uint8_t> desc;
+        size_t band_cap = 0;             // (found .. out: six buffers at different multiples of it)
+        size_t desc_records() const { return desc.capacity() / CT_DESCRIPTOR_BYTES; }
         double ms[4] = { 0, 0, 0, 0 };   // the last ct_network_render_* call (ct_debug_network_render_time); a baked call leaves it
         // ct_network_render_shard_*: this shard's 8x8 tiles in ascending ty * tiles_x + tx (ct_shard_tiles), built on first use
-        uint32_t *tiles = nullptr;
+        DevBuf<uint32_t> tiles;
         uint32_t n_tiles = 0;
         bool tiles_built = false;
     } net;
@@ -316,32 +316,3 @@ int ensure_pyramid(CtHandle h);
             return rc_flush_;                          \
         }                                              \
     } while (0)
-
-template <typename T>
-hipError_t dmalloc(T **p, size_t count)
-{
-    return hipMalloc((void **)p, count * sizeof(T));
-}
-
-// A device temporary (move-only): allocated by dmalloc, freed when it goes out of scope -- which its user places after the
-// stream synchronise that follows the temporary's last use.
-template <typename T>
-struct DevTemp {
-    T *p = nullptr;
-    DevTemp() = default;
-    DevTemp(DevTemp &&o) noexcept : p(std::exchange(o.p, nullptr)) {}
-    ~DevTemp()
-    {
-        if (p) {
-            hipFree(p);
-        }
-    }
-    operator T *() const { return p; }
-    T *release() { return std::exchange(p, nullptr); }
-};
-
-template <typename T>
-hipError_t dmalloc(DevTemp<T> *t, size_t count)
-{
-    return dmalloc(&t->p, count);
-}

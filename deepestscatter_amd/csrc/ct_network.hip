@@ -37,6 +37,7 @@
 #include <new>
 #include <vector>
 
+#include "ct_devmem.hpp"
 #include "ct_network.hpp"
 
 namespace {
@@ -464,9 +465,9 @@ int failf(int code, char *err, size_t err_len, const char *fmt, ...)
 struct CtNetwork_ {
     int device = 0;
     Geometry geo{};
-    uint16_t *d_stream = nullptr;
-    float *d_bias = nullptr;
-    hipEvent_t ev[2] = { nullptr, nullptr };
+    ct::DevBuf<uint16_t> d_stream;
+    ct::DevBuf<float> d_bias;
+    ct::Event ev[2];
     double last_ms = 0;
 };
 
@@ -520,12 +521,12 @@ int network_create(int device, const CtNetworkDesc *d, CtNetwork *out, char *err
         return failf(CT_E_NOMEM, err, err_len, "ct_network_create: out of host memory");
     }
     const size_t sbytes = p.stream.size() * sizeof(uint16_t), bbytes = p.bias.size() * sizeof(float);
-    hipError_t e = hipMalloc((void **)&n->d_stream, sbytes);
-    e = e == hipSuccess ? hipMalloc((void **)&n->d_bias, bbytes) : e;
+    hipError_t e = n->d_stream.alloc(p.stream.size());
+    e = e == hipSuccess ? n->d_bias.alloc(p.bias.size()) : e;
     e = e == hipSuccess ? hipMemcpy(n->d_stream, p.stream.data(), sbytes, hipMemcpyHostToDevice) : e;
     e = e == hipSuccess ? hipMemcpy(n->d_bias, p.bias.data(), bbytes, hipMemcpyHostToDevice) : e;
-    e = e == hipSuccess ? hipEventCreate(&n->ev[0]) : e;
-    e = e == hipSuccess ? hipEventCreate(&n->ev[1]) : e;
+    e = e == hipSuccess ? n->ev[0].create() : e;
+    e = e == hipSuccess ? n->ev[1].create() : e;
     if (e != hipSuccess) {
         ct_network_destroy(n);
         return failf(e == hipErrorOutOfMemory ? CT_E_NOMEM : CT_E_HIP, err, err_len, "ct_network_create: %s", hipGetErrorString(e));
@@ -559,7 +560,7 @@ int network_eval(CtNetwork n, hipStream_t stream, const uint8_t *descriptors_dev
     if (((uintptr_t)descriptors_dev & 3u) || ((uintptr_t)aux_dev & 3u) || ((uintptr_t)out_dev & 3u)) {
         return failf(CT_E_INVAL, err, err_len, "ct_network_eval: the device arrays must be 4-byte aligned");
     }
-    NetArgs a{ reinterpret_cast<const u32x4 *>(n->d_stream), n->d_bias, descriptors_dev, aux_dev, out_dev, count, n->geo.aux,
+    NetArgs a{ reinterpret_cast<const u32x4 *>(n->d_stream.get()), n->d_bias, descriptors_dev, aux_dev, out_dev, count, n->geo.aux,
                n->geo.head, n->geo.groups() };
     const uint32_t blocks = (count + kWaves * kTileRecords - 1) / (kWaves * kTileRecords);
     n->last_ms = 0;
@@ -597,17 +598,10 @@ extern "C" int ct_network_destroy(CtNetwork n)
     }
     int prev = 0;
     const bool switched = hipGetDevice(&prev) == hipSuccess && prev != n->device && hipSetDevice(n->device) == hipSuccess;
-    for (hipEvent_t ev : n->ev) {
-        if (ev) {
-            hipEventDestroy(ev);
-        }
-    }
-    hipFree(n->d_stream);
-    hipFree(n->d_bias);
+    delete n;   // (its buffers and events: on its device)
     if (switched) {
         hipSetDevice(prev);
     }
-    delete n;
     return CT_OK;
 }
 

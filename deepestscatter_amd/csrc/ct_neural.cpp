@@ -82,7 +82,7 @@ int ct::ensure_pyramid(CtHandle h)
     if (total >= (1ull << 32)) {
         return fail(h, CT_E_INVAL, "volume too large for the mip pyramid");
     }
-    HIPCHK(h, dmalloc(&h->d_pyramid, total));
+    HIPCHK(h, h->d_pyramid.alloc(total));
     HIPCHK(h, hipMemcpyAsync(h->d_pyramid, h->d_density, (size_t)nx * ny * nz, hipMemcpyDeviceToDevice, h->stream));
     for (uint32_t l = 1; l < levels; l++) {
         HIPCHK(h, launch_mip_level(h->d_pyramid + mp.offset[l - 1], mp.nx[l - 1], mp.ny[l - 1], mp.nz[l - 1],
@@ -105,12 +105,12 @@ extern "C" int ct_collect_descriptors(CtHandle h, const float *positions_host, c
         return prc;
     }
     const DescriptorScale ds = descriptor_scale(h);
-    DevTemp<float> d_pos, d_dir;
-    DevTemp<uint8_t> d_out;
+    DevBuf<float> d_pos, d_dir;
+    DevBuf<uint8_t> d_out;
     return drained(h, [&]() -> int {
-        HIPCHK(h, dmalloc(&d_pos, 3 * (size_t)count));
-        HIPCHK(h, dmalloc(&d_dir, 3 * (size_t)count));
-        HIPCHK(h, dmalloc(&d_out, (size_t)count * CT_DESCRIPTOR_BYTES));
+        HIPCHK(h, d_pos.alloc(3 * (size_t)count));
+        HIPCHK(h, d_dir.alloc(3 * (size_t)count));
+        HIPCHK(h, d_out.alloc((size_t)count * CT_DESCRIPTOR_BYTES));
         HIPCHK(h, hipMemcpyAsync(d_pos, positions_host, 3 * (size_t)count * sizeof(float), hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipMemcpyAsync(d_dir, directions_host, 3 * (size_t)count * sizeof(float), hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, launch_descriptors(h->dev, h->pyramid, d_pos, d_dir, count, ds.level0, ds.voxel_m, h->scene.cloud_size_m,
@@ -157,26 +157,26 @@ extern "C" int ct_descriptor_frame(CtHandle h, uint32_t subframe_id, const uint3
     }
     const uint32_t rw = x1 - x0, n = rw * (y1 - y0), n_pad = (n + 255u) / 256u * 256u;
     const DescriptorScale ds = descriptor_scale(h);
-    DevTemp<float4> d_found;
-    DevTemp<uint32_t> d_waves;
-    DevTemp<float> d_pos, d_dir;
+    DevBuf<float4> d_found;
+    DevBuf<uint32_t> d_waves;
+    DevBuf<float> d_pos, d_dir;
     h->dframe_scatter_ms = h->dframe_gather_ms = 0;
     return drained(h, [&]() -> int {
         // every temporary before any kernel
         const size_t held = std::max<size_t>(1, std::min<size_t>(capacity, n));   // records the compacting write can produce
-        HIPCHK(h, dmalloc(&d_found, n_pad));
-        HIPCHK(h, dmalloc(&d_waves, n_pad / 64u + 1u));
+        HIPCHK(h, d_found.alloc(n_pad));
+        HIPCHK(h, d_waves.alloc(n_pad / 64u + 1u));
         if (!positions_dev) {
-            HIPCHK(h, dmalloc(&d_pos, 3 * held));
+            HIPCHK(h, d_pos.alloc(3 * held));
         }
         if (!directions_dev) {
-            HIPCHK(h, dmalloc(&d_dir, 3 * held));
+            HIPCHK(h, d_dir.alloc(3 * held));
         }
         const int prc = ensure_pyramid(h);
         if (prc != CT_OK) {
             return prc;
         }
-        float *pos = positions_dev ? positions_dev : d_pos.p, *dir = directions_dev ? directions_dev : d_dir.p;
+        float *pos = positions_dev ? positions_dev : d_pos.get(), *dir = directions_dev ? directions_dev : d_dir.get();
         uint32_t count = 0;
         const int rc = flights_counted(h, rect_band(x0, y0, rw, y1 - y0), { d_found, d_waves, nullptr }, subframe_id, capacity, pos, dir,
                                        pixels_dev, &h->dframe_scatter_ms, &count);
@@ -293,44 +293,35 @@ static int net_reserve(CtHandle h, size_t band_pixels, bool direct)
 {
     CtHandle_::NetScratch &s = h->net;
     const size_t n_pad = (band_pixels + 255u) / 256u * 256u;
-    if (direct && n_pad > s.direct_cap) {
-        DevTemp<float4> sun;
-        HIPCHK(h, dmalloc(&sun, n_pad));
-        if (s.direct) {
-            hipFree(s.direct);
-        }
-        s.direct = sun.release();
-        s.direct_cap = n_pad;
+    // (allocate, then swap, here and in net_grow_descriptors)
+    if (direct && n_pad > s.direct.capacity()) {
+        DevBuf<float4> sun;
+        HIPCHK(h, sun.alloc(n_pad));
+        s.direct = std::move(sun);
     }
     if (n_pad > s.band_cap) {
-        DevTemp<float4> found;
-        DevTemp<uint32_t> waves;
-        DevTemp<float> pos, dir, aux, out;
-        HIPCHK(h, dmalloc(&found, n_pad));
-        HIPCHK(h, dmalloc(&waves, n_pad / 64u + 1u));
-        HIPCHK(h, dmalloc(&pos, 3 * n_pad));
-        HIPCHK(h, dmalloc(&dir, 3 * n_pad));
-        HIPCHK(h, dmalloc(&aux, n_pad));
-        HIPCHK(h, dmalloc(&out, n_pad));
-        for (void *old : { (void *)s.found, (void *)s.waves, (void *)s.pos, (void *)s.dir, (void *)s.aux, (void *)s.out }) {
-            if (old) {
-                hipFree(old);
-            }
-        }
-        s.found = found.release();
-        s.waves = waves.release();
-        s.pos = pos.release();
-        s.dir = dir.release();
-        s.aux = aux.release();
-        s.out = out.release();
+        DevBuf<float4> found;
+        DevBuf<uint32_t> waves;
+        DevBuf<float> pos, dir, aux, out;
+        HIPCHK(h, found.alloc(n_pad));
+        HIPCHK(h, waves.alloc(n_pad / 64u + 1u));
+        HIPCHK(h, pos.alloc(3 * n_pad));
+        HIPCHK(h, dir.alloc(3 * n_pad));
+        HIPCHK(h, aux.alloc(n_pad));
+        HIPCHK(h, out.alloc(n_pad));
+        s.found = std::move(found);
+        s.waves = std::move(waves);
+        s.pos = std::move(pos);
+        s.dir = std::move(dir);
+        s.aux = std::move(aux);
+        s.out = std::move(out);
         s.band_cap = n_pad;
     }
-    if (s.desc_cap == 0) {
+    if (!s.desc) {
         // (CT_NET_DESC_RECORDS: the array never holds more records than this -- what a device without room for the growth leaves
         // a handle with, for the test that runs a band in pieces)
         const size_t first = std::min<size_t>(std::min<size_t>(n_pad, 4096), net_descriptor_limit(h));
-        HIPCHK(h, dmalloc(&s.desc, first * CT_DESCRIPTOR_BYTES));
-        s.desc_cap = first;
+        HIPCHK(h, s.desc.alloc(first * CT_DESCRIPTOR_BYTES));
     }
     return CT_OK;
 }
@@ -341,17 +332,15 @@ static void net_grow_descriptors(CtHandle h, size_t count)
 {
     CtHandle_::NetScratch &s = h->net;
     count = std::min(count, net_descriptor_limit(h));
-    if (count <= s.desc_cap) {
+    if (count <= s.desc_records()) {
         return;
     }
-    uint8_t *bigger = nullptr;
-    if (dmalloc(&bigger, count * CT_DESCRIPTOR_BYTES) != hipSuccess) {
+    DevBuf<uint8_t> bigger;
+    if (bigger.alloc(count * CT_DESCRIPTOR_BYTES) != hipSuccess) {
         (void)hipGetLastError();
         return;
     }
-    hipFree(s.desc);
-    s.desc = bigger;
-    s.desc_cap = count;
+    s.desc = std::move(bigger);
 }
 
 // The shard's tile list on the device, from ct_shard_tiles, once per handle.  The stream is idle.
@@ -369,47 +358,51 @@ static int net_ensure_tiles(CtHandle h)
     if (ct_shard_tiles(h->scene.width, h->scene.height, h->scene.shard_index, h->scene.shard_count, list.data(), count, &count) != CT_OK) {
         return fail(h, CT_E_INVAL, "internal: ct_shard_tiles refused the handle's own frame");
     }
-    DevTemp<uint32_t> dev;
-    HIPCHK(h, dmalloc(&dev, list.size()));
-    HIPCHK(h, hipMemcpy(dev.p, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    s.tiles = dev.release();
+    DevBuf<uint32_t> dev;
+    HIPCHK(h, dev.alloc(list.size()));
+    HIPCHK(h, hipMemcpy(dev, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    s.tiles = std::move(dev);
     s.n_tiles = count;
     s.tiles_built = true;
     return CT_OK;
 }
 
 // ---- the network baked into a probe table (ct_network_bake, ct_baked_render_*) -----------------------------------------
-struct CtBake_ {
+// What a bake of the table writes besides the table: ct_bake_update and ct_bake_retrace fill a second table, and a failure puts
+// this part back as it was.
+struct BakeState {
+    float l[3] = {}, a[3] = {}, b[3] = {};   // the light the table holds and the azimuth frame
+    uint64_t epoch = 0;                      // the handle's light epoch at the bake
+    double gather_ms = 0, network_ms = 0, mask_ms = 0;
+    uint32_t samples = 0;                    // a traced bake: experiments folded into every stored entry of an active node
+    uint64_t paths = 0;
+    double trace_ms = 0, fold_ms = 0;
+};
+
+struct CtBake_ : BakeState {
     CtHandle h = nullptr;
     int device = 0;
     uint32_t grid[3] = { 0, 0, 0 }, azimuths = 0, cosines = 0;
     uint64_t entries = 0;
-    float *d_table = nullptr;
-    float l[3] = {}, a[3] = {}, b[3] = {};   // the light the table holds and the azimuth frame
+    DevBuf<float> d_table;
     float cosine[64] = {};
-    uint64_t epoch = 0;                      // the handle's light epoch at the bake
-    double gather_ms = 0, network_ms = 0;
     // ct_network_bake_sparse: only the probes of the active position nodes are baked.  The density of a live handle
     // never changes, so the mask and the list are made once and ct_bake_update reuses them.
     bool sparse = false;
     uint32_t margin = 0;                     // M
     uint64_t active = 0;                     // active nodes
-    uint8_t *d_nodes = nullptr;              // one byte per node
-    uint32_t *d_list = nullptr;              // the active nodes, ascending
-    float *d_probe = nullptr;                // the position nodes of x, y, z and the Nphi probe directions (bake_probe's floats)
-    double mask_ms = 0;
+    DevBuf<uint8_t> d_nodes;                 // one byte per node
+    DevBuf<uint32_t> d_list;                 // the active nodes, ascending
+    DevBuf<float> d_probe;                   // the position nodes of x, y, z and the Nphi probe directions (bake_probe's floats)
     // ct_network_bake_compact: a sparse bake whose table holds a zero block and then the blocks of the active nodes
     // in the list's order; d_slots finds a node's block.  `stored` is the floats d_table holds (every other bake: entries).
     bool compact = false;
     uint64_t stored = 0;
-    uint32_t *d_slots = nullptr;             // one word per node: 1 + its place in the list, 0 for an inactive node
+    DevBuf<uint32_t> d_slots;                // one word per node: 1 + its place in the list, 0 for an inactive node
     // ct_bake_traced: the entries are means of the path tracer's point estimator, no network.  A traced bake of
     // any kind has d_probe (its position nodes) and d_dirs, the Nphi x Nc x 3 direction table of its frame.
     bool traced = false;
-    uint32_t samples = 0;                    // experiments folded into every stored entry of an active node
-    uint64_t paths = 0;
-    double trace_ms = 0, fold_ms = 0;
-    float *d_dirs = nullptr;
+    DevBuf<float> d_dirs;
 };
 
 static uint64_t bake_probes_total(const CtBake_ *b)
@@ -481,8 +474,8 @@ static BakeTable bake_table(const CtBake_ *b)
 struct BakeMask {
     std::vector<uint32_t> host_ranges;   // lo | hi << 16 per cell of x, then y, then z
     uint32_t margin = 0, slab = 0;
-    DevTemp<uint32_t> ranges, waves, list, slots;   // slots: only with bake_mask_reserve's `slots`
-    DevTemp<uint8_t> tmp_x, tmp_xy, cells, nodes;
+    DevBuf<uint32_t> ranges, waves, list, slots;   // slots: only with bake_mask_reserve's `slots`
+    DevBuf<uint8_t> tmp_x, tmp_xy, cells, nodes;
 };
 
 static size_t bake_mask_waves(uint64_t nodes)
@@ -509,15 +502,15 @@ static int bake_mask_reserve(CtHandle h, const uint32_t grid[3], BakeMask &m, bo
     // (CT_BAKE_MASK_BYTES: the most the first temporary may take; a volume whose planes need more goes through in slabs of z)
     const size_t cap = (size_t)knob_int(h->tune.BAKE_MASK_BYTES, 1, 1 << 30, 64 << 20), plane = (size_t)dims[1] * cx;
     m.slab = (uint32_t)std::min<size_t>(dims[2], std::max<size_t>(1, cap / plane));
-    HIPCHK(h, dmalloc(&m.ranges, m.host_ranges.size()));
-    HIPCHK(h, dmalloc(&m.tmp_x, m.slab * plane));
-    HIPCHK(h, dmalloc(&m.tmp_xy, m.slab * cy * cx));
-    HIPCHK(h, dmalloc(&m.cells, cz * cy * cx));
-    HIPCHK(h, dmalloc(&m.nodes, nodes));
-    HIPCHK(h, dmalloc(&m.waves, bake_mask_waves(nodes)));
-    HIPCHK(h, dmalloc(&m.list, nodes));
+    HIPCHK(h, m.ranges.alloc(m.host_ranges.size()));
+    HIPCHK(h, m.tmp_x.alloc(m.slab * plane));
+    HIPCHK(h, m.tmp_xy.alloc(m.slab * cy * cx));
+    HIPCHK(h, m.cells.alloc(cz * cy * cx));
+    HIPCHK(h, m.nodes.alloc(nodes));
+    HIPCHK(h, m.waves.alloc(bake_mask_waves(nodes)));
+    HIPCHK(h, m.list.alloc(nodes));
     if (slots) {
-        HIPCHK(h, dmalloc(&m.slots, nodes));
+        HIPCHK(h, m.slots.alloc(nodes));
     }
     return CT_OK;
 }
@@ -664,7 +657,7 @@ static int bake_run(CtHandle h, CtNetwork n, CtBake_ *b, float *table)
                 return rc;
             }
             for (uint32_t at = 0; at < count;) {
-                const uint32_t piece = (uint32_t)std::min<size_t>(count - at, s.desc_cap);
+                const uint32_t piece = (uint32_t)std::min<size_t>(count - at, s.desc_records());
                 float ms = 0;
                 HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
                 HIPCHK(h, launch_descriptors(h->dev, h->pyramid, s.pos + 3 * (size_t)at, s.dir + 3 * (size_t)at, piece, ds.level0, ds.voxel_m,
@@ -734,18 +727,6 @@ static uint32_t bake_trace_budget(CtHandle h)
     return (uint32_t)knob_int(h->tune.BAKE_TRACE_RESULTS, 64, 1 << 26, 1 << 24);
 }
 
-struct TraceEvents {
-    hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
-    ~TraceEvents()
-    {
-        for (hipEvent_t e : ev) {
-            if (e) {
-                hipEventDestroy(e);
-            }
-        }
-    }
-};
-
 // Experiments b->samples + 1 .. b->samples + samples of every stored entry of an active node, folded into `table` (b->stored
 // floats, which hold the means of b->samples experiments).  The stream is idle and the tables of b's frame are uploaded.  The
 // entries go through in chunks of at most 2^20, a chunk's samples in passes that keep at most the budget of results; the
@@ -762,9 +743,9 @@ static int bake_trace(CtHandle h, CtBake_ *b, float *table, uint32_t samples)
     const uint32_t chunk = (uint32_t)std::min<uint64_t>(total, std::min<uint32_t>(budget, 1u << 20));
     DevScene sc = h->dev;
     sc.mode = CT_MODE_SUN_MULTIPLE_SCATTER;
-    TraceEvents te;
-    for (hipEvent_t &e : te.ev) {
-        HIPCHK(h, hipEventCreate(&e));
+    Event ev[4];
+    for (Event &e : ev) {
+        HIPCHK(h, e.create());
     }
     CtHandle_::PointBuffers &pt = h->pt;
     const double render_before = h->render_ms;
@@ -788,23 +769,23 @@ static int bake_trace(CtHandle h, CtBake_ *b, float *table, uint32_t samples)
             const int rc = point_launch(
                 h, sc, a.n, done + 1u, passes,
                 [&]() -> int {
-                    HIPCHK(h, hipEventRecord(te.ev[0], h->stream));
+                    HIPCHK(h, hipEventRecord(ev[0], h->stream));
                     HIPCHK(h, launch_bake_trace_tasks(sc, a, pt.primary, pt.pixels, h->stream));
-                    HIPCHK(h, hipEventRecord(te.ev[1], h->stream));
+                    HIPCHK(h, hipEventRecord(ev[1], h->stream));
                     return CT_OK;
                 },
                 [&]() -> int {
-                    HIPCHK(h, hipEventRecord(te.ev[2], h->stream));
+                    HIPCHK(h, hipEventRecord(ev[2], h->stream));
                     HIPCHK(h, launch_bake_trace_fold(a, pt.frames, a.n_pad, passes, done, table, h->stream));
-                    HIPCHK(h, hipEventRecord(te.ev[3], h->stream));
+                    HIPCHK(h, hipEventRecord(ev[3], h->stream));
                     return CT_OK;
                 });
             if (rc != CT_OK) {
                 return rc;
             }
             float ms0 = 0, ms1 = 0;
-            HIPCHK(h, hipEventElapsedTime(&ms0, te.ev[0], te.ev[1]));
-            HIPCHK(h, hipEventElapsedTime(&ms1, te.ev[2], te.ev[3]));
+            HIPCHK(h, hipEventElapsedTime(&ms0, ev[0], ev[1]));
+            HIPCHK(h, hipEventElapsedTime(&ms1, ev[2], ev[3]));
             fold_ms += (double)ms0 + (double)ms1;
         }
     }
@@ -813,16 +794,6 @@ static int bake_trace(CtHandle h, CtBake_ *b, float *table, uint32_t samples)
     b->trace_ms = h->render_ms - render_before;
     b->fold_ms = fold_ms;
     return CT_OK;
-}
-
-static void bake_free(CtBake_ *b)
-{
-    for (void *p : { (void *)b->d_table, (void *)b->d_nodes, (void *)b->d_list, (void *)b->d_probe, (void *)b->d_slots, (void *)b->d_dirs }) {
-        if (p) {
-            hipFree(p);
-        }
-    }
-    delete b;
 }
 
 // ct_network_bake, ct_network_bake_sparse and ct_network_bake_compact: one validation, one order of errors.  trace_samples:
@@ -889,22 +860,22 @@ static int bake_create(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtBake *out
     for (uint32_t k = 0; k < b->cosines; k++) {
         b->cosine[k] = (float)(-1.0 + 2.0 * (double)k / (double)(b->cosines - 1u));
     }
-    if (!compact && dmalloc(&b->d_table, (size_t)entries) != hipSuccess) {   // (before the first kernel)
+    if (!compact && b->d_table.alloc((size_t)entries) != hipSuccess) {   // (before the first kernel)
         (void)hipGetLastError();
         delete b;
         return fail(h, CT_E_NOMEM, "%s: no device memory for a table of %llu entries", who, (unsigned long long)entries);
     }
-    if (traced && (dmalloc(&b->d_dirs, 3 * (size_t)b->azimuths * b->cosines) != hipSuccess ||
-                   (!sparse && dmalloc(&b->d_probe, b->grid[0] + b->grid[1] + b->grid[2] + 3 * (size_t)b->azimuths) != hipSuccess))) {
+    if (traced && (b->d_dirs.alloc(3 * (size_t)b->azimuths * b->cosines) != hipSuccess ||
+                   (!sparse && b->d_probe.alloc(b->grid[0] + b->grid[1] + b->grid[2] + 3 * (size_t)b->azimuths) != hipSuccess))) {
         (void)hipGetLastError();
-        bake_free(b);
+        delete b;
         return fail(h, CT_E_NOMEM, "%s: no device memory for the direction and probe tables", who);
     }
     double mask_ms = 0;
     if (sparse) {   // the mask's temporaries, the node bytes, the list, the slots and the record tables: all before the first kernel, too
         BakeMask m;
         rc = bake_mask_reserve(h, b->grid, m, compact);
-        if (rc == CT_OK && dmalloc(&b->d_probe, b->grid[0] + b->grid[1] + b->grid[2] + 3 * (size_t)b->azimuths) != hipSuccess) {
+        if (rc == CT_OK && b->d_probe.alloc(b->grid[0] + b->grid[1] + b->grid[2] + 3 * (size_t)b->azimuths) != hipSuccess) {
             (void)hipGetLastError();
             rc = fail(h, CT_E_NOMEM, "%s: no device memory for the probe tables", who);
         }
@@ -919,22 +890,22 @@ static int bake_create(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtBake *out
             if (b->stored > (1ull << 26)) {
                 rc = fail(h, CT_E_INVAL, "%s: %u active nodes of %llu store %llu entries, a table holds at most 2^26 (%llu)", who, active,
                           (unsigned long long)(entries / b->azimuths / b->cosines), (unsigned long long)b->stored, 1ull << 26);
-            } else if (dmalloc(&b->d_table, (size_t)b->stored) != hipSuccess) {
+            } else if (b->d_table.alloc((size_t)b->stored) != hipSuccess) {
                 (void)hipGetLastError();
                 rc = fail(h, CT_E_NOMEM, "%s: no device memory for a table of %llu stored entries", who, (unsigned long long)b->stored);
             }
         }
         if (rc != CT_OK) {
-            bake_free(b);
+            delete b;
             return rc;
         }
         b->sparse = true;
         b->compact = compact;
         b->margin = m.margin;
         b->active = active;
-        b->d_nodes = m.nodes.release();
-        b->d_list = m.list.release();
-        b->d_slots = m.slots.release();   // (nullptr unless compact)
+        b->d_nodes = std::move(m.nodes);
+        b->d_list = std::move(m.list);
+        b->d_slots = std::move(m.slots);   // (empty unless compact)
     }
     bake_frame(h, b);
     if (traced) {
@@ -949,7 +920,7 @@ static int bake_create(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtBake *out
     }
     b->mask_ms += mask_ms;   // (bake_run has set it to its record kernel's time)
     if (rc != CT_OK) {
-        bake_free(b);
+        delete b;
         return rc;
     }
     *out = b;
@@ -1140,20 +1111,19 @@ extern "C" int ct_bake_update(CtHandle h, CtNetwork n, CtBake b)
         return rc;
     }
     // into a second table: a failure leaves the old table, its light and its frame as they were
-    DevTemp<float> fresh;
-    if (dmalloc(&fresh, (size_t)b->stored) != hipSuccess) {   // (a compact bake: its stored table; list and slots are reused)
+    DevBuf<float> fresh;
+    if (fresh.alloc((size_t)b->stored) != hipSuccess) {   // (a compact bake: its stored table; list and slots are reused)
         (void)hipGetLastError();
         return fail(h, CT_E_NOMEM, "%s: no device memory for a table of %llu entries", who, (unsigned long long)b->stored);
     }
-    const CtBake_ before = *b;
+    const BakeState before = *b;
     bake_frame(h, b);
     rc = bake_run(h, n, b, fresh);
     if (rc != CT_OK) {
-        *b = before;
+        static_cast<BakeState &>(*b) = before;
         return rc;
     }
-    hipFree(b->d_table);
-    b->d_table = fresh.release();
+    b->d_table = std::move(fresh);
     return CT_OK;
 }
 
@@ -1213,12 +1183,12 @@ extern "C" int ct_bake_retrace(CtHandle h, CtBake b, uint32_t samples)
         return rc;
     }
     // into a second table, as ct_bake_update: a failure leaves the old table, its frame and its sample count as they were
-    DevTemp<float> fresh;
-    if (dmalloc(&fresh, (size_t)b->stored) != hipSuccess) {
+    DevBuf<float> fresh;
+    if (fresh.alloc((size_t)b->stored) != hipSuccess) {
         (void)hipGetLastError();
         return fail(h, CT_E_NOMEM, "%s: no device memory for a table of %llu entries", who, (unsigned long long)b->stored);
     }
-    const CtBake_ before = *b;
+    const BakeState before = *b;
     bake_frame(h, b);
     b->samples = 0;
     b->paths = 0;
@@ -1230,14 +1200,13 @@ extern "C" int ct_bake_retrace(CtHandle h, CtBake b, uint32_t samples)
     });
     if (rc != CT_OK) {
         const std::string text = h->error;
-        *b = before;
+        static_cast<BakeState &>(*b) = before;
         if (bake_upload_trace_tables(h, b) == CT_OK) {   // (the old frame's tables again; otherwise that failure is the one to report)
             h->error = text;
         }
         return rc;
     }
-    hipFree(b->d_table);
-    b->d_table = fresh.release();
+    b->d_table = std::move(fresh);
     return CT_OK;
 }
 
@@ -1278,7 +1247,7 @@ extern "C" int ct_bake_destroy(CtBake b)
         return CT_OK;
     }
     hipSetDevice(b->device);
-    bake_free(b);
+    delete b;
     return CT_OK;
 }
 
@@ -1483,7 +1452,7 @@ static int net_band(CtHandle h, const NetCall &c, uint32_t sid, uint32_t unit0, 
     }
     net_grow_descriptors(h, count);
     for (uint32_t at = 0; at < count;) {
-        const uint32_t piece = (uint32_t)std::min<size_t>(count - at, s.desc_cap);
+        const uint32_t piece = (uint32_t)std::min<size_t>(count - at, s.desc_records());
         float ms = 0;
         HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
         HIPCHK(h, launch_descriptors(h->dev, h->pyramid, s.pos + 3 * (size_t)at, s.dir + 3 * (size_t)at, piece, c.ds.level0, c.ds.voxel_m,
@@ -1719,7 +1688,7 @@ extern "C" int ct_debug_network_scratch(CtHandle h, uint64_t out[12])
         out[i] = (uint64_t)(uintptr_t)ptrs[i];
     }
     out[9] = s.band_cap;
-    out[10] = s.desc_cap;
-    out[11] = s.direct_cap;
+    out[10] = s.desc_records();
+    out[11] = s.direct.capacity();
     return CT_OK;
 }

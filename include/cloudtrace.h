@@ -1105,6 +1105,12 @@ CT_API uint32_t ct_tile_owner(uint32_t tile_x, uint32_t tile_y, uint32_t shard_c
 CT_API int ct_shard_tiles(uint32_t width, uint32_t height, uint32_t shard_index, uint32_t shard_count, uint32_t *tiles_out,
                           uint32_t capacity, uint32_t *count_out);
 
+/* Diagnostic, process-wide (no handle): what the library holds right now.  out[0] = device buffers, out[1] = their bytes,
+ * out[2] = pinned host buffers, out[3] = their bytes.  Every allocation of the library has exactly one owner, which counts it
+ * when it allocates and when it frees, so the difference around a create ... destroy pair is exactly zero in all four.  The
+ * physical chunks behind CT_FLAG_VMM_BRICKS (experiments build) are not counted.  CT_E_INVAL: out == NULL. */
+CT_API int ct_debug_allocations(uint64_t out[4]);
+
 /* Synthetic cloud of SURVEY section 8(d): 5-octave gradient-noise fBm x ellipsoidal falloff,
  * thresholded, quantised by ct_quantize_volume's rule into an n^3 texture (payload n-2). */
 CT_API int ct_make_procedural_cloud(uint32_t n, uint32_t seed, uint8_t *texture_host_out);

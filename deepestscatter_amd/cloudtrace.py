@@ -797,8 +797,8 @@ class CloudTracer:
         # running after they had found the job queue empty (0.5 ms bins)
         d["wave_end_hist_5ms"] = [int(v) for v in out[16:40]]
         d["wave_end_minus_drained_hist_0p5ms"] = [int(v) for v in out[40:64]]
-        ex = np.zeros(75, np.uint64)
-        check(self.L.ct_debug_stats_ex(self.h, _p(ex), 75), self.h)
+        ex = np.zeros(82, np.uint64)
+        check(self.L.ct_debug_stats_ex(self.h, _p(ex), 82), self.h)
         # of the march fetches: the lane's previous fetch was in the same 128-B brick line / a lower lane of the wave
         # fetches the same line in the same instruction (what a brick cache in LDS could find: DESIGN.md 4.3)
         d["march_fetch_same_line_as_lanes_previous"] = int(ex[68])
@@ -811,6 +811,13 @@ class CloudTracer:
         # skip_loop_wave_iterations counts the replay blocks the waves executed
         d["free_space_skips"] = int(ex[73])
         d["replay_lane_steps"] = int(ex[74])
+        # MARCH schedule mix: scheduler visits of all waves, the idle lanes they found (summed), the march bursts and the rule
+        # that ended each (the step count, too few marching lanes, burst_scatter, the rule of a drained wave)
+        d["scheduler_visits"] = int(ex[75])
+        d["idle_lanes_at_visits"] = int(ex[76])
+        d["march_bursts"] = int(ex[77])
+        d["bursts_ended_by"] = {"step_count": int(ex[78]), "march_min": int(ex[79]), "burst_scatter": int(ex[80]),
+                                "tail_rule": int(ex[81])}
         d["raw"] = [int(v) for v in out]
         d["watchdog"] = int(out[63])     # exchange kernels: waves that gave up on a bounded wait (must be 0)
         return d

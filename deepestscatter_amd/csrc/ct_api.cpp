@@ -578,16 +578,33 @@ static int choose_schedule(const CtScene *s, CtHandle h)
     d.march_burst = (uint32_t)knob_int(t.MARCH_BURST, 1, 1024, delta ? 2 : 8);
     // (round 6, with the bounded free-space replay, CT_MARCH_REPLAY_MAX = 4: burst_scatter 24 / 28 / 32 / 36 / 40 / 48 ->
     // 3825 / 3880 / 3895 / 3862 / 3766 / 3481 Msamples/s; the parent's loop: 3725 / 3790 / 3827 / 3823 / 3763 / 3532; profiles/r06a)
+    // (round 10, on the list without through pixels, 512^3 / 1024^2, Msamples/s, the other knobs at their defaults; profiles/r10a:
+    //    march_burst      1 / 2 / 4 / 6 / 8 / 12 / 16 / 32 / 64   2996 / 3867 / 4097 / 4086 / 4081 / 4069 / 4065 / 4052 / 4045
+    //    burst_scatter    8 / 16 / 24 / 28 / 32 / 36 / 40 / 48 / 65   3079 / 3674 / 4009 / 4066 / 4081 / 4032 / 3933 / 3613 / 3419
+    //    burst_idle       4 / 8 / 16 / 32 / 48 / 65   3411 / 4081 / 4084 / 4081 / 4083 / 4084
+    //    burst_march_min  1 / 4 / 8 / 16 / 32   4081 / 4082 / 4082 / 4081 / 4075
+    //    tail_burst       2 / 8 / 32   4081 / 4081 / 4080
+    //  march_burst 4 is +0.3-0.4 % with and without the refill at 4 lanes -- twice the run-to-run spread, not ten times: 8 stays;
+    //  83 % of the bursts end at burst_scatter after 3.4 steps, 3 % at their step count, none for idle lanes -- the MARCH kernel
+    //  no longer has that rule, burst_idle is the DELTA kernel's)
     d.burst_scatter = (uint32_t)knob_int(t.BURST_SCATTER, 1, 65, delta || big ? 48 : 32);
-    d.burst_idle = (uint32_t)knob_int(t.BURST_IDLE, 1, 65, 32);
+    d.burst_idle = (uint32_t)knob_int(t.BURST_IDLE, 1, 65, 32);   // (render_delta_kernel only)
     d.burst_march_min = (uint32_t)knob_int(t.BURST_MARCH_MIN, 1, 64, 1);
     d.tail_burst = (uint32_t)knob_int(t.TAIL_BURST, 1, 1024, 8);
     // (re-swept on the final kernel: 8 instead of 16 is worth +1.4 % at 512^3 and +5 % at 256^3; 16 stays best at 1024^3)
-    d.regen_min = (uint32_t)knob_int(t.REGEN_MIN, 1, 64, delta ? 4 : big ? 16 : 8);
+    // (round 10: every sample a wave takes is now a path of some 56 bounces, a lane idles only when such a path ends, and a
+    // regeneration hands out 8 of them after an average of 11 idle lanes per scheduler visit.  Refilling at 4:
+    //    regen_min  1 / 2 / 3 / 4 / 5 / 6 / 8 / 12 / 16 / 24 / 32
+    //    no priority   4030 / 4099 / - / 4130 / - / 4110 / 4081 / 3990 / 3875 / 3594 / 3358
+    //    with phase priority   - / - / 4182 / 4182 / 4177 / - / 4135 / ...     (+1.1-1.2 % either way; profiles/r10a)
+    //  the >= 768^3 value and the short batches' 16 were not swept again)
+    d.regen_min = (uint32_t)knob_int(t.REGEN_MIN, 1, 64, delta ? 4 : big ? 16 : 4);
     // measured: running the scatter phase as soon as any lane needs it beats waiting for a fuller
     // phase (927 vs 877 Msamples/s); a waiting lane is latency added to a serial path
     // (DELTA: 16 until the tracking burst followed the scatter phase in one iteration; 8 / 12 / 16 / 24 / 32: 5284 / 5290 / 5273
     // / 5168 / 5104, profiles/r04h, r04i)
+    // (round 10, MARCH: scatter_min 1 / 2 / 4 / 8 / 16 -> 4081 / 4072 / 4074 / 4069 / 4069; entry ratio 0 / 1/8 / 1/4 / 1/2 -> 4081 / 4081 /
+    // 4081 / 4080: a scatter phase has 30 lanes as it is, because the bursts end at burst_scatter)
     d.scatter_min = (uint32_t)knob_int(t.SCATTER_MIN, 1, 64, delta ? 12 : 1);
     d.scatter_num = 0;
     d.scatter_den = 1;
@@ -1410,6 +1427,10 @@ static bool short_batch(CtHandle h, uint32_t S)
 // Job list for batches of S subframes.  A job is (group, subframe range); its length is chosen
 // so that a job's expected serial work per lane stays bounded: groups whose paths are deep get
 // one-subframe jobs, cheap groups up to 16 subframes per job (Handle::job_max, job_work).
+// (Round 10, with the through pixels off the list: 98.7 % of the benchmark pose's cost is in groups that this rule gives
+// one-subframe jobs already.  One subframe for EVERY group measures the same (4083 against 4080 Msamples/s, L2 hit rate 74.8 %
+// both); 2 / 4 / 8 subframes for every group 4080 / 4079 / 4066, and at 8 the hit rate falls to 71.0 %: longer jobs lose
+// locality now, shorter ones have nothing left to gain.  The rule stays.  profiles/r10a)
 static int build_jobs(CtHandle h, uint32_t S, uint32_t chunk_groups)
 {
     chunk_groups = std::max(1u, std::min(chunk_groups, std::max(h->n_groups, 1u)));

@@ -19,6 +19,27 @@ namespace ct {
 
 #define CT_DEV __device__ __forceinline__
 
+// Phase-aware wave priority of the MARCH kernel (render_persistent_kernel).  Six waves share a SIMD and issue is arbitrated by
+// priority, then age: a wave raises its priority from the point where a load's address computation starts until the load has
+// issued (the march step's two footprint loads, the issue half of the scatter phase, the two start-record loads of a
+// regeneration), and drops it ahead of the first instruction that waits for the load, so that its loads go out ahead of the
+// other waves' arithmetic.  Same instructions, another order between waves: +1.5 % at 512^3 / 1024^2 (DESIGN.md 4.1 "Round 10";
+// levels 1 and 3 measure alike, there being no third level in use).  s_setprio ignores EXEC: every raise is followed by its
+// drop on every way through the code, never inside a branch of its own.
+// Two waits do stand inside a raised range.  The dense march step has an s_waitcnt vmcnt(0) three instructions behind its
+// raise, as the kernel without priority has it at the same place: it waits for the previous burst step's result store, not
+// for a load of this step, and is normally satisfied.  The sparse march step must have its row record (m_rows) before the
+// footprint's address exists, so its range begins behind that wait (load_footprint_m), not at the position add; only the
+// dense instantiation was timed.
+CT_DEV void phase_prio_raise()
+{
+    __builtin_amdgcn_s_setprio(1);
+}
+CT_DEV void phase_prio_drop()
+{
+    __builtin_amdgcn_s_setprio(0);
+}
+
 struct f3 {
     float x, y, z;
 };
@@ -328,7 +349,11 @@ CT_DEV void load_footprint_pair(const uint8_t *bricks, uint32_t brick, uint32_t 
 }
 
 // Footprint + row meta byte from the 3x4x4 march bricks (see DevScene::mbricks): two loads.
-template <bool SPARSE, bool WIDE = true>
+// PRIO (render_persistent_kernel's march step only): the wave's raised priority ends between the loads' issue and the first
+// instruction that reads them (phase_prio_drop).  The dense kernel raises it at its position add; SPARSE raises it here, once
+// the row record has arrived, so that no wave waits for that load at the raised level.  Raise and drop stand in the code every
+// lane with a stored brick runs through, outside the branch of the lanes beyond their row's extent.
+template <bool SPARSE, bool WIDE = true, bool PRIO = false>
 CT_DEV uint2 load_footprint_m(const DevScene &sc, int32_t ix, int32_t iy, int32_t iz, uint32_t &meta)
 {
     const uint32_t x = (uint32_t)(ix + sc.m_bias_x), y = (uint32_t)(iy + sc.brick_bias), z = (uint32_t)(iz + sc.brick_bias);
@@ -354,9 +379,15 @@ CT_DEV uint2 load_footprint_m(const DevScene &sc, int32_t ix, int32_t iy, int32_
             return make_uint2(0u, 0u);
         }
         brick = ri.x + rel;
+        if (PRIO) {
+            phase_prio_raise();
+        }
     }
     uint2 a, c;   // t_lx, t_lx+1 of row ly at bytes 0,1; of row ly+1 at 5,6; M at 4-lx; c: the same one z-slice up
     load_footprint_pair<WIDE>(sc.mbricks, brick, local, a, c);
+    if (PRIO) {
+        phase_prio_drop();
+    }
     meta = __builtin_amdgcn_perm(a.y, a.x, 0x0c0c0c04u - lx);
     uint2 r;
     r.x = __builtin_amdgcn_perm(a.y, a.x, 0x06050100u);
@@ -535,11 +566,11 @@ CT_DEV uint2 combine_raw_footprint(const uint4 &raw)
     return make_uint2(__builtin_amdgcn_perm(raw.y, raw.x, 0x06050100u), __builtin_amdgcn_perm(raw.w, raw.z, 0x06050100u));
 }
 
-template <bool SPARSE, bool WIDE = true>
+template <bool SPARSE, bool WIDE = true, bool PRIO = false>
 CT_DEV uint2 fetch_cell_m(const DevScene &sc, f3 p, uint32_t &meta)
 {
     const float x = fmaf(p.x, sc.sx, -0.5f), y = fmaf(p.y, sc.sy, -0.5f), z = fmaf(p.z, sc.sz, -0.5f);
-    return load_footprint_m<SPARSE, WIDE>(sc, floor_to_int(x), floor_to_int(y), floor_to_int(z), meta);
+    return load_footprint_m<SPARSE, WIDE, PRIO>(sc, floor_to_int(x), floor_to_int(y), floor_to_int(z), meta);
 }
 
 template <bool FIXED8>

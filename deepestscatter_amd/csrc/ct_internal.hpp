@@ -12,9 +12,11 @@ constexpr int kTile = 8;            // pixel tile edge: 8x8 = one wave of primar
 constexpr int kCounterCount = 9;    // paths, box_hits, density, inscatter, scatter, capped (the algorithm's, = the oracle's);
                                     // then what the kernels ISSUED: density fetches, shadow-volume fetches (ct_fetch_counters),
                                     // and the samples the accumulate kernels found without alpha == 1 (ct_debug_invariants)
-constexpr int kStatCount = 75;      // scheduler diagnostics (ct_debug_stats): [0,64) as before, [64,68) path conservation
+constexpr int kStatCount = 82;      // scheduler diagnostics (ct_debug_stats): [0,64) as before, [64,68) path conservation
                                     // (samples dealt, paths resumed, results written, paths suspended; STATS kernels only),
-                                    // [73,75) MARCH free-space skips and the burst steps their replays took, per lane
+                                    // [73,75) MARCH free-space skips and the burst steps their replays took, per lane,
+                                    // [75,82) MARCH schedule mix: scheduler visits, idle lanes summed over them, bursts, and the
+                                    // bursts ended by: the step count, too few marching lanes, burst_scatter, the tail rule
 constexpr int kContWords = 16;      // words of a suspended path (render_persistent_kernel)
 constexpr int kContWordsDelta = 32; // the same for render_delta_kernel (its DDA state rides along)
 constexpr int kLeftWords = 8;        // words of a job handed to the next launch (BatchArgs::left_out)

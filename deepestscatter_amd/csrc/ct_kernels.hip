@@ -1046,6 +1046,7 @@ CT_DEV NeeLoads in_scattering_issue_lds(const DevScene &sc, const MieLdsFull &ld
                                         uint32_t &nee_key, NeeCache &nee_cell, bool &reused)
 {
     NeeLoads n;
+    phase_prio_raise();   // (over the issue of the phase-table reads and of the footprint's loads)
     const float cos_light = dot3(mk3(sc.nlx, sc.nly, sc.nlz), dir);
     const float u = (cos_light + 1) / 2;
     const float x = fmaf(u, (float)kMieN, -0.5f);
@@ -1054,10 +1055,11 @@ CT_DEV NeeLoads in_scattering_issue_lds(const DevScene &sc, const MieLdsFull &ld
     float2 pair;
     LdsFloat *table = chopped ? (LdsFloat *)lds.chopped : (LdsFloat *)lds.mie;
     pair = make_float2(table[j], table[j + 1]);
+    fetch_cell_cached_raw<WIDE>(sc, sc.ibricks, pos, nee_key, nee_cell, reused);
+    phase_prio_drop();
     n.a = (i > kMieN - 2) ? pair.y : pair.x;
     n.b = (i < 0) ? pair.x : pair.y;
     n.w = tex_weight<FIXED8>(x);
-    fetch_cell_cached_raw<WIDE>(sc, sc.ibricks, pos, nee_key, nee_cell, reused);
     return n;
 }
 
@@ -1407,6 +1409,8 @@ __global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu(6
     uint32_t st_same_line = 0, st_dup_line = 0, st_prev_line = 0xffffffffu;   // brick-line reuse of the march fetches (STATS)
     uint32_t st_nee_zero = 0;   // NEE lookups skipped in shadow-zero rows (STATS)
     uint32_t st_skips = 0, st_replay_l = 0;   // free-space skips of at least one step; burst steps in which a lane replayed adds (STATS)
+    // the schedule's mix (STATS): idle lanes summed over the scheduler visits, bursts, and the rule that ended each burst
+    uint32_t st_idle_l = 0, st_bursts = 0, st_end_count = 0, st_end_nomarch = 0, st_end_scatter = 0, st_end_tail = 0;
 
     // ---------------- resume the paths the previous launch suspended ----------------
     // How often this lane's path has been suspended so far (0 = started by this launch).  A path may be handed on while its
@@ -1495,6 +1499,9 @@ __global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu(6
         // ---------------- regenerate ----------------
         const uint64_t idle = __builtin_amdgcn_ballot_w64(state == ST_IDLE);
         const uint32_t n_idle = (uint32_t)__builtin_popcountll(idle);
+        if (STATS) {
+            st_idle_l += n_idle;
+        }
         if ((n_idle >= sc.regen_min || n_idle == 64u) && !(drained && job.next == job.end)) {
             if (job.next == job.end && !take_leftover(ba, lane, left_done, job)) {
                 uint32_t j = 0;
@@ -1536,7 +1543,9 @@ __global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu(6
                     if (ba.start) {
                         // image launches: the slot's start record (start_records_kernel), two loads side by side
                         const float4 *rec = ba.start + 2 * (size_t)(g * 64u + l);
+                        phase_prio_raise();
                         const float4 r0 = rec[0], r1 = rec[1];
+                        phase_prio_drop();
                         const uint32_t w = __float_as_uint(r0.w);
                         valid = (w & 0x40000000u) == 0u;
                         starts = (w & 0x80000000u) == 0u;
@@ -1733,11 +1742,12 @@ __global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu(6
             // ---------------- march (getNextScatteringEvent, cloud.cuh:87-105) ----------------
             if (STATS) {
                 st_march += 1;   // (st_march_l: the lanes that step, counted in the burst)
+                st_bursts += 1;
             }
             // A burst of up to sc.march_burst steps per scheduler visit: the scheduler's own
             // instructions are paid once per burst, and the lanes that collide meanwhile wait for a
             // fuller scatter phase.  The burst ends early when enough lanes wait for the scatter
-            // phase or for new samples, or nobody marches any more.
+            // phase, or nobody marches any more.
             // once the queue is empty nothing is left to amortise: what remains of the launch is the
             // latency of its longest paths, so a collided lane no longer waits for a burst to end
             uint32_t burst = drained ? sc.tail_burst : sc.march_burst;
@@ -1777,9 +1787,12 @@ __global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu(6
                 }
             }
             if (steps) {
+                if (!SPARSE) {
+                    phase_prio_raise();   // (until the footprint's two loads have issued: load_footprint_m, where SPARSE raises it)
+                }
                 pos = add3(pos, stepv);
                 uint32_t meta;
-                const uint2 cell = fetch_cell_m<SPARSE, WIDE>(sc, pos, meta);
+                const uint2 cell = fetch_cell_m<SPARSE, WIDE, true>(sc, pos, meta);
                 dfree = meta & 0x3fu;
                 c_dl += 1;
                 if (COST) {
@@ -1840,6 +1853,9 @@ __global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu(6
                 }
             }
             if (--burst == 0u) {
+                if (STATS) {
+                    st_end_count += 1;
+                }
                 break;
             }
             const uint32_t m_now = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(state == ST_MARCH));
@@ -1850,9 +1866,21 @@ __global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu(6
                 // nothing left to regenerate, so idle lanes are no reason to leave the burst: what matters
                 // now is the latency of the surviving paths -- march until half of them wait for the scatter
                 if (m_now == 0u || 2u * b_now >= m_now + b_now) {
+                    if (STATS) {
+                        st_end_tail += 1;
+                    }
                     break;
                 }
-            } else if (m_now < sc.burst_march_min || b_now >= sc.burst_scatter || 64u - m_now - b_now >= sc.burst_idle) {
+            } else if (m_now < sc.burst_march_min || b_now >= sc.burst_scatter) {
+                // (until round 10 a burst also ended when sc.burst_idle lanes were idle: a rule for the one-step samples of
+                // through pixels, which idled most of a wave within a burst.  A listed path ends after some 230 steps, the wave
+                // refills at regen_min idle lanes, and the rule ended no burst at any threshold from 8 up: ct_api.cpp.  Measured
+                // at 512^3 with whole-frame launches and at the display cadence of 10 subframes; not at >= 768^3, where the
+                // refill at 16 lanes is as far below the rule's 32 -- DESIGN.md 4.1 "Round 10")
+                if (STATS) {   // (the first rule that holds, in the order of the test)
+                    st_end_nomarch += (m_now < sc.burst_march_min) ? 1u : 0u;
+                    st_end_scatter += (m_now >= sc.burst_march_min) ? 1u : 0u;
+                }
                 break;
             }
             if (STATS) {
@@ -1960,6 +1988,13 @@ __global__ __launch_bounds__(kMarchThreads) __attribute__((amdgpu_waves_per_eu(6
             atomicAdd(&ba.stats[72], (unsigned long long)sv[15]);
             atomicAdd(&ba.stats[73], (unsigned long long)sv[16]);
             atomicAdd(&ba.stats[74], (unsigned long long)sv[17]);
+            atomicAdd(&ba.stats[75], (unsigned long long)st_iters);
+            atomicAdd(&ba.stats[76], (unsigned long long)st_idle_l);
+            atomicAdd(&ba.stats[77], (unsigned long long)st_bursts);
+            atomicAdd(&ba.stats[78], (unsigned long long)st_end_count);
+            atomicAdd(&ba.stats[79], (unsigned long long)st_end_nomarch);
+            atomicAdd(&ba.stats[80], (unsigned long long)st_end_scatter);
+            atomicAdd(&ba.stats[81], (unsigned long long)st_end_tail);
         }
     }
     flush_counters(ba, lane, vals[0], vals[1], vals[2], w_fetch, w_nee);

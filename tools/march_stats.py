@@ -32,5 +32,20 @@ out = {"volume": n, "size": size, "spp": spp, "memory": t.debug_memory(),
                       "march_phase_lanes": d(s0, s1, "march_lanes") / max(d(s0, s1, "march_phases"), 1),
                       "scatter_phase_lanes": d(s0, s1, "scatter_lanes") / max(d(s0, s1, "scatter_phases"), 1)},
        "per_march_burst_step": {"skip_loop_wave_iterations": d(s0, s1, "skip_loop_wave_iterations") / max(d(s0, s1, "march_phases"), 1)},
-       "march_burst_steps_per_sample": d(s0, s1, "march_phases") / paths}
+       "march_burst_steps_per_sample": d(s0, s1, "march_phases") / paths,
+       # the schedule's mix per listed path (through pixels never reach the kernel): what the scheduler's rules are fitted to
+       "schedule_mix": {"scheduler_visits_per_sample": d(s0, s1, "scheduler_visits") / paths,
+                        "idle_lanes_per_scheduler_visit": d(s0, s1, "idle_lanes_at_visits") / max(d(s0, s1, "scheduler_visits"), 1),
+                        "regen_phases_per_sample": d(s0, s1, "regen_phases") / paths,
+                        "lanes_per_regen_phase": d(s0, s1, "regen_lanes") / max(d(s0, s1, "regen_phases"), 1),
+                        "scatter_phases_per_sample": d(s0, s1, "scatter_phases") / paths,
+                        "burst_steps_per_burst": d(s0, s1, "march_phases") / max(d(s0, s1, "march_bursts"), 1),
+                        "bursts_ended_by": {k: (s1["bursts_ended_by"][k] - s0["bursts_ended_by"][k]) / max(d(s0, s1, "march_bursts"), 1)
+                                            for k in s1["bursts_ended_by"]},
+                        "replay_lane_steps_per_sample": d(s0, s1, "replay_lane_steps") / paths,
+                        # per LISTED path (a lane that a regeneration phase gave a sample): lane-steps and lane-phases
+                        "listed_paths": d(s0, s1, "regen_lanes"),
+                        "march_lane_steps_per_listed_path": d(s0, s1, "march_lanes") / max(d(s0, s1, "regen_lanes"), 1),
+                        "scatter_lane_phases_per_listed_path": d(s0, s1, "scatter_lanes") / max(d(s0, s1, "regen_lanes"), 1),
+                        "replay_lane_steps_per_listed_path": d(s0, s1, "replay_lane_steps") / max(d(s0, s1, "regen_lanes"), 1)}}
 print(json.dumps(out, indent=1))

@@ -23,6 +23,10 @@
 
 #include "../../include/cloudtrace.h"
 #include "ct_handle.hpp"
+#include "ct_plan.hpp"
+
+static_assert(plan::kTile == kTile && plan::kQueues == kQueues && plan::kMaxRegions == CtHandle_::kMaxRegions,
+              "ct_plan.hpp plans for the kernels' tile and queue counts and the handle's ring");
 
 static thread_local std::string g_create_error;
 
@@ -156,41 +160,6 @@ static int nee_skip_radius(const DevScene &d, bool mie_finite)
         r = std::max(r, (int)std::ceil(D));
     }
     return std::max(r, 1);
-}
-
-static uint32_t morton2(uint32_t x, uint32_t y)
-{
-    auto spread = [](uint32_t v) {
-        v &= 0xffffu;
-        v = (v | (v << 8)) & 0x00ff00ffu;
-        v = (v | (v << 4)) & 0x0f0f0f0fu;
-        v = (v | (v << 2)) & 0x33333333u;
-        v = (v | (v << 1)) & 0x55555555u;
-        return v;
-    };
-    return spread(x) | (spread(y) << 1);
-}
-
-// Position of tile (x, y) along a Hilbert curve over a 2^15 x 2^15 grid (the standard xy2d): like the Morton index a
-// locality-preserving order of the tiles, but without its jumps -- consecutive tiles are always neighbours.
-static uint32_t hilbert2(uint32_t x, uint32_t y)
-{
-    const uint32_t n = 1u << 15;
-    uint32_t d = 0;
-    for (uint32_t s = n / 2; s > 0; s /= 2) {
-        const uint32_t rx = (x & s) ? 1u : 0u, ry = (y & s) ? 1u : 0u;
-        d += s * s * ((3u * rx) ^ ry);
-        if (ry == 0) {
-            if (rx == 1) {
-                x = n - 1u - x;
-                y = n - 1u - y;
-            }
-            const uint32_t t = x;
-            x = y;
-            y = t;
-        }
-    }
-    return d;
 }
 
 static void release(CtHandle h)
@@ -1320,47 +1289,22 @@ static int rebuild_queue(CtHandle h)
                                h->scene.shard_count, (unsigned long long *)(h->d_hit + sum_at), h->stream));
     HIPCHK(h, hipMemcpyAsync(h->hit_host, h->d_hit, plane_bytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    const uint8_t *hit = h->hit_host;
     const uint32_t tiles_x = h->dev.tiles_x, tiles_y = h->dev.tiles_y;
-    std::vector<std::pair<uint32_t, uint32_t>> tiles;
-    for (uint32_t ty = 0; ty < tiles_y; ty++) {
-        for (uint32_t tx = 0; tx < tiles_x; tx++) {
-            if (tile_owner(tx, ty, h->scene.shard_count) == h->scene.shard_index) {
-                tiles.emplace_back(h->tile_hilbert ? hilbert2(tx, ty) : morton2(tx, ty), ty * tiles_x + tx);
-            }
-        }
-    }
-    std::sort(tiles.begin(), tiles.end());
     std::vector<uint32_t> list;
     list.reserve(pixels / std::max(1u, h->scene.shard_count) + 64);
-    uint64_t own = 0, through_pixels = 0;
-    for (const auto &t : tiles) {
-        const uint32_t ty = t.second / tiles_x, tx = t.second - ty * tiles_x;
-        for (uint32_t l = 0; l < 64; l++) {
-            const uint32_t x = tx * kTile + (l & 7u), y = ty * kTile + (l >> 3);
-            if (x < W && y < H) {
-                own++;
-                const uint32_t p = y * W + x;
-                if (hit[p] == 1u) {
-                    list.push_back(p);
-                } else if (hit[p] == 2u) {
-                    through_pixels++;
-                }
-            }
-        }
-    }
-    h->own_pixels = own;
-    h->listed_pixels = list.size();
-    h->through_pixels = through_pixels;
-    h->hit_pixels = h->listed_pixels + through_pixels;
-    h->miss_pixels = own - h->hit_pixels;
+    const plan::PixelCounts n = plan::list_pixels(
+        h->hit_host, W, H, tiles_x, tiles_y, h->tile_hilbert,
+        [&](uint32_t tx, uint32_t ty) { return tile_owner(tx, ty, h->scene.shard_count) == h->scene.shard_index; }, list, h->group_tile);
+    plan::seed_group_order(h->group_tile, h->tile_deepest, (size_t)tiles_x * tiles_y, h->group_order);
+    h->own_pixels = n.own;
+    h->listed_pixels = n.listed;
+    h->through_pixels = n.through;
+    h->hit_pixels = n.listed + n.through;
+    h->miss_pixels = n.own - h->hit_pixels;
     {
         unsigned long long steps = 0;
         memcpy(&steps, h->hit_host + sum_at, sizeof steps);
         h->through_steps = steps;
-    }
-    while (list.size() % 64 != 0) {
-        list.push_back(0xffffffffu);
     }
     h->n_groups = (uint32_t)(list.size() / 64);
     // (the old contents are dead: free, then allocate)
@@ -1370,29 +1314,6 @@ static int rebuild_queue(CtHandle h)
     HIPCHK(h, h->d_group_order.reserve((size_t)h->n_groups));
     if (start_records(h)) {
         HIPCHK(h, h->d_start.reserve(2 * (size_t)h->n_groups * 64));
-    }
-    h->group_order.resize(h->n_groups);
-    h->group_tile.resize(h->n_groups);
-    for (uint32_t i = 0; i < h->n_groups; i++) {
-        h->group_order[i] = i;
-        const uint32_t p = list[(size_t)i * 64];
-        h->group_tile[i] = (p / W / kTile) * tiles_x + (p % W) / kTile;
-    }
-    if (h->tile_deepest.size() == (size_t)tiles_x * tiles_y) {
-        // The cost-measuring launch of this pose is waited for to its last path, so it should START with the groups whose paths
-        // are long.  Where those were for the last pose that was measured is a good guess while the camera is dragged
-        // (Camera::rotate, Camera.cpp:93-98): classes of the deepest path seen in a group's tile, deepest first, tile order within.
-        auto log2_class = [](uint32_t c) {
-            uint32_t k = 0;
-            while (c) {
-                k++;
-                c >>= 1;
-            }
-            return k;
-        };
-        std::stable_sort(h->group_order.begin(), h->group_order.end(), [&](uint32_t a, uint32_t b) {
-            return log2_class(h->tile_deepest[h->group_tile[a]]) > log2_class(h->tile_deepest[h->group_tile[b]]);
-        });
     }
     h->group_depth.assign(h->n_groups, 0.f);
     if (h->n_groups) {
@@ -1413,27 +1334,36 @@ static int rebuild_queue(CtHandle h)
     return CT_OK;
 }
 
-// A launch of about 5 ms or less (10-40 subframes of a 1024^2 frame: the reference's display cadence, Camera.cpp:189).  Such a
-// launch works on EVERY pixel group at once instead of a few neighbouring ones for a thousand subframes each, and its paths
-// miss L2 half again as often at the same instruction count (profiles/r03f/pmc_prog.txt: hit rate 41 % instead of 62 %); what
-// helps is keeping an XCD on a compact part of the image -- per-XCD queues over 16 regions -- with single-subframe jobs for
-// every group deeper than four bounces and refills of 16 lanes at a time: 5.43 -> 4.74 ms per 10-subframe update.
 static bool short_batch(CtHandle h, uint32_t S)
 {
-    // (MARCH only: the DELTA kernel, which makes a sixteenth of the fetches, loses 3 % with this layout -- 3.94 vs 3.82 ms)
-    return h->scene.estimator != CT_EST_DELTA && (double)S * (double)std::max<uint64_t>(h->hit_pixels, 1) < 4.0e7;
+    return plan::short_batch(h->scene.estimator == CT_EST_DELTA, S, h->hit_pixels);
 }
 
-// Job list for batches of S subframes.  A job is (group, subframe range); its length is chosen
-// so that a job's expected serial work per lane stays bounded: groups whose paths are deep get
-// one-subframe jobs, cheap groups up to 16 subframes per job (Handle::job_max, job_work).
-// (Round 10, with the through pixels off the list: 98.7 % of the benchmark pose's cost is in groups that this rule gives
-// one-subframe jobs already.  One subframe for EVERY group measures the same (4083 against 4080 Msamples/s, L2 hit rate 74.8 %
-// both); 2 / 4 / 8 subframes for every group 4080 / 4079 / 4066, and at 8 the hit rate falls to 71.0 %: longer jobs lose
-// locality now, shorter ones have nothing left to gain.  The rule stays.  profiles/r10a)
+// What the handle and the knobs decide about a job list for batches of S subframes.
+static plan::JobPolicy job_policy(CtHandle h, uint32_t S)
+{
+    plan::JobPolicy p;
+    p.unit = (h->scene.estimator == CT_EST_DELTA) ? 1.f : 16.f;
+    p.brief = short_batch(h, S);
+    // (per-XCD queues are cut at equal shares of the MEASURED cost: before anything is measured they would be equal shares of
+    // pixels, and the XCD that got the cloud's body would finish long after the others)
+    const bool queues = (h->queues_enabled || (p.brief && !h->tune.XCD_QUEUES.get())) && !(h->scene.flags & CT_FLAG_SIMPLE_KERNEL) &&
+                        (h->order_tuned || h->tune.XCD_QUEUES_UNTUNED.get());
+    p.nq = (queues && h->n_groups >= (uint32_t)kQueues) ? (uint32_t)kQueues : 1u;
+    p.regions_wanted = (p.brief && !h->queues_enabled && !h->tune.XCD_REGIONS.get()) ? 16u : h->regions;
+    p.job_work = (p.brief && !h->tune.JOB_WORK.get()) ? 4.f : h->job_work;
+    p.job_max = h->job_max;
+    p.shared_depth = h->shared_depth;
+    p.order_tuned = h->order_tuned;
+    p.chunk_interleave = h->chunk_interleave;
+    p.chunk_morton = h->chunk_morton;
+    return p;
+}
+
+// Job list for batches of S subframes, in chunks of chunk_groups pixel groups (plan::fill_jobs).
 static int build_jobs(CtHandle h, uint32_t S, uint32_t chunk_groups)
 {
-    chunk_groups = std::max(1u, std::min(chunk_groups, std::max(h->n_groups, 1u)));
+    chunk_groups = plan::clamp_chunk_groups(chunk_groups, h->n_groups);
     if (h->jobs_S >= S && h->jobs_brief == short_batch(h, S) && h->chunk_groups == chunk_groups) {
         return CT_OK; // a list for a larger batch serves a smaller one (the kernel clips the jobs)
     }
@@ -1441,166 +1371,43 @@ static int build_jobs(CtHandle h, uint32_t S, uint32_t chunk_groups)
     if (h->order_tuned) {
         S = std::max(S, h->jobs_hint);   // (the cost-measuring launch gets a list of its own: one-subframe jobs, its few subframes only)
     }
-    // One queue per XCD: groups are in tile-Morton order, so a contiguous range of them is a
-    // compact image region whose paths read a compact part of the volume.  The ranges are cut at
-    // equal shares of the measured cost (path depth + the primary march), not of the pixel count.
-    // cost units per bounce (BatchArgs::cost): MARCH counts fetches + 4 per bounce, DELTA bounces
-    const float unit = (h->scene.estimator == CT_EST_DELTA) ? 1.f : 16.f;
-    const bool brief = short_batch(h, S);
-    // (per-XCD queues are cut at equal shares of the MEASURED cost: before anything is measured they would be equal shares of
-    // pixels, and the XCD that got the cloud's body would finish long after the others)
-    const bool queues = (h->queues_enabled || (brief && !h->tune.XCD_QUEUES.get())) && !(h->scene.flags & CT_FLAG_SIMPLE_KERNEL) &&
-                        (h->order_tuned || h->tune.XCD_QUEUES_UNTUNED.get());
-    const uint32_t nq = (queues && h->n_groups >= (uint32_t)kQueues) ? (uint32_t)kQueues : 1u;
-    const uint32_t regions_wanted = (brief && !h->queues_enabled && !h->tune.XCD_REGIONS.get()) ? 16u : h->regions;
-    const float job_work = (brief && !h->tune.JOB_WORK.get()) ? 4.f : h->job_work;
-    // Groups whose paths are deep (mean cost >= shared_depth bounces) go to the shared queue.
-    const float shared_cost = h->shared_depth * unit;
-    std::vector<uint8_t> queue_of(h->n_groups, 0);
-    {
-        double total = 0;
-        for (uint32_t g = 0; g < h->n_groups; g++) {
-            if (nq > 1u && h->group_depth[g] >= shared_cost) {
-                queue_of[g] = (uint8_t)kQueues;
-            } else {
-                total += (double)h->group_depth[g] + unit;
-            }
-        }
-        double run = 0;
-        for (uint32_t g = 0; g < h->n_groups; g++) {
-            if (queue_of[g] == (uint8_t)kQueues) {
-                continue;
-            }
-            const double w = (double)h->group_depth[g] + unit;
-            // h->regions compact image regions of equal cost, dealt round-robin to the queues: every
-            // XCD still works on 1/8 of the image (a handful of compact pieces), and errors of the
-            // cost estimate, which are correlated in space, average out over its pieces
-            const uint32_t regions = std::max(nq, regions_wanted);
-            const uint32_t r = (uint32_t)std::min<double>(regions - 1, std::floor((run + 0.5 * w) / total * regions));
-            queue_of[g] = (uint8_t)(r % nq);
-            run += w;
-        }
-    }
-    // (the list itself is written into pinned host memory that stays with the handle: a new pose builds it twice, and 860 k
-    // jobs in two fresh vectors cost 9 ms of page faults and staged copies)
-    auto job_length = [&](uint32_t g) {
-        const float d = h->group_depth[g];
-        if (!h->order_tuned) {
-            // the cost-measuring launch of a pose knows no depths yet: ONE subframe per job, or the wave that gets a group of the
-            // cloud's body runs its eight or ten subframes one after another in the same 64 lanes -- 21 ms for 10 subframes
-            // of a 1024^2 frame that are 13 ms once the order is set
-            return 1u;
-        }
-        uint32_t len = h->job_max;
-        if (d > 0.f) {
-            len = (uint32_t)std::min((float)h->job_max, std::max(1.f, job_work * unit / d));
-        }
-        return len;
-    };
-    size_t total_jobs = 0;
-    for (uint32_t g = 0; g < h->n_groups; g++) {
-        const uint32_t len = job_length(g);
-        total_jobs += (S + len - 1) / len;
-    }
+    const plan::JobPolicy policy = job_policy(h, S);
+    const size_t total_jobs = plan::count_jobs(policy, h->group_depth, S);
     HIPCHK(h, h->jobs_host_g.reserve(total_jobs, total_jobs / 4 + 1024));
     HIPCHK(h, h->jobs_host_s.reserve(total_jobs, total_jobs / 4 + 1024));
-    uint32_t *const jg = h->jobs_host_g, *const js = h->jobs_host_s;
-    size_t nj = 0;
-    std::vector<double> q_weight(kQueues + 1, 0.0);
-    // chunk by chunk (a contiguous piece of the group order each), and within a chunk queue by queue
-    const uint32_t n_chunks = h->n_groups ? (h->n_groups + chunk_groups - 1) / chunk_groups : 1u;
-    if (n_chunks > 1 && h->chunk_interleave) {
-        // Every chunk gets the same mix of expensive and cheap groups (2 % of the groups make 98 % of the cost): the job order
-        // becomes places 0, C, 2C, ... of the cost-sorted order, then 1, C + 1, ..., so that a contiguous piece of it is every
-        // C-th group -- launches of equal length instead of a few long ones and many that are over before the paths they
-        // resumed have moved.
-        std::vector<uint32_t> mixed;
-        mixed.reserve(h->n_groups);
-        for (uint32_t c = 0; c < n_chunks; c++) {
-            for (uint32_t r = c; r < h->n_groups; r += n_chunks) {
-                mixed.push_back(h->group_order[r]);
-            }
-        }
-        // (pieces must be whole chunks: with n_groups not a multiple of n_chunks the first chunks are one group longer than
-        // chunk_groups allows only if chunk_groups * n_chunks < n_groups, which the rounding above excludes)
-        h->job_order = mixed;
-    } else if (n_chunks > 1 && h->chunk_morton) {
-        // (probe: chunks = compact image regions -- the groups in tile-Morton order, which is their index order)
-        h->job_order.resize(h->n_groups);
-        for (uint32_t g = 0; g < h->n_groups; g++) {
-            h->job_order[g] = g;
-        }
-    } else {
-        h->job_order = h->group_order;
-    }
-    h->chunk_q_begin.assign(n_chunks, std::array<uint32_t, kQueues + 2>{});
-    for (uint32_t c = 0; c < n_chunks; c++) {
-        const uint32_t r0 = c * chunk_groups, r1 = std::min(h->n_groups, r0 + chunk_groups);
-        for (uint32_t x = 0; x <= (uint32_t)kQueues; x++) {
-            h->chunk_q_begin[c][x] = (uint32_t)nj;
-            if (x != 0u && nq == 1u && x != (uint32_t)kQueues) {
-                continue;   // (one global list: everything is in queue 0)
-            }
-            for (uint32_t r = r0; r < r1; r++) {
-                const uint32_t g = h->job_order[r];
-                if (queue_of[g] != x) {
-                    continue;
-                }
-                q_weight[x] += (double)h->group_depth[g] + unit;
-                const uint32_t len = job_length(g);
-                for (uint32_t s0 = 0; s0 < S; s0 += len) {
-                    jg[nj] = g;
-                    js[nj] = s0 | (std::min(len, S - s0) << 16);
-                    nj += 1;
-                }
-            }
-        }
-        h->chunk_q_begin[c][kQueues + 1] = (uint32_t)nj;
-    }
-    for (int x = 0; x <= kQueues + 1; x++) {
-        h->q_begin[x] = h->chunk_q_begin[0][x];
-    }
+    plan::JobPlan jp;
+    plan::fill_jobs(policy, h->group_depth, h->group_order, S, chunk_groups, h->jobs_host_g, h->jobs_host_s, jp);
     if (h->tune.STATS.get()) {
-        fprintf(stderr, "[cloudtrace] job queues (S=%u, %u chunk(s) of %u groups):", S, n_chunks, chunk_groups);
+        fprintf(stderr, "[cloudtrace] job queues (S=%u, %u chunk(s) of %u groups):", S, jp.n_chunks, chunk_groups);
         for (int x = 0; x <= kQueues; x++) {
-            fprintf(stderr, " q%d weight %.0f;", x, q_weight[x]);
+            fprintf(stderr, " q%d weight %.0f;", x, jp.q_weight[x]);
         }
         fprintf(stderr, "\n");
     }
-    {
-        // the job order itself, both ways: where a group's results go in its chunk's scratch, and whose a column is
-        std::vector<uint32_t> rank(h->n_groups);
-        for (uint32_t r = 0; r < h->n_groups; r++) {
-            rank[h->job_order[r]] = r;
-        }
-        if (h->n_groups) {
-            HIPCHK(h, hipMemcpyAsync(h->d_group_rank, rank.data(), rank.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-            HIPCHK(h, hipMemcpyAsync(h->d_group_order, h->job_order.data(), h->job_order.size() * sizeof(uint32_t),
-                                     hipMemcpyHostToDevice, h->stream));
-            HIPCHK(h, hipStreamSynchronize(h->stream));   // (`rank` dies at the end of this block)
-        }
+    h->job_order = std::move(jp.job_order);
+    h->chunk_q_begin = std::move(jp.chunk_q_begin);
+    if (h->n_groups) {
+        HIPCHK(h, hipMemcpyAsync(h->d_group_rank, jp.rank.data(), jp.rank.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->d_group_order, h->job_order.data(), h->job_order.size() * sizeof(uint32_t),
+                                 hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
     }
     h->chunk_groups = chunk_groups;
-    h->n_chunks = n_chunks;
-    // (nq == 1: everything sits in queue 0 and the other XCDs' waves steal from it -- one global
-    // cost-sorted list, the behaviour before the queues were split)
-    h->n_jobs = (uint32_t)nj;
+    h->n_chunks = jp.n_chunks;
+    h->n_jobs = (uint32_t)jp.n_jobs;
     HIPCHK(h, h->d_job_group.reserve(h->n_jobs, h->n_jobs / 4));
     HIPCHK(h, h->d_job_sub.reserve(h->n_jobs, h->n_jobs / 4));
     if (h->n_jobs) {
-        HIPCHK(h, hipMemcpyAsync(h->d_job_group, jg, nj * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->d_job_sub, js, nj * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->d_job_group, h->jobs_host_g, jp.n_jobs * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->d_job_sub, h->jobs_host_s, jp.n_jobs * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));   // (the pinned list is rewritten by the next build)
     }
     h->jobs_S = S;
-    h->jobs_brief = brief;
+    h->jobs_brief = policy.brief;
     return CT_OK;
 }
 
-// Longest-processing-time-first: visit the groups whose paths were deepest first, so that the
-// 2000-bounce paths start at the head of the launch instead of becoming its tail.  Groups of
-// the same cost class (power of two) keep their Morton order for cache locality.  The order and
-// the job lengths only change the schedule, never a result.
+// The group order and depths from what the cost-measuring launch of a pose has booked (plan::tune_groups).
 static int tune_order(CtHandle h, uint32_t measured_subframes)
 {
     TracePhase trace(h, "tune_order");
@@ -1612,47 +1419,14 @@ static int tune_order(CtHandle h, uint32_t measured_subframes)
     HIPCHK(h, hipMemcpyAsync(cost.data(), h->d_cost, cost.size() * sizeof(uint32_t), hipMemcpyDeviceToHost,
                              h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    auto log2_class = [](uint32_t c) {
-        uint32_t k = 0;
-        while (c) {
-            k++;
-            c >>= 1;
-        }
-        return k;
-    };
-    // Order: by the deepest path a group has produced (a launch ends when its last path does, so
-    // the groups that can produce long paths must not be the last ones running), then by mean cost.
-    const uint32_t *deepest = cost.data() + h->n_groups;
-    h->tile_deepest.assign((size_t)h->dev.tiles_x * h->dev.tiles_y, 0u);
-    for (uint32_t g = 0; g < h->n_groups; g++) {
-        h->group_order[g] = g;
-        h->group_depth[g] = (float)cost[g] / (64.f * (float)measured_subframes);
-        if (g < h->group_tile.size()) {
-            uint32_t &t = h->tile_deepest[h->group_tile[g]];
-            t = std::max(t, deepest[g]);   // (a guess for the next pose's cost-measuring launch: rebuild_queue)
-        }
-    }
-    std::stable_sort(h->group_order.begin(), h->group_order.end(), [&](uint32_t a, uint32_t b) {
-        const uint32_t ka = log2_class(deepest[a]), kb = log2_class(deepest[b]);
-        if (ka != kb) {
-            return ka > kb;
-        }
-        return log2_class(cost[a]) > log2_class(cost[b]);
-    });
+    plan::tune_groups(cost.data(), h->n_groups, measured_subframes, h->group_tile, (size_t)h->dev.tiles_x * h->dev.tiles_y, h->group_order,
+                      h->group_depth, h->tile_deepest);
     if (h->tune.STATS.get()) {
-        // share of the measured cost by class of the deepest path seen
-        std::vector<double> share(34, 0.0);
-        std::vector<uint32_t> count(34, 0);
-        double total = 0;
-        for (uint32_t g = 0; g < h->n_groups; g++) {
-            share[log2_class(deepest[g])] += cost[g];
-            count[log2_class(deepest[g])] += 1;
-            total += cost[g];
-        }
+        const plan::CostShare cs = plan::cost_share(cost.data(), h->n_groups);
         fprintf(stderr, "[cloudtrace] cost share by deepest-path class (2^(k-1) <= depth < 2^k):");
         for (int k = 0; k < 34; k++) {
-            if (count[k]) {
-                fprintf(stderr, " k=%d groups %u share %.1f%%;", k, count[k], 100.0 * share[k] / std::max(total, 1.0));
+            if (cs.count[k]) {
+                fprintf(stderr, " k=%d groups %u share %.1f%%;", k, cs.count[k], 100.0 * cs.share[k] / std::max(cs.total, 1.0));
             }
         }
         fprintf(stderr, "\n");
@@ -1670,21 +1444,9 @@ static size_t frame_stride(CtHandle h)
     return (size_t)std::max(h->chunk_groups, 1u) * 64;
 }
 
-// How many regions a batch of S subframes should have: enough launches between a batch and its accumulate kernel that
-// no path of it is still running -- a path needs up to ~10 ms (2000 bounces) of running time, a launch lasts about as long
-// as its samples take at ~3 Gsamples/s -- but never more than the budget holds.
-static int wanted_regions(CtHandle h, uint32_t S, uint64_t need, uint64_t budget_float4)
+static int wanted_regions(CtHandle h, uint64_t need, uint64_t budget_float4)
 {
-    int r;
-    if (h->max_age_override > 0) {
-        r = h->max_age_override + 1;
-    } else {
-        const double est_ms = std::max(0.05, (double)need / 3.0e6);
-        r = 1 + (int)std::ceil(15.0 / est_ms);
-    }
-    (void)S;
-    r = (int)std::min<uint64_t>((uint64_t)r, std::max<uint64_t>(budget_float4 / std::max<uint64_t>(need, 1), 2));
-    return std::min(CtHandle_::kMaxRegions, std::max(2, r));
+    return plan::wanted_regions(h->max_age_override, need, budget_float4);
 }
 
 static uint64_t scratch_slot_bytes(CtHandle h)
@@ -1701,17 +1463,12 @@ static uint64_t scratch_slot_bytes(CtHandle h)
     return (uint64_t)knob_int(h->tune.SCRATCH_GIB, 1, 64, 16) << 30;
 }
 
-// How many pixel groups a launch of S subframes renders at once: what one scratch region holds (all of them when it can).
 static uint32_t groups_per_chunk(CtHandle h, uint32_t S)
 {
     if (h->scene.flags & CT_FLAG_SIMPLE_KERNEL) {
         return std::max(h->n_groups, 1u);
     }
-    const uint64_t region = scratch_slot_bytes(h) / sizeof(float4);
-    // (two regions at least, and result indices are 32 bits)
-    const uint64_t cap = std::min<uint64_t>(region, 0xffffffffull / 2);
-    const uint64_t g = cap / ((uint64_t)std::max(S, 1u) * 64);
-    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(g, std::max(h->n_groups, 1u)));
+    return plan::groups_per_chunk(scratch_slot_bytes(h) / sizeof(float4), S, h->n_groups);
 }
 
 // At least `total` float4 of per-sample scratch (nothing may be in flight when it grows: the caller has flushed).
@@ -1747,7 +1504,7 @@ static int ensure_frames(CtHandle h, uint32_t S, bool relayout)
     discard_ahead(h);
     const uint64_t budget = 2 * scratch_slot_bytes(h) / sizeof(float4);
     // (a waited-for batch needs one region; the others are allocated when batches are first enqueued)
-    const int regions = relayout ? wanted_regions(h, S, need, std::max<uint64_t>(budget, 2 * need)) : 1;
+    const int regions = relayout ? wanted_regions(h, need, std::max<uint64_t>(budget, 2 * need)) : 1;
     size_t total = (size_t)regions * need;
     if (total > 0xffffffffull) {
         if ((relayout ? 2 : 1) * need > 0xffffffffull) {
@@ -2353,12 +2110,12 @@ static int render_accumulate_impl(CtHandle h, uint32_t first_subframe_id, uint32
             // and shrinks as the camera moves, and every growth of the scratch would be a hipFree + hipMalloc of tens of GB --
             // 25 ms when the driver has the pages at hand, a second when it has not)
             const uint64_t all_groups = (h->own_pixels + 63u) / 64u;
-            const uint64_t region_groups = std::min<uint64_t>(scratch_slot_bytes(h) / sizeof(float4), 0xffffffffull / 2) / ((uint64_t)std::max(h->jobs_hint, 1u) * 64u);
+            const uint64_t region_groups = plan::region_groups(scratch_slot_bytes(h) / sizeof(float4), h->jobs_hint);
             const uint32_t gc_reserve = (gc >= h->n_groups && all_groups <= region_groups) ? (uint32_t)std::max<uint64_t>(all_groups, gc) : gc;
             const size_t need = (size_t)h->jobs_hint * gc_reserve * 64;
             const bool enqueue = !wait || gc < h->n_groups;
             const uint64_t budget = 2 * scratch_slot_bytes(h) / sizeof(float4);
-            const size_t total = std::min<size_t>((size_t)(enqueue ? wanted_regions(h, h->jobs_hint, need, std::max<uint64_t>(budget, 2 * need)) : 1) * need,
+            const size_t total = std::min<size_t>((size_t)(enqueue ? wanted_regions(h, need, std::max<uint64_t>(budget, 2 * need)) : 1) * need,
                                                   (0xffffffffull / std::max<size_t>(need, 1)) * need);
             if (total <= h->d_frames_all.capacity()) {
                 break;
@@ -2403,7 +2160,7 @@ static int render_accumulate_impl(CtHandle h, uint32_t first_subframe_id, uint32
             const size_t need = (size_t)layout * frame_stride(h);
             // (an enqueued batch may use the regions of a layout made for larger ones, as long as the ring is long enough for it)
             const bool ring_too_short = enqueue && (h->n_regions < 2 ||
-                                                    (layout != h->layout_S && h->n_regions < wanted_regions(h, layout, need, 2 * scratch_slot_bytes(h) / sizeof(float4))));
+                                                    (layout != h->layout_S && h->n_regions < wanted_regions(h, need, 2 * scratch_slot_bytes(h) / sizeof(float4))));
             if (rc == CT_OK && (need > h->slot_capacity || ring_too_short)) {
                 rc = flush(h); // the layout of the scratch changes: nothing may be in flight
                 if (rc == CT_OK) {

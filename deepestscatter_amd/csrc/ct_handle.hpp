@@ -188,7 +188,6 @@ struct CtHandle_ {
     // launch of an eighth of the tiles is 1.6 % shorter, 43.6 instead of 44.3 ms)
     uint32_t job_max = 16;
     float job_work = 16.f;
-    uint32_t q_begin[kQueues + 2] = {}; // job ranges of the per-XCD queues + the shared one
     // This shard's pixels; those whose primary ray hits the box (what short_batch and the other heuristics are tuned on) =
     // listed_pixels (in the pixel list: their samples are rendered) + through_pixels (the ray crosses the box without meeting
     // a non-zero footprint: every sample is (0,0,0,1) after through_steps / through_pixels lookups on average, settled by the

@@ -443,6 +443,19 @@ class CloudTracer:
             raise ValueError("traced_bake: sparse or compact, not both")
         return Bake(self, None, grid, azimuths, cosines, sparse, compact, samples=int(samples))
 
+    def traced_bake_adaptive(self, grid, azimuths: int, cosines: int, round_samples: int, max_samples: int, rel_tol: float = 2e-2,
+                             abs_tol: float = 1e-4, zero_samples: int = 100000, sparse: bool = False, compact: bool = False):
+        """ct_bake_traced_adaptive -> deepestscatter_amd.network.Bake: traced_bake's table, traced in rounds of `round_samples`
+        experiments that go only to the entries which have not yet passed the reference's stopping rule (95 % confidence interval
+        below rel_tol of the mean or below abs_tol; a zero entry after zero_samples experiments), at most `max_samples` per entry.
+        Bake.counts / m2 / adaptive_info describe the result, Bake.trace_adaptive_more raises the cap, Bake.retrace_adaptive
+        follows set_light.  With the default zero_samples a dense bake runs every empty node to the cap: use sparse or compact."""
+        from .network import AdaptiveParams, Bake
+        if sparse and compact:
+            raise ValueError("traced_bake_adaptive: sparse or compact, not both")
+        return Bake(self, None, grid, azimuths, cosines, sparse, compact,
+                    adaptive=AdaptiveParams(int(round_samples), int(max_samples), float(rel_tol), float(abs_tol), int(zero_samples)))
+
     def bake_mask(self, grid):
         """ct_debug_bake_mask: the sparse bake's mask of a grid (Nx, Ny, Nz) on this handle, no network needed
         -> (cells uint8 [Nz-1, Ny-1, Nx-1], nodes uint8 [Nz, Ny, Nx], the active node indices uint32, ascending)."""

@@ -308,10 +308,28 @@ struct BakeTraceArgs {
     uint32_t nx, ny, nphi, nc;
     uint64_t first;
     uint32_t n, n_pad, compact;
+    const uint32_t *live;   // ct_bake_traced_adaptive: lane i is stored entry live[first + i]; nullptr: first + i
 };
 hipError_t launch_bake_trace_tasks(const DevScene &sc, const BakeTraceArgs &a, float4 *primary, uint32_t *pixels, hipStream_t stream);
 hipError_t launch_bake_trace_fold(const BakeTraceArgs &a, const float4 *frames, uint32_t stride, uint32_t passes, uint32_t done,
                                   float *table, hipStream_t stream);
+// ct_bake_traced_adaptive: the state of an entry -- mean (the table), m2 and count at the entry's stored address -- and the
+// stopping rule of include/cloudtrace.h, "the adaptive traced bake".  launch_bake_adaptive_fold folds a pass as
+// point_accumulate_kernel does, mean and m2, and stores count = done + passes; with `waves` (the round's last pass; a.first is a
+// multiple of 64 then) it also tests the rule and wave (a.first + i) / 64 of the live list writes how many of its lanes go on.
+// launch_bake_adaptive_compact: the scan of the n_live / 64 (rounded up) wave counts, the number of survivors behind them, and
+// the stored indices of the survivors of live_in (nullptr: 0 .. n_live - 1) into live_out, in live_in's order.
+struct BakeAdaptiveState {
+    float *table, *m2;
+    uint32_t *counts;
+    float rel_tol, abs_tol;
+    uint32_t zero_samples;
+};
+hipError_t launch_bake_adaptive_fold(const BakeTraceArgs &a, const float4 *frames, uint32_t stride, uint32_t passes, uint32_t done,
+                                     const BakeAdaptiveState &st, uint32_t *waves, hipStream_t stream);
+hipError_t launch_bake_adaptive_scan(uint32_t *waves, uint32_t n_live, hipStream_t stream);
+hipError_t launch_bake_adaptive_compact(const BakeTraceArgs &a, const BakeAdaptiveState &st, const uint32_t *live_in, uint32_t n_live,
+                                        const uint32_t *waves, uint32_t *live_out, hipStream_t stream);
 // Density pyramid (Resources::generateMipmaps) and the descriptor gather.
 constexpr int kMaxMipLevels = 16;
 struct MipPyramid {

@@ -2,7 +2,9 @@
 // (ct_collect_descriptors, ct_descriptor_frame), the scattering network (ct_network_create, ct_network_eval) and the network as a
 // renderer (ct_network_render_*) and baked into a probe table (ct_network_bake, ct_baked_render_*), on the handle of ct_handle.hpp.
 // The network itself is ct_network.hip.  The traced bake (ct_bake_traced) fills the same table with the path tracer's point
-// estimator instead: its two kernels are ct_bake_trace.hip, its launches ct_api.cpp's point_launch.
+// estimator instead: its two kernels are ct_bake_trace.hip, its launches ct_api.cpp's point_launch.  The adaptive traced bake
+// (ct_bake_traced_adaptive) traces in rounds, keeps m2 and count per entry and stops entries by the reference's rule: its fold,
+// scan and compaction kernels are in ct_bake_trace.hip too.
 #include <cmath>
 
 #include "ct_handle.hpp"
@@ -377,6 +379,11 @@ struct BakeState {
     uint32_t samples = 0;                    // a traced bake: experiments folded into every stored entry of an active node
     uint64_t paths = 0;
     double trace_ms = 0, fold_ms = 0;
+    // an adaptive traced bake: `samples` is the count its last round reached
+    uint32_t cap = 0, rounds = 0;            // max_samples as it is now; rounds traced
+    uint64_t live = 0;                       // entries in d_live[live_cur]: those at the cap that fail the rule
+    int live_cur = 0;
+    double test_ms = 0;
 };
 
 struct CtBake_ : BakeState {
@@ -403,6 +410,12 @@ struct CtBake_ : BakeState {
     // any kind has d_probe (its position nodes) and d_dirs, the Nphi x Nc x 3 direction table of its frame.
     bool traced = false;
     DevBuf<float> d_dirs;
+    // ct_bake_traced_adaptive: m2 and count beside every stored mean, the two live lists the rounds alternate
+    // between (stored indices, counted through the blocks of the active nodes as the task kernel counts them) and the wave counts.
+    bool adaptive = false;
+    CtBakeAdaptive ap{};                     // (max_samples: as given; BakeState::cap is the one in force)
+    DevBuf<float> d_m2;
+    DevBuf<uint32_t> d_counts, d_live[2], d_waves;
 };
 
 static uint64_t bake_probes_total(const CtBake_ *b)
@@ -796,14 +809,176 @@ static int bake_trace(CtHandle h, CtBake_ *b, float *table, uint32_t samples)
     return CT_OK;
 }
 
+// ---- the adaptive traced bake (ct_bake_traced_adaptive): rounds of experiments for the entries that have not converged ----------
+static uint64_t bake_trace_total(const CtBake_ *b)
+{
+    const uint64_t block = (uint64_t)b->azimuths * b->cosines;
+    return b->sparse ? b->active * block : b->entries;
+}
+
+// What an adaptive trace writes: the bake's own arrays, or ct_bake_retrace_adaptive's second set.
+struct BakeAdaptiveSet {
+    DevBuf<float> table, m2;
+    DevBuf<uint32_t> counts, live[2], waves;
+};
+struct BakeAdaptiveTarget {
+    float *table, *m2;
+    uint32_t *counts, *live[2], *waves;
+};
+
+// m2, counts, the live lists and the wave counts of b (and the table, with_table), whose kind and active count are known.
+static int bake_adaptive_reserve(CtHandle h, const CtBake_ *b, BakeAdaptiveSet &s, bool with_table, const char *who)
+{
+    const size_t total = (size_t)std::max<uint64_t>(1, bake_trace_total(b)), stored = (size_t)b->stored;
+    if ((with_table && s.table.alloc(stored) != hipSuccess) || s.m2.alloc(stored) != hipSuccess || s.counts.alloc(stored) != hipSuccess ||
+        s.live[0].alloc(total) != hipSuccess || s.live[1].alloc(total) != hipSuccess || s.waves.alloc((total + 255u) / 256u * 4u + 1u) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(h, CT_E_NOMEM, "%s: no device memory for the variances, counts and live lists of %llu stored entries", who,
+                    (unsigned long long)b->stored);
+    }
+    return CT_OK;
+}
+
+// The parameters of an adaptive bake; nothing of the handle is touched.
+static int bake_adaptive_validate(CtHandle h, const CtBakeAdaptive *p, const char *who)
+{
+    if (p->abi_version != CT_ABI_VERSION) {
+        return fail(h, CT_E_INVAL, "%s: parameters of abi_version %u, this library is %u", who, p->abi_version, CT_ABI_VERSION);
+    }
+    if (p->round_samples == 0u || p->round_samples > 0xffffu) {
+        return fail(h, CT_E_INVAL, "%s: round_samples %u, a round traces 1 .. 65535 experiments per entry", who, p->round_samples);
+    }
+    if (p->max_samples == 0u || p->max_samples % p->round_samples != 0u || p->max_samples > (1u << 24)) {
+        return fail(h, CT_E_INVAL, "%s: max_samples %u; a multiple of round_samples (%u), at most 2^24", who, p->max_samples, p->round_samples);
+    }
+    if (!std::isfinite(p->rel_tol) || !std::isfinite(p->abs_tol) || p->rel_tol < 0.f || p->abs_tol < 0.f) {
+        return fail(h, CT_E_INVAL, "%s: rel_tol and abs_tol must be finite and not negative", who);
+    }
+    return CT_OK;
+}
+
+// b takes over what a trace has filled (the table, when the set has one).
+static void bake_adaptive_adopt(CtBake_ *b, BakeAdaptiveSet &s)
+{
+    if (s.table) {
+        b->d_table = std::move(s.table);
+    }
+    b->d_m2 = std::move(s.m2);
+    b->d_counts = std::move(s.counts);
+    b->d_live[0] = std::move(s.live[0]);
+    b->d_live[1] = std::move(s.live[1]);
+    b->d_waves = std::move(s.waves);
+}
+
+// Rounds of b->ap.round_samples experiments until no entry is live or the live ones hold b->cap.  On entry the `n_live` live
+// entries all hold b->samples experiments; listed: they are t.live[b->live_cur], otherwise (the first round) every stored entry
+// of an active node.  The stream is idle, the tables of b's frame are uploaded, t's table, m2 and counts hold the state.  A
+// round's live entries go through bake_trace's chunks (whole groups of 64: a chunk's waves are the live list's) and passes;
+// behind the last fold of the round follow the scan, the compacting write into the other list and the read of the survivors'
+// number, which point_launch's wait covers.  Books b's counts and times; b->live entries are left at the cap, unconverged.
+static int bake_trace_adaptive(CtHandle h, CtBake_ *b, const BakeAdaptiveTarget &t, uint64_t n_live, bool listed)
+{
+    b->trace_ms = b->fold_ms = b->test_ms = 0;
+    const uint32_t R = b->ap.round_samples, budget = bake_trace_budget(h);
+    DevScene sc = h->dev;
+    sc.mode = CT_MODE_SUN_MULTIPLE_SCATTER;
+    Event ev[6];
+    for (Event &e : ev) {
+        HIPCHK(h, e.create());
+    }
+    CtHandle_::PointBuffers &pt = h->pt;
+    const BakeAdaptiveState st{ t.table, t.m2, t.counts, b->ap.rel_tol, b->ap.abs_tol, b->ap.zero_samples };
+    const double render_before = h->render_ms;
+    double fold_ms = 0, test_ms = 0;
+    while (n_live != 0u && b->samples < b->cap) {
+        const uint32_t c = b->samples, L = (uint32_t)n_live;
+        uint32_t chunk = std::min(L, std::min<uint32_t>(budget, 1u << 20));
+        if (chunk >= 64u) {
+            chunk &= ~63u;
+        }
+        const uint32_t *live_in = listed ? t.live[b->live_cur] : nullptr;
+        uint32_t *live_out = t.live[listed ? b->live_cur ^ 1 : 0];
+        uint32_t survivors = 0;
+        for (uint32_t first = 0; first < L; first += chunk) {
+            BakeTraceArgs a{};
+            a.list = b->sparse ? b->d_list : nullptr;
+            a.axes = b->d_probe;
+            a.directions = b->d_dirs;
+            a.nx = b->grid[0];
+            a.ny = b->grid[1];
+            a.nphi = b->azimuths;
+            a.nc = b->cosines;
+            a.first = first;
+            a.n = std::min(chunk, L - first);
+            a.n_pad = (a.n + 63u) & ~63u;
+            a.compact = b->compact ? 1u : 0u;
+            a.live = live_in;
+            const uint32_t per_pass = std::min(0xffffu, std::max(1u, budget / a.n_pad));
+            for (uint32_t at = 0; at < R; at += per_pass) {
+                const uint32_t passes = std::min(per_pass, R - at), done = c + at;
+                const bool last_pass = at + passes == R, last = last_pass && first + a.n == L;
+                const int rc = point_launch(
+                    h, sc, a.n, done + 1u, passes,
+                    [&]() -> int {
+                        HIPCHK(h, hipEventRecord(ev[0], h->stream));
+                        HIPCHK(h, launch_bake_trace_tasks(sc, a, pt.primary, pt.pixels, h->stream));
+                        HIPCHK(h, hipEventRecord(ev[1], h->stream));
+                        return CT_OK;
+                    },
+                    [&]() -> int {
+                        HIPCHK(h, hipEventRecord(ev[2], h->stream));
+                        HIPCHK(h, launch_bake_adaptive_fold(a, pt.frames, a.n_pad, passes, done, st, last_pass ? t.waves : nullptr, h->stream));
+                        HIPCHK(h, hipEventRecord(ev[3], h->stream));
+                        if (last) {
+                            HIPCHK(h, hipEventRecord(ev[4], h->stream));
+                            HIPCHK(h, launch_bake_adaptive_scan(t.waves, L, h->stream));
+                            HIPCHK(h, launch_bake_adaptive_compact(a, st, live_in, L, t.waves, live_out, h->stream));
+                            HIPCHK(h, hipEventRecord(ev[5], h->stream));
+                            HIPCHK(h, hipMemcpyAsync(&survivors, t.waves + (L + 63u) / 64u, sizeof survivors, hipMemcpyDeviceToHost, h->stream));
+                        }
+                        return CT_OK;
+                    });
+                if (rc != CT_OK) {
+                    return rc;
+                }
+                float ms0 = 0, ms1 = 0, ms2 = 0;
+                HIPCHK(h, hipEventElapsedTime(&ms0, ev[0], ev[1]));
+                HIPCHK(h, hipEventElapsedTime(&ms1, ev[2], ev[3]));
+                if (last) {
+                    HIPCHK(h, hipEventElapsedTime(&ms2, ev[4], ev[5]));
+                }
+                fold_ms += (double)ms0 + (double)ms1;
+                test_ms += (double)ms2;
+            }
+        }
+        if (survivors > L) {
+            return fail(h, CT_E_HIP, "internal: a round of %u live entries counted %u survivors", L, survivors);
+        }
+        b->samples = c + R;
+        b->rounds += 1u;
+        b->paths += (uint64_t)L * R;
+        b->live_cur = listed ? b->live_cur ^ 1 : 0;
+        listed = true;
+        n_live = survivors;
+        b->live = n_live;   // (with every round: a call that fails later leaves whole rounds)
+    }
+    b->live = n_live;
+    b->trace_ms = h->render_ms - render_before;
+    b->fold_ms = fold_ms;
+    b->test_ms = test_ms;
+    return CT_OK;
+}
+
 // ct_network_bake, ct_network_bake_sparse and ct_network_bake_compact: one validation, one order of errors.  trace_samples:
 // ct_bake_traced, which takes no network (n is NULL) and fills the table with that many experiments per entry.
 enum class BakeKind { Dense, Sparse, Compact };
 
-static int bake_create(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtBake *out, BakeKind kind, const uint32_t *trace_samples = nullptr)
+// adaptive: ct_bake_traced_adaptive, traced likewise, in rounds under the stopping rule of *adaptive.
+static int bake_create(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtBake *out, BakeKind kind, const uint32_t *trace_samples = nullptr,
+                       const CtBakeAdaptive *adaptive = nullptr)
 {
-    const bool sparse = kind != BakeKind::Dense, compact = kind == BakeKind::Compact, traced = trace_samples != nullptr;
-    const char *const who = traced ? "ct_bake_traced" : compact ? "ct_network_bake_compact" : sparse ? "ct_network_bake_sparse" : "ct_network_bake";
+    const bool sparse = kind != BakeKind::Dense, compact = kind == BakeKind::Compact, traced = trace_samples != nullptr || adaptive != nullptr;
+    const char *const who = adaptive ? "ct_bake_traced_adaptive" : traced ? "ct_bake_traced" : compact ? "ct_network_bake_compact" : sparse ? "ct_network_bake_sparse" : "ct_network_bake";
     if (!h) {
         return fail(nullptr, CT_E_INVAL, "null handle");
     }
@@ -831,8 +1006,14 @@ static int bake_create(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtBake *out
     if (!compact && entries > (1ull << 26)) {        // (a compact bake bounds what it stores, once the mask has been counted)
         return fail(h, CT_E_INVAL, "%s: %llu entries, a table holds at most 2^26", who, (unsigned long long)entries);
     }
-    if (traced && *trace_samples > 0xffffu) {
+    if (trace_samples && *trace_samples > 0xffffu) {
         return fail(h, CT_E_INVAL, "%s: %u samples, one call traces at most 65535", who, *trace_samples);
+    }
+    if (adaptive) {
+        const int rc = bake_adaptive_validate(h, adaptive, who);
+        if (rc != CT_OK) {
+            return rc;
+        }
     }
     if (traced && (h->scene.flags & CT_FLAG_SIMPLE_KERNEL)) {
         return fail(h, CT_E_INVAL, "%s: point radiance tasks need the persistent kernel", who);
@@ -907,8 +1088,30 @@ static int bake_create(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtBake *out
         b->d_list = std::move(m.list);
         b->d_slots = std::move(m.slots);   // (empty unless compact)
     }
+    BakeAdaptiveSet set;
+    if (adaptive) {   // (a dense bake: no kernel has run yet; the others: behind the mask's count, like the compact table)
+        b->adaptive = true;
+        b->ap = *adaptive;
+        b->cap = adaptive->max_samples;
+        rc = bake_adaptive_reserve(h, b, set, false, who);
+        if (rc != CT_OK) {
+            delete b;
+            return rc;
+        }
+    }
     bake_frame(h, b);
-    if (traced) {
+    if (adaptive) {
+        rc = drained(h, [&]() -> int {
+            const BakeAdaptiveTarget t{ b->d_table, set.m2, set.counts, { set.live[0], set.live[1] }, set.waves };
+            HIPCHK(h, hipMemsetAsync(t.table, 0, (size_t)b->stored * sizeof(float), h->stream));
+            HIPCHK(h, hipMemsetAsync(t.m2, 0, (size_t)b->stored * sizeof(float), h->stream));
+            HIPCHK(h, hipMemsetAsync(t.counts, 0, (size_t)b->stored * sizeof(uint32_t), h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            const int up = bake_upload_trace_tables(h, b);
+            return up != CT_OK ? up : bake_trace_adaptive(h, b, t, bake_trace_total(b), false);
+        });
+        bake_adaptive_adopt(b, set);
+    } else if (traced) {
         rc = drained(h, [&]() -> int {
             HIPCHK(h, hipMemsetAsync(b->d_table, 0, (size_t)b->stored * sizeof(float), h->stream));
             HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1104,7 +1307,8 @@ extern "C" int ct_bake_update(CtHandle h, CtNetwork n, CtBake b)
         return fail(h, CT_E_INVAL, "%s: the bake was made on another handle", who);
     }
     if (b->traced) {
-        return fail(h, CT_E_INVAL, "%s: a traced bake holds no network's outputs; ct_bake_retrace traces it again", who);
+        return fail(h, CT_E_INVAL, "%s: a traced bake holds no network's outputs; %s traces it again", who,
+                    b->adaptive ? "ct_bake_retrace_adaptive" : "ct_bake_retrace");
     }
     rc = flush(h);
     if (rc != CT_OK) {
@@ -1142,6 +1346,10 @@ static int bake_trace_checks(CtHandle h, CtBake b, uint32_t samples, const char 
     }
     if (!b->traced) {
         return fail(h, CT_E_INVAL, "%s: the bake holds a network's outputs; ct_bake_update bakes it again", who);
+    }
+    if (b->adaptive) {
+        return fail(h, CT_E_INVAL, "%s: the entries of an adaptive bake hold different counts; ct_bake_trace_adaptive_more raises its cap, "
+                                   "ct_bake_retrace_adaptive traces it again", who);
     }
     if (samples == 0u || samples > 0xffffu) {
         return fail(h, CT_E_INVAL, "%s: %u samples, a call traces 1 .. 65535", who, samples);
@@ -1224,6 +1432,168 @@ extern "C" int ct_bake_trace_info(CtBake b, CtBakeTraceInfo *out)
         out->fold_ms = b->fold_ms;
     }
     return CT_OK;
+}
+
+extern "C" int ct_bake_traced_adaptive(CtHandle h, const CtBakeDesc *d, uint32_t kind, const CtBakeAdaptive *p, CtBake *out)
+{
+    const char *const who = "ct_bake_traced_adaptive";
+    if (!h) {
+        return fail(nullptr, CT_E_INVAL, "null handle");
+    }
+    if (!d || !p || !out) {
+        return fail(h, CT_E_INVAL, "%s: need a description, parameters and out", who);
+    }
+    *out = nullptr;
+    if (kind != CT_BAKE_DENSE && kind != CT_BAKE_SPARSE && kind != CT_BAKE_COMPACT) {
+        return fail(h, CT_E_INVAL, "%s: unknown kind %u (CT_BAKE_DENSE, CT_BAKE_SPARSE or CT_BAKE_COMPACT)", who, kind);
+    }
+    return bake_create(h, nullptr, d, out, kind == CT_BAKE_COMPACT ? BakeKind::Compact : kind == CT_BAKE_SPARSE ? BakeKind::Sparse : BakeKind::Dense,
+                       nullptr, p);
+}
+
+// What ct_bake_trace_adaptive_more and ct_bake_retrace_adaptive check alike, in this order; the device is set, nothing is flushed.
+static int bake_adaptive_checks(CtHandle h, CtBake b, const char *who)
+{
+    if (!h) {
+        return fail(nullptr, CT_E_INVAL, "null handle");
+    }
+    if (!b) {
+        return fail(h, CT_E_INVAL, "%s: need a bake", who);
+    }
+    NEED_NOFLUSH(h);
+    if (b->h != h) {
+        return fail(h, CT_E_INVAL, "%s: the bake was made on another handle", who);
+    }
+    if (!b->adaptive) {
+        return fail(h, CT_E_INVAL, "%s: the bake was not made by ct_bake_traced_adaptive; %s", who,
+                    b->traced ? "ct_bake_trace_more / ct_bake_retrace trace it" : "ct_bake_update bakes it again");
+    }
+    return CT_OK;
+}
+
+static BakeAdaptiveTarget bake_adaptive_target(const CtBake_ *b)
+{
+    return { b->d_table, b->d_m2, b->d_counts, { b->d_live[0], b->d_live[1] }, b->d_waves };
+}
+
+extern "C" int ct_bake_trace_adaptive_more(CtHandle h, CtBake b, uint32_t max_samples)
+{
+    const char *const who = "ct_bake_trace_adaptive_more";
+    int rc = bake_adaptive_checks(h, b, who);
+    if (rc != CT_OK) {
+        return rc;
+    }
+    if (max_samples <= b->cap || max_samples % b->ap.round_samples != 0u || max_samples > (1u << 24)) {
+        return fail(h, CT_E_INVAL, "%s: max_samples %u; a multiple of round_samples (%u) above the cap in force (%u), at most 2^24", who,
+                    max_samples, b->ap.round_samples, b->cap);
+    }
+    if (b->epoch != h->light_epoch) {
+        return fail(h, CT_E_STATE, "%s: the handle's light has changed since the bake; ct_bake_retrace_adaptive traces it again", who);
+    }
+    rc = flush(h);
+    if (rc != CT_OK) {
+        return rc;
+    }
+    // (in place, like ct_bake_trace_more: a failure between two rounds leaves the rounds that were completed)
+    return drained(h, [&]() -> int {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        b->cap = max_samples;
+        return bake_trace_adaptive(h, b, bake_adaptive_target(b), b->live, true);
+    });
+}
+
+extern "C" int ct_bake_retrace_adaptive(CtHandle h, CtBake b)
+{
+    const char *const who = "ct_bake_retrace_adaptive";
+    int rc = bake_adaptive_checks(h, b, who);
+    if (rc == CT_OK) {
+        rc = flush(h);
+    }
+    if (rc != CT_OK) {
+        return rc;
+    }
+    // into a second table, m2, counts and pair of live lists: a failure leaves the bake as it was
+    BakeAdaptiveSet fresh;
+    rc = bake_adaptive_reserve(h, b, fresh, true, who);
+    if (rc != CT_OK) {
+        return rc;
+    }
+    const BakeState before = *b;
+    bake_frame(h, b);
+    b->samples = b->rounds = 0;
+    b->paths = b->live = 0;
+    rc = drained(h, [&]() -> int {
+        const BakeAdaptiveTarget t{ fresh.table, fresh.m2, fresh.counts, { fresh.live[0], fresh.live[1] }, fresh.waves };
+        HIPCHK(h, hipMemsetAsync(t.table, 0, (size_t)b->stored * sizeof(float), h->stream));
+        HIPCHK(h, hipMemsetAsync(t.m2, 0, (size_t)b->stored * sizeof(float), h->stream));
+        HIPCHK(h, hipMemsetAsync(t.counts, 0, (size_t)b->stored * sizeof(uint32_t), h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        const int up = bake_upload_trace_tables(h, b);
+        return up != CT_OK ? up : bake_trace_adaptive(h, b, t, bake_trace_total(b), false);
+    });
+    if (rc != CT_OK) {
+        const std::string text = h->error;
+        static_cast<BakeState &>(*b) = before;
+        if (bake_upload_trace_tables(h, b) == CT_OK) {   // (the old frame's tables again; otherwise that failure is the one to report)
+            h->error = text;
+        }
+        return rc;
+    }
+    bake_adaptive_adopt(b, fresh);
+    return CT_OK;
+}
+
+extern "C" int ct_bake_adaptive_info(CtBake b, CtBakeAdaptiveInfo *out)
+{
+    if (!b || !out) {
+        return fail(b ? b->h : nullptr, CT_E_INVAL, "ct_bake_adaptive_info: need a bake and out");
+    }
+    *out = CtBakeAdaptiveInfo{};
+    if (b->adaptive) {
+        out->adaptive = 1u;
+        out->round_samples = b->ap.round_samples;
+        out->max_samples = b->cap;
+        out->zero_samples = b->ap.zero_samples;
+        out->rel_tol = b->ap.rel_tol;
+        out->abs_tol = b->ap.abs_tol;
+        out->rounds = b->rounds;
+        out->entries_active = bake_trace_total(b);
+        out->capped = b->live;
+        out->converged = b->rounds != 0u ? out->entries_active - b->live : 0u;
+        out->paths = b->paths;
+        out->trace_ms = b->trace_ms;
+        out->fold_ms = b->fold_ms;
+        out->test_ms = b->test_ms;
+    }
+    return CT_OK;
+}
+
+// ct_bake_download_counts and ct_bake_download_m2: `count` words of an adaptive bake's array, as stored.
+static int bake_adaptive_download(CtBake b, const void *dev, void *host_out, size_t count, const char *who)
+{
+    if (!b) {
+        return fail(nullptr, CT_E_INVAL, "%s: null bake", who);
+    }
+    CtHandle h = b->h;
+    if (!b->adaptive) {
+        return fail(h, CT_E_INVAL, "%s: only a bake of ct_bake_traced_adaptive keeps counts and variances", who);
+    }
+    if (!host_out || count != b->stored) {
+        return fail(h, CT_E_INVAL, "%s: need an array of exactly %llu values", who, (unsigned long long)b->stored);
+    }
+    NEED(h);
+    HIPCHK(h, hipMemcpy(host_out, dev, count * 4u, hipMemcpyDeviceToHost));
+    return CT_OK;
+}
+
+extern "C" int ct_bake_download_counts(CtBake b, uint32_t *counts_host_out, size_t count)
+{
+    return bake_adaptive_download(b, b ? b->d_counts.get() : nullptr, counts_host_out, count, "ct_bake_download_counts");
+}
+
+extern "C" int ct_bake_download_m2(CtBake b, float *m2_host_out, size_t count)
+{
+    return bake_adaptive_download(b, b ? b->d_m2.get() : nullptr, m2_host_out, count, "ct_bake_download_m2");
 }
 
 extern "C" int ct_bake_directions(CtBake b, float *directions_host_out, size_t count)
@@ -1332,7 +1702,8 @@ static int bake_stale(CtHandle h, CtBake b, const char *who)
 {
     if (b->epoch != h->light_epoch) {
         return fail(h, CT_E_STATE, "%s: the handle's light has changed since the bake; %s", who,
-                    b->traced ? "ct_bake_retrace traces it again" : "ct_bake_update bakes it again");
+                    b->adaptive ? "ct_bake_retrace_adaptive traces it again" : b->traced ? "ct_bake_retrace traces it again"
+                                                                                           : "ct_bake_update bakes it again");
     }
     return CT_OK;
 }

@@ -5,6 +5,7 @@
 #include "Exr.h"
 #include <algorithm>
 #include <cfloat>
+#include <cstdio>
 #include <filesystem>
 
 #include "NetworkFile.h"
@@ -196,11 +197,15 @@ namespace DeepestScatter
     // The baked renderer without a network (--traced-bake NX,NY,NZ,NPHI,NC --bake-samples N): the probe table holds the means of
     // N experiments of the path tracer's point estimator per entry (ct_bake_traced) and every subframe is interpolated from it.
     // Traced in init, and again (ct_bake_retrace) should the light have changed since.  One GPU only.
+    // With --bake-adaptive R,MAX[,REL[,ABS[,ZERO]]] in place of --bake-samples the table is traced in rounds under the stopping rule
+    // (ct_bake_traced_adaptive, ct_bake_retrace_adaptive) and init prints what ct_bake_adaptive_info reports.
     class TracedBakeRenderer : public PathTracingRenderer
     {
     public:
-        TracedBakeRenderer(std::shared_ptr<Context> context, const CtNetworkRender& params, const CtBakeDesc& desc, uint32_t kind, uint32_t samples)
-            : PathTracingRenderer(std::move(context)), params(params), desc(desc), kind(kind), samples(samples) {}
+        TracedBakeRenderer(std::shared_ptr<Context> context, const CtNetworkRender& params, const CtBakeDesc& desc, uint32_t kind, uint32_t samples,
+                           const CtBakeAdaptive* adaptive = nullptr)
+            : PathTracingRenderer(std::move(context)), params(params), desc(desc), kind(kind), samples(samples), isAdaptive(adaptive != nullptr),
+              adaptive(adaptive ? *adaptive : CtBakeAdaptive{}) {}
         ~TracedBakeRenderer() override
         {
             if (bake) ct_bake_destroy(bake);   // (before the handle)
@@ -210,7 +215,14 @@ namespace DeepestScatter
         {
             PathTracingRenderer::init();
             if (context->group) throw std::runtime_error("--traced-bake renders on one GPU only");
-            if (!bake) Context::check(ct_bake_traced(context->handle, &desc, kind, samples, &bake), context->handle, "ct_bake_traced");
+            if (bake) return;
+            if (!isAdaptive)
+            {
+                Context::check(ct_bake_traced(context->handle, &desc, kind, samples, &bake), context->handle, "ct_bake_traced");
+                return;
+            }
+            Context::check(ct_bake_traced_adaptive(context->handle, &desc, kind, &adaptive, &bake), context->handle, "ct_bake_traced_adaptive");
+            printAdaptiveInfo();
         }
 
         void render(float* frameResultBuffer) override
@@ -234,12 +246,31 @@ namespace DeepestScatter
         {
             CtBakeInfo info;
             Context::check(ct_bake_info(bake, &info), context->handle, "ct_bake_info");
-            if (!info.current) Context::check(ct_bake_retrace(context->handle, bake, samples), context->handle, "ct_bake_retrace");
+            if (info.current) return;
+            if (!isAdaptive)
+            {
+                Context::check(ct_bake_retrace(context->handle, bake, samples), context->handle, "ct_bake_retrace");
+                return;
+            }
+            Context::check(ct_bake_retrace_adaptive(context->handle, bake), context->handle, "ct_bake_retrace_adaptive");
+            printAdaptiveInfo();
+        }
+
+        void printAdaptiveInfo()
+        {
+            CtBakeAdaptiveInfo i;
+            Context::check(ct_bake_adaptive_info(bake, &i), context->handle, "ct_bake_adaptive_info");
+            std::printf("adaptive bake: %u rounds of %u, cap %u; %llu entries, %llu converged, %llu capped, %llu paths; "
+                        "trace %.3f ms, fold %.3f ms, test %.3f ms\n", i.rounds, i.round_samples, i.max_samples,
+                        (unsigned long long)i.entries_active, (unsigned long long)i.converged, (unsigned long long)i.capped,
+                        (unsigned long long)i.paths, i.trace_ms, i.fold_ms, i.test_ms);
         }
 
         CtNetworkRender params;
         CtBakeDesc desc;
         uint32_t kind, samples;
+        bool isAdaptive;
+        CtBakeAdaptive adaptive;
         CtBake bake = nullptr;
     };
 

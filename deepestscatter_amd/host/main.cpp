@@ -20,6 +20,9 @@
 //              [--traced-bake NX,NY,NZ,NPHI,NC --bake-samples N [--net-bake-sparse | --net-bake-compact] [--net-direct]]   without
 //                               --network: fill that probe grid with N path-traced experiments per entry (ct_bake_traced) and
 //                               interpolate every subframe from the table; --net-scale and --net-transform apply; one GPU
+//              [--bake-adaptive R,MAX[,REL[,ABS[,ZERO]]]]   in place of --bake-samples: trace in rounds of R experiments, only the entries
+//                               that fail the stopping rule (95 % interval below REL of the mean, default 0.02, or below ABS, default
+//                               1e-4; a zero entry after ZERO experiments, default 100000), at most MAX each (ct_bake_traced_adaptive)
 //   <cloud> = file.vdb | procedural:<N>[:<seed>] | file.f32grid
 //
 //   cloudtrace collect <cloud>|@list.txt [--scene-id I] [--scenes N] [--jobs K] [--gpus ..] [--batch 2048] [--light L] [--size-m M] [--out DIR] [--data DIR] [--estimator ..] [--tex-fixed8]
@@ -83,6 +86,8 @@ namespace
         bool netBakeCompact = false;                                              // --net-bake-compact: ct_network_bake_compact in place of ct_network_bake
         bool tracedBake = false;                                                  // --traced-bake NX,NY,NZ,NPHI,NC: the table of `bake` traced, no network (TracedBakeRenderer)
         uint32_t bakeSamples = 0;                                                 // --bake-samples N: experiments per entry of the traced bake
+        bool bakeAdaptive = false;                                                // --bake-adaptive R,MAX[,REL[,ABS[,ZERO]]]: the traced bake in rounds under the stopping rule
+        CtBakeAdaptive adaptive{ CT_ABI_VERSION, 0, 0, 100000, 2e-2f, 1e-4f };
         bool netDirect = false;                                                   // --net-direct: CT_NET_ADD_SINGLE_SCATTER joins networkRender.transform
         bool collect = false;                                                     // `cloudtrace collect ...`
         int32_t sceneId = 0;
@@ -282,7 +287,8 @@ namespace
             auto outputPath = std::filesystem::path(opt.outDir) / (stem + "." + toString(lightDirection) + "." + PathTracingRenderer::NAME + "." + opt.format);
             // installFramework + installApp: Sun, VDBCloud, CloudMaterial, Camera in this order (installers.cpp:28-38)
             std::shared_ptr<PathTracingRenderer> renderer = opt.tracedBake ? std::make_shared<TracedBakeRenderer>(context, opt.networkRender, opt.bake,
-                    opt.netBakeCompact ? CT_BAKE_COMPACT : opt.netBakeSparse ? CT_BAKE_SPARSE : CT_BAKE_DENSE, opt.bakeSamples)
+                    opt.netBakeCompact ? CT_BAKE_COMPACT : opt.netBakeSparse ? CT_BAKE_SPARSE : CT_BAKE_DENSE, opt.bakeSamples,
+                    opt.bakeAdaptive ? &opt.adaptive : nullptr)
                 : !opt.network ? std::make_shared<PathTracingRenderer>(context)
                 : opt.netBaked ? std::make_shared<BakedRenderer>(context, opt.network, opt.networkRender, opt.bake, opt.netBakeSparse, opt.netBakeCompact)
                                : std::make_shared<NetworkRenderer>(context, opt.network, opt.networkRender);
@@ -376,6 +382,12 @@ int main(int argc, char* argv[])
                 if (n < 1 || n > 65535) throw std::invalid_argument("--bake-samples N, 1 .. 65535");
                 opt.bakeSamples = (uint32_t)n;
             }
+            else if (a == "--bake-adaptive")
+            {
+                CtBakeAdaptive& p = opt.adaptive;
+                if (std::sscanf(next().c_str(), "%u,%u,%f,%f,%u", &p.round_samples, &p.max_samples, &p.rel_tol, &p.abs_tol, &p.zero_samples) < 2) throw std::invalid_argument("--bake-adaptive R,MAX[,REL[,ABS[,ZERO]]]");
+                opt.bakeAdaptive = true;
+            }
             else if (a == "--net-bake-sparse")
             {
                 opt.netBakeSparse = true;
@@ -417,7 +429,9 @@ int main(int argc, char* argv[])
         if (opt.netDirect) opt.networkRender.transform |= CT_NET_ADD_SINGLE_SCATTER;   // (after the loop: --net-transform may follow it)
         if (opt.tracedBake && !opt.networkPath.empty()) throw std::invalid_argument("--traced-bake fills the table with path-traced radiance: it cannot be combined with --network");
         if (opt.tracedBake && opt.netBaked) throw std::invalid_argument("--traced-bake and --net-baked are two ways to fill one table: give one of them");
-        if (opt.tracedBake && opt.bakeSamples == 0) throw std::invalid_argument("--traced-bake needs --bake-samples N");
+        if (opt.bakeAdaptive && opt.bakeSamples != 0) throw std::invalid_argument("--bake-adaptive and --bake-samples are two ways to trace one table: give one of them");
+        if (opt.bakeAdaptive && !opt.tracedBake) throw std::invalid_argument("--bake-adaptive sets the rounds of --traced-bake NX,NY,NZ,NPHI,NC");
+        if (opt.tracedBake && opt.bakeSamples == 0 && !opt.bakeAdaptive) throw std::invalid_argument("--traced-bake needs --bake-samples N or --bake-adaptive R,MAX[,REL[,ABS[,ZERO]]]");
         if (opt.bakeSamples != 0 && !opt.tracedBake) throw std::invalid_argument("--bake-samples counts the experiments of --traced-bake NX,NY,NZ,NPHI,NC");
         if (opt.tracedBake && !opt.devices.empty()) throw std::invalid_argument("--traced-bake renders on one GPU: it cannot be combined with --gpus");
         if (opt.netBakeCompact && !opt.netBaked && !opt.tracedBake) throw std::invalid_argument("--net-bake-compact chooses how --net-baked NX,NY,NZ,NPHI,NC bakes and stores its table");

@@ -12,6 +12,7 @@ residual MLP of the paper the reference implements (Kallweit et al. 2017), param
     bake_azimuth / bake_lookup_reference   numpy float32 restatement of the table lookup: what the device is held to
     bake_mask_reference numpy restatement of the sparse bake's mask (ct_network_bake_sparse): cells, nodes and the margin M
     bake_slots_reference numpy restatement of the compact bake's slot index (ct_network_bake_compact)
+    point_fold_var_reference / point_converged_reference   numpy restatement of an adaptive traced bake's fold and stopping rule
     save_weights / load_weights   the weight file `cloudtrace --network` reads
 
 State-dict names (the mapping an exported model needs): blocks.k.fc1 = W1_k, c1_k; blocks.k.fc2 = W2_k, c2_k (k = 0 .. 9);
@@ -327,6 +328,55 @@ def point_fold_reference(values_f32, mean=None, count: int = 0) -> np.ndarray:
     return rad
 
 
+def point_fold_var_reference(values_f32, mean=None, m2=None, count=0):
+    """PointRadianceTask::addExperimentResult applied to values_f32[0], values_f32[1], ... (float32 [S, ...]) in order, every
+    operation rounded to float32: experimentCount++, N = (float)count, newWeight = (float)(1.0 / (double)N), newMean = mean +
+    (x - mean) * newWeight, runningVariance += (x - mean) * (x - newMean) with the old mean in the first factor -- what
+    ct_point_radiance_launch and an adaptive traced bake store.  mean / m2 / count: the state to continue from (default: zeros);
+    count is one number or an integer array of the values' shape -> (mean, m2, count)."""
+    f32 = np.float32
+    v = np.ascontiguousarray(values_f32, f32)
+    rad = np.zeros(v.shape[1:], f32) if mean is None else np.array(mean, f32)
+    var = np.zeros(v.shape[1:], f32) if m2 is None else np.array(m2, f32)
+    cnt = np.broadcast_to(np.asarray(count, np.int64), v.shape[1:]).copy()
+    for x in v:
+        cnt = cnt + 1
+        weight = (1.0 / cnt.astype(f32).astype(np.float64)).astype(f32)
+        previous = rad
+        rad = (previous + ((x - previous).astype(f32) * weight).astype(f32)).astype(f32)
+        var = (var + ((x - previous).astype(f32) * (x - rad).astype(f32)).astype(f32)).astype(f32)
+    return rad, var, cnt
+
+
+def point_converged_reference(mean, m2, count, rel_tol, abs_tol, zero_samples) -> np.ndarray:
+    """The stopping rule of an adaptive traced bake (include/cloudtrace.h, "the adaptive traced bake"), which is
+    RadianceCollector::update's test of a PointRadianceTask (PointRadianceTask.h:23-36, RadianceCollector.cpp:112-118) with its
+    constants as parameters, in float32: absolute = (1.96f * sqrt(m2 / N)) / sqrt(N), relative = absolute / (mean + FLT_EPSILON),
+    converged = relative < rel_tol or absolute < abs_tol, and where mean < FLT_EPSILON: converged = count > zero_samples.  A NaN
+    compares false -> bool array."""
+    f32 = np.float32
+    eps = np.finfo(f32).eps
+    rad, var = np.asarray(mean, f32), np.asarray(m2, f32)
+    cnt = np.asarray(count, np.int64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        N = cnt.astype(f32)
+        absolute = (f32(1.96) * np.sqrt(var / N)) / np.sqrt(N)
+        relative = absolute / (rad + eps)
+        converged = (relative < f32(rel_tol)) | (absolute < f32(abs_tol))
+        return np.where(rad < eps, cnt > int(zero_samples), converged)
+
+
+@dataclass(frozen=True)
+class AdaptiveParams:
+    """CtBakeAdaptive: R experiments per live entry and round, the cap per entry (a multiple of R), and the stopping rule's
+    tolerances; the defaults are the reference's (RadianceCollector.cpp:112-118)."""
+    round_samples: int
+    max_samples: int
+    rel_tol: float = 2e-2
+    abs_tol: float = 1e-4
+    zero_samples: int = 100000
+
+
 # The weight file: a 32-byte little-endian header -- magic "CTNW", u32 version, blocks, width, aux, head_layers, u64 weight
 # count -- and then weight_count float32 values in the order of CtNetworkDesc.weights_host.
 WEIGHT_MAGIC = b"CTNW"
@@ -433,21 +483,33 @@ class Bake:
     rest of the table 0.  compact: ct_network_bake_compact, the sparse bake with only the active nodes stored, behind a slot index.
     Close it before the tracer; after tracer.set_light call update().
     net=None with samples=S: a traced bake (ct_bake_traced) of the same kind, whose entries are the means of S experiments of
-    the path tracer's point estimator instead of a network's outputs; trace_more() refines it, retrace() follows a new light."""
+    the path tracer's point estimator instead of a network's outputs; trace_more() refines it, retrace() follows a new light.
+    net=None with adaptive=AdaptiveParams(...) (or a dict of its fields): an adaptive traced bake (ct_bake_traced_adaptive), traced
+    in rounds until every entry passes the stopping rule or holds max_samples experiments; counts() and m2() are its per-entry
+    experiment counts and sums of squared deviations, trace_adaptive_more() raises the cap, retrace_adaptive() follows a new light."""
 
-    def __init__(self, tracer, net, grid, azimuths: int, cosines: int, sparse: bool = False, compact: bool = False, samples: int | None = None):
+    def __init__(self, tracer, net, grid, azimuths: int, cosines: int, sparse: bool = False, compact: bool = False, samples: int | None = None,
+                 adaptive: "AdaptiveParams | dict | None" = None):
         if sparse and compact:
             raise ValueError("a bake is sparse or compact, not both")
-        if net is not None and samples is not None:
-            raise ValueError("a bake holds a network's outputs (net) or traced radiance (net=None, samples=...), not both")
-        if net is None and samples is None:
-            raise ValueError("a bake needs a network, or net=None and samples=... for a traced bake")
+        if net is not None and (samples is not None or adaptive is not None):
+            raise ValueError("a bake holds a network's outputs (net) or traced radiance (net=None, samples=... or adaptive=...), not both")
+        if samples is not None and adaptive is not None:
+            raise ValueError("a traced bake takes samples=... (uniform) or adaptive=... (rounds under the stopping rule), not both")
+        if net is None and samples is None and adaptive is None:
+            raise ValueError("a bake needs a network, or net=None and samples=... or adaptive=... for a traced bake")
+        if isinstance(adaptive, dict):
+            adaptive = AdaptiveParams(**adaptive)
         self.L = _lib.load()
         self.tracer = tracer
         d = _lib.CtBakeDesc(_lib.CT_ABI_VERSION, (C.c_uint32 * 3)(*[int(v) for v in grid]), int(azimuths), int(cosines))
         b = C.c_void_p()
-        if net is None:
-            kind = _lib.CT_BAKE_COMPACT if compact else _lib.CT_BAKE_SPARSE if sparse else _lib.CT_BAKE_DENSE
+        kind = _lib.CT_BAKE_COMPACT if compact else _lib.CT_BAKE_SPARSE if sparse else _lib.CT_BAKE_DENSE
+        if adaptive is not None:
+            p = _lib.CtBakeAdaptive(_lib.CT_ABI_VERSION, int(adaptive.round_samples), int(adaptive.max_samples), int(adaptive.zero_samples),
+                                    float(adaptive.rel_tol), float(adaptive.abs_tol))
+            check(self.L.ct_bake_traced_adaptive(tracer.h, C.byref(d), kind, C.byref(p), C.byref(b)), tracer.h)
+        elif net is None:
             check(self.L.ct_bake_traced(tracer.h, C.byref(d), kind, int(samples), C.byref(b)), tracer.h)
         else:
             entry = self.L.ct_network_bake_compact if compact else self.L.ct_network_bake_sparse if sparse else self.L.ct_network_bake
@@ -489,6 +551,41 @@ class Bake:
         check(self.L.ct_bake_trace_info(self.b, C.byref(i)), self.tracer.h)
         return {"traced": bool(i.traced), "samples": int(i.samples), "paths": int(i.paths), "trace_ms": float(i.trace_ms),
                 "fold_ms": float(i.fold_ms)}
+
+    def trace_adaptive_more(self, max_samples: int):
+        """ct_bake_trace_adaptive_more: raise an adaptive bake's cap and go on with the entries that stopped at the old one."""
+        check(self.L.ct_bake_trace_adaptive_more(self.tracer.h, self.b, int(max_samples)), self.tracer.h)
+
+    def retrace_adaptive(self):
+        """ct_bake_retrace_adaptive: an adaptive bake again from experiment 1, for the tracer's light as it is now."""
+        check(self.L.ct_bake_retrace_adaptive(self.tracer.h, self.b), self.tracer.h)
+
+    def adaptive_info(self) -> dict:
+        """ct_bake_adaptive_info: adaptive, the parameters with the cap in force, rounds, entries_active, converged, capped, paths,
+        trace_ms, fold_ms, test_ms (any other bake: all zero)."""
+        i = _lib.CtBakeAdaptiveInfo()
+        check(self.L.ct_bake_adaptive_info(self.b, C.byref(i)), self.tracer.h)
+        out = {n: getattr(i, n) for n, _ in i._fields_ if n != "reserved"}
+        out["adaptive"] = bool(i.adaptive)
+        return out
+
+    def counts(self) -> np.ndarray:
+        """ct_bake_download_counts -> uint32, the experiments every entry holds, as stored: [Nz, Ny, Nx, azimuths, cosines], or
+        (compact) [slots, azimuths, cosines] like stored_table()."""
+        return self._stored_array(self.L.ct_bake_download_counts, np.uint32)
+
+    def m2(self) -> np.ndarray:
+        """ct_bake_download_m2 -> float32, every entry's sum of squared deviations (runningVariance), shaped as counts()."""
+        return self._stored_array(self.L.ct_bake_download_m2, np.float32)
+
+    def _stored_array(self, entry, dtype) -> np.ndarray:
+        i, st = self.info, self.storage_info
+        a = np.empty(st["stored_entries"], dtype)
+        check(entry(self.b, a.ctypes.data_as(C.c_void_p), a.size), self.tracer.h)
+        if st["compact"]:
+            return a.reshape(-1, i["azimuths"], i["cosines"])
+        nx, ny, nz = i["grid"]
+        return a.reshape(nz, ny, nx, i["azimuths"], i["cosines"])
 
     def directions(self) -> np.ndarray:
         """ct_bake_directions -> float32 [azimuths, cosines, 3]: d(j, k), the direction a traced bake's entry (j, k) stands for."""

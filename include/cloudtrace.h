@@ -829,6 +829,93 @@ CT_API int ct_bake_trace_info(CtBake b, CtBakeTraceInfo *out);
 /* 3 * Nphi * Nc floats, [j][k][xyz]; any kind of bake.  count must equal that number. */
 CT_API int ct_bake_directions(CtBake b, float *directions_host_out, size_t count);
 
+/* ---- the adaptive traced bake: per-entry variance and the reference's stopping rule ------------------
+ *
+ * ct_bake_traced gives every entry the same number of experiments and keeps only the mean.  ct_bake_traced_adaptive traces in
+ * rounds, keeps m2 and count beside every mean, and after each round stops the entries that pass the reference's test
+ * (PointRadianceTask.h:23-36, RadianceCollector.cpp:112-118), on the device: rule and compaction are kernels, the host reads one
+ * survivor count per round.
+ *
+ * Grid, limits, frame, cosine[k], nodes, u_j, d(j, k), mask, list, slots, the virtual index e, validation and order of errors are
+ * ct_bake_traced's for the same kind.  Experiment f of entry e is the same path: task index (uint32_t)e, seed
+ * tea<4>((uint32_t)(e * 4096), f), on a CT_MODE_SUN_MULTIPLE_SCATTER copy of the scene, with the handle's estimator and
+ * CT_FLAG_TEX_FIXED8.
+ *
+ * State per stored entry of an active node: mean (the table), m2, count, all 0 at the start.  A round: every live entry holds the
+ * same count c and receives experiments c + 1 .. c + R (R = round_samples), folded in frame order with
+ * PointRadianceTask::addExperimentResult's arithmetic in float32, no contraction:
+ *     N = (float)count, w = (float)(1.0 / (double)N), new_mean = mean + (x - mean) * w, m2 += (x - mean) * (x - new_mean)
+ * (the old mean in the first factor).  Then, in float32 with IEEE division and square root:
+ *     absolute = (1.96f * sqrt(m2 / N)) / sqrt(N),  relative = absolute / (mean + FLT_EPSILON),
+ *     converged = relative < rel_tol || absolute < abs_tol;  if mean < FLT_EPSILON: converged = count > zero_samples
+ * (a NaN compares false).  An entry leaves the live set when it is converged or count == max_samples; the call ends when the
+ * live set is empty.  In the first round every stored entry of an active node is live.  Since all live entries share c, every
+ * estimator launch of a round has first_frame_id = c + 1: max_samples is a multiple of R, and a bake continues only by a higher cap.
+ *
+ * A dense bake traces every node, sparse and compact bakes the active ones; the three agree bit for bit in mean, m2 and count
+ * on every active node's block, a sparse bake holds 0 / 0 / 0 off the mask and a compact bake 0 / 0 / 0 in its zero block.  WITH
+ * THE REFERENCE'S zero_samples (100000) A DENSE BAKE RUNS EVERY NODE WHOSE RAYS MEET NO LIT CLOUD TO THE CAP: sparse and compact
+ * bakes are the intended kinds.
+ *
+ * ct_bake_download_counts / ct_bake_download_m2 return the arrays as stored: count must equal CtBakeStorageInfo's
+ * stored_entries (the virtual count for dense and sparse bakes, [slot][Nphi][Nc] for a compact one).  CT_E_INVAL on a bake that
+ * is not adaptive.
+ *
+ * ct_bake_trace_adaptive_more(h, b, max): max is a multiple of R, greater than the current cap, at most 2^24.  Its live set is
+ * the entries that reached the old cap without converging (they all hold that count); converged entries stay as they are:
+ * adaptive(cap a) and then more(b) are the bits of adaptive(cap b).  ct_bake_retrace_adaptive, after ct_set_light, works as
+ * ct_bake_retrace: the new frame, a zeroed second table / m2 / counts, traced with the bake's parameters and cap, then all three
+ * are swapped in; a failure leaves everything as it was.
+ *
+ * On an adaptive bake ct_bake_trace_more, ct_bake_retrace and ct_bake_update are CT_E_INVAL (the message names the adaptive
+ * call), and the two adaptive calls are CT_E_INVAL on any other bake.  ct_bake_trace_info reports traced = 1, samples = the
+ * count the last round reached (rounds * R) and paths = the exact sum of the counts.  ct_baked_render_*, ct_debug_bake_lookup,
+ * ct_bake_download, ct_bake_download_stored, ct_bake_directions and the other ct_bake_* functions take it as any traced bake.
+ *
+ * Table, m2, counts, the two live lists (one word per stored entry of an active node each; the bake keeps them for
+ * ct_bake_trace_adaptive_more) and the wave counts are allocated before the first trace kernel: for a dense bake before any
+ * kernel, for a sparse or compact bake behind the mask's count, which sizes them (as it sizes a compact table there); CT_E_NOMEM
+ * leaves the handle as it was.  The estimator launches are ct_bake_traced's: a round's live
+ * entries in chunks of at most min(2^20, CT_BAKE_TRACE_RESULTS) (whole groups of 64), a chunk's R samples in passes of at most
+ * max(1, CT_BAKE_TRACE_RESULTS / padded chunk); the result depends on neither.  What the calls leave alone and what the counters
+ * see is as for ct_bake_traced.
+ *
+ * CT_E_INVAL, before anything changes, in ct_bake_traced's order and then: a NULL parameter struct, a wrong abi_version there,
+ * round_samples 0 or > 65535, a cap that is 0, no multiple of round_samples or > 2^24, a tolerance that is negative or not finite.
+ * CT_E_STATE: ct_bake_trace_adaptive_more on a bake whose light is no longer the handle's. */
+typedef struct CtBakeAdaptive {
+    uint32_t abi_version;    /* CT_ABI_VERSION */
+    uint32_t round_samples;  /* R: experiments per live entry and round, 1 .. 65535 (reference: 100) */
+    uint32_t max_samples;    /* cap per entry: a multiple of R, R .. 2^24 */
+    uint32_t zero_samples;   /* an entry whose mean is < FLT_EPSILON stops once count > zero_samples (reference: 100000) */
+    float    rel_tol;        /* finite, >= 0 (reference: 2e-2f) */
+    float    abs_tol;        /* finite, >= 0 (reference: 1e-4f) */
+} CtBakeAdaptive;            /* 24 bytes */
+typedef struct CtBakeAdaptiveInfo {
+    uint32_t adaptive;        /* 1: made by ct_bake_traced_adaptive (any other bake answers all zeros) */
+    uint32_t round_samples;   /* the bake's parameters, max_samples as ct_bake_trace_adaptive_more has left it */
+    uint32_t max_samples;
+    uint32_t zero_samples;
+    float    rel_tol;
+    float    abs_tol;
+    uint32_t rounds;          /* rounds traced since the table was (re)started */
+    uint32_t reserved;
+    uint64_t entries_active;  /* stored entries of active nodes */
+    uint64_t converged;       /* ... of them, those that passed the rule */
+    uint64_t capped;          /* ... and those at max_samples that fail it */
+    uint64_t paths;           /* the sum of the counts */
+    double   trace_ms;        /* GPU time of the last call: the estimator launches, */
+    double   fold_ms;         /* the task and fold kernels (the fold of a round's last pass evaluates the rule), */
+    double   test_ms;         /* the scans and the compacting writes */
+} CtBakeAdaptiveInfo;         /* 88 bytes; rounds at 24, entries_active at 32, paths at 56, trace_ms at 64 */
+
+CT_API int ct_bake_traced_adaptive(CtHandle h, const CtBakeDesc *d, uint32_t kind, const CtBakeAdaptive *p, CtBake *out);
+CT_API int ct_bake_trace_adaptive_more(CtHandle h, CtBake b, uint32_t max_samples);   /* raise the cap, continue */
+CT_API int ct_bake_retrace_adaptive(CtHandle h, CtBake b);                             /* after ct_set_light */
+CT_API int ct_bake_adaptive_info(CtBake b, CtBakeAdaptiveInfo *out);
+CT_API int ct_bake_download_counts(CtBake b, uint32_t *counts_host_out, size_t count);
+CT_API int ct_bake_download_m2(CtBake b, float *m2_host_out, size_t count);
+
 /* ct_network_render_subframe / _accumulate / _shard_subframe / _shard_accumulate with the table in the network's place. */
 CT_API int ct_baked_render_subframe(CtHandle h, CtBake b, const CtNetworkRender *p, uint32_t subframe_id, float *frame_rgba_dev);
 CT_API int ct_baked_render_accumulate(CtHandle h, CtBake b, const CtNetworkRender *p, uint32_t first_subframe_id, uint32_t count);

@@ -8,9 +8,13 @@ cloud, the default pose, a compact traced bake per grid (g^3 x --azimuths x --co
   baked_render_accumulate(direct=True) on the traced bake and the mode-0 path-traced mean of the same --subframes subframes;
   beside it the same distance between two path-traced means over disjoint subframe ranges (1 .. S and S + 1 .. 2 S): the noise
   floor a picture of S subframes cannot be told from.
+--adaptive R,MAX[,REL[,ABS[,ZERO]]] (defaults: the reference's 0.02, 1e-4, 100000): per grid an adaptive bake
+(ct_bake_traced_adaptive) in place of the --samples list -- its rounds, converged and capped shares, paths and
+trace / fold / test ms (CtBakeAdaptiveInfo) -- and then a uniform bake of the nearest S with at least as many paths, each with
+the same distances.
 Needs a GPU.  No threshold: resolution and samples are the user's trade.
     python tools/traced_bake_time.py [--volume 256] [--size 512] [--subframes 16] [--grids 16 32] [--azimuths 8] [--cosines 4]
-                                     [--samples 4 16] [--estimator march|delta] [--kind compact|sparse|dense]"""
+                                     [--samples 4 16 | --adaptive 16,256] [--estimator march|delta] [--kind compact|sparse|dense]"""
 import argparse, json, statistics, sys, time
 from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
@@ -33,6 +37,7 @@ if __name__ == "__main__":
     ap.add_argument("--azimuths", type=int, default=8)
     ap.add_argument("--cosines", type=int, default=4)
     ap.add_argument("--samples", type=int, nargs="+", default=[4, 16])
+    ap.add_argument("--adaptive", default=None, metavar="R,MAX[,REL[,ABS[,ZERO]]]")
     ap.add_argument("--estimator", choices=["march", "delta"], default="march")
     ap.add_argument("--kind", choices=["compact", "sparse", "dense"], default="compact")
     a = ap.parse_args()
@@ -54,12 +59,28 @@ if __name__ == "__main__":
               "pixels_with_a_record": int(lit.sum()),
               "relative_l2_of_two_path_traced_means": rel_l2(second, first, lit)}
     kw = {"compact": a.kind == "compact", "sparse": a.kind == "sparse"}
+    adaptive = None
+    if a.adaptive:
+        v = a.adaptive.split(",")
+        adaptive = dict(zip(("round_samples", "max_samples", "rel_tol", "abs_tol", "zero_samples"),
+                            [int(v[0]), int(v[1])] + [float(x) for x in v[2:4]] + [int(x) for x in v[4:5]]))
     for g in a.grids:
-        for samples in a.samples:
+        runs = [None] if adaptive else list(a.samples)                    # None: the adaptive bake, which appends its uniform twin
+        for samples in runs:
             t0 = time.perf_counter()
-            bake = tr.traced_bake((g, g, g), a.azimuths, a.cosines, samples, **kw)
+            if samples is None:
+                bake = tr.traced_bake_adaptive((g, g, g), a.azimuths, a.cosines, **adaptive, **kw)
+            else:
+                bake = tr.traced_bake((g, g, g), a.azimuths, a.cosines, samples, **kw)
             wall = (time.perf_counter() - t0) * 1e3
             ti, sp, st = bake.trace_info(), bake.sparse_info, bake.storage_info
+            extra = {}
+            if samples is None:
+                ai = bake.adaptive_info()
+                extra = {"adaptive": adaptive, "rounds": ai["rounds"], "entries_active": ai["entries_active"],
+                         "converged_share": ai["converged"] / max(ai["entries_active"], 1), "capped_share": ai["capped"] / max(ai["entries_active"], 1),
+                         "test_ms": ai["test_ms"], "mean_samples_per_entry": ai["paths"] / max(ai["entries_active"], 1)}
+                runs.append(min(65535, max(1, -(-ai["paths"] // max(ai["entries_active"], 1)))))
             gpu = []
             for _ in range(6):                                            # (the first subframe of a fresh table reads it cold)
                 tr.baked_render_subframe(bake, 1, out=False, direct=True)
@@ -67,7 +88,8 @@ if __name__ == "__main__":
             tr.reset()
             tr.baked_render_accumulate(bake, 1, S, direct=True)
             got = tr.mean()[..., :3].astype(np.float64)
-            print(json.dumps({"route": "ct_bake_traced", **common, "grid": [g, g, g, a.azimuths, a.cosines], "samples": samples,
+            print(json.dumps({"route": "ct_bake_traced_adaptive" if samples is None else "ct_bake_traced", **common, **extra,
+                              "grid": [g, g, g, a.azimuths, a.cosines], "samples": ti["samples"],
                               "nodes": sp["nodes"], "active_nodes": sp["active_nodes"], "active_share": sp["active_nodes"] / sp["nodes"],
                               "table_bytes": st["table_bytes"], "paths": ti["paths"], "trace_ms": ti["trace_ms"], "fold_ms": ti["fold_ms"],
                               "bake_wall_ms": wall, "paths_per_second": ti["paths"] / ti["trace_ms"] * 1e3 if ti["trace_ms"] > 0 else None,

@@ -275,6 +275,13 @@ class CloudTracer:
         check(self.L.ct_point_radiance_launch(self.h, _p(tasks), len(tasks), first_frame_id, launches), self.h)
         return tasks
 
+    def radiance_collector(self, positions, directions, **params):
+        """A collector.DeviceRadianceCollector on this handle (ct_collector_*): RadianceCollector's loop over these tasks with
+        replication, merge, stopping rule and re-packing on the device.  params: batch_start_id, max_thread_count,
+        launches_per_update, rel_tol, abs_tol, zero_samples (default: the reference's)."""
+        from .collector import DeviceRadianceCollector
+        return DeviceRadianceCollector(self, positions, directions, **params)
+
     def generate_scatter_samples(self, count: int, batch_seed: int = 0):
         """generatePoints + firstScatterPosition: -> (positions [count,3], view directions [count,3])."""
         pos = np.empty((count, 3), np.float32)

@@ -6,20 +6,25 @@ The device part -- estimateEmission over (point, direction) tasks with per-task 
 libcloudtrace.so; what stays here is exactly what the reference does on the host: task
 replication (scheduleTasks, :176-192), merging the replicas with PointRadianceTask::operator+=
 (PointRadianceTask.h:56-68), the convergence rule (:112-118) and re-packing the unconverged tasks.
+DeviceRadianceCollector is the same collector with that host part on the device too (ct_collector_*),
+and collect_reference the host loop as a function, which the device collector is held to bit for bit.
 LMDB is not available on the target image, so records go to a flat file that
 tools/flat_to_lmdb.py turns into the reference's LMDB layout where the `lmdb` module exists.
 """
 from __future__ import annotations
 
+import ctypes as C
 import struct
 from typing import Callable
 
 import numpy as np
 
+from . import _lib
 from .cloudtrace import POINT_TASK_DTYPE, make_point_tasks
 
 MAX_THREAD_COUNT = 10 * 2048          # RadianceCollector.cpp:17
 LAUNCHES_PER_UPDATE = 100             # :88
+REL_TOL, ABS_TOL, ZERO_SAMPLES = 2e-2, 1e-4, 100000   # :112-118
 FLT_EPSILON = np.float32(1.1920929e-07)
 f32 = np.float32
 
@@ -53,12 +58,14 @@ class RadianceCollector:
 
     def __init__(self, launch: Callable[[np.ndarray, int, int], np.ndarray], positions, directions,
                  batch_start_id: int = 0, max_thread_count: int = MAX_THREAD_COUNT,
-                 launches_per_update: int = LAUNCHES_PER_UPDATE):
+                 launches_per_update: int = LAUNCHES_PER_UPDATE, rel_tol: float = REL_TOL, abs_tol: float = ABS_TOL,
+                 zero_samples: int = ZERO_SAMPLES):
         self.launch = launch
         self.batch_start_id = batch_start_id
         self.batch_size = len(positions)
         self.max_thread_count = max_thread_count
         self.launches_per_update = launches_per_update
+        self.rel_tol, self.abs_tol, self.zero_samples = f32(rel_tol), f32(abs_tol), int(zero_samples)
         self.converged_tasks: list[np.void] = []
         self.all_pixels_converged = False
         self.frame_id = 0
@@ -114,8 +121,8 @@ class RadianceCollector:
             N = cnt.astype(f32)
             absolute = (f32(1.96) * np.sqrt(var / N)) / np.sqrt(N)                    # PointRadianceTask.h:31-36
             relative = absolute / (rad + FLT_EPSILON)                                 # :23-26
-        converged = (relative < f32(2e-2)) | (absolute < f32(1e-4))                   # :112-114
-        converged = np.where(rad < FLT_EPSILON, cnt > 100000, converged)              # :115-118
+        converged = (relative < self.rel_tol) | (absolute < self.abs_tol)             # :112-114 (2e-2f, 1e-4f)
+        converged = np.where(rad < FLT_EPSILON, cnt > self.zero_samples, converged)   # :115-118 (100000)
         self.converged_tasks.extend(rep[converged])
         self.all_pixels_converged = self.get_converged_count() == self.batch_size
         if not self.all_pixels_converged:
@@ -128,6 +135,104 @@ class RadianceCollector:
         for t in sorted(self.converged_tasks, key=lambda t: int(t["id"])):
             out.append((self.batch_start_id + int(t["id"]), encode_result(float(t["radiance"]), True)))
         return out
+
+
+def collect_reference(launch, positions, directions, *, max_thread_count: int = MAX_THREAD_COUNT,
+                      launches_per_update: int = LAUNCHES_PER_UPDATE, rel_tol: float = REL_TOL, abs_tol: float = ABS_TOL,
+                      zero_samples: int = ZERO_SAMPLES, updates: int):
+    """RadianceCollector's loop for at most `updates` updates, as a function: what a CtCollector (include/cloudtrace.h, "the
+    radiance collector on the device") is held to, bit for bit.  -> (tasks, converged_update, history): the B tasks in id order
+    (POINT_TASK_DTYPE; a task that is still live carries the statistics merged so far), the update each task converged in
+    (uint32, 0 = live), and per update that ran (n live tasks, r replicas per task, tasks converged in it)."""
+    c = RadianceCollector(launch, positions, directions, max_thread_count=max_thread_count, launches_per_update=launches_per_update,
+                          rel_tol=rel_tol, abs_tol=abs_tol, zero_samples=zero_samples)
+    converged_update = np.zeros(c.batch_size, np.uint32)
+    history = []
+    for u in range(1, updates + 1):
+        if c.is_completed():
+            break
+        n, r, before = c.get_remaining_count(), c.task_repeat_count, c.get_converged_count()
+        c.update()
+        for t in c.converged_tasks[before:]:
+            converged_update[int(t["id"])] = u
+        history.append((n, r, c.get_converged_count() - before))
+    tasks = make_point_tasks(positions, directions)
+    for t in c.converged_tasks:
+        tasks[int(t["id"])] = t
+    if not c.is_completed():
+        live = c.tasks_buffer[0::c.task_repeat_count]           # slot 0 of every task: the merged statistics
+        tasks[live["id"]] = live
+    return tasks, converged_update, history
+
+
+class DeviceRadianceCollector:
+    """RadianceCollector's surface on a CtCollector (ct_collector_*): replication, merge, rule and re-packing run on the
+    device, and `update` reads back one count.  `tracer`: the CloudTracer whose handle the collector runs on."""
+
+    def __init__(self, tracer, positions, directions, batch_start_id: int = 0, max_thread_count: int = MAX_THREAD_COUNT,
+                 launches_per_update: int = LAUNCHES_PER_UPDATE, rel_tol: float = REL_TOL, abs_tol: float = ABS_TOL,
+                 zero_samples: int = ZERO_SAMPLES):
+        self.tracer, self.L = tracer, tracer.L
+        self.batch_start_id = batch_start_id
+        pos = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+        if len(pos) != len(d):
+            raise ValueError("positions and directions differ in length")
+        self.batch_size = len(pos)
+        desc = _lib.CtCollectorDesc(_lib.CT_ABI_VERSION, max_thread_count, launches_per_update, zero_samples, rel_tol, abs_tol)
+        c = C.c_void_p()
+        _lib.check(self.L.ct_collector_create(tracer.h, C.byref(desc), pos.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p),
+                                              len(pos), C.byref(c)), tracer.h)
+        self.c = c
+
+    def close(self):
+        if getattr(self, "c", None):
+            self.L.ct_collector_destroy(self.c)
+            self.c = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self) -> dict:
+        """ct_collector_info: batch, remaining, converged, updates, frame_id, repeat_count, threads, completed, paths and the
+        GPU milliseconds of the last update call (trace_ms, fold_ms, test_ms)."""
+        i = _lib.CtCollectorInfo()
+        _lib.check(self.L.ct_collector_info(self.c, C.byref(i)), self.tracer.h)
+        return i.as_dict()
+
+    def update(self, updates: int = 1) -> None:
+        _lib.check(self.L.ct_collector_update(self.tracer.h, self.c, updates), self.tracer.h)
+
+    def is_completed(self) -> bool:
+        return bool(self.info()["completed"])
+
+    def get_converged_count(self) -> int:
+        return self.info()["converged"]
+
+    def get_remaining_count(self) -> int:
+        return self.info()["remaining"]
+
+    def tasks(self):
+        """ct_collector_download -> (the B tasks in id order, POINT_TASK_DTYPE; converged_update, uint32, 0 = live)."""
+        tasks = np.zeros(self.batch_size, POINT_TASK_DTYPE)
+        converged_update = np.zeros(self.batch_size, np.uint32)
+        _lib.check(self.L.ct_collector_download(self.c, tasks.ctypes.data_as(C.c_void_p), converged_update.ctypes.data_as(C.c_void_p),
+                                                     self.batch_size), self.tracer.h)
+        return tasks, converged_update
+
+    def results(self) -> list[tuple[int, bytes]]:
+        """(record id, serialized Persistance::Result) of the converged tasks, sorted by task id."""
+        tasks, converged_update = self.tasks()
+        return [(self.batch_start_id + int(t["id"]), encode_result(float(t["radiance"]), True)) for t, u in zip(tasks, converged_update) if u]
 
 
 # ---- proto3 wire format of the three messages the path exchanges (TR/Protocols/*.proto) --------

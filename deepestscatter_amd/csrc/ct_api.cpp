@@ -2468,6 +2468,264 @@ extern "C" int ct_point_radiance_launch(CtHandle h, CtPointRadianceTask *tasks_h
         });
 }
 
+// ---- the radiance collector on the device (ct_collector_*): RadianceCollector's loop over point_launch -------------------
+// Kernels: ct_collect.hip.  All device memory is allocated in ct_collector_create; an update reads back one word, the number of
+// survivors, behind the wait point_launch makes anyway.
+struct CtCollector_ {
+    CtHandle h = nullptr;
+    int device = 0;
+    CtCollectorDesc d{};
+    uint32_t batch = 0;
+    uint32_t n_live = 0;      // tasks in live[cur]
+    int cur = 0;
+    uint32_t count = 0;       // experiments every live task holds
+    uint32_t updates = 0, frame_id = 0;
+    uint64_t paths = 0, epoch = 0;
+    double trace_ms = 0, fold_ms = 0, test_ms = 0;
+    DevBuf<float> positions, directions, mean, m2;
+    DevBuf<uint32_t> counts, converged_update, live[2], waves;
+    Event ev[5];              // around the rays kernel, the fold kernel, and behind the compaction
+};
+
+static_assert(sizeof(CtCollectorDesc) == 24 && sizeof(CtCollectorInfo) == 64, "include/cloudtrace.h states these sizes");
+
+extern "C" int ct_collector_create(CtHandle h, const CtCollectorDesc *d, const float *positions_host, const float *directions_host,
+                                   uint32_t count, CtCollector *out)
+{
+    if (!h) {
+        return fail(nullptr, CT_E_INVAL, "null handle");
+    }
+    if (out) {
+        *out = nullptr;
+    }
+    if (!d || !positions_host || !directions_host || !out) {
+        return fail(h, CT_E_INVAL, "ct_collector_create: need a description, positions, directions and out");
+    }
+    if (d->abi_version != CT_ABI_VERSION) {
+        return fail(h, CT_E_INVAL, "ct_collector_create: abi_version %u, this library is %u", d->abi_version, CT_ABI_VERSION);
+    }
+    if (d->max_thread_count == 0u || d->max_thread_count > (1u << 24)) {
+        return fail(h, CT_E_INVAL, "ct_collector_create: max_thread_count %u, a collector has 1 .. 2^24 threads", d->max_thread_count);
+    }
+    if (d->launches_per_update == 0u || d->launches_per_update > 0xffffu) {
+        return fail(h, CT_E_INVAL, "ct_collector_create: launches_per_update %u, an update traces 1 .. 65535 frames", d->launches_per_update);
+    }
+    if (!std::isfinite(d->rel_tol) || !std::isfinite(d->abs_tol) || d->rel_tol < 0.f || d->abs_tol < 0.f) {
+        return fail(h, CT_E_INVAL, "ct_collector_create: rel_tol and abs_tol must be finite and not negative");
+    }
+    if (count == 0u || count > d->max_thread_count) {
+        return fail(h, CT_E_INVAL, "ct_collector_create: %u tasks for %u threads; need 1 .. max_thread_count", count, d->max_thread_count);
+    }
+    if ((uint64_t)((d->max_thread_count + 63u) & ~63u) * d->launches_per_update > 0xffffffffull) {
+        return fail(h, CT_E_INVAL, "ct_collector_create: too many task-launches for one update");
+    }
+    for (uint32_t i = 0; i < count; i++) {   // (ct_point_radiance_launch's test of its tasks)
+        const float *dir = directions_host + 3 * (size_t)i, *o = positions_host + 3 * (size_t)i;
+        if (!(std::isfinite(dir[0]) && std::isfinite(dir[1]) && std::isfinite(dir[2])) || (dir[0] == 0.f && dir[1] == 0.f && dir[2] == 0.f)) {
+            return fail(h, CT_E_INVAL, "ct_collector_create: task %u has a zero or non-finite direction", i);
+        }
+        if (!(std::isfinite(o[0]) && std::isfinite(o[1]) && std::isfinite(o[2]))) {
+            return fail(h, CT_E_INVAL, "ct_collector_create: task %u has a non-finite position", i);
+        }
+    }
+    if (h->scene.flags & CT_FLAG_SIMPLE_KERNEL) {
+        return fail(h, CT_E_INVAL, "ct_collector_create: point radiance tasks need the persistent kernel");
+    }
+    NEED(h);
+    CtCollector_ *c = new CtCollector_();
+    c->h = h;
+    c->device = h->device;
+    c->d = *d;
+    c->batch = c->n_live = count;
+    c->epoch = h->light_epoch;
+    const size_t B = count;
+    if (c->positions.alloc(3 * B) != hipSuccess || c->directions.alloc(3 * B) != hipSuccess || c->mean.alloc(B) != hipSuccess ||
+        c->m2.alloc(B) != hipSuccess || c->counts.alloc(B) != hipSuccess || c->converged_update.alloc(B) != hipSuccess ||
+        c->live[0].alloc(B) != hipSuccess || c->live[1].alloc(B) != hipSuccess || c->waves.alloc(B + 1u) != hipSuccess) {
+        (void)hipGetLastError();
+        delete c;
+        return fail(h, CT_E_NOMEM, "ct_collector_create: no device memory for the state and live lists of %u tasks", count);
+    }
+    std::vector<uint32_t> ids(B);
+    for (uint32_t i = 0; i < count; i++) {
+        ids[i] = i;
+    }
+    auto fill = [&]() -> int {
+        for (Event &e : c->ev) {
+            HIPCHK(h, e.create());
+        }
+        HIPCHK(h, hipMemcpyAsync(c->positions, positions_host, 3 * B * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(c->directions, directions_host, 3 * B * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(c->live[0], ids.data(), B * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemsetAsync(c->mean, 0, B * sizeof(float), h->stream));
+        HIPCHK(h, hipMemsetAsync(c->m2, 0, B * sizeof(float), h->stream));
+        HIPCHK(h, hipMemsetAsync(c->counts, 0, B * sizeof(uint32_t), h->stream));
+        HIPCHK(h, hipMemsetAsync(c->converged_update, 0, B * sizeof(uint32_t), h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return CT_OK;
+    };
+    const int rc = fill();
+    if (rc != CT_OK) {
+        hipStreamSynchronize(h->stream);
+        delete c;
+        return rc;
+    }
+    *out = c;
+    return CT_OK;
+}
+
+extern "C" int ct_collector_update(CtHandle h, CtCollector c, uint32_t updates)
+{
+    if (!h) {
+        return fail(nullptr, CT_E_INVAL, "null handle");
+    }
+    if (!c) {
+        return fail(h, CT_E_INVAL, "ct_collector_update: null collector");
+    }
+    if (c->h != h) {
+        return fail(h, CT_E_INVAL, "ct_collector_update: the collector belongs to another handle");
+    }
+    if (updates == 0u) {
+        return fail(h, CT_E_INVAL, "ct_collector_update: need at least one update");
+    }
+    NEED(h);
+    if (c->epoch != h->light_epoch) {
+        return fail(h, CT_E_STATE, "ct_collector_update: the handle's light has changed since ct_collector_create");
+    }
+    c->trace_ms = c->fold_ms = c->test_ms = 0;
+    CtHandle_::PointBuffers &pt = h->pt;
+    const uint32_t L = c->d.launches_per_update;
+    for (uint32_t k = 0; k < updates && c->n_live != 0u; k++) {
+        const uint32_t n = c->n_live, r = c->d.max_thread_count / n, threads = n * r;
+        if ((uint64_t)c->count + (uint64_t)r * L > 0xffffffffull) {
+            return fail(h, CT_E_STATE, "ct_collector_update: update %u would carry the tasks' experiment count (%u) beyond 2^32 - 1", c->updates + 1u, c->count);
+        }
+        if ((uint64_t)c->frame_id + L > 0xffffffffull) {
+            return fail(h, CT_E_STATE, "ct_collector_update: the frame ids of update %u would wrap", c->updates + 1u);
+        }
+        CollectArgs a{};
+        a.live = c->live[c->cur];
+        a.positions = c->positions;
+        a.directions = c->directions;
+        a.mean = c->mean;
+        a.m2 = c->m2;
+        a.counts = c->counts;
+        a.converged_update = c->converged_update;
+        a.n = n;
+        a.r = r;
+        a.n_pad = (threads + 63u) & ~63u;
+        a.rel_tol = c->d.rel_tol;
+        a.abs_tol = c->d.abs_tol;
+        a.zero_samples = c->d.zero_samples;
+        uint32_t survivors = 0;
+        const double render_before = h->render_ms;
+        const int rc = point_launch(
+            h, h->dev, threads, c->frame_id + 1u, L,
+            [&]() -> int {
+                HIPCHK(h, hipEventRecord(c->ev[0], h->stream));
+                HIPCHK(h, launch_collect_rays(h->dev, a, pt.primary, pt.pixels, h->stream));
+                HIPCHK(h, hipEventRecord(c->ev[1], h->stream));
+                return CT_OK;
+            },
+            [&]() -> int {
+                HIPCHK(h, hipEventRecord(c->ev[2], h->stream));
+                HIPCHK(h, launch_collect_fold(a, pt.frames, a.n_pad, L, c->count, c->updates + 1u, c->waves, h->stream));
+                HIPCHK(h, hipEventRecord(c->ev[3], h->stream));
+                HIPCHK(h, launch_collect_compact(a, c->waves, c->live[c->cur ^ 1], h->stream));
+                HIPCHK(h, hipEventRecord(c->ev[4], h->stream));
+                HIPCHK(h, hipMemcpyAsync(&survivors, c->waves + collect_groups(a), sizeof survivors, hipMemcpyDeviceToHost, h->stream));
+                return CT_OK;
+            });
+        if (rc != CT_OK) {
+            return rc;
+        }
+        float ms0 = 0, ms1 = 0, ms2 = 0;
+        HIPCHK(h, hipEventElapsedTime(&ms0, c->ev[0], c->ev[1]));
+        HIPCHK(h, hipEventElapsedTime(&ms1, c->ev[2], c->ev[3]));
+        HIPCHK(h, hipEventElapsedTime(&ms2, c->ev[3], c->ev[4]));
+        c->trace_ms += h->render_ms - render_before;
+        c->fold_ms += (double)ms0 + (double)ms1;
+        c->test_ms += (double)ms2;
+        if (survivors > n) {
+            return fail(h, CT_E_HIP, "internal: an update of %u live tasks counted %u survivors", n, survivors);
+        }
+        c->count += r * L;
+        c->frame_id += L;
+        c->updates += 1u;
+        c->paths += (uint64_t)threads * L;
+        c->cur ^= 1;
+        c->n_live = survivors;
+    }
+    return CT_OK;
+}
+
+extern "C" int ct_collector_info(CtCollector c, CtCollectorInfo *out)
+{
+    if (!c || !out) {
+        return fail(c ? c->h : nullptr, CT_E_INVAL, "ct_collector_info: need a collector and out");
+    }
+    *out = CtCollectorInfo{};
+    out->batch = c->batch;
+    out->remaining = c->n_live;
+    out->converged = c->batch - c->n_live;
+    out->updates = c->updates;
+    out->frame_id = c->frame_id;
+    out->repeat_count = c->n_live ? c->d.max_thread_count / c->n_live : 0u;
+    out->threads = c->n_live * out->repeat_count;
+    out->completed = c->n_live == 0u ? 1u : 0u;
+    out->paths = c->paths;
+    out->trace_ms = c->trace_ms;
+    out->fold_ms = c->fold_ms;
+    out->test_ms = c->test_ms;
+    return CT_OK;
+}
+
+extern "C" int ct_collector_download(CtCollector c, CtPointRadianceTask *tasks_host_out, uint32_t *converged_update_host_out, uint32_t count)
+{
+    if (!c) {
+        return fail(nullptr, CT_E_INVAL, "ct_collector_download: null collector");
+    }
+    CtHandle h = c->h;
+    if (!tasks_host_out || count != c->batch) {
+        return fail(h, CT_E_INVAL, "ct_collector_download: need an array of exactly %u tasks", c->batch);
+    }
+    NEED(h);
+    const size_t B = c->batch;
+    std::vector<float> pos(3 * B), dir(3 * B), mean(B), m2(B);
+    std::vector<uint32_t> counts(B), conv(B);
+    HIPCHK(h, hipMemcpy(pos.data(), c->positions, 3 * B * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(dir.data(), c->directions, 3 * B * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(mean.data(), c->mean, B * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(m2.data(), c->m2, B * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(counts.data(), c->counts, B * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(conv.data(), c->converged_update, B * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < B; i++) {
+        CtPointRadianceTask &t = tasks_host_out[i];
+        t.id = (int32_t)i;
+        t.experimentCount = counts[i];
+        t.radiance = mean[i];
+        t.runningVariance = m2[i];
+        for (int k = 0; k < 3; k++) {
+            t.position[k] = pos[3 * i + k];
+            t.direction[k] = dir[3 * i + k];
+        }
+        if (converged_update_host_out) {
+            converged_update_host_out[i] = conv[i];
+        }
+    }
+    return CT_OK;
+}
+
+extern "C" int ct_collector_destroy(CtCollector c)
+{
+    if (!c) {
+        return CT_OK;
+    }
+    hipSetDevice(c->device);
+    delete c;
+    return CT_OK;
+}
+
 extern "C" int ct_generate_scatter_samples(CtHandle h, uint32_t count, uint32_t batch_seed,
                                            float *positions_host_out, float *directions_host_out)
 {

@@ -275,7 +275,7 @@ int fail(CtHandle h, int code, const char *fmt, ...);
 int flush(CtHandle h);            // waits for the batches in flight
 void discard_ahead(CtHandle h);
 int enqueue_convergence_test(CtHandle h, uint32_t subframes);
-// ct_point_radiance_launch's launch half (ct_api.cpp), shared with the traced bake: job list, queue split, grid share, the
+// ct_point_radiance_launch's launch half (ct_api.cpp), shared with the traced bake and the device collector: job list, queue split, grid share, the
 // estimator launch with `sc`, its time and the host counters.  rays / fold enqueue what fills h->pt.primary and h->pt.pixels
 // before the estimator and what reads h->pt.frames[f * pad64(count) + i] behind it; the stream is idle when it returns.
 int point_launch(CtHandle h, const DevScene &sc, uint32_t count, uint32_t first_frame_id, uint32_t launches,

@@ -330,6 +330,33 @@ hipError_t launch_bake_adaptive_fold(const BakeTraceArgs &a, const float4 *frame
 hipError_t launch_bake_adaptive_scan(uint32_t *waves, uint32_t n_live, hipStream_t stream);
 hipError_t launch_bake_adaptive_compact(const BakeTraceArgs &a, const BakeAdaptiveState &st, const uint32_t *live_in, uint32_t n_live,
                                         const uint32_t *waves, uint32_t *live_out, hipStream_t stream);
+// ct_collector_* (ct_collect.hip): an update of the device collector of include/cloudtrace.h, "the radiance collector on the
+// device".  live: the n live task ids, ascending; r = T / n replicas per task, thread i = t * r + j replica j of live[t].
+// positions / directions / mean / m2 / counts / converged_update are indexed by task id.  launch_collect_rays writes
+// primary[2 i], primary[2 i + 1] and pixels[i] for i < n_pad (a multiple of 64, >= n * r) as launch_point_rays does for a task
+// array with those replicas.  launch_collect_fold folds frames[f * stride + i].x, f < launches, per replica (replica 0 from the
+// stored state, which holds `done` experiments; the others from zero), merges replicas 1 .. r - 1 into replica 0 in that order
+// with PointRadianceTask::operator+=, stores the triple, tests the rule, stores `update` into converged_update of a task that
+// passes, and writes waves[g] = the survivors of group g: a group is one task (r > 1: one wave per task) or 64 consecutive
+// tasks of the list (r == 1: one lane per task).  launch_collect_compact: the scan of those counts, the number of survivors
+// behind them in waves[groups], and the survivors' ids into live_out in live's order.
+struct CollectArgs {
+    const uint32_t *live;
+    const float *positions, *directions;
+    float *mean, *m2;
+    uint32_t *counts, *converged_update;
+    uint32_t n, r, n_pad;
+    float rel_tol, abs_tol;
+    uint32_t zero_samples;
+};
+inline uint32_t collect_groups(const CollectArgs &a)
+{
+    return a.r > 1u ? a.n : (a.n + 63u) / 64u;
+}
+hipError_t launch_collect_rays(const DevScene &sc, const CollectArgs &a, float4 *primary, uint32_t *pixels, hipStream_t stream);
+hipError_t launch_collect_fold(const CollectArgs &a, const float4 *frames, uint32_t stride, uint32_t launches, uint32_t done,
+                               uint32_t update, uint32_t *waves, hipStream_t stream);
+hipError_t launch_collect_compact(const CollectArgs &a, uint32_t *waves, uint32_t *live_out, hipStream_t stream);
 // Density pyramid (Resources::generateMipmaps) and the descriptor gather.
 constexpr int kMaxMipLevels = 16;
 struct MipPyramid {

@@ -1,6 +1,7 @@
 // Collectors.h -- host-side mirror of the reference's dataset collectors on top of the libcloudtrace C ABI:
 //   ScatterSampleCollector     src/Scene/ScatterSampleCollector.{h,cpp}   -> ct_generate_scatter_samples
 //   RadianceCollector          src/Scene/RadianceCollector.{h,cpp}        -> ct_point_radiance_launch
+//   DeviceRadianceCollector    the same, its host arithmetic included      -> ct_collector_*
 //   DisneyDescriptorCollector  src/Scene/DisneyDescriptorCollector.{h,cpp} -> ct_collect_descriptors
 //   Dataset                    src/Util/Dataset/Dataset.{h,cpp}            (named tables, int32 keys, proto3 values)
 // Same class names, the same init / update / isCompleted life cycle (SceneItem), the same batch numbering
@@ -223,7 +224,15 @@ namespace DeepestScatter
         bool done = false;
     };
 
-    class RadianceCollector : public SceneItem                                 // RadianceCollector.cpp:15-192
+    // what the reference's "MS/Render" lines add up to (RadianceCollector.cpp:87-97), for `cloudtrace collect`'s timing lines
+    struct RadianceTimings
+    {
+        double totalRenderMs = 0;
+        uint64_t totalExperiments = 0;
+        uint32_t updates = 0;
+    };
+
+    class RadianceCollector : public SceneItem, public RadianceTimings         // RadianceCollector.cpp:15-192
     {
     public:
         static constexpr uint32_t MAX_THREAD_COUNT = 10 * 2048;               // :17
@@ -278,11 +287,6 @@ namespace DeepestScatter
         }
 
         bool isCompleted() override { return allPixelsConverged; }
-
-        // what the reference's "MS/Render" lines add up to (RadianceCollector.cpp:87-97), for `cloudtrace collect --timings`
-        double totalRenderMs = 0;
-        uint64_t totalExperiments = 0;
-        uint32_t updates = 0;
 
         // PointRadianceTask.h:23-36 (95 % confidence), :56-68 (operator+=: the M2 values are added as they are)
         static float absoluteConfidenceInterval(const CtPointRadianceTask& t)
@@ -339,6 +343,71 @@ namespace DeepestScatter
         std::vector<CtPointRadianceTask> tasksBuffer, convergedTasks;
         uint32_t taskRepeatCount = 0, threadsCount = 0, frameId = 0;
         bool allPixelsConverged = false;
+    };
+
+    // RadianceCollector on a CtCollector (ct_collector_*, include/cloudtrace.h "the radiance collector on the device"): the
+    // same life cycle, log lines and records, with replication, merge, rule and re-packing behind the C ABI -- an update is one
+    // call that reads back one count.  `cloudtrace collect --device-collector`.
+    class DeviceRadianceCollector : public SceneItem, public RadianceTimings
+    {
+    public:
+        DeviceRadianceCollector(std::shared_ptr<Context> context, std::shared_ptr<Dataset> dataset, BatchSettings settings)
+            : context(std::move(context)), dataset(std::move(dataset)), settings(settings) {}
+        DeviceRadianceCollector(const DeviceRadianceCollector&) = delete;
+        DeviceRadianceCollector& operator=(const DeviceRadianceCollector&) = delete;
+        ~DeviceRadianceCollector() override { ct_collector_destroy(collector); }   // (before the handle: `context` is a member)
+
+        void init() override
+        {
+            std::vector<float> positions(3 * (size_t)settings.batchSize), directions(3 * (size_t)settings.batchSize);
+            for (uint32_t i = 0; i < settings.batchSize; i++)
+                Persistance::readScatterSample(dataset->getRecord("ScatterSample", (int32_t)(settings.batchStartId + i)), &positions[3 * (size_t)i],
+                                               &directions[3 * (size_t)i]);
+            const CtCollectorDesc desc{ CT_ABI_VERSION, RadianceCollector::MAX_THREAD_COUNT, 100, 100000, 2e-2f, 1e-4f };
+            Context::check(ct_collector_create(context->handle, &desc, positions.data(), directions.data(), settings.batchSize, &collector),
+                           context->handle, "ct_collector_create");
+            Context::check(ct_collector_info(collector, &info), context->handle, "ct_collector_info");
+        }
+
+        int32_t getConvergedCount() const { return (int32_t)info.converged; }
+        int32_t getRemainingCount() const { return (int32_t)info.remaining; }
+
+        void update() override
+        {
+            if (info.completed) return;
+            const uint32_t remaining = info.remaining;
+            const auto t1 = std::chrono::steady_clock::now();
+            Context::check(ct_collector_update(context->handle, collector, 1), context->handle, "ct_collector_update");
+            const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+            totalRenderMs += ms;
+            totalExperiments += (uint64_t)info.threads * 100u;
+            updates++;
+            Context::check(ct_collector_info(collector, &info), context->handle, "ct_collector_info");
+            CollectorLog::out() << "MS/Render: " << ms << " " << remaining << std::endl;
+            CollectorLog::out() << "converged: " << getConvergedCount() << " of " << settings.batchSize << std::endl;
+            if (info.completed) recordToDataset();
+        }
+
+        bool isCompleted() override { return info.completed != 0; }
+
+    private:
+        void recordToDataset()
+        {
+            std::vector<CtPointRadianceTask> tasks(settings.batchSize);
+            Context::check(ct_collector_download(collector, tasks.data(), nullptr, settings.batchSize), context->handle, "ct_collector_download");
+            CollectorLog::out() << "Serializing emissions..." << std::endl;
+            std::vector<std::string> results(settings.batchSize);
+            for (uint32_t i = 0; i < settings.batchSize; i++) results[i] = Persistance::result(tasks[i].radiance, true);
+            CollectorLog::out() << "Writing emissions..." << std::endl;
+            dataset->batchAppend("Result", results, (int32_t)settings.batchStartId);
+            CollectorLog::out() << "Finished writing emissions." << std::endl;
+        }
+
+        std::shared_ptr<Context> context;
+        std::shared_ptr<Dataset> dataset;
+        BatchSettings settings;
+        CtCollector collector = nullptr;
+        CtCollectorInfo info{};
     };
 
     class DisneyDescriptorCollector : public SceneItem                         // DisneyDescriptorCollector.cpp:15-100

@@ -25,9 +25,10 @@
 //                               1e-4; a zero entry after ZERO experiments, default 100000), at most MAX each (ct_bake_traced_adaptive)
 //   <cloud> = file.vdb | procedural:<N>[:<seed>] | file.f32grid
 //
-//   cloudtrace collect <cloud>|@list.txt [--scene-id I] [--scenes N] [--jobs K] [--gpus ..] [--batch 2048] [--light L] [--size-m M] [--out DIR] [--data DIR] [--estimator ..] [--tex-fixed8]
+//   cloudtrace collect <cloud>|@list.txt [--scene-id I] [--scenes N] [--jobs K] [--gpus ..] [--batch 2048] [--light L] [--size-m M] [--out DIR] [--data DIR] [--estimator ..] [--tex-fixed8] [--device-collector]
 //              = Tasks::collect (Tasks.cpp:114-155) for one SceneSetup: the ScatterSample, Result and DisneyDescriptor
-//              collectors one after the other over records [I * batch, (I + 1) * batch), written as flat tables
+//              collectors one after the other over records [I * batch, (I + 1) * batch), written as flat tables;
+//              --device-collector: the radiance collector's loop runs on the device (ct_collector_*), same tables
 #include <atomic>
 #include <chrono>
 #include <cstring>
@@ -94,6 +95,7 @@ namespace
         uint32_t batch = 2048;                                                    // Tasks.cpp:137
         uint32_t scenes = 1;                                                      // --scenes N: N setups of the same cloud (lights cycle), ids from --scene-id
         uint32_t jobs = 1;                                                        // --jobs K: scene setups in flight at once
+        bool deviceCollector = false;                                             // --device-collector: DeviceRadianceCollector in place of RadianceCollector
     };
 
     // One line of a scene-setup list = what a Persistance::SceneSetup record carries (cloud path, cloud size, light direction).
@@ -140,10 +142,23 @@ namespace
         auto dataset = std::make_shared<Dataset>();
         dataset->batchAppend("SceneSetup", { Persistance::sceneSetup(setup.cloud, setup.sizeM, scene.light.direction.data()) }, sceneId);
         const BatchSettings settings((uint32_t)sceneId * opt.batch, opt.batch);
-        auto radiance = std::make_shared<RadianceCollector>(context, dataset, settings);
+        std::shared_ptr<SceneItem> radianceItem;
+        const RadianceTimings* radiance = nullptr;
+        if (opt.deviceCollector)
+        {
+            auto c = std::make_shared<DeviceRadianceCollector>(context, dataset, settings);
+            radianceItem = c;
+            radiance = c.get();
+        }
+        else
+        {
+            auto c = std::make_shared<RadianceCollector>(context, dataset, settings);
+            radianceItem = c;
+            radiance = c.get();
+        }
         std::vector<std::shared_ptr<SceneItem>> collectors{
             std::make_shared<ScatterSampleCollector>(context, dataset, settings, sceneId),
-            radiance,
+            radianceItem,
             std::make_shared<DisneyDescriptorCollector>(context, dataset, settings) };
         double phaseMs[3] = { 0, 0, 0 };
         for (size_t k = 0; k < collectors.size(); k++)                            // each is its own task in the reference: init, update until completed
@@ -340,6 +355,7 @@ int main(int argc, char* argv[])
             else if (a == "--batch") opt.batch = (uint32_t)std::stoul(next());
             else if (a == "--scenes") opt.scenes = (uint32_t)std::stoul(next());
             else if (a == "--jobs") opt.jobs = (uint32_t)std::stoul(next());
+            else if (a == "--device-collector") opt.deviceCollector = true;
             else if (a == "--gpus")
             {
                 // "N" = devices 0..N-1; "a,b,c" = that list (a device may repeat: a rehearsal of N shards on fewer GPUs)

@@ -337,6 +337,91 @@ typedef struct CtPointRadianceTask {
 CT_API int ct_point_radiance_launch(CtHandle h, CtPointRadianceTask *tasks_host, uint32_t count,
                                     uint32_t first_frame_id, uint32_t launches);
 
+/* ---- the radiance collector on the device: RadianceCollector's loop behind the C ABI ------------------
+ *
+ * RadianceCollector::update (RadianceCollector.cpp:73-141) around ct_point_radiance_launch is, on the host: replicate the
+ * unconverged tasks over max_thread_count threads (scheduleTasks, :176-192), launch, merge the replicas of every task with
+ * PointRadianceTask::operator+= (:104-108), test the rule (:112-118), re-pack.  A CtCollector does all of that on the device; the
+ * host reads one word per update, the number of tasks that go on.
+ *
+ * Tasks have ids 0 .. B-1 (B = count); task i has position positions_host[3 i ..] and direction directions_host[3 i ..].
+ * State per id: mean, m2, count and converged_update, all 0 at create.  The live list is 0 .. B-1, ascending; frame_id is 0.
+ *
+ * Update u (u = 1, 2, ..) with n live tasks, in list order, T = max_thread_count, L = launches_per_update:
+ *     r = T / n (integer division), threads = n r; thread i = t r + j is replica j of the t-th live task.
+ *     Thread i traces frames frame_id + 1 .. frame_id + L: exactly the paths ct_point_radiance_launch traces on this handle for
+ *     a task at array index i -- seed tea<4>(i * 4096, frame) -- with the handle's mode, estimator and CT_FLAG_TEX_FIXED8.
+ *     Replica 0 folds its L results onto the task's (mean, m2, count), replicas j >= 1 fold theirs from (0, 0, 0), all with
+ *     PointRadianceTask::addExperimentResult's arithmetic as ct_point_radiance_launch folds (float32, no contraction):
+ *         N = (float)count, w = (float)(1.0 / (double)N), new_mean = mean + (x - mean) * w, m2 += (x - mean) * (x - new_mean)
+ *     Merge: replicas j = 1 .. r-1 into replica 0, in that order, with PointRadianceTask::operator+= (PointRadianceTask.h:56-68):
+ *         w = ((float)n1 * 1.0f) / (float)(n0 + n1)    (IEEE division, the integer sum converted once)
+ *         mean = mean + (o.mean - mean) * w            (no contraction)
+ *         m2 = m2 + o.m2                               (the reference omits the between-means term, and so does this)
+ *         count = n0 + n1
+ *     Test, on the merged triple, in float32 with IEEE division and square root:
+ *         absolute = (1.96f * sqrt(m2 / N)) / sqrt(N),  relative = absolute / (mean + FLT_EPSILON),
+ *         converged = relative < rel_tol || absolute < abs_tol;  if mean < FLT_EPSILON: converged = count > zero_samples
+ *     (a NaN compares false).  A converged task stores converged_update[id] = u and leaves the list; the survivors keep their
+ *     order.  frame_id += L.  The collector is completed when the list is empty.
+ *
+ * All live tasks hold the same count c at all times.  An update that would carry it beyond 2^32 - 1 (c + r L), or whose frame ids
+ * would wrap, is CT_E_STATE, answered before anything of that update runs; the updates of the call before it stand.
+ *
+ * ct_collector_update runs up to `updates` updates and stops when the collector is completed; on a completed collector it is
+ * CT_OK and launches nothing.  After k updates the state is, bit for bit, what RadianceCollector's loop with the same constants
+ * leaves after k update()s over ct_point_radiance_launch on the same handle: the statistics of every task, the set converged in
+ * every update, r and frame_id -- whatever the split of k over calls.
+ *
+ * ct_collector_download writes the B tasks in id order: id, experimentCount, radiance, runningVariance, and position and
+ * direction as given; a live task carries its current merged statistics and converged_update 0.  count must equal B.
+ * converged_update_host_out may be NULL.
+ *
+ * CtCounters, CtFetchCounters, ct_kernel_time and the armed invariants (CT_DEBUG_INVARIANTS) see the paths exactly as
+ * ct_point_radiance_launch's of the same threads.  Mean, M2, frame, subframe count, samples rendered ahead and the pose's pixel
+ * list are not touched.
+ *
+ * Everything the collector owns -- positions, directions, the three state arrays, converged_update, two live lists of B words,
+ * the wave counts -- is allocated in ct_collector_create: CT_E_NOMEM there leaves the handle as it was.  The estimator's
+ * scratch is the handle's, grown as for ct_point_radiance_launch.
+ *
+ * CT_E_INVAL, before anything changes: a NULL argument (a NULL handle is answered without a device); a wrong abi_version; T, L
+ * or a tolerance out of range; count == 0 or count > T; T rounded up to 64, times L, > 2^32 - 1; a zero or non-finite direction
+ * or a non-finite position (the message names the task, as ct_point_radiance_launch's); a CT_FLAG_SIMPLE_KERNEL handle; a
+ * collector of another handle; updates == 0; a wrong count in ct_collector_download.
+ * CT_E_STATE: an update after ct_set_light changed the handle's light (ct_collector_download still works); the two overflows.
+ * ct_collector_destroy(NULL) is a no-op; destroy a collector before its handle. */
+typedef struct CtCollectorDesc {
+    uint32_t abi_version;         /* CT_ABI_VERSION */
+    uint32_t max_thread_count;    /* T: 1 .. 2^24 (reference: 20480, RadianceCollector.cpp:17) */
+    uint32_t launches_per_update; /* L: 1 .. 65535 (reference: 100, :88) */
+    uint32_t zero_samples;        /* a task whose mean is < FLT_EPSILON stops once count > zero_samples (reference: 100000) */
+    float    rel_tol;             /* finite, >= 0 (reference: 2e-2f) */
+    float    abs_tol;             /* finite, >= 0 (reference: 1e-4f) */
+} CtCollectorDesc;                /* 24 bytes */
+typedef struct CtCollector_ *CtCollector;
+typedef struct CtCollectorInfo {
+    uint32_t batch;               /* B */
+    uint32_t remaining;           /* live tasks */
+    uint32_t converged;           /* B - remaining */
+    uint32_t updates;             /* updates run since create */
+    uint32_t frame_id;
+    uint32_t repeat_count;        /* r of the next update, 0 when completed */
+    uint32_t threads;             /* remaining * repeat_count */
+    uint32_t completed;           /* 1: the live list is empty */
+    uint64_t paths;               /* estimator paths since create */
+    double   trace_ms;            /* GPU time of the last ct_collector_update call: the estimator launches, */
+    double   fold_ms;             /* the rays and fold-and-merge kernels (the fold evaluates the rule), */
+    double   test_ms;             /* the scans and the compacting writes */
+} CtCollectorInfo;                /* 64 bytes; frame_id at 16, paths at 32, trace_ms at 40 */
+
+CT_API int ct_collector_create(CtHandle h, const CtCollectorDesc *d, const float *positions_host, const float *directions_host,
+                               uint32_t count, CtCollector *out);
+CT_API int ct_collector_update(CtHandle h, CtCollector c, uint32_t updates);
+CT_API int ct_collector_info(CtCollector c, CtCollectorInfo *out);
+CT_API int ct_collector_download(CtCollector c, CtPointRadianceTask *tasks_host_out, uint32_t *converged_update_host_out, uint32_t count);
+CT_API int ct_collector_destroy(CtCollector c);
+
 /* generatePoints (src/CUDA/pointGeneratorCamera.cu:20-42) + firstScatterPosition
  * (cloudFirstScatterMaterial.cu:8-29), launched over `count` threads by ScatterSampleCollector::collect
  * (ScatterSampleCollector.cpp:36-62): thread i draws a direction uniformly on the sphere and a point on

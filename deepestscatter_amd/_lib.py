@@ -27,7 +27,7 @@ CT_NET_ADD_SINGLE_SCATTER = 0x100            # CtNetworkRender.transform, bit 8:
 # every symbol include/cloudtrace.h declares (tests check the library exports all of them)
 EXPORTS = [
     "ct_create", "ct_destroy", "ct_last_error", "ct_set_stream", "ct_set_camera", "ct_set_light", "ct_render_subframe",
-    "ct_accumulate", "ct_render_accumulate", "ct_render_accumulate_async", "ct_synchronize", "ct_copy_to_device_async", "ct_point_radiance_launch", "ct_collector_create", "ct_collector_update", "ct_collector_info", "ct_collector_download", "ct_collector_destroy", "ct_generate_scatter_samples", "ct_collect_descriptors", "ct_descriptor_frame", "ct_debug_descriptor_frame_time", "ct_network_create", "ct_network_destroy", "ct_network_eval", "ct_debug_network_time", "ct_network_render_subframe", "ct_network_render_accumulate", "ct_network_render_shard_subframe", "ct_network_render_shard_accumulate", "ct_debug_network_scratch", "ct_debug_network_aux", "ct_debug_network_render_time", "ct_network_bake", "ct_bake_update", "ct_bake_destroy", "ct_bake_info", "ct_bake_probes", "ct_bake_download", "ct_debug_bake_lookup", "ct_network_bake_sparse", "ct_bake_sparse_info", "ct_bake_mask", "ct_network_bake_compact", "ct_bake_storage_info", "ct_bake_slots", "ct_bake_download_stored", "ct_bake_traced", "ct_bake_trace_more", "ct_bake_retrace", "ct_bake_trace_info", "ct_bake_directions", "ct_bake_traced_adaptive", "ct_bake_trace_adaptive_more", "ct_bake_retrace_adaptive", "ct_bake_adaptive_info", "ct_bake_download_counts", "ct_debug_bake_mask", "ct_baked_render_subframe", "ct_baked_render_accumulate", "ct_baked_render_shard_subframe", "ct_baked_render_shard_accumulate", "ct_debug_baked_render_time", "ct_reset", "ct_tonemap", "ct_tonemap_async", "ct_set_render_ahead", "ct_rendered_subframes", "ct_set_stop_when_converged", "ct_converged_at", "ct_is_converged", "ct_tonemap_buffer", "ct_is_converged_buffers", "ct_download", "ct_upload",
+    "ct_accumulate", "ct_render_accumulate", "ct_render_accumulate_async", "ct_synchronize", "ct_copy_to_device_async", "ct_point_radiance_launch", "ct_collector_create", "ct_collector_update", "ct_collector_info", "ct_collector_download", "ct_collector_destroy", "ct_adaptive_frame_create", "ct_adaptive_frame_update", "ct_adaptive_frame_raise_cap", "ct_adaptive_frame_info", "ct_adaptive_frame_download", "ct_adaptive_frame_device_ptr", "ct_adaptive_frame_destroy", "ct_generate_scatter_samples", "ct_collect_descriptors", "ct_descriptor_frame", "ct_debug_descriptor_frame_time", "ct_network_create", "ct_network_destroy", "ct_network_eval", "ct_debug_network_time", "ct_network_render_subframe", "ct_network_render_accumulate", "ct_network_render_shard_subframe", "ct_network_render_shard_accumulate", "ct_debug_network_scratch", "ct_debug_network_aux", "ct_debug_network_render_time", "ct_network_bake", "ct_bake_update", "ct_bake_destroy", "ct_bake_info", "ct_bake_probes", "ct_bake_download", "ct_debug_bake_lookup", "ct_network_bake_sparse", "ct_bake_sparse_info", "ct_bake_mask", "ct_network_bake_compact", "ct_bake_storage_info", "ct_bake_slots", "ct_bake_download_stored", "ct_bake_traced", "ct_bake_trace_more", "ct_bake_retrace", "ct_bake_trace_info", "ct_bake_directions", "ct_bake_traced_adaptive", "ct_bake_trace_adaptive_more", "ct_bake_retrace_adaptive", "ct_bake_adaptive_info", "ct_bake_download_counts", "ct_debug_bake_mask", "ct_baked_render_subframe", "ct_baked_render_accumulate", "ct_baked_render_shard_subframe", "ct_baked_render_shard_accumulate", "ct_debug_baked_render_time", "ct_reset", "ct_tonemap", "ct_tonemap_async", "ct_set_render_ahead", "ct_rendered_subframes", "ct_set_stop_when_converged", "ct_converged_at", "ct_is_converged", "ct_tonemap_buffer", "ct_is_converged_buffers", "ct_download", "ct_upload",
     "ct_buffer_bytes", "ct_copy_to_device", "ct_device_ptr", "ct_subframes", "ct_set_subframes", "ct_counters", "ct_kernel_time",
     "ct_debug_cdf_inversion", "ct_debug_math_selftest", "ct_debug_math_eval", "ct_debug_fetch_probe", "ct_debug_fetch_probe_ws", "ct_debug_track_lines", "ct_debug_touched_lines", "ct_debug_stats", "ct_debug_stats_ex", "ct_debug_suspended", "ct_debug_timeline", "ct_debug_invariants", "ct_debug_pixel_classes", "ct_debug_pixel_class_plane", "ct_debug_memory", "ct_debug_delta_grid", "ct_debug_march_meta", "ct_debug_layout", "ct_fetch_counters", "ct_calculate_camera_variables", "ct_quantize_volume", "ct_load_vdb", "ct_generate_mipmaps",
     "ct_tile_owner", "ct_shard_tiles", "ct_debug_allocations", "ct_make_procedural_cloud",
@@ -224,6 +224,46 @@ class CtCollectorInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+CT_ADAPTIVE_MEAN, CT_ADAPTIVE_M2, CT_ADAPTIVE_COUNTS = 0, 1, 2   # ct_adaptive_frame_download / _device_ptr
+
+
+class CtAdaptiveFrameDesc(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_uint32),
+        ("round_samples", C.c_uint32),
+        ("min_samples", C.c_uint32),
+        ("max_samples", C.c_uint32),
+        ("rel_tol", C.c_float),
+        ("abs_tol", C.c_float),
+        ("chunk_pixels", C.c_uint32),
+        ("pass_subframes", C.c_uint32),
+    ]
+
+
+class CtAdaptiveFrameInfo(C.Structure):
+    _fields_ = [
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("round_samples", C.c_uint32),
+        ("min_samples", C.c_uint32),
+        ("max_samples", C.c_uint32),
+        ("rounds", C.c_uint32),
+        ("rel_tol", C.c_float),
+        ("abs_tol", C.c_float),
+        ("pixels", C.c_uint64),
+        ("live", C.c_uint64),
+        ("converged", C.c_uint64),
+        ("capped", C.c_uint64),
+        ("paths", C.c_uint64),
+        ("trace_ms", C.c_double),
+        ("fold_ms", C.c_double),
+        ("test_ms", C.c_double),
+    ]
+
+    def as_dict(self) -> dict:
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class CtFetchCounters(C.Structure):
     _fields_ = [("density_fetches", C.c_uint64), ("inscatter_fetches", C.c_uint64)]
 
@@ -270,6 +310,13 @@ def load():
         "ct_collector_info": (i32, [vp, C.POINTER(CtCollectorInfo)]),
         "ct_collector_download": (i32, [vp, vp, vp, u32]),
         "ct_collector_destroy": (i32, [vp]),
+        "ct_adaptive_frame_create": (i32, [vp, C.POINTER(CtAdaptiveFrameDesc), C.POINTER(vp)]),
+        "ct_adaptive_frame_update": (i32, [vp, u32]),
+        "ct_adaptive_frame_raise_cap": (i32, [vp, u32]),
+        "ct_adaptive_frame_info": (i32, [vp, C.POINTER(CtAdaptiveFrameInfo)]),
+        "ct_adaptive_frame_download": (i32, [vp, u32, vp, C.c_size_t]),
+        "ct_adaptive_frame_device_ptr": (i32, [vp, u32, C.POINTER(vp)]),
+        "ct_adaptive_frame_destroy": (i32, [vp]),
         "ct_generate_scatter_samples": (i32, [vp, u32, u32, vp, vp]),
         "ct_collect_descriptors": (i32, [vp, vp, vp, u32, vp]),
         "ct_descriptor_frame": (i32, [vp, u32, vp, u32, vp, vp, vp, vp, C.POINTER(u32)]),

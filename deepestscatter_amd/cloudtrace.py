@@ -282,6 +282,15 @@ class CloudTracer:
         from .collector import DeviceRadianceCollector
         return DeviceRadianceCollector(self, positions, directions, **params)
 
+    def adaptive_frame(self, round_samples: int = 10, max_samples: int = 1000, min_samples: int = 100, rel_tol: float = 2e-2,
+                       abs_tol: float = 1e-2, chunk_pixels: int = 0, pass_subframes: int = 0):
+        """An adaptive.AdaptiveFrame on this handle (ct_adaptive_frame_*): the image of the current pose and light in rounds of
+        `round_samples` subframes that go only to the pixels which have not yet passed Camera::isConverged's test (tested from
+        `min_samples` on), at most `max_samples` per pixel.  The handle's own image is not touched.  Defaults: the reference's
+        cadence, minimum and tolerances."""
+        from .adaptive import AdaptiveFrame
+        return AdaptiveFrame(self, round_samples, max_samples, min_samples, rel_tol, abs_tol, chunk_pixels, pass_subframes)
+
     def generate_scatter_samples(self, count: int, batch_seed: int = 0):
         """generatePoints + firstScatterPosition: -> (positions [count,3], view directions [count,3])."""
         pos = np.empty((count, 3), np.float32)

@@ -2726,6 +2726,345 @@ extern "C" int ct_collector_destroy(CtCollector c)
     return CT_OK;
 }
 
+// ---- the adaptive frame (ct_adaptive_frame_*): the progressive image in rounds that go to the unconverged pixels only ----------
+// Kernels: ct_adaptive.hip.  The scheme is bake_trace_adaptive's (ct_neural.cpp): a round's live list goes through point_launch in
+// chunks of whole groups of 64 and passes, the fold of the round's last pass counts the survivors per wave, a scan and a ranked
+// write compact them into the other list, and the host reads one word per round behind the wait point_launch makes anyway.
+struct CtAdaptiveFrame_ {
+    CtHandle h = nullptr;
+    int device = 0;
+    CtAdaptiveFrameDesc d{};
+    uint32_t width = 0, height = 0, pixels = 0;
+    uint32_t n_live = 0;      // entries of the live list: live[cur], or every pixel of the frame while !listed
+    uint32_t n_capped = 0;    // n_live == 0: the entries of live[cur] that failed the rule at the cap
+    bool listed = false;
+    int cur = 0;
+    uint32_t count = 0;       // samples every live (or capped) pixel holds
+    uint32_t cap = 0, rounds = 0;
+    uint64_t paths = 0, epoch = 0;
+    float pose[12] = {};
+    double trace_ms = 0, fold_ms = 0, test_ms = 0;
+    DevBuf<float4> mean, m2;
+    DevBuf<uint32_t> counts, live[2], waves;
+    Event ev[6];              // around the rays kernel, the fold kernel and the compaction
+};
+
+static_assert(sizeof(CtAdaptiveFrameDesc) == 32 && sizeof(CtAdaptiveFrameInfo) == 96, "include/cloudtrace.h states these sizes");
+
+// The twelve floats ct_set_camera sets.
+static void adaptive_pose(const DevScene &d, float out[12])
+{
+    const float v[12] = { d.ex, d.ey, d.ez, d.ux, d.uy, d.uz, d.vx, d.vy, d.vz, d.wx, d.wy, d.wz };
+    memcpy(out, v, sizeof v);
+}
+
+// Is the frame still the image of the handle's pose and light?  (update and raise_cap; sets the handle's error)
+static int adaptive_current(CtAdaptiveFrame f, const char *who)
+{
+    CtHandle h = f->h;
+    if (f->epoch != h->light_epoch) {
+        return fail(h, CT_E_STATE, "%s: the handle's light has changed since ct_adaptive_frame_create", who);
+    }
+    float pose[12];
+    adaptive_pose(h->dev, pose);
+    if (memcmp(pose, f->pose, sizeof pose) != 0) {
+        return fail(h, CT_E_STATE, "%s: the handle's camera pose has changed since ct_adaptive_frame_create", who);
+    }
+    return CT_OK;
+}
+
+extern "C" int ct_adaptive_frame_create(CtHandle h, const CtAdaptiveFrameDesc *d, CtAdaptiveFrame *out)
+{
+    const char *const who = "ct_adaptive_frame_create";
+    if (!h) {
+        return fail(nullptr, CT_E_INVAL, "null handle");
+    }
+    if (out) {
+        *out = nullptr;
+    }
+    if (!d || !out) {
+        return fail(h, CT_E_INVAL, "%s: need a description and out", who);
+    }
+    if (d->abi_version != CT_ABI_VERSION) {
+        return fail(h, CT_E_INVAL, "%s: abi_version %u, this library is %u", who, d->abi_version, CT_ABI_VERSION);
+    }
+    const uint32_t R = d->round_samples;
+    if (R == 0u || R > 0xffffu) {
+        return fail(h, CT_E_INVAL, "%s: round_samples %u, a round traces 1 .. 65535 subframes per pixel", who, R);
+    }
+    if (d->max_samples == 0u || d->max_samples % R != 0u || d->max_samples > (1u << 24)) {
+        return fail(h, CT_E_INVAL, "%s: max_samples %u; a multiple of round_samples (%u), at most 2^24", who, d->max_samples, R);
+    }
+    if (d->min_samples == 0u || d->min_samples % R != 0u || d->min_samples > d->max_samples) {
+        return fail(h, CT_E_INVAL, "%s: min_samples %u; a multiple of round_samples (%u), at most max_samples (%u)", who, d->min_samples, R,
+                    d->max_samples);
+    }
+    if (!std::isfinite(d->rel_tol) || !std::isfinite(d->abs_tol) || d->rel_tol < 0.f || d->abs_tol < 0.f) {
+        return fail(h, CT_E_INVAL, "%s: rel_tol and abs_tol must be finite and not negative", who);
+    }
+    if (d->chunk_pixels % 64u != 0u) {
+        return fail(h, CT_E_INVAL, "%s: chunk_pixels %u; 0 or a multiple of 64", who, d->chunk_pixels);
+    }
+    if (d->pass_subframes > R) {
+        return fail(h, CT_E_INVAL, "%s: pass_subframes %u; 0 or 1 .. round_samples (%u)", who, d->pass_subframes, R);
+    }
+    if (h->scene.flags & CT_FLAG_SIMPLE_KERNEL) {
+        return fail(h, CT_E_INVAL, "%s: an adaptive frame needs the persistent kernel", who);
+    }
+    if (h->scene.shard_count > 1u) {
+        return fail(h, CT_E_INVAL, "%s: this handle renders shard %u of %u; an adaptive frame is a whole frame", who, h->scene.shard_index,
+                    h->scene.shard_count);
+    }
+    NEED(h);
+    CtAdaptiveFrame_ *f = new CtAdaptiveFrame_();
+    f->h = h;
+    f->device = h->device;
+    f->d = *d;
+    f->width = h->scene.width;
+    f->height = h->scene.height;
+    f->pixels = f->n_live = f->width * f->height;   // (at most 12288 x 4096: ct_create)
+    f->cap = d->max_samples;
+    f->epoch = h->light_epoch;
+    adaptive_pose(h->dev, f->pose);
+    const size_t P = f->pixels;
+    if (f->mean.alloc(P) != hipSuccess || f->m2.alloc(P) != hipSuccess || f->counts.alloc(P) != hipSuccess || f->live[0].alloc(P) != hipSuccess ||
+        f->live[1].alloc(P) != hipSuccess || f->waves.alloc((P + 63u) / 64u + 1u) != hipSuccess) {
+        (void)hipGetLastError();
+        delete f;
+        return fail(h, CT_E_NOMEM, "%s: no device memory for the state and live lists of %zu pixels", who, P);
+    }
+    auto fill = [&]() -> int {
+        for (Event &e : f->ev) {
+            HIPCHK(h, e.create());
+        }
+        HIPCHK(h, hipMemsetAsync(f->mean, 0, P * sizeof(float4), h->stream));
+        HIPCHK(h, hipMemsetAsync(f->m2, 0, P * sizeof(float4), h->stream));
+        HIPCHK(h, hipMemsetAsync(f->counts, 0, P * sizeof(uint32_t), h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return CT_OK;
+    };
+    const int rc = fill();
+    if (rc != CT_OK) {
+        hipStreamSynchronize(h->stream);
+        delete f;
+        return rc;
+    }
+    *out = f;
+    return CT_OK;
+}
+
+extern "C" int ct_adaptive_frame_update(CtAdaptiveFrame f, uint32_t rounds)
+{
+    const char *const who = "ct_adaptive_frame_update";
+    if (!f) {
+        return fail(nullptr, CT_E_INVAL, "%s: null frame", who);
+    }
+    CtHandle h = f->h;
+    NEED(h);
+    const int current = adaptive_current(f, who);
+    if (current != CT_OK) {
+        return current;
+    }
+    f->trace_ms = f->fold_ms = f->test_ms = 0;
+    CtHandle_::PointBuffers &pt = h->pt;
+    const uint32_t R = f->d.round_samples;
+    const double render_before = h->render_ms;
+    for (uint32_t k = 0; (rounds == 0u || k < rounds) && f->n_live != 0u; k++) {
+        const uint32_t c = f->count, L = f->n_live;
+        uint32_t chunk = std::min(L, f->d.chunk_pixels ? f->d.chunk_pixels : 1u << 20);
+        if (chunk >= 64u) {
+            chunk &= ~63u;   // (whole groups of 64: a chunk's waves are the live list's)
+        }
+        const uint32_t *live_in = f->listed ? (const uint32_t *)f->live[f->cur] : nullptr;
+        uint32_t *live_out = f->live[f->listed ? f->cur ^ 1 : 0];
+        uint32_t survivors = 0;
+        AdaptiveArgs a{};
+        a.live = live_in;
+        a.mean = f->mean;
+        a.m2 = f->m2;
+        a.counts = f->counts;
+        a.rel_tol = f->d.rel_tol;
+        a.abs_tol = f->d.abs_tol;
+        a.min_samples = f->d.min_samples;
+        for (uint32_t first = 0; first < L; first += chunk) {
+            a.first = first;
+            a.n = std::min(chunk, L - first);
+            a.n_pad = (a.n + 63u) & ~63u;
+            // at most 2^24 results per launch: 256 MiB of pt.frames, which point_launch keeps from call to call
+            const uint32_t fit = std::max(1u, (1u << 24) / a.n_pad);
+            const uint32_t per_pass = std::min(f->d.pass_subframes ? f->d.pass_subframes : R, std::min(fit, 0xffffu));
+            for (uint32_t at = 0; at < R; at += per_pass) {
+                const uint32_t passes = std::min(per_pass, R - at), done = c + at;
+                const bool last_pass = at + passes == R, last = last_pass && first + a.n == L;
+                AdaptiveArgs whole = a;   // the compaction's view: the whole list
+                whole.first = 0;
+                whole.n = L;
+                whole.n_pad = (L + 63u) & ~63u;
+                const int rc = point_launch(
+                    h, h->dev, a.n, done + 1u, passes,
+                    [&]() -> int {
+                        HIPCHK(h, hipEventRecord(f->ev[0], h->stream));
+                        HIPCHK(h, launch_adaptive_rays(h->dev, a, pt.primary, pt.pixels, h->stream));
+                        HIPCHK(h, hipEventRecord(f->ev[1], h->stream));
+                        return CT_OK;
+                    },
+                    [&]() -> int {
+                        HIPCHK(h, hipEventRecord(f->ev[2], h->stream));
+                        HIPCHK(h, launch_adaptive_fold(a, pt.frames, a.n_pad, passes, done, last_pass ? (uint32_t *)f->waves : nullptr, h->stream));
+                        HIPCHK(h, hipEventRecord(f->ev[3], h->stream));
+                        if (last) {
+                            HIPCHK(h, hipEventRecord(f->ev[4], h->stream));
+                            HIPCHK(h, launch_adaptive_compact(whole, f->waves, live_out, h->stream));
+                            HIPCHK(h, hipEventRecord(f->ev[5], h->stream));
+                            HIPCHK(h, hipMemcpyAsync(&survivors, f->waves + (L + 63u) / 64u, sizeof survivors, hipMemcpyDeviceToHost, h->stream));
+                        }
+                        return CT_OK;
+                    });
+                if (rc != CT_OK) {
+                    return rc;
+                }
+                float ms0 = 0, ms1 = 0, ms2 = 0;
+                HIPCHK(h, hipEventElapsedTime(&ms0, f->ev[0], f->ev[1]));
+                HIPCHK(h, hipEventElapsedTime(&ms1, f->ev[2], f->ev[3]));
+                if (last) {
+                    HIPCHK(h, hipEventElapsedTime(&ms2, f->ev[4], f->ev[5]));
+                }
+                f->fold_ms += (double)ms0 + (double)ms1;
+                f->test_ms += (double)ms2;
+                f->trace_ms = h->render_ms - render_before;
+            }
+        }
+        if (survivors > L) {
+            return fail(h, CT_E_HIP, "internal: a round of %u live pixels counted %u survivors", L, survivors);
+        }
+        f->count = c + R;
+        f->rounds += 1u;
+        f->paths += (uint64_t)L * R;
+        f->cur = f->listed ? f->cur ^ 1 : 0;
+        f->listed = true;
+        if (f->count >= f->cap) {   // the survivors fail the rule at the cap: kept for ct_adaptive_frame_raise_cap
+            f->n_capped = survivors;
+            f->n_live = 0;
+        } else {
+            f->n_live = survivors;
+        }
+    }
+    return CT_OK;
+}
+
+extern "C" int ct_adaptive_frame_raise_cap(CtAdaptiveFrame f, uint32_t max_samples)
+{
+    const char *const who = "ct_adaptive_frame_raise_cap";
+    if (!f) {
+        return fail(nullptr, CT_E_INVAL, "%s: null frame", who);
+    }
+    CtHandle h = f->h;
+    if (max_samples <= f->cap || max_samples % f->d.round_samples != 0u || max_samples > (1u << 24)) {
+        return fail(h, CT_E_INVAL, "%s: max_samples %u; a multiple of round_samples (%u) above the cap (%u), at most 2^24", who, max_samples,
+                    f->d.round_samples, f->cap);
+    }
+    NEED(h);
+    const int current = adaptive_current(f, who);
+    if (current != CT_OK) {
+        return current;
+    }
+    f->cap = max_samples;
+    if (f->n_capped != 0u) {   // (they all hold the old cap's count, as f->count says)
+        f->n_live = f->n_capped;
+        f->n_capped = 0;
+    }
+    return CT_OK;
+}
+
+extern "C" int ct_adaptive_frame_info(CtAdaptiveFrame f, CtAdaptiveFrameInfo *out)
+{
+    if (!f || !out) {
+        return fail(f ? f->h : nullptr, CT_E_INVAL, "ct_adaptive_frame_info: need a frame and out");
+    }
+    *out = CtAdaptiveFrameInfo{};
+    out->width = f->width;
+    out->height = f->height;
+    out->round_samples = f->d.round_samples;
+    out->min_samples = f->d.min_samples;
+    out->max_samples = f->cap;
+    out->rounds = f->rounds;
+    out->rel_tol = f->d.rel_tol;
+    out->abs_tol = f->d.abs_tol;
+    out->pixels = f->pixels;
+    out->live = f->n_live;
+    out->capped = f->n_capped;
+    out->converged = (uint64_t)f->pixels - f->n_live - f->n_capped;
+    out->paths = f->paths;
+    out->trace_ms = f->trace_ms;
+    out->fold_ms = f->fold_ms;
+    out->test_ms = f->test_ms;
+    return CT_OK;
+}
+
+// The device array `which` names and its size; nullptr: no such array.
+static void *adaptive_array(CtAdaptiveFrame f, uint32_t which, size_t &bytes)
+{
+    switch (which) {
+    case CT_ADAPTIVE_MEAN:
+        bytes = (size_t)f->pixels * sizeof(float4);
+        return (float4 *)f->mean;
+    case CT_ADAPTIVE_M2:
+        bytes = (size_t)f->pixels * sizeof(float4);
+        return (float4 *)f->m2;
+    case CT_ADAPTIVE_COUNTS:
+        bytes = (size_t)f->pixels * sizeof(uint32_t);
+        return (uint32_t *)f->counts;
+    default:
+        bytes = 0;
+        return nullptr;
+    }
+}
+
+extern "C" int ct_adaptive_frame_download(CtAdaptiveFrame f, uint32_t which, void *host, size_t bytes)
+{
+    const char *const who = "ct_adaptive_frame_download";
+    if (!f) {
+        return fail(nullptr, CT_E_INVAL, "%s: null frame", who);
+    }
+    CtHandle h = f->h;
+    size_t need = 0;
+    void *src = adaptive_array(f, which, need);
+    if (!src) {
+        return fail(h, CT_E_INVAL, "%s: which = %u; CT_ADAPTIVE_MEAN, CT_ADAPTIVE_M2 or CT_ADAPTIVE_COUNTS", who, which);
+    }
+    if (!host || bytes != need) {
+        return fail(h, CT_E_INVAL, "%s: need a host array of exactly %zu bytes", who, need);
+    }
+    NEED(h);
+    HIPCHK(h, hipMemcpy(host, src, need, hipMemcpyDeviceToHost));
+    return CT_OK;
+}
+
+extern "C" int ct_adaptive_frame_device_ptr(CtAdaptiveFrame f, uint32_t which, void **out)
+{
+    const char *const who = "ct_adaptive_frame_device_ptr";
+    if (!f) {
+        return fail(nullptr, CT_E_INVAL, "%s: null frame", who);
+    }
+    size_t bytes = 0;
+    void *p = adaptive_array(f, which, bytes);
+    if (!p || !out) {
+        return fail(f->h, CT_E_INVAL, "%s: need CT_ADAPTIVE_MEAN, CT_ADAPTIVE_M2 or CT_ADAPTIVE_COUNTS and out", who);
+    }
+    *out = p;
+    return CT_OK;
+}
+
+extern "C" int ct_adaptive_frame_destroy(CtAdaptiveFrame f)
+{
+    if (!f) {
+        return CT_OK;
+    }
+    hipSetDevice(f->device);
+    delete f;
+    return CT_OK;
+}
+
 extern "C" int ct_generate_scatter_samples(CtHandle h, uint32_t count, uint32_t batch_seed,
                                            float *positions_host_out, float *directions_host_out)
 {

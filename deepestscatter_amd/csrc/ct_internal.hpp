@@ -357,6 +357,27 @@ hipError_t launch_collect_rays(const DevScene &sc, const CollectArgs &a, float4 
 hipError_t launch_collect_fold(const CollectArgs &a, const float4 *frames, uint32_t stride, uint32_t launches, uint32_t done,
                                uint32_t update, uint32_t *waves, hipStream_t stream);
 hipError_t launch_collect_compact(const CollectArgs &a, uint32_t *waves, uint32_t *live_out, hipStream_t stream);
+// ct_adaptive_frame_* (ct_adaptive.hip): a round of the adaptive frame of include/cloudtrace.h, "the adaptive frame".  A chunk is
+// the entries [first, first + n) of the live list: pixels live[first + i] (y * width + x, ascending), or first + i while the list
+// is the whole frame (live == nullptr).  mean / m2 / counts are indexed by pixel.  launch_adaptive_rays writes primary[2 i],
+// primary[2 i + 1] and pixels[i] for i < n_pad (a multiple of 64, >= n) as launch_primary_rays forms the pixel's ray, with the
+// entry as the estimator's pixel.  launch_adaptive_fold folds frames[f * stride + i], f < passes, as subframes done + 1 .. onto
+// the pixel's mean and m2 with welford() and stores count = done + passes; with `waves` (the round's last pass; first is a
+// multiple of 64 then) wave (first + i) / 64 of the list also writes how many of its lanes go on: count < min_samples, or the
+// rule fails.  launch_adaptive_compact (first == 0, n == the list's length): the scan of the n / 64 (rounded up) wave counts, the
+// number of survivors behind them, and the survivors' pixels into live_out in the list's order.
+struct AdaptiveArgs {
+    const uint32_t *live;
+    uint32_t first, n, n_pad;
+    float4 *mean, *m2;
+    uint32_t *counts;
+    float rel_tol, abs_tol;
+    uint32_t min_samples;
+};
+hipError_t launch_adaptive_rays(const DevScene &sc, const AdaptiveArgs &a, float4 *primary, uint32_t *pixels, hipStream_t stream);
+hipError_t launch_adaptive_fold(const AdaptiveArgs &a, const float4 *frames, uint32_t stride, uint32_t passes, uint32_t done,
+                                uint32_t *waves, hipStream_t stream);
+hipError_t launch_adaptive_compact(const AdaptiveArgs &a, uint32_t *waves, uint32_t *live_out, hipStream_t stream);
 // Density pyramid (Resources::generateMipmaps) and the descriptor gather.
 constexpr int kMaxMipLevels = 16;
 struct MipPyramid {

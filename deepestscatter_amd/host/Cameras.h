@@ -69,6 +69,8 @@ namespace DeepestScatter
             context->renderAccumulate(first, count, enqueue);
         }
 
+        void publishCamera() { applyCamera(); }   // for a caller that renders on the handle itself (Camera's adaptive frame)
+
         uint32_t subframeId = 0;        // context["subframeId"], set by Camera::render (Camera.cpp:191-192)
         int estimator = CT_EST_MARCH;   // CT_EST_DELTA: Woodcock tracking instead of the reference's fixed-step march
         inline static const std::string NAME = "PT";
@@ -330,6 +332,13 @@ namespace DeepestScatter
 
         bool deviceStops = false;       // the convergence test runs on the device (ct_set_stop_when_converged)
 
+        // --adaptive: the image is an adaptive frame (ct_adaptive_frame_*) -- rounds that go only to the pixels which still fail
+        // the test -- run to its end in one update; the handle's own image is not rendered.  adaptiveCountsFile: where the
+        // per-pixel sample counts go, raw little-endian uint32, row-major (empty: nowhere).
+        bool adaptive = false;
+        CtAdaptiveFrameDesc adaptiveDesc{ CT_ABI_VERSION, 10, 100, 1000, 2e-2f, 1e-2f, 0, 0 };
+        std::filesystem::path adaptiveCountsFile;
+
         uint32_t getSubframeId() const { return subframeId; }
         const std::vector<uint8_t>& getScreen() const { return screen; }
 
@@ -337,6 +346,12 @@ namespace DeepestScatter
         {
             std::vector<float> mean((size_t)width * height * 4);
             context->downloadMean(mean.data(), mean.size() * sizeof(float));
+            writeImage(mean);
+        }
+
+    private:
+        void writeImage(const std::vector<float>& mean) const
+        {
             std::cout << mean[((size_t)width * height / 2 + width / 2) * 4] << std::endl;   // :163
             if (outputFile.extension() == ".pfm")
             {
@@ -352,7 +367,6 @@ namespace DeepestScatter
             }
         }
 
-    private:
         void updatePosition()                                                    // :100-134 (arcball path is UI-only)
         {
             const float hfov = 30.0f;
@@ -367,8 +381,44 @@ namespace DeepestScatter
             }
         }
 
+        // The whole job of --adaptive: create, update until nothing is live, save mean and counts, one line of totals.
+        void renderAdaptive()
+        {
+            auto* pt = dynamic_cast<PathTracingRenderer*>(renderer.get());
+            if (pt == nullptr || context->group || context->handle == nullptr) throw std::runtime_error("--adaptive renders with the path tracer on one GPU");
+            pt->publishCamera();
+            CtHandle h = context->handle;
+            CtAdaptiveFrame frame = nullptr;
+            Context::check(ct_adaptive_frame_create(h, &adaptiveDesc, &frame), h, "ct_adaptive_frame_create");
+            std::vector<float> mean((size_t)width * height * 4);
+            std::vector<uint32_t> counts((size_t)width * height);
+            CtAdaptiveFrameInfo info{};
+            int rc = ct_adaptive_frame_update(frame, 0);
+            if (rc == CT_OK) rc = ct_adaptive_frame_info(frame, &info);
+            if (rc == CT_OK) rc = ct_adaptive_frame_download(frame, CT_ADAPTIVE_MEAN, mean.data(), mean.size() * sizeof(float));
+            if (rc == CT_OK) rc = ct_adaptive_frame_download(frame, CT_ADAPTIVE_COUNTS, counts.data(), counts.size() * sizeof(uint32_t));
+            if (rc != CT_OK)
+            {
+                const std::string why = ct_last_error(h);   // (before the frame goes: destroy leaves the text alone, but keep it anyway)
+                ct_adaptive_frame_destroy(frame);
+                throw std::runtime_error("ct_adaptive_frame: " + why);
+            }
+            ct_adaptive_frame_destroy(frame);
+            std::cout << "adaptive {\"rounds\": " << info.rounds << ", \"pixels\": " << info.pixels << ", \"converged\": " << info.converged
+                      << ", \"capped\": " << info.capped << ", \"paths\": " << info.paths << "}" << std::endl;
+            writeImage(mean);
+            if (!adaptiveCountsFile.empty())
+            {
+                std::ofstream f(adaptiveCountsFile, std::ios::binary);
+                f.write(reinterpret_cast<const char*>(counts.data()), (std::streamsize)(counts.size() * sizeof(uint32_t)));
+                if (!f) throw std::runtime_error("cannot write " + adaptiveCountsFile.string());
+            }
+            completed = true;
+        }
+
         void render()                                                            // :177-230
         {
+            if (adaptive) { renderAdaptive(); return; }
             // headless: nobody looks at the screen between saves, so batches are enqueued (a launch hands its
             // unfinished paths to the next one instead of ending with a tail) and the buffers are only read --
             // tonemap, save -- every 40 subframes, where the reference saves (:211-214).  The reference tests convergence

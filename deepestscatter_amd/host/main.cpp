@@ -23,6 +23,12 @@
 //              [--bake-adaptive R,MAX[,REL[,ABS[,ZERO]]]]   in place of --bake-samples: trace in rounds of R experiments, only the entries
 //                               that fail the stopping rule (95 % interval below REL of the mean, default 0.02, or below ABS, default
 //                               1e-4; a zero entry after ZERO experiments, default 100000), at most MAX each (ct_bake_traced_adaptive)
+//              [--adaptive R,MAX[,MIN[,REL[,ABS]]] [--adaptive-counts FILE]]   the image as an adaptive frame (ct_adaptive_frame_*):
+//                               rounds of R subframes that go only to the pixels which still fail the stopping rule (tested from MIN
+//                               samples on, default 100; 95 % interval below REL of the mean, default 0.02, or below ABS, default
+//                               0.01), at most MAX per pixel; the EXR is the adaptive mean, FILE gets the per-pixel sample counts
+//                               (raw little-endian uint32, row-major); one GPU, the path tracer: not with --gpus, --network,
+//                               --traced-bake or --display
 //   <cloud> = file.vdb | procedural:<N>[:<seed>] | file.f32grid
 //
 //   cloudtrace collect <cloud>|@list.txt [--scene-id I] [--scenes N] [--jobs K] [--gpus ..] [--batch 2048] [--light L] [--size-m M] [--out DIR] [--data DIR] [--estimator ..] [--tex-fixed8] [--device-collector]
@@ -89,6 +95,9 @@ namespace
         uint32_t bakeSamples = 0;                                                 // --bake-samples N: experiments per entry of the traced bake
         bool bakeAdaptive = false;                                                // --bake-adaptive R,MAX[,REL[,ABS[,ZERO]]]: the traced bake in rounds under the stopping rule
         CtBakeAdaptive adaptive{ CT_ABI_VERSION, 0, 0, 100000, 2e-2f, 1e-4f };
+        bool adaptiveFrame = false;                                               // --adaptive R,MAX[,MIN[,REL[,ABS]]]: the image as an adaptive frame (Camera::adaptive)
+        CtAdaptiveFrameDesc adaptiveDesc{ CT_ABI_VERSION, 0, 100, 0, 2e-2f, 1e-2f, 0, 0 };
+        std::string adaptiveCounts;                                               // --adaptive-counts FILE: the per-pixel sample counts
         bool netDirect = false;                                                   // --net-direct: CT_NET_ADD_SINGLE_SCATTER joins networkRender.transform
         bool collect = false;                                                     // `cloudtrace collect ...`
         int32_t sceneId = 0;
@@ -316,6 +325,9 @@ namespace
             camera->maxSubframes = opt.spp;
             camera->fused = opt.fused;
             camera->headless = opt.fused && !opt.display;
+            camera->adaptive = opt.adaptiveFrame;
+            camera->adaptiveDesc = opt.adaptiveDesc;
+            camera->adaptiveCountsFile = opt.adaptiveCounts;
             std::vector<std::shared_ptr<SceneItem>> items{ sun, cloud, material, camera };
             if (relight) items = { sun, material, camera };                       // the volume is on the device already
             return std::make_shared<Scene>(items, context, opt.dataDir);
@@ -328,7 +340,7 @@ int main(int argc, char* argv[])
     try
     {
         Options opt;
-        if (argc < 2) { std::cerr << "usage: cloudtrace <cloud> [--size WxH] [--spp N] [--mode total|multi|single] [--light L] [--size-m M] [--out DIR] [--data DIR] [--unfused] [--display] [--estimator march|delta] [--format exr|pfm] [--gpus N|a,b,c] [--tex-fixed8] [--network FILE [--net-transform linear|expm1] [--net-scale r,g,b] [--net-direct] [--net-baked NX,NY,NZ,NPHI,NC [--net-bake-sparse | --net-bake-compact]]] [--traced-bake NX,NY,NZ,NPHI,NC --bake-samples N [--net-bake-sparse | --net-bake-compact] [--net-direct]] (--network with --gpus: every GPU renders its own tiles; --net-baked: one GPU)\n"; return 2; }
+        if (argc < 2) { std::cerr << "usage: cloudtrace <cloud> [--size WxH] [--spp N] [--mode total|multi|single] [--light L] [--size-m M] [--out DIR] [--data DIR] [--unfused] [--display] [--estimator march|delta] [--format exr|pfm] [--gpus N|a,b,c] [--tex-fixed8] [--network FILE [--net-transform linear|expm1] [--net-scale r,g,b] [--net-direct] [--net-baked NX,NY,NZ,NPHI,NC [--net-bake-sparse | --net-bake-compact]]] [--traced-bake NX,NY,NZ,NPHI,NC --bake-samples N [--net-bake-sparse | --net-bake-compact] [--net-direct]] [--adaptive R,MAX[,MIN[,REL[,ABS]]] [--adaptive-counts FILE]] (--network with --gpus: every GPU renders its own tiles; --net-baked: one GPU)\n"; return 2; }
         int first = 2;
         bool lightsGiven = false;
         opt.cloud = argv[1];
@@ -404,6 +416,14 @@ int main(int argc, char* argv[])
                 if (std::sscanf(next().c_str(), "%u,%u,%f,%f,%u", &p.round_samples, &p.max_samples, &p.rel_tol, &p.abs_tol, &p.zero_samples) < 2) throw std::invalid_argument("--bake-adaptive R,MAX[,REL[,ABS[,ZERO]]]");
                 opt.bakeAdaptive = true;
             }
+            else if (a == "--adaptive")
+            {
+                CtAdaptiveFrameDesc& p = opt.adaptiveDesc;
+                const int got = std::sscanf(next().c_str(), "%u,%u,%u,%f,%f", &p.round_samples, &p.max_samples, &p.min_samples, &p.rel_tol, &p.abs_tol);
+                if (got < 2) throw std::invalid_argument("--adaptive R,MAX[,MIN[,REL[,ABS]]]");
+                opt.adaptiveFrame = true;
+            }
+            else if (a == "--adaptive-counts") opt.adaptiveCounts = next();
             else if (a == "--net-bake-sparse")
             {
                 opt.netBakeSparse = true;
@@ -455,6 +475,9 @@ int main(int argc, char* argv[])
         if (opt.netBakeSparse && !opt.netBaked && !opt.tracedBake) throw std::invalid_argument("--net-bake-sparse chooses how --net-baked NX,NY,NZ,NPHI,NC bakes its table");
         if (opt.netBaked && opt.networkPath.empty()) throw std::invalid_argument("--net-baked bakes the network of --network FILE");
         if (opt.netBaked && !opt.devices.empty()) throw std::invalid_argument("--net-baked renders on one GPU: it cannot be combined with --gpus");
+        if (opt.adaptiveFrame && (!opt.devices.empty() || !opt.networkPath.empty() || opt.tracedBake || opt.display))
+            throw std::invalid_argument("--adaptive renders with the path tracer on one GPU, headless: it cannot be combined with --gpus, --network, --traced-bake or --display");
+        if (!opt.adaptiveCounts.empty() && !opt.adaptiveFrame) throw std::invalid_argument("--adaptive-counts FILE names where the counts of --adaptive R,MAX[,MIN[,REL[,ABS]]] go");
         if (!opt.networkPath.empty())
         {
             // read and checked against the header's formula here, before a renderer exists: a malformed file costs no device

@@ -422,6 +422,85 @@ CT_API int ct_collector_info(CtCollector c, CtCollectorInfo *out);
 CT_API int ct_collector_download(CtCollector c, CtPointRadianceTask *tasks_host_out, uint32_t *converged_update_host_out, uint32_t count);
 CT_API int ct_collector_destroy(CtCollector c);
 
+/* ---- the adaptive frame: the progressive image with the stopping rule applied per pixel ---------------
+ *
+ * ct_set_stop_when_converged mirrors Camera::isConverged (Camera.cpp:232-268): every pixel of the frame gets further subframes
+ * until fewer than 500 pixels fail the test, so the whole frame pays for the few pixels over the dense core.  A CtAdaptiveFrame
+ * renders the handle's image, for the pose and light the handle has at ct_adaptive_frame_create, in rounds of R = round_samples
+ * subframes that go only to the pixels which have not yet passed the test.  It keeps a mean, an M2 and a sample count per pixel
+ * of its own; the handle's image state (frame, mean, M2, subframe count, samples rendered ahead, freeze state) and the pose's
+ * pixel list are not touched.
+ *
+ * Pixels are p = y * width + x.  At create every pixel of the frame is live, in ascending p, and mean, M2 and count are 0.
+ * All live pixels hold the same count c.  A round gives each of them subframes c + 1 .. c + R:
+ *     The sample of pixel p and subframe s is ct_render_subframe's for that pixel: the pose's primary ray as for the image,
+ *     seed tea<4>(x * 4096 + y, s), the handle's mode, estimator and CT_FLAG_TEX_FIXED8.
+ *     The samples are folded in subframe order as ct_accumulate folds, on all four channels (float32, no contraction):
+ *         w = 1.0f / (float)s,  nm = mu + (v - mu) * w,  m2 += (v - mu) * (v - nm),  mu = nm
+ *     If c + R >= min_samples, the test of ct_is_converged is applied with the frame's tolerances: channel x only, in float32
+ *     with IEEE division and square root, N = (float)(c + R):
+ *         sigma = sqrt(m2.x / N),  abs = 1.96f * sigma / sqrt(N),  rel = abs / (mean.x + FLT_EPSILON),
+ *         converged = rel < rel_tol || abs < abs_tol          (a NaN compares false)
+ *     A pixel leaves the live list when it is converged, or when its count equals max_samples.  At the cap the pixels that
+ *     fail the rule are kept as the capped list.  Survivors keep their ascending order.
+ * So, for every pixel, (mean, M2) is bit for bit that pixel of ct_render_accumulate(h2, 1, counts[p]) on a handle h2 of the same
+ * scene and pose, and counts is what the rule gives on those uniform images -- whatever the split of rounds over calls,
+ * chunk_pixels or pass_subframes.
+ *
+ * ct_adaptive_frame_update runs at most `rounds` rounds (0: until nothing is live).  With nothing live it is CT_OK and launches
+ * nothing.  ct_adaptive_frame_raise_cap sets a higher cap, a multiple of R: the capped pixels go live again, and the next
+ * updates give the bits of a frame created with that cap.  ct_adaptive_frame_info may be called at any time.
+ * ct_adaptive_frame_download copies CT_ADAPTIVE_MEAN or CT_ADAPTIVE_M2 (width * height float4) or CT_ADAPTIVE_COUNTS (width *
+ * height uint32) to the host; `bytes` must be the exact size.  ct_adaptive_frame_device_ptr gives the device address of the
+ * same arrays: ct_tonemap_buffer(h, mean, ..) and ct_is_converged_buffers work on them unchanged.
+ *
+ * A round's live list is traced in chunks of whole groups of 64 entries (chunk_pixels; default: at most 2^20 entries) and a
+ * chunk's R subframes in passes (pass_subframes; default: at most 2^24 results per estimator launch); the fold of a round's
+ * last pass evaluates the rule, a scan and a ranked write compact the survivors, and the host reads one count per round.
+ * CtCounters, CtFetchCounters, ct_kernel_time and the armed invariants (CT_DEBUG_INVARIANTS) see the paths exactly as
+ * ct_point_radiance_launch's.  The estimator's scratch is the handle's, grown as for ct_point_radiance_launch; everything else
+ * -- mean, M2, counts, two live lists of width * height words, the wave counts -- is allocated in ct_adaptive_frame_create:
+ * CT_E_NOMEM there leaves the handle as it was.
+ *
+ * Stopping per pixel biases a pixel's mean towards runs of low variance: a pixel whose first samples happen to agree leaves
+ * early, with them.  min_samples is the guard against that -- no pixel is tested on fewer samples -- and the only one; keep the
+ * reference's 100 unless the bias has been measured for the scene.
+ *
+ * CT_E_INVAL, before anything changes: a NULL argument (a NULL handle or frame is answered without a device); a wrong
+ * abi_version; a value outside the ranges below; a CT_FLAG_SIMPLE_KERNEL handle; a shard of a multi-GPU job (shard_count > 1);
+ * a cap that is not higher, or no multiple of R, or above 2^24; an unknown `which` or a wrong size.
+ * CT_E_STATE: ct_adaptive_frame_update and ct_adaptive_frame_raise_cap after ct_set_camera changed the pose or after
+ * ct_set_light (info, download and device_ptr still work).  Errors go to the owning handle's ct_last_error.
+ * ct_adaptive_frame_destroy(NULL) is a no-op; destroy a frame before its handle. */
+#define CT_ADAPTIVE_MEAN 0
+#define CT_ADAPTIVE_M2 1
+#define CT_ADAPTIVE_COUNTS 2
+typedef struct CtAdaptiveFrameDesc {
+    uint32_t abi_version;    /* CT_ABI_VERSION */
+    uint32_t round_samples;  /* R: subframes per live pixel and round, 1 .. 65535 (reference cadence: 10) */
+    uint32_t min_samples;    /* a pixel is tested only at counts >= this; a multiple of R, R .. max_samples (reference: 100) */
+    uint32_t max_samples;    /* cap per pixel: a multiple of R, R .. 2^24 */
+    float    rel_tol;        /* finite, >= 0 (reference: 2e-2f) */
+    float    abs_tol;        /* finite, >= 0 (reference: 1e-2f, Camera.cpp:232-268) */
+    uint32_t chunk_pixels;   /* 0 = the library's choice; else a multiple of 64: live entries per estimator launch */
+    uint32_t pass_subframes; /* 0 = the library's choice; else 1 .. R: subframes per estimator launch */
+} CtAdaptiveFrameDesc;       /* 32 bytes */
+typedef struct CtAdaptiveFrame_ *CtAdaptiveFrame;
+typedef struct CtAdaptiveFrameInfo {
+    uint32_t width, height, round_samples, min_samples, max_samples, rounds;
+    float    rel_tol, abs_tol;                       /* 32 bytes so far */
+    uint64_t pixels, live, converged, capped, paths; /* pixels = live + converged + capped; paths = sum of the counts */
+    double   trace_ms, fold_ms, test_ms;             /* GPU time of the last ct_adaptive_frame_update call, as CtCollectorInfo's */
+} CtAdaptiveFrameInfo;       /* 96 bytes */
+
+CT_API int ct_adaptive_frame_create(CtHandle h, const CtAdaptiveFrameDesc *d, CtAdaptiveFrame *out);
+CT_API int ct_adaptive_frame_update(CtAdaptiveFrame f, uint32_t rounds);
+CT_API int ct_adaptive_frame_raise_cap(CtAdaptiveFrame f, uint32_t max_samples);
+CT_API int ct_adaptive_frame_info(CtAdaptiveFrame f, CtAdaptiveFrameInfo *out);
+CT_API int ct_adaptive_frame_download(CtAdaptiveFrame f, uint32_t which, void *host, size_t bytes);
+CT_API int ct_adaptive_frame_device_ptr(CtAdaptiveFrame f, uint32_t which, void **out);
+CT_API int ct_adaptive_frame_destroy(CtAdaptiveFrame f);
+
 /* generatePoints (src/CUDA/pointGeneratorCamera.cu:20-42) + firstScatterPosition
  * (cloudFirstScatterMaterial.cu:8-29), launched over `count` threads by ScatterSampleCollector::collect
  * (ScatterSampleCollector.cpp:36-62): thread i draws a direction uniformly on the sphere and a point on

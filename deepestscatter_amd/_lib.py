@@ -35,6 +35,9 @@ EXPORTS = [
     "ct_group_render_accumulate", "ct_group_reset", "ct_group_merge", "ct_group_download", "ct_group_tonemap",
     "ct_group_is_converged", "ct_group_counters",
     "ct_group_network_create", "ct_group_network_destroy", "ct_group_network_render_accumulate",
+    "ct_adaptive_frame_create_shard", "ct_group_adaptive_frame_create", "ct_group_adaptive_frame_update", "ct_group_adaptive_frame_raise_cap",
+    "ct_group_adaptive_frame_info", "ct_group_adaptive_frame_shard", "ct_group_adaptive_frame_merge", "ct_group_adaptive_frame_download",
+    "ct_group_adaptive_frame_device_ptr", "ct_group_adaptive_frame_destroy",
 ]
 # ... and the declared symbols whose names have digits (the list above is matched by name pattern)
 DEBUG_EXPORTS = ["ct_debug_bf16_round"]
@@ -428,6 +431,16 @@ def load():
         "ct_group_network_destroy": (i32, [vp]),
         "ct_group_network_render_accumulate": (i32, [vp, vp, C.POINTER(CtNetworkRender), u32, u32]),
         "ct_make_procedural_cloud": (i32, [u32, u32, vp]),
+        "ct_adaptive_frame_create_shard": (i32, [vp, C.POINTER(CtAdaptiveFrameDesc), C.POINTER(vp)]),
+        "ct_group_adaptive_frame_create": (i32, [vp, C.POINTER(CtAdaptiveFrameDesc), C.POINTER(vp)]),   # -> CtGroupAdaptiveFrame
+        "ct_group_adaptive_frame_update": (i32, [vp, u32]),
+        "ct_group_adaptive_frame_raise_cap": (i32, [vp, u32]),
+        "ct_group_adaptive_frame_info": (i32, [vp, C.POINTER(CtAdaptiveFrameInfo)]),
+        "ct_group_adaptive_frame_shard": (i32, [vp, u32, C.POINTER(vp)]),
+        "ct_group_adaptive_frame_merge": (i32, [vp]),
+        "ct_group_adaptive_frame_download": (i32, [vp, u32, vp, C.c_size_t]),
+        "ct_group_adaptive_frame_device_ptr": (i32, [vp, u32, C.POINTER(vp)]),
+        "ct_group_adaptive_frame_destroy": (i32, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

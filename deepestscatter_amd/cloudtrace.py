@@ -283,13 +283,14 @@ class CloudTracer:
         return DeviceRadianceCollector(self, positions, directions, **params)
 
     def adaptive_frame(self, round_samples: int = 10, max_samples: int = 1000, min_samples: int = 100, rel_tol: float = 2e-2,
-                       abs_tol: float = 1e-2, chunk_pixels: int = 0, pass_subframes: int = 0):
+                       abs_tol: float = 1e-2, chunk_pixels: int = 0, pass_subframes: int = 0, shard: bool = False):
         """An adaptive.AdaptiveFrame on this handle (ct_adaptive_frame_*): the image of the current pose and light in rounds of
         `round_samples` subframes that go only to the pixels which have not yet passed Camera::isConverged's test (tested from
         `min_samples` on), at most `max_samples` per pixel.  The handle's own image is not touched.  Defaults: the reference's
-        cadence, minimum and tolerances."""
+        cadence, minimum and tolerances.  shard: ct_adaptive_frame_create_shard -- the frame of this tracer's own pixels
+        (shard_index of shard_count), zero elsewhere; without it a sharded tracer is refused."""
         from .adaptive import AdaptiveFrame
-        return AdaptiveFrame(self, round_samples, max_samples, min_samples, rel_tol, abs_tol, chunk_pixels, pass_subframes)
+        return AdaptiveFrame(self, round_samples, max_samples, min_samples, rel_tol, abs_tol, chunk_pixels, pass_subframes, shard)
 
     def generate_scatter_samples(self, count: int, batch_seed: int = 0):
         """generatePoints + firstScatterPosition: -> (positions [count,3], view directions [count,3])."""
@@ -907,8 +908,8 @@ class TracerGroup:
 
     def close(self):
         if getattr(self, "g", None):
-            for net in list(getattr(self, "_networks", ())):
-                net.close()       # (a group's networks go before the group)
+            for net in list(getattr(self, "_networks", ())) + list(getattr(self, "_adaptive_frames", ())):
+                net.close()       # (a group's networks and adaptive frames go before the group)
             self.L.ct_group_destroy(self.g)
             self.g = None
 
@@ -947,6 +948,19 @@ class TracerGroup:
         p = CloudTracer._network_render_params(transform, rgb_scale, band_pixels, direct)
         self._check(self.L.ct_group_network_render_accumulate(self.g, net.gn if net is not None else None, C.byref(p),
                                                               first_subframe_id & 0xFFFFFFFF, count))
+
+    def adaptive_frame(self, **params):
+        """ct_group_adaptive_frame_create -> adaptive.GroupAdaptiveFrame: CloudTracer.adaptive_frame's image with every shard
+        running its own rounds over its own pixels (params as there: round_samples, max_samples, min_samples, rel_tol, abs_tol,
+        chunk_pixels, pass_subframes); the merged frame is the unsharded tracer's, bit for bit."""
+        from .adaptive import GroupAdaptiveFrame
+        return GroupAdaptiveFrame(self, **params)
+
+    def handle(self, index: int):
+        """ct_group_handle: shard `index`'s CtHandle (owned by the group), for the entry points that take one."""
+        h = C.c_void_p()
+        self._check(self.L.ct_group_handle(self.g, index, C.byref(h)))
+        return h
 
     def reset(self):
         self._check(self.L.ct_group_reset(self.g))

@@ -177,6 +177,51 @@ __global__ __launch_bounds__(256) void adaptive_compact_kernel(AdaptiveArgs a, c
     }
 }
 
+// ct_adaptive_frame_create_shard: is pixel p of the frame the shard's own?  The tile rule of ct_tile_owner on the pixel's 8 x 8 tile.
+CT_DEV bool adaptive_own(const AdaptiveShard &s, uint32_t p)
+{
+    return tile_owner((p % s.width) >> 3, (p / s.width) >> 3, s.shard_count) == s.shard_index;
+}
+
+// The first live list of a shard frame, pass 1: lane p of the frame's pixels tests the tile rule and every wave of 64 consecutive
+// pixels writes how many of them are the shard's own.  Every lane reaches the ballot; the last wave's lanes p >= pixels vote no.
+__global__ __launch_bounds__(256) void adaptive_own_count_kernel(AdaptiveShard s, uint32_t *__restrict__ wave_counts)
+{
+    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+    const bool own = p < s.pixels && adaptive_own(s, p);
+    const uint64_t mask = __builtin_amdgcn_ballot_w64(own);
+    if ((threadIdx.x & 63u) == 0u && p < s.pixels) {
+        wave_counts[p >> 6] = (uint32_t)__popcll(mask);
+    }
+}
+
+// ... and pass 2, behind adaptive_scan_kernel over those counts: adaptive_compact_kernel's ranked write with the tile rule as the
+// predicate.  live_out is the shard's pixels in ascending p, the same list on every run.
+__global__ __launch_bounds__(256) void adaptive_own_list_kernel(AdaptiveShard s, const uint32_t *__restrict__ wave_offsets,
+                                                                uint32_t *__restrict__ live_out)
+{
+    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+    const bool own = p < s.pixels && adaptive_own(s, p);
+    const uint64_t mask = __builtin_amdgcn_ballot_w64(own);
+    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+    if (own) {
+        live_out[wave_offsets[p >> 6] + rank] = p;
+    }
+}
+
+hipError_t launch_adaptive_own_count(const AdaptiveShard &s, uint32_t *waves, hipStream_t stream)
+{
+    hipLaunchKernelGGL(adaptive_own_count_kernel, dim3((s.pixels + 255u) / 256u), dim3(256), 0, stream, s, waves);
+    hipLaunchKernelGGL(adaptive_scan_kernel, dim3(1), dim3(1024), 0, stream, waves, (s.pixels + 63u) / 64u);
+    return hipGetLastError();
+}
+
+hipError_t launch_adaptive_own_list(const AdaptiveShard &s, const uint32_t *waves, uint32_t *live_out, hipStream_t stream)
+{
+    hipLaunchKernelGGL(adaptive_own_list_kernel, dim3((s.pixels + 255u) / 256u), dim3(256), 0, stream, s, waves, live_out);
+    return hipGetLastError();
+}
+
 hipError_t launch_adaptive_rays(const DevScene &sc, const AdaptiveArgs &a, float4 *primary, uint32_t *pixels, hipStream_t stream)
 {
     hipLaunchKernelGGL(adaptive_rays_kernel, dim3((a.n_pad + 255u) / 256u), dim3(256), 0, stream, sc, a, primary, pixels);

@@ -2735,6 +2735,7 @@ struct CtAdaptiveFrame_ {
     int device = 0;
     CtAdaptiveFrameDesc d{};
     uint32_t width = 0, height = 0, pixels = 0;
+    uint32_t own = 0;         // the pixels the frame renders: all of them, or (ct_adaptive_frame_create_shard) the shard's own
     uint32_t n_live = 0;      // entries of the live list: live[cur], or every pixel of the frame while !listed
     uint32_t n_capped = 0;    // n_live == 0: the entries of live[cur] that failed the rule at the cap
     bool listed = false;
@@ -2773,9 +2774,21 @@ static int adaptive_current(CtAdaptiveFrame f, const char *who)
     return CT_OK;
 }
 
-extern "C" int ct_adaptive_frame_create(CtHandle h, const CtAdaptiveFrameDesc *d, CtAdaptiveFrame *out)
+// ct_group_adaptive_frame_create (ct_group.hip): were two shards' frames created for the same camera pose and light?  Shards
+// of one image must be; a caller that moved one handle of a group on its own is told so.
+namespace ct {
+bool adaptive_same_view(CtAdaptiveFrame a, CtAdaptiveFrame b)
 {
-    const char *const who = "ct_adaptive_frame_create";
+    const CtScene &sa = a->h->scene, &sb = b->h->scene;
+    return memcmp(a->pose, b->pose, sizeof a->pose) == 0 && memcmp(sa.light_direction, sb.light_direction, sizeof sa.light_direction) == 0 &&
+           memcmp(sa.light_color, sb.light_color, sizeof sa.light_color) == 0 && sa.light_intensity == sb.light_intensity;
+}
+} // namespace ct
+
+// ct_adaptive_frame_create (shard == false: a whole frame, a shard of a multi-GPU job is refused) and
+// ct_adaptive_frame_create_shard (shard == true: the handle's own pixels, any shard_count).
+static int adaptive_create(CtHandle h, const CtAdaptiveFrameDesc *d, CtAdaptiveFrame *out, const char *who, bool shard)
+{
     if (!h) {
         return fail(nullptr, CT_E_INVAL, "null handle");
     }
@@ -2811,28 +2824,35 @@ extern "C" int ct_adaptive_frame_create(CtHandle h, const CtAdaptiveFrameDesc *d
     if (h->scene.flags & CT_FLAG_SIMPLE_KERNEL) {
         return fail(h, CT_E_INVAL, "%s: an adaptive frame needs the persistent kernel", who);
     }
-    if (h->scene.shard_count > 1u) {
+    if (!shard && h->scene.shard_count > 1u) {
         return fail(h, CT_E_INVAL, "%s: this handle renders shard %u of %u; an adaptive frame is a whole frame", who, h->scene.shard_index,
                     h->scene.shard_count);
     }
     NEED(h);
+    const bool listed = h->scene.shard_count > 1u;   // (one shard of one: the whole frame, ct_adaptive_frame_create's object)
     CtAdaptiveFrame_ *f = new CtAdaptiveFrame_();
     f->h = h;
     f->device = h->device;
     f->d = *d;
     f->width = h->scene.width;
     f->height = h->scene.height;
-    f->pixels = f->n_live = f->width * f->height;   // (at most 12288 x 4096: ct_create)
+    f->pixels = f->own = f->n_live = f->width * f->height;   // (at most 12288 x 4096: ct_create)
     f->cap = d->max_samples;
     f->epoch = h->light_epoch;
     adaptive_pose(h->dev, f->pose);
     const size_t P = f->pixels;
-    if (f->mean.alloc(P) != hipSuccess || f->m2.alloc(P) != hipSuccess || f->counts.alloc(P) != hipSuccess || f->live[0].alloc(P) != hipSuccess ||
-        f->live[1].alloc(P) != hipSuccess || f->waves.alloc((P + 63u) / 64u + 1u) != hipSuccess) {
+    auto no_memory = [&]() {
         (void)hipGetLastError();
         delete f;
         return fail(h, CT_E_NOMEM, "%s: no device memory for the state and live lists of %zu pixels", who, P);
+    };
+    if (f->mean.alloc(P) != hipSuccess || f->m2.alloc(P) != hipSuccess || f->counts.alloc(P) != hipSuccess ||
+        (!listed && (f->live[0].alloc(P) != hipSuccess || f->live[1].alloc(P) != hipSuccess)) ||
+        f->waves.alloc((P + 63u) / 64u + 1u) != hipSuccess) {
+        return no_memory();
     }
+    const AdaptiveShard own{ f->width, f->pixels, h->scene.shard_index, h->scene.shard_count };
+    uint32_t n_own = 0;
     auto fill = [&]() -> int {
         for (Event &e : f->ev) {
             HIPCHK(h, e.create());
@@ -2840,10 +2860,32 @@ extern "C" int ct_adaptive_frame_create(CtHandle h, const CtAdaptiveFrameDesc *d
         HIPCHK(h, hipMemsetAsync(f->mean, 0, P * sizeof(float4), h->stream));
         HIPCHK(h, hipMemsetAsync(f->m2, 0, P * sizeof(float4), h->stream));
         HIPCHK(h, hipMemsetAsync(f->counts, 0, P * sizeof(uint32_t), h->stream));
+        if (listed) {   // the wave counts of the tile rule and their scan; the total sizes the two lists
+            HIPCHK(h, launch_adaptive_own_count(own, f->waves, h->stream));
+            HIPCHK(h, hipMemcpyAsync(&n_own, f->waves + (P + 63u) / 64u, sizeof n_own, hipMemcpyDeviceToHost, h->stream));
+        }
         HIPCHK(h, hipStreamSynchronize(h->stream));
         return CT_OK;
     };
-    const int rc = fill();
+    int rc = fill();
+    if (rc == CT_OK && listed) {
+        if (n_own > P) {
+            rc = fail(h, CT_E_HIP, "internal: %u of %zu pixels counted as the shard's own", n_own, P);
+        } else if (n_own != 0u && (f->live[0].alloc(n_own) != hipSuccess || f->live[1].alloc(n_own) != hipSuccess)) {
+            return no_memory();
+        } else {
+            f->own = f->n_live = n_own;
+            f->listed = true;
+            auto list = [&]() -> int {
+                if (n_own != 0u) {
+                    HIPCHK(h, launch_adaptive_own_list(own, f->waves, f->live[0], h->stream));
+                    HIPCHK(h, hipStreamSynchronize(h->stream));
+                }
+                return CT_OK;
+            };
+            rc = list();
+        }
+    }
     if (rc != CT_OK) {
         hipStreamSynchronize(h->stream);
         delete f;
@@ -2851,6 +2893,16 @@ extern "C" int ct_adaptive_frame_create(CtHandle h, const CtAdaptiveFrameDesc *d
     }
     *out = f;
     return CT_OK;
+}
+
+extern "C" int ct_adaptive_frame_create(CtHandle h, const CtAdaptiveFrameDesc *d, CtAdaptiveFrame *out)
+{
+    return adaptive_create(h, d, out, "ct_adaptive_frame_create", false);
+}
+
+extern "C" int ct_adaptive_frame_create_shard(CtHandle h, const CtAdaptiveFrameDesc *d, CtAdaptiveFrame *out)
+{
+    return adaptive_create(h, d, out, "ct_adaptive_frame_create_shard", true);
 }
 
 extern "C" int ct_adaptive_frame_update(CtAdaptiveFrame f, uint32_t rounds)
@@ -2990,10 +3042,10 @@ extern "C" int ct_adaptive_frame_info(CtAdaptiveFrame f, CtAdaptiveFrameInfo *ou
     out->rounds = f->rounds;
     out->rel_tol = f->d.rel_tol;
     out->abs_tol = f->d.abs_tol;
-    out->pixels = f->pixels;
+    out->pixels = f->own;
     out->live = f->n_live;
     out->capped = f->n_capped;
-    out->converged = (uint64_t)f->pixels - f->n_live - f->n_capped;
+    out->converged = (uint64_t)f->own - f->n_live - f->n_capped;
     out->paths = f->paths;
     out->trace_ms = f->trace_ms;
     out->fold_ms = f->fold_ms;

@@ -15,6 +15,9 @@
 // a process that already holds a copy, e.g. PyTorch's, shares it).  A missing library is CT_E_RCCL, never a fallback.
 // RCCL refuses two ranks on one device; a device list that repeats a device (a rehearsal on a one-GPU box) therefore
 // merges with peer copies and an add kernel on the first device instead -- the same sums, no communicator.
+//
+// The adaptive frame on a group (ct_group_adaptive_frame_*, at the end of the file) has a merge of its own: the unsigned maximum
+// of every 32-bit word instead of a float sum, always by peer copies and a kernel on the first device.
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 
@@ -96,7 +99,27 @@ __global__ void add_into_kernel(float4 *__restrict__ dst, const float4 *__restri
     }
 }
 
+// ct_group_adaptive_frame_merge: dst = max(dst, src) on every 32-bit word as an unsigned integer.  A pixel's words are non-zero in
+// at most one shard's arrays, so the maximum IS that shard's word, whatever its bit pattern.  n4 uint4, then the words % 4 tail.
+__global__ void max_into_kernel(uint32_t *__restrict__ dst, const uint32_t *__restrict__ src, size_t words)
+{
+    const size_t n4 = words / 4, stride = (size_t)gridDim.x * blockDim.x, first = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint4 *__restrict__ dst4 = (uint4 *)dst;
+    const uint4 *__restrict__ src4 = (const uint4 *)src;
+    for (size_t i = first; i < n4; i += stride) {
+        const uint4 a = dst4[i], b = src4[i];
+        dst4[i] = make_uint4(max(a.x, b.x), max(a.y, b.y), max(a.z, b.z), max(a.w, b.w));
+    }
+    for (size_t i = 4 * n4 + first; i < words; i += stride) {
+        dst[i] = max(dst[i], src[i]);
+    }
+}
+
 } // namespace
+
+namespace ct {
+bool adaptive_same_view(CtAdaptiveFrame a, CtAdaptiveFrame b);   // ct_api.cpp: the same pose and light at create?
+}
 
 struct CtGroup_ {
     std::vector<CtHandle> handles;
@@ -531,5 +554,282 @@ extern "C" int ct_group_counters(CtGroup g, CtCounters *out)
         out->scatter_events += c.scatter_events;
         out->depth_capped += c.depth_capped;
     }
+    return CT_OK;
+}
+
+// ---- the adaptive frame on a group (ct_group_adaptive_frame_*) -----------------------------------------------------------
+// One shard frame per handle (ct_adaptive_frame_create_shard): every shard runs its own rounds over its own pixels and never
+// waits for another.  The merge stages every shard's [mean | M2 | counts] (9 * W*H words) on its device, copies them one after
+// the other into a landing buffer on the first device and folds each with max_into_kernel into shard 0's staging buffer -- the
+// one path for every device list, the one ct_group_merge takes in a rehearsal; no collective.
+struct CtGroupAdaptiveFrame_ {
+    CtGroup group = nullptr;
+    std::vector<CtAdaptiveFrame> frames;             // per shard, on its device
+    std::vector<ct::DevBuf<uint32_t>> staging;       // per shard, on its device: [mean | M2 | counts]
+    ct::DevBuf<uint32_t> landing;                    // on the first device
+    CtAdaptiveFrameDesc d{};
+    uint32_t cap = 0;
+    bool merged = false;
+};
+
+extern "C" int ct_group_adaptive_frame_destroy(CtGroupAdaptiveFrame gf)
+{
+    if (!gf) {
+        return CT_OK;
+    }
+    CtGroup g = gf->group;
+    for (size_t i = 0; i < g->handles.size(); i++) {
+        hipSetDevice(g->devices[i]);
+        if (i < gf->staging.size()) {
+            gf->staging[i].reset();
+        }
+        if (i < gf->frames.size()) {
+            ct_adaptive_frame_destroy(gf->frames[i]);
+        }
+    }
+    hipSetDevice(g->devices[0]);
+    gf->landing.reset();
+    delete gf;
+    return CT_OK;
+}
+
+extern "C" int ct_group_adaptive_frame_create(CtGroup g, const CtAdaptiveFrameDesc *d, CtGroupAdaptiveFrame *out)
+{
+    const char *const who = "ct_group_adaptive_frame_create";
+    if (!g) {
+        return gfail(nullptr, CT_E_INVAL, "null group");
+    }
+    if (out) {
+        *out = nullptr;
+    }
+    if (!d || !out) {
+        return gfail(g, CT_E_INVAL, "%s: need a description and out", who);
+    }
+    CtGroupAdaptiveFrame gf = new (std::nothrow) CtGroupAdaptiveFrame_();
+    if (!gf) {
+        return gfail(g, CT_E_NOMEM, "out of host memory");
+    }
+    gf->group = g;
+    gf->d = *d;
+    gf->cap = d->max_samples;
+    const size_t words = (size_t)9 * g->width * g->height;
+    for (uint32_t i = 0; i < g->handles.size(); i++) {
+        CtAdaptiveFrame f = nullptr;
+        int rc = ct_adaptive_frame_create_shard(g->handles[i], d, &f);
+        if (rc != CT_OK) {
+            rc = shard_fail(g, i, rc);
+            ct_group_adaptive_frame_destroy(gf);
+            return rc;
+        }
+        gf->frames.push_back(f);
+        if (i != 0 && !ct::adaptive_same_view(gf->frames[0], f)) {
+            ct_group_adaptive_frame_destroy(gf);
+            return gfail(g, CT_E_STATE, "%s: shard %u (device %d) has another camera pose or light than shard 0; ct_group_set_camera and "
+                                        "ct_group_set_light set them on every shard", who, i, g->devices[i]);
+        }
+        ct::DevBuf<uint32_t> st;
+        const bool ok = hipSetDevice(g->devices[i]) == hipSuccess && st.alloc(words) == hipSuccess;
+        gf->staging.push_back(std::move(st));
+        if (!ok) {
+            (void)hipGetLastError();
+            ct_group_adaptive_frame_destroy(gf);
+            return gfail(g, CT_E_NOMEM, "%s: out of device memory (staging buffer of shard %u)", who, i);
+        }
+    }
+    if (hipSetDevice(g->devices[0]) != hipSuccess || gf->landing.alloc(words) != hipSuccess) {
+        (void)hipGetLastError();
+        ct_group_adaptive_frame_destroy(gf);
+        return gfail(g, CT_E_NOMEM, "%s: out of device memory (landing buffer)", who);
+    }
+    *out = gf;
+    return CT_OK;
+}
+
+// ct_adaptive_frame_update waits for every round's survivor count, so -- as in ct_group_network_render_accumulate -- the devices
+// only work at the same time when every shard has a host thread: shards 1 .. N-1 on threads of this call, shard 0 on the caller.
+extern "C" int ct_group_adaptive_frame_update(CtGroupAdaptiveFrame gf, uint32_t rounds)
+{
+    if (!gf) {
+        return gfail(nullptr, CT_E_INVAL, "ct_group_adaptive_frame_update: null frame");
+    }
+    CtGroup g = gf->group;
+    const uint32_t shards = (uint32_t)gf->frames.size();
+    std::vector<int> codes(shards, CT_OK);
+    auto shard = [&](uint32_t i) { codes[i] = ct_adaptive_frame_update(gf->frames[i], rounds); };
+    std::vector<std::thread> threads;
+    threads.reserve(shards);
+    for (uint32_t i = 1; i < shards; i++) {
+        threads.emplace_back(shard, i);
+    }
+    shard(0);
+    for (std::thread &t : threads) {
+        t.join();
+    }
+    gf->merged = false;
+    for (uint32_t i = 0; i < shards; i++) {
+        if (codes[i] != CT_OK) {
+            return shard_fail(g, i, codes[i]);
+        }
+    }
+    return CT_OK;
+}
+
+extern "C" int ct_group_adaptive_frame_raise_cap(CtGroupAdaptiveFrame gf, uint32_t max_samples)
+{
+    const char *const who = "ct_group_adaptive_frame_raise_cap";
+    if (!gf) {
+        return gfail(nullptr, CT_E_INVAL, "%s: null frame", who);
+    }
+    CtGroup g = gf->group;
+    if (max_samples <= gf->cap || max_samples % gf->d.round_samples != 0u || max_samples > (1u << 24)) {
+        return gfail(g, CT_E_INVAL, "%s: max_samples %u; a multiple of round_samples (%u) above the cap (%u), at most 2^24", who, max_samples,
+                     gf->d.round_samples, gf->cap);
+    }
+    for (uint32_t i = 0; i < gf->frames.size(); i++) {
+        const int rc = ct_adaptive_frame_raise_cap(gf->frames[i], max_samples);
+        if (rc != CT_OK) {
+            return shard_fail(g, i, rc);
+        }
+    }
+    gf->cap = max_samples;
+    gf->merged = false;
+    return CT_OK;
+}
+
+extern "C" int ct_group_adaptive_frame_info(CtGroupAdaptiveFrame gf, CtAdaptiveFrameInfo *out)
+{
+    if (!gf || !out) {
+        return gfail(gf ? gf->group : nullptr, CT_E_INVAL, "ct_group_adaptive_frame_info: need a frame and out");
+    }
+    CtAdaptiveFrameInfo sum{};
+    for (uint32_t i = 0; i < gf->frames.size(); i++) {
+        CtAdaptiveFrameInfo s{};
+        const int rc = ct_adaptive_frame_info(gf->frames[i], &s);
+        if (rc != CT_OK) {
+            return shard_fail(gf->group, i, rc);
+        }
+        if (i == 0) {
+            sum = s;   // width, height, R, min, cap and the tolerances: the same on every shard
+            continue;
+        }
+        sum.rounds = s.rounds > sum.rounds ? s.rounds : sum.rounds;
+        sum.pixels += s.pixels;
+        sum.live += s.live;
+        sum.converged += s.converged;
+        sum.capped += s.capped;
+        sum.paths += s.paths;
+        sum.trace_ms = s.trace_ms > sum.trace_ms ? s.trace_ms : sum.trace_ms;   // (the shards run at the same time)
+        sum.fold_ms = s.fold_ms > sum.fold_ms ? s.fold_ms : sum.fold_ms;
+        sum.test_ms = s.test_ms > sum.test_ms ? s.test_ms : sum.test_ms;
+    }
+    *out = sum;
+    return CT_OK;
+}
+
+extern "C" int ct_group_adaptive_frame_shard(CtGroupAdaptiveFrame gf, uint32_t index, CtAdaptiveFrame *out)
+{
+    if (!gf || !out || index >= gf->frames.size()) {
+        return gfail(gf ? gf->group : nullptr, CT_E_INVAL, "ct_group_adaptive_frame_shard: need a frame, out and an index below the group's size");
+    }
+    *out = gf->frames[index];
+    return CT_OK;
+}
+
+extern "C" int ct_group_adaptive_frame_merge(CtGroupAdaptiveFrame gf)
+{
+    if (!gf) {
+        return gfail(nullptr, CT_E_INVAL, "ct_group_adaptive_frame_merge: null frame");
+    }
+    CtGroup g = gf->group;
+    const size_t n = (size_t)g->width * g->height, words = 9 * n;
+    const size_t at[3] = { 0, 4 * n, 8 * n }, size[3] = { 4 * n, 4 * n, n };   // in words: mean, M2, counts
+    for (uint32_t i = 0; i < gf->frames.size(); i++) {
+        GHIP(g, hipSetDevice(g->devices[i]));
+        (void)hipGetLastError();
+        for (uint32_t which = 0; which < 3; which++) {
+            void *src = nullptr;
+            const int rc = ct_adaptive_frame_device_ptr(gf->frames[i], which, &src);
+            if (rc != CT_OK) {
+                return shard_fail(g, i, rc);
+            }
+            GHIP(g, hipMemcpyAsync(gf->staging[i].get() + at[which], src, size[which] * sizeof(uint32_t), hipMemcpyDeviceToDevice, g->streams[i]));
+        }
+        GHIP(g, hipStreamSynchronize(g->streams[i]));
+    }
+    GHIP(g, hipSetDevice(g->devices[0]));
+    for (uint32_t i = 1; i < gf->frames.size(); i++) {
+        GHIP(g, hipMemcpyPeerAsync(gf->landing, g->devices[0], gf->staging[i], g->devices[i], words * sizeof(uint32_t), g->streams[0]));
+        hipLaunchKernelGGL(max_into_kernel, dim3(1024), dim3(256), 0, g->streams[0], gf->staging[0].get(), (const uint32_t *)gf->landing.get(), words);
+        GHIP(g, hipGetLastError());
+    }
+    GHIP(g, hipStreamSynchronize(g->streams[0]));
+    gf->merged = true;
+    return CT_OK;
+}
+
+// The merged array `which` names on the first device and its size; nullptr: no such array.
+static uint32_t *group_adaptive_array(CtGroupAdaptiveFrame gf, uint32_t which, size_t &bytes)
+{
+    const size_t n = (size_t)gf->group->width * gf->group->height;
+    switch (which) {
+    case CT_ADAPTIVE_MEAN:
+        bytes = n * sizeof(float4);
+        return gf->staging[0].get();
+    case CT_ADAPTIVE_M2:
+        bytes = n * sizeof(float4);
+        return gf->staging[0].get() + 4 * n;
+    case CT_ADAPTIVE_COUNTS:
+        bytes = n * sizeof(uint32_t);
+        return gf->staging[0].get() + 8 * n;
+    default:
+        bytes = 0;
+        return nullptr;
+    }
+}
+
+extern "C" int ct_group_adaptive_frame_download(CtGroupAdaptiveFrame gf, uint32_t which, void *host, size_t bytes)
+{
+    const char *const who = "ct_group_adaptive_frame_download";
+    if (!gf) {
+        return gfail(nullptr, CT_E_INVAL, "%s: null frame", who);
+    }
+    CtGroup g = gf->group;
+    size_t need = 0;
+    const uint32_t *src = group_adaptive_array(gf, which, need);
+    if (!src) {
+        return gfail(g, CT_E_INVAL, "%s: which = %u; CT_ADAPTIVE_MEAN, CT_ADAPTIVE_M2 or CT_ADAPTIVE_COUNTS", who, which);
+    }
+    if (!host || bytes != need) {
+        return gfail(g, CT_E_INVAL, "%s: need a host array of exactly %zu bytes", who, need);
+    }
+    if (!gf->merged) {
+        const int rc = ct_group_adaptive_frame_merge(gf);
+        if (rc != CT_OK) {
+            return rc;
+        }
+    }
+    GHIP(g, hipSetDevice(g->devices[0]));
+    GHIP(g, hipMemcpy(host, src, need, hipMemcpyDeviceToHost));
+    return CT_OK;
+}
+
+extern "C" int ct_group_adaptive_frame_device_ptr(CtGroupAdaptiveFrame gf, uint32_t which, void **out)
+{
+    const char *const who = "ct_group_adaptive_frame_device_ptr";
+    if (!gf) {
+        return gfail(nullptr, CT_E_INVAL, "%s: null frame", who);
+    }
+    size_t bytes = 0;
+    uint32_t *p = group_adaptive_array(gf, which, bytes);
+    if (!p || !out) {
+        return gfail(gf->group, CT_E_INVAL, "%s: need CT_ADAPTIVE_MEAN, CT_ADAPTIVE_M2 or CT_ADAPTIVE_COUNTS and out", who);
+    }
+    if (!gf->merged) {
+        const int rc = ct_group_adaptive_frame_merge(gf);
+        if (rc != CT_OK) {
+            return rc;
+        }
+    }
+    *out = p;
     return CT_OK;
 }

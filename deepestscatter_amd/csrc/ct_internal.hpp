@@ -378,6 +378,15 @@ hipError_t launch_adaptive_rays(const DevScene &sc, const AdaptiveArgs &a, float
 hipError_t launch_adaptive_fold(const AdaptiveArgs &a, const float4 *frames, uint32_t stride, uint32_t passes, uint32_t done,
                                 uint32_t *waves, hipStream_t stream);
 hipError_t launch_adaptive_compact(const AdaptiveArgs &a, uint32_t *waves, uint32_t *live_out, hipStream_t stream);
+// ct_adaptive_frame_create_shard: the first live list of a shard frame, the pixels p = y * width + x < pixels whose 8 x 8 tile is
+// the shard's (tile_owner), ascending.  launch_adaptive_own_count: waves[w], w < pixels / 64 (rounded up), becomes the number of
+// own pixels before wave w of 64 consecutive pixels and waves[that wave count] their total (the count pass, then the round's
+// scan); launch_adaptive_own_list writes the list behind it -- the host reads the total in between and sizes live_out by it.
+struct AdaptiveShard {
+    uint32_t width, pixels, shard_index, shard_count;
+};
+hipError_t launch_adaptive_own_count(const AdaptiveShard &s, uint32_t *waves, hipStream_t stream);
+hipError_t launch_adaptive_own_list(const AdaptiveShard &s, const uint32_t *waves, uint32_t *live_out, hipStream_t stream);
 // Density pyramid (Resources::generateMipmaps) and the descriptor gather.
 constexpr int kMaxMipLevels = 16;
 struct MipPyramid {

@@ -7,6 +7,7 @@
 #include <cfloat>
 #include <cstdio>
 #include <filesystem>
+#include <sstream>
 
 #include "NetworkFile.h"
 #include "Scene.h"
@@ -334,7 +335,8 @@ namespace DeepestScatter
 
         // --adaptive: the image is an adaptive frame (ct_adaptive_frame_*) -- rounds that go only to the pixels which still fail
         // the test -- run to its end in one update; the handle's own image is not rendered.  adaptiveCountsFile: where the
-        // per-pixel sample counts go, raw little-endian uint32, row-major (empty: nowhere).
+        // per-pixel sample counts go, raw little-endian uint32, row-major (empty: nowhere).  On a context that is a group
+        // (--adaptive-gpus) the frame is a CtGroupAdaptiveFrame: the same files and totals, from every GPU's own rounds.
         bool adaptive = false;
         CtAdaptiveFrameDesc adaptiveDesc{ CT_ABI_VERSION, 10, 100, 1000, 2e-2f, 1e-2f, 0, 0 };
         std::filesystem::path adaptiveCountsFile;
@@ -385,14 +387,15 @@ namespace DeepestScatter
         void renderAdaptive()
         {
             auto* pt = dynamic_cast<PathTracingRenderer*>(renderer.get());
-            if (pt == nullptr || context->group || context->handle == nullptr) throw std::runtime_error("--adaptive renders with the path tracer on one GPU");
+            if (pt == nullptr || (context->group == nullptr && context->handle == nullptr)) throw std::runtime_error("--adaptive renders with the path tracer");
             pt->publishCamera();
-            CtHandle h = context->handle;
-            CtAdaptiveFrame frame = nullptr;
-            Context::check(ct_adaptive_frame_create(h, &adaptiveDesc, &frame), h, "ct_adaptive_frame_create");
             std::vector<float> mean((size_t)width * height * 4);
             std::vector<uint32_t> counts((size_t)width * height);
             CtAdaptiveFrameInfo info{};
+            if (context->group) { renderAdaptiveGroup(mean, counts, info); finishAdaptive(mean, counts, info); return; }
+            CtHandle h = context->handle;
+            CtAdaptiveFrame frame = nullptr;
+            Context::check(ct_adaptive_frame_create(h, &adaptiveDesc, &frame), h, "ct_adaptive_frame_create");
             int rc = ct_adaptive_frame_update(frame, 0);
             if (rc == CT_OK) rc = ct_adaptive_frame_info(frame, &info);
             if (rc == CT_OK) rc = ct_adaptive_frame_download(frame, CT_ADAPTIVE_MEAN, mean.data(), mean.size() * sizeof(float));
@@ -404,6 +407,43 @@ namespace DeepestScatter
                 throw std::runtime_error("ct_adaptive_frame: " + why);
             }
             ct_adaptive_frame_destroy(frame);
+            finishAdaptive(mean, counts, info);
+        }
+
+        // --adaptive-gpus: the same job on the context's group (ct_group_adaptive_frame_*) -- every shard runs its own rounds over
+        // its own pixels, the merged mean and counts are the single handle's bytes -- and one line with every shard's paths and rounds.
+        void renderAdaptiveGroup(std::vector<float>& mean, std::vector<uint32_t>& counts, CtAdaptiveFrameInfo& info)
+        {
+            CtGroup g = context->group;
+            CtGroupAdaptiveFrame frame = nullptr;
+            Context::checkGroup(ct_group_adaptive_frame_create(g, &adaptiveDesc, &frame), g, "ct_group_adaptive_frame_create");
+            uint32_t shards = 0;
+            std::ostringstream line;
+            int rc = ct_group_adaptive_frame_update(frame, 0);
+            if (rc == CT_OK) rc = ct_group_adaptive_frame_info(frame, &info);
+            if (rc == CT_OK) rc = ct_group_adaptive_frame_download(frame, CT_ADAPTIVE_MEAN, mean.data(), mean.size() * sizeof(float));
+            if (rc == CT_OK) rc = ct_group_adaptive_frame_download(frame, CT_ADAPTIVE_COUNTS, counts.data(), counts.size() * sizeof(uint32_t));
+            if (rc == CT_OK) rc = ct_group_size(g, &shards);
+            for (uint32_t i = 0; rc == CT_OK && i < shards; i++)
+            {
+                CtAdaptiveFrame shard = nullptr;
+                CtAdaptiveFrameInfo s{};
+                rc = ct_group_adaptive_frame_shard(frame, i, &shard);
+                if (rc == CT_OK && ct_adaptive_frame_info(shard, &s) != CT_OK) rc = CT_E_INVAL;
+                line << (i ? ", " : "") << "{\"pixels\": " << s.pixels << ", \"paths\": " << s.paths << ", \"rounds\": " << s.rounds << "}";
+            }
+            if (rc != CT_OK)
+            {
+                const std::string why = ct_group_last_error(g);
+                ct_group_adaptive_frame_destroy(frame);
+                throw std::runtime_error("ct_group_adaptive_frame: " + why);
+            }
+            ct_group_adaptive_frame_destroy(frame);
+            std::cout << "adaptive_shards [" << line.str() << "]" << std::endl;
+        }
+
+        void finishAdaptive(const std::vector<float>& mean, const std::vector<uint32_t>& counts, const CtAdaptiveFrameInfo& info)
+        {
             std::cout << "adaptive {\"rounds\": " << info.rounds << ", \"pixels\": " << info.pixels << ", \"converged\": " << info.converged
                       << ", \"capped\": " << info.capped << ", \"paths\": " << info.paths << "}" << std::endl;
             writeImage(mean);

@@ -57,7 +57,7 @@ namespace DeepestScatter
         void create()
         {
             destroy();
-            if (devices.size() > 1) checkGroup(ct_group_create(&scene, devices.data(), (uint32_t)devices.size(), &group), nullptr, "ct_group_create");
+            if (devices.size() > 1 || (alwaysGroup && !devices.empty())) checkGroup(ct_group_create(&scene, devices.data(), (uint32_t)devices.size(), &group), nullptr, "ct_group_create");
             else { if (!devices.empty()) scene.device = devices[0]; check(ct_create(&scene, &handle), nullptr, "ct_create"); }
         }
         void setCamera(const float* eye, const float* U, const float* V, const float* W)
@@ -121,6 +121,7 @@ namespace DeepestScatter
         CtHandle handle = nullptr;
         CtGroup group = nullptr;
         std::vector<int32_t> devices;       // empty: device 0
+        bool alwaysGroup = false;           // a group even of one device (cloudtrace --adaptive-gpus)
         std::vector<uint8_t> density;       // filled by VDBCloud::InitVolume
         std::vector<float> mie, choppedMie; // filled by Scene::init (Mie::get*Sampler)
     };

@@ -29,6 +29,9 @@
 //                               0.01), at most MAX per pixel; the EXR is the adaptive mean, FILE gets the per-pixel sample counts
 //                               (raw little-endian uint32, row-major); one GPU, the path tracer: not with --gpus, --network,
 //                               --traced-bake or --display
+//              [--adaptive-gpus N | --adaptive-gpus a,b,c]   with --adaptive: the frame on a CtGroup (ct_group_adaptive_frame_*), every
+//                               GPU running its own rounds over its own 8x8-pixel tiles; the same EXR, counts file and adaptive {...}
+//                               line as without it, byte for byte, and one adaptive_shards [...] line with every shard's paths and rounds
 //   <cloud> = file.vdb | procedural:<N>[:<seed>] | file.f32grid
 //
 //   cloudtrace collect <cloud>|@list.txt [--scene-id I] [--scenes N] [--jobs K] [--gpus ..] [--batch 2048] [--light L] [--size-m M] [--out DIR] [--data DIR] [--estimator ..] [--tex-fixed8] [--device-collector]
@@ -98,6 +101,7 @@ namespace
         bool adaptiveFrame = false;                                               // --adaptive R,MAX[,MIN[,REL[,ABS]]]: the image as an adaptive frame (Camera::adaptive)
         CtAdaptiveFrameDesc adaptiveDesc{ CT_ABI_VERSION, 0, 100, 0, 2e-2f, 1e-2f, 0, 0 };
         std::string adaptiveCounts;                                               // --adaptive-counts FILE: the per-pixel sample counts
+        std::vector<int32_t> adaptiveDevices;                                     // --adaptive-gpus N | a,b,c: the adaptive frame on a CtGroup (ct_group_adaptive_frame_*)
         bool netDirect = false;                                                   // --net-direct: CT_NET_ADD_SINGLE_SCATTER joins networkRender.transform
         bool collect = false;                                                     // `cloudtrace collect ...`
         int32_t sceneId = 0;
@@ -297,7 +301,8 @@ namespace
         return [=]()
         {
             const bool relight = context->created();
-            context->devices = opt.devices;
+            context->devices = opt.adaptiveDevices.empty() ? opt.devices : opt.adaptiveDevices;
+            context->alwaysGroup = !opt.adaptiveDevices.empty();                 // (--adaptive-gpus 1 is a group of one)
             if (opt.texFixed8) context->scene.flags |= CT_FLAG_TEX_FIXED8;
             auto resources = std::make_shared<Resources>(context);
             // installSceneSetup (installers.cpp:65-105)
@@ -340,7 +345,7 @@ int main(int argc, char* argv[])
     try
     {
         Options opt;
-        if (argc < 2) { std::cerr << "usage: cloudtrace <cloud> [--size WxH] [--spp N] [--mode total|multi|single] [--light L] [--size-m M] [--out DIR] [--data DIR] [--unfused] [--display] [--estimator march|delta] [--format exr|pfm] [--gpus N|a,b,c] [--tex-fixed8] [--network FILE [--net-transform linear|expm1] [--net-scale r,g,b] [--net-direct] [--net-baked NX,NY,NZ,NPHI,NC [--net-bake-sparse | --net-bake-compact]]] [--traced-bake NX,NY,NZ,NPHI,NC --bake-samples N [--net-bake-sparse | --net-bake-compact] [--net-direct]] [--adaptive R,MAX[,MIN[,REL[,ABS]]] [--adaptive-counts FILE]] (--network with --gpus: every GPU renders its own tiles; --net-baked: one GPU)\n"; return 2; }
+        if (argc < 2) { std::cerr << "usage: cloudtrace <cloud> [--size WxH] [--spp N] [--mode total|multi|single] [--light L] [--size-m M] [--out DIR] [--data DIR] [--unfused] [--display] [--estimator march|delta] [--format exr|pfm] [--gpus N|a,b,c] [--tex-fixed8] [--network FILE [--net-transform linear|expm1] [--net-scale r,g,b] [--net-direct] [--net-baked NX,NY,NZ,NPHI,NC [--net-bake-sparse | --net-bake-compact]]] [--traced-bake NX,NY,NZ,NPHI,NC --bake-samples N [--net-bake-sparse | --net-bake-compact] [--net-direct]] [--adaptive R,MAX[,MIN[,REL[,ABS]]] [--adaptive-counts FILE] [--adaptive-gpus N|a,b,c]] (--network with --gpus: every GPU renders its own tiles; --net-baked: one GPU)\n"; return 2; }
         int first = 2;
         bool lightsGiven = false;
         opt.cloud = argv[1];
@@ -368,14 +373,15 @@ int main(int argc, char* argv[])
             else if (a == "--scenes") opt.scenes = (uint32_t)std::stoul(next());
             else if (a == "--jobs") opt.jobs = (uint32_t)std::stoul(next());
             else if (a == "--device-collector") opt.deviceCollector = true;
-            else if (a == "--gpus")
+            else if (a == "--gpus" || a == "--adaptive-gpus")
             {
                 // "N" = devices 0..N-1; "a,b,c" = that list (a device may repeat: a rehearsal of N shards on fewer GPUs)
                 const std::string v = next();
-                opt.devices.clear();
-                if (v.find(',') == std::string::npos) { for (int d = 0; d < std::stoi(v); d++) opt.devices.push_back(d); }
-                else { size_t p = 0; while (p <= v.size()) { const size_t q = v.find(',', p); opt.devices.push_back(std::stoi(v.substr(p, q - p))); if (q == std::string::npos) break; p = q + 1; } }
-                if (opt.devices.empty()) throw std::invalid_argument("--gpus N | --gpus a,b,c");
+                std::vector<int32_t>& devices = a == "--gpus" ? opt.devices : opt.adaptiveDevices;
+                devices.clear();
+                if (v.find(',') == std::string::npos) { for (int d = 0; d < std::stoi(v); d++) devices.push_back(d); }
+                else { size_t p = 0; while (p <= v.size()) { const size_t q = v.find(',', p); devices.push_back(std::stoi(v.substr(p, q - p))); if (q == std::string::npos) break; p = q + 1; } }
+                if (devices.empty()) throw std::invalid_argument(a + " N | " + a + " a,b,c");
             }
             else if (a == "--display") opt.display = true;
             else if (a == "--network") opt.networkPath = next();
@@ -477,6 +483,7 @@ int main(int argc, char* argv[])
         if (opt.netBaked && !opt.devices.empty()) throw std::invalid_argument("--net-baked renders on one GPU: it cannot be combined with --gpus");
         if (opt.adaptiveFrame && (!opt.devices.empty() || !opt.networkPath.empty() || opt.tracedBake || opt.display))
             throw std::invalid_argument("--adaptive renders with the path tracer on one GPU, headless: it cannot be combined with --gpus, --network, --traced-bake or --display");
+        if (!opt.adaptiveDevices.empty() && !opt.adaptiveFrame) throw std::invalid_argument("--adaptive-gpus N|a,b,c names the GPUs of --adaptive R,MAX[,MIN[,REL[,ABS]]]");
         if (!opt.adaptiveCounts.empty() && !opt.adaptiveFrame) throw std::invalid_argument("--adaptive-counts FILE names where the counts of --adaptive R,MAX[,MIN[,REL[,ABS]]] go");
         if (!opt.networkPath.empty())
         {

@@ -467,8 +467,8 @@ CT_API int ct_collector_destroy(CtCollector c);
  * reference's 100 unless the bias has been measured for the scene.
  *
  * CT_E_INVAL, before anything changes: a NULL argument (a NULL handle or frame is answered without a device); a wrong
- * abi_version; a value outside the ranges below; a CT_FLAG_SIMPLE_KERNEL handle; a shard of a multi-GPU job (shard_count > 1);
- * a cap that is not higher, or no multiple of R, or above 2^24; an unknown `which` or a wrong size.
+ * abi_version; a value outside the ranges below; a CT_FLAG_SIMPLE_KERNEL handle; a shard of a multi-GPU job (shard_count > 1;
+ * ct_adaptive_frame_create_shard below takes one); a cap that is not higher, or no multiple of R, or above 2^24; an unknown `which` or a wrong size.
  * CT_E_STATE: ct_adaptive_frame_update and ct_adaptive_frame_raise_cap after ct_set_camera changed the pose or after
  * ct_set_light (info, download and device_ptr still work).  Errors go to the owning handle's ct_last_error.
  * ct_adaptive_frame_destroy(NULL) is a no-op; destroy a frame before its handle. */
@@ -500,6 +500,25 @@ CT_API int ct_adaptive_frame_info(CtAdaptiveFrame f, CtAdaptiveFrameInfo *out);
 CT_API int ct_adaptive_frame_download(CtAdaptiveFrame f, uint32_t which, void *host, size_t bytes);
 CT_API int ct_adaptive_frame_device_ptr(CtAdaptiveFrame f, uint32_t which, void **out);
 CT_API int ct_adaptive_frame_destroy(CtAdaptiveFrame f);
+
+/* The adaptive frame of one shard of a multi-GPU job.  ct_adaptive_frame_create_shard is ct_adaptive_frame_create for a handle
+ * of any shard_count >= 1 -- the same checks in the same order, only the refusal of a shard is absent (ct_adaptive_frame_create
+ * itself keeps it).  The live list at create is the handle's own pixels in ascending p: those with
+ * ct_tile_owner(x / 8, y / 8, shard_count) == shard_index, listed on the device by a ballot count per 64 pixels, a scan and a
+ * ranked write (no atomics: the same list on every run).  A pixel's samples depend on (x, y, subframe) alone and all live pixels
+ * hold one count, so the shard's rounds need nothing from the other shards:
+ *     on its own pixels mean, M2 and counts are, bit for bit and after the same number of completed rounds, those of the frame
+ *     ct_adaptive_frame_create makes on an unsharded handle of the same scene, pose, light and description;
+ *     a foreign pixel's 36 bytes are never written and stay all-zero bits for the frame's lifetime;
+ *     over the shards of one job `live`, `converged`, `capped`, `paths` and the handles' CtCounters::paths sum to that frame's.
+ * mean, M2 and counts stay whole-frame arrays (width * height float4, float4, uint32).  CtAdaptiveFrameInfo::pixels is the number
+ * of own pixels (pixels = live + converged + capped as before); width and height are the frame's.  A shard that owns no pixel is
+ * legal: create is CT_OK, nothing is live, update launches nothing.  Everything else -- update, raise_cap, info, download,
+ * device_ptr, destroy, the CT_E_STATE rules, counters, invariants, chunks and passes -- is the object above.  With
+ * shard_count == 1 the frame is ct_adaptive_frame_create's, allocations included.  Allocated at create for shard_count > 1:
+ * mean, M2, counts, width * height / 64 (rounded up) + 1 wave counts, and two live lists of exactly the own-pixel count of words
+ * each (none for a shard without pixels); CT_E_NOMEM leaves the handle as it was. */
+CT_API int ct_adaptive_frame_create_shard(CtHandle h, const CtAdaptiveFrameDesc *d, CtAdaptiveFrame *out);
 
 /* generatePoints (src/CUDA/pointGeneratorCamera.cu:20-42) + firstScatterPosition
  * (cloudFirstScatterMaterial.cu:8-29), launched over `count` threads by ScatterSampleCollector::collect
@@ -1313,6 +1332,43 @@ CT_API int ct_group_network_create(CtGroup g, const CtNetworkDesc *d, CtGroupNet
 CT_API int ct_group_network_destroy(CtGroupNetwork gn);   /* NULL is a no-op */
 CT_API int ct_group_network_render_accumulate(CtGroup g, CtGroupNetwork gn, const CtNetworkRender *p, uint32_t first_subframe_id,
                                               uint32_t count);
+
+/* The adaptive frame on a group: one shard frame per handle (ct_adaptive_frame_create_shard's rules; the first failing shard's
+ * code and message become the group's, the frames already made are destroyed and the group is left as it was), per shard a
+ * staging buffer of 9 * width * height 32-bit words [mean | M2 | counts] on the shard's device, and one landing buffer of that
+ * size on devices[0].  The shards must show one view: CT_E_STATE when a handle of the group was given another pose or light on
+ * its own.  Destroy it BEFORE the group.
+ * ct_group_adaptive_frame_update is ct_adaptive_frame_update(shard i, rounds) on every shard -- shards 1 .. N-1 each on a host
+ * thread of their own, shard 0 on the caller, because the entry point is synchronous -- and returns when all have finished;
+ * the first failing shard's code and message are reported then.  Shards do not wait for each other between rounds, and a shard
+ * whose list empties stops.  ct_group_adaptive_frame_raise_cap checks the cap once, before any shard changes, then raises it on
+ * every shard.  Both invalidate the merge.  ct_group_adaptive_frame_info: width, height, R, min, cap and tolerances as given;
+ * rounds and the three times are the largest over the shards (they run concurrently); pixels, live, converged, capped and paths
+ * are sums.  ct_group_adaptive_frame_shard gives shard `index`'s frame (owned by gf).
+ * ct_group_adaptive_frame_merge stages every shard's three arrays and reduces them onto devices[0] with the UNSIGNED MAXIMUM OF
+ * EACH 32-BIT WORD: a pixel's 36 bytes are non-zero on at most one shard, so the result is that shard's bytes for every bit
+ * pattern (-0.0, NaN payloads, denormals, the integer counts) -- deliberately not ct_group_merge's float sum.  One path for every
+ * device list: hipMemcpyPeerAsync into the landing buffer, then a max-into kernel on devices[0]'s stream; no collective.
+ * download and device_ptr serve the merged arrays on devices[0] (CT_ADAPTIVE_MEAN, _M2, _COUNTS) and merge first when needed;
+ * ct_tonemap_buffer and ct_is_converged_buffers on ct_group_handle(g, 0) take the pointers unchanged.
+ * So after any sequence of update and raise_cap calls the merged mean, M2 and counts are the bytes of the frame
+ * ct_adaptive_frame_create makes on one unsharded handle after the same calls, and rounds, pixels, live, converged, capped and
+ * paths of the info are that frame's -- for every N and every device list, shards that own nothing and partial edge tiles
+ * included.  The group's own image state (mean, M2, subframe count, merged flag) is not touched.  Nothing here has been run on
+ * more than one device; a device list that repeats a device takes the same path.
+ * CT_E_STATE: update and raise_cap after ct_group_set_camera or ct_group_set_light (the shards' own check; download still
+ * works).  CT_E_INVAL: a NULL argument (a NULL gf is answered without a device), an index >= the group's size, a wrong `which`
+ * or size, a cap that is not higher, no multiple of R or above 2^24.  Errors go to ct_group_last_error(g). */
+typedef struct CtGroupAdaptiveFrame_ *CtGroupAdaptiveFrame;
+CT_API int ct_group_adaptive_frame_create(CtGroup g, const CtAdaptiveFrameDesc *d, CtGroupAdaptiveFrame *out);
+CT_API int ct_group_adaptive_frame_update(CtGroupAdaptiveFrame gf, uint32_t rounds);
+CT_API int ct_group_adaptive_frame_raise_cap(CtGroupAdaptiveFrame gf, uint32_t max_samples);
+CT_API int ct_group_adaptive_frame_info(CtGroupAdaptiveFrame gf, CtAdaptiveFrameInfo *out);
+CT_API int ct_group_adaptive_frame_shard(CtGroupAdaptiveFrame gf, uint32_t index, CtAdaptiveFrame *out);   /* owned by gf */
+CT_API int ct_group_adaptive_frame_merge(CtGroupAdaptiveFrame gf);
+CT_API int ct_group_adaptive_frame_download(CtGroupAdaptiveFrame gf, uint32_t which, void *host, size_t bytes);
+CT_API int ct_group_adaptive_frame_device_ptr(CtGroupAdaptiveFrame gf, uint32_t which, void **out);
+CT_API int ct_group_adaptive_frame_destroy(CtGroupAdaptiveFrame gf);   /* NULL is a no-op; destroy before the group */
 
 /* ---- host-side helpers of the same path (pure CPU, no handle, no GPU) ------------------- */
 

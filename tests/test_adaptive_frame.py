@@ -215,7 +215,7 @@ def gpu_reference(name, **kw):
     return _GPU_RUNS[key]
 
 
-def assert_equals_reference(f, ref, cap=96):
+def assert_equals_reference(f, ref, cap=96, W=W, H=H):
     mean, m2, counts, history, capped = ref
     assert f.counts().tobytes() == counts.tobytes()
     assert f.mean().tobytes() == mean.tobytes()

@@ -183,9 +183,9 @@ def gpu_reference(name, **kw):
     return _GPU_RUNS[key]
 
 
-def assert_equals_reference(tr, c, name, ref):
+def assert_equals_reference(tr, c, name, ref, sets=SETS):
     tasks, converged_update, history, counters = ref
-    p = SETS[name]
+    p = sets[name]
     got_tasks, got_update = c.tasks()
     assert got_tasks.tobytes() == tasks.tobytes()
     assert got_update.tobytes() == converged_update.tobytes()

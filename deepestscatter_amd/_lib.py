@@ -38,6 +38,8 @@ EXPORTS = [
     "ct_adaptive_frame_create_shard", "ct_group_adaptive_frame_create", "ct_group_adaptive_frame_update", "ct_group_adaptive_frame_raise_cap",
     "ct_group_adaptive_frame_info", "ct_group_adaptive_frame_shard", "ct_group_adaptive_frame_merge", "ct_group_adaptive_frame_download",
     "ct_group_adaptive_frame_device_ptr", "ct_group_adaptive_frame_destroy",
+    "ct_bake_save", "ct_bake_file_info", "ct_bake_load", "ct_debug_volume_hash", "ct_bake_half", "ct_bake_format", "ct_bake_download_half",
+    "ct_debug_half_round",
 ]
 # ... and the declared symbols whose names have digits (the list above is matched by name pattern)
 DEBUG_EXPORTS = ["ct_debug_bf16_round"]
@@ -193,6 +195,66 @@ class CtBakeAdaptiveInfo(C.Structure):
         ("trace_ms", C.c_double),
         ("fold_ms", C.c_double),
         ("test_ms", C.c_double),
+    ]
+
+
+CT_BAKE_F32, CT_BAKE_F16 = 0, 1   # a bake's format (ct_bake_format, CtBakeFileHeader.format)
+CT_BAKE_FILE_MAGIC = b"CTBAKE\r\n"
+CT_BAKE_FILE_VERSION = 1
+
+
+class CtBakeFileHeader(C.Structure):
+    _fields_ = [
+        ("magic", C.c_uint8 * 8),
+        ("version", C.c_uint32),
+        ("header_bytes", C.c_uint32),
+        ("kind", C.c_uint32),
+        ("format", C.c_uint32),
+        ("traced", C.c_uint32),
+        ("adaptive", C.c_uint32),
+        ("grid", C.c_uint32 * 3),
+        ("azimuths", C.c_uint32),
+        ("cosines", C.c_uint32),
+        ("margin_texels", C.c_uint32),
+        ("entries", C.c_uint64),
+        ("stored_entries", C.c_uint64),
+        ("active_nodes", C.c_uint64),
+        ("light", C.c_float * 3),
+        ("axis_a", C.c_float * 3),
+        ("axis_b", C.c_float * 3),
+        ("dims", C.c_uint32 * 3),
+        ("sample_step_bits", C.c_uint32),
+        ("mean_free_path_bits", C.c_uint32),
+        ("cloud_size_bits", C.c_uint32),
+        ("estimator", C.c_int32),
+        ("tex_fixed8", C.c_uint32),
+        ("light_color_bits", C.c_uint32 * 3),
+        ("light_intensity_bits", C.c_uint32),
+        ("samples", C.c_uint32),
+        ("volume_hash", C.c_uint64),
+        ("paths", C.c_uint64),
+        ("round_samples", C.c_uint32),
+        ("max_samples", C.c_uint32),
+        ("zero_samples", C.c_uint32),
+        ("rel_tol_bits", C.c_uint32),
+        ("abs_tol_bits", C.c_uint32),
+        ("rounds", C.c_uint32),
+        ("converged", C.c_uint64),
+        ("capped", C.c_uint64),
+        ("reserved", C.c_uint8 * 32),
+    ]
+
+
+class CtBakeFileInfo(C.Structure):
+    _fields_ = [
+        ("header", CtBakeFileHeader),
+        ("file_bytes", C.c_uint64),
+        ("nodes_offset", C.c_uint64),
+        ("table_offset", C.c_uint64),
+        ("m2_offset", C.c_uint64),
+        ("counts_offset", C.c_uint64),
+        ("checksum_offset", C.c_uint64),
+        ("checksum", C.c_uint64),
     ]
 
 
@@ -362,6 +424,14 @@ def load():
         "ct_bake_adaptive_info": (i32, [vp, C.POINTER(CtBakeAdaptiveInfo)]),
         "ct_bake_download_counts": (i32, [vp, vp, C.c_size_t]),
         "ct_bake_download_m2": (i32, [vp, vp, C.c_size_t]),
+        "ct_bake_save": (i32, [vp, C.c_char_p]),
+        "ct_bake_file_info": (i32, [C.c_char_p, C.POINTER(CtBakeFileInfo)]),
+        "ct_bake_load": (i32, [vp, C.c_char_p, C.POINTER(vp)]),
+        "ct_debug_volume_hash": (i32, [vp, C.POINTER(C.c_uint64)]),
+        "ct_bake_half": (i32, [vp, vp, C.POINTER(vp)]),
+        "ct_bake_format": (i32, [vp, C.POINTER(u32)]),
+        "ct_bake_download_half": (i32, [vp, vp, C.c_size_t]),
+        "ct_debug_half_round": (C.c_uint16, [f32]),
         "ct_baked_render_subframe": (i32, [vp, vp, C.POINTER(CtNetworkRender), u32, vp]),
         "ct_baked_render_accumulate": (i32, [vp, vp, C.POINTER(CtNetworkRender), u32, u32]),
         "ct_baked_render_shard_subframe": (i32, [vp, vp, C.POINTER(CtNetworkRender), u32, vp]),

@@ -473,6 +473,19 @@ class CloudTracer:
         return Bake(self, None, grid, azimuths, cosines, sparse, compact,
                     adaptive=AdaptiveParams(int(round_samples), int(max_samples), float(rel_tol), float(abs_tol), int(zero_samples)))
 
+    def load_bake(self, path):
+        """ct_bake_load -> deepestscatter_amd.network.Bake: the bake that Bake.save wrote to `path`, on this tracer, which must
+        hold the same cloud, scene floats, estimator and CT_FLAG_TEX_FIXED8 bit.  A traced or adaptive bake continues from where
+        it was saved (Bake.trace_more / trace_adaptive_more); a bake saved under another light loads stale (info["current"] False)."""
+        from .network import Bake
+        return Bake.load(self, path)
+
+    def volume_hash(self) -> int:
+        """ct_debug_volume_hash: the hash of this tracer's quantised density that a bake file carries."""
+        v = C.c_uint64(0)
+        check(self.L.ct_debug_volume_hash(self.h, C.byref(v)), self.h)
+        return int(v.value)
+
     def bake_mask(self, grid):
         """ct_debug_bake_mask: the sparse bake's mask of a grid (Nx, Ny, Nz) on this handle, no network needed
         -> (cells uint8 [Nz-1, Ny-1, Nx-1], nodes uint8 [Nz, Ny, Nx], the active node indices uint32, ascending)."""

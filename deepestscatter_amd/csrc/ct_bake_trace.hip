@@ -147,6 +147,23 @@ __global__ __launch_bounds__(256) void bake_adaptive_fold_kernel(BakeTraceArgs a
     }
 }
 
+// ct_bake_load: the fold kernel's count without a fold.  Lane p tests the stored state of stored entry p < n of an active node;
+// an entry that stopped by the rule still passes it, so the lanes that fail are the live set the bake was left with.
+__global__ __launch_bounds__(256) void bake_adaptive_count_kernel(BakeTraceArgs a, BakeAdaptiveState st, uint32_t n,
+                                                                  uint32_t *__restrict__ wave_counts)
+{
+    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+    bool goes_on = false;
+    if (p < n) {
+        const uint64_t at = bake_trace_address(a, p);
+        goes_on = !bake_adaptive_converged(st, st.table[at], st.m2[at], st.counts[at]);
+    }
+    const uint64_t mask = __builtin_amdgcn_ballot_w64(goes_on);
+    if ((threadIdx.x & 63u) == 0u && p < ((n + 63u) & ~63u)) {
+        wave_counts[p >> 6] = (uint32_t)__popcll(mask);
+    }
+}
+
 // first_scatter_scan_kernel (ct_kernels.hip) for the live list's waves: counts[w] becomes the number of survivors in the waves
 // before w, counts[n_waves] their total.  One block.
 __global__ __launch_bounds__(1024) void bake_adaptive_scan_kernel(uint32_t *__restrict__ counts, uint32_t n_waves)
@@ -203,6 +220,12 @@ hipError_t launch_bake_adaptive_fold(const BakeTraceArgs &a, const float4 *frame
                                      const BakeAdaptiveState &st, uint32_t *waves, hipStream_t stream)
 {
     hipLaunchKernelGGL(bake_adaptive_fold_kernel, dim3((a.n + 255u) / 256u), dim3(256), 0, stream, a, frames, stride, passes, done, st, waves);
+    return hipGetLastError();
+}
+
+hipError_t launch_bake_adaptive_count(const BakeTraceArgs &a, const BakeAdaptiveState &st, uint32_t n, uint32_t *waves, hipStream_t stream)
+{
+    hipLaunchKernelGGL(bake_adaptive_count_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, a, st, n, waves);
     return hipGetLastError();
 }
 

@@ -265,6 +265,7 @@ struct BakeTable {
     float lx, ly, lz;                // the light travel direction the table was baked for
     float ax, ay, az, bx, by, bz;    // the azimuth frame
     const uint32_t *slots;           // ct_network_bake_compact: the block of node (z Ny + y) Nx + x in the table; nullptr: dense addressing
+    const uint16_t *half;            // ct_bake_half: the table as binary16 in the same order (`table` is nullptr then); nullptr: float32
 };
 // The bake's own kernels: aux[i] = value; table[i * stride + k] = out[i]; and (ct_debug_bake_lookup) the lookup of caller-supplied
 // records.  launch_baked_compose forms a band's pixels as launch_network_compose does (the kernels share everything behind a
@@ -296,6 +297,12 @@ hipError_t launch_bake_store_list(const float *out, const uint32_t *list, uint64
                                   uint32_t stride, uint32_t k, hipStream_t stream);
 hipError_t launch_baked_compose(const DevScene &sc, const PixelBand &band, const FlightTemps &t, const BakeTable &table, const NetCompose &c,
                                 const ComposeTarget &dst, const uint32_t *frozen, hipStream_t stream);
+// Bake files and half tables (ct_bake_file.hip).  launch_volume_hash: *hash (zeroed by the caller) += the volume hash of
+// include/cloudtrace.h, "bake files", over `count` texels, in whatever order the waves run.  launch_bake_half_convert: half[i] =
+// half_round_bits(table[i]) for i < count, one lane per value; refused[0] (zeroed) counts the values ct_bake_half refuses and
+// refused[1] (0xffffffff) becomes the smallest index of one.
+hipError_t launch_volume_hash(const uint8_t *texels, uint64_t count, unsigned long long *hash, hipStream_t stream);
+hipError_t launch_bake_half_convert(const float *table, uint32_t count, uint16_t *half, uint32_t *refused, hipStream_t stream);
 // ct_bake_traced (ct_bake_trace.hip): the stored entries [first, first + n) of a bake as point tasks and their fold.  list:
 // nullptr for a dense bake (stored entry = virtual entry), otherwise the active nodes, whose blocks the stored entries count
 // through.  axes: the position nodes of x, y, z; directions: nphi x nc x 3.  launch_bake_trace_tasks writes primary[2 i],
@@ -327,6 +334,9 @@ struct BakeAdaptiveState {
 };
 hipError_t launch_bake_adaptive_fold(const BakeTraceArgs &a, const float4 *frames, uint32_t stride, uint32_t passes, uint32_t done,
                                      const BakeAdaptiveState &st, uint32_t *waves, hipStream_t stream);
+// ct_bake_load: the count pass alone over the stored entries [0, n) of active nodes (a.first == 0, a.live == nullptr): waves[w] =
+// the lanes of wave w whose stored state fails the rule.  Scan and compact follow as behind a round.
+hipError_t launch_bake_adaptive_count(const BakeTraceArgs &a, const BakeAdaptiveState &st, uint32_t n, uint32_t *waves, hipStream_t stream);
 hipError_t launch_bake_adaptive_scan(uint32_t *waves, uint32_t n_live, hipStream_t stream);
 hipError_t launch_bake_adaptive_compact(const BakeTraceArgs &a, const BakeAdaptiveState &st, const uint32_t *live_in, uint32_t n_live,
                                         const uint32_t *waves, uint32_t *live_out, hipStream_t stream);

@@ -3789,7 +3789,17 @@ CT_DEV float bake_azimuth(const BakeTable &t, f3 d)
 // is slots[node].  The two x-neighbours of a corner pair are adjacent words, so the eight slots are four loads of 8 bytes
 // (4-byte aligned), all issued before the first table load: the index costs one memory round trip per lookup, not eight.  An
 // inactive corner reads the zero block, so there is no branch on activity.
-template <bool COMPACT>
+// HALF (ct_bake_half): the table is binary16 in the same order, and the pair of polar nodes is two adjacent binary16 values at
+// half index (probe + j) Nc + k0 -- 4 bytes that are only 2-byte aligned when Nc or k0 is odd, which the copy from a uint16_t
+// pointer tells the compiler -- widened exactly (v_cvt_f32_f16) before the first lerp.  Everything else is the same code.
+CT_DEV float2 bake_half_pair(const uint16_t *p)
+{
+    _Float16 pair[2];
+    __builtin_memcpy(pair, p, sizeof pair);
+    return make_float2((float)pair[0], (float)pair[1]);
+}
+
+template <bool COMPACT, bool HALF = false>
 CT_DEV float bake_lookup(const DevScene &sc, const BakeTable &t, f3 w, f3 d)
 {
     uint32_t x0, y0, z0, k0;
@@ -3821,8 +3831,13 @@ CT_DEV float bake_lookup(const DevScene &sc, const BakeTable &t, f3 w, f3 d)
         // (dense: entries <= 2^26; compact: stored entries <= 2^26)
         const uint32_t probe = (COMPACT ? slot[q] : (z * t.ny + y) * t.nx + x) * t.nphi;
         float2 a, b;
-        __builtin_memcpy(&a, t.table + (size_t)(probe + j0) * t.nc + k0, sizeof a);
-        __builtin_memcpy(&b, t.table + (size_t)(probe + j1) * t.nc + k0, sizeof b);
+        if constexpr (HALF) {
+            a = bake_half_pair(t.half + (size_t)(probe + j0) * t.nc + k0);
+            b = bake_half_pair(t.half + (size_t)(probe + j1) * t.nc + k0);
+        } else {
+            __builtin_memcpy(&a, t.table + (size_t)(probe + j0) * t.nc + k0, sizeof a);
+            __builtin_memcpy(&b, t.table + (size_t)(probe + j1) * t.nc + k0, sizeof b);
+        }
         corner[q] = lerp_(lerp_(a.x, a.y, wc), lerp_(b.x, b.y, wc), wphi);
     }
     const float c00 = lerp_(corner[0], corner[1], wx), c10 = lerp_(corner[2], corner[3], wx);
@@ -3830,7 +3845,7 @@ CT_DEV float bake_lookup(const DevScene &sc, const BakeTable &t, f3 w, f3 d)
     return lerp_(lerp_(c00, c10, wy), lerp_(c01, c11, wy), wz);
 }
 
-template <bool COMPACT>
+template <bool COMPACT, bool HALF = false>
 __global__ __launch_bounds__(256) void bake_lookup_kernel(DevScene sc, BakeTable t, const float *__restrict__ positions,
                                                           const float *__restrict__ directions, uint32_t count, float *__restrict__ out)
 {
@@ -3839,23 +3854,25 @@ __global__ __launch_bounds__(256) void bake_lookup_kernel(DevScene sc, BakeTable
         return;
     }
     const size_t at = 3 * (size_t)i;
-    out[i] = bake_lookup<COMPACT>(sc, t, mk3(positions[at], positions[at + 1], positions[at + 2]),
-                                  mk3(directions[at], directions[at + 1], directions[at + 2]));
+    out[i] = bake_lookup<COMPACT, HALF>(sc, t, mk3(positions[at], positions[at + 1], positions[at + 2]),
+                                        mk3(directions[at], directions[at + 1], directions[at + 2]));
 }
 
 hipError_t launch_bake_lookup(const DevScene &sc, const BakeTable &t, const float *positions, const float *directions, uint32_t count,
                               float *out, hipStream_t stream)
 {
-    hipLaunchKernelGGL(t.slots ? bake_lookup_kernel<true> : bake_lookup_kernel<false>, dim3((count + 255u) / 256u), dim3(256), 0, stream, sc,
-                       t, positions, directions, count, out);
+    static constexpr decltype(&bake_lookup_kernel<false, false>) lookups[4] = { bake_lookup_kernel<false, false>, bake_lookup_kernel<true, false>,
+                                                                                bake_lookup_kernel<false, true>, bake_lookup_kernel<true, true> };
+    hipLaunchKernelGGL(lookups[2 * (t.half != nullptr) + (t.slots != nullptr)], dim3((count + 255u) / 256u), dim3(256), 0, stream, sc, t,
+                       positions, directions, count, out);
     return hipGetLastError();
 }
 
 // The band's pixels with a record's output looked up in the table at the record's world position (the flight's temporary) and
 // d2, made again from the pixel as first_scatter_compact_kernel makes it: no ballot, no rank, no wave offsets.  ACCUMULATE,
 // DIRECT and TILES mean what they mean for network_compose_kernel, and everything behind the output is the shared compose_* code.
-// COMPACT: the table of a compact bake (bake_lookup).
-template <bool ACCUMULATE, bool DIRECT, bool TILES, bool COMPACT>
+// COMPACT: the table of a compact bake, HALF: of a half bake (bake_lookup).
+template <bool ACCUMULATE, bool DIRECT, bool TILES, bool COMPACT, bool HALF = false>
 __global__ __launch_bounds__(256) void baked_compose_kernel(DevScene sc, PixelBand b, const float4 *__restrict__ found, BakeTable t,
                                                             NetCompose c, float4 *__restrict__ frame, float4 *__restrict__ mean,
                                                             float4 *__restrict__ m2, uint32_t subframe_id,
@@ -3877,7 +3894,7 @@ __global__ __launch_bounds__(256) void baked_compose_kernel(DevScene sc, PixelBa
     float4 v = compose_miss();
     if (f.w != 0.f) {
         const f3 dir = normalize3(primary_direction(sc, x, y));
-        v = compose_value<DIRECT>(c, bake_lookup<COMPACT>(sc, t, mk3(f.x, f.y, f.z), dir), direct, i);
+        v = compose_value<DIRECT>(c, bake_lookup<COMPACT, HALF>(sc, t, mk3(f.x, f.y, f.z), dir), direct, i);
     }
     compose_store<ACCUMULATE>(v, at, frame, mean, m2, subframe_id);
 }
@@ -3885,15 +3902,16 @@ __global__ __launch_bounds__(256) void baked_compose_kernel(DevScene sc, PixelBa
 hipError_t launch_baked_compose(const DevScene &sc, const PixelBand &band, const FlightTemps &t, const BakeTable &table, const NetCompose &c,
                                 const ComposeTarget &dst, const uint32_t *frozen, hipStream_t stream)
 {
-#define K(ACCUMULATE, TILES, COMPACT) \
-    baked_compose_kernel<ACCUMULATE, false, TILES, COMPACT>, baked_compose_kernel<ACCUMULATE, true, TILES, COMPACT>
-#define K4(COMPACT) K(false, false, COMPACT), K(false, true, COMPACT), K(true, false, COMPACT), K(true, true, COMPACT)
-    static constexpr decltype(&baked_compose_kernel<false, false, false, false>) composes[16] = { K4(false), K4(true) };
+#define K(ACCUMULATE, TILES, COMPACT, HALF) \
+    baked_compose_kernel<ACCUMULATE, false, TILES, COMPACT, HALF>, baked_compose_kernel<ACCUMULATE, true, TILES, COMPACT, HALF>
+#define K4(COMPACT, HALF) K(false, false, COMPACT, HALF), K(false, true, COMPACT, HALF), K(true, false, COMPACT, HALF), K(true, true, COMPACT, HALF)
+    static constexpr decltype(&baked_compose_kernel<false, false, false, false, false>) composes[32] = { K4(false, false), K4(true, false),
+                                                                                                         K4(false, true), K4(true, true) };
 #undef K4
 #undef K
     const bool accumulate = dst.frame == nullptr, tiles = band.tiles != nullptr, direct = t.direct != nullptr;
-    const bool compact = table.slots != nullptr;
-    hipLaunchKernelGGL(composes[8 * compact + 4 * accumulate + 2 * tiles + direct], dim3((band.n + 255u) / 256u), dim3(256), 0, stream, sc, band,
+    const bool compact = table.slots != nullptr, half = table.half != nullptr;
+    hipLaunchKernelGGL(composes[16 * half + 8 * compact + 4 * accumulate + 2 * tiles + direct], dim3((band.n + 255u) / 256u), dim3(256), 0, stream, sc, band,
                        (const float4 *)t.found, table, c, dst.frame, dst.mean, dst.m2, dst.subframe_id, frozen, (const float4 *)t.direct);
     return hipGetLastError();
 }

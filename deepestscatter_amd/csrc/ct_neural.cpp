@@ -5,8 +5,17 @@
 // estimator instead: its two kernels are ct_bake_trace.hip, its launches ct_api.cpp's point_launch.  The adaptive traced bake
 // (ct_bake_traced_adaptive) traces in rounds, keeps m2 and count per entry and stops entries by the reference's rule: its fold,
 // scan and compaction kernels are in ct_bake_trace.hip too.
+// Bake files (ct_bake_save, ct_bake_load) and half tables (ct_bake_half) are at the end of the bake's part; the file's parser is
+// the device-free ct_bakefile.hpp, their two kernels ct_bake_file.hip.
+#include <cerrno>
 #include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <new>
 
+#include <unistd.h>
+
+#include "ct_bakefile.hpp"
 #include "ct_handle.hpp"
 #include "ct_network.hpp"
 
@@ -375,6 +384,7 @@ static int net_ensure_tiles(CtHandle h)
 struct BakeState {
     float l[3] = {}, a[3] = {}, b[3] = {};   // the light the table holds and the azimuth frame
     uint64_t epoch = 0;                      // the handle's light epoch at the bake
+    uint32_t light_bits[4] = {};             // ... and the bits of its light colour and intensity then (the bake file's header)
     double gather_ms = 0, network_ms = 0, mask_ms = 0;
     uint32_t samples = 0;                    // a traced bake: experiments folded into every stored entry of an active node
     uint64_t paths = 0;
@@ -416,6 +426,9 @@ struct CtBake_ : BakeState {
     CtBakeAdaptive ap{};                     // (max_samples: as given; BakeState::cap is the one in force)
     DevBuf<float> d_m2;
     DevBuf<uint32_t> d_counts, d_live[2], d_waves;
+    // ct_bake_half: the stored table as binary16 in d_half, no d_table.  Final: nothing bakes or traces into it.
+    bool half = false;
+    DevBuf<uint16_t> d_half;
 };
 
 static uint64_t bake_probes_total(const CtBake_ *b)
@@ -474,12 +487,16 @@ static void bake_frame(CtHandle h, CtBake_ *b)
         b->b[axis] = (float)bb[axis];
     }
     b->epoch = h->light_epoch;
+    for (int c = 0; c < 3; c++) {
+        b->light_bits[c] = float_bits(h->scene.light_color[c]);
+    }
+    b->light_bits[3] = float_bits(h->scene.light_intensity);
 }
 
 static BakeTable bake_table(const CtBake_ *b)
 {
     return { b->d_table, b->grid[0], b->grid[1], b->grid[2], b->azimuths, b->cosines, b->l[0], b->l[1], b->l[2],
-             b->a[0], b->a[1], b->a[2], b->b[0], b->b[1], b->b[2], b->d_slots };
+             b->a[0], b->a[1], b->a[2], b->b[0], b->b[1], b->b[2], b->d_slots, b->d_half };
 }
 
 // The mask of a probe grid on h (include/cloudtrace.h, "the sparse bake"): its device memory, allocated by bake_mask_reserve
@@ -1171,9 +1188,30 @@ extern "C" int ct_bake_storage_info(CtBake b, CtBakeStorageInfo *out)
     out->compact = b->compact ? 1u : 0u;
     out->slots = b->compact ? b->active + 1u : nodes;
     out->stored_entries = b->stored;
-    out->table_bytes = 4u * b->stored;
+    out->table_bytes = (b->half ? 2u : 4u) * b->stored;
     out->index_bytes = b->compact ? 4u * nodes : 0u;
     return CT_OK;
+}
+
+// The stored table as b->stored floats on the host: a half bake's values widened, which is exact.
+static int bake_stored_floats(CtHandle h, const CtBake_ *b, float *out)
+{
+    if (!b->half) {
+        HIPCHK(h, hipMemcpy(out, b->d_table, (size_t)b->stored * sizeof(float), hipMemcpyDeviceToHost));
+        return CT_OK;
+    }
+    std::vector<uint16_t> bits((size_t)b->stored);
+    HIPCHK(h, hipMemcpy(bits.data(), b->d_half, bits.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < bits.size(); i++) {
+        out[i] = half_widen(bits[i]);
+    }
+    return CT_OK;
+}
+
+// A half bake is final (include/cloudtrace.h, "half tables").
+static int bake_half_final(CtHandle h, CtBake b, const char *who)
+{
+    return b->half ? fail(h, CT_E_INVAL, "%s: a half bake is final; bake again from float32 and take ct_bake_half of that", who) : CT_OK;
 }
 
 extern "C" int ct_bake_slots(CtBake b, uint32_t *slots_host_out, size_t count)
@@ -1207,8 +1245,7 @@ extern "C" int ct_bake_download_stored(CtBake b, float *table_host_out, size_t c
         return fail(h, CT_E_INVAL, "ct_bake_download_stored: need an array of exactly %llu floats", (unsigned long long)b->stored);
     }
     NEED(h);
-    HIPCHK(h, hipMemcpy(table_host_out, b->d_table, count * sizeof(float), hipMemcpyDeviceToHost));
-    return CT_OK;
+    return bake_stored_floats(h, b, table_host_out);
 }
 
 extern "C" int ct_bake_sparse_info(CtBake b, CtBakeSparseInfo *out)
@@ -1306,6 +1343,10 @@ extern "C" int ct_bake_update(CtHandle h, CtNetwork n, CtBake b)
     if (b->h != h) {
         return fail(h, CT_E_INVAL, "%s: the bake was made on another handle", who);
     }
+    rc = bake_half_final(h, b, who);
+    if (rc != CT_OK) {
+        return rc;
+    }
     if (b->traced) {
         return fail(h, CT_E_INVAL, "%s: a traced bake holds no network's outputs; %s traces it again", who,
                     b->adaptive ? "ct_bake_retrace_adaptive" : "ct_bake_retrace");
@@ -1343,6 +1384,9 @@ static int bake_trace_checks(CtHandle h, CtBake b, uint32_t samples, const char 
     NEED_NOFLUSH(h);
     if (b->h != h) {
         return fail(h, CT_E_INVAL, "%s: the bake was made on another handle", who);
+    }
+    if (b->half) {
+        return bake_half_final(h, b, who);
     }
     if (!b->traced) {
         return fail(h, CT_E_INVAL, "%s: the bake holds a network's outputs; ct_bake_update bakes it again", who);
@@ -1463,6 +1507,9 @@ static int bake_adaptive_checks(CtHandle h, CtBake b, const char *who)
     NEED_NOFLUSH(h);
     if (b->h != h) {
         return fail(h, CT_E_INVAL, "%s: the bake was made on another handle", who);
+    }
+    if (b->half) {
+        return bake_half_final(h, b, who);
     }
     if (!b->adaptive) {
         return fail(h, CT_E_INVAL, "%s: the bake was not made by ct_bake_traced_adaptive; %s", who,
@@ -1678,7 +1725,10 @@ extern "C" int ct_bake_download(CtBake b, float *table_host_out, size_t count)
         const size_t block = (size_t)b->azimuths * b->cosines, nodes = (size_t)b->grid[0] * b->grid[1] * b->grid[2];
         std::vector<float> stored((size_t)b->stored);
         std::vector<uint32_t> slots(nodes);
-        HIPCHK(h, hipMemcpy(stored.data(), b->d_table, stored.size() * sizeof(float), hipMemcpyDeviceToHost));
+        const int rc = bake_stored_floats(h, b, stored.data());
+        if (rc != CT_OK) {
+            return rc;
+        }
         HIPCHK(h, hipMemcpy(slots.data(), b->d_slots, nodes * sizeof(uint32_t), hipMemcpyDeviceToHost));
         for (size_t node = 0; node < nodes; node++) {
             if (slots[node] > b->active) {
@@ -1689,8 +1739,7 @@ extern "C" int ct_bake_download(CtBake b, float *table_host_out, size_t count)
         }
         return CT_OK;
     }
-    HIPCHK(h, hipMemcpy(table_host_out, b->d_table, count * sizeof(float), hipMemcpyDeviceToHost));
-    return CT_OK;
+    return bake_stored_floats(h, b, table_host_out);
 }
 
 // A bake that belongs to h and holds h's light: CT_E_INVAL / CT_E_STATE otherwise.
@@ -1702,7 +1751,7 @@ static int bake_stale(CtHandle h, CtBake b, const char *who)
 {
     if (b->epoch != h->light_epoch) {
         return fail(h, CT_E_STATE, "%s: the handle's light has changed since the bake; %s", who,
-                    b->adaptive ? "ct_bake_retrace_adaptive traces it again" : b->traced ? "ct_bake_retrace traces it again"
+                    b->half ? "a half bake is final: bake again from float32" : b->adaptive ? "ct_bake_retrace_adaptive traces it again" : b->traced ? "ct_bake_retrace traces it again"
                                                                                            : "ct_bake_update bakes it again");
     }
     return CT_OK;
@@ -1731,6 +1780,490 @@ extern "C" int ct_debug_bake_lookup(CtHandle h, CtBake b, const float *positions
     }
     HIPCHK(h, launch_bake_lookup(h->dev, bake_table(b), positions_dev, directions_dev, count, out_dev, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    return CT_OK;
+}
+
+// ---- half tables (ct_bake_half) and bake files (ct_bake_save, ct_bake_file_info, ct_bake_load): DESIGN 8 f-18 ----------------------
+extern "C" uint16_t ct_debug_half_round(float x)
+{
+    return half_round_bits(float_bits(x));
+}
+
+extern "C" int ct_bake_format(CtBake b, uint32_t *format_out)
+{
+    if (!b || !format_out) {
+        return fail(b ? b->h : nullptr, CT_E_INVAL, "ct_bake_format: need a bake and format_out");
+    }
+    *format_out = b->half ? CT_BAKE_F16 : CT_BAKE_F32;
+    return CT_OK;
+}
+
+extern "C" int ct_bake_download_half(CtBake b, uint16_t *table_host_out, size_t count)
+{
+    if (!b) {
+        return fail(nullptr, CT_E_INVAL, "ct_bake_download_half: null bake");
+    }
+    CtHandle h = b->h;
+    if (!b->half) {
+        return fail(h, CT_E_INVAL, "ct_bake_download_half: a float32 bake holds no binary16 table; ct_bake_half makes one");
+    }
+    if (!table_host_out || count != b->stored) {
+        return fail(h, CT_E_INVAL, "ct_bake_download_half: need an array of exactly %llu values", (unsigned long long)b->stored);
+    }
+    NEED(h);
+    HIPCHK(h, hipMemcpy(table_host_out, b->d_half, count * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    return CT_OK;
+}
+
+// What a bake is apart from its table, m2, counts and live lists: the scalars, and copies of the node bytes, the list, the
+// slots and the probe and direction tables.  Everything is allocated before the first copy; the copies are enqueued on h's stream.
+template <typename T>
+static bool bake_dup_alloc(DevBuf<T> &dst, const DevBuf<T> &src)
+{
+    return src.capacity() == 0u || dst.alloc(src.capacity()) == hipSuccess;
+}
+template <typename T>
+static hipError_t bake_dup_copy(CtHandle h, DevBuf<T> &dst, const DevBuf<T> &src)
+{
+    return src.capacity() == 0u ? hipSuccess : hipMemcpyAsync(dst, src, src.capacity() * sizeof(T), hipMemcpyDeviceToDevice, h->stream);
+}
+
+extern "C" int ct_bake_half(CtHandle h, CtBake src, CtBake *out)
+{
+    const char *const who = "ct_bake_half";
+    if (!h) {
+        return fail(nullptr, CT_E_INVAL, "null handle");
+    }
+    if (!src || !out) {
+        return fail(h, CT_E_INVAL, "%s: need a bake and out", who);
+    }
+    *out = nullptr;
+    NEED_NOFLUSH(h);
+    int rc = bake_foreign(h, src, who);
+    if (rc == CT_OK) {
+        rc = bake_half_final(h, src, who);
+    }
+    if (rc == CT_OK) {
+        rc = flush(h);
+    }
+    if (rc != CT_OK) {
+        return rc;
+    }
+    CtBake_ *b = new CtBake_();
+    static_cast<BakeState &>(*b) = *src;   // the frame, its epoch, samples and paths; the times and the adaptive state are not carried
+    b->gather_ms = b->network_ms = b->mask_ms = b->trace_ms = b->fold_ms = b->test_ms = 0;
+    b->cap = b->rounds = 0;
+    b->live = 0;
+    b->live_cur = 0;
+    b->h = h;
+    b->device = src->device;
+    std::copy_n(src->grid, 3, b->grid);
+    b->azimuths = src->azimuths;
+    b->cosines = src->cosines;
+    b->entries = src->entries;
+    std::copy_n(src->cosine, 64, b->cosine);
+    b->sparse = src->sparse;
+    b->margin = src->margin;
+    b->active = src->active;
+    b->compact = src->compact;
+    b->stored = src->stored;
+    b->traced = src->traced;
+    b->half = true;
+    DevBuf<uint32_t> refused;   // [0] the values refused, [1] the first of them
+    if (b->d_half.alloc((size_t)b->stored) != hipSuccess || refused.alloc(2) != hipSuccess || !bake_dup_alloc(b->d_nodes, src->d_nodes) ||
+        !bake_dup_alloc(b->d_list, src->d_list) || !bake_dup_alloc(b->d_slots, src->d_slots) || !bake_dup_alloc(b->d_probe, src->d_probe) ||
+        !bake_dup_alloc(b->d_dirs, src->d_dirs)) {
+        (void)hipGetLastError();
+        delete b;
+        return fail(h, CT_E_NOMEM, "%s: no device memory for a half table of %llu stored entries", who, (unsigned long long)src->stored);
+    }
+    uint32_t count = 0, first = 0;
+    rc = drained(h, [&]() -> int {
+        HIPCHK(h, bake_dup_copy(h, b->d_nodes, src->d_nodes));
+        HIPCHK(h, bake_dup_copy(h, b->d_list, src->d_list));
+        HIPCHK(h, bake_dup_copy(h, b->d_slots, src->d_slots));
+        HIPCHK(h, bake_dup_copy(h, b->d_probe, src->d_probe));
+        HIPCHK(h, bake_dup_copy(h, b->d_dirs, src->d_dirs));
+        HIPCHK(h, hipMemsetAsync(refused, 0, sizeof(uint32_t), h->stream));
+        HIPCHK(h, hipMemsetAsync(refused + 1, 0xff, sizeof(uint32_t), h->stream));
+        HIPCHK(h, launch_bake_half_convert(src->d_table, (uint32_t)b->stored, b->d_half, refused, h->stream));   // (stored <= 2^26)
+        HIPCHK(h, hipMemcpyAsync(&count, refused, sizeof count, hipMemcpyDeviceToHost, h->stream));             // the one 4-byte read
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (count != 0u) {   // (only the refusal reads a second word)
+            HIPCHK(h, hipMemcpy(&first, refused + 1, sizeof first, hipMemcpyDeviceToHost));
+        }
+        return CT_OK;
+    });
+    if (rc == CT_OK && count != 0u) {
+        rc = fail(h, CT_E_INVAL, "%s: %u stored values are NaN, infinite or round to an infinity (|v| >= 65520), the first at stored index %u", who,
+                  count, first);
+    }
+    if (rc != CT_OK) {
+        delete b;
+        return rc;
+    }
+    *out = b;
+    return CT_OK;
+}
+
+// The handle's volume hash, reduced on the device in whatever order the waves run (the sum is exact).  Nothing is in flight.
+static int bake_volume_hash(CtHandle h, uint64_t *hash_out)
+{
+    DevBuf<unsigned long long> sum;
+    HIPCHK(h, sum.alloc(1));
+    unsigned long long host = 0;
+    const uint64_t texels = (uint64_t)h->scene.dims[0] * h->scene.dims[1] * h->scene.dims[2];
+    return drained(h, [&]() -> int {
+        HIPCHK(h, hipMemsetAsync(sum, 0, sizeof host, h->stream));
+        HIPCHK(h, launch_volume_hash(h->d_density, texels, sum, h->stream));
+        HIPCHK(h, hipMemcpyAsync(&host, sum, sizeof host, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        *hash_out = host;
+        return CT_OK;
+    });
+}
+
+extern "C" int ct_debug_volume_hash(CtHandle h, uint64_t *hash_out)
+{
+    if (!h) {
+        return fail(nullptr, CT_E_INVAL, "null handle");
+    }
+    if (!hash_out) {
+        return fail(h, CT_E_INVAL, "ct_debug_volume_hash: need hash_out");
+    }
+    NEED(h);
+    return bake_volume_hash(h, hash_out);
+}
+
+extern "C" int ct_bake_save(CtBake b, const char *path)
+{
+    const char *const who = "ct_bake_save";
+    if (!b || !path) {
+        return fail(b ? b->h : nullptr, CT_E_INVAL, "%s: need a bake and a path", who);
+    }
+    CtHandle h = b->h;
+    NEED(h);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    CtBakeFileInfo fi{};
+    CtBakeFileHeader &hd = fi.header;
+    std::memcpy(hd.magic, CT_BAKE_FILE_MAGIC, 8);
+    hd.version = CT_BAKE_FILE_VERSION;
+    hd.header_bytes = sizeof hd;
+    hd.kind = b->compact ? CT_BAKE_COMPACT : b->sparse ? CT_BAKE_SPARSE : CT_BAKE_DENSE;
+    hd.format = b->half ? CT_BAKE_F16 : CT_BAKE_F32;
+    hd.traced = b->traced ? 1u : 0u;
+    hd.adaptive = b->adaptive ? 1u : 0u;
+    const uint64_t nodes = (uint64_t)b->grid[0] * b->grid[1] * b->grid[2];
+    for (int axis = 0; axis < 3; axis++) {
+        hd.grid[axis] = b->grid[axis];
+        hd.light[axis] = b->l[axis];
+        hd.axis_a[axis] = b->a[axis];
+        hd.axis_b[axis] = b->b[axis];
+        hd.dims[axis] = h->scene.dims[axis];
+        hd.light_color_bits[axis] = b->light_bits[axis];
+    }
+    hd.light_intensity_bits = b->light_bits[3];
+    hd.azimuths = b->azimuths;
+    hd.cosines = b->cosines;
+    hd.margin_texels = b->margin;
+    hd.entries = b->entries;
+    hd.stored_entries = b->stored;
+    hd.active_nodes = b->sparse ? b->active : nodes;
+    hd.sample_step_bits = float_bits(h->scene.sample_step);
+    hd.mean_free_path_bits = float_bits(h->scene.mean_free_path_m);
+    hd.cloud_size_bits = float_bits(h->scene.cloud_size_m);
+    hd.estimator = h->scene.estimator;
+    hd.tex_fixed8 = (h->scene.flags & CT_FLAG_TEX_FIXED8) ? 1u : 0u;
+    if (b->traced) {
+        hd.samples = b->samples;
+        hd.paths = b->paths;
+    }
+    if (b->adaptive) {
+        hd.round_samples = b->ap.round_samples;
+        hd.max_samples = b->cap;
+        hd.zero_samples = b->ap.zero_samples;
+        hd.rel_tol_bits = float_bits(b->ap.rel_tol);
+        hd.abs_tol_bits = float_bits(b->ap.abs_tol);
+        hd.rounds = b->rounds;
+        hd.capped = b->live;
+        hd.converged = b->rounds != 0u ? bake_trace_total(b) - b->live : 0u;
+    }
+    int rc = bake_volume_hash(h, &hd.volume_hash);
+    if (rc != CT_OK) {
+        return rc;
+    }
+    bakefile_layout(&fi);
+    std::vector<uint8_t> bytes;
+    try {
+        bytes.assign((size_t)fi.file_bytes, 0);
+    } catch (const std::bad_alloc &) {
+        return fail(h, CT_E_NOMEM, "%s: no host memory for a file of %llu bytes", who, (unsigned long long)fi.file_bytes);
+    }
+    std::memcpy(bytes.data(), &hd, sizeof hd);
+    if (b->sparse) {
+        HIPCHK(h, hipMemcpy(bytes.data() + fi.nodes_offset, b->d_nodes, (size_t)nodes, hipMemcpyDeviceToHost));
+    }
+    if (b->half) {
+        HIPCHK(h, hipMemcpy(bytes.data() + fi.table_offset, b->d_half, (size_t)b->stored * 2u, hipMemcpyDeviceToHost));
+    } else {
+        HIPCHK(h, hipMemcpy(bytes.data() + fi.table_offset, b->d_table, (size_t)b->stored * 4u, hipMemcpyDeviceToHost));
+    }
+    if (b->adaptive) {
+        HIPCHK(h, hipMemcpy(bytes.data() + fi.m2_offset, b->d_m2, (size_t)b->stored * 4u, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(bytes.data() + fi.counts_offset, b->d_counts, (size_t)b->stored * 4u, hipMemcpyDeviceToHost));
+    }
+    const uint64_t sum = fnv1a64(bytes.data(), (size_t)fi.checksum_offset);
+    std::memcpy(bytes.data() + fi.checksum_offset, &sum, 8);
+    // through a temporary name in the same directory, then renamed: no partial file ever stands under `path`
+    const std::string tmp = std::string(path) + ".tmp" + std::to_string((long long)getpid());
+    FILE *f = std::fopen(tmp.c_str(), "wb");
+    if (!f) {
+        return fail(h, CT_E_INVAL, "%s: cannot create %s: %s", who, tmp.c_str(), std::strerror(errno));
+    }
+    const bool written = std::fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size();
+    const bool closed = std::fclose(f) == 0;
+    if (!written || !closed || std::rename(tmp.c_str(), path) != 0) {
+        const int err = errno;
+        std::remove(tmp.c_str());
+        return fail(h, CT_E_INVAL, "%s: cannot write %s: %s", who, path, std::strerror(err));
+    }
+    return CT_OK;
+}
+
+// A whole file read and checked by the device-free parser.  h: whose error text a failure sets (NULL: the thread's).
+static int bake_file_read(CtHandle h, const char *path, const char *who, std::vector<uint8_t> &data, CtBakeFileInfo *fi)
+{
+    FILE *f = std::fopen(path, "rb");
+    if (!f) {
+        return fail(h, CT_E_INVAL, "%s: cannot open %s: %s", who, path, std::strerror(errno));
+    }
+    // (the largest valid file: header, 2^24 node bytes, three sections of 2^26 words)
+    const size_t limit = sizeof(CtBakeFileHeader) + (1u << 24) + 3u * ((size_t)4 << 26) + 64u;
+    bool ok = true;
+    try {
+        uint8_t chunk[65536];
+        size_t got;
+        while ((got = std::fread(chunk, 1, sizeof chunk, f)) != 0u) {
+            if (data.size() + got > limit) {
+                ok = false;
+                break;
+            }
+            data.insert(data.end(), chunk, chunk + got);
+        }
+    } catch (const std::bad_alloc &) {
+        std::fclose(f);
+        return fail(h, CT_E_NOMEM, "%s: no host memory for %s", who, path);
+    }
+    const bool read_error = std::ferror(f) != 0;
+    std::fclose(f);
+    if (read_error) {
+        return fail(h, CT_E_INVAL, "%s: cannot read %s", who, path);
+    }
+    if (!ok) {
+        return fail(h, CT_E_INVAL, "%s: %s is longer than any bake file", who, path);
+    }
+    BakeFileError err;
+    if (bakefile_parse(data.data(), data.size(), fi, err) != CT_OK) {
+        return fail(h, CT_E_INVAL, "%s: %s: %s", who, path, err.text);
+    }
+    return CT_OK;
+}
+
+extern "C" int ct_bake_file_info(const char *path, CtBakeFileInfo *out)
+{
+    if (!path || !out) {
+        return fail(nullptr, CT_E_INVAL, "ct_bake_file_info: need a path and out");
+    }
+    std::vector<uint8_t> data;
+    return bake_file_read(nullptr, path, "ct_bake_file_info", data, out);
+}
+
+extern "C" int ct_bake_load(CtHandle h, const char *path, CtBake *out)
+{
+    const char *const who = "ct_bake_load";
+    if (!h) {
+        return fail(nullptr, CT_E_INVAL, "null handle");
+    }
+    if (!path || !out) {
+        return fail(h, CT_E_INVAL, "%s: need a path and out", who);
+    }
+    *out = nullptr;
+    std::vector<uint8_t> data;
+    CtBakeFileInfo fi{};
+    int rc = bake_file_read(h, path, who, data, &fi);
+    if (rc != CT_OK) {
+        return rc;
+    }
+    const CtBakeFileHeader &hd = fi.header;
+    // the cloud and the estimator the table was made on
+    const char *const other = "a bake of another cloud / estimator";
+    for (int axis = 0; axis < 3; axis++) {
+        if (hd.dims[axis] != h->scene.dims[axis]) {
+            return fail(h, CT_E_INVAL, "%s: %s: dims[%d] is %u in the file, %u on the handle", who, other, axis, hd.dims[axis], h->scene.dims[axis]);
+        }
+    }
+    const struct {
+        const char *name;
+        uint32_t file, handle;
+    } fields[] = {
+        { "sample_step", hd.sample_step_bits, float_bits(h->scene.sample_step) },
+        { "mean_free_path_m", hd.mean_free_path_bits, float_bits(h->scene.mean_free_path_m) },
+        { "cloud_size_m", hd.cloud_size_bits, float_bits(h->scene.cloud_size_m) },
+        { "estimator", (uint32_t)hd.estimator, (uint32_t)h->scene.estimator },
+        { "CT_FLAG_TEX_FIXED8", hd.tex_fixed8, (h->scene.flags & CT_FLAG_TEX_FIXED8) ? 1u : 0u },
+    };
+    for (const auto &fd : fields) {
+        if (fd.file != fd.handle) {
+            return fail(h, CT_E_INVAL, "%s: %s: %s is 0x%08x in the file, 0x%08x on the handle", who, other, fd.name, fd.file, fd.handle);
+        }
+    }
+    if (hd.traced && (h->scene.flags & CT_FLAG_SIMPLE_KERNEL)) {
+        return fail(h, CT_E_INVAL, "%s: a traced bake's point radiance tasks need the persistent kernel", who);
+    }
+    NEED_NOFLUSH(h);
+    rc = flush(h);
+    if (rc != CT_OK) {
+        return rc;
+    }
+    uint64_t hash = 0;
+    rc = bake_volume_hash(h, &hash);
+    if (rc != CT_OK) {
+        return rc;
+    }
+    if (hash != hd.volume_hash) {
+        return fail(h, CT_E_INVAL, "%s: %s: the volume hash is %016llx in the file, %016llx on the handle", who, other,
+                    (unsigned long long)hd.volume_hash, (unsigned long long)hash);
+    }
+    CtBake_ *b = new CtBake_();
+    struct Guard {   // (every return below that is not the last deletes b)
+        CtBake_ *b;
+        ~Guard() { delete b; }
+    } guard{ b };
+    b->h = h;
+    b->device = h->device;
+    const uint64_t nodes = (uint64_t)hd.grid[0] * hd.grid[1] * hd.grid[2];
+    for (int axis = 0; axis < 3; axis++) {
+        b->grid[axis] = hd.grid[axis];
+        b->l[axis] = hd.light[axis];
+        b->a[axis] = hd.axis_a[axis];
+        b->b[axis] = hd.axis_b[axis];
+        b->light_bits[axis] = hd.light_color_bits[axis];
+    }
+    b->light_bits[3] = hd.light_intensity_bits;
+    b->azimuths = hd.azimuths;
+    b->cosines = hd.cosines;
+    b->entries = hd.entries;
+    b->stored = hd.stored_entries;
+    for (uint32_t k = 0; k < b->cosines; k++) {
+        b->cosine[k] = (float)(-1.0 + 2.0 * (double)k / (double)(b->cosines - 1u));
+    }
+    b->sparse = hd.kind != (uint32_t)CT_BAKE_DENSE;
+    b->compact = hd.kind == (uint32_t)CT_BAKE_COMPACT;
+    b->traced = hd.traced != 0u;
+    b->adaptive = hd.adaptive != 0u;
+    b->half = hd.format == (uint32_t)CT_BAKE_F16;
+    b->samples = hd.samples;
+    b->paths = hd.paths;
+    if (b->adaptive) {
+        b->ap = CtBakeAdaptive{ CT_ABI_VERSION, hd.round_samples, hd.max_samples, hd.zero_samples, bits_float(hd.rel_tol_bits), bits_float(hd.abs_tol_bits) };
+        b->cap = hd.max_samples;
+        b->rounds = hd.rounds;
+    }
+    {   // current: the file's light, colour and intensity are the handle's, bit for bit
+        CtBake_ now;
+        bake_frame(h, &now);
+        bool same = std::memcmp(now.light_bits, b->light_bits, sizeof now.light_bits) == 0;
+        for (int axis = 0; axis < 3; axis++) {
+            same = same && float_bits(now.l[axis]) == float_bits(b->l[axis]);
+        }
+        b->epoch = same ? h->light_epoch : h->light_epoch - 1u;
+    }
+    // The mask again, on this handle: the file's node bytes must be it; list and slots are the recomputation's.
+    if (b->sparse) {
+        BakeMask m;
+        rc = bake_mask_reserve(h, b->grid, m, b->compact);
+        uint32_t active = 0;
+        double ms = 0;
+        if (rc == CT_OK) {
+            rc = bake_mask_run(h, b->grid, m, &active, &ms);
+        }
+        if (rc != CT_OK) {
+            return rc;
+        }
+        std::vector<uint8_t> mask((size_t)nodes);
+        HIPCHK(h, hipMemcpy(mask.data(), m.nodes, (size_t)nodes, hipMemcpyDeviceToHost));
+        if (m.margin != hd.margin_texels || active != hd.active_nodes || std::memcmp(mask.data(), data.data() + fi.nodes_offset, (size_t)nodes) != 0) {
+            return fail(h, CT_E_INVAL, "%s: the file's node bytes are not this handle's mask of the grid (%llu active nodes, margin %u in the file; "
+                                       "%u, margin %u here)", who, (unsigned long long)hd.active_nodes, hd.margin_texels, active, m.margin);
+        }
+        b->margin = m.margin;
+        b->active = active;
+        b->d_nodes = std::move(m.nodes);
+        b->d_list = std::move(m.list);
+        b->d_slots = std::move(m.slots);   // (empty unless compact)
+    }
+    // everything else, allocated before the first copy
+    const size_t stored = (size_t)b->stored, total = (size_t)std::max<uint64_t>(1, bake_trace_total(b));
+    bool got = b->half ? b->d_half.alloc(stored) == hipSuccess : b->d_table.alloc(stored) == hipSuccess;
+    got = got && ((!b->sparse && !b->traced) || b->d_probe.alloc(b->grid[0] + b->grid[1] + b->grid[2] + 3 * (size_t)b->azimuths) == hipSuccess);
+    got = got && (!b->traced || b->d_dirs.alloc(3 * (size_t)b->azimuths * b->cosines) == hipSuccess);
+    if (got && b->adaptive) {
+        got = b->d_m2.alloc(stored) == hipSuccess && b->d_counts.alloc(stored) == hipSuccess && b->d_live[0].alloc(total) == hipSuccess &&
+              b->d_live[1].alloc(total) == hipSuccess && b->d_waves.alloc((total + 255u) / 256u * 4u + 1u) == hipSuccess;
+    }
+    if (!got) {
+        (void)hipGetLastError();
+        return fail(h, CT_E_NOMEM, "%s: no device memory for a bake of %llu stored entries", who, (unsigned long long)b->stored);
+    }
+    rc = drained(h, [&]() -> int {
+        if (b->half) {
+            HIPCHK(h, hipMemcpyAsync(b->d_half, data.data() + fi.table_offset, stored * 2u, hipMemcpyHostToDevice, h->stream));
+        } else {
+            HIPCHK(h, hipMemcpyAsync(b->d_table, data.data() + fi.table_offset, stored * 4u, hipMemcpyHostToDevice, h->stream));
+        }
+        if (b->adaptive) {
+            HIPCHK(h, hipMemcpyAsync(b->d_m2, data.data() + fi.m2_offset, stored * 4u, hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipMemcpyAsync(b->d_counts, data.data() + fi.counts_offset, stored * 4u, hipMemcpyHostToDevice, h->stream));
+        }
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (b->traced) {
+            const int up = bake_upload_trace_tables(h, b);
+            if (up != CT_OK) {
+                return up;
+            }
+        }
+        const uint64_t n = bake_trace_total(b);
+        if (b->adaptive && b->rounds != 0u && n != 0u) {
+            // The live list the bake was left with: the stored entries of active nodes that fail the rule, ascending.  (An entry
+            // that stopped by the rule passes it; one that fails holds `samples` experiments, or it would have gone on.)
+            BakeTraceArgs a{};
+            a.list = b->sparse ? b->d_list.get() : nullptr;
+            a.nx = b->grid[0];
+            a.ny = b->grid[1];
+            a.nphi = b->azimuths;
+            a.nc = b->cosines;
+            a.compact = b->compact ? 1u : 0u;
+            const BakeAdaptiveState st{ b->d_table, b->d_m2, b->d_counts, b->ap.rel_tol, b->ap.abs_tol, b->ap.zero_samples };
+            uint32_t survivors = 0;
+            HIPCHK(h, launch_bake_adaptive_count(a, st, (uint32_t)n, b->d_waves, h->stream));
+            HIPCHK(h, launch_bake_adaptive_scan(b->d_waves, (uint32_t)n, h->stream));
+            HIPCHK(h, launch_bake_adaptive_compact(a, st, nullptr, (uint32_t)n, b->d_waves, b->d_live[0], h->stream));
+            HIPCHK(h, hipMemcpyAsync(&survivors, b->d_waves + (n + 63u) / 64u, sizeof survivors, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            b->live = survivors;
+            b->live_cur = 0;
+        }
+        return CT_OK;
+    });
+    if (rc != CT_OK) {
+        return rc;
+    }
+    if (b->adaptive && b->live != hd.capped) {
+        return fail(h, CT_E_INVAL, "%s: the header counts %llu capped entries, the stored means, m2 and counts leave %llu", who,
+                    (unsigned long long)hd.capped, (unsigned long long)b->live);
+    }
+    guard.b = nullptr;
+    *out = b;
     return CT_OK;
 }
 

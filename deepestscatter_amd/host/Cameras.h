@@ -142,6 +142,55 @@ namespace DeepestScatter
         CtGroupNetwork groupNetwork = nullptr;   // with --gpus: one network per shard, destroyed before the group
     };
 
+    // --bake-in FILE / --bake-out FILE / --bake-half (include/cloudtrace.h, "bake files" and "half tables"), for both baked
+    // renderers below.  in: the table comes from ct_bake_load instead of a bake run.  half: the frames are interpolated from the
+    // ct_bake_half copy of the table.  out: the table that renders -- the half copy with --bake-half -- is saved by ct_bake_save.
+    struct BakeFiles
+    {
+        std::string in, out;
+        bool half = false;
+    };
+
+    // What the two renderers do alike with their table once it exists: the half copy, the file, and which of the two renders.
+    class BakeHolder
+    {
+    public:
+        ~BakeHolder()
+        {
+            if (halfCopy) ct_bake_destroy(halfCopy);
+            if (bake) ct_bake_destroy(bake);   // (before the network and the handle)
+        }
+        CtBake shown() const { return halfCopy ? halfCopy : bake; }
+        bool isHalf(CtHandle handle) const
+        {
+            uint32_t format = CT_BAKE_F32;
+            Context::check(ct_bake_format(bake, &format), handle, "ct_bake_format");
+            return format == CT_BAKE_F16;
+        }
+        bool load(CtHandle handle, const BakeFiles& files)   // true: the table came from --bake-in
+        {
+            if (files.in.empty()) return false;
+            Context::check(ct_bake_load(handle, files.in.c_str(), &bake), handle, "ct_bake_load");
+            return true;
+        }
+        void finish(CtHandle handle, const BakeFiles& files, bool save)   // behind every bake, load, update and retrace
+        {
+            if (halfCopy) ct_bake_destroy(halfCopy);
+            halfCopy = nullptr;
+            if (files.half && !isHalf(handle)) Context::check(ct_bake_half(handle, bake, &halfCopy), handle, "ct_bake_half");
+            if (save && !files.out.empty()) Context::check(ct_bake_save(shown(), files.out.c_str()), handle, "ct_bake_save");
+        }
+        bool current(CtHandle handle) const
+        {
+            CtBakeInfo info;
+            Context::check(ct_bake_info(shown(), &info), handle, "ct_bake_info");
+            if (!info.current && isHalf(handle))
+                throw std::runtime_error("--bake-in: the file holds a half table made under another light, and a half bake is final; bake again");
+            return info.current != 0;
+        }
+        CtBake bake = nullptr, halfCopy = nullptr;
+    };
+
     // The reference's default renderer (BakedRenderer): the network evaluated once per light on a probe grid (ct_network_bake,
     // --net-baked NX,NY,NZ,NPHI,NC) and every subframe interpolated from that table (ct_baked_render_*): no gather and no
     // network per subframe.  The table is baked in init, which follows Sun::init and so every ct_set_light, and baked again
@@ -152,27 +201,29 @@ namespace DeepestScatter
     {
     public:
         BakedRenderer(std::shared_ptr<Context> context, std::shared_ptr<const NetworkFile> file, const CtNetworkRender& params, const CtBakeDesc& desc,
-                      bool sparse = false, bool compact = false)
-            : NetworkRenderer(std::move(context), std::move(file), params), desc(desc), sparse(sparse), compact(compact) {}
-        ~BakedRenderer() override
-        {
-            if (bake) ct_bake_destroy(bake);   // (before the network and the handle)
-        }
+                      bool sparse = false, bool compact = false, const BakeFiles& files = {})
+            : NetworkRenderer(std::move(context), std::move(file), params), desc(desc), sparse(sparse), compact(compact), files(files) {}
 
         void init() override
         {
             NetworkRenderer::init();
             if (context->group) throw std::runtime_error("--net-baked renders on one GPU only");
-            if (!bake && compact) Context::check(ct_network_bake_compact(context->handle, network, &desc, &bake), context->handle, "ct_network_bake_compact");
-            if (!bake && sparse) Context::check(ct_network_bake_sparse(context->handle, network, &desc, &bake), context->handle, "ct_network_bake_sparse");
-            if (!bake) Context::check(ct_network_bake(context->handle, network, &desc, &bake), context->handle, "ct_network_bake");
+            CtBake& bake = table.bake;
+            if (bake) return;
+            if (!table.load(context->handle, files))
+            {
+                if (compact) Context::check(ct_network_bake_compact(context->handle, network, &desc, &bake), context->handle, "ct_network_bake_compact");
+                else if (sparse) Context::check(ct_network_bake_sparse(context->handle, network, &desc, &bake), context->handle, "ct_network_bake_sparse");
+                else Context::check(ct_network_bake(context->handle, network, &desc, &bake), context->handle, "ct_network_bake");
+            }
+            table.finish(context->handle, files, true);
         }
 
         void render(float* frameResultBuffer) override
         {
             applyCamera();
             refresh();
-            Context::check(ct_baked_render_subframe(context->handle, bake, &params, subframeId, frameResultBuffer), context->handle,
+            Context::check(ct_baked_render_subframe(context->handle, table.shown(), &params, subframeId, frameResultBuffer), context->handle,
                            "ct_baked_render_subframe");
         }
 
@@ -180,21 +231,22 @@ namespace DeepestScatter
         {
             applyCamera();
             refresh();
-            Context::check(ct_baked_render_accumulate(context->handle, bake, &params, first, count), context->handle,
+            Context::check(ct_baked_render_accumulate(context->handle, table.shown(), &params, first, count), context->handle,
                            "ct_baked_render_accumulate");
         }
 
     private:
-        void refresh()   // a light set since the bake: bake again
+        void refresh()   // a light set since the bake: bake again (and round again, with --bake-half)
         {
-            CtBakeInfo info;
-            Context::check(ct_bake_info(bake, &info), context->handle, "ct_bake_info");
-            if (!info.current) Context::check(ct_bake_update(context->handle, network, bake), context->handle, "ct_bake_update");
+            if (table.current(context->handle)) return;
+            Context::check(ct_bake_update(context->handle, network, table.bake), context->handle, "ct_bake_update");
+            table.finish(context->handle, files, false);
         }
 
         CtBakeDesc desc;
         bool sparse, compact;
-        CtBake bake = nullptr;
+        BakeFiles files;
+        BakeHolder table;   // (destroyed before the network and the handle)
     };
 
     // The baked renderer without a network (--traced-bake NX,NY,NZ,NPHI,NC --bake-samples N): the probe table holds the means of
@@ -206,33 +258,37 @@ namespace DeepestScatter
     {
     public:
         TracedBakeRenderer(std::shared_ptr<Context> context, const CtNetworkRender& params, const CtBakeDesc& desc, uint32_t kind, uint32_t samples,
-                           const CtBakeAdaptive* adaptive = nullptr)
+                           const CtBakeAdaptive* adaptive = nullptr, const BakeFiles& files = {})
             : PathTracingRenderer(std::move(context)), params(params), desc(desc), kind(kind), samples(samples), isAdaptive(adaptive != nullptr),
-              adaptive(adaptive ? *adaptive : CtBakeAdaptive{}) {}
-        ~TracedBakeRenderer() override
-        {
-            if (bake) ct_bake_destroy(bake);   // (before the handle)
-        }
+              adaptive(adaptive ? *adaptive : CtBakeAdaptive{}), files(files) {}
 
         void init() override
         {
             PathTracingRenderer::init();
             if (context->group) throw std::runtime_error("--traced-bake renders on one GPU only");
+            CtBake& bake = table.bake;
             if (bake) return;
-            if (!isAdaptive)
+            if (table.load(context->handle, files))   // --bake-in: how to trace it again, should the light change, is the file's
             {
-                Context::check(ct_bake_traced(context->handle, &desc, kind, samples, &bake), context->handle, "ct_bake_traced");
-                return;
+                CtBakeTraceInfo ti;
+                CtBakeAdaptiveInfo ai;
+                Context::check(ct_bake_trace_info(bake, &ti), context->handle, "ct_bake_trace_info");
+                Context::check(ct_bake_adaptive_info(bake, &ai), context->handle, "ct_bake_adaptive_info");
+                if (!ti.traced) throw std::runtime_error("--bake-in: the file holds a network's bake; give its network with --network FILE");
+                samples = ti.samples;
+                isAdaptive = ai.adaptive != 0;
             }
-            Context::check(ct_bake_traced_adaptive(context->handle, &desc, kind, &adaptive, &bake), context->handle, "ct_bake_traced_adaptive");
-            printAdaptiveInfo();
+            else if (!isAdaptive) Context::check(ct_bake_traced(context->handle, &desc, kind, samples, &bake), context->handle, "ct_bake_traced");
+            else Context::check(ct_bake_traced_adaptive(context->handle, &desc, kind, &adaptive, &bake), context->handle, "ct_bake_traced_adaptive");
+            if (isAdaptive) printAdaptiveInfo();
+            table.finish(context->handle, files, true);
         }
 
         void render(float* frameResultBuffer) override
         {
             applyCamera();
             refresh();
-            Context::check(ct_baked_render_subframe(context->handle, bake, &params, subframeId, frameResultBuffer), context->handle,
+            Context::check(ct_baked_render_subframe(context->handle, table.shown(), &params, subframeId, frameResultBuffer), context->handle,
                            "ct_baked_render_subframe");
         }
 
@@ -240,29 +296,27 @@ namespace DeepestScatter
         {
             applyCamera();
             refresh();
-            Context::check(ct_baked_render_accumulate(context->handle, bake, &params, first, count), context->handle,
+            Context::check(ct_baked_render_accumulate(context->handle, table.shown(), &params, first, count), context->handle,
                            "ct_baked_render_accumulate");
         }
 
     private:
-        void refresh()   // a light set since the bake: trace again
+        void refresh()   // a light set since the bake: trace again (and round again, with --bake-half)
         {
-            CtBakeInfo info;
-            Context::check(ct_bake_info(bake, &info), context->handle, "ct_bake_info");
-            if (info.current) return;
-            if (!isAdaptive)
+            if (table.current(context->handle)) return;
+            if (!isAdaptive) Context::check(ct_bake_retrace(context->handle, table.bake, samples), context->handle, "ct_bake_retrace");
+            else
             {
-                Context::check(ct_bake_retrace(context->handle, bake, samples), context->handle, "ct_bake_retrace");
-                return;
+                Context::check(ct_bake_retrace_adaptive(context->handle, table.bake), context->handle, "ct_bake_retrace_adaptive");
+                printAdaptiveInfo();
             }
-            Context::check(ct_bake_retrace_adaptive(context->handle, bake), context->handle, "ct_bake_retrace_adaptive");
-            printAdaptiveInfo();
+            table.finish(context->handle, files, false);
         }
 
         void printAdaptiveInfo()
         {
             CtBakeAdaptiveInfo i;
-            Context::check(ct_bake_adaptive_info(bake, &i), context->handle, "ct_bake_adaptive_info");
+            Context::check(ct_bake_adaptive_info(table.bake, &i), context->handle, "ct_bake_adaptive_info");
             std::printf("adaptive bake: %u rounds of %u, cap %u; %llu entries, %llu converged, %llu capped, %llu paths; "
                         "trace %.3f ms, fold %.3f ms, test %.3f ms\n", i.rounds, i.round_samples, i.max_samples,
                         (unsigned long long)i.entries_active, (unsigned long long)i.converged, (unsigned long long)i.capped,
@@ -274,7 +328,8 @@ namespace DeepestScatter
         uint32_t kind, samples;
         bool isAdaptive;
         CtBakeAdaptive adaptive;
-        CtBake bake = nullptr;
+        BakeFiles files;
+        BakeHolder table;   // (destroyed before the handle)
     };
 
     class Camera : public SceneItem                                              // Camera.h:16-103

@@ -23,6 +23,10 @@
 //              [--bake-adaptive R,MAX[,REL[,ABS[,ZERO]]]]   in place of --bake-samples: trace in rounds of R experiments, only the entries
 //                               that fail the stopping rule (95 % interval below REL of the mean, default 0.02, or below ABS, default
 //                               1e-4; a zero entry after ZERO experiments, default 100000), at most MAX each (ct_bake_traced_adaptive)
+//              [--bake-out FILE]                with --net-baked or --traced-bake: save the table as a bake file (ct_bake_save)
+//              [--bake-in FILE]                 in place of --net-baked / --traced-bake and their flags: render from the table in FILE
+//                               (ct_bake_load); a traced file needs no network, a network's bake needs its --network FILE (a new light bakes it again)
+//              [--bake-half]                    render from the binary16 copy of the table (ct_bake_half); with --bake-out that copy is saved
 //              [--adaptive R,MAX[,MIN[,REL[,ABS]]] [--adaptive-counts FILE]]   the image as an adaptive frame (ct_adaptive_frame_*):
 //                               rounds of R subframes that go only to the pixels which still fail the stopping rule (tested from MIN
 //                               samples on, default 100; 95 % interval below REL of the mean, default 0.02, or below ABS, default
@@ -98,6 +102,7 @@ namespace
         uint32_t bakeSamples = 0;                                                 // --bake-samples N: experiments per entry of the traced bake
         bool bakeAdaptive = false;                                                // --bake-adaptive R,MAX[,REL[,ABS[,ZERO]]]: the traced bake in rounds under the stopping rule
         CtBakeAdaptive adaptive{ CT_ABI_VERSION, 0, 0, 100000, 2e-2f, 1e-4f };
+        BakeFiles bakeFiles;                                                      // --bake-in FILE, --bake-out FILE, --bake-half
         bool adaptiveFrame = false;                                               // --adaptive R,MAX[,MIN[,REL[,ABS]]]: the image as an adaptive frame (Camera::adaptive)
         CtAdaptiveFrameDesc adaptiveDesc{ CT_ABI_VERSION, 0, 100, 0, 2e-2f, 1e-2f, 0, 0 };
         std::string adaptiveCounts;                                               // --adaptive-counts FILE: the per-pixel sample counts
@@ -317,9 +322,9 @@ namespace
             // installFramework + installApp: Sun, VDBCloud, CloudMaterial, Camera in this order (installers.cpp:28-38)
             std::shared_ptr<PathTracingRenderer> renderer = opt.tracedBake ? std::make_shared<TracedBakeRenderer>(context, opt.networkRender, opt.bake,
                     opt.netBakeCompact ? CT_BAKE_COMPACT : opt.netBakeSparse ? CT_BAKE_SPARSE : CT_BAKE_DENSE, opt.bakeSamples,
-                    opt.bakeAdaptive ? &opt.adaptive : nullptr)
+                    opt.bakeAdaptive ? &opt.adaptive : nullptr, opt.bakeFiles)
                 : !opt.network ? std::make_shared<PathTracingRenderer>(context)
-                : opt.netBaked ? std::make_shared<BakedRenderer>(context, opt.network, opt.networkRender, opt.bake, opt.netBakeSparse, opt.netBakeCompact)
+                : opt.netBaked ? std::make_shared<BakedRenderer>(context, opt.network, opt.networkRender, opt.bake, opt.netBakeSparse, opt.netBakeCompact, opt.bakeFiles)
                                : std::make_shared<NetworkRenderer>(context, opt.network, opt.networkRender);
             renderer->estimator = opt.estimator;
             auto sun = std::make_shared<Sun>(std::make_shared<DirectionalLight>(scene.light), context);
@@ -438,6 +443,9 @@ int main(int argc, char* argv[])
             {
                 opt.netBakeCompact = true;
             }
+            else if (a == "--bake-in") opt.bakeFiles.in = next();
+            else if (a == "--bake-out") opt.bakeFiles.out = next();
+            else if (a == "--bake-half") opt.bakeFiles.half = true;
             else if (a == "--tex-fixed8") opt.texFixed8 = true;
             else if (a == "--estimator")
             {
@@ -469,11 +477,27 @@ int main(int argc, char* argv[])
         if (opt.collect) return collectScenes(opt);
 
         if (opt.netDirect) opt.networkRender.transform |= CT_NET_ADD_SINGLE_SCATTER;   // (after the loop: --net-transform may follow it)
+        if (!opt.bakeFiles.in.empty())
+        {
+            if (opt.tracedBake || opt.netBaked || opt.bakeSamples != 0 || opt.bakeAdaptive || opt.netBakeSparse || opt.netBakeCompact)
+                throw std::invalid_argument("--bake-in takes the table and its kind from FILE: it cannot be combined with --net-baked, --traced-bake, "
+                                            "--bake-samples, --bake-adaptive, --net-bake-sparse or --net-bake-compact");
+            if (opt.bakeFiles.in == opt.bakeFiles.out) throw std::invalid_argument("--bake-in and --bake-out name the same file");
+            CtBakeFileInfo info;   // (no device: a malformed file stops here)
+            if (ct_bake_file_info(opt.bakeFiles.in.c_str(), &info) != CT_OK) throw std::invalid_argument(std::string("--bake-in: ") + ct_last_error(nullptr));
+            if (info.header.traced && !opt.networkPath.empty())
+                throw std::invalid_argument("--bake-in: the file holds a traced bake, which renders without a network: drop --network");
+            if (!info.header.traced && opt.networkPath.empty())
+                throw std::invalid_argument("--bake-in: the file holds a network's bake: give its network with --network FILE");
+            (info.header.traced ? opt.tracedBake : opt.netBaked) = true;
+        }
+        else if ((!opt.bakeFiles.out.empty() || opt.bakeFiles.half) && !opt.tracedBake && !opt.netBaked)
+            throw std::invalid_argument("--bake-out and --bake-half work on the table of --net-baked, --traced-bake or --bake-in");
         if (opt.tracedBake && !opt.networkPath.empty()) throw std::invalid_argument("--traced-bake fills the table with path-traced radiance: it cannot be combined with --network");
         if (opt.tracedBake && opt.netBaked) throw std::invalid_argument("--traced-bake and --net-baked are two ways to fill one table: give one of them");
         if (opt.bakeAdaptive && opt.bakeSamples != 0) throw std::invalid_argument("--bake-adaptive and --bake-samples are two ways to trace one table: give one of them");
         if (opt.bakeAdaptive && !opt.tracedBake) throw std::invalid_argument("--bake-adaptive sets the rounds of --traced-bake NX,NY,NZ,NPHI,NC");
-        if (opt.tracedBake && opt.bakeSamples == 0 && !opt.bakeAdaptive) throw std::invalid_argument("--traced-bake needs --bake-samples N or --bake-adaptive R,MAX[,REL[,ABS[,ZERO]]]");
+        if (opt.tracedBake && opt.bakeSamples == 0 && !opt.bakeAdaptive && opt.bakeFiles.in.empty()) throw std::invalid_argument("--traced-bake needs --bake-samples N or --bake-adaptive R,MAX[,REL[,ABS[,ZERO]]]");
         if (opt.bakeSamples != 0 && !opt.tracedBake) throw std::invalid_argument("--bake-samples counts the experiments of --traced-bake NX,NY,NZ,NPHI,NC");
         if (opt.tracedBake && !opt.devices.empty()) throw std::invalid_argument("--traced-bake renders on one GPU: it cannot be combined with --gpus");
         if (opt.netBakeCompact && !opt.netBaked && !opt.tracedBake) throw std::invalid_argument("--net-bake-compact chooses how --net-baked NX,NY,NZ,NPHI,NC bakes and stores its table");

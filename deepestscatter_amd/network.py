@@ -13,6 +13,9 @@ residual MLP of the paper the reference implements (Kallweit et al. 2017), param
     bake_mask_reference numpy restatement of the sparse bake's mask (ct_network_bake_sparse): cells, nodes and the margin M
     bake_slots_reference numpy restatement of the compact bake's slot index (ct_network_bake_compact)
     point_fold_var_reference / point_converged_reference   numpy restatement of an adaptive traced bake's fold and stopping rule
+    bake_file_dtype / write_bake_file_reference / read_bake_file_reference   numpy restatement of the bake file (ct_bake_save)
+    volume_hash_reference / half_round_reference   the file's volume hash; ct_bake_half's rounding and refusal rule
+    bake_file_info      ct_bake_file_info: a bake file checked without a device
     save_weights / load_weights   the weight file `cloudtrace --network` reads
 
 State-dict names (the mapping an exported model needs): blocks.k.fc1 = W1_k, c1_k; blocks.k.fc2 = W2_k, c2_k (k = 0 .. 9);
@@ -366,6 +369,139 @@ def point_converged_reference(mean, m2, count, rel_tol, abs_tol, zero_samples) -
         return np.where(rad < eps, cnt > int(zero_samples), converged)
 
 
+# ---- bake files and half tables (include/cloudtrace.h, "bake files" and "half tables"), restated in numpy: no library call ----
+BAKE_FILE_MAGIC = b"CTBAKE\r\n"
+BAKE_FILE_VERSION = 1
+BAKE_F32, BAKE_F16 = 0, 1
+
+# The 256-byte header, little-endian, every field at the offset include/cloudtrace.h documents (CtBakeFileHeader).
+bake_file_dtype = np.dtype({
+    "names": ["magic", "version", "header_bytes", "kind", "format", "traced", "adaptive", "grid", "azimuths", "cosines", "margin_texels",
+              "entries", "stored_entries", "active_nodes", "light", "axis_a", "axis_b", "dims", "sample_step_bits", "mean_free_path_bits",
+              "cloud_size_bits", "estimator", "tex_fixed8", "light_color_bits", "light_intensity_bits", "samples", "volume_hash", "paths",
+              "round_samples", "max_samples", "zero_samples", "rel_tol_bits", "abs_tol_bits", "rounds", "converged", "capped", "reserved"],
+    "formats": ["S8", "<u4", "<u4", "<u4", "<u4", "<u4", "<u4", ("<u4", 3), "<u4", "<u4", "<u4",
+                "<u8", "<u8", "<u8", ("<f4", 3), ("<f4", 3), ("<f4", 3), ("<u4", 3), "<u4", "<u4",
+                "<u4", "<i4", "<u4", ("<u4", 3), "<u4", "<u4", "<u8", "<u8",
+                "<u4", "<u4", "<u4", "<u4", "<u4", "<u4", "<u8", "<u8", ("u1", 32)],
+    "offsets": [0, 8, 12, 16, 20, 24, 28, 32, 44, 48, 52,
+                56, 64, 72, 80, 92, 104, 116, 128, 132,
+                136, 140, 144, 148, 160, 164, 168, 176,
+                184, 188, 192, 196, 200, 204, 208, 216, 224],
+    "itemsize": 256,
+})
+
+
+def fnv1a64_reference(data: bytes) -> int:
+    """FNV-1a 64 of `data`: the bake file's trailing checksum."""
+    h = 0xCBF29CE484222325
+    for byte in bytes(data):
+        h = ((h ^ byte) * 0x100000001B3) & 0xFFFFFFFFFFFFFFFF
+    return h
+
+
+def volume_hash_reference(density) -> int:
+    """The volume hash of a bake file: H = sum_i (t_i + 1) * ((i + 1) * 0x9E3779B97F4A7C15 mod 2^64) mod 2^64 over the level-0
+    texels in linear order (x fastest), in uint64 arithmetic, which wraps."""
+    t = np.ascontiguousarray(density, np.uint8).reshape(-1).astype(np.uint64)
+    i = np.arange(1, t.size + 1, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        return int(np.sum((t + np.uint64(1)) * (i * np.uint64(0x9E3779B97F4A7C15)), dtype=np.uint64))
+
+
+def half_round_reference(values_f32):
+    """ct_bake_half's rounding: (bits, refused).  bits: uint16, numpy's float32 -> float16 conversion (nearest, ties to even,
+    subnormals, the sign of zero); refused: bool, the values the call refuses -- NaN, infinite, or |v| >= 65520, which round to
+    an infinity."""
+    v = np.ascontiguousarray(values_f32, np.float32)
+    with np.errstate(over="ignore", invalid="ignore"):
+        bits = v.astype(np.float16).view(np.uint16)
+        refused = ~(np.abs(v) < np.float32(65520.0))
+    return bits, refused
+
+
+def _bake_file_sections(header):
+    """-> {section: (offset, dtype, count)} and the checksum's offset, for a header record."""
+    def pad(v, to=16):
+        return (v + to - 1) // to * to
+    at, out = 256, {}
+    stored = int(header["stored_entries"])
+    if int(header["kind"]) != 0:
+        out["nodes"] = (at, np.dtype("u1"), int(np.prod(header["grid"].astype(np.uint64))))
+        at += out["nodes"][2]
+    at = pad(at)
+    out["table"] = (at, np.dtype("<f2" if int(header["format"]) == BAKE_F16 else "<f4"), stored)
+    at += stored * out["table"][1].itemsize
+    if int(header["adaptive"]):
+        at = pad(at)
+        out["m2"] = (at, np.dtype("<f4"), stored)
+        at = pad(at + 4 * stored)
+        out["counts"] = (at, np.dtype("<u4"), stored)
+        at += 4 * stored
+    return out, pad(at, 8)
+
+
+def write_bake_file_reference(header: dict, table, nodes=None, m2=None, counts=None) -> bytes:
+    """The bytes of a bake file.  header: the fields of bake_file_dtype by name (missing ones are 0; magic, version and
+    header_bytes are filled in); table: the stored table, float32, or uint16 binary16 bits for format 1; nodes: uint8 node bytes
+    (sparse and compact kinds); m2 / counts: adaptive bakes."""
+    h = np.zeros((), bake_file_dtype)
+    h["magic"], h["version"], h["header_bytes"] = BAKE_FILE_MAGIC, BAKE_FILE_VERSION, 256
+    for name, value in header.items():
+        h[name] = value
+    sections, end = _bake_file_sections(h)
+    data = bytearray(end)
+    data[:256] = h.tobytes()
+    half = int(h["format"]) == BAKE_F16
+    parts = {"nodes": (nodes, np.uint8), "table": (table, np.uint16 if half else np.float32), "m2": (m2, np.float32), "counts": (counts, np.uint32)}
+    for name, (at, dtype, count) in sections.items():
+        array, host = parts[name]
+        raw = np.ascontiguousarray(array, host).reshape(-1)
+        if raw.size != count:
+            raise ValueError(f"write_bake_file_reference: {name} holds {raw.size} values, the header implies {count}")
+        data[at:at + count * dtype.itemsize] = raw.astype(raw.dtype.newbyteorder("<")).tobytes()
+    return bytes(data) + np.array(fnv1a64_reference(data), "<u8").tobytes()
+
+
+def read_bake_file_reference(data: bytes) -> dict:
+    """-> {"header": the bake_file_dtype record, "table" (float32, or uint16 bits for format 1), "nodes", "m2", "counts" (None where
+    the file has no such section), "checksum"}.  ValueError for a wrong magic, version, length or checksum; the ranges are the
+    library's to check (bake_file_info)."""
+    data = bytes(data)
+    if len(data) < 264:
+        raise ValueError("shorter than a bake file's header and checksum")
+    h = np.frombuffer(data, bake_file_dtype, 1)[0]
+    if bytes(h["magic"]).ljust(8, b"\0") != BAKE_FILE_MAGIC or int(h["version"]) != BAKE_FILE_VERSION or int(h["header_bytes"]) != 256:
+        raise ValueError("not a bake file of this version")
+    sections, end = _bake_file_sections(h)
+    if len(data) != end + 8:
+        raise ValueError(f"{len(data)} bytes, the header implies {end + 8}")
+    checksum = int(np.frombuffer(data, "<u8", 1, end)[0])
+    if checksum != fnv1a64_reference(data[:end]):
+        raise ValueError("wrong checksum")
+    out = {"header": h, "nodes": None, "m2": None, "counts": None, "checksum": checksum}
+    for name, (at, dtype, count) in sections.items():
+        a = np.frombuffer(data, dtype, count, at)
+        out[name] = a.view(np.uint16).copy() if dtype == np.dtype("<f2") else a.astype(dtype.newbyteorder("=")).copy()
+    return out
+
+
+def bake_file_info(path) -> dict:
+    """ct_bake_file_info: a bake file read and checked without a device -> the header's fields by name (arrays as numpy arrays)
+    and file_bytes, the sections' offsets and the checksum."""
+    import os
+    L = _lib.load()
+    i = _lib.CtBakeFileInfo()
+    check(L.ct_bake_file_info(os.fsencode(path), C.byref(i)), None)
+    out = {}
+    for name, ctype in i.header._fields_:
+        v = getattr(i.header, name)
+        out[name] = bytes(v) if name == "magic" else np.ctypeslib.as_array(v).copy() if hasattr(v, "__len__") else v
+    for name, _ in i._fields_[1:]:
+        out[name] = int(getattr(i, name))
+    return out
+
+
 @dataclass(frozen=True)
 class AdaptiveParams:
     """CtBakeAdaptive: R experiments per live entry and round, the cap per entry (a multiple of R), and the stopping rule's
@@ -515,6 +651,47 @@ class Bake:
             entry = self.L.ct_network_bake_compact if compact else self.L.ct_network_bake_sparse if sparse else self.L.ct_network_bake
             check(entry(tracer.h, net.n, C.byref(d), C.byref(b)), tracer.h)
         self.b = b
+
+    @classmethod
+    def _adopt(cls, tracer, handle) -> "Bake":
+        """A Bake around a CtBake the library has made another way (ct_bake_load, ct_bake_half)."""
+        self = cls.__new__(cls)
+        self.L = _lib.load()
+        self.tracer = tracer
+        self.b = handle
+        return self
+
+    @classmethod
+    def load(cls, tracer, path) -> "Bake":
+        """ct_bake_load: the bake a file holds, on `tracer`, which must hold the cloud and estimator the file was made on."""
+        import os
+        b = C.c_void_p()
+        check(_lib.load().ct_bake_load(tracer.h, os.fsencode(path), C.byref(b)), tracer.h)
+        return cls._adopt(tracer, b)
+
+    def save(self, path):
+        """ct_bake_save: this bake, of any kind and format, as a bake file (written under a temporary name and renamed)."""
+        import os
+        check(self.L.ct_bake_save(self.b, os.fsencode(path)), self.tracer.h)
+
+    def half(self) -> "Bake":
+        """ct_bake_half: a NEW bake of the same kind, grid, frame and mask whose stored table is binary16 (each value rounded to
+        nearest, ties to even).  CloudTraceError (CT_E_INVAL) when a value is not finite or rounds to an infinity.  A half bake
+        is final: it renders and saves, and nothing bakes or traces into it."""
+        b = C.c_void_p()
+        check(self.L.ct_bake_half(self.tracer.h, self.b, C.byref(b)), self.tracer.h)
+        return Bake._adopt(self.tracer, b)
+
+    @property
+    def format(self) -> int:
+        """ct_bake_format: 0 (CT_BAKE_F32) or 1 (CT_BAKE_F16)."""
+        f = C.c_uint32(0)
+        check(self.L.ct_bake_format(self.b, C.byref(f)), self.tracer.h)
+        return int(f.value)
+
+    def half_table(self) -> np.ndarray:
+        """ct_bake_download_half -> uint16, the stored binary16 bits of a half bake, shaped as counts() / stored_table()."""
+        return self._stored_array(self.L.ct_bake_download_half, np.uint16)
 
     def close(self):
         if getattr(self, "b", None):

@@ -940,7 +940,7 @@ typedef struct CtBakeStorageInfo {
     uint32_t reserved;       /* 0 */
     uint64_t slots;          /* active + 1; dense / sparse bake: Nx Ny Nz */
     uint64_t stored_entries; /* floats the table holds on the device */
-    uint64_t table_bytes;    /* 4 * stored_entries */
+    uint64_t table_bytes;    /* 4 * stored_entries (a half bake, "half tables" below: 2 * stored_entries) */
     uint64_t index_bytes;    /* 4 * Nx Ny Nz; 0 for a dense / sparse bake */
 } CtBakeStorageInfo;
 
@@ -1098,6 +1098,140 @@ CT_API int ct_bake_retrace_adaptive(CtHandle h, CtBake b);                      
 CT_API int ct_bake_adaptive_info(CtBake b, CtBakeAdaptiveInfo *out);
 CT_API int ct_bake_download_counts(CtBake b, uint32_t *counts_host_out, size_t count);
 CT_API int ct_bake_download_m2(CtBake b, float *m2_host_out, size_t count);
+
+/* ---- bake files ----------------------------------------------------------------------------------
+ *
+ * A bake is the most expensive object of this ABI and lived as long as its process.  ct_bake_save writes any bake to a file,
+ * ct_bake_load makes a CtBake from such a file on a handle of the same cloud, ct_bake_file_info reads and checks a file without
+ * a device.  The format is THIS PROJECT'S.
+ *
+ * Layout, little-endian: the 256-byte header below, then the sections, each starting at the next multiple of 16 bytes with the
+ * gap zero-filled, in this order:
+ *   1. node bytes, Nx Ny Nz of them, 0 or 1, node index (z Ny + y) Nx + x (ct_bake_mask's).  A dense bake has no such section;
+ *   2. the stored table: stored_entries values, float32 (CT_BAKE_F32) or IEEE binary16 (CT_BAKE_F16), in the order of
+ *      ct_bake_download_stored for a compact bake and of ct_bake_download for dense and sparse ones;
+ *   3. m2, stored_entries float32, adaptive bakes only;
+ *   4. counts, stored_entries uint32, adaptive bakes only;
+ *   5. at the next multiple of 8 bytes, a uint64: FNV-1a 64 (offset basis 0xCBF29CE484222325, prime 0x100000001B3, byte by
+ *      byte) over every byte of the file before it.  The file ends there.
+ * Nothing in the file depends on the machine that wrote it beyond its endianness.
+ *
+ * The volume hash identifies the cloud: with i the linear index of a level-0 texel of the handle's quantised density (x fastest)
+ * and t_i its byte, H = sum_i (t_i + 1) * ((i + 1) * 0x9E3779B97F4A7C15 mod 2^64) mod 2^64.  The sum does not depend on its order.
+ *
+ * ct_bake_save(b, path): every kind and format of bake.  Waits for the handle's stream, writes "<path>.tmp<pid>" in path's
+ * directory and renames it: a failure leaves no partial file under `path` (CT_E_INVAL: the file cannot be written).  ms fields are
+ * not stored.  Saving a loaded bake writes the bytes it was loaded from.
+ *
+ * ct_bake_file_info(path, out): no device, no handle.  CT_E_INVAL, with a message (ct_last_error(NULL)) that names the reason, for:
+ * a file that cannot be read or is shorter than header and checksum; a wrong magic; an unknown version; an unknown kind or
+ * format; any size outside the ranges of ct_network_bake (grid 2 .. 256, azimuths a multiple of 4 in 4 .. 64, cosines 2 .. 64,
+ * entries = their product, at most 2^26 stored entries) or of ct_bake_traced / ct_bake_traced_adaptive (samples, the adaptive
+ * parameters); counts that contradict each other (stored_entries against kind and active_nodes; a half or a network file that
+ * claims to be adaptive); non-zero reserved bytes; a length other than the one the header implies (a truncated section); a wrong
+ * checksum; node bytes other than 0 / 1 or whose number of ones is not active_nodes.
+ *
+ * ct_bake_load(h, path, out): ct_bake_file_info's checks, then, before anything is allocated: dims, the bits of sample_step,
+ * mean_free_path_m and cloud_size_m, the estimator, the CT_FLAG_TEX_FIXED8 bit and the volume hash must be the handle's
+ * (CT_E_INVAL, "a bake of another cloud / estimator", naming the field); a traced file on a CT_FLAG_SIMPLE_KERNEL handle is
+ * CT_E_INVAL as in ct_bake_traced.  For sparse and compact kinds the mask is computed again on this handle by the mask kernels;
+ * it must equal the file's node bytes (CT_E_INVAL), and list and slots are the recomputation's.  Everything is allocated before
+ * the first copy: CT_E_NOMEM leaves the handle as it was and *out = NULL.  The bake is current when the file's light, light
+ * colour and light intensity are the handle's, bit for bit; otherwise it loads with current = 0: rendering it is CT_E_STATE and
+ * ct_bake_retrace / ct_bake_retrace_adaptive / ct_bake_update work on it as on any bake whose light is stale.
+ *
+ * A loaded bake answers every accessor as the saved one did (the ms fields are 0), renders the same frames, and continues:
+ * traced(a), save, load, trace_more(b) is traced(a + b); adaptive(cap a), save, load, trace_adaptive_more(b) is adaptive(cap b)
+ * in mean, m2 and counts -- the live list is made again at load by the rule and compaction kernels from the stored state: the
+ * stored entries of active nodes that fail the rule, ascending (a file whose `capped` disagrees is CT_E_INVAL).  A loaded network
+ * bake takes ct_bake_update.
+ *
+ * The header, packed (every field is naturally aligned): */
+#define CT_BAKE_FILE_MAGIC "CTBAKE\r\n"   /* 8 bytes, no terminator */
+#define CT_BAKE_FILE_VERSION 1u
+enum { CT_BAKE_F32 = 0, CT_BAKE_F16 = 1 };
+typedef struct CtBakeFileHeader {
+    uint8_t  magic[8];             /*   0  CT_BAKE_FILE_MAGIC */
+    uint32_t version;              /*   8  CT_BAKE_FILE_VERSION */
+    uint32_t header_bytes;         /*  12  256 */
+    uint32_t kind;                 /*  16  CT_BAKE_DENSE / _SPARSE / _COMPACT */
+    uint32_t format;               /*  20  CT_BAKE_F32 / CT_BAKE_F16 */
+    uint32_t traced;               /*  24  0 / 1 */
+    uint32_t adaptive;             /*  28  0 / 1 */
+    uint32_t grid[3];              /*  32  Nx, Ny, Nz */
+    uint32_t azimuths;             /*  44  Nphi */
+    uint32_t cosines;              /*  48  Nc */
+    uint32_t margin_texels;        /*  52  M (0 for a dense bake) */
+    uint64_t entries;              /*  56  the virtual count Nx Ny Nz Nphi Nc */
+    uint64_t stored_entries;       /*  64  values in the table section */
+    uint64_t active_nodes;         /*  72  (a dense bake: Nx Ny Nz) */
+    float    light[3];             /*  80  CtBakeInfo's light, */
+    float    axis_a[3];            /*  92  axis_a */
+    float    axis_b[3];            /* 104  and axis_b */
+    uint32_t dims[3];              /* 116  the volume the table was made on */
+    uint32_t sample_step_bits;     /* 128  the bits of CtScene's sample_step, */
+    uint32_t mean_free_path_bits;  /* 132  mean_free_path_m */
+    uint32_t cloud_size_bits;      /* 136  and cloud_size_m */
+    int32_t  estimator;            /* 140  CtEstimator */
+    uint32_t tex_fixed8;           /* 144  1: the handle had CT_FLAG_TEX_FIXED8 */
+    uint32_t light_color_bits[3];  /* 148  the bits of the handle's light colour */
+    uint32_t light_intensity_bits; /* 160  and intensity at the bake */
+    uint32_t samples;              /* 164  CtBakeTraceInfo's samples */
+    uint64_t volume_hash;          /* 168  H above */
+    uint64_t paths;                /* 176  CtBakeTraceInfo's paths */
+    uint32_t round_samples;        /* 184  CtBakeAdaptive's parameters, max_samples as it is in force; 0 unless adaptive */
+    uint32_t max_samples;          /* 188 */
+    uint32_t zero_samples;         /* 192 */
+    uint32_t rel_tol_bits;         /* 196 */
+    uint32_t abs_tol_bits;         /* 200 */
+    uint32_t rounds;               /* 204  CtBakeAdaptiveInfo's rounds, */
+    uint64_t converged;            /* 208  converged */
+    uint64_t capped;               /* 216  and capped */
+    uint8_t  reserved[32];         /* 224  zero */
+} CtBakeFileHeader;                /* 256 bytes */
+typedef struct CtBakeFileInfo {
+    CtBakeFileHeader header;       /*   0  as read */
+    uint64_t file_bytes;           /* 256 */
+    uint64_t nodes_offset;         /* 264  byte offsets of the sections; 0 for a section the file does not have */
+    uint64_t table_offset;         /* 272 */
+    uint64_t m2_offset;            /* 280 */
+    uint64_t counts_offset;        /* 288 */
+    uint64_t checksum_offset;      /* 296 */
+    uint64_t checksum;             /* 304 */
+} CtBakeFileInfo;                  /* 312 bytes */
+
+CT_API int ct_bake_save(CtBake b, const char *path);
+CT_API int ct_bake_file_info(const char *path, CtBakeFileInfo *out);   /* errors: ct_last_error(NULL) */
+CT_API int ct_bake_load(CtHandle h, const char *path, CtBake *out);
+/* Diagnostic: the handle's volume hash, by the device reduction ct_bake_save and ct_bake_load use. */
+CT_API int ct_debug_volume_hash(CtHandle h, uint64_t *hash_out);
+
+/* ---- half tables: a bake whose stored table is IEEE binary16 ---------------------------------------
+ *
+ * The table is the one large, randomly read array of the baked subframe.  ct_bake_half(h, src, out) makes a NEW bake with
+ * format CT_BAKE_F16 from any float32 bake of h: same kind, grid, frame, mask, list and slots (copies: src stays as it is and can
+ * be destroyed), its stored table the binary16 value nearest to each float32 value, ties to even, subnormals included, the
+ * sign of zero kept (ct_debug_half_round is the rounding, on the host).  If any stored value is a NaN, infinite, or rounds to
+ * an infinity (|v| >= 65520) the call is CT_E_INVAL -- a condition, not a measurement; the message gives the number of such
+ * values and the first stored index -- with *out = NULL and nothing changed.  The conversion kernel counts them; the host reads
+ * that count (4 bytes) and, only when it refuses, the index.
+ *
+ * The lookup of a half bake is the lookup of "the network baked into a probe table" / "the compact bake": same cell split,
+ * weights, lerp order k, j, x, y, z, slot loads, no branch on activity.  Each tap pair is two adjacent binary16 values at half
+ * index (probe + j) Nc + k0, widened exactly to float32 before the first lerp.  Every frame is therefore defined bit for bit by
+ * the rounded table: ct_bake_download / ct_bake_download_stored return the stored values widened to float32, and the float32
+ * lookup applied to them is the half bake's lookup.  Every ct_baked_render_* entry point and ct_debug_bake_lookup take it.
+ *
+ * A half bake is final: traced and samples are carried over for information, adaptive is 0 (no m2, no counts);
+ * ct_bake_update, ct_bake_trace_more, ct_bake_retrace, ct_bake_trace_adaptive_more, ct_bake_retrace_adaptive and ct_bake_half on
+ * it are CT_E_INVAL (bake again from float32); after ct_set_light it is simply not current.  ct_bake_storage_info reports
+ * table_bytes = 2 * stored_entries.  The entry limits are unchanged.  ct_bake_save / ct_bake_load carry it with a 2-byte table
+ * section and no m2 or counts sections. */
+CT_API int ct_bake_half(CtHandle h, CtBake src, CtBake *out);
+CT_API int ct_bake_format(CtBake b, uint32_t *format_out);                             /* CT_BAKE_F32 / CT_BAKE_F16 */
+/* The stored bits.  count must equal stored_entries; CT_E_INVAL on a float32 bake. */
+CT_API int ct_bake_download_half(CtBake b, uint16_t *table_host_out, size_t count);
+CT_API uint16_t ct_debug_half_round(float x);   /* float32 -> binary16 bits, as the conversion kernel rounds (no device) */
 
 /* ct_network_render_subframe / _accumulate / _shard_subframe / _shard_accumulate with the table in the network's place. */
 CT_API int ct_baked_render_subframe(CtHandle h, CtBake b, const CtNetworkRender *p, uint32_t subframe_id, float *frame_rgba_dev);

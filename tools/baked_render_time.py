@@ -18,9 +18,15 @@ route the table's and the index's bytes, the medians of the bake's wall ms and o
 over the repeats, and whether the three routes' means after --subframes subframes are bit-identical (exit 1 if not).  Then one
 grid beyond the dense limit, --beyond^3 (128), compact only: the active share and the sizes, or -- should (active + 1) x azimuths x
 cosines exceed 2^26 -- the library's CT_E_INVAL message.
+--half: instead, what a binary16 table (ct_bake_half) costs and saves.  Per grid (default 64^3) one sparse
+float32 bake and its half copy take turns, --repeats rounds of 16 subframes each after one warm-up round, and one JSON line
+carries, for both: ct_debug_baked_render_time as lowest / median / highest, the table's bytes; the relative L2 of the half bake's
+64-subframe mean to the float32 bake's, beside the distance between two float32 means of disjoint subframes (1 .. 64 against
+65 .. 128: the noise floor); and the wall ms of ct_bake_save and ct_bake_load of each table (to --scratch, default the system's
+temporary directory).
 Needs a GPU.  No threshold: the table's resolution is the user's trade.
     python tools/baked_render_time.py [--repeats 5] [--volume 512] [--size 1024] [--subframes 16] [--grids 16 32 64]
-                                      [--azimuths 16] [--cosines 8] [--direct] [--bias 1.0] [--sparse | --compact [--beyond 128]]"""
+                                      [--azimuths 16] [--cosines 8] [--direct] [--bias 1.0] [--sparse | --compact [--beyond 128] | --half [--scratch DIR]]"""
 import argparse, json, statistics, sys, time
 from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
@@ -146,6 +152,57 @@ def compact_against_the_others(a, tr, net, common):
     return same
 
 
+def half_against_float(a, tr, net, common):
+    """The --half protocol."""
+    import os, tempfile
+    import numpy as np
+    grids = a.grids if a.grids != [16, 32, 64] else [64]
+    for g in grids:
+        src = tr.network_bake(net, (g, g, g), a.azimuths, a.cosines, sparse=True)
+        half = src.half()
+        routes = (("float32", src), ("half", half))
+        gpu = {name: [] for name, _ in routes}
+        for i in range(a.repeats + 1):          # (the first round is the warm-up)
+            for name, bake in routes:
+                for sid in range(1, 17):
+                    tr.baked_render_subframe(bake, sid, out=False, direct=a.direct)
+                    if i:
+                        gpu[name].append(tr.baked_render_time())
+
+        def rel(x, y):
+            return float(np.sqrt(((x - y) ** 2).sum() / (y ** 2).sum()))
+
+        # (a mean over subframes 65 .. 128 would fold onto a count of 64: both means are taken from a count of zero)
+        tr.reset()
+        tr.baked_render_accumulate(src, 1, 64, direct=a.direct)
+        f_a = tr.mean()[..., :3].astype(np.float64)
+        tr.reset()
+        tr.baked_render_accumulate(half, 1, 64, direct=a.direct)
+        h_a = tr.mean()[..., :3].astype(np.float64)
+        tr.reset()
+        tr.baked_render_accumulate(src, 1, 128, direct=a.direct)
+        f_ab = tr.mean()[..., :3].astype(np.float64)
+        f_b = 2.0 * f_ab - f_a                      # the mean of subframes 65 .. 128, from the two running means
+        line = {"route": "ct_bake_half against its float32 bake", **common, "grid": [g, g, g, a.azimuths, a.cosines], "kind": "sparse",
+                "active_share": src.sparse_info["active_nodes"] / src.sparse_info["nodes"], "subframes_timed": len(gpu["half"]),
+                "relative_l2_half_mean_to_float32_mean_64_subframes": rel(h_a, f_a),
+                "relative_l2_float32_subframes_65_128_to_1_64": rel(f_b, f_a)}
+        with tempfile.TemporaryDirectory(dir=a.scratch) as d:
+            for name, bake in routes:
+                path = os.path.join(d, name + ".bake")
+                save = wall_ms(lambda: bake.save(path))
+                t0 = time.perf_counter()
+                loaded = tr.load_bake(path)
+                load = (time.perf_counter() - t0) * 1e3
+                loaded.close()
+                line.update({f"{name}_baked_subframe_gpu_ms_min_median_max": [min(gpu[name]), statistics.median(gpu[name]), max(gpu[name])],
+                             f"{name}_table_bytes": bake.storage_info["table_bytes"], f"{name}_file_bytes": os.path.getsize(path),
+                             f"{name}_save_wall_ms": save, f"{name}_load_wall_ms": load})
+        print(json.dumps(line), flush=True)
+        half.close()
+        src.close()
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
@@ -160,6 +217,8 @@ if __name__ == "__main__":
     ap.add_argument("--sparse", action="store_true")
     ap.add_argument("--compact", action="store_true")
     ap.add_argument("--beyond", type=int, default=128)
+    ap.add_argument("--half", action="store_true")
+    ap.add_argument("--scratch", default=None)
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -175,6 +234,11 @@ if __name__ == "__main__":
     common = {"network": [200, 1, 3], "output_bias_raised_by": a.bias, "volume": a.volume, "frame": [a.size, a.size], "repeats": a.repeats,
               "direct": a.direct}
 
+    if a.half:
+        half_against_float(a, tr, net, common)
+        net.close()
+        tr.close()
+        sys.exit(0)
     if a.sparse or a.compact:
         ok = compact_against_the_others(a, tr, net, common) if a.compact else sparse_against_dense(a, tr, net, common)
         net.close()

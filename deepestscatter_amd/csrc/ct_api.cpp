@@ -2301,7 +2301,7 @@ extern "C" int ct_synchronize(CtHandle h)
 
 static_assert(sizeof(CtPointRadianceTask) == 40, "Gpu::PointRadianceTask is 40 bytes (PointRadianceTask.h:70-77)");
 
-// The launch half of ct_point_radiance_launch, which the traced bake (ct_neural.cpp) shares: `launches` experiments, frames
+// The launch half of ct_point_radiance_launch, which the traced bake (ct_bake.cpp) shares: `launches` experiments, frames
 // first_frame_id .., of the `count` point tasks whose rays `rays` enqueues into h->pt.primary / h->pt.pixels (grown to
 // pad64(count) entries by then).  The results are h->pt.frames[f * pad64(count) + i]; `fold` enqueues what consumes them.
 // Waits for the stream, books the estimator's time and the paths.  sc: the scene the estimator runs with.
@@ -2727,7 +2727,7 @@ extern "C" int ct_collector_destroy(CtCollector c)
 }
 
 // ---- the adaptive frame (ct_adaptive_frame_*): the progressive image in rounds that go to the unconverged pixels only ----------
-// Kernels: ct_adaptive.hip.  The scheme is bake_trace_adaptive's (ct_neural.cpp): a round's live list goes through point_launch in
+// Kernels: ct_adaptive.hip.  The scheme is bake_trace_adaptive's (ct_bake.cpp): a round's live list goes through point_launch in
 // chunks of whole groups of 64 and passes, the fold of the round's last pass counts the survivors per wave, a scan and a ranked
 // write compact them into the other list, and the host reads one word per round behind the wait point_launch makes anyway.
 struct CtAdaptiveFrame_ {

@@ -1,4 +1,4 @@
-// ct_bake_file.hip -- the two kernels of include/cloudtrace.h, "bake files" and "half tables" (host side: ct_neural.cpp): the
+// ct_bake_file.hip -- the two kernels of include/cloudtrace.h, "bake files" and "half tables" (host side: ct_bake.cpp): the
 // volume hash that ties a bake file to its cloud, and the float32 -> binary16 conversion of ct_bake_half.  The half lookup itself
 // is bake_lookup<COMPACT, HALF> in ct_kernels.hip.
 #include <algorithm>

@@ -1,4 +1,4 @@
-// ct_bake_trace.hip -- the kernels of the traced bake (include/cloudtrace.h, "the traced bake"; host side: ct_neural.cpp).
+// ct_bake_trace.hip -- the kernels of the traced bake (include/cloudtrace.h, "the traced bake"; host side: ct_bake.cpp).
 // A traced bake fills a probe table with Monte-Carlo means of ct_point_radiance_launch's estimator: the task kernel turns a
 // range of the table's stored entries into that entry point's rays, the estimator kernels of ct_kernels.hip trace them, and the
 // fold kernel folds the per-experiment results into the table with PointRadianceTask::addExperimentResult's arithmetic.

@@ -1,5 +1,5 @@
 // ct_handle.hpp -- the handle behind CtHandle and what the host translation units that work on it share (ct_api.cpp: lifetime,
-// scheduler, buffers and diagnostics; ct_neural.cpp: descriptors and the scattering network).  Private: not installed, and
+// scheduler, buffers and diagnostics; ct_neural.cpp: descriptors, the scattering network and its renderer; ct_bake.cpp: the bakes).  Private: not installed, and
 // ct_group.hip keeps to the C ABI.
 #pragma once
 

@@ -1,4 +1,4 @@
-// ct_internal.hpp -- launcher declarations shared by ct_kernels.hip and the host files (ct_api.cpp, ct_neural.cpp).
+// ct_internal.hpp -- launcher declarations shared by ct_kernels.hip and the host files (ct_api.cpp, ct_neural.cpp, ct_bake.cpp).
 #pragma once
 
 #include <hip/hip_runtime.h>

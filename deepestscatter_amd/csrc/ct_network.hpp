@@ -1,4 +1,4 @@
-// ct_network.hpp -- what ct_neural.cpp needs of ct_network.hip: the handle-free half of ct_network_create / ct_network_eval.
+// ct_network.hpp -- what ct_neural.cpp and ct_bake.cpp need of ct_network.hip: the handle-free half of ct_network_create / ct_network_eval.
 // ct_network_destroy, ct_debug_network_time and ct_debug_bf16_round need no handle and are defined in ct_network.hip itself.
 #pragma once
 

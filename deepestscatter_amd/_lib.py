@@ -40,6 +40,10 @@ EXPORTS = [
     "ct_group_adaptive_frame_device_ptr", "ct_group_adaptive_frame_destroy",
     "ct_bake_save", "ct_bake_file_info", "ct_bake_load", "ct_debug_volume_hash", "ct_bake_half", "ct_bake_format", "ct_bake_download_half",
     "ct_debug_half_round",
+    "ct_group_network_bake", "ct_group_bake_traced", "ct_group_bake_traced_adaptive", "ct_group_bake_load", "ct_group_bake_update",
+    "ct_group_bake_trace_more", "ct_group_bake_retrace", "ct_group_bake_trace_adaptive_more", "ct_group_bake_retrace_adaptive",
+    "ct_group_bake_shard", "ct_group_bake_spans", "ct_group_baked_render_accumulate", "ct_group_bake_destroy", "ct_debug_group_bake_exchange",
+    "ct_debug_bake_shard",
 ]
 # ... and the declared symbols whose names have digits (the list above is matched by name pattern)
 DEBUG_EXPORTS = ["ct_debug_bf16_round"]
@@ -511,6 +515,21 @@ def load():
         "ct_group_adaptive_frame_download": (i32, [vp, u32, vp, C.c_size_t]),
         "ct_group_adaptive_frame_device_ptr": (i32, [vp, u32, C.POINTER(vp)]),
         "ct_group_adaptive_frame_destroy": (i32, [vp]),
+        "ct_group_network_bake": (i32, [vp, vp, C.POINTER(CtBakeDesc), u32, C.POINTER(vp)]),   # -> CtGroupBake
+        "ct_group_bake_traced": (i32, [vp, C.POINTER(CtBakeDesc), u32, u32, C.POINTER(vp)]),
+        "ct_group_bake_traced_adaptive": (i32, [vp, C.POINTER(CtBakeDesc), u32, C.POINTER(CtBakeAdaptive), C.POINTER(vp)]),
+        "ct_group_bake_load": (i32, [vp, C.c_char_p, C.POINTER(vp)]),
+        "ct_group_bake_update": (i32, [vp, vp]),
+        "ct_group_bake_trace_more": (i32, [vp, u32]),
+        "ct_group_bake_retrace": (i32, [vp, u32]),
+        "ct_group_bake_trace_adaptive_more": (i32, [vp, u32]),
+        "ct_group_bake_retrace_adaptive": (i32, [vp]),
+        "ct_group_bake_shard": (i32, [vp, u32, C.POINTER(vp)]),
+        "ct_group_bake_spans": (i32, [vp, vp, C.c_size_t]),
+        "ct_group_baked_render_accumulate": (i32, [vp, vp, C.POINTER(CtNetworkRender), u32, u32]),
+        "ct_group_bake_destroy": (i32, [vp]),
+        "ct_debug_group_bake_exchange": (i32, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+        "ct_debug_bake_shard": (i32, [vp, C.POINTER(CtBakeDesc), u32, u32, C.POINTER(CtBakeAdaptive), u32, u32, C.POINTER(vp)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

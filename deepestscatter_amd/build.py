@@ -19,7 +19,7 @@ ROOT = PKG.parent
 LIB = PKG / "libcloudtrace.so"
 
 SOURCES = ["ct_kernels.hip", "ct_group.hip", "ct_network.hip", "ct_bake_trace.hip", "ct_bake_file.hip", "ct_collect.hip", "ct_adaptive.hip", "ct_api.cpp", "ct_neural.cpp", "ct_bake.cpp", "ct_host.cpp"]
-HEADERS = [CSRC / "ct_device.hpp", CSRC / "ct_internal.hpp", CSRC / "ct_handle.hpp", CSRC / "ct_devmem.hpp", CSRC / "ct_exchange.hpp", CSRC / "ct_sched.hpp", CSRC / "ct_network.hpp", CSRC / "ct_plan.hpp", CSRC / "ct_bakefile.hpp", CSRC / "ct_bake.hpp",
+HEADERS = [CSRC / "ct_device.hpp", CSRC / "ct_internal.hpp", CSRC / "ct_handle.hpp", CSRC / "ct_devmem.hpp", CSRC / "ct_exchange.hpp", CSRC / "ct_sched.hpp", CSRC / "ct_network.hpp", CSRC / "ct_plan.hpp", CSRC / "ct_bakefile.hpp", CSRC / "ct_bake.hpp", CSRC / "ct_bake_group.hpp",
            ROOT / "include" / "cloudtrace.h",
            ROOT / "include" / "ct_fmath.h", PKG / "host" / "VdbReader.h"]
 

@@ -921,8 +921,8 @@ class TracerGroup:
 
     def close(self):
         if getattr(self, "g", None):
-            for net in list(getattr(self, "_networks", ())) + list(getattr(self, "_adaptive_frames", ())):
-                net.close()       # (a group's networks and adaptive frames go before the group)
+            for net in list(getattr(self, "_bakes", ())) + list(getattr(self, "_networks", ())) + list(getattr(self, "_adaptive_frames", ())):
+                net.close()       # (a group's bakes, networks and adaptive frames go before the group)
             self.L.ct_group_destroy(self.g)
             self.g = None
 
@@ -961,6 +961,59 @@ class TracerGroup:
         p = CloudTracer._network_render_params(transform, rgb_scale, band_pixels, direct)
         self._check(self.L.ct_group_network_render_accumulate(self.g, net.gn if net is not None else None, C.byref(p),
                                                               first_subframe_id & 0xFFFFFFFF, count))
+
+    # -- bakes on the group (ct_group_bake_*): built across the shards, complete on every shard ------------------------
+    @staticmethod
+    def _bake_args(who, grid, azimuths, cosines, sparse, compact):
+        if sparse and compact:
+            raise ValueError(f"{who}: sparse or compact, not both")
+        d = _lib.CtBakeDesc(_lib.CT_ABI_VERSION, (C.c_uint32 * 3)(*[int(v) for v in grid]), int(azimuths), int(cosines))
+        return d, _lib.CT_BAKE_COMPACT if compact else _lib.CT_BAKE_SPARSE if sparse else _lib.CT_BAKE_DENSE
+
+    def network_bake(self, net, grid, azimuths: int, cosines: int, sparse: bool = False, compact: bool = False):
+        """ct_group_network_bake -> deepestscatter_amd.network.GroupBake: CloudTracer.network_bake of the GroupNetwork `net`, every
+        shard baking its span of the nodes; every shard then holds the single-GPU bake, bit for bit."""
+        from .network import GroupBake
+        d, kind = self._bake_args("network_bake", grid, azimuths, cosines, sparse, compact)
+        gb = C.c_void_p()
+        self._check(self.L.ct_group_network_bake(self.g, net.gn if net is not None else None, C.byref(d), kind, C.byref(gb)))
+        return GroupBake(self, gb)
+
+    def traced_bake(self, grid, azimuths: int, cosines: int, samples: int, sparse: bool = False, compact: bool = False):
+        """ct_group_bake_traced -> GroupBake: CloudTracer.traced_bake with every shard tracing its span of the nodes."""
+        from .network import GroupBake
+        d, kind = self._bake_args("traced_bake", grid, azimuths, cosines, sparse, compact)
+        gb = C.c_void_p()
+        self._check(self.L.ct_group_bake_traced(self.g, C.byref(d), kind, int(samples), C.byref(gb)))
+        return GroupBake(self, gb)
+
+    def traced_bake_adaptive(self, grid, azimuths: int, cosines: int, round_samples: int, max_samples: int, rel_tol: float = 2e-2,
+                             abs_tol: float = 1e-4, zero_samples: int = 100000, sparse: bool = False, compact: bool = False):
+        """ct_group_bake_traced_adaptive -> GroupBake: CloudTracer.traced_bake_adaptive with every shard running its own rounds over
+        its span; a shard whose entries all stop early ends sooner."""
+        from .network import GroupBake
+        d, kind = self._bake_args("traced_bake_adaptive", grid, azimuths, cosines, sparse, compact)
+        p = _lib.CtBakeAdaptive(_lib.CT_ABI_VERSION, int(round_samples), int(max_samples), int(zero_samples), float(rel_tol), float(abs_tol))
+        gb = C.c_void_p()
+        self._check(self.L.ct_group_bake_traced_adaptive(self.g, C.byref(d), kind, C.byref(p), C.byref(gb)))
+        return GroupBake(self, gb)
+
+    def load_bake(self, path):
+        """ct_group_bake_load -> GroupBake: CloudTracer.load_bake on every shard; a single-GPU file loads on a group and continues
+        under the group's span rule."""
+        import os
+        from .network import GroupBake
+        gb = C.c_void_p()
+        self._check(self.L.ct_group_bake_load(self.g, os.fsencode(path), C.byref(gb)))
+        return GroupBake(self, gb)
+
+    def baked_render_accumulate(self, bake, first_subframe_id: int, count: int, transform="linear", rgb_scale=(1.0, 1.0, 1.0),
+                                band_pixels: int = 0, direct: bool = False):
+        """ct_group_baked_render_accumulate: CloudTracer.baked_render_shard_accumulate of the GroupBake `bake` on every shard, each
+        on a host thread of its own; mean(), m2() and tonemap() then give what baked_render_accumulate gives on one tracer."""
+        p = CloudTracer._network_render_params(transform, rgb_scale, band_pixels, direct)
+        self._check(self.L.ct_group_baked_render_accumulate(self.g, bake.gb if bake is not None else None, C.byref(p),
+                                                            first_subframe_id & 0xFFFFFFFF, count))
 
     def adaptive_frame(self, **params):
         """ct_group_adaptive_frame_create -> adaptive.GroupAdaptiveFrame: CloudTracer.adaptive_frame's image with every shard

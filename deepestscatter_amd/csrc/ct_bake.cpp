@@ -5,6 +5,8 @@
 // rounds, keeps m2 and count per entry and stops entries by the reference's rule: its fold, scan and compaction kernels are in
 // ct_bake_trace.hip too.  Half tables (ct_bake_half) and bake files (ct_bake_save, ct_bake_load) are at the end; the file's
 // parser is the device-free ct_bakefile.hpp, their two kernels ct_bake_file.hip.  What crosses to ct_neural.cpp: ct_bake.hpp.
+// A bake on a group (ct_group_bake_*, ct_group.hip) is a CtBake_ per shard that builds a span of the node list; the span, the
+// checks a group call passes through and the exchange between the shards are here, behind ct_bake_group.hpp.
 #include <cerrno>
 #include <cmath>
 #include <cstdio>
@@ -15,6 +17,7 @@
 #include <unistd.h>
 
 #include "ct_bake.hpp"
+#include "ct_bake_group.hpp"
 #include "ct_bakefile.hpp"
 #include "ct_network.hpp"
 
@@ -72,6 +75,11 @@ struct CtBake_ : BakeState, BakeShape {
     // ct_bake_half: the stored table as binary16 in d_half, no d_table.  Final: nothing bakes or traces into it.
     bool half = false;
     DevBuf<uint16_t> d_half;
+    // A bake on a group (ct_group_bake_*): shard `shard` of `shards` builds and continues only the positions
+    // [span_lo, span_hi) of the node list -- all nodes for a dense bake -- which are the floats [range_lo, range_hi) of the stored
+    // arrays; the group's exchange brings the rest.  shards == 1: everything, and none of the four is read.
+    uint32_t shard = 0, shards = 1;
+    uint64_t span_lo = 0, span_hi = 0, range_lo = 0, range_hi = 0;
 };
 
 static uint64_t bake_nodes(const BakeShape &s)
@@ -116,6 +124,46 @@ static BakeShape bake_shape(CtHandle h, const uint32_t grid[3], uint32_t azimuth
 static uint64_t bake_probes_total(const CtBake_ *b)
 {
     return b->entries / b->cosines;
+}
+
+// The nodes a build covers: every node of a dense bake, the active ones in the list's order otherwise.  A bake on a group covers
+// its span of them.
+static uint64_t bake_cover(const CtBake_ *b)
+{
+    return b->sparse ? b->active : bake_nodes(*b);
+}
+static void bake_span(const CtBake_ *b, uint64_t *lo, uint64_t *hi)
+{
+    *lo = b->shards == 1u ? 0u : b->span_lo;
+    *hi = b->shards == 1u ? bake_cover(b) : b->span_hi;
+}
+
+// Cuts b, whose mask is counted, for shard `shard` of `shards`: positions [shard A / shards, (shard + 1) A / shards) of the A nodes
+// it covers (A <= 2^24, shards <= 64), and the floats of the stored arrays they are.  A sparse bake reads the two ends of its
+// span from the list.
+static int bake_cut(CtHandle h, CtBake_ *b, uint32_t shard, uint32_t shards)
+{
+    const uint64_t A = bake_cover(b), block = (uint64_t)b->azimuths * b->cosines;
+    b->shard = shard;
+    b->shards = shards;
+    b->span_lo = (uint64_t)shard * A / shards;
+    b->span_hi = ((uint64_t)shard + 1u) * A / shards;
+    if (b->compact) {
+        b->range_lo = block + b->span_lo * block;
+        b->range_hi = block + b->span_hi * block;
+    } else if (b->sparse && b->span_lo < b->span_hi && shards != 1u) {
+        uint32_t first = 0, last = 0;
+        HIPCHK(h, hipMemcpy(&first, b->d_list + b->span_lo, sizeof first, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(&last, b->d_list + (b->span_hi - 1u), sizeof last, hipMemcpyDeviceToHost));
+        b->range_lo = (uint64_t)first * block;
+        b->range_hi = ((uint64_t)last + 1u) * block;
+    } else if (b->sparse) {
+        b->range_lo = b->range_hi = 0;
+    } else {
+        b->range_lo = b->span_lo * block;
+        b->range_hi = b->span_hi * block;
+    }
+    return CT_OK;
 }
 
 // The record of probe `index` = ((z Ny + y) Nx + x) Nphi + j: its position node and u_j, made in double and rounded once.
@@ -340,13 +388,15 @@ static int bake_store_piece(CtHandle h, const CtBake_ *b, float *table, uint64_t
     return CT_OK;
 }
 
-// Fills `table` (b->stored floats, allocated) for the handle's light and network n: the probes in chunks through the handle's
+// Fills `table` (b->stored floats, allocated) for the handle's light and network n: the probes of b's span in chunks through the handle's
 // scratch, one gather per piece and one evaluation per polar node.  b's frame is the new light's already.
 // A sparse bake zeroes the table first and runs only the probes of its list; a compact one zeroes only the zero block.
 static int bake_run(CtHandle h, CtNetwork n, CtBake_ *b, float *table)
 {
     CtHandle_::NetScratch &s = h->net;
-    const uint64_t probes = b->sparse ? b->active * b->azimuths : bake_probes_total(b);
+    uint64_t lo, hi;
+    bake_span(b, &lo, &hi);
+    const uint64_t probes_lo = lo * b->azimuths, probes_hi = hi * b->azimuths, probes = probes_hi - probes_lo;
     const size_t chunk = (size_t)std::min<uint64_t>(probes, std::min<size_t>(net_descriptor_limit(h), (size_t)1 << 20));
     const DescriptorScale ds = descriptor_scale(h);
     std::vector<float> pos(b->sparse ? 0 : 3 * chunk), dir(b->sparse ? 0 : 3 * chunk);
@@ -355,10 +405,10 @@ static int bake_run(CtHandle h, CtNetwork n, CtBake_ *b, float *table)
         if (b->sparse) {
             const uint64_t zeroed = b->compact ? (uint64_t)b->azimuths * b->cosines : b->entries;
             HIPCHK(h, hipMemsetAsync(table, 0, (size_t)zeroed * sizeof(float), h->stream));
-            if (probes == 0u) {
-                HIPCHK(h, hipStreamSynchronize(h->stream));
-                return CT_OK;
-            }
+        }
+        if (probes == 0u) {   // (a bake without active nodes, or a shard's empty span)
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            return CT_OK;
         }
         int rc = net_reserve(h, chunk, false);
         if (rc == CT_OK) {
@@ -374,8 +424,8 @@ static int bake_run(CtHandle h, CtNetwork n, CtBake_ *b, float *table)
                 return rc;
             }
         }
-        for (uint64_t first = 0; first < probes; first += chunk) {
-            const uint32_t count = (uint32_t)std::min<uint64_t>(chunk, probes - first);
+        for (uint64_t first = probes_lo; first < probes_hi; first += chunk) {
+            const uint32_t count = (uint32_t)std::min<uint64_t>(chunk, probes_hi - first);
             rc = bake_chunk_records(h, b, first, count, pos, dir, &records_ms);
             if (rc != CT_OK) {
                 return rc;
@@ -479,7 +529,10 @@ static uint32_t bake_trace_budget(CtHandle h)
 // estimator runs on a copy of the handle's scene in CT_MODE_SUN_MULTIPLE_SCATTER.  Books b's counts and times.
 static int bake_trace(CtHandle h, CtBake_ *b, float *table, uint32_t samples)
 {
-    const uint64_t total = bake_trace_total(b);
+    const uint64_t block = (uint64_t)b->azimuths * b->cosines;
+    uint64_t lo, hi;
+    bake_span(b, &lo, &hi);
+    const uint64_t begin = lo * block, end = hi * block, total = end - begin;   // (a bake on a group: its span's entries)
     b->trace_ms = b->fold_ms = 0;
     if (samples == 0u || total == 0u) {
         b->samples += samples;
@@ -496,10 +549,10 @@ static int bake_trace(CtHandle h, CtBake_ *b, float *table, uint32_t samples)
     CtHandle_::PointBuffers &pt = h->pt;
     const double render_before = h->render_ms;
     double fold_ms = 0;
-    for (uint64_t first = 0; first < total; first += chunk) {
+    for (uint64_t first = begin; first < end; first += chunk) {
         BakeTraceArgs a = bake_trace_args(b);
         a.first = first;
-        a.n = (uint32_t)std::min<uint64_t>(chunk, total - first);
+        a.n = (uint32_t)std::min<uint64_t>(chunk, end - first);
         a.n_pad = (a.n + 63u) & ~63u;
         const uint32_t per_pass = std::min(0xffffu, std::max(1u, budget / a.n_pad));
         for (uint32_t at = 0; at < samples; at += per_pass) {
@@ -614,7 +667,9 @@ static void bake_adaptive_adopt(CtBake_ *b, BakeAdaptiveSet &s)
 // round's live entries go through bake_trace's chunks (whole groups of 64: a chunk's waves are the live list's) and passes;
 // behind the last fold of the round follow the scan, the compacting write into the other list and the read of the survivors'
 // number, which point_launch's wait covers.  Books b's counts and times; b->live entries are left at the cap, unconverged.
-static int bake_trace_adaptive(CtHandle h, CtBake_ *b, const BakeAdaptiveTarget &t, uint64_t n_live, bool listed)
+// live_at: where in t.live[b->live_cur] the n_live entries begin -- a shard's sub-range of a merged list; the wave counts and the
+// list a round writes start at 0 whatever it is.
+static int bake_trace_adaptive(CtHandle h, CtBake_ *b, const BakeAdaptiveTarget &t, uint64_t n_live, bool listed, uint64_t live_at = 0)
 {
     b->trace_ms = b->fold_ms = b->test_ms = 0;
     const uint32_t R = b->ap.round_samples, budget = bake_trace_budget(h);
@@ -634,7 +689,7 @@ static int bake_trace_adaptive(CtHandle h, CtBake_ *b, const BakeAdaptiveTarget 
         if (chunk >= 64u) {
             chunk &= ~63u;
         }
-        const uint32_t *live_in = listed ? t.live[b->live_cur] : nullptr;
+        const uint32_t *live_in = listed ? t.live[b->live_cur] + live_at : nullptr;
         uint32_t *live_out = t.live[listed ? b->live_cur ^ 1 : 0];
         uint32_t survivors = 0;
         for (uint32_t first = 0; first < L; first += chunk) {
@@ -689,6 +744,7 @@ static int bake_trace_adaptive(CtHandle h, CtBake_ *b, const BakeAdaptiveTarget 
         b->paths += (uint64_t)L * R;
         b->live_cur = listed ? b->live_cur ^ 1 : 0;
         listed = true;
+        live_at = 0;
         n_live = survivors;
         b->live = n_live;   // (with every round: a call that fails later leaves whole rounds)
     }
@@ -709,15 +765,24 @@ static int bake_trace_adaptive_fresh(CtHandle h, CtBake_ *b, const BakeAdaptiveT
         HIPCHK(h, hipMemsetAsync(t.counts, 0, (size_t)b->stored * sizeof(uint32_t), h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         const int up = bake_upload_trace_tables(h, b);
-        return up != CT_OK ? up : bake_trace_adaptive(h, b, t, bake_trace_total(b), false);
+        if (up != CT_OK || b->shards == 1u) {
+            return up != CT_OK ? up : bake_trace_adaptive(h, b, t, bake_trace_total(b), false);
+        }
+        // a bake on a group: the first round's list is the span's stored indices, written out
+        const uint64_t block = (uint64_t)b->azimuths * b->cosines, n = (b->span_hi - b->span_lo) * block;
+        HIPCHK(h, launch_bake_live_iota(t.live[0], (uint32_t)(b->span_lo * block), (uint32_t)n, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        b->live_cur = 0;
+        return bake_trace_adaptive(h, b, t, n, true);
     });
 }
 
 // ct_network_bake, ct_network_bake_sparse and ct_network_bake_compact: one validation, one order of errors.  kind: CT_BAKE_DENSE,
 // _SPARSE or _COMPACT.  trace_samples: ct_bake_traced, which takes no network (n is NULL) and fills the table with that many
 // experiments per entry.  adaptive: ct_bake_traced_adaptive, traced likewise, in rounds under the stopping rule of *adaptive.
+// shard of shards: ct_group_bake_*, which builds that span of the bake on this handle and exchanges the rest.
 static int bake_create(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtBake *out, uint32_t kind, const uint32_t *trace_samples = nullptr,
-                       const CtBakeAdaptive *adaptive = nullptr)
+                       const CtBakeAdaptive *adaptive = nullptr, uint32_t shard = 0, uint32_t shards = 1)
 {
     const bool sparse = kind != CT_BAKE_DENSE, compact = kind == CT_BAKE_COMPACT, traced = trace_samples != nullptr || adaptive != nullptr;
     const char *const who = adaptive ? "ct_bake_traced_adaptive" : traced ? "ct_bake_traced" : compact ? "ct_network_bake_compact" : sparse ? "ct_network_bake_sparse" : "ct_network_bake";
@@ -811,6 +876,12 @@ static int bake_create(CtHandle h, CtNetwork n, const CtBakeDesc *d, CtBake *out
             return rc;
         }
         bake_adopt_mask(b, m, active);
+    }
+    if (shards != 1u) {   // (a bake on a group: the nodes it covers are counted now)
+        rc = bake_cut(h, b, shard, shards);
+        if (rc != CT_OK) {
+            return rc;
+        }
     }
     BakeAdaptiveSet set;
     if (adaptive) {   // (a dense bake: no kernel has run yet; the others: behind the mask's count, like the compact table)
@@ -1027,9 +1098,9 @@ static int bake_refill(CtHandle h, CtBake_ *b, F &&fill)
     return rc;
 }
 
-extern "C" int ct_bake_update(CtHandle h, CtNetwork n, CtBake b)
+// What ct_bake_update checks before it flushes, in this order.
+static int bake_update_checks(CtHandle h, CtNetwork n, CtBake b, const char *who)
 {
-    const char *const who = "ct_bake_update";
     if (!h) {
         return fail(nullptr, CT_E_INVAL, "null handle");
     }
@@ -1052,7 +1123,16 @@ extern "C" int ct_bake_update(CtHandle h, CtNetwork n, CtBake b)
         return fail(h, CT_E_INVAL, "%s: a traced bake holds no network's outputs; %s traces it again", who,
                     b->adaptive ? "ct_bake_retrace_adaptive" : "ct_bake_retrace");
     }
-    rc = flush(h);
+    return CT_OK;
+}
+
+extern "C" int ct_bake_update(CtHandle h, CtNetwork n, CtBake b)
+{
+    const char *const who = "ct_bake_update";
+    int rc = bake_update_checks(h, n, b, who);
+    if (rc == CT_OK) {
+        rc = flush(h);
+    }
     if (rc != CT_OK) {
         return rc;
     }
@@ -1103,10 +1183,9 @@ static int bake_trace_checks(CtHandle h, CtBake b, uint32_t samples, const char 
     return CT_OK;
 }
 
-extern "C" int ct_bake_trace_more(CtHandle h, CtBake b, uint32_t samples)
+static int bake_trace_more_checks(CtHandle h, CtBake b, uint32_t samples, const char *who)
 {
-    const char *const who = "ct_bake_trace_more";
-    int rc = bake_trace_checks(h, b, samples, who);
+    const int rc = bake_trace_checks(h, b, samples, who);
     if (rc != CT_OK) {
         return rc;
     }
@@ -1116,7 +1195,15 @@ extern "C" int ct_bake_trace_more(CtHandle h, CtBake b, uint32_t samples)
     if (b->epoch != h->light_epoch) {
         return fail(h, CT_E_STATE, "%s: the handle's light has changed since the bake; ct_bake_retrace traces it again", who);
     }
-    rc = flush(h);
+    return CT_OK;
+}
+
+extern "C" int ct_bake_trace_more(CtHandle h, CtBake b, uint32_t samples)
+{
+    int rc = bake_trace_more_checks(h, b, samples, "ct_bake_trace_more");
+    if (rc == CT_OK) {
+        rc = flush(h);
+    }
     if (rc != CT_OK) {
         return rc;
     }
@@ -1195,10 +1282,9 @@ static int bake_adaptive_checks(CtHandle h, CtBake b, const char *who)
     return CT_OK;
 }
 
-extern "C" int ct_bake_trace_adaptive_more(CtHandle h, CtBake b, uint32_t max_samples)
+static int bake_adaptive_more_checks(CtHandle h, CtBake b, uint32_t max_samples, const char *who)
 {
-    const char *const who = "ct_bake_trace_adaptive_more";
-    int rc = bake_adaptive_checks(h, b, who);
+    const int rc = bake_adaptive_checks(h, b, who);
     if (rc != CT_OK) {
         return rc;
     }
@@ -1209,15 +1295,37 @@ extern "C" int ct_bake_trace_adaptive_more(CtHandle h, CtBake b, uint32_t max_sa
     if (b->epoch != h->light_epoch) {
         return fail(h, CT_E_STATE, "%s: the handle's light has changed since the bake; ct_bake_retrace_adaptive traces it again", who);
     }
-    rc = flush(h);
+    return CT_OK;
+}
+
+extern "C" int ct_bake_trace_adaptive_more(CtHandle h, CtBake b, uint32_t max_samples)
+{
+    int rc = bake_adaptive_more_checks(h, b, max_samples, "ct_bake_trace_adaptive_more");
+    if (rc == CT_OK) {
+        rc = flush(h);
+    }
     if (rc != CT_OK) {
         return rc;
     }
     // (in place, like ct_bake_trace_more: a failure between two rounds leaves the rounds that were completed)
     return drained(h, [&]() -> int {
         HIPCHK(h, hipStreamSynchronize(h->stream));
+        uint64_t at = 0, n_live = b->live;
+        if (b->shards != 1u && n_live != 0u) {   // a bake on a group: the span's sub-range of the merged or loaded list
+            const uint64_t block = (uint64_t)b->azimuths * b->cosines;
+            uint32_t bounds[2] = { 0, 0 };
+            HIPCHK(h, launch_bake_live_bounds(b->d_live[b->live_cur], (uint32_t)n_live, (uint32_t)(b->span_lo * block),
+                                              (uint32_t)(b->span_hi * block), b->d_waves, h->stream));
+            HIPCHK(h, hipMemcpyAsync(bounds, b->d_waves, sizeof bounds, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            if (bounds[0] > bounds[1] || bounds[1] > n_live) {
+                return fail(h, CT_E_HIP, "internal: a live list of %llu entries gave the span %u .. %u", (unsigned long long)n_live, bounds[0], bounds[1]);
+            }
+            at = bounds[0];
+            n_live = bounds[1] - bounds[0];
+        }
         b->cap = max_samples;
-        return bake_trace_adaptive(h, b, bake_adaptive_target(b), b->live, true);
+        return bake_trace_adaptive(h, b, bake_adaptive_target(b), n_live, true, at);
     });
 }
 
@@ -1955,5 +2063,146 @@ extern "C" int ct_bake_load(CtHandle h, const char *path, CtBake *out)
         }
     }
     *out = made.release();
+    return CT_OK;
+}
+
+// ---- a bake on a group (ct_group_bake_*, ct_group.hip): one shard's span, the checks passed through, the exchange: DESIGN 8 f-19 ----
+int ct::bake_create_shard(CtHandle h, CtNetwork n, const CtBakeDesc *d, uint32_t kind, const uint32_t *samples, const CtBakeAdaptive *p,
+                          uint32_t shard, uint32_t shards, CtBake *out)
+{
+    return bake_create(h, n, d, out, kind, samples, p, shard, shards);
+}
+
+extern "C" int ct_debug_bake_shard(CtHandle h, const CtBakeDesc *d, uint32_t kind, uint32_t samples, const CtBakeAdaptive *p, uint32_t shard,
+                                   uint32_t shards, CtBake *out)
+{
+    if (!h) {
+        return fail(nullptr, CT_E_INVAL, "null handle");
+    }
+    if (!d || !out || shards == 0u || shards > 64u || shard >= shards) {
+        return fail(h, CT_E_INVAL, "ct_debug_bake_shard: need a description, out and shard < shards <= 64");
+    }
+    return bake_create(h, nullptr, d, out, kind, p ? nullptr : &samples, p, shard, shards);
+}
+
+int ct::bake_cut_shard(CtBake b, uint32_t shard, uint32_t shards)
+{
+    CtHandle h = b->h;
+    NEED(h);
+    return bake_cut(h, b, shard, shards);
+}
+
+void ct::bake_shard_span(CtBake b, uint64_t lo_hi_out[2])
+{
+    bake_span(b, &lo_hi_out[0], &lo_hi_out[1]);
+}
+
+int ct::bake_op_checks(CtHandle h, CtNetwork n, CtBake b, BakeOp op, uint32_t arg)
+{
+    switch (op) {
+    case BAKE_OP_UPDATE:
+        return bake_update_checks(h, n, b, "ct_bake_update");
+    case BAKE_OP_TRACE_MORE:
+        return bake_trace_more_checks(h, b, arg, "ct_bake_trace_more");
+    case BAKE_OP_RETRACE:
+        return bake_trace_checks(h, b, arg, "ct_bake_retrace");
+    case BAKE_OP_ADAPTIVE_MORE:
+        return bake_adaptive_more_checks(h, b, arg, "ct_bake_trace_adaptive_more");
+    default:
+        return bake_adaptive_checks(h, b, "ct_bake_retrace_adaptive");
+    }
+}
+
+// `count` words from src on s's device into dst on d's: on d's stream, which the caller waits for.
+static hipError_t bake_exchange_copy(const CtBake_ *d, void *dst, const CtBake_ *s, const void *src, size_t count)
+{
+    if (count == 0u) {
+        return hipSuccess;
+    }
+    return d->device == s->device ? hipMemcpyAsync(dst, src, count * 4u, hipMemcpyDeviceToDevice, d->h->stream)
+                                  : hipMemcpyPeerAsync(dst, d->device, src, s->device, count * 4u, d->h->stream);
+}
+
+int ct::bake_exchange(CtBake const *bakes, uint32_t count, uint64_t paths_before, uint64_t *bytes_out, char *error, size_t error_bytes)
+{
+    auto failed = [&](const char *what, hipError_t e) {
+        std::snprintf(error, error_bytes, "the exchange of a group bake: %s failed: %s", what, hipGetErrorString(e));
+        return e == hipErrorOutOfMemory ? CT_E_NOMEM : CT_E_HIP;
+    };
+    const CtBake_ *const b0 = bakes[0];
+    BakeState whole = *b0;
+    whole.paths = paths_before;
+    whole.live = 0;
+    for (uint32_t i = 0; i < count; i++) {
+        const CtBake_ *s = bakes[i];
+        whole.samples = std::max(whole.samples, s->samples);
+        whole.rounds = std::max(whole.rounds, s->rounds);
+        whole.paths += s->paths - paths_before;
+        whole.live += s->live;
+        whole.gather_ms = std::max(whole.gather_ms, s->gather_ms);
+        whole.network_ms = std::max(whole.network_ms, s->network_ms);
+        whole.mask_ms = std::max(whole.mask_ms, s->mask_ms);
+        whole.trace_ms = std::max(whole.trace_ms, s->trace_ms);
+        whole.fold_ms = std::max(whole.fold_ms, s->fold_ms);
+        whole.test_ms = std::max(whole.test_ms, s->test_ms);
+    }
+    if (whole.live > bake_trace_total(b0)) {   // (what a live list holds)
+        std::snprintf(error, error_bytes, "internal: the shards of a group bake leave %llu live entries of %llu",
+                      (unsigned long long)whole.live, (unsigned long long)bake_trace_total(b0));
+        return CT_E_HIP;
+    }
+    uint64_t moved = 0;
+    for (uint32_t i = 0; i < count; i++) {
+        CtBake_ *d = bakes[i];
+        hipError_t e = hipSetDevice(d->device);
+        if (e != hipSuccess) {
+            return failed("hipSetDevice", e);
+        }
+        (void)hipGetLastError();
+        uint64_t at = 0;
+        for (uint32_t j = 0; j < count; j++) {
+            const CtBake_ *s = bakes[j];
+            const size_t first = (size_t)s->range_lo, n = (size_t)(s->range_hi - s->range_lo);
+            if (j != i) {
+                e = bake_exchange_copy(d, d->d_table + first, s, s->d_table + first, n);
+                if (e == hipSuccess && d->adaptive) {
+                    e = bake_exchange_copy(d, d->d_m2 + first, s, s->d_m2 + first, n);
+                }
+                if (e == hipSuccess && d->adaptive) {
+                    e = bake_exchange_copy(d, d->d_counts + first, s, s->d_counts + first, n);
+                }
+                moved += (d->adaptive ? 12u : 4u) * (uint64_t)n + (d->adaptive ? 4u * s->live : 0u);
+            }
+            if (e == hipSuccess && d->adaptive) {   // (its own survivors too: from the front of one of its lists into the other)
+                e = bake_exchange_copy(d, d->d_live[d->live_cur ^ 1] + at, s, s->d_live[s->live_cur], (size_t)s->live);
+                at += s->live;
+            }
+            if (e != hipSuccess) {
+                return failed("a copy between shards", e);
+            }
+        }
+    }
+    for (uint32_t i = 0; i < count; i++) {   // (no list changes its role before every copy that reads it has landed)
+        hipError_t e = hipSetDevice(bakes[i]->device);
+        if (e == hipSuccess) {
+            e = hipStreamSynchronize(bakes[i]->h->stream);
+        }
+        if (e != hipSuccess) {
+            return failed("hipStreamSynchronize", e);
+        }
+    }
+    for (uint32_t i = 0; i < count; i++) {
+        CtBake_ *d = bakes[i];
+        BakeState next = whole;   // the frame, its epoch, its light's bits and the cap are the shard's own: the same values
+        std::copy_n(d->l, 3, next.l);
+        std::copy_n(d->a, 3, next.a);
+        std::copy_n(d->b, 3, next.b);
+        std::copy_n(d->light_bits, 4, next.light_bits);
+        next.epoch = d->epoch;
+        next.cap = d->cap;
+        next.live_cur = d->adaptive ? d->live_cur ^ 1 : d->live_cur;
+        static_cast<BakeState &>(*d) = next;
+    }
+    *bytes_out = moved;
     return CT_OK;
 }

@@ -216,6 +216,50 @@ __global__ __launch_bounds__(256) void bake_adaptive_compact_kernel(BakeTraceArg
     }
 }
 
+// ---- a bake on a group (ct_group_bake_*): a shard's span of the live list ---------------------------------------------------------
+// The first round of a shard: live[i] = first + i for i < n, the stored indices of its span (first + n <= 2^26).
+__global__ __launch_bounds__(256) void bake_live_iota_kernel(uint32_t *__restrict__ live, uint32_t first, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n) {
+        live[i] = first + i;
+    }
+}
+
+// A later call of a shard: bounds[t] = the number of entries of the ascending live[0 .. n) below key t, t < 2.  One block.
+__global__ __launch_bounds__(64) void bake_live_bounds_kernel(const uint32_t *__restrict__ live, uint32_t n, uint32_t key_lo, uint32_t key_hi,
+                                                              uint32_t *__restrict__ bounds)
+{
+    if (threadIdx.x >= 2u) {
+        return;
+    }
+    const uint32_t key = threadIdx.x == 0u ? key_lo : key_hi;
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        if (live[mid] < key) {
+            lo = mid + 1u;
+        } else {
+            hi = mid;
+        }
+    }
+    bounds[threadIdx.x] = lo;
+}
+
+hipError_t launch_bake_live_iota(uint32_t *live, uint32_t first, uint32_t n, hipStream_t stream)
+{
+    if (n != 0u) {
+        hipLaunchKernelGGL(bake_live_iota_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, live, first, n);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_bake_live_bounds(const uint32_t *live, uint32_t n, uint32_t key_lo, uint32_t key_hi, uint32_t *bounds, hipStream_t stream)
+{
+    hipLaunchKernelGGL(bake_live_bounds_kernel, dim3(1), dim3(64), 0, stream, live, n, key_lo, key_hi, bounds);
+    return hipGetLastError();
+}
+
 hipError_t launch_bake_adaptive_fold(const BakeTraceArgs &a, const float4 *frames, uint32_t stride, uint32_t passes, uint32_t done,
                                      const BakeAdaptiveState &st, uint32_t *waves, hipStream_t stream)
 {

@@ -18,9 +18,12 @@
 //
 // The adaptive frame on a group (ct_group_adaptive_frame_*, at the end of the file) has a merge of its own: the unsigned maximum
 // of every 32-bit word instead of a float sum, always by peer copies and a kernel on the first device.
+//
+// Bakes on a group (ct_group_bake_*, behind it): every shard builds a span of the bake and copies bring every shard the rest.
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -32,6 +35,7 @@
 #include <vector>
 
 #include "../../include/cloudtrace.h"
+#include "ct_bake_group.hpp"
 #include "ct_devmem.hpp"
 
 namespace {
@@ -831,5 +835,330 @@ extern "C" int ct_group_adaptive_frame_device_ptr(CtGroupAdaptiveFrame gf, uint3
         }
     }
     *out = p;
+    return CT_OK;
+}
+
+// ---- bakes on a group (ct_group_bake_*) -------------------------------------------------------------------------
+// One CtBake per shard, on its handle.  A call that builds or continues the bake cuts the nodes it covers into one span per shard
+// (ct_bake.cpp: shard i of N takes list positions [i A / N, (i + 1) A / N)), every shard works on its span on a host thread of its
+// own -- a bake waits for its chunks as a band of the network renderer does -- and the exchange (ct::bake_exchange: copies, no
+// collective) leaves every shard with the whole bake, because a shard's tiles look up anywhere in the table.
+struct CtGroupBake_ {
+    CtGroup group = nullptr;
+    std::vector<CtBake> bakes;   // per shard, on its device
+    bool failed = false;         // a shard has failed in a build: good for ct_group_bake_destroy only
+    uint64_t exchange_bytes = 0;
+    double exchange_ms = 0;      // the last exchange, on the host's clock
+};
+
+// f(i) for every shard: shards 1 .. N-1 on threads of this call, shard 0 on the caller.  -> the first failing shard, or N.
+template <typename F>
+static uint32_t on_every_shard(uint32_t shards, std::vector<int> &codes, F &&f)
+{
+    codes.assign(shards, CT_OK);
+    auto shard = [&](uint32_t i) { codes[i] = f(i); };
+    std::vector<std::thread> threads;
+    threads.reserve(shards);
+    for (uint32_t i = 1; i < shards; i++) {
+        threads.emplace_back(shard, i);
+    }
+    shard(0);
+    for (std::thread &t : threads) {
+        t.join();
+    }
+    for (uint32_t i = 0; i < shards; i++) {
+        if (codes[i] != CT_OK) {
+            return i;
+        }
+    }
+    return shards;
+}
+
+static int group_bake_usable(CtGroupBake gb, const char *who)
+{
+    if (!gb) {
+        return gfail(nullptr, CT_E_INVAL, "%s: null group bake", who);
+    }
+    if (gb->failed) {
+        return gfail(gb->group, CT_E_STATE, "%s: a shard of this group bake has failed in a build; it is good for ct_group_bake_destroy only", who);
+    }
+    return CT_OK;
+}
+
+static int group_bake_exchange(CtGroupBake gb, uint64_t paths_before)
+{
+    char text[512] = "";
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = ct::bake_exchange(gb->bakes.data(), (uint32_t)gb->bakes.size(), paths_before, &gb->exchange_bytes, text, sizeof text);
+    gb->exchange_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (rc != CT_OK) {
+        gb->failed = true;
+        return gfail(gb->group, rc, "%s", text);
+    }
+    return CT_OK;
+}
+
+extern "C" int ct_group_bake_destroy(CtGroupBake gb)
+{
+    if (!gb) {
+        return CT_OK;
+    }
+    for (CtBake b : gb->bakes) {
+        ct_bake_destroy(b);   // (NULL is a no-op; selects its device)
+    }
+    delete gb;
+    return CT_OK;
+}
+
+// The three builds: gn, samples or p says which.
+static int group_bake_build(CtGroup g, CtGroupNetwork gn, const CtBakeDesc *d, uint32_t kind, const uint32_t *samples, const CtBakeAdaptive *p,
+                            CtGroupBake *out)
+{
+    const uint32_t shards = (uint32_t)g->handles.size();
+    CtGroupBake gb = new (std::nothrow) CtGroupBake_();
+    if (!gb) {
+        return gfail(g, CT_E_NOMEM, "out of host memory");
+    }
+    gb->group = g;
+    gb->bakes.assign(shards, nullptr);
+    std::vector<int> codes;
+    const uint32_t bad = on_every_shard(shards, codes, [&](uint32_t i) {
+        return ct::bake_create_shard(g->handles[i], gn ? gn->nets[i] : nullptr, d, kind, samples, p, i, shards, &gb->bakes[i]);
+    });
+    int rc = bad < shards ? shard_fail(g, bad, codes[bad]) : group_bake_exchange(gb, 0);
+    if (rc != CT_OK) {
+        ct_group_bake_destroy(gb);
+        return rc;
+    }
+    *out = gb;
+    return CT_OK;
+}
+
+extern "C" int ct_group_network_bake(CtGroup g, CtGroupNetwork gn, const CtBakeDesc *d, uint32_t kind, CtGroupBake *out)
+{
+    if (!g) {
+        return gfail(nullptr, CT_E_INVAL, "null group");
+    }
+    if (out) {
+        *out = nullptr;
+    }
+    if (!gn || !d || !out) {
+        return gfail(g, CT_E_INVAL, "ct_group_network_bake: need a group network, a description and out");
+    }
+    if (gn->group != g || gn->nets.size() != g->handles.size()) {
+        return gfail(g, CT_E_INVAL, "ct_group_network_bake: need a CtGroupNetwork of this group");
+    }
+    return group_bake_build(g, gn, d, kind, nullptr, nullptr, out);
+}
+
+extern "C" int ct_group_bake_traced(CtGroup g, const CtBakeDesc *d, uint32_t kind, uint32_t samples, CtGroupBake *out)
+{
+    if (!g) {
+        return gfail(nullptr, CT_E_INVAL, "null group");
+    }
+    if (out) {
+        *out = nullptr;
+    }
+    if (!d || !out) {
+        return gfail(g, CT_E_INVAL, "ct_group_bake_traced: need a description and out");
+    }
+    return group_bake_build(g, nullptr, d, kind, &samples, nullptr, out);
+}
+
+extern "C" int ct_group_bake_traced_adaptive(CtGroup g, const CtBakeDesc *d, uint32_t kind, const CtBakeAdaptive *p, CtGroupBake *out)
+{
+    if (!g) {
+        return gfail(nullptr, CT_E_INVAL, "null group");
+    }
+    if (out) {
+        *out = nullptr;
+    }
+    if (!d || !p || !out) {
+        return gfail(g, CT_E_INVAL, "ct_group_bake_traced_adaptive: need a description, parameters and out");
+    }
+    return group_bake_build(g, nullptr, d, kind, nullptr, p, out);
+}
+
+// ct_bake_load on every shard: every shard holds the whole bake at once, and is cut for what follows.
+extern "C" int ct_group_bake_load(CtGroup g, const char *path, CtGroupBake *out)
+{
+    if (!g) {
+        return gfail(nullptr, CT_E_INVAL, "null group");
+    }
+    if (out) {
+        *out = nullptr;
+    }
+    if (!path || !out) {
+        return gfail(g, CT_E_INVAL, "ct_group_bake_load: need a path and out");
+    }
+    const uint32_t shards = (uint32_t)g->handles.size();
+    CtGroupBake gb = new (std::nothrow) CtGroupBake_();
+    if (!gb) {
+        return gfail(g, CT_E_NOMEM, "out of host memory");
+    }
+    gb->group = g;
+    gb->bakes.assign(shards, nullptr);
+    std::vector<int> codes;
+    const uint32_t bad = on_every_shard(shards, codes, [&](uint32_t i) {
+        const int rc = ct_bake_load(g->handles[i], path, &gb->bakes[i]);
+        return rc != CT_OK ? rc : ct::bake_cut_shard(gb->bakes[i], i, shards);
+    });
+    if (bad < shards) {
+        const int rc = shard_fail(g, bad, codes[bad]);
+        ct_group_bake_destroy(gb);
+        return rc;
+    }
+    *out = gb;
+    return CT_OK;
+}
+
+// A call that continues the bake or builds it again.  The single-GPU call's own checks are passed through from shard 0 before
+// any shard works: a refusal leaves everything as it was.  from_zero: the call counts its paths from 0 (retrace).
+template <typename F>
+static int group_bake_continue(CtGroupBake gb, CtNetwork n0, ct::BakeOp op, uint32_t arg, bool from_zero, F &&call)
+{
+    CtGroup g = gb->group;
+    const uint32_t shards = (uint32_t)gb->bakes.size();
+    int rc = ct::bake_op_checks(g->handles[0], n0, gb->bakes[0], op, arg);
+    if (rc != CT_OK) {
+        return shard_fail(g, 0, rc);
+    }
+    CtBakeTraceInfo before{};
+    rc = ct_bake_trace_info(gb->bakes[0], &before);
+    if (rc != CT_OK) {
+        return shard_fail(g, 0, rc);
+    }
+    std::vector<int> codes;
+    const uint32_t bad = on_every_shard(shards, codes, call);
+    if (bad < shards) {
+        gb->failed = true;
+        return shard_fail(g, bad, codes[bad]);
+    }
+    return group_bake_exchange(gb, from_zero ? 0 : before.paths);
+}
+
+extern "C" int ct_group_bake_update(CtGroupBake gb, CtGroupNetwork gn)
+{
+    const char *const who = "ct_group_bake_update";
+    const int rc = group_bake_usable(gb, who);
+    if (rc != CT_OK) {
+        return rc;
+    }
+    CtGroup g = gb->group;
+    if (!gn || gn->group != g || gn->nets.size() != g->handles.size()) {
+        return gfail(g, CT_E_INVAL, "%s: need a CtGroupNetwork of the bake's group", who);
+    }
+    return group_bake_continue(gb, gn->nets[0], ct::BAKE_OP_UPDATE, 0, true,
+                               [&](uint32_t i) { return ct_bake_update(g->handles[i], gn->nets[i], gb->bakes[i]); });
+}
+
+extern "C" int ct_group_bake_trace_more(CtGroupBake gb, uint32_t samples)
+{
+    const int rc = group_bake_usable(gb, "ct_group_bake_trace_more");
+    if (rc != CT_OK) {
+        return rc;
+    }
+    CtGroup g = gb->group;
+    return group_bake_continue(gb, nullptr, ct::BAKE_OP_TRACE_MORE, samples, false,
+                               [&](uint32_t i) { return ct_bake_trace_more(g->handles[i], gb->bakes[i], samples); });
+}
+
+extern "C" int ct_group_bake_retrace(CtGroupBake gb, uint32_t samples)
+{
+    const int rc = group_bake_usable(gb, "ct_group_bake_retrace");
+    if (rc != CT_OK) {
+        return rc;
+    }
+    CtGroup g = gb->group;
+    return group_bake_continue(gb, nullptr, ct::BAKE_OP_RETRACE, samples, true,
+                               [&](uint32_t i) { return ct_bake_retrace(g->handles[i], gb->bakes[i], samples); });
+}
+
+extern "C" int ct_group_bake_trace_adaptive_more(CtGroupBake gb, uint32_t max_samples)
+{
+    const int rc = group_bake_usable(gb, "ct_group_bake_trace_adaptive_more");
+    if (rc != CT_OK) {
+        return rc;
+    }
+    CtGroup g = gb->group;
+    return group_bake_continue(gb, nullptr, ct::BAKE_OP_ADAPTIVE_MORE, max_samples, false,
+                               [&](uint32_t i) { return ct_bake_trace_adaptive_more(g->handles[i], gb->bakes[i], max_samples); });
+}
+
+extern "C" int ct_group_bake_retrace_adaptive(CtGroupBake gb)
+{
+    const int rc = group_bake_usable(gb, "ct_group_bake_retrace_adaptive");
+    if (rc != CT_OK) {
+        return rc;
+    }
+    CtGroup g = gb->group;
+    return group_bake_continue(gb, nullptr, ct::BAKE_OP_RETRACE_ADAPTIVE, 0, true,
+                               [&](uint32_t i) { return ct_bake_retrace_adaptive(g->handles[i], gb->bakes[i]); });
+}
+
+extern "C" int ct_group_bake_shard(CtGroupBake gb, uint32_t index, CtBake *out)
+{
+    const char *const who = "ct_group_bake_shard";
+    const int rc = group_bake_usable(gb, who);
+    if (rc != CT_OK) {
+        return rc;
+    }
+    if (!out || index >= gb->bakes.size()) {
+        return gfail(gb->group, CT_E_INVAL, "%s: need out and an index below the group's size", who);
+    }
+    *out = gb->bakes[index];
+    return CT_OK;
+}
+
+extern "C" int ct_group_bake_spans(CtGroupBake gb, uint64_t *lo_hi_out, size_t count)
+{
+    const char *const who = "ct_group_bake_spans";
+    const int rc = group_bake_usable(gb, who);
+    if (rc != CT_OK) {
+        return rc;
+    }
+    if (!lo_hi_out || count != 2u * gb->bakes.size()) {
+        return gfail(gb->group, CT_E_INVAL, "%s: need an array of exactly %zu words, lo and hi per shard", who, 2u * gb->bakes.size());
+    }
+    for (size_t i = 0; i < gb->bakes.size(); i++) {
+        ct::bake_shard_span(gb->bakes[i], lo_hi_out + 2u * i);
+    }
+    return CT_OK;
+}
+
+extern "C" int ct_debug_group_bake_exchange(CtGroupBake gb, uint64_t *bytes_out, double *ms_out)
+{
+    if (!gb || !bytes_out || !ms_out) {
+        return gfail(gb ? gb->group : nullptr, CT_E_INVAL, "ct_debug_group_bake_exchange: need a group bake, bytes_out and ms_out");
+    }
+    *bytes_out = gb->exchange_bytes;
+    *ms_out = gb->exchange_ms;
+    return CT_OK;
+}
+
+// ct_baked_render_shard_accumulate on every shard, as ct_group_network_render_accumulate runs the network renderer.
+extern "C" int ct_group_baked_render_accumulate(CtGroup g, CtGroupBake gb, const CtNetworkRender *p, uint32_t first_subframe_id, uint32_t count)
+{
+    const char *const who = "ct_group_baked_render_accumulate";
+    if (!g) {
+        return gfail(nullptr, CT_E_INVAL, "null group");
+    }
+    if (!gb || gb->group != g || gb->bakes.size() != g->handles.size()) {
+        return gfail(g, CT_E_INVAL, "%s: need a CtGroupBake of this group", who);
+    }
+    const int rc = group_bake_usable(gb, who);
+    if (rc != CT_OK) {
+        return rc;
+    }
+    const uint32_t shards = (uint32_t)g->handles.size();
+    std::vector<int> codes;
+    const uint32_t bad = on_every_shard(shards, codes, [&](uint32_t i) {
+        return ct_baked_render_shard_accumulate(g->handles[i], gb->bakes[i], p, first_subframe_id, count);
+    });
+    g->merged = false;
+    if (bad < shards) {
+        return shard_fail(g, bad, codes[bad]);
+    }
+    g->subframes = first_subframe_id + count - 1;
     return CT_OK;
 }

@@ -340,6 +340,11 @@ hipError_t launch_bake_adaptive_count(const BakeTraceArgs &a, const BakeAdaptive
 hipError_t launch_bake_adaptive_scan(uint32_t *waves, uint32_t n_live, hipStream_t stream);
 hipError_t launch_bake_adaptive_compact(const BakeTraceArgs &a, const BakeAdaptiveState &st, const uint32_t *live_in, uint32_t n_live,
                                         const uint32_t *waves, uint32_t *live_out, hipStream_t stream);
+// A bake on a group (ct_group_bake_*): a shard's span of an adaptive bake's live list.  launch_bake_live_iota: live[i] = first + i
+// for i < n, the list of its first round.  launch_bake_live_bounds: bounds[0] and bounds[1] = how many entries of the ascending
+// live[0 .. n) lie below key_lo and below key_hi -- the span's sub-range of a merged or loaded list.
+hipError_t launch_bake_live_iota(uint32_t *live, uint32_t first, uint32_t n, hipStream_t stream);
+hipError_t launch_bake_live_bounds(const uint32_t *live, uint32_t n, uint32_t key_lo, uint32_t key_hi, uint32_t *bounds, hipStream_t stream);
 // ct_collector_* (ct_collect.hip): an update of the device collector of include/cloudtrace.h, "the radiance collector on the
 // device".  live: the n live task ids, ascending; r = T / n replicas per task, thread i = t * r + j replica j of live[t].
 // positions / directions / mean / m2 / counts / converged_update are indexed by task id.  launch_collect_rays writes

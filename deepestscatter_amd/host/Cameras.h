@@ -152,13 +152,35 @@ namespace DeepestScatter
     };
 
     // What the two renderers do alike with their table once it exists: the half copy, the file, and which of the two renders.
+    // With --gpus the table is a CtGroupBake (ct_group_bake_*): built across the group's GPUs, complete on every shard; `bake` is
+    // then shard 0's, owned by the group bake, which is what the accessors and --bake-out work on.
     class BakeHolder
     {
     public:
         ~BakeHolder()
         {
             if (halfCopy) ct_bake_destroy(halfCopy);
-            if (bake) ct_bake_destroy(bake);   // (before the network and the handle)
+            if (groupBake) ct_group_bake_destroy(groupBake);   // (before the networks and the group)
+            else if (bake) ct_bake_destroy(bake);              // (before the network and the handle)
+        }
+        // The handle the table's accessors report through: the context's, or shard 0's.
+        static CtHandle handleOf(const Context& context)
+        {
+            CtHandle h = context.handle;
+            if (context.group) Context::checkGroup(ct_group_handle(context.group, 0, &h), context.group, "ct_group_handle");
+            return h;
+        }
+        void adoptShard(const Context& context)   // behind every call that makes the group bake
+        {
+            Context::checkGroup(ct_group_bake_shard(groupBake, 0, &bake), context.group, "ct_group_bake_shard");
+        }
+        bool load(const Context& context, const BakeFiles& files)   // true: the table came from --bake-in
+        {
+            if (files.in.empty()) return false;
+            if (!context.group) return load(context.handle, files);
+            Context::checkGroup(ct_group_bake_load(context.group, files.in.c_str(), &groupBake), context.group, "ct_group_bake_load");
+            adoptShard(context);
+            return true;
         }
         CtBake shown() const { return halfCopy ? halfCopy : bake; }
         bool isHalf(CtHandle handle) const
@@ -189,12 +211,14 @@ namespace DeepestScatter
             return info.current != 0;
         }
         CtBake bake = nullptr, halfCopy = nullptr;
+        CtGroupBake groupBake = nullptr;
     };
 
     // The reference's default renderer (BakedRenderer): the network evaluated once per light on a probe grid (ct_network_bake,
     // --net-baked NX,NY,NZ,NPHI,NC) and every subframe interpolated from that table (ct_baked_render_*): no gather and no
     // network per subframe.  The table is baked in init, which follows Sun::init and so every ct_set_light, and baked again
-    // should the light have changed since.  One GPU only: main refuses --net-baked with --gpus.  sparse (--net-bake-sparse): the
+    // should the light have changed since.  With --gpus the table is built on the group (ct_group_network_bake) and every GPU
+    // renders its own tiles from its copy (ct_group_baked_render_accumulate).  sparse (--net-bake-sparse): the
     // table is baked by ct_network_bake_sparse, only where a first flight can look it up; the images are the same.  compact
     // (--net-bake-compact): ct_network_bake_compact, which also stores only those probes; the images are the same again.
     class BakedRenderer : public NetworkRenderer
@@ -207,9 +231,19 @@ namespace DeepestScatter
         void init() override
         {
             NetworkRenderer::init();
-            if (context->group) throw std::runtime_error("--net-baked renders on one GPU only");
             CtBake& bake = table.bake;
             if (bake) return;
+            if (context->group)
+            {
+                if (!table.load(*context, files))
+                {
+                    Context::checkGroup(ct_group_network_bake(context->group, groupNetwork, &desc, compact ? CT_BAKE_COMPACT : sparse ? CT_BAKE_SPARSE : CT_BAKE_DENSE,
+                                                              &table.groupBake), context->group, "ct_group_network_bake");
+                    table.adoptShard(*context);
+                }
+                table.finish(BakeHolder::handleOf(*context), files, true);
+                return;
+            }
             if (!table.load(context->handle, files))
             {
                 if (compact) Context::check(ct_network_bake_compact(context->handle, network, &desc, &bake), context->handle, "ct_network_bake_compact");
@@ -221,6 +255,7 @@ namespace DeepestScatter
 
         void render(float* frameResultBuffer) override
         {
+            if (context->group) throw std::runtime_error("the two-launch loop (--unfused) renders on one GPU only");
             applyCamera();
             refresh();
             Context::check(ct_baked_render_subframe(context->handle, table.shown(), &params, subframeId, frameResultBuffer), context->handle,
@@ -231,6 +266,12 @@ namespace DeepestScatter
         {
             applyCamera();
             refresh();
+            if (context->group)
+            {
+                Context::checkGroup(ct_group_baked_render_accumulate(context->group, table.groupBake, &params, first, count), context->group,
+                                    "ct_group_baked_render_accumulate");
+                return;
+            }
             Context::check(ct_baked_render_accumulate(context->handle, table.shown(), &params, first, count), context->handle,
                            "ct_baked_render_accumulate");
         }
@@ -238,9 +279,11 @@ namespace DeepestScatter
     private:
         void refresh()   // a light set since the bake: bake again (and round again, with --bake-half)
         {
-            if (table.current(context->handle)) return;
-            Context::check(ct_bake_update(context->handle, network, table.bake), context->handle, "ct_bake_update");
-            table.finish(context->handle, files, false);
+            const CtHandle handle = BakeHolder::handleOf(*context);
+            if (table.current(handle)) return;
+            if (context->group) Context::checkGroup(ct_group_bake_update(table.groupBake, groupNetwork), context->group, "ct_group_bake_update");
+            else Context::check(ct_bake_update(context->handle, network, table.bake), context->handle, "ct_bake_update");
+            table.finish(handle, files, false);
         }
 
         CtBakeDesc desc;
@@ -251,7 +294,8 @@ namespace DeepestScatter
 
     // The baked renderer without a network (--traced-bake NX,NY,NZ,NPHI,NC --bake-samples N): the probe table holds the means of
     // N experiments of the path tracer's point estimator per entry (ct_bake_traced) and every subframe is interpolated from it.
-    // Traced in init, and again (ct_bake_retrace) should the light have changed since.  One GPU only.
+    // Traced in init, and again (ct_bake_retrace) should the light have changed since.  With --gpus the table is traced on the
+    // group (ct_group_bake_traced, ct_group_bake_traced_adaptive) and every GPU renders its own tiles from its copy.
     // With --bake-adaptive R,MAX[,REL[,ABS[,ZERO]]] in place of --bake-samples the table is traced in rounds under the stopping rule
     // (ct_bake_traced_adaptive, ct_bake_retrace_adaptive) and init prints what ct_bake_adaptive_info reports.
     class TracedBakeRenderer : public PathTracingRenderer
@@ -265,27 +309,34 @@ namespace DeepestScatter
         void init() override
         {
             PathTracingRenderer::init();
-            if (context->group) throw std::runtime_error("--traced-bake renders on one GPU only");
             CtBake& bake = table.bake;
             if (bake) return;
-            if (table.load(context->handle, files))   // --bake-in: how to trace it again, should the light change, is the file's
+            const CtHandle handle = BakeHolder::handleOf(*context);
+            if (table.load(*context, files))   // --bake-in: how to trace it again, should the light change, is the file's
             {
                 CtBakeTraceInfo ti;
                 CtBakeAdaptiveInfo ai;
-                Context::check(ct_bake_trace_info(bake, &ti), context->handle, "ct_bake_trace_info");
-                Context::check(ct_bake_adaptive_info(bake, &ai), context->handle, "ct_bake_adaptive_info");
+                Context::check(ct_bake_trace_info(bake, &ti), handle, "ct_bake_trace_info");
+                Context::check(ct_bake_adaptive_info(bake, &ai), handle, "ct_bake_adaptive_info");
                 if (!ti.traced) throw std::runtime_error("--bake-in: the file holds a network's bake; give its network with --network FILE");
                 samples = ti.samples;
                 isAdaptive = ai.adaptive != 0;
             }
+            else if (context->group)
+            {
+                if (!isAdaptive) Context::checkGroup(ct_group_bake_traced(context->group, &desc, kind, samples, &table.groupBake), context->group, "ct_group_bake_traced");
+                else Context::checkGroup(ct_group_bake_traced_adaptive(context->group, &desc, kind, &adaptive, &table.groupBake), context->group, "ct_group_bake_traced_adaptive");
+                table.adoptShard(*context);
+            }
             else if (!isAdaptive) Context::check(ct_bake_traced(context->handle, &desc, kind, samples, &bake), context->handle, "ct_bake_traced");
             else Context::check(ct_bake_traced_adaptive(context->handle, &desc, kind, &adaptive, &bake), context->handle, "ct_bake_traced_adaptive");
             if (isAdaptive) printAdaptiveInfo();
-            table.finish(context->handle, files, true);
+            table.finish(handle, files, true);
         }
 
         void render(float* frameResultBuffer) override
         {
+            if (context->group) throw std::runtime_error("the two-launch loop (--unfused) renders on one GPU only");
             applyCamera();
             refresh();
             Context::check(ct_baked_render_subframe(context->handle, table.shown(), &params, subframeId, frameResultBuffer), context->handle,
@@ -296,6 +347,12 @@ namespace DeepestScatter
         {
             applyCamera();
             refresh();
+            if (context->group)
+            {
+                Context::checkGroup(ct_group_baked_render_accumulate(context->group, table.groupBake, &params, first, count), context->group,
+                                    "ct_group_baked_render_accumulate");
+                return;
+            }
             Context::check(ct_baked_render_accumulate(context->handle, table.shown(), &params, first, count), context->handle,
                            "ct_baked_render_accumulate");
         }
@@ -303,20 +360,23 @@ namespace DeepestScatter
     private:
         void refresh()   // a light set since the bake: trace again (and round again, with --bake-half)
         {
-            if (table.current(context->handle)) return;
-            if (!isAdaptive) Context::check(ct_bake_retrace(context->handle, table.bake, samples), context->handle, "ct_bake_retrace");
-            else
+            const CtHandle handle = BakeHolder::handleOf(*context);
+            if (table.current(handle)) return;
+            if (context->group)
             {
-                Context::check(ct_bake_retrace_adaptive(context->handle, table.bake), context->handle, "ct_bake_retrace_adaptive");
-                printAdaptiveInfo();
+                if (!isAdaptive) Context::checkGroup(ct_group_bake_retrace(table.groupBake, samples), context->group, "ct_group_bake_retrace");
+                else Context::checkGroup(ct_group_bake_retrace_adaptive(table.groupBake), context->group, "ct_group_bake_retrace_adaptive");
             }
-            table.finish(context->handle, files, false);
+            else if (!isAdaptive) Context::check(ct_bake_retrace(context->handle, table.bake, samples), context->handle, "ct_bake_retrace");
+            else Context::check(ct_bake_retrace_adaptive(context->handle, table.bake), context->handle, "ct_bake_retrace_adaptive");
+            if (isAdaptive) printAdaptiveInfo();
+            table.finish(handle, files, false);
         }
 
         void printAdaptiveInfo()
         {
             CtBakeAdaptiveInfo i;
-            Context::check(ct_bake_adaptive_info(table.bake, &i), context->handle, "ct_bake_adaptive_info");
+            Context::check(ct_bake_adaptive_info(table.bake, &i), BakeHolder::handleOf(*context), "ct_bake_adaptive_info");
             std::printf("adaptive bake: %u rounds of %u, cap %u; %llu entries, %llu converged, %llu capped, %llu paths; "
                         "trace %.3f ms, fold %.3f ms, test %.3f ms\n", i.rounds, i.round_samples, i.max_samples,
                         (unsigned long long)i.entries_active, (unsigned long long)i.converged, (unsigned long long)i.capped,

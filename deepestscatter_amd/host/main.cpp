@@ -14,19 +14,21 @@
 //                               estimator; --net-direct adds the sun's single-scatter term (CT_NET_ADD_SINGLE_SCATTER), so that a
 //                               network trained on the multiple-scatter labels gives the picture --mode total gives
 //              [--net-baked NX,NY,NZ,NPHI,NC]   with --network: bake the network once per light on that probe grid (ct_network_bake)
-//                               and interpolate every subframe from the table (ct_baked_render_accumulate); one GPU, not with --gpus
+//                               and interpolate every subframe from the table (ct_baked_render_accumulate); with --gpus the table is
+//                               baked across the GPUs and every GPU renders its own tiles from its copy (ct_group_bake_*)
 //              [--net-bake-sparse]              with --net-baked: bake only the probes a first flight can reach (ct_network_bake_sparse); the same images
 //              [--net-bake-compact]             with --net-baked: bake and store only those probes (ct_network_bake_compact); the same images; not with --net-bake-sparse
 //              [--traced-bake NX,NY,NZ,NPHI,NC --bake-samples N [--net-bake-sparse | --net-bake-compact] [--net-direct]]   without
 //                               --network: fill that probe grid with N path-traced experiments per entry (ct_bake_traced) and
-//                               interpolate every subframe from the table; --net-scale and --net-transform apply; one GPU
+//                               interpolate every subframe from the table; --net-scale and --net-transform apply; with --gpus every GPU
+//                               traces a span of the table's nodes (ct_group_bake_traced) and renders its own tiles
 //              [--bake-adaptive R,MAX[,REL[,ABS[,ZERO]]]]   in place of --bake-samples: trace in rounds of R experiments, only the entries
 //                               that fail the stopping rule (95 % interval below REL of the mean, default 0.02, or below ABS, default
 //                               1e-4; a zero entry after ZERO experiments, default 100000), at most MAX each (ct_bake_traced_adaptive)
-//              [--bake-out FILE]                with --net-baked or --traced-bake: save the table as a bake file (ct_bake_save)
+//              [--bake-out FILE]                with --net-baked or --traced-bake: save the table as a bake file (ct_bake_save; with --gpus shard 0's, which is the whole table)
 //              [--bake-in FILE]                 in place of --net-baked / --traced-bake and their flags: render from the table in FILE
 //                               (ct_bake_load); a traced file needs no network, a network's bake needs its --network FILE (a new light bakes it again)
-//              [--bake-half]                    render from the binary16 copy of the table (ct_bake_half); with --bake-out that copy is saved
+//              [--bake-half]                    render from the binary16 copy of the table (ct_bake_half); with --bake-out that copy is saved; not with --gpus
 //              [--adaptive R,MAX[,MIN[,REL[,ABS]]] [--adaptive-counts FILE]]   the image as an adaptive frame (ct_adaptive_frame_*):
 //                               rounds of R subframes that go only to the pixels which still fail the stopping rule (tested from MIN
 //                               samples on, default 100; 95 % interval below REL of the mean, default 0.02, or below ABS, default
@@ -347,10 +349,11 @@ namespace
 
 int main(int argc, char* argv[])
 {
+    std::string onGroup;   // told before a failure's text when a bake was asked for on a group of GPUs
     try
     {
         Options opt;
-        if (argc < 2) { std::cerr << "usage: cloudtrace <cloud> [--size WxH] [--spp N] [--mode total|multi|single] [--light L] [--size-m M] [--out DIR] [--data DIR] [--unfused] [--display] [--estimator march|delta] [--format exr|pfm] [--gpus N|a,b,c] [--tex-fixed8] [--network FILE [--net-transform linear|expm1] [--net-scale r,g,b] [--net-direct] [--net-baked NX,NY,NZ,NPHI,NC [--net-bake-sparse | --net-bake-compact]]] [--traced-bake NX,NY,NZ,NPHI,NC --bake-samples N [--net-bake-sparse | --net-bake-compact] [--net-direct]] [--adaptive R,MAX[,MIN[,REL[,ABS]]] [--adaptive-counts FILE] [--adaptive-gpus N|a,b,c]] (--network with --gpus: every GPU renders its own tiles; --net-baked: one GPU)\n"; return 2; }
+        if (argc < 2) { std::cerr << "usage: cloudtrace <cloud> [--size WxH] [--spp N] [--mode total|multi|single] [--light L] [--size-m M] [--out DIR] [--data DIR] [--unfused] [--display] [--estimator march|delta] [--format exr|pfm] [--gpus N|a,b,c] [--tex-fixed8] [--network FILE [--net-transform linear|expm1] [--net-scale r,g,b] [--net-direct] [--net-baked NX,NY,NZ,NPHI,NC [--net-bake-sparse | --net-bake-compact]]] [--traced-bake NX,NY,NZ,NPHI,NC --bake-samples N [--net-bake-sparse | --net-bake-compact] [--net-direct]] [--adaptive R,MAX[,MIN[,REL[,ABS]]] [--adaptive-counts FILE] [--adaptive-gpus N|a,b,c]] (--network, --net-baked and --traced-bake with --gpus: every GPU renders its own tiles; --bake-half: one GPU)\n"; return 2; }
         int first = 2;
         bool lightsGiven = false;
         opt.cloud = argv[1];
@@ -499,12 +502,14 @@ int main(int argc, char* argv[])
         if (opt.bakeAdaptive && !opt.tracedBake) throw std::invalid_argument("--bake-adaptive sets the rounds of --traced-bake NX,NY,NZ,NPHI,NC");
         if (opt.tracedBake && opt.bakeSamples == 0 && !opt.bakeAdaptive && opt.bakeFiles.in.empty()) throw std::invalid_argument("--traced-bake needs --bake-samples N or --bake-adaptive R,MAX[,REL[,ABS[,ZERO]]]");
         if (opt.bakeSamples != 0 && !opt.tracedBake) throw std::invalid_argument("--bake-samples counts the experiments of --traced-bake NX,NY,NZ,NPHI,NC");
-        if (opt.tracedBake && !opt.devices.empty()) throw std::invalid_argument("--traced-bake renders on one GPU: it cannot be combined with --gpus");
+        if (opt.bakeFiles.half && !opt.devices.empty()) throw std::invalid_argument("--bake-half makes its binary16 copy on one GPU: it cannot be combined with --gpus");
         if (opt.netBakeCompact && !opt.netBaked && !opt.tracedBake) throw std::invalid_argument("--net-bake-compact chooses how --net-baked NX,NY,NZ,NPHI,NC bakes and stores its table");
         if (opt.netBakeCompact && opt.netBakeSparse) throw std::invalid_argument("--net-bake-compact and --net-bake-sparse are two ways to bake one table: give one of them");
         if (opt.netBakeSparse && !opt.netBaked && !opt.tracedBake) throw std::invalid_argument("--net-bake-sparse chooses how --net-baked NX,NY,NZ,NPHI,NC bakes its table");
         if (opt.netBaked && opt.networkPath.empty()) throw std::invalid_argument("--net-baked bakes the network of --network FILE");
-        if (opt.netBaked && !opt.devices.empty()) throw std::invalid_argument("--net-baked renders on one GPU: it cannot be combined with --gpus");
+        if ((opt.netBaked || opt.tracedBake) && opt.devices.size() > 1)
+            onGroup = std::string(opt.netBaked ? "--net-baked" : "--traced-bake") + " with --gpus builds and renders its table on a group of " +
+                      std::to_string(opt.devices.size()) + " GPUs: ";
         if (opt.adaptiveFrame && (!opt.devices.empty() || !opt.networkPath.empty() || opt.tracedBake || opt.display))
             throw std::invalid_argument("--adaptive renders with the path tracer on one GPU, headless: it cannot be combined with --gpus, --network, --traced-bake or --display");
         if (!opt.adaptiveDevices.empty() && !opt.adaptiveFrame) throw std::invalid_argument("--adaptive-gpus N|a,b,c names the GPUs of --adaptive R,MAX[,MIN[,REL[,ABS]]]");
@@ -537,7 +542,7 @@ int main(int argc, char* argv[])
     }
     catch (const std::exception& e)                                               // main.cpp:65-76
     {
-        std::cout << e.what() << std::endl;
+        std::cout << onGroup << e.what() << std::endl;
         return 1;
     }
 }

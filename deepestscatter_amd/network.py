@@ -669,6 +669,20 @@ class Bake:
         check(_lib.load().ct_bake_load(tracer.h, os.fsencode(path), C.byref(b)), tracer.h)
         return cls._adopt(tracer, b)
 
+    @classmethod
+    def traced_shard(cls, tracer, grid, azimuths: int, cosines: int, shard: int, shards: int, samples: int = 0,
+                     adaptive: "AdaptiveParams | None" = None, sparse: bool = False, compact: bool = False) -> "Bake":
+        """ct_debug_bake_shard: what shard `shard` of `shards` traces of a bake on a group, alone on `tracer` -- for timing it."""
+        d = _lib.CtBakeDesc(_lib.CT_ABI_VERSION, (C.c_uint32 * 3)(*[int(v) for v in grid]), int(azimuths), int(cosines))
+        kind = _lib.CT_BAKE_COMPACT if compact else _lib.CT_BAKE_SPARSE if sparse else _lib.CT_BAKE_DENSE
+        p = None
+        if adaptive is not None:
+            p = C.byref(_lib.CtBakeAdaptive(_lib.CT_ABI_VERSION, int(adaptive.round_samples), int(adaptive.max_samples), int(adaptive.zero_samples),
+                                            float(adaptive.rel_tol), float(adaptive.abs_tol)))
+        b = C.c_void_p()
+        check(_lib.load().ct_debug_bake_shard(tracer.h, C.byref(d), kind, int(samples), p, int(shard), int(shards), C.byref(b)), tracer.h)
+        return cls._adopt(tracer, b)
+
     def save(self, path):
         """ct_bake_save: this bake, of any kind and format, as a bake file (written under a temporary name and renamed)."""
         import os
@@ -836,3 +850,102 @@ class Bake:
         check(self.L.ct_bake_download(self.b, t.ctypes.data_as(C.c_void_p), t.size), self.tracer.h)
         nx, ny, nz = i["grid"]
         return t.reshape(nz, ny, nx, i["azimuths"], i["cosines"])
+
+
+def bake_spans_reference(active: int, shards: int) -> np.ndarray:
+    """The split of a bake on a group (include/cloudtrace.h, "bakes on a group") in numpy: `active` = the nodes a build covers
+    (every node of a dense bake, the active nodes in the list's order otherwise); shard i of `shards` owns the list positions
+    [floor(i A / n), floor((i + 1) A / n)) -> uint64 [shards, 2]."""
+    A, n = int(active), int(shards)
+    if A < 0 or n < 1:
+        raise ValueError("bake_spans_reference: active >= 0 and shards >= 1")
+    return np.array([[i * A // n, (i + 1) * A // n] for i in range(n)], np.uint64).reshape(n, 2)
+
+
+class _ShardTracer:
+    """What a Bake needs of its tracer, for a shard's handle that a TracerGroup owns."""
+
+    def __init__(self, h):
+        self.h = h
+
+
+class _BakeView(Bake):
+    """A Bake around a CtBake that a GroupBake owns: every accessor and save() work, close() only lets go of it."""
+
+    def close(self):
+        self.b = None
+
+
+class GroupBake:
+    """A CtGroupBake on a TracerGroup (ct_group_bake_*): one CtBake per shard.  Every build cuts the bake's nodes into one span
+    per shard (bake_spans_reference), every shard bakes or traces its span, and copies leave every shard with the whole bake,
+    which is the single-GPU bake bit for bit.  Made by TracerGroup.network_bake / traced_bake / traced_bake_adaptive / load_bake;
+    closed with, or before, its group.  shard(i) is shard i's bake as a network.Bake view: table(), counts(), info, save(), ..."""
+
+    def __init__(self, group, gb):
+        self.L, self.group, self.gb = group.L, group, gb
+        group.__dict__.setdefault("_bakes", []).append(self)
+
+    def close(self):
+        if getattr(self, "gb", None):
+            self.L.ct_group_bake_destroy(self.gb)
+            self.gb = None
+            if self in getattr(self.group, "_bakes", []):
+                self.group._bakes.remove(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def shard(self, index: int) -> Bake:
+        """ct_group_bake_shard -> a Bake view of shard `index`'s bake (owned by this GroupBake; do not change it through the view)."""
+        b, h = C.c_void_p(), C.c_void_p()
+        self.group._check(self.L.ct_group_bake_shard(self.gb, index, C.byref(b)))
+        self.group._check(self.L.ct_group_handle(self.group.g, index, C.byref(h)))
+        return _BakeView._adopt(_ShardTracer(h), b)
+
+    def spans(self) -> np.ndarray:
+        """ct_group_bake_spans -> uint64 [shards, 2]: lo and hi of every shard, node-list positions."""
+        n = C.c_uint32(0)
+        self.group._check(self.L.ct_group_size(self.group.g, C.byref(n)))
+        out = np.zeros((int(n.value), 2), np.uint64)
+        self.group._check(self.L.ct_group_bake_spans(self.gb, out.ctypes.data_as(C.c_void_p), out.size))
+        return out
+
+    def update(self, net):
+        """ct_group_bake_update: bake again for the group's light as it is now (TracerGroup.set_light) and the GroupNetwork `net`."""
+        self.group._check(self.L.ct_group_bake_update(self.gb, net.gn if net is not None else None))
+
+    def trace_more(self, samples: int):
+        """ct_group_bake_trace_more: Bake.trace_more on the group."""
+        self.group._check(self.L.ct_group_bake_trace_more(self.gb, int(samples)))
+
+    def retrace(self, samples: int):
+        """ct_group_bake_retrace: Bake.retrace on the group."""
+        self.group._check(self.L.ct_group_bake_retrace(self.gb, int(samples)))
+
+    def trace_adaptive_more(self, max_samples: int):
+        """ct_group_bake_trace_adaptive_more: Bake.trace_adaptive_more on the group."""
+        self.group._check(self.L.ct_group_bake_trace_adaptive_more(self.gb, int(max_samples)))
+
+    def retrace_adaptive(self):
+        """ct_group_bake_retrace_adaptive: Bake.retrace_adaptive on the group."""
+        self.group._check(self.L.ct_group_bake_retrace_adaptive(self.gb))
+
+    def save(self, path, shard: int = 0):
+        """ct_bake_save of shard `shard`'s bake: every shard holds the whole bake, so any shard's file is the bake's."""
+        self.shard(shard).save(path)
+
+    def exchange_info(self) -> dict:
+        """ct_debug_group_bake_exchange: bytes copied between shards by the last exchange and its host milliseconds."""
+        n, ms = C.c_uint64(0), C.c_double(0)
+        self.group._check(self.L.ct_debug_group_bake_exchange(self.gb, C.byref(n), C.byref(ms)))
+        return {"bytes": int(n.value), "ms": float(ms.value)}

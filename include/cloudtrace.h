@@ -1504,6 +1504,61 @@ CT_API int ct_group_adaptive_frame_download(CtGroupAdaptiveFrame gf, uint32_t wh
 CT_API int ct_group_adaptive_frame_device_ptr(CtGroupAdaptiveFrame gf, uint32_t which, void **out);
 CT_API int ct_group_adaptive_frame_destroy(CtGroupAdaptiveFrame gf);   /* NULL is a no-op; destroy before the group */
 
+/* ---- bakes on a group: a bake built and rendered across the group's GPUs -------------------
+ * A CtGroupBake holds one CtBake per shard, on that shard's device and handle.  Every call that builds or continues the bake
+ *   1. cuts the nodes the build covers into one span per shard: with A = Nx Ny Nz nodes for a dense bake, the active nodes in
+ *      the list's order otherwise, shard i of N owns the list positions [floor(i A / N), floor((i + 1) A / N)) in 64-bit
+ *      arithmetic (deepestscatter_amd.network.bake_spans_reference restates it).  A span covers whole node blocks -- x Nphi Nc
+ *      stored entries, x Nphi probes -- and may be empty (A < N, a bake without active nodes);
+ *   2. lets every shard bake or trace its own span with the single-GPU call, shards 1 .. N-1 each on a host thread of their own,
+ *      shard 0 on the caller.  Entry e's experiment f depends on (e, f) alone and a network record's output not on its batch, so
+ *      the values are the single-GPU bake's;
+ *   3. exchanges the results, so that EVERY SHARD THEN HOLDS THE COMPLETE BAKE (a shard's tiles look up anywhere in the table): a
+ *      span is one contiguous range of the stored arrays -- dense [lo B, hi B) with B = Nphi Nc, compact [B + lo B, B + hi B),
+ *      sparse [list[lo] B, (list[hi - 1] + 1) B), where only the zero blocks of inactive nodes lie between two shards' ranges --
+ *      and every shard's range of the table (an adaptive bake: of m2 and counts too) goes to every other shard with device-to-
+ *      device copies: peer copies across devices, plain copies where a device list repeats a device.  No collective, no kernel.
+ *      The lists of the entries left at the cap are concatenated in shard order into every shard's live list, ascending as the
+ *      single-GPU list is.  samples and rounds become the maximum over the shards (a shard whose entries all stop early ends
+ *      sooner), paths and the capped count the sums, the millisecond fields the slowest shard's.
+ * After a call returns CT_OK every shard's CtBake is indistinguishable -- bit for bit, for every N -- from the bake the same
+ * sequence of single-GPU calls leaves on one handle of the scene: stored table, table, slots, mask, directions, m2, counts, the
+ * live list, ct_bake_info, _storage_info, _sparse_info, _trace_info and _adaptive_info, the millisecond fields apart.  A file
+ * saved from any shard loads on a single handle as that bake and continues as it does; a single-GPU file loads on a group
+ * (ct_group_bake_load is ct_bake_load on every shard) and is continued under the same span rule.
+ * ct_group_baked_render_accumulate is ct_baked_render_shard_accumulate on every shard, each on a host thread of its own as in
+ * ct_group_network_render_accumulate; ct_group_merge then gives ct_baked_render_accumulate's mean and M2 of one handle, bit for
+ * bit.  A build leaves the group's and the shards' image state untouched.
+ * ct_group_bake_update follows ct_group_set_light; the uniform, adaptive and network calls refuse each other's bakes as the
+ * single-GPU calls do: their checks are passed through from shard 0 BEFORE any shard works, and such a refusal, like every
+ * argument error, leaves everything as it was.  When a shard fails in its work, the first failing shard's code and message are
+ * the group's and the CtGroupBake is good for ct_group_bake_destroy only: every other call returns CT_E_STATE and says so.
+ * ct_group_bake_shard gives shard `index`'s bake, owned by gb: every ct_bake_* accessor and ct_bake_save work on it, nothing that
+ * changes it may be called on it.  ct_group_bake_spans: lo and hi of every shard, 2 N words of node-list positions.
+ * ct_bake_half has no group form.  Nothing here has been run on more than one device; a device list that repeats a device takes
+ * the same path with plain copies.  CT_E_INVAL: a NULL argument (a NULL group or gb is answered without a device), a gn or gb of
+ * another group, an index >= the group's size, a wrong count.  Errors go to ct_group_last_error(g). */
+typedef struct CtGroupBake_ *CtGroupBake;
+CT_API int ct_group_network_bake(CtGroup g, CtGroupNetwork gn, const CtBakeDesc *d, uint32_t kind /*CT_BAKE_DENSE | _SPARSE | _COMPACT*/, CtGroupBake *out);
+CT_API int ct_group_bake_traced(CtGroup g, const CtBakeDesc *d, uint32_t kind, uint32_t samples, CtGroupBake *out);
+CT_API int ct_group_bake_traced_adaptive(CtGroup g, const CtBakeDesc *d, uint32_t kind, const CtBakeAdaptive *p, CtGroupBake *out);
+CT_API int ct_group_bake_load(CtGroup g, const char *path, CtGroupBake *out);
+CT_API int ct_group_bake_update(CtGroupBake gb, CtGroupNetwork gn);
+CT_API int ct_group_bake_trace_more(CtGroupBake gb, uint32_t samples);
+CT_API int ct_group_bake_retrace(CtGroupBake gb, uint32_t samples);
+CT_API int ct_group_bake_trace_adaptive_more(CtGroupBake gb, uint32_t max_samples);
+CT_API int ct_group_bake_retrace_adaptive(CtGroupBake gb);
+CT_API int ct_group_bake_shard(CtGroupBake gb, uint32_t index, CtBake *out);   /* owned by gb */
+CT_API int ct_group_bake_spans(CtGroupBake gb, uint64_t *lo_hi_out, size_t count);
+CT_API int ct_group_baked_render_accumulate(CtGroup g, CtGroupBake gb, const CtNetworkRender *p, uint32_t first_subframe_id, uint32_t count);
+CT_API int ct_group_bake_destroy(CtGroupBake gb);   /* NULL is a no-op; destroy before the group */
+/* Diagnostic: what shard `shard` of `shards` builds of ct_bake_traced (p == NULL) or ct_bake_traced_adaptive, alone on h: only
+ * its span of the table is traced, the rest is zero.  For timing one shard's work without the others (tools/traced_bake_time.py). */
+CT_API int ct_debug_bake_shard(CtHandle h, const CtBakeDesc *d, uint32_t kind, uint32_t samples, const CtBakeAdaptive *p, uint32_t shard,
+                               uint32_t shards, CtBake *out);
+/* Diagnostic: the bytes the last exchange of gb copied between shards and its milliseconds on the host's clock. */
+CT_API int ct_debug_group_bake_exchange(CtGroupBake gb, uint64_t *bytes_out, double *ms_out);
+
 /* ---- host-side helpers of the same path (pure CPU, no handle, no GPU) ------------------- */
 
 /* sutil::calculateCameraVariables(..., fov_is_vertical=false), src/Util/sutil.cpp:501-524, as

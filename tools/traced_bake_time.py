@@ -12,9 +12,14 @@ cloud, the default pose, a compact traced bake per grid (g^3 x --azimuths x --co
 (ct_bake_traced_adaptive) in place of the --samples list -- its rounds, converged and capped shares, paths and
 trace / fold / test ms (CtBakeAdaptiveInfo) -- and then a uniform bake of the nearest S with at least as many paths, each with
 the same distances.
+--shards N ...: the same bake on a group (ct_group_bake_*), rehearsed on one device: per N every shard's span
+is traced alone, one after the other (ct_debug_bake_shard), and the slowest shard's trace_ms + fold_ms + test_ms and wall ms are
+printed beside the whole bake's; then the bake is built once on TracerGroup([0] * N) for the bytes and the host ms of its
+exchange (ct_debug_group_bake_exchange) and the wall ms of the whole group call, whose shards share the one device there.
 Needs a GPU.  No threshold: resolution and samples are the user's trade.
     python tools/traced_bake_time.py [--volume 256] [--size 512] [--subframes 16] [--grids 16 32] [--azimuths 8] [--cosines 4]
-                                     [--samples 4 16 | --adaptive 16,256] [--estimator march|delta] [--kind compact|sparse|dense]"""
+                                     [--samples 4 16 | --adaptive 16,256] [--estimator march|delta] [--kind compact|sparse|dense]
+                                     [--shards 2 4 8]"""
 import argparse, json, statistics, sys, time
 from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
@@ -40,6 +45,7 @@ if __name__ == "__main__":
     ap.add_argument("--adaptive", default=None, metavar="R,MAX[,REL[,ABS[,ZERO]]]")
     ap.add_argument("--estimator", choices=["march", "delta"], default="march")
     ap.add_argument("--kind", choices=["compact", "sparse", "dense"], default="compact")
+    ap.add_argument("--shards", type=int, nargs="*", default=[])
     a = ap.parse_args()
     import numpy as np
     import torch  # noqa: F401  (before the library: descriptor_frame allocates through it)
@@ -96,4 +102,37 @@ if __name__ == "__main__":
                               "baked_subframe_gpu_ms": statistics.median(gpu[1:]),
                               "relative_l2_against_the_path_traced_mean": rel_l2(got, first, lit)}), flush=True)
             bake.close()
+            for n in a.shards:                                            # the same job cut for a group of n, on this one device
+                from deepestscatter_amd.network import AdaptiveParams, Bake
+                per_shard = []
+                for i in range(n):
+                    t0 = time.perf_counter()
+                    if samples is None:
+                        part = Bake.traced_shard(tr, (g, g, g), a.azimuths, a.cosines, i, n, adaptive=AdaptiveParams(**adaptive), **kw)
+                    else:
+                        part = Bake.traced_shard(tr, (g, g, g), a.azimuths, a.cosines, i, n, samples=samples, **kw)
+                    shard_wall = (time.perf_counter() - t0) * 1e3
+                    pi, pa = part.trace_info(), part.adaptive_info()
+                    per_shard.append({"wall_ms": shard_wall, "gpu_ms": pi["trace_ms"] + pi["fold_ms"] + pa["test_ms"], "paths": pi["paths"],
+                                      "rounds": pa["rounds"]})
+                    part.close()
+                grp = ds.TracerGroup(ds.make_procedural_cloud(a.volume), [0] * n, width=a.size, height=a.size,
+                                     estimator=0 if a.estimator == "march" else 1)
+                t0 = time.perf_counter()
+                if samples is None:
+                    gb = grp.traced_bake_adaptive((g, g, g), a.azimuths, a.cosines, **adaptive, **kw)
+                else:
+                    gb = grp.traced_bake((g, g, g), a.azimuths, a.cosines, samples, **kw)
+                group_wall = (time.perf_counter() - t0) * 1e3
+                ex = gb.exchange_info()
+                gb.close()
+                grp.close()
+                print(json.dumps({"route": "ct_group_bake_traced_adaptive" if samples is None else "ct_group_bake_traced", "rehearsal": "one device",
+                                  "grid": [g, g, g, a.azimuths, a.cosines], "samples": ti["samples"], "shards": n,
+                                  "whole_bake_gpu_ms": ti["trace_ms"] + ti["fold_ms"] + extra.get("test_ms", 0.0), "whole_bake_wall_ms": wall,
+                                  "slowest_shard_gpu_ms": max(s["gpu_ms"] for s in per_shard),
+                                  "slowest_shard_wall_ms": max(s["wall_ms"] for s in per_shard),
+                                  "shard_gpu_ms": [round(s["gpu_ms"], 3) for s in per_shard], "shard_paths": [s["paths"] for s in per_shard],
+                                  "shard_rounds": [s["rounds"] for s in per_shard],
+                                  "exchange_bytes": ex["bytes"], "exchange_ms": ex["ms"], "group_call_wall_ms_on_one_device": group_wall}), flush=True)
     tr.close()

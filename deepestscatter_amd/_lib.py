@@ -44,6 +44,8 @@ EXPORTS = [
     "ct_group_bake_trace_more", "ct_group_bake_retrace", "ct_group_bake_trace_adaptive_more", "ct_group_bake_retrace_adaptive",
     "ct_group_bake_shard", "ct_group_bake_spans", "ct_group_baked_render_accumulate", "ct_group_bake_destroy", "ct_debug_group_bake_exchange",
     "ct_debug_bake_shard",
+    "ct_baked_render_hybrid_subframe", "ct_baked_render_hybrid_accumulate", "ct_baked_render_hybrid_shard_subframe",
+    "ct_baked_render_hybrid_shard_accumulate", "ct_group_baked_render_hybrid_accumulate",
 ]
 # ... and the declared symbols whose names have digits (the list above is matched by name pattern)
 DEBUG_EXPORTS = ["ct_debug_bf16_round"]
@@ -441,6 +443,10 @@ def load():
         "ct_baked_render_shard_subframe": (i32, [vp, vp, C.POINTER(CtNetworkRender), u32, vp]),
         "ct_baked_render_shard_accumulate": (i32, [vp, vp, C.POINTER(CtNetworkRender), u32, u32]),
         "ct_debug_baked_render_time": (i32, [vp, C.POINTER(C.c_double)]),
+        "ct_baked_render_hybrid_subframe": (i32, [vp, vp, C.POINTER(CtNetworkRender), u32, u32, vp]),
+        "ct_baked_render_hybrid_accumulate": (i32, [vp, vp, C.POINTER(CtNetworkRender), u32, u32, u32]),
+        "ct_baked_render_hybrid_shard_subframe": (i32, [vp, vp, C.POINTER(CtNetworkRender), u32, u32, vp]),
+        "ct_baked_render_hybrid_shard_accumulate": (i32, [vp, vp, C.POINTER(CtNetworkRender), u32, u32, u32]),
         "ct_reset": (i32, [vp]),
         "ct_tonemap": (i32, [vp, f32, vp, C.POINTER(f32)]),
         "ct_tonemap_async": (i32, [vp, f32]),
@@ -527,6 +533,7 @@ def load():
         "ct_group_bake_shard": (i32, [vp, u32, C.POINTER(vp)]),
         "ct_group_bake_spans": (i32, [vp, vp, C.c_size_t]),
         "ct_group_baked_render_accumulate": (i32, [vp, vp, C.POINTER(CtNetworkRender), u32, u32]),
+        "ct_group_baked_render_hybrid_accumulate": (i32, [vp, vp, C.POINTER(CtNetworkRender), u32, u32, u32]),
         "ct_group_bake_destroy": (i32, [vp]),
         "ct_debug_group_bake_exchange": (i32, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
         "ct_debug_bake_shard": (i32, [vp, C.POINTER(CtBakeDesc), u32, u32, C.POINTER(CtBakeAdaptive), u32, u32, C.POINTER(vp)]),

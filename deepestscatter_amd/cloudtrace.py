@@ -540,6 +540,38 @@ class CloudTracer:
         p = self._network_render_params(transform, rgb_scale, band_pixels, direct)
         check(self.L.ct_baked_render_shard_accumulate(self.h, bake.b, C.byref(p), first_subframe_id & 0xFFFFFFFF, count), self.h)
 
+    # -- hybrid frames (ct_baked_render_hybrid_*): the path tracer's path through `depth` collisions, then the bake ------------
+    def baked_render_hybrid_subframe(self, bake, depth: int, subframe_id: int, transform="linear", rgb_scale=(1.0, 1.0, 1.0),
+                                     band_pixels: int = 0, out=None, direct: bool = True):
+        """ct_baked_render_hybrid_subframe: baked_render_subframe with the mode-0 path followed through its first `depth` (1 .. 64,
+        below max_depth) collisions, their NEE terms added as the path tracer adds them, and `bake` read at collision `depth`
+        along the direction the path arrived in.  depth 1 is baked_render_subframe; from depth 2 on `direct` must be True."""
+        def entry(h, b, p, sid, ptr):
+            return self.L.ct_baked_render_hybrid_subframe(h, b, p, int(depth) & 0xFFFFFFFF, sid, ptr)
+        return self._network_render_subframe(entry, bake.b, subframe_id, transform, rgb_scale, band_pixels, out, direct)
+
+    def baked_render_hybrid_accumulate(self, bake, depth: int, first_subframe_id: int, count: int, transform="linear",
+                                       rgb_scale=(1.0, 1.0, 1.0), band_pixels: int = 0, direct: bool = True):
+        """ct_baked_render_hybrid_accumulate: baked_render_hybrid_subframe(id) + accumulate(id) for the ids, fused."""
+        p = self._network_render_params(transform, rgb_scale, band_pixels, direct)
+        check(self.L.ct_baked_render_hybrid_accumulate(self.h, bake.b, C.byref(p), int(depth) & 0xFFFFFFFF, first_subframe_id & 0xFFFFFFFF,
+                                                       count), self.h)
+
+    def baked_render_hybrid_shard_subframe(self, bake, depth: int, subframe_id: int, transform="linear", rgb_scale=(1.0, 1.0, 1.0),
+                                           band_pixels: int = 0, out=None, direct: bool = True):
+        """ct_baked_render_hybrid_shard_subframe: baked_render_hybrid_subframe on a tracer of any shard_count (foreign pixels
+        (0, 0, 0, 0))."""
+        def entry(h, b, p, sid, ptr):
+            return self.L.ct_baked_render_hybrid_shard_subframe(h, b, p, int(depth) & 0xFFFFFFFF, sid, ptr)
+        return self._network_render_subframe(entry, bake.b, subframe_id, transform, rgb_scale, band_pixels, out, direct)
+
+    def baked_render_hybrid_shard_accumulate(self, bake, depth: int, first_subframe_id: int, count: int, transform="linear",
+                                             rgb_scale=(1.0, 1.0, 1.0), band_pixels: int = 0, direct: bool = True):
+        """ct_baked_render_hybrid_shard_accumulate: baked_render_hybrid_accumulate on a tracer of any shard_count."""
+        p = self._network_render_params(transform, rgb_scale, band_pixels, direct)
+        check(self.L.ct_baked_render_hybrid_shard_accumulate(self.h, bake.b, C.byref(p), int(depth) & 0xFFFFFFFF,
+                                                             first_subframe_id & 0xFFFFFFFF, count), self.h)
+
     def baked_render_time(self) -> float:
         """GPU milliseconds of the last baked_render_* call (ct_debug_baked_render_time)."""
         ms = C.c_double(0)
@@ -1014,6 +1046,14 @@ class TracerGroup:
         p = CloudTracer._network_render_params(transform, rgb_scale, band_pixels, direct)
         self._check(self.L.ct_group_baked_render_accumulate(self.g, bake.gb if bake is not None else None, C.byref(p),
                                                             first_subframe_id & 0xFFFFFFFF, count))
+
+    def baked_render_hybrid_accumulate(self, bake, depth: int, first_subframe_id: int, count: int, transform="linear",
+                                       rgb_scale=(1.0, 1.0, 1.0), band_pixels: int = 0, direct: bool = True):
+        """ct_group_baked_render_hybrid_accumulate: CloudTracer.baked_render_hybrid_shard_accumulate of the GroupBake `bake` on
+        every shard; mean(), m2() and tonemap() then give what baked_render_hybrid_accumulate gives on one tracer."""
+        p = CloudTracer._network_render_params(transform, rgb_scale, band_pixels, direct)
+        self._check(self.L.ct_group_baked_render_hybrid_accumulate(self.g, bake.gb if bake is not None else None, C.byref(p),
+                                                                   int(depth) & 0xFFFFFFFF, first_subframe_id & 0xFFFFFFFF, count))
 
     def adaptive_frame(self, **params):
         """ct_group_adaptive_frame_create -> adaptive.GroupAdaptiveFrame: CloudTracer.adaptive_frame's image with every shard

@@ -23,7 +23,7 @@ int net_validate_network(CtHandle h, CtNetwork n, const char *who);
 size_t net_descriptor_limit(CtHandle h);
 // Everything a call needs before its first kernel: the band-sized temporaries and a first piece of the descriptor array.  The
 // stream is idle.  A failed growth leaves what the handle had.  direct: the call carries CT_NET_ADD_SINGLE_SCATTER.
-int net_reserve(CtHandle h, size_t band_pixels, bool direct);
+int net_reserve(CtHandle h, size_t band_pixels, bool direct, bool hybrid = false);
 // The descriptor array follows the largest record count seen.  Between bands, the stream idle.  When the device has no room
 // for it the array stays as it is and the band's records are gathered and evaluated in pieces of its size.
 void net_grow_descriptors(CtHandle h, size_t count);

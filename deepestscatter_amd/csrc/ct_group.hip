@@ -1136,10 +1136,12 @@ extern "C" int ct_debug_group_bake_exchange(CtGroupBake gb, uint64_t *bytes_out,
     return CT_OK;
 }
 
-// ct_baked_render_shard_accumulate on every shard, as ct_group_network_render_accumulate runs the network renderer.
-extern "C" int ct_group_baked_render_accumulate(CtGroup g, CtGroupBake gb, const CtNetworkRender *p, uint32_t first_subframe_id, uint32_t count)
+// ct_baked_render_shard_accumulate -- with a depth (1 .. 64), ct_baked_render_hybrid_shard_accumulate -- on every shard, as
+// ct_group_network_render_accumulate runs the network renderer.
+static int group_baked_accumulate(CtGroup g, CtGroupBake gb, const CtNetworkRender *p, uint32_t depth, bool hybrid, uint32_t first_subframe_id,
+                                  uint32_t count)
 {
-    const char *const who = "ct_group_baked_render_accumulate";
+    const char *const who = hybrid ? "ct_group_baked_render_hybrid_accumulate" : "ct_group_baked_render_accumulate";
     if (!g) {
         return gfail(nullptr, CT_E_INVAL, "null group");
     }
@@ -1153,7 +1155,8 @@ extern "C" int ct_group_baked_render_accumulate(CtGroup g, CtGroupBake gb, const
     const uint32_t shards = (uint32_t)g->handles.size();
     std::vector<int> codes;
     const uint32_t bad = on_every_shard(shards, codes, [&](uint32_t i) {
-        return ct_baked_render_shard_accumulate(g->handles[i], gb->bakes[i], p, first_subframe_id, count);
+        return hybrid ? ct_baked_render_hybrid_shard_accumulate(g->handles[i], gb->bakes[i], p, depth, first_subframe_id, count)
+                      : ct_baked_render_shard_accumulate(g->handles[i], gb->bakes[i], p, first_subframe_id, count);
     });
     g->merged = false;
     if (bad < shards) {
@@ -1161,4 +1164,15 @@ extern "C" int ct_group_baked_render_accumulate(CtGroup g, CtGroupBake gb, const
     }
     g->subframes = first_subframe_id + count - 1;
     return CT_OK;
+}
+
+extern "C" int ct_group_baked_render_accumulate(CtGroup g, CtGroupBake gb, const CtNetworkRender *p, uint32_t first_subframe_id, uint32_t count)
+{
+    return group_baked_accumulate(g, gb, p, 0u, false, first_subframe_id, count);
+}
+
+extern "C" int ct_group_baked_render_hybrid_accumulate(CtGroup g, CtGroupBake gb, const CtNetworkRender *p, uint32_t depth,
+                                                       uint32_t first_subframe_id, uint32_t count)
+{
+    return group_baked_accumulate(g, gb, p, depth, true, first_subframe_id, count);
 }

@@ -246,9 +246,10 @@ struct CtHandle_ {
     // many bands, a render many frames).  The baked renderer uses found / waves / direct only, reserved at the same sizes.
     // found / waves / pos / dir / aux / out hold a band of band_cap pixels; desc holds desc_records() records, the largest count
     // seen so far (or what the device gave: a band with more records goes through gather and network in pieces).  direct holds
-    // a band of direct.capacity() pixels and exists from the first call with CT_NET_ADD_SINGLE_SCATTER on.
+    // a band of direct.capacity() pixels and exists from the first call with CT_NET_ADD_SINGLE_SCATTER on; omega likewise, from
+    // the first ct_baked_render_hybrid_* call on.
     struct NetScratch {
-        DevBuf<float4> found, direct;
+        DevBuf<float4> found, direct, omega;
         DevBuf<uint32_t> waves;
         DevBuf<float> pos, dir, aux, out;
         DevBuf<uint8_t> desc;

@@ -297,6 +297,14 @@ hipError_t launch_bake_store_list(const float *out, const uint32_t *list, uint64
                                   uint32_t stride, uint32_t k, hipStream_t stream);
 hipError_t launch_baked_compose(const DevScene &sc, const PixelBand &band, const FlightTemps &t, const BakeTable &table, const NetCompose &c,
                                 const ComposeTarget &dst, const uint32_t *frozen, hipStream_t stream);
+// ct_baked_render_hybrid_*: launch_first_flights followed through the path tracer's first `depth` collisions -- found[i].w = 0
+// none, 1 alive at collision `depth`, 2 ended before it; t.direct = the NEE sum so far (NULL: depth 1 without the single-scatter
+// term); omega (as large as found) = the direction the path reached its collision along; t.waves is not used -- and
+// launch_baked_compose with that direction and the ended state.
+hipError_t launch_hybrid_flights(const DevScene &sc, const PixelBand &band, const FlightTemps &t, float4 *omega, uint32_t subframe_id,
+                                 uint32_t depth, hipStream_t stream);
+hipError_t launch_hybrid_compose(const DevScene &sc, const PixelBand &band, const FlightTemps &t, const float4 *omega, const BakeTable &table,
+                                 const NetCompose &c, const ComposeTarget &dst, const uint32_t *frozen, hipStream_t stream);
 // Bake files and half tables (ct_bake_file.hip).  launch_volume_hash: *hash (zeroed by the caller) += the volume hash of
 // include/cloudtrace.h, "bake files", over `count` texels, in whatever order the waves run.  launch_bake_half_convert: half[i] =
 // half_round_bits(table[i]) for i < count, one lane per value; refused[0] (zeroed) counts the values ct_bake_half refuses and

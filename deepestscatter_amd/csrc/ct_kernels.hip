@@ -3917,6 +3917,133 @@ hipError_t launch_baked_compose(const DevScene &sc, const PixelBand &band, const
 }
 
 // =============================================================================================
+// the hybrid frame (ct_baked_render_hybrid_*): the path tracer's own path for its first `depth` collisions, then the table.
+// =============================================================================================
+// hybrid_flight_kernel: lane i is lane i of the band, as in first_scatter_frame_kernel, and the path is the one
+// render_simple_kernel draws in mode 0 for the lane's pixel and subframe -- the same seed, one draw per flight, then
+// new_direction's draws, the march flight (plain_flight), the NEE with the un-chopped table at the first collision and the
+// chopped one after.  It writes found[i] = (x_k - half box, state): 0 no collision (a miss, a clipped lane), 1 alive at collision
+// `depth`, 2 ended before it (a flight left the box); omega[i] = the direction the path travelled along when it reached x_k; and,
+// where `direct` is not NULL, direct[i] = S, the sum of the NEE terms so far in the path tracer's order (from (0, 0, 0)).
+// direct == NULL is depth 1 without CT_NET_ADD_SINGLE_SCATTER: no NEE is evaluated.
+// The bounce loop is left per wave: a wave whose lanes all missed or ended pays for nothing further.
+template <bool FIXED8, bool TILES>
+__global__ __launch_bounds__(256) void hybrid_flight_kernel(DevScene sc, PixelBand r, uint32_t subframe_id, uint32_t depth,
+                                                            float4 *__restrict__ found, float4 *__restrict__ direct,
+                                                            float4 *__restrict__ omega)
+{
+    __shared__ MieLds lds;
+    load_tables(sc, lds);   // (ends with the block's barrier: no early return before it)
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const f3 half_box = scale3(mk3(sc.bx, sc.by, sc.bz), 0.5f);
+    uint32_t state = 0u, seed = 0u;
+    f3 pos = mk3(0, 0, 0), dir = mk3(0, 0, 0), S = mk3(0, 0, 0);
+    if (i < r.n) {
+        uint32_t x, y;
+        const bool pixel = band_pixel<TILES>(r, i, x, y);
+        const f3 eye = mk3(sc.ex, sc.ey, sc.ez);
+        const f3 d = primary_direction(sc, x, y);
+        float t_hit = 0;
+        if (pixel && intersect_box(sc, eye, d, t_hit)) {
+            pos = add3(add3(eye, scale3(d, t_hit)), half_box);   // cloudRadianceMaterials.cu:11-12
+            dir = normalize3(d);                                 // :17
+            seed = tea4(x * 4096u + y, subframe_id);             // :21
+            const float xi = u24_to_float(lcg24(seed));
+            if (plain_flight<FIXED8>(sc, xi, pos, dir) && in_box(sc, pos)) {
+                state = 1u;
+            }
+        }
+    }
+    for (uint32_t k = 1u;; k++) {   // the lanes in state 1 are at collision k
+        if (__builtin_amdgcn_ballot_w64(state == 1u) == 0ull) {
+            break;
+        }
+        if (state == 1u && direct) {
+            S = add3(S, in_scattering<FIXED8>(sc, pos, dir, k != 1u));
+        }
+        if (k == depth) {
+            break;
+        }
+        if (state == 1u) {
+            dir = new_direction(lds.cdf, lds.guide, seed, dir);
+            const float xi = u24_to_float(lcg24(seed));
+            if (!(plain_flight<FIXED8>(sc, xi, pos, dir) && in_box(sc, pos))) {
+                state = 2u;
+            }
+        }
+    }
+    if (i < r.n) {
+        const f3 world = state == 1u ? sub3(pos, half_box) : mk3(0, 0, 0);
+        found[i] = make_float4(world.x, world.y, world.z, (float)state);
+        omega[i] = make_float4(dir.x, dir.y, dir.z, 0.f);
+        if (direct) {
+            direct[i] = make_float4(S.x, S.y, S.z, 0.f);
+        }
+    }
+}
+
+// baked_compose_kernel with the direction read from the flight's temporary, the ended state -- the pixel is (S, 1) -- and S
+// where that kernel takes the single-scatter term (direct == NULL: nothing is added).  Everything else is the shared code.
+template <bool ACCUMULATE, bool TILES, bool COMPACT, bool HALF>
+__global__ __launch_bounds__(256) void hybrid_compose_kernel(DevScene sc, PixelBand b, const float4 *__restrict__ found, BakeTable t,
+                                                             NetCompose c, float4 *__restrict__ frame, float4 *__restrict__ mean,
+                                                             float4 *__restrict__ m2, uint32_t subframe_id,
+                                                             const uint32_t *__restrict__ frozen, const float4 *__restrict__ direct,
+                                                             const float4 *__restrict__ omega)
+{
+    if (ACCUMULATE && frozen && *frozen != 0u) {
+        return;   // the image has converged (converged_freeze_kernel): the running mean stays as it is
+    }
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= b.n) {
+        return;
+    }
+    uint32_t x, y;
+    if (!band_pixel<TILES>(b, i, x, y)) {
+        return;
+    }
+    const size_t at = TILES ? (size_t)y * b.width + x : (size_t)i;
+    const float4 f = found[i];
+    float4 v = compose_miss();
+    if (f.w == 1.f) {
+        const float4 w = omega[i];
+        const float o = bake_lookup<COMPACT, HALF>(sc, t, mk3(f.x, f.y, f.z), mk3(w.x, w.y, w.z));
+        v = direct ? compose_value<true>(c, o, direct, i) : compose_value<false>(c, o, direct, i);
+    } else if (f.w == 2.f) {
+        const float4 s = direct[i];   // (an ended path has depth >= 2, and such a call has S)
+        v = make_float4(s.x, s.y, s.z, 1.f);
+    }
+    compose_store<ACCUMULATE>(v, at, frame, mean, m2, subframe_id);
+}
+
+hipError_t launch_hybrid_flights(const DevScene &sc, const PixelBand &band, const FlightTemps &t, float4 *omega, uint32_t subframe_id,
+                                 uint32_t depth, hipStream_t stream)
+{
+    static constexpr decltype(&hybrid_flight_kernel<false, false>) flights[4] = { hybrid_flight_kernel<false, false>, hybrid_flight_kernel<true, false>,
+                                                                                  hybrid_flight_kernel<false, true>, hybrid_flight_kernel<true, true> };
+    const bool tiles = band.tiles != nullptr;
+    hipLaunchKernelGGL(flights[2 * tiles + (sc.tex_fixed8 ? 1 : 0)], dim3((band.n + 255u) / 256u), dim3(256), 0, stream, sc, band, subframe_id,
+                       depth, t.found, t.direct, omega);
+    return hipGetLastError();
+}
+
+hipError_t launch_hybrid_compose(const DevScene &sc, const PixelBand &band, const FlightTemps &t, const float4 *omega, const BakeTable &table,
+                                 const NetCompose &c, const ComposeTarget &dst, const uint32_t *frozen, hipStream_t stream)
+{
+#define K(COMPACT, HALF) \
+    hybrid_compose_kernel<false, false, COMPACT, HALF>, hybrid_compose_kernel<false, true, COMPACT, HALF>, \
+    hybrid_compose_kernel<true, false, COMPACT, HALF>, hybrid_compose_kernel<true, true, COMPACT, HALF>
+    static constexpr decltype(&hybrid_compose_kernel<false, false, false, false>) composes[16] = { K(false, false), K(true, false), K(false, true),
+                                                                                                  K(true, true) };
+#undef K
+    const bool accumulate = dst.frame == nullptr, tiles = band.tiles != nullptr;
+    const bool compact = table.slots != nullptr, half = table.half != nullptr;
+    hipLaunchKernelGGL(composes[8 * half + 4 * compact + 2 * accumulate + tiles], dim3((band.n + 255u) / 256u), dim3(256), 0, stream, sc, band,
+                       (const float4 *)t.found, table, c, dst.frame, dst.mean, dst.m2, dst.subframe_id, frozen, (const float4 *)t.direct, omega);
+    return hipGetLastError();
+}
+
+// =============================================================================================
 // progressive accumulation (progressive.cu:17-27) of S consecutive subframes, in order.
 // Only this shard's pixels are touched; everything else stays exactly 0 so that a sum over
 // shards (RCCL) reproduces the single-GPU image bit for bit.

@@ -248,11 +248,16 @@ size_t ct::net_descriptor_limit(CtHandle h)
     return (size_t)knob_int(h->tune.NET_DESC_RECORDS, 1, 1 << 20, 1 << 20);
 }
 
-int ct::net_reserve(CtHandle h, size_t band_pixels, bool direct)
+int ct::net_reserve(CtHandle h, size_t band_pixels, bool direct, bool hybrid)
 {
     CtHandle_::NetScratch &s = h->net;
     const size_t n_pad = (band_pixels + 255u) / 256u * 256u;
     // (allocate, then swap, here and in net_grow_descriptors)
+    if (hybrid && n_pad > s.omega.capacity()) {
+        DevBuf<float4> omega;
+        HIPCHK(h, omega.alloc(n_pad));
+        s.omega = std::move(omega);
+    }
     if (direct && n_pad > s.direct.capacity()) {
         DevBuf<float4> sun;
         HIPCHK(h, sun.alloc(n_pad));
@@ -325,7 +330,7 @@ static int net_ensure_tiles(CtHandle h)
 }
 
 // ---- the renderer: the network evaluated band by band (ct_network_render_*) or looked up in its bake (ct_baked_render_*) -------
-// A call of one of the eight entry points.  Its bands are made of units: rows of the frame, or (tiles: the *_shard_* entry
+// A call of one of the twelve entry points.  Its bands are made of units: rows of the frame, or (tiles: the *_shard_* entry
 // points) tiles of the shard's tile list.  The entry point fills the first part, net_begin the second.
 struct NetCall {
     const char *who;
@@ -333,10 +338,29 @@ struct NetCall {
     CtBake b;          // ... or (baked) its bake; the other one is NULL
     const CtNetworkRender *p;
     bool baked, tiles;
+    uint32_t depth;    // ct_baked_render_hybrid_*: the collisions the path is traced through before the bake is read; 0 otherwise
+    bool hybrid;       // ... and that the call is one of them
     bool accumulate;   // into mean / M2 instead of the frame
     bool direct;       // the call carries CT_NET_ADD_SINGLE_SCATTER
     DescriptorScale ds;
 };
+
+// A hybrid call's depth: 1 .. 64, below the scene's max_depth (the path tracer itself stops there), and from 2 on only with the
+// single-scatter term, without which the sum is no picture the library defines.
+static int net_validate_depth(CtHandle h, const NetCall &c)
+{
+    if (c.depth == 0u || c.depth > 64u) {
+        return fail(h, CT_E_INVAL, "%s: depth %u is outside 1 .. 64", c.who, c.depth);
+    }
+    if (c.depth >= h->scene.max_depth) {
+        return fail(h, CT_E_INVAL, "%s: depth %u is not below the scene's max_depth %u", c.who, c.depth, h->scene.max_depth);
+    }
+    if (c.depth >= 2u && !(c.p->transform & CT_NET_ADD_SINGLE_SCATTER)) {
+        return fail(h, CT_E_INVAL, "%s: depth %u needs CT_NET_ADD_SINGLE_SCATTER (only depth 1 is defined without the first collision's term)",
+                    c.who, c.depth);
+    }
+    return CT_OK;
+}
 
 // What the entry points do before they run: the handle, every argument (first: a rejected call leaves the handle exactly as it
 // was, batches in flight included), the camera, a bake's light, then the wait for the batches in flight.  bad_ids: NULL, or the
@@ -355,7 +379,10 @@ static int net_begin(CtHandle h, NetCall &c, bool accumulate, const char *bad_id
         rc = c.baked ? bake_foreign(h, c.b, c.who) : net_validate_network(h, c.n, c.who);
     }
     if (rc == CT_OK) {
-        rc = net_validate_shards(h, c.who, c.tiles, c.baked ? "ct_baked_render" : "ct_network_render");
+        rc = net_validate_shards(h, c.who, c.tiles, c.hybrid ? "ct_baked_render_hybrid" : c.baked ? "ct_baked_render" : "ct_network_render");
+    }
+    if (rc == CT_OK && c.hybrid) {
+        rc = net_validate_depth(h, c);
     }
     if (rc != CT_OK) {
         return rc;
@@ -388,7 +415,8 @@ static uint32_t net_band_units(CtHandle h, const NetCall &c)
 }
 
 // One band of subframe `sid`, units [unit0, unit0 + units) of the call, into the frame or into mean / M2.
-// Baked: the flights and one kernel that looks the table up and forms the pixels, enqueued only.  Otherwise the flights with
+// Baked: the flights and one kernel that looks the table up and forms the pixels, enqueued only; hybrid: the same two steps with
+// the flights followed through c.depth collisions and their directions in a third temporary.  Otherwise the flights with
 // scan and compaction, the wait for the record count, gather and network in pieces of the descriptor array, and the compose
 // kernel; every stage is waited for and booked into h->net.ms.
 static int net_band(CtHandle h, const NetCall &c, uint32_t sid, uint32_t unit0, uint32_t units)
@@ -401,6 +429,11 @@ static int net_band(CtHandle h, const NetCall &c, uint32_t sid, uint32_t unit0, 
     const size_t first_pixel = c.tiles ? 0 : (size_t)unit0 * W;   // (the tile path writes at y * W + x of the whole frame)
     const ComposeTarget dst{ c.accumulate ? nullptr : h->d_frame + first_pixel, h->d_mean + first_pixel, h->d_m2 + first_pixel, sid };
     const uint32_t *const frozen = h->stop_cadence ? h->d_freeze : nullptr;
+    if (c.hybrid) {
+        HIPCHK(h, launch_hybrid_flights(h->dev, band, temps, s.omega, sid, c.depth, h->stream));
+        HIPCHK(h, launch_hybrid_compose(h->dev, band, temps, s.omega, bake_table(c.b), compose, dst, frozen, h->stream));
+        return CT_OK;
+    }
     if (c.baked) {
         HIPCHK(h, launch_first_flights(h->dev, band, temps, sid, h->stream));
         HIPCHK(h, launch_baked_compose(h->dev, band, temps, bake_table(c.b), compose, dst, frozen, h->stream));
@@ -469,7 +502,7 @@ static int net_run(CtHandle h, const NetCall &c, uint32_t first, uint32_t count)
         // (bands of the row path run bottom to top over H rows; those of the tile path over the list's n_tiles tiles)
         const uint32_t units = c.tiles ? h->net.n_tiles : H;
         const size_t band = c.tiles ? (size_t)64 * std::min(per_band, std::max(units, 1u)) : (size_t)W * per_band;
-        rc = net_reserve(h, band, c.direct);
+        rc = net_reserve(h, band, c.direct, c.hybrid);
         if (rc == CT_OK && !c.baked) {
             rc = ensure_pyramid(h);
         }
@@ -600,6 +633,30 @@ extern "C" int ct_baked_render_shard_accumulate(CtHandle h, CtBake b, const CtNe
     return net_accumulate(h, { "ct_baked_render_shard_accumulate", nullptr, b, p, true, true }, first_subframe_id, count);
 }
 
+
+extern "C" int ct_baked_render_hybrid_subframe(CtHandle h, CtBake b, const CtNetworkRender *p, uint32_t depth, uint32_t subframe_id,
+                                               float *frame_rgba_dev)
+{
+    return net_subframe(h, { "ct_baked_render_hybrid_subframe", nullptr, b, p, true, false, depth, true }, subframe_id, frame_rgba_dev);
+}
+
+extern "C" int ct_baked_render_hybrid_shard_subframe(CtHandle h, CtBake b, const CtNetworkRender *p, uint32_t depth, uint32_t subframe_id,
+                                                     float *frame_rgba_dev)
+{
+    return net_subframe(h, { "ct_baked_render_hybrid_shard_subframe", nullptr, b, p, true, true, depth, true }, subframe_id, frame_rgba_dev);
+}
+
+extern "C" int ct_baked_render_hybrid_accumulate(CtHandle h, CtBake b, const CtNetworkRender *p, uint32_t depth, uint32_t first_subframe_id,
+                                                 uint32_t count)
+{
+    return net_accumulate(h, { "ct_baked_render_hybrid_accumulate", nullptr, b, p, true, false, depth, true }, first_subframe_id, count);
+}
+
+extern "C" int ct_baked_render_hybrid_shard_accumulate(CtHandle h, CtBake b, const CtNetworkRender *p, uint32_t depth,
+                                                       uint32_t first_subframe_id, uint32_t count)
+{
+    return net_accumulate(h, { "ct_baked_render_hybrid_shard_accumulate", nullptr, b, p, true, true, depth, true }, first_subframe_id, count);
+}
 
 extern "C" int ct_debug_baked_render_time(CtHandle h, double *gpu_ms_out)
 {

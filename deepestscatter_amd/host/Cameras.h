@@ -210,6 +210,29 @@ namespace DeepestScatter
                 throw std::runtime_error("--bake-in: the file holds a half table made under another light, and a half bake is final; bake again");
             return info.current != 0;
         }
+        // One subframe, or `count` accumulated ones, from the table: ct_baked_render_*, or with a depth (--net-trace-depth K) the hybrid
+        // frames of ct_baked_render_hybrid_*; on a group every GPU renders its own tiles.
+        void render(const Context& context, const CtNetworkRender& params, uint32_t depth, uint32_t subframeId, float* frameResultBuffer) const
+        {
+            if (depth) Context::check(ct_baked_render_hybrid_subframe(context.handle, shown(), &params, depth, subframeId, frameResultBuffer), context.handle,
+                                      "ct_baked_render_hybrid_subframe");
+            else Context::check(ct_baked_render_subframe(context.handle, shown(), &params, subframeId, frameResultBuffer), context.handle,
+                                "ct_baked_render_subframe");
+        }
+        void renderAccumulate(const Context& context, const CtNetworkRender& params, uint32_t depth, uint32_t first, uint32_t count) const
+        {
+            if (context.group && depth)
+                Context::checkGroup(ct_group_baked_render_hybrid_accumulate(context.group, groupBake, &params, depth, first, count), context.group,
+                                    "ct_group_baked_render_hybrid_accumulate");
+            else if (context.group)
+                Context::checkGroup(ct_group_baked_render_accumulate(context.group, groupBake, &params, first, count), context.group,
+                                    "ct_group_baked_render_accumulate");
+            else if (depth)
+                Context::check(ct_baked_render_hybrid_accumulate(context.handle, shown(), &params, depth, first, count), context.handle,
+                               "ct_baked_render_hybrid_accumulate");
+            else
+                Context::check(ct_baked_render_accumulate(context.handle, shown(), &params, first, count), context.handle, "ct_baked_render_accumulate");
+        }
         CtBake bake = nullptr, halfCopy = nullptr;
         CtGroupBake groupBake = nullptr;
     };
@@ -225,8 +248,9 @@ namespace DeepestScatter
     {
     public:
         BakedRenderer(std::shared_ptr<Context> context, std::shared_ptr<const NetworkFile> file, const CtNetworkRender& params, const CtBakeDesc& desc,
-                      bool sparse = false, bool compact = false, const BakeFiles& files = {})
-            : NetworkRenderer(std::move(context), std::move(file), params), desc(desc), sparse(sparse), compact(compact), files(files) {}
+                      bool sparse = false, bool compact = false, const BakeFiles& files = {}, uint32_t traceDepth = 0)
+            : NetworkRenderer(std::move(context), std::move(file), params), desc(desc), sparse(sparse), compact(compact), files(files),
+              traceDepth(traceDepth) {}
 
         void init() override
         {
@@ -258,22 +282,14 @@ namespace DeepestScatter
             if (context->group) throw std::runtime_error("the two-launch loop (--unfused) renders on one GPU only");
             applyCamera();
             refresh();
-            Context::check(ct_baked_render_subframe(context->handle, table.shown(), &params, subframeId, frameResultBuffer), context->handle,
-                           "ct_baked_render_subframe");
+            table.render(*context, params, traceDepth, subframeId, frameResultBuffer);
         }
 
         void renderAccumulate(uint32_t first, uint32_t count, bool /*enqueue: the call waits once, at its end*/) override
         {
             applyCamera();
             refresh();
-            if (context->group)
-            {
-                Context::checkGroup(ct_group_baked_render_accumulate(context->group, table.groupBake, &params, first, count), context->group,
-                                    "ct_group_baked_render_accumulate");
-                return;
-            }
-            Context::check(ct_baked_render_accumulate(context->handle, table.shown(), &params, first, count), context->handle,
-                           "ct_baked_render_accumulate");
+            table.renderAccumulate(*context, params, traceDepth, first, count);
         }
 
     private:
@@ -289,6 +305,7 @@ namespace DeepestScatter
         CtBakeDesc desc;
         bool sparse, compact;
         BakeFiles files;
+        uint32_t traceDepth;   // --net-trace-depth K: hybrid frames of depth K (0: the table is read at the first collision)
         BakeHolder table;   // (destroyed before the network and the handle)
     };
 
@@ -302,9 +319,9 @@ namespace DeepestScatter
     {
     public:
         TracedBakeRenderer(std::shared_ptr<Context> context, const CtNetworkRender& params, const CtBakeDesc& desc, uint32_t kind, uint32_t samples,
-                           const CtBakeAdaptive* adaptive = nullptr, const BakeFiles& files = {})
+                           const CtBakeAdaptive* adaptive = nullptr, const BakeFiles& files = {}, uint32_t traceDepth = 0)
             : PathTracingRenderer(std::move(context)), params(params), desc(desc), kind(kind), samples(samples), isAdaptive(adaptive != nullptr),
-              adaptive(adaptive ? *adaptive : CtBakeAdaptive{}), files(files) {}
+              adaptive(adaptive ? *adaptive : CtBakeAdaptive{}), files(files), traceDepth(traceDepth) {}
 
         void init() override
         {
@@ -339,22 +356,14 @@ namespace DeepestScatter
             if (context->group) throw std::runtime_error("the two-launch loop (--unfused) renders on one GPU only");
             applyCamera();
             refresh();
-            Context::check(ct_baked_render_subframe(context->handle, table.shown(), &params, subframeId, frameResultBuffer), context->handle,
-                           "ct_baked_render_subframe");
+            table.render(*context, params, traceDepth, subframeId, frameResultBuffer);
         }
 
         void renderAccumulate(uint32_t first, uint32_t count, bool /*enqueue: the call waits once, at its end*/) override
         {
             applyCamera();
             refresh();
-            if (context->group)
-            {
-                Context::checkGroup(ct_group_baked_render_accumulate(context->group, table.groupBake, &params, first, count), context->group,
-                                    "ct_group_baked_render_accumulate");
-                return;
-            }
-            Context::check(ct_baked_render_accumulate(context->handle, table.shown(), &params, first, count), context->handle,
-                           "ct_baked_render_accumulate");
+            table.renderAccumulate(*context, params, traceDepth, first, count);
         }
 
     private:
@@ -389,6 +398,7 @@ namespace DeepestScatter
         bool isAdaptive;
         CtBakeAdaptive adaptive;
         BakeFiles files;
+        uint32_t traceDepth;   // --net-trace-depth K, as in BakedRenderer
         BakeHolder table;   // (destroyed before the handle)
     };
 

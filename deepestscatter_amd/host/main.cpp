@@ -28,6 +28,9 @@
 //              [--bake-out FILE]                with --net-baked or --traced-bake: save the table as a bake file (ct_bake_save; with --gpus shard 0's, which is the whole table)
 //              [--bake-in FILE]                 in place of --net-baked / --traced-bake and their flags: render from the table in FILE
 //                               (ct_bake_load); a traced file needs no network, a network's bake needs its --network FILE (a new light bakes it again)
+//              [--net-trace-depth K]            with --net-baked, --traced-bake or --bake-in: a hybrid frame (ct_baked_render_hybrid_*) -- the path
+//                               tracer's own path through its first K collisions (1 .. 64), their NEE terms added, and the table read at
+//                               collision K; K >= 2 needs --net-direct; works with --gpus
 //              [--bake-half]                    render from the binary16 copy of the table (ct_bake_half); with --bake-out that copy is saved; not with --gpus
 //              [--adaptive R,MAX[,MIN[,REL[,ABS]]] [--adaptive-counts FILE]]   the image as an adaptive frame (ct_adaptive_frame_*):
 //                               rounds of R subframes that go only to the pixels which still fail the stopping rule (tested from MIN
@@ -109,6 +112,7 @@ namespace
         CtAdaptiveFrameDesc adaptiveDesc{ CT_ABI_VERSION, 0, 100, 0, 2e-2f, 1e-2f, 0, 0 };
         std::string adaptiveCounts;                                               // --adaptive-counts FILE: the per-pixel sample counts
         std::vector<int32_t> adaptiveDevices;                                     // --adaptive-gpus N | a,b,c: the adaptive frame on a CtGroup (ct_group_adaptive_frame_*)
+        uint32_t traceDepth = 0;                                                  // --net-trace-depth K: hybrid frames of depth K from the table (0: ct_baked_render_*)
         bool netDirect = false;                                                   // --net-direct: CT_NET_ADD_SINGLE_SCATTER joins networkRender.transform
         bool collect = false;                                                     // `cloudtrace collect ...`
         int32_t sceneId = 0;
@@ -324,9 +328,9 @@ namespace
             // installFramework + installApp: Sun, VDBCloud, CloudMaterial, Camera in this order (installers.cpp:28-38)
             std::shared_ptr<PathTracingRenderer> renderer = opt.tracedBake ? std::make_shared<TracedBakeRenderer>(context, opt.networkRender, opt.bake,
                     opt.netBakeCompact ? CT_BAKE_COMPACT : opt.netBakeSparse ? CT_BAKE_SPARSE : CT_BAKE_DENSE, opt.bakeSamples,
-                    opt.bakeAdaptive ? &opt.adaptive : nullptr, opt.bakeFiles)
+                    opt.bakeAdaptive ? &opt.adaptive : nullptr, opt.bakeFiles, opt.traceDepth)
                 : !opt.network ? std::make_shared<PathTracingRenderer>(context)
-                : opt.netBaked ? std::make_shared<BakedRenderer>(context, opt.network, opt.networkRender, opt.bake, opt.netBakeSparse, opt.netBakeCompact, opt.bakeFiles)
+                : opt.netBaked ? std::make_shared<BakedRenderer>(context, opt.network, opt.networkRender, opt.bake, opt.netBakeSparse, opt.netBakeCompact, opt.bakeFiles, opt.traceDepth)
                                : std::make_shared<NetworkRenderer>(context, opt.network, opt.networkRender);
             renderer->estimator = opt.estimator;
             auto sun = std::make_shared<Sun>(std::make_shared<DirectionalLight>(scene.light), context);
@@ -353,7 +357,7 @@ int main(int argc, char* argv[])
     try
     {
         Options opt;
-        if (argc < 2) { std::cerr << "usage: cloudtrace <cloud> [--size WxH] [--spp N] [--mode total|multi|single] [--light L] [--size-m M] [--out DIR] [--data DIR] [--unfused] [--display] [--estimator march|delta] [--format exr|pfm] [--gpus N|a,b,c] [--tex-fixed8] [--network FILE [--net-transform linear|expm1] [--net-scale r,g,b] [--net-direct] [--net-baked NX,NY,NZ,NPHI,NC [--net-bake-sparse | --net-bake-compact]]] [--traced-bake NX,NY,NZ,NPHI,NC --bake-samples N [--net-bake-sparse | --net-bake-compact] [--net-direct]] [--adaptive R,MAX[,MIN[,REL[,ABS]]] [--adaptive-counts FILE] [--adaptive-gpus N|a,b,c]] (--network, --net-baked and --traced-bake with --gpus: every GPU renders its own tiles; --bake-half: one GPU)\n"; return 2; }
+        if (argc < 2) { std::cerr << "usage: cloudtrace <cloud> [--size WxH] [--spp N] [--mode total|multi|single] [--light L] [--size-m M] [--out DIR] [--data DIR] [--unfused] [--display] [--estimator march|delta] [--format exr|pfm] [--gpus N|a,b,c] [--tex-fixed8] [--network FILE [--net-transform linear|expm1] [--net-scale r,g,b] [--net-direct] [--net-baked NX,NY,NZ,NPHI,NC [--net-bake-sparse | --net-bake-compact]]] [--traced-bake NX,NY,NZ,NPHI,NC --bake-samples N [--net-bake-sparse | --net-bake-compact] [--net-direct]] [--net-trace-depth K] [--adaptive R,MAX[,MIN[,REL[,ABS]]] [--adaptive-counts FILE] [--adaptive-gpus N|a,b,c]] (--network, --net-baked and --traced-bake with --gpus: every GPU renders its own tiles; --bake-half: one GPU)\n"; return 2; }
         int first = 2;
         bool lightsGiven = false;
         opt.cloud = argv[1];
@@ -406,6 +410,12 @@ int main(int argc, char* argv[])
                 if (std::sscanf(next().c_str(), "%f,%f,%f", &s[0], &s[1], &s[2]) != 3) throw std::invalid_argument("--net-scale r,g,b");
             }
             else if (a == "--net-direct") opt.netDirect = true;
+            else if (a == "--net-trace-depth")
+            {
+                const long k = std::stol(next());
+                if (k < 1 || k > 64) throw std::invalid_argument("--net-trace-depth K, 1 .. 64");
+                opt.traceDepth = (uint32_t)k;
+            }
             else if (a == "--net-baked")
             {
                 CtBakeDesc& b = opt.bake;
@@ -496,6 +506,10 @@ int main(int argc, char* argv[])
         }
         else if ((!opt.bakeFiles.out.empty() || opt.bakeFiles.half) && !opt.tracedBake && !opt.netBaked)
             throw std::invalid_argument("--bake-out and --bake-half work on the table of --net-baked, --traced-bake or --bake-in");
+        if (opt.traceDepth != 0 && !opt.tracedBake && !opt.netBaked)
+            throw std::invalid_argument("--net-trace-depth K traces K collisions before the table of --net-baked, --traced-bake or --bake-in is read");
+        if (opt.traceDepth >= 2 && !opt.netDirect)
+            throw std::invalid_argument("--net-trace-depth K with K >= 2 needs --net-direct: a hybrid frame is the path tracer's total, the first collision's term included");
         if (opt.tracedBake && !opt.networkPath.empty()) throw std::invalid_argument("--traced-bake fills the table with path-traced radiance: it cannot be combined with --network");
         if (opt.tracedBake && opt.netBaked) throw std::invalid_argument("--traced-bake and --net-baked are two ways to fill one table: give one of them");
         if (opt.bakeAdaptive && opt.bakeSamples != 0) throw std::invalid_argument("--bake-adaptive and --bake-samples are two ways to trace one table: give one of them");

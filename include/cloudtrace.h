@@ -1241,6 +1241,48 @@ CT_API int ct_baked_render_shard_accumulate(CtHandle h, CtBake b, const CtNetwor
 /* Diagnostic: GPU milliseconds of the last ct_baked_render_* of this handle, one event pair around the call's kernels. */
 CT_API int ct_debug_baked_render_time(CtHandle h, double *gpu_ms_out);
 
+/* ---- hybrid frames: trace `depth` collisions, then read the bake -----------------------------------------
+ *
+ * The table of a traced bake is read at the FIRST collision, at the cloud's lit surface, where the multiply scattered radiance
+ * varies most sharply; a few collisions further in it is smooth.  A hybrid frame of depth k follows the path tracer's own path
+ * through its first k collisions, adding their NEE terms as the path tracer does, and reads the bake at collision k for
+ * everything beyond: a depth knob that costs no memory.  A table entry at (x, d) stands for multipleScatterSunRadiance of a point
+ * task at x with view direction d, which redirects first and then scatters with the chopped phase -- in distribution what a
+ * mode-0 path still has to collect after a collision at x that it reached travelling along d.
+ *
+ * Defined on a handle h and a bake b with CtNetworkRender p, for subframe s and pixel (x, y); 1 <= k <= 64 and k < the scene's
+ * max_depth.
+ *   The path is the one ct_render_subframe draws for that pixel and subframe in CT_MODE_SUN_AND_SKY_ALL_SCATTER: seed
+ *     tea<4>(x * 4096 + y, s); per bounce one draw for the flight, then getNewDirection's draws.  The flight is the march flight,
+ *     whatever the handle's estimator and mode, as for ct_baked_render_*; CT_FLAG_TEX_FIXED8 applies as everywhere.
+ *   If the primary ray misses the box, or its first flight has no collision inside the box, the pixel is (0, 0, 0, 1), as
+ *     ct_baked_render_* gives.
+ *   Otherwise S = (0, 0, 0) and for i = 1 .. k: S += the NEE at collision i (un-chopped Mie at i = 1, chopped after); if i < k
+ *     the new direction is drawn and the next flight made, and if that has no collision inside the box the path has ENDED: the
+ *     pixel is (S, 1).
+ *   A path that reaches collision k is ALIVE at x_k, having travelled there along w_{k-1} (for k = 1 the normalised primary
+ *     direction); no direction is drawn at x_k.  Its pixel is rgb_scale * g + S, alpha 1, each product rounded before its sum,
+ *     where g is the transform of p (as in ct_network_render_*) applied to the lookup of b at (x_k - half box, w_{k-1}).
+ *   CT_NET_ADD_SINGLE_SCATTER must be set in p for k >= 2: the frame is the path tracer's total, and without the first NEE it is
+ *     no picture this library defines.  For k = 1 both settings are legal and mean what they mean for ct_baked_render_*.
+ * Consequences, bit for bit: depth 1 is ct_baked_render_* with the same arguments; with a table that is 0 everywhere and a finite
+ * rgb_scale the frame is ct_render_subframe's on a MARCH mode-0 handle of the same scene with max_depth = k + 1, and the number
+ * of alive pixels is that handle's depth_capped; _accumulate is the loop of _subframe + ct_accumulate whatever the band size; a
+ * shard writes its own tiles only and the shards sum to the frame; ct_group_baked_render_hybrid_accumulate + ct_group_merge give
+ * one handle's mean and M2.
+ * Every check, CT_E_STATE rule (the bake's light, a frozen image) and side effect is ct_baked_render_*'s, the counters and
+ * ct_debug_baked_render_time included, and every kind of bake is taken.  The handle keeps one more temporary, 16 bytes per band
+ * pixel, from the first hybrid call on.  CT_E_INVAL, each naming the value: depth 0, depth above 64, depth >= max_depth, depth
+ * >= 2 without the flag.  A NULL handle is answered without a device. */
+CT_API int ct_baked_render_hybrid_subframe(CtHandle h, CtBake b, const CtNetworkRender *p, uint32_t depth, uint32_t subframe_id,
+                                           float *frame_rgba_dev);
+CT_API int ct_baked_render_hybrid_accumulate(CtHandle h, CtBake b, const CtNetworkRender *p, uint32_t depth, uint32_t first_subframe_id,
+                                             uint32_t count);
+CT_API int ct_baked_render_hybrid_shard_subframe(CtHandle h, CtBake b, const CtNetworkRender *p, uint32_t depth, uint32_t subframe_id,
+                                                 float *frame_rgba_dev);
+CT_API int ct_baked_render_hybrid_shard_accumulate(CtHandle h, CtBake b, const CtNetworkRender *p, uint32_t depth,
+                                                   uint32_t first_subframe_id, uint32_t count);
+
 /* ---- data access -------------------------------------------------------------------- */
 
 /* BufferBind<T>(buffer) map/copy, src/Util/BufferBind.h:11-74 (e.g. Camera.cpp:161,239-240).
@@ -1551,6 +1593,9 @@ CT_API int ct_group_bake_retrace_adaptive(CtGroupBake gb);
 CT_API int ct_group_bake_shard(CtGroupBake gb, uint32_t index, CtBake *out);   /* owned by gb */
 CT_API int ct_group_bake_spans(CtGroupBake gb, uint64_t *lo_hi_out, size_t count);
 CT_API int ct_group_baked_render_accumulate(CtGroup g, CtGroupBake gb, const CtNetworkRender *p, uint32_t first_subframe_id, uint32_t count);
+/* ct_baked_render_hybrid_shard_accumulate on every shard ("hybrid frames"), otherwise as ct_group_baked_render_accumulate. */
+CT_API int ct_group_baked_render_hybrid_accumulate(CtGroup g, CtGroupBake gb, const CtNetworkRender *p, uint32_t depth,
+                                                   uint32_t first_subframe_id, uint32_t count);
 CT_API int ct_group_bake_destroy(CtGroupBake gb);   /* NULL is a no-op; destroy before the group */
 /* Diagnostic: what shard `shard` of `shards` builds of ct_bake_traced (p == NULL) or ct_bake_traced_adaptive, alone on h: only
  * its span of the table is traced, the rest is zero.  For timing one shard's work without the others (tools/traced_bake_time.py). */
